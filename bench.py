@@ -13,6 +13,13 @@ RCCL's stream, so it overlaps the next step's pass; all of them complete inside 
 At --gpus N>1 (launched by torch.distributed.run, one rank per GPU, RCCL) the SAME total work
 is sharded over the ranks (strong scaling); `value` is whole-job words/s.
 
+A plain run sets up, warms up, times --steps steps and prints the result line. --full adds
+everything else, each after the timed steps unless noted: the dominant kernel bracketed by HIP
+events inside the timed steps, the roofline, untimed single passes, the column-identity check, the
+FP4-shadow-resident figure, the CPU oracle baseline and (N > 1) the per-rank diagnostics.
+--dump-outputs DIR writes what the last timed step returned to its caller (the all-pairs total)
+as DIR/total.npy.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -77,6 +84,17 @@ def free_port():
         return sock.getsockname()[1]
 
 
+def dump_outputs(path, total):
+    """--dump-outputs: what the timed path hands its caller, the uint64 all-pairs total of the last
+    timed step, as float64 (exact below 2^53; every configuration the README lists stays below)."""
+    import numpy as np
+    value = np.array([total], dtype=np.float64)
+    if int(value[0]) != total:
+        raise SystemExit(f"--dump-outputs: total {total} is not exact in float64")
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "total.npy"), value)
+
+
 def launch_ranks(args, real_stdout):
     """`python3 bench.py --gpus N` without RANK in the environment: run
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same arguments>`
@@ -94,6 +112,8 @@ def launch_ranks(args, real_stdout):
     env.setdefault("OMP_NUM_THREADS", "1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+    if args.dump_outputs:   # the ranks run in ROOT: pass the caller's directory as an absolute path (last one wins)
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     print("bench.py: starting", args.gpus, "ranks:", " ".join(cmd), file=sys.stderr)
     child = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=None, env=env, cwd=ROOT)
     out, _ = child.communicate()
@@ -124,8 +144,12 @@ def main():
     ap.add_argument("--variant", type=int, default=-1)
     ap.add_argument("--prewarm-ms", type=float, default=150.0,
                     help="untimed passes for this long before the warmup steps (clock ramp)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-shadow-resident", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the diagnostics, checks and secondary figures (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result (the all-pairs total) as DIR/total.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle baseline")
+    ap.add_argument("--no-shadow-resident", action="store_true", help="--full without the shadow-resident figure")
     ap.add_argument("--opt", action="append", default=[], help="ctx option key=value (tuning)")
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL, default) | gloo (rehearsal)")
     ap.add_argument("--all-on-device0", action="store_true",
@@ -133,6 +157,8 @@ def main():
     ap.add_argument("--master-port", type=int, default=0,
                     help="rendezvous port when bench.py starts its own ranks (0 = a free one)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # Called bare (`python3 bench.py --gpus N`), not under a launcher: start the N ranks as CHILD
@@ -257,25 +283,30 @@ def main():
     for _ in range(args.warmup):
         step()
     fence()
-    # dominant kernel alone: the library brackets it with HIP events on the launch stream
-    ctx.set_option("time_kernels", 1)
-    # The timed region carries exactly the contract's instrumentation: the library's two HIP events
-    # around the dominant kernel on the launch stream (roofline.achieved). An event record costs the
-    # stream ~4 us (measured: 8.7 us per step for a second pair around the whole pass), so the
-    # per-pass durations are taken in a separate, untimed loop below.
-    # At N > 1 a rank's pass is 1/N as long and the two event records (~8 us) are not: there the kernel is
-    # bracketed on every 4th step only (still live, still inside the timed region; `kernel_ms_samples`).
-    sample_every = 1 if world == 1 else 4
-    t0 = time.perf_counter()
     host_us = []
-    for i in range(args.steps):
-        th = time.perf_counter()
-        if sample_every > 1 and i % sample_every < 2:
-            ctx.set_option("time_kernels", 0 if i % sample_every else (2 if i else 1))  # 2: resume the series
-        k = launch_pass()
-        reduce_total(k)
-        state["n"] += 1
-        host_us.append((time.perf_counter() - th) * 1e6)
+    if args.full:
+        # dominant kernel alone: the library brackets it with HIP events on the launch stream
+        ctx.set_option("time_kernels", 1)
+        # The timed region carries exactly the contract's instrumentation: the library's two HIP events
+        # around the dominant kernel on the launch stream (roofline.achieved). An event record costs the
+        # stream ~4 us (measured: 8.7 us per step for a second pair around the whole pass), so the
+        # per-pass durations are taken in a separate, untimed loop below.
+        # At N > 1 a rank's pass is 1/N as long and the two event records (~8 us) are not: there the kernel is
+        # bracketed on every 4th step only (still live, still inside the timed region; `kernel_ms_samples`).
+        sample_every = 1 if world == 1 else 4
+        t0 = time.perf_counter()
+        for i in range(args.steps):
+            th = time.perf_counter()
+            if sample_every > 1 and i % sample_every < 2:
+                ctx.set_option("time_kernels", 0 if i % sample_every else (2 if i else 1))  # 2: resume the series
+            k = launch_pass()
+            reduce_total(k)
+            state["n"] += 1
+            host_us.append((time.perf_counter() - th) * 1e6)
+    else:
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
     fence()
     elapsed = time.perf_counter() - t0
     my_elapsed = elapsed
@@ -284,27 +315,31 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     total = last_total()
-    dom_sum_ms, dom_n = ctx.kernel_time()
-    ctx.set_option("time_kernels", 0)
-    # untimed diagnostic: expand + dominant kernel + fold of single passes, bracketed by stream events
-    # (same collective count on every rank: min(steps, 24) more steps)
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-          for _ in range(min(args.steps, 24))]
-    for a, b in ev:
-        a.record(stream)
-        k = launch_pass()
-        b.record(stream)
-        reduce_total(k)
-        state["n"] += 1
-    fence()
-    per_step_pass_ms = [a.elapsed_time(b) for a, b in ev]
-    launch_ms = sum(per_step_pass_ms) / len(ev)
-    kernel_ms = dom_sum_ms / dom_n if dom_n else launch_ms
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, total)
+
+    if args.full:
+        dom_sum_ms, dom_n = ctx.kernel_time()
+        ctx.set_option("time_kernels", 0)
+        # untimed diagnostic: expand + dominant kernel + fold of single passes, bracketed by stream events
+        # (same collective count on every rank: min(steps, 24) more steps)
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+              for _ in range(min(args.steps, 24))]
+        for a, b in ev:
+            a.record(stream)
+            k = launch_pass()
+            b.record(stream)
+            reduce_total(k)
+            state["n"] += 1
+        fence()
+        per_step_pass_ms = [a.elapsed_time(b) for a, b in ev]
+        launch_ms = sum(per_step_pass_ms) / len(ev)
+        kernel_ms = dom_sum_ms / dom_n if dom_n else launch_ms
 
     # N > 1 diagnostics (outside the timed region): the 8-byte all-reduce alone, and every rank's
     # own kernel / pass / wall time, so that a scaling run can be read rank by rank
     per_rank = None
-    if collective:
+    if collective and args.full:
         n_ar = 20
         scratch = torch.zeros(1, dtype=torch.int64, device=dev if args.backend != "gloo" else "cpu")
         dist.all_reduce(scratch); fence()
@@ -346,7 +381,7 @@ def main():
     # do) — i.e. without the O(N*M) expansion at the head of every pass.
     shadow_resident = None
     operands_used = ctx.get_option("k2_operands_used")
-    if not args.no_shadow_resident and ctx.get_option("variant_used") >= 4 and operands_used == 4:
+    if args.full and not args.no_shadow_resident and ctx.get_option("variant_used") >= 4 and operands_used == 4:
         ctx.set_option("keep_shadow", 1)
         step(); fence()
         n2 = max(1, args.steps // 2)
@@ -368,69 +403,14 @@ def main():
     words = pairs * 2 * W
     value = words * args.steps / elapsed
 
-    # correctness of what was timed: size-independent identity sum_c C(n_c, 2), on the device
-    identity = mat.column_identity()
-    ok = (total == identity)
+    ok = True
+    if args.full:
+        # correctness of what was timed: size-independent identity sum_c C(n_c, 2), on the device
+        identity = mat.column_identity()
+        ok = (total == identity)
 
     if rank == 0:
         used = ctx.get_option("variant_used")
-        alg_bytes_launch = pairs * W * 16 / world                # 16 B / word pair
-        alg_flop_launch = pairs * W * 64 * 2 / world             # 64 bit-MACs per word pair
-        hbm_gbs = alg_bytes_launch / (kernel_ms * 1e-3) / 1e9
-        # HBM-side bytes of the dominant kernel per launch: measured with rocprofv3 PMC passes
-        # (tools/profile_default.sh -> tools/pmc_traffic.py) and only quoted while the device
-        # sources are the ones it was measured on
-        traffic, traffic_note = None, "no PMC summary for this kernel variant under profiles/"
-        pmc = os.path.join(ROOT, "profiles", "pmc_hbm_bytes_per_launch.json")
-        if os.path.exists(pmc):
-            try:
-                from stormbitmaps_amd._lib import kernel_source_hash
-                entry = json.load(open(pmc)).get(f"variant{used}", {})
-                if entry.get("source_hash") == kernel_source_hash():
-                    traffic = entry.get("hbm_bytes_per_launch")
-                    traffic_note = (f"rocprofv3 FETCH_SIZE x 2 + WRITE_SIZE of {entry.get('dominant_kernel')} "
-                                    f"at 1 GPU, sources {entry.get('source_hash')}")
-                elif entry:
-                    traffic_note = ("stale: the PMC summary was measured on other device sources "
-                                    f"({entry.get('source_hash')}); re-run tools/profile_default.sh")
-            except Exception as e:  # noqa: BLE001
-                traffic_note = f"unreadable PMC summary: {e}"
-        step_ms = elapsed * 1e3 / args.steps
-        if used >= 3:
-            # K2/K2s: the bits are multiplied as FP4 on the matrix cores -> MFMA-bound
-            achieved = alg_flop_launch / (kernel_ms * 1e-3) / 1e12
-            roof = {"bound": "mfma", "achieved": achieved, "peak": FP4_PEAK_TFLOPS, "unit": "TFLOP/s",
-                    "frac": achieved / FP4_PEAK_TFLOPS, "traffic": traffic if world == 1 else None,
-                    "traffic_note": traffic_note,
-                    # the same FLOPs over everything one step contains (fold, launch gaps, all-reduce;
-                    # the FP4-shadow form: its expansion pass too): wall time of the timed loop / steps
-                    "frac_whole_pass": alg_flop_launch / (step_ms * 1e-3) / 1e12 / FP4_PEAK_TFLOPS,
-                    "kernel": ({5: "storm::strip16_bits_kernel", 2: "storm::bitstream_kernel<false>",
-                                1: "storm::stripbits_kernel"}.get(operands_used,
-                                "storm::strip16_fp4_kernel<4>" if ctx.get_option("k2_shape") == 16 else
-                                "storm::strip_fp4_kernel")) if used >= 4 else "storm::pairw_fp4_kernel",
-                    "operand_form": ({5: "bit rows read as they are; the FP4 image of every 64-row B stage is built in "
-                                         "the LDS by the workgroup (no shadow matrix, no expansion pass)",
-                                      2: "bit rows inflated in registers, one stage stream per workgroup",
-                                      4: "FP4 shadow matrix rebuilt by expand_fp4_kernel in front of every pass"}
-                                     .get(operands_used, str(operands_used))) if used >= 4 else "FP4 shadow",
-                    "kernel_ms": kernel_ms, "kernel_ms_samples": dom_n, "pass_ms_untimed": launch_ms,
-                    "algorithmic_flop_per_launch": alg_flop_launch,
-                    "measured_fp4_mfma_peak_frac": (pairs * W / world / (kernel_ms * 1e-3)) / FP4_MEASURED_WORDPAIRS,
-                    "hbm_algorithmic_gb_s": hbm_gbs, "hbm_algorithmic_frac": hbm_gbs / HBM_PEAK_GBS,
-                    "note": "1 word pair = 64 bit-MACs = 128 FLOP on v_mfma_f32_16x16x128_f8f6f4 (FP4 operands). The "
-                            "reference's no-reuse byte accounting (16 B per word pair, benchmark.cpp:131) is "
-                            "kept as hbm_algorithmic_*; on-chip reuse puts it far above the HBM peak."}
-        else:
-            roof = {"bound": "hbm", "achieved": hbm_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": hbm_gbs / HBM_PEAK_GBS, "traffic": traffic, "traffic_note": traffic_note,
-                    "kernel": f"storm::pairw_dense_kernel<{used}>", "kernel_ms": kernel_ms,
-                    "pass_ms_untimed": launch_ms,
-                    "algorithmic_bytes_per_launch": alg_bytes_launch,
-                    "valu_popcount_frac": (info["word_pairs_executed"] / (kernel_ms * 1e-3)) / VALU_PEAK_WORDPAIRS,
-                    "note": "algorithmic bytes use the reference's no-reuse accounting (16 B per word pair, "
-                            "benchmark.cpp:131); on-chip reuse lets it exceed the HBM peak — the binding "
-                            "resource is VALU popcount issue (valu_popcount_frac)"}
         out = {
             "metric": f"64-bit bitmap words/s, XX^T upper-tri pairwise AND+popcount ({N}x{M})",
             "value": value, "unit": "words/s", "n_gpus": world, "steps": args.steps,
@@ -447,36 +427,95 @@ def main():
                                       "pair space), X replicated, one uint64 all-reduce per step",
                        "kernel_variant": used, "work_items": info["items"]},
             "gb_per_s_algorithmic": value * 8 / 1e9,
-            "total": total, "verified_against_column_identity": ok,
-            "roofline": roof,
+            "total": total,
         }
-        out["pass_ms_untimed_passes"] = [round(x, 4) for x in per_step_pass_ms[:24]]  # rank 0, after the timed steps
-        out["host_enqueue_us_first_steps"] = [round(x, 1) for x in host_us[:24]]
-        if per_rank is not None:
-            out["per_rank"] = per_rank
-            out["rccl_ranks"] = dist.get_world_size()     # ranks the process group (backend below) holds
-            out["collective_backend"] = dist.get_backend()
-            out["distinct_gpus"] = len({r["pci_bus_id"] for r in per_rank})
-            out["slowest_rank_kernel_ms"] = max(r["kernel_ms"] for r in per_rank)
-        if shadow_resident is not None:
-            shadow_resident["value"] = words / (shadow_resident["ms_per_step"] * 1e-3)
-            shadow_resident["note"] = ("same pass with the FP4 shadow of the unchanged matrix kept resident "
-                                       "(option keep_shadow); informational, `value` always re-expands")
-            out["shadow_resident"] = shadow_resident
-        if world == 1 and not args.no_cpu_baseline:
-            base = cpu_baseline(lambda n: mat.download(0, min(n, N)), W)
-            out["cpu_baseline"] = base
-            # the checker's word on what was timed: when the CPU sample was the whole matrix its
-            # pair-by-pair total must be the GPU's (a smaller sample is checked on its own rows)
-            n_cpu = base.pop("sample_rows")
-            want = total if n_cpu == N else mat_head_total(ctx, mat, n_cpu, W)
-            base["sample_total_matches_gpu"] = (base["sample_total"] == want)
-            if not base["sample_total_matches_gpu"]:
-                print(f"VERIFICATION FAILED: CPU oracle total over the first {n_cpu} rows "
-                      f"{base['sample_total']} != GPU {want}", file=sys.stderr)
-                ok = False
+        if args.full:
+            alg_bytes_launch = pairs * W * 16 / world                # 16 B / word pair
+            alg_flop_launch = pairs * W * 64 * 2 / world             # 64 bit-MACs per word pair
+            hbm_gbs = alg_bytes_launch / (kernel_ms * 1e-3) / 1e9
+            # HBM-side bytes of the dominant kernel per launch: measured with rocprofv3 PMC passes
+            # (tools/profile_default.sh -> tools/pmc_traffic.py) and only quoted while the device
+            # sources are the ones it was measured on
+            traffic, traffic_note = None, "no PMC summary for this kernel variant under profiles/"
+            pmc = os.path.join(ROOT, "profiles", "pmc_hbm_bytes_per_launch.json")
+            if os.path.exists(pmc):
+                try:
+                    from stormbitmaps_amd._lib import kernel_source_hash
+                    entry = json.load(open(pmc)).get(f"variant{used}", {})
+                    if entry.get("source_hash") == kernel_source_hash():
+                        traffic = entry.get("hbm_bytes_per_launch")
+                        traffic_note = (f"rocprofv3 FETCH_SIZE x 2 + WRITE_SIZE of {entry.get('dominant_kernel')} "
+                                        f"at 1 GPU, sources {entry.get('source_hash')}")
+                    elif entry:
+                        traffic_note = ("stale: the PMC summary was measured on other device sources "
+                                        f"({entry.get('source_hash')}); re-run tools/profile_default.sh")
+                except Exception as e:  # noqa: BLE001
+                    traffic_note = f"unreadable PMC summary: {e}"
+            step_ms = elapsed * 1e3 / args.steps
+            if used >= 3:
+                # K2/K2s: the bits are multiplied as FP4 on the matrix cores -> MFMA-bound
+                achieved = alg_flop_launch / (kernel_ms * 1e-3) / 1e12
+                roof = {"bound": "mfma", "achieved": achieved, "peak": FP4_PEAK_TFLOPS, "unit": "TFLOP/s",
+                        "frac": achieved / FP4_PEAK_TFLOPS, "traffic": traffic if world == 1 else None,
+                        "traffic_note": traffic_note,
+                        # the same FLOPs over everything one step contains (fold, launch gaps, all-reduce;
+                        # the FP4-shadow form: its expansion pass too): wall time of the timed loop / steps
+                        "frac_whole_pass": alg_flop_launch / (step_ms * 1e-3) / 1e12 / FP4_PEAK_TFLOPS,
+                        "kernel": ({5: "storm::strip16_bits_kernel", 2: "storm::bitstream_kernel<false>",
+                                    1: "storm::stripbits_kernel"}.get(operands_used,
+                                    "storm::strip16_fp4_kernel<4>" if ctx.get_option("k2_shape") == 16 else
+                                    "storm::strip_fp4_kernel")) if used >= 4 else "storm::pairw_fp4_kernel",
+                        "operand_form": ({5: "bit rows read as they are; the FP4 image of every 64-row B stage is built in "
+                                             "the LDS by the workgroup (no shadow matrix, no expansion pass)",
+                                          2: "bit rows inflated in registers, one stage stream per workgroup",
+                                          4: "FP4 shadow matrix rebuilt by expand_fp4_kernel in front of every pass"}
+                                         .get(operands_used, str(operands_used))) if used >= 4 else "FP4 shadow",
+                        "kernel_ms": kernel_ms, "kernel_ms_samples": dom_n, "pass_ms_untimed": launch_ms,
+                        "algorithmic_flop_per_launch": alg_flop_launch,
+                        "measured_fp4_mfma_peak_frac": (pairs * W / world / (kernel_ms * 1e-3)) / FP4_MEASURED_WORDPAIRS,
+                        "hbm_algorithmic_gb_s": hbm_gbs, "hbm_algorithmic_frac": hbm_gbs / HBM_PEAK_GBS,
+                        "note": "1 word pair = 64 bit-MACs = 128 FLOP on v_mfma_f32_16x16x128_f8f6f4 (FP4 operands). The "
+                                "reference's no-reuse byte accounting (16 B per word pair, benchmark.cpp:131) is "
+                                "kept as hbm_algorithmic_*; on-chip reuse puts it far above the HBM peak."}
+            else:
+                roof = {"bound": "hbm", "achieved": hbm_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": hbm_gbs / HBM_PEAK_GBS, "traffic": traffic, "traffic_note": traffic_note,
+                        "kernel": f"storm::pairw_dense_kernel<{used}>", "kernel_ms": kernel_ms,
+                        "pass_ms_untimed": launch_ms,
+                        "algorithmic_bytes_per_launch": alg_bytes_launch,
+                        "valu_popcount_frac": (info["word_pairs_executed"] / (kernel_ms * 1e-3)) / VALU_PEAK_WORDPAIRS,
+                        "note": "algorithmic bytes use the reference's no-reuse accounting (16 B per word pair, "
+                                "benchmark.cpp:131); on-chip reuse lets it exceed the HBM peak — the binding "
+                                "resource is VALU popcount issue (valu_popcount_frac)"}
+            out["verified_against_column_identity"] = ok
+            out["roofline"] = roof
+            out["pass_ms_untimed_passes"] = [round(x, 4) for x in per_step_pass_ms[:24]]  # rank 0, after the timed steps
+            out["host_enqueue_us_first_steps"] = [round(x, 1) for x in host_us[:24]]
+            if per_rank is not None:
+                out["per_rank"] = per_rank
+                out["rccl_ranks"] = dist.get_world_size()     # ranks the process group (backend below) holds
+                out["collective_backend"] = dist.get_backend()
+                out["distinct_gpus"] = len({r["pci_bus_id"] for r in per_rank})
+                out["slowest_rank_kernel_ms"] = max(r["kernel_ms"] for r in per_rank)
+            if shadow_resident is not None:
+                shadow_resident["value"] = words / (shadow_resident["ms_per_step"] * 1e-3)
+                shadow_resident["note"] = ("same pass with the FP4 shadow of the unchanged matrix kept resident "
+                                           "(option keep_shadow); informational, `value` always re-expands")
+                out["shadow_resident"] = shadow_resident
+            if world == 1 and not args.no_cpu_baseline:
+                base = cpu_baseline(lambda n: mat.download(0, min(n, N)), W)
+                out["cpu_baseline"] = base
+                # the checker's word on what was timed: when the CPU sample was the whole matrix its
+                # pair-by-pair total must be the GPU's (a smaller sample is checked on its own rows)
+                n_cpu = base.pop("sample_rows")
+                want = total if n_cpu == N else mat_head_total(ctx, mat, n_cpu, W)
+                base["sample_total_matches_gpu"] = (base["sample_total"] == want)
+                if not base["sample_total_matches_gpu"]:
+                    print(f"VERIFICATION FAILED: CPU oracle total over the first {n_cpu} rows "
+                          f"{base['sample_total']} != GPU {want}", file=sys.stderr)
+                    ok = False
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
-        if not ok:
+        if args.full and total != identity:
             print(f"VERIFICATION FAILED: total {total} != column identity {identity}", file=sys.stderr)
     if collective:
         dist.barrier()

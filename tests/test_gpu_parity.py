@@ -454,7 +454,7 @@ def test_multi_rank_rehearsal_of_bench_on_one_gpu(ranks):
     # torch.distributed.run on a free port) and relays the job's one JSON line
     cmd = [sys.executable, os.path.join(root, "bench.py"),
            "--gpus", str(ranks), "--backend", "gloo", "--all-on-device0", "--steps", "5", "--warmup", "1",
-           "--rows", "3000", "--no-cpu-baseline"]
+           "--rows", "3000", "--no-cpu-baseline", "--full"]
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=root, env=env)
@@ -477,6 +477,38 @@ def test_multi_rank_rehearsal_of_bench_on_one_gpu(ranks):
     assert out["roofline"]["kernel_ms_samples"] == 2
 
 
+def test_plain_bench_prints_the_headline_and_dumps_the_timed_total(tmp_path):
+    """A plain `bench.py` run (no --full) prints the headline line only, and --dump-outputs writes what the
+    last timed step returned: the all-pairs total, which must be the column identity of the same seeded matrix."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    N, M = 3000, 65536
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--rows", str(N), "--bits", str(M), "--dump-outputs", str(tmp_path / "out")],
+                         capture_output=True, text=True, timeout=240, cwd=root, env=env)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [l for l in res.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, res.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["n_gpus"] == 1
+    assert out["unit"] == "words/s" and out["higher_is_better"] is True and out["ms_per_step"] > 0
+    assert out["value"] == pytest.approx(N * (N - 1) // 2 * 2 * (M // 64) * 1e3 / out["ms_per_step"], rel=1e-9)
+    assert not {"roofline", "cpu_baseline", "shadow_resident", "per_rank", "verified_against_column_identity"} & set(out)
+    dumped = np.load(tmp_path / "out" / "total.npy")
+    assert dumped.dtype == np.float64 and dumped.shape == (1,) and int(dumped[0]) == out["total"]
+    ctx = sb.HipContext(0)
+    try:
+        m = ctx.matrix(N, M // 64)
+        m.fill_synthetic(M, M // 2, seed=42)
+        assert out["total"] == m.column_identity()
+        m.close()
+    finally:
+        ctx.close()
+
+
 def test_bench_over_rccl_when_the_box_has_two_gpus():
     """The first multi-GPU box must carry a rank > 0 over RCCL inside the suite, not only in the
     driver's scaling run: `python bench.py --gpus 2` (bare; bench.py starts the ranks), backend
@@ -491,7 +523,7 @@ def test_bench_over_rccl_when_the_box_has_two_gpus():
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "10",
-                          "--warmup", "2"], capture_output=True, text=True, timeout=600, cwd=root, env=env)
+                          "--warmup", "2", "--full"], capture_output=True, text=True, timeout=600, cwd=root, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, res.stdout

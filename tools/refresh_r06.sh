@@ -8,7 +8,7 @@ R=$PWD
 O=$R/gpurun_out/refresh_r06
 mkdir -p $O
 if [ "${1:-1}" = "1" ]; then
-python3 bench.py > $O/bench_unprofiled.json 2> $O/bench_unprofiled.err
+python3 bench.py --full > $O/bench_unprofiled.json 2> $O/bench_unprofiled.err
 tail -c 600 $O/bench_unprofiled.json; echo
 bash tools/profile_default.sh r06 > $O/profile.log 2>&1 || tail -5 $O/profile.log
 echo "profile done"
