@@ -15,7 +15,7 @@
  *   - Results follow the intended semantics (the mathematically exact count). The reference
  *     deviates from it in three sparse regimes (SURVEY.md §8 a-note, defects D1-D3).
  *   - *_free() also releases the handle itself and every device buffer.
- *   - Both container structs carry private members after the reference's public ones.
+ *   - The container structs and the block struct carry private members after the reference's public ones.
  *
  * Every declaration cites the reference lines it stands in for (storm.h / storm.c).
  */
@@ -114,6 +114,9 @@ struct STORM_bitmap_s {
     uint32_t n_scalar : 31, n_scalar_set : 1, n_missing;
     uint32_t m_scalar;
     uint32_t id;
+    /* private (in the tail padding: the struct stays 128 bytes): the mutation epoch of the block's last change through
+     * the public block / row functions (storm_host.c). The device copies of a STORM_t are matched to it. */
+    uint64_t hip_stamp;
 };
 
 /* one row: its blocks in ascending id order (reference storm.h:168-173) */
@@ -276,8 +279,10 @@ int STORM_contig_pairw_matrix_device(STORM_contiguous_t* bitmap, int op, uint32_
 int STORM_hip_set_devices(int n_devices, const int* device_ids);
 /* The containers keep a device copy of their rows between all-pairs calls. It follows every
  * change made through STORM_add / STORM_clear / STORM_contig_add / STORM_contig_clear, and for
- * STORM_t also edits made with the public per-row / per-block adders directly on h->conts[i]
- * (a fingerprint of rows, blocks and set-bit counts is compared on every call). What it cannot
+ * STORM_t also edits made with the public per-row / per-block adders and clears directly on
+ * h->conts[i] (a fingerprint of rows, blocks, set-bit counts and each block's stamp — the epoch of its
+ * last change through those functions — is compared on every call: a clear and an add that give back
+ * the same ids and counts are seen too). What it cannot
  * see is a caller writing into the public buffers in place (h->data, bitmaps[i].data: the
  * reference structs are not opaque): after such an edit call the matching function below, or the
  * next all-pairs call answers for the rows as they were. Returns 0, -1 for a NULL handle. */

@@ -1409,16 +1409,23 @@ uint64_t STORM_contig_pairw_intersect_cardinality_blocked_list(STORM_contiguous_
 /* Every public function that changes a STORM_t, a row or a block (they are public, storm.h:203-222, and a block
  * does not know the container it belongs to) bumps this process-wide epoch. A handle remembers the epoch its
  * device arena was last verified at: while no mutator has run since, an all-pairs call skips the O(blocks)
- * fingerprint walk. Members edited in place, without any of these functions: STORM_hip_invalidate (storm.h).
+ * fingerprint walk. Every block mutator also writes the new epoch into the block (hip_stamp): a block cleared and
+ * filled again with other positions — same id, same count, so the same header — carries a new stamp, and the
+ * fingerprint and the stage's record of it (stage_blk_t) see the change without reading the block's contents.
+ * Members edited in place, without any of these functions: STORM_hip_invalidate (storm.h).
  * STORM_HIP_ALWAYS_FINGERPRINT=1 walks the fingerprint on every call, as rounds 2 - 3 did. */
 static uint64_t g_mutation_epoch = 1;
-static inline void storm_mutated(void) { __atomic_add_fetch(&g_mutation_epoch, 1, __ATOMIC_RELAXED); }
+static inline uint64_t storm_mutated(void) { return __atomic_add_fetch(&g_mutation_epoch, 1, __ATOMIC_RELAXED); }
 static inline uint64_t storm_epoch(void) { return __atomic_load_n(&g_mutation_epoch, __ATOMIC_RELAXED); }
+static inline void block_mutated(STORM_bitmap_t* b) {
+    const uint64_t e = storm_mutated();
+    if (b) b->hip_stamp = e;
+}
 
 void STORM_bitmap_init(STORM_bitmap_t* b) {
-    storm_mutated();
+    if (b) memset(b, 0, sizeof(*b));
+    block_mutated(b);
     if (!b) return;
-    memset(b, 0, sizeof(*b));
     b->own_data = 1;
     b->own_scalar = 1;
 }
@@ -1468,7 +1475,7 @@ static int bitmap_ensure_list(STORM_bitmap_t* b, uint32_t extra) {
 
 /* bitmap kind: reference storm.c:442-465 (-1 / -2 / -3 for NULL handle / NULL values / empty) */
 int STORM_bitmap_add(STORM_bitmap_t* b, const uint32_t* values, const uint32_t n_values) {
-    storm_mutated();
+    block_mutated(b);
     if (!b) return -1;
     if (!values) return -2;
     if (n_values == 0) return -3;
@@ -1486,7 +1493,7 @@ int STORM_bitmap_add(STORM_bitmap_t* b, const uint32_t* values, const uint32_t n
 /* both representations: reference storm.c:468-518 (-1 / -3 / -4) */
 int STORM_bitmap_add_with_scalar(STORM_bitmap_t* b, const uint32_t* values,
                                  const uint32_t n_values) {
-    storm_mutated();
+    block_mutated(b);
     if (!b) return -1;
     if (!values) return -3;
     if (n_values == 0) return -4;
@@ -1510,7 +1517,7 @@ int STORM_bitmap_add_with_scalar(STORM_bitmap_t* b, const uint32_t* values,
  * list stays duplicate-free, which the list intersections require */
 int STORM_bitmap_add_scalar_only(STORM_bitmap_t* b, const uint32_t* values,
                                  const uint32_t n_values) {
-    storm_mutated();
+    block_mutated(b);
     if (!b) return -1;
     if (!values) return -3;
     if (n_values == 0) return -4;
@@ -1529,7 +1536,7 @@ int STORM_bitmap_add_scalar_only(STORM_bitmap_t* b, const uint32_t* values,
 }
 
 int STORM_bitmap_clear(STORM_bitmap_t* b) { /* storm.c:561-569: buffers are kept */
-    storm_mutated();
+    block_mutated(b);
     if (!b) return -1;
     if (b->data) memset(b->data, 0, sizeof(uint64_t) * BLOCK_WORDS);
     b->n_scalar = 0;
@@ -1707,10 +1714,11 @@ typedef struct {
  * blocks go the same way (storm_hip_stage_add_list: 2 bytes per position; 420 MB and 14 ms of the first call at 20971
  * draws per row). The first add also creates the context (the
  * process's HIP initialisation: 150 - 250 ms that the first call used to pay). Same switch as the dense container's
- * streaming (STORM_HIP_STREAM_ROWS). What was staged is remembered per block as (row, index, id, set-bit count): a block
- * edited behind STORM_add's back (the public per-row / per-block adders) no longer matches at build time and the arena is
+ * streaming (STORM_HIP_STREAM_ROWS). What was staged is remembered per block as (row, index, id, set-bit count, stamp): a
+ * block edited behind STORM_add's back (the public per-row / per-block adders and clears) carries a new stamp
+ * (block_mutated), so it no longer matches at build time even where its id and count came back the same, and the arena is
  * then built from the host's blocks as before. The stage is given up once the arena exists. */
-typedef struct { uint32_t row, b, id, bits; uint64_t token; } stage_blk_t; /* bits: set bits of a bitmap block, length of a list block */
+typedef struct { uint32_t row, b, id, bits; uint64_t token, stamp; } stage_blk_t; /* bits: set bits of a bitmap block, length of a list block */
 typedef struct {
     storm_hip_stage_t* stage;
     int slot;                 /* the device slot the stage lives on */
@@ -1775,11 +1783,11 @@ static void storm_stage_row_locked(STORM_t* h, uint32_t row) {
         uint64_t token = 0;
         if (is_list) { /* (lists too since round 6: 420 MB and 14 ms of the first call at c4's 20971 draws per row) */
             if (storm_hip_stage_add_list(ctx, sg->stage, blk->scalar, blk->n_scalar, &token) != STORM_HIP_OK) goto give_up;
-            sg->blk[sg->n_blk++] = (stage_blk_t){row, b, blk->id, blk->n_scalar, token};
+            sg->blk[sg->n_blk++] = (stage_blk_t){row, b, blk->id, blk->n_scalar, token, blk->hip_stamp};
         } else {
             if (storm_hip_stage_add(ctx, sg->stage, blk->data, &token) != STORM_HIP_OK || token != sg->n_bitmaps_staged) goto give_up;
             ++sg->n_bitmaps_staged;
-            sg->blk[sg->n_blk++] = (stage_blk_t){row, b, blk->id, blk->n_bits_set, token};
+            sg->blk[sg->n_blk++] = (stage_blk_t){row, b, blk->id, blk->n_bits_set, token, blk->hip_stamp};
         }
     }
     return;
@@ -2028,10 +2036,12 @@ static uint64_t serialized_pairw_locked(const void* buf, uint64_t n_bytes) {
 }
 
 /* Fingerprint of what the device arena was built from: rows, blocks per row, and per block its
- * id, kind and set-bit count. STORM_bitmap_cont_add / STORM_bitmap_add are public (storm.h:203-222)
- * and a caller may use them on h->conts[i] directly, behind STORM_add's back; O(blocks) per call
- * makes such an edit rebuild the arena instead of returning the old total. (In-place edits of a
- * block's words that keep its set-bit count are not seen: call STORM_hip_invalidate.) */
+ * id, kind, set-bit count and stamp (the epoch of its last change, block_mutated). STORM_bitmap_cont_add /
+ * STORM_bitmap_add / the _clear functions are public (storm.h:203-222) and a caller may use them on
+ * h->conts[i] directly, behind STORM_add's back; O(blocks) per call makes such an edit rebuild the arena
+ * instead of returning the old total — a clear and an add that give back the same ids and counts
+ * included, by the stamp. (In-place edits of a block's words or list, without these functions, are not
+ * seen: call STORM_hip_invalidate.) */
 static uint64_t storm_fingerprint_rows(const STORM_t* h, uint32_t r0, uint32_t r1) {
     /* four independent accumulators and one multiply per block on the chain: the first version (FNV, three
      * dependent multiplies per block) cost 0.23 ms per all-pairs call at c4's 80000 blocks — more than the
@@ -2044,8 +2054,11 @@ static uint64_t storm_fingerprint_rows(const STORM_t* h, uint32_t r0, uint32_t r
         acc[i & 3u] = (acc[i & 3u] ^ ((uint64_t)r->n_bitmaps + ((uint64_t)i << 32))) * 1099511628211ull;
         for (uint32_t b = 0; b < r->n_bitmaps; ++b, ++k) {
             const STORM_bitmap_t* blk = &r->bitmaps[b];
+            /* (the stamp through a multiply of its own: XOR-ed into the count, an add of one position one epoch later
+             *  could leave both unchanged) */
             const uint64_t v = (((uint64_t)blk->id << 32) | blk->n_bits_set) * 0xff51afd7ed558ccdull ^
-                               ((((uint64_t)blk->n_bitmap << 32) | blk->n_scalar) + k) * 0xc4ceb9fe1a85ec53ull;
+                               ((((uint64_t)blk->n_bitmap << 32) | blk->n_scalar) + k) * 0xc4ceb9fe1a85ec53ull ^
+                               blk->hip_stamp * 0x9e3779b97f4a7c15ull;
             acc[k & 3u] = (acc[k & 3u] ^ v) * 1099511628211ull;
         }
     }
@@ -2196,7 +2209,7 @@ static int storm_build_device(STORM_t* h, sparse_state_t* st, int dense) {
                     tokens[at] = ~0ull;
                     if (blk->n_bitmap ? !blk->data : (!blk->n_scalar || !blk->scalar)) continue; /* (never staged) */
                     if (k < sg->n_blk && sg->blk[k].row == i && sg->blk[k].b == b && sg->blk[k].id == blk->id &&
-                        sg->blk[k].bits == (blk->n_bitmap ? blk->n_bits_set : blk->n_scalar)) {
+                        sg->blk[k].bits == (blk->n_bitmap ? blk->n_bits_set : blk->n_scalar) && sg->blk[k].stamp == blk->hip_stamp) {
                         tokens[at] = sg->blk[k++].token;
                     } else {
                         ok = 0;
