@@ -227,8 +227,14 @@ uint64_t STORM_serialized_size(const STORM_t* bitmap);
 uint64_t STORM_serialize(const STORM_t* bitmap, void* buf, uint64_t capacity);
 STORM_t* STORM_deserialize(const void* buf, uint64_t n_bytes);
 uint64_t STORM_serialized_pairw_intersect_cardinality(const void* buf, uint64_t n_bytes);
-/* (reference storm.h:231 declares STORM_intersect_cardinality_square but never defines it,
- *  storm.c:975; nothing to stand in for.) */
+/* Reference storm.h:231 declares this and never defines it (storm.c:975). Here: the sum over every row i of bitmap1 and
+ * every row j of bitmap2 of STORM_bitmap_cont_intersect_cardinality(&bitmap1->conts[i], &bitmap2->conts[j]) — the whole
+ * rectangle, both orders, no triangle — computed on the GPU. 0 when either container is empty; (uint64_t)-1 for a NULL
+ * handle or a device failure (STORM_hip_error says why). bitmap1 == bitmap2 is allowed: 2 x the all-pairs total plus each
+ * row's count with itself. `const` is the containers': the device copies kept behind the handles may be (re)built.
+ * One device slot and one process only (STORM_hip_set_devices / _set_thread_devices with several slots, or
+ * STORM_hip_set_shard with more than one shard: refused, on every rank alike). */
+uint64_t STORM_intersect_cardinality_square(const STORM_t* STORM_RESTRICT bitmap1, const STORM_t* STORM_RESTRICT bitmap2);
 
 /* dense container (reference storm.h:235-242, storm.c:1001-1346).
  * STORM_contig_add: returns n_values; 0 for an empty input (no row appended); -1 / -2 for a
@@ -267,6 +273,16 @@ int STORM_pairw_matrix(STORM_t* bitmap, int op, uint32_t* out, uint64_t out_rows
  * the n x n window are written as 0 only inside the tiles the kernel touches: clear the buffer once if they matter. The
  * 4 n^2 bytes then never cross the bus (half of a STORM_pairw_matrix call at n = 10000). Same return codes otherwise. */
 int STORM_pairw_matrix_device(STORM_t* bitmap, int op, uint32_t* d_out, uint64_t out_rows, uint64_t out_ld);
+/* The rectangle of two STORM_t: entry (i, j) = popcount(A_i OP B_j) for EVERY row i of `a` and j of `b` at
+ * out[i * out_ld + j] (op 0 / 1 / 2 as above; STORM_bitmap_cont_intersect_cardinality(&a->conts[i], &b->conts[j]) for
+ * op 0). Every entry of the N_A x N_B window is written. a == b is allowed (the full symmetric matrix, the rows' own
+ * counts on the diagonal). Same return codes as STORM_pairw_matrix, with -4 when out_rows < N_A or out_ld < N_B;
+ * _device: `d_out` in device memory, -5 as for STORM_pairw_matrix_device. Two list-only containers that are sparse
+ * enough (option matrix_lists, as for STORM_pairw_matrix) are joined from their lists; otherwise both go to dense
+ * replicas of one common width (the wider of the two: a handle may keep its widened replica; the 2^25-bit row limit
+ * applies). One device slot and one process, as STORM_intersect_cardinality_square. */
+int STORM_square_matrix(STORM_t* a, STORM_t* b, int op, uint32_t* out, uint64_t out_rows, uint64_t out_ld);
+int STORM_square_matrix_device(STORM_t* a, STORM_t* b, int op, uint32_t* d_out, uint64_t out_rows, uint64_t out_ld);
 int STORM_contig_pairw_matrix_device(STORM_contiguous_t* bitmap, int op, uint32_t* d_out, uint64_t out_rows,
                                      uint64_t out_ld);
 

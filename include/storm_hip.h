@@ -170,6 +170,15 @@ int storm_hip_square_matrix_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_
                                    const storm_hip_matrix_t* b, int op, uint32_t* d_out, uint64_t ld);
 int storm_hip_square_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a,
                             const storm_hip_matrix_t* b, int op, uint32_t* h_out);
+/* The same two on the dense replicas of two STORM_t (storm.h: STORM_intersect_cardinality_square, STORM_square_matrix),
+ * and a last-pass report naming the kernels that ran (the two above leave the report as it was). _matrix_device is
+ * complete on return; _matrix: `h_out` is a HOST buffer, h_out[i * ld + j], ld >= b's rows. */
+int storm_hip_cross_dense_total(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b,
+                                uint64_t* h_total);
+int storm_hip_cross_dense_matrix_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b,
+                                        int op, uint32_t* d_out, uint64_t ld);
+int storm_hip_cross_dense_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b, int op,
+                                 uint32_t* h_out, uint64_t ld);
 
 /* sum_c C(n_c,2) on the device — verification identity only, never the product
  * path: used by tests at sizes where a CPU pairwise oracle is infeasible */
@@ -339,6 +348,7 @@ typedef struct storm_hip_comm_s storm_hip_comm_t;
 #define STORM_HIP_RAN_LIST_PROBE 32u /* probe_lists_kernel (K4), list x list blocks       roof: LDS lookups    */
 #define STORM_HIP_RAN_TILES_OUT 128u  /* tilering_kernel / tilebits8_kernel: per-pair output of a dense matrix (or replica) roof: FP4 matrix cores */
 #define STORM_HIP_RAN_LISTS_MATRIX 64u /* lists_matrix_kernel (K5), per-pair output from the lists: out[2] = its table lookups, out[3] = 64 */
+#define STORM_HIP_RAN_LISTS_SQUARE 256u /* lists_square_kernel (K5x), the rectangle of two list-only containers: out[2] = its table lookups, out[3] = 64 */
 int storm_hip_last_pass_report(storm_hip_ctx_t* ctx, uint64_t out[4]);
 
 int storm_hip_comm_unique_id(uint8_t id[STORM_HIP_COMM_ID_BYTES]);
@@ -411,6 +421,12 @@ int storm_hip_matrix_create_from_blocks(storm_hip_ctx_t* ctx, uint64_t n_rows, u
                                         const uint64_t* row_block_offset, const uint32_t* block_id,
                                         const uint8_t* block_kind, const uint32_t* block_n,
                                         const void* const* block_ptr, storm_hip_matrix_t** out);
+/* ... with rows of at least min_blocks x 65536 bits (the common width of two containers whose rectangle is multiplied;
+ * at most 512 blocks = 2^25 bits). 0: the container's own width, as above. */
+int storm_hip_matrix_create_from_blocks_wide(storm_hip_ctx_t* ctx, uint64_t n_rows, uint64_t n_blocks,
+                                             const uint64_t* row_block_offset, const uint32_t* block_id,
+                                             const uint8_t* block_kind, const uint32_t* block_n,
+                                             const void* const* block_ptr, uint32_t min_blocks, storm_hip_matrix_t** out);
 void storm_hip_sparse_destroy(storm_hip_ctx_t* ctx, storm_hip_sparse_t* s);
 /* [r5] K5 — the per-pair matrix of a LIST-ONLY container straight from its lists (replaces, for every pair at once,
  * STORM_bitmap_cont_intersect_cardinality, storm.c:790-814, with two list blocks meeting in
@@ -445,6 +461,21 @@ int storm_hip_rowlists_pairw_matrix_device(storm_hip_ctx_t* ctx, const storm_hip
 int storm_hip_rowlists_pairw_matrix(storm_hip_ctx_t* ctx, const storm_hip_rowlists_t* l, int op, uint32_t* h_out,
                                     uint64_t ld);
 uint64_t storm_hip_rowlists_n_elems(const storm_hip_rowlists_t* l);
+/* [K5x] The rectangle of TWO list-only containers from their lists: A = la's rows, B = lb's (la == lb allowed), each built
+ * by storm_hip_rowlists_create_blocks*. The window kernel's join with A's groups of 64 rows against B's chunks of 768 rows,
+ * every tile (no triangle); windows beyond either container's universe are skipped. The hash join (K5h) has no cross form:
+ * option matrix_lists_kernel = 2 still runs this one.
+ *   _square_total          : *h_total = sum over i < n_A, j < n_B of |A_i & B_j| (integer fold on the device).
+ *   _square_matrix_device  : out[i * ld + j] = popcount(A_i OP B_j) for EVERY i < n_A, j < n_B (ld >= n_B); device
+ *                            memory, complete on return.
+ *   _square_matrix         : the same into HOST memory, h_out[i * ld + j].
+ * la's device copy caches the tile list of the last B (not its rows). */
+int storm_hip_rowlists_square_total(storm_hip_ctx_t* ctx, storm_hip_rowlists_t* la, const storm_hip_rowlists_t* lb,
+                                    uint64_t* h_total);
+int storm_hip_rowlists_square_matrix_device(storm_hip_ctx_t* ctx, storm_hip_rowlists_t* la, const storm_hip_rowlists_t* lb,
+                                            int op, uint32_t* d_out, uint64_t ld);
+int storm_hip_rowlists_square_matrix(storm_hip_ctx_t* ctx, storm_hip_rowlists_t* la, const storm_hip_rowlists_t* lb, int op,
+                                     uint32_t* h_out, uint64_t ld);
 
 int storm_hip_pairw_sparse(storm_hip_ctx_t* ctx, const storm_hip_sparse_t* s,
                            uint32_t shard_rank, uint32_t shard_count, uint64_t* h_total);

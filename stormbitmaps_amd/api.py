@@ -163,6 +163,30 @@ class Storm:
         if rc != 0:
             raise RuntimeError(f"STORM_pairw_matrix_device -> {rc}: {self._lib.STORM_hip_error().decode()}")
 
+    def intersect_cardinality_square(self, other: "Storm") -> int:
+        """STORM_intersect_cardinality_square (declared by the reference, storm.h:231): the sum over every row i of self
+        and j of other of STORM_bitmap_cont_intersect_cardinality(row_i, row_j)."""
+        return _all_pairs(self._lib.STORM_intersect_cardinality_square(self._h, other._h),
+                          "STORM_intersect_cardinality_square")
+
+    def square_matrix(self, other: "Storm", op: str = "and") -> np.ndarray:
+        """STORM_square_matrix (extension): [self.n_rows, other.n_rows] uint32, every entry (i, j) = popcount(row_i OP
+        other_j)."""
+        na, nb = self.n_rows, other.n_rows
+        out = np.zeros((na, nb), dtype=np.uint32)
+        rc = int(self._lib.STORM_square_matrix(self._h, other._h, {"and": 0, "or": 1, "xor": 2}[op],
+                                               _ptr(out) if out.size else _ptr(np.zeros(1, np.uint32)), na, nb))
+        if rc != 0:
+            raise RuntimeError(f"STORM_square_matrix -> {rc}: {self._lib.STORM_hip_error().decode()}")
+        return out
+
+    def square_matrix_device(self, other: "Storm", d_out: int, out_rows: int, out_ld: int, op: str = "and") -> None:
+        """STORM_square_matrix_device (extension): the same rectangle left in device memory at address d_out."""
+        rc = int(self._lib.STORM_square_matrix_device(self._h, other._h, {"and": 0, "or": 1, "xor": 2}[op],
+                                                      C.c_void_p(d_out), out_rows, out_ld))
+        if rc != 0:
+            raise RuntimeError(f"STORM_square_matrix_device -> {rc}: {self._lib.STORM_hip_error().decode()}")
+
     def serialized_size(self) -> int:
         return int(self._lib.STORM_serialized_size(self._h))  # storm.c:963
 

@@ -1727,6 +1727,64 @@ int storm_hip_square_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a,
     });
 }
 
+// The rectangle of two STORM_t dense replicas (storm_host.c: STORM_intersect_cardinality_square, STORM_square_matrix*):
+// storm_hip_square_dense / storm_hip_square_matrix_device, and a last-pass report that names the kernels that ran
+// (those two leave the report alone, as the raw-buffer STORM_wrapper_square has always had them).
+int storm_hip_cross_dense_total(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b,
+                                uint64_t* h_total) {
+    const int rc = storm_hip_square_dense(ctx, a, b, h_total);
+    if (rc != STORM_HIP_OK) return rc;
+    ctx->pass_report[0] = ctx->variant_used >= 3 ? STORM_HIP_RAN_FP4_STRIPS : STORM_HIP_RAN_POPCOUNT;
+    ctx->pass_report[1] = a->n_rows * b->n_rows * a->n_words;
+    ctx->pass_report[2] = ctx->pass_report[3] = 0;
+    return STORM_HIP_OK;
+}
+
+int storm_hip_cross_dense_matrix_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b,
+                                        int op, uint32_t* d_out, uint64_t ld) {
+    int rc = storm_hip_square_matrix_device(ctx, a, b, op, d_out, ld);
+    if (rc == STORM_HIP_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) {
+        set_error("cross_dense_matrix: HIP failure");
+        rc = STORM_HIP_EHIP;
+    }
+    if (rc != STORM_HIP_OK) return rc;
+    ctx->pass_report[0] = STORM_HIP_RAN_TILES_OUT;
+    ctx->pass_report[1] = a->n_rows * b->n_rows * a->n_words;
+    ctx->pass_report[2] = ctx->pass_report[3] = 0;
+    return STORM_HIP_OK;
+}
+
+// ... into HOST memory with a row pitch: h_out[i * ld + j], i < a rows, j < b rows (the context's band buffer in between)
+int storm_hip_cross_dense_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b, int op,
+                                 uint32_t* h_out, uint64_t ld) {
+    return guarded("storm_hip_cross_dense_matrix", [&]() -> int {
+    if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+    if (!a || !b || !h_out || ld < b->n_rows) {
+        set_error("cross_dense_matrix: NULL argument or ld < rows of B");
+        return STORM_HIP_EINVAL;
+    }
+    const uint64_t na = a->n_rows, nb = b->n_rows;
+    if (na == 0 || nb == 0) return STORM_HIP_OK;
+    STORM_HIP_TRY(hipSetDevice(ctx->device));
+    const size_t need = (size_t)na * nb * sizeof(uint32_t);
+    if (need > ctx->band_capacity) {
+        if (ctx->d_band) STORM_HIP_TRY(hipFree(ctx->d_band));
+        ctx->d_band = nullptr;
+        ctx->band_capacity = 0;
+        if (hipMalloc(reinterpret_cast<void**>(&ctx->d_band), need) != hipSuccess) {
+            set_error("cross_dense_matrix: hipMalloc of %zu bytes for the output failed", need);
+            return STORM_HIP_ENOMEM;
+        }
+        ctx->band_capacity = need;
+    }
+    if (int rc = storm_hip_cross_dense_matrix_device(ctx, a, b, op, ctx->d_band, nb)) return rc;
+    STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(uint32_t), ctx->d_band, nb * sizeof(uint32_t), nb * sizeof(uint32_t), na,
+                                   hipMemcpyDeviceToHost, ctx->stream));
+    STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return STORM_HIP_OK;
+    });
+}
+
 int storm_hip_pairw_matrix_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int op,
                                   uint32_t* d_out, uint64_t ld) {
     return guarded("storm_hip_pairw_matrix_device", [&]() -> int {

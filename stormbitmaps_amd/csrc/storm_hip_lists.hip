@@ -137,10 +137,18 @@ __global__ __launch_bounds__(256) void lists_deal_kernel(uint32_t* __restrict__ 
 
 struct LmWin { uint32_t ab, ae, fb, fe; bool ok; };
 
-__global__ __launch_bounds__(kLmThreads, 1) void lists_matrix_kernel(
-    const uint32_t* __restrict__ elems, const uint32_t* __restrict__ off, uint32_t n_windows,
-    const uint32_t* __restrict__ rowlen, const LmItem* __restrict__ items, uint32_t n_rows, int op,
-    uint32_t* __restrict__ out, uint64_t ld, uint32_t dbg) {
+// The join of one item, shared by the triangle (K5, kJoin = kJoinTriangle: A and far rows from ONE container) and the
+// rectangle of two containers (K5x: A rows from container A, far rows from container B, each with its own element array
+// and offset table; the windows walked are those below min(windows of A, windows of B), the only ones both can list).
+// The triangle kernel passes one container as both sides and compiles to the code it had as a kernel of its own.
+enum : int { kJoinTriangle = 0, kJoinCrossMatrix = 1, kJoinCrossTotal = 2 };
+template <int kJoin>
+__device__ __forceinline__ void lists_join(
+    const uint32_t* __restrict__ elemsA, const uint32_t* __restrict__ offA, uint32_t strideA,
+    const uint32_t* __restrict__ elemsF, const uint32_t* __restrict__ offF, uint32_t strideF, uint32_t n_windows,
+    const uint32_t* __restrict__ rowlenA, const uint32_t* __restrict__ rowlenF, const LmItem* __restrict__ items,
+    uint32_t n_rows, uint32_t n_cols, int op, uint32_t* __restrict__ out, uint64_t ld,
+    unsigned long long* __restrict__ slots, uint32_t dbg) {
     // (one array, the table first: its entries are addressed by the elements' own 16-bit byte offsets)
     __shared__ __attribute__((aligned(16))) uint32_t lds[(kLmTableBytes + kLmCountBytes) / 4u];
     uint32_t* const table = lds;                          // [1 + position][2 words]
@@ -153,10 +161,10 @@ __global__ __launch_bounds__(kLmThreads, 1) void lists_matrix_kernel(
     for (uint32_t w = tid * 4u; w < kLmCountBytes / 4u; w += (uint32_t)kLmThreads * 4u)
         *reinterpret_cast<uint4*>(&cnt[w]) = uint4{0u, 0u, 0u, 0u};
 
-    const uint32_t* offA0 = off + (uint64_t)it.gi * n_windows;
-    const uint32_t* offA1 = offA0 + n_windows;
-    const uint32_t* offF0 = off + (uint64_t)(it.cj * kLmChunkGroups) * n_windows;
-    const uint32_t* offF1 = offF0 + (uint64_t)kLmChunkGroups * n_windows;
+    const uint32_t* offA0 = offA + (uint64_t)it.gi * strideA;
+    const uint32_t* offA1 = offA0 + strideA;
+    const uint32_t* offF0 = offF + (uint64_t)(it.cj * kLmChunkGroups) * strideF;
+    const uint32_t* offF1 = offF0 + (uint64_t)kLmChunkGroups * strideF;
 
     // the windows in which both sides list something, 64 at a time: every wave finds the same ones (uniform control flow)
     uint32_t wb = 0;
@@ -228,11 +236,13 @@ __global__ __launch_bounds__(kLmThreads, 1) void lists_matrix_kernel(
             if (m[q].x | m[q].y) count_bits(v[q], m[q]);
     };
     // elems[b, e) as a buffer: what is read beyond its end is 0 = no element (matrix_lists_debug & 1: an empty buffer)
-    auto range = [&](uint32_t b, uint32_t e) -> __amdgpu_buffer_rsrc_t {
+    auto range_in = [&](const uint32_t* elems, uint32_t b, uint32_t e) -> __amdgpu_buffer_rsrc_t {
         const uint32_t bytes = (dbg & 1u) || e <= b ? 0u : (e - b) * 4u;
         return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(elems) + __builtin_amdgcn_readfirstlane((int)b), 0,
                                                  __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
     };
+    auto rangeA = [&](uint32_t b, uint32_t e) { return range_in(elemsA, b, e); };
+    auto rangeF = [&](uint32_t b, uint32_t e) { return range_in(elemsF, b, e); };
     auto load_el = [&](__amdgpu_buffer_rsrc_t rs, uint32_t idx) -> uint32_t {
         return (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, (int)(idx * 4u), 0, 0);
     };
@@ -243,7 +253,7 @@ __global__ __launch_bounds__(kLmThreads, 1) void lists_matrix_kernel(
             if (count > g * kFarGroup * kT) lookup_batch(&v[g * kFarGroup]);
     };
     auto load_regs = [&](uint32_t (&v)[kFarRegs], uint32_t b, uint32_t e, bool ok) {
-        const __amdgpu_buffer_rsrc_t rs = range(b, ok ? e : b);
+        const __amdgpu_buffer_rsrc_t rs = rangeF(b, ok ? e : b);
 #pragma unroll
         for (uint32_t g = 0; g < kFarRegs / kFarGroup; ++g)
             if (ok && e - b > g * kFarGroup * kT) {
@@ -253,7 +263,7 @@ __global__ __launch_bounds__(kLmThreads, 1) void lists_matrix_kernel(
     };
     // the elements of [b, e) from the `skip`-th per thread on, kBatch loads in flight
     auto toggle_rest = [&](uint32_t b, uint32_t e, uint32_t skip) {
-        const __amdgpu_buffer_rsrc_t rs = range(b, e);
+        const __amdgpu_buffer_rsrc_t rs = rangeA(b, e);
         for (uint32_t i = skip * kT; i < e - b; i += kBatch * kT) {   // (scalars: the same trips for every wave)
             uint32_t v[kBatch];
 #pragma unroll
@@ -266,7 +276,7 @@ __global__ __launch_bounds__(kLmThreads, 1) void lists_matrix_kernel(
     auto lookup_rest = [&](uint32_t b, uint32_t e, uint32_t skip) {
         const uint32_t first = skip * kT, n = e - b;
         if (first >= n) return;
-        const __amdgpu_buffer_rsrc_t rs = range(b, e);
+        const __amdgpu_buffer_rsrc_t rs = rangeF(b, e);
         uint32_t va[kFarGroup], vb[kFarGroup];
 #pragma unroll
         for (uint32_t q = 0; q < kFarGroup; ++q) va[q] = load_el(rs, first + tid + q * kT);
@@ -307,8 +317,8 @@ __global__ __launch_bounds__(kLmThreads, 1) void lists_matrix_kernel(
 #pragma unroll
     for (uint32_t q = 0; q < kARegs; ++q) {
         a_next2[q] = kInvalid;
-        a_cur[q] = load_el(range(w0.ab, w0.ok ? w0.ae : w0.ab), tid + q * kT);
-        a_next[q] = load_el(range(w1.ab, w1.ok ? w1.ae : w1.ab), tid + q * kT);
+        a_cur[q] = load_el(rangeA(w0.ab, w0.ok ? w0.ae : w0.ab), tid + q * kT);
+        a_next[q] = load_el(rangeA(w1.ab, w1.ok ? w1.ae : w1.ab), tid + q * kT);
     }
 #pragma unroll
     for (uint32_t q = 0; q < kFarRegs; ++q) f_cur[q] = f_next[q] = kInvalid;
@@ -323,7 +333,7 @@ __global__ __launch_bounds__(kLmThreads, 1) void lists_matrix_kernel(
     // that rotated the names with v_mov at the end of a step waited there for every load it had just issued).
     auto step = [&](uint32_t (&fc)[kFarRegs], uint32_t (&fn)[kFarRegs], uint32_t (&an)[kARegs], uint32_t (&an2)[kARegs]) {
 #pragma unroll
-        for (uint32_t q = 0; q < kARegs; ++q) an2[q] = load_el(range(w2.ab, w2.ok ? w2.ae : w2.ab), tid + q * kT);
+        for (uint32_t q = 0; q < kARegs; ++q) an2[q] = load_el(rangeA(w2.ab, w2.ok ? w2.ae : w2.ab), tid + q * kT);
         load_regs(fn, w1.fb, w1.fe, w1.ok);
         lookup_regs(fc, w0.fe - w0.fb);
         if (w0.fe - w0.fb > kFarRegs * kT) lookup_rest(w0.fb, w0.fe, kFarRegs);
@@ -345,18 +355,54 @@ __global__ __launch_bounds__(kLmThreads, 1) void lists_matrix_kernel(
         if (!w0.ok) break;
         step(f_next, f_cur, a_next2, a_next);
     }
-    // the tile: rows gi * 64 + a, columns cj * 768 + j, strict upper part
+    if constexpr (kJoin == kJoinCrossTotal) {
+        // the tile's sum: a thread adds 24 counter words (at most 24 x 2 x 65535 < 2^22), a wave its 64 threads (< 2^28),
+        // and every wave that found something adds into a slot of the fold (storm_hip.hip: fold_slots_kernel)
+        uint32_t s = 0;
+        for (uint32_t w = tid; w < kLmCountBytes / 4u; w += kT) {
+            const uint32_t v = cnt[w];
+            s += (v & 0xffffu) + (v >> 16);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += (uint32_t)__shfl_xor((int)s, o, 64);
+        if (lane == 0 && s != 0u && !(dbg & 8u))
+            atomicAdd(&slots[(blockIdx.x * (uint32_t)(kLmThreads / 64) + (tid >> 6)) & (uint32_t)(kSlots - 1)],
+                      (unsigned long long)s);
+        return;
+    }
+    // the tile: rows gi * 64 + a, columns cj * 768 + j; the triangle writes its strict upper part, the rectangle all of it
     const uint32_t row0 = it.gi * kLmGroup, col0 = it.cj * kLmChunk;
     for (uint32_t idx = tid; idx < kLmGroup * kLmChunk; idx += (uint32_t)kLmThreads) {
         const uint32_t a = idx / kLmChunk, j = idx % kLmChunk;
         const uint32_t row = row0 + a, col = col0 + j;
-        if (row < n_rows && col < n_rows && col > row && !(dbg & 8u)) {
+        if (row < n_rows && col < n_cols && (kJoin != kJoinTriangle || col > row) && !(dbg & 8u)) {
             uint32_t c = (cnt[idx >> 1] >> (16u * (j & 1u))) & 0xffffu;
-            if (op == STORM_HIP_OP_OR) c = rowlen[row] + rowlen[col] - c;
-            else if (op == STORM_HIP_OP_XOR) c = rowlen[row] + rowlen[col] - 2u * c;
+            if (op == STORM_HIP_OP_OR) c = rowlenA[row] + rowlenF[col] - c;
+            else if (op == STORM_HIP_OP_XOR) c = rowlenA[row] + rowlenF[col] - 2u * c;
             out[(uint64_t)row * ld + col] = c;
         }
     }
+}
+
+__global__ __launch_bounds__(kLmThreads, 1) void lists_matrix_kernel(
+    const uint32_t* __restrict__ elems, const uint32_t* __restrict__ off, uint32_t n_windows,
+    const uint32_t* __restrict__ rowlen, const LmItem* __restrict__ items, uint32_t n_rows, int op,
+    uint32_t* __restrict__ out, uint64_t ld, uint32_t dbg) {
+    lists_join<kJoinTriangle>(elems, off, n_windows, elems, off, n_windows, n_windows, rowlen, rowlen, items, n_rows, n_rows, op,
+                              out, ld, nullptr, dbg);
+}
+
+// K5x: the rectangle of two list-only containers — every (A group, B chunk) tile, all of it (no diagonal: A row i and B
+// row i are different rows). kTotal: the tile's sum into the fold's slots instead of the tile into `out`.
+template <bool kTotal>
+__global__ __launch_bounds__(kLmThreads, 1) void lists_square_kernel(
+    const uint32_t* __restrict__ elemsA, const uint32_t* __restrict__ offA, uint32_t nwA,
+    const uint32_t* __restrict__ elemsB, const uint32_t* __restrict__ offB, uint32_t nwB,
+    const uint32_t* __restrict__ rowlenA, const uint32_t* __restrict__ rowlenB, const LmItem* __restrict__ items,
+    uint32_t n_rows, uint32_t n_cols, int op, uint32_t* __restrict__ out, uint64_t ld,
+    unsigned long long* __restrict__ slots, uint32_t dbg) {
+    lists_join<kTotal ? kJoinCrossTotal : kJoinCrossMatrix>(elemsA, offA, nwA, elemsB, offB, nwB, min(nwA, nwB), rowlenA,
+                                                              rowlenB, items, n_rows, n_cols, op, out, ld, slots, dbg);
 }
 
 
@@ -494,6 +540,31 @@ static std::vector<LmItem> tile_order(uint64_t n_rows, uint32_t group_rows, uint
     return items;
 }
 
+// K5x: the tiles of the rectangle, every (A group, B chunk) pair, dealt like tile_order's: the tiles of a chunk on one XCD,
+// one after the other. Where the chunks are fewer than the XCDs, a chunk's groups are cut into that many runs, so that
+// every XCD has work (each run streams the chunk's elements through its own L2).
+static std::vector<LmItem> cross_order(uint32_t n_group, uint32_t n_chunk) {
+    constexpr uint32_t kXcds = 8;
+    const uint32_t runs = std::max<uint32_t>(1u, std::min<uint32_t>(n_group, (kXcds + n_chunk - 1u) / n_chunk));
+    std::vector<std::vector<LmItem>> per_xcd(kXcds);
+    for (uint32_t c = 0; c < n_chunk; ++c)
+        for (uint32_t r = 0; r < runs; ++r) {
+            size_t best = 0;
+            for (size_t x = 1; x < kXcds; ++x)
+                if (per_xcd[x].size() < per_xcd[best].size()) best = x;
+            for (uint32_t gi = (uint32_t)((uint64_t)n_group * r / runs); gi < (uint32_t)((uint64_t)n_group * (r + 1u) / runs); ++gi)
+                per_xcd[best].push_back({gi, c});
+        }
+    size_t longest = 0;
+    for (const auto& v : per_xcd) longest = std::max(longest, v.size());
+    std::vector<LmItem> items;
+    for (size_t i = 0; i < longest; ++i)
+        for (uint32_t x = 0; x < kXcds; ++x)
+            items.push_back(i < per_xcd[x].size() ? per_xcd[x][i] : LmItem{0xffffffffu, 0u});
+    while (!items.empty() && items.back().gi == 0xffffffffu) items.pop_back();
+    return items;
+}
+
 }  // namespace
 
 struct storm_hip_rowlists_s {
@@ -512,6 +583,10 @@ struct storm_hip_rowlists_s {
     LmItem* d_hash_items = nullptr;
     uint32_t n_hash_items = 0;
     uint32_t hash_g_log2 = 0;   // 0: no group size fits the table (rows too long): the window kernel only
+    // K5x with these rows on the A side: the tiles against the last B seen (cross_order), kept for the next call
+    LmItem* d_cross_items = nullptr;
+    uint32_t n_cross_items = 0;
+    uint32_t cross_chunks = 0;   // chunks of that B (0: none built)
 };
 
 extern "C" {
@@ -530,6 +605,7 @@ void storm_hip_rowlists_destroy(storm_hip_ctx_t* ctx, storm_hip_rowlists_t* l) {
     (void)hipFree(l->d_rtag);
     (void)hipFree(l->d_row_off);
     (void)hipFree(l->d_hash_items);
+    (void)hipFree(l->d_cross_items);
     delete l;
 }
 
@@ -896,5 +972,122 @@ int storm_hip_rowlists_pairw_matrix(storm_hip_ctx_t* ctx, const storm_hip_rowlis
 }
 
 uint64_t storm_hip_rowlists_n_elems(const storm_hip_rowlists_t* l) { return l ? l->n_elems : 0; }
+
+}  // extern "C"
+
+// K5x: the rectangle of two list-only containers (A = la's rows, B = lb's; la == lb is allowed). d_out: every entry of
+// the n_A x n_B window; NULL: the total, into the context's result word (through the fold of the slots).
+static int launch_lists_square(storm_hip_ctx_t* ctx, storm_hip_rowlists_t* la, const storm_hip_rowlists_t* lb, int op,
+                               uint32_t* d_out, uint64_t ld) {
+    if (!ctx || !la || !lb) {
+        set_error("rowlists_square: NULL argument");
+        return STORM_HIP_EINVAL;
+    }
+    if (d_out && op != STORM_HIP_OP_AND && op != STORM_HIP_OP_OR && op != STORM_HIP_OP_XOR) {
+        set_error("rowlists_square: op %d", op);
+        return STORM_HIP_EINVAL;
+    }
+    if (d_out && ld < lb->n_rows) {
+        set_error("rowlists_square: ld %llu < %llu rows of B", (unsigned long long)ld, (unsigned long long)lb->n_rows);
+        return STORM_HIP_EINVAL;
+    }
+    STORM_HIP_TRY(hipSetDevice(ctx->device));
+    const uint32_t n_group = (uint32_t)((la->n_rows + kLmGroup - 1u) / kLmGroup);
+    const uint32_t n_chunk = lb->n_groups / kLmChunkGroups;
+    if (la->cross_chunks != n_chunk || !la->d_cross_items) {
+        const std::vector<LmItem> items = cross_order(n_group, n_chunk);
+        if (la->d_cross_items) {
+            STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+            STORM_HIP_TRY(hipFree(la->d_cross_items));
+        }
+        la->d_cross_items = nullptr;
+        la->cross_chunks = 0;
+        STORM_HIP_TRY(hipMalloc(&la->d_cross_items, items.size() * sizeof(LmItem)));
+        STORM_HIP_TRY(hipMemcpyAsync(la->d_cross_items, items.data(), items.size() * sizeof(LmItem), hipMemcpyHostToDevice,
+                                     ctx->stream));
+        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));   // (`items` leaves scope)
+        la->n_cross_items = (uint32_t)items.size();
+        la->cross_chunks = n_chunk;
+    }
+    kernel_time_mark(ctx);
+    if (d_out)
+        hipLaunchKernelGGL(lists_square_kernel<false>, dim3(la->n_cross_items), dim3(kLmThreads), 0, ctx->stream, la->d_elems,
+                           la->d_off, la->n_windows, lb->d_elems, lb->d_off, lb->n_windows, la->d_rowlen, lb->d_rowlen,
+                           la->d_cross_items, (uint32_t)la->n_rows, (uint32_t)lb->n_rows, op, d_out, ld,
+                           (unsigned long long*)nullptr, (uint32_t)ctx->matrix_lists_debug);
+    else
+        hipLaunchKernelGGL(lists_square_kernel<true>, dim3(la->n_cross_items), dim3(kLmThreads), 0, ctx->stream, la->d_elems,
+                           la->d_off, la->n_windows, lb->d_elems, lb->d_off, lb->n_windows, la->d_rowlen, lb->d_rowlen,
+                           la->d_cross_items, (uint32_t)la->n_rows, (uint32_t)lb->n_rows, op, (uint32_t*)nullptr, (uint64_t)0,
+                           ctx->d_slots, (uint32_t)ctx->matrix_lists_debug);
+    kernel_time_mark(ctx);
+    STORM_HIP_TRY(hipGetLastError());
+    ctx->pass_report[0] = STORM_HIP_RAN_LISTS_SQUARE;
+    ctx->pass_report[1] = 0;
+    ctx->pass_report[2] = (uint64_t)n_group * lb->n_elems;   // every far element of B once per A group
+    ctx->pass_report[3] = kLmGroup;
+    return STORM_HIP_OK;
+}
+
+extern "C" {
+
+int storm_hip_rowlists_square_total(storm_hip_ctx_t* ctx, storm_hip_rowlists_t* la, const storm_hip_rowlists_t* lb,
+                                    uint64_t* h_total) {
+    return guarded("storm_hip_rowlists_square_total", [&]() -> int {
+        if (!h_total) {
+            set_error("rowlists_square_total: NULL output");
+            return STORM_HIP_EINVAL;
+        }
+        if (int rc = launch_lists_square(ctx, la, lb, STORM_HIP_OP_AND, nullptr, 0)) return rc;
+        if (int rc = launch_fold_slots(ctx, result_target(ctx))) return rc;
+        return fetch_result_word(ctx, h_total);
+    });
+}
+
+int storm_hip_rowlists_square_matrix_device(storm_hip_ctx_t* ctx, storm_hip_rowlists_t* la, const storm_hip_rowlists_t* lb,
+                                            int op, uint32_t* d_out, uint64_t ld) {
+    return guarded("storm_hip_rowlists_square_matrix_device", [&]() -> int {
+        if (!d_out) {
+            set_error("rowlists_square_matrix: NULL output");
+            return STORM_HIP_EINVAL;
+        }
+        if (int rc = launch_lists_square(ctx, la, lb, op, d_out, ld)) return rc;
+        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return STORM_HIP_OK;
+    });
+}
+
+// ... into HOST memory: the n_A x n_B window is built in the context's band buffer and copied out row by row
+int storm_hip_rowlists_square_matrix(storm_hip_ctx_t* ctx, storm_hip_rowlists_t* la, const storm_hip_rowlists_t* lb, int op,
+                                     uint32_t* h_out, uint64_t ld) {
+    return guarded("storm_hip_rowlists_square_matrix", [&]() -> int {
+        if (!ctx || !la || !lb || !h_out) {
+            set_error("rowlists_square_matrix: NULL argument");
+            return STORM_HIP_EINVAL;
+        }
+        const uint64_t na = la->n_rows, nb = lb->n_rows;
+        if (ld < nb) {
+            set_error("rowlists_square_matrix: ld %llu < %llu rows of B", (unsigned long long)ld, (unsigned long long)nb);
+            return STORM_HIP_EINVAL;
+        }
+        STORM_HIP_TRY(hipSetDevice(ctx->device));
+        const size_t need = (size_t)na * nb * sizeof(uint32_t);
+        if (need > ctx->band_capacity) {
+            if (ctx->d_band) STORM_HIP_TRY(hipFree(ctx->d_band));
+            ctx->d_band = nullptr;
+            ctx->band_capacity = 0;
+            if (hipMalloc(reinterpret_cast<void**>(&ctx->d_band), need) != hipSuccess) {
+                set_error("rowlists_square_matrix: hipMalloc of %zu bytes for the output failed", need);
+                return STORM_HIP_ENOMEM;
+            }
+            ctx->band_capacity = need;
+        }
+        if (int rc = launch_lists_square(ctx, la, lb, op, ctx->d_band, nb)) return rc;
+        STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(uint32_t), ctx->d_band, nb * sizeof(uint32_t), nb * sizeof(uint32_t), na,
+                                       hipMemcpyDeviceToHost, ctx->stream));
+        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return STORM_HIP_OK;
+    });
+}
 
 }  // extern "C"

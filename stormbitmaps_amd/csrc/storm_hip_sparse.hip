@@ -1663,6 +1663,16 @@ int storm_hip_matrix_create_from_blocks(storm_hip_ctx_t* ctx, uint64_t n_rows, u
                                                    const uint64_t* row_block_offset, const uint32_t* block_id,
                                                    const uint8_t* block_kind, const uint32_t* block_n,
                                                    const void* const* block_ptr, storm_hip_matrix_t** out) {
+    return storm_hip_matrix_create_from_blocks_wide(ctx, n_rows, n_blocks, row_block_offset, block_id, block_kind, block_n,
+                                                    block_ptr, 0u, out);
+}
+
+// ... with rows of at least min_blocks x 65536 bits: the common width of two containers whose rectangle the matrix kernels
+// multiply (they want both operands equally wide; the columns beyond a container's own blocks stay zero)
+int storm_hip_matrix_create_from_blocks_wide(storm_hip_ctx_t* ctx, uint64_t n_rows, uint64_t n_blocks,
+                                             const uint64_t* row_block_offset, const uint32_t* block_id,
+                                             const uint8_t* block_kind, const uint32_t* block_n,
+                                             const void* const* block_ptr, uint32_t min_blocks, storm_hip_matrix_t** out) {
     return guarded("storm_hip_matrix_create_from_blocks", [&]() -> int {
         if (!ctx || !out) {
             set_error("matrix_create_from_blocks: NULL context or output");
@@ -1697,8 +1707,13 @@ int storm_hip_matrix_create_from_blocks(storm_hip_ctx_t* ctx, uint64_t n_rows, u
             set_error("matrix_create_from_blocks: block id %u: rows of the dense form stop at 2^25 bits", max_id);
             return STORM_HIP_EINVAL;
         }
+        if (min_blocks > (1u << 25) / 65536u) {
+            set_error("matrix_create_from_blocks: %u blocks per row asked for: rows of the dense form stop at 2^25 bits",
+                      min_blocks);
+            return STORM_HIP_EINVAL;
+        }
         storm_hip_matrix_t* m = nullptr;
-        if (int rc = storm_hip_matrix_create(ctx, n_rows, (max_id + 1u) * kBlockWords, &m)) return rc;
+        if (int rc = storm_hip_matrix_create(ctx, n_rows, std::max(max_id + 1u, min_blocks) * kBlockWords, &m)) return rc;
         m->sparse_origin = true;   // (the output kernel is chosen by this: storm_hip_internal.h, k2_tile_shape)
         struct MatrixDeleter {
             storm_hip_ctx_t* ctx;

@@ -20,10 +20,10 @@
 #include <pthread.h>
 
 #include "storm_hip.h"
+#include "storm_host_internal.h"
 
 #define BLOCK_BITS ((uint32_t)STORM_DEFAULT_BLOCK_SIZE)
 #define BLOCK_WORDS (BLOCK_BITS / 64u)
-#define MAX_DEVICES 16
 #define ALL_PAIRS_FAILED ((uint64_t)-1)
 
 /* ------------------------------------------------------------------------------------------
@@ -1697,15 +1697,7 @@ uint64_t STORM_bitmap_cont_intersect_cardinality(
  * ---------------------------------------------------------------------------------------- */
 STORM_t* STORM_new() { return (STORM_t*)calloc(1, sizeof(STORM_t)); }
 
-/* device state of a STORM_t handle, per configured GPU: a replica of the block arena (what the all-pairs totals run
- * on) and/or of the rows as a dense bit matrix (what STORM_pairw_matrix runs on); each is built by its first user */
-typedef struct {
-    storm_hip_sparse_t* a[MAX_DEVICES];
-    storm_hip_matrix_t* m[MAX_DEVICES];
-    storm_hip_rowlists_t* l[MAX_DEVICES]; /* [r5] a list-only container's rows as window-ordered positions (K5) */
-    int have_arena, have_dense;
-    int have_lists; /* 0 not tried, 1 built (on every slot of the view), -1 not eligible */
-} sparse_state_t;
+/* (sparse_state_t, the device state of a STORM_t handle: storm_host_internal.h) */
 
 /* [r6] Streaming for the sparse container. STORM_add hands every bitmap block it finishes to a block stage on the device
  * (storm_hip_stage_*: 8 KiB into a pinned ring, on its way 4 MiB at a time), so that the first all-pairs call — the one
@@ -2172,7 +2164,11 @@ static sparse_state_t* storm_state(STORM_t* h, int* fresh) {
  * bitmap where it lies in the containers, ships the raw data through its pinned ring and lays it out on the
  * device (storm_hip_sparse_create_blocks / storm_hip_matrix_create_from_blocks). A first call at c4's 20971 draws
  * per row cost 0.6 - 0.9 s with the host-side flattening and element layout of rounds 2 - 3. */
-static int storm_build_device(STORM_t* h, sparse_state_t* st, int dense) {
+static int storm_build_device_wide(STORM_t* h, sparse_state_t* st, int dense, storm_dense_builder_t wide, uint32_t min_blocks);
+static int storm_build_device(STORM_t* h, sparse_state_t* st, int dense) { return storm_build_device_wide(h, st, dense, NULL, 0); }
+/* (wide, min_blocks: for dense = 1, the builder of a replica whose rows are at least min_blocks blocks wide — the common
+ *  width of a rectangle's two sides, storm_square.c; NULL: the container's own width) */
+static int storm_build_device_wide(STORM_t* h, sparse_state_t* st, int dense, storm_dense_builder_t wide, uint32_t min_blocks) {
     uint64_t n_blocks = 0;
     for (uint32_t i = 0; i < h->n_conts; ++i) n_blocks += h->conts[i].n_bitmaps;
     uint64_t* row_off = (uint64_t*)malloc((h->n_conts + 1ull) * sizeof(uint64_t));
@@ -2229,8 +2225,9 @@ static int storm_build_device(STORM_t* h, sparse_state_t* st, int dense) {
                                                                                         kinds, lens, ptrs, sg->stage, tokens, &st->l[d])
                                               : storm_hip_rowlists_create_blocks(ctx, h->n_conts, n_blocks, row_off, ids, kinds,
                                                                                  lens, ptrs, &st->l[d]))
-                          : dense ? storm_hip_matrix_create_from_blocks(ctx, h->n_conts, n_blocks, row_off, ids, kinds,
-                                                                        lens, ptrs, &st->m[d])
+                          : dense ? (wide ? wide(ctx, h->n_conts, n_blocks, row_off, ids, kinds, lens, ptrs, min_blocks, &st->m[d])
+                                          : storm_hip_matrix_create_from_blocks(ctx, h->n_conts, n_blocks, row_off, ids, kinds,
+                                                                                lens, ptrs, &st->m[d]))
                           : (tokens && d == sg->slot)
                               ? storm_hip_sparse_create_blocks_staged(ctx, h->n_conts, n_blocks, row_off, ids, kinds, lens,
                                                                       ptrs, sg->stage, tokens, &st->a[d])
@@ -2532,4 +2529,43 @@ uint64_t STORM_pairw_intersect_cardinality_blocked(STORM_t* h, uint32_t bsize) {
     (void)bsize;
     if (!h) return (uint64_t)-1;
     return storm_pairw_device(h);
+}
+
+/* ---- for storm_square.c (storm_host_internal.h): the rectangle of two containers on this file's device state */
+void storm_host_lock(void) { device_lock(); }
+void storm_host_unlock(void) { device_unlock(); }
+void storm_host_error(const char* msg) { host_error(msg); }
+void storm_host_device_error(const char* where) { device_error(where); }
+int storm_host_one_slot_or_refuse(const char* who) { return one_slot_or_refuse(who); }
+int storm_host_single_device(void) {
+    configure_from_env();
+    return VN == 1 && g_shard_count == 1;
+}
+int storm_host_slot(void) { return V0; }
+storm_hip_ctx_t* storm_host_ctx(void) { return device_ctx(V0); }
+/* the state of a handle checked against the container as it is now (fingerprint / epoch / stamps, as
+ * storm_pairw_matrix_locked does it) */
+sparse_state_t* storm_host_checked_state(STORM_t* h) {
+    int fresh = 0;
+    sparse_state_t* st = storm_state(h, &fresh);
+    if (!st) return NULL;
+    const uint64_t epoch = storm_epoch();
+    if (!fresh && !h->hip_private && (h->hip_epoch != epoch || always_fingerprint()) &&
+        storm_fingerprint(h) != h->hip_fingerprint) { /* rows edited through the public adders behind STORM_add */
+        storm_drop_device(h);
+        if (!(st = storm_state(h, &fresh))) return NULL;
+    }
+    h->hip_epoch = epoch;
+    return st;
+}
+int storm_host_build(STORM_t* h, sparse_state_t* st, int dense, storm_dense_builder_t wide, uint32_t min_blocks) {
+    return storm_build_device_wide(h, st, dense, wide, min_blocks);
+}
+void storm_host_drop_dense(sparse_state_t* st) {
+    for (int d = 0; d < MAX_DEVICES; ++d)
+        if (st->m[d]) {
+            storm_hip_matrix_destroy(g_ctx[d], st->m[d]);
+            st->m[d] = NULL;
+        }
+    st->have_dense = 0;
 }

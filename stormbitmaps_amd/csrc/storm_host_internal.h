@@ -1,0 +1,42 @@
+/* storm_host_internal.h — what the host side of the storm.h containers shares between its files: the device state of a
+ * STORM_t handle (storm_host.c) and the helpers the rectangle of two containers (storm_square.c) runs on. Not installed. */
+#ifndef STORM_HOST_INTERNAL_H_
+#define STORM_HOST_INTERNAL_H_
+#include <stdint.h>
+
+#include "storm.h"
+#include "storm_hip.h"
+
+#define MAX_DEVICES 16
+
+/* device state of a STORM_t handle, per configured GPU: a replica of the block arena (what the all-pairs totals run
+ * on) and/or of the rows as a dense bit matrix (what STORM_pairw_matrix runs on); each is built by its first user */
+typedef struct {
+    storm_hip_sparse_t* a[MAX_DEVICES];
+    storm_hip_matrix_t* m[MAX_DEVICES];
+    storm_hip_rowlists_t* l[MAX_DEVICES]; /* [r5] a list-only container's rows as window-ordered positions (K5) */
+    int have_arena, have_dense;
+    int have_lists; /* 0 not tried, 1 built (on every slot of the view), -1 not eligible */
+} sparse_state_t;
+
+/* a dense replica builder with a minimum row width (storm_hip_matrix_create_from_blocks_wide) */
+typedef int (*storm_dense_builder_t)(storm_hip_ctx_t* ctx, uint64_t n_rows, uint64_t n_blocks,
+                                     const uint64_t* row_block_offset, const uint32_t* block_id, const uint8_t* block_kind,
+                                     const uint32_t* block_n, const void* const* block_ptr, uint32_t min_blocks,
+                                     storm_hip_matrix_t** out);
+
+/* storm_host.c */
+void storm_host_lock(void);   /* the calling thread's device slots */
+void storm_host_unlock(void);
+void storm_host_error(const char* msg);
+void storm_host_device_error(const char* where);
+int storm_host_one_slot_or_refuse(const char* who);  /* 0, or -5 with the reason */
+int storm_host_single_device(void);                  /* 1: one device slot and one shard */
+int storm_host_slot(void);                           /* the calling thread's first device slot */
+storm_hip_ctx_t* storm_host_ctx(void);               /* its context (NULL: no device, the reason reported) */
+sparse_state_t* storm_host_checked_state(STORM_t* h);
+/* storm_build_device: dense = 0 arena, 1 dense replica (`wide` with min_blocks, or NULL: own width), 2 row lists */
+int storm_host_build(STORM_t* h, sparse_state_t* st, int dense, storm_dense_builder_t wide, uint32_t min_blocks);
+void storm_host_drop_dense(sparse_state_t* st);
+
+#endif /* STORM_HOST_INTERNAL_H_ */

@@ -1,0 +1,146 @@
+/* storm_square.c — the rectangle of two STORM_t (storm.h: STORM_intersect_cardinality_square, STORM_square_matrix,
+ * STORM_square_matrix_device). The reference declares the first (storm.h:231) and never defines it (storm.c:975).
+ *
+ * Both handles keep their device copies exactly as for STORM_pairw_matrix (storm_host.c: state, fingerprint / epoch /
+ * block stamps, one build per kind, all under the calling thread's device lock). Two list-only containers that the K5
+ * rule (option matrix_lists, applied to the two together) sends to the lists are joined from their row lists (K5x,
+ * storm_hip_lists.hip); any other pair is multiplied as dense replicas of one common width (the wider of the two; a
+ * handle keeps its widened replica, whose extra zero columns change no count of its own triangle). One device slot and
+ * one process: the rectangle is not split over devices or shards, and every rank refuses alike. */
+#include <stdint.h>
+#include <stdlib.h>
+
+#include "storm.h"
+#include "storm_hip.h"
+#include "storm_host_internal.h"
+
+#define BLOCK_WORDS ((uint32_t)STORM_DEFAULT_BLOCK_SIZE / 64u)
+
+/* listed positions and the width in bits of a list-only container (0: it holds a bitmap block) */
+static int list_counts(const STORM_t* h, uint64_t* n_elems, uint64_t* n_bits) {
+    uint64_t e = 0, max_id = 0;
+    for (uint32_t i = 0; i < h->n_conts; ++i)
+        for (uint32_t b = 0; b < h->conts[i].n_bitmaps; ++b) {
+            const STORM_bitmap_t* blk = &h->conts[i].bitmaps[b];
+            if (blk->n_bitmap) return 0;
+            e += blk->n_scalar;
+            if (blk->n_scalar && blk->id > max_id) max_id = blk->id;
+        }
+    *n_elems = e;
+    *n_bits = (max_id + 1) * 65536ull;
+    return 1;
+}
+
+/* blocks per row of a container's own dense replica (storm_hip_matrix_create_from_blocks: largest block id + 1) */
+static uint32_t dense_blocks(const STORM_t* h) {
+    uint32_t max_id = 0;
+    for (uint32_t i = 0; i < h->n_conts; ++i)
+        for (uint32_t b = 0; b < h->conts[i].n_bitmaps; ++b)
+            if (h->conts[i].bitmaps[b].id > max_id) max_id = h->conts[i].bitmaps[b].id;
+    return max_id + 1u;
+}
+
+static uint32_t replica_blocks(const sparse_state_t* st, int slot) {
+    return st->have_dense ? storm_hip_matrix_words(st->m[slot]) / BLOCK_WORDS : 0u;
+}
+
+/* the dense replica of `h` at least `blocks` wide: a narrower one is rebuilt, a wider one kept */
+static int dense_at_width(STORM_t* h, sparse_state_t* st, int slot, uint32_t blocks) {
+    if (st->have_dense && replica_blocks(st, slot) >= blocks) return 0;
+    storm_host_drop_dense(st);
+    return storm_host_build(h, st, 1, storm_hip_matrix_create_from_blocks_wide, blocks);
+}
+
+/* what = 0: *total; 1: the window into host `out`; 2: into device `out`. 0, or -3 with the reason in STORM_hip_error(). */
+static int square_locked(STORM_t* a, STORM_t* b, int what, int op, uint32_t* out, uint64_t out_ld, uint64_t* total) {
+    if (!storm_host_single_device()) {
+        storm_host_error("STORM_intersect_cardinality_square / STORM_square_matrix: the rectangle of two containers is "
+                         "computed on ONE device slot by ONE process; it is not split over devices or shards "
+                         "(STORM_hip_set_devices, STORM_hip_set_thread_devices, STORM_hip_set_shard)");
+        return -3;
+    }
+    storm_hip_ctx_t* ctx = storm_host_ctx();
+    if (!ctx) return -3;
+    const int slot = storm_host_slot();
+    sparse_state_t* sa = storm_host_checked_state(a);
+    sparse_state_t* sb = sa && b != a ? storm_host_checked_state(b) : sa;
+    if (!sa || !sb) return -3;
+    /* [K5x] both list-only, and the K5 rule sends the two together to the lists */
+    uint64_t ea = 0, eb = 0, wa = 0, wb = 0;
+    if (storm_hip_rowlists_worthwhile(ctx, NULL) && sa->have_lists != -1 && sb->have_lists != -1 &&
+        list_counts(a, &ea, &wa) && list_counts(b, &eb, &wb) &&
+        storm_hip_rowlists_worthwhile_counts(ctx, (uint64_t)a->n_conts + b->n_conts, ea + eb, wa > wb ? wa : wb)) {
+        if (sa->have_lists == 0 && storm_host_build(a, sa, 2, NULL, 0)) return -3;
+        if (sb->have_lists == 0 && storm_host_build(b, sb, 2, NULL, 0)) return -3;
+        if (sa->have_lists == 1 && sb->have_lists == 1) {
+            storm_hip_rowlists_t* la = sa->l[slot];
+            const storm_hip_rowlists_t* lb = sb->l[slot];
+            const int rc = what == 0   ? storm_hip_rowlists_square_total(ctx, la, lb, total)
+                           : what == 1 ? storm_hip_rowlists_square_matrix(ctx, la, lb, op, out, out_ld)
+                                       : storm_hip_rowlists_square_matrix_device(ctx, la, lb, op, out, out_ld);
+            if (rc != STORM_HIP_OK) {
+                storm_host_device_error("storm_hip_rowlists_square");
+                return -3;
+            }
+            return 0;
+        }
+    }
+    /* dense replicas of one common width: the wider of the two containers, or of a replica one of them already keeps */
+    uint32_t blocks = dense_blocks(a), x = dense_blocks(b);
+    if (x > blocks) blocks = x;
+    if ((x = replica_blocks(sa, slot)) > blocks) blocks = x;
+    if ((x = replica_blocks(sb, slot)) > blocks) blocks = x;
+    if (dense_at_width(a, sa, slot, blocks) || (b != a && dense_at_width(b, sb, slot, blocks))) return -3;
+    const int rc = what == 0   ? storm_hip_cross_dense_total(ctx, sa->m[slot], sb->m[slot], total)
+                   : what == 1 ? storm_hip_cross_dense_matrix(ctx, sa->m[slot], sb->m[slot], op, out, out_ld)
+                               : storm_hip_cross_dense_matrix_device(ctx, sa->m[slot], sb->m[slot], op, out, out_ld);
+    if (rc != STORM_HIP_OK) {
+        storm_host_device_error("storm_hip_cross_dense");
+        return -3;
+    }
+    return 0;
+}
+
+uint64_t STORM_intersect_cardinality_square(const STORM_t* STORM_RESTRICT bitmap1, const STORM_t* STORM_RESTRICT bitmap2) {
+    if (!bitmap1 || !bitmap2) {
+        storm_host_error("STORM_intersect_cardinality_square: NULL handle");
+        return (uint64_t)-1;
+    }
+    if (bitmap1->n_conts == 0 || bitmap2->n_conts == 0) return 0;
+    uint64_t total = 0;
+    storm_host_lock();
+    /* (the containers are const; the device copies behind them are built and kept as for every other call) */
+    const int rc = square_locked((STORM_t*)bitmap1, (STORM_t*)bitmap2, 0, 0, NULL, 0, &total);
+    storm_host_unlock();
+    return rc ? (uint64_t)-1 : total;
+}
+
+int STORM_square_matrix(STORM_t* a, STORM_t* b, int op, uint32_t* out, uint64_t out_rows, uint64_t out_ld) {
+    if (!a || !b) return -1;
+    if (!out) return -2;
+    if (out_rows < a->n_conts || out_ld < b->n_conts) return -4;
+    if (op < 0 || op > 2) {
+        storm_host_error("STORM_square_matrix: op must be 0 (and), 1 (or) or 2 (xor)");
+        return -3;
+    }
+    if (a->n_conts == 0 || b->n_conts == 0) return 0;
+    storm_host_lock();
+    const int rc = square_locked(a, b, 1, op, out, out_ld, NULL);
+    storm_host_unlock();
+    return rc;
+}
+
+int STORM_square_matrix_device(STORM_t* a, STORM_t* b, int op, uint32_t* d_out, uint64_t out_rows, uint64_t out_ld) {
+    if (!a || !b) return -1;
+    if (!d_out) return -2;
+    storm_host_lock();
+    int rc = storm_host_one_slot_or_refuse("STORM_square_matrix_device");
+    if (!rc && (out_rows < a->n_conts || out_ld < b->n_conts)) rc = -4;
+    if (!rc && (op < 0 || op > 2)) {
+        storm_host_error("STORM_square_matrix_device: op must be 0 (and), 1 (or) or 2 (xor)");
+        rc = -3;
+    }
+    if (!rc && a->n_conts != 0 && b->n_conts != 0) rc = square_locked(a, b, 2, op, d_out, out_ld, NULL);
+    storm_host_unlock();
+    return rc;
+}
