@@ -140,7 +140,10 @@ int storm_hip_pairw_dense_op(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, 
  * _device: `d_out` is a DEVICE pointer to n_rows x ld uint32 (ld >= n_rows); synchronous.
  * plain  : `h_out` is a HOST n_rows x n_rows uint32 buffer; entries i >= j come back as 0.
  * Rows of 2^24 bits and more (beyond exact f32 accumulation in one go) are cut along k and the
- * parts added; the limit is 2^25 bits per row (32-bit DMA offsets of the tile kernel). */
+ * parts added; the limit is 2^25 bits per row (32-bit DMA offsets of the tile kernel).
+ * Empty shapes: a matrix of fewer than two rows has no pairs, a band of 0 rows and a rectangle with an empty side have no
+ * entries — these calls (and the band and rectangle forms below) return STORM_HIP_OK and write nothing; the host form of a
+ * one-row matrix returns its single 0. */
 int storm_hip_pairw_matrix_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int op,
                                   uint32_t* d_out, uint64_t ld);
 int storm_hip_pairw_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int op,

@@ -389,6 +389,12 @@ class HipMatrix:
     def clear(self) -> None:
         check(self._lib.storm_hip_matrix_clear(self.ctx._h, self._h), "storm_hip_matrix_clear")
 
+    def resize(self, n_rows: int) -> None:
+        """storm_hip_matrix_resize: change the logical row count. Rows dropped by a shrink are cleared, rows gained are
+        zero until uploaded; growing beyond the allocation reallocates and keeps the rows."""
+        check(self._lib.storm_hip_matrix_resize(self.ctx._h, self._h, n_rows), "storm_hip_matrix_resize")
+        self.n_rows = n_rows
+
     @property
     def device_ptr(self) -> int:
         return int(self._lib.storm_hip_matrix_device_ptr(self._h) or 0)
@@ -409,6 +415,17 @@ class HipMatrix:
         check(self._lib.storm_hip_pairw_dense_launch(self.ctx._h, self._h, shard_rank,
                                                      shard_count, C.c_void_p(d_total_ptr)),
               "storm_hip_pairw_dense_launch")
+
+    def pairw_upload(self, host_rows: np.ndarray) -> int:
+        """storm_hip_pairw_dense_upload: `host_rows` ([n_rows, >= n_words] uint64; a wider array's surplus words are not
+        read) replace all rows of the matrix while the pass multiplies the panels that have landed; the all-pairs total."""
+        v = np.ascontiguousarray(host_rows, dtype=np.uint64)
+        if v.ndim != 2 or v.shape[0] != self.n_rows:
+            raise ValueError(f"pairw_upload: {v.shape} is not [{self.n_rows}, >= {self.n_words}]")
+        out = C.c_uint64()
+        check(self._lib.storm_hip_pairw_dense_upload(self.ctx._h, self._h, _ptr(v), v.shape[1], C.byref(out)),
+              "storm_hip_pairw_dense_upload")
+        return int(out.value)
 
     def square(self, other: "HipMatrix") -> int:
         out = C.c_uint64()
