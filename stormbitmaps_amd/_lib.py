@@ -214,14 +214,15 @@ def check(rc: int, what: str) -> None:
 
 
 def kernel_source_hash() -> str:
-    """Fingerprint of the device sources (csrc/*.hip, csrc/*.inc + the shared internal header): what a
+    """Fingerprint of the device sources (csrc/*.hip, csrc/*.inc + the shared internal header and the item
+    layouts of storm_hip_plan.h): what a
     profile summary under profiles/ was measured on. bench.py only quotes measured HBM traffic
     whose fingerprint equals the current one."""
     import hashlib
     h = hashlib.sha256()
     csrc = os.path.join(_HERE, "csrc")
     for name in sorted(os.listdir(csrc)):
-        if name.endswith((".hip", ".inc")) or name == "storm_hip_internal.h":
+        if name.endswith((".hip", ".inc")) or name in ("storm_hip_internal.h", "storm_hip_plan.h"):
             with open(os.path.join(csrc, name), "rb") as f:
                 h.update(name.encode() + b"\0" + f.read())
     return h.hexdigest()[:16]

@@ -457,14 +457,7 @@ static int ensure_segments(storm_hip_ctx_t* ctx, uint64_t n_rows, uint32_t shard
 
     uint64_t row_sum = 0;
     for (const Seg& s : mine) row_sum += s.j_hi - s.j_lo;
-    if (mine.size() > ctx->segs_capacity) {
-        if (ctx->d_segs) STORM_HIP_TRY(hipFree(ctx->d_segs));
-        ctx->d_segs = nullptr;
-        ctx->segs_capacity = 0;
-        const size_t cap = std::max<size_t>(mine.size(), 1024);
-        STORM_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ctx->d_segs), cap * sizeof(Seg)));
-        ctx->segs_capacity = cap;
-    }
+    if (int rc = ctx->d_segs.ensure(mine.size() * sizeof(Seg), "pairw_dense: the segment table", 1024 * sizeof(Seg))) return rc;
     if (!mine.empty()) {
         // pageable host memory: the copy is complete (staged) when the call returns
         STORM_HIP_TRY(hipMemcpyAsync(ctx->d_segs, mine.data(), mine.size() * sizeof(Seg),
@@ -634,16 +627,157 @@ void storm_hip_ctx_destroy(storm_hip_ctx_t* ctx) {
     drain_deferred(ctx, false);
     if (ctx->d_slots) (void)hipFree(ctx->d_slots);
     if (ctx->d_scalar) (void)hipFree(ctx->d_scalar);
-    if (ctx->d_positions) (void)hipFree(ctx->d_positions);
+    ctx->d_positions.release();
     if (ctx->h_scalar) (void)hipHostFree(ctx->h_scalar);
     if (ctx->h_mail) (void)hipHostFree(ctx->h_mail);
     if (ctx->h_stage_ring) (void)hipHostFree(ctx->h_stage_ring);
     for (hipEvent_t e : ctx->stage_ev)
         if (e) (void)hipEventDestroy(e);
-    if (ctx->d_segs) (void)hipFree(ctx->d_segs);
+    ctx->d_segs.release();
     release_mfma_state(ctx);
     for (hipEvent_t ev : ctx->kernel_events) (void)hipEventDestroy(ev);
     delete ctx;
+}
+
+// ---- options: one row per key ----
+// A row names the int member of the context the option is stored in, the values it takes, which of them exist in the
+// tools build only (`make probes`), and the error texts. storm_hip_ctx_set_option, storm_hip_ctx_get_option and
+// storm_hip_option_check walk the table; every key that can be set reads back under the same name.
+#ifdef STORM_HIP_PROBES
+constexpr bool kToolsBuild = true;
+#else
+constexpr bool kToolsBuild = false;
+#endif
+
+struct OptionRow {
+    const char* name;
+    int storm_hip_ctx_s::*member;
+    enum Kind { RANGE, SET, BOOL, ANY, HOOK } kind;   // [lo, hi] / one of `set` / stored as value != 0 / stored as it is / `hook` validates and stores
+    int64_t lo, hi;
+    int64_t step;                     // RANGE: positive values are multiples of this (0: any)
+    std::vector<int64_t> set;
+    const char* text;                 // what an illegal value is told ("%s": the key)
+    std::vector<int64_t> tools_only;  // legal values the shipped build refuses ...
+    const char* tools_text;           // ... with these words
+    int (*hook)(storm_hip_ctx_t* ctx, int64_t value);     // HOOK
+    void (*after)(storm_hip_ctx_t* ctx, int64_t value);   // runs behind the store (the value as it was given)
+};
+
+static void drop_shadow(storm_hip_ctx_t* ctx, int64_t) { memset(ctx->x4_key, 0, sizeof(ctx->x4_key)); }
+// time_kernels 1: start a new series of bracketed launches; 0: pause (the series is kept for storm_hip_kernel_time);
+// 2: resume it (bench.py brackets every 4th step at N > 1)
+static void restart_series(storm_hip_ctx_t* ctx, int64_t value) {
+    if (value == 1) ctx->kernel_events_used = 0;
+}
+static int set_matrix_pad(storm_hip_ctx_t* ctx, int64_t value) {
+    ctx->k2_matrix_pad = value < 0 ? -1 : (int)std::min<int64_t>(value, 64);   // chunks of 512 bytes
+    return STORM_HIP_OK;
+}
+static int set_fold_inline(storm_hip_ctx_t* ctx, int64_t value) {
+    ctx->k2_fold_inline = value < 0 ? -1 : value != 0;
+    return STORM_HIP_OK;
+}
+static int set_ring(storm_hip_ctx_t* ctx, int64_t value) {
+    if (kToolsBuild ? (value < 3 || value > 5) && (value < 11 || value > 18) && value != 26 : value != 4) {
+        set_error(kToolsBuild ? "k2_ring must be 3, 4 or 5 (10 + bits = timing probes)"
+                              : "k2_ring: this build ships the 4-deep ring only (other depths and the timing "
+                                "probes: build with STORM_HIP_PROBES, `make probes`)");
+        return STORM_HIP_EINVAL;
+    }
+    ctx->k2_ring = (int)value;
+    return STORM_HIP_OK;
+}
+static int set_debug(storm_hip_ctx_t* ctx, int64_t value) {   // stored in the tools build, refused (non-zero) in the shipped one
+    if (kToolsBuild) {
+        ctx->k2_debug = (int)value;
+    } else if (value != 0) {
+        set_error("k2_debug: timing probes (wrong results by design) are not in this build "
+                  "(STORM_HIP_PROBES, `make probes`)");
+        return STORM_HIP_EINVAL;
+    }
+    return STORM_HIP_OK;
+}
+
+static const std::vector<OptionRow>& option_table() {
+    using C = storm_hip_ctx_s;
+    constexpr auto RANGE = OptionRow::RANGE, SET = OptionRow::SET, BOOL = OptionRow::BOOL, ANY = OptionRow::ANY, HOOK = OptionRow::HOOK;
+    constexpr const char* kCostText = "%s is a percentage of a full tile's time, 5..100";
+    static const std::vector<OptionRow> rows = {
+        {"variant", &C::variant, RANGE, -1, 5, 0, {}, "variant must be -1 (auto) or 0..5", {5},
+         "variant 5 (wide 32x32x64 strips) is a form of the tools build (`make probes`), not of the shipped library"},
+        {"probe_bundle", &C::probe_bundle, SET, 0, 0, 0, {-1, 1, 4},
+         "probe_bundle must be -1 (auto: 1), 1 (one group of 128 rows per workgroup) or 4 (bundles of four)"},
+        {"sparse_probe", &C::sparse_probe, RANGE, -1, 1, 0, {}, "sparse_probe must be -1 (auto), 0 (never) or 1 (every eligible column)"},
+        {"result_mailbox", &C::result_mailbox, BOOL},
+        {"sync_poll_us", &C::sync_poll_us, RANGE, 0, 1000000, 0, {}, "sync_poll_us: 0 .. 1000000 microseconds"},
+        {"matrix_lists", &C::matrix_lists, RANGE, -1, 1, 0, {}, "matrix_lists must be -1 (by density), 0 (never) or 1 (whenever eligible)"},
+        {"matrix_lists_kernel", &C::matrix_lists_kernel, RANGE, 0, 2, 0, {},
+         "matrix_lists_kernel: 0 (by the row length), 1 (window kernel) or 2 (hash kernel)"},
+        {"matrix_lists_hash_min_log2", &C::matrix_lists_hash_min_log2, RANGE, 3, 7, 0, {}, "matrix_lists_hash_min_log2: 3 .. 7"},
+        {"matrix_lists_debug", &C::matrix_lists_debug, ANY},
+        {"matrix_lists_density", &C::matrix_lists_permille_x10, RANGE, 0, 10000, 0, {},
+         "matrix_lists_density: 0 .. 10000 (1/10000 of the dense replica's bits)"},
+        {"seg_rows", &C::seg_rows, RANGE, 1, 1 << 20, 0, {}, "seg_rows out of range"},
+        {"k2_stages_per_item", &C::k2_stages_per_item, RANGE, 1, 65536, 0, {}, "k2_stages_per_item out of range"},
+        {"k2_max_run", &C::k2_max_run, RANGE, 0, 4096, 0, {},
+         "k2_max_run out of range (0 = chosen by the list-scheduling estimate, 1..4096)"},
+        {"k2_ring", &C::k2_ring, HOOK, 0, 0, 0, {}, nullptr, {}, nullptr, set_ring},
+        {"k2_shadow_budget_mb", &C::k2_shadow_budget_mb, RANGE, 0, 1 << 22, 0, {}, "k2_shadow_budget_mb must be 0 (unbounded) .. 4194304",
+         {}, nullptr, nullptr, drop_shadow},
+        {"k2_tile_shape", &C::k2_tile_shape, SET, 0, 0, 0, {0, 1, 2, 3, 4, 5, 6, 16, 32},
+         "k2_tile_shape must be 0 (chosen by the matrix), 5 (both operands as FP4 images in the LDS, 16x16x128 MFMAs), 1, 2 (bit operands inflated in registers), 3 / 4 (B as FP4 images in the LDS, 16x16x128 / 32x32x64 MFMAs), 6 (128 x 128 tiles, k-parts whose sums meet inside the launch), 16 or 32 (FP4 shadow)",
+         {1, 16},
+         "k2_tile_shape = 1 / 16 (tilebits_kernel, tile16_fp4_kernel) is a form of the tools build (`make probes`), not of the shipped library"},
+        {"k2_ring_sync", &C::k2_ring_sync, BOOL},
+        {"k2_wave_below", &C::k2_wave_below, RANGE, 0, 1 << 30, 0, {}, "k2_wave_below: 0 (never) .. 2^30 tiles of 256 x 256"},
+        {"k2_part_slots", &C::k2_part_slots, RANGE, 0, 2, 0, {}, "k2_part_slots must be 0 (by the length of the segments), 1 or 2 per CU"},
+        {"k2_part_min_chunks", &C::k2_part_min_chunks, RANGE, 1, 4096, 0, {}, "k2_part_min_chunks: 1 .. 4096 chunks of 512 bits"},
+        {"k2_part_narrow", &C::k2_part_narrow, BOOL},
+        {"k2_part_cost_diag", &C::k2_part_cost_diag, RANGE, 10, 100, 0, {}, "k2_part_cost_diag: 10 .. 100 percent of a full tile's chunk"},
+        {"k2_ring_cost_diag", &C::k2_ring_cost_diag, RANGE, 5, 100, 0, {}, kCostText},
+        {"k2_ring_cost_ragged", &C::k2_ring_cost_ragged, RANGE, 5, 100, 0, {}, kCostText},
+        {"k2_tile_cost_diag", &C::k2_tile_cost_diag, RANGE, 5, 100, 0, {}, kCostText},
+        {"k2_tile_cost_ragged", &C::k2_tile_cost_ragged, RANGE, 5, 100, 0, {}, kCostText},
+        {"k2_strip_operands", &C::k2_strip_operands, RANGE, 0, 6, 0, {},
+         "k2_strip_operands must be 0 (by size), 1 (bit operands, one item per workgroup), 2 (bit operands, one stream per workgroup), 3 (the same with a ring per wave), 4 (FP4 shadow), 5 (bit operands, FP4 image built in the LDS) or 6 (the same with 512-row A tiles, two halves behind one image)",
+         {1, 3},
+         "k2_strip_operands = 1 (stripbits_kernel) and 3 (bitwave_kernel) are forms of the tools build (`make probes`), not of the shipped library"},
+        {"k2_shard_pairs", &C::k2_shard_pairs, BOOL},
+        {"k2_matrix_pad", &C::k2_matrix_pad, HOOK, 0, 0, 0, {}, nullptr, {}, nullptr, set_matrix_pad},     // clamps to -1 / 0 .. 64
+        {"k2_fold_inline", &C::k2_fold_inline, HOOK, 0, 0, 0, {}, nullptr, {}, nullptr, set_fold_inline},  // normalises to -1 / 0 / 1
+        {"k2_wave_ring", &C::k2_wave_ring, SET, 0, 0, 0, {0, 3, 4, 6, 8}, "k2_wave_ring must be 0 (by occupancy), 3, 4, 6 or 8"},
+        // (accepted and read by nothing in the shipped build: K2q is no longer chosen by the row count; tests/test_gpu_round3.py sets it)
+        {"k2_stream_max_rows", &C::k2_stream_max_rows, RANGE, 0, 1ll << 31, 0, {}, "k2_stream_max_rows must be 0 .. 2^31"},
+        {"k2_stream_groups_per_cu", &C::k2_stream_groups_per_cu, RANGE, 0, 255, 0, {}, "k2_stream_groups_per_cu must be 0 (auto) .. 255"},
+        {"k2_stream_min_piece", &C::k2_stream_min_piece, RANGE, 1, 4096, 0, {}, "%s must be 1..4096 stages"},
+        {"k2_stream_min_run", &C::k2_stream_min_run, RANGE, 1, 4096, 0, {}, "%s must be 1..4096 stages"},
+        {"k2_stream_w3_1", &C::k2_stream_w3_1, RANGE, 10, 1000, 0, {}, "%s must be 10..1000 percent of the first workgroup's share"},
+        {"k2_stream_w3_2", &C::k2_stream_w3_2, RANGE, 10, 1000, 0, {}, "%s must be 10..1000 percent of the first workgroup's share"},
+        {"k2_shape", &C::k2_shape, SET, 0, 0, 0, {16, 32}, "k2_shape must be 16 (16x16x128 MFMA) or 32 (32x32x64)", {32},
+         "k2_shape = 32 (strip_fp4_kernel) is a form of the tools build (`make probes`), not of the shipped library"},
+        {"keep_shadow", &C::keep_shadow, BOOL, 0, 0, 0, {}, nullptr, {}, nullptr, nullptr, drop_shadow},
+        {"k2_matrix_parts", &C::k2_matrix_parts, BOOL},
+        {"k2_matrix_min_part", &C::k2_matrix_min_part, RANGE, 4, 4096, 4, {},
+         "k2_matrix_min_part: a multiple of 4 in 4 .. 4096 (stages of 128 bits)"},
+        {"k2_matrix_split", &C::k2_matrix_split, BOOL},
+        {"k2_pitch_pad", &C::k2_pitch_pad, RANGE, -1, 65536, 128, {}, "k2_pitch_pad must be -1 (auto) or a multiple of 128 in 0..65536"},
+        {"k2_lds_pad", &C::k2_lds_pad, RANGE, 0, 120 * 1024, 0, {}, "k2_lds_pad must be 0..122880"},
+        {"k2_persistent", &C::k2_persistent, BOOL, 0, 0, 0, {}, nullptr, {1},
+         "k2_persistent (strip_fp4_kernel with work queues) is a form of the tools build (`make probes`), not of the shipped library"},
+        {"k2_lpt_rounds", &C::k2_lpt_rounds, RANGE, 0, 63, 0, {}, "k2_lpt_rounds must be 0..63"},
+        {"k2_tail_slices", &C::k2_tail_slices, RANGE, 0, 255, 0, {}, "k2_tail_slices must be 0..255"},
+        {"k2_tail_run", &C::k2_tail_run, RANGE, 1, 4096, 0, {}, "k2_tail_run must be 1..4096"},
+        {"k2_debug", &C::k2_debug, HOOK, 0, 0, 0, {}, nullptr, {}, nullptr, set_debug},
+        {"time_kernels", &C::time_kernels, BOOL, 0, 0, 0, {}, nullptr, {}, nullptr, nullptr, restart_series},
+        {"chunks_per_item", &C::chunks_per_item, RANGE, 0, 4096, 0, {}, "chunks_per_item out of range"},
+    };
+    return rows;
+}
+
+static const OptionRow* find_option(const char* key) {
+    for (const OptionRow& row : option_table())
+        if (!strcmp(key, row.name)) return &row;
+    return nullptr;
 }
 
 int storm_hip_option_check(const char* key, int64_t value) {
@@ -655,338 +789,37 @@ int storm_hip_option_check(const char* key, int64_t value) {
 
 int storm_hip_ctx_set_option(storm_hip_ctx_t* ctx, const char* key, int64_t value) {
     if (check_ctx(ctx) || !key) return STORM_HIP_EINVAL;
-    if (!strcmp(key, "variant")) {
-        if (value < -1 || value > 5) {
-            set_error("variant must be -1 (auto) or 0..5");
-            return STORM_HIP_EINVAL;
-        }
-#ifndef STORM_HIP_PROBES
-        if (value == 5) {
-            set_error("variant 5 (wide 32x32x64 strips) is a form of the tools build (`make probes`), not of the shipped library");
-            return STORM_HIP_EINVAL;
-        }
-#endif
-        ctx->variant = (int)value;
-    } else if (!strcmp(key, "probe_bundle")) {
-        if (value != -1 && value != 1 && value != 4) {
-            set_error("probe_bundle must be -1 (auto: 1), 1 (one group of 128 rows per workgroup) or 4 (bundles of four)");
-            return STORM_HIP_EINVAL;
-        }
-        ctx->probe_bundle = (int)value;
-    } else if (!strcmp(key, "sparse_probe")) {
-        if (value < -1 || value > 1) {
-            set_error("sparse_probe must be -1 (auto), 0 (never) or 1 (every eligible column)");
-            return STORM_HIP_EINVAL;
-        }
-        ctx->sparse_probe = (int)value;
-    } else if (!strcmp(key, "result_mailbox")) {
-        ctx->result_mailbox = value != 0;
-    } else if (!strcmp(key, "sync_poll_us")) {
-        if (value < 0 || value > 1000000) {
-            set_error("sync_poll_us: 0 .. 1000000 microseconds");
-            return STORM_HIP_EINVAL;
-        }
-        ctx->sync_poll_us = (int)value;
-    } else if (!strcmp(key, "matrix_lists")) {
-        if (value < -1 || value > 1) {
-            set_error("matrix_lists must be -1 (by density), 0 (never) or 1 (whenever eligible)");
-            return STORM_HIP_EINVAL;
-        }
-        ctx->matrix_lists = (int)value;
-    } else if (!strcmp(key, "matrix_lists_kernel")) {
-        if (value < 0 || value > 2) {
-            set_error("matrix_lists_kernel: 0 (by the row length), 1 (window kernel) or 2 (hash kernel)");
-            return STORM_HIP_EINVAL;
-        }
-        ctx->matrix_lists_kernel = (int)value;
-    } else if (!strcmp(key, "matrix_lists_hash_min_log2")) {
-        if (value < 3 || value > 7) {
-            set_error("matrix_lists_hash_min_log2: 3 .. 7");
-            return STORM_HIP_EINVAL;
-        }
-        ctx->matrix_lists_hash_min_log2 = (int)value;
-    } else if (!strcmp(key, "matrix_lists_debug")) {
-        ctx->matrix_lists_debug = (int)value;
-    } else if (!strcmp(key, "matrix_lists_density")) {
-        if (value < 0 || value > 10000) {
-            set_error("matrix_lists_density: 0 .. 10000 (1/10000 of the dense replica's bits)");
-            return STORM_HIP_EINVAL;
-        }
-        ctx->matrix_lists_permille_x10 = (int)value;
-    } else if (!strcmp(key, "seg_rows")) {
-        if (value < 1 || value > (1 << 20)) {
-            set_error("seg_rows out of range");
-            return STORM_HIP_EINVAL;
-        }
-        ctx->seg_rows = (int)value;
-    } else if (!strcmp(key, "k2_stages_per_item")) {
-        if (value < 1 || value > 65536) {
-            set_error("k2_stages_per_item out of range");
-            return STORM_HIP_EINVAL;
-        }
-        ctx->k2_stages_per_item = (int)value;
-    } else if (!strcmp(key, "k2_max_run")) {
-        if (value < 0 || value > 4096) {
-            set_error("k2_max_run out of range (0 = chosen by the list-scheduling estimate, 1..4096)");
-            return STORM_HIP_EINVAL;
-        }
-        ctx->k2_max_run = (int)value;
-    } else if (!strcmp(key, "k2_ring")) {
-#ifdef STORM_HIP_PROBES
-        if ((value < 3 || value > 5) && (value < 11 || value > 18) && value != 26) {
-            set_error("k2_ring must be 3, 4 or 5 (10 + bits = timing probes)");
-            return STORM_HIP_EINVAL;
-        }
-#else
-        if (value != 4) {
-            set_error("k2_ring: this build ships the 4-deep ring only (other depths and the timing "
-                      "probes: build with STORM_HIP_PROBES, `make probes`)");
-            return STORM_HIP_EINVAL;
-        }
-#endif
-        ctx->k2_ring = (int)value;
-    } else if (!strcmp(key, "k2_shadow_budget_mb")) {
-        if (value < 0 || value > (1 << 22)) {
-            set_error("k2_shadow_budget_mb must be 0 (unbounded) .. 4194304");
-            return STORM_HIP_EINVAL;
-        }
-        ctx->k2_shadow_budget_mb = (int)value;
-        memset(ctx->x4_key, 0, sizeof(ctx->x4_key));
-    } else if (!strcmp(key, "k2_tile_shape")) {
-        if (value != 0 && value != 1 && value != 2 && value != 3 && value != 4 && value != 5 && value != 6 && value != 16 && value != 32) {
-            set_error("k2_tile_shape must be 0 (chosen by the matrix), 5 (both operands as FP4 images in the LDS, 16x16x128 MFMAs), 1, 2 (bit operands inflated in registers), 3 / 4 (B as FP4 images in the LDS, 16x16x128 / 32x32x64 MFMAs), 6 (128 x 128 tiles, k-parts whose sums meet inside the launch), 16 or 32 (FP4 shadow)");
-            return STORM_HIP_EINVAL;
-        }
-#ifndef STORM_HIP_PROBES
-        if (value == 1 || value == 16) {
-            set_error("k2_tile_shape = 1 / 16 (tilebits_kernel, tile16_fp4_kernel) is a form of the tools build (`make probes`), not of the shipped library");
-            return STORM_HIP_EINVAL;
-        }
-#endif
-        ctx->k2_tile_shape = (int)value;
-    } else if (!strcmp(key, "k2_ring_sync")) {
-        ctx->k2_ring_sync = value != 0;
-    } else if (!strcmp(key, "k2_wave_below")) {
-        if (value < 0 || value > (1 << 30)) {
-            set_error("k2_wave_below: 0 (never) .. 2^30 tiles of 256 x 256");
-            return STORM_HIP_EINVAL;
-        }
-        ctx->k2_wave_below = (int)value;
-    } else if (!strcmp(key, "k2_part_slots")) {
-        if (value < 0 || value > 2) {
-            set_error("k2_part_slots must be 0 (by the length of the segments), 1 or 2 per CU");
-            return STORM_HIP_EINVAL;
-        }
-        ctx->k2_part_slots = (int)value;
-    } else if (!strcmp(key, "k2_part_min_chunks")) {
-        if (value < 1 || value > 4096) {
-            set_error("k2_part_min_chunks: 1 .. 4096 chunks of 512 bits");
-            return STORM_HIP_EINVAL;
-        }
-        ctx->k2_part_min_chunks = (int)value;
-    } else if (!strcmp(key, "k2_part_narrow")) {
-        ctx->k2_part_narrow = value != 0;
-    } else if (!strcmp(key, "k2_part_cost_diag")) {
-        if (value < 10 || value > 100) {
-            set_error("k2_part_cost_diag: 10 .. 100 percent of a full tile's chunk");
-            return STORM_HIP_EINVAL;
-        }
-        ctx->k2_part_cost_diag = (int)value;
-    } else if (!strcmp(key, "k2_ring_cost_diag") || !strcmp(key, "k2_ring_cost_ragged")) {
-        if (value < 5 || value > 100) {
-            set_error("%s is a percentage of a full tile's time, 5..100", key);
-            return STORM_HIP_EINVAL;
-        }
-        (key[13] == 'd' ? ctx->k2_ring_cost_diag : ctx->k2_ring_cost_ragged) = (int)value;
-    } else if (!strcmp(key, "k2_tile_cost_diag") || !strcmp(key, "k2_tile_cost_ragged")) {
-        if (value < 5 || value > 100) {
-            set_error("%s is a percentage of a full tile's time, 5..100", key);
-            return STORM_HIP_EINVAL;
-        }
-        (key[13] == 'd' ? ctx->k2_tile_cost_diag : ctx->k2_tile_cost_ragged) = (int)value;
-    } else if (!strcmp(key, "k2_strip_operands")) {
-        if (value < 0 || value > 6) {
-            set_error("k2_strip_operands must be 0 (by size), 1 (bit operands, one item per workgroup), 2 (bit operands, one stream per workgroup), 3 (the same with a ring per wave), 4 (FP4 shadow), 5 (bit operands, FP4 image built in the LDS) or 6 (the same with 512-row A tiles, two halves behind one image)");
-            return STORM_HIP_EINVAL;
-        }
-#ifndef STORM_HIP_PROBES
-        if (value == 1 || value == 3) {
-            set_error("k2_strip_operands = 1 (stripbits_kernel) and 3 (bitwave_kernel) are forms of the tools build (`make probes`), not of the shipped library");
-            return STORM_HIP_EINVAL;
-        }
-#endif
-        ctx->k2_strip_operands = (int)value;
-    } else if (!strcmp(key, "k2_shard_pairs")) {
-        ctx->k2_shard_pairs = value != 0;
-    } else if (!strcmp(key, "k2_matrix_pad")) {
-        ctx->k2_matrix_pad = value < 0 ? -1 : (int)std::min<int64_t>(value, 64);   // chunks of 512 bytes
-    } else if (!strcmp(key, "k2_fold_inline")) {
-        ctx->k2_fold_inline = value < 0 ? -1 : value != 0;
-    } else if (!strcmp(key, "k2_wave_ring")) {
-        if (value != 0 && value != 3 && value != 4 && value != 6 && value != 8) {
-            set_error("k2_wave_ring must be 0 (by occupancy), 3, 4, 6 or 8");
-            return STORM_HIP_EINVAL;
-        }
-        ctx->k2_wave_ring = (int)value;
-    } else if (!strcmp(key, "k2_stream_max_rows")) {
-        if (value < 0 || value > (1ll << 31)) {
-            set_error("k2_stream_max_rows must be 0 .. 2^31");
-            return STORM_HIP_EINVAL;
-        }
-        ctx->k2_stream_max_rows = (int)value;
-    } else if (!strcmp(key, "k2_stream_groups_per_cu")) {
-        if (value < 0 || value > 255) {
-            set_error("k2_stream_groups_per_cu must be 0 (auto) .. 255");
-            return STORM_HIP_EINVAL;
-        }
-        ctx->k2_stream_groups_per_cu = (int)value;
-    } else if (!strcmp(key, "k2_stream_min_piece") || !strcmp(key, "k2_stream_min_run")) {
-        if (value < 1 || value > 4096) {
-            set_error("%s must be 1..4096 stages", key);
-            return STORM_HIP_EINVAL;
-        }
-        (key[14] == 'p' ? ctx->k2_stream_min_piece : ctx->k2_stream_min_run) = (int)value;
-    } else if (!strcmp(key, "k2_stream_w3_1") || !strcmp(key, "k2_stream_w3_2")) {
-        if (value < 10 || value > 1000) {
-            set_error("%s must be 10..1000 percent of the first workgroup's share", key);
-            return STORM_HIP_EINVAL;
-        }
-        (key[13] == '1' ? ctx->k2_stream_w3_1 : ctx->k2_stream_w3_2) = (int)value;
-    } else if (!strcmp(key, "k2_shape")) {
-        if (value != 16 && value != 32) {
-            set_error("k2_shape must be 16 (16x16x128 MFMA) or 32 (32x32x64)");
-            return STORM_HIP_EINVAL;
-        }
-#ifndef STORM_HIP_PROBES
-        if (value == 32) {
-            set_error("k2_shape = 32 (strip_fp4_kernel) is a form of the tools build (`make probes`), not of the shipped library");
-            return STORM_HIP_EINVAL;
-        }
-#endif
-        ctx->k2_shape = (int)value;
-    } else if (!strcmp(key, "keep_shadow")) {
-        ctx->keep_shadow = value != 0;
-        memset(ctx->x4_key, 0, sizeof(ctx->x4_key));
-    } else if (!strcmp(key, "k2_matrix_parts")) {
-        ctx->k2_matrix_parts = value != 0;
-    } else if (!strcmp(key, "k2_matrix_min_part")) {
-        if (value < 4 || value > 4096 || value % 4) {
-            set_error("k2_matrix_min_part: a multiple of 4 in 4 .. 4096 (stages of 128 bits)");
-            return STORM_HIP_EINVAL;
-        }
-        ctx->k2_matrix_min_part = (int)value;
-    } else if (!strcmp(key, "k2_matrix_split")) {
-        ctx->k2_matrix_split = value != 0;
-    } else if (!strcmp(key, "k2_pitch_pad")) {
-        if (value < -1 || value > 65536 || (value > 0 && value % 128 != 0)) {
-            set_error("k2_pitch_pad must be -1 (auto) or a multiple of 128 in 0..65536");
-            return STORM_HIP_EINVAL;
-        }
-        ctx->k2_pitch_pad = (int)value;
-    } else if (!strcmp(key, "k2_lds_pad")) {
-        if (value < 0 || value > 120 * 1024) {
-            set_error("k2_lds_pad must be 0..122880");
-            return STORM_HIP_EINVAL;
-        }
-        ctx->k2_lds_pad = (int)value;
-    } else if (!strcmp(key, "k2_persistent")) {
-#ifndef STORM_HIP_PROBES
-        if (value != 0) {
-            set_error("k2_persistent (strip_fp4_kernel with work queues) is a form of the tools build (`make probes`), not of the shipped library");
-            return STORM_HIP_EINVAL;
-        }
-#endif
-        ctx->k2_persistent = value != 0;
-    } else if (!strcmp(key, "k2_lpt_rounds")) {
-        if (value < 0 || value > 63) {
-            set_error("k2_lpt_rounds must be 0..63");
-            return STORM_HIP_EINVAL;
-        }
-        ctx->k2_lpt_rounds = (int)value;
-    } else if (!strcmp(key, "k2_tail_slices")) {
-        if (value < 0 || value > 255) {
-            set_error("k2_tail_slices must be 0..255");
-            return STORM_HIP_EINVAL;
-        }
-        ctx->k2_tail_slices = (int)value;
-    } else if (!strcmp(key, "k2_tail_run")) {
-        if (value < 1 || value > 4096) {
-            set_error("k2_tail_run must be 1..4096");
-            return STORM_HIP_EINVAL;
-        }
-        ctx->k2_tail_run = (int)value;
-    } else if (!strcmp(key, "k2_debug")) {
-#ifdef STORM_HIP_PROBES
-        ctx->k2_debug = (int)value;
-#else
-        if (value != 0) {
-            set_error("k2_debug: timing probes (wrong results by design) are not in this build "
-                      "(STORM_HIP_PROBES, `make probes`)");
-            return STORM_HIP_EINVAL;
-        }
-#endif
-    } else if (!strcmp(key, "time_kernels")) {
-        // 1: start a new series of bracketed launches; 0: pause (the series is kept for
-        // storm_hip_kernel_time); 2: resume it (bench.py brackets every 4th step at N > 1)
-        ctx->time_kernels = value != 0;
-        if (value == 1) ctx->kernel_events_used = 0;
-    } else if (!strcmp(key, "chunks_per_item")) {
-        if (value < 0 || value > 4096) {
-            set_error("chunks_per_item out of range");
-            return STORM_HIP_EINVAL;
-        }
-        ctx->chunks_per_item = (int)value;
-    } else {
+    const OptionRow* row = find_option(key);
+    if (!row) {
         set_error("unknown option '%s'", key);
         return STORM_HIP_EINVAL;
     }
+    if (row->kind == OptionRow::HOOK) return row->hook(ctx, value);
+    const auto among = [](const std::vector<int64_t>& set, int64_t v) { return std::find(set.begin(), set.end(), v) != set.end(); };
+    const int64_t stored = row->kind == OptionRow::BOOL ? value != 0 : value;
+    if ((row->kind == OptionRow::RANGE && (value < row->lo || value > row->hi || (row->step && value > 0 && value % row->step))) ||
+        (row->kind == OptionRow::SET && !among(row->set, value))) {
+        set_error(row->text, key);
+        return STORM_HIP_EINVAL;
+    }
+    if (!kToolsBuild && among(row->tools_only, stored)) {
+        set_error(row->tools_text, key);
+        return STORM_HIP_EINVAL;
+    }
+    ctx->*(row->member) = (int)stored;
+    if (row->after) row->after(ctx, value);
     return STORM_HIP_OK;
 }
 
 int64_t storm_hip_ctx_get_option(storm_hip_ctx_t* ctx, const char* key) {
     if (check_ctx(ctx) || !key) return -1;
-    if (!strcmp(key, "variant")) return ctx->variant;
+    if (const OptionRow* row = find_option(key)) return ctx->*(row->member);
+    // read-only names
     if (!strcmp(key, "variant_used")) return ctx->variant_used;
-    if (!strcmp(key, "seg_rows")) return ctx->seg_rows;
-    if (!strcmp(key, "result_mailbox")) return ctx->result_mailbox;
-    if (!strcmp(key, "probe_bundle")) return ctx->probe_bundle;
-    if (!strcmp(key, "sync_poll_us")) return ctx->sync_poll_us;
-    if (!strcmp(key, "matrix_lists")) return ctx->matrix_lists;
-    if (!strcmp(key, "matrix_lists_density")) return ctx->matrix_lists_permille_x10;
-    if (!strcmp(key, "chunks_per_item")) return ctx->chunks_per_item;
-    if (!strcmp(key, "k2_stages_per_item")) return ctx->k2_stages_per_item;
-    if (!strcmp(key, "k2_max_run")) return ctx->k2_max_run;
-    if (!strcmp(key, "k2_shape")) return ctx->k2_shape;
-    if (!strcmp(key, "k2_strip_operands")) return ctx->k2_strip_operands;
     if (!strcmp(key, "k2_operands_used")) return ctx->k2_operands_used;
-    if (!strcmp(key, "k2_stream_max_rows")) return ctx->k2_stream_max_rows;
-    if (!strcmp(key, "k2_fold_inline")) return ctx->k2_fold_inline;
-    if (!strcmp(key, "k2_matrix_pad")) return ctx->k2_matrix_pad;
-    if (!strcmp(key, "k2_shard_pairs")) return ctx->k2_shard_pairs;
-    if (!strcmp(key, "k2_ring_sync")) return ctx->k2_ring_sync;
-    if (!strcmp(key, "k2_tile_shape")) return ctx->k2_tile_shape;
-    if (!strcmp(key, "k2_wave_below")) return ctx->k2_wave_below;
-    if (!strcmp(key, "k2_part_slots")) return ctx->k2_part_slots;
-    if (!strcmp(key, "k2_part_min_chunks")) return ctx->k2_part_min_chunks;
-    if (!strcmp(key, "k2_part_cost_diag")) return ctx->k2_part_cost_diag;
-    if (!strcmp(key, "k2_part_narrow")) return ctx->k2_part_narrow;
     if (!strcmp(key, "k2_tile_shape_used")) return ctx->k2_tile_shape_eff;
-    if (!strcmp(key, "k2_stream_w3_1")) return ctx->k2_stream_w3_1;
-    if (!strcmp(key, "k2_stream_w3_2")) return ctx->k2_stream_w3_2;
-    if (!strcmp(key, "k2_shadow_budget_mb")) return ctx->k2_shadow_budget_mb;
     if (!strcmp(key, "n_cus")) return ctx->n_cus;
-    if (!strcmp(key, "probes_build")) {
-#ifdef STORM_HIP_PROBES
-        return 1;
-#else
-        return 0;
-#endif
-    }
-#ifdef STORM_HIP_PROBES
-    if (!strcmp(key, "probes_built")) return 1;
-#else
-    if (!strcmp(key, "probes_built")) return 0;
-#endif
+    if (!strcmp(key, "probes_build") || !strcmp(key, "probes_built")) return kToolsBuild;
     return -1;
 }
 
@@ -1231,19 +1064,12 @@ int storm_hip_matrix_set_rows_from_positions(storm_hip_ctx_t* ctx, storm_hip_mat
     // a hipMalloc / hipFree pair per batch costs more than its copy)
     const size_t off_bytes = ((n_rows + 1) * sizeof(uint64_t) + 255) / 256 * 256;
     const size_t need = off_bytes + n_pos * sizeof(uint32_t);
-    if (need > ctx->positions_capacity) {
-        if (ctx->d_positions) STORM_HIP_TRY(hipFree(ctx->d_positions));
-        ctx->d_positions = nullptr;
-        ctx->positions_capacity = 0;
-        const size_t cap = std::max<size_t>(need + need / 2, 1u << 20);
-        if (hipMalloc(&ctx->d_positions, cap) != hipSuccess) {
-            set_error("hipMalloc for %llu positions failed", (unsigned long long)n_pos);
-            return STORM_HIP_ENOMEM;
-        }
-        ctx->positions_capacity = cap;
-    }
-    uint64_t* d_off = static_cast<uint64_t*>(ctx->d_positions);
-    uint32_t* d_pos = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(ctx->d_positions) + off_bytes);
+    // (it grows by half more than is asked for)
+    if (int rc = ctx->d_positions.ensure(need > ctx->d_positions.capacity ? need + need / 2 : need, "set_rows_from_positions: the staging buffer",
+                                         1u << 20))
+        return rc;
+    uint64_t* d_off = static_cast<uint64_t*>(ctx->d_positions.d);
+    uint32_t* d_pos = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(ctx->d_positions.d) + off_bytes);
     int rc = STORM_HIP_OK;
     if (hipMemcpyAsync(d_off, offsets, (n_rows + 1) * sizeof(uint64_t), hipMemcpyHostToDevice,
                        ctx->stream) != hipSuccess ||
@@ -1767,16 +1593,7 @@ int storm_hip_cross_dense_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_t*
     if (na == 0 || nb == 0) return STORM_HIP_OK;
     STORM_HIP_TRY(hipSetDevice(ctx->device));
     const size_t need = (size_t)na * nb * sizeof(uint32_t);
-    if (need > ctx->band_capacity) {
-        if (ctx->d_band) STORM_HIP_TRY(hipFree(ctx->d_band));
-        ctx->d_band = nullptr;
-        ctx->band_capacity = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&ctx->d_band), need) != hipSuccess) {
-            set_error("cross_dense_matrix: hipMalloc of %zu bytes for the output failed", need);
-            return STORM_HIP_ENOMEM;
-        }
-        ctx->band_capacity = need;
-    }
+    if (int rc = ctx->d_band.ensure(need, "cross_dense_matrix: the output")) return rc;
     if (int rc = storm_hip_cross_dense_matrix_device(ctx, a, b, op, ctx->d_band, nb)) return rc;
     STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(uint32_t), ctx->d_band, nb * sizeof(uint32_t), nb * sizeof(uint32_t), na,
                                    hipMemcpyDeviceToHost, ctx->stream));
@@ -1830,16 +1647,7 @@ int storm_hip_pairw_matrix_band_begin(storm_hip_ctx_t* ctx, const storm_hip_matr
     if (n == 0 || n_band_rows == 0) return STORM_HIP_OK;
     STORM_HIP_TRY(hipSetDevice(ctx->device));
     const size_t need = (size_t)n_band_rows * n * sizeof(uint32_t);
-    if (need > ctx->band_capacity) {
-        if (ctx->d_band) STORM_HIP_TRY(hipFree(ctx->d_band));
-        ctx->d_band = nullptr;
-        ctx->band_capacity = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&ctx->d_band), need) != hipSuccess) {
-            set_error("pairw_matrix_band: hipMalloc of %zu bytes for the output band failed", need);
-            return STORM_HIP_ENOMEM;
-        }
-        ctx->band_capacity = need;
-    }
+    if (int rc = ctx->d_band.ensure(need, "pairw_matrix_band: the output band")) return rc;
     STORM_HIP_TRY(hipMemsetAsync(ctx->d_band, 0, need, ctx->stream));
     if (int rc = launch_pairw_matrix(ctx, m, op, ctx->d_band, n, row0, n_band_rows, false)) return rc;
     STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(uint32_t), ctx->d_band, n * sizeof(uint32_t),

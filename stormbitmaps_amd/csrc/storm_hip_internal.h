@@ -9,19 +9,20 @@
 #include <exception>
 #include <cstring>
 #include <new>
+#include <optional>
 #include <thread>
 #include <utility>
+#include <variant>
 #include <vector>
 
 #include "storm_hip.h"
+#include "storm_hip_plan.h"   // the work-list records, their geometry and the planners (host-only: storm_hip_plan.cpp)
 
 struct storm_hip_ctx_s;
 typedef struct storm_hip_ctx_s storm_hip_ctx_t;
 struct storm_hip_matrix_s;
 
 namespace storm {
-
-void set_error(const char* fmt, ...);
 
 #define STORM_HIP_TRY(expr)                                                                  \
     do {                                                                                     \
@@ -51,11 +52,41 @@ static inline int guarded(const char* what, Fn&& fn) noexcept {
     }
 }
 
+// A grow-only device buffer of the context's workspace, capacity in bytes. ensure() never shrinks and keeps the
+// contents only when it does not reallocate (every caller refills); a failed allocation leaves the buffer empty.
+// Reads as its pointer.
+template <class T>
+struct DevBuf {
+    T* d = nullptr;
+    size_t capacity = 0;
+    operator T*() const { return d; }
+    int ensure(size_t bytes, const char* what, size_t floor_bytes = 0) {
+        if (bytes <= capacity) return STORM_HIP_OK;
+        T* const old = d;
+        d = nullptr;
+        capacity = 0;
+        if (old) STORM_HIP_TRY(hipFree(old));
+        bytes = std::max(bytes, floor_bytes);
+        if (hipMalloc(reinterpret_cast<void**>(&d), bytes) != hipSuccess) {
+            d = nullptr;
+            set_error("%s: hipMalloc of %zu bytes failed", what, bytes);
+            return STORM_HIP_ENOMEM;
+        }
+        capacity = bytes;
+        return STORM_HIP_OK;
+    }
+    void release() {
+        if (d) (void)hipFree(d);
+        d = nullptr;
+        capacity = 0;
+    }
+};
+
 // Geometry of the dense kernel (see DESIGN.md "K1").
 constexpr int kLanes = 64;                           // gfx950 wavefront
 constexpr int kWaves = 4;                            // waves per workgroup
 constexpr int kThreads = kLanes * kWaves;            // 256
-constexpr int kChunkWords = 64;                      // k-chunk: one 64-bit word per lane
+// (kChunkWords = 64, the k-chunk of one 64-bit word per lane: storm_hip_plan.h)
 constexpr int kRowsPerWave = 32;                     // A rows held in VGPRs by one wave
 constexpr int kABlockRows = kWaves * kRowsPerWave;   // 128 A rows per workgroup
 constexpr int kRowPad = 256;                         // allocated rows: a multiple of this, zero beyond n_rows (a strip's A tile)
@@ -102,8 +133,7 @@ struct storm_hip_ctx_s {
     bool stage_used[3] = {false, false, false};
     int stage_next = 0;
     void* h_stage_ring = nullptr;            // pinned staging ring of the sparse arena builder (storm_hip_sparse.hip: Stager), allocated on first use
-    storm::Seg* d_segs = nullptr;            // segment table of the last geometry
-    size_t segs_capacity = 0;
+    storm::DevBuf<storm::Seg> d_segs;        // segment table of the last geometry
     // cache key of d_segs
     uint64_t seg_rows_n = 0;
     uint32_t seg_shard_rank = 0, seg_shard_count = 0, seg_len = 0;
@@ -130,17 +160,16 @@ struct storm_hip_ctx_s {
     // lookup stands for (128). A harness prices every row against the roof of the kernel that ran.
     uint64_t pass_report[4] = {0, 0, 0, 0};
     // K2 (MFMA FP4) state: nibble-expanded shadow of the matrix + item table
-    uint8_t* d_x4 = nullptr;
-    size_t x4_capacity = 0;
-    void* d_items = nullptr;
-    size_t items_capacity = 0;
-    uint64_t items_key[4] = {0, 0, 0, 0};  // rows, stages, shard rank/count, stages per item
-    uint32_t n_items = 0;
+    storm::DevBuf<uint8_t> d_x4;
+    storm::DevBuf<void> d_items;     // one list at a time: MfmaItem records (sum mode, matrix output) or PartItem records (K2h)
+    // the request the list in d_items was planned from (monostate: none)
+    std::variant<std::monostate, storm::TileSumRequest, storm::MatrixTilesRequest, storm::Tile128Request> items_key;
+    uint32_t n_items = 0;            // items of the sum-mode list
+    storm::MatrixPlan matrix_plan;   // ... of the matrix-output list
     void* panel_lists = nullptr;     // work lists of the row panels of storm_hip_pairw_dense_upload (std::vector<PanelList>*)
     hipStream_t copy_stream = nullptr;   // ... its copies travel here while ctx->stream multiplies the panel before
-    void* d_strip_items = nullptr;
-    size_t strip_capacity = 0;
-    uint64_t strip_key[4] = {0, 0, 0, 0};
+    storm::DevBuf<storm::StripItem> d_strip_items;
+    std::optional<storm::StripRequest> strip_key;   // the request the all-pairs list in d_strip_items was planned from
     uint32_t n_strip_items = 0;
     int k2_stages_per_item = 32;
     int k2_max_run = 0;     // strips: B stages per item at most; 0 = 64 / 96 / 128, whichever list schedules shortest (ensure_strip_items)
@@ -159,8 +188,7 @@ struct storm_hip_ctx_s {
     int k2_part_narrow = 1;       // K2h: windows of 16-bit counts where every part of a tile covers fewer than 2^16 bits of k (half the bytes the part that ends the tile has to read)
     int k2_part_cost_diag = 80;   // K2h: what a chunk of a tile on the diagonal costs next to one of a full tile, percent
     uint32_t n_part_items = 0;    // items of the K2h list cached in d_items (items_key)
-    uint32_t* d_tickets = nullptr;   // K2h: one arrival counter per tile (zero between launches)
-    size_t tickets_capacity = 0;
+    storm::DevBuf<uint32_t> d_tickets;   // K2h: one arrival counter per tile (zero between launches)
     bool tickets_dirty = false;   // a launch failed: clear the tickets before the next one
     int k2_tile_shape_eff = 2;  // what the call in flight runs (set by launch_pairw_matrix / launch_square_matrix)
     int k2_ring_sync = 0;   // tilering_kernel: 0 = one s_barrier per stage; 1 = arrival counters in the LDS (waves may drift a stage apart; measured 2 % slower)
@@ -176,8 +204,7 @@ struct storm_hip_ctx_s {
     uint64_t x4_key[4] = {0, 0, 0, 0};
     int k2_matrix_split = 1; // matrix output: cut the last round's tiles along k to fill the CUs
     int k2_matrix_parts = 0;  // ... 0: the parts add into the cleared output with atomics; 1: every part writes its own window and reduce_parts_kernel adds them up (round 5: the tile kernel gets 10 us faster at 1024 rows, the second kernel costs more than the clearing and the atomics did: profiles/r05_k_matrix_sizes.jsonl)
-    uint32_t* d_parts = nullptr;   // the parts' windows (256 x 256 uint32 each)
-    size_t parts_capacity = 0;
+    storm::DevBuf<uint32_t> d_parts;   // the parts' windows (256 x 256 uint32 each)
     int k2_matrix_min_part = 32;  // ... into parts of at least this many 128-bit stages (a multiple of 4)
     int k2_pitch_pad = -1;  // K2/K2s: extra bytes per row of the FP4 shadow (multiple of 128; -1 = auto)
     int k2_lds_pad = 0;     // K2s: bytes of unused dynamic LDS per workgroup (caps workgroups per CU)
@@ -189,21 +216,15 @@ struct storm_hip_ctx_s {
     int time_kernels = 0;
     std::vector<hipEvent_t> kernel_events;  // begin/end alternating
     size_t kernel_events_used = 0;
-    uint32_t* d_band = nullptr;    // device staging of the host-output matrix calls (band x n_rows uint32)
-    size_t band_capacity = 0;
-    void* d_positions = nullptr;   // staging of storm_hip_matrix_set_rows_from_positions: offsets, then positions
-    size_t positions_capacity = 0;
-    uint32_t* d_counts = nullptr;  // row-count scratch of the matrix-output paths
-    size_t counts_capacity = 0;
-    unsigned long long* d_trace = nullptr;  // k2_ring = 18: per-item schedule trace of the strip kernel
-    size_t trace_capacity = 0;
+    storm::DevBuf<uint32_t> d_band;     // device staging of the host-output matrix calls (band x n_rows uint32)
+    storm::DevBuf<void> d_positions;    // staging of storm_hip_matrix_set_rows_from_positions: offsets, then positions
+    storm::DevBuf<uint32_t> d_counts;   // row-count scratch of the matrix-output paths
+    storm::DevBuf<unsigned long long> d_trace;  // k2_ring = 18: per-item schedule trace of the strip kernel
     uint32_t trace_items = 0;
     // K2q (bitstream_kernel): segment table + per-workgroup bounds of the last geometry
-    void* d_bitsegs = nullptr;
-    size_t bitsegs_capacity = 0;
-    void* d_bitfirst = nullptr;
-    size_t bitfirst_capacity = 0;
-    uint64_t bit_key[4] = {0, 0, 0, 0};
+    storm::DevBuf<storm::BitSeg> d_bitsegs;
+    storm::DevBuf<uint32_t> d_bitfirst;
+    std::optional<storm::BitstreamRequest> bit_key;   // the request both were planned from
     uint32_t n_bit_groups = 0, n_bit_segs = 0, bit_max_stages = 0;
     uint64_t bit_stages = 0;
     int k2_stream_groups_per_cu = 0;  // K2q: workgroups per CU (0 = by the length of the stream: 1, 2 or 3)
@@ -221,17 +242,6 @@ namespace storm {
 // K2: all-pairs total of a dense matrix through v_mfma_f32_32x32x64_f8f6f4 (storm_hip_mfma.hip)
 int launch_pairw_mfma(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint32_t shard_rank,
                       uint32_t shard_count, uint64_t* d_total);
-struct RowRange {
-    uint64_t r0, r1;     // rows [r0, r1) form one all-pairs problem; r0 is a multiple of the A tile (256; 512 for wide strips)
-    uint64_t a_end = 0;  // 0: the whole triangle. Otherwise only the pairs with the EARLIER row below a_end (a
-                         // multiple of the A tile from r0, or >= r1): the rows [r0, a_end) among themselves and
-                         // against everything behind them — a block column's bitmap rows, with its list rows,
-                         // which the list-probe kernel pairs with each other, behind them
-    uint64_t back_from = ~0ull;  // != ~0: a row PANEL [back_from, r1) that has just arrived (a multiple of the A tile): only the
-                                 // pairs whose LATER row lies in the panel — every A tile of the panel against all the blocks in
-                                 // front of it (from r0) plus its own triangle (popcount(a & b) is symmetric: the new rows are the
-                                 // stationary operand, the rows already there stream past in long runs)
-};
 int launch_pairw_mfma_ranges(storm_hip_ctx_t* ctx, const uint64_t* X, uint64_t stride_words,
                              uint64_t n_rows_src, uint64_t n_rows_dst,
                              const std::vector<RowRange>& ranges, uint32_t shard_rank,

@@ -953,16 +953,7 @@ int storm_hip_rowlists_pairw_matrix(storm_hip_ctx_t* ctx, const storm_hip_rowlis
     }
     STORM_HIP_TRY(hipSetDevice(ctx->device));
     const size_t need = (size_t)n * n * sizeof(uint32_t);
-    if (need > ctx->band_capacity) {
-        if (ctx->d_band) STORM_HIP_TRY(hipFree(ctx->d_band));
-        ctx->d_band = nullptr;
-        ctx->band_capacity = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&ctx->d_band), need) != hipSuccess) {
-            set_error("rowlists_pairw_matrix: hipMalloc of %zu bytes for the output failed", need);
-            return STORM_HIP_ENOMEM;
-        }
-        ctx->band_capacity = need;
-    }
+    if (int rc = ctx->d_band.ensure(need, "rowlists_pairw_matrix: the output")) return rc;
     STORM_HIP_TRY(hipMemsetAsync(ctx->d_band, 0, need, ctx->stream));
     if (int rc = launch_lists(ctx, l, op, ctx->d_band, n)) return rc;
     STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(uint32_t), ctx->d_band, n * sizeof(uint32_t), n * sizeof(uint32_t), n,
@@ -1072,16 +1063,7 @@ int storm_hip_rowlists_square_matrix(storm_hip_ctx_t* ctx, storm_hip_rowlists_t*
         }
         STORM_HIP_TRY(hipSetDevice(ctx->device));
         const size_t need = (size_t)na * nb * sizeof(uint32_t);
-        if (need > ctx->band_capacity) {
-            if (ctx->d_band) STORM_HIP_TRY(hipFree(ctx->d_band));
-            ctx->d_band = nullptr;
-            ctx->band_capacity = 0;
-            if (hipMalloc(reinterpret_cast<void**>(&ctx->d_band), need) != hipSuccess) {
-                set_error("rowlists_square_matrix: hipMalloc of %zu bytes for the output failed", need);
-                return STORM_HIP_ENOMEM;
-            }
-            ctx->band_capacity = need;
-        }
+        if (int rc = ctx->d_band.ensure(need, "rowlists_square_matrix: the output")) return rc;
         if (int rc = launch_lists_square(ctx, la, lb, op, ctx->d_band, nb)) return rc;
         STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(uint32_t), ctx->d_band, nb * sizeof(uint32_t), nb * sizeof(uint32_t), na,
                                        hipMemcpyDeviceToHost, ctx->stream));

@@ -61,11 +61,6 @@ __device__ unsigned long long g_clock_probe[4];
 #define STORM_CLOCK_END() do {} while (0)
 #endif
 
-static bool timing_env() {
-    static const bool on = getenv("STORM_HIP_TIMING") != nullptr;   // (read once, not per call)
-    return on;
-}
-
 // The end of a synchronous call whose kernels have just been queued: hipStreamSynchronize parks the thread and is woken
 // by an interrupt (5 - 8 us of a call that runs 20 - 40); a few hundred hipStreamQuery polls see the end of a short
 // launch sooner. Option sync_poll_us: how long to poll before parking (0: park at once).
@@ -83,18 +78,10 @@ static hipError_t wait_stream(storm_hip_ctx_t* ctx) {
     return hipStreamSynchronize(ctx->stream);
 }
 
-constexpr int kTile = 256;           // rows per tile side
-constexpr int kStageBytes = 64;      // bytes of one row per stage = 128 nibbles = 128 bits of k
+// (kTile = 256 rows per tile side, kStageBytes = 64, kGroupStages and the item record MfmaItem: storm_hip_plan.h)
 constexpr int kMfmaThreads = 512;
 constexpr int kTileStageBytes = kTile * kStageBytes;  // 16 KiB per operand per stage
 constexpr int kRing = 4;             // LDS stages (4 x 32 KiB = 128 KiB of the CU's 160 KiB)
-constexpr uint32_t kGroupStages = 32;  // multi-GPU ownership unit along k: 32 stages = 64 words
-
-struct MfmaItem {
-    uint16_t I, J;       // row-block indices, I <= J
-    uint32_t stage0;     // first stage of the k-slice
-    uint32_t n_stages;   // stages in this k-slice
-};
 
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -121,7 +108,6 @@ struct ExpandOwn {
     uint32_t rank, count, unit_shift, modulo_units;
 };
 constexpr ExpandOwn kExpandAll = {0u, 1u, 7u, 0u};
-constexpr uint32_t kOwnSlices = 4;  // strips: k-slices per ownership unit
 
 // One thread per 32-bit half word: 16 output bytes, fully coalesced on both sides.
 // Rows >= n_rows_src (padding up to a multiple of 256) are written as zeros. The half words
@@ -426,22 +412,14 @@ __global__ __launch_bounds__(kMfmaThreads, 2) void pairw_fp4_kernel(
 // (N x 128 B = 1.3 MB at N = 10000); the shadow's row pitch is padded off powers of two, so the
 // strips miss L2 for only ~2.6x the shadow's size per launch.
 // ------------------------------------------------------------------------------------------
-constexpr int kStripRowBytes = 128;                      // 256 bits of k as nibbles
-constexpr int kStripBRows = 64;                          // B rows per stage
+// (kStripRowBytes = 128, kStripBRows = 64, kStripWaves = 4, kStripATile = 256: storm_hip_plan.h)
 constexpr int kStripStageBytes = kStripBRows * kStripRowBytes;  // 8 KiB
-constexpr int kStripWaves = 4;                           // waves per workgroup = A tile / 64 rows
-constexpr int kStripATile = 64 * kStripWaves;            // A rows per workgroup (256; 8 waves / 512 rows measured slower)
 constexpr int kStripThreads = 64 * kStripWaves;
 [[maybe_unused]] constexpr int kStripPieces = 8 / kStripWaves;            // LDS-DMA instructions per wave and stage
 static_assert(kStripWaves == 4 || kStripWaves == 8, "a B stage is 8 DMA pieces");
 constexpr int kStripRingDefault = 4;
 
-struct StripItem {
-    uint32_t a_row0;  // first row of the A tile (kStripATile rows, multiple of 64)
-    uint32_t diag;    // 1: the item starts with the stages of its own tile (strict upper part)
-    uint32_t j0, j1;  // then the later B stages: 64-row blocks [j0, j1), walked downwards
-    uint32_t ks;      // k-slice index (128 bytes of the nibble rows each)
-};
+// (the item record StripItem: storm_hip_plan.h)
 
 // kProbe: timing probes with WRONG results: bit 0 no barriers, bit 1 no LDS-DMA, bit 2 no ds_read
 // kMB: 32-row MFMA blocks of A per wave. 2 = 64 rows per wave, 256-row A tile, 4 workgroups per
@@ -1296,20 +1274,9 @@ constexpr int kSbStageBytes = kStripBRows * kSbRowBytes;         // 4 KiB
 // storm.c:1199-1238 (blocked upper triangle), whose order of pairs the cyclic deal does not keep —
 // the total does not depend on it.
 // ------------------------------------------------------------------------------------------
-struct BitSeg {
-    uint32_t a_blk;     // first 64-row block of the A tile (4 blocks; absolute block index)
-    uint32_t ks;        // k-slice: 64 bytes of every bit row
-    uint32_t b_first;   // first later block, relative to range_b0, cyclic over range_nb
-    uint32_t n_b;       // later blocks = stages behind the tile's own four
-    uint32_t range_b0;  // first block of the all-pairs problem (row range) the tile belongs to
-    uint32_t range_nb;  // blocks of that problem: the cyclic order wraps here
-    uint32_t flags;     // bit 0: the tile's own four stages are multiplied (else they only bring A in); bits 8-9: rotation
-    uint32_t pad;
-};
-constexpr uint32_t kBsDiag = 1u;
+// (the segment record BitSeg and kBsDiag: storm_hip_plan.h)
 constexpr int kBsFoldSlots = 64;             // partial sums of this kernel: slots[0 .. 64)
 constexpr int kBsTicket = kSlots + 6;        // arrival counter (behind the strip queue heads; zero between passes)
-constexpr uint32_t kBsMaxStages = 8192;      // per workgroup: accumulators stay below 2^22 (in halves: 2^23)
 constexpr int kBsRing = 8;                   // LDS stages of 4 KiB; ONE barrier serves two stages (four, with a ring
                                              // of 12: faster at N = 512 only, 12.0 against 12.2 us, slower from 2048 up)
 
@@ -1615,9 +1582,8 @@ __global__ __launch_bounds__(kStripThreads, 3) void bitstream_kernel(
 #endif  // STORM_HIP_PROBES
 
 struct PanelList {   // the work list of one row panel of launch_pairw_bits_upload, kept on the device between calls
-    uint64_t key[4] = {0, 0, 0, 0};
-    void* d = nullptr;
-    size_t cap = 0;
+    std::optional<StripRequest> key;   // the request it was planned from
+    DevBuf<StripItem> d;
     uint32_t n = 0;
     hipEvent_t landed = nullptr;
 };
@@ -1625,7 +1591,7 @@ static void release_panel_lists(storm_hip_ctx_t* ctx) {
     auto* lists = static_cast<std::vector<PanelList>*>(ctx->panel_lists);
     if (lists) {
         for (PanelList& l : *lists) {
-            if (l.d) (void)hipFree(l.d);
+            l.d.release();
             if (l.landed) (void)hipEventDestroy(l.landed);
         }
         delete lists;
@@ -1642,459 +1608,81 @@ __global__ void warm_mfma_kernel() {}
 void warm_mfma_code(hipStream_t stream) { hipLaunchKernelGGL(warm_mfma_kernel, dim3(1), dim3(64), 0, stream); }
 
 void release_mfma_state(storm_hip_ctx_t* ctx) {
-    if (ctx->d_x4) (void)hipFree(ctx->d_x4);
-    if (ctx->d_items) (void)hipFree(ctx->d_items);
     release_panel_lists(ctx);
-    if (ctx->d_strip_items) (void)hipFree(ctx->d_strip_items);
-    if (ctx->d_trace) (void)hipFree(ctx->d_trace);
-    if (ctx->d_counts) (void)hipFree(ctx->d_counts);
-    if (ctx->d_band) (void)hipFree(ctx->d_band);
-    if (ctx->d_parts) (void)hipFree(ctx->d_parts);
-    ctx->d_parts = nullptr;
-    ctx->parts_capacity = 0;
-    if (ctx->d_tickets) (void)hipFree(ctx->d_tickets);
-    ctx->d_tickets = nullptr;
-    ctx->tickets_capacity = 0;
-    if (ctx->d_bitsegs) (void)hipFree(ctx->d_bitsegs);
-    if (ctx->d_bitfirst) (void)hipFree(ctx->d_bitfirst);
-    ctx->d_bitsegs = ctx->d_bitfirst = nullptr;
-    ctx->bitsegs_capacity = ctx->bitfirst_capacity = 0;
-    memset(ctx->bit_key, 0, sizeof(ctx->bit_key));
-    ctx->d_band = nullptr;
-    ctx->band_capacity = 0;
-    ctx->d_counts = nullptr;
-    ctx->counts_capacity = 0;
-    ctx->d_trace = nullptr;
-    ctx->trace_capacity = 0;
-    ctx->d_strip_items = nullptr;
-    ctx->strip_capacity = 0;
-    ctx->d_x4 = nullptr;
-    ctx->d_items = nullptr;
-    ctx->x4_capacity = ctx->items_capacity = 0;
+    ctx->d_x4.release();
+    ctx->d_items.release();
+    ctx->d_strip_items.release();
+    ctx->d_trace.release();
+    ctx->d_counts.release();
+    ctx->d_band.release();
+    ctx->d_parts.release();
+    ctx->d_tickets.release();
+    ctx->d_bitsegs.release();
+    ctx->d_bitfirst.release();
+    ctx->bit_key.reset();
 }
 
-// A "range" is a run of rows [r0, r1) of the FP4 shadow that forms one all-pairs problem: the
-// whole matrix for the dense container, one block column of the pool for the sparse one.
-// r0 is a multiple of the A tile (256 rows; 512 for the wide strips) and the rows from r1 up to the
-// next multiple of it are zero.
-static uint64_t ranges_hash(const std::vector<RowRange>& ranges) {
-    uint64_t h = 1469598103934665603ull;
-    for (const RowRange& r : ranges) {
-        h = (h ^ r.r0) * 1099511628211ull;
-        h = (h ^ r.r1) * 1099511628211ull;
-        h = (h ^ r.a_end) * 1099511628211ull;
-        h = (h ^ r.back_from) * 1099511628211ull;
-    }
-    return h;
-}
+// The list buffers start at 4096 records: the lists of small matrices never reallocate them.
+constexpr size_t kItemsFloorBytes = 4096 * sizeof(MfmaItem);
 
+// The summing tile kernel's list (plan_tile_sum, storm_hip_plan.cpp), cached by its request.
 static int ensure_items(storm_hip_ctx_t* ctx, const std::vector<RowRange>& ranges,
                         uint32_t total_stages, uint32_t shard_rank, uint32_t shard_count,
                         bool diag_only) {
-    const uint32_t spi = (uint32_t)std::max(1, ctx->k2_stages_per_item);
-    const uint64_t key[4] = {ranges_hash(ranges), total_stages,
-                             ((uint64_t)shard_rank << 32) | shard_count,
-                             spi | ((uint64_t)ctx->k2_debug << 32) | ((uint64_t)diag_only << 63)};
-    if (ctx->d_items && !memcmp(key, ctx->items_key, sizeof(key))) return STORM_HIP_OK;
-
-    // tiles of every range's upper triangle, in groups of 4 (I) x 8 (J) row blocks
-    std::vector<std::pair<uint16_t, uint16_t>> tiles;
-    for (const RowRange& rg : ranges) {
-        const uint32_t b0 = (uint32_t)(rg.r0 / kTile);
-        const uint32_t nT = (uint32_t)((rg.r1 - rg.r0 + kTile - 1) / kTile);
-        // (a_end: only the tile rows below it)
-        const uint32_t nTa = rg.a_end ? (uint32_t)std::min<uint64_t>(nT, (std::min(rg.a_end, rg.r1) - rg.r0 + kTile - 1) / kTile) : nT;
-        for (uint32_t gi = 0; gi < nTa; gi += 4)
-            for (uint32_t gj = gi / 8 * 8; gj < nT; gj += 8)
-                for (uint32_t i = gi; i < std::min(gi + 4, nTa); ++i)
-                    for (uint32_t j = std::max(gj, i); j < std::min(gj + 8, nT); ++j)
-                        if (!diag_only || i == j)
-                            tiles.emplace_back((uint16_t)(b0 + i), (uint16_t)(b0 + j));
-    }
-    // Sharding is by k-group (kGroupStages stages = 64 words of k), the same ownership rule as
-    // the strips and the expand kernel; k-slices are cut so that none straddles two groups.
-    std::vector<std::pair<uint32_t, uint32_t>> slices;  // (first stage, stages) owned by this shard
-    for (uint32_t g0 = 0; g0 < total_stages; g0 += kGroupStages) {
-        if ((g0 / kGroupStages) % shard_count != shard_rank) continue;
-        const uint32_t g1 = std::min(total_stages, g0 + kGroupStages);
-        for (uint32_t s0 = g0; s0 < g1; s0 += spi) slices.emplace_back(s0, std::min(spi, g1 - s0));
-    }
-    // k-slice major; within a slice, runs of 32 consecutive tiles go to one XCD. Block b runs
-    // on XCD b % 8 (observed round-robin dispatch; only speed depends on it), so each chunk of
-    // 256 tiles (8 runs of 32) is emitted interleaved: position-major, run-minor.
+    const TileSumRequest rq = {ranges_hash(ranges), total_stages, shard_rank, shard_count,
+                               (uint32_t)std::max(1, ctx->k2_stages_per_item), diag_only ? 1u : 0u,
+                               (ctx->k2_debug & 3) == 1 ? 1u : 0u};
+    const TileSumRequest* have = std::get_if<TileSumRequest>(&ctx->items_key);
+    if (ctx->d_items && have && *have == rq) return STORM_HIP_OK;
     std::vector<MfmaItem> items;
-    const size_t n = tiles.size();
-    for (const auto& sl : slices) {
-        const uint32_t s0 = sl.first, ns = sl.second;
-        for (size_t c = 0; c < n; c += 256)
-            for (size_t pos = 0; pos < 32; ++pos)
-                for (size_t x = 0; x < 8; ++x) {
-                    const size_t L = c + x * 32 + pos;
-                    if (L >= n) continue;
-                    if ((ctx->k2_debug & 3) == 1)  // timing probe only: every item reads one tile
-                        items.push_back({tiles[0].first, tiles[0].first, s0, ns});
-                    else
-                        items.push_back({tiles[L].first, tiles[L].second, s0, ns});
-                }
-    }
-    if (items.size() != slices.size() * n) {
-        set_error("K2 item table construction lost tiles (%zu != %zu)", items.size(),
-                  slices.size() * n);
-        return STORM_HIP_EINVAL;
-    }
-    if (items.size() >= (1ull << 31)) {
-        set_error("K2: %zu tile items exceed the grid limit", items.size());
-        return STORM_HIP_EINVAL;
-    }
-    if (items.size() > ctx->items_capacity) {
-        if (ctx->d_items) STORM_HIP_TRY(hipFree(ctx->d_items));
-        ctx->d_items = nullptr;
-        ctx->items_capacity = 0;
-        const size_t cap = std::max<size_t>(items.size(), 4096);
-        STORM_HIP_TRY(hipMalloc(&ctx->d_items, cap * sizeof(MfmaItem)));
-        ctx->items_capacity = cap;
-    }
+    if (int rc = plan_tile_sum(rq, ranges, items)) return rc;
+    ctx->items_key = std::monostate{};
+    if (int rc = ctx->d_items.ensure(items.size() * sizeof(MfmaItem), "K2: the item table", kItemsFloorBytes)) return rc;
     if (!items.empty()) {
         STORM_HIP_TRY(hipMemcpyAsync(ctx->d_items, items.data(), items.size() * sizeof(MfmaItem),
                                      hipMemcpyHostToDevice, ctx->stream));
         STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
     ctx->n_items = (uint32_t)items.size();
-    memcpy(ctx->items_key, key, sizeof(key));
+    ctx->items_key = rq;
     return STORM_HIP_OK;
 }
 
-// Ownership of the strip work among shard_count shards (multi-GPU ranks; reference loop being
-// sharded: storm.c:1199-1238). Two levels:
-//   * whole k-slices (256 bits of every row), in units of 4 (1024 bits = one 128-byte line of the bit
-//     matrix, so that a shard's expansion reads whole lines): the first (n_units / G) * G units go
-//     to shard unit % G, so a shard expands and multiplies only its own columns — 1/G of the O(N*M)
-//     expansion and of the pair work, equal shares whatever N is;
-//   * the remaining slices ("leftover", fewer than 4 G) are cut along the PAIR space: their items
-//     (A tile x run of B blocks) are dealt to the shards longest-first onto the least loaded one
-//     (deterministic, every shard computes the same deal), every shard expands those few slices.
-// Hence any G balances to within one short item per leftover slice (c2 at G = 3: 85 1/3 slices
-// each), and a matrix with fewer slices than shards (M <= 256 * G bits) still splits G ways.
-static inline uint32_t strip_modulo_slices(uint32_t n_kslices, uint32_t shard_count) {
-    return n_kslices / kOwnSlices / shard_count * shard_count * kOwnSlices;  // whole units, a multiple of G
-}
-static inline bool strip_owns_slice(uint32_t ks, uint32_t shard_rank, uint32_t shard_count) {
-    return (ks / kOwnSlices) % shard_count == shard_rank;
-}
-static inline uint32_t strip_item_cost(const StripItem& it, uint32_t per_tile) {
-    return (it.j1 - it.j0) + it.diag * per_tile + 10u;  // stages + ~10 stages' worth of prologue
-}
-
-// Strip items for this shard; the shard's slices are dealt to the 8 XCDs (block b runs on XCD
-// b % 8 — observed, speed only), and inside an XCD's list the items of one slice are consecutive,
-// longest run first.
-struct StripShaping {  // work-list shaping knobs (context options of the same names)
-    int max_run = 128, tail_run = 32, tail_slices = 3, lpt_rounds = 6;
-    int xcd_group = 1;  // consecutive slices that share an XCD (2 for the bit-operand strips: slices 2j, 2j + 1 read the same bits)
-    bool persistent = false, one_slice_probe = false;
-    // Ownership among the shards: false = whole k-slices first, the leftover slices cut along the pair space
-    // (above); true = EVERY slice is cut along the pair space (north_star's literal split: a shard multiplies
-    // its share of the tile pairs over all of k). Option k2_shard_pairs; rehearsed side by side in
-    // tools/bench_shards.py.
-    bool pair_space = false;
-};
-// Pure host computation (no device): the list, in launch order, and for the persistent form the
-// per-XCD queue bounds.
-static void build_strip_items(const StripShaping& sh, const std::vector<RowRange>& ranges,
-                              uint32_t n_kslices, uint32_t shard_rank, uint32_t shard_count,
-                              uint32_t a_tile, std::vector<StripItem>& items,
-                              uint32_t queue_base[8], uint32_t queue_count[8], double* makespan = nullptr,
-                              uint32_t slots_per_xcd = 128) {
-    // stages per item: <= 4096 keeps the f32 accumulators exact; shorter runs trade one more A
-    // load per run for a shorter tail at the end of the launch
-    const uint32_t kMaxRun = (uint32_t)std::min(4096, std::max(1, sh.max_run));
-    const uint32_t kTailRun = (uint32_t)std::min(4096, std::max(1, sh.tail_run));
-    const uint32_t kPerTile = a_tile / kStripBRows;
-    // The slices of this shard, dealt to the XCDs in turn.
-    std::vector<std::vector<uint32_t>> slices_of(8);
-    uint32_t local = 0;
-    const bool pair_mode = sh.pair_space && shard_count > 1;
-    const uint32_t modulo_slices = pair_mode ? n_kslices : strip_modulo_slices(n_kslices, shard_count);
-    const uint32_t xg = (uint32_t)std::max(1, sh.xcd_group);
-    for (uint32_t ks = 0; ks < modulo_slices; ++ks)
-        if (pair_mode || strip_owns_slice(ks, shard_rank, shard_count)) slices_of[(local++ / xg) % 8].push_back(ks);
-    // One slice = every A tile against the B blocks behind it; `max_run` caps the stages per item.
-    std::vector<uint64_t> pair_load(shard_count, 0);  // pair mode: stages dealt to every shard so far
-    auto emit_slice_all = [&](uint32_t ks, uint32_t max_run, std::vector<StripItem>& dst) {
-        // k2_debug & 16 (timing probe, wrong results): every XCD re-reads one k-slice, i.e. the
-        // launch as it would run if nothing ever missed in L2
-        const uint32_t ks_data = sh.one_slice_probe ? ks % 8u : ks;
-        for (const RowRange& rg : ranges) {
-            if (rg.back_from != ~0ull) {   // a row panel that has just arrived: its tiles against everything in front of them
-                const uint32_t blk0 = (uint32_t)(rg.r0 / kStripBRows);
-                for (uint64_t a0 = rg.back_from; a0 < rg.r1; a0 += a_tile) {
-                    const uint32_t a_row0 = (uint32_t)a0, end = (uint32_t)(a0 / kStripBRows);
-                    if (end <= blk0) {
-                        dst.push_back({a_row0, 1, end, end, ks_data});
-                        continue;
-                    }
-                    for (uint32_t j0 = blk0; j0 < end; j0 += max_run)
-                        dst.push_back({a_row0, (uint32_t)(j0 == blk0), j0, std::min(end, j0 + max_run), ks_data});
-                }
-                continue;
-            }
-            // A tiles of a_tile rows from the start of the range (the rows between r1 and
-            // the end of its last A tile are zero: the caller pads ranges accordingly)
-            const uint64_t a_rows = (rg.a_end ? std::min(rg.a_end, rg.r1) : rg.r1) - rg.r0;  // A tiles only below a_end
-            const uint32_t nA = (uint32_t)((a_rows + a_tile - 1) / a_tile);
-            const uint32_t jend = (uint32_t)((rg.r1 + kStripBRows - 1) / kStripBRows);  // absolute
-            for (uint32_t i = 0; i < nA; ++i) {
-                const uint32_t a_row0 = (uint32_t)rg.r0 + i * a_tile;
-                const uint32_t first = a_row0 / (uint32_t)kStripBRows + kPerTile;
-                if (first >= jend) {  // last tile of the range: only its own triangle
-                    dst.push_back({a_row0, 1, first, first, ks_data});
-                    continue;
-                }
-                for (uint32_t j0 = first; j0 < jend; j0 += max_run)
-                    dst.push_back({a_row0, (uint32_t)(j0 == first), j0,
-                                   std::min(jend, j0 + max_run), ks_data});
-            }
-        }
-    };
-    // Every slice holds the same items but for its slice number: the list of one slice is built (and, for the long runs,
-    // sorted longest first) ONCE per run length and copied with the number filled in — built and sorted slice by slice,
-    // three candidate run lengths and the final list cost the first call at the headline shape 1.4 ms of host time, a first
-    // call at 10000 x 524288 twenty times that [r6].
-    const uint32_t kTailLen = std::min(kMaxRun, kTailRun);
-    std::vector<StripItem> proto_main, proto_tail;
-    bool have_main = false, have_tail = false;
-    auto by_length = [&](const StripItem& p, const StripItem& q) {
-        return (p.j1 - p.j0) + p.diag * kPerTile > (q.j1 - q.j0) + q.diag * kPerTile;
-    };
-    auto emit_copy = [&](uint32_t ks, uint32_t max_run, std::vector<StripItem>& dst) {
-        std::vector<StripItem>& proto = max_run == kMaxRun ? proto_main : proto_tail;
-        bool& have = max_run == kMaxRun ? have_main : have_tail;
-        if (!have) {
-            emit_slice_all(0u, max_run, proto);
-            if (max_run == kMaxRun) std::stable_sort(proto.begin(), proto.end(), by_length);
-            have = true;
-        }
-        const uint32_t ks_data = sh.one_slice_probe ? ks % 8u : ks;
-        const size_t at = dst.size();
-        dst.insert(dst.end(), proto.begin(), proto.end());
-        for (size_t k = at; k < dst.size(); ++k) dst[k].ks = ks_data;
-    };
-    // pair mode: this shard's share of the slice — the slice's items, longest first onto the least loaded shard
-    // (every shard walks the slices in the same order and computes the same deal)
-    auto emit_slice = [&](uint32_t ks, uint32_t max_run, std::vector<StripItem>& dst) {
-        if (!pair_mode) return (max_run == kMaxRun || max_run == kTailLen) ? emit_copy(ks, max_run, dst) : emit_slice_all(ks, max_run, dst);
-        std::vector<StripItem> all;
-        emit_slice_all(ks, max_run, all);
-        std::stable_sort(all.begin(), all.end(), [&](const StripItem& p, const StripItem& q) {
-            return strip_item_cost(p, kPerTile) > strip_item_cost(q, kPerTile);
-        });
-        for (const StripItem& it : all) {
-            const uint32_t r = (uint32_t)(std::min_element(pair_load.begin(), pair_load.end()) - pair_load.begin());
-            pair_load[r] += strip_item_cost(it, kPerTile);
-            if (r == shard_rank) dst.push_back(it);
-        }
-    };
-    // An XCD runs its list in order on ~128 workgroup slots. Long items keep the per-item cost
-    // (A fragments, ring fill, diagonal phase) low, but whatever is still running when the list
-    // runs dry sets the tail: with whole-length items the last slices leave most slots idle for
-    // up to one 157-stage item (10 % of the launch at the headline shape, by list-scheduling
-    // simulation and by measurement). So the LAST k2_tail_slices slices of every XCD are cut into
-    // short runs and merged longest-first, which lets the list end on many small items.
-    // leftover slices: short runs, dealt to the shards by longest-processing-time-first
-    std::vector<std::vector<StripItem>> leftover_of(8);
-    if (modulo_slices < n_kslices) {
-        std::vector<uint64_t> load(shard_count, 0);
-        for (uint32_t ks = modulo_slices; ks < n_kslices; ++ks) {
-            std::vector<StripItem> all;
-            emit_slice_all(ks, std::min(kMaxRun, kTailRun), all);
-            std::stable_sort(all.begin(), all.end(), [&](const StripItem& p, const StripItem& q) {
-                return strip_item_cost(p, kPerTile) > strip_item_cost(q, kPerTile);
-            });
-            const uint32_t xcd = (local++ / xg) % 8;  // one slice stays on one XCD's L2
-            for (const StripItem& it : all) {
-                const uint32_t r = (uint32_t)(std::min_element(load.begin(), load.end()) - load.begin());
-                load[r] += strip_item_cost(it, kPerTile);
-                if (r == shard_rank) leftover_of[xcd].push_back(it);
-            }
-        }
-    }
-    const uint32_t kTail = (uint32_t)std::max(0, sh.tail_slices);
-    std::vector<std::vector<StripItem>> per_xcd(8);
-    // (an estimate — `makespan` asked for — is made from the list of XCD 0 alone: the slices are dealt to the XCDs in turn
-    //  from 0, so its list is as long as any; the other seven lists and the launch order are not built)
-    const int n_lists = makespan ? 1 : 8;
-    for (int x = 0; x < n_lists; ++x) {
-        const std::vector<uint32_t>& sl = slices_of[x];
-        const size_t n_main = sl.size() > kTail ? sl.size() - kTail : 0;
-        // Within a slice, longest first: the XCD's dispatcher deals consecutive workgroups to its
-        // shader engines in turn, so a list that alternates long and short items (the two runs of
-        // one A tile) sends all the long ones to the same engines and leaves the others idle
-        // (schedule trace: 60 % of the slots occupied; max_run = 64, 72 or 100 lost 10-25 %).
-        for (size_t k = 0; k < n_main; ++k) {
-            if (!pair_mode) {   // (the copy of the sorted list of one slice)
-                emit_slice(sl[k], kMaxRun, per_xcd[x]);
-                continue;
-            }
-            std::vector<StripItem> one;
-            emit_slice(sl[k], kMaxRun, one);
-            std::stable_sort(one.begin(), one.end(), by_length);
-            per_xcd[x].insert(per_xcd[x].end(), one.begin(), one.end());
-        }
-        std::vector<StripItem> tail;
-        for (size_t k = n_main; k < sl.size(); ++k) emit_slice(sl[k], std::min(kMaxRun, kTailRun), tail);
-        tail.insert(tail.end(), leftover_of[x].begin(), leftover_of[x].end());
-        std::stable_sort(tail.begin(), tail.end(), [&](const StripItem& p, const StripItem& q) {
-            return (p.j1 - p.j0) + p.diag * kPerTile > (q.j1 - q.j0) + q.diag * kPerTile;
-        });
-        per_xcd[x].insert(per_xcd[x].end(), tail.begin(), tail.end());
-        // A short list (a few rounds of the XCD's ~128 slots: small N, or a 1/8 shard) is all
-        // tail: order the whole of it longest-first. The L2 locality that slice-major order buys
-        // is worth 1-2 %, the tail of a 2-round launch a third of its time (N = 2048: the
-        // schedule trace showed the launch draining for 24 of its 66 us).
-        if (per_xcd[x].size() <= (size_t)128 * (size_t)std::max(0, sh.lpt_rounds))
-            std::stable_sort(per_xcd[x].begin(), per_xcd[x].end(),
-                             [&](const StripItem& p, const StripItem& q) {
-                                 return (p.j1 - p.j0) + p.diag * kPerTile > (q.j1 - q.j0) + q.diag * kPerTile;
-                             });
-    }
-    if (makespan) {
-        // List-scheduling estimate of the launch, in stage times: an XCD hands its list, in order, to its workgroup
-        // slots (4 per CU); an item costs its stages + ~5 for the prologue (A rows, two images) + 3 more for the
-        // non-pipelined diagonal phase. Used to choose the run length (k2_max_run = 0).
-        // [r6] Only the list of XCD 0 is walked (above), and of a long list only the last 16 rounds, behind an evenly loaded start: what decides
-        // between the run lengths is the tail. The full walk of all eight lists took 2.5 ms of a first call at the
-        // headline shape (three candidates), 25 ms at 10000 x 524288.
-        auto cost_of = [&](const StripItem& it) { return (double)(it.j1 - it.j0) + (it.diag ? kPerTile + 3.0 : 0.0) + 5.0; };
-        const std::vector<StripItem>& list = per_xcd[0];
-        const size_t n_slots = std::max<uint32_t>(1, slots_per_xcd);
-        const size_t start = list.size() > 16 * n_slots ? list.size() - 16 * n_slots : 0;
-        double before = 0;
-        for (size_t k = 0; k < start; ++k) before += cost_of(list[k]);
-        std::vector<double> slot(n_slots, before / (double)n_slots);  // a min-heap of the slots' free times
-        auto later = [](double p, double q) { return p > q; };
-        for (size_t k = start; k < list.size(); ++k) {
-            std::pop_heap(slot.begin(), slot.end(), later);
-            slot.back() += cost_of(list[k]);
-            std::push_heap(slot.begin(), slot.end(), later);
-        }
-        const double worst = *std::max_element(slot.begin(), slot.end());
-        *makespan = worst;
-        items.clear();
-        return;
-    }
-    items.clear();
-    if (sh.persistent) {  // one contiguous queue per XCD
-        for (int x = 0; x < 8; ++x) {
-            queue_base[x] = (uint32_t)items.size();
-            queue_count[x] = (uint32_t)per_xcd[x].size();
-            items.insert(items.end(), per_xcd[x].begin(), per_xcd[x].end());
-        }
-    } else {  // dispatcher order: block b runs on XCD b % 8
-        size_t longest = 0;
-        for (auto& v : per_xcd) longest = std::max(longest, v.size());
-        for (size_t pos = 0; pos < longest; ++pos)
-            for (int x = 0; x < 8; ++x)
-                if (pos < per_xcd[x].size()) items.push_back(per_xcd[x][pos]);
-    }
-}
-
-// The shaping a pass runs with, from the options alone — NEVER from the calling rank. Where ownership is dealt along
-// the pair space (k2_shard_pairs, and the leftover slices of the default mode) every rank replays the same deal of
-// the same items, so every rank must cut the slices at the same run length: a choice made from one rank's own list
-// gave ranks [64, 96, 96] at N = 6144 / world 3 and pairs were dropped or counted twice. The automatic
-// run length (max_run = 0) is therefore the candidate whose SLOWEST rank schedules shortest; every rank evaluates
-// all ranks' lists and arrives at the same answer. Shared by the device path (ensure_strip_items) and the host-only
-// planner (storm_hip_strip_plan3), so that the plan the CPU tests partition is the plan the GPU launches.
-struct StripOptions {
-    int max_run = 0, tail_run = 32, tail_slices = 3, lpt_rounds = 6;   // the context's defaults (storm_hip_internal.h)
-    int shard_pairs = 0;
-    int n_cus = 256;
-};
-static StripShaping choose_strip_shaping(const StripOptions& o, const std::vector<RowRange>& ranges, uint32_t n_kslices,
-                                         uint32_t shard_count, uint32_t a_tile, int xcd_group) {
-    StripShaping sh;
-    sh.tail_run = o.tail_run;
-    sh.tail_slices = o.tail_slices;
-    sh.lpt_rounds = o.lpt_rounds;
-    sh.xcd_group = xcd_group;
-    sh.pair_space = o.shard_pairs != 0;
-    sh.max_run = o.max_run;
-    if (o.max_run != 0) return sh;
-    // auto: the run length whose list schedules shortest (the tail of the launch decides between them: N = 6144 is
-    // 6 % faster with 64, N = 7168 / 8192 with 96, N = 3072 with 128; tools/archive/sweep_maxrun.py)
-    const uint32_t slots = (uint32_t)std::max(1, o.n_cus / 8 * 4);
-    const bool timing = timing_env();
-    double best = 0;
-    for (int cand : {96, 64, 128}) {
-        StripShaping trial = sh;
-        trial.max_run = cand;
-        double worst = 0;
-        size_t n_items = 0;
-        for (uint32_t r = 0; r < shard_count; ++r) {
-            std::vector<StripItem> tmp;
-            uint32_t qb[8], qc[8];
-            double ms = 0;
-            build_strip_items(trial, ranges, n_kslices, r, shard_count, a_tile, tmp, qb, qc, &ms, slots);
-            worst = std::max(worst, ms);
-            n_items += tmp.size();
-        }
-        if (timing)
-            fprintf(stderr, "[strip plan] max_run %3d: %zu items over %u rank(s), predicted makespan %.0f stages\n", cand,
-                    n_items, shard_count, worst);
-        if (sh.max_run == 0 || worst < best * 0.995) {   // (ties and near-ties go to the earlier candidate)
-            sh.max_run = cand;
-            best = worst;
-        }
-    }
-    return sh;
-}
-static StripOptions strip_options_of(const storm_hip_ctx_t* ctx) {
+// The strip list of an all-pairs pass (plan_strips, storm_hip_plan.cpp), cached by its request: the context's shaping
+// options, the shape and the shard.
+static StripOptions strip_options_of(const storm_hip_ctx_t* ctx, int xcd_group) {
     StripOptions o;
     o.max_run = ctx->k2_max_run;
     o.tail_run = ctx->k2_tail_run;
     o.tail_slices = ctx->k2_tail_slices;
     o.lpt_rounds = ctx->k2_lpt_rounds;
-    o.shard_pairs = ctx->k2_shard_pairs;
+    o.shard_pairs = ctx->k2_shard_pairs != 0;
     o.n_cus = ctx->n_cus;
+    o.xcd_group = xcd_group;
+    o.persistent = ctx->k2_persistent != 0;
+    o.one_slice_probe = (ctx->k2_debug & 16) != 0;
     return o;
 }
 
 static int ensure_strip_items(storm_hip_ctx_t* ctx, const std::vector<RowRange>& ranges,
                               uint32_t n_kslices, uint32_t shard_rank, uint32_t shard_count,
                               uint32_t a_tile, int xcd_group = 1) {
-    const uint64_t key[4] = {ranges_hash(ranges) ^ ((uint64_t)xcd_group << 56) ^ ((uint64_t)(ctx->k2_shard_pairs != 0) << 55), n_kslices,
-                             ((uint64_t)shard_rank << 32) | shard_count,
-                             ((uint64_t)a_tile << 48) | ((uint64_t)(ctx->k2_debug & 16) << 40) |
-                                 ((uint64_t)(ctx->k2_persistent != 0) << 47) |
-                                 ((uint64_t)(ctx->k2_lpt_rounds & 0x3f) << 41) |
-                                 ((uint64_t)(ctx->k2_tail_slices & 0xff) << 32) |
-                                 ((uint64_t)(ctx->k2_tail_run & 0xffff) << 16) |
-                                 (uint64_t)(ctx->k2_max_run & 0xffff)};
-    if (ctx->d_strip_items && !memcmp(key, ctx->strip_key, sizeof(key))) return STORM_HIP_OK;
-    StripShaping sh = choose_strip_shaping(strip_options_of(ctx), ranges, n_kslices, shard_count, a_tile, xcd_group);
-    sh.persistent = ctx->k2_persistent != 0;
-    sh.one_slice_probe = (ctx->k2_debug & 16) != 0;
+    const StripRequest rq = strip_request(strip_options_of(ctx, xcd_group), ranges, n_kslices, shard_rank, shard_count, a_tile);
+    if (ctx->d_strip_items && ctx->strip_key == rq) return STORM_HIP_OK;
+    ctx->strip_key.reset();
     std::vector<StripItem> items;
-    build_strip_items(sh, ranges, n_kslices, shard_rank, shard_count, a_tile, items,
-                      ctx->strip_queue_base, ctx->strip_queue_count);
+    plan_strips(rq, ranges, items, ctx->strip_queue_base, ctx->strip_queue_count);
     if (items.size() >= (1ull << 31)) {
         set_error("K2s: %zu strip items exceed the grid limit", items.size());
         return STORM_HIP_EINVAL;
     }
-    if (items.size() > ctx->strip_capacity) {
-        if (ctx->d_strip_items) STORM_HIP_TRY(hipFree(ctx->d_strip_items));
-        ctx->d_strip_items = nullptr;
-        ctx->strip_capacity = 0;
-        const size_t cap = std::max<size_t>(items.size(), 4096);
-        STORM_HIP_TRY(hipMalloc(&ctx->d_strip_items, cap * sizeof(StripItem)));
-        ctx->strip_capacity = cap;
-    }
+    if (int rc = ctx->d_strip_items.ensure(items.size() * sizeof(StripItem), "K2s: the strip items", 4096 * sizeof(StripItem))) return rc;
     if (!items.empty()) {
         if (int rc_up = upload_bytes(ctx, ctx->d_strip_items, items.data(), items.size() * sizeof(StripItem))) return rc_up;
         STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
     ctx->n_strip_items = (uint32_t)items.size();
-    memcpy(ctx->strip_key, key, sizeof(key));
+    ctx->strip_key = rq;
     return STORM_HIP_OK;
 }
 
@@ -2107,10 +1695,14 @@ static int ensure_strip_items(storm_hip_ctx_t* ctx, const std::vector<RowRange>&
 // (xcd_grouped_tiles): materialised matrix 1.72 ms dense, 1.56 ms with 384 B, 1.99 ms with 128 B
 // (profiles/r02_e_matrix_order_pad.txt). In round 1's row-major tile order it had measured the
 // other way round (1.96 dense, 2.25 padded).
-static uint64_t shadow_pitch(const storm_hip_ctx_t* ctx, uint64_t row_bytes, bool strips) {
-    (void)strips;
+static uint64_t shadow_pitch(const storm_hip_ctx_t* ctx, uint64_t row_bytes) {
     if (ctx->k2_pitch_pad >= 0) return row_bytes + (uint64_t)ctx->k2_pitch_pad;
     return row_bytes + (row_bytes % 1024 == 0 ? 384u : 0u);
+}
+// The FP4 shadow of at least `bytes`; a shadow that moves holds nothing ("keep_shadow").
+static int ensure_shadow(storm_hip_ctx_t* ctx, size_t bytes, const char* what) {
+    if (bytes > ctx->d_x4.capacity) memset(ctx->x4_key, 0, sizeof(ctx->x4_key));
+    return ctx->d_x4.ensure(bytes, what);
 }
 
 // X: bit rows (stride_words per row), n_rows_src of them readable; the FP4 shadow gets
@@ -2144,7 +1736,7 @@ int launch_pairw_mfma_ranges(storm_hip_ctx_t* ctx, const uint64_t* X, uint64_t s
         uint64_t want = 1;  // chunks needed
         if (ctx->k2_shadow_budget_mb > 0) {
             const uint64_t budget = (uint64_t)ctx->k2_shadow_budget_mb << 20;
-            const uint64_t full = rows_alloc * shadow_pitch(ctx, row_bytes, true);
+            const uint64_t full = rows_alloc * shadow_pitch(ctx, row_bytes);
             if (full > budget && n_kslices > 8) want = (full + budget - 1) / budget;
         }
         // the strips address a B stage (64 shadow rows) with 32-bit DMA offsets: a chunk's row pitch
@@ -2159,27 +1751,17 @@ int launch_pairw_mfma_ranges(storm_hip_ctx_t* ctx, const uint64_t* X, uint64_t s
             shadow_row_bytes = (uint64_t)chunk_slices * kStripRowBytes;
         }
     }
-    const uint64_t pitch = shadow_pitch(ctx, shadow_row_bytes, strip_mode != 0);
+    const uint64_t pitch = shadow_pitch(ctx, shadow_row_bytes);
     const size_t x4_bytes = (size_t)rows_alloc * pitch;
     if (n_rows_dst / kTile >= 65535) {
         set_error("K2: too many row blocks");
         return STORM_HIP_EINVAL;
     }
-    if (x4_bytes > ctx->x4_capacity) {
-        if (ctx->d_x4) STORM_HIP_TRY(hipFree(ctx->d_x4));
-        ctx->d_x4 = nullptr;
-        ctx->x4_capacity = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&ctx->d_x4), x4_bytes) != hipSuccess) {
-            set_error("K2: hipMalloc of %zu bytes for the FP4 shadow matrix failed", x4_bytes);
-            return STORM_HIP_ENOMEM;
-        }
-        ctx->x4_capacity = x4_bytes;
-        memset(ctx->x4_key, 0, sizeof(ctx->x4_key));
-    }
+    if (int rc = ensure_shadow(ctx, x4_bytes, "K2: the FP4 shadow matrix")) return rc;
     const uint32_t total_stages = (uint32_t)(row_bytes / kStageBytes);
     if (strips) {
         ctx->n_items = 0;  // the strip items carry the diagonal tiles themselves
-        memset(ctx->items_key, 0xff, sizeof(ctx->items_key));
+        ctx->items_key = std::monostate{};
     } else if (int rc = ensure_items(ctx, ranges, total_stages, shard_rank, shard_count, false)) {
         return rc;
     }
@@ -2218,13 +1800,13 @@ int launch_pairw_mfma_ranges(storm_hip_ctx_t* ctx, const uint64_t* X, uint64_t s
                 hipLaunchKernelGGL(expand_fp4_kernel,
                                    expand_grid(n_rows_dst, stride_words, expand_compact_halves(own, stride_words * 2)),
                                    dim3(256), 0, ctx->stream, X, stride_words, n_src, n_rows_dst,
-                                   reinterpret_cast<uint4*>(ctx->d_x4), own, nib, pitch / 16);
+                                   reinterpret_cast<uint4*>(ctx->d_x4.d), own, nib, pitch / 16);
             } else {
                 const uint64_t h0 = (uint64_t)chunk * chunk_slices * 8u, h1 = h0 + (uint64_t)chunk_slices * 8u;
                 hipLaunchKernelGGL(expand_fp4_kernel,
                                    expand_grid(n_rows_dst, stride_words, expand_compact_halves(own, h1 - h0)),
                                    dim3(256), 0, ctx->stream, X, stride_words, n_src, n_rows_dst,
-                                   reinterpret_cast<uint4*>(ctx->d_x4), own, nib, pitch / 16, h0, h1, h0);
+                                   reinterpret_cast<uint4*>(ctx->d_x4.d), own, nib, pitch / 16, h0, h1, h0);
             }
         }
         STORM_HIP_TRY(hipGetLastError());
@@ -2232,8 +1814,9 @@ int launch_pairw_mfma_ranges(storm_hip_ctx_t* ctx, const uint64_t* X, uint64_t s
         else memset(ctx->x4_key, 0, sizeof(ctx->x4_key));
         if (n_strip > 0) {
             kernel_time_mark(ctx);
-            const StripItem* sit = static_cast<const StripItem*>(ctx->d_strip_items);
+            const StripItem* sit = ctx->d_strip_items;
             const dim3 sgrid(n_strip), sblock(kStripThreads);
+#ifdef STORM_HIP_PROBES   // the other forms of the strips (ring depths, 32x32x64, wide, persistent, timing probes, trace): tools build
             StripQueues queues;
             memcpy(queues.base, ctx->strip_queue_base, sizeof(queues.base));
             memcpy(queues.count, ctx->strip_queue_count, sizeof(queues.count));
@@ -2244,40 +1827,35 @@ int launch_pairw_mfma_ranges(storm_hip_ctx_t* ctx, const uint64_t* X, uint64_t s
             //  k-chunked pass launches the strips several times in front of it, so it runs the plain
             //  form — found by the randomised soak, a second chunk saw exhausted queues)
             const bool persist = ctx->k2_persistent && n_chunks == 1;
-#ifdef STORM_HIP_PROBES
             const int sel = strip_mode == 2 ? 100 + ctx->k2_ring
                                             : (persist && ctx->k2_ring == 4) ? 204
                                             : (persist && ctx->k2_ring == 18) ? 218
                                                                               : ctx->k2_ring;
-#else
-            (void)persist; (void)pgrid; (void)heads; (void)queues;
-            const int sel = 4;  // (the shipped library refuses the options that select the other forms)
-#endif
             switch (sel) {  // ring depth: tuning probe
-#ifdef STORM_HIP_PROBES  // launch cases of the 32x32x64 strips, their timing probes and the schedule trace (inside launch_pairw_mfma_ranges' switch): tools build (make probes)
 #include "../../tools/probes/strip_fp4_32_launch.hip"
-#endif  // STORM_HIP_PROBES
                 default:
-                    // k2_lds_pad: unused dynamic LDS, only to cap the workgroups per CU (tuning)
-#ifdef STORM_HIP_PROBES
                     if (ctx->k2_shape != 16)
                         hipLaunchKernelGGL(strip_fp4_kernel<kStripRingDefault>, sgrid, sblock,
                                            (size_t)ctx->k2_lds_pad, ctx->stream, ctx->d_x4, pitch, sit,
                                            ctx->d_slots);
                     else
-#endif
                         hipLaunchKernelGGL(strip16_fp4_kernel<kStripRingDefault>, sgrid, sblock,
                                            (size_t)ctx->k2_lds_pad, ctx->stream, ctx->d_x4, pitch, sit,
                                            ctx->d_slots);
                     break;
             }
+#else   // (the shipped library refuses the options that select the other forms)
+            // k2_lds_pad: unused dynamic LDS, only to cap the workgroups per CU (tuning)
+            hipLaunchKernelGGL(strip16_fp4_kernel<kStripRingDefault>, sgrid, sblock, (size_t)ctx->k2_lds_pad, ctx->stream,
+                               ctx->d_x4, pitch, sit, ctx->d_slots);
+#endif
             kernel_time_mark(ctx);
             STORM_HIP_TRY(hipGetLastError());
         }
         if (ctx->n_items > 0) {
             kernel_time_mark(ctx);
             const dim3 kgrid(ctx->n_items), block(kMfmaThreads);
-            const MfmaItem* items = static_cast<const MfmaItem*>(ctx->d_items);
+            const MfmaItem* items = static_cast<const MfmaItem*>(ctx->d_items.d);
             switch (ctx->k2_debug & 12) {  // 4 / 8: timing probes without DMA / without MFMA
 #ifdef STORM_HIP_PROBES
                 case 4:
@@ -2317,7 +1895,7 @@ int launch_square_mfma(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
                        const storm_hip_matrix_s* b, uint64_t* d_total) {
     const uint64_t stride_words = a->stride_words;
     const uint64_t row_bytes = stride_words * 32;
-    const uint64_t pitch = shadow_pitch(ctx, row_bytes, true);
+    const uint64_t pitch = shadow_pitch(ctx, row_bytes);
     const uint64_t rows_a = (a->n_rows + kStripATile - 1) / kStripATile * kStripATile;
     const uint64_t rows_b = (b->n_rows + kStripATile - 1) / kStripATile * kStripATile;
     const size_t x4_bytes = (size_t)(rows_a + rows_b) * pitch;
@@ -2325,17 +1903,7 @@ int launch_square_mfma(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
         set_error("square (matrix cores): operand too large for the strip kernel's 32-bit offsets");
         return STORM_HIP_EINVAL;
     }
-    if (x4_bytes > ctx->x4_capacity) {
-        if (ctx->d_x4) STORM_HIP_TRY(hipFree(ctx->d_x4));
-        ctx->d_x4 = nullptr;
-        ctx->x4_capacity = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&ctx->d_x4), x4_bytes) != hipSuccess) {
-            set_error("square: hipMalloc of %zu bytes for the FP4 shadow failed", x4_bytes);
-            return STORM_HIP_ENOMEM;
-        }
-        ctx->x4_capacity = x4_bytes;
-        memset(ctx->x4_key, 0, sizeof(ctx->x4_key));
-    }
+    if (int rc = ensure_shadow(ctx, x4_bytes, "square: the FP4 shadow")) return rc;
     memset(ctx->x4_key, 0, sizeof(ctx->x4_key));  // the shadow is about to hold [A ; B]
     const uint32_t n_kslices = (uint32_t)(row_bytes / kStripRowBytes);
     const uint32_t kMaxRun = (uint32_t)std::min(4096, ctx->k2_max_run > 0 ? ctx->k2_max_run : 128);   // (0 = auto: the rectangle has no tail problem)
@@ -2350,16 +1918,9 @@ int launch_square_mfma(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
         set_error("square: %zu strip items exceed the grid limit", items.size());
         return STORM_HIP_EINVAL;
     }
-    if (items.size() > ctx->strip_capacity) {
-        if (ctx->d_strip_items) STORM_HIP_TRY(hipFree(ctx->d_strip_items));
-        ctx->d_strip_items = nullptr;
-        ctx->strip_capacity = 0;
-        const size_t cap = std::max<size_t>(items.size(), 4096);
-        STORM_HIP_TRY(hipMalloc(&ctx->d_strip_items, cap * sizeof(StripItem)));
-        ctx->strip_capacity = cap;
-    }
-    memset(ctx->strip_key, 0xff, sizeof(ctx->strip_key));  // the cached all-pairs table is gone
+    ctx->strip_key.reset();  // the cached all-pairs table is gone
     ctx->n_strip_items = 0;
+    if (int rc = ctx->d_strip_items.ensure(items.size() * sizeof(StripItem), "square: the strip items", 4096 * sizeof(StripItem))) return rc;
     if (int rc_up = upload_bytes(ctx, ctx->d_strip_items, items.data(), items.size() * sizeof(StripItem))) return rc_up;
     STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));  // `items` leaves scope
     for (int side = 0; side < 2; ++side) {
@@ -2368,7 +1929,7 @@ int launch_square_mfma(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
         const dim3 grid = expand_grid(rows_dst, stride_words);
         hipLaunchKernelGGL(expand_fp4_kernel, grid, dim3(256), 0, ctx->stream, m->d,
                            stride_words, std::min<uint64_t>(m->n_rows_pad, rows_dst), rows_dst,
-                           reinterpret_cast<uint4*>(ctx->d_x4 + (side ? rows_a * pitch : 0)),
+                           reinterpret_cast<uint4*>(ctx->d_x4.d + (side ? rows_a * pitch : 0)),
                            kExpandAll, 2u, pitch / 16);
         STORM_HIP_TRY(hipGetLastError());
     }
@@ -2376,12 +1937,12 @@ int launch_square_mfma(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
     if (ctx->k2_shape != 16)
         hipLaunchKernelGGL(strip_fp4_kernel<kStripRingDefault>, dim3((uint32_t)items.size()),
                            dim3(kStripThreads), 0, ctx->stream, ctx->d_x4, pitch,
-                           static_cast<const StripItem*>(ctx->d_strip_items), ctx->d_slots);
+                           ctx->d_strip_items.d, ctx->d_slots);
     else
 #endif
         hipLaunchKernelGGL(strip16_fp4_kernel<kStripRingDefault>, dim3((uint32_t)items.size()),
                            dim3(kStripThreads), 0, ctx->stream, ctx->d_x4, pitch,
-                           static_cast<const StripItem*>(ctx->d_strip_items), ctx->d_slots);
+                           ctx->d_strip_items.d, ctx->d_slots);
     STORM_HIP_TRY(hipGetLastError());
     ctx->last_info[0] = (uint32_t)items.size();
     return launch_fold_slots(ctx, d_total);
@@ -2389,16 +1950,7 @@ int launch_square_mfma(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
 
 // Per-row set-bit counts for the OR / XOR epilogues: a scratch buffer kept in the context.
 static int ensure_counts_scratch(storm_hip_ctx_t* ctx, size_t n, uint32_t** out) {
-    if (n * sizeof(uint32_t) > ctx->counts_capacity) {
-        if (ctx->d_counts) STORM_HIP_TRY(hipFree(ctx->d_counts));
-        ctx->d_counts = nullptr;
-        ctx->counts_capacity = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&ctx->d_counts), n * sizeof(uint32_t)) != hipSuccess) {
-            set_error("matrix output: hipMalloc of the row-count scratch failed");
-            return STORM_HIP_ENOMEM;
-        }
-        ctx->counts_capacity = n * sizeof(uint32_t);
-    }
+    if (int rc = ctx->d_counts.ensure(n * sizeof(uint32_t), "matrix output: the row-count scratch")) return rc;
     *out = ctx->d_counts;
     return STORM_HIP_OK;
 }
@@ -2463,106 +2015,31 @@ __global__ __launch_bounds__(256) void reduce_parts_kernel(const MfmaItem* __res
     }
 }
 
-struct MatrixPlan {  // item table of one matrix-output launch, already in ctx->d_items
-    uint32_t n_items = 0;  // workgroups to launch
-    uint32_t n_full = 0;   // items [0, n_full) are whole tiles; the rest are k-parts that add into a cleared window
-    uint32_t n_cut = 0;    // tiles that are cut into parts: behind the items the table holds one record per such tile
-                           // (what zero_tiles_kernel walks: one workgroup column per window, not one per part)
-};
-
-// Builds and uploads the item table (before the caller launches anything else, so that the one
-// host wait for the pageable upload does not sit between the kernels). `cost` (optional, one per
-// tile, 1 = a full tile): the tiles beyond the last full round of workgroups are cut along k into
-// parts of about equal cost, as many as fill the CUs — a short tile (diagonal or ragged under
-// tilebits8_kernel) into fewer parts than a full one.
-static int plan_matrix_tiles(storm_hip_ctx_t* ctx, const std::vector<std::pair<uint16_t, uint16_t>>& tiles,
-                             uint32_t total_stages, MatrixPlan* plan, const std::vector<float>* cost = nullptr) {
-    const size_t slots = (size_t)std::max(1, ctx->n_cus);
-    size_t leftover = ctx->k2_matrix_split ? tiles.size() % slots : 0;
-    // f32 accumulators hold exact integers below 2^24: an item may span at most kMaxExactStages
-    // stages (128 bits each). Rows of 2^24 bits and more are therefore cut along k for EVERY tile;
-    // the parts add into the cleared window like the parts of the last round do.
-    constexpr uint32_t kMaxExactStages = (1u << 24) / 128u - 1u;
-    uint32_t min_parts = 1;
-    if (total_stages > kMaxExactStages) {
-        leftover = tiles.size();
-        min_parts = (total_stages + kMaxExactStages - 1) / kMaxExactStages;
+// Plans (plan_matrix_tiles, storm_hip_plan.cpp) and uploads the item table of a matrix-output launch, before the caller
+// launches anything else, so that the one host wait for the pageable upload does not sit between the kernels.
+// The table of the previous call is still on the device when this call asks for the same tiles cut the same way (a
+// repeated call, the bands of one output): no upload, and no host wait in front of the kernels.
+static int ensure_matrix_tiles(storm_hip_ctx_t* ctx, MatrixTilesRequest&& rq, MatrixPlan* plan) {
+    rq.n_cus = (uint32_t)std::max(1, ctx->n_cus);
+    rq.split = ctx->k2_matrix_split;
+    rq.min_part = ctx->k2_matrix_min_part;
+    const MatrixTilesRequest* have = std::get_if<MatrixTilesRequest>(&ctx->items_key);
+    if (ctx->d_items && have && *have == rq) {
+        *plan = ctx->matrix_plan;
+        return STORM_HIP_OK;
     }
-    const size_t n_full = tiles.size() - leftover;
-    const uint32_t max_parts = std::max(min_parts, total_stages / (uint32_t)ctx->k2_matrix_min_part);
-    auto cost_of = [&](size_t t) { return cost ? std::max(0.05f, (*cost)[t]) : 1.0f; };
-    double left_cost = 0;
-    for (size_t t = n_full; t < tiles.size(); ++t) left_cost += cost_of(t);
-    const double per_part = left_cost / (double)slots;  // what one CU should get of the last round
-    std::vector<uint32_t> parts_of(leftover, 1);
-    size_t n_parts = 0;
-    for (size_t t = n_full; t < tiles.size(); ++t) {
-        const double want = per_part > 0 ? cost_of(t) / per_part : 1.0;
-        n_parts += parts_of[t - n_full] = std::min(max_parts, std::max(min_parts, (uint32_t)want));
-    }
-    // rounding down leaves CUs without a part: give them to the tiles whose parts are longest (never
-    // more parts than CUs — a 257th item would wait for a whole part)
-    while (min_parts == 1 && n_parts < slots && leftover > 0) {
-        size_t best = leftover;
-        double longest = 0;
-        for (size_t i = 0; i < leftover; ++i) {
-            const double len = cost_of(n_full + i) / parts_of[i];
-            if (parts_of[i] < max_parts && len > longest) longest = len, best = i;
-        }
-        if (best == leftover) break;
-        ++parts_of[best];
-        ++n_parts;
-    }
-    // The table of the previous call is still on the device when this call asks for the same tiles
-    // cut the same way (a repeated call, the bands of one output): no upload, and no host wait in
-    // front of the kernels. The key lives in items_key, which the summing tile kernel's own table
-    // (another key layout) overwrites.
-    uint64_t h = 0xcbf29ce484222325ull;
-    auto mix = [&h](uint64_t v) { h = (h ^ v) * 0x100000001b3ull; };
-    for (const auto& t : tiles) mix(((uint64_t)t.first << 16) | t.second);
-    mix(tiles.size());
-    size_t n_items = n_full;
-    for (uint32_t p : parts_of) {
-        mix(p);
-        n_items += p;
-    }
-    mix((uint64_t)ctx->k2_matrix_min_part);
-    const uint64_t key[4] = {h, 0x4d504c414e000000ull ^ total_stages, ((uint64_t)n_items << 32) | (uint64_t)n_full,
-                             (uint64_t)leftover};
-    plan->n_items = (uint32_t)n_items;
-    plan->n_full = (uint32_t)n_full;
-    plan->n_cut = (uint32_t)leftover;
-    if (ctx->d_items && !memcmp(key, ctx->items_key, sizeof(key))) return STORM_HIP_OK;
     std::vector<MfmaItem> items;
-    items.reserve(n_items);
-    for (size_t t = 0; t < n_full; ++t) items.push_back({tiles[t].first, tiles[t].second, 0, total_stages});
-    for (size_t t = n_full; t < tiles.size(); ++t) {
-        const uint32_t parts = parts_of[t - n_full];
-        for (uint32_t p = 0; p < parts; ++p) {
-            // cuts on multiples of 4 stages: the 16x16 kernel's stage is two of these (128 bytes of
-            // an FP4 row), the bit-operand kernels' four (512 bits)
-            const uint32_t s0 = (uint32_t)((uint64_t)(total_stages / 4) * p / parts) * 4u;
-            const uint32_t s1 = (uint32_t)((uint64_t)(total_stages / 4) * (p + 1) / parts) * 4u;
-            items.push_back({tiles[t].first, tiles[t].second, s0, s1 - s0});
-        }
-    }
-    for (size_t t = n_full; t < tiles.size(); ++t) items.push_back({tiles[t].first, tiles[t].second, 0u, 0u});   // the cut tiles once more: the windows to clear
+    plan_matrix_tiles(rq, items, plan);
     // the context's item buffer (shared with the tile kernel's sum mode, whose cached table is
     // dropped here); hipMalloc / hipFree per call would cost more than the kernel's tail
-    if (items.size() > ctx->items_capacity) {
-        if (ctx->d_items) STORM_HIP_TRY(hipFree(ctx->d_items));
-        ctx->d_items = nullptr;
-        ctx->items_capacity = 0;
-        const size_t cap = std::max<size_t>(items.size(), 4096);
-        STORM_HIP_TRY(hipMalloc(&ctx->d_items, cap * sizeof(MfmaItem)));
-        ctx->items_capacity = cap;
-    }
-    memset(ctx->items_key, 0xff, sizeof(ctx->items_key));
+    ctx->items_key = std::monostate{};
     ctx->n_items = 0;
+    if (int rc = ctx->d_items.ensure(items.size() * sizeof(MfmaItem), "matrix output: the item table", kItemsFloorBytes)) return rc;
     STORM_HIP_TRY(hipMemcpyAsync(ctx->d_items, items.data(), items.size() * sizeof(MfmaItem),
                                  hipMemcpyHostToDevice, ctx->stream));
     STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));  // `items` is pageable and leaves scope
-    memcpy(ctx->items_key, key, sizeof(key));
+    ctx->matrix_plan = *plan;
+    ctx->items_key = std::move(rq);
     return STORM_HIP_OK;
 }
 
@@ -2577,7 +2054,7 @@ static int run_matrix_tiles(storm_hip_ctx_t* ctx, const MatrixPlan& plan, uint64
                             uint32_t n_cols = 0, bool sync = true, const TileOperands* bits = nullptr) {
     if (n_cols == 0) n_cols = n_rows;
     if (!bits) memset(ctx->x4_key, 0, sizeof(ctx->x4_key));  // callers rebuilt the shadow in the tile layout
-    const MfmaItem* d_items = static_cast<const MfmaItem*>(ctx->d_items);
+    const MfmaItem* d_items = static_cast<const MfmaItem*>(ctx->d_items.d);
     // [r5] option k2_matrix_parts: the k-parts of the tile kernels that ship write their own windows and a second kernel
     // adds them up (no clearing, no atomics); otherwise — and for the other forms, and for part lists beyond 1 GiB of
     // windows — the parts add into the cleared output
@@ -2586,13 +2063,8 @@ static int run_matrix_tiles(storm_hip_ctx_t* ctx, const MatrixPlan& plan, uint64
     if (n_split && bits && (ctx->k2_tile_shape_eff == 2 || ctx->k2_tile_shape_eff == 5) && ctx->k2_matrix_parts &&
         (size_t)n_split * kTile * kTile * sizeof(uint32_t) <= ((size_t)1 << 30)) {
         const size_t need = (size_t)n_split * kTile * kTile * sizeof(uint32_t);
-        if (need > ctx->parts_capacity) {
-            if (ctx->d_parts) (void)hipFree(ctx->d_parts);
-            ctx->d_parts = nullptr;
-            ctx->parts_capacity = 0;
-            if (hipMalloc(reinterpret_cast<void**>(&ctx->d_parts), need) == hipSuccess) ctx->parts_capacity = need;
-        }
-        if (ctx->parts_capacity >= need) d_parts = ctx->d_parts;   // (no memory for the windows: the atomics still work)
+        if (ctx->d_parts.ensure(need, "matrix output: the k-parts' windows") == STORM_HIP_OK)
+            d_parts = ctx->d_parts;   // (no memory for the windows: the atomics still work)
     }
     if (n_split && !d_parts)
         hipLaunchKernelGGL(zero_tiles_kernel, dim3(plan.n_cut, kTile / 16), dim3(256), 0,
@@ -2645,34 +2117,6 @@ static int run_matrix_tiles(storm_hip_ctx_t* ctx, const MatrixPlan& plan, uint64
     return STORM_HIP_OK;
 }
 
-// Launch order of write-mode tiles for L2 reuse. A tile item streams 8 MiB per operand at the
-// headline shape (256 rows x all of k), twice an XCD's L2: in row-major order the 32 tiles an
-// XCD works on at a time share their A rows and nothing else, and the kernel fetched 12.6 GB per
-// launch from beyond L2 (47 % of its L2 requests missed; it ran at the HBM rate with the matrix
-// pipe 44 % busy: profiles/r02_d_*). Here the tiles [i0, i1) x [j0, j1) (upper triangle only when
-// `triangle`) are cut into groups of 4 x 8, group g goes to XCD g % 8 (block b runs on XCD b % 8:
-// observed, speed only), so the 32 workgroups of an XCD — which start together and advance along k
-// at the same pace — fetch 12 row-block slices per k-stage instead of 33.
-static void xcd_grouped_tiles(uint32_t i0, uint32_t i1, uint32_t j0, uint32_t j1, bool triangle,
-                              std::vector<std::pair<uint16_t, uint16_t>>& out) {
-    std::vector<std::vector<std::pair<uint16_t, uint16_t>>> per_xcd(8);
-    uint32_t g = 0;
-    for (uint32_t gi = i0; gi < i1; gi += 4)
-        for (uint32_t gj = triangle ? std::max(j0, gi / 8 * 8) : j0; gj < j1; gj += 8) {
-            std::vector<std::pair<uint16_t, uint16_t>>& dst = per_xcd[g % 8];
-            const size_t before = dst.size();
-            for (uint32_t i = gi; i < std::min(gi + 4, i1); ++i)
-                for (uint32_t j = std::max(gj, triangle ? i + 1 : gj); j < std::min(gj + 8, j1); ++j)
-                    dst.emplace_back((uint16_t)i, (uint16_t)j);
-            if (dst.size() != before) ++g;
-        }
-    size_t longest = 0;
-    for (auto& v : per_xcd) longest = std::max(longest, v.size());
-    for (size_t pos = 0; pos < longest; ++pos)
-        for (int x = 0; x < 8; ++x)
-            if (pos < per_xcd[x].size()) out.push_back(per_xcd[x][pos]);
-}
-
 // ---- K2h (tile128_kernel): 128 x 128 tiles for matrices of few 256 x 256 tiles, k-parts whose sums meet inside the launch ----
 // Eligible: bit operands, and a 128-row window within the 32-bit buffer offsets. `tiles256` = what the 256 x 256
 // decomposition would launch; k2_tile_shape = 6 forces, 0 takes K2h below k2_wave_below tiles.
@@ -2682,97 +2126,8 @@ static bool choose_tile128(const storm_hip_ctx_t* ctx, uint64_t tiles256, uint64
     return ctx->k2_tile_shape == 0 && tiles256 < (uint64_t)ctx->k2_wave_below;
 }
 
-// The item list of a K2h launch. An item is one part of one tile; a tile of several parts has its sums meet in the launch
-// (tile128_kernel). The chip offers `slots` places for workgroups, one or two per CU:
-//   * whole rounds of tiles (slots tiles each) stay whole;
-//   * the tiles beyond the last whole round — all of them where there are fewer tiles than slots — are cut along k into
-//     EQUAL parts, together as many as there are slots: a tile gets its share of the slots rounded down, the slots left
-//     over go to the tiles whose parts are longest (the longest part ends the launch; cutting the chunk stream at equal
-//     distances across the tile boundaries leaves crumbs that must join a neighbour, and the parts so lengthened — 28
-//     chunks where 18 were due at 1024 rows — ended the launch);
-//   * one or two slots per CU: whichever loads a CU less, counting what an item costs besides its chunks.
-// The tiles on the diagonal come last (they are the ones cut: beside a second workgroup their chunks are cheaper — one wave
-// idle, one at three blocks of four — alone on a CU they take as long as any). Items longest first: the dispatcher hands
-// the short ones to the slots that end first. Pure host computation.
-struct Tile128Plan {
-    std::vector<PartItem> items;
-    uint32_t n_tiles = 0, n_windows = 0;
-};
-static void plan_tile128(uint32_t ia0, uint32_t ia1, uint32_t jb0, uint32_t jb1, bool triangle, uint32_t total_stages,
-                         uint32_t n_cus, int slots_per_cu, int min_chunks, int diag_cost_pct, bool narrow_windows,
-                         Tile128Plan* plan) {
-    struct T { uint16_t I, J; bool diag; };
-    std::vector<T> tiles;
-    // groups of 4 x 8 neighbouring tiles first (they share rows), the tiles on the diagonal last
-    for (int pass = 0; pass < 2; ++pass)
-        for (uint32_t gi = ia0; gi < ia1; gi += 4)
-            for (uint32_t gj = jb0; gj < jb1; gj += 8)
-                for (uint32_t i = gi; i < std::min(gi + 4, ia1); ++i)
-                    for (uint32_t j = gj; j < std::min(gj + 8, jb1); ++j) {
-                        if (triangle && j < i) continue;
-                        const bool diag = triangle && j == i;
-                        if (diag != (pass == 1)) continue;
-                        tiles.push_back({(uint16_t)i, (uint16_t)j, diag});
-                    }
-    const uint32_t nC = total_stages / 4u;
-    plan->n_tiles = (uint32_t)tiles.size();
-    plan->n_windows = 0;
-    plan->items.clear();
-    if (tiles.empty() || nC == 0) return;
-    constexpr uint32_t kMaxExactChunks = (1u << 24) / 512u - 1u;   // f32 accumulators: an item stays below 2^24 bits of k
-    constexpr double kItemChunks = 5.0;                             // what an item costs besides its chunks, in chunks
-    min_chunks = std::max(min_chunks, (int)(nC / 32000u) + 1);      // (a tile has fewer than 2^15 parts: PartItem::part)
-    const uint32_t min_parts = (nC + kMaxExactChunks - 1) / kMaxExactChunks;
-    const uint32_t max_parts = std::max(min_parts, nC / (uint32_t)min_chunks);
-    const size_t nT = tiles.size();
-    std::vector<uint32_t> parts_of(nT), best_parts;
-    double best_load = 0;
-    for (int spc = 1; spc <= 2; ++spc) {
-        if (slots_per_cu > 0 && spc != slots_per_cu) continue;
-        const size_t slots = (size_t)n_cus * spc;
-        const double dcost = spc >= 2 ? diag_cost_pct / 100.0 : 1.0;
-        auto cost_of = [&](size_t t) { return tiles[t].diag ? dcost : 1.0; };
-        const size_t n_whole = min_parts > 1 ? 0 : nT / slots * slots;
-        std::fill(parts_of.begin(), parts_of.end(), 1u);
-        double rest = 0;
-        for (size_t t = n_whole; t < nT; ++t) rest += cost_of(t) * nC;
-        const double seg = rest / (double)slots;
-        size_t n_items = n_whole;
-        for (size_t t = n_whole; t < nT; ++t)
-            n_items += parts_of[t] = std::min(max_parts, std::max(min_parts, (uint32_t)(cost_of(t) * nC / std::max(seg, 1e-9))));
-        while (n_items < n_whole + slots) {   // the slots left over: to the tiles whose parts are longest
-            size_t best = nT;
-            double longest = 0;
-            for (size_t t = n_whole; t < nT; ++t) {
-                const double len = cost_of(t) * nC / parts_of[t];
-                if (parts_of[t] < max_parts && len > longest) longest = len, best = t;
-            }
-            if (best == nT) break;
-            ++parts_of[best];
-            ++n_items;
-        }
-        double longest = 0;
-        for (size_t t = n_whole; t < nT; ++t) longest = std::max(longest, cost_of(t) * std::ceil((double)nC / parts_of[t]));
-        // a CU's load: its slots' whole tiles and one part each, and what its items cost besides
-        const double load = spc * ((double)(n_whole / slots) * nC + longest) + kItemChunks * (double)n_items / n_cus;
-        if (best_parts.empty() || load < best_load) best_load = load, best_parts = parts_of;
-    }
-    for (uint32_t t = 0; t < nT; ++t) {
-        const uint32_t np = best_parts[t];
-        // windows of 16-bit counts while every part of the tile stays below 2^16 bits of k (127 chunks)
-        const uint16_t narrow = (np > 1 && (nC + np - 1) / np <= 127u && narrow_windows) ? kThNarrow : (uint16_t)0;
-        for (uint32_t p = 0; p < np; ++p) {
-            const uint32_t c0 = (uint32_t)((uint64_t)nC * p / np), c1 = (uint32_t)((uint64_t)nC * (p + 1) / np);
-            plan->items.push_back({tiles[t].I, tiles[t].J, c0 * 4u, (c1 - c0) * 4u, t, np > 1 ? plan->n_windows : 0u,
-                                   (uint16_t)((uint16_t)p | narrow), (uint16_t)np});
-        }
-        if (np > 1) plan->n_windows += np;
-    }
-    std::stable_sort(plan->items.begin(), plan->items.end(),
-                     [](const PartItem& a, const PartItem& b) { return a.n_stages > b.n_stages; });
-}
-
-// Uploads the list (cached by its key while the same call repeats) and launches tile128_kernel.
+// Plans the K2h list (plan_tile128, storm_hip_plan.cpp; cached by its request while the same call repeats), uploads it
+// and launches tile128_kernel.
 static int run_tile128(storm_hip_ctx_t* ctx, uint32_t ia0, uint32_t ia1, uint32_t jb0, uint32_t jb1, bool triangle,
                        uint32_t total_stages, const TileOperands& ops, uint32_t* d_out, uint64_t ld, uint32_t n_rows,
                        const uint32_t* d_counts, uint32_t and_weight, uint32_t j_base, uint32_t j_count, uint32_t i_lo,
@@ -2781,64 +2136,40 @@ static int run_tile128(storm_hip_ctx_t* ctx, uint32_t ia0, uint32_t ia1, uint32_
         set_error("pairw_matrix: too many row blocks");
         return STORM_HIP_EINVAL;
     }
-    const uint64_t key[4] = {((uint64_t)ia0 << 32) | ia1, ((uint64_t)jb0 << 32) | jb1,
-                             0x4b32680000000000ull ^ ((uint64_t)(uint32_t)ctx->k2_part_slots << 36) ^
-                                 ((uint64_t)(uint32_t)ctx->k2_part_min_chunks << 24) ^ total_stages,
-                             (triangle ? 1ull : 2ull) | ((uint64_t)(uint32_t)ctx->k2_part_cost_diag << 8) |
-                                 ((uint64_t)(ctx->k2_part_narrow != 0) << 4)};
-    if (!(ctx->d_items && !memcmp(key, ctx->items_key, sizeof(key)))) {
+    const Tile128Request rq = {ia0, ia1, jb0, jb1, triangle ? 1u : 0u, total_stages, (uint32_t)std::max(1, ctx->n_cus),
+                               ctx->k2_part_slots, ctx->k2_part_min_chunks, ctx->k2_part_cost_diag,
+                               ctx->k2_part_narrow != 0 ? 1u : 0u};
+    const Tile128Request* have = std::get_if<Tile128Request>(&ctx->items_key);
+    if (!(ctx->d_items && have && *have == rq)) {
         Tile128Plan plan;
-        plan_tile128(ia0, ia1, jb0, jb1, triangle, total_stages, (uint32_t)std::max(1, ctx->n_cus), ctx->k2_part_slots,
-                     ctx->k2_part_min_chunks, ctx->k2_part_cost_diag, ctx->k2_part_narrow != 0, &plan);
+        plan_tile128(rq, &plan);
         const size_t bytes = plan.items.size() * sizeof(PartItem);
-        if (bytes > ctx->items_capacity * sizeof(MfmaItem)) {
-            if (ctx->d_items) STORM_HIP_TRY(hipFree(ctx->d_items));
-            ctx->d_items = nullptr;
-            ctx->items_capacity = 0;
-            const size_t cap = std::max<size_t>((bytes + sizeof(MfmaItem) - 1) / sizeof(MfmaItem), 4096);
-            STORM_HIP_TRY(hipMalloc(&ctx->d_items, cap * sizeof(MfmaItem)));
-            ctx->items_capacity = cap;
-        }
-        memset(ctx->items_key, 0xff, sizeof(ctx->items_key));
+        ctx->items_key = std::monostate{};
         ctx->n_items = 0;
         ctx->n_part_items = 0;
+        if (int rc = ctx->d_items.ensure(bytes, "pairw_matrix: the item table", kItemsFloorBytes)) return rc;
         // the parts' windows and the tiles' tickets (zero between launches: the part that ends a tile clears its ticket)
-        const size_t need = (size_t)plan.n_windows * kThWindowWords * sizeof(uint32_t);
-        if (need > ctx->parts_capacity) {
-            if (ctx->d_parts) (void)hipFree(ctx->d_parts);
-            ctx->d_parts = nullptr;
-            ctx->parts_capacity = 0;
-            if (hipMalloc(reinterpret_cast<void**>(&ctx->d_parts), need) != hipSuccess) {
-                set_error("pairw_matrix: hipMalloc of %zu bytes for the k-parts' windows failed", need);
-                return STORM_HIP_ENOMEM;
-            }
-            ctx->parts_capacity = need;
-        }
-        if (plan.n_tiles > ctx->tickets_capacity || ctx->tickets_dirty) {
-            if (plan.n_tiles > ctx->tickets_capacity) {
-                if (ctx->d_tickets) (void)hipFree(ctx->d_tickets);
-                ctx->d_tickets = nullptr;
-                ctx->tickets_capacity = 0;
-                const size_t cap = std::max<size_t>(plan.n_tiles, 4096);
-                STORM_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ctx->d_tickets), cap * sizeof(uint32_t)));
-                ctx->tickets_capacity = cap;
-            }
-            STORM_HIP_TRY(hipMemsetAsync(ctx->d_tickets, 0, ctx->tickets_capacity * sizeof(uint32_t), ctx->stream));
+        if (int rc = ctx->d_parts.ensure((size_t)plan.n_windows * kThWindowWords * sizeof(uint32_t), "pairw_matrix: the k-parts' windows"))
+            return rc;
+        if (plan.n_tiles * sizeof(uint32_t) > ctx->d_tickets.capacity || ctx->tickets_dirty) {
+            if (int rc = ctx->d_tickets.ensure(plan.n_tiles * sizeof(uint32_t), "pairw_matrix: the tiles' tickets", 4096 * sizeof(uint32_t)))
+                return rc;
+            STORM_HIP_TRY(hipMemsetAsync(ctx->d_tickets, 0, ctx->d_tickets.capacity, ctx->stream));
             ctx->tickets_dirty = false;
         }
         if (!plan.items.empty()) {
             STORM_HIP_TRY(hipMemcpyAsync(ctx->d_items, plan.items.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
             STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));  // the list is pageable and leaves scope
         }
-        memcpy(ctx->items_key, key, sizeof(key));
+        ctx->items_key = rq;
         ctx->n_part_items = (uint32_t)plan.items.size();
     } else if (ctx->tickets_dirty) {
-        STORM_HIP_TRY(hipMemsetAsync(ctx->d_tickets, 0, ctx->tickets_capacity * sizeof(uint32_t), ctx->stream));
+        STORM_HIP_TRY(hipMemsetAsync(ctx->d_tickets, 0, ctx->d_tickets.capacity, ctx->stream));
         ctx->tickets_dirty = false;
     }
     if (ctx->n_part_items)
         hipLaunchKernelGGL(tile128_kernel, dim3(ctx->n_part_items), dim3(kThThreads), 0, ctx->stream, ops,
-                           static_cast<const PartItem*>(ctx->d_items), d_out, ld, n_rows, d_counts, and_weight, j_base,
+                           static_cast<const PartItem*>(ctx->d_items.d), d_out, ld, n_rows, d_counts, and_weight, j_base,
                            j_count, i_lo, n_cols, ctx->d_parts, ctx->d_tickets);
     if (hipGetLastError() != hipSuccess) {
         ctx->tickets_dirty = true;
@@ -2868,7 +2199,7 @@ int launch_pairw_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int o
     const uint64_t row_bytes = m->stride_words * 32;
     // bit-operand kernel: the operands are the matrix rows themselves (no shadow, no expansion)
     const bool bits = ctx->k2_tile_shape_eff <= 5;
-    const uint64_t pitch = bits ? m->stride_words * 8 : shadow_pitch(ctx, row_bytes, false);
+    const uint64_t pitch = bits ? m->stride_words * 8 : shadow_pitch(ctx, row_bytes);
     const size_t x4_bytes = bits ? 0 : (size_t)n_rows4 * pitch;
     if (n_rows4 / kTile >= 65535) {
         set_error("pairw_matrix: too many row blocks");
@@ -2879,17 +2210,7 @@ int launch_pairw_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int o
                   (unsigned long long)pitch);
         return STORM_HIP_EINVAL;
     }
-    if (x4_bytes > ctx->x4_capacity) {
-        if (ctx->d_x4) STORM_HIP_TRY(hipFree(ctx->d_x4));
-        ctx->d_x4 = nullptr;
-        ctx->x4_capacity = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&ctx->d_x4), x4_bytes) != hipSuccess) {
-            set_error("pairw_matrix: hipMalloc of %zu bytes for the FP4 shadow failed", x4_bytes);
-            return STORM_HIP_ENOMEM;
-        }
-        ctx->x4_capacity = x4_bytes;
-        memset(ctx->x4_key, 0, sizeof(ctx->x4_key));
-    }
+    if (int rc = ensure_shadow(ctx, x4_bytes, "pairw_matrix: the FP4 shadow")) return rc;
     // stages of 128 bits; the bit kernels walk whole 512-bit chunks that hold DATA (the pitch's pad chunks — 8 of 136 at
     // the headline shape since round 4's pitch pad — are never multiplied)
     const uint32_t total_stages = bits ? (m->n_words + 7u) / 8u * 4u : (uint32_t)(row_bytes / kStageBytes);
@@ -2921,7 +2242,9 @@ int launch_pairw_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int o
     }
     // off-diagonal tiles first; the diagonal ones (half of their window is written) go last,
     // where run_matrix_tiles may cut them along k
-    std::vector<std::pair<uint16_t, uint16_t>> tiles;
+    MatrixTilesRequest rq;
+    rq.total_stages = total_stages;
+    std::vector<std::pair<uint16_t, uint16_t>>& tiles = rq.tiles;
     const uint32_t t_lo = (uint32_t)(band_row0 / kTile), t_hi = (uint32_t)((band_end + kTile - 1) / kTile);
     // ... and last of all the tiles of a ragged last row block (few valid columns): with
     // tilebits8_kernel both kinds are short items, and the k-split of the last round then works on
@@ -2937,7 +2260,7 @@ int launch_pairw_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int o
     // what a tile costs next to a full one under tilebits8_kernel: a diagonal tile multiplies 5 of its
     // 8 block pairs per SIMD; a ragged one ceil(columns / 64) of 4 blocks per wave, but not below the
     // inflation work of its A operands (measured: 0.3)
-    std::vector<float> cost;
+    std::vector<float>& cost = rq.cost;
     if (ctx->k2_tile_shape_eff >= 2 && ctx->k2_tile_shape_eff <= 5) {
         // (tilering_kernel: a diagonal tile keeps its busiest SIMD at 12 of 16 block rows; a ragged column multiplies one
         //  block column in two of the eight waves but stores all of its images: options k2_ring_cost_*)
@@ -2950,7 +2273,7 @@ int launch_pairw_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int o
             cost.push_back(c);
         }
     }
-    int rc = plan_matrix_tiles(ctx, tiles, total_stages, &plan, cost.empty() ? nullptr : &cost);
+    int rc = ensure_matrix_tiles(ctx, std::move(rq), &plan);
     if (rc == STORM_HIP_OK && op != STORM_HIP_OP_AND) {
         rc = ensure_counts_scratch(ctx, m->n_rows, &d_counts);
         if (rc == STORM_HIP_OK) rc = launch_row_counts(ctx, m, d_counts);
@@ -2962,7 +2285,7 @@ int launch_pairw_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int o
             const dim3 grid = expand_grid(n_rows4, m->stride_words);
             hipLaunchKernelGGL(expand_fp4_kernel, grid, dim3(256), 0, ctx->stream, m->d,
                                m->stride_words, std::min<uint64_t>(m->n_rows_pad, n_rows4), n_rows4,
-                               reinterpret_cast<uint4*>(ctx->d_x4), kExpandAll, 2u, pitch / 16);
+                               reinterpret_cast<uint4*>(ctx->d_x4.d), kExpandAll, 2u, pitch / 16);
         }
         // rows [band_row0, band_end) are written; the columns run over the whole matrix
         rc = run_matrix_tiles(ctx, plan, pitch, d_out, ld, (uint32_t)band_end, d_counts,
@@ -2982,7 +2305,7 @@ int launch_square_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
     const uint64_t stride_words = a->stride_words;
     const uint64_t row_bytes = stride_words * 32;
     const bool bits = ctx->k2_tile_shape_eff <= 5 && b->stride_words == stride_words;
-    const uint64_t pitch = bits ? stride_words * 8 : shadow_pitch(ctx, row_bytes, false);
+    const uint64_t pitch = bits ? stride_words * 8 : shadow_pitch(ctx, row_bytes);
     const uint64_t rows_a = (a->n_rows + kTile - 1) / kTile * kTile;
     const uint64_t rows_b = (b->n_rows + kTile - 1) / kTile * kTile;
     if ((rows_a + rows_b) / kTile >= 65535) {
@@ -2995,17 +2318,7 @@ int launch_square_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
         return STORM_HIP_EINVAL;
     }
     const size_t x4_bytes = bits ? 0 : (size_t)(rows_a + rows_b) * pitch;
-    if (x4_bytes > ctx->x4_capacity) {
-        if (ctx->d_x4) STORM_HIP_TRY(hipFree(ctx->d_x4));
-        ctx->d_x4 = nullptr;
-        ctx->x4_capacity = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&ctx->d_x4), x4_bytes) != hipSuccess) {
-            set_error("square_matrix: hipMalloc of %zu bytes for the FP4 shadow failed", x4_bytes);
-            return STORM_HIP_ENOMEM;
-        }
-        ctx->x4_capacity = x4_bytes;
-        memset(ctx->x4_key, 0, sizeof(ctx->x4_key));
-    }
+    if (int rc = ensure_shadow(ctx, x4_bytes, "square_matrix: the FP4 shadow")) return rc;
     // (bit kernels: whole 512-bit chunks that hold DATA; the pitch's pad chunks are never multiplied)
     const uint32_t total_stages = bits ? (std::max(a->n_words, b->n_words) + 7u) / 8u * 4u : (uint32_t)(row_bytes / kStageBytes);
     const uint32_t ta = (uint32_t)(rows_a / kTile), tb = (uint32_t)(rows_b / kTile);
@@ -3030,11 +2343,12 @@ int launch_square_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
         if (rc == STORM_HIP_EHIP) set_error("square_matrix: HIP failure");
         return rc;
     }
-    std::vector<std::pair<uint16_t, uint16_t>> tiles;
-    xcd_grouped_tiles(0, ta, ta, ta + tb, false, tiles);
+    MatrixTilesRequest rq;
+    rq.total_stages = total_stages;
+    xcd_grouped_tiles(0, ta, ta, ta + tb, false, rq.tiles);
     uint32_t* d_counts = nullptr;  // per shadow row
     MatrixPlan plan;
-    int rc = plan_matrix_tiles(ctx, tiles, total_stages, &plan);
+    int rc = ensure_matrix_tiles(ctx, std::move(rq), &plan);
     if (rc == STORM_HIP_OK && op != STORM_HIP_OP_AND) {
         rc = ensure_counts_scratch(ctx, rows_a + rows_b, &d_counts);
         if (rc == STORM_HIP_OK) rc = launch_row_counts(ctx, a, d_counts);
@@ -3051,7 +2365,7 @@ int launch_square_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
             const dim3 grid = expand_grid(rows_dst, stride_words);
             hipLaunchKernelGGL(expand_fp4_kernel, grid, dim3(256), 0, ctx->stream, m->d,
                                stride_words, std::min<uint64_t>(m->n_rows_pad, rows_dst), rows_dst,
-                               reinterpret_cast<uint4*>(ctx->d_x4 + (side ? rows_a * pitch : 0)),
+                               reinterpret_cast<uint4*>(ctx->d_x4.d + (side ? rows_a * pitch : 0)),
                                kExpandAll, 2u, pitch / 16);
         }
         rc = run_matrix_tiles(ctx, plan, pitch, d_out, ld, (uint32_t)a->n_rows, d_counts,
@@ -3062,215 +2376,25 @@ int launch_square_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
     return rc;
 }
 
-// ---- K2q work decomposition: the stage stream of bitstream_kernel, cut into equal shares ----
-// Pure host computation (no device). `groups` workgroups; workgroup w walks segs[first[w] .. first[w+1]).
-struct BitstreamPlan {
-    std::vector<BitSeg> segs;
-    std::vector<uint32_t> bases;        // per stage, workgroup by workgroup: where its 64 rows x 64 B start (64-byte units)
-    std::vector<uint32_t> first_stage;  // workgroup w's stages are bases[first_stage[w] .. first_stage[w + 1])
-    std::vector<uint32_t> first;
-    uint32_t groups = 0;
-    uint64_t stages = 0;      // multiplied + operand-only stages of this shard, after cutting
-    uint32_t max_stages = 0;  // longest workgroup
-};
-struct BitstreamShaping {
-    int groups_per_cu = 0;  // 0 = by the length of the stream: 1, 2 or 3
-    int min_piece = 6;      // stages a workgroup should have at least before a CU's share is cut further
-    int min_run = 2;        // a cut leaves at least this many later blocks on either side of it
-    int long_piece = 80;    // stages per workgroup once the stream is longer than the chip's slots x this
-    // one round of 3 workgroups per CU: the later workgroups' shares in percent of the first one's (below) ...
-    int w3_1 = 120, w3_2 = 60;
-    int weighted_min = 16;       // ... from this many stages per share (shorter ones: equal shares)
-    int single_round_max = 220;  // stages per slot up to which the stream is ONE round of weighted shares
-};
-
-static void build_bitstream(const BitstreamShaping& sh, const std::vector<RowRange>& ranges,
-                            uint32_t n_kslices, uint32_t shard_rank, uint32_t shard_count,
-                            uint32_t n_cus, uint64_t pitch_bytes, BitstreamPlan& plan) {
-    // natural segments, k-slice major: every A tile of every range with the later tiles dealt cyclically
-    struct Nat {
-        BitSeg s;
-        uint64_t start;  // position of its first stage in the stream
-    };
-    std::vector<Nat> nat;
-    uint64_t L = 0;
-    for (uint32_t ks = 0; ks < n_kslices; ++ks)
-        for (const RowRange& rg : ranges) {
-            if (rg.r1 < rg.r0 + 2) continue;
-            const uint32_t b0 = (uint32_t)(rg.r0 / kStripBRows);
-            const uint32_t nb = (uint32_t)((rg.r1 - rg.r0 + kStripBRows - 1) / kStripBRows);
-            const uint32_t nT = (nb + 3u) / 4u;
-            auto blocks_of = [&](uint32_t J) { return std::min(4u, nb - 4u * J); };
-            for (uint32_t I = 0; I < nT; ++I) {
-                // tile I takes the (nT - 1) / 2 tiles behind it (cyclically); with an even number of
-                // tiles the opposite one goes to the lower tile on even k-slices, to the upper on odd ones
-                uint32_t take = (nT - 1u) / 2u;
-                if (nT > 1u && nT % 2u == 0u && ((I < nT / 2u) == ((ks & 1u) == 0u))) ++take;
-                uint32_t n_b = 0;
-                for (uint32_t d = 1; d <= take; ++d) n_b += blocks_of((I + d) % nT);
-                BitSeg s = {};
-                s.a_blk = b0 + 4u * I;
-                s.ks = ks;
-                s.b_first = (I + 1u == nT) ? 0u : 4u * (I + 1u);
-                s.n_b = n_b;
-                s.range_b0 = b0;
-                s.range_nb = nb;
-                s.flags = kBsDiag | (((I + ks) & 3u) << 8);
-                nat.push_back({s, L});
-                L += 4u + n_b;
-            }
-        }
-    plan.segs.clear();
-    plan.first.clear();
-    plan.bases.clear();
-    plan.first_stage.clear();
-    plan.stages = 0;
-    plan.max_stages = 0;
-    // this shard's part of the stream (contiguous: a shard touches a contiguous range of k-slices)
-    const uint64_t lo = L * shard_rank / shard_count, hi = L * (shard_rank + 1ull) / shard_count;
-    const uint64_t Ls = hi - lo;
-    // workgroups: as many per CU as the share of a CU is worth cutting, and never a workgroup
-    // beyond the accumulators' exact range
-    uint32_t per_cu = (uint32_t)sh.groups_per_cu;
-    if (per_cu == 0) {
-        const uint64_t share = Ls / std::max(1u, n_cus);
-        per_cu = share >= 3ull * (uint64_t)sh.min_piece ? 3u : share >= 2ull * (uint64_t)sh.min_piece ? 2u : 1u;
-    }
-    uint64_t G = (uint64_t)n_cus * per_cu;
-    // A long stream is cut into MORE shares than the chip holds workgroups (three per CU): the waves of a SIMD
-    // do not advance evenly (its arbiter prefers the oldest), so equal shares end at very different times and
-    // the last ones run alone, at a lone wave's 60 % of the pipe; with shares of ~80 stages a CU that finishes
-    // one early simply gets the next (headline shape: 883 us with 768 shares, 821 with 6144; N = 6144: 341 ->
-    // 317; from ~30 stages down the four stages that bring a continued segment's A rows in cost more than the
-    // tail does: N = 2048 is fastest with 768). Never a share beyond the accumulators' exact range.
-    // Whole rounds of the chip's slots only: 870 shares on 768 slots leave a fourth share to 102 CUs (N = 4096:
-    // 185 us against 152 with 768 or 1536).
-    if (sh.groups_per_cu == 0 && per_cu == 3u) {
-        const uint64_t slots = (uint64_t)n_cus * 3u;
-        const uint64_t rounds = (Ls + slots * (uint64_t)std::max(1, sh.long_piece) / 2) /
-                                (slots * (uint64_t)std::max(1, sh.long_piece));
-        // up to ~220 stages per slot ONE round of weighted shares (below) is faster than the dynamic deal, which
-        // pays four operand-only stages per cut (N = 6144: 308 against 314 us; N = 8192: 545 against 538)
-        G = slots * (Ls <= slots * (uint64_t)sh.single_round_max ? 1ull : std::max<uint64_t>(1, rounds));
-    }
-    G = std::max<uint64_t>(G, (Ls + kBsMaxStages / 2 - 1) / (kBsMaxStages / 2));
-    G = std::max<uint64_t>(1, std::min<uint64_t>(G, std::max<uint64_t>(1, Ls / 4)));
-    if (Ls == 0) G = 0;
-    plan.groups = (uint32_t)G;
-    if (G == 0) {
-        plan.first.push_back(0);
-        plan.first_stage.push_back(0);
-        return;
-    }
-    // cut positions, snapped: never inside a tile's own four stages, never leaving a stub of a run
-    auto seg_at = [&](uint64_t p) {  // natural segment holding stream position p (< L)
-        size_t a = 0, b = nat.size();
-        while (b - a > 1) {
-            const size_t m = (a + b) / 2;
-            if (nat[m].start <= p) a = m; else b = m;
-        }
-        return a;
-    };
-    // Shares of ONE round are not equal. The waves of a SIMD do not take turns: its arbiter issues for the oldest
-    // wave that can go, and a wave alone reaches ~60 % of the matrix pipe (one instruction every four cycles). Of
-    // three equal shares per CU the first-dispatched workgroup ends after 0.55 of the kernel, the second at 0.75,
-    // the third runs the last quarter nearly alone (N = 2048: 24 / 33 / 42 us; tools/archive/stream_trace.py, end by
-    // dispatch round; workgroup w is dispatched in round w / n_cus, one per CU per round). Shares in the proportion
-    // 100 : 120 : 60 let the three end closer together: -3 % at N = 2048, -6 % at 3072 ... 4096, -2 % at 6144
-    // against the dynamic deal (profiles/r03_e_stream_weights.txt; the optimum is flat: 100 : 100 : 50 and
-    // 100 : 125 : 65 are within 1 %). Shares shorter than ~16 stages keep equal lengths: start-up and drain
-    // dominate them, and whole segments as shares (no cut, no operand-only stages, but two workgroups per CU) lose
-    // 15 % at N = 1024.
-    std::vector<uint32_t> weight(G, 100u);
-    if (G == (uint64_t)n_cus * 3u && n_cus % 8u == 0u && Ls >= G * (uint64_t)sh.weighted_min) {
-        const uint32_t wr[3] = {100u, (uint32_t)sh.w3_1, (uint32_t)sh.w3_2};
-        for (uint64_t p = 0; p < G; ++p) weight[p] = std::max(1u, wr[(p % (G / 8)) / (n_cus / 8u)]);
-    }
-    std::vector<uint64_t> cum(G + 1, 0);
-    for (uint64_t p = 0; p < G; ++p) cum[p + 1] = cum[p] + weight[p];
-    std::vector<uint64_t> cut(G + 1);
-    for (uint64_t k = 0; k <= G; ++k) {
-        uint64_t c = lo + (uint64_t)((unsigned __int128)Ls * cum[k] / cum[G]);
-        if (c < L) {
-            const Nat& n = nat[seg_at(c)];
-            const uint64_t off = c - n.start, len = 4ull + n.s.n_b;
-            if (off > 0 && off < 4ull + (uint64_t)sh.min_run) c = n.start;
-            else if (off > 0 && len - off < (uint64_t)sh.min_run) c = n.start + len;
-        }
-        cut[k] = c;
-    }
-    for (uint64_t k = 1; k <= G; ++k) cut[k] = std::max(cut[k], cut[k - 1]);
-    // piece p of the stream goes to workgroup w with p = (w % 8) * (G / 8) + w / 8: block w runs on XCD
-    // w % 8 (observed; speed only), so an XCD's workgroups hold one contiguous eighth of the stream
-    std::vector<uint32_t> piece_of(G);
-    for (uint64_t w = 0; w < G; ++w) piece_of[w] = (uint32_t)(G % 8 == 0 ? (w % 8) * (G / 8) + w / 8 : w);
-    for (uint64_t w = 0; w < G; ++w) {
-        const uint64_t p = piece_of[w];
-        plan.first.push_back((uint32_t)plan.segs.size());
-        uint64_t c0 = cut[p], c1 = cut[p + 1];
-        uint32_t mine = 0;
-        while (c0 < c1) {
-            const Nat& n = nat[seg_at(c0)];
-            const uint64_t len = 4ull + n.s.n_b, off = c0 - n.start;
-            const uint64_t end = std::min(c1, n.start + len);
-            BitSeg s = n.s;
-            if (off == 0) {
-                s.n_b = (uint32_t)(end - n.start - 4ull);
-            } else {  // continues a cut segment: its four blocks only bring the A rows in
-                const uint32_t skip = (uint32_t)(off - 4ull);
-                s.flags &= ~kBsDiag;
-                s.b_first = (n.s.b_first + skip) % n.s.range_nb;
-                s.n_b = (uint32_t)(end - c0);
-            }
-            plan.segs.push_back(s);
-            mine += 4u + s.n_b;
-            c0 = end;
-        }
-        plan.stages += mine;
-        plan.max_stages = std::max(plan.max_stages, mine);
-    }
-    plan.first.push_back((uint32_t)plan.segs.size());
-    // the DMA's view of the same stream: the start of every stage's 64 rows x 64 B, in 64-byte units from the
-    // matrix ((ks * 64 + blk * 64 * pitch) / 64; the pitch is a multiple of 64 bytes)
-    plan.bases.reserve(plan.stages);
-    for (uint64_t w = 0; w < G; ++w) {
-        plan.first_stage.push_back((uint32_t)plan.bases.size());
-        for (uint32_t si = plan.first[w]; si < plan.first[w + 1]; ++si) {
-            const BitSeg& sg = plan.segs[si];
-            for (uint32_t i = 0; i < 4u + sg.n_b; ++i) {
-                uint32_t blk;
-                if (i < 4u) {
-                    blk = sg.a_blk + i;
-                } else {
-                    uint32_t rel = sg.b_first + (i - 4u);
-                    if (rel >= sg.range_nb) rel -= sg.range_nb;
-                    blk = sg.range_b0 + rel;
-                }
-                plan.bases.push_back((uint32_t)((uint64_t)sg.ks + (uint64_t)blk * pitch_bytes));
-            }
-        }
-    }
-    plan.first_stage.push_back((uint32_t)plan.bases.size());
-}
-
-static int ensure_bitstream(storm_hip_ctx_t* ctx, const std::vector<RowRange>& ranges, uint32_t n_kslices,
-                            uint32_t shard_rank, uint32_t shard_count, uint64_t pitch) {
-    const uint64_t key[4] = {ranges_hash(ranges) ^ (pitch * 0x9e3779b97f4a7c15ull) ^
-                                 ((uint64_t)(ctx->k2_stream_w3_2) * 0xc2b2ae3d27d4eb4full),
-                             n_kslices, ((uint64_t)shard_rank << 32) | shard_count,
-                             ((uint64_t)(ctx->k2_stream_groups_per_cu & 0xff) << 32) |
-                                 ((uint64_t)(ctx->k2_stream_min_piece & 0xffff) << 16) |
-                                 (uint64_t)(ctx->k2_stream_min_run & 0xffff) |
-                                 ((uint64_t)(ctx->k2_stream_w3_1 & 0x3ff) << 40)};
-    if (ctx->d_bitsegs && !memcmp(key, ctx->bit_key, sizeof(key))) return STORM_HIP_OK;
+// The K2q work list of the last geometry (build_bitstream, storm_hip_plan.cpp), cached by its request.
+static BitstreamRequest bitstream_request_of(const storm_hip_ctx_t* ctx, const std::vector<RowRange>& ranges, uint32_t n_kslices,
+                                             uint32_t shard_rank, uint32_t shard_count, uint64_t pitch) {
     BitstreamShaping sh;
     sh.groups_per_cu = ctx->k2_stream_groups_per_cu;
     sh.min_piece = std::max(1, ctx->k2_stream_min_piece);
     sh.min_run = std::max(1, ctx->k2_stream_min_run);
     sh.w3_1 = ctx->k2_stream_w3_1;
     sh.w3_2 = ctx->k2_stream_w3_2;
+    return bitstream_request(sh, ranges, n_kslices, shard_rank, shard_count, (uint32_t)std::max(1, ctx->n_cus), pitch);
+}
+
+static int ensure_bitstream(storm_hip_ctx_t* ctx, const std::vector<RowRange>& ranges, uint32_t n_kslices,
+                            uint32_t shard_rank, uint32_t shard_count, uint64_t pitch) {
+    const BitstreamRequest rq = bitstream_request_of(ctx, ranges, n_kslices, shard_rank, shard_count, pitch);
+    if (ctx->d_bitsegs && ctx->bit_key == rq) return STORM_HIP_OK;
+    ctx->bit_key.reset();
     BitstreamPlan plan;
-    build_bitstream(sh, ranges, n_kslices, shard_rank, shard_count, (uint32_t)std::max(1, ctx->n_cus), pitch, plan);
+    build_bitstream(rq, ranges, plan);
     if (plan.bases.size() >= (1ull << 32) ||
         (!ranges.empty() && ranges.back().r1 * pitch / 64 + n_kslices >= (1ull << 32))) {
         set_error("K2q: the matrix is beyond the 32-bit stage addresses (64-byte units)");
@@ -3287,20 +2411,8 @@ static int ensure_bitstream(storm_hip_ctx_t* ctx, const std::vector<RowRange>& r
     packed.insert(packed.end(), plan.bases.begin(), plan.bases.end());
     packed.push_back(0u);  // a trailing workgroup without stages reads bases[total stages] (bitstream_kernel: prep)
     const size_t first_bytes = packed.size() * sizeof(uint32_t);
-    if (seg_bytes > ctx->bitsegs_capacity) {
-        if (ctx->d_bitsegs) STORM_HIP_TRY(hipFree(ctx->d_bitsegs));
-        ctx->d_bitsegs = nullptr;
-        ctx->bitsegs_capacity = 0;
-        STORM_HIP_TRY(hipMalloc(&ctx->d_bitsegs, seg_bytes));
-        ctx->bitsegs_capacity = seg_bytes;
-    }
-    if (first_bytes > ctx->bitfirst_capacity) {
-        if (ctx->d_bitfirst) STORM_HIP_TRY(hipFree(ctx->d_bitfirst));
-        ctx->d_bitfirst = nullptr;
-        ctx->bitfirst_capacity = 0;
-        STORM_HIP_TRY(hipMalloc(&ctx->d_bitfirst, first_bytes));
-        ctx->bitfirst_capacity = first_bytes;
-    }
+    if (int rc = ctx->d_bitsegs.ensure(seg_bytes, "K2q: the segment table")) return rc;
+    if (int rc = ctx->d_bitfirst.ensure(first_bytes, "K2q: the workgroups' stage tables")) return rc;
     if (!plan.segs.empty())
         STORM_HIP_TRY(hipMemcpyAsync(ctx->d_bitsegs, plan.segs.data(), plan.segs.size() * sizeof(BitSeg),
                                      hipMemcpyHostToDevice, ctx->stream));
@@ -3311,7 +2423,7 @@ static int ensure_bitstream(storm_hip_ctx_t* ctx, const std::vector<RowRange>& r
     ctx->bit_stages = plan.stages;
     ctx->bit_max_stages = plan.max_stages;
     ctx->n_bit_segs = (uint32_t)plan.segs.size();
-    memcpy(ctx->bit_key, key, sizeof(key));
+    ctx->bit_key = rq;
     return STORM_HIP_OK;
 }
 
@@ -3329,7 +2441,7 @@ int launch_pairw_bitstream(storm_hip_ctx_t* ctx, const uint64_t* X, uint64_t pit
     ctx->pass_report[0] |= STORM_HIP_RAN_BITSTREAM;
     ctx->pass_report[1] += ranges_word_pairs(ranges, (uint64_t)n_kslices * 8u, shard_count);
     ctx->n_items = 0;
-    memset(ctx->items_key, 0xff, sizeof(ctx->items_key));
+    ctx->items_key = std::monostate{};
     ctx->last_info[0] = ctx->n_bit_groups;
     ctx->last_info[1] = ctx->bit_max_stages;
     ctx->last_info[2] = 1;
@@ -3341,29 +2453,22 @@ int launch_pairw_bitstream(storm_hip_ctx_t* ctx, const uint64_t* X, uint64_t pit
 #ifdef STORM_HIP_PROBES
     if (ctx->k2_ring == 18) {  // schedule trace (results stay correct)
         const size_t need = (size_t)ctx->n_bit_groups * 8 * sizeof(unsigned long long);
-        if (need > ctx->trace_capacity) {
-            if (ctx->d_trace) STORM_HIP_TRY(hipFree(ctx->d_trace));
-            ctx->d_trace = nullptr;
-            ctx->trace_capacity = 0;
-            STORM_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ctx->d_trace), need));
-            ctx->trace_capacity = need;
-        }
+        if (int rc = ctx->d_trace.ensure(need, "K2q: the schedule trace")) return rc;
         ctx->trace_items = ctx->n_bit_groups;
         ctx->trace_is_stream = true;
-        ctx->trace_is_stream = true;
         hipLaunchKernelGGL(bitstream_kernel<true>, grid, block, 0, ctx->stream,
-                           reinterpret_cast<const uint8_t*>(X), pitch, static_cast<const BitSeg*>(ctx->d_bitsegs),
-                           static_cast<const uint32_t*>(ctx->d_bitfirst),
-                           static_cast<const uint32_t*>(ctx->d_bitfirst) + 2 * ((size_t)ctx->n_bit_groups + 1),
-                           static_cast<const uint32_t*>(ctx->d_bitfirst) + ((size_t)ctx->n_bit_groups + 1), ctx->d_slots,
+                           reinterpret_cast<const uint8_t*>(X), pitch, ctx->d_bitsegs.d,
+                           ctx->d_bitfirst.d,
+                           ctx->d_bitfirst.d + 2 * ((size_t)ctx->n_bit_groups + 1),
+                           ctx->d_bitfirst.d + ((size_t)ctx->n_bit_groups + 1), ctx->d_slots,
                            reinterpret_cast<unsigned long long*>(d_total), ctx->d_trace);
     } else
 #endif
         hipLaunchKernelGGL(bitstream_kernel<false>, grid, block, 0, ctx->stream,
-                           reinterpret_cast<const uint8_t*>(X), pitch, static_cast<const BitSeg*>(ctx->d_bitsegs),
-                           static_cast<const uint32_t*>(ctx->d_bitfirst),
-                           static_cast<const uint32_t*>(ctx->d_bitfirst) + 2 * ((size_t)ctx->n_bit_groups + 1),
-                           static_cast<const uint32_t*>(ctx->d_bitfirst) + ((size_t)ctx->n_bit_groups + 1), ctx->d_slots,
+                           reinterpret_cast<const uint8_t*>(X), pitch, ctx->d_bitsegs.d,
+                           ctx->d_bitfirst.d,
+                           ctx->d_bitfirst.d + 2 * ((size_t)ctx->n_bit_groups + 1),
+                           ctx->d_bitfirst.d + ((size_t)ctx->n_bit_groups + 1), ctx->d_slots,
                            reinterpret_cast<unsigned long long*>(d_total), (unsigned long long*)nullptr);
     kernel_time_mark(ctx);
     STORM_HIP_TRY(hipGetLastError());
@@ -3386,7 +2491,7 @@ int launch_pairw_bits_ranges(storm_hip_ctx_t* ctx, const uint8_t* X, uint64_t pi
         return STORM_HIP_EINVAL;
     }
     ctx->n_items = 0;  // the strip items carry the diagonal tiles themselves
-    memset(ctx->items_key, 0xff, sizeof(ctx->items_key));
+    ctx->items_key = std::monostate{};
     if (int rc = ensure_strip_items(ctx, ranges, n_kslices2, shard_rank, shard_count, a_tile, 2))
         return rc;
     const uint32_t n_strip = ctx->n_strip_items;
@@ -3417,11 +2522,11 @@ int launch_pairw_bits_ranges(storm_hip_ctx_t* ctx, const uint8_t* X, uint64_t pi
         kernel_time_mark(ctx);
         if (waves == 8u)
             hipLaunchKernelGGL(strip16_bits2_kernel, dim3(n_strip), dim3(512), (size_t)ctx->k2_lds_pad,
-                               ctx->stream, X, pitch, static_cast<const StripItem*>(ctx->d_strip_items), ctx->d_slots,
+                               ctx->stream, X, pitch, ctx->d_strip_items.d, ctx->d_slots,
                                fold_inline ? reinterpret_cast<unsigned long long*>(d_total) : nullptr, fold_slots);
         else
             hipLaunchKernelGGL(strip16_bits_kernel, dim3(n_strip), dim3(kStripThreads), (size_t)ctx->k2_lds_pad,
-                               ctx->stream, X, pitch, static_cast<const StripItem*>(ctx->d_strip_items), ctx->d_slots,
+                               ctx->stream, X, pitch, ctx->d_strip_items.d, ctx->d_slots,
                                fold_inline ? reinterpret_cast<unsigned long long*>(d_total) : nullptr, fold_slots);
         kernel_time_mark(ctx);
         STORM_HIP_TRY(hipGetLastError());
@@ -3450,7 +2555,7 @@ static int launch_pairw_bits(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, 
         return launch_pairw_bitwave(ctx, m->d, pitch, ranges, n_kslices, shard_rank, shard_count, d_total);
 #endif
     ctx->n_items = 0;  // the strip items carry the diagonal tiles themselves
-    memset(ctx->items_key, 0xff, sizeof(ctx->items_key));
+    ctx->items_key = std::monostate{};
     if (operands == 5 || operands == 6)
         return launch_pairw_bits_ranges(ctx, reinterpret_cast<const uint8_t*>(m->d), pitch, ranges, n_kslices * 2u,
                                         shard_rank, shard_count, d_total, false, operands == 6 ? 512u : (uint32_t)kStripATile);
@@ -3465,7 +2570,7 @@ static int launch_pairw_bits(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, 
         kernel_time_mark(ctx);
         hipLaunchKernelGGL(stripbits_kernel, dim3(n_strip), dim3(kStripThreads), 0, ctx->stream,
                            reinterpret_cast<const uint8_t*>(m->d), pitch,
-                           static_cast<const StripItem*>(ctx->d_strip_items), ctx->d_slots);
+                           ctx->d_strip_items.d, ctx->d_slots);
         kernel_time_mark(ctx);
         STORM_HIP_TRY(hipGetLastError());
     }
@@ -3542,42 +2647,36 @@ static int pairw_bits_upload_queue(storm_hip_ctx_t* ctx, storm_hip_matrix_s* m, 
                                        src_stride_words * 8, (size_t)m->n_words * 8, row1 - row0, hipMemcpyHostToDevice,
                                        ctx->copy_stream));
         STORM_HIP_TRY(hipEventRecord(l.landed, ctx->copy_stream));
-        const uint64_t key[4] = {m->n_rows, ((uint64_t)n_kslices2 << 32) | (uint64_t)p, (t0 << 48) | (t1 << 32) | (uint64_t)ctx->k2_tail_run,
-                                 ((uint64_t)ctx->k2_tail_slices << 32) | (uint64_t)ctx->k2_lpt_rounds};
-        if (!l.d || memcmp(key, l.key, sizeof(key))) {
-            StripShaping sh;   // (a fixed run length: a panel's list is short and all tail)
-            sh.tail_run = ctx->k2_tail_run;
-            sh.tail_slices = ctx->k2_tail_slices;
-            sh.lpt_rounds = ctx->k2_lpt_rounds;
-            sh.xcd_group = 2;
-            RowRange rg{0, row1};
-            rg.back_from = row0;
+        // (a fixed run length: a panel's list is short and all tail)
+        StripOptions po = strip_options_of(ctx, 2);
+        po.max_run = 128;
+        po.shard_pairs = po.persistent = po.one_slice_probe = 0;
+        RowRange rg{0, row1};
+        rg.back_from = row0;
+        const std::vector<RowRange> panel = {rg};
+        const StripRequest rq = strip_request(po, panel, n_kslices2, 0, 1, (uint32_t)kStripATile);
+        if (!l.d || !(l.key == rq)) {
+            l.key.reset();
             std::vector<StripItem> items;
             uint32_t qb[8], qc[8];
-            build_strip_items(sh, {rg}, n_kslices2, 0, 1, (uint32_t)kStripATile, items, qb, qc);
+            plan_strips(rq, panel, items, qb, qc);
             if (items.size() >= (1ull << 31)) {
                 set_error("pairw_dense_upload: %zu strip items exceed the grid limit", items.size());
                 return STORM_HIP_EINVAL;
             }
-            if (items.size() > l.cap) {
-                if (l.d) STORM_HIP_TRY(hipFree(l.d));
-                l.d = nullptr;
-                l.cap = 0;
-                const size_t cap = std::max<size_t>(items.size(), 1024);
-                STORM_HIP_TRY(hipMalloc(&l.d, cap * sizeof(StripItem)));
-                l.cap = cap;
-            }
+            if (int rc = l.d.ensure(items.size() * sizeof(StripItem), "pairw_dense_upload: a panel's strip items", 1024 * sizeof(StripItem)))
+                return rc;
             l.n = (uint32_t)items.size();
             if (l.n) {
                 if (int rc_up = upload_bytes(ctx, l.d, items.data(), items.size() * sizeof(StripItem))) return rc_up;
                 STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));   // `items` leaves scope
             }
-            memcpy(l.key, key, sizeof(key));
+            l.key = rq;
         }
         STORM_HIP_TRY(hipStreamWaitEvent(ctx->stream, l.landed, 0));
         if (l.n) {
             hipLaunchKernelGGL(strip16_bits_kernel, dim3(l.n), dim3(kStripThreads), (size_t)ctx->k2_lds_pad, ctx->stream,
-                               reinterpret_cast<const uint8_t*>(m->d), pitch, static_cast<const StripItem*>(l.d), ctx->d_slots,
+                               reinterpret_cast<const uint8_t*>(m->d), pitch, l.d.d, ctx->d_slots,
                                (unsigned long long*)nullptr, (uint32_t)kSlots);
             STORM_HIP_TRY(hipGetLastError());
         }
@@ -3628,154 +2727,6 @@ int launch_pairw_mfma(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint32_
 }
 
 }  // namespace storm
-
-// Host-only view of the default path's work decomposition (no device is touched): what a shard
-// of a multi-GPU run multiplies, so that the partition of the pair space can be checked — and
-// rehearsed with CPU partials — without a GPU (tests/test_dist_cpu.py).
-extern "C" int storm_hip_matrix_plan(uint64_t n_rows_a, uint64_t n_rows_b, uint32_t n_words, uint64_t band_row0,
-                                     uint64_t band_rows, uint32_t n_cus, int slots_per_cu, int min_chunks, int diag_cost_pct,
-                                     uint32_t* out, uint64_t capacity_items, uint64_t* n_items) {
-    using namespace storm;
-    if (!n_items || n_rows_a == 0 || n_words == 0 || n_cus == 0 || slots_per_cu < 0 || slots_per_cu > 2 || min_chunks < 1 ||
-        diag_cost_pct < 10 || diag_cost_pct > 100) {
-        set_error("matrix_plan: bad arguments");
-        return STORM_HIP_EINVAL;
-    }
-    try {
-        const uint32_t total_stages = (n_words + 7u) / 8u * 4u;
-        Tile128Plan plan;
-        if (n_rows_b == 0) {   // triangle (a band of it)
-            const uint64_t end = std::min(n_rows_a, band_row0 + (band_rows ? band_rows : n_rows_a));
-            if (band_row0 < end)
-                plan_tile128((uint32_t)(band_row0 / kThTile), (uint32_t)((end + kThTile - 1) / kThTile), 0u,
-                             (uint32_t)((n_rows_a + kThTile - 1) / kThTile), true, total_stages, n_cus, slots_per_cu, min_chunks,
-                             diag_cost_pct, true, &plan);
-        } else {   // rectangle: B's tiles count on behind A's rows padded to 256
-            const uint64_t rows_a = (n_rows_a + kTile - 1) / kTile * kTile;
-            plan_tile128(0u, (uint32_t)((n_rows_a + kThTile - 1) / kThTile), (uint32_t)(rows_a / kThTile),
-                         (uint32_t)((rows_a + n_rows_b + kThTile - 1) / kThTile), false, total_stages, n_cus, slots_per_cu,
-                         min_chunks, diag_cost_pct, true, &plan);
-        }
-        *n_items = plan.items.size();
-        if (out) {
-            if (capacity_items < plan.items.size()) {
-                set_error("matrix_plan: capacity %llu < %zu items", (unsigned long long)capacity_items, plan.items.size());
-                return STORM_HIP_EINVAL;
-            }
-            for (size_t k = 0; k < plan.items.size(); ++k) {
-                const PartItem& it = plan.items[k];
-                uint32_t* o = out + 8 * k;
-                o[0] = it.I, o[1] = it.J, o[2] = it.stage0 / 4u, o[3] = it.n_stages / 4u, o[4] = it.tile;
-                o[5] = (uint32_t)(it.part & (uint16_t)~kThNarrow), o[6] = it.n_parts, o[7] = (it.part & kThNarrow) ? 1u : 0u;
-            }
-        }
-        return STORM_HIP_OK;
-    } catch (const std::exception& e) {
-        set_error("matrix_plan: %s", e.what());
-        return STORM_HIP_ENOMEM;
-    }
-}
-
-extern "C" int storm_hip_strip_plan3(uint64_t n_rows, uint32_t n_words, uint32_t shard_rank,
-                                     uint32_t shard_count, int form, int pair_space, int max_run, int tail_run,
-                                     int tail_slices, int lpt_rounds, uint32_t n_cus, uint32_t* out,
-                                     uint64_t capacity_items, uint64_t* n_items, int* run_chosen) {
-    using namespace storm;
-    if (!n_items || shard_count == 0 || shard_rank >= shard_count || n_words == 0 || (form != 0 && form != 1) ||
-        max_run < 0 || max_run > 4096 || tail_run < 1 || tail_run > 4096 || tail_slices < 0 || tail_slices > 255 ||
-        lpt_rounds < 0 || lpt_rounds > 63 || n_cus == 0) {
-        set_error("strip_plan: bad arguments");
-        return STORM_HIP_EINVAL;
-    }
-    try {
-        // slices that hold data: form 0 (FP4 shadow, launch_pairw_mfma_ranges): 256 consecutive bits each;
-        // form 1 (K2b, launch_pairw_bits_ranges): slice ks = class pair ks & 1 of the 512-bit chunk ks / 2
-        const uint32_t n_kslices = form == 0 ? (n_words + 3u) / 4u : 2u * ((n_words + 7u) / 8u);
-        std::vector<RowRange> ranges;
-        if (n_rows > 1) ranges.push_back({0, n_rows});
-        std::vector<StripItem> items;
-        uint32_t qb[8], qc[8];
-        StripOptions o;
-        o.max_run = max_run;
-        o.tail_run = tail_run;
-        o.tail_slices = tail_slices;
-        o.lpt_rounds = lpt_rounds;
-        o.shard_pairs = pair_space != 0;
-        o.n_cus = (int)n_cus;
-        // exactly what ensure_strip_items launches for these options (one function derives the shaping)
-        const StripShaping sh = choose_strip_shaping(o, ranges, n_kslices, shard_count, (uint32_t)kStripATile, form == 0 ? 1 : 2);
-        if (run_chosen) *run_chosen = sh.max_run;
-        build_strip_items(sh, ranges, n_kslices, shard_rank, shard_count, (uint32_t)kStripATile, items, qb, qc);
-        *n_items = items.size();
-        if (out)
-            for (uint64_t i = 0; i < std::min<uint64_t>(capacity_items, items.size()); ++i) {
-                out[i * 5 + 0] = items[i].a_row0;
-                out[i * 5 + 1] = items[i].diag;
-                out[i * 5 + 2] = items[i].j0;
-                out[i * 5 + 3] = items[i].j1;
-                out[i * 5 + 4] = items[i].ks;
-            }
-    } catch (const std::exception& e) {
-        set_error("strip_plan: %s", e.what());
-        return STORM_HIP_ENOMEM;
-    }
-    return STORM_HIP_OK;
-}
-
-// The context's default options on a 256-CU device (what a fresh context launches on an MI355X).
-extern "C" int storm_hip_strip_plan2(uint64_t n_rows, uint32_t n_words, uint32_t shard_rank,
-                                     uint32_t shard_count, int form, int pair_space, uint32_t* out,
-                                     uint64_t capacity_items, uint64_t* n_items) {
-    const storm::StripOptions d;
-    return storm_hip_strip_plan3(n_rows, n_words, shard_rank, shard_count, form, pair_space, d.max_run, d.tail_run,
-                                 d.tail_slices, d.lpt_rounds, (uint32_t)d.n_cus, out, capacity_items, n_items, nullptr);
-}
-
-extern "C" int storm_hip_strip_plan(uint64_t n_rows, uint32_t n_words, uint32_t shard_rank,
-                                    uint32_t shard_count, uint32_t* out, uint64_t capacity_items,
-                                    uint64_t* n_items) {
-    return storm_hip_strip_plan2(n_rows, n_words, shard_rank, shard_count, 0, 0, out, capacity_items, n_items);
-}
-
-extern "C" int storm_hip_stream_plan(uint64_t n_rows, uint32_t n_words, uint32_t shard_rank, uint32_t shard_count,
-                                     uint32_t n_cus, uint32_t* out, uint64_t capacity_segments,
-                                     uint64_t* n_segments, uint32_t* n_workgroups) {
-    using namespace storm;
-    if (!n_segments || shard_count == 0 || shard_rank >= shard_count || n_words == 0 || n_cus == 0) {
-        set_error("stream_plan: bad arguments");
-        return STORM_HIP_EINVAL;
-    }
-    try {
-        std::vector<RowRange> ranges;
-        if (n_rows > 1) ranges.push_back({0, n_rows});
-        BitstreamPlan plan;
-        const uint64_t stride_words = ((uint64_t)n_words + kChunkWords - 1) / kChunkWords * kChunkWords;
-        build_bitstream(BitstreamShaping{}, ranges, (n_words + 7u) / 8u, shard_rank, shard_count, n_cus,
-                        stride_words * 8, plan);
-        *n_segments = plan.segs.size();
-        if (n_workgroups) *n_workgroups = plan.groups;
-        if (out) {
-            uint32_t wg = 0;
-            for (uint64_t i = 0; i < std::min<uint64_t>(capacity_segments, plan.segs.size()); ++i) {
-                while (wg + 1 < plan.first.size() && plan.first[wg + 1] <= i) ++wg;
-                const BitSeg& sg = plan.segs[i];
-                uint32_t* o = out + i * 8;
-                o[0] = wg;
-                o[1] = sg.a_blk;
-                o[2] = sg.ks;
-                o[3] = sg.b_first;
-                o[4] = sg.n_b;
-                o[5] = sg.range_nb;
-                o[6] = sg.flags & kBsDiag;
-                o[7] = 4u + sg.n_b;
-            }
-        }
-    } catch (const std::exception& e) {
-        set_error("stream_plan: %s", e.what());
-        return STORM_HIP_ENOMEM;
-    }
-    return STORM_HIP_OK;
-}
 
 #ifdef STORM_HIP_PROBES
 // Tools build only: the in-kernel clock witness of the stamped kernels (STORM_CLOCK_BEGIN / _END above) since the last

@@ -1,0 +1,879 @@
+// storm_hip_plan.cpp — the planners of the matrix-core kernels' work lists: pure host computation, no device, no HIP
+// runtime (storm_hip_plan.h). The launchers in storm_hip_mfma.hip compare a request with the one their cached list was
+// planned from, call the planner, and upload; the exported storm_hip_*_plan functions at the end show the same plans to
+// the CPU tests (tests/test_dist_cpu.py).
+#include "storm_hip_plan.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <exception>
+
+#include "storm_hip.h"
+
+namespace storm {
+
+bool timing_env() {
+    static const bool on = getenv("STORM_HIP_TIMING") != nullptr;   // (read once, not per call)
+    return on;
+}
+
+uint64_t ranges_hash(const std::vector<RowRange>& ranges) {
+    uint64_t h = 1469598103934665603ull;
+    for (const RowRange& r : ranges) {
+        h = (h ^ r.r0) * 1099511628211ull;
+        h = (h ^ r.r1) * 1099511628211ull;
+        h = (h ^ r.a_end) * 1099511628211ull;
+        h = (h ^ r.back_from) * 1099511628211ull;
+    }
+    return h;
+}
+
+// ---- K2 tiles, sum mode: the tiles of every range's upper triangle x this shard's k-slices ----
+int plan_tile_sum(const TileSumRequest& rq, const std::vector<RowRange>& ranges, std::vector<MfmaItem>& items) {
+    const uint32_t total_stages = rq.total_stages, shard_rank = rq.shard_rank, shard_count = rq.shard_count;
+    const uint32_t spi = std::max(1u, rq.stages_per_item);
+    const bool diag_only = rq.diag_only != 0;
+    // tiles of every range's upper triangle, in groups of 4 (I) x 8 (J) row blocks
+    std::vector<std::pair<uint16_t, uint16_t>> tiles;
+    for (const RowRange& rg : ranges) {
+        const uint32_t b0 = (uint32_t)(rg.r0 / kTile);
+        const uint32_t nT = (uint32_t)((rg.r1 - rg.r0 + kTile - 1) / kTile);
+        // (a_end: only the tile rows below it)
+        const uint32_t nTa = rg.a_end ? (uint32_t)std::min<uint64_t>(nT, (std::min(rg.a_end, rg.r1) - rg.r0 + kTile - 1) / kTile) : nT;
+        for (uint32_t gi = 0; gi < nTa; gi += 4)
+            for (uint32_t gj = gi / 8 * 8; gj < nT; gj += 8)
+                for (uint32_t i = gi; i < std::min(gi + 4, nTa); ++i)
+                    for (uint32_t j = std::max(gj, i); j < std::min(gj + 8, nT); ++j)
+                        if (!diag_only || i == j)
+                            tiles.emplace_back((uint16_t)(b0 + i), (uint16_t)(b0 + j));
+    }
+    // Sharding is by k-group (kGroupStages stages = 64 words of k), the same ownership rule as
+    // the strips and the expand kernel; k-slices are cut so that none straddles two groups.
+    std::vector<std::pair<uint32_t, uint32_t>> slices;  // (first stage, stages) owned by this shard
+    for (uint32_t g0 = 0; g0 < total_stages; g0 += kGroupStages) {
+        if ((g0 / kGroupStages) % shard_count != shard_rank) continue;
+        const uint32_t g1 = std::min(total_stages, g0 + kGroupStages);
+        for (uint32_t s0 = g0; s0 < g1; s0 += spi) slices.emplace_back(s0, std::min(spi, g1 - s0));
+    }
+    // k-slice major; within a slice, runs of 32 consecutive tiles go to one XCD. Block b runs
+    // on XCD b % 8 (observed round-robin dispatch; only speed depends on it), so each chunk of
+    // 256 tiles (8 runs of 32) is emitted interleaved: position-major, run-minor.
+    items.clear();
+    const size_t n = tiles.size();
+    for (const auto& sl : slices) {
+        const uint32_t s0 = sl.first, ns = sl.second;
+        for (size_t c = 0; c < n; c += 256)
+            for (size_t pos = 0; pos < 32; ++pos)
+                for (size_t x = 0; x < 8; ++x) {
+                    const size_t L = c + x * 32 + pos;
+                    if (L >= n) continue;
+                    if (rq.one_tile_probe)  // timing probe only: every item reads one tile
+                        items.push_back({tiles[0].first, tiles[0].first, s0, ns});
+                    else
+                        items.push_back({tiles[L].first, tiles[L].second, s0, ns});
+                }
+    }
+    if (items.size() != slices.size() * n) {
+        set_error("K2 item table construction lost tiles (%zu != %zu)", items.size(),
+                  slices.size() * n);
+        return STORM_HIP_EINVAL;
+    }
+    if (items.size() >= (1ull << 31)) {
+        set_error("K2: %zu tile items exceed the grid limit", items.size());
+        return STORM_HIP_EINVAL;
+    }
+    return STORM_HIP_OK;
+}
+
+// ---- strips ----
+static inline uint32_t strip_item_cost(const StripItem& it, uint32_t per_tile) {
+    return (it.j1 - it.j0) + it.diag * per_tile + 10u;  // stages + ~10 stages' worth of prologue
+}
+
+// Strip items for this shard; the shard's slices are dealt to the 8 XCDs (block b runs on XCD
+// b % 8 — observed, speed only), and inside an XCD's list the items of one slice are consecutive,
+// longest run first.
+struct StripShaping {  // work-list shaping knobs: StripOptions with the run length decided
+    int max_run = 128, tail_run = 32, tail_slices = 3, lpt_rounds = 6;
+    int xcd_group = 1;  // consecutive slices that share an XCD (2 for the bit-operand strips: slices 2j, 2j + 1 read the same bits)
+    bool persistent = false, one_slice_probe = false;
+    // Ownership among the shards: false = whole k-slices first, the leftover slices cut along the pair space
+    // (above); true = EVERY slice is cut along the pair space (north_star's literal split: a shard multiplies
+    // its share of the tile pairs over all of k). Option k2_shard_pairs; rehearsed side by side in
+    // tools/bench_shards.py.
+    bool pair_space = false;
+};
+// Pure host computation (no device): the list, in launch order, and for the persistent form the
+// per-XCD queue bounds.
+static void build_strip_items(const StripShaping& sh, const std::vector<RowRange>& ranges,
+                              uint32_t n_kslices, uint32_t shard_rank, uint32_t shard_count,
+                              uint32_t a_tile, std::vector<StripItem>& items,
+                              uint32_t queue_base[8], uint32_t queue_count[8], double* makespan = nullptr,
+                              uint32_t slots_per_xcd = 128) {
+    // stages per item: <= 4096 keeps the f32 accumulators exact; shorter runs trade one more A
+    // load per run for a shorter tail at the end of the launch
+    const uint32_t kMaxRun = (uint32_t)std::min(4096, std::max(1, sh.max_run));
+    const uint32_t kTailRun = (uint32_t)std::min(4096, std::max(1, sh.tail_run));
+    const uint32_t kPerTile = a_tile / kStripBRows;
+    // The slices of this shard, dealt to the XCDs in turn.
+    std::vector<std::vector<uint32_t>> slices_of(8);
+    uint32_t local = 0;
+    const bool pair_mode = sh.pair_space && shard_count > 1;
+    const uint32_t modulo_slices = pair_mode ? n_kslices : strip_modulo_slices(n_kslices, shard_count);
+    const uint32_t xg = (uint32_t)std::max(1, sh.xcd_group);
+    for (uint32_t ks = 0; ks < modulo_slices; ++ks)
+        if (pair_mode || strip_owns_slice(ks, shard_rank, shard_count)) slices_of[(local++ / xg) % 8].push_back(ks);
+    // One slice = every A tile against the B blocks behind it; `max_run` caps the stages per item.
+    std::vector<uint64_t> pair_load(shard_count, 0);  // pair mode: stages dealt to every shard so far
+    auto emit_slice_all = [&](uint32_t ks, uint32_t max_run, std::vector<StripItem>& dst) {
+        // k2_debug & 16 (timing probe, wrong results): every XCD re-reads one k-slice, i.e. the
+        // launch as it would run if nothing ever missed in L2
+        const uint32_t ks_data = sh.one_slice_probe ? ks % 8u : ks;
+        for (const RowRange& rg : ranges) {
+            if (rg.back_from != ~0ull) {   // a row panel that has just arrived: its tiles against everything in front of them
+                const uint32_t blk0 = (uint32_t)(rg.r0 / kStripBRows);
+                for (uint64_t a0 = rg.back_from; a0 < rg.r1; a0 += a_tile) {
+                    const uint32_t a_row0 = (uint32_t)a0, end = (uint32_t)(a0 / kStripBRows);
+                    if (end <= blk0) {
+                        dst.push_back({a_row0, 1, end, end, ks_data});
+                        continue;
+                    }
+                    for (uint32_t j0 = blk0; j0 < end; j0 += max_run)
+                        dst.push_back({a_row0, (uint32_t)(j0 == blk0), j0, std::min(end, j0 + max_run), ks_data});
+                }
+                continue;
+            }
+            // A tiles of a_tile rows from the start of the range (the rows between r1 and
+            // the end of its last A tile are zero: the caller pads ranges accordingly)
+            const uint64_t a_rows = (rg.a_end ? std::min(rg.a_end, rg.r1) : rg.r1) - rg.r0;  // A tiles only below a_end
+            const uint32_t nA = (uint32_t)((a_rows + a_tile - 1) / a_tile);
+            const uint32_t jend = (uint32_t)((rg.r1 + kStripBRows - 1) / kStripBRows);  // absolute
+            for (uint32_t i = 0; i < nA; ++i) {
+                const uint32_t a_row0 = (uint32_t)rg.r0 + i * a_tile;
+                const uint32_t first = a_row0 / (uint32_t)kStripBRows + kPerTile;
+                if (first >= jend) {  // last tile of the range: only its own triangle
+                    dst.push_back({a_row0, 1, first, first, ks_data});
+                    continue;
+                }
+                for (uint32_t j0 = first; j0 < jend; j0 += max_run)
+                    dst.push_back({a_row0, (uint32_t)(j0 == first), j0,
+                                   std::min(jend, j0 + max_run), ks_data});
+            }
+        }
+    };
+    // Every slice holds the same items but for its slice number: the list of one slice is built (and, for the long runs,
+    // sorted longest first) ONCE per run length and copied with the number filled in — built and sorted slice by slice,
+    // three candidate run lengths and the final list cost the first call at the headline shape 1.4 ms of host time, a first
+    // call at 10000 x 524288 twenty times that [r6].
+    const uint32_t kTailLen = std::min(kMaxRun, kTailRun);
+    std::vector<StripItem> proto_main, proto_tail;
+    bool have_main = false, have_tail = false;
+    auto by_length = [&](const StripItem& p, const StripItem& q) {
+        return (p.j1 - p.j0) + p.diag * kPerTile > (q.j1 - q.j0) + q.diag * kPerTile;
+    };
+    auto emit_copy = [&](uint32_t ks, uint32_t max_run, std::vector<StripItem>& dst) {
+        std::vector<StripItem>& proto = max_run == kMaxRun ? proto_main : proto_tail;
+        bool& have = max_run == kMaxRun ? have_main : have_tail;
+        if (!have) {
+            emit_slice_all(0u, max_run, proto);
+            if (max_run == kMaxRun) std::stable_sort(proto.begin(), proto.end(), by_length);
+            have = true;
+        }
+        const uint32_t ks_data = sh.one_slice_probe ? ks % 8u : ks;
+        const size_t at = dst.size();
+        dst.insert(dst.end(), proto.begin(), proto.end());
+        for (size_t k = at; k < dst.size(); ++k) dst[k].ks = ks_data;
+    };
+    // pair mode: this shard's share of the slice — the slice's items, longest first onto the least loaded shard
+    // (every shard walks the slices in the same order and computes the same deal)
+    auto emit_slice = [&](uint32_t ks, uint32_t max_run, std::vector<StripItem>& dst) {
+        if (!pair_mode) return (max_run == kMaxRun || max_run == kTailLen) ? emit_copy(ks, max_run, dst) : emit_slice_all(ks, max_run, dst);
+        std::vector<StripItem> all;
+        emit_slice_all(ks, max_run, all);
+        std::stable_sort(all.begin(), all.end(), [&](const StripItem& p, const StripItem& q) {
+            return strip_item_cost(p, kPerTile) > strip_item_cost(q, kPerTile);
+        });
+        for (const StripItem& it : all) {
+            const uint32_t r = (uint32_t)(std::min_element(pair_load.begin(), pair_load.end()) - pair_load.begin());
+            pair_load[r] += strip_item_cost(it, kPerTile);
+            if (r == shard_rank) dst.push_back(it);
+        }
+    };
+    // An XCD runs its list in order on ~128 workgroup slots. Long items keep the per-item cost
+    // (A fragments, ring fill, diagonal phase) low, but whatever is still running when the list
+    // runs dry sets the tail: with whole-length items the last slices leave most slots idle for
+    // up to one 157-stage item (10 % of the launch at the headline shape, by list-scheduling
+    // simulation and by measurement). So the LAST k2_tail_slices slices of every XCD are cut into
+    // short runs and merged longest-first, which lets the list end on many small items.
+    // leftover slices: short runs, dealt to the shards by longest-processing-time-first
+    std::vector<std::vector<StripItem>> leftover_of(8);
+    if (modulo_slices < n_kslices) {
+        std::vector<uint64_t> load(shard_count, 0);
+        for (uint32_t ks = modulo_slices; ks < n_kslices; ++ks) {
+            std::vector<StripItem> all;
+            emit_slice_all(ks, std::min(kMaxRun, kTailRun), all);
+            std::stable_sort(all.begin(), all.end(), [&](const StripItem& p, const StripItem& q) {
+                return strip_item_cost(p, kPerTile) > strip_item_cost(q, kPerTile);
+            });
+            const uint32_t xcd = (local++ / xg) % 8;  // one slice stays on one XCD's L2
+            for (const StripItem& it : all) {
+                const uint32_t r = (uint32_t)(std::min_element(load.begin(), load.end()) - load.begin());
+                load[r] += strip_item_cost(it, kPerTile);
+                if (r == shard_rank) leftover_of[xcd].push_back(it);
+            }
+        }
+    }
+    const uint32_t kTail = (uint32_t)std::max(0, sh.tail_slices);
+    std::vector<std::vector<StripItem>> per_xcd(8);
+    // (an estimate — `makespan` asked for — is made from the list of XCD 0 alone: the slices are dealt to the XCDs in turn
+    //  from 0, so its list is as long as any; the other seven lists and the launch order are not built)
+    const int n_lists = makespan ? 1 : 8;
+    for (int x = 0; x < n_lists; ++x) {
+        const std::vector<uint32_t>& sl = slices_of[x];
+        const size_t n_main = sl.size() > kTail ? sl.size() - kTail : 0;
+        // Within a slice, longest first: the XCD's dispatcher deals consecutive workgroups to its
+        // shader engines in turn, so a list that alternates long and short items (the two runs of
+        // one A tile) sends all the long ones to the same engines and leaves the others idle
+        // (schedule trace: 60 % of the slots occupied; max_run = 64, 72 or 100 lost 10-25 %).
+        for (size_t k = 0; k < n_main; ++k) {
+            if (!pair_mode) {   // (the copy of the sorted list of one slice)
+                emit_slice(sl[k], kMaxRun, per_xcd[x]);
+                continue;
+            }
+            std::vector<StripItem> one;
+            emit_slice(sl[k], kMaxRun, one);
+            std::stable_sort(one.begin(), one.end(), by_length);
+            per_xcd[x].insert(per_xcd[x].end(), one.begin(), one.end());
+        }
+        std::vector<StripItem> tail;
+        for (size_t k = n_main; k < sl.size(); ++k) emit_slice(sl[k], std::min(kMaxRun, kTailRun), tail);
+        tail.insert(tail.end(), leftover_of[x].begin(), leftover_of[x].end());
+        std::stable_sort(tail.begin(), tail.end(), [&](const StripItem& p, const StripItem& q) {
+            return (p.j1 - p.j0) + p.diag * kPerTile > (q.j1 - q.j0) + q.diag * kPerTile;
+        });
+        per_xcd[x].insert(per_xcd[x].end(), tail.begin(), tail.end());
+        // A short list (a few rounds of the XCD's ~128 slots: small N, or a 1/8 shard) is all
+        // tail: order the whole of it longest-first. The L2 locality that slice-major order buys
+        // is worth 1-2 %, the tail of a 2-round launch a third of its time (N = 2048: the
+        // schedule trace showed the launch draining for 24 of its 66 us).
+        if (per_xcd[x].size() <= (size_t)128 * (size_t)std::max(0, sh.lpt_rounds))
+            std::stable_sort(per_xcd[x].begin(), per_xcd[x].end(),
+                             [&](const StripItem& p, const StripItem& q) {
+                                 return (p.j1 - p.j0) + p.diag * kPerTile > (q.j1 - q.j0) + q.diag * kPerTile;
+                             });
+    }
+    if (makespan) {
+        // List-scheduling estimate of the launch, in stage times: an XCD hands its list, in order, to its workgroup
+        // slots (4 per CU); an item costs its stages + ~5 for the prologue (A rows, two images) + 3 more for the
+        // non-pipelined diagonal phase. Used to choose the run length (k2_max_run = 0).
+        // [r6] Only the list of XCD 0 is walked (above), and of a long list only the last 16 rounds, behind an evenly loaded start: what decides
+        // between the run lengths is the tail. The full walk of all eight lists took 2.5 ms of a first call at the
+        // headline shape (three candidates), 25 ms at 10000 x 524288.
+        auto cost_of = [&](const StripItem& it) { return (double)(it.j1 - it.j0) + (it.diag ? kPerTile + 3.0 : 0.0) + 5.0; };
+        const std::vector<StripItem>& list = per_xcd[0];
+        const size_t n_slots = std::max<uint32_t>(1, slots_per_xcd);
+        const size_t start = list.size() > 16 * n_slots ? list.size() - 16 * n_slots : 0;
+        double before = 0;
+        for (size_t k = 0; k < start; ++k) before += cost_of(list[k]);
+        std::vector<double> slot(n_slots, before / (double)n_slots);  // a min-heap of the slots' free times
+        auto later = [](double p, double q) { return p > q; };
+        for (size_t k = start; k < list.size(); ++k) {
+            std::pop_heap(slot.begin(), slot.end(), later);
+            slot.back() += cost_of(list[k]);
+            std::push_heap(slot.begin(), slot.end(), later);
+        }
+        const double worst = *std::max_element(slot.begin(), slot.end());
+        *makespan = worst;
+        items.clear();
+        return;
+    }
+    items.clear();
+    if (sh.persistent) {  // one contiguous queue per XCD
+        for (int x = 0; x < 8; ++x) {
+            queue_base[x] = (uint32_t)items.size();
+            queue_count[x] = (uint32_t)per_xcd[x].size();
+            items.insert(items.end(), per_xcd[x].begin(), per_xcd[x].end());
+        }
+    } else {  // dispatcher order: block b runs on XCD b % 8
+        size_t longest = 0;
+        for (auto& v : per_xcd) longest = std::max(longest, v.size());
+        for (size_t pos = 0; pos < longest; ++pos)
+            for (int x = 0; x < 8; ++x)
+                if (pos < per_xcd[x].size()) items.push_back(per_xcd[x][pos]);
+    }
+}
+
+// The shaping a pass runs with, from the options alone — NEVER from the calling rank. Where ownership is dealt along
+// the pair space (k2_shard_pairs, and the leftover slices of the default mode) every rank replays the same deal of
+// the same items, so every rank must cut the slices at the same run length: a choice made from one rank's own list
+// gave ranks [64, 96, 96] at N = 6144 / world 3 and pairs were dropped or counted twice. The automatic
+// run length (max_run = 0) is therefore the candidate whose SLOWEST rank schedules shortest; every rank evaluates
+// all ranks' lists and arrives at the same answer. Shared (through plan_strips) by the device path (ensure_strip_items)
+// and the host-only planner (storm_hip_strip_plan3), so that the plan the CPU tests partition is the plan the GPU launches.
+static StripShaping choose_strip_shaping(const StripOptions& o, const std::vector<RowRange>& ranges, uint32_t n_kslices,
+                                         uint32_t shard_count, uint32_t a_tile) {
+    StripShaping sh;
+    sh.tail_run = o.tail_run;
+    sh.tail_slices = o.tail_slices;
+    sh.lpt_rounds = o.lpt_rounds;
+    sh.xcd_group = o.xcd_group;
+    sh.persistent = o.persistent != 0;
+    sh.one_slice_probe = o.one_slice_probe != 0;
+    sh.pair_space = o.shard_pairs != 0;
+    sh.max_run = o.max_run;
+    if (o.max_run != 0) return sh;
+    // auto: the run length whose list schedules shortest (the tail of the launch decides between them: N = 6144 is
+    // 6 % faster with 64, N = 7168 / 8192 with 96, N = 3072 with 128; tools/archive/sweep_maxrun.py)
+    const uint32_t slots = (uint32_t)std::max(1, o.n_cus / 8 * 4);
+    const bool timing = timing_env();
+    double best = 0;
+    for (int cand : {96, 64, 128}) {
+        StripShaping trial = sh;
+        trial.max_run = cand;
+        double worst = 0;
+        size_t n_items = 0;
+        for (uint32_t r = 0; r < shard_count; ++r) {
+            std::vector<StripItem> tmp;
+            uint32_t qb[8], qc[8];
+            double ms = 0;
+            build_strip_items(trial, ranges, n_kslices, r, shard_count, a_tile, tmp, qb, qc, &ms, slots);
+            worst = std::max(worst, ms);
+            n_items += tmp.size();
+        }
+        if (timing)
+            fprintf(stderr, "[strip plan] max_run %3d: %zu items over %u rank(s), predicted makespan %.0f stages\n", cand,
+                    n_items, shard_count, worst);
+        if (sh.max_run == 0 || worst < best * 0.995) {   // (ties and near-ties go to the earlier candidate)
+            sh.max_run = cand;
+            best = worst;
+        }
+    }
+    return sh;
+}
+
+StripRequest strip_request(const StripOptions& opt, const std::vector<RowRange>& ranges, uint32_t n_kslices,
+                           uint32_t shard_rank, uint32_t shard_count, uint32_t a_tile) {
+    StripRequest rq;
+    rq.opt = opt;
+    rq.n_kslices = n_kslices;
+    rq.shard_rank = shard_rank;
+    rq.shard_count = shard_count;
+    rq.a_tile = a_tile;
+    rq.ranges_hash = ranges_hash(ranges);
+    return rq;
+}
+
+void plan_strips(const StripRequest& rq, const std::vector<RowRange>& ranges, std::vector<StripItem>& items,
+                 uint32_t queue_base[8], uint32_t queue_count[8], int* run_chosen) {
+    const StripShaping sh = choose_strip_shaping(rq.opt, ranges, rq.n_kslices, rq.shard_count, rq.a_tile);
+    if (run_chosen) *run_chosen = sh.max_run;
+    build_strip_items(sh, ranges, rq.n_kslices, rq.shard_rank, rq.shard_count, rq.a_tile, items, queue_base, queue_count);
+}
+
+// ---- write-mode tiles of 256 x 256 ----
+// Launch order of write-mode tiles for L2 reuse. A tile item streams 8 MiB per operand at the
+// headline shape (256 rows x all of k), twice an XCD's L2: in row-major order the 32 tiles an
+// XCD works on at a time share their A rows and nothing else, and the kernel fetched 12.6 GB per
+// launch from beyond L2 (47 % of its L2 requests missed; it ran at the HBM rate with the matrix
+// pipe 44 % busy: profiles/r02_d_*). Here the tiles [i0, i1) x [j0, j1) (upper triangle only when
+// `triangle`) are cut into groups of 4 x 8, group g goes to XCD g % 8 (block b runs on XCD b % 8:
+// observed, speed only), so the 32 workgroups of an XCD — which start together and advance along k
+// at the same pace — fetch 12 row-block slices per k-stage instead of 33.
+void xcd_grouped_tiles(uint32_t i0, uint32_t i1, uint32_t j0, uint32_t j1, bool triangle,
+                              std::vector<std::pair<uint16_t, uint16_t>>& out) {
+    std::vector<std::vector<std::pair<uint16_t, uint16_t>>> per_xcd(8);
+    uint32_t g = 0;
+    for (uint32_t gi = i0; gi < i1; gi += 4)
+        for (uint32_t gj = triangle ? std::max(j0, gi / 8 * 8) : j0; gj < j1; gj += 8) {
+            std::vector<std::pair<uint16_t, uint16_t>>& dst = per_xcd[g % 8];
+            const size_t before = dst.size();
+            for (uint32_t i = gi; i < std::min(gi + 4, i1); ++i)
+                for (uint32_t j = std::max(gj, triangle ? i + 1 : gj); j < std::min(gj + 8, j1); ++j)
+                    dst.emplace_back((uint16_t)i, (uint16_t)j);
+            if (dst.size() != before) ++g;
+        }
+    size_t longest = 0;
+    for (auto& v : per_xcd) longest = std::max(longest, v.size());
+    for (size_t pos = 0; pos < longest; ++pos)
+        for (int x = 0; x < 8; ++x)
+            if (pos < per_xcd[x].size()) out.push_back(per_xcd[x][pos]);
+}
+
+// The item table of a matrix-output launch. The tile kernel holds one workgroup per CU, so n tiles take ceil(n / CUs)
+// rounds and a nearly empty last round costs a whole one. `cost` (optional, one per tile, 1 = a full tile): the tiles
+// beyond the last full round of workgroups are cut along k into parts of about equal cost, as many as fill the CUs — a
+// short tile (diagonal or ragged under tilebits8_kernel) into fewer parts than a full one.
+void plan_matrix_tiles(const MatrixTilesRequest& rq, std::vector<MfmaItem>& items, MatrixPlan* plan) {
+    const std::vector<std::pair<uint16_t, uint16_t>>& tiles = rq.tiles;
+    const uint32_t total_stages = rq.total_stages;
+    const size_t slots = (size_t)std::max(1u, rq.n_cus);
+    size_t leftover = rq.split ? tiles.size() % slots : 0;
+    // f32 accumulators hold exact integers below 2^24: an item may span at most kMaxExactStages
+    // stages (128 bits each). Rows of 2^24 bits and more are therefore cut along k for EVERY tile;
+    // the parts add into the cleared window like the parts of the last round do.
+    constexpr uint32_t kMaxExactStages = (1u << 24) / 128u - 1u;
+    uint32_t min_parts = 1;
+    if (total_stages > kMaxExactStages) {
+        leftover = tiles.size();
+        min_parts = (total_stages + kMaxExactStages - 1) / kMaxExactStages;
+    }
+    const size_t n_full = tiles.size() - leftover;
+    const uint32_t max_parts = std::max(min_parts, total_stages / (uint32_t)rq.min_part);
+    auto cost_of = [&](size_t t) { return rq.cost.empty() ? 1.0f : std::max(0.05f, rq.cost[t]); };
+    double left_cost = 0;
+    for (size_t t = n_full; t < tiles.size(); ++t) left_cost += cost_of(t);
+    const double per_part = left_cost / (double)slots;  // what one CU should get of the last round
+    std::vector<uint32_t> parts_of(leftover, 1);
+    size_t n_parts = 0;
+    for (size_t t = n_full; t < tiles.size(); ++t) {
+        const double want = per_part > 0 ? cost_of(t) / per_part : 1.0;
+        n_parts += parts_of[t - n_full] = std::min(max_parts, std::max(min_parts, (uint32_t)want));
+    }
+    // rounding down leaves CUs without a part: give them to the tiles whose parts are longest (never
+    // more parts than CUs — a 257th item would wait for a whole part)
+    while (min_parts == 1 && n_parts < slots && leftover > 0) {
+        size_t best = leftover;
+        double longest = 0;
+        for (size_t i = 0; i < leftover; ++i) {
+            const double len = cost_of(n_full + i) / parts_of[i];
+            if (parts_of[i] < max_parts && len > longest) longest = len, best = i;
+        }
+        if (best == leftover) break;
+        ++parts_of[best];
+        ++n_parts;
+    }
+    items.clear();
+    for (size_t t = 0; t < n_full; ++t) items.push_back({tiles[t].first, tiles[t].second, 0, total_stages});
+    for (size_t t = n_full; t < tiles.size(); ++t) {
+        const uint32_t parts = parts_of[t - n_full];
+        for (uint32_t p = 0; p < parts; ++p) {
+            // cuts on multiples of 4 stages: the 16x16 kernel's stage is two of these (128 bytes of
+            // an FP4 row), the bit-operand kernels' four (512 bits)
+            const uint32_t s0 = (uint32_t)((uint64_t)(total_stages / 4) * p / parts) * 4u;
+            const uint32_t s1 = (uint32_t)((uint64_t)(total_stages / 4) * (p + 1) / parts) * 4u;
+            items.push_back({tiles[t].first, tiles[t].second, s0, s1 - s0});
+        }
+    }
+    plan->n_items = (uint32_t)items.size();
+    plan->n_full = (uint32_t)n_full;
+    plan->n_cut = (uint32_t)leftover;
+    for (size_t t = n_full; t < tiles.size(); ++t) items.push_back({tiles[t].first, tiles[t].second, 0u, 0u});   // the cut tiles once more: the windows to clear
+}
+
+// ---- K2h (tile128_kernel): 128 x 128 tiles for matrices of few 256 x 256 tiles, k-parts whose sums meet inside the launch ----
+// The item list of a K2h launch. An item is one part of one tile; a tile of several parts has its sums meet in the launch
+// (tile128_kernel). The chip offers `slots` places for workgroups, one or two per CU:
+//   * whole rounds of tiles (slots tiles each) stay whole;
+//   * the tiles beyond the last whole round — all of them where there are fewer tiles than slots — are cut along k into
+//     EQUAL parts, together as many as there are slots: a tile gets its share of the slots rounded down, the slots left
+//     over go to the tiles whose parts are longest (the longest part ends the launch; cutting the chunk stream at equal
+//     distances across the tile boundaries leaves crumbs that must join a neighbour, and the parts so lengthened — 28
+//     chunks where 18 were due at 1024 rows — ended the launch);
+//   * one or two slots per CU: whichever loads a CU less, counting what an item costs besides its chunks.
+// The tiles on the diagonal come last (they are the ones cut: beside a second workgroup their chunks are cheaper — one wave
+// idle, one at three blocks of four — alone on a CU they take as long as any). Items longest first: the dispatcher hands
+// the short ones to the slots that end first. Pure host computation.
+void plan_tile128(const Tile128Request& rq, Tile128Plan* plan) {
+    const uint32_t ia0 = rq.ia0, ia1 = rq.ia1, jb0 = rq.jb0, jb1 = rq.jb1, total_stages = rq.total_stages, n_cus = rq.n_cus;
+    const bool triangle = rq.triangle != 0, narrow_windows = rq.narrow_windows != 0;
+    const int slots_per_cu = rq.slots_per_cu, diag_cost_pct = rq.diag_cost_pct;
+    int min_chunks = rq.min_chunks;
+    struct T { uint16_t I, J; bool diag; };
+    std::vector<T> tiles;
+    // groups of 4 x 8 neighbouring tiles first (they share rows), the tiles on the diagonal last
+    for (int pass = 0; pass < 2; ++pass)
+        for (uint32_t gi = ia0; gi < ia1; gi += 4)
+            for (uint32_t gj = jb0; gj < jb1; gj += 8)
+                for (uint32_t i = gi; i < std::min(gi + 4, ia1); ++i)
+                    for (uint32_t j = gj; j < std::min(gj + 8, jb1); ++j) {
+                        if (triangle && j < i) continue;
+                        const bool diag = triangle && j == i;
+                        if (diag != (pass == 1)) continue;
+                        tiles.push_back({(uint16_t)i, (uint16_t)j, diag});
+                    }
+    const uint32_t nC = total_stages / 4u;
+    plan->n_tiles = (uint32_t)tiles.size();
+    plan->n_windows = 0;
+    plan->items.clear();
+    if (tiles.empty() || nC == 0) return;
+    constexpr uint32_t kMaxExactChunks = (1u << 24) / 512u - 1u;   // f32 accumulators: an item stays below 2^24 bits of k
+    constexpr double kItemChunks = 5.0;                             // what an item costs besides its chunks, in chunks
+    min_chunks = std::max(min_chunks, (int)(nC / 32000u) + 1);      // (a tile has fewer than 2^15 parts: PartItem::part)
+    const uint32_t min_parts = (nC + kMaxExactChunks - 1) / kMaxExactChunks;
+    const uint32_t max_parts = std::max(min_parts, nC / (uint32_t)min_chunks);
+    const size_t nT = tiles.size();
+    std::vector<uint32_t> parts_of(nT), best_parts;
+    double best_load = 0;
+    for (int spc = 1; spc <= 2; ++spc) {
+        if (slots_per_cu > 0 && spc != slots_per_cu) continue;
+        const size_t slots = (size_t)n_cus * spc;
+        const double dcost = spc >= 2 ? diag_cost_pct / 100.0 : 1.0;
+        auto cost_of = [&](size_t t) { return tiles[t].diag ? dcost : 1.0; };
+        const size_t n_whole = min_parts > 1 ? 0 : nT / slots * slots;
+        std::fill(parts_of.begin(), parts_of.end(), 1u);
+        double rest = 0;
+        for (size_t t = n_whole; t < nT; ++t) rest += cost_of(t) * nC;
+        const double seg = rest / (double)slots;
+        size_t n_items = n_whole;
+        for (size_t t = n_whole; t < nT; ++t)
+            n_items += parts_of[t] = std::min(max_parts, std::max(min_parts, (uint32_t)(cost_of(t) * nC / std::max(seg, 1e-9))));
+        while (n_items < n_whole + slots) {   // the slots left over: to the tiles whose parts are longest
+            size_t best = nT;
+            double longest = 0;
+            for (size_t t = n_whole; t < nT; ++t) {
+                const double len = cost_of(t) * nC / parts_of[t];
+                if (parts_of[t] < max_parts && len > longest) longest = len, best = t;
+            }
+            if (best == nT) break;
+            ++parts_of[best];
+            ++n_items;
+        }
+        double longest = 0;
+        for (size_t t = n_whole; t < nT; ++t) longest = std::max(longest, cost_of(t) * std::ceil((double)nC / parts_of[t]));
+        // a CU's load: its slots' whole tiles and one part each, and what its items cost besides
+        const double load = spc * ((double)(n_whole / slots) * nC + longest) + kItemChunks * (double)n_items / n_cus;
+        if (best_parts.empty() || load < best_load) best_load = load, best_parts = parts_of;
+    }
+    for (uint32_t t = 0; t < nT; ++t) {
+        const uint32_t np = best_parts[t];
+        // windows of 16-bit counts while every part of the tile stays below 2^16 bits of k (127 chunks)
+        const uint16_t narrow = (np > 1 && (nC + np - 1) / np <= 127u && narrow_windows) ? kThNarrow : (uint16_t)0;
+        for (uint32_t p = 0; p < np; ++p) {
+            const uint32_t c0 = (uint32_t)((uint64_t)nC * p / np), c1 = (uint32_t)((uint64_t)nC * (p + 1) / np);
+            plan->items.push_back({tiles[t].I, tiles[t].J, c0 * 4u, (c1 - c0) * 4u, t, np > 1 ? plan->n_windows : 0u,
+                                   (uint16_t)((uint16_t)p | narrow), (uint16_t)np});
+        }
+        if (np > 1) plan->n_windows += np;
+    }
+    std::stable_sort(plan->items.begin(), plan->items.end(),
+                     [](const PartItem& a, const PartItem& b) { return a.n_stages > b.n_stages; });
+}
+
+// ---- K2q work decomposition: the stage stream of bitstream_kernel, cut into equal shares ----
+// `groups` workgroups; workgroup w walks segs[first[w] .. first[w+1]).
+BitstreamRequest bitstream_request(const BitstreamShaping& sh, const std::vector<RowRange>& ranges, uint32_t n_kslices,
+                                   uint32_t shard_rank, uint32_t shard_count, uint32_t n_cus, uint64_t pitch_bytes) {
+    return {sh, n_kslices, shard_rank, shard_count, n_cus, pitch_bytes, ranges_hash(ranges)};
+}
+void build_bitstream(const BitstreamRequest& rq, const std::vector<RowRange>& ranges, BitstreamPlan& plan) {
+    const BitstreamShaping& sh = rq.sh;
+    const uint32_t n_kslices = rq.n_kslices, shard_rank = rq.shard_rank, shard_count = rq.shard_count, n_cus = rq.n_cus;
+    const uint64_t pitch_bytes = rq.pitch_bytes;
+    // natural segments, k-slice major: every A tile of every range with the later tiles dealt cyclically
+    struct Nat {
+        BitSeg s;
+        uint64_t start;  // position of its first stage in the stream
+    };
+    std::vector<Nat> nat;
+    uint64_t L = 0;
+    for (uint32_t ks = 0; ks < n_kslices; ++ks)
+        for (const RowRange& rg : ranges) {
+            if (rg.r1 < rg.r0 + 2) continue;
+            const uint32_t b0 = (uint32_t)(rg.r0 / kStripBRows);
+            const uint32_t nb = (uint32_t)((rg.r1 - rg.r0 + kStripBRows - 1) / kStripBRows);
+            const uint32_t nT = (nb + 3u) / 4u;
+            auto blocks_of = [&](uint32_t J) { return std::min(4u, nb - 4u * J); };
+            for (uint32_t I = 0; I < nT; ++I) {
+                // tile I takes the (nT - 1) / 2 tiles behind it (cyclically); with an even number of
+                // tiles the opposite one goes to the lower tile on even k-slices, to the upper on odd ones
+                uint32_t take = (nT - 1u) / 2u;
+                if (nT > 1u && nT % 2u == 0u && ((I < nT / 2u) == ((ks & 1u) == 0u))) ++take;
+                uint32_t n_b = 0;
+                for (uint32_t d = 1; d <= take; ++d) n_b += blocks_of((I + d) % nT);
+                BitSeg s = {};
+                s.a_blk = b0 + 4u * I;
+                s.ks = ks;
+                s.b_first = (I + 1u == nT) ? 0u : 4u * (I + 1u);
+                s.n_b = n_b;
+                s.range_b0 = b0;
+                s.range_nb = nb;
+                s.flags = kBsDiag | (((I + ks) & 3u) << 8);
+                nat.push_back({s, L});
+                L += 4u + n_b;
+            }
+        }
+    plan.segs.clear();
+    plan.first.clear();
+    plan.bases.clear();
+    plan.first_stage.clear();
+    plan.stages = 0;
+    plan.max_stages = 0;
+    // this shard's part of the stream (contiguous: a shard touches a contiguous range of k-slices)
+    const uint64_t lo = L * shard_rank / shard_count, hi = L * (shard_rank + 1ull) / shard_count;
+    const uint64_t Ls = hi - lo;
+    // workgroups: as many per CU as the share of a CU is worth cutting, and never a workgroup
+    // beyond the accumulators' exact range
+    uint32_t per_cu = (uint32_t)sh.groups_per_cu;
+    if (per_cu == 0) {
+        const uint64_t share = Ls / std::max(1u, n_cus);
+        per_cu = share >= 3ull * (uint64_t)sh.min_piece ? 3u : share >= 2ull * (uint64_t)sh.min_piece ? 2u : 1u;
+    }
+    uint64_t G = (uint64_t)n_cus * per_cu;
+    // A long stream is cut into MORE shares than the chip holds workgroups (three per CU): the waves of a SIMD
+    // do not advance evenly (its arbiter prefers the oldest), so equal shares end at very different times and
+    // the last ones run alone, at a lone wave's 60 % of the pipe; with shares of ~80 stages a CU that finishes
+    // one early simply gets the next (headline shape: 883 us with 768 shares, 821 with 6144; N = 6144: 341 ->
+    // 317; from ~30 stages down the four stages that bring a continued segment's A rows in cost more than the
+    // tail does: N = 2048 is fastest with 768). Never a share beyond the accumulators' exact range.
+    // Whole rounds of the chip's slots only: 870 shares on 768 slots leave a fourth share to 102 CUs (N = 4096:
+    // 185 us against 152 with 768 or 1536).
+    if (sh.groups_per_cu == 0 && per_cu == 3u) {
+        const uint64_t slots = (uint64_t)n_cus * 3u;
+        const uint64_t rounds = (Ls + slots * (uint64_t)std::max(1, sh.long_piece) / 2) /
+                                (slots * (uint64_t)std::max(1, sh.long_piece));
+        // up to ~220 stages per slot ONE round of weighted shares (below) is faster than the dynamic deal, which
+        // pays four operand-only stages per cut (N = 6144: 308 against 314 us; N = 8192: 545 against 538)
+        G = slots * (Ls <= slots * (uint64_t)sh.single_round_max ? 1ull : std::max<uint64_t>(1, rounds));
+    }
+    G = std::max<uint64_t>(G, (Ls + kBsMaxStages / 2 - 1) / (kBsMaxStages / 2));
+    G = std::max<uint64_t>(1, std::min<uint64_t>(G, std::max<uint64_t>(1, Ls / 4)));
+    if (Ls == 0) G = 0;
+    plan.groups = (uint32_t)G;
+    if (G == 0) {
+        plan.first.push_back(0);
+        plan.first_stage.push_back(0);
+        return;
+    }
+    // cut positions, snapped: never inside a tile's own four stages, never leaving a stub of a run
+    auto seg_at = [&](uint64_t p) {  // natural segment holding stream position p (< L)
+        size_t a = 0, b = nat.size();
+        while (b - a > 1) {
+            const size_t m = (a + b) / 2;
+            if (nat[m].start <= p) a = m; else b = m;
+        }
+        return a;
+    };
+    // Shares of ONE round are not equal. The waves of a SIMD do not take turns: its arbiter issues for the oldest
+    // wave that can go, and a wave alone reaches ~60 % of the matrix pipe (one instruction every four cycles). Of
+    // three equal shares per CU the first-dispatched workgroup ends after 0.55 of the kernel, the second at 0.75,
+    // the third runs the last quarter nearly alone (N = 2048: 24 / 33 / 42 us; tools/archive/stream_trace.py, end by
+    // dispatch round; workgroup w is dispatched in round w / n_cus, one per CU per round). Shares in the proportion
+    // 100 : 120 : 60 let the three end closer together: -3 % at N = 2048, -6 % at 3072 ... 4096, -2 % at 6144
+    // against the dynamic deal (profiles/r03_e_stream_weights.txt; the optimum is flat: 100 : 100 : 50 and
+    // 100 : 125 : 65 are within 1 %). Shares shorter than ~16 stages keep equal lengths: start-up and drain
+    // dominate them, and whole segments as shares (no cut, no operand-only stages, but two workgroups per CU) lose
+    // 15 % at N = 1024.
+    std::vector<uint32_t> weight(G, 100u);
+    if (G == (uint64_t)n_cus * 3u && n_cus % 8u == 0u && Ls >= G * (uint64_t)sh.weighted_min) {
+        const uint32_t wr[3] = {100u, (uint32_t)sh.w3_1, (uint32_t)sh.w3_2};
+        for (uint64_t p = 0; p < G; ++p) weight[p] = std::max(1u, wr[(p % (G / 8)) / (n_cus / 8u)]);
+    }
+    std::vector<uint64_t> cum(G + 1, 0);
+    for (uint64_t p = 0; p < G; ++p) cum[p + 1] = cum[p] + weight[p];
+    std::vector<uint64_t> cut(G + 1);
+    for (uint64_t k = 0; k <= G; ++k) {
+        uint64_t c = lo + (uint64_t)((unsigned __int128)Ls * cum[k] / cum[G]);
+        if (c < L) {
+            const Nat& n = nat[seg_at(c)];
+            const uint64_t off = c - n.start, len = 4ull + n.s.n_b;
+            if (off > 0 && off < 4ull + (uint64_t)sh.min_run) c = n.start;
+            else if (off > 0 && len - off < (uint64_t)sh.min_run) c = n.start + len;
+        }
+        cut[k] = c;
+    }
+    for (uint64_t k = 1; k <= G; ++k) cut[k] = std::max(cut[k], cut[k - 1]);
+    // piece p of the stream goes to workgroup w with p = (w % 8) * (G / 8) + w / 8: block w runs on XCD
+    // w % 8 (observed; speed only), so an XCD's workgroups hold one contiguous eighth of the stream
+    std::vector<uint32_t> piece_of(G);
+    for (uint64_t w = 0; w < G; ++w) piece_of[w] = (uint32_t)(G % 8 == 0 ? (w % 8) * (G / 8) + w / 8 : w);
+    for (uint64_t w = 0; w < G; ++w) {
+        const uint64_t p = piece_of[w];
+        plan.first.push_back((uint32_t)plan.segs.size());
+        uint64_t c0 = cut[p], c1 = cut[p + 1];
+        uint32_t mine = 0;
+        while (c0 < c1) {
+            const Nat& n = nat[seg_at(c0)];
+            const uint64_t len = 4ull + n.s.n_b, off = c0 - n.start;
+            const uint64_t end = std::min(c1, n.start + len);
+            BitSeg s = n.s;
+            if (off == 0) {
+                s.n_b = (uint32_t)(end - n.start - 4ull);
+            } else {  // continues a cut segment: its four blocks only bring the A rows in
+                const uint32_t skip = (uint32_t)(off - 4ull);
+                s.flags &= ~kBsDiag;
+                s.b_first = (n.s.b_first + skip) % n.s.range_nb;
+                s.n_b = (uint32_t)(end - c0);
+            }
+            plan.segs.push_back(s);
+            mine += 4u + s.n_b;
+            c0 = end;
+        }
+        plan.stages += mine;
+        plan.max_stages = std::max(plan.max_stages, mine);
+    }
+    plan.first.push_back((uint32_t)plan.segs.size());
+    // the DMA's view of the same stream: the start of every stage's 64 rows x 64 B, in 64-byte units from the
+    // matrix ((ks * 64 + blk * 64 * pitch) / 64; the pitch is a multiple of 64 bytes)
+    plan.bases.reserve(plan.stages);
+    for (uint64_t w = 0; w < G; ++w) {
+        plan.first_stage.push_back((uint32_t)plan.bases.size());
+        for (uint32_t si = plan.first[w]; si < plan.first[w + 1]; ++si) {
+            const BitSeg& sg = plan.segs[si];
+            for (uint32_t i = 0; i < 4u + sg.n_b; ++i) {
+                uint32_t blk;
+                if (i < 4u) {
+                    blk = sg.a_blk + i;
+                } else {
+                    uint32_t rel = sg.b_first + (i - 4u);
+                    if (rel >= sg.range_nb) rel -= sg.range_nb;
+                    blk = sg.range_b0 + rel;
+                }
+                plan.bases.push_back((uint32_t)((uint64_t)sg.ks + (uint64_t)blk * pitch_bytes));
+            }
+        }
+    }
+    plan.first_stage.push_back((uint32_t)plan.bases.size());
+}
+
+}  // namespace storm
+
+// Host-only view of the default path's work decomposition (no device is touched): what a shard
+// of a multi-GPU run multiplies, so that the partition of the pair space can be checked — and
+// rehearsed with CPU partials — without a GPU (tests/test_dist_cpu.py).
+extern "C" int storm_hip_matrix_plan(uint64_t n_rows_a, uint64_t n_rows_b, uint32_t n_words, uint64_t band_row0,
+                                     uint64_t band_rows, uint32_t n_cus, int slots_per_cu, int min_chunks, int diag_cost_pct,
+                                     uint32_t* out, uint64_t capacity_items, uint64_t* n_items) {
+    using namespace storm;
+    if (!n_items || n_rows_a == 0 || n_words == 0 || n_cus == 0 || slots_per_cu < 0 || slots_per_cu > 2 || min_chunks < 1 ||
+        diag_cost_pct < 10 || diag_cost_pct > 100) {
+        set_error("matrix_plan: bad arguments");
+        return STORM_HIP_EINVAL;
+    }
+    try {
+        const uint32_t total_stages = (n_words + 7u) / 8u * 4u;
+        Tile128Plan plan;
+        if (n_rows_b == 0) {   // triangle (a band of it)
+            const uint64_t end = std::min(n_rows_a, band_row0 + (band_rows ? band_rows : n_rows_a));
+            if (band_row0 < end)
+                plan_tile128({(uint32_t)(band_row0 / kThTile), (uint32_t)((end + kThTile - 1) / kThTile), 0u,
+                              (uint32_t)((n_rows_a + kThTile - 1) / kThTile), 1u, total_stages, n_cus, slots_per_cu, min_chunks,
+                              diag_cost_pct, 1u}, &plan);
+        } else {   // rectangle: B's tiles count on behind A's rows padded to 256
+            const uint64_t rows_a = (n_rows_a + kTile - 1) / kTile * kTile;
+            plan_tile128({0u, (uint32_t)((n_rows_a + kThTile - 1) / kThTile), (uint32_t)(rows_a / kThTile),
+                          (uint32_t)((rows_a + n_rows_b + kThTile - 1) / kThTile), 0u, total_stages, n_cus, slots_per_cu,
+                          min_chunks, diag_cost_pct, 1u}, &plan);
+        }
+        *n_items = plan.items.size();
+        if (out) {
+            if (capacity_items < plan.items.size()) {
+                set_error("matrix_plan: capacity %llu < %zu items", (unsigned long long)capacity_items, plan.items.size());
+                return STORM_HIP_EINVAL;
+            }
+            for (size_t k = 0; k < plan.items.size(); ++k) {
+                const PartItem& it = plan.items[k];
+                uint32_t* o = out + 8 * k;
+                o[0] = it.I, o[1] = it.J, o[2] = it.stage0 / 4u, o[3] = it.n_stages / 4u, o[4] = it.tile;
+                o[5] = (uint32_t)(it.part & (uint16_t)~kThNarrow), o[6] = it.n_parts, o[7] = (it.part & kThNarrow) ? 1u : 0u;
+            }
+        }
+        return STORM_HIP_OK;
+    } catch (const std::exception& e) {
+        set_error("matrix_plan: %s", e.what());
+        return STORM_HIP_ENOMEM;
+    }
+}
+
+extern "C" int storm_hip_strip_plan3(uint64_t n_rows, uint32_t n_words, uint32_t shard_rank,
+                                     uint32_t shard_count, int form, int pair_space, int max_run, int tail_run,
+                                     int tail_slices, int lpt_rounds, uint32_t n_cus, uint32_t* out,
+                                     uint64_t capacity_items, uint64_t* n_items, int* run_chosen) {
+    using namespace storm;
+    if (!n_items || shard_count == 0 || shard_rank >= shard_count || n_words == 0 || (form != 0 && form != 1) ||
+        max_run < 0 || max_run > 4096 || tail_run < 1 || tail_run > 4096 || tail_slices < 0 || tail_slices > 255 ||
+        lpt_rounds < 0 || lpt_rounds > 63 || n_cus == 0) {
+        set_error("strip_plan: bad arguments");
+        return STORM_HIP_EINVAL;
+    }
+    try {
+        // slices that hold data: form 0 (FP4 shadow, launch_pairw_mfma_ranges): 256 consecutive bits each;
+        // form 1 (K2b, launch_pairw_bits_ranges): slice ks = class pair ks & 1 of the 512-bit chunk ks / 2
+        const uint32_t n_kslices = form == 0 ? (n_words + 3u) / 4u : 2u * ((n_words + 7u) / 8u);
+        std::vector<RowRange> ranges;
+        if (n_rows > 1) ranges.push_back({0, n_rows});
+        std::vector<StripItem> items;
+        uint32_t qb[8], qc[8];
+        StripOptions o;
+        o.max_run = max_run;
+        o.tail_run = tail_run;
+        o.tail_slices = tail_slices;
+        o.lpt_rounds = lpt_rounds;
+        o.shard_pairs = pair_space != 0;
+        o.n_cus = (int)n_cus;
+        o.xcd_group = form == 0 ? 1 : 2;
+        // exactly what ensure_strip_items launches for these options (one function plans both)
+        plan_strips(strip_request(o, ranges, n_kslices, shard_rank, shard_count, (uint32_t)kStripATile), ranges, items, qb, qc,
+                    run_chosen);
+        *n_items = items.size();
+        if (out)
+            for (uint64_t i = 0; i < std::min<uint64_t>(capacity_items, items.size()); ++i) {
+                out[i * 5 + 0] = items[i].a_row0;
+                out[i * 5 + 1] = items[i].diag;
+                out[i * 5 + 2] = items[i].j0;
+                out[i * 5 + 3] = items[i].j1;
+                out[i * 5 + 4] = items[i].ks;
+            }
+    } catch (const std::exception& e) {
+        set_error("strip_plan: %s", e.what());
+        return STORM_HIP_ENOMEM;
+    }
+    return STORM_HIP_OK;
+}
+
+// The context's default options on a 256-CU device (what a fresh context launches on an MI355X).
+extern "C" int storm_hip_strip_plan2(uint64_t n_rows, uint32_t n_words, uint32_t shard_rank,
+                                     uint32_t shard_count, int form, int pair_space, uint32_t* out,
+                                     uint64_t capacity_items, uint64_t* n_items) {
+    const storm::StripOptions d;
+    return storm_hip_strip_plan3(n_rows, n_words, shard_rank, shard_count, form, pair_space, d.max_run, d.tail_run,
+                                 d.tail_slices, d.lpt_rounds, (uint32_t)d.n_cus, out, capacity_items, n_items, nullptr);
+}
+
+extern "C" int storm_hip_strip_plan(uint64_t n_rows, uint32_t n_words, uint32_t shard_rank,
+                                    uint32_t shard_count, uint32_t* out, uint64_t capacity_items,
+                                    uint64_t* n_items) {
+    return storm_hip_strip_plan2(n_rows, n_words, shard_rank, shard_count, 0, 0, out, capacity_items, n_items);
+}
+
+extern "C" int storm_hip_stream_plan(uint64_t n_rows, uint32_t n_words, uint32_t shard_rank, uint32_t shard_count,
+                                     uint32_t n_cus, uint32_t* out, uint64_t capacity_segments,
+                                     uint64_t* n_segments, uint32_t* n_workgroups) {
+    using namespace storm;
+    if (!n_segments || shard_count == 0 || shard_rank >= shard_count || n_words == 0 || n_cus == 0) {
+        set_error("stream_plan: bad arguments");
+        return STORM_HIP_EINVAL;
+    }
+    try {
+        std::vector<RowRange> ranges;
+        if (n_rows > 1) ranges.push_back({0, n_rows});
+        BitstreamPlan plan;
+        const uint64_t stride_words = ((uint64_t)n_words + kChunkWords - 1) / kChunkWords * kChunkWords;
+        build_bitstream(bitstream_request(BitstreamShaping{}, ranges, (n_words + 7u) / 8u, shard_rank, shard_count, n_cus,
+                                          stride_words * 8),
+                        ranges, plan);
+        *n_segments = plan.segs.size();
+        if (n_workgroups) *n_workgroups = plan.groups;
+        if (out) {
+            uint32_t wg = 0;
+            for (uint64_t i = 0; i < std::min<uint64_t>(capacity_segments, plan.segs.size()); ++i) {
+                while (wg + 1 < plan.first.size() && plan.first[wg + 1] <= i) ++wg;
+                const BitSeg& sg = plan.segs[i];
+                uint32_t* o = out + i * 8;
+                o[0] = wg;
+                o[1] = sg.a_blk;
+                o[2] = sg.ks;
+                o[3] = sg.b_first;
+                o[4] = sg.n_b;
+                o[5] = sg.range_nb;
+                o[6] = sg.flags & kBsDiag;
+                o[7] = 4u + sg.n_b;
+            }
+        }
+    } catch (const std::exception& e) {
+        set_error("stream_plan: %s", e.what());
+        return STORM_HIP_ENOMEM;
+    }
+    return STORM_HIP_OK;
+}

@@ -1,0 +1,225 @@
+// storm_hip_plan.h — the work lists of the matrix-core kernels (K2*): the records the planners write and the kernels
+// read, the geometry both sides need, and the planners themselves (storm_hip_plan.cpp: plain C++, no device, no HIP
+// runtime). storm_hip_internal.h includes this header; the planners see nothing of the context.
+//
+// Every planner takes ONE request struct that holds all it reads besides the row ranges (which travel next to it and
+// are part of the request by their hash). The launchers cache an uploaded list under the request it was planned from
+// and compare requests for equality, so an option the planner reads cannot be missing from the key.
+#pragma once
+
+#include <cstdint>
+#include <cstring>
+#include <type_traits>
+#include <utility>
+#include <vector>
+
+namespace storm {
+
+void set_error(const char* fmt, ...);   // storm_hip.hip
+bool timing_env();                      // STORM_HIP_TIMING is set (read once)
+
+// A request is compared bytewise: it must have no padding (every member a 32- or 64-bit integer).
+template <class T>
+inline bool same_request(const T& a, const T& b) {
+    static_assert(std::has_unique_object_representations_v<T>, "a request struct with padding cannot be compared with memcmp");
+    return !memcmp(&a, &b, sizeof(T));
+}
+
+constexpr int kChunkWords = 64;        // K1's k-chunk, one 64-bit word per lane: a row's stride is a multiple of it
+
+// ---- K2 tiles (pairw_fp4_kernel and the write-mode tile kernels) ----
+constexpr int kTile = 256;             // rows per tile side
+constexpr int kStageBytes = 64;        // bytes of one row per stage = 128 nibbles = 128 bits of k
+constexpr uint32_t kGroupStages = 32;  // multi-GPU ownership unit along k: 32 stages = 64 words
+
+struct MfmaItem {
+    uint16_t I, J;       // row-block indices, I <= J
+    uint32_t stage0;     // first stage of the k-slice
+    uint32_t n_stages;   // stages in this k-slice
+};
+static_assert(sizeof(MfmaItem) == 12, "read by device code");
+
+// ---- K2s / K2b strips ----
+constexpr uint32_t kOwnSlices = 4;                       // strips: k-slices per ownership unit
+constexpr int kStripRowBytes = 128;                      // 256 bits of k as nibbles
+constexpr int kStripBRows = 64;                          // B rows per stage
+constexpr int kStripWaves = 4;                           // waves per workgroup = A tile / 64 rows
+constexpr int kStripATile = 64 * kStripWaves;            // A rows per workgroup (256; 8 waves / 512 rows measured slower)
+
+struct StripItem {
+    uint32_t a_row0;  // first row of the A tile (kStripATile rows, multiple of 64)
+    uint32_t diag;    // 1: the item starts with the stages of its own tile (strict upper part)
+    uint32_t j0, j1;  // then the later B stages: 64-row blocks [j0, j1), walked downwards
+    uint32_t ks;      // k-slice index (128 bytes of the nibble rows each)
+};
+static_assert(sizeof(StripItem) == 20, "read by device code");
+
+// ---- K2q (bitstream_kernel) ----
+struct BitSeg {
+    uint32_t a_blk;     // first 64-row block of the A tile (4 blocks; absolute block index)
+    uint32_t ks;        // k-slice: 64 bytes of every bit row
+    uint32_t b_first;   // first later block, relative to range_b0, cyclic over range_nb
+    uint32_t n_b;       // later blocks = stages behind the tile's own four
+    uint32_t range_b0;  // first block of the all-pairs problem (row range) the tile belongs to
+    uint32_t range_nb;  // blocks of that problem: the cyclic order wraps here
+    uint32_t flags;     // bit 0: the tile's own four stages are multiplied (else they only bring A in); bits 8-9: rotation
+    uint32_t pad;
+};
+static_assert(sizeof(BitSeg) == 32, "read by device code");
+constexpr uint32_t kBsDiag = 1u;
+constexpr uint32_t kBsMaxStages = 8192;      // per workgroup: accumulators stay below 2^22 (in halves: 2^23)
+
+// ---- K2h (tile128_kernel) ----
+constexpr uint32_t kThTile = 128u;
+struct PartItem {
+    uint16_t I, J;               // tile indices in units of 128 (virtual) rows
+    uint32_t stage0, n_stages;   // the item's k range in 128-bit stages (multiples of 4)
+    uint32_t tile;               // the tile's index among the launch's tiles: its ticket
+    uint32_t win0;               // the first of the tile's n_parts windows in `parts` (part p: win0 + p)
+    uint16_t part, n_parts;      // this item is part `part` of `n_parts` of its tile; bit 15 of `part`: the tile's windows hold
+                                 // 16-bit counts (every part of the tile covers fewer than 2^16 bits of k)
+};
+static_assert(sizeof(PartItem) == 24, "read by device code");
+constexpr uint16_t kThNarrow = 0x8000u;
+
+// A "range" is a run of rows [r0, r1) that forms one all-pairs problem: the whole matrix for the dense container, one
+// block column of the pool for the sparse one. r0 is a multiple of the A tile (256 rows; 512 for the wide strips) and
+// the rows from r1 up to the next multiple of it are zero.
+struct RowRange {
+    uint64_t r0, r1;     // rows [r0, r1) form one all-pairs problem; r0 is a multiple of the A tile (256; 512 for wide strips)
+    uint64_t a_end = 0;  // 0: the whole triangle. Otherwise only the pairs with the EARLIER row below a_end (a
+                         // multiple of the A tile from r0, or >= r1): the rows [r0, a_end) among themselves and
+                         // against everything behind them — a block column's bitmap rows, with its list rows,
+                         // which the list-probe kernel pairs with each other, behind them
+    uint64_t back_from = ~0ull;  // != ~0: a row PANEL [back_from, r1) that has just arrived (a multiple of the A tile): only the
+                                 // pairs whose LATER row lies in the panel — every A tile of the panel against all the blocks in
+                                 // front of it (from r0) plus its own triangle (popcount(a & b) is symmetric: the new rows are the
+                                 // stationary operand, the rows already there stream past in long runs)
+};
+uint64_t ranges_hash(const std::vector<RowRange>& ranges);
+
+// Ownership of the strip work among shard_count shards (multi-GPU ranks; reference loop being
+// sharded: storm.c:1199-1238). Two levels:
+//   * whole k-slices (256 bits of every row), in units of 4 (1024 bits = one 128-byte line of the bit
+//     matrix, so that a shard's expansion reads whole lines): the first (n_units / G) * G units go
+//     to shard unit % G, so a shard expands and multiplies only its own columns — 1/G of the O(N*M)
+//     expansion and of the pair work, equal shares whatever N is;
+//   * the remaining slices ("leftover", fewer than 4 G) are cut along the PAIR space: their items
+//     (A tile x run of B blocks) are dealt to the shards longest-first onto the least loaded one
+//     (deterministic, every shard computes the same deal), every shard expands those few slices.
+// Hence any G balances to within one short item per leftover slice (c2 at G = 3: 85 1/3 slices
+// each), and a matrix with fewer slices than shards (M <= 256 * G bits) still splits G ways.
+inline uint32_t strip_modulo_slices(uint32_t n_kslices, uint32_t shard_count) {
+    return n_kslices / kOwnSlices / shard_count * shard_count * kOwnSlices;  // whole units, a multiple of G
+}
+inline bool strip_owns_slice(uint32_t ks, uint32_t shard_rank, uint32_t shard_count) {
+    return (ks / kOwnSlices) % shard_count == shard_rank;
+}
+
+// ---- the summing tile kernel's list (pairw_fp4_kernel) ----
+struct TileSumRequest {
+    uint64_t ranges_hash;
+    uint32_t total_stages, shard_rank, shard_count;
+    uint32_t stages_per_item;   // option k2_stages_per_item
+    uint32_t diag_only;
+    uint32_t one_tile_probe;    // k2_debug & 3 == 1, timing probe only: every item reads one tile
+    bool operator==(const TileSumRequest& o) const { return same_request(*this, o); }
+};
+int plan_tile_sum(const TileSumRequest& rq, const std::vector<RowRange>& ranges, std::vector<MfmaItem>& items);
+
+// ---- strips ----
+// The options a strip list is shaped by (context options of the same names), as the caller states them: max_run 0 = the
+// run length is chosen by the list-scheduling estimate.
+struct StripOptions {
+    int32_t max_run = 0, tail_run = 32, tail_slices = 3, lpt_rounds = 6;   // the context's defaults (storm_hip_internal.h)
+    int32_t shard_pairs = 0;
+    int32_t n_cus = 256;
+    int32_t xcd_group = 1;         // consecutive slices that share an XCD (2 for the bit-operand strips: slices 2j, 2j + 1 read the same bits)
+    int32_t persistent = 0;        // k2_persistent: one contiguous queue per XCD
+    int32_t one_slice_probe = 0;   // k2_debug & 16 (timing probe, wrong results): every XCD re-reads one k-slice
+};
+struct StripRequest {
+    StripOptions opt;
+    uint32_t n_kslices, shard_rank, shard_count, a_tile;
+    uint32_t unused = 0;   // (no padding in front of the 64-bit member: same_request)
+    uint64_t ranges_hash;
+    bool operator==(const StripRequest& o) const { return same_request(*this, o); }
+};
+StripRequest strip_request(const StripOptions& opt, const std::vector<RowRange>& ranges, uint32_t n_kslices,
+                           uint32_t shard_rank, uint32_t shard_count, uint32_t a_tile);
+// The list in launch order and, for the persistent form, the per-XCD queue bounds; run_chosen: the run length in use.
+void plan_strips(const StripRequest& rq, const std::vector<RowRange>& ranges, std::vector<StripItem>& items,
+                 uint32_t queue_base[8], uint32_t queue_count[8], int* run_chosen = nullptr);
+
+// ---- write-mode tiles of 256 x 256 ----
+// Launch order of the tiles [i0, i1) x [j0, j1) (upper triangle only when `triangle`) for L2 reuse: appended to `out`.
+void xcd_grouped_tiles(uint32_t i0, uint32_t i1, uint32_t j0, uint32_t j1, bool triangle,
+                       std::vector<std::pair<uint16_t, uint16_t>>& out);
+struct MatrixTilesRequest {
+    std::vector<std::pair<uint16_t, uint16_t>> tiles;   // in launch order
+    std::vector<float> cost;    // empty, or one per tile (1 = a full tile): what the planner assumes when it cuts the last round
+    uint32_t total_stages = 0;
+    uint32_t n_cus = 1;
+    int32_t split = 1;          // option k2_matrix_split
+    int32_t min_part = 32;      // option k2_matrix_min_part
+    bool operator==(const MatrixTilesRequest& o) const {
+        return total_stages == o.total_stages && n_cus == o.n_cus && split == o.split && min_part == o.min_part &&
+               tiles == o.tiles && cost == o.cost;
+    }
+};
+struct MatrixPlan {  // item table of one matrix-output launch
+    uint32_t n_items = 0;  // workgroups to launch
+    uint32_t n_full = 0;   // items [0, n_full) are whole tiles; the rest are k-parts that add into a cleared window
+    uint32_t n_cut = 0;    // tiles that are cut into parts: behind the items the table holds one record per such tile
+                           // (what zero_tiles_kernel walks: one workgroup column per window, not one per part)
+};
+void plan_matrix_tiles(const MatrixTilesRequest& rq, std::vector<MfmaItem>& items, MatrixPlan* plan);
+
+// ---- K2h ----
+struct Tile128Request {
+    uint32_t ia0, ia1, jb0, jb1;   // tiles of 128 rows: A [ia0, ia1) x B [jb0, jb1)
+    uint32_t triangle;
+    uint32_t total_stages;
+    uint32_t n_cus;
+    int32_t slots_per_cu, min_chunks, diag_cost_pct;   // options k2_part_slots, k2_part_min_chunks, k2_part_cost_diag
+    uint32_t narrow_windows;                           // option k2_part_narrow
+    bool operator==(const Tile128Request& o) const { return same_request(*this, o); }
+};
+struct Tile128Plan {
+    std::vector<PartItem> items;
+    uint32_t n_tiles = 0, n_windows = 0;
+};
+void plan_tile128(const Tile128Request& rq, Tile128Plan* plan);
+
+// ---- K2q ----
+struct BitstreamShaping {
+    int32_t groups_per_cu = 0;  // 0 = by the length of the stream: 1, 2 or 3
+    int32_t min_piece = 6;      // stages a workgroup should have at least before a CU's share is cut further
+    int32_t min_run = 2;        // a cut leaves at least this many later blocks on either side of it
+    int32_t long_piece = 80;    // stages per workgroup once the stream is longer than the chip's slots x this
+    // one round of 3 workgroups per CU: the later workgroups' shares in percent of the first one's (build_bitstream) ...
+    int32_t w3_1 = 120, w3_2 = 60;
+    int32_t weighted_min = 16;       // ... from this many stages per share (shorter ones: equal shares)
+    int32_t single_round_max = 220;  // stages per slot up to which the stream is ONE round of weighted shares
+};
+struct BitstreamRequest {
+    BitstreamShaping sh;
+    uint32_t n_kslices, shard_rank, shard_count, n_cus;
+    uint64_t pitch_bytes;
+    uint64_t ranges_hash;
+    bool operator==(const BitstreamRequest& o) const { return same_request(*this, o); }
+};
+struct BitstreamPlan {
+    std::vector<BitSeg> segs;
+    std::vector<uint32_t> bases;        // per stage, workgroup by workgroup: where its 64 rows x 64 B start (64-byte units)
+    std::vector<uint32_t> first_stage;  // workgroup w's stages are bases[first_stage[w] .. first_stage[w + 1])
+    std::vector<uint32_t> first;
+    uint32_t groups = 0;
+    uint64_t stages = 0;      // multiplied + operand-only stages of this shard, after cutting
+    uint32_t max_stages = 0;  // longest workgroup
+};
+BitstreamRequest bitstream_request(const BitstreamShaping& sh, const std::vector<RowRange>& ranges, uint32_t n_kslices,
+                                   uint32_t shard_rank, uint32_t shard_count, uint32_t n_cus, uint64_t pitch_bytes);
+void build_bitstream(const BitstreamRequest& rq, const std::vector<RowRange>& ranges, BitstreamPlan& plan);
+
+}  // namespace storm

@@ -32,20 +32,11 @@
 // reference (README.md:165-167: per-pair counts for LD); the loop it stands for is storm.c:1199-1238 with the leaf's
 // result kept per pair.
 constexpr int kThThreads = 256;
-constexpr uint32_t kThTile = 128u;
+// (kThTile = 128 rows per tile side, the item record PartItem and kThNarrow: storm_hip_plan.h)
 constexpr uint32_t kThSlotBytes = 2u * kThTile * 64u;   // 16 KiB: A rows 0 .. 127, then B rows 0 .. 127, 64 B of bits each
 constexpr uint32_t kThRing = 4u;
 constexpr uint32_t kThWindowWords = kThTile * kThTile;   // a part's window: 64 KiB of uint32
 
-struct PartItem {
-    uint16_t I, J;               // tile indices in units of 128 (virtual) rows
-    uint32_t stage0, n_stages;   // the item's k range in 128-bit stages (multiples of 4)
-    uint32_t tile;               // the tile's index among the launch's tiles: its ticket
-    uint32_t win0;               // the first of the tile's n_parts windows in `parts` (part p: win0 + p)
-    uint16_t part, n_parts;      // this item is part `part` of `n_parts` of its tile; bit 15 of `part`: the tile's windows hold
-                                 // 16-bit counts (every part of the tile covers fewer than 2^16 bits of k)
-};
-constexpr uint16_t kThNarrow = 0x8000u;
 
 __global__ __launch_bounds__(kThThreads, 2) void tile128_kernel(
     TileOperands ops, const PartItem* __restrict__ items, uint32_t* __restrict__ out, uint64_t ld,

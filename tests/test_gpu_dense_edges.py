@@ -17,11 +17,18 @@ from tests.conftest import shipped
 pytestmark = pytest.mark.gpu
 
 SENTINEL = 0x9E3779B9
-DEFAULTS = {"variant": -1, "seg_rows": 256, "chunks_per_item": 0, "keep_shadow": 0, "k2_tile_shape": 0, "k2_ring_sync": 0,
-            "k2_wave_below": 400, "k2_part_slots": 0, "k2_part_min_chunks": 8, "k2_part_cost_diag": 80, "k2_part_narrow": 1,
-            "k2_matrix_split": 1, "k2_matrix_parts": 0, "k2_strip_operands": 0, "k2_shape": 16, "k2_max_run": 0,
-            "k2_tail_run": 32, "k2_fold_inline": -1, "k2_shard_pairs": 0, "k2_stream_groups_per_cu": 0, "k2_stream_w3_1": 120,
-            "k2_stream_w3_2": 60, "k2_persistent": 0}
+# every settable option and the initialiser of its member in storm_hip_ctx_s (storm_hip_internal.h)
+DEFAULTS = {"variant": -1, "probe_bundle": -1, "sparse_probe": -1, "result_mailbox": 1, "sync_poll_us": 0, "matrix_lists": -1,
+            "matrix_lists_kernel": 0, "matrix_lists_hash_min_log2": 6, "matrix_lists_debug": 0, "matrix_lists_density": 80,
+            "seg_rows": 256, "k2_stages_per_item": 32, "k2_max_run": 0, "k2_ring": 4, "k2_shadow_budget_mb": 96 * 1024,
+            "k2_tile_shape": 0, "k2_ring_sync": 0, "k2_wave_below": 400, "k2_part_slots": 0, "k2_part_min_chunks": 8,
+            "k2_part_narrow": 1, "k2_part_cost_diag": 80, "k2_ring_cost_diag": 78, "k2_ring_cost_ragged": 40,
+            "k2_tile_cost_diag": 63, "k2_tile_cost_ragged": 30, "k2_strip_operands": 0, "k2_shard_pairs": 0, "k2_matrix_pad": -1,
+            "k2_fold_inline": -1, "k2_wave_ring": 0, "k2_stream_max_rows": 8192, "k2_stream_groups_per_cu": 0,
+            "k2_stream_min_piece": 6, "k2_stream_min_run": 2, "k2_stream_w3_1": 120, "k2_stream_w3_2": 60, "k2_shape": 16,
+            "keep_shadow": 0, "k2_matrix_parts": 0, "k2_matrix_min_part": 32, "k2_matrix_split": 1, "k2_pitch_pad": -1,
+            "k2_lds_pad": 0, "k2_persistent": 0, "k2_lpt_rounds": 6, "k2_tail_slices": 3, "k2_tail_run": 32, "k2_debug": 0,
+            "time_kernels": 0, "chunks_per_item": 0}
 
 
 @pytest.fixture(scope="module")
@@ -694,3 +701,37 @@ def test_empty_shapes(ctx):
             assert (sentinel.cpu().numpy().view(np.uint32) == SENTINEL).all(), (tile_shape, n_rows)
             other.close()
             m.close()
+
+
+def test_every_option_reads_back():
+    """On a fresh context every key of the option table reads its member's initialiser; after set_option with a legal
+    non-default value it reads what was stored (clamped, normalised); unknown names read -1."""
+    from tests.test_plan_golden import gen
+    assert set(gen.OPTIONS) == set(DEFAULTS)
+    stored_as = {"k2_matrix_pad": (100, 64), "k2_fold_inline": (7, 1), "matrix_lists_debug": (3, 3)}
+    fresh = sb.HipContext(0)
+    try:
+        for key, default in DEFAULTS.items():
+            assert fresh.get_option(key) == default, key
+        assert fresh.get_option("no_such_option") == -1
+        for key, (kind, a, b, tools_only) in gen.OPTIONS.items():
+            default = DEFAULTS[key]
+            if key in stored_as:
+                value, want = stored_as[key]
+            elif kind == "any":   # a boolean
+                value = 5 if default == 0 else 0
+                want = int(value != 0)
+            else:
+                legal = [v for v in ((a, b, a + 1, b - 1) if kind == "range" else a) if v not in tools_only and v != default]
+                if key == "k2_stream_max_rows":
+                    legal = [0]   # (2^31 is accepted and does not fit the int it is stored in)
+                value = want = legal[0] if legal else None
+            if value is None or want in tools_only:
+                continue   # (k2_ring, k2_shape, k2_persistent, k2_debug: the shipped build takes the default alone)
+            fresh.set_option(key, value)
+            assert fresh.get_option(key) == want, (key, value)
+        for key, default in DEFAULTS.items():
+            fresh.set_option(key, default)
+            assert fresh.get_option(key) == default, key
+    finally:
+        fresh.close()

@@ -6,22 +6,13 @@
 // K2w: per-wave stage words of the same plan (bitwave_kernel). One buffer: first[4 G + 1] | words.
 static int ensure_bitwave(storm_hip_ctx_t* ctx, const std::vector<RowRange>& ranges, uint32_t n_kslices,
                           uint32_t shard_rank, uint32_t shard_count, uint64_t pitch) {
-    const uint64_t key[4] = {ranges_hash(ranges) ^ (pitch * 0x9e3779b97f4a7c15ull) ^ 0x77aa77aa77aa77aaull ^
-                                 ((uint64_t)ctx->k2_stream_w3_2 * 0xc2b2ae3d27d4eb4full),
-                             n_kslices, ((uint64_t)shard_rank << 32) | shard_count,
-                             ((uint64_t)(ctx->k2_stream_groups_per_cu & 0xff) << 32) |
-                                 ((uint64_t)(ctx->k2_stream_min_piece & 0xffff) << 16) |
-                                 (uint64_t)(ctx->k2_stream_min_run & 0xffff) |
-                                 ((uint64_t)(ctx->k2_stream_w3_1 & 0x3ff) << 40)};
-    if (ctx->d_bitfirst && !memcmp(key, ctx->bit_key, sizeof(key))) return STORM_HIP_OK;
-    BitstreamShaping sh;
-    sh.groups_per_cu = ctx->k2_stream_groups_per_cu;
-    sh.min_piece = std::max(1, ctx->k2_stream_min_piece);
-    sh.min_run = std::max(1, ctx->k2_stream_min_run);
-    sh.w3_1 = ctx->k2_stream_w3_1;
-    sh.w3_2 = ctx->k2_stream_w3_2;
+    const BitstreamRequest rq = bitstream_request_of(ctx, ranges, n_kslices, shard_rank, shard_count, pitch);
+    BitstreamRequest key = rq;
+    key.ranges_hash ^= 0x77aa77aa77aa77aaull;   // (the same plan in another device layout than ensure_bitstream's)
+    if (ctx->d_bitfirst && ctx->bit_key == key) return STORM_HIP_OK;
+    ctx->bit_key.reset();
     BitstreamPlan plan;
-    build_bitstream(sh, ranges, n_kslices, shard_rank, shard_count, (uint32_t)std::max(1, ctx->n_cus), pitch, plan);
+    build_bitstream(rq, ranges, plan);
     if (!ranges.empty() && ranges.back().r1 * pitch / 64 + n_kslices + 4 * pitch >= (1ull << 30)) {
         set_error("K2w: the matrix is beyond the 30-bit stage addresses (64-byte units)");
         return STORM_HIP_EINVAL;
@@ -56,20 +47,14 @@ static int ensure_bitwave(storm_hip_ctx_t* ctx, const std::vector<RowRange>& ran
     std::vector<uint32_t> packed(first);
     packed.insert(packed.end(), words.begin(), words.end());
     const size_t bytes = std::max<size_t>(packed.size(), 1) * sizeof(uint32_t);
-    if (bytes > ctx->bitfirst_capacity) {
-        if (ctx->d_bitfirst) STORM_HIP_TRY(hipFree(ctx->d_bitfirst));
-        ctx->d_bitfirst = nullptr;
-        ctx->bitfirst_capacity = 0;
-        STORM_HIP_TRY(hipMalloc(&ctx->d_bitfirst, bytes));
-        ctx->bitfirst_capacity = bytes;
-    }
+    if (int rc = ctx->d_bitfirst.ensure(bytes, "K2w: the waves' stage words")) return rc;
     STORM_HIP_TRY(hipMemcpyAsync(ctx->d_bitfirst, packed.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
     STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->n_bit_groups = plan.groups;
     ctx->bit_stages = words.size();
     ctx->bit_max_stages = longest;
     ctx->n_bit_segs = (uint32_t)plan.segs.size();
-    memcpy(ctx->bit_key, key, sizeof(key));
+    ctx->bit_key = key;
     return STORM_HIP_OK;
 }
 
@@ -83,7 +68,7 @@ int launch_pairw_bitwave(storm_hip_ctx_t* ctx, const uint64_t* X, uint64_t pitch
     }
     if (int rc = ensure_bitwave(ctx, ranges, n_kslices, shard_rank, shard_count, pitch)) return rc;
     ctx->n_items = 0;
-    memset(ctx->items_key, 0xff, sizeof(ctx->items_key));
+    ctx->items_key = std::monostate{};
     ctx->last_info[0] = ctx->n_bit_groups;
     ctx->last_info[1] = ctx->bit_max_stages;
     ctx->last_info[2] = 1;
@@ -95,7 +80,7 @@ int launch_pairw_bitwave(storm_hip_ctx_t* ctx, const uint64_t* X, uint64_t pitch
     const uint32_t G = ctx->n_bit_groups, cus = (uint32_t)std::max(1, ctx->n_cus);
     int ring = ctx->k2_wave_ring;
     if (ring == 0) ring = G <= cus ? 8 : G <= 2 * cus ? 4 : 3;
-    const uint32_t* first = static_cast<const uint32_t*>(ctx->d_bitfirst);
+    const uint32_t* first = ctx->d_bitfirst.d;
     const uint32_t* words = first + 4 * (size_t)G + 1;
     kernel_time_mark(ctx);
 #define STORM_BW_LAUNCH(R)                                                                                      \

@@ -10,15 +10,8 @@
                     break;
                 case 218: {
                     const size_t need = (size_t)n_strip * 4 * sizeof(unsigned long long);
-                    if (need > ctx->trace_capacity) {
-                        if (ctx->d_trace) STORM_HIP_TRY(hipFree(ctx->d_trace));
-                        ctx->d_trace = nullptr;
-                        ctx->trace_capacity = 0;
-                        STORM_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ctx->d_trace), need));
-                        ctx->trace_capacity = need;
-                    }
+                    if (int rc = ctx->d_trace.ensure(need, "K2s: the schedule trace")) return rc;
                     ctx->trace_items = n_strip;
-                    ctx->trace_is_stream = false;
                     ctx->trace_is_stream = false;
                     hipLaunchKernelGGL((strip_fp4_kernel<4, 8, 2, true>), pgrid, sblock, 0, ctx->stream,
                                        ctx->d_x4, pitch, sit, ctx->d_slots, ctx->d_trace, queues, heads);
@@ -66,15 +59,8 @@
                     break;
                 case 18: {  // schedule trace (results stay correct)
                     const size_t need = (size_t)n_strip * 4 * sizeof(unsigned long long);
-                    if (need > ctx->trace_capacity) {
-                        if (ctx->d_trace) STORM_HIP_TRY(hipFree(ctx->d_trace));
-                        ctx->d_trace = nullptr;
-                        ctx->trace_capacity = 0;
-                        STORM_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ctx->d_trace), need));
-                        ctx->trace_capacity = need;
-                    }
+                    if (int rc = ctx->d_trace.ensure(need, "K2s: the schedule trace")) return rc;
                     ctx->trace_items = n_strip;
-                    ctx->trace_is_stream = false;
                     ctx->trace_is_stream = false;
                     hipLaunchKernelGGL((strip_fp4_kernel<4, 8>), sgrid, sblock, 0, ctx->stream,
                                        ctx->d_x4, pitch, sit, ctx->d_slots, ctx->d_trace);
