@@ -286,6 +286,44 @@ int STORM_square_matrix_device(STORM_t* a, STORM_t* b, int op, uint32_t* d_out, 
 int STORM_contig_pairw_matrix_device(STORM_contiguous_t* bitmap, int op, uint32_t* d_out, uint64_t out_rows,
                                      uint64_t out_ld);
 
+/* Extension: the per-pair matrices above finished into the statistic they are computed for (README.md:165-167: linkage
+ * disequilibrium, "any intersect-count problem") — on the device, where the counts lie, instead of 4 n^2 bytes over the bus
+ * and n^2 divisions on the host. With c = the pair's intersect count (storm.c:790-814 / :1149-1173 per pair), a and b the
+ * two rows' set-bit counts and M = n_bits, the size of the universe (for LD: the number of haplotypes):
+ *   STORM_SIM_JACCARD  c / (a + b - c)                         NaN when both rows are empty
+ *   STORM_SIM_COSINE   c / sqrt(a b)   (Ochiai)                NaN when either row is empty
+ *   STORM_SIM_LD_D     (M c - a b) / M^2                       always defined
+ *   STORM_SIM_LD_R2    (M c - a b)^2 / (a (M - a) b (M - b))   NaN unless 0 < a < M and 0 < b < M
+ * as float: M c - a b exactly in integers, the rest in double, rounded once (at most one float from the exactly rounded
+ * value); NaN is always the bit pattern 0x7FC00000. `out` holds out_rows x out_ld float, row-major, entry (i, j) at
+ * out[i * out_ld + j].
+ *   STORM_contig_pairw_similarity / STORM_pairw_similarity: entries i < j < n; 0.0f for i >= j (_device: entries i >= j stay
+ *     as the count kernel left them, see STORM_pairw_matrix_device). The kernels and their choice are those of
+ *     STORM_contig_pairw_matrix / STORM_pairw_matrix with op 0.
+ *   STORM_square_similarity: every entry of the N_A x N_B window, as STORM_square_matrix; a == b is allowed (the diagonal is
+ *     a row with itself: Jaccard = cosine = 1, NaN for an empty row).
+ * n_bits: not read by Jaccard and cosine. STORM_contiguous_t: 0 = the container's vector_length (storm.h:188-200). A STORM_t
+ * declares no universe: the LD measures need n_bits > 0. At most 2^32.
+ * Returns 0; -1 NULL handle, -2 NULL out, -4 out_rows or out_ld smaller than the rows held (nothing is written), -3 device
+ * failure, unknown measure or bad n_bits (STORM_hip_error says which), -5 when the calling thread's view spans several
+ * device slots — host forms too: like the rectangle, these run on one device slot and one process. Empty containers: 0,
+ * nothing written. _device: `d_out` in device memory on that slot. */
+#define STORM_SIM_JACCARD 0
+#define STORM_SIM_COSINE 1
+#define STORM_SIM_LD_D 2
+#define STORM_SIM_LD_R2 3
+int STORM_contig_pairw_similarity(STORM_contiguous_t* bitmap, int measure, uint64_t n_bits, float* out, uint64_t out_rows,
+                                  uint64_t out_ld);
+int STORM_contig_pairw_similarity_device(STORM_contiguous_t* bitmap, int measure, uint64_t n_bits, float* d_out,
+                                         uint64_t out_rows, uint64_t out_ld);
+int STORM_pairw_similarity(STORM_t* bitmap, int measure, uint64_t n_bits, float* out, uint64_t out_rows, uint64_t out_ld);
+int STORM_pairw_similarity_device(STORM_t* bitmap, int measure, uint64_t n_bits, float* d_out, uint64_t out_rows,
+                                  uint64_t out_ld);
+int STORM_square_similarity(STORM_t* a, STORM_t* b, int measure, uint64_t n_bits, float* out, uint64_t out_rows,
+                            uint64_t out_ld);
+int STORM_square_similarity_device(STORM_t* a, STORM_t* b, int measure, uint64_t n_bits, float* d_out, uint64_t out_rows,
+                                   uint64_t out_ld);
+
 /* ------------------------------------------------------------- extensions (not in ref) ---
  * Device selection for the entry points above. By default device 0 computes everything.
  * STORM_hip_set_devices(n, ids): the pair space is sharded over the listed GPUs of this node

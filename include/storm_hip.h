@@ -183,6 +183,44 @@ int storm_hip_cross_dense_matrix_device(storm_hip_ctx_t* ctx, const storm_hip_ma
 int storm_hip_cross_dense_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b, int op,
                                  uint32_t* h_out, uint64_t ld);
 
+/* ---- per-pair similarity: the count matrix finished on the device ------------------------------------------
+ * What the per-pair counts are for (reference README.md:165-167: linkage disequilibrium, "any intersect-count
+ * problem"): one formula per entry over c = |A_i & B_j|, a = |A_i|, b = |B_j| and the universe size M = n_bits,
+ *   STORM_HIP_SIM_JACCARD  c / (a + b - c)                         NaN when a + b - c = 0
+ *   STORM_HIP_SIM_COSINE   c / sqrt(a b)   (Ochiai)                NaN when a b = 0
+ *   STORM_HIP_SIM_LD_D     (M c - a b) / M^2                       always defined
+ *   STORM_HIP_SIM_LD_R2    (M c - a b)^2 / (a (M - a) b (M - b))   NaN unless 0 < a < M and 0 < b < M
+ * M c - a b exactly in 64-bit integers, the rest in double, rounded once to float (at most one float from the exactly
+ * rounded rational); NaN is always the one quiet pattern 0x7FC00000. Jaccard and cosine do not read n_bits (it must
+ * still be valid).
+ * _finish_device, the primitive: `d_io` is a DEVICE matrix of n_rows x ld 32-bit words holding the counts as uint32;
+ *   every converted entry is overwritten in place with its float. d_counts_rows[n_rows] / d_counts_cols[n_cols] (device)
+ *   are the set-bit counts of the rows' and the columns' side. triangle != 0: only entries i < j (n_rows == n_cols);
+ *   entries i >= j and the pitch columns [n_cols, ld) are neither read nor written. Asynchronous on the context's
+ *   stream (similarity_finish_kernel). STORM_HIP_EINVAL: NULL argument, unknown measure, n_bits 0 or above 2^32,
+ *   ld < n_cols, a triangle that is not square. Empty shapes: STORM_HIP_OK, nothing touched. A caller with a count
+ *   matrix of its own needs nothing else; the last-pass report is then STORM_HIP_RAN_SIMILARITY alone.
+ * The other forms are the AND-count path of the operand kind (storm_hip_pairw_matrix_device, _cross_dense_matrix_device,
+ * _rowlists_pairw_matrix_device, _rowlists_square_matrix_device: same kernels, same choice), the rows' counts, then
+ * the finish; complete on return. _device: out[i * ld + j] in DEVICE memory (triangle forms: i < j, other entries as the
+ * count kernel left them). Host forms: h_out[i * ld + j], whole rows, +0.0f at i >= j of a triangle. They add
+ * STORM_HIP_RAN_SIMILARITY to the last-pass mask of the count kernel that ran. */
+#define STORM_HIP_SIM_JACCARD 0
+#define STORM_HIP_SIM_COSINE 1
+#define STORM_HIP_SIM_LD_D 2
+#define STORM_HIP_SIM_LD_R2 3
+int storm_hip_similarity_finish_device(storm_hip_ctx_t* ctx, void* d_io, uint64_t ld, uint64_t n_rows, uint64_t n_cols,
+                                       const uint32_t* d_counts_rows, const uint32_t* d_counts_cols, int triangle,
+                                       int measure, uint64_t n_bits);
+int storm_hip_pairw_similarity_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_bits,
+                                      float* d_out, uint64_t ld);
+int storm_hip_pairw_similarity(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_bits,
+                               float* h_out, uint64_t ld);
+int storm_hip_cross_dense_similarity_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b,
+                                            int measure, uint64_t n_bits, float* d_out, uint64_t ld);
+int storm_hip_cross_dense_similarity(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b,
+                                     int measure, uint64_t n_bits, float* h_out, uint64_t ld);
+
 /* sum_c C(n_c,2) on the device — verification identity only, never the product
  * path: used by tests at sizes where a CPU pairwise oracle is infeasible */
 int storm_hip_column_identity(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m,
@@ -352,6 +390,7 @@ typedef struct storm_hip_comm_s storm_hip_comm_t;
 #define STORM_HIP_RAN_TILES_OUT 128u  /* tilering_kernel / tilebits8_kernel: per-pair output of a dense matrix (or replica) roof: FP4 matrix cores */
 #define STORM_HIP_RAN_LISTS_MATRIX 64u /* lists_matrix_kernel (K5), per-pair output from the lists: out[2] = its table lookups, out[3] = 64 */
 #define STORM_HIP_RAN_LISTS_SQUARE 256u /* lists_square_kernel (K5x), the rectangle of two list-only containers: out[2] = its table lookups, out[3] = 64 */
+#define STORM_HIP_RAN_SIMILARITY 512u /* similarity_finish_kernel behind one of the per-pair kernels above (its flag stays set), or alone (storm_hip_similarity_finish_device)  roof: HBM bandwidth */
 int storm_hip_last_pass_report(storm_hip_ctx_t* ctx, uint64_t out[4]);
 
 int storm_hip_comm_unique_id(uint8_t id[STORM_HIP_COMM_ID_BYTES]);
@@ -479,6 +518,16 @@ int storm_hip_rowlists_square_matrix_device(storm_hip_ctx_t* ctx, storm_hip_rowl
                                             int op, uint32_t* d_out, uint64_t ld);
 int storm_hip_rowlists_square_matrix(storm_hip_ctx_t* ctx, storm_hip_rowlists_t* la, const storm_hip_rowlists_t* lb, int op,
                                      uint32_t* h_out, uint64_t ld);
+/* The similarity forms of the row lists (see storm_hip_similarity_finish_device): K5 / K5x with op AND, then the finish
+ * with the lists' own row lengths as the counts. */
+int storm_hip_rowlists_pairw_similarity_device(storm_hip_ctx_t* ctx, const storm_hip_rowlists_t* l, int measure,
+                                               uint64_t n_bits, float* d_out, uint64_t ld);
+int storm_hip_rowlists_pairw_similarity(storm_hip_ctx_t* ctx, const storm_hip_rowlists_t* l, int measure, uint64_t n_bits,
+                                        float* h_out, uint64_t ld);
+int storm_hip_rowlists_square_similarity_device(storm_hip_ctx_t* ctx, storm_hip_rowlists_t* la, const storm_hip_rowlists_t* lb,
+                                                int measure, uint64_t n_bits, float* d_out, uint64_t ld);
+int storm_hip_rowlists_square_similarity(storm_hip_ctx_t* ctx, storm_hip_rowlists_t* la, const storm_hip_rowlists_t* lb,
+                                         int measure, uint64_t n_bits, float* h_out, uint64_t ld);
 
 int storm_hip_pairw_sparse(storm_hip_ctx_t* ctx, const storm_hip_sparse_t* s,
                            uint32_t shard_rank, uint32_t shard_count, uint64_t* h_total);

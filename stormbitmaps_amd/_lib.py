@@ -109,6 +109,15 @@ SIGNATURES = {
     "storm_hip_cross_dense_total": (C.c_int, [vp, vp, vp, P(u64)]),
     "storm_hip_cross_dense_matrix_device": (C.c_int, [vp, vp, vp, C.c_int, vp, u64]),
     "storm_hip_cross_dense_matrix": (C.c_int, [vp, vp, vp, C.c_int, vp, u64]),
+    "storm_hip_similarity_finish_device": (C.c_int, [vp, vp, u64, u64, u64, vp, vp, C.c_int, C.c_int, u64]),
+    "storm_hip_pairw_similarity_device": (C.c_int, [vp, vp, C.c_int, u64, vp, u64]),
+    "storm_hip_pairw_similarity": (C.c_int, [vp, vp, C.c_int, u64, vp, u64]),
+    "storm_hip_cross_dense_similarity_device": (C.c_int, [vp, vp, vp, C.c_int, u64, vp, u64]),
+    "storm_hip_cross_dense_similarity": (C.c_int, [vp, vp, vp, C.c_int, u64, vp, u64]),
+    "storm_hip_rowlists_pairw_similarity_device": (C.c_int, [vp, vp, C.c_int, u64, vp, u64]),
+    "storm_hip_rowlists_pairw_similarity": (C.c_int, [vp, vp, C.c_int, u64, vp, u64]),
+    "storm_hip_rowlists_square_similarity_device": (C.c_int, [vp, vp, vp, C.c_int, u64, vp, u64]),
+    "storm_hip_rowlists_square_similarity": (C.c_int, [vp, vp, vp, C.c_int, u64, vp, u64]),
     "storm_hip_matrix_create_from_blocks_wide": (C.c_int, [vp, u64, u64, vp, vp, vp, vp, vp, u32, P(vp)]),
     "storm_hip_pairw_sparse_begin": (C.c_int, [vp, vp, u32, u32]),
     "storm_hip_pairw_sparse_end": (C.c_int, [vp, P(u64)]),
@@ -155,6 +164,12 @@ SIGNATURES = {
     "STORM_intersect_cardinality_square": (u64, [vp, vp]),
     "STORM_square_matrix": (C.c_int, [vp, vp, C.c_int, vp, u64, u64]),
     "STORM_square_matrix_device": (C.c_int, [vp, vp, C.c_int, vp, u64, u64]),
+    "STORM_contig_pairw_similarity": (C.c_int, [vp, C.c_int, u64, vp, u64, u64]),
+    "STORM_contig_pairw_similarity_device": (C.c_int, [vp, C.c_int, u64, vp, u64, u64]),
+    "STORM_pairw_similarity": (C.c_int, [vp, C.c_int, u64, vp, u64, u64]),
+    "STORM_pairw_similarity_device": (C.c_int, [vp, C.c_int, u64, vp, u64, u64]),
+    "STORM_square_similarity": (C.c_int, [vp, vp, C.c_int, u64, vp, u64, u64]),
+    "STORM_square_similarity_device": (C.c_int, [vp, vp, C.c_int, u64, vp, u64, u64]),
     "STORM_hip_set_option": (C.c_int, [C.c_char_p, C.c_int64]),
     "STORM_contig_pairw_matrix_device": (C.c_int, [vp, C.c_int, vp, u64, u64]),
     "STORM_serialize": (u64, [vp, vp, u64]),

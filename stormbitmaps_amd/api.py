@@ -25,6 +25,14 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+MEASURES = {"jaccard": 0, "cosine": 1, "ld_d": 2, "ld_r2": 3}  # STORM_SIM_* (storm.h)
+
+
+def _similarity(lib, what: str, rc: int) -> None:
+    if rc != 0:
+        raise RuntimeError(f"{what} -> {rc}: {lib.STORM_hip_error().decode()}")
+
+
 def _all_pairs(value: int, what: str) -> int:
     if value == ALL_PAIRS_FAILED:
         lib = _lib.load()
@@ -94,6 +102,24 @@ class StormContig:
                                                             out_rows, out_ld))
         if rc != 0:
             raise RuntimeError(f"STORM_contig_pairw_matrix_device -> {rc}: {self._lib.STORM_hip_error().decode()}")
+
+    def pairw_similarity(self, measure: str = "jaccard", n_bits: int = 0) -> np.ndarray:
+        """STORM_contig_pairw_similarity (extension): [n_rows, n_rows] float32, entry (i, j), i < j = the measure ("jaccard",
+        "cosine", "ld_d", "ld_r2") of rows i and j, finished on the device; 0 for i >= j. n_bits: the universe size of the
+        LD measures, 0 = vector_length."""
+        n = self.n_rows
+        out = np.zeros((n, n), dtype=np.float32)
+        _similarity(self._lib, "STORM_contig_pairw_similarity",
+                    int(self._lib.STORM_contig_pairw_similarity(self._h, MEASURES[measure], n_bits,
+                                                                _ptr(out) if out.size else _ptr(np.zeros(1, np.float32)), n, n)))
+        return out
+
+    def pairw_similarity_device(self, d_out: int, out_rows: int, out_ld: int, measure: str = "jaccard", n_bits: int = 0) -> None:
+        """STORM_contig_pairw_similarity_device (extension): the same triangle left in device memory at address d_out
+        (out_rows x out_ld float32; entries i >= j are not converted)."""
+        _similarity(self._lib, "STORM_contig_pairw_similarity_device",
+                    int(self._lib.STORM_contig_pairw_similarity_device(self._h, MEASURES[measure], n_bits, C.c_void_p(d_out),
+                                                                       out_rows, out_ld)))
 
     def hip_invalidate(self) -> None:
         """STORM_contig_hip_invalidate: forget the device copy after an in-place edit of the
@@ -186,6 +212,40 @@ class Storm:
                                                       C.c_void_p(d_out), out_rows, out_ld))
         if rc != 0:
             raise RuntimeError(f"STORM_square_matrix_device -> {rc}: {self._lib.STORM_hip_error().decode()}")
+
+    def pairw_similarity(self, measure: str = "jaccard", n_bits: int = 0) -> np.ndarray:
+        """STORM_pairw_similarity (extension): [n_rows, n_rows] float32, entry (i, j), i < j = the measure ("jaccard",
+        "cosine", "ld_d", "ld_r2") of rows i and j, finished on the device; 0 for i >= j. The LD measures need n_bits, the
+        size of the universe (a STORM_t declares none)."""
+        n = self.n_rows
+        out = np.zeros((n, n), dtype=np.float32)
+        _similarity(self._lib, "STORM_pairw_similarity",
+                    int(self._lib.STORM_pairw_similarity(self._h, MEASURES[measure], n_bits,
+                                                         _ptr(out) if out.size else _ptr(np.zeros(1, np.float32)), n, n)))
+        return out
+
+    def pairw_similarity_device(self, d_out: int, out_rows: int, out_ld: int, measure: str = "jaccard", n_bits: int = 0) -> None:
+        """STORM_pairw_similarity_device (extension): the same triangle left in device memory at address d_out."""
+        _similarity(self._lib, "STORM_pairw_similarity_device",
+                    int(self._lib.STORM_pairw_similarity_device(self._h, MEASURES[measure], n_bits, C.c_void_p(d_out),
+                                                                out_rows, out_ld)))
+
+    def square_similarity(self, other: "Storm", measure: str = "jaccard", n_bits: int = 0) -> np.ndarray:
+        """STORM_square_similarity (extension): [self.n_rows, other.n_rows] float32, every entry (i, j) = the measure of
+        row i of self and row j of other."""
+        na, nb = self.n_rows, other.n_rows
+        out = np.zeros((na, nb), dtype=np.float32)
+        _similarity(self._lib, "STORM_square_similarity",
+                    int(self._lib.STORM_square_similarity(self._h, other._h, MEASURES[measure], n_bits,
+                                                          _ptr(out) if out.size else _ptr(np.zeros(1, np.float32)), na, nb)))
+        return out
+
+    def square_similarity_device(self, other: "Storm", d_out: int, out_rows: int, out_ld: int, measure: str = "jaccard",
+                                 n_bits: int = 0) -> None:
+        """STORM_square_similarity_device (extension): the same rectangle left in device memory at address d_out."""
+        _similarity(self._lib, "STORM_square_similarity_device",
+                    int(self._lib.STORM_square_similarity_device(self._h, other._h, MEASURES[measure], n_bits,
+                                                                 C.c_void_p(d_out), out_rows, out_ld)))
 
     def serialized_size(self) -> int:
         return int(self._lib.STORM_serialized_size(self._h))  # storm.c:963
@@ -318,7 +378,7 @@ class HipContext:
         out = (C.c_uint64 * 4)()
         check(self._lib.storm_hip_last_pass_report(self._h, out), "storm_hip_last_pass_report")
         names = {1: "pairw_dense_kernel", 2: "pairw_fp4_kernel", 4: "strip16_fp4_kernel", 8: "bitstream_kernel",
-                 16: "strip16_bits_kernel", 32: "probe_lists_kernel"}
+                 16: "strip16_bits_kernel", 32: "probe_lists_kernel", 512: "similarity_finish_kernel"}
         return {"kernels": [n for b, n in names.items() if out[0] & b], "dense_word_pairs": int(out[1]),
                 "probe_lookups": int(out[2]), "rows_per_lookup": int(out[3])}
 

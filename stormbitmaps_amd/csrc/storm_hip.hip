@@ -482,14 +482,6 @@ void drain_deferred(storm_hip_ctx_t* ctx, bool aged) {
     ctx->deferred_age = 0;
 }
 
-static int check_ctx(const storm_hip_ctx_t* ctx) {
-    if (!ctx) {
-        set_error("NULL context");
-        return STORM_HIP_EINVAL;
-    }
-    return STORM_HIP_OK;
-}
-
 }  // namespace storm
 
 using namespace storm;

@@ -52,6 +52,15 @@ static inline int guarded(const char* what, Fn&& fn) noexcept {
     }
 }
 
+// the first check of every entry point that takes a context
+static inline int check_ctx(const storm_hip_ctx_t* ctx) {
+    if (!ctx) {
+        set_error("NULL context");
+        return STORM_HIP_EINVAL;
+    }
+    return STORM_HIP_OK;
+}
+
 // A grow-only device buffer of the context's workspace, capacity in bytes. ensure() never shrinks and keeps the
 // contents only when it does not reallocate (every caller refills); a failed allocation leaves the buffer empty.
 // Reads as its pointer.
@@ -271,8 +280,14 @@ int launch_pairw_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int o
 int launch_square_mfma(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
                        const storm_hip_matrix_s* b, uint64_t* d_total);
 int launch_square_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
-                         const storm_hip_matrix_s* b, int op, uint32_t* d_out, uint64_t ld);
+                         const storm_hip_matrix_s* b, int op, uint32_t* d_out, uint64_t ld,
+                         bool sync = true);   // false: queued only, the caller waits for the stream
 int launch_row_counts(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint32_t* d_counts);
+// similarity_finish_kernel over a count matrix in device memory, asynchronous (storm_hip_similarity.hip; the checks of
+// storm_hip_similarity_finish_device)
+int launch_similarity_finish(storm_hip_ctx_t* ctx, void* d_io, uint64_t ld, uint64_t n_rows, uint64_t n_cols,
+                             const uint32_t* d_counts_rows, const uint32_t* d_counts_cols, int triangle, int measure,
+                             uint64_t n_bits);
 void release_mfma_state(storm_hip_ctx_t* ctx);
 // releases what was put off (storm_hip_ctx_s::deferred_free); `aged`: only what an earlier call left behind
 void drain_deferred(storm_hip_ctx_t* ctx, bool aged);

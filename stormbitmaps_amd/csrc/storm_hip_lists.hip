@@ -1072,4 +1072,83 @@ int storm_hip_rowlists_square_matrix(storm_hip_ctx_t* ctx, storm_hip_rowlists_t*
     });
 }
 
+// ---- the similarity forms (storm_hip.h: storm_hip_similarity_finish_device): K5 / K5x with op AND, then
+// similarity_finish_kernel on the same stream with the lists' own row lengths as the rows' counts. lb == nullptr: the
+// triangle of la. h_out: through the context's band buffer (cleared for a triangle: +0.0f at i >= j), one 2-D copy out.
+static int lists_similarity(storm_hip_ctx_t* ctx, storm_hip_rowlists_t* la, const storm_hip_rowlists_t* lb, int measure,
+                            uint64_t n_bits, float* d_out, float* h_out, uint64_t ld) {
+    if (!ctx || !la || !(d_out || h_out)) {
+        set_error("rowlists_similarity: NULL argument");
+        return STORM_HIP_EINVAL;
+    }
+    if (measure < STORM_HIP_SIM_JACCARD || measure > STORM_HIP_SIM_LD_R2 || n_bits == 0 || n_bits > (1ull << 32)) {
+        set_error("rowlists_similarity: unknown measure %d, or n_bits %llu is not in [1, 2^32]", measure, (unsigned long long)n_bits);
+        return STORM_HIP_EINVAL;
+    }
+    const bool triangle = lb == nullptr;
+    const uint64_t na = la->n_rows, nb = triangle ? na : lb->n_rows;
+    if (ld < nb) {
+        set_error("rowlists_similarity: ld %llu < %llu columns", (unsigned long long)ld, (unsigned long long)nb);
+        return STORM_HIP_EINVAL;
+    }
+    if (na == 0 || nb == 0) return STORM_HIP_OK;
+    STORM_HIP_TRY(hipSetDevice(ctx->device));
+    uint32_t* d_io = reinterpret_cast<uint32_t*>(d_out);
+    uint64_t d_ld = ld;
+    if (h_out) {
+        const size_t need = (size_t)na * nb * sizeof(uint32_t);
+        if (int rc = ctx->d_band.ensure(need, "rowlists_similarity: the output")) return rc;
+        if (triangle) STORM_HIP_TRY(hipMemsetAsync(ctx->d_band, 0, need, ctx->stream));
+        d_io = ctx->d_band;
+        d_ld = nb;
+    }
+    if (int rc = triangle ? launch_lists(ctx, la, STORM_HIP_OP_AND, d_io, d_ld)
+                          : launch_lists_square(ctx, la, lb, STORM_HIP_OP_AND, d_io, d_ld))
+        return rc;
+    if (int rc = launch_similarity_finish(ctx, d_io, d_ld, na, nb, la->d_rowlen, triangle ? la->d_rowlen : lb->d_rowlen,
+                                          triangle ? 1 : 0, measure, n_bits))
+        return rc;
+    if (h_out)
+        STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(float), d_io, nb * sizeof(uint32_t), nb * sizeof(uint32_t), na,
+                                       hipMemcpyDeviceToHost, ctx->stream));
+    STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return STORM_HIP_OK;
+}
+
+int storm_hip_rowlists_pairw_similarity_device(storm_hip_ctx_t* ctx, const storm_hip_rowlists_t* l, int measure,
+                                               uint64_t n_bits, float* d_out, uint64_t ld) {
+    return guarded("storm_hip_rowlists_pairw_similarity_device", [&]() -> int {
+        return lists_similarity(ctx, const_cast<storm_hip_rowlists_t*>(l), nullptr, measure, n_bits, d_out, nullptr, ld);
+    });
+}
+
+int storm_hip_rowlists_pairw_similarity(storm_hip_ctx_t* ctx, const storm_hip_rowlists_t* l, int measure, uint64_t n_bits,
+                                        float* h_out, uint64_t ld) {
+    return guarded("storm_hip_rowlists_pairw_similarity", [&]() -> int {
+        return lists_similarity(ctx, const_cast<storm_hip_rowlists_t*>(l), nullptr, measure, n_bits, nullptr, h_out, ld);
+    });
+}
+
+int storm_hip_rowlists_square_similarity_device(storm_hip_ctx_t* ctx, storm_hip_rowlists_t* la, const storm_hip_rowlists_t* lb,
+                                                int measure, uint64_t n_bits, float* d_out, uint64_t ld) {
+    return guarded("storm_hip_rowlists_square_similarity_device", [&]() -> int {
+        if (!lb) {
+            set_error("rowlists_similarity: NULL argument");
+            return STORM_HIP_EINVAL;
+        }
+        return lists_similarity(ctx, la, lb, measure, n_bits, d_out, nullptr, ld);
+    });
+}
+
+int storm_hip_rowlists_square_similarity(storm_hip_ctx_t* ctx, storm_hip_rowlists_t* la, const storm_hip_rowlists_t* lb,
+                                         int measure, uint64_t n_bits, float* h_out, uint64_t ld) {
+    return guarded("storm_hip_rowlists_square_similarity", [&]() -> int {
+        if (!lb) {
+            set_error("rowlists_similarity: NULL argument");
+            return STORM_HIP_EINVAL;
+        }
+        return lists_similarity(ctx, la, lb, measure, n_bits, nullptr, h_out, ld);
+    });
+}
+
 }  // extern "C"

@@ -2299,7 +2299,7 @@ int launch_pairw_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int o
 // Materialised rectangle: out[i * ld + j] = popcount(a_i OP b_j) for every row i of A and j of B
 // (device pointer, uint32, ld >= b->n_rows): the tile kernel over a shadow holding [A ; B].
 int launch_square_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
-                         const storm_hip_matrix_s* b, int op, uint32_t* d_out, uint64_t ld) {
+                         const storm_hip_matrix_s* b, int op, uint32_t* d_out, uint64_t ld, bool sync) {
     if (a->n_rows == 0 || b->n_rows == 0) return STORM_HIP_OK;
     ctx->k2_tile_shape_eff = (ctx->k2_tile_shape && ctx->k2_tile_shape != 6) ? ctx->k2_tile_shape : ((a->sparse_origin && b->sparse_origin) ? 2 : 5);
     const uint64_t stride_words = a->stride_words;
@@ -2338,7 +2338,7 @@ int launch_square_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
             rc = run_tile128(ctx, 0u, (uint32_t)((a->n_rows + kThTile - 1) / kThTile), (uint32_t)(rows_a / kThTile),
                              (uint32_t)((rows_a + b->n_rows + kThTile - 1) / kThTile), false, total_stages, ops, d_out, ld,
                              (uint32_t)a->n_rows, d_counts, op == STORM_HIP_OP_XOR ? 2u : 1u, (uint32_t)rows_a,
-                             (uint32_t)b->n_rows, 0u, 0u, true);
+                             (uint32_t)b->n_rows, 0u, 0u, sync);
         }
         if (rc == STORM_HIP_EHIP) set_error("square_matrix: HIP failure");
         return rc;
@@ -2370,7 +2370,7 @@ int launch_square_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
         }
         rc = run_matrix_tiles(ctx, plan, pitch, d_out, ld, (uint32_t)a->n_rows, d_counts,
                               op == STORM_HIP_OP_XOR ? 2u : 1u, (uint32_t)rows_a, (uint32_t)b->n_rows,
-                              0u, 0u, true, bits ? &ops : nullptr);
+                              0u, 0u, sync, bits ? &ops : nullptr);
     }
     if (rc == STORM_HIP_EHIP) set_error("square_matrix: HIP failure");
     return rc;

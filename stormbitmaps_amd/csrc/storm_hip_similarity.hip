@@ -1,0 +1,257 @@
+// storm_hip_similarity.hip — the per-pair matrix finished where the counts lie: one pass that overwrites a matrix of
+// intersection counts (uint32, what every matrix-output path of this library writes) with a similarity statistic
+// (float, the same 4 bytes per entry): Jaccard, cosine (Ochiai), and the two linkage-disequilibrium measures D and r^2
+// the reference names as the purpose of the per-pair counts (README.md:165-167).
+//
+// A separate launch on the context's stream, not an epilogue of the count kernels: those finish an entry in different
+// places (k-parts that add into a cleared window, counts that are complete only at the end of a launch), and a
+// non-linear formula is right only on complete counts. 4 bytes read and 4 written per converted entry: the pass is
+// bound by HBM bandwidth.
+#include "storm_hip_internal.h"
+#include "storm_similarity_math.h"
+
+namespace storm {
+
+constexpr int kSimThreads = 256;    // 4 waves
+constexpr int kSimTileRows = 64;    // a wave walks every 4th row of the tile ...
+constexpr int kSimTileCols = 256;   // ... one 128-bit vector (4 entries) per lane
+constexpr int kSimUnroll = 4;       // rows a wave has in flight
+
+// Grid (column tiles, row tiles) of kSimTileRows x kSimTileCols entries. triangle: only entries i < j are touched — a
+// tile at or below the diagonal exits at once; entries i >= j and the pitch columns [n_cols, ld) are neither read nor
+// written. vec: the base is 16-byte aligned and ld a multiple of 4, so a lane's 4 entries are one 128-bit access
+// wherever all 4 are converted; the diagonal's vector, the last columns and everything of a misaligned matrix go entry
+// by entry.
+__global__ __launch_bounds__(kSimThreads) void similarity_finish_kernel(uint32_t* __restrict__ io, uint64_t ld, uint64_t n_rows,
+                                                                        uint64_t n_cols,
+                                                                        const uint32_t* __restrict__ counts_rows,
+                                                                        const uint32_t* __restrict__ counts_cols, int triangle,
+                                                                        int measure, uint64_t n_bits, int vec) {
+    const uint64_t row0 = (uint64_t)blockIdx.y * kSimTileRows, col0 = (uint64_t)blockIdx.x * kSimTileCols;
+    if (triangle && col0 + kSimTileCols <= row0 + 1) return;   // the tile's last column is not beyond its first row
+    // the tile's counts, once per workgroup: the rows' through the LDS, a lane's 4 columns in registers
+    __shared__ uint32_t s_rows[kSimTileRows];
+    if (threadIdx.x < kSimTileRows) s_rows[threadIdx.x] = row0 + threadIdx.x < n_rows ? counts_rows[row0 + threadIdx.x] : 0u;
+    const uint64_t c0 = col0 + (threadIdx.x & 63u) * 4u;
+    uint32_t b[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) b[k] = c0 + k < n_cols ? counts_cols[c0 + k] : 0u;
+    __syncthreads();
+    const uint32_t wave = threadIdx.x >> 6;
+    for (uint32_t r = wave; r < kSimTileRows; r += 4 * kSimUnroll) {
+        uint4 v[kSimUnroll];
+        bool whole[kSimUnroll];
+#pragma unroll
+        for (int u = 0; u < kSimUnroll; ++u) {   // the loads of kSimUnroll rows leave before the first divide
+            const uint64_t i = row0 + r + 4u * u;
+            whole[u] = vec && i < n_rows && c0 + 4 <= n_cols && (!triangle || c0 > i);
+            if (whole[u]) v[u] = *reinterpret_cast<const uint4*>(io + i * ld + c0);
+        }
+#pragma unroll
+        for (int u = 0; u < kSimUnroll; ++u) {
+            const uint64_t i = row0 + r + 4u * u;
+            if (i >= n_rows) continue;
+            const uint32_t a = s_rows[r + 4u * u];
+            uint32_t* const p = io + i * ld + c0;
+            if (whole[u]) {
+                uint4 w;
+                w.x = similarity_bits(v[u].x, a, b[0], measure, n_bits);
+                w.y = similarity_bits(v[u].y, a, b[1], measure, n_bits);
+                w.z = similarity_bits(v[u].z, a, b[2], measure, n_bits);
+                w.w = similarity_bits(v[u].w, a, b[3], measure, n_bits);
+                *reinterpret_cast<uint4*>(p) = w;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (c0 + k < n_cols && (!triangle || c0 + k > i)) p[k] = similarity_bits(p[k], a, b[k], measure, n_bits);
+            }
+        }
+    }
+}
+
+int launch_similarity_finish(storm_hip_ctx_t* ctx, void* d_io, uint64_t ld, uint64_t n_rows, uint64_t n_cols,
+                             const uint32_t* d_counts_rows, const uint32_t* d_counts_cols, int triangle, int measure,
+                             uint64_t n_bits) {
+    if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+    if (!d_io || !d_counts_rows || !d_counts_cols) {
+        set_error("similarity_finish: NULL argument");
+        return STORM_HIP_EINVAL;
+    }
+    if (measure < STORM_HIP_SIM_JACCARD || measure > STORM_HIP_SIM_LD_R2) {
+        set_error("similarity_finish: unknown measure %d (0 Jaccard, 1 cosine, 2 LD D, 3 LD r^2)", measure);
+        return STORM_HIP_EINVAL;
+    }
+    if (n_bits == 0 || n_bits > (1ull << 32)) {
+        set_error("similarity_finish: n_bits %llu is not in [1, 2^32]", (unsigned long long)n_bits);
+        return STORM_HIP_EINVAL;
+    }
+    if (ld < n_cols || (triangle && n_rows != n_cols)) {
+        set_error("similarity_finish: leading dimension < columns, or a triangle that is not square");
+        return STORM_HIP_EINVAL;
+    }
+    if (n_rows == 0 || n_cols == 0) return STORM_HIP_OK;
+    const uint64_t tiles_x = (n_cols + kSimTileCols - 1) / kSimTileCols, tiles_y = (n_rows + kSimTileRows - 1) / kSimTileRows;
+    if (tiles_y > 65535u || tiles_x > 0x7fffffffu) {
+        set_error("similarity_finish: %llu x %llu entries exceed the launch grid", (unsigned long long)n_rows,
+                  (unsigned long long)n_cols);
+        return STORM_HIP_EINVAL;
+    }
+    STORM_HIP_TRY(hipSetDevice(ctx->device));
+    const int vec = reinterpret_cast<uintptr_t>(d_io) % 16 == 0 && ld % 4 == 0;
+    hipLaunchKernelGGL(similarity_finish_kernel, dim3((uint32_t)tiles_x, (uint32_t)tiles_y), dim3(kSimThreads), 0, ctx->stream,
+                       static_cast<uint32_t*>(d_io), ld, n_rows, n_cols, d_counts_rows, d_counts_cols, triangle ? 1 : 0, measure,
+                       n_bits, vec);
+    STORM_HIP_TRY(hipGetLastError());
+    ctx->pass_report[0] |= STORM_HIP_RAN_SIMILARITY;
+    return STORM_HIP_OK;
+}
+
+// the row counts of `m` into the context's scratch at word `at` (ensured by the caller)
+static int counts_of(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint64_t at) {
+    return launch_row_counts(ctx, m, ctx->d_counts.d + at);
+}
+
+// A's rows against B's (a == b: one matrix): the finish over counts that are already complete in stream order
+static int finish_dense(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, void* d_io, uint64_t ld,
+                        int triangle, int measure, uint64_t n_bits) {
+    const uint64_t na = a->n_rows, nb = b->n_rows;
+    if (int rc = ctx->d_counts.ensure((na + (b != a ? nb : 0)) * sizeof(uint32_t), "similarity: the row-count scratch")) return rc;
+    if (int rc = counts_of(ctx, a, 0)) return rc;
+    if (b != a)
+        if (int rc = counts_of(ctx, b, na)) return rc;
+    return launch_similarity_finish(ctx, d_io, ld, na, nb, ctx->d_counts.d, ctx->d_counts.d + (b != a ? na : 0), triangle, measure,
+                                    n_bits);
+}
+
+// The AND counts of A's rows against B's, queued and not waited for, with the report storm_hip_cross_dense_matrix_device
+// writes (that one waits for the stream, which the forms below do once, after the finish).
+static int cross_counts(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, uint32_t* d_out,
+                        uint64_t ld) {
+    if (a->n_words != b->n_words) {
+        set_error("cross_dense_similarity: row widths differ");
+        return STORM_HIP_EINVAL;
+    }
+    if (int rc = launch_square_matrix(ctx, a, b, STORM_HIP_OP_AND, d_out, ld, false)) return rc;
+    ctx->pass_report[0] = STORM_HIP_RAN_TILES_OUT;
+    ctx->pass_report[1] = a->n_rows * b->n_rows * a->n_words;
+    ctx->pass_report[2] = ctx->pass_report[3] = 0;
+    return STORM_HIP_OK;
+}
+
+// the measure and n_bits before anything is launched (what launch_similarity_finish would refuse after the counts)
+static int check_measure(int measure, uint64_t n_bits) {
+    if (measure < STORM_HIP_SIM_JACCARD || measure > STORM_HIP_SIM_LD_R2 || n_bits == 0 || n_bits > (1ull << 32)) {
+        set_error("similarity: unknown measure %d, or n_bits %llu is not in [1, 2^32]", measure, (unsigned long long)n_bits);
+        return STORM_HIP_EINVAL;
+    }
+    return STORM_HIP_OK;
+}
+
+}  // namespace storm
+
+using namespace storm;
+
+extern "C" {
+
+int storm_hip_similarity_finish_device(storm_hip_ctx_t* ctx, void* d_io, uint64_t ld, uint64_t n_rows, uint64_t n_cols,
+                                       const uint32_t* d_counts_rows, const uint32_t* d_counts_cols, int triangle, int measure,
+                                       uint64_t n_bits) {
+    return guarded("storm_hip_similarity_finish_device", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        if (int rc = launch_similarity_finish(ctx, d_io, ld, n_rows, n_cols, d_counts_rows, d_counts_cols, triangle, measure,
+                                              n_bits))
+            return rc;
+        // alone on a caller's matrix the pass is the whole call: a report of its own, not an earlier call's kernels
+        // beside it (an empty shape launched nothing and leaves the report as it was)
+        if (n_rows && n_cols) {
+            memset(ctx->pass_report, 0, sizeof(ctx->pass_report));
+            ctx->pass_report[0] = STORM_HIP_RAN_SIMILARITY;
+        }
+        return STORM_HIP_OK;
+    });
+}
+
+int storm_hip_pairw_similarity_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_bits,
+                                      float* d_out, uint64_t ld) {
+    return guarded("storm_hip_pairw_similarity_device", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        if (!m || !d_out || ld < m->n_rows) {
+            set_error("pairw_similarity: NULL argument or leading dimension < rows");
+            return STORM_HIP_EINVAL;
+        }
+        if (int rc = check_measure(measure, n_bits)) return rc;
+        if (m->n_rows < 2) return STORM_HIP_OK;
+        STORM_HIP_TRY(hipSetDevice(ctx->device));
+        if (int rc = launch_pairw_matrix(ctx, m, STORM_HIP_OP_AND, reinterpret_cast<uint32_t*>(d_out), ld, 0, ~0ull, false)) return rc;
+        if (int rc = finish_dense(ctx, m, m, d_out, ld, 1, measure, n_bits)) return rc;
+        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return STORM_HIP_OK;
+    });
+}
+
+int storm_hip_pairw_similarity(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_bits, float* h_out,
+                               uint64_t ld) {
+    return guarded("storm_hip_pairw_similarity", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        if (!m || !h_out || ld < m->n_rows) {
+            set_error("pairw_similarity: NULL argument or leading dimension < rows");
+            return STORM_HIP_EINVAL;
+        }
+        if (int rc = check_measure(measure, n_bits)) return rc;
+        const uint64_t n = m->n_rows;
+        if (n == 0) return STORM_HIP_OK;
+        STORM_HIP_TRY(hipSetDevice(ctx->device));
+        const size_t need = (size_t)n * n * sizeof(uint32_t);
+        if (int rc = ctx->d_band.ensure(need, "pairw_similarity: the output")) return rc;
+        STORM_HIP_TRY(hipMemsetAsync(ctx->d_band, 0, need, ctx->stream));   // (entries i >= j: +0.0f is the same zero bits)
+        if (int rc = launch_pairw_matrix(ctx, m, STORM_HIP_OP_AND, ctx->d_band, n, 0, ~0ull, false)) return rc;
+        if (n >= 2)
+            if (int rc = finish_dense(ctx, m, m, ctx->d_band, n, 1, measure, n_bits)) return rc;
+        STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(float), ctx->d_band, n * sizeof(uint32_t), n * sizeof(uint32_t), n,
+                                       hipMemcpyDeviceToHost, ctx->stream));
+        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return STORM_HIP_OK;
+    });
+}
+
+int storm_hip_cross_dense_similarity_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b,
+                                            int measure, uint64_t n_bits, float* d_out, uint64_t ld) {
+    return guarded("storm_hip_cross_dense_similarity_device", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        if (!a || !b || !d_out || ld < b->n_rows) {
+            set_error("cross_dense_similarity: NULL argument or ld < rows of B");
+            return STORM_HIP_EINVAL;
+        }
+        if (int rc = check_measure(measure, n_bits)) return rc;
+        if (a->n_rows == 0 || b->n_rows == 0) return STORM_HIP_OK;
+        STORM_HIP_TRY(hipSetDevice(ctx->device));
+        if (int rc = cross_counts(ctx, a, b, reinterpret_cast<uint32_t*>(d_out), ld)) return rc;
+        if (int rc = finish_dense(ctx, a, b, d_out, ld, 0, measure, n_bits)) return rc;
+        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return STORM_HIP_OK;
+    });
+}
+
+int storm_hip_cross_dense_similarity(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b, int measure,
+                                     uint64_t n_bits, float* h_out, uint64_t ld) {
+    return guarded("storm_hip_cross_dense_similarity", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        if (!a || !b || !h_out || ld < b->n_rows) {
+            set_error("cross_dense_similarity: NULL argument or ld < rows of B");
+            return STORM_HIP_EINVAL;
+        }
+        if (int rc = check_measure(measure, n_bits)) return rc;
+        const uint64_t na = a->n_rows, nb = b->n_rows;
+        if (na == 0 || nb == 0) return STORM_HIP_OK;
+        STORM_HIP_TRY(hipSetDevice(ctx->device));
+        if (int rc = ctx->d_band.ensure((size_t)na * nb * sizeof(uint32_t), "cross_dense_similarity: the output")) return rc;
+        if (int rc = cross_counts(ctx, a, b, ctx->d_band, nb)) return rc;
+        if (int rc = finish_dense(ctx, a, b, ctx->d_band, nb, 0, measure, n_bits)) return rc;
+        STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(float), ctx->d_band, nb * sizeof(uint32_t), nb * sizeof(uint32_t), na,
+                                       hipMemcpyDeviceToHost, ctx->stream));
+        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return STORM_HIP_OK;
+    });
+}
+
+}  // extern "C"

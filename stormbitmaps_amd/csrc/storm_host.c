@@ -2422,6 +2422,42 @@ static int storm_lists_worthwhile(const STORM_t* h) {
     return storm_hip_rowlists_worthwhile_counts(g_ctx[V0], h->n_conts, n_elems, (max_id + 1) * 65536ull);
 }
 
+/* What the per-pair matrix of `h` runs on, on the calling thread's one slot: the handle's state checked against the container
+ * as it is now, then its row lists (*from_lists = 1) where `try_lists` and the K5 rule say so, else its dense replica (built
+ * here when the handle has none). The one path choice of STORM_pairw_matrix_device and STORM_pairw_similarity*. 0 or -3. */
+static int storm_matrix_operand(STORM_t* h, int try_lists, sparse_state_t** out, int* from_lists, int lap_on, double* lap) {
+    double lap_t0 = *lap;
+    int fresh = 0, rc = 0;
+    *from_lists = 0;
+    sparse_state_t* st = storm_state(h, &fresh);
+    const uint64_t epoch = storm_epoch();
+    if (st && !fresh && !h->hip_private && (h->hip_epoch != epoch || always_fingerprint()) &&
+        storm_fingerprint(h) != h->hip_fingerprint) {
+        storm_drop_device(h);
+        st = storm_state(h, &fresh);
+    }
+    if (!st) rc = -3;
+    if (!rc) {
+        h->hip_epoch = epoch;
+        HOST_LAP("state, fingerprint");
+        if (!device_ctx(V0)) rc = -3; /* (contexts are opened on first use) */
+    }
+    /* [r5] a list-only container that is sparse enough: straight from the lists (K5, storm_hip_lists.hip) — no dense
+     * replica is built at all then */
+    if (!rc && try_lists && storm_hip_rowlists_worthwhile(g_ctx[V0], NULL) && /* (NULL: are the lists switched on at all) */
+        (st->have_lists != 0 || storm_lists_worthwhile(h))) {
+        if (st->have_lists == 0 && storm_build_device(h, st, 2)) rc = -3;
+        else *from_lists = st->have_lists == 1 && storm_hip_rowlists_worthwhile(g_ctx[V0], st->l[V0]);
+    }
+    if (!rc) {
+        HOST_LAP("row lists built");
+        if (!*from_lists && !st->have_dense && storm_build_device(h, st, 1)) rc = -3;
+    }
+    *out = st;
+    *lap = lap_t0; /* (after a failure too: the caller's next lap starts where this one's last ended) */
+    return rc;
+}
+
 int STORM_pairw_matrix_device(STORM_t* h, int op, uint32_t* d_out, uint64_t out_rows, uint64_t out_ld) {
     if (!h) return -1;
     if (!d_out) return -2;
@@ -2432,41 +2468,18 @@ int STORM_pairw_matrix_device(STORM_t* h, int op, uint32_t* d_out, uint64_t out_
     const uint64_t n = h->n_conts;
     if (!rc && (out_rows < n || out_ld < n)) rc = -4;
     if (!rc && n != 0) {
-        int fresh = 0;
-        sparse_state_t* st = storm_state(h, &fresh);
-        if (!st) rc = -3;
-        if (!rc) {
-            const uint64_t epoch = storm_epoch();
-            if (!fresh && !h->hip_private && (h->hip_epoch != epoch || always_fingerprint()) &&
-                storm_fingerprint(h) != h->hip_fingerprint) {
-                storm_drop_device(h);
-                if (!(st = storm_state(h, &fresh))) rc = -3;
-            }
-            if (!rc) h->hip_epoch = epoch;
-        }
-        /* [r5] a list-only container that is sparse enough: straight from the lists (K5, storm_hip_lists.hip) — no dense
-         * replica is built at all then */
+        sparse_state_t* st = NULL;
         int from_lists = 0;
-        HOST_LAP("state, fingerprint");
-        if (!rc && !device_ctx(V0)) rc = -3; /* (contexts are opened on first use) */
-        if (!rc && (op == 0 || op == 1 || op == 2) && storm_hip_rowlists_worthwhile(g_ctx[V0], NULL) && /* (NULL: are the lists switched on at all) */
-            (st->have_lists != 0 || storm_lists_worthwhile(h))) {
-            if (st->have_lists == 0 && storm_build_device(h, st, 2)) rc = -3;
-            from_lists = !rc && st->have_lists == 1 && storm_hip_rowlists_worthwhile(g_ctx[V0], st->l[V0]);
-        }
-        HOST_LAP("row lists built");
+        rc = storm_matrix_operand(h, op == 0 || op == 1 || op == 2, &st, &from_lists, lap_on, &lap_t0);
         if (!rc && from_lists) {
             if (storm_hip_rowlists_pairw_matrix_device(g_ctx[V0], st->l[V0], op, d_out, out_ld) != STORM_HIP_OK) {
                 device_error("storm_hip_rowlists_pairw_matrix_device");
                 rc = -3;
             }
             HOST_LAP("matrix from the lists");
-        } else {
-            if (!rc && !st->have_dense && storm_build_device(h, st, 1)) rc = -3;
-            if (!rc && storm_hip_pairw_matrix_device(g_ctx[V0], st->m[V0], op, d_out, out_ld) != STORM_HIP_OK) {
-                device_error("storm_hip_pairw_matrix_device");
-                rc = -3;
-            }
+        } else if (!rc && storm_hip_pairw_matrix_device(g_ctx[V0], st->m[V0], op, d_out, out_ld) != STORM_HIP_OK) {
+            device_error("storm_hip_pairw_matrix_device");
+            rc = -3;
         }
     }
     device_unlock();
@@ -2540,6 +2553,16 @@ int storm_host_one_slot_or_refuse(const char* who) { return one_slot_or_refuse(w
 int storm_host_single_device(void) {
     configure_from_env();
     return VN == 1 && g_shard_count == 1;
+}
+/* what the similarity forms of the per-pair matrices run on (storm_square.c): a STORM_contiguous_t's device mirror on the
+ * calling thread's slot (NULL: the failure reported), and a STORM_t's operand by the path choice of STORM_pairw_matrix_device */
+storm_hip_matrix_t* storm_host_contig_matrix(STORM_contiguous_t* h) {
+    dense_state_t* st = contig_mirror(h);
+    return st ? st->m[V0] : NULL;
+}
+int storm_host_matrix_operand(STORM_t* h, sparse_state_t** st, int* from_lists) {
+    double lap = 0;
+    return storm_matrix_operand(h, 1, st, from_lists, 0, &lap);
 }
 int storm_host_slot(void) { return V0; }
 storm_hip_ctx_t* storm_host_ctx(void) { return device_ctx(V0); }

@@ -32,6 +32,9 @@ void storm_host_error(const char* msg);
 void storm_host_device_error(const char* where);
 int storm_host_one_slot_or_refuse(const char* who);  /* 0, or -5 with the reason */
 int storm_host_single_device(void);                  /* 1: one device slot and one shard */
+storm_hip_matrix_t* storm_host_contig_matrix(STORM_contiguous_t* h); /* its device mirror on that slot (NULL: reported) */
+/* the operand of STORM_pairw_matrix_device's path choice: *from_lists ? st->l[slot] (K5) : st->m[slot]. 0 or -3 */
+int storm_host_matrix_operand(STORM_t* h, sparse_state_t** st, int* from_lists);
 int storm_host_slot(void);                           /* the calling thread's first device slot */
 storm_hip_ctx_t* storm_host_ctx(void);               /* its context (NULL: no device, the reason reported) */
 sparse_state_t* storm_host_checked_state(STORM_t* h);

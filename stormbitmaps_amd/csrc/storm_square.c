@@ -6,8 +6,12 @@
  * rule (option matrix_lists, applied to the two together) sends to the lists are joined from their row lists (K5x,
  * storm_hip_lists.hip); any other pair is multiplied as dense replicas of one common width (the wider of the two; a
  * handle keeps its widened replica, whose extra zero columns change no count of its own triangle). One device slot and
- * one process: the rectangle is not split over devices or shards, and every rank refuses alike. */
+ * one process: the rectangle is not split over devices or shards, and every rank refuses alike.
+ *
+ * Also here, because they too sit on storm_host.c's locked paths without adding to them: the similarity forms of all three
+ * per-pair matrices (storm.h: STORM_contig_pairw_similarity, STORM_pairw_similarity, STORM_square_similarity and _device). */
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
 
 #include "storm.h"
@@ -51,10 +55,13 @@ static int dense_at_width(STORM_t* h, sparse_state_t* st, int slot, uint32_t blo
     return storm_host_build(h, st, 1, storm_hip_matrix_create_from_blocks_wide, blocks);
 }
 
-/* what = 0: *total; 1: the window into host `out`; 2: into device `out`. 0, or -3 with the reason in STORM_hip_error(). */
-static int square_locked(STORM_t* a, STORM_t* b, int what, int op, uint32_t* out, uint64_t out_ld, uint64_t* total) {
+/* what = 0: *total; 1: the window into host `out`; 2: into device `out`. measure < 0: counts under `op`; else the window
+ * finished into that similarity measure (float entries in `out`, universe n_bits). 0, or -3 with the reason in
+ * STORM_hip_error(). */
+static int square_locked(STORM_t* a, STORM_t* b, int what, int op, uint32_t* out, uint64_t out_ld, uint64_t* total,
+                         int measure, uint64_t n_bits) {
     if (!storm_host_single_device()) {
-        storm_host_error("STORM_intersect_cardinality_square / STORM_square_matrix: the rectangle of two containers is "
+        storm_host_error("STORM_intersect_cardinality_square / STORM_square_matrix / STORM_square_similarity: the rectangle of two containers is "
                          "computed on ONE device slot by ONE process; it is not split over devices or shards "
                          "(STORM_hip_set_devices, STORM_hip_set_thread_devices, STORM_hip_set_shard)");
         return -3;
@@ -75,9 +82,11 @@ static int square_locked(STORM_t* a, STORM_t* b, int what, int op, uint32_t* out
         if (sa->have_lists == 1 && sb->have_lists == 1) {
             storm_hip_rowlists_t* la = sa->l[slot];
             const storm_hip_rowlists_t* lb = sb->l[slot];
-            const int rc = what == 0   ? storm_hip_rowlists_square_total(ctx, la, lb, total)
-                           : what == 1 ? storm_hip_rowlists_square_matrix(ctx, la, lb, op, out, out_ld)
-                                       : storm_hip_rowlists_square_matrix_device(ctx, la, lb, op, out, out_ld);
+            const int rc = what == 0    ? storm_hip_rowlists_square_total(ctx, la, lb, total)
+                           : measure >= 0 ? (what == 1 ? storm_hip_rowlists_square_similarity(ctx, la, lb, measure, n_bits, (float*)out, out_ld)
+                                                       : storm_hip_rowlists_square_similarity_device(ctx, la, lb, measure, n_bits, (float*)out, out_ld))
+                           : what == 1  ? storm_hip_rowlists_square_matrix(ctx, la, lb, op, out, out_ld)
+                                        : storm_hip_rowlists_square_matrix_device(ctx, la, lb, op, out, out_ld);
             if (rc != STORM_HIP_OK) {
                 storm_host_device_error("storm_hip_rowlists_square");
                 return -3;
@@ -91,9 +100,11 @@ static int square_locked(STORM_t* a, STORM_t* b, int what, int op, uint32_t* out
     if ((x = replica_blocks(sa, slot)) > blocks) blocks = x;
     if ((x = replica_blocks(sb, slot)) > blocks) blocks = x;
     if (dense_at_width(a, sa, slot, blocks) || (b != a && dense_at_width(b, sb, slot, blocks))) return -3;
-    const int rc = what == 0   ? storm_hip_cross_dense_total(ctx, sa->m[slot], sb->m[slot], total)
-                   : what == 1 ? storm_hip_cross_dense_matrix(ctx, sa->m[slot], sb->m[slot], op, out, out_ld)
-                               : storm_hip_cross_dense_matrix_device(ctx, sa->m[slot], sb->m[slot], op, out, out_ld);
+    const int rc = what == 0    ? storm_hip_cross_dense_total(ctx, sa->m[slot], sb->m[slot], total)
+                   : measure >= 0 ? (what == 1 ? storm_hip_cross_dense_similarity(ctx, sa->m[slot], sb->m[slot], measure, n_bits, (float*)out, out_ld)
+                                               : storm_hip_cross_dense_similarity_device(ctx, sa->m[slot], sb->m[slot], measure, n_bits, (float*)out, out_ld))
+                   : what == 1  ? storm_hip_cross_dense_matrix(ctx, sa->m[slot], sb->m[slot], op, out, out_ld)
+                                : storm_hip_cross_dense_matrix_device(ctx, sa->m[slot], sb->m[slot], op, out, out_ld);
     if (rc != STORM_HIP_OK) {
         storm_host_device_error("storm_hip_cross_dense");
         return -3;
@@ -110,7 +121,7 @@ uint64_t STORM_intersect_cardinality_square(const STORM_t* STORM_RESTRICT bitmap
     uint64_t total = 0;
     storm_host_lock();
     /* (the containers are const; the device copies behind them are built and kept as for every other call) */
-    const int rc = square_locked((STORM_t*)bitmap1, (STORM_t*)bitmap2, 0, 0, NULL, 0, &total);
+    const int rc = square_locked((STORM_t*)bitmap1, (STORM_t*)bitmap2, 0, 0, NULL, 0, &total, -1, 0);
     storm_host_unlock();
     return rc ? (uint64_t)-1 : total;
 }
@@ -125,7 +136,7 @@ int STORM_square_matrix(STORM_t* a, STORM_t* b, int op, uint32_t* out, uint64_t 
     }
     if (a->n_conts == 0 || b->n_conts == 0) return 0;
     storm_host_lock();
-    const int rc = square_locked(a, b, 1, op, out, out_ld, NULL);
+    const int rc = square_locked(a, b, 1, op, out, out_ld, NULL, -1, 0);
     storm_host_unlock();
     return rc;
 }
@@ -140,7 +151,131 @@ int STORM_square_matrix_device(STORM_t* a, STORM_t* b, int op, uint32_t* d_out, 
         storm_host_error("STORM_square_matrix_device: op must be 0 (and), 1 (or) or 2 (xor)");
         rc = -3;
     }
-    if (!rc && a->n_conts != 0 && b->n_conts != 0) rc = square_locked(a, b, 2, op, d_out, out_ld, NULL);
+    if (!rc && a->n_conts != 0 && b->n_conts != 0) rc = square_locked(a, b, 2, op, d_out, out_ld, NULL, -1, 0);
     storm_host_unlock();
     return rc;
+}
+
+
+/* ---- Extension (storm.h): the per-pair matrices finished into a similarity statistic on the device — the AND-count path of
+ * the matrix calls as it is (same kernels, same choice), the rows' counts, then similarity_finish_kernel
+ * (storm_hip_similarity.hip) behind the count kernel. One device slot and one process, host forms too. */
+/* The measure and the universe size as the shim takes them: 0, or -3 with the reason. Jaccard and cosine do not read n_bits;
+ * the LD measures take `n_bits_default` (a STORM_contiguous_t's vector_length; 0 for a STORM_t, which declares none) for 0. */
+static int similarity_args(const char* who, int measure, uint64_t* n_bits, uint64_t n_bits_default) {
+    char msg[200];
+    if (measure < STORM_SIM_JACCARD || measure > STORM_SIM_LD_R2) {
+        snprintf(msg, sizeof(msg), "%s: measure must be 0 (Jaccard), 1 (cosine), 2 (LD D) or 3 (LD r^2)", who);
+        storm_host_error(msg);
+        return -3;
+    }
+    if (measure < STORM_SIM_LD_D) {
+        *n_bits = 1;
+        return 0;
+    }
+    if (*n_bits == 0) *n_bits = n_bits_default;
+    if (*n_bits == 0 || *n_bits > (1ull << 32)) {
+        snprintf(msg, sizeof(msg), "%s: the LD measures need n_bits, the size of the universe, in [1, 2^32]%s", who,
+                 n_bits_default ? "" : " (a STORM_t declares none: 0 is refused)");
+        storm_host_error(msg);
+        return -3;
+    }
+    return 0;
+}
+
+static int contig_pairw_similarity(STORM_contiguous_t* h, int measure, uint64_t n_bits, float* out, uint64_t out_rows,
+                                   uint64_t out_ld, int device, const char* who) {
+    if (!h) return -1;
+    if (!out) return -2;
+    storm_host_lock();
+    int rc = storm_host_one_slot_or_refuse(who);
+    const uint64_t n = h->n_data;
+    if (!rc && (out_rows < n || out_ld < n)) rc = -4;
+    if (!rc) rc = similarity_args(who, measure, &n_bits, h->vector_length);
+    if (!rc && n != 0) {
+        const storm_hip_matrix_t* m = storm_host_contig_matrix(h);
+        storm_hip_ctx_t* ctx = m ? storm_host_ctx() : NULL;
+        if (!ctx) rc = -3;
+        else if ((device ? storm_hip_pairw_similarity_device(ctx, m, measure, n_bits, out, out_ld)
+                         : storm_hip_pairw_similarity(ctx, m, measure, n_bits, out, out_ld)) != STORM_HIP_OK) {
+            storm_host_device_error("storm_hip_pairw_similarity");
+            rc = -3;
+        }
+    }
+    storm_host_unlock();
+    return rc;
+}
+
+int STORM_contig_pairw_similarity(STORM_contiguous_t* h, int measure, uint64_t n_bits, float* out, uint64_t out_rows,
+                                  uint64_t out_ld) {
+    return contig_pairw_similarity(h, measure, n_bits, out, out_rows, out_ld, 0, "STORM_contig_pairw_similarity");
+}
+
+int STORM_contig_pairw_similarity_device(STORM_contiguous_t* h, int measure, uint64_t n_bits, float* d_out, uint64_t out_rows,
+                                         uint64_t out_ld) {
+    return contig_pairw_similarity(h, measure, n_bits, d_out, out_rows, out_ld, 1, "STORM_contig_pairw_similarity_device");
+}
+
+static int storm_pairw_similarity(STORM_t* h, int measure, uint64_t n_bits, float* out, uint64_t out_rows, uint64_t out_ld,
+                                  int device, const char* who) {
+    if (!h) return -1;
+    if (!out) return -2;
+    storm_host_lock();
+    int rc = storm_host_one_slot_or_refuse(who);
+    const uint64_t n = h->n_conts;
+    if (!rc && (out_rows < n || out_ld < n)) rc = -4;
+    if (!rc) rc = similarity_args(who, measure, &n_bits, 0);
+    if (!rc && n != 0) {
+        sparse_state_t* st = NULL;
+        int from_lists = 0;
+        rc = storm_host_matrix_operand(h, &st, &from_lists);
+        storm_hip_ctx_t* ctx = rc ? NULL : storm_host_ctx();
+        const int slot = storm_host_slot();
+        if (!rc && !ctx) rc = -3;
+        if (!rc && from_lists) {
+            if ((device ? storm_hip_rowlists_pairw_similarity_device(ctx, st->l[slot], measure, n_bits, out, out_ld)
+                        : storm_hip_rowlists_pairw_similarity(ctx, st->l[slot], measure, n_bits, out, out_ld)) != STORM_HIP_OK) {
+                storm_host_device_error("storm_hip_rowlists_pairw_similarity");
+                rc = -3;
+            }
+        } else if (!rc && (device ? storm_hip_pairw_similarity_device(ctx, st->m[slot], measure, n_bits, out, out_ld)
+                                  : storm_hip_pairw_similarity(ctx, st->m[slot], measure, n_bits, out, out_ld)) != STORM_HIP_OK) {
+            storm_host_device_error("storm_hip_pairw_similarity");
+            rc = -3;
+        }
+    }
+    storm_host_unlock();
+    return rc;
+}
+
+int STORM_pairw_similarity(STORM_t* h, int measure, uint64_t n_bits, float* out, uint64_t out_rows, uint64_t out_ld) {
+    return storm_pairw_similarity(h, measure, n_bits, out, out_rows, out_ld, 0, "STORM_pairw_similarity");
+}
+
+int STORM_pairw_similarity_device(STORM_t* h, int measure, uint64_t n_bits, float* d_out, uint64_t out_rows, uint64_t out_ld) {
+    return storm_pairw_similarity(h, measure, n_bits, d_out, out_rows, out_ld, 1, "STORM_pairw_similarity_device");
+}
+
+/* the rectangle: what = 1 host, 2 device */
+static int square_similarity(STORM_t* a, STORM_t* b, int measure, uint64_t n_bits, float* out, uint64_t out_rows, uint64_t out_ld,
+                             int what, const char* who) {
+    if (!a || !b) return -1;
+    if (!out) return -2;
+    storm_host_lock();
+    int rc = storm_host_one_slot_or_refuse(who);
+    if (!rc && (out_rows < a->n_conts || out_ld < b->n_conts)) rc = -4;
+    if (!rc) rc = similarity_args(who, measure, &n_bits, 0);
+    if (!rc && a->n_conts != 0 && b->n_conts != 0) rc = square_locked(a, b, what, 0, (uint32_t*)out, out_ld, NULL, measure, n_bits);
+    storm_host_unlock();
+    return rc;
+}
+
+int STORM_square_similarity(STORM_t* a, STORM_t* b, int measure, uint64_t n_bits, float* out, uint64_t out_rows,
+                            uint64_t out_ld) {
+    return square_similarity(a, b, measure, n_bits, out, out_rows, out_ld, 1, "STORM_square_similarity");
+}
+
+int STORM_square_similarity_device(STORM_t* a, STORM_t* b, int measure, uint64_t n_bits, float* d_out, uint64_t out_rows,
+                                   uint64_t out_ld) {
+    return square_similarity(a, b, measure, n_bits, d_out, out_rows, out_ld, 2, "STORM_square_similarity_device");
 }
