@@ -97,19 +97,13 @@ constexpr int kWaves = 4;                            // waves per workgroup
 constexpr int kThreads = kLanes * kWaves;            // 256
 // (kChunkWords = 64, the k-chunk of one 64-bit word per lane: storm_hip_plan.h)
 constexpr int kRowsPerWave = 32;                     // A rows held in VGPRs by one wave
-constexpr int kABlockRows = kWaves * kRowsPerWave;   // 128 A rows per workgroup
+static_assert(kABlockRows == kWaves * kRowsPerWave, "128 A rows per workgroup (storm_hip_plan.h)");
 constexpr int kRowPad = 256;                         // allocated rows: a multiple of this, zero beyond n_rows (a strip's A tile)
 constexpr int kStageRows = 32;                       // B rows per LDS stage
 constexpr int kSlots = 4096;  // partial-sum slots (uint64 each)
 constexpr int kSlotsExtra = 8;  // words behind the slots: work-queue heads, zeroed by the fold
 
-struct Seg {            // one (A block, B row range) segment of the upper triangle
-    uint32_t a_row0;    // first A row of the block (kABlockRows rows are loaded from here)
-    uint32_t a_end;     // A rows >= a_end are treated as all-zero (block-column / matrix edge)
-    uint32_t j_lo;      // B rows [j_lo, j_hi)
-    uint32_t j_hi;      // j_lo == a_row0 marks a diagonal segment: count only pairs i < j
-};
-
+// (Seg, one (A block, B row range) segment of the upper triangle: storm_hip_plan.h)
 // shared launcher of the dense kernel over an arbitrary segment table (dense + sparse paths)
 int launch_pairw_segments(storm_hip_ctx_t* ctx, const uint64_t* X, uint64_t stride_words,
                           const Seg* d_segs, uint32_t n_segs, uint64_t seg_row_sum,

@@ -1,13 +1,14 @@
-// storm_hip_plan.cpp — the planners of the matrix-core kernels' work lists: pure host computation, no device, no HIP
-// runtime (storm_hip_plan.h). The launchers in storm_hip_mfma.hip compare a request with the one their cached list was
-// planned from, call the planner, and upload; the exported storm_hip_*_plan functions at the end show the same plans to
-// the CPU tests (tests/test_dist_cpu.py).
+// storm_hip_plan.cpp — the planners of the matrix-core kernels' work lists and of the sparse arena: pure host computation,
+// no device, no HIP runtime (storm_hip_plan.h). The launchers in storm_hip_mfma.hip and storm_hip_sparse.hip compare a
+// request with the one their cached list was planned from, call the planner, and upload; the exported storm_hip_*_plan
+// functions at the end show the K2 plans to the CPU tests (tests/test_dist_cpu.py), tests/arena_plan/driver.cpp the arena's.
 #include "storm_hip_plan.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <chrono>
 #include <exception>
 
 #include "storm_hip.h"
@@ -725,6 +726,471 @@ void build_bitstream(const BitstreamRequest& rq, const std::vector<RowRange>& ra
         }
     }
     plan.first_stage.push_back((uint32_t)plan.bases.size());
+}
+
+// ---- the sparse arena ----
+static int64_t steady_ns() {
+    return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+ArenaLaps::ArenaLaps() : t0_ns(steady_ns()) {}
+void ArenaLaps::lap(const char* what) {
+    if (!timing_env()) return;
+    const int64_t t = steady_ns();
+    fprintf(stderr, "[build_arena] %-28s %8.1f ms\n", what, (double)(t - t0_ns) * 1e-6);
+    t0_ns = t;
+}
+
+// The texts and codes of storm_hip_sparse_create*; max_id: the largest block id.
+static int check_arena_blocks(const ArenaBlocks& in, uint32_t* max_id_out) {
+    const uint64_t n_rows = in.n_rows, n_blocks = in.n_blocks;
+    const uint64_t* const row_block_offset = in.row_block_offset;
+    const uint32_t* const block_id = in.block_id;
+    const uint8_t* const block_kind = in.block_kind;
+    const uint32_t* const block_n = in.block_n;
+    const void* const* const block_ptr = in.block_ptr;
+    if (n_blocks > 0 && (!row_block_offset || !block_id || !block_kind || !block_ptr || !block_n)) {
+        set_error("sparse_create: NULL descriptor array");
+        return STORM_HIP_EINVAL;
+    }
+    if (n_blocks >= (1ull << 32) - kABlockRows) {
+        set_error("sparse_create: too many blocks");
+        return STORM_HIP_EINVAL;
+    }
+    // ---- validate + count blocks per column ----
+    if (n_blocks > 0 && n_rows == 0) {
+        set_error("sparse_create: %llu blocks but no rows", (unsigned long long)n_blocks);
+        return STORM_HIP_EINVAL;
+    }
+    if (n_rows > 0 && (!row_block_offset || row_block_offset[0] != 0 || row_block_offset[n_rows] != n_blocks)) {
+        set_error("sparse_create: row_block_offset must run from 0 to n_blocks = %llu", (unsigned long long)n_blocks);
+        return STORM_HIP_EINVAL;
+    }
+    uint32_t max_id = 0;
+    for (uint64_t r = 0; r < n_rows; ++r) {
+        if (row_block_offset[r] > row_block_offset[r + 1] || row_block_offset[r + 1] > n_blocks) {
+            set_error("sparse_create: row_block_offset is not a CSR over %llu blocks", (unsigned long long)n_blocks);
+            return STORM_HIP_EINVAL;
+        }
+        for (uint64_t b = row_block_offset[r]; b < row_block_offset[r + 1]; ++b) {
+            if (b > row_block_offset[r] && block_id[b] <= block_id[b - 1]) {
+                set_error("sparse_create: block ids of row %llu are not ascending", (unsigned long long)r);
+                return STORM_HIP_EINVAL;
+            }
+            if (block_id[b] >= kMaxBlockId) {  // positions are uint32: ids stop at 2^32 / 65536
+                set_error("sparse_create: block id %u out of range", block_id[b]);
+                return STORM_HIP_EINVAL;
+            }
+            if (block_kind[b] > 1) {
+                set_error("sparse_create: block kind %u", block_kind[b]);
+                return STORM_HIP_EINVAL;
+            }
+            if (block_kind[b] == 0 ? (block_n[b] > 65536u || (block_n[b] && (!block_ptr[b] || ((uintptr_t)block_ptr[b] & 1))))
+                                   : !block_ptr[b]) {
+                set_error("sparse_create: block %llu has no data (or a list that is too long or not 2-byte aligned)",
+                          (unsigned long long)b);
+                return STORM_HIP_EINVAL;
+            }
+            max_id = std::max(max_id, block_id[b]);
+        }
+    }
+    *max_id_out = max_id;
+    return STORM_HIP_OK;
+}
+
+int plan_arena_columns(const ArenaBlocks& in, ArenaColumns* cols, ArenaRows* rows, ArenaLaps& laps) {
+    uint32_t max_id = 0;
+    if (int rc = check_arena_blocks(in, &max_id)) return rc;
+    const uint64_t n_blocks = in.n_blocks;
+    const uint32_t* const block_id = in.block_id;
+    const uint8_t* const block_kind = in.block_kind;
+    const uint32_t* const block_n = in.block_n;
+    std::vector<uint64_t> per_col((size_t)max_id + 2, 0), n_list_col((size_t)max_id + 2, 0);
+    for (uint64_t b = 0; b < n_blocks; ++b) {
+        per_col[block_id[b]]++;
+        if (block_kind[b] == 0) n_list_col[block_id[b]]++;
+    }
+    // Which columns the list-probe kernel (K4) can take: all blocks lists, 2 .. 65535 rows, element offsets
+    // within 32 bits (8 octants x up to 7 elements of alignment each). Their pool rows come LAST in the
+    // layout and are not materialised at all unless a dense pass over them is asked for (sparse_probe = 0,
+    // the popcount variants): a column of short lists costs its listed positions, not 8 KiB per block.
+    std::vector<uint64_t> col_elems((size_t)max_id + 2, 0);
+    for (uint64_t b = 0; b < n_blocks; ++b)
+        if (block_kind[b] == 0) col_elems[block_id[b]] += block_n[b];
+    std::vector<uint8_t> probe_c((size_t)max_id + 2, 0);
+    {
+        uint64_t total = 0;
+        for (uint32_t c = 0; c <= max_id; ++c) {
+            const uint64_t n_l = n_list_col[c];
+            if (n_l >= 2 && n_l <= 65535 && col_elems[c] > 0 && total + col_elems[c] + 64 < (1ull << 32) - (1u << 20)) {  // (the probe kernel's element indices run up to 12 x 8192 past an item's end)
+                probe_c[c] = 1;
+                total += col_elems[c] + 64;
+            }
+        }
+    }
+    // Layout of a column: its bitmap blocks, then — on the next multiple of 512 rows — its list blocks (the kind
+    // dispatch of storm.c:618-656, once per block: list x list pairs go to the probe kernel, every pair with a
+    // bitmap block to the matrix cores, which then need the bitmap rows alone as A rows). Columns made of lists
+    // only come last: they need no pool rows at all.
+    std::vector<uint64_t> start((size_t)max_id + 2, 0), list0((size_t)max_id + 2, 0), col_end((size_t)max_id + 2, 0);
+    uint64_t run = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        for (uint32_t c = 0; c <= max_id; ++c) {
+            const bool lists_only = probe_c[c] && n_list_col[c] == per_col[c];
+            if (per_col[c] && (int)lists_only == pass) {
+                const uint64_t n_b = per_col[c] - n_list_col[c];
+                start[c] = run;
+                list0[c] = n_b && n_list_col[c] ? (run + n_b + 511) / 512 * 512 : run + n_b;
+                col_end[c] = list0[c] + n_list_col[c];
+                run = (col_end[c] + 511) / 512 * 512;  // next column starts on a 512-row A tile
+            }
+        }
+        if (pass == 0) cols->pool_rows_ready = run;
+    }
+    for (uint32_t c = 0; c <= max_id; ++c)
+        if (per_col[c]) {
+            cols->cols.push_back({start[c], col_end[c]});
+            cols->col_list0.push_back(list0[c]);
+            const uint64_t nl = n_list_col[c], nb = per_col[c] - nl;
+            cols->census[0] += nl * (nl - (nl != 0)) / 2;
+            cols->census[1] += nl * nb;
+            cols->census[2] += nb * (nb - (nb != 0)) / 2;
+            cols->census[3] += 1;
+        }
+    cols->n_pool_rows = run;
+    if (cols->n_pool_rows >= (1ull << 32) - 512) {
+        set_error("sparse_create: block pool too large");
+        return STORM_HIP_EINVAL;
+    }
+
+    laps.lap("validate");
+    // ---- pool row of every block (rows are visited in order => row order inside a column)
+    std::vector<uint32_t>&list_row = rows->list_row, &dense_row = rows->dense_row, &list_len = rows->list_len;
+    std::vector<uint64_t>&list_blk = rows->list_blk, &dense_blk = rows->dense_blk;   // the blocks behind those rows
+    {
+        std::vector<uint64_t> next_bitmap(start), next_list(list0);
+        for (uint64_t b = 0; b < n_blocks; ++b) {
+            const uint32_t pr = (uint32_t)(block_kind[b] == 0 ? next_list[block_id[b]]++ : next_bitmap[block_id[b]]++);
+            if (block_kind[b] == 0) {
+                if (block_n[b] && pr < cols->pool_rows_ready) {
+                    list_row.push_back(pr);
+                    list_blk.push_back(b);
+                    list_len.push_back(block_n[b]);
+                }
+            } else {
+                dense_row.push_back(pr);
+                dense_blk.push_back(b);
+            }
+        }
+    }
+    // ---- probe data (K4): columns whose blocks are all lists and that have at most 65535 rows
+    std::vector<uint64_t>& probe_blocks = rows->probe_blocks;
+    for (uint64_t b = 0; b < n_blocks; ++b)
+        if (block_kind[b] == 0 && probe_c[block_id[b]]) probe_blocks.push_back(b);
+    {
+        std::vector<int64_t>& col_entry = rows->col_entry;
+        col_entry.assign((size_t)max_id + 2, -1);  // column id -> index into cols->cols
+        cols->col_probe.assign(cols->cols.size(), 0);
+        cols->col_avg_len.assign(cols->cols.size(), 0);
+        size_t entry = 0;
+        for (uint32_t c = 0; c <= max_id; ++c) {
+            if (!per_col[c]) continue;
+            col_entry[c] = (int64_t)entry;
+            if (probe_c[c]) {
+                cols->col_probe[entry] = 1;
+                cols->col_avg_len[entry] = (uint32_t)(col_elems[c] / n_list_col[c]);
+            }
+            ++entry;
+        }
+    }
+    return STORM_HIP_OK;
+}
+
+namespace {
+
+// One (probe column, octant) stream: the elements of the column's list rows in that octant, in row order. Atom t is the
+// part of rows [128 t, 128 t + 128): the group of those rows reads it as its own elements, every group in front of it as
+// far positions.
+struct ProbeStream {
+    std::vector<uint32_t> row_start;   // first element of every list row of the column, then the end of the octant
+    uint32_t col = 0;                  // index into ArenaColumns::cols
+    uint32_t n_rows() const { return (uint32_t)row_start.size() - 1u; }
+    uint32_t n_atoms() const { return (n_rows() + kProbeRows - 1) / kProbeRows; }
+    uint32_t atom_start(uint32_t t) const { return row_start[std::min(t * kProbeRows, n_rows())]; }
+    uint32_t end() const { return row_start.back(); }
+};
+
+// a list that is not ascending may give ends that run backwards: refused here, before they are laid out
+// (ascending ends that disagree with the values are caught by probe_fill_kernel)
+int check_run_ends(const ArenaBlocks& in, const std::vector<uint64_t>& probe_blocks, const std::vector<uint32_t>& run_end) {
+    for (size_t pb = 0; pb < probe_blocks.size(); ++pb) {
+        uint32_t from = 0;
+        for (uint32_t o = 0; o < kProbeOctants; ++o) {
+            const uint32_t end = run_end[pb * kProbeOctants + o];
+            if (end < from || end > in.block_n[probe_blocks[pb]]) {
+                set_error("sparse_create: a list block is not strictly ascending");
+                return STORM_HIP_EINVAL;
+            }
+            from = end;
+        }
+    }
+    return STORM_HIP_OK;
+}
+
+// Where every run of a list goes: count per (probe column, octant), the octants one after the other, each on a 16-byte
+// boundary of the uint16 position array; then, rows visited in order, the element offset of every row per octant.
+std::vector<ProbeStream> lay_out_streams(const ArenaBlocks& in, const ArenaColumns& cols, const ArenaRows& rows,
+                                         const std::vector<uint32_t>& run_end, ProbeWork* work, ProbeLayout* layout) {
+    constexpr uint32_t kNoBlock = 0xffffffffu;
+    const std::vector<uint64_t>& probe_blocks = rows.probe_blocks;
+    const size_t n_e = cols.cols.size();
+    std::vector<uint64_t> oct_count(n_e * kProbeOctants, 0), oct_base(n_e * kProbeOctants, 0);
+    layout->run_dst.assign(probe_blocks.size() * kProbeOctants, 0);
+    layout->block_local.assign(probe_blocks.size(), kNoBlock);
+    for (size_t pb = 0; pb < probe_blocks.size(); ++pb) {
+        const size_t e = (size_t)rows.col_entry[in.block_id[probe_blocks[pb]]];
+        uint32_t from = 0;
+        for (uint32_t o = 0; o < kProbeOctants; ++o) {
+            oct_count[e * kProbeOctants + o] += run_end[pb * kProbeOctants + o] - from;
+            from = run_end[pb * kProbeOctants + o];
+        }
+    }
+    uint64_t at = 0;
+    for (size_t i = 0; i < oct_count.size(); ++i) {
+        at = (at + 7) & ~7ull;
+        oct_base[i] = at;
+        at += oct_count[i];
+    }
+    layout->n_probe_elems = (size_t)at + 8;
+    for (size_t i = 0; i < oct_count.size(); ++i)
+        if (oct_count[i])
+            work->probe_regions.push_back({(uint32_t)oct_base[i], (uint32_t)(oct_base[i] + oct_count[i]),
+                                           (uint32_t)cols.col_list0[i / kProbeOctants], (uint32_t)(i % kProbeOctants)});
+    std::vector<uint64_t> cursor(oct_base);
+    std::vector<uint64_t> next(rows.col_entry.size(), 0);  // list blocks of the column seen so far
+    std::vector<ProbeStream> streams(n_e * kProbeOctants);
+    for (size_t e = 0; e < n_e; ++e)
+        if (cols.col_probe[e])
+            for (uint32_t o = 0; o < kProbeOctants; ++o)
+                streams[e * kProbeOctants + o].row_start.reserve((size_t)(cols.cols[e].r1 - cols.col_list0[e]) + 1);
+    size_t pb = 0;
+    for (uint64_t b = 0; b < in.n_blocks; ++b) {
+        if (in.block_kind[b] != 0) continue;
+        const uint32_t c = in.block_id[b];
+        const uint64_t local = next[c]++;
+        const int64_t e = rows.col_entry[c];
+        if (e < 0 || !cols.col_probe[(size_t)e]) continue;
+        layout->block_local[pb] = (uint32_t)local;
+        uint32_t from = 0;
+        for (uint32_t o = 0; o < kProbeOctants; ++o) {
+            const size_t i = (size_t)e * kProbeOctants + o;
+            streams[i].row_start.push_back((uint32_t)cursor[i]);
+            layout->run_dst[pb * kProbeOctants + o] = (uint32_t)cursor[i];
+            cursor[i] += run_end[pb * kProbeOctants + o] - from;
+            from = run_end[pb * kProbeOctants + o];
+        }
+        ++pb;
+    }
+    // the streams of the probe columns, each closed by the end of its octant
+    std::vector<ProbeStream> out;
+    for (size_t i = 0; i < streams.size(); ++i)
+        if (!streams[i].row_start.empty()) {
+            streams[i].row_start.push_back((uint32_t)(oct_base[i] + oct_count[i]));
+            streams[i].col = (uint32_t)(i / kProbeOctants);
+            out.push_back(std::move(streams[i]));
+        }
+    return out;
+}
+
+// The items that read one chunk of a stream; the families of a launch and their deal onto the XCDs.
+template <class Item>
+struct Families {
+    struct Family {
+        uint64_t work = 0;
+        uint32_t col = 0;
+        std::vector<Item> items;
+    };
+    std::vector<Family> families;
+
+    // families to XCDs: heaviest first onto the lightest queue; block b of the launch runs on XCD b % 8
+    // (observed; speed only), so the launch order takes one item of every queue in turn
+    void deal(std::vector<Item>* items, std::vector<uint32_t>* item_col) const {
+        std::vector<size_t> order(families.size());
+        for (size_t f = 0; f < order.size(); ++f) order[f] = f;
+        std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return families[x].work > families[y].work; });
+        std::vector<Item> queue[8];
+        std::vector<uint32_t> queue_col[8];
+        uint64_t load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (size_t f : order) {
+            if (families[f].items.empty()) continue;
+            int q = 0;
+            for (int x = 1; x < 8; ++x)
+                if (load[x] < load[q]) q = x;
+            queue[q].insert(queue[q].end(), families[f].items.begin(), families[f].items.end());
+            queue_col[q].insert(queue_col[q].end(), families[f].items.size(), families[f].col);
+            load[q] += families[f].work;
+        }
+        size_t longest = 0;
+        for (int x = 0; x < 8; ++x) longest = std::max(longest, queue[x].size());
+        for (size_t pos = 0; pos < longest; ++pos)
+            for (int x = 0; x < 8; ++x)
+                if (pos < queue[x].size()) {
+                    items->push_back(queue[x][pos]);
+                    item_col->push_back(queue_col[x][pos]);
+                }
+    }
+};
+
+// The items of one stream, `per_item` groups to an item. chunk_first: the first atom of every chunk of the stream's grid,
+// then n_atoms — the grid runs over atoms 1 .. (atom 0 is nobody's far part). An item's groups need the rest of the chunk
+// their successor atom lies in and every later chunk: the first item of the groups takes their own pairs too, one item
+// follows per later chunk; groups with nobody behind them go to the stream's last family. make(stream, g0, g1, first,
+// b0, b1, &item) fills the item of groups [g0, g1) with the far piece [min(b0, b1), b1) and says whether it is needed.
+template <class Item, class Make>
+void plan_stream_items(const ProbeStream& st, const std::vector<uint32_t>& chunk_first, uint32_t per_item,
+                       Families<Item>* fams, Make make) {
+    const uint32_t n_atoms = st.n_atoms();
+    const size_t fam0 = fams->families.size();
+    fams->families.resize(fam0 + chunk_first.size());  // one per chunk (+ one for groups without a far part)
+    for (size_t f = fam0; f < fams->families.size(); ++f) fams->families[f].col = st.col;
+    auto emit = [&](size_t c, uint32_t g0, uint32_t g1, bool first, uint32_t b0, uint32_t b1) {
+        Item it{};
+        if (!make(st, g0, g1, first, b0, b1, &it)) return;
+        fams->families[fam0 + c].items.push_back(it);
+        // every item pays for the histograms of its groups
+        fams->families[fam0 + c].work += (uint64_t)(b1 - std::min(b0, b1)) * (g1 - g0) + 8192u * (g1 - g0);
+    };
+    for (uint32_t g0 = 0; g0 < n_atoms; g0 += per_item) {
+        const uint32_t g1 = std::min(g0 + per_item, n_atoms);
+        const uint32_t own_end = st.atom_start(g1);
+        if (own_end == st.atom_start(g0)) continue;  // no listed position of these rows in this octant
+        if (g1 >= n_atoms) {  // the last groups have nobody behind them
+            emit(chunk_first.size() - 1, g0, g1, true, own_end, own_end);
+            continue;
+        }
+        size_t c = 0;
+        while (c + 1 < chunk_first.size() && chunk_first[c + 1] <= g1) ++c;
+        for (bool first = true; c + 1 < chunk_first.size(); ++c, first = false)
+            emit(c, g0, g1, first, first ? own_end : st.atom_start(chunk_first[c]), st.atom_start(chunk_first[c + 1]));
+    }
+}
+
+// probe_lists_kernel: one group per item; its first item carries the near range
+bool make_thin_item(const ProbeStream& st, uint32_t g0, uint32_t g1, bool first, uint32_t b0, uint32_t b1, ProbeItem* it) {
+    const uint32_t a_begin = st.atom_start(g0), a_end = st.atom_start(g1);
+    const uint32_t n0 = first ? a_begin : 0u, n1 = first ? a_end : 0u;
+    *it = {a_begin, a_end, n0, n1, std::min(b0, b1), b1, g0 * kProbeRows};
+    return n1 > n0 || b1 > b0;
+}
+// [r6] probe_lists_fat_kernel: the same work in bundles of kFatGroups groups — atoms at[k] .. at[k + 1] of the groups of
+// the bundle, the far piece, first = the bundle's near parts are this item's
+bool make_fat_item(const ProbeStream& st, uint32_t g0, uint32_t g1, bool first, uint32_t b0, uint32_t b1, ProbeFatItem* it) {
+    for (uint32_t k = 0; k <= kFatGroups; ++k) it->at[k] = st.atom_start(std::min(g0 + k, g1));
+    it->b_begin = std::min(b0, b1);
+    it->b_end = b1;
+    it->first = first ? 1u : 0u;
+    return first || b1 > it->b_begin;
+}
+
+}  // namespace
+
+int plan_arena_probe(const ArenaBlocks& in, const ArenaColumns& cols, const ArenaRows& rows, const std::vector<uint32_t>& run_end,
+                     ProbeWork* work, ProbeLayout* layout, ArenaLaps& laps) {
+    if (int rc = check_run_ends(in, rows.probe_blocks, run_end)) return rc;
+    if (rows.probe_blocks.empty()) return STORM_HIP_OK;
+    const std::vector<ProbeStream> streams = lay_out_streams(in, cols, rows, run_end, work, layout);
+    laps.lap("layout (prefix sums, row starts)");
+    // atoms of the far stream (the elements of one group of kProbeRows rows in one octant): the device deals
+    // the positions of every atom by LDS bank (probe_deal_kernel; why: see there)
+    // far work of all groups -> positions per item: about 4096 items over all probe columns, between
+    // 2^15 and 2^21 positions each (an item zeroes and scatters its 128 KiB table first)
+    uint64_t far_work = 0;
+    for (const ProbeStream& st : streams)
+        for (uint32_t t = 0; t < st.n_atoms(); ++t) {
+            layout->atoms.push_back(st.atom_start(t));
+            layout->atoms.push_back(st.atom_start(t + 1));
+            far_work += st.end() - st.atom_start(t + 1);
+        }
+    // Chunks of the far stream are the SAME for every group of a (column, octant) stream: a fixed grid of runs
+    // of atoms, ~far_work / 2048 positions each and at most 2^23. A group needs the rest of the chunk its own
+    // atom lies in and every later chunk. The items that read one chunk are a FAMILY; a family goes to one XCD,
+    // its items one after the other, so that the XCD's 32 CUs work through the same positions at the same time
+    // and HBM delivers them once (the kernel fetched 16 GB per launch at c4's 20971 draws — every group
+    // streaming its own 4 MiB chunks through an L2 that hit 9 % of the time — and ran at the HBM rate with the
+    // LDS half idle). Every item pays for its group's histogram, so fewer, longer items win as long as the
+    // 512 workgroup slots stay filled: / 4096 and 2^21 until round 4; / 2048 is 8 - 18 % faster at every c4
+    // load and 2^23 another 7 % at 30000 draws (profiles/r04_h_sparse_probe.txt).
+    const uint64_t kProbeChunk =
+        std::min<uint64_t>(1u << 23, std::max<uint64_t>(1u << 15, far_work / 2048)) & ~7ull;
+    Families<ProbeItem> thin;
+    Families<ProbeFatItem> fat;   // the same chunk grid, the same families and queues
+    std::vector<uint32_t> chunk_first;
+    for (const ProbeStream& st : streams) {
+        chunk_first.clear();
+        for (uint32_t t = 1; t < st.n_atoms();) {
+            chunk_first.push_back(t);
+            const uint64_t from = st.atom_start(t);
+            ++t;
+            while (t < st.n_atoms() && st.atom_start(t) - from < kProbeChunk) ++t;
+        }
+        chunk_first.push_back(st.n_atoms());
+        plan_stream_items(st, chunk_first, 1u, &thin, make_thin_item);
+        plan_stream_items(st, chunk_first, kFatGroups, &fat, make_fat_item);
+    }
+    thin.deal(&work->items, &work->item_col);
+    fat.deal(&work->fat_items, &work->fat_col);
+    return STORM_HIP_OK;
+}
+
+// lookups of an item: a streamed far position against every group of the item + the own rows' elements (against
+// their own group and, in a bundle, the groups in front of it)
+static uint64_t item_lookups(const ProbeItem& it) { return (uint64_t)(it.b_end - it.b_begin) + (it.n_end - it.n_begin); }
+static uint64_t item_lookups(const ProbeFatItem& it) {
+    uint64_t lookups = 0;
+    uint32_t groups = 0;
+    for (uint32_t g = 0; g < kFatGroups; ++g) {
+        const uint32_t len = it.at[g + 1] - it.at[g];
+        groups += len != 0;
+        if (it.first) lookups += (uint64_t)len * (g + 1u);
+    }
+    return lookups + (uint64_t)(it.b_end - it.b_begin) * groups;
+}
+template <class Item>
+static void plan_launch_of(const std::vector<Item>& all, const std::vector<uint32_t>& col, const ProbeLaunchRequest& rq,
+                           std::vector<Item>* mine, ProbeLaunchPlan* plan) {
+    for (size_t k = 0; k < all.size(); ++k)
+        if (rq.use_probe[col[k]]) mine->push_back(all[k]);
+    // shard r of G takes items r, r + G, ...: the grid covers ceil((n - r) / G) of them
+    const size_t n_mine = mine->size();
+    plan->n_probe_launch = n_mine > rq.shard_rank ? (uint32_t)((n_mine - rq.shard_rank + rq.shard_count - 1) / rq.shard_count) : 0u;
+    for (size_t k = rq.shard_rank; k < n_mine; k += rq.shard_count) plan->probe_lookups_launch += item_lookups((*mine)[k]);
+}
+
+void plan_probe_launch(const ProbeWork& work, const ProbeLaunchRequest& rq, ProbeLaunchPlan* plan) {
+    *plan = ProbeLaunchPlan();
+    for (uint8_t u : rq.use_probe) plan->n_probe_cols_launch += u;
+    if (rq.bundle == 1) plan_launch_of(work.items, work.item_col, rq, &plan->mine, plan);
+    else plan_launch_of(work.fat_items, work.fat_col, rq, &plan->fat, plan);
+}
+
+void plan_sparse_segments(const std::vector<RowRange>& cols, uint32_t seg_len, uint32_t shard_rank, uint32_t shard_count,
+                          std::vector<Seg>* out, uint64_t* seg_row_sum) {
+    std::vector<Seg>& mine = *out;
+    mine.clear();
+    // upper triangle of every block column; shard = every shard_count-th segment
+    std::vector<Seg> full, diag;
+    for (const RowRange& col : cols) {
+        const uint64_t lo = col.r0, hi = col.r1;
+        for (uint64_t a0 = lo; a0 < hi; a0 += kABlockRows) {
+            const uint32_t a_end = (uint32_t)std::min<uint64_t>(a0 + kABlockRows, hi);
+            if (a_end - a0 > 1) diag.push_back({(uint32_t)a0, a_end, (uint32_t)a0, a_end});
+            for (uint64_t j = a0 + kABlockRows; j < hi; j += seg_len)
+                full.push_back({(uint32_t)a0, a_end, (uint32_t)j, (uint32_t)std::min<uint64_t>(j + seg_len, hi)});
+        }
+    }
+    for (size_t i = shard_rank; i < full.size(); i += shard_count) mine.push_back(full[i]);
+    for (size_t i = shard_rank; i < diag.size(); i += shard_count) mine.push_back(diag[i]);
+    *seg_row_sum = 0;
+    for (const Seg& g : mine) *seg_row_sum += g.j_hi - g.j_lo;
 }
 
 }  // namespace storm

@@ -1,6 +1,7 @@
-// storm_hip_plan.h — the work lists of the matrix-core kernels (K2*): the records the planners write and the kernels
-// read, the geometry both sides need, and the planners themselves (storm_hip_plan.cpp: plain C++, no device, no HIP
-// runtime). storm_hip_internal.h includes this header; the planners see nothing of the context.
+// storm_hip_plan.h — the work lists of the matrix-core kernels (K2*) and of the sparse arena (column layout, K4's items,
+// K1's segments over the pool): the records the planners write and the kernels read, the geometry both sides need, and
+// the planners themselves (storm_hip_plan.cpp: plain C++, no device, no HIP runtime). storm_hip_internal.h includes this
+// header; the planners see nothing of the context.
 //
 // Every planner takes ONE request struct that holds all it reads besides the row ranges (which travel next to it and
 // are part of the request by their hash). The launchers cache an uploaded list under the request it was planned from
@@ -221,5 +222,123 @@ struct BitstreamPlan {
 BitstreamRequest bitstream_request(const BitstreamShaping& sh, const std::vector<RowRange>& ranges, uint32_t n_kslices,
                                    uint32_t shard_rank, uint32_t shard_count, uint32_t n_cus, uint64_t pitch_bytes);
 void build_bitstream(const BitstreamRequest& rq, const std::vector<RowRange>& ranges, BitstreamPlan& plan);
+
+// ---- the sparse arena (storm_hip_sparse.hip): block-column layout, K4's work lists, K1's segments ----
+constexpr uint32_t kBlockWords = 1024;      // 65536 bits
+constexpr uint32_t kMaxBlockId = 65536;     // uint32 positions / 65536 bits per block
+constexpr int kABlockRows = 128;            // K1: A rows per workgroup (storm_hip_internal.h: kWaves * kRowsPerWave)
+// (256 rows x 4096 positions — half the passes over the elements, two 16-byte reads per lookup — is slower:
+//  4.57 against 3.67 ms at c4's 20971 draws; the LDS reads are the larger half of the time)
+constexpr uint32_t kProbeRows = 128;        // A rows per item
+constexpr uint32_t kProbeOctBits = 13;      // positions per table: 2^13 of the block's 2^16 (table = 2^13 x 16 B)
+constexpr uint32_t kProbeOctants = 1u << (16 - kProbeOctBits);
+constexpr uint32_t kFatGroups = 4;          // groups per workgroup of probe_lists_fat_kernel
+
+struct Seg {            // one (A block, B row range) segment of the upper triangle (K1)
+    uint32_t a_row0;    // first A row of the block (kABlockRows rows are loaded from here)
+    uint32_t a_end;     // A rows >= a_end are treated as all-zero (block-column / matrix edge)
+    uint32_t j_lo;      // B rows [j_lo, j_hi)
+    uint32_t j_hi;      // j_lo == a_row0 marks a diagonal segment: count only pairs i < j
+};
+static_assert(sizeof(Seg) == 16, "read by device code");
+
+struct ProbeItem {            // probe_lists_kernel: one group of kProbeRows rows x one octant x one chunk of the far stream
+    uint32_t a_begin, a_end;  // elements of the A rows [a0, a0 + 128) in this octant
+    uint32_t n_begin, n_end;  // "near" elements: the A rows' own (row-tagged, masked); first chunk only
+    uint32_t b_begin, b_end;  // chunk of the elements of the rows behind the group (positions only)
+    uint32_t a0;              // first A row (row index within the column)
+};
+static_assert(sizeof(ProbeItem) == 28, "read by device code");
+struct ProbeFatItem {              // probe_lists_fat_kernel: a bundle of kFatGroups consecutive groups
+    uint32_t at[kFatGroups + 1];   // elements of group k of the bundle in this octant: [at[k], at[k + 1])
+    uint32_t b_begin, b_end;       // chunk of the elements of the rows behind the bundle
+    uint32_t first;                // 1: the bundle's own pairs (inside and between its groups) belong to this item
+};
+static_assert(sizeof(ProbeFatItem) == 32, "read by device code");
+struct ProbeRegion { uint32_t e_begin, e_end, pool_row0, octant; };   // expand_probe_kernel: four uint32 per region
+static_assert(sizeof(ProbeRegion) == 16, "read by device code");
+
+// The flat block description of storm_hip.h: rows -> blocks (CSR), per block its column id, kind (0 list, 1 bitmap),
+// list length and data.
+struct ArenaBlocks {
+    uint64_t n_rows = 0, n_blocks = 0;
+    const uint64_t* row_block_offset = nullptr;
+    const uint32_t* block_id = nullptr;
+    const uint8_t* block_kind = nullptr;
+    const uint32_t* block_n = nullptr;
+    const void* const* block_ptr = nullptr;
+};
+
+// STORM_HIP_TIMING: the host time since the last lap, to stderr
+struct ArenaLaps {
+    int64_t t0_ns;
+    ArenaLaps();
+    void lap(const char* what);
+};
+
+// What the arena keeps of its column layout.
+struct ArenaColumns {
+    std::vector<RowRange> cols;      // pool-row range [r0, r1) of each non-empty column; every r0
+                                     // is a multiple of 512 and the gap up to it is zero rows
+    uint64_t census[4] = {0, 0, 0, 0};
+    uint64_t n_pool_rows = 0;        // rows of the whole layout: columns the list-probe kernel cannot take first, ...
+    uint64_t pool_rows_ready = 0;    // ... and only those exist until a dense pass over a probe column is asked for
+    // list-probe path (K4): columns whose blocks are all short lists
+    std::vector<uint64_t> col_list0; // per entry of `cols`: first pool row of the column's LIST blocks (its bitmap
+                                     // blocks come first, the lists on the next multiple of 512 rows)
+    std::vector<uint8_t> col_probe;  // per entry of `cols`: 1 = has probe data (its list blocks among themselves)
+    std::vector<uint32_t> col_avg_len;  // per entry of `cols`: mean list length (probe columns)
+};
+// ... and what only the build reads: the pool row of every block (rows are visited in order => row order inside a column)
+struct ArenaRows {
+    std::vector<uint32_t> list_row, list_len, dense_row;   // list blocks that own a pool row (and are not empty); bitmap blocks
+    std::vector<uint64_t> list_blk, dense_blk;             // the blocks behind those rows
+    std::vector<uint64_t> probe_blocks;                    // the list blocks of probe columns, in row order
+    std::vector<int64_t> col_entry;                        // column id -> index into `cols` (-1: no block), ids 0 .. max id + 1
+};
+// Validates the description (the texts and codes of storm_hip_sparse_create*) and lays the block columns out.
+int plan_arena_columns(const ArenaBlocks& in, ArenaColumns* cols, ArenaRows* rows, ArenaLaps& laps);
+
+// K4's work: what the arena keeps ...
+struct ProbeWork {
+    std::vector<ProbeRegion> probe_regions;  // (column, octant) element ranges: how ensure_full_pool expands the lists
+    // both lists hold the same work for all eligible columns, in launch order (family by family on 8 queues); *_col: the
+    // item's entry of `cols`, by which a launch filters them
+    std::vector<ProbeItem> items;          // one group per workgroup (probe_lists_kernel)
+    std::vector<uint32_t> item_col;
+    std::vector<ProbeFatItem> fat_items;   // [r6] bundles of kFatGroups groups (probe_lists_fat_kernel)
+    std::vector<uint32_t> fat_col;
+};
+// ... and where the build's kernels put the elements
+struct ProbeLayout {
+    size_t n_probe_elems = 0;
+    std::vector<uint32_t> run_dst;       // per probe block and octant: where the octant's run starts in the element arrays
+    std::vector<uint32_t> block_local;   // the block's row inside its column's list rows
+    std::vector<uint32_t> atoms;         // {first element, end} of every atom of the far stream
+};
+// run_end: per probe block and octant, the end of the octant's run inside the list (probe_run_end_kernel).
+int plan_arena_probe(const ArenaBlocks& in, const ArenaColumns& cols, const ArenaRows& rows, const std::vector<uint32_t>& run_end,
+                     ProbeWork* work, ProbeLayout* layout, ArenaLaps& laps);
+
+// One launch of K4: this shard's view of the items of the columns in use.
+struct ProbeLaunchRequest {
+    uint32_t shard_rank = 0, shard_count = 0;
+    int32_t bundle = 0;                  // 1: ProbeWork::items (probe_lists_kernel), kFatGroups: fat_items
+    std::vector<uint8_t> use_probe;      // per entry of `cols`
+    bool operator==(const ProbeLaunchRequest& o) const {
+        return shard_rank == o.shard_rank && shard_count == o.shard_count && bundle == o.bundle && use_probe == o.use_probe;
+    }
+};
+struct ProbeLaunchPlan {
+    std::vector<ProbeItem> mine;         // the records to upload: one of the two lists is filled
+    std::vector<ProbeFatItem> fat;
+    uint32_t n_probe_launch = 0, n_probe_cols_launch = 0;
+    uint64_t probe_lookups_launch = 0;   // positions the launched items stream + their own rows' elements (this shard)
+};
+void plan_probe_launch(const ProbeWork& work, const ProbeLaunchRequest& rq, ProbeLaunchPlan* plan);
+
+// K1 over the pool: the upper triangle of every block column; shard = every shard_count-th segment.
+void plan_sparse_segments(const std::vector<RowRange>& cols, uint32_t seg_len, uint32_t shard_rank, uint32_t shard_count,
+                          std::vector<Seg>* mine, uint64_t* seg_row_sum);
 
 }  // namespace storm

@@ -38,33 +38,15 @@ void warm_sparse_code(hipStream_t stream) { hipLaunchKernelGGL(warm_sparse_kerne
 
 constexpr uint64_t kPoolPitchDefault = 1024;
 
-struct storm_hip_sparse_s {
+struct storm_hip_sparse_s : storm::ArenaColumns, storm::ProbeWork {   // the column layout and K4's work: storm_hip_plan.h
     uint64_t* d_pool = nullptr;      // pool rows: [pool_rows_ready + 512][pitch] words, 1024 of them used
-    uint64_t pitch = kPoolPitchDefault;  // words per pool row (see build_arena: the row pitch and the memory channels)
-    uint64_t n_pool_rows = 0;        // rows of the whole layout: columns the list-probe kernel cannot take first, ...
-    uint64_t pool_rows_ready = 0;    // ... and only those exist until a dense pass over a probe column is asked for
-    struct ProbeRegion { uint32_t e_begin, e_end, pool_row0, octant; };
-    std::vector<ProbeRegion> probe_regions;  // (column, octant) element ranges: how ensure_full_pool expands the lists
-    std::vector<RowRange> cols;      // pool-row range [r0, r1) of each non-empty column; every r0
-                                     // is a multiple of 512 and the gap up to it is zero rows
-    uint64_t census[4] = {0, 0, 0, 0};
-    // list-probe path (K4): columns whose blocks are all short lists
-    std::vector<uint64_t> col_list0; // per entry of `cols`: first pool row of the column's LIST blocks (its bitmap
-                                     // blocks come first, the lists on the next multiple of 512 rows)
-    std::vector<uint8_t> col_probe;  // per entry of `cols`: 1 = has probe data (its list blocks among themselves)
-    std::vector<uint32_t> col_avg_len;  // per entry of `cols`: mean list length (probe columns)
+    uint64_t pitch = kPoolPitchDefault;  // words per pool row (see fill_pool_rows: the row pitch and the memory channels)
     uint32_t* d_probe_elems = nullptr;  // (row in column) << 16 | position in block, column by column, row order
     uint16_t* d_probe_pos16 = nullptr;  // 2 x the positions alone (byte offsets into a count table), same index ranges, own order
-    struct ProbeItemHost { uint32_t a_begin, a_end, n_begin, n_end, b_begin, b_end, a0, col; };
-    std::vector<ProbeItemHost> probe_items;  // all eligible columns (family order); filtered per launch
-    // [r6] the same work in bundles of kFatGroups groups (probe_lists_fat_kernel): atoms at[k] .. at[k + 1] of the groups
-    // of the bundle, the far piece, first = the bundle's near parts are this item's
-    struct ProbeFatItemHost { uint32_t at[5]; uint32_t b_begin, b_end, first, col; };
-    std::vector<ProbeFatItemHost> probe_fat_items;
-    int probe_bundle_launch = 1;   // which list the device holds (1: probe_items, 4: probe_fat_items)
+    // K4's item list on the device: planned from probe_request (which list, which columns, which shard)
+    storm::ProbeLaunchRequest probe_request;   // (shard_count 0: nothing is uploaded yet)
     void* d_probe_items = nullptr;
     size_t probe_items_capacity = 0;
-    uint64_t probe_key = ~0ull;
     uint32_t n_probe_launch = 0, n_probe_cols_launch = 0;
     uint64_t probe_lookups_launch = 0;  // positions the launched items stream + their own rows' elements (this shard)
     // segment table cache (per shard)
@@ -76,8 +58,6 @@ struct storm_hip_sparse_s {
 
 namespace {
 
-constexpr uint32_t kBlockWords = 1024;  // 65536 bits
-constexpr uint32_t kMaxBlockId = 65536;  // uint32 positions / 65536 bits per block
 constexpr uint32_t kSerialMagic = 0x314d5453u;  // "STM1": second header word of STORM_serialize
 
 // list-kind block -> pool row: one workgroup per block
@@ -121,19 +101,8 @@ __global__ __launch_bounds__(kThreads) void expand_lists_kernel(
 // as a transposed BITMAP (128-bit masks per position, 128 KiB, popcounts per lookup — v_bcnt_u32_b32 is half rate);
 // the counts are what those popcounts add up to.
 // ------------------------------------------------------------------------------------------
-struct ProbeItem {
-    uint32_t a_begin, a_end;  // elements of the A rows [a0, a0 + 128) in this octant
-    uint32_t n_begin, n_end;  // "near" elements: the A rows' own (row-tagged, masked); first chunk only
-    uint32_t b_begin, b_end;  // chunk of the elements of the rows behind the group (positions only)
-    uint32_t a0;              // first A row (row index within the column)
-};
 constexpr int kProbeThreads = 1024;
-// (256 rows x 4096 positions — half the passes over the elements, two 16-byte reads per lookup — is slower:
-//  4.57 against 3.67 ms at c4's 20971 draws; the LDS reads are the larger half of the time)
-constexpr uint32_t kProbeRows = 128;        // A rows per item
 [[maybe_unused]] constexpr uint32_t kProbeWords = kProbeRows / 32u;  // (the mask words of the bitmap form)
-constexpr uint32_t kProbeOctBits = 13;      // positions per table: 2^13 of the block's 2^16 (table = 2^13 x 16 B)
-constexpr uint32_t kProbeOctants = 1u << (16 - kProbeOctBits);
 
 // One workgroup = one item = one group of kProbeRows rows x one octant of the block, against a chunk of the positions
 // of the rows behind the group. All it needs of the group is HOW MANY of its rows list each position: Cn, built by an
@@ -294,12 +263,6 @@ __global__ __launch_bounds__(kT, 8) void probe_lists_kernel(  // (8 waves per SI
 //     counters; the pairs between two groups of the bundle from the later group's elements in the earlier group's table.
 // Tables: 4 x 16 KiB of 16-bit counts. Same slots / in-launch fold as probe_lists_kernel.
 // ------------------------------------------------------------------------------------------
-constexpr uint32_t kFatGroups = 4;
-struct ProbeFatItem {
-    uint32_t at[kFatGroups + 1];   // elements of group k of the bundle in this octant: [at[k], at[k + 1])
-    uint32_t b_begin, b_end;       // chunk of the elements of the rows behind the bundle
-    uint32_t first;                // 1: the bundle's own pairs (inside and between its groups) belong to this item
-};
 template <int kT>
 __global__ __launch_bounds__(kT, kT / 128) void probe_lists_fat_kernel(   // (two workgroups per CU by LDS: 2 x 64 KiB)
     const uint16_t* __restrict__ pos16, const ProbeFatItem* __restrict__ items, uint32_t item_stride, uint32_t item_first,
@@ -830,10 +793,243 @@ void storm_hip_stage_destroy(storm_hip_ctx_t* ctx, storm_hip_stage_t* st) {
     delete st;
 }
 
-// Builds the device arena from the flat block description of storm_hip.h. `bitmaps_in_stream`:
-// the bitmap blocks' words are not in `bitmap_pool` but inside `list_pool` itself (then a byte
-// stream viewed as uint16, block_data_offset of a bitmap block in uint16 units): the whole stream
-// is uploaded once and both block kinds are unpacked from it on the device.
+// ---- build_arena: the device arena from the flat block description of storm_hip.h ----
+// device temporaries of the build: released on every way out
+struct DevTemps {
+    uint32_t *lrow = nullptr, *llen = nullptr, *tags = nullptr, *rend = nullptr, *rdst = nullptr;
+    uint32_t *atoms = nullptr, *bad = nullptr, *pllen = nullptr;
+    uint64_t *loff = nullptr, *ploff = nullptr;
+    uint16_t *lists = nullptr, *pos_tmp = nullptr;
+    uint64_t* ltable = nullptr;
+    storm_hip_ctx_t* ctx = nullptr;
+    ~DevTemps() {
+        // (the build has waited for its last kernel; a hipFree waits for the device once more and costs ~0.2 ms: put off)
+        for (void* p : {(void*)lrow, (void*)loff, (void*)llen, (void*)lists, (void*)tags, (void*)rend, (void*)rdst,
+                        (void*)atoms, (void*)bad, (void*)pllen, (void*)ploff, (void*)pos_tmp, (void*)ltable})
+            if (p) {
+                if (ctx) ctx->deferred_free.push_back(p);
+                else (void)hipFree(p);
+            }
+    }
+};
+
+// What the steps of a build hand to each other. The host tables stay until the build's last synchronize: they are
+// uploaded from pageable memory.
+struct ArenaBuild {
+    storm_hip_ctx_t* ctx;
+    storm_hip_sparse_t* s;
+    ArenaBlocks in;
+    storm_hip_stage_t* stage;
+    const uint64_t* stage_token;
+    ArenaLaps laps;
+    ArenaRows rows;
+    ProbeLayout layout;
+    DevTemps dt;
+    std::vector<uint64_t> dev_off;          // per block: where its list lies behind lists_view (uint16 units), ~0: not sent
+    const uint16_t* lists_view = nullptr;   // where the kernels find the raw lists: dt.lists, or the stage's one chunk
+    std::vector<uint64_t> ploff, loff;
+    std::vector<uint32_t> pllen, run_end, tags;
+    uint32_t bad = 0;
+
+    int send_lists(Stager& stager);
+    int device_run_ends();
+    int fill_pool_rows(Stager& stager);
+    int expand_lists();
+    int lay_out_elements();
+};
+
+// The raw lists the device needs — of the probe columns (element layout) and of the list blocks that own a pool row
+// (expanded there) — go up FIRST, block after block: the device then finds where the octants' runs end inside every
+// list of a probe column, which is all the host's probe plan needs to know of them.
+int ArenaBuild::send_lists(Stager& stager) {
+    dev_off.assign(in.n_blocks + 1, ~0ull);
+    uint64_t n_list_elems = 0;
+    std::vector<uint8_t> wanted(in.n_blocks, 0);
+    for (uint64_t b : rows.probe_blocks) wanted[b] = 1;
+    for (uint64_t b : rows.list_blk) wanted[b] = 1;
+    // [r6] lists the caller staged while it built the container (storm_hip_stage_add_list: a token that is not ~0) are
+    // gathered from the stage's chunks by one kernel; the others travel now, through the pinned ring. Both kinds lie in
+    // dt.lists in block order: first the run from the host, behind it the staged ones.
+    std::vector<std::pair<const void*, size_t>> run;
+    std::vector<uint64_t> staged;   // blocks whose list is in the stage
+    const uint64_t list_space = stage ? stage->lbase + stage->lfill : 0;
+    for (uint64_t b = 0; b < in.n_blocks; ++b)
+        if (wanted[b] && in.block_n[b]) {
+            if (stage && stage_token && stage_token[b] != ~0ull) {
+                if ((stage_token[b] & 1u) || stage_token[b] + (uint64_t)in.block_n[b] * 2u > list_space) {
+                    set_error("sparse_create: block %llu carries a list token outside the stage", (unsigned long long)b);
+                    return STORM_HIP_EINVAL;
+                }
+                staged.push_back(b);
+                continue;
+            }
+            dev_off[b] = n_list_elems;
+            n_list_elems += in.block_n[b];
+            run.emplace_back(in.block_ptr[b], (size_t)in.block_n[b] * sizeof(uint16_t));
+        }
+    // ... unless EVERY wanted list is staged and the stage's lists fit one chunk (up to 32 M positions: every sparse
+    // load of c4): the builder then reads them where they lie — dev_off = the token, no table, no gather, no copy
+    if (run.empty() && !staged.empty() && list_space <= storm_hip_stage_s::kListChunk) {
+        if (int rc0 = stage_send_lists(ctx, stage)) return rc0;   // what is still in the ring
+        for (uint64_t b : staged) dev_off[b] = stage_token[b] / 2u;
+        lists_view = reinterpret_cast<const uint16_t*>(stage->lchunks[0]);
+        staged.clear();
+    }
+    std::vector<uint64_t> ltable;
+    ltable.reserve(3 * staged.size());
+    for (uint64_t b : staged) {
+        dev_off[b] = n_list_elems;
+        ltable.insert(ltable.end(), {n_list_elems, stage_token[b], (uint64_t)in.block_n[b]});
+        n_list_elems += in.block_n[b];
+    }
+    if (n_list_elems) {
+        if (hipMalloc(reinterpret_cast<void**>(&dt.lists), n_list_elems * sizeof(uint16_t)) != hipSuccess) {
+            set_error("sparse_create: hipMalloc of %llu bytes for the lists failed", (unsigned long long)(n_list_elems * sizeof(uint16_t)));
+            return STORM_HIP_ENOMEM;
+        }
+        if (int rc0 = stager.send_run(reinterpret_cast<uint8_t*>(dt.lists), run)) return rc0;
+    }
+    if (!staged.empty())
+        if (int rc0 = stage_gather_lists(ctx, stage, ltable, dt.lists, &dt.ltable)) return rc0;
+    if (!lists_view) lists_view = dt.lists;
+    return STORM_HIP_OK;
+}
+
+// run_end: per probe block and octant, where the octant's run ends inside the list (probe_run_end_kernel); waits for it.
+int ArenaBuild::device_run_ends() {
+    if (rows.probe_blocks.empty()) return STORM_HIP_OK;
+    ploff.reserve(rows.probe_blocks.size());
+    pllen.reserve(rows.probe_blocks.size());
+    for (uint64_t b : rows.probe_blocks) {
+        ploff.push_back(in.block_n[b] ? dev_off[b] : 0);
+        pllen.push_back(in.block_n[b]);
+    }
+    run_end.assign(rows.probe_blocks.size() * kProbeOctants, 0);
+    if (int rc0 = upload(ctx, &dt.ploff, ploff.data(), ploff.size())) return rc0;
+    if (int rc0 = upload(ctx, &dt.pllen, pllen.data(), pllen.size())) return rc0;
+    STORM_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dt.rend), run_end.size() * sizeof(uint32_t)));
+    const uint32_t n_threads = (uint32_t)run_end.size();
+    hipLaunchKernelGGL(probe_run_end_kernel, dim3((n_threads + kThreads - 1) / kThreads), dim3(kThreads), 0, ctx->stream,
+                       lists_view, dt.ploff, dt.pllen, (uint32_t)rows.probe_blocks.size(), dt.rend);
+    STORM_HIP_TRY(hipGetLastError());
+    STORM_HIP_TRY(hipMemcpyAsync(run_end.data(), dt.rend, run_end.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    laps.lap("run ends on the device");
+    return STORM_HIP_OK;
+}
+
+// The pool and its bitmap-kind blocks: straight into their pool rows — in pool-row order the blocks of a column are
+// consecutive rows, so a run of them is ONE contiguous destination (no staging copy on the device, no placement kernel;
+// the words may sit at any alignment on the host: a serialized stream)
+int ArenaBuild::fill_pool_rows(Stager& stager) {
+    // Pool rows are 8 KiB of bits; their PITCH gets a 512-byte chunk more (K2b fetches 64-byte pieces of 64
+    // consecutive rows: at a power-of-two pitch they fall into a handful of memory channels — the dense matrix's
+    // finding, pitch_pad_chunks; option k2_matrix_pad; K2b over the c4 pool 5.95 -> 5.82 ms).
+    // The pad words stay zero: the kernels that take the pitch for the row length multiply zeros there.
+    s->pitch = kBlockWords + pitch_pad_chunks(ctx->k2_matrix_pad, kBlockWords) * kChunkWords;
+    const size_t row_bytes = s->pitch * sizeof(uint64_t);
+    const size_t pool_bytes = (s->pool_rows_ready + 512) * row_bytes;
+    if (hipMalloc(reinterpret_cast<void**>(&s->d_pool), pool_bytes) != hipSuccess) {
+        set_error("sparse_create: hipMalloc of %zu bytes for the block pool failed", pool_bytes);
+        return STORM_HIP_ENOMEM;
+    }
+    if (hipMemsetAsync(s->d_pool, 0, pool_bytes, ctx->stream) != hipSuccess) return STORM_HIP_EHIP;
+    if (rows.dense_row.empty()) return STORM_HIP_OK;
+    // [r6] ... unless every one of them already lies on the device (the block stage filled while the rows were
+    // added): one kernel gathers the pool rows from the stage's chunks
+    bool all = stage && stage_token;
+    if (all)
+        for (uint64_t b : rows.dense_blk) all = all && stage_token[b] < stage->n_blocks;
+    if (all) {
+        if (int rc = stage_send(ctx, stage)) return rc;   // the blocks still in the ring
+        std::vector<uint64_t> table(2 * rows.dense_row.size());
+        for (size_t k = 0; k < rows.dense_row.size(); ++k) table[2 * k] = rows.dense_row[k], table[2 * k + 1] = stage_token[rows.dense_blk[k]];
+        uint64_t* d_table = nullptr;
+        if (stage->d_chunk_table) (void)hipFree(stage->d_chunk_table);
+        stage->d_chunk_table = nullptr;
+        if (hipMalloc(reinterpret_cast<void**>(&stage->d_chunk_table), stage->chunks.size() * sizeof(uint8_t*)) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&d_table), table.size() * sizeof(uint64_t)) != hipSuccess) {
+            set_error("sparse_create: hipMalloc of the gather table failed");
+            return STORM_HIP_ENOMEM;
+        }
+        if (hipMemcpyAsync(stage->d_chunk_table, stage->chunks.data(), stage->chunks.size() * sizeof(uint8_t*),
+                           hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+            upload_bytes(ctx, d_table, table.data(), table.size() * sizeof(uint64_t)) != STORM_HIP_OK) {
+            (void)hipFree(d_table);
+            return STORM_HIP_EHIP;
+        }
+        hipLaunchKernelGGL(gather_staged_kernel, dim3((uint32_t)rows.dense_row.size()), dim3(256), 0, ctx->stream,
+                           stage->d_chunk_table, d_table, s->d_pool, (uint64_t)s->pitch);
+        const bool ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;   // `table` is pageable
+        (void)hipFree(d_table);
+        return ok ? STORM_HIP_OK : STORM_HIP_EHIP;
+    }
+    std::vector<uint32_t> order(rows.dense_row.size());
+    for (uint32_t i = 0; i < order.size(); ++i) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return rows.dense_row[x] < rows.dense_row[y]; });
+    std::vector<const void*> run;
+    for (size_t i = 0; i < order.size();) {
+        const uint32_t row0 = rows.dense_row[order[i]];
+        run.clear();
+        size_t j = i;
+        while (j < order.size() && rows.dense_row[order[j]] == row0 + (j - i)) {
+            run.push_back(in.block_ptr[rows.dense_blk[order[j]]]);
+            ++j;
+        }
+        if (int rc = stager.send_rows(reinterpret_cast<uint8_t*>(s->d_pool) + (size_t)row0 * row_bytes, run,
+                                      (size_t)kBlockWords * sizeof(uint64_t), row_bytes))
+            return rc;
+        i = j;
+    }
+    return STORM_HIP_OK;
+}
+
+// list-kind blocks that own a pool row (mixed columns, columns the probe kernel cannot take): expanded there
+int ArenaBuild::expand_lists() {
+    if (rows.list_row.empty()) return STORM_HIP_OK;
+    loff.reserve(rows.list_blk.size());
+    for (uint64_t b : rows.list_blk) loff.push_back(dev_off[b]);
+    if (int rc = upload(ctx, &dt.lrow, rows.list_row.data(), rows.list_row.size())) return rc;
+    if (int rc = upload(ctx, &dt.loff, loff.data(), loff.size())) return rc;
+    if (int rc = upload(ctx, &dt.llen, rows.list_len.data(), rows.list_len.size())) return rc;
+    hipLaunchKernelGGL(expand_lists_kernel, dim3((uint32_t)rows.list_row.size()), dim3(kThreads), 0, ctx->stream, s->d_pool,
+                       s->pitch, dt.lrow, dt.loff, dt.llen, lists_view);
+    return hipGetLastError() == hipSuccess ? STORM_HIP_OK : STORM_HIP_EHIP;
+}
+
+// probe columns: element layout on the device (bad arrives with the build's last synchronize)
+int ArenaBuild::lay_out_elements() {
+    if (!layout.n_probe_elems) return STORM_HIP_OK;
+    if (hipMalloc(reinterpret_cast<void**>(&s->d_probe_elems), layout.n_probe_elems * sizeof(uint32_t)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&s->d_probe_pos16), layout.n_probe_elems * sizeof(uint16_t)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&dt.pos_tmp), layout.n_probe_elems * sizeof(uint16_t)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&dt.bad), sizeof(uint32_t)) != hipSuccess) {
+        set_error("sparse_create: hipMalloc of the probe element arrays (%zu elements) failed", layout.n_probe_elems);
+        return STORM_HIP_ENOMEM;
+    }
+    // (the alignment gaps behind every octant read as zero)
+    if (hipMemsetAsync(s->d_probe_elems, 0, layout.n_probe_elems * sizeof(uint32_t), ctx->stream) != hipSuccess ||
+        hipMemsetAsync(s->d_probe_pos16, 0, layout.n_probe_elems * sizeof(uint16_t), ctx->stream) != hipSuccess ||
+        hipMemsetAsync(dt.bad, 0, sizeof(uint32_t), ctx->stream) != hipSuccess)
+        return STORM_HIP_EHIP;
+    tags.reserve(rows.probe_blocks.size());
+    for (size_t pb = 0; pb < rows.probe_blocks.size(); ++pb) tags.push_back(layout.block_local[pb] << 16);
+    // (the lists' offsets, their lengths and the run ends are on the device since the start)
+    if (int rc = upload(ctx, &dt.tags, tags.data(), tags.size())) return rc;
+    if (int rc = upload(ctx, &dt.rdst, layout.run_dst.data(), layout.run_dst.size())) return rc;
+    if (int rc = upload(ctx, &dt.atoms, layout.atoms.data(), layout.atoms.size())) return rc;
+    if (rows.probe_blocks.size())
+        hipLaunchKernelGGL(probe_fill_kernel, dim3((uint32_t)rows.probe_blocks.size()), dim3(kThreads), 0, ctx->stream,
+                           lists_view, dt.ploff, dt.pllen, dt.tags, dt.rend, dt.rdst, s->d_probe_elems, dt.pos_tmp, dt.bad);
+    if (!layout.atoms.empty())
+        hipLaunchKernelGGL(probe_deal_kernel, dim3((uint32_t)(layout.atoms.size() / 2)), dim3(kThreads), 0, ctx->stream,
+                           dt.atoms, dt.pos_tmp, s->d_probe_pos16);
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&bad, dt.bad, sizeof(bad), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+        return STORM_HIP_EHIP;
+    return STORM_HIP_OK;
+}
+
+// `stage`, `stage_token`: blocks the caller staged on the device while it built the container (storm_hip_stage_add*).
 static int build_arena(storm_hip_ctx_t* ctx, uint64_t n_rows, uint64_t n_blocks,
                        const uint64_t* row_block_offset, const uint32_t* block_id,
                        const uint8_t* block_kind, const uint32_t* block_n,
@@ -844,673 +1040,49 @@ static int build_arena(storm_hip_ctx_t* ctx, uint64_t n_rows, uint64_t n_blocks,
         return STORM_HIP_EINVAL;
     }
     *out = nullptr;
-    if (n_blocks > 0 && (!row_block_offset || !block_id || !block_kind || !block_ptr || !block_n)) {
-        set_error("sparse_create: NULL descriptor array");
-        return STORM_HIP_EINVAL;
-    }
-    if (n_blocks >= (1ull << 32) - kABlockRows) {
-        set_error("sparse_create: too many blocks");
-        return STORM_HIP_EINVAL;
-    }
-    auto T0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (getenv("STORM_HIP_TIMING")) {
-            auto t = std::chrono::steady_clock::now();
-            fprintf(stderr, "[build_arena] %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(t - T0).count());
-            T0 = t;
-        }
-    };
-    // ---- validate + count blocks per column ----
-    if (n_blocks > 0 && n_rows == 0) {
-        set_error("sparse_create: %llu blocks but no rows", (unsigned long long)n_blocks);
-        return STORM_HIP_EINVAL;
-    }
-    if (n_rows > 0 && (!row_block_offset || row_block_offset[0] != 0 ||
-                       row_block_offset[n_rows] != n_blocks)) {
-        set_error("sparse_create: row_block_offset must run from 0 to n_blocks = %llu",
-                  (unsigned long long)n_blocks);
-        return STORM_HIP_EINVAL;
-    }
-    uint32_t max_id = 0;
-    for (uint64_t r = 0; r < n_rows; ++r) {
-        if (row_block_offset[r] > row_block_offset[r + 1] ||
-            row_block_offset[r + 1] > n_blocks) {
-            set_error("sparse_create: row_block_offset is not a CSR over %llu blocks",
-                      (unsigned long long)n_blocks);
-            return STORM_HIP_EINVAL;
-        }
-        for (uint64_t b = row_block_offset[r]; b < row_block_offset[r + 1]; ++b) {
-            if (b > row_block_offset[r] && block_id[b] <= block_id[b - 1]) {
-                set_error("sparse_create: block ids of row %llu are not ascending",
-                          (unsigned long long)r);
-                return STORM_HIP_EINVAL;
-            }
-            if (block_id[b] >= kMaxBlockId) {  // positions are uint32: ids stop at 2^32 / 65536
-                set_error("sparse_create: block id %u out of range", block_id[b]);
-                return STORM_HIP_EINVAL;
-            }
-            if (block_kind[b] > 1) {
-                set_error("sparse_create: block kind %u", block_kind[b]);
-                return STORM_HIP_EINVAL;
-            }
-            if (block_kind[b] == 0 ? (block_n[b] > 65536u || (block_n[b] && (!block_ptr[b] || ((uintptr_t)block_ptr[b] & 1))))
-                                   : !block_ptr[b]) {
-                set_error("sparse_create: block %llu has no data (or a list that is too long or not 2-byte aligned)",
-                          (unsigned long long)b);
-                return STORM_HIP_EINVAL;
-            }
-            max_id = std::max(max_id, block_id[b]);
-        }
-    }
-    std::vector<uint64_t> per_col((size_t)max_id + 2, 0), n_list_col((size_t)max_id + 2, 0);
-    for (uint64_t b = 0; b < n_blocks; ++b) {
-        per_col[block_id[b]]++;
-        if (block_kind[b] == 0) n_list_col[block_id[b]]++;
-    }
+    std::unique_ptr<storm_hip_sparse_t> fresh(new (std::nothrow) storm_hip_sparse_t());   // (host memory only so far)
+    storm_hip_sparse_t* s = fresh.get();
+    if (!s) return STORM_HIP_ENOMEM;
+    ArenaBuild a{ctx, s, {n_rows, n_blocks, row_block_offset, block_id, block_kind, block_n, block_ptr}, stage, stage_token};
+    // 1. the columns: validation, layout, the pool row of every block (host only: storm_hip_plan.cpp)
+    if (int rc0 = plan_arena_columns(a.in, s, &a.rows, a.laps)) return rc0;
     // owned here until it is handed to the caller: a std::vector below may throw (guarded() turns that into
     // ENOMEM) and every early return must release the arena and its device buffers
     struct ArenaDeleter {
         storm_hip_ctx_t* ctx;
         void operator()(storm_hip_sparse_t* a) const { storm_hip_sparse_destroy(ctx, a); }
     };
-    std::unique_ptr<storm_hip_sparse_t, ArenaDeleter> owner(new (std::nothrow) storm_hip_sparse_t(), ArenaDeleter{ctx});
-    storm_hip_sparse_t* s = owner.get();
-    if (!s) return STORM_HIP_ENOMEM;
-    // Which columns the list-probe kernel (K4) can take: all blocks lists, 2 .. 65535 rows, element offsets
-    // within 32 bits (8 octants x up to 7 elements of alignment each). Their pool rows come LAST in the
-    // layout and are not materialised at all unless a dense pass over them is asked for (sparse_probe = 0,
-    // the popcount variants): a column of short lists costs its listed positions, not 8 KiB per block.
-    std::vector<uint64_t> col_elems((size_t)max_id + 2, 0);
-    for (uint64_t b = 0; b < n_blocks; ++b)
-        if (block_kind[b] == 0) col_elems[block_id[b]] += block_n[b];
-    std::vector<uint8_t> probe_c((size_t)max_id + 2, 0);
-    {
-        uint64_t total = 0;
-        for (uint32_t c = 0; c <= max_id; ++c) {
-            const uint64_t n_l = n_list_col[c];
-            if (n_l >= 2 && n_l <= 65535 && col_elems[c] > 0 && total + col_elems[c] + 64 < (1ull << 32) - (1u << 20)) {  // (the probe kernel's element indices run up to 12 x 8192 past an item's end)
-                probe_c[c] = 1;
-                total += col_elems[c] + 64;
-            }
-        }
-    }
-    // Layout of a column: its bitmap blocks, then — on the next multiple of 512 rows — its list blocks (the kind
-    // dispatch of storm.c:618-656, once per block: list x list pairs go to the probe kernel, every pair with a
-    // bitmap block to the matrix cores, which then need the bitmap rows alone as A rows). Columns made of lists
-    // only come last: they need no pool rows at all.
-    std::vector<uint64_t> start((size_t)max_id + 2, 0), list0((size_t)max_id + 2, 0), col_end((size_t)max_id + 2, 0);
-    uint64_t run = 0;
-    for (int pass = 0; pass < 2; ++pass) {
-        for (uint32_t c = 0; c <= max_id; ++c) {
-            const bool lists_only = probe_c[c] && n_list_col[c] == per_col[c];
-            if (per_col[c] && (int)lists_only == pass) {
-                const uint64_t n_b = per_col[c] - n_list_col[c];
-                start[c] = run;
-                list0[c] = n_b && n_list_col[c] ? (run + n_b + 511) / 512 * 512 : run + n_b;
-                col_end[c] = list0[c] + n_list_col[c];
-                run = (col_end[c] + 511) / 512 * 512;  // next column starts on a 512-row A tile
-            }
-        }
-        if (pass == 0) s->pool_rows_ready = run;
-    }
-    for (uint32_t c = 0; c <= max_id; ++c)
-        if (per_col[c]) {
-            s->cols.push_back({start[c], col_end[c]});
-            s->col_list0.push_back(list0[c]);
-            const uint64_t nl = n_list_col[c], nb = per_col[c] - nl;
-            s->census[0] += nl * (nl - (nl != 0)) / 2;
-            s->census[1] += nl * nb;
-            s->census[2] += nb * (nb - (nb != 0)) / 2;
-            s->census[3] += 1;
-        }
-    s->n_pool_rows = run;
-    if (s->n_pool_rows >= (1ull << 32) - 512) {
-        set_error("sparse_create: block pool too large");
-        return STORM_HIP_EINVAL;
-    }
-
-    lap("validate");
-    // ---- pool row of every block (rows are visited in order => row order inside a column)
-    std::vector<uint32_t> list_row, dense_row, list_len;
-    std::vector<uint64_t> list_blk, dense_blk;   // the blocks behind those rows
-    {
-        std::vector<uint64_t> next_bitmap(start), next_list(list0);
-        for (uint64_t b = 0; b < n_blocks; ++b) {
-            const uint32_t pr = (uint32_t)(block_kind[b] == 0 ? next_list[block_id[b]]++ : next_bitmap[block_id[b]]++);
-            if (block_kind[b] == 0) {
-                if (block_n[b] && pr < s->pool_rows_ready) {
-                    list_row.push_back(pr);
-                    list_blk.push_back(b);
-                    list_len.push_back(block_n[b]);
-                }
-            } else {
-                dense_row.push_back(pr);
-                dense_blk.push_back(b);
-            }
-        }
-    }
-
-    lap("pool rows");
-    // ---- probe data (K4): columns whose blocks are all lists and that have at most 65535 rows. Per column
-    //      and octant (8192 positions of the block) the listed positions in row order.
-    // The host only decides WHERE every run of a list goes (a walk over the block records); the elements are laid
-    // out by the device from the raw lists (probe_fill_kernel, probe_deal_kernel).
-    size_t n_probe_elems = 0;
-    constexpr uint32_t kNoBlock = 0xffffffffu;
-    std::vector<uint64_t> probe_blocks;  // the list blocks of probe columns, in row order
-    std::vector<uint32_t> run_end;       // per probe block and octant: end of the octant's run inside the list
-    std::vector<uint32_t> run_dst;       // ... and where the run starts in the element arrays
-    std::vector<uint32_t> block_local;   // the block's row inside its column's list rows
-    std::vector<uint32_t> atoms;         // {first element, end} of every atom of the far stream
-    // device temporaries of the build: released on every way out
-    struct DevTemps {
-        uint32_t *lrow = nullptr, *llen = nullptr, *tags = nullptr, *rend = nullptr, *rdst = nullptr;
-        uint32_t *atoms = nullptr, *bad = nullptr, *pllen = nullptr;
-        uint64_t *loff = nullptr, *ploff = nullptr;
-        uint16_t *lists = nullptr, *pos_tmp = nullptr;
-        uint64_t* ltable = nullptr;
-        storm_hip_ctx_t* ctx = nullptr;
-        ~DevTemps() {
-            // (the build has waited for its last kernel; a hipFree waits for the device once more and costs ~0.2 ms: put off)
-            for (void* p : {(void*)lrow, (void*)loff, (void*)llen, (void*)lists, (void*)tags, (void*)rend, (void*)rdst,
-                            (void*)atoms, (void*)bad, (void*)pllen, (void*)ploff, (void*)pos_tmp, (void*)ltable})
-                if (p) {
-                    if (ctx) ctx->deferred_free.push_back(p);
-                    else (void)hipFree(p);
-                }
-        }
-    } dt;
-    dt.ctx = ctx;
+    std::unique_ptr<storm_hip_sparse_t, ArenaDeleter> owner(fresh.release(), ArenaDeleter{ctx});
+    a.laps.lap("pool rows");
+    a.dt.ctx = ctx;
     drain_deferred(ctx, false);   // (whatever an earlier build left behind)
     STORM_HIP_TRY(hipSetDevice(ctx->device));
     Stager stager(ctx);
     if (int rc0 = stager.init()) return rc0;
-    // ---- the raw lists the device needs — of the probe columns (element layout) and of the list blocks that own a
-    //      pool row (expanded there) — go up FIRST, block after block: the device then finds where the octants' runs
-    //      end inside every list of a probe column, which is all the host's layout below needs to know of them
-    for (uint64_t b = 0; b < n_blocks; ++b)
-        if (block_kind[b] == 0 && probe_c[block_id[b]]) probe_blocks.push_back(b);
-    std::vector<uint64_t> dev_off(n_blocks + 1, ~0ull);
-    uint64_t n_list_elems = 0;
-    const uint16_t* lists_view = nullptr;   // where the kernels below find the raw lists: dt.lists, or the stage's one chunk
-    {
-        std::vector<uint8_t> wanted(n_blocks, 0);
-        for (uint64_t b : probe_blocks) wanted[b] = 1;
-        for (uint64_t b : list_blk) wanted[b] = 1;
-        // [r6] lists the caller staged while it built the container (storm_hip_stage_add_list: a token that is not ~0) are
-        // gathered from the stage's chunks by one kernel; the others travel now, through the pinned ring. Both kinds lie in
-        // dt.lists in block order: first the run from the host, behind it the staged ones.
-        std::vector<std::pair<const void*, size_t>> run;
-        std::vector<uint64_t> staged;   // blocks whose list is in the stage
-        const uint64_t list_space = stage ? stage->lbase + stage->lfill : 0;
-        for (uint64_t b = 0; b < n_blocks; ++b)
-            if (wanted[b] && block_n[b]) {
-                if (stage && stage_token && stage_token[b] != ~0ull) {
-                    if ((stage_token[b] & 1u) || stage_token[b] + (uint64_t)block_n[b] * 2u > list_space) {
-                        set_error("sparse_create: block %llu carries a list token outside the stage", (unsigned long long)b);
-                        return STORM_HIP_EINVAL;
-                    }
-                    staged.push_back(b);
-                    continue;
-                }
-                dev_off[b] = n_list_elems;
-                n_list_elems += block_n[b];
-                run.emplace_back(block_ptr[b], (size_t)block_n[b] * sizeof(uint16_t));
-            }
-        // ... unless EVERY wanted list is staged and the stage's lists fit one chunk (up to 32 M positions: every sparse
-        // load of c4): the builder then reads them where they lie — dev_off = the token, no table, no gather, no copy
-        if (run.empty() && !staged.empty() && list_space <= storm_hip_stage_s::kListChunk) {
-            if (int rc0 = stage_send_lists(ctx, stage)) return rc0;   // what is still in the ring
-            for (uint64_t b : staged) dev_off[b] = stage_token[b] / 2u;
-            lists_view = reinterpret_cast<const uint16_t*>(stage->lchunks[0]);
-            staged.clear();
-        }
-        std::vector<uint64_t> ltable;
-        ltable.reserve(3 * staged.size());
-        for (uint64_t b : staged) {
-            dev_off[b] = n_list_elems;
-            ltable.insert(ltable.end(), {n_list_elems, stage_token[b], (uint64_t)block_n[b]});
-            n_list_elems += block_n[b];
-        }
-        if (n_list_elems) {
-            if (hipMalloc(reinterpret_cast<void**>(&dt.lists), n_list_elems * sizeof(uint16_t)) != hipSuccess) {
-                set_error("sparse_create: hipMalloc of %llu bytes for the lists failed",
-                          (unsigned long long)(n_list_elems * sizeof(uint16_t)));
-                return STORM_HIP_ENOMEM;
-            }
-            if (int rc0 = stager.send_run(reinterpret_cast<uint8_t*>(dt.lists), run)) return rc0;
-        }
-        if (!staged.empty())
-            if (int rc0 = stage_gather_lists(ctx, stage, ltable, dt.lists, &dt.ltable)) return rc0;
-        if (!lists_view) lists_view = dt.lists;
+    // 2. the raw lists, 3. where the octants' runs end in them
+    if (int rc0 = a.send_lists(stager)) return rc0;
+    a.laps.lap("lists -> device");
+    if (int rc0 = a.device_run_ends()) return rc0;
+    // 4. K4's element layout and work lists (host only). The host only decides WHERE every run of a list goes (a walk
+    //    over the block records); the elements are laid out by the device from the raw lists
+    if (int rc0 = plan_arena_probe(a.in, *s, a.rows, a.run_end, s, &a.layout, a.laps)) return rc0;
+    a.laps.lap("items");
+    // 5. - 7. device side: pool rows, the lists expanded into theirs, element layout by kernels
+    int rc = a.fill_pool_rows(stager);
+    if (rc == STORM_HIP_OK) {
+        a.laps.lap("bitmaps -> pool rows");
+        rc = a.expand_lists();
     }
-    lap("lists -> device");
-    std::vector<uint64_t> ploff;
-    std::vector<uint32_t> pllen;
-    if (!probe_blocks.empty()) {
-        ploff.reserve(probe_blocks.size());
-        pllen.reserve(probe_blocks.size());
-        for (uint64_t b : probe_blocks) {
-            ploff.push_back(block_n[b] ? dev_off[b] : 0);
-            pllen.push_back(block_n[b]);
-        }
-        run_end.assign(probe_blocks.size() * kProbeOctants, 0);
-        if (int rc0 = upload(ctx, &dt.ploff, ploff.data(), ploff.size())) return rc0;
-        if (int rc0 = upload(ctx, &dt.pllen, pllen.data(), pllen.size())) return rc0;
-        STORM_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dt.rend), run_end.size() * sizeof(uint32_t)));
-        const uint32_t n_threads = (uint32_t)run_end.size();
-        hipLaunchKernelGGL(probe_run_end_kernel, dim3((n_threads + kThreads - 1) / kThreads), dim3(kThreads), 0, ctx->stream,
-                           lists_view, dt.ploff, dt.pllen, (uint32_t)probe_blocks.size(), dt.rend);
-        STORM_HIP_TRY(hipGetLastError());
-        STORM_HIP_TRY(hipMemcpyAsync(run_end.data(), dt.rend, run_end.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        // a list that is not ascending may give ends that run backwards: refused here, before they are laid out
-        // (ascending ends that disagree with the values are caught by probe_fill_kernel)
-        for (size_t pb = 0; pb < probe_blocks.size(); ++pb) {
-            uint32_t from = 0;
-            for (uint32_t o = 0; o < kProbeOctants; ++o) {
-                const uint32_t end = run_end[pb * kProbeOctants + o];
-                if (end < from || end > pllen[pb]) {
-                    set_error("sparse_create: a list block is not strictly ascending");
-                    return STORM_HIP_EINVAL;
-                }
-                from = end;
-            }
-        }
-        lap("run ends on the device");
-    }
-    {
-        std::vector<int64_t> col_entry((size_t)max_id + 2, -1);  // column id -> index into s->cols
-        s->col_probe.assign(s->cols.size(), 0);
-        s->col_avg_len.assign(s->cols.size(), 0);
-        uint64_t total = 0;
-        size_t entry = 0;
-        for (uint32_t c = 0; c <= max_id; ++c) {
-            if (!per_col[c]) continue;
-            col_entry[c] = (int64_t)entry;
-            if (probe_c[c]) {
-                s->col_probe[entry] = 1;
-                s->col_avg_len[entry] = (uint32_t)(col_elems[c] / n_list_col[c]);
-                total += col_elems[c] + 64;
-            }
-            ++entry;
-        }
-        if (total > 0) {
-            // count per (probe column, octant), then lay the octants out one after the other, each on a
-            // 16-byte boundary of the uint16 position array
-            const size_t n_e = s->cols.size();
-            std::vector<uint64_t> oct_count(n_e * kProbeOctants, 0), oct_base(n_e * kProbeOctants, 0);
-            run_dst.assign(probe_blocks.size() * kProbeOctants, 0);
-            block_local.assign(probe_blocks.size(), kNoBlock);
-            for (size_t pb = 0; pb < probe_blocks.size(); ++pb) {
-                const size_t e = (size_t)col_entry[block_id[probe_blocks[pb]]];
-                uint32_t from = 0;
-                for (uint32_t o = 0; o < kProbeOctants; ++o) {
-                    oct_count[e * kProbeOctants + o] += run_end[pb * kProbeOctants + o] - from;
-                    from = run_end[pb * kProbeOctants + o];
-                }
-            }
-            uint64_t at = 0;
-            for (size_t i = 0; i < oct_count.size(); ++i) {
-                at = (at + 7) & ~7ull;
-                oct_base[i] = at;
-                at += oct_count[i];
-            }
-            n_probe_elems = (size_t)at + 8;
-            for (size_t i = 0; i < oct_count.size(); ++i)
-                if (oct_count[i])
-                    s->probe_regions.push_back({(uint32_t)oct_base[i], (uint32_t)(oct_base[i] + oct_count[i]),
-                                                (uint32_t)s->col_list0[i / kProbeOctants], (uint32_t)(i % kProbeOctants)});
-            // rows are visited in order: element offset of every row, per octant
-            std::vector<uint64_t> cursor(oct_base);
-            std::vector<uint64_t> next((size_t)max_id + 2, 0);  // list blocks of the column seen so far
-            std::vector<std::vector<uint32_t>> row_start(n_e * kProbeOctants);
-            for (size_t e = 0; e < n_e; ++e)
-                if (s->col_probe[e])
-                    for (uint32_t o = 0; o < kProbeOctants; ++o)
-                        row_start[e * kProbeOctants + o].reserve((size_t)(s->cols[e].r1 - s->col_list0[e]) + 1);
-            {
-                size_t pb = 0;
-                for (uint64_t b = 0; b < n_blocks; ++b) {
-                    if (block_kind[b] != 0) continue;
-                    const uint32_t c = block_id[b];
-                    const uint64_t local = next[c]++;
-                    const int64_t e = col_entry[c];
-                    if (e < 0 || !s->col_probe[(size_t)e]) continue;
-                    block_local[pb] = (uint32_t)local;
-                    uint32_t from = 0;
-                    for (uint32_t o = 0; o < kProbeOctants; ++o) {
-                        const size_t i = (size_t)e * kProbeOctants + o;
-                        row_start[i].push_back((uint32_t)cursor[i]);
-                        run_dst[pb * kProbeOctants + o] = (uint32_t)cursor[i];
-                        cursor[i] += run_end[pb * kProbeOctants + o] - from;
-                        from = run_end[pb * kProbeOctants + o];
-                    }
-                    ++pb;
-                }
-            }
-            lap("layout (prefix sums, row starts)");
-            // atoms of the far stream (the elements of one group of kProbeRows rows in one octant): the device deals
-            // the positions of every atom by LDS bank (probe_deal_kernel; why: see there)
-            for (size_t i = 0; i < row_start.size(); ++i) {
-                const std::vector<uint32_t>& rs = row_start[i];
-                const uint32_t end = (uint32_t)(oct_base[i] + oct_count[i]);
-                for (size_t k = 0; k < rs.size(); k += kProbeRows) {
-                    atoms.push_back(rs[k]);
-                    atoms.push_back(k + kProbeRows < rs.size() ? rs[k + kProbeRows] : end);
-                }
-            }
-            // far work of all groups -> positions per item: about 4096 items over all probe columns, between
-            // 2^15 and 2^21 positions each (an item zeroes and scatters its 128 KiB table first)
-            uint64_t far_work = 0;
-            for (size_t i = 0; i < row_start.size(); ++i) {
-                const std::vector<uint32_t>& rs = row_start[i];
-                if (rs.empty()) continue;
-                const uint32_t n_c = (uint32_t)rs.size();
-                const uint64_t end = oct_base[i] + oct_count[i];
-                for (uint32_t a0 = 0; a0 < n_c; a0 += kProbeRows) {
-                    const uint32_t a1 = std::min(a0 + kProbeRows, n_c);
-                    far_work += end - (a1 < n_c ? rs[a1] : end);
-                }
-            }
-            // Chunks of the far stream are the SAME for every group of a (column, octant) stream: a fixed grid of runs
-            // of atoms, ~far_work / 2048 positions each and at most 2^23. A group needs the rest of the chunk its own
-            // atom lies in and every later chunk. The items that read one chunk are a FAMILY; a family goes to one XCD,
-            // its items one after the other, so that the XCD's 32 CUs work through the same positions at the same time
-            // and HBM delivers them once (the kernel fetched 16 GB per launch at c4's 20971 draws — every group
-            // streaming its own 4 MiB chunks through an L2 that hit 9 % of the time — and ran at the HBM rate with the
-            // LDS half idle). Every item pays for its group's histogram, so fewer, longer items win as long as the
-            // 512 workgroup slots stay filled: / 4096 and 2^21 until round 4; / 2048 is 8 - 18 % faster at every c4
-            // load and 2^23 another 7 % at 30000 draws (profiles/r04_h_sparse_probe.txt).
-            const uint64_t kProbeChunk =
-                std::min<uint64_t>(1u << 23, std::max<uint64_t>(1u << 15, far_work / 2048)) & ~7ull;
-            struct Family {
-                uint64_t work = 0;
-                std::vector<storm_hip_sparse_s::ProbeItemHost> items;
-            };
-            std::vector<Family> families;
-            for (size_t i = 0; i < row_start.size(); ++i) {
-                std::vector<uint32_t>& rs = row_start[i];
-                if (rs.empty()) continue;
-                const uint32_t n_c = (uint32_t)rs.size();
-                rs.push_back((uint32_t)(oct_base[i] + oct_count[i]));  // end of the octant
-                const uint32_t e = (uint32_t)(i / kProbeOctants);
-                // atoms t = 0 .. n_atoms - 1: rows [128 t, 128 t + 128); chunk grid over atoms 1 .. (atom 0 is nobody's far part)
-                const uint32_t n_atoms = (n_c + kProbeRows - 1) / kProbeRows;
-                auto atom_start = [&](uint32_t t) { return rs[std::min(t * (uint32_t)kProbeRows, n_c)]; };
-                std::vector<uint32_t> chunk_first;  // first atom of every chunk, + n_atoms
-                for (uint32_t t = 1; t < n_atoms;) {
-                    chunk_first.push_back(t);
-                    const uint64_t from = atom_start(t);
-                    ++t;
-                    while (t < n_atoms && atom_start(t) - from < kProbeChunk) ++t;
-                }
-                chunk_first.push_back(n_atoms);
-                const size_t fam0 = families.size();
-                families.resize(fam0 + chunk_first.size());  // one per chunk (+ one for groups without a far part)
-                for (uint32_t g = 0; g < n_atoms; ++g) {
-                    const uint32_t a0 = g * kProbeRows, a1 = std::min(a0 + (uint32_t)kProbeRows, n_c);
-                    if (rs[a1] == rs[a0]) continue;  // no listed position of the A rows in this octant
-                    // first item of the group: its own rows among themselves (n range set) + the rest of the chunk the
-                    // next atom lies in; one item per later chunk
-                    if (g + 1 >= n_atoms) {  // the last group has nobody behind it
-                        families[fam0 + chunk_first.size() - 1].items.push_back({rs[a0], rs[a1], rs[a0], rs[a1], rs[a1], rs[a1], a0, e});
-                        families[fam0 + chunk_first.size() - 1].work += 8192;
-                        continue;
-                    }
-                    size_t c = 0;
-                    while (c + 1 < chunk_first.size() && chunk_first[c + 1] <= g + 1) ++c;
-                    bool first = true;
-                    for (; c + 1 < chunk_first.size(); ++c) {
-                        const uint32_t b0 = first ? rs[a1] : atom_start(chunk_first[c]);
-                        const uint32_t b1 = atom_start(chunk_first[c + 1]);
-                        const uint32_t n0 = first ? rs[a0] : 0u, n1 = first ? rs[a1] : 0u;
-                        if (n1 > n0 || b1 > b0) {
-                            families[fam0 + c].items.push_back({rs[a0], rs[a1], n0, n1, std::min(b0, b1), b1, a0, e});
-                            families[fam0 + c].work += (uint64_t)(b1 - std::min(b0, b1)) + 8192;
-                        }
-                        first = false;
-                    }
-                }
-            }
-            // families to XCDs: heaviest first onto the lightest queue; block b of the launch runs on XCD b % 8
-            // (observed; speed only), so the launch order takes one item of every queue in turn
-            std::vector<size_t> order(families.size());
-            for (size_t f = 0; f < order.size(); ++f) order[f] = f;
-            std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return families[x].work > families[y].work; });
-            std::vector<std::vector<storm_hip_sparse_s::ProbeItemHost>> queue(8);
-            uint64_t load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            for (size_t f : order) {
-                if (families[f].items.empty()) continue;
-                int q = 0;
-                for (int x = 1; x < 8; ++x)
-                    if (load[x] < load[q]) q = x;
-                queue[q].insert(queue[q].end(), families[f].items.begin(), families[f].items.end());
-                load[q] += families[f].work;
-            }
-            size_t longest = 0;
-            for (int x = 0; x < 8; ++x) longest = std::max(longest, queue[x].size());
-            for (size_t pos = 0; pos < longest; ++pos)
-                for (int x = 0; x < 8; ++x)
-                    if (pos < queue[x].size()) s->probe_items.push_back(queue[x][pos]);
-            // [r6] the same work in bundles of kFatGroups groups (probe_lists_fat_kernel): the same chunk grid (a bundle
-            // needs the rest of the chunk its successor atom lies in and every later chunk), the same families and queues
-            {
-                struct FatFamily {
-                    uint64_t work = 0;
-                    std::vector<storm_hip_sparse_s::ProbeFatItemHost> items;
-                };
-                std::vector<FatFamily> fat;
-                for (size_t i = 0; i < row_start.size(); ++i) {
-                    const std::vector<uint32_t>& rs = row_start[i];   // (ends with the end of the octant since the loop above)
-                    if (rs.size() < 2) continue;
-                    const uint32_t n_c = (uint32_t)rs.size() - 1u;
-                    const uint32_t e = (uint32_t)(i / kProbeOctants);
-                    const uint32_t n_atoms = (n_c + kProbeRows - 1) / kProbeRows;
-                    auto atom_start = [&](uint32_t t) { return rs[std::min(t * (uint32_t)kProbeRows, n_c)]; };
-                    std::vector<uint32_t> chunk_first;
-                    for (uint32_t t = 1; t < n_atoms;) {
-                        chunk_first.push_back(t);
-                        const uint64_t from = atom_start(t);
-                        ++t;
-                        while (t < n_atoms && atom_start(t) - from < kProbeChunk) ++t;
-                    }
-                    chunk_first.push_back(n_atoms);
-                    const size_t fam0 = fat.size();
-                    fat.resize(fam0 + chunk_first.size());
-                    for (uint32_t g0 = 0; g0 < n_atoms; g0 += kFatGroups) {
-                        const uint32_t g1 = std::min(g0 + kFatGroups, n_atoms);
-                        storm_hip_sparse_s::ProbeFatItemHost it{};
-                        for (uint32_t k = 0; k <= kFatGroups; ++k) it.at[k] = atom_start(std::min(g0 + k, g1));
-                        it.col = e;
-                        const uint32_t own = it.at[kFatGroups] - it.at[0];
-                        if (own == 0) continue;   // no listed position of the bundle's rows in this octant
-                        if (g1 >= n_atoms) {      // the last bundle has nobody behind it
-                            it.b_begin = it.b_end = it.at[kFatGroups];
-                            it.first = 1;
-                            fat[fam0 + chunk_first.size() - 1].items.push_back(it);
-                            fat[fam0 + chunk_first.size() - 1].work += 8192u * (g1 - g0);
-                            continue;
-                        }
-                        size_t c = 0;
-                        while (c + 1 < chunk_first.size() && chunk_first[c + 1] <= g1) ++c;
-                        bool first = true;
-                        for (; c + 1 < chunk_first.size(); ++c) {
-                            const uint32_t b1 = atom_start(chunk_first[c + 1]);
-                            const uint32_t b0 = std::min(first ? it.at[kFatGroups] : atom_start(chunk_first[c]), b1);
-                            if (first || b1 > b0) {
-                                it.b_begin = b0;
-                                it.b_end = b1;
-                                it.first = first ? 1u : 0u;
-                                fat[fam0 + c].items.push_back(it);
-                                fat[fam0 + c].work += (uint64_t)(b1 - b0) * (g1 - g0) + 8192u * (g1 - g0);
-                            }
-                            first = false;
-                        }
-                    }
-                }
-                std::vector<size_t> forder(fat.size());
-                for (size_t f = 0; f < forder.size(); ++f) forder[f] = f;
-                std::stable_sort(forder.begin(), forder.end(), [&](size_t x, size_t y) { return fat[x].work > fat[y].work; });
-                std::vector<std::vector<storm_hip_sparse_s::ProbeFatItemHost>> fqueue(8);
-                uint64_t fload[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                for (size_t f : forder) {
-                    if (fat[f].items.empty()) continue;
-                    int q = 0;
-                    for (int x = 1; x < 8; ++x)
-                        if (fload[x] < fload[q]) q = x;
-                    fqueue[q].insert(fqueue[q].end(), fat[f].items.begin(), fat[f].items.end());
-                    fload[q] += fat[f].work;
-                }
-                size_t flongest = 0;
-                for (int x = 0; x < 8; ++x) flongest = std::max(flongest, fqueue[x].size());
-                for (size_t pos = 0; pos < flongest; ++pos)
-                    for (int x = 0; x < 8; ++x)
-                        if (pos < fqueue[x].size()) s->probe_fat_items.push_back(fqueue[x][pos]);
-            }
-        }
-    }
-
-    lap("items");
-    // ---- device side: pool rows, raw lists through the pinned ring, element layout by kernels ----
-    int rc = STORM_HIP_OK;
-    do {
-        // Pool rows are 8 KiB of bits; their PITCH gets a 512-byte chunk more (K2b fetches 64-byte pieces of 64
-        // consecutive rows: at a power-of-two pitch they fall into a handful of memory channels — the dense matrix's
-        // finding, pitch_pad_chunks; option k2_matrix_pad; K2b over the c4 pool 5.95 -> 5.82 ms).
-        // The pad words stay zero: the kernels that take the pitch for the row length multiply zeros there.
-        s->pitch = kBlockWords + pitch_pad_chunks(ctx->k2_matrix_pad, kBlockWords) * kChunkWords;
-        const size_t row_bytes = s->pitch * sizeof(uint64_t);
-        const size_t pool_bytes = (s->pool_rows_ready + 512) * row_bytes;
-        if (hipMalloc(reinterpret_cast<void**>(&s->d_pool), pool_bytes) != hipSuccess) {
-            set_error("sparse_create: hipMalloc of %zu bytes for the block pool failed",
-                      pool_bytes);
-            rc = STORM_HIP_ENOMEM;
-            break;
-        }
-        if (hipMemsetAsync(s->d_pool, 0, pool_bytes, ctx->stream) != hipSuccess) {
-            rc = STORM_HIP_EHIP;
-            break;
-        }
-        // bitmap-kind blocks: straight into their pool rows — in pool-row order the blocks of a column are
-        // consecutive rows, so a run of them is ONE contiguous destination (no staging copy on the device, no
-        // placement kernel; the words may sit at any alignment on the host: a serialized stream)
-        // [r6] ... unless every one of them already lies on the device (the block stage filled while the rows were
-        // added): one kernel gathers the pool rows from the stage's chunks
-        bool gathered = false;
-        if (!dense_row.empty() && stage && stage_token) {
-            bool all = true;
-            for (uint64_t b : dense_blk) all = all && stage_token[b] < stage->n_blocks;
-            if (all) {
-                if ((rc = stage_send(ctx, stage)) != STORM_HIP_OK) break;   // the blocks still in the ring
-                std::vector<uint64_t> table(2 * dense_row.size());
-                for (size_t k = 0; k < dense_row.size(); ++k) table[2 * k] = dense_row[k], table[2 * k + 1] = stage_token[dense_blk[k]];
-                uint64_t* d_table = nullptr;
-                if (stage->d_chunk_table) (void)hipFree(stage->d_chunk_table);
-                stage->d_chunk_table = nullptr;
-                if (hipMalloc(reinterpret_cast<void**>(&stage->d_chunk_table), stage->chunks.size() * sizeof(uint8_t*)) != hipSuccess ||
-                    hipMalloc(reinterpret_cast<void**>(&d_table), table.size() * sizeof(uint64_t)) != hipSuccess) {
-                    set_error("sparse_create: hipMalloc of the gather table failed");
-                    rc = STORM_HIP_ENOMEM;
-                    break;
-                }
-                if (hipMemcpyAsync(stage->d_chunk_table, stage->chunks.data(), stage->chunks.size() * sizeof(uint8_t*),
-                                   hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-                    upload_bytes(ctx, d_table, table.data(), table.size() * sizeof(uint64_t)) != STORM_HIP_OK) {
-                    (void)hipFree(d_table);
-                    rc = STORM_HIP_EHIP;
-                    break;
-                }
-                hipLaunchKernelGGL(gather_staged_kernel, dim3((uint32_t)dense_row.size()), dim3(256), 0, ctx->stream,
-                                   stage->d_chunk_table, d_table, s->d_pool, (uint64_t)s->pitch);
-                const bool ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;   // `table` is pageable
-                (void)hipFree(d_table);
-                if (!ok) { rc = STORM_HIP_EHIP; break; }
-                gathered = true;
-            }
-        }
-        if (!dense_row.empty() && !gathered) {
-            std::vector<uint32_t> order(dense_row.size());
-            for (uint32_t i = 0; i < order.size(); ++i) order[i] = i;
-            std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return dense_row[x] < dense_row[y]; });
-            std::vector<const void*> run;
-            size_t i = 0;
-            while (i < order.size() && rc == STORM_HIP_OK) {
-                const uint32_t row0 = dense_row[order[i]];
-                run.clear();
-                size_t j = i;
-                while (j < order.size() && dense_row[order[j]] == row0 + (j - i)) {
-                    run.push_back(block_ptr[dense_blk[order[j]]]);
-                    ++j;
-                }
-                rc = stager.send_rows(reinterpret_cast<uint8_t*>(s->d_pool) + (size_t)row0 * row_bytes, run,
-                                      (size_t)kBlockWords * sizeof(uint64_t), row_bytes);
-                i = j;
-            }
-            if (rc != STORM_HIP_OK) break;
-        }
-        lap("bitmaps -> pool rows");
-        // list-kind blocks that own a pool row (mixed columns, columns the probe kernel cannot take): expanded there
-        std::vector<uint64_t> loff;
-        if (!list_row.empty()) {
-            loff.reserve(list_blk.size());
-            for (uint64_t b : list_blk) loff.push_back(dev_off[b]);
-            if ((rc = upload(ctx, &dt.lrow, list_row.data(), list_row.size())) ||
-                (rc = upload(ctx, &dt.loff, loff.data(), loff.size())) ||
-                (rc = upload(ctx, &dt.llen, list_len.data(), list_len.size())))
-                break;
-            hipLaunchKernelGGL(expand_lists_kernel, dim3((uint32_t)list_row.size()),
-                               dim3(kThreads), 0, ctx->stream, s->d_pool, s->pitch, dt.lrow, dt.loff, dt.llen,
-                               lists_view);
-            if (hipGetLastError() != hipSuccess) { rc = STORM_HIP_EHIP; break; }
-        }
-        // probe columns: element layout on the device
-        std::vector<uint32_t> tags;
-        uint32_t bad = 0;
-        if (n_probe_elems) {
-            if (hipMalloc(reinterpret_cast<void**>(&s->d_probe_elems), n_probe_elems * sizeof(uint32_t)) != hipSuccess ||
-                hipMalloc(reinterpret_cast<void**>(&s->d_probe_pos16), n_probe_elems * sizeof(uint16_t)) != hipSuccess ||
-                hipMalloc(reinterpret_cast<void**>(&dt.pos_tmp), n_probe_elems * sizeof(uint16_t)) != hipSuccess ||
-                hipMalloc(reinterpret_cast<void**>(&dt.bad), sizeof(uint32_t)) != hipSuccess) {
-                set_error("sparse_create: hipMalloc of the probe element arrays (%zu elements) failed", n_probe_elems);
-                rc = STORM_HIP_ENOMEM;
-                break;
-            }
-            // (the alignment gaps behind every octant read as zero)
-            if (hipMemsetAsync(s->d_probe_elems, 0, n_probe_elems * sizeof(uint32_t), ctx->stream) != hipSuccess ||
-                hipMemsetAsync(s->d_probe_pos16, 0, n_probe_elems * sizeof(uint16_t), ctx->stream) != hipSuccess ||
-                hipMemsetAsync(dt.bad, 0, sizeof(uint32_t), ctx->stream) != hipSuccess) {
-                rc = STORM_HIP_EHIP;
-                break;
-            }
-            tags.reserve(probe_blocks.size());
-            for (size_t pb = 0; pb < probe_blocks.size(); ++pb) tags.push_back(block_local[pb] << 16);
-            // (the lists' offsets, their lengths and the run ends are on the device since the start)
-            if ((rc = upload(ctx, &dt.tags, tags.data(), tags.size())) ||
-                (rc = upload(ctx, &dt.rdst, run_dst.data(), run_dst.size())) ||
-                (rc = upload(ctx, &dt.atoms, atoms.data(), atoms.size())))
-                break;
-            if (!probe_blocks.empty())
-                hipLaunchKernelGGL(probe_fill_kernel, dim3((uint32_t)probe_blocks.size()), dim3(kThreads), 0, ctx->stream,
-                                   lists_view, dt.ploff, dt.pllen, dt.tags, dt.rend, dt.rdst, s->d_probe_elems, dt.pos_tmp, dt.bad);
-            if (!atoms.empty())
-                hipLaunchKernelGGL(probe_deal_kernel, dim3((uint32_t)(atoms.size() / 2)), dim3(kThreads), 0, ctx->stream,
-                                   dt.atoms, dt.pos_tmp, s->d_probe_pos16);
-            if (hipGetLastError() != hipSuccess ||
-                hipMemcpyAsync(&bad, dt.bad, sizeof(bad), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) {
-                rc = STORM_HIP_EHIP;
-                break;
-            }
-        }
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = STORM_HIP_EHIP; break; }
-        if (bad) {
+    if (rc == STORM_HIP_OK) rc = a.lay_out_elements();
+    if (rc == STORM_HIP_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = STORM_HIP_EHIP;
+    if (rc == STORM_HIP_OK) {
+        if (a.bad) {
             set_error("sparse_create: a list block is not strictly ascending");
             rc = STORM_HIP_EINVAL;
         }
-        lap("element layout on the device");
-    } while (0);
-    if (rc == STORM_HIP_EHIP) set_error("sparse_create: HIP failure: %s",
-                                        hipGetErrorString(hipGetLastError()));
+        a.laps.lap("element layout on the device");
+    }
+    if (rc == STORM_HIP_EHIP) set_error("sparse_create: HIP failure: %s", hipGetErrorString(hipGetLastError()));
     if (rc != STORM_HIP_OK) return rc;
     *out = owner.release();
     return STORM_HIP_OK;
@@ -1536,7 +1108,6 @@ static int ensure_full_pool(storm_hip_ctx_t* ctx, storm_hip_sparse_t* s) {
             break;
         }
         if (!s->probe_regions.empty()) {
-            static_assert(sizeof(storm_hip_sparse_s::ProbeRegion) == 16, "four uint32 per region");
             if ((rc = upload(ctx, &d_regions, reinterpret_cast<const uint32_t*>(s->probe_regions.data()),
                              s->probe_regions.size() * 4)))
                 break;
@@ -1873,6 +1444,90 @@ int storm_hip_pairw_sparse(storm_hip_ctx_t* ctx, const storm_hip_sparse_t* cs,
     return storm_hip_pairw_sparse_end(ctx, h_total);
 }
 
+// K4's item list of this launch on the device: planned from the request (storm_hip_plan.cpp) and uploaded when the request
+// differs from the one the device's list was planned from.
+static int ensure_probe_items(storm_hip_ctx_t* ctx, storm_hip_sparse_t* s, ProbeLaunchRequest&& rq) {
+    if (rq == s->probe_request) return STORM_HIP_OK;
+    static_assert(sizeof(ProbeFatItem) >= sizeof(ProbeItem), "one device buffer for either list");
+    ProbeLaunchPlan plan;
+    plan_probe_launch(*s, rq, &plan);
+    s->probe_request.shard_count = 0;   // (no list on the device until the upload below is through)
+    const size_t n_mine = rq.bundle == 1 ? plan.mine.size() : plan.fat.size();
+    if (n_mine > s->probe_items_capacity) {
+        if (s->d_probe_items) STORM_HIP_TRY(hipFree(s->d_probe_items));
+        s->d_probe_items = nullptr;
+        s->probe_items_capacity = 0;
+        STORM_HIP_TRY(hipMalloc(&s->d_probe_items, std::max<size_t>(n_mine, 1024) * sizeof(ProbeFatItem)));
+        s->probe_items_capacity = std::max<size_t>(n_mine, 1024);
+    }
+    if (n_mine) {
+        STORM_HIP_TRY(hipMemcpyAsync(s->d_probe_items, rq.bundle == 1 ? (const void*)plan.mine.data() : (const void*)plan.fat.data(),
+                                     n_mine * (rq.bundle == 1 ? sizeof(ProbeItem) : sizeof(ProbeFatItem)),
+                                     hipMemcpyHostToDevice, ctx->stream));
+        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    s->n_probe_launch = plan.n_probe_launch;
+    s->n_probe_cols_launch = plan.n_probe_cols_launch;
+    s->probe_lookups_launch = plan.probe_lookups_launch;
+    s->probe_request = std::move(rq);
+    return STORM_HIP_OK;
+}
+
+// The probe kernel over the uploaded items; fold_out != nullptr: the kernel folds inside the launch.
+static int launch_probe(storm_hip_ctx_t* ctx, const storm_hip_sparse_t* s, uint32_t shard_rank, uint32_t shard_count,
+                        unsigned long long* fold_out) {
+    // Threads per workgroup by the length of the items (c4, ms per call at 104 / 524 / 1048 / 2097 / 5242 / 10485 /
+    // 20971 draws per row, one box, profiles/r04_h_sparse_probe.txt):
+    //     256 threads, 8 workgroups per CU   0.034 0.047 0.063 0.095 0.193 0.495 1.554
+    //     512, 4                             0.039 0.051 0.064 0.096 0.183 0.341 0.917
+    //    1024, 2                             0.055 0.065 0.078 0.106 0.189 0.328 0.664
+    // Short items are all fixed cost — the item record, the group's positions and the far positions are three
+    // dependent trips to memory, then the histogram — and what covers that is workgroups per CU; long ones want
+    // the workgroups of a CU in step on the same chunk of the stream (its L2 lines are read once per XCD).
+    const bool fat = s->probe_request.bundle != 1;
+    const uint64_t per_item = s->probe_lookups_launch / s->n_probe_launch;
+    const int threads = fat ? (per_item < 1500000u ? 512 : kProbeThreads)
+                        : per_item < 400000u  ? 256
+                        : per_item < 1500000u ? 512
+                                              : kProbeThreads;
+#define STORM_PROBE_LAUNCH(T)                                                                                          \
+    hipLaunchKernelGGL(probe_lists_kernel<T>, dim3(s->n_probe_launch), dim3(T), 0, ctx->stream, s->d_probe_elems,       \
+                       s->d_probe_pos16, static_cast<const ProbeItem*>(s->d_probe_items), shard_count, shard_rank, ctx->d_slots, \
+                       fold_out, 256u)
+#define STORM_PROBE_FAT_LAUNCH(T)                                                                                      \
+    hipLaunchKernelGGL(probe_lists_fat_kernel<T>, dim3(s->n_probe_launch), dim3(T), 0, ctx->stream, s->d_probe_pos16,     \
+                       static_cast<const ProbeFatItem*>(s->d_probe_items), shard_count, shard_rank, ctx->d_slots, fold_out, 256u)
+    if (fat) {
+        if (threads == 512) STORM_PROBE_FAT_LAUNCH(512);
+        else STORM_PROBE_FAT_LAUNCH(kProbeThreads);
+    } else if (threads == 256) STORM_PROBE_LAUNCH(256);
+    else if (threads == 512) STORM_PROBE_LAUNCH(512);
+    else STORM_PROBE_LAUNCH(kProbeThreads);
+#undef STORM_PROBE_FAT_LAUNCH
+#undef STORM_PROBE_LAUNCH
+    STORM_HIP_TRY(hipGetLastError());
+    return STORM_HIP_OK;
+}
+
+// K1's segment table of this shard on the device (cached per shard and segment length)
+static int ensure_segments(storm_hip_ctx_t* ctx, storm_hip_sparse_t* s, uint32_t seg_len, uint32_t shard_rank, uint32_t shard_count) {
+    if (s->d_segs && s->seg_rank == shard_rank && s->seg_count == shard_count && s->seg_len == seg_len) return STORM_HIP_OK;
+    std::vector<Seg> mine;
+    if (s->d_segs) STORM_HIP_TRY(hipFree(s->d_segs));
+    s->d_segs = nullptr;
+    plan_sparse_segments(s->cols, seg_len, shard_rank, shard_count, &mine, &s->seg_row_sum);
+    if (!mine.empty()) {
+        STORM_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s->d_segs), mine.size() * sizeof(Seg)));
+        STORM_HIP_TRY(hipMemcpyAsync(s->d_segs, mine.data(), mine.size() * sizeof(Seg), hipMemcpyHostToDevice, ctx->stream));
+        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    s->n_segs = (uint32_t)mine.size();
+    s->seg_rank = shard_rank;
+    s->seg_count = shard_count;
+    s->seg_len = seg_len;
+    return STORM_HIP_OK;
+}
+
 // Launches this shard's share into the context's result word; _end fetches it.
 int storm_hip_pairw_sparse_begin(storm_hip_ctx_t* ctx, const storm_hip_sparse_t* cs,
                                  uint32_t shard_rank, uint32_t shard_count) {
@@ -1898,198 +1553,75 @@ int storm_hip_pairw_sparse_begin(storm_hip_ctx_t* ctx, const storm_hip_sparse_t*
     int variant = ctx->variant;
     if (variant < 0) variant = widest >= 64 ? 4 : 2;
     ctx->variant_used = variant;
-    if (variant >= 3) {
-        // K4: columns of short lists go to the probe kernel ("sparse_probe": -1 = when the mean list
-        // has at most 1000 positions — measured at c4 (profiles/r02_q_sparse_probe.jsonl): 47x faster
-        // than the dense path at 13 positions per list, 15x at 65, 3.0x at 393, 1.7x at 655, 1.1x at 1012 —,
-        // 1 = every eligible column, 0 = never); what it counts lands in the same slots the strips'
-        // fold sums up
-        std::vector<uint8_t> use_probe(s->cols.size(), 0);
-        if (ctx->sparse_probe != 0 && s->d_probe_elems)
-            for (size_t e = 0; e < s->cols.size(); ++e)
-                use_probe[e] = s->col_probe[e];
-        {
-            // [r6] one group per workgroup (probe_lists_kernel) unless the option asks for bundles of four
-            // (probe_bundle 4: probe_lists_fat_kernel — measured 5 - 25 % slower at every c4 load); both lists hold the same work
-            const int bundle = ctx->probe_bundle == 4 ? (int)kFatGroups : 1;
-            uint64_t key = 1469598103934665603ull ^ ((uint64_t)shard_rank << 32 | shard_count) ^ ((uint64_t)bundle << 56);
-            for (uint8_t u : use_probe) key = (key ^ u) * 1099511628211ull;
-            if (key != s->probe_key) {
-                static_assert(sizeof(ProbeFatItem) >= sizeof(ProbeItem), "one device buffer for either list");
-                std::vector<ProbeItem> mine;
-                std::vector<ProbeFatItem> fat;
-                uint32_t cols_used = 0;
-                for (size_t e = 0; e < use_probe.size(); ++e) cols_used += use_probe[e];
-                if (bundle == 1) {
-                    for (const auto& pi : s->probe_items)
-                        if (use_probe[pi.col])
-                            mine.push_back({pi.a_begin, pi.a_end, pi.n_begin, pi.n_end, pi.b_begin, pi.b_end, pi.a0});
-                } else {
-                    for (const auto& pi : s->probe_fat_items)
-                        if (use_probe[pi.col])
-                            fat.push_back({{pi.at[0], pi.at[1], pi.at[2], pi.at[3], pi.at[4]}, pi.b_begin, pi.b_end, pi.first});
-                }
-                const size_t n_mine = bundle == 1 ? mine.size() : fat.size();
-                if (n_mine > s->probe_items_capacity) {
-                    if (s->d_probe_items) STORM_HIP_TRY(hipFree(s->d_probe_items));
-                    s->d_probe_items = nullptr;
-                    s->probe_items_capacity = 0;
-                    STORM_HIP_TRY(hipMalloc(&s->d_probe_items, std::max<size_t>(n_mine, 1024) * sizeof(ProbeFatItem)));
-                    s->probe_items_capacity = std::max<size_t>(n_mine, 1024);
-                }
-                if (n_mine) {
-                    STORM_HIP_TRY(hipMemcpyAsync(s->d_probe_items, bundle == 1 ? (const void*)mine.data() : (const void*)fat.data(),
-                                                 n_mine * (bundle == 1 ? sizeof(ProbeItem) : sizeof(ProbeFatItem)),
-                                                 hipMemcpyHostToDevice, ctx->stream));
-                    STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-                }
-                // shard r of G takes items r, r + G, ...: the grid covers ceil((n - r) / G) of them
-                s->n_probe_launch = n_mine > shard_rank ? (uint32_t)((n_mine - shard_rank + shard_count - 1) / shard_count) : 0u;
-                s->n_probe_cols_launch = cols_used;
-                // lookups of this shard's items: a streamed far position against every group of the item + the own rows'
-                // elements (against their own group and, in a bundle, the groups in front of it)
-                s->probe_lookups_launch = 0;
-                if (bundle == 1) {
-                    for (size_t k = shard_rank; k < mine.size(); k += shard_count)
-                        s->probe_lookups_launch += (uint64_t)(mine[k].b_end - mine[k].b_begin) + (mine[k].n_end - mine[k].n_begin);
-                } else {
-                    for (size_t k = shard_rank; k < fat.size(); k += shard_count) {
-                        uint32_t groups = 0;
-                        for (uint32_t g = 0; g < kFatGroups; ++g) {
-                            const uint32_t len = fat[k].at[g + 1] - fat[k].at[g];
-                            groups += len != 0;
-                            if (fat[k].first) s->probe_lookups_launch += (uint64_t)len * (g + 1u);
-                        }
-                        s->probe_lookups_launch += (uint64_t)(fat[k].b_end - fat[k].b_begin) * groups;
-                    }
-                }
-                s->probe_bundle_launch = bundle;
-                s->probe_key = key;
-            }
+    if (variant < 3) {
+        if (int rc = ensure_full_pool(ctx, s)) return rc;  // the popcount kernel walks every column's pool rows
+        if (int rc = ensure_segments(ctx, s, (uint32_t)ctx->seg_rows, shard_rank, shard_count)) return rc;
+        return launch_pairw_segments(ctx, s->d_pool, s->pitch, s->d_segs, s->n_segs, s->seg_row_sum, d_result);
+    }
+    // K4: columns of short lists go to the probe kernel ("sparse_probe": -1 = when the mean list
+    // has at most 1000 positions — measured at c4 (profiles/r02_q_sparse_probe.jsonl): 47x faster
+    // than the dense path at 13 positions per list, 15x at 65, 3.0x at 393, 1.7x at 655, 1.1x at 1012 —,
+    // 1 = every eligible column, 0 = never); what it counts lands in the same slots the strips'
+    // fold sums up
+    // [r6] one group per workgroup (probe_lists_kernel) unless the option asks for bundles of four
+    // (probe_bundle 4: probe_lists_fat_kernel — measured 5 - 25 % slower at every c4 load); both lists hold the same work
+    ProbeLaunchRequest rq{shard_rank, shard_count, ctx->probe_bundle == 4 ? (int32_t)kFatGroups : 1,
+                          std::vector<uint8_t>(s->cols.size(), 0)};
+    if (ctx->sparse_probe != 0 && s->d_probe_elems) rq.use_probe = s->col_probe;
+    if (int rc = ensure_probe_items(ctx, s, std::move(rq))) return rc;
+    const std::vector<uint8_t>& use_probe = s->probe_request.use_probe;
+    std::vector<RowRange> ranges;
+    uint64_t rows_needed = 0;
+    for (size_t e = 0; e < s->cols.size(); ++e) {
+        RowRange rg = s->cols[e];
+        if (use_probe[e]) {
+            // the list blocks pair with each other in the probe kernel: the matrix cores take the pairs with a
+            // bitmap block — the column's bitmap rows as A rows, against each other and the lists behind them
+            if (s->col_list0[e] == rg.r0) continue;  // no bitmap block
+            rg.a_end = s->col_list0[e];
         }
-        bool probe_folds = false;
-        std::vector<RowRange> ranges;
-        uint64_t rows_needed = 0;
-        for (size_t e = 0; e < s->cols.size(); ++e) {
-            RowRange rg = s->cols[e];
-            if (use_probe[e]) {
-                // the list blocks pair with each other in the probe kernel: the matrix cores take the pairs with a
-                // bitmap block — the column's bitmap rows as A rows, against each other and the lists behind them
-                if (s->col_list0[e] == rg.r0) continue;  // no bitmap block
-                rg.a_end = s->col_list0[e];
-            }
-            if (rg.r1 - rg.r0 > 1) {
-                ranges.push_back(rg);
-                rows_needed = std::max(rows_needed, rg.r1);
-            }
+        if (rg.r1 - rg.r0 > 1) {
+            ranges.push_back(rg);
+            rows_needed = std::max(rows_needed, rg.r1);
         }
-        if (s->n_probe_launch > 0) {
-            ctx->pass_report[0] |= STORM_HIP_RAN_LIST_PROBE;
-            ctx->pass_report[2] += s->probe_lookups_launch;
-            ctx->pass_report[3] = kProbeRows;
-            // Threads per workgroup by the length of the items (c4, ms per call at 104 / 524 / 1048 / 2097 / 5242 / 10485 /
-            // 20971 draws per row, one box, profiles/r04_h_sparse_probe.txt):
-            //     256 threads, 8 workgroups per CU   0.034 0.047 0.063 0.095 0.193 0.495 1.554
-            //     512, 4                             0.039 0.051 0.064 0.096 0.183 0.341 0.917
-            //    1024, 2                             0.055 0.065 0.078 0.106 0.189 0.328 0.664
-            // Short items are all fixed cost — the item record, the group's positions and the far positions are three
-            // dependent trips to memory, then the histogram — and what covers that is workgroups per CU; long ones want
-            // the workgroups of a CU in step on the same chunk of the stream (its L2 lines are read once per XCD).
-            const uint64_t per_item = s->probe_lookups_launch / s->n_probe_launch;
-            const int threads = s->probe_bundle_launch != 1 ? (per_item < 1500000u ? 512 : kProbeThreads)
-                                : per_item < 400000u        ? 256
-                                : per_item < 1500000u       ? 512
-                                                            : kProbeThreads;
-            // lists only (no pool rows to multiply) and a short launch: the probe kernel folds inside the launch
-            // (option k2_fold_inline as for the strips; the slot words' 48-bit sums hold any total below 2^47 / 4096 x 256)
-            probe_folds = ranges.empty() && ctx->k2_fold_inline != 0 && s->n_probe_launch <= 16384u &&
-                          s->probe_lookups_launch < (1ull << 38);
-            unsigned long long* fold_out = probe_folds ? reinterpret_cast<unsigned long long*>(d_result) : nullptr;
-#define STORM_PROBE_LAUNCH(T)                                                                                          \
-    hipLaunchKernelGGL(probe_lists_kernel<T>, dim3(s->n_probe_launch), dim3(T), 0, ctx->stream, s->d_probe_elems,       \
-                       s->d_probe_pos16, static_cast<const ProbeItem*>(s->d_probe_items), shard_count, shard_rank, ctx->d_slots, \
-                       fold_out, 256u)
-#define STORM_PROBE_FAT_LAUNCH(T)                                                                                      \
-    hipLaunchKernelGGL(probe_lists_fat_kernel<T>, dim3(s->n_probe_launch), dim3(T), 0, ctx->stream, s->d_probe_pos16,     \
-                       static_cast<const ProbeFatItem*>(s->d_probe_items), shard_count, shard_rank, ctx->d_slots, fold_out, 256u)
-            if (s->probe_bundle_launch != 1) {
-                if (threads == 512) STORM_PROBE_FAT_LAUNCH(512);
-                else STORM_PROBE_FAT_LAUNCH(kProbeThreads);
-            } else if (threads == 256) STORM_PROBE_LAUNCH(256);
-            else if (threads == 512) STORM_PROBE_LAUNCH(512);
-            else STORM_PROBE_LAUNCH(kProbeThreads);
-#undef STORM_PROBE_FAT_LAUNCH
-#undef STORM_PROBE_LAUNCH
-            STORM_HIP_TRY(hipGetLastError());
-        }
+    }
+    if (s->n_probe_launch > 0) {
+        ctx->pass_report[0] |= STORM_HIP_RAN_LIST_PROBE;
+        ctx->pass_report[2] += s->probe_lookups_launch;
+        ctx->pass_report[3] = kProbeRows;
+        // lists only (no pool rows to multiply) and a short launch: the probe kernel folds inside the launch
+        // (option k2_fold_inline as for the strips; the slot words' 48-bit sums hold any total below 2^47 / 4096 x 256)
+        const bool probe_folds = ranges.empty() && ctx->k2_fold_inline != 0 && s->n_probe_launch <= 16384u &&
+                                 s->probe_lookups_launch < (1ull << 38);
+        if (int rc = launch_probe(ctx, s, shard_rank, shard_count,
+                                  probe_folds ? reinterpret_cast<unsigned long long*>(d_result) : nullptr))
+            return rc;
         if (probe_folds) {   // the total is in d_scalar already: nothing to multiply, nothing to fold
             ctx->last_info[0] = 0;
             ctx->last_info[3] = s->n_probe_cols_launch;
             ctx->k2_operands_used = 5;
             return STORM_HIP_OK;
         }
-        if (rows_needed > s->pool_rows_ready)
-            if (int rc = ensure_full_pool(ctx, s)) return rc;
-        // (only the rows the dense pass multiplies are expanded: the probe columns lie behind them)
-        const uint64_t rows_dst = (rows_needed + 511) / 512 * 512;
-        // The strips on bit operands (K2b) multiply the pool rows as they are: no FP4 shadow of the pool (2.6 GB
-        // at c4), no expansion pass. The rows behind a column's last one up to the next multiple of 512 are zero
-        // in the pool (columns start on multiples of 512 and nothing writes between them).
-        if (variant == 4 && strip_operands_of(ctx) == 5 && ctx->k2_debug == 0 && !ctx->k2_persistent &&
-            rows_dst <= s->pool_rows_ready + 512) {
-            if (int rc = launch_pairw_bits_ranges(ctx, reinterpret_cast<const uint8_t*>(s->d_pool), s->pitch * 8ull,
-                                                  ranges, kBlockWords / 4u, shard_rank, shard_count,
-                                                  d_result, s->n_probe_launch > 0))
-                return rc;
-            ctx->last_info[3] = s->n_probe_cols_launch;
-            return STORM_HIP_OK;
-        }
-        if (int rc = launch_pairw_mfma_ranges(ctx, s->d_pool, s->pitch, s->pool_rows_ready + 512,
-                                              std::max<uint64_t>(rows_dst, 512), ranges,
-                                              shard_rank, shard_count, variant == 5 ? 2 : variant == 4 ? 1 : 0,
-                                              d_result))
+    }
+    if (rows_needed > s->pool_rows_ready)
+        if (int rc = ensure_full_pool(ctx, s)) return rc;
+    // (only the rows the dense pass multiplies are expanded: the probe columns lie behind them)
+    const uint64_t rows_dst = (rows_needed + 511) / 512 * 512;
+    // The strips on bit operands (K2b) multiply the pool rows as they are: no FP4 shadow of the pool (2.6 GB
+    // at c4), no expansion pass. The rows behind a column's last one up to the next multiple of 512 are zero
+    // in the pool (columns start on multiples of 512 and nothing writes between them).
+    if (variant == 4 && strip_operands_of(ctx) == 5 && ctx->k2_debug == 0 && !ctx->k2_persistent &&
+        rows_dst <= s->pool_rows_ready + 512) {
+        if (int rc = launch_pairw_bits_ranges(ctx, reinterpret_cast<const uint8_t*>(s->d_pool), s->pitch * 8ull,
+                                              ranges, kBlockWords / 4u, shard_rank, shard_count,
+                                              d_result, s->n_probe_launch > 0))
             return rc;
-        ctx->last_info[3] = s->n_probe_cols_launch;  // block columns counted by the list-probe kernel
-        return STORM_HIP_OK;
-    }
-    if (int rc = ensure_full_pool(ctx, s)) return rc;  // the popcount kernel walks every column's pool rows
-    const uint32_t seg_len = (uint32_t)ctx->seg_rows;
-    if (!s->d_segs || s->seg_rank != shard_rank || s->seg_count != shard_count ||
-        s->seg_len != seg_len) {
-        // upper triangle of every block column; shard = every shard_count-th segment
-        std::vector<Seg> full, diag, mine;
-        for (const RowRange& col : s->cols) {
-            const uint64_t lo = col.r0, hi = col.r1;
-            for (uint64_t a0 = lo; a0 < hi; a0 += kABlockRows) {
-                const uint32_t a_end = (uint32_t)std::min<uint64_t>(a0 + kABlockRows, hi);
-                if (a_end - a0 > 1) diag.push_back({(uint32_t)a0, a_end, (uint32_t)a0, a_end});
-                for (uint64_t j = a0 + kABlockRows; j < hi; j += seg_len)
-                    full.push_back({(uint32_t)a0, a_end, (uint32_t)j,
-                                    (uint32_t)std::min<uint64_t>(j + seg_len, hi)});
-            }
-        }
-        for (size_t i = shard_rank; i < full.size(); i += shard_count) mine.push_back(full[i]);
-        for (size_t i = shard_rank; i < diag.size(); i += shard_count) mine.push_back(diag[i]);
-        if (s->d_segs) STORM_HIP_TRY(hipFree(s->d_segs));
-        s->d_segs = nullptr;
-        s->seg_row_sum = 0;
-        for (const Seg& g : mine) s->seg_row_sum += g.j_hi - g.j_lo;
-        if (!mine.empty()) {
-            STORM_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s->d_segs),
-                                    mine.size() * sizeof(Seg)));
-            STORM_HIP_TRY(hipMemcpyAsync(s->d_segs, mine.data(), mine.size() * sizeof(Seg),
-                                         hipMemcpyHostToDevice, ctx->stream));
-            STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        }
-        s->n_segs = (uint32_t)mine.size();
-        s->seg_rank = shard_rank;
-        s->seg_count = shard_count;
-        s->seg_len = seg_len;
-    }
-    if (int rc = launch_pairw_segments(ctx, s->d_pool, s->pitch, s->d_segs, s->n_segs,
-                                       s->seg_row_sum,
-                                       d_result))
+    } else if (int rc = launch_pairw_mfma_ranges(ctx, s->d_pool, s->pitch, s->pool_rows_ready + 512,
+                                                 std::max<uint64_t>(rows_dst, 512), ranges,
+                                                 shard_rank, shard_count, variant == 5 ? 2 : variant == 4 ? 1 : 0,
+                                                 d_result))
         return rc;
+    ctx->last_info[3] = s->n_probe_cols_launch;  // block columns counted by the list-probe kernel
     return STORM_HIP_OK;
     });
 }

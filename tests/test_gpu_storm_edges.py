@@ -474,6 +474,46 @@ def test_ragged_row_counts(orc, N):
         check_all(orc, rows, combos=((1, 1), (0, 0)), ops=("and",), serialized=False)
 
 
+def test_probe_streams_of_several_chunks_and_three_shards(orc):
+    """Case E of tests/test_arena_plan.py (700 lists of 800 positions in one block column: every octant's far stream has
+    several chunks, the last atom is ragged) as a STORM_t: the total through every build and both item lists, then the
+    arena's shards of worlds 1 and 3 summed."""
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location(
+        "make_arena_digests", os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "make_arena_digests.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    rows = [row[0][2].astype(np.uint32) for row in gen.case_rows("E")]
+    want = _np_total(rows)
+    assert orc.storm(rows).pairw() == want
+    s = _storm(rows)
+    lib = sb.load()
+    ctx = sb.HipContext(0)
+    h = C.c_void_p()
+    try:
+        check_totals(s, rows, want)
+        data = s.serialize()
+        assert lib.storm_hip_sparse_create_serialized(ctx._h, data.ctypes.data_as(C.c_void_p), data.size, C.byref(h)) == 0, \
+            lib.storm_hip_last_error()
+        out = C.c_uint64()
+        ctx.set_option("sparse_probe", 1)
+        for bundle in (1, 4):
+            ctx.set_option("probe_bundle", bundle)
+            for world in (1, 3, 1):     # (back to one shard: the list on the device is planned again)
+                parts = []
+                for rank in range(world):
+                    assert lib.storm_hip_pairw_sparse(ctx._h, h, rank, world, C.byref(out)) == 0, lib.storm_hip_last_error()
+                    assert "probe_lists_kernel" in ctx.last_pass_report()["kernels"]
+                    parts.append(out.value)
+                assert sum(parts) == want and (world == 1 or all(parts)), (bundle, world, parts, want)
+    finally:
+        if h:
+            lib.storm_hip_sparse_destroy(ctx._h, h)
+        ctx.close()
+        s.free()
+
+
 # ---------------------------------------------------------------------------------------------- device copies follow edits
 _ROW_BYTES, _BLOCK_BYTES = 32, 128     # sizeof(STORM_bitmap_cont_t), sizeof(STORM_bitmap_t) (tests/test_abi.py)
 
