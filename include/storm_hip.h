@@ -437,7 +437,16 @@ int storm_hip_sparse_create_blocks(storm_hip_ctx_t* ctx, uint64_t n_rows, uint64
  * the block's 1024 words into a pinned ring (sent 4 MiB at a time into 64 MiB device chunks) and returns its token;
  * storm_hip_sparse_create_blocks_staged builds the arena of storm_hip_sparse_create_blocks with the pool rows gathered
  * from the stage when EVERY bitmap block carries a valid token (token[b] < storm_hip_stage_count), and from block_ptr
- * otherwise; list blocks: a token of storm_hip_stage_add_list or ~0 (from block_ptr). The stage may be destroyed once the arena exists. */
+ * otherwise; list blocks: a token of storm_hip_stage_add_list or ~0 (from block_ptr). The stage may be destroyed once the arena exists.
+ * A list token is the list's byte position in the stage's list space, which is cut into chunks of 64 MiB; a list never runs
+ * across a chunk's end, so the bytes between a chunk's last list and its end (the gap) are never written. Both staged
+ * builders refuse — STORM_HIP_EINVAL, *out NULL, storm_hip_last_error() names the stage token, nothing is sent or launched —
+ * a list token (other than ~0) with block_n[b] = n that
+ *   - is odd,
+ *   - lies beyond the chunks the stage has written to,
+ *   - lies in a gap, or
+ *   - whose 2 n bytes run across its chunk's end or past the last list the chunk holds.
+ * A token that points into the middle of a staged list is in bounds and is read as it lies. */
 typedef struct storm_hip_stage_s storm_hip_stage_t;
 int storm_hip_stage_create(storm_hip_ctx_t* ctx, storm_hip_stage_t** out);
 int storm_hip_stage_add(storm_hip_ctx_t* ctx, storm_hip_stage_t* stage, const uint64_t* words, uint64_t* token);
@@ -485,7 +494,8 @@ int storm_hip_rowlists_create_blocks(storm_hip_ctx_t* ctx, uint64_t n_rows, uint
                                      const uint8_t* block_kind, const uint32_t* block_n,
                                      const void* const* block_ptr, storm_hip_rowlists_t** out);
 /* ... with the lists taken from a block stage (storm_hip_stage_add_list) when EVERY non-empty block carries a token
- * (token[b] != ~0); from block_ptr otherwise. The stage is only read. */
+ * (token[b] != ~0); from block_ptr otherwise. The stage is only read. Tokens the stage cannot answer are refused as above,
+ * before anything is allocated on the device. */
 int storm_hip_rowlists_create_blocks_staged(storm_hip_ctx_t* ctx, uint64_t n_rows, uint64_t n_blocks,
                                             const uint64_t* row_block_offset, const uint32_t* block_id,
                                             const uint8_t* block_kind, const uint32_t* block_n,

@@ -746,6 +746,8 @@ int storm_hip_rowlists_create_blocks_staged(storm_hip_ctx_t* ctx, uint64_t n_row
             row_off[n_rows] = (uint32_t)e;
         }
         lap("block walk");
+        if (all_staged)   // (before anything is allocated or sent)
+            if (int rc = stage_check_lists(stage, ltable)) return rc;
         STORM_HIP_TRY(hipSetDevice(ctx->device));
         struct Temps {
             uint32_t *pos = nullptr, *row_off = nullptr, *cursor = nullptr, *bad = nullptr;   // (pos and row_off: the arena's own, see below)

@@ -1193,6 +1193,35 @@ void plan_sparse_segments(const std::vector<RowRange>& cols, uint32_t seg_len, u
     for (const Seg& g : mine) *seg_row_sum += g.j_hi - g.j_lo;
 }
 
+// ---- the block stage's list space ----
+StageListPlace stage_place_list(uint64_t lbase, uint32_t lfill, uint32_t n) {
+    const uint64_t bytes = (uint64_t)n * 2u, at = lbase + lfill;
+    // the buffer goes to its chunk with ONE copy: with this list behind its bytes it must end inside the chunk it starts
+    // in. (A buffer that ends exactly ON the chunk's end leaves too: at % kStageListChunk is 0 there, and a list appended
+    // to it would be copied past the end of the chunk it does not belong to.)
+    const bool over_chunk = lbase % kStageListChunk + lfill + bytes > kStageListChunk;
+    StageListPlace p;
+    p.send = (over_chunk || lfill + bytes > kStageListBuf) ? 1u : 0u;
+    p.lbase = p.send ? at : lbase;
+    if (over_chunk) p.lbase = (at + kStageListChunk - 1u) / kStageListChunk * kStageListChunk;
+    p.token = p.send ? p.lbase : at;
+    return p;
+}
+
+void stage_note_list(std::vector<uint64_t>* written, uint64_t token, uint32_t n) {
+    const uint64_t chunk = token / kStageListChunk;
+    if (written->size() <= chunk) written->resize(chunk + 1u, 0);
+    (*written)[chunk] = token % kStageListChunk + (uint64_t)n * 2u;
+}
+
+bool stage_list_readable(const std::vector<uint64_t>& written, uint64_t token, uint64_t n) {
+    if (token & 1u) return false;
+    const uint64_t chunk = token / kStageListChunk, off = token % kStageListChunk;
+    if (chunk >= written.size()) return false;                  // beyond the stage
+    if (n > kStageListChunk) return false;                      // (2 n below cannot wrap)
+    return off + n * 2u <= written[chunk];                      // not in the gap, not across the chunk's end
+}
+
 }  // namespace storm
 
 // Host-only view of the default path's work decomposition (no device is touched): what a shard

@@ -341,4 +341,27 @@ void plan_probe_launch(const ProbeWork& work, const ProbeLaunchRequest& rq, Prob
 void plan_sparse_segments(const std::vector<RowRange>& cols, uint32_t seg_len, uint32_t shard_rank, uint32_t shard_count,
                           std::vector<Seg>* mine, uint64_t* seg_row_sum);
 
+// ---- the block stage's list space (storm_hip_sparse.hip: storm_hip_stage_add_list and the staged builders) ----
+// The staged lists are one byte stream: position p = list chunk p / kStageListChunk, offset p % kStageListChunk. They
+// leave the host in buffers of at most kStageListBuf bytes, one copy each, so a buffer — and with it every list — lies
+// inside ONE chunk: a list that would run across a chunk's end starts the next chunk instead, and the bytes between
+// the last list of a chunk and the chunk's end (the gap) are never written. A list's token is its position.
+constexpr uint64_t kStageListBuf = 4u << 20, kStageListChunk = 64u << 20;
+constexpr uint32_t kStageMaxList = 65536;   // positions of a list block at most
+struct StageListPlace {
+    uint64_t lbase;   // where the current buffer starts once the list is in it
+    uint64_t token;   // the list's position
+    uint32_t send;    // 1: the current buffer [lbase, lbase + lfill) leaves first
+    uint32_t pad = 0;
+};
+// Where a list of n positions (1 .. kStageMaxList) goes when the current buffer starts at lbase and holds lfill bytes.
+StageListPlace stage_place_list(uint64_t lbase, uint32_t lfill, uint32_t n);
+// written[c] = the bytes of list chunk c that hold lists (they lie back to back from the chunk's start): the record
+// stage_list_readable answers from. Called for every list placed, in order.
+void stage_note_list(std::vector<uint64_t>* written, uint64_t token, uint32_t n);
+// Do all 2 n bytes at `token` lie inside bytes the stage wrote, within one chunk? No for an odd token, a token beyond the
+// stage, a token in a gap and a list that would run across its chunk's end or past what the chunk holds. (A token that
+// points into the middle of a staged list is in bounds: yes.)
+bool stage_list_readable(const std::vector<uint64_t>& written, uint64_t token, uint64_t n);
+
 }  // namespace storm

@@ -574,8 +574,10 @@ struct storm_hip_stage_s {
     const uint8_t** d_chunk_table = nullptr;   // the chunks' addresses on the device (rebuilt per gather)
     // the LIST blocks: a byte stream of its own ("list space": position p = chunk p / 64 MiB, offset p % 64 MiB; a list never
     // straddles a chunk), through two pinned buffers of kListBuf bytes behind the bitmaps' ring in the same allocation
-    static constexpr size_t kListBuf = 4u << 20, kListChunk = 64u << 20;
+    // (where a list goes and which tokens may be read: stage_place_list / stage_list_readable, storm_hip_plan.cpp)
+    static constexpr size_t kListBuf = storm::kStageListBuf, kListChunk = storm::kStageListChunk;
     std::vector<uint8_t*> lchunks;
+    std::vector<uint64_t> lwritten;   // per list chunk: the bytes that hold lists (stage_note_list); behind them the gap
     uint8_t* h_lring = nullptr;
     hipEvent_t lev[2] = {nullptr, nullptr};
     bool lused[2] = {false, false};
@@ -665,6 +667,18 @@ __global__ __launch_bounds__(256) void gather_staged_kernel(const uint8_t* const
 }  // namespace
 
 namespace storm {
+// Every (token, length) of `ltable` against what the stage holds (stage_list_readable). Host only: nothing is sent or
+// launched for a table that is refused.
+int stage_check_lists(const storm_hip_stage_t* stage, const std::vector<uint64_t>& ltable) {
+    for (size_t k = 0; k < ltable.size(); k += 3)
+        if (!stage_list_readable(stage->lwritten, ltable[k + 1], ltable[k + 2])) {
+            set_error("block stage: the stage token %llu of a list of %llu positions is odd or names bytes the stage does not hold",
+                      (unsigned long long)ltable[k + 1], (unsigned long long)ltable[k + 2]);
+            return STORM_HIP_EINVAL;
+        }
+    return STORM_HIP_OK;
+}
+
 // lists[dst ..) <- the staged lists of `ltable` (three words per block: destination element, list token, length): what is
 // still in the stage's ring goes first; the table's device copy is handed back for the caller to free. Waits for the stream
 // (the tables are pageable). Tokens are checked against what the stage holds.
@@ -672,12 +686,7 @@ int stage_gather_lists(storm_hip_ctx_t* ctx, storm_hip_stage_t* stage, const std
                        uint64_t** d_table) {
     *d_table = nullptr;
     if (ltable.empty()) return STORM_HIP_OK;
-    const uint64_t list_space = stage->lbase + stage->lfill;
-    for (size_t k = 0; k < ltable.size(); k += 3)
-        if ((ltable[k + 1] & 1u) || ltable[k + 1] + ltable[k + 2] * 2u > list_space) {
-            set_error("block stage: a list token lies outside the stage");
-            return STORM_HIP_EINVAL;
-        }
+    if (int rc0 = stage_check_lists(stage, ltable)) return rc0;
     if (int rc0 = stage_send_lists(ctx, stage)) return rc0;
     if (stage->d_lchunk_table) ctx->deferred_free.push_back(stage->d_lchunk_table);
     stage->d_lchunk_table = nullptr;
@@ -741,21 +750,21 @@ int storm_hip_stage_add(storm_hip_ctx_t* ctx, storm_hip_stage_t* st, const uint6
 
 int storm_hip_stage_add_list(storm_hip_ctx_t* ctx, storm_hip_stage_t* st, const uint16_t* list, uint32_t n, uint64_t* token) {
     return guarded("storm_hip_stage_add_list", [&]() -> int {
-        if (!ctx || !st || !list || !token || n == 0 || n > 65536u) {
+        if (!ctx || !st || !list || !token || n == 0 || n > kStageMaxList) {
             set_error("stage_add_list: NULL argument or a list of %u positions", n);
             return STORM_HIP_EINVAL;
         }
         const uint32_t bytes = n * 2u;
-        const uint64_t at = st->lbase + st->lfill;
-        const bool over_chunk = at % storm_hip_stage_s::kListChunk + bytes > storm_hip_stage_s::kListChunk;
-        if (over_chunk || st->lfill + bytes > storm_hip_stage_s::kListBuf) {
+        const StageListPlace at = stage_place_list(st->lbase, st->lfill, n);
+        if (at.send) {
             STORM_HIP_TRY(hipSetDevice(ctx->device));
             if (int rc = stage_send_lists(ctx, st)) return rc;
-            if (over_chunk) st->lbase = (st->lbase / storm_hip_stage_s::kListChunk + 1u) * storm_hip_stage_s::kListChunk;
+            st->lbase = at.lbase;   // (behind what has left, or the start of the next chunk)
         }
         memcpy(st->h_lring + (size_t)st->lcur * storm_hip_stage_s::kListBuf + st->lfill, list, bytes);
-        *token = st->lbase + st->lfill;
+        *token = at.token;
         st->lfill += bytes;
+        stage_note_list(&st->lwritten, at.token, n);
         return STORM_HIP_OK;
     });
 }
@@ -856,8 +865,9 @@ int ArenaBuild::send_lists(Stager& stager) {
     for (uint64_t b = 0; b < in.n_blocks; ++b)
         if (wanted[b] && in.block_n[b]) {
             if (stage && stage_token && stage_token[b] != ~0ull) {
-                if ((stage_token[b] & 1u) || stage_token[b] + (uint64_t)in.block_n[b] * 2u > list_space) {
-                    set_error("sparse_create: block %llu carries a list token outside the stage", (unsigned long long)b);
+                if (!stage_list_readable(stage->lwritten, stage_token[b], in.block_n[b])) {
+                    set_error("sparse_create: the stage token %llu of block %llu, a list of %u positions, is odd or names bytes the "
+                              "stage does not hold", (unsigned long long)stage_token[b], (unsigned long long)b, in.block_n[b]);
                     return STORM_HIP_EINVAL;
                 }
                 staged.push_back(b);

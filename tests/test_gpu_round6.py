@@ -355,8 +355,9 @@ def test_blocks_edited_between_the_adds_and_the_first_call_do_not_come_from_the_
 def test_block_stage_through_the_c_abi_with_some_lists_staged_and_some_from_the_host(hip_ctx, orc):
     """storm_hip_stage_* + storm_hip_sparse_create_blocks_staged / storm_hip_rowlists_create_blocks_staged called directly
     (storm.h hands over all of a container's blocks or none): every bitmap block staged, every SECOND list block staged and the
-    others with token ~0 (they travel from block_ptr at build time), lists long enough to cross a ring buffer; then every list
-    staged for the row lists' build. Totals and per-pair counts against the oracle's STORM_t restatement (storm.c:790-814)."""
+    others with token ~0 (they travel from block_ptr at build time); then every list staged for the row lists' build. About
+    150 bitmap blocks and under 1 MiB of lists: one ring buffer of either kind, never sent before the build (the ring and
+    chunk limits: tests/test_gpu_stage_edges.py). Totals and per-pair counts against the oracle's STORM_t restatement (storm.c:790-814)."""
     import ctypes as C
     import torch
     lib = sb._lib.load()
