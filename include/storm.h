@@ -324,6 +324,33 @@ int STORM_square_similarity(STORM_t* a, STORM_t* b, int measure, uint64_t n_bits
 int STORM_square_similarity_device(STORM_t* a, STORM_t* b, int measure, uint64_t n_bits, float* d_out, uint64_t out_rows,
                                    uint64_t out_ld);
 
+/* Extension: the per-pair matrices for the pairs within max_lag rows of each other only — what LD pruning, clumping, r^2 decay
+ * and banded LD matrices ask for: row i against the next w rows in container order, not all-vs-all. With n the rows held
+ * and L = min(max_lag, n - 1), `out` holds out_rows x out_ld entries (out_rows >= n, out_ld >= L) and the pair (i, j),
+ * 1 <= j - i <= L, lies at out[i * out_ld + (j - i - 1)]: n x L entries instead of n x n, and only the tiles within L rows
+ * of the diagonal are multiplied. Host forms write columns [0, L) of every row (0 / 0.0f where i + 1 + d >= n); _device forms
+ * (`d_out` in device memory) leave everything outside the layout untouched. Counts under `op` (0 and, 1 or, 2 xor) as uint32,
+ * or the measures of STORM_*_pairw_similarity as float (same n_bits rule, bit-identical to the same pairs of those calls).
+ * A STORM_t always runs on its dense replica here (there is no list-join form). One device slot and one process.
+ * Returns 0; -1 NULL handle, -2 NULL out, -4 out_rows < n or out_ld < L (nothing is written), -3 device failure, bad op,
+ * measure or n_bits, or max_lag 0 (STORM_hip_error says which), -5 several device slots in view. Fewer than two rows: 0,
+ * nothing written. */
+int STORM_contig_pairw_lag_matrix(STORM_contiguous_t* bitmap, int op, uint64_t max_lag, uint32_t* out, uint64_t out_rows,
+                                  uint64_t out_ld);
+int STORM_contig_pairw_lag_matrix_device(STORM_contiguous_t* bitmap, int op, uint64_t max_lag, uint32_t* d_out,
+                                         uint64_t out_rows, uint64_t out_ld);
+int STORM_contig_pairw_lag_similarity(STORM_contiguous_t* bitmap, int measure, uint64_t n_bits, uint64_t max_lag, float* out,
+                                      uint64_t out_rows, uint64_t out_ld);
+int STORM_contig_pairw_lag_similarity_device(STORM_contiguous_t* bitmap, int measure, uint64_t n_bits, uint64_t max_lag,
+                                             float* d_out, uint64_t out_rows, uint64_t out_ld);
+int STORM_pairw_lag_matrix(STORM_t* bitmap, int op, uint64_t max_lag, uint32_t* out, uint64_t out_rows, uint64_t out_ld);
+int STORM_pairw_lag_matrix_device(STORM_t* bitmap, int op, uint64_t max_lag, uint32_t* d_out, uint64_t out_rows,
+                                  uint64_t out_ld);
+int STORM_pairw_lag_similarity(STORM_t* bitmap, int measure, uint64_t n_bits, uint64_t max_lag, float* out, uint64_t out_rows,
+                               uint64_t out_ld);
+int STORM_pairw_lag_similarity_device(STORM_t* bitmap, int measure, uint64_t n_bits, uint64_t max_lag, float* d_out,
+                                      uint64_t out_rows, uint64_t out_ld);
+
 /* ------------------------------------------------------------- extensions (not in ref) ---
  * Device selection for the entry points above. By default device 0 computes everything.
  * STORM_hip_set_devices(n, ids): the pair space is sharded over the listed GPUs of this node

@@ -221,6 +221,41 @@ int storm_hip_cross_dense_similarity_device(storm_hip_ctx_t* ctx, const storm_hi
 int storm_hip_cross_dense_similarity(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b,
                                      int measure, uint64_t n_bits, float* h_out, uint64_t ld);
 
+/* ---- the lag layout: every row against the next max_lag rows ------------------------------------------------
+ * Linkage disequilibrium (what the per-pair counts are for) is rarely wanted all-vs-all: pruning, clumping, r^2 decay and
+ * banded LD matrices ask for row i against the next w rows in container order. The lag of a pair i < j is j - i; with
+ * L = min(max_lag, n_rows - 1) the lag layout of an n_rows x ld matrix (ld >= L) holds the pair (i, j), 1 <= j - i <= L, at
+ *   out[i * ld + (j - i - 1)]          (column d of row i is the pair (i, i + 1 + d)):
+ * n x L entries instead of n x n, and only the 128 x 128 tiles within L rows of the diagonal are multiplied (always K2h,
+ * tile128_kernel in its lag form, whatever k2_tile_shape says). Entries with i + 1 + d >= n_rows (the
+ * lower-right corner) and the pitch columns [L, ld) are not part of the output.
+ * _lag_matrix_device: counts under `op` into DEVICE memory; the row band [row0, row0 + n_band_rows) (n_band_rows = ~0: all
+ *   rows from row0) is written from output row 0: d_out[(i - row0) * ld + (j - i - 1)]. Complete on return, like
+ *   storm_hip_pairw_matrix_band_device. Entries outside the layout stay untouched.
+ * _lag_matrix: all rows into HOST memory, h_out[i * ld + d]: columns [0, L) of every row are written, 0 in the corner;
+ *   columns [L, ld) stay untouched (the n x L device matrix in between is the context's band buffer).
+ * _similarity_finish_lag_device: the in-place uint32 -> float pass (see storm_hip_similarity_finish_device) over a count
+ *   matrix in the lag layout: entry (i - row0, d) from d_counts[i] and d_counts[i + 1 + d] (d_counts: n_rows set-bit counts,
+ *   device). Asynchronous on the context's stream (similarity_finish_lag_kernel); alone the last-pass report is
+ *   STORM_HIP_RAN_SIMILARITY.
+ * _lag_similarity_device / _lag_similarity: the AND counts, the rows' counts, then that pass; complete on return; host form:
+ *   +0.0f in the corner. Bit-identical to the same pairs of storm_hip_pairw_similarity.
+ * STORM_HIP_EINVAL: NULL argument, unknown op or measure, bad n_bits, max_lag 0, ld < L, a band outside the rows, rows beyond
+ * K2h's reach (row pitch x 128 >= 2^32 bytes, more than 65535 tiles of 128 rows). Fewer than two rows or an empty band:
+ * STORM_HIP_OK, nothing written. Last-pass report: STORM_HIP_RAN_TILES_OUT (| STORM_HIP_RAN_SIMILARITY), [1] = the band's
+ * pairs within the lag x n_words. */
+int storm_hip_pairw_lag_matrix_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int op, uint64_t max_lag,
+                                      uint64_t row0, uint64_t n_band_rows, uint32_t* d_out, uint64_t ld);
+int storm_hip_pairw_lag_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int op, uint64_t max_lag, uint32_t* h_out,
+                               uint64_t ld);
+int storm_hip_similarity_finish_lag_device(storm_hip_ctx_t* ctx, void* d_io, uint64_t ld, uint64_t n_rows, uint64_t row0,
+                                           uint64_t n_band_rows, uint64_t max_lag, const uint32_t* d_counts, int measure,
+                                           uint64_t n_bits);
+int storm_hip_pairw_lag_similarity_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_bits,
+                                          uint64_t max_lag, float* d_out, uint64_t ld);
+int storm_hip_pairw_lag_similarity(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_bits,
+                                   uint64_t max_lag, float* h_out, uint64_t ld);
+
 /* sum_c C(n_c,2) on the device — verification identity only, never the product
  * path: used by tests at sizes where a CPU pairwise oracle is infeasible */
 int storm_hip_column_identity(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m,
@@ -346,6 +381,13 @@ int storm_hip_strip_plan3(uint64_t n_rows, uint32_t n_words, uint32_t shard_rank
 int storm_hip_matrix_plan(uint64_t n_rows_a, uint64_t n_rows_b, uint32_t n_words, uint64_t band_row0, uint64_t band_rows,
                           uint32_t n_cus, int slots_per_cu, int min_chunks, int diag_cost_pct, uint32_t* out,
                           uint64_t capacity_items, uint64_t* n_items);
+
+/* The K2h list of the lag layout (storm_hip_pairw_lag_matrix_device): the same records for the triangle's tiles (I, J) that
+ * hold a pair with j - i <= L = min(max_lag, n_rows - 1), I <= J <= (128 I + 127 + L) / 128; band_rows == 0: all rows.
+ * max_lag >= n_rows - 1 lists what storm_hip_matrix_plan lists for the triangle. Host only; `out` may be NULL. */
+int storm_hip_lag_plan(uint64_t n_rows, uint32_t n_words, uint64_t max_lag, uint64_t band_row0, uint64_t band_rows,
+                       uint32_t n_cus, int slots_per_cu, int min_chunks, int diag_cost_pct, uint32_t* out,
+                       uint64_t capacity_items, uint64_t* n_items);
 
 /* The same for the one-launch stage stream on bit operands (K2q, the default for matrices of up to 8192
  * rows on one device): the segments shard `shard_rank` of `shard_count` walks on a device of

@@ -33,6 +33,47 @@ def _similarity(lib, what: str, rc: int) -> None:
         raise RuntimeError(f"{what} -> {rc}: {lib.STORM_hip_error().decode()}")
 
 
+OPS = {"and": 0, "or": 1, "xor": 2}
+
+
+class _LagForms:
+    """The lag-layout calls of a storm.h container (extension; `_LAG` = the C prefix, STORM_contig_ or STORM_): the pairs
+    within max_lag rows of each other, pair (i, j) at [i, j - i - 1] of an [n_rows, L] matrix, L = min(max_lag, n_rows - 1)."""
+
+    def _lag_width(self, max_lag: int) -> int:
+        return min(max_lag, max(self.n_rows - 1, 0))
+
+    def pairw_lag_matrix(self, max_lag: int, op: str = "and") -> np.ndarray:
+        """[n_rows, L] uint32: entry (i, d) = popcount(row_i OP row_{i+1+d}); 0 where i + 1 + d >= n_rows."""
+        n, w = self.n_rows, self._lag_width(max_lag)
+        out = np.zeros((n, w), dtype=np.uint32)
+        name = self._LAG + "pairw_lag_matrix"
+        _similarity(self._lib, name, int(getattr(self._lib, name)(self._h, OPS[op], max_lag,
+                                                                  _ptr(out) if out.size else _ptr(np.zeros(1, np.uint32)), n, w)))
+        return out
+
+    def pairw_lag_matrix_device(self, d_out: int, out_rows: int, out_ld: int, max_lag: int, op: str = "and") -> None:
+        """The same left in device memory at address d_out (out_rows x out_ld uint32; nothing outside the layout is written)."""
+        name = self._LAG + "pairw_lag_matrix_device"
+        _similarity(self._lib, name, int(getattr(self._lib, name)(self._h, OPS[op], max_lag, C.c_void_p(d_out), out_rows, out_ld)))
+
+    def pairw_lag_similarity(self, max_lag: int, measure: str = "jaccard", n_bits: int = 0) -> np.ndarray:
+        """[n_rows, L] float32: entry (i, d) = the measure of rows i and i + 1 + d (as pairw_similarity); 0 in the corner."""
+        n, w = self.n_rows, self._lag_width(max_lag)
+        out = np.zeros((n, w), dtype=np.float32)
+        name = self._LAG + "pairw_lag_similarity"
+        _similarity(self._lib, name, int(getattr(self._lib, name)(self._h, MEASURES[measure], n_bits, max_lag,
+                                                                  _ptr(out) if out.size else _ptr(np.zeros(1, np.float32)), n, w)))
+        return out
+
+    def pairw_lag_similarity_device(self, d_out: int, out_rows: int, out_ld: int, max_lag: int, measure: str = "jaccard",
+                                    n_bits: int = 0) -> None:
+        """The same left in device memory at address d_out (out_rows x out_ld float32)."""
+        name = self._LAG + "pairw_lag_similarity_device"
+        _similarity(self._lib, name, int(getattr(self._lib, name)(self._h, MEASURES[measure], n_bits, max_lag, C.c_void_p(d_out),
+                                                                  out_rows, out_ld)))
+
+
 def _all_pairs(value: int, what: str) -> int:
     if value == ALL_PAIRS_FAILED:
         lib = _lib.load()
@@ -44,8 +85,9 @@ def _all_pairs(value: int, what: str) -> int:
 # ------------------------------------------------------------------------------------------
 # storm.h containers
 # ------------------------------------------------------------------------------------------
-class StormContig:
+class StormContig(_LagForms):
     """STORM_contiguous_t (storm.h:188-200, :235-242): dense row-major bitmap matrix."""
+    _LAG = "STORM_contig_"
 
     def __init__(self, vector_length: int):
         self._lib = _lib.load()
@@ -145,8 +187,9 @@ class StormContig:
             pass
 
 
-class Storm:
+class Storm(_LagForms):
     """STORM_t (storm.h:175-178, :225-232): rows of 65536-bit blocks, list or bitmap kind."""
+    _LAG = "STORM_"
 
     def __init__(self):
         self._lib = _lib.load()
@@ -527,6 +570,51 @@ class HipMatrix:
         check(self._lib.storm_hip_pairw_matrix_band_device(self.ctx._h, self._h, self.OPS[op], row0,
                                                            n_band_rows, C.c_void_p(d_out), ld),
               "storm_hip_pairw_matrix_band_device")
+
+    def _lag_width(self, max_lag: int) -> int:
+        return min(max_lag, max(self.n_rows - 1, 0))
+
+    def pairw_lag_matrix(self, max_lag: int, op: str = "and") -> np.ndarray:
+        """[n_rows, L] uint32, L = min(max_lag, n_rows - 1): entry (i, d) = popcount(row_i OP row_{i+1+d}), 0 where
+        i + 1 + d >= n_rows (the lag layout of storm_hip.h)."""
+        w = self._lag_width(max_lag)
+        out = np.zeros((self.n_rows, w), dtype=np.uint32)
+        check(self._lib.storm_hip_pairw_lag_matrix(self.ctx._h, self._h, self.OPS[op], max_lag,
+                                                   _ptr(out) if out.size else _ptr(np.zeros(1, np.uint32)), w),
+              "storm_hip_pairw_lag_matrix")
+        return out
+
+    def pairw_lag_matrix_device(self, d_out: int, ld: int, max_lag: int, op: str = "and", row0: int = 0,
+                                n_band_rows: Optional[int] = None) -> None:
+        """Same, rows [row0, row0 + n_band_rows) (None: all) into a device buffer (n_band_rows x ld uint32); synchronous."""
+        check(self._lib.storm_hip_pairw_lag_matrix_device(self.ctx._h, self._h, self.OPS[op], max_lag, row0,
+                                                          (1 << 64) - 1 if n_band_rows is None else n_band_rows,
+                                                          C.c_void_p(d_out), ld),
+              "storm_hip_pairw_lag_matrix_device")
+
+    def pairw_lag_similarity(self, max_lag: int, measure: str = "jaccard", n_bits: int = 1) -> np.ndarray:
+        """[n_rows, L] float32: the measure of rows i and i + 1 + d, +0.0 in the corner."""
+        w = self._lag_width(max_lag)
+        out = np.zeros((self.n_rows, w), dtype=np.float32)
+        check(self._lib.storm_hip_pairw_lag_similarity(self.ctx._h, self._h, MEASURES[measure], n_bits, max_lag,
+                                                       _ptr(out) if out.size else _ptr(np.zeros(1, np.float32)), w),
+              "storm_hip_pairw_lag_similarity")
+        return out
+
+    def pairw_lag_similarity_device(self, d_out: int, ld: int, max_lag: int, measure: str = "jaccard", n_bits: int = 1) -> None:
+        """Same, into a device buffer (n_rows x ld float32); complete on return."""
+        check(self._lib.storm_hip_pairw_lag_similarity_device(self.ctx._h, self._h, MEASURES[measure], n_bits, max_lag,
+                                                              C.c_void_p(d_out), ld),
+              "storm_hip_pairw_lag_similarity_device")
+
+    def similarity_finish_lag_device(self, d_io: int, ld: int, max_lag: int, d_counts: int, measure: str = "jaccard",
+                                     n_bits: int = 1, row0: int = 0, n_band_rows: Optional[int] = None) -> None:
+        """The finish pass alone over a count matrix in the lag layout at d_io (d_counts: n_rows uint32 set-bit counts on the
+        device); asynchronous on the context's stream."""
+        check(self._lib.storm_hip_similarity_finish_lag_device(self.ctx._h, C.c_void_p(d_io), ld, self.n_rows, row0,
+                                                               (1 << 64) - 1 if n_band_rows is None else n_band_rows, max_lag,
+                                                               C.c_void_p(d_counts), MEASURES[measure], n_bits),
+              "storm_hip_similarity_finish_lag_device")
 
     def row_counts(self) -> np.ndarray:
         out = np.zeros(self.n_rows, dtype=np.uint32)

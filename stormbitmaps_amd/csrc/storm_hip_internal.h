@@ -272,6 +272,9 @@ static inline uint64_t ranges_word_pairs(const std::vector<RowRange>& ranges, ui
 int launch_pairw_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int op, uint32_t* d_out,
                         uint64_t ld, uint64_t band_row0 = 0, uint64_t band_rows = ~0ull,
                         bool sync = true);
+// the same for the pairs within max_lag rows of each other, in the lag layout (n x L instead of n x n): always K2h
+int launch_pairw_lag_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int op, uint64_t max_lag, uint64_t band_row0,
+                            uint64_t band_rows, uint32_t* d_out, uint64_t ld, bool sync);
 int launch_square_mfma(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
                        const storm_hip_matrix_s* b, uint64_t* d_total);
 int launch_square_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
@@ -283,6 +286,9 @@ int launch_row_counts(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint32_
 int launch_similarity_finish(storm_hip_ctx_t* ctx, void* d_io, uint64_t ld, uint64_t n_rows, uint64_t n_cols,
                              const uint32_t* d_counts_rows, const uint32_t* d_counts_cols, int triangle, int measure,
                              uint64_t n_bits);
+// similarity_finish_lag_kernel: the same pass over the lag layout (rows [row0, row0 + n_band_rows) from output row 0)
+int launch_similarity_finish_lag(storm_hip_ctx_t* ctx, void* d_io, uint64_t ld, uint64_t n_rows, uint64_t row0,
+                                 uint64_t n_band_rows, uint64_t max_lag, const uint32_t* d_counts, int measure, uint64_t n_bits);
 void release_mfma_state(storm_hip_ctx_t* ctx);
 // releases what was put off (storm_hip_ctx_s::deferred_free); `aged`: only what an earlier call left behind
 void drain_deferred(storm_hip_ctx_t* ctx, bool aged);

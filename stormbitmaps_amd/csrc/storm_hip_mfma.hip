@@ -2127,18 +2127,19 @@ static bool choose_tile128(const storm_hip_ctx_t* ctx, uint64_t tiles256, uint64
 }
 
 // Plans the K2h list (plan_tile128, storm_hip_plan.cpp; cached by its request while the same call repeats), uploads it
-// and launches tile128_kernel.
+// and launches tile128_kernel. lag != 0 (triangle only): the lag form — the tiles within `lag` rows of the diagonal, written
+// in the lag layout (j_base and j_count must be 0: the kernel takes the lag where the rectangle's column count travels).
 static int run_tile128(storm_hip_ctx_t* ctx, uint32_t ia0, uint32_t ia1, uint32_t jb0, uint32_t jb1, bool triangle,
                        uint32_t total_stages, const TileOperands& ops, uint32_t* d_out, uint64_t ld, uint32_t n_rows,
                        const uint32_t* d_counts, uint32_t and_weight, uint32_t j_base, uint32_t j_count, uint32_t i_lo,
-                       uint32_t n_cols, bool sync) {
+                       uint32_t n_cols, bool sync, uint32_t lag = 0u) {
     if (ia1 > 65535u || jb1 > 65535u) {
         set_error("pairw_matrix: too many row blocks");
         return STORM_HIP_EINVAL;
     }
     const Tile128Request rq = {ia0, ia1, jb0, jb1, triangle ? 1u : 0u, total_stages, (uint32_t)std::max(1, ctx->n_cus),
                                ctx->k2_part_slots, ctx->k2_part_min_chunks, ctx->k2_part_cost_diag,
-                               ctx->k2_part_narrow != 0 ? 1u : 0u};
+                               ctx->k2_part_narrow != 0 ? 1u : 0u, lag};
     const Tile128Request* have = std::get_if<Tile128Request>(&ctx->items_key);
     if (!(ctx->d_items && have && *have == rq)) {
         Tile128Plan plan;
@@ -2167,8 +2168,12 @@ static int run_tile128(storm_hip_ctx_t* ctx, uint32_t ia0, uint32_t ia1, uint32_
         STORM_HIP_TRY(hipMemsetAsync(ctx->d_tickets, 0, ctx->d_tickets.capacity, ctx->stream));
         ctx->tickets_dirty = false;
     }
-    if (ctx->n_part_items)
-        hipLaunchKernelGGL(tile128_kernel, dim3(ctx->n_part_items), dim3(kThThreads), 0, ctx->stream, ops,
+    if (ctx->n_part_items && lag)
+        hipLaunchKernelGGL(tile128_kernel<true>, dim3(ctx->n_part_items), dim3(kThThreads), 0, ctx->stream, ops,
+                           static_cast<const PartItem*>(ctx->d_items.d), d_out, ld, n_rows, d_counts, and_weight, 0u, lag, i_lo,
+                           n_cols, ctx->d_parts, ctx->d_tickets);
+    else if (ctx->n_part_items)
+        hipLaunchKernelGGL(tile128_kernel<false>, dim3(ctx->n_part_items), dim3(kThThreads), 0, ctx->stream, ops,
                            static_cast<const PartItem*>(ctx->d_items.d), d_out, ld, n_rows, d_counts, and_weight, j_base,
                            j_count, i_lo, n_cols, ctx->d_parts, ctx->d_tickets);
     if (hipGetLastError() != hipSuccess) {
@@ -2293,6 +2298,54 @@ int launch_pairw_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int o
                               (uint32_t)m->n_rows, sync, bits ? &ops : nullptr);
     }
     if (rc == STORM_HIP_EHIP) set_error("pairw_matrix: HIP failure");
+    return rc;
+}
+
+// The triangle's pairs within max_lag rows of each other, in the lag layout: out[(i - band_row0) * ld + (j - i - 1)] =
+// popcount(row_i OP row_j) for band_row0 <= i < band_row0 + band_rows, i < j < n_rows, j - i <= L = min(max_lag, n_rows - 1)
+// (device pointer, uint32, ld >= L). Always K2h (tile128_kernel<true>): the tile list follows the diagonal, whatever
+// k2_tile_shape says; nothing outside the layout is written.
+int launch_pairw_lag_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int op, uint64_t max_lag, uint64_t band_row0,
+                            uint64_t band_rows, uint32_t* d_out, uint64_t ld, bool sync) {
+    const uint64_t n = m->n_rows;
+    const uint64_t band_end = std::min<uint64_t>(n, band_row0 + std::min<uint64_t>(band_rows, n));
+    if (n < 2 || band_row0 >= band_end || max_lag == 0) return STORM_HIP_OK;
+    const uint64_t L = std::min<uint64_t>(max_lag, n - 1);
+    const uint64_t pitch = m->stride_words * 8;
+    if (pitch * 128u >= (1ull << 32)) {
+        set_error("pairw_lag_matrix: rows of %llu operand bytes exceed the tile kernel's 32-bit DMA offsets",
+                  (unsigned long long)pitch);
+        return STORM_HIP_EINVAL;
+    }
+    if ((n + kThTile - 1) / kThTile > 65535u) {
+        set_error("pairw_lag_matrix: too many row blocks");
+        return STORM_HIP_EINVAL;
+    }
+    // pairs (i, j) of the band within the lag: row i has min(L, n - 1 - i) of them
+    auto pairs_below = [&](uint64_t r) {   // ... of the rows [0, r)
+        const uint64_t full = std::min(r, n - L);            // rows with all L partners
+        const uint64_t rest = r - full;                      // rows n - L + t, t < rest: L - t partners
+        return full * L + rest * L - rest * (rest + 1) / 2;
+    };
+    ctx->k2_tile_shape_eff = 6;
+    ctx->pass_report[0] = STORM_HIP_RAN_TILES_OUT;
+    ctx->pass_report[1] = (pairs_below(band_end) - pairs_below(band_row0)) * m->n_words;
+    ctx->pass_report[2] = ctx->pass_report[3] = 0;
+    uint32_t* d_counts = nullptr;
+    int rc = STORM_HIP_OK;
+    if (op != STORM_HIP_OP_AND) {
+        rc = ensure_counts_scratch(ctx, n, &d_counts);
+        if (rc == STORM_HIP_OK) rc = launch_row_counts(ctx, m, d_counts);
+    }
+    if (rc == STORM_HIP_OK) {
+        const TileOperands ops = {reinterpret_cast<const uint8_t*>(m->d), nullptr, pitch, 0xffffffffu,
+                                  (uint32_t)std::min<uint64_t>(m->n_rows_pad, 0xffffffffu), 0u};
+        rc = run_tile128(ctx, (uint32_t)(band_row0 / kThTile), (uint32_t)((band_end + kThTile - 1) / kThTile), 0u,
+                         (uint32_t)((n + kThTile - 1) / kThTile), true, (m->n_words + 7u) / 8u * 4u, ops, d_out, ld,
+                         (uint32_t)band_end, d_counts, op == STORM_HIP_OP_XOR ? 2u : 1u, 0u, 0u, (uint32_t)band_row0, (uint32_t)n,
+                         sync, (uint32_t)L);
+    }
+    if (rc == STORM_HIP_EHIP) set_error("pairw_lag_matrix: HIP failure");
     return rc;
 }
 

@@ -490,6 +490,8 @@ void plan_tile128(const Tile128Request& rq, Tile128Plan* plan) {
                 for (uint32_t i = gi; i < std::min(gi + 4, ia1); ++i)
                     for (uint32_t j = gj; j < std::min(gj + 8, jb1); ++j) {
                         if (triangle && j < i) continue;
+                        // lag limit: the tile's nearest pair is (128 i + 127, 128 j): j <= (128 i + 127 + lag) / 128
+                        if (triangle && rq.lag && (uint64_t)j > ((uint64_t)kThTile * i + kThTile - 1u + rq.lag) / kThTile) continue;
                         const bool diag = triangle && j == i;
                         if (diag != (pass == 1)) continue;
                         tiles.push_back({(uint16_t)i, (uint16_t)j, diag});
@@ -1224,6 +1226,26 @@ bool stage_list_readable(const std::vector<uint64_t>& written, uint64_t token, u
 
 }  // namespace storm
 
+// a K2h list as the 8-word records of storm_hip_matrix_plan / storm_hip_lag_plan (out == NULL: the count alone)
+static int export_part_items(const char* who, const storm::Tile128Plan& plan, uint32_t* out, uint64_t capacity_items,
+                             uint64_t* n_items) {
+    using namespace storm;
+    *n_items = plan.items.size();
+    if (out) {
+        if (capacity_items < plan.items.size()) {
+            set_error("%s: capacity %llu < %zu items", who, (unsigned long long)capacity_items, plan.items.size());
+            return STORM_HIP_EINVAL;
+        }
+        for (size_t k = 0; k < plan.items.size(); ++k) {
+            const PartItem& it = plan.items[k];
+            uint32_t* o = out + 8 * k;
+            o[0] = it.I, o[1] = it.J, o[2] = it.stage0 / 4u, o[3] = it.n_stages / 4u, o[4] = it.tile;
+            o[5] = (uint32_t)(it.part & (uint16_t)~kThNarrow), o[6] = it.n_parts, o[7] = (it.part & kThNarrow) ? 1u : 0u;
+        }
+    }
+    return STORM_HIP_OK;
+}
+
 // Host-only view of the default path's work decomposition (no device is touched): what a shard
 // of a multi-GPU run multiplies, so that the partition of the pair space can be checked — and
 // rehearsed with CPU partials — without a GPU (tests/test_dist_cpu.py).
@@ -1244,29 +1266,41 @@ extern "C" int storm_hip_matrix_plan(uint64_t n_rows_a, uint64_t n_rows_b, uint3
             if (band_row0 < end)
                 plan_tile128({(uint32_t)(band_row0 / kThTile), (uint32_t)((end + kThTile - 1) / kThTile), 0u,
                               (uint32_t)((n_rows_a + kThTile - 1) / kThTile), 1u, total_stages, n_cus, slots_per_cu, min_chunks,
-                              diag_cost_pct, 1u}, &plan);
+                              diag_cost_pct, 1u, 0u}, &plan);
         } else {   // rectangle: B's tiles count on behind A's rows padded to 256
             const uint64_t rows_a = (n_rows_a + kTile - 1) / kTile * kTile;
             plan_tile128({0u, (uint32_t)((n_rows_a + kThTile - 1) / kThTile), (uint32_t)(rows_a / kThTile),
                           (uint32_t)((rows_a + n_rows_b + kThTile - 1) / kThTile), 0u, total_stages, n_cus, slots_per_cu,
-                          min_chunks, diag_cost_pct, 1u}, &plan);
+                          min_chunks, diag_cost_pct, 1u, 0u}, &plan);
         }
-        *n_items = plan.items.size();
-        if (out) {
-            if (capacity_items < plan.items.size()) {
-                set_error("matrix_plan: capacity %llu < %zu items", (unsigned long long)capacity_items, plan.items.size());
-                return STORM_HIP_EINVAL;
-            }
-            for (size_t k = 0; k < plan.items.size(); ++k) {
-                const PartItem& it = plan.items[k];
-                uint32_t* o = out + 8 * k;
-                o[0] = it.I, o[1] = it.J, o[2] = it.stage0 / 4u, o[3] = it.n_stages / 4u, o[4] = it.tile;
-                o[5] = (uint32_t)(it.part & (uint16_t)~kThNarrow), o[6] = it.n_parts, o[7] = (it.part & kThNarrow) ? 1u : 0u;
-            }
-        }
-        return STORM_HIP_OK;
+        return export_part_items("matrix_plan", plan, out, capacity_items, n_items);
     } catch (const std::exception& e) {
         set_error("matrix_plan: %s", e.what());
+        return STORM_HIP_ENOMEM;
+    }
+}
+
+// The K2h list of the lag layout (launch_pairw_lag_matrix): the triangle's tiles that hold a pair within max_lag rows.
+extern "C" int storm_hip_lag_plan(uint64_t n_rows, uint32_t n_words, uint64_t max_lag, uint64_t band_row0, uint64_t band_rows,
+                                  uint32_t n_cus, int slots_per_cu, int min_chunks, int diag_cost_pct, uint32_t* out,
+                                  uint64_t capacity_items, uint64_t* n_items) {
+    using namespace storm;
+    if (!n_items || n_rows == 0 || n_words == 0 || max_lag == 0 || n_cus == 0 || slots_per_cu < 0 || slots_per_cu > 2 ||
+        min_chunks < 1 || diag_cost_pct < 10 || diag_cost_pct > 100 || (n_rows + kThTile - 1) / kThTile > 65535u) {
+        set_error("lag_plan: bad arguments");
+        return STORM_HIP_EINVAL;
+    }
+    try {
+        Tile128Plan plan;
+        const uint64_t end = std::min(n_rows, band_row0 + std::min(band_rows ? band_rows : n_rows, n_rows));
+        const uint32_t lag = (uint32_t)std::min<uint64_t>(max_lag, n_rows - 1);
+        if (band_row0 < end && lag)
+            plan_tile128({(uint32_t)(band_row0 / kThTile), (uint32_t)((end + kThTile - 1) / kThTile), 0u,
+                          (uint32_t)((n_rows + kThTile - 1) / kThTile), 1u, (n_words + 7u) / 8u * 4u, n_cus, slots_per_cu,
+                          min_chunks, diag_cost_pct, 1u, lag}, &plan);
+        return export_part_items("lag_plan", plan, out, capacity_items, n_items);
+    } catch (const std::exception& e) {
+        set_error("lag_plan: %s", e.what());
         return STORM_HIP_ENOMEM;
     }
 }

@@ -184,6 +184,7 @@ struct Tile128Request {
     uint32_t n_cus;
     int32_t slots_per_cu, min_chunks, diag_cost_pct;   // options k2_part_slots, k2_part_min_chunks, k2_part_cost_diag
     uint32_t narrow_windows;                           // option k2_part_narrow
+    uint32_t lag;   // 0: none. Triangle only: just the tiles that hold a pair i < j with j - i <= lag (the lag layout's list)
     bool operator==(const Tile128Request& o) const { return same_request(*this, o); }
 };
 struct Tile128Plan {

@@ -106,6 +106,96 @@ int launch_similarity_finish(storm_hip_ctx_t* ctx, void* d_io, uint64_t ld, uint
     return STORM_HIP_OK;
 }
 
+// The same pass over the LAG layout (storm_hip_pairw_lag_matrix_device): entry (r, d) of the band is the pair (i, i + 1 + d),
+// i = row0 + r, so a tile of kSimTileRows x kSimTileCols entries reads the counts of its 64 rows and of the 64 + 256 - 1 rows
+// i0 + 1 + col0 .. behind them: both staged once per workgroup. Only entries with d < lag and i + 1 + d < n_rows are
+// touched (the lower-right corner and the pitch columns are neither read nor written); a lane's 4 entries are one
+// 128-bit access where all 4 are converted and `vec` (base 16-byte aligned, ld a multiple of 4), else entry by entry.
+__global__ __launch_bounds__(kSimThreads) void similarity_finish_lag_kernel(uint32_t* __restrict__ io, uint64_t ld, uint64_t n_rows,
+                                                                            uint64_t row0, uint64_t band_end, uint64_t lag,
+                                                                            const uint32_t* __restrict__ counts, int measure,
+                                                                            uint64_t n_bits, int vec) {
+    const uint64_t i0 = row0 + (uint64_t)blockIdx.y * kSimTileRows, col0 = (uint64_t)blockIdx.x * kSimTileCols;
+    if (i0 + 1 + col0 >= n_rows) return;   // the tile's first pair is already in the corner
+    __shared__ uint32_t s_rows[kSimTileRows];
+    __shared__ uint32_t s_cols[kSimTileRows + kSimTileCols];
+    if (threadIdx.x < kSimTileRows) s_rows[threadIdx.x] = i0 + threadIdx.x < band_end ? counts[i0 + threadIdx.x] : 0u;
+    for (uint32_t k = threadIdx.x; k < kSimTileRows + kSimTileCols; k += kSimThreads)
+        s_cols[k] = i0 + 1 + col0 + k < n_rows ? counts[i0 + 1 + col0 + k] : 0u;
+    __syncthreads();
+    const uint32_t lane4 = (threadIdx.x & 63u) * 4u;
+    const uint64_t c0 = col0 + lane4;
+    const uint32_t wave = threadIdx.x >> 6;
+    for (uint32_t r = wave; r < kSimTileRows; r += 4 * kSimUnroll) {
+        uint4 v[kSimUnroll];
+        bool whole[kSimUnroll];
+#pragma unroll
+        for (int u = 0; u < kSimUnroll; ++u) {   // the loads of kSimUnroll rows leave before the first divide
+            const uint64_t i = i0 + r + 4u * u;
+            whole[u] = vec && i < band_end && c0 + 4 <= lag && i + 1 + c0 + 3 < n_rows;
+            if (whole[u]) v[u] = *reinterpret_cast<const uint4*>(io + (i - row0) * ld + c0);
+        }
+#pragma unroll
+        for (int u = 0; u < kSimUnroll; ++u) {
+            const uint32_t rr = r + 4u * u;
+            const uint64_t i = i0 + rr;
+            if (i >= band_end) continue;
+            const uint32_t a = s_rows[rr];
+            const uint32_t* const b = &s_cols[rr + lane4];   // entry d = c0 + k: row i + 1 + c0 + k
+            uint32_t* const p = io + (i - row0) * ld + c0;
+            if (whole[u]) {
+                uint4 w;
+                w.x = similarity_bits(v[u].x, a, b[0], measure, n_bits);
+                w.y = similarity_bits(v[u].y, a, b[1], measure, n_bits);
+                w.z = similarity_bits(v[u].z, a, b[2], measure, n_bits);
+                w.w = similarity_bits(v[u].w, a, b[3], measure, n_bits);
+                *reinterpret_cast<uint4*>(p) = w;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (c0 + k < lag && i + 1 + c0 + k < n_rows) p[k] = similarity_bits(p[k], a, b[k], measure, n_bits);
+            }
+        }
+    }
+}
+
+int launch_similarity_finish_lag(storm_hip_ctx_t* ctx, void* d_io, uint64_t ld, uint64_t n_rows, uint64_t row0,
+                                 uint64_t n_band_rows, uint64_t max_lag, const uint32_t* d_counts, int measure, uint64_t n_bits) {
+    if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+    if (!d_io || !d_counts) {
+        set_error("similarity_finish_lag: NULL argument");
+        return STORM_HIP_EINVAL;
+    }
+    if (measure < STORM_HIP_SIM_JACCARD || measure > STORM_HIP_SIM_LD_R2) {
+        set_error("similarity_finish_lag: unknown measure %d (0 Jaccard, 1 cosine, 2 LD D, 3 LD r^2)", measure);
+        return STORM_HIP_EINVAL;
+    }
+    if (n_bits == 0 || n_bits > (1ull << 32)) {
+        set_error("similarity_finish_lag: n_bits %llu is not in [1, 2^32]", (unsigned long long)n_bits);
+        return STORM_HIP_EINVAL;
+    }
+    if (n_band_rows == ~0ull && row0 <= n_rows) n_band_rows = n_rows - row0;
+    const uint64_t lag = n_rows ? std::min(max_lag, n_rows - 1) : 0;
+    if (max_lag == 0 || row0 > n_rows || n_band_rows > n_rows - row0 || ld < lag) {
+        set_error("similarity_finish_lag: max_lag 0, a band outside the rows, or leading dimension < min(max_lag, rows - 1)");
+        return STORM_HIP_EINVAL;
+    }
+    if (n_rows < 2 || n_band_rows == 0) return STORM_HIP_OK;
+    const uint64_t tiles_x = (lag + kSimTileCols - 1) / kSimTileCols, tiles_y = (n_band_rows + kSimTileRows - 1) / kSimTileRows;
+    if (tiles_y > 65535u || tiles_x > 0x7fffffffu) {
+        set_error("similarity_finish_lag: %llu x %llu entries exceed the launch grid", (unsigned long long)n_band_rows,
+                  (unsigned long long)lag);
+        return STORM_HIP_EINVAL;
+    }
+    STORM_HIP_TRY(hipSetDevice(ctx->device));
+    const int vec = reinterpret_cast<uintptr_t>(d_io) % 16 == 0 && ld % 4 == 0;
+    hipLaunchKernelGGL(similarity_finish_lag_kernel, dim3((uint32_t)tiles_x, (uint32_t)tiles_y), dim3(kSimThreads), 0, ctx->stream,
+                       static_cast<uint32_t*>(d_io), ld, n_rows, row0, row0 + n_band_rows, lag, d_counts, measure, n_bits, vec);
+    STORM_HIP_TRY(hipGetLastError());
+    ctx->pass_report[0] |= STORM_HIP_RAN_SIMILARITY;
+    return STORM_HIP_OK;
+}
+
 // the row counts of `m` into the context's scratch at word `at` (ensured by the caller)
 static int counts_of(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint64_t at) {
     return launch_row_counts(ctx, m, ctx->d_counts.d + at);
@@ -208,6 +298,124 @@ int storm_hip_pairw_similarity(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m
         if (n >= 2)
             if (int rc = finish_dense(ctx, m, m, ctx->d_band, n, 1, measure, n_bits)) return rc;
         STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(float), ctx->d_band, n * sizeof(uint32_t), n * sizeof(uint32_t), n,
+                                       hipMemcpyDeviceToHost, ctx->stream));
+        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return STORM_HIP_OK;
+    });
+}
+
+// ---- the lag layout (storm_hip.h): row i against the next L = min(max_lag, rows - 1) rows, an n x L matrix ----
+// what the lag calls refuse alike; *lag = L (0 for an empty matrix)
+static int check_lag(const char* who, const storm_hip_matrix_t* m, const void* out, uint64_t max_lag, uint64_t ld, uint64_t* lag) {
+    if (!m || !out || max_lag == 0) {
+        set_error("%s: NULL argument or max_lag 0", who);
+        return STORM_HIP_EINVAL;
+    }
+    *lag = m->n_rows ? std::min(max_lag, m->n_rows - 1) : 0;
+    if (ld < *lag) {
+        set_error("%s: leading dimension %llu < min(max_lag, rows - 1) = %llu", who, (unsigned long long)ld, (unsigned long long)*lag);
+        return STORM_HIP_EINVAL;
+    }
+    return STORM_HIP_OK;
+}
+
+int storm_hip_pairw_lag_matrix_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int op, uint64_t max_lag, uint64_t row0,
+                                      uint64_t n_band_rows, uint32_t* d_out, uint64_t ld) {
+    return guarded("storm_hip_pairw_lag_matrix_device", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        uint64_t lag = 0;
+        if (int rc = check_lag("pairw_lag_matrix", m, d_out, max_lag, ld, &lag)) return rc;
+        if (n_band_rows == ~0ull && row0 <= m->n_rows) n_band_rows = m->n_rows - row0;
+        if (op < STORM_HIP_OP_AND || op > STORM_HIP_OP_XOR || row0 > m->n_rows || n_band_rows > m->n_rows - row0) {
+            set_error("pairw_lag_matrix: unknown op or a band outside the rows");
+            return STORM_HIP_EINVAL;
+        }
+        if (m->n_rows < 2 || n_band_rows == 0) return STORM_HIP_OK;
+        STORM_HIP_TRY(hipSetDevice(ctx->device));
+        return launch_pairw_lag_matrix(ctx, m, op, max_lag, row0, n_band_rows, d_out, ld, true);
+    });
+}
+
+int storm_hip_pairw_lag_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int op, uint64_t max_lag, uint32_t* h_out,
+                               uint64_t ld) {
+    return guarded("storm_hip_pairw_lag_matrix", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        uint64_t lag = 0;
+        if (int rc = check_lag("pairw_lag_matrix", m, h_out, max_lag, ld, &lag)) return rc;
+        if (op < STORM_HIP_OP_AND || op > STORM_HIP_OP_XOR) {
+            set_error("pairw_lag_matrix: unknown op %d", op);
+            return STORM_HIP_EINVAL;
+        }
+        const uint64_t n = m->n_rows;
+        if (n < 2) return STORM_HIP_OK;
+        STORM_HIP_TRY(hipSetDevice(ctx->device));
+        const size_t need = (size_t)n * lag * sizeof(uint32_t);
+        if (int rc = ctx->d_band.ensure(need, "pairw_lag_matrix: the output")) return rc;
+        STORM_HIP_TRY(hipMemsetAsync(ctx->d_band, 0, need, ctx->stream));   // (the lower-right corner)
+        if (int rc = launch_pairw_lag_matrix(ctx, m, op, max_lag, 0, n, ctx->d_band, lag, false)) return rc;
+        STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(uint32_t), ctx->d_band, lag * sizeof(uint32_t), lag * sizeof(uint32_t), n,
+                                       hipMemcpyDeviceToHost, ctx->stream));
+        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return STORM_HIP_OK;
+    });
+}
+
+int storm_hip_similarity_finish_lag_device(storm_hip_ctx_t* ctx, void* d_io, uint64_t ld, uint64_t n_rows, uint64_t row0,
+                                           uint64_t n_band_rows, uint64_t max_lag, const uint32_t* d_counts, int measure,
+                                           uint64_t n_bits) {
+    return guarded("storm_hip_similarity_finish_lag_device", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        if (int rc = launch_similarity_finish_lag(ctx, d_io, ld, n_rows, row0, n_band_rows, max_lag, d_counts, measure, n_bits))
+            return rc;
+        // (alone on a caller's matrix: a report of its own, as storm_hip_similarity_finish_device; nothing launched: as it was)
+        if (n_rows >= 2 && n_band_rows != 0 && row0 < n_rows) {
+            memset(ctx->pass_report, 0, sizeof(ctx->pass_report));
+            ctx->pass_report[0] = STORM_HIP_RAN_SIMILARITY;
+        }
+        return STORM_HIP_OK;
+    });
+}
+
+// counts in the lag layout at d_io (pitch ld), queued; then the rows' counts and the finish, queued too
+static int lag_similarity_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_bits, uint64_t max_lag,
+                                 uint32_t* d_io, uint64_t ld) {
+    const uint64_t n = m->n_rows;
+    if (int rc = launch_pairw_lag_matrix(ctx, m, STORM_HIP_OP_AND, max_lag, 0, n, d_io, ld, false)) return rc;
+    if (int rc = ctx->d_counts.ensure(n * sizeof(uint32_t), "similarity: the row-count scratch")) return rc;
+    if (int rc = counts_of(ctx, m, 0)) return rc;
+    return launch_similarity_finish_lag(ctx, d_io, ld, n, 0, n, max_lag, ctx->d_counts.d, measure, n_bits);
+}
+
+int storm_hip_pairw_lag_similarity_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_bits,
+                                          uint64_t max_lag, float* d_out, uint64_t ld) {
+    return guarded("storm_hip_pairw_lag_similarity_device", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        uint64_t lag = 0;
+        if (int rc = check_lag("pairw_lag_similarity", m, d_out, max_lag, ld, &lag)) return rc;
+        if (int rc = check_measure(measure, n_bits)) return rc;
+        if (m->n_rows < 2) return STORM_HIP_OK;
+        STORM_HIP_TRY(hipSetDevice(ctx->device));
+        if (int rc = lag_similarity_queued(ctx, m, measure, n_bits, max_lag, reinterpret_cast<uint32_t*>(d_out), ld)) return rc;
+        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return STORM_HIP_OK;
+    });
+}
+
+int storm_hip_pairw_lag_similarity(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_bits,
+                                   uint64_t max_lag, float* h_out, uint64_t ld) {
+    return guarded("storm_hip_pairw_lag_similarity", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        uint64_t lag = 0;
+        if (int rc = check_lag("pairw_lag_similarity", m, h_out, max_lag, ld, &lag)) return rc;
+        if (int rc = check_measure(measure, n_bits)) return rc;
+        const uint64_t n = m->n_rows;
+        if (n < 2) return STORM_HIP_OK;
+        STORM_HIP_TRY(hipSetDevice(ctx->device));
+        const size_t need = (size_t)n * lag * sizeof(uint32_t);
+        if (int rc = ctx->d_band.ensure(need, "pairw_lag_similarity: the output")) return rc;
+        STORM_HIP_TRY(hipMemsetAsync(ctx->d_band, 0, need, ctx->stream));   // (the corner: +0.0f is the same zero bits)
+        if (int rc = lag_similarity_queued(ctx, m, measure, n_bits, max_lag, ctx->d_band, lag)) return rc;
+        STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(float), ctx->d_band, lag * sizeof(uint32_t), lag * sizeof(uint32_t), n,
                                        hipMemcpyDeviceToHost, ctx->stream));
         STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
         return STORM_HIP_OK;

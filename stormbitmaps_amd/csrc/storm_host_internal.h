@@ -1,5 +1,6 @@
 /* storm_host_internal.h — what the host side of the storm.h containers shares between its files: the device state of a
- * STORM_t handle (storm_host.c) and the helpers the rectangle of two containers (storm_square.c) runs on. Not installed. */
+ * STORM_t handle (storm_host.c) and the helpers the rectangle of two containers (storm_square.c) and the lag forms
+ * (storm_lag.c) run on. Not installed. */
 #ifndef STORM_HOST_INTERNAL_H_
 #define STORM_HOST_INTERNAL_H_
 #include <stdint.h>

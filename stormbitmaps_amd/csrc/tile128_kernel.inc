@@ -31,6 +31,11 @@
 // Output conventions (triangle / band / rectangle, AND / OR / XOR through row_counts) are tilebits8_kernel's. Extends the
 // reference (README.md:165-167: per-pair counts for LD); the loop it stands for is storm.c:1199-1238 with the leaf's
 // result kept per pair.
+//
+// Lag form (kLag, DESIGN.md §4 "lag layout"): the triangle's pairs with j - i <= L only (L travels in `j_count`, which the
+// triangle never uses), written as out[(i - i_lo) * ld + (j - i - 1)]: an n x L matrix instead of n x n. The host lists only
+// the tiles that hold such a pair; a wave whose 64 x 64 block holds none takes the "nothing to multiply" dispatch, and the
+// epilogue is the per-element one (a row's columns shift by one word per row: no 16-byte row runs to store).
 constexpr int kThThreads = 256;
 // (kThTile = 128 rows per tile side, the item record PartItem and kThNarrow: storm_hip_plan.h)
 constexpr uint32_t kThSlotBytes = 2u * kThTile * 64u;   // 16 KiB: A rows 0 .. 127, then B rows 0 .. 127, 64 B of bits each
@@ -38,6 +43,7 @@ constexpr uint32_t kThRing = 4u;
 constexpr uint32_t kThWindowWords = kThTile * kThTile;   // a part's window: 64 KiB of uint32
 
 
+template <bool kLag>
 __global__ __launch_bounds__(kThThreads, 2) void tile128_kernel(
     TileOperands ops, const PartItem* __restrict__ items, uint32_t* __restrict__ out, uint64_t ld,
     uint32_t n_rows, const uint32_t* __restrict__ row_counts, uint32_t and_weight, uint32_t j_base,
@@ -55,7 +61,7 @@ __global__ __launch_bounds__(kThThreads, 2) void tile128_kernel(
     const uint32_t nC = it.n_stages / 4u;                      // chunks of 64 B (512 bits of k)
     const uint32_t kbyte0 = it.stage0 * 16u;
     const uint32_t pitch = (uint32_t)ops.pitch;
-    const bool rect = j_count != 0;
+    const bool rect = !kLag && j_count != 0;
 
     auto window = [&](uint32_t v0, const uint8_t*& base, uint32_t& bytes) {
         const bool second = v0 >= ops.split;
@@ -98,7 +104,9 @@ __global__ __launch_bounds__(kThThreads, 2) void tile128_kernel(
     const uint32_t fb0 = lds_base + kThTile * 64u + (64u * wb + frow) * 64u + fq * 16u, fb1 = fb0 ^ 32u;
 
     // block offset of the wave's B rows from its A rows: block (m, n) holds a pair i < j iff n + d >= m
-    const int32_t d = rect ? 64 : (int32_t)((b_row0 + 64u * wb) / 32u) - (int32_t)((a_row0 + 64u * wa) / 32u);
+    int32_t d = rect ? 64 : (int32_t)((b_row0 + 64u * wb) / 32u) - (int32_t)((a_row0 + 64u * wa) / 32u);
+    if constexpr (kLag)   // the block's nearest pair (i0 + 63, j0) is already beyond the lag: every part of the tile agrees
+        if (b_row0 + 64u * wb > a_row0 + 64u * wa + 63u + j_count) d = -1;
 
     auto run = [&](auto dc) __attribute__((always_inline)) {
         constexpr int D = decltype(dc)::value;          // 64: every block; 0: the block below the diagonal drops out; -1: nothing
@@ -322,7 +330,7 @@ __global__ __launch_bounds__(kThThreads, 2) void tile128_kernel(
             const bool inside = i0 >= i_lo && i0 + 64u <= n_rows &&
                                 (rect ? (j0 >= j_base && j0 - j_base + 64u <= j_count) : (j0 + 64u <= n_cols && i0 + 64u <= j0)) &&
                                 (ld & 3u) == 0 && ((uintptr_t)out & 15u) == 0 && (j_base & 3u) == 0;
-            if constexpr (D > 0) {
+            if constexpr (D > 0 && !kLag) {
                 if (inside) {
                     uint32_t* w32 = reinterpret_cast<uint32_t*>(lds + wave * (32u * 68u * 4u));
                     uint32_t* out_tile = &out[(uint64_t)(i0 - i_lo) * ld + (j0 - j_base)];
@@ -355,7 +363,7 @@ __global__ __launch_bounds__(kThThreads, 2) void tile128_kernel(
 #pragma unroll
             for (int n = 0; n < 2; ++n) {
                 const uint32_t jj = j0 + 32u * (uint32_t)n + col;
-                const bool j_ok = rect ? (jj >= j_base && jj - j_base < j_count) : jj < n_cols;
+                const bool j_ok = rect ? (jj >= j_base && jj - j_base < j_count) : jj < n_cols;   // (lag form: rect is false)
                 const uint32_t nj = (row_counts && j_ok) ? row_counts[jj] : 0u;
 #pragma unroll
                 for (int m = 0; m < 2; ++m) {
@@ -363,7 +371,12 @@ __global__ __launch_bounds__(kThThreads, 2) void tile128_kernel(
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const uint32_t ii = i0 + 32u * (uint32_t)m + (uint32_t)((r & 3) + 8 * (r >> 2)) + 4u * (lane >> 5);
-                        if (j_ok && ii >= i_lo && ii < n_rows && (rect || ii < jj))
+                        if constexpr (kLag) {
+                            // (a register's 32 lanes of one half-wave: one row, 32 consecutive columns = one 128-byte run)
+                            if (j_ok && ii >= i_lo && ii < n_rows && ii < jj && jj - ii <= j_count)
+                                out[(uint64_t)(ii - i_lo) * ld + (jj - ii - 1u)] =
+                                    row_counts ? row_counts[ii] + nj - and_weight * cnt[m][n][r] : cnt[m][n][r];
+                        } else if (j_ok && ii >= i_lo && ii < n_rows && (rect || ii < jj))
                             out[(uint64_t)(ii - i_lo) * ld + (jj - j_base)] =
                                 row_counts ? row_counts[ii] + nj - and_weight * cnt[m][n][r] : cnt[m][n][r];
                     }
