@@ -351,6 +351,34 @@ int STORM_pairw_lag_similarity(STORM_t* bitmap, int measure, uint64_t n_bits, ui
 int STORM_pairw_lag_similarity_device(STORM_t* bitmap, int measure, uint64_t n_bits, uint64_t max_lag, float* d_out,
                                       uint64_t out_rows, uint64_t out_ld);
 
+/* Extension: for each row its k most similar rows, selected on the device (k-NN graphs on Jaccard or cosine, the best LD
+ * tags of a variant, the nearest sets of a query container in a reference container): n x k entries instead of n x n.
+ * `score` is one of the measures of STORM_*_pairw_similarity (same n_bits rule, values bit-identical to those calls) or
+ * STORM_TOPK_COUNT, the AND count itself. idx[i * out_ld + t] is the row (of `b` for STORM_square_topk) that ranks t-th for
+ * row i, val[i * out_ld + t] its value (float bits, or the count as uint32): value descending, then row index ascending. A
+ * row never lists itself (pairw forms), and never a row its value is undefined (NaN) against. Fewer than k candidates: the
+ * rest of columns [0, k) is padding, idx 0xFFFFFFFF with val NaN (0x7FC00000), or val 0 under STORM_TOPK_COUNT. Columns
+ * [k, out_ld) are not touched. 1 <= k <= STORM_TOPK_MAX; out_rows >= n and out_ld >= k. panel_rows: rows whose counts are
+ * on the device at a time, 0 (chosen by the library) or a multiple of 256. _device forms: idx / val in device memory.
+ * A STORM_t always runs on its dense replica here, two of them at their common width (there is no list-join form). One
+ * device slot and one process. Returns 0; -1 NULL handle, -2 NULL idx or val, -4 out_rows < n or out_ld < k (nothing is
+ * written), -3 device failure, bad score, n_bits, k or panel_rows (STORM_hip_error says which), -5 several device slots in
+ * view. No rows: 0, nothing written. */
+#define STORM_TOPK_COUNT 4
+#define STORM_TOPK_MAX 128
+int STORM_contig_pairw_topk(STORM_contiguous_t* bitmap, int score, uint64_t n_bits, uint64_t k, uint64_t panel_rows,
+                            uint32_t* idx, void* val, uint64_t out_rows, uint64_t out_ld);
+int STORM_contig_pairw_topk_device(STORM_contiguous_t* bitmap, int score, uint64_t n_bits, uint64_t k, uint64_t panel_rows,
+                                   uint32_t* d_idx, void* d_val, uint64_t out_rows, uint64_t out_ld);
+int STORM_pairw_topk(STORM_t* bitmap, int score, uint64_t n_bits, uint64_t k, uint64_t panel_rows, uint32_t* idx, void* val,
+                     uint64_t out_rows, uint64_t out_ld);
+int STORM_pairw_topk_device(STORM_t* bitmap, int score, uint64_t n_bits, uint64_t k, uint64_t panel_rows, uint32_t* d_idx,
+                            void* d_val, uint64_t out_rows, uint64_t out_ld);
+int STORM_square_topk(STORM_t* a, STORM_t* b, int score, uint64_t n_bits, uint64_t k, uint64_t panel_rows, uint32_t* idx,
+                      void* val, uint64_t out_rows, uint64_t out_ld);
+int STORM_square_topk_device(STORM_t* a, STORM_t* b, int score, uint64_t n_bits, uint64_t k, uint64_t panel_rows,
+                             uint32_t* d_idx, void* d_val, uint64_t out_rows, uint64_t out_ld);
+
 /* ------------------------------------------------------------- extensions (not in ref) ---
  * Device selection for the entry points above. By default device 0 computes everything.
  * STORM_hip_set_devices(n, ids): the pair space is sharded over the listed GPUs of this node

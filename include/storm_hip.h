@@ -256,6 +256,46 @@ int storm_hip_pairw_lag_similarity_device(storm_hip_ctx_t* ctx, const storm_hip_
 int storm_hip_pairw_lag_similarity(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_bits,
                                    uint64_t max_lag, float* h_out, uint64_t ld);
 
+/* ---- per-row top-k neighbours: the selection on the device -------------------------------------------------
+ * For each row its k most similar rows (k-NN graphs on Jaccard or cosine, the best LD tags of a variant, the nearest sets
+ * of a query container in a reference container): n x k entries leave the device instead of n x n. `score` is one of the
+ * similarity measures above (the value is bit-identical to what the similarity calls write) or STORM_HIP_TOPK_COUNT, the
+ * AND count itself; that constant is valid in the top-k calls only. Order within a row: value descending, then column
+ * index ascending (fully determined: no two entries of a row compare equal). An undefined entry (NaN, 0x7FC00000) is not
+ * a candidate. A row with fewer than k candidates is padded: idx 0xFFFFFFFF with val NaN (0x7FC00000) for the measures,
+ * idx 0xFFFFFFFF with val 0 for STORM_HIP_TOPK_COUNT. 1 <= k <= STORM_HIP_TOPK_MAX.
+ * Outputs: idx is n_rows x ld_k uint32 (the column), val n_rows x ld_k 32-bit words (float, or uint32 for the count);
+ *   columns [0, k) of every row are always written, columns [k, ld_k) are not touched.
+ * _topk_rows_device, the primitive: `d_counts_matrix` is a COMPLETE count matrix in DEVICE memory, n_rows x ld uint32
+ *   (read, never written; the pitch columns [n_cols, ld) are not read), d_counts_rows[n_rows] / d_counts_cols[n_cols] the
+ *   set-bit counts of the rows' and the columns' side. Row r never takes column skip0 + r as a candidate (how a row
+ *   excludes itself); skip0 = ~0: none. Asynchronous on the context's stream (topk_rows_kernel, one 128-bit load per lane
+ *   where the base is 16-byte aligned and ld a multiple of 4); alone the last-pass report is STORM_HIP_RAN_TOPK.
+ * _pairw_topk: row i of `m` against every other row j != i, on both sides of the diagonal. _cross_dense_topk: every row of
+ *   `a` against every row of `b` (equal row widths). Both run in row panels: the AND-count rectangle of panel_rows rows
+ *   against all columns into the context's band buffer (the kernels and the choice of storm_hip_cross_dense_matrix_device),
+ *   then the selection over it. panel_rows = 0: the largest multiple of 256 whose panel is at most 256 MiB, at least 256;
+ *   else a multiple of 256. _device: idx / val in DEVICE memory, complete on return; the others copy n x k of each back.
+ *   The pairw form multiplies both sides of the diagonal: twice the work of the triangle (open).
+ * STORM_HIP_EINVAL: NULL argument, unknown score, n_bits outside [1, 2^32] (read by LD D and r^2 only), k of 0 or above the
+ *   maximum, ld_k < k, ld < n_cols, panel_rows not a multiple of 256, row widths that differ. No rows: STORM_HIP_OK,
+ *   nothing written; pairw on one row, or cross with an empty `b`: every row is k paddings. Last-pass report:
+ *   STORM_HIP_RAN_TILES_OUT | STORM_HIP_RAN_TOPK, [1] = rows x columns x n_words. */
+#define STORM_HIP_TOPK_COUNT 4
+#define STORM_HIP_TOPK_MAX 128
+int storm_hip_topk_rows_device(storm_hip_ctx_t* ctx, const uint32_t* d_counts_matrix, uint64_t ld, uint64_t n_rows,
+                               uint64_t n_cols, const uint32_t* d_counts_rows, const uint32_t* d_counts_cols, uint64_t skip0,
+                               int score, uint64_t n_bits, uint64_t k, uint32_t* d_idx, void* d_val, uint64_t ld_k);
+int storm_hip_pairw_topk_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int score, uint64_t n_bits, uint64_t k,
+                                uint64_t panel_rows, uint32_t* d_idx, void* d_val, uint64_t ld_k);
+int storm_hip_pairw_topk(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int score, uint64_t n_bits, uint64_t k,
+                         uint64_t panel_rows, uint32_t* h_idx, void* h_val, uint64_t ld_k);
+int storm_hip_cross_dense_topk_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b,
+                                      int score, uint64_t n_bits, uint64_t k, uint64_t panel_rows, uint32_t* d_idx,
+                                      void* d_val, uint64_t ld_k);
+int storm_hip_cross_dense_topk(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b, int score,
+                               uint64_t n_bits, uint64_t k, uint64_t panel_rows, uint32_t* h_idx, void* h_val, uint64_t ld_k);
+
 /* sum_c C(n_c,2) on the device — verification identity only, never the product
  * path: used by tests at sizes where a CPU pairwise oracle is infeasible */
 int storm_hip_column_identity(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m,
@@ -433,6 +473,7 @@ typedef struct storm_hip_comm_s storm_hip_comm_t;
 #define STORM_HIP_RAN_LISTS_MATRIX 64u /* lists_matrix_kernel (K5), per-pair output from the lists: out[2] = its table lookups, out[3] = 64 */
 #define STORM_HIP_RAN_LISTS_SQUARE 256u /* lists_square_kernel (K5x), the rectangle of two list-only containers: out[2] = its table lookups, out[3] = 64 */
 #define STORM_HIP_RAN_SIMILARITY 512u /* similarity_finish_kernel behind one of the per-pair kernels above (its flag stays set), or alone (storm_hip_similarity_finish_device)  roof: HBM bandwidth */
+#define STORM_HIP_RAN_TOPK 1024u /* topk_rows_kernel behind the panels' count kernel (its flag stays set), or alone (storm_hip_topk_rows_device)  roof: HBM bandwidth */
 int storm_hip_last_pass_report(storm_hip_ctx_t* ctx, uint64_t out[4]);
 
 int storm_hip_comm_unique_id(uint8_t id[STORM_HIP_COMM_ID_BYTES]);

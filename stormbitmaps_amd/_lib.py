@@ -124,6 +124,11 @@ SIGNATURES = {
     "storm_hip_similarity_finish_lag_device": (C.c_int, [vp, vp, u64, u64, u64, u64, u64, vp, C.c_int, u64]),
     "storm_hip_pairw_lag_similarity_device": (C.c_int, [vp, vp, C.c_int, u64, u64, vp, u64]),
     "storm_hip_pairw_lag_similarity": (C.c_int, [vp, vp, C.c_int, u64, u64, vp, u64]),
+    "storm_hip_topk_rows_device": (C.c_int, [vp, vp, u64, u64, u64, vp, vp, u64, C.c_int, u64, u64, vp, vp, u64]),
+    "storm_hip_pairw_topk_device": (C.c_int, [vp, vp, C.c_int, u64, u64, u64, vp, vp, u64]),
+    "storm_hip_pairw_topk": (C.c_int, [vp, vp, C.c_int, u64, u64, u64, vp, vp, u64]),
+    "storm_hip_cross_dense_topk_device": (C.c_int, [vp, vp, vp, C.c_int, u64, u64, u64, vp, vp, u64]),
+    "storm_hip_cross_dense_topk": (C.c_int, [vp, vp, vp, C.c_int, u64, u64, u64, vp, vp, u64]),
     "storm_hip_matrix_create_from_blocks_wide": (C.c_int, [vp, u64, u64, vp, vp, vp, vp, vp, u32, P(vp)]),
     "storm_hip_pairw_sparse_begin": (C.c_int, [vp, vp, u32, u32]),
     "storm_hip_pairw_sparse_end": (C.c_int, [vp, P(u64)]),
@@ -184,6 +189,12 @@ SIGNATURES = {
     "STORM_pairw_lag_matrix_device": (C.c_int, [vp, C.c_int, u64, vp, u64, u64]),
     "STORM_pairw_lag_similarity": (C.c_int, [vp, C.c_int, u64, u64, vp, u64, u64]),
     "STORM_pairw_lag_similarity_device": (C.c_int, [vp, C.c_int, u64, u64, vp, u64, u64]),
+    "STORM_contig_pairw_topk": (C.c_int, [vp, C.c_int, u64, u64, u64, vp, vp, u64, u64]),
+    "STORM_contig_pairw_topk_device": (C.c_int, [vp, C.c_int, u64, u64, u64, vp, vp, u64, u64]),
+    "STORM_pairw_topk": (C.c_int, [vp, C.c_int, u64, u64, u64, vp, vp, u64, u64]),
+    "STORM_pairw_topk_device": (C.c_int, [vp, C.c_int, u64, u64, u64, vp, vp, u64, u64]),
+    "STORM_square_topk": (C.c_int, [vp, vp, C.c_int, u64, u64, u64, vp, vp, u64, u64]),
+    "STORM_square_topk_device": (C.c_int, [vp, vp, C.c_int, u64, u64, u64, vp, vp, u64, u64]),
     "STORM_hip_set_option": (C.c_int, [C.c_char_p, C.c_int64]),
     "STORM_contig_pairw_matrix_device": (C.c_int, [vp, C.c_int, vp, u64, u64]),
     "STORM_serialize": (u64, [vp, vp, u64]),

@@ -74,6 +74,39 @@ class _LagForms:
                                                                   out_rows, out_ld)))
 
 
+SCORES = dict(MEASURES, count=4)  # what the top-k calls rank by: a measure, or STORM_TOPK_COUNT (the AND count itself)
+
+
+def _topk_out(n: int, k: int, score: str):
+    """(idx, val) of n rows: val float32 for a measure, uint32 for the count (at least one entry, so that both have an address)"""
+    return (np.zeros((n, k), dtype=np.uint32), np.zeros((n, k), dtype=np.uint32 if score == "count" else np.float32))
+
+
+class _TopkForms:
+    """The top-k calls of a storm.h container (extension; `_LAG` = the C prefix): for each row its k most similar rows,
+    selected on the device. idx[i, t] is the row that ranks t-th for row i (value descending, then row index ascending),
+    val[i, t] its value; fewer than k candidates: idx 0xFFFFFFFF with val NaN (0 under score "count")."""
+
+    def pairw_topk(self, k: int, score: str = "jaccard", n_bits: int = 0, panel_rows: int = 0):
+        """(idx [n_rows, k] uint32, val [n_rows, k] float32, or uint32 for score "count"): row i against every other row."""
+        n = self.n_rows
+        idx, val = _topk_out(n, k, score)
+        name = self._LAG + "pairw_topk"
+        spare = np.zeros(1, np.uint32)
+        _similarity(self._lib, name, int(getattr(self._lib, name)(self._h, SCORES[score], n_bits, k, panel_rows,
+                                                                  _ptr(idx) if idx.size else _ptr(spare),
+                                                                  _ptr(val) if val.size else _ptr(spare), n, k)))
+        return idx, val
+
+    def pairw_topk_device(self, d_idx: int, d_val: int, out_rows: int, out_ld: int, k: int, score: str = "jaccard",
+                          n_bits: int = 0, panel_rows: int = 0) -> None:
+        """The same left in device memory at addresses d_idx / d_val (out_rows x out_ld 32-bit words each; columns [k, out_ld)
+        are not touched)."""
+        name = self._LAG + "pairw_topk_device"
+        _similarity(self._lib, name, int(getattr(self._lib, name)(self._h, SCORES[score], n_bits, k, panel_rows, C.c_void_p(d_idx),
+                                                                  C.c_void_p(d_val), out_rows, out_ld)))
+
+
 def _all_pairs(value: int, what: str) -> int:
     if value == ALL_PAIRS_FAILED:
         lib = _lib.load()
@@ -85,7 +118,7 @@ def _all_pairs(value: int, what: str) -> int:
 # ------------------------------------------------------------------------------------------
 # storm.h containers
 # ------------------------------------------------------------------------------------------
-class StormContig(_LagForms):
+class StormContig(_LagForms, _TopkForms):
     """STORM_contiguous_t (storm.h:188-200, :235-242): dense row-major bitmap matrix."""
     _LAG = "STORM_contig_"
 
@@ -187,7 +220,7 @@ class StormContig(_LagForms):
             pass
 
 
-class Storm(_LagForms):
+class Storm(_LagForms, _TopkForms):
     """STORM_t (storm.h:175-178, :225-232): rows of 65536-bit blocks, list or bitmap kind."""
     _LAG = "STORM_"
 
@@ -289,6 +322,25 @@ class Storm(_LagForms):
         _similarity(self._lib, "STORM_square_similarity_device",
                     int(self._lib.STORM_square_similarity_device(self._h, other._h, MEASURES[measure], n_bits,
                                                                  C.c_void_p(d_out), out_rows, out_ld)))
+
+    def square_topk(self, other: "Storm", k: int, score: str = "jaccard", n_bits: int = 0, panel_rows: int = 0):
+        """STORM_square_topk (extension): (idx, val) of [self.n_rows, k]: for each row of self its k most similar rows of
+        other (see pairw_topk)."""
+        na = self.n_rows
+        idx, val = _topk_out(na, k, score)
+        spare = np.zeros(1, np.uint32)
+        _similarity(self._lib, "STORM_square_topk",
+                    int(self._lib.STORM_square_topk(self._h, other._h, SCORES[score], n_bits, k, panel_rows,
+                                                    _ptr(idx) if idx.size else _ptr(spare),
+                                                    _ptr(val) if val.size else _ptr(spare), na, k)))
+        return idx, val
+
+    def square_topk_device(self, other: "Storm", d_idx: int, d_val: int, out_rows: int, out_ld: int, k: int,
+                           score: str = "jaccard", n_bits: int = 0, panel_rows: int = 0) -> None:
+        """STORM_square_topk_device (extension): the same left in device memory at addresses d_idx / d_val."""
+        _similarity(self._lib, "STORM_square_topk_device",
+                    int(self._lib.STORM_square_topk_device(self._h, other._h, SCORES[score], n_bits, k, panel_rows,
+                                                           C.c_void_p(d_idx), C.c_void_p(d_val), out_rows, out_ld)))
 
     def serialized_size(self) -> int:
         return int(self._lib.STORM_serialized_size(self._h))  # storm.c:963
@@ -615,6 +667,44 @@ class HipMatrix:
                                                                (1 << 64) - 1 if n_band_rows is None else n_band_rows, max_lag,
                                                                C.c_void_p(d_counts), MEASURES[measure], n_bits),
               "storm_hip_similarity_finish_lag_device")
+
+    def pairw_topk(self, k: int, score: str = "jaccard", n_bits: int = 1, panel_rows: int = 0):
+        """(idx [n_rows, k] uint32, val [n_rows, k] float32, or uint32 for score "count"): for each row its k best other rows,
+        value descending, then row index ascending; fewer than k candidates: idx 0xFFFFFFFF with val NaN (0 for "count")."""
+        idx, val = _topk_out(self.n_rows, k, score)
+        spare = np.zeros(1, np.uint32)
+        check(self._lib.storm_hip_pairw_topk(self.ctx._h, self._h, SCORES[score], n_bits, k, panel_rows,
+                                             _ptr(idx) if idx.size else _ptr(spare), _ptr(val) if val.size else _ptr(spare), k),
+              "storm_hip_pairw_topk")
+        return idx, val
+
+    def pairw_topk_device(self, d_idx: int, d_val: int, ld_k: int, k: int, score: str = "jaccard", n_bits: int = 1,
+                          panel_rows: int = 0) -> None:
+        """Same, into device buffers (n_rows x ld_k 32-bit words each; columns [k, ld_k) are not touched); complete on return."""
+        check(self._lib.storm_hip_pairw_topk_device(self.ctx._h, self._h, SCORES[score], n_bits, k, panel_rows, C.c_void_p(d_idx),
+                                                    C.c_void_p(d_val), ld_k),
+              "storm_hip_pairw_topk_device")
+
+    def cross_topk(self, other: "HipMatrix", k: int, score: str = "jaccard", n_bits: int = 1, panel_rows: int = 0):
+        """(idx, val) of [n_rows, k]: for each row of self its k best rows of other (equal row widths)."""
+        idx, val = _topk_out(self.n_rows, k, score)
+        spare = np.zeros(1, np.uint32)
+        check(self._lib.storm_hip_cross_dense_topk(self.ctx._h, self._h, other._h, SCORES[score], n_bits, k, panel_rows,
+                                                   _ptr(idx) if idx.size else _ptr(spare),
+                                                   _ptr(val) if val.size else _ptr(spare), k),
+              "storm_hip_cross_dense_topk")
+        return idx, val
+
+    def topk_rows_device(self, d_counts_matrix: int, ld: int, n_rows: int, n_cols: int, d_counts_rows: int, d_counts_cols: int,
+                         d_idx: int, d_val: int, ld_k: int, k: int, score: str = "jaccard", n_bits: int = 1,
+                         skip0: Optional[int] = None) -> None:
+        """The selection alone over a complete count matrix of the caller's in device memory (storm_hip_topk_rows_device; the
+        matrix only lends its context); asynchronous on the context's stream. skip0: row r never lists column skip0 + r."""
+        check(self._lib.storm_hip_topk_rows_device(self.ctx._h, C.c_void_p(d_counts_matrix), ld, n_rows, n_cols,
+                                                   C.c_void_p(d_counts_rows), C.c_void_p(d_counts_cols),
+                                                   (1 << 64) - 1 if skip0 is None else skip0, SCORES[score], n_bits, k,
+                                                   C.c_void_p(d_idx), C.c_void_p(d_val), ld_k),
+              "storm_hip_topk_rows_device")
 
     def row_counts(self) -> np.ndarray:
         out = np.zeros(self.n_rows, dtype=np.uint32)

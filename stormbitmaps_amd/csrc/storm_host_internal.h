@@ -1,6 +1,6 @@
 /* storm_host_internal.h — what the host side of the storm.h containers shares between its files: the device state of a
  * STORM_t handle (storm_host.c) and the helpers the rectangle of two containers (storm_square.c) and the lag forms
- * (storm_lag.c) run on. Not installed. */
+ * (storm_lag.c) and the top-k forms (storm_topk.c) run on. Not installed. */
 #ifndef STORM_HOST_INTERNAL_H_
 #define STORM_HOST_INTERNAL_H_
 #include <stdint.h>
@@ -42,5 +42,9 @@ sparse_state_t* storm_host_checked_state(STORM_t* h);
 /* storm_build_device: dense = 0 arena, 1 dense replica (`wide` with min_blocks, or NULL: own width), 2 row lists */
 int storm_host_build(STORM_t* h, sparse_state_t* st, int dense, storm_dense_builder_t wide, uint32_t min_blocks);
 void storm_host_drop_dense(sparse_state_t* st);
+
+/* storm_square.c: the dense replicas of two containers at one common width (the wider of the two, or of a replica one of
+ * them already keeps) on device slot `slot`; 0, or nonzero with the reason reported */
+int storm_host_common_dense(STORM_t* a, sparse_state_t* sa, STORM_t* b, sparse_state_t* sb, int slot);
 
 #endif /* STORM_HOST_INTERNAL_H_ */

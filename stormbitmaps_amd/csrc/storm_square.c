@@ -55,6 +55,16 @@ static int dense_at_width(STORM_t* h, sparse_state_t* st, int slot, uint32_t blo
     return storm_host_build(h, st, 1, storm_hip_matrix_create_from_blocks_wide, blocks);
 }
 
+/* dense replicas of one common width: the wider of the two containers, or of a replica one of them already keeps
+ * (storm_host_internal.h: the top-k rectangle of storm_topk.c runs on them too). 0, or nonzero with the reason reported. */
+int storm_host_common_dense(STORM_t* a, sparse_state_t* sa, STORM_t* b, sparse_state_t* sb, int slot) {
+    uint32_t blocks = dense_blocks(a), x = dense_blocks(b);
+    if (x > blocks) blocks = x;
+    if ((x = replica_blocks(sa, slot)) > blocks) blocks = x;
+    if ((x = replica_blocks(sb, slot)) > blocks) blocks = x;
+    return dense_at_width(a, sa, slot, blocks) || (b != a && dense_at_width(b, sb, slot, blocks));
+}
+
 /* what = 0: *total; 1: the window into host `out`; 2: into device `out`. measure < 0: counts under `op`; else the window
  * finished into that similarity measure (float entries in `out`, universe n_bits). 0, or -3 with the reason in
  * STORM_hip_error(). */
@@ -94,12 +104,7 @@ static int square_locked(STORM_t* a, STORM_t* b, int what, int op, uint32_t* out
             return 0;
         }
     }
-    /* dense replicas of one common width: the wider of the two containers, or of a replica one of them already keeps */
-    uint32_t blocks = dense_blocks(a), x = dense_blocks(b);
-    if (x > blocks) blocks = x;
-    if ((x = replica_blocks(sa, slot)) > blocks) blocks = x;
-    if ((x = replica_blocks(sb, slot)) > blocks) blocks = x;
-    if (dense_at_width(a, sa, slot, blocks) || (b != a && dense_at_width(b, sb, slot, blocks))) return -3;
+    if (storm_host_common_dense(a, sa, b, sb, slot)) return -3;
     const int rc = what == 0    ? storm_hip_cross_dense_total(ctx, sa->m[slot], sb->m[slot], total)
                    : measure >= 0 ? (what == 1 ? storm_hip_cross_dense_similarity(ctx, sa->m[slot], sb->m[slot], measure, n_bits, (float*)out, out_ld)
                                                : storm_hip_cross_dense_similarity_device(ctx, sa->m[slot], sb->m[slot], measure, n_bits, (float*)out, out_ld))
