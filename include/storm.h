@@ -379,6 +379,45 @@ int STORM_square_topk(STORM_t* a, STORM_t* b, int score, uint64_t n_bits, uint64
 int STORM_square_topk_device(STORM_t* a, STORM_t* b, int score, uint64_t n_bits, uint64_t k, uint64_t panel_rows,
                              uint32_t* d_idx, void* d_val, uint64_t out_rows, uint64_t out_ld);
 
+/* Extension: rows of 2-bit DOSAGES instead of bits — unphased genotypes, 0 / 1 / 2 copies of an allele per sample — and
+ * the LD asked of them: PLINK's --r / --r2, the (squared) Pearson correlation of two dosage vectors. A row is n_samples
+ * values in 0 .. 3, packed 2 bits each: sample s in bits 2 (s % 32) and 2 (s % 32) + 1 of 64-bit word s / 32, as an
+ * unsigned integer; ceil(n_samples / 32) words per row, tail bits zero. 3 is an ordinary value (the arithmetic is linear
+ * up to 3). MISSING GENOTYPES ARE OUT OF SCOPE: there is no missing code and no pairwise-complete statistic; impute or
+ * drop such samples first. On the device one FP4 multiply does the work (the E2M1 codes 0 .. 3 are 0, 0.5, 1, 1.5: linear
+ * in the value), so a sample pair costs what a bit pair costs the other containers; every result is exact.
+ *   STORM_dosage_new(n_samples)        1 <= n_samples <= 2^24, else NULL
+ *   STORM_dosage_add(h, values, n)     one row, one byte per sample; n must be n_samples and every value <= 3
+ *   STORM_dosage_add_packed(h, w, r)   r rows already packed, ceil(n_samples / 32) words each; tail bits must be zero
+ *   STORM_dosage_row_sums              sum[i] = sum_s v, sum_sq[i] = sum_s v^2 of every row, computed on the device
+ *   STORM_dosage_pairw_dot             out[i * out_ld + j] = P(i, j) = sum_s v_i[s] v_j[s] for i < j < n (uint32, exact)
+ *   STORM_dosage_pairw_corr            with S = n_samples, s = sum v, q = sum v^2: num = S P - s_i s_j, d = S q - s^2, exactly in
+ *                                      64-bit integers; STORM_DOSAGE_R2: num^2 / (d_i d_j), STORM_DOSAGE_R: num / sqrt(d_i d_j);
+ *                                      the division in double, rounded once to float (at most one float from the exactly
+ *                                      rounded value); NaN (0x7FC00000) when d_i or d_j is 0: a constant row
+ * Output conventions of STORM_contig_pairw_matrix[_device] and STORM_*_similarity: out_rows >= n and out_ld >= n; host forms
+ * write 0 / +0.0f at i >= j inside the n x n window; _device forms (`d_out` in device memory) leave i >= j as they were;
+ * nothing outside the n x n window is touched. The host keeps the packed rows and uploads them on the first call after a
+ * change (no streaming at add time). One device slot and one process.
+ * Returns 0; -1 NULL handle, -2 NULL values / words / out, -4 out_rows < n or out_ld < n (nothing is written), -3 device
+ * failure or a bad argument — a value above 3, n != n_samples, non-zero tail bits (nothing is appended), an unknown
+ * measure — STORM_hip_error says which; -5 several device slots in view. Fewer than two rows: 0, nothing written. There
+ * is no CPU fallback: without a device the compute calls return -3. */
+typedef struct STORM_dosage_s STORM_dosage_t;
+#define STORM_DOSAGE_R2 0
+#define STORM_DOSAGE_R 1
+STORM_dosage_t* STORM_dosage_new(uint64_t n_samples);
+void STORM_dosage_free(STORM_dosage_t* h);
+int STORM_dosage_add(STORM_dosage_t* h, const uint8_t* values, uint64_t n_values);
+int STORM_dosage_add_packed(STORM_dosage_t* h, const uint64_t* words, uint64_t n_rows);
+int STORM_dosage_clear(STORM_dosage_t* h);
+uint64_t STORM_dosage_n_rows(const STORM_dosage_t* h);
+int STORM_dosage_row_sums(STORM_dosage_t* h, uint32_t* sum, uint32_t* sum_sq);
+int STORM_dosage_pairw_dot(STORM_dosage_t* h, uint32_t* out, uint64_t out_rows, uint64_t out_ld);
+int STORM_dosage_pairw_dot_device(STORM_dosage_t* h, uint32_t* d_out, uint64_t out_rows, uint64_t out_ld);
+int STORM_dosage_pairw_corr(STORM_dosage_t* h, int measure, float* out, uint64_t out_rows, uint64_t out_ld);
+int STORM_dosage_pairw_corr_device(STORM_dosage_t* h, int measure, float* d_out, uint64_t out_rows, uint64_t out_ld);
+
 /* ------------------------------------------------------------- extensions (not in ref) ---
  * Device selection for the entry points above. By default device 0 computes everything.
  * STORM_hip_set_devices(n, ids): the pair space is sharded over the listed GPUs of this node

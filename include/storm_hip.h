@@ -296,6 +296,35 @@ int storm_hip_cross_dense_topk_device(storm_hip_ctx_t* ctx, const storm_hip_matr
 int storm_hip_cross_dense_topk(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b, int score,
                                uint64_t n_bits, uint64_t k, uint64_t panel_rows, uint32_t* h_idx, void* h_val, uint64_t ld_k);
 
+/* ---- rows of 2-bit values: dot products and genotype correlation (PLINK --r / --r2) --------------------------
+ * Unphased genotype data holds a dosage of 0, 1 or 2 per sample, and the LD asked of it is the (squared) Pearson
+ * correlation of two dosage vectors. Here a "dosage matrix" is an ordinary storm_hip_matrix_t whose rows hold VALUES
+ * 0 .. 3 in 2 bits each: value s of a row in bits 2 (s % 32) and 2 (s % 32) + 1 of word s / 32 (ceil(n_samples / 32)
+ * words per row, tail bits zero, at most 2^24 samples). 3 is an ordinary value; missing genotypes are out of scope.
+ * With P = sum v_i v_j, s = sum v, q = sum v^2 and S = n_samples:
+ *   num = S P - s_i s_j and d = S q - s^2 exactly in 64-bit integers, then in double, rounded once to float,
+ *   STORM_HIP_DOSAGE_R2   num^2 / (d_i d_j)          STORM_HIP_DOSAGE_R   num / sqrt(d_i d_j)
+ *   at most one float from the exactly rounded value; NaN (0x7FC00000) when d_i or d_j is 0: a constant row.
+ * _dosage_row_sums: h_sum[i] = s_i, h_sum_sq[i] = q_i (host pointers, n_rows entries), computed on the device.
+ * _pairw_dosage_matrix[_device]: out[i * ld + j] = P(i, j) for i < j (uint32, exact), ld >= n_rows. Always K2h in its
+ *   dosage form (tile128_kernel on two classes per nibble at block scale 128: the FP4 codes 0 .. 3 are linear in the
+ *   value), whatever k2_tile_shape says; read-only option "k2_tile_shape_used" then reads 7 (6: K2h on
+ *   bits). _device: entries i >= j stay as they were, complete on return. Host form: whole rows, 0 at i >= j.
+ * _pairw_dosage_corr[_device]: the dot products, the rows' sums, then dosage_finish_kernel in place; n_samples must be
+ *   the S the rows were packed with (ceil(S / 32) == the matrix's words). Host form: +0.0f at i >= j.
+ * STORM_HIP_EINVAL: NULL argument, ld < rows, unknown measure, n_samples that does not match the row width, rows of more
+ * than 2^24 values, rows beyond K2h's reach. Fewer than two rows: STORM_HIP_OK, nothing written (host forms of one row:
+ * its single 0). Last-pass report: STORM_HIP_RAN_TILES_OUT (| STORM_HIP_RAN_SIMILARITY for the correlation). */
+#define STORM_HIP_DOSAGE_R2 0
+#define STORM_HIP_DOSAGE_R 1
+int storm_hip_dosage_row_sums(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint32_t* h_sum, uint32_t* h_sum_sq);
+int storm_hip_pairw_dosage_matrix_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint32_t* d_out, uint64_t ld);
+int storm_hip_pairw_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint32_t* h_out, uint64_t ld);
+int storm_hip_pairw_dosage_corr_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_samples,
+                                       float* d_out, uint64_t ld);
+int storm_hip_pairw_dosage_corr(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_samples,
+                                float* h_out, uint64_t ld);
+
 /* sum_c C(n_c,2) on the device — verification identity only, never the product
  * path: used by tests at sizes where a CPU pairwise oracle is infeasible */
 int storm_hip_column_identity(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m,
@@ -419,6 +448,15 @@ int storm_hip_strip_plan3(uint64_t n_rows, uint32_t n_words, uint32_t shard_rank
  * k2_part_cost_diag. The items of a tile cover its chunks exactly once, the tiles every pair of the output exactly once.
  * Cuts the reference loop storm.c:1199-1238 (its per-pair results kept). Host only; `out` may be NULL to query the count. */
 int storm_hip_matrix_plan(uint64_t n_rows_a, uint64_t n_rows_b, uint32_t n_words, uint64_t band_row0, uint64_t band_rows,
+                          uint32_t n_cus, int slots_per_cu, int min_chunks, int diag_cost_pct, uint32_t* out,
+                          uint64_t capacity_items, uint64_t* n_items);
+
+/* The K2h list of the dosage form (storm_hip_pairw_dosage_matrix_device): arguments and records as storm_hip_matrix_plan
+ * for a matrix of n_words words of 2-bit values, planned with what a chunk of such values can add to an accumulator
+ * (9 x 256 instead of 512): an item covers at most 7281 chunks (chunks x 2304 <= 2^24, exact f32 accumulation), and a
+ * tile's windows are narrow only while a part covers at most 28 (chunks x 2304 <= 65535). Triangle only: n_rows_b must
+ * be 0. Host only; `out` may be NULL to query the count. */
+int storm_hip_dosage_plan(uint64_t n_rows_a, uint64_t n_rows_b, uint32_t n_words, uint64_t band_row0, uint64_t band_rows,
                           uint32_t n_cus, int slots_per_cu, int min_chunks, int diag_cost_pct, uint32_t* out,
                           uint64_t capacity_items, uint64_t* n_items);
 

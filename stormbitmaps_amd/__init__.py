@@ -9,9 +9,9 @@ Layout
     synth.py         deterministic synthetic inputs (splitmix64), numpy restatement
     dist.py          one-process-per-GPU sharding + RCCL all-reduce of the 8-byte total
 """
-from .api import (HipContext, HipMatrix, Storm, StormContig, wrapper_diag,  # noqa: F401
+from .api import (HipContext, HipMatrix, Storm, StormContig, StormDosage, wrapper_diag,  # noqa: F401
                   wrapper_diag_blocked, wrapper_square)
 from ._lib import StormHipError, load  # noqa: F401
 
-__all__ = ["HipContext", "HipMatrix", "Storm", "StormContig", "StormHipError", "load",
+__all__ = ["HipContext", "HipMatrix", "Storm", "StormContig", "StormDosage", "StormHipError", "load",
            "wrapper_diag", "wrapper_diag_blocked", "wrapper_square"]

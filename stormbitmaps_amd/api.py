@@ -220,6 +220,107 @@ class StormContig(_LagForms, _TopkForms):
             pass
 
 
+DOSAGE_MEASURES = {"r2": 0, "r": 1}  # STORM_DOSAGE_* (storm.h)
+
+
+def _device_window(device, n: int):
+    """(address, rows, leading dimension) of a 2-D torch tensor of 4-byte entries in device memory that receives an n x n
+    result (rows contiguous; the leading dimension is the tensor's row stride)"""
+    if device.dim() != 2 or device.element_size() != 4 or device.stride(1) != 1 or not device.is_cuda:
+        raise ValueError("device=: a 2-D tensor of 32-bit entries in device memory with contiguous rows")
+    if device.shape[0] < n or device.shape[1] < n:
+        raise ValueError(f"device=: a tensor of {tuple(device.shape)} cannot hold {n} x {n} entries")
+    return C.c_void_p(device.data_ptr()), int(device.shape[0]), int(device.stride(0))
+
+
+class StormDosage:
+    """STORM_dosage_t (storm.h, extension): rows of n_samples 2-bit dosages (0 / 1 / 2 copies of an allele per sample; 3 is an
+    ordinary value), their per-pair dot products and genotype correlations (PLINK --r / --r2) on the device. Missing
+    genotypes are out of scope."""
+
+    def __init__(self, n_samples: int):
+        self._lib = _lib.load()
+        self._h = self._lib.STORM_dosage_new(n_samples) if 0 <= n_samples < (1 << 64) else None
+        if not self._h:
+            raise ValueError(f"STORM_dosage_new({n_samples}): 1 .. 2^24 samples")
+        self.n_samples = n_samples
+        self.n_words = (n_samples + 31) // 32
+
+    def _check(self, what: str, rc: int) -> None:
+        if rc != 0:
+            raise RuntimeError(f"{what} -> {rc}: {self._lib.STORM_hip_error().decode()}")
+
+    def add(self, values) -> None:
+        """STORM_dosage_add: one row, one value 0 .. 3 per sample."""
+        v = np.ascontiguousarray(np.asarray(values, dtype=np.uint8))
+        self._check("STORM_dosage_add", int(self._lib.STORM_dosage_add(self._h, _ptr(v) if v.size else _ptr(np.zeros(1, np.uint8)),
+                                                                       v.size)))
+
+    def add_packed(self, words) -> None:
+        """STORM_dosage_add_packed: rows already packed, [n_rows, n_words] uint64 (32 values per word, tail bits zero)."""
+        w = np.ascontiguousarray(np.asarray(words, dtype=np.uint64))
+        if w.ndim == 1:
+            w = w.reshape(1, -1)
+        if w.ndim != 2 or w.shape[1] != self.n_words:
+            raise ValueError(f"add_packed: rows of {self.n_words} words expected, got an array of {w.shape}")
+        self._check("STORM_dosage_add_packed", int(self._lib.STORM_dosage_add_packed(self._h, _ptr(w), w.shape[0])))
+
+    def clear(self) -> None:
+        self._check("STORM_dosage_clear", int(self._lib.STORM_dosage_clear(self._h)))
+
+    @property
+    def n_rows(self) -> int:
+        return int(self._lib.STORM_dosage_n_rows(self._h))
+
+    def row_sums(self):
+        """(sum v, sum v^2) of every row, [n_rows] uint32 each, computed on the device."""
+        n = self.n_rows
+        s, q = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+        self._check("STORM_dosage_row_sums", int(self._lib.STORM_dosage_row_sums(self._h, _ptr(s), _ptr(q))))
+        return s[:n], q[:n]
+
+    def pairw_dot(self, device=None):
+        """STORM_dosage_pairw_dot: [n_rows, n_rows] uint32, entry (i, j), i < j = sum_s v_i[s] v_j[s]; 0 for i >= j.
+        device=: a 2-D torch tensor of 32-bit entries in device memory that receives the triangle instead
+        (STORM_dosage_pairw_dot_device: entries i >= j stay as they were); returns None then."""
+        n = self.n_rows
+        if device is not None:
+            ptr, rows, ld = _device_window(device, n)
+            self._check("STORM_dosage_pairw_dot_device", int(self._lib.STORM_dosage_pairw_dot_device(self._h, ptr, rows, ld)))
+            return None
+        out = np.zeros((n, n), dtype=np.uint32)
+        self._check("STORM_dosage_pairw_dot",
+                    int(self._lib.STORM_dosage_pairw_dot(self._h, _ptr(out) if out.size else _ptr(np.zeros(1, np.uint32)), n, n)))
+        return out
+
+    def pairw_corr(self, measure: str = "r2", device=None):
+        """STORM_dosage_pairw_corr: [n_rows, n_rows] float32, entry (i, j), i < j = the Pearson correlation ("r") of the two
+        dosage vectors or its square ("r2"), finished on the device; NaN against a constant row; 0 for i >= j.
+        device=: as pairw_dot (STORM_dosage_pairw_corr_device)."""
+        n = self.n_rows
+        if device is not None:
+            ptr, rows, ld = _device_window(device, n)
+            self._check("STORM_dosage_pairw_corr_device",
+                        int(self._lib.STORM_dosage_pairw_corr_device(self._h, DOSAGE_MEASURES[measure], ptr, rows, ld)))
+            return None
+        out = np.zeros((n, n), dtype=np.float32)
+        self._check("STORM_dosage_pairw_corr",
+                    int(self._lib.STORM_dosage_pairw_corr(self._h, DOSAGE_MEASURES[measure],
+                                                          _ptr(out) if out.size else _ptr(np.zeros(1, np.float32)), n, n)))
+        return out
+
+    def free(self) -> None:
+        if self._h:
+            self._lib.STORM_dosage_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Storm(_LagForms, _TopkForms):
     """STORM_t (storm.h:175-178, :225-232): rows of 65536-bit blocks, list or bitmap kind."""
     _LAG = "STORM_"

@@ -1,0 +1,234 @@
+/* storm_dosage.c — the container of 2-bit dosage rows (storm.h: STORM_dosage_*): n_samples values 0 .. 3 per row, packed
+ * 32 to a 64-bit word, and the per-pair dot products and genotype correlations (PLINK --r / --r2) of its rows.
+ *
+ * The host keeps the packed rows; they go up into an ordinary storm_hip_matrix_t on the first compute call after a change
+ * (whole, from the row the device copy ends at: rows never change once added). On storm_host.c's locked paths without
+ * adding to them, like storm_lag.c and storm_topk.c: one device slot and one process. No CPU fallback. */
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "storm.h"
+#include "storm_hip.h"
+#include "storm_host_internal.h"
+
+#define DOSAGE_MAX_SAMPLES (1ull << 24)
+
+struct STORM_dosage_s {
+    uint64_t n_samples;
+    uint32_t n_words;    /* ceil(n_samples / 32) */
+    uint64_t n_rows, m_rows;
+    uint64_t* rows;      /* n_rows x n_words, packed */
+    /* the device copy: rows [0, synced) of `m` on device slot `slot`, made under view generation `generation` */
+    storm_hip_matrix_t* m;
+    int slot;
+    uint32_t generation;
+    uint64_t synced;
+};
+
+STORM_dosage_t* STORM_dosage_new(uint64_t n_samples) {
+    if (n_samples == 0 || n_samples > DOSAGE_MAX_SAMPLES) return NULL;
+    STORM_dosage_t* h = (STORM_dosage_t*)calloc(1, sizeof(*h));
+    if (!h) return NULL;
+    h->n_samples = n_samples;
+    h->n_words = (uint32_t)((n_samples + 31u) / 32u);
+    return h;
+}
+
+/* (the caller holds the device lock) */
+static void dosage_drop_device(STORM_dosage_t* h) {
+    if (h->m) storm_hip_matrix_destroy(storm_host_open_ctx(h->slot), h->m);
+    h->m = NULL;
+    h->synced = 0;
+}
+
+void STORM_dosage_free(STORM_dosage_t* h) {
+    if (!h) return;
+    storm_host_lock();
+    dosage_drop_device(h);
+    storm_host_unlock();
+    free(h->rows);
+    free(h);
+}
+
+int STORM_dosage_clear(STORM_dosage_t* h) {
+    if (!h) return -1;
+    storm_host_lock();
+    dosage_drop_device(h);
+    storm_host_unlock();
+    h->n_rows = 0;
+    return 0;
+}
+
+uint64_t STORM_dosage_n_rows(const STORM_dosage_t* h) { return h ? h->n_rows : 0; }
+
+/* room for `more` rows: 0, or -3 with the reason */
+static int dosage_reserve(STORM_dosage_t* h, uint64_t more) {
+    if (h->n_rows + more <= h->m_rows) return 0;
+    uint64_t want = h->m_rows ? h->m_rows : 64;
+    while (want < h->n_rows + more) want *= 2;
+    if (want > SIZE_MAX / sizeof(uint64_t) / h->n_words) {
+        storm_host_error("STORM_dosage_add: the container would exceed the address space");
+        return -3;
+    }
+    uint64_t* p = (uint64_t*)realloc(h->rows, (size_t)want * h->n_words * sizeof(uint64_t));
+    if (!p) {
+        storm_host_error("STORM_dosage_add: out of host memory");
+        return -3;
+    }
+    h->rows = p;
+    h->m_rows = want;
+    return 0;
+}
+
+int STORM_dosage_add(STORM_dosage_t* h, const uint8_t* values, uint64_t n_values) {
+    if (!h) return -1;
+    if (!values) return -2;
+    if (n_values != h->n_samples) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "STORM_dosage_add: %llu values for rows of %llu samples", (unsigned long long)n_values,
+                 (unsigned long long)h->n_samples);
+        storm_host_error(msg);
+        return -3;
+    }
+    for (uint64_t s = 0; s < n_values; ++s)
+        if (values[s] > 3) {
+            char msg[160];
+            snprintf(msg, sizeof(msg), "STORM_dosage_add: value %u at sample %llu (a dosage is 0 .. 3)", (unsigned)values[s],
+                     (unsigned long long)s);
+            storm_host_error(msg);
+            return -3;
+        }
+    if (dosage_reserve(h, 1)) return -3;
+    uint64_t* row = h->rows + h->n_rows * h->n_words;
+    for (uint32_t w = 0; w < h->n_words; ++w) {
+        const uint64_t s0 = (uint64_t)w * 32u, s1 = s0 + 32u < n_values ? s0 + 32u : n_values;
+        uint64_t word = 0;
+        for (uint64_t s = s0; s < s1; ++s) word |= (uint64_t)values[s] << (2u * (s - s0));
+        row[w] = word;
+    }
+    ++h->n_rows;
+    return 0;
+}
+
+int STORM_dosage_add_packed(STORM_dosage_t* h, const uint64_t* words, uint64_t n_rows) {
+    if (!h) return -1;
+    if (!words) return -2;
+    if (n_rows == 0) return 0;
+    const uint32_t tail = (uint32_t)(h->n_samples % 32u); /* values in the last word (0: all 32) */
+    if (tail)
+        for (uint64_t r = 0; r < n_rows; ++r)
+            if (words[r * h->n_words + h->n_words - 1u] >> (2u * tail)) {
+                char msg[160];
+                snprintf(msg, sizeof(msg), "STORM_dosage_add_packed: row %llu has bits beyond sample %llu", (unsigned long long)r,
+                         (unsigned long long)h->n_samples);
+                storm_host_error(msg);
+                return -3;
+            }
+    if (n_rows > UINT64_MAX - h->n_rows) {
+        storm_host_error("STORM_dosage_add_packed: too many rows");
+        return -3;
+    }
+    if (dosage_reserve(h, n_rows)) return -3;
+    memcpy(h->rows + h->n_rows * h->n_words, words, (size_t)n_rows * h->n_words * sizeof(uint64_t));
+    h->n_rows += n_rows;
+    return 0;
+}
+
+/* the device copy brought up to date on the calling thread's slot (the caller holds the lock): NULL with the reason reported */
+static storm_hip_matrix_t* dosage_mirror(STORM_dosage_t* h, storm_hip_ctx_t** ctx_out) {
+    const uint32_t generation = storm_host_view_generation();
+    if (h->m && (h->generation != generation || h->slot != storm_host_slot() || h->synced > h->n_rows)) dosage_drop_device(h);
+    storm_hip_ctx_t* ctx = storm_host_ctx();
+    if (!ctx) return NULL;
+    if (!h->m) {
+        if (storm_hip_matrix_create(ctx, h->n_rows, h->n_words, &h->m) != STORM_HIP_OK) {
+            storm_host_device_error("storm_hip_matrix_create");
+            h->m = NULL;
+            return NULL;
+        }
+        h->slot = storm_host_slot();
+        h->generation = generation;
+        h->synced = 0;
+    }
+    if (h->synced != h->n_rows) {
+        if (storm_hip_matrix_resize(ctx, h->m, h->n_rows) != STORM_HIP_OK ||
+            storm_hip_matrix_upload(ctx, h->m, h->synced, h->n_rows - h->synced, h->rows + h->synced * h->n_words, h->n_words) !=
+                STORM_HIP_OK) {
+            storm_host_device_error("dosage upload");
+            dosage_drop_device(h);
+            return NULL;
+        }
+        h->synced = h->n_rows;
+    }
+    *ctx_out = ctx;
+    return h->m;
+}
+
+int STORM_dosage_row_sums(STORM_dosage_t* h, uint32_t* sum, uint32_t* sum_sq) {
+    if (!h) return -1;
+    if (!sum || !sum_sq) return -2;
+    storm_host_lock();
+    int rc = storm_host_one_slot_or_refuse("STORM_dosage_row_sums");
+    if (!rc && h->n_rows != 0) {
+        storm_hip_ctx_t* ctx = NULL;
+        const storm_hip_matrix_t* m = dosage_mirror(h, &ctx);
+        if (!m) rc = -3;
+        else if (storm_hip_dosage_row_sums(ctx, m, sum, sum_sq) != STORM_HIP_OK) {
+            storm_host_device_error("storm_hip_dosage_row_sums");
+            rc = -3;
+        }
+    }
+    storm_host_unlock();
+    return rc;
+}
+
+/* measure < 0: the dot products */
+static int dosage_pairw(STORM_dosage_t* h, int measure, void* out, uint64_t out_rows, uint64_t out_ld, int device, const char* who) {
+    if (!h) return -1;
+    if (!out) return -2;
+    storm_host_lock();
+    int rc = storm_host_one_slot_or_refuse(who);
+    const uint64_t n = h->n_rows;
+    if (!rc && (out_rows < n || out_ld < n)) rc = -4;
+    if (!rc && measure >= 0 && measure != STORM_DOSAGE_R2 && measure != STORM_DOSAGE_R) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "%s: measure must be 0 (STORM_DOSAGE_R2) or 1 (STORM_DOSAGE_R)", who);
+        storm_host_error(msg);
+        rc = -3;
+    }
+    if (!rc && n >= 2) {
+        storm_hip_ctx_t* ctx = NULL;
+        const storm_hip_matrix_t* m = dosage_mirror(h, &ctx);
+        if (!m) rc = -3;
+        else {
+            int hrc;
+            if (measure < 0)
+                hrc = device ? storm_hip_pairw_dosage_matrix_device(ctx, m, (uint32_t*)out, out_ld)
+                             : storm_hip_pairw_dosage_matrix(ctx, m, (uint32_t*)out, out_ld);
+            else
+                hrc = device ? storm_hip_pairw_dosage_corr_device(ctx, m, measure, h->n_samples, (float*)out, out_ld)
+                             : storm_hip_pairw_dosage_corr(ctx, m, measure, h->n_samples, (float*)out, out_ld);
+            if (hrc != STORM_HIP_OK) {
+                storm_host_device_error(measure < 0 ? "storm_hip_pairw_dosage_matrix" : "storm_hip_pairw_dosage_corr");
+                rc = -3;
+            }
+        }
+    }
+    storm_host_unlock();
+    return rc;
+}
+
+int STORM_dosage_pairw_dot(STORM_dosage_t* h, uint32_t* out, uint64_t out_rows, uint64_t out_ld) {
+    return dosage_pairw(h, -1, out, out_rows, out_ld, 0, "STORM_dosage_pairw_dot");
+}
+int STORM_dosage_pairw_dot_device(STORM_dosage_t* h, uint32_t* d_out, uint64_t out_rows, uint64_t out_ld) {
+    return dosage_pairw(h, -1, d_out, out_rows, out_ld, 1, "STORM_dosage_pairw_dot_device");
+}
+int STORM_dosage_pairw_corr(STORM_dosage_t* h, int measure, float* out, uint64_t out_rows, uint64_t out_ld) {
+    return dosage_pairw(h, measure < 0 ? STORM_DOSAGE_R + 1 : measure, out, out_rows, out_ld, 0, "STORM_dosage_pairw_corr");
+}
+int STORM_dosage_pairw_corr_device(STORM_dosage_t* h, int measure, float* d_out, uint64_t out_rows, uint64_t out_ld) {
+    return dosage_pairw(h, measure < 0 ? STORM_DOSAGE_R + 1 : measure, d_out, out_rows, out_ld, 1, "STORM_dosage_pairw_corr_device");
+}

@@ -275,6 +275,8 @@ int launch_pairw_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int o
 // the same for the pairs within max_lag rows of each other, in the lag layout (n x L instead of n x n): always K2h
 int launch_pairw_lag_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int op, uint64_t max_lag, uint64_t band_row0,
                             uint64_t band_rows, uint32_t* d_out, uint64_t ld, bool sync);
+// the dot products of rows of 2-bit values, upper triangle (K2h in its dosage form; storm_hip_dosage.hip finishes them)
+int launch_pairw_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint32_t* d_out, uint64_t ld, bool sync);
 int launch_square_mfma(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
                        const storm_hip_matrix_s* b, uint64_t* d_total);
 int launch_square_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,

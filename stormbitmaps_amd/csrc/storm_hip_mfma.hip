@@ -2129,17 +2129,19 @@ static bool choose_tile128(const storm_hip_ctx_t* ctx, uint64_t tiles256, uint64
 // Plans the K2h list (plan_tile128, storm_hip_plan.cpp; cached by its request while the same call repeats), uploads it
 // and launches tile128_kernel. lag != 0 (triangle only): the lag form — the tiles within `lag` rows of the diagonal, written
 // in the lag layout (j_base and j_count must be 0: the kernel takes the lag where the rectangle's column count travels).
+// value_bits = 2 (triangle, no lag, no row counts): the rows hold 2-bit values and the kernel writes their dot products
+// (tile128_kernel<false, 2>); the list is planned with a chunk's weight of 9 x 256.
 static int run_tile128(storm_hip_ctx_t* ctx, uint32_t ia0, uint32_t ia1, uint32_t jb0, uint32_t jb1, bool triangle,
                        uint32_t total_stages, const TileOperands& ops, uint32_t* d_out, uint64_t ld, uint32_t n_rows,
                        const uint32_t* d_counts, uint32_t and_weight, uint32_t j_base, uint32_t j_count, uint32_t i_lo,
-                       uint32_t n_cols, bool sync, uint32_t lag = 0u) {
+                       uint32_t n_cols, bool sync, uint32_t lag = 0u, uint32_t value_bits = 1u) {
     if (ia1 > 65535u || jb1 > 65535u) {
         set_error("pairw_matrix: too many row blocks");
         return STORM_HIP_EINVAL;
     }
     const Tile128Request rq = {ia0, ia1, jb0, jb1, triangle ? 1u : 0u, total_stages, (uint32_t)std::max(1, ctx->n_cus),
                                ctx->k2_part_slots, ctx->k2_part_min_chunks, ctx->k2_part_cost_diag,
-                               ctx->k2_part_narrow != 0 ? 1u : 0u, lag};
+                               ctx->k2_part_narrow != 0 ? 1u : 0u, lag, value_bits == 2u ? kThWeightDosage : kThWeightBits};
     const Tile128Request* have = std::get_if<Tile128Request>(&ctx->items_key);
     if (!(ctx->d_items && have && *have == rq)) {
         Tile128Plan plan;
@@ -2172,6 +2174,10 @@ static int run_tile128(storm_hip_ctx_t* ctx, uint32_t ia0, uint32_t ia1, uint32_
         hipLaunchKernelGGL(tile128_kernel<true>, dim3(ctx->n_part_items), dim3(kThThreads), 0, ctx->stream, ops,
                            static_cast<const PartItem*>(ctx->d_items.d), d_out, ld, n_rows, d_counts, and_weight, 0u, lag, i_lo,
                            n_cols, ctx->d_parts, ctx->d_tickets);
+    else if (ctx->n_part_items && value_bits == 2u)
+        hipLaunchKernelGGL((tile128_kernel<false, 2>), dim3(ctx->n_part_items), dim3(kThThreads), 0, ctx->stream, ops,
+                           static_cast<const PartItem*>(ctx->d_items.d), d_out, ld, n_rows, nullptr, 1u, 0u, 0u, i_lo, n_cols,
+                           ctx->d_parts, ctx->d_tickets);
     else if (ctx->n_part_items)
         hipLaunchKernelGGL(tile128_kernel<false>, dim3(ctx->n_part_items), dim3(kThThreads), 0, ctx->stream, ops,
                            static_cast<const PartItem*>(ctx->d_items.d), d_out, ld, n_rows, d_counts, and_weight, j_base,
@@ -2346,6 +2352,35 @@ int launch_pairw_lag_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, i
                          sync, (uint32_t)L);
     }
     if (rc == STORM_HIP_EHIP) set_error("pairw_lag_matrix: HIP failure");
+    return rc;
+}
+
+// The dot products of rows of 2-bit values (storm_hip_pairw_dosage_matrix_device): out[i * ld + j] = sum_s v_i[s] v_j[s] for
+// i < j < n_rows, value s of a row in bits 2 (s % 32), 2 (s % 32) + 1 of word s / 32 (device pointer, uint32). Always K2h in
+// its dosage form (tile128_kernel<false, 2>), whatever k2_tile_shape says: the other output kernels know bits only.
+int launch_pairw_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint32_t* d_out, uint64_t ld, bool sync) {
+    const uint64_t n = m->n_rows;
+    if (n < 2) return STORM_HIP_OK;
+    const uint64_t pitch = m->stride_words * 8;
+    if (pitch * 128u >= (1ull << 32)) {
+        set_error("pairw_dosage_matrix: rows of %llu operand bytes exceed the tile kernel's 32-bit DMA offsets",
+                  (unsigned long long)pitch);
+        return STORM_HIP_EINVAL;
+    }
+    if ((n + kThTile - 1) / kThTile > 65535u) {
+        set_error("pairw_dosage_matrix: too many row blocks");
+        return STORM_HIP_EINVAL;
+    }
+    ctx->k2_tile_shape_eff = 7;   // (option k2_tile_shape_used: 6 = K2h on bits, 7 = K2h on 2-bit values)
+    ctx->pass_report[0] = STORM_HIP_RAN_TILES_OUT;
+    ctx->pass_report[1] = n * (n - 1) / 2 * m->n_words;
+    ctx->pass_report[2] = ctx->pass_report[3] = 0;
+    const TileOperands ops = {reinterpret_cast<const uint8_t*>(m->d), nullptr, pitch, 0xffffffffu,
+                              (uint32_t)std::min<uint64_t>(m->n_rows_pad, 0xffffffffu), 0u};
+    const int rc = run_tile128(ctx, 0u, (uint32_t)((n + kThTile - 1) / kThTile), 0u, (uint32_t)((n + kThTile - 1) / kThTile), true,
+                               (m->n_words + 7u) / 8u * 4u, ops, d_out, ld, (uint32_t)n, nullptr, 1u, 0u, 0u, 0u, (uint32_t)n, sync,
+                               0u, 2u);
+    if (rc == STORM_HIP_EHIP) set_error("pairw_dosage_matrix: HIP failure");
     return rc;
 }
 

@@ -501,7 +501,11 @@ void plan_tile128(const Tile128Request& rq, Tile128Plan* plan) {
     plan->n_windows = 0;
     plan->items.clear();
     if (tiles.empty() || nC == 0) return;
-    constexpr uint32_t kMaxExactChunks = (1u << 24) / 512u - 1u;   // f32 accumulators: an item stays below 2^24 bits of k
+    // f32 accumulators: an item's chunks x weight stay at or below 2^24 (bits: 32767 chunks, below 2^24 bits of k;
+    // 2-bit values: 7281 chunks)
+    const uint32_t weight = std::max(rq.chunk_weight, 1u);
+    const uint32_t kMaxExactChunks = ((1u << 24) - 1u) / weight;
+    const uint32_t max_narrow_chunks = 65535u / weight;   // 16-bit windows: 127 chunks of bits, 28 of 2-bit values
     constexpr double kItemChunks = 5.0;                             // what an item costs besides its chunks, in chunks
     min_chunks = std::max(min_chunks, (int)(nC / 32000u) + 1);      // (a tile has fewer than 2^15 parts: PartItem::part)
     const uint32_t min_parts = (nC + kMaxExactChunks - 1) / kMaxExactChunks;
@@ -541,8 +545,8 @@ void plan_tile128(const Tile128Request& rq, Tile128Plan* plan) {
     }
     for (uint32_t t = 0; t < nT; ++t) {
         const uint32_t np = best_parts[t];
-        // windows of 16-bit counts while every part of the tile stays below 2^16 bits of k (127 chunks)
-        const uint16_t narrow = (np > 1 && (nC + np - 1) / np <= 127u && narrow_windows) ? kThNarrow : (uint16_t)0;
+        // windows of 16-bit counts while every part of the tile stays below 2^16 (bits: 127 chunks of k)
+        const uint16_t narrow = (np > 1 && (nC + np - 1) / np <= max_narrow_chunks && narrow_windows) ? kThNarrow : (uint16_t)0;
         for (uint32_t p = 0; p < np; ++p) {
             const uint32_t c0 = (uint32_t)((uint64_t)nC * p / np), c1 = (uint32_t)((uint64_t)nC * (p + 1) / np);
             plan->items.push_back({tiles[t].I, tiles[t].J, c0 * 4u, (c1 - c0) * 4u, t, np > 1 ? plan->n_windows : 0u,
@@ -1266,16 +1270,41 @@ extern "C" int storm_hip_matrix_plan(uint64_t n_rows_a, uint64_t n_rows_b, uint3
             if (band_row0 < end)
                 plan_tile128({(uint32_t)(band_row0 / kThTile), (uint32_t)((end + kThTile - 1) / kThTile), 0u,
                               (uint32_t)((n_rows_a + kThTile - 1) / kThTile), 1u, total_stages, n_cus, slots_per_cu, min_chunks,
-                              diag_cost_pct, 1u, 0u}, &plan);
+                              diag_cost_pct, 1u, 0u, kThWeightBits}, &plan);
         } else {   // rectangle: B's tiles count on behind A's rows padded to 256
             const uint64_t rows_a = (n_rows_a + kTile - 1) / kTile * kTile;
             plan_tile128({0u, (uint32_t)((n_rows_a + kThTile - 1) / kThTile), (uint32_t)(rows_a / kThTile),
                           (uint32_t)((rows_a + n_rows_b + kThTile - 1) / kThTile), 0u, total_stages, n_cus, slots_per_cu,
-                          min_chunks, diag_cost_pct, 1u, 0u}, &plan);
+                          min_chunks, diag_cost_pct, 1u, 0u, kThWeightBits}, &plan);
         }
         return export_part_items("matrix_plan", plan, out, capacity_items, n_items);
     } catch (const std::exception& e) {
         set_error("matrix_plan: %s", e.what());
+        return STORM_HIP_ENOMEM;
+    }
+}
+
+// The K2h list of the dosage form (launch_pairw_dosage_matrix): the triangle of one matrix of rows of 2-bit values, planned
+// with a chunk's weight of 9 x 256. Arguments and records as storm_hip_matrix_plan; the rectangle has no dosage form.
+extern "C" int storm_hip_dosage_plan(uint64_t n_rows_a, uint64_t n_rows_b, uint32_t n_words, uint64_t band_row0,
+                                     uint64_t band_rows, uint32_t n_cus, int slots_per_cu, int min_chunks, int diag_cost_pct,
+                                     uint32_t* out, uint64_t capacity_items, uint64_t* n_items) {
+    using namespace storm;
+    if (!n_items || n_rows_a == 0 || n_rows_b != 0 || n_words == 0 || n_cus == 0 || slots_per_cu < 0 || slots_per_cu > 2 ||
+        min_chunks < 1 || diag_cost_pct < 10 || diag_cost_pct > 100 || (n_rows_a + kThTile - 1) / kThTile > 65535u) {
+        set_error("dosage_plan: bad arguments (the dosage form is the triangle of one matrix: n_rows_b must be 0)");
+        return STORM_HIP_EINVAL;
+    }
+    try {
+        Tile128Plan plan;
+        const uint64_t end = std::min(n_rows_a, band_row0 + std::min(band_rows ? band_rows : n_rows_a, n_rows_a));
+        if (band_row0 < end)
+            plan_tile128({(uint32_t)(band_row0 / kThTile), (uint32_t)((end + kThTile - 1) / kThTile), 0u,
+                          (uint32_t)((n_rows_a + kThTile - 1) / kThTile), 1u, (n_words + 7u) / 8u * 4u, n_cus, slots_per_cu,
+                          min_chunks, diag_cost_pct, 1u, 0u, kThWeightDosage}, &plan);
+        return export_part_items("dosage_plan", plan, out, capacity_items, n_items);
+    } catch (const std::exception& e) {
+        set_error("dosage_plan: %s", e.what());
         return STORM_HIP_ENOMEM;
     }
 }
@@ -1297,7 +1326,7 @@ extern "C" int storm_hip_lag_plan(uint64_t n_rows, uint32_t n_words, uint64_t ma
         if (band_row0 < end && lag)
             plan_tile128({(uint32_t)(band_row0 / kThTile), (uint32_t)((end + kThTile - 1) / kThTile), 0u,
                           (uint32_t)((n_rows + kThTile - 1) / kThTile), 1u, (n_words + 7u) / 8u * 4u, n_cus, slots_per_cu,
-                          min_chunks, diag_cost_pct, 1u, lag}, &plan);
+                          min_chunks, diag_cost_pct, 1u, lag, kThWeightBits}, &plan);
         return export_part_items("lag_plan", plan, out, capacity_items, n_items);
     } catch (const std::exception& e) {
         set_error("lag_plan: %s", e.what());

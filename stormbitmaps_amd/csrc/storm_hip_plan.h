@@ -82,6 +82,8 @@ struct PartItem {
 };
 static_assert(sizeof(PartItem) == 24, "read by device code");
 constexpr uint16_t kThNarrow = 0x8000u;
+constexpr uint32_t kThWeightBits = 512u;           // 512 products of 1
+constexpr uint32_t kThWeightDosage = 9u * 256u;    // 256 products of two values 0 .. 3
 
 // A "range" is a run of rows [r0, r1) that forms one all-pairs problem: the whole matrix for the dense container, one
 // block column of the pool for the sparse one. r0 is a multiple of the A tile (256 rows; 512 for the wide strips) and
@@ -185,6 +187,9 @@ struct Tile128Request {
     int32_t slots_per_cu, min_chunks, diag_cost_pct;   // options k2_part_slots, k2_part_min_chunks, k2_part_cost_diag
     uint32_t narrow_windows;                           // option k2_part_narrow
     uint32_t lag;   // 0: none. Triangle only: just the tiles that hold a pair i < j with j - i <= lag (the lag layout's list)
+    uint32_t chunk_weight;   // the most one 512-bit chunk adds to an accumulator: kThWeightBits, or kThWeightDosage for rows of
+                             // 2-bit values. An item stays at chunks x weight <= 2^24 (f32 accumulators), a narrow window's
+                             // part at <= 65535
     bool operator==(const Tile128Request& o) const { return same_request(*this, o); }
 };
 struct Tile128Plan {

@@ -2584,6 +2584,11 @@ sparse_state_t* storm_host_checked_state(STORM_t* h) {
 int storm_host_build(STORM_t* h, sparse_state_t* st, int dense, storm_dense_builder_t wide, uint32_t min_blocks) {
     return storm_build_device_wide(h, st, dense, wide, min_blocks);
 }
+uint32_t storm_host_view_generation(void) {
+    configure_from_env();
+    return VIEW_GENERATION;
+}
+storm_hip_ctx_t* storm_host_open_ctx(int slot) { return slot >= 0 && slot < MAX_DEVICES ? g_ctx[slot] : NULL; }
 void storm_host_drop_dense(sparse_state_t* st) {
     for (int d = 0; d < MAX_DEVICES; ++d)
         if (st->m[d]) {

@@ -1,6 +1,6 @@
 /* storm_host_internal.h — what the host side of the storm.h containers shares between its files: the device state of a
  * STORM_t handle (storm_host.c) and the helpers the rectangle of two containers (storm_square.c) and the lag forms
- * (storm_lag.c) and the top-k forms (storm_topk.c) run on. Not installed. */
+ * (storm_lag.c), the top-k forms (storm_topk.c) and the dosage container (storm_dosage.c) run on. Not installed. */
 #ifndef STORM_HOST_INTERNAL_H_
 #define STORM_HOST_INTERNAL_H_
 #include <stdint.h>
@@ -42,6 +42,9 @@ sparse_state_t* storm_host_checked_state(STORM_t* h);
 /* storm_build_device: dense = 0 arena, 1 dense replica (`wide` with min_blocks, or NULL: own width), 2 row lists */
 int storm_host_build(STORM_t* h, sparse_state_t* st, int dense, storm_dense_builder_t wide, uint32_t min_blocks);
 void storm_host_drop_dense(sparse_state_t* st);
+/* what a device copy kept in a handle is valid for: changes with the device configuration and the thread's view */
+uint32_t storm_host_view_generation(void);
+storm_hip_ctx_t* storm_host_open_ctx(int slot);      /* the context of `slot` if one is open (NULL: none; nothing is created) */
 
 /* storm_square.c: the dense replicas of two containers at one common width (the wider of the two, or of a replica one of
  * them already keeps) on device slot `slot`; 0, or nonzero with the reason reported */

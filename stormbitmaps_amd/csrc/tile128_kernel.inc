@@ -42,14 +42,29 @@ constexpr uint32_t kThSlotBytes = 2u * kThTile * 64u;   // 16 KiB: A rows 0 .. 1
 constexpr uint32_t kThRing = 4u;
 constexpr uint32_t kThWindowWords = kThTile * kThTile;   // a part's window: 64 KiB of uint32
 
+// Dosage form (kBits = 2, DESIGN.md §4 "K2h, dosage form"): a row holds VALUES 0 .. 3 in 2 bits each instead of bits, and
+// the kernel writes the dot products sum_k v_i[k] v_j[k]. A nibble then holds two values, and the low two bits of a nibble
+// read as E2M1 are 0, 0.5, 1.0, 1.5: linear in the value. So there are two classes per piece instead of four — class 0:
+// w & 0x33333333, class 1: (w >> 2) & 0x33333333 — and block scale 128 (x 2) on both operands of both makes the operand
+// the value itself; 16 multiply steps per trip instead of 32. A chunk (256 values) adds up to 9 x 256 = 2304 to an
+// accumulator: the host plans the k-parts and the narrow windows by that weight (plan_tile128, chunk_weight). Triangle
+// only, row_counts null.
+template <int C>
+__device__ __forceinline__ v4i th_inflate2(v4i w) {
+    typedef unsigned v4u __attribute__((ext_vector_type(4)));
+    if constexpr (C == 1) return (v4i)(((v4u)w >> 2u) & 0x33333333u);
+    else return w & (int)0x33333333u;
+}
 
-template <bool kLag>
+template <bool kLag, int kBits = 1>
 __global__ __launch_bounds__(kThThreads, 2) void tile128_kernel(
     TileOperands ops, const PartItem* __restrict__ items, uint32_t* __restrict__ out, uint64_t ld,
     uint32_t n_rows, const uint32_t* __restrict__ row_counts, uint32_t and_weight, uint32_t j_base,
     uint32_t j_count, uint32_t i_lo, uint32_t n_cols, uint32_t* __restrict__ parts, uint32_t* __restrict__ tickets) {
     __shared__ __attribute__((aligned(1024))) uint8_t lds[kThRing * kThSlotBytes];
     __shared__ uint32_t ticket_seen;
+    static_assert(kBits == 1 || (kBits == 2 && !kLag), "bits, or 2-bit values in the triangle form");
+    constexpr int kClasses = kBits == 1 ? 4 : 2;   // multiply steps per piece
     STORM_CLOCK_BEGIN();
 
     const uint32_t tid = threadIdx.x;
@@ -145,16 +160,17 @@ __global__ __launch_bounds__(kThThreads, 2) void tile128_kernel(
             __builtin_amdgcn_sched_barrier(0);
             tb_static_for<4>([&](auto gc) __attribute__((always_inline)) {
                 constexpr int g = decltype(gc)::value;
-                fr[0][g] = tb_inflate<0>(raw[0][g]);
+                if constexpr (kBits == 1) fr[0][g] = tb_inflate<0>(raw[0][g]);
+                else fr[0][g] = th_inflate2<0>(raw[0][g]);
             });
         }
 
-        // ---- four chunks per trip: 8 pieces x 4 classes = 32 multiply steps of 4 MFMAs
+        // ---- four chunks per trip: 8 pieces x 4 classes = 32 multiply steps of 4 MFMAs (2-bit values: x 2 classes = 16)
         const uint32_t n_trips = (nC + 3u) / 4u;
         for (uint32_t trip = 0; trip < n_trips; ++trip) {
-            tb_static_for<32>([&](auto sc) __attribute__((always_inline)) {
+            tb_static_for<8 * kClasses>([&](auto sc) __attribute__((always_inline)) {
                 constexpr int s = decltype(sc)::value;
-                constexpr int c = s & 3, P = s >> 2, cur = s & 1;
+                constexpr int c = s % kClasses, P = s / kClasses, cur = s & 1;
                 if constexpr (c == 0 && (P & 1) == 0) {
                     // top of chunk q = P / 2: the NEXT chunk has landed for everybody (this wave's share: all but its 4
                     // youngest pieces), and everybody has read the last of the chunk before — its slot takes the chunk
@@ -167,11 +183,12 @@ __global__ __launch_bounds__(kThThreads, 2) void tile128_kernel(
                 if constexpr (kWork) {
                     // the piece after this one: its registers held the piece before (every class inflated two steps ago)
                     if constexpr (c == 0) read_piece(std::integral_constant<int, (P + 1) & 7>{});
-                    if constexpr (c == 3) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the next piece's fragments
+                    if constexpr (c == kClasses - 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the next piece's fragments
                     __builtin_amdgcn_sched_barrier(0);
                     // what the NEXT step multiplies: class c + 1 of this piece, or class 0 of the next piece
-                    constexpr int cn = (c + 1) & 3;
-                    constexpr int pn = c == 3 ? ((P + 1) & 1) : (P & 1);
+                    constexpr int cn = (c + 1) % kClasses;
+                    constexpr int pn = c == kClasses - 1 ? ((P + 1) & 1) : (P & 1);
+                    const int scale = kBits == 1 ? tb_scale<c>() : 128;
                     tb_static_for<4>([&](auto qc) __attribute__((always_inline)) {
                         constexpr int q = decltype(qc)::value;
                         constexpr int m = q >> 1, n = q & 1;
@@ -179,8 +196,9 @@ __global__ __launch_bounds__(kThThreads, 2) void tile128_kernel(
                             acc[m][n] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
                                 v8i{fr[cur][m].x, fr[cur][m].y, fr[cur][m].z, fr[cur][m].w, 0, 0, 0, 0},
                                 v8i{fr[cur][2 + n].x, fr[cur][2 + n].y, fr[cur][2 + n].z, fr[cur][2 + n].w, 0, 0, 0, 0},
-                                acc[m][n], 4, 4, 0, tb_scale<c>(), 0, tb_scale<c>());
-                        fr[cur ^ 1][q] = tb_inflate<cn>(raw[pn][q]);
+                                acc[m][n], 4, 4, 0, scale, 0, scale);
+                        if constexpr (kBits == 1) fr[cur ^ 1][q] = tb_inflate<cn>(raw[pn][q]);
+                        else fr[cur ^ 1][q] = th_inflate2<cn>(raw[pn][q]);
                         __builtin_amdgcn_sched_barrier(0);
                     });
                 }
