@@ -355,6 +355,11 @@ int storm_hip_column_identity(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m,
  *        "k2_strip_operands" (0): operands of the strips: 0 / 5 = the bit matrix itself, the FP4 image of every B
  *        stage built in the LDS by the workgroup (K2b, the default); 4 = FP4 shadow (expansion pass + strips); 2 = one
  *        stage stream per workgroup on bit operands (K2q); 1 / 3: tools build only;
+ *        "k2_strip_rows" (0): K2b's A rows per wave: 64 = 256-row A tiles on slices of a class pair of 512 bits
+ *        (strip16_bits_kernel); 128 = 512-row A tiles on slices of 128 bits, one image store and four fragment reads per
+ *        stage instead of two and eight (strip16_rows_kernel) — only where the matrix's zero rows reach the next multiple
+ *        of 512, otherwise 64 runs; 0 = by measurement: 128 for one device's whole pass over 2048 rows x 65536 bits and
+ *        more. Read-only "k2_strip_rows_used": what the last K2b launch ran ("k2_operands_used" is 5 for both);
  *        "k2_tile_shape" (0): materialised-output kernel: 0 = by the matrix (5 for a dense matrix, 2 for the dense
  *        replica of a sparse container); 5 = tilering_kernel: both operands as FP4 images built once per workgroup in the
  *        LDS, 16x16x128 MFMAs, SIMD partners half a stage apart ("k2_ring_sync" (0): 0 = one barrier per stage, 1 = arrival
@@ -418,6 +423,9 @@ int storm_hip_strip_plan(uint64_t n_rows, uint32_t n_words, uint32_t shard_rank,
  *   form 1: the strips on bit operands (K2b, the DEFAULT path): slice ks = class pair ks & 1 — the bits b of
  *           the 512-bit chunk ks / 2 (bits [512 (ks / 2), +512)) with (b % 4) / 2 == ks & 1 — 256 bit positions
  *           as well; 2 x ceil(n_words / 8) slices;
+ *   form 2: K2b with 128 A rows per wave (option k2_strip_rows = 128): slice ks = bits [128 ks, 128 ks + 128) of
+ *           every row, ceil(n_words / 2) slices; the A tile is 512 rows (a_row0 a multiple of 512, 8 own blocks), the
+ *           ownership units are 4 slices = 64 bytes of every row;
  *   pair_space 0: whole k-slices first, leftover slices along the pair space (above);
  *   pair_space 1: EVERY slice is cut along the pair space (context option k2_shard_pairs): a shard multiplies
  *           its share of every slice's items (longest first onto the least loaded shard, the load carried

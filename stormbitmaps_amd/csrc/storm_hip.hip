@@ -734,6 +734,8 @@ static const std::vector<OptionRow>& option_table() {
          "k2_strip_operands must be 0 (by size), 1 (bit operands, one item per workgroup), 2 (bit operands, one stream per workgroup), 3 (the same with a ring per wave), 4 (FP4 shadow), 5 (bit operands, FP4 image built in the LDS) or 6 (the same with 512-row A tiles, two halves behind one image)",
          {1, 3},
          "k2_strip_operands = 1 (stripbits_kernel) and 3 (bitwave_kernel) are forms of the tools build (`make probes`), not of the shipped library"},
+        {"k2_strip_rows", &C::k2_strip_rows, SET, 0, 0, 0, {0, 64, 128},
+         "k2_strip_rows must be 0 (by rule), 64 (64 A rows per wave, 256-row A tiles) or 128 (128 A rows per wave on 128-bit slices, 512-row A tiles)"},
         {"k2_shard_pairs", &C::k2_shard_pairs, BOOL},
         {"k2_matrix_pad", &C::k2_matrix_pad, HOOK, 0, 0, 0, {}, nullptr, {}, nullptr, set_matrix_pad},     // clamps to -1 / 0 .. 64
         {"k2_fold_inline", &C::k2_fold_inline, HOOK, 0, 0, 0, {}, nullptr, {}, nullptr, set_fold_inline},  // normalises to -1 / 0 / 1
@@ -809,6 +811,7 @@ int64_t storm_hip_ctx_get_option(storm_hip_ctx_t* ctx, const char* key) {
     // read-only names
     if (!strcmp(key, "variant_used")) return ctx->variant_used;
     if (!strcmp(key, "k2_operands_used")) return ctx->k2_operands_used;
+    if (!strcmp(key, "k2_strip_rows_used")) return ctx->k2_strip_rows_used;
     if (!strcmp(key, "k2_tile_shape_used")) return ctx->k2_tile_shape_eff;
     if (!strcmp(key, "n_cus")) return ctx->n_cus;
     if (!strcmp(key, "probes_build") || !strcmp(key, "probes_built")) return kToolsBuild;

@@ -184,6 +184,8 @@ struct storm_hip_ctx_s {
     int k2_matrix_pad = -1;         // matrices created from now on: rows that are a multiple of 1 KiB get this many 512-byte chunks more of pitch (0: dense pitch; -1: by the pitch, pitch_pad_chunks)
     int k2_fold_inline = -1;        // K2b: the workgroup dispatched last folds the partial sums inside the launch: -1 = for short launches (<= 4096 workgroups, where the fold launch and its gaps are a fifth of a pass), 1 = always (level at N = 10000), 0 = never (a fold launch behind the strips); profiles/r05_c_fold_ab.jsonl
     int k2_operands_used = 4;       // what the last strip launch ran (1, 2 or 4)
+    int k2_strip_rows = 0;          // K2b: A rows per wave: 64 = strip16_bits_kernel (256-row A tiles, slices of a class pair of 512 bits), 128 = strip16_rows_kernel (512-row A tiles, slices of 128 bits) where the matrix's zero rows reach the next multiple of 512 (otherwise 64), 0 = by the rule (strip_rows128_by_rule, storm_hip_mfma.hip)
+    int k2_strip_rows_used = 64;    // what the last K2b launch ran: 64 or 128
     int k2_tile_shape = 0;  // write-mode tile kernel: 0 = by the matrix (5 for a dense matrix, 2 for the dense replica of a sparse container: sparse operands let tilebits8_kernel, which sits at the socket's power cap, clock higher; crossover near 20 % density, profiles/r05_g_*); 5 = tilering_kernel (both operands as FP4 images in the LDS, 16x16x128); 2 = tilebits8_kernel (bit operands inflated in registers, 32x32x64); 3 / 4 = K2tb; 1 / 16 / 32: tools build
     int k2_wave_below = 400;      // [r6] k2_tile_shape 0: matrices (bands, rectangles) of fewer 256 x 256 tiles than this take tile128_kernel (K2h: 128 x 128 tiles, cut along k where they are too few, the parts' sums meeting inside the launch; no window clearing, no atomics into the output)
     int k2_part_slots = 0;        // K2h: segments per CU the tiles' chunk stream is cut into: 0 = two once that leaves segments of 4 x k2_part_min_chunks, else one; 1 / 2: forced
@@ -259,7 +261,8 @@ int strip_operands_of(const storm_hip_ctx_t* ctx);   // 5 = K2b, 4 = FP4 strips,
 int launch_pairw_bits_ranges(storm_hip_ctx_t* ctx, const uint8_t* X, uint64_t pitch_bytes,
                              const std::vector<RowRange>& ranges, uint32_t n_kslices2, uint32_t shard_rank,
                              uint32_t shard_count, uint64_t* d_total, bool slots_hold_sums = false,
-                             uint32_t a_tile = 256u);   // a_tile 512: strip16_bits2_kernel (the last tile's rows up to the multiple of 512 must exist and be zero)
+                             uint32_t a_tile = 256u,    // a_tile 512: strip16_bits2_kernel (the last tile's rows up to the multiple of 512 must exist and be zero)
+                             bool rows128 = false);     // strip16_rows_kernel: a_tile 512, n_kslices2 = its slices of 16 bytes (strip_rows_kslices)
 // pairs x words of a set of row ranges, divided among shard_count shards (the report's algorithmic word pairs)
 static inline uint64_t ranges_word_pairs(const std::vector<RowRange>& ranges, uint64_t words, uint32_t shard_count) {
     uint64_t pairs = 0;

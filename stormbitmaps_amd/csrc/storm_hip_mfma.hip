@@ -720,6 +720,41 @@ __device__ __forceinline__ v4i sb16_inflate(v4i w, uint32_t rot) {
 #undef STORM_SB16_WAVES
 #undef STORM_SB16_NAME
 
+// K2b with 128 A rows per wave (strip16_rows_kernel, option k2_strip_rows = 128): the same 96 registers spent the other way
+// round. strip16_bits_kernel keeps 64 A rows x 256 bit-MACs per wave (a[2][4]) and accumulates 64 x 64: a B fragment meets
+// the 4 A fragments of its k-step. Here a wave keeps 128 A rows x 128 bit-MACs — 8 A fragments of ONE k-step, blocks w and
+// w + 4 of a 512-row A tile — and accumulates 128 x 32 (acc[8][2]): every B fragment feeds 8 MFMAs.
+//   * k-slice `ks` = the 16 bytes [16 ks, 16 ks + 16) of every row, all four bit classes of its four dwords; element order
+//     inside the k-step = (dword, class, nibble) on both sides (sr16_inflate builds both).
+//   * B stage = 64 rows x 16 B = 1 KiB of bits: wave w DMAs its 16 rows as 4 bytes per lane (256 B per wave and slot, ring
+//     of 3, own vmcnt), reads its dword back (ds_read_b32), inflates the four classes (7 VALU) and writes ONE ds_write_b128
+//     into the image: 64 rows x 64 B = 4 KiB, ring of 3.
+//   per 64 B rows and wave    strip16_bits_kernel    strip16_rows_kernel
+//   MFMAs                     32                     32
+//   fragment ds_read_b128     8                      4
+//   image ds_write_b128       2                      1
+//   inflation VALU            16                     7
+//   piece read-back           ds_read_b128           ds_read_b32
+//   LDS per workgroup         36 KiB                 15 KiB
+// Ring protocol, barrier per stage, diagonal phase outside the pipelined loop, epilogue and fold: strip16_bits_kernel's.
+// The A tile has 8 own blocks, so an item with a diagonal spends 8 non-pipelined stages where the 256-row form spends 4.
+constexpr uint32_t kSr16SliceBytes = 16;                          // a k-slice of a row: 128 bits
+constexpr uint32_t kSr16PerTile = kStripRowsATile / kStripBRows;  // 8 own blocks
+constexpr uint32_t kSr16StageBytes = kStripBRows * 64;            // an FP4 image: 64 rows x 64 B
+constexpr uint32_t kSr16ImgBytes = 3 * kSr16StageBytes;
+constexpr uint32_t kSr16BitRing = 3;
+constexpr uint32_t kSr16BitStage = 4 * 256;                       // 1 KiB of bits per B stage, 256 B per wave
+
+__device__ __forceinline__ v4i sr16_inflate(uint32_t w) {   // the four classes of one dword: class c = rotate right by c - 1
+    v4i e;
+    e.x = (int)(__builtin_amdgcn_alignbit(w, w, 31u) & kSb16Mask);
+    e.y = (int)(w & kSb16Mask);
+    e.z = (int)(__builtin_amdgcn_alignbit(w, w, 1u) & kSb16Mask);
+    e.w = (int)(__builtin_amdgcn_alignbit(w, w, 2u) & kSb16Mask);
+    return e;
+}
+#include "strip16_rows_kernel.inc"
+
 // ------------------------------------------------------------------------------------------
 // K2t16: write-mode tile kernel on v_mfma_scale_f32_16x16x128_f8f6f4 (materialised XX^T, AND /
 // OR / XOR counts, triangle / band / rectangle). Same items and output conventions as
@@ -2573,21 +2608,27 @@ int launch_pairw_bitstream(storm_hip_ctx_t* ctx, const uint64_t* X, uint64_t pit
 // sparse container: the pool rows of its block columns.
 int launch_pairw_bits_ranges(storm_hip_ctx_t* ctx, const uint8_t* X, uint64_t pitch,
                              const std::vector<RowRange>& ranges, uint32_t n_kslices2, uint32_t shard_rank,
-                             uint32_t shard_count, uint64_t* d_total, bool slots_hold_sums, uint32_t a_tile) {
+                             uint32_t shard_count, uint64_t* d_total, bool slots_hold_sums, uint32_t a_tile, bool rows128) {
     if (pitch * (uint64_t)kStripBRows >= (1ull << 32)) {
         set_error("K2b: rows of %llu bytes are beyond the strips' 32-bit DMA offsets", (unsigned long long)pitch);
         return STORM_HIP_EINVAL;
     }
     ctx->n_items = 0;  // the strip items carry the diagonal tiles themselves
     ctx->items_key = std::monostate{};
-    if (int rc = ensure_strip_items(ctx, ranges, n_kslices2, shard_rank, shard_count, a_tile, 2))
+    // (rows128 — strip16_rows_kernel: n_kslices2 counts slices of 16 bytes, a_tile is 512, the 8 slices of a 128-byte line share an XCD)
+    if (rows128 && a_tile != kStripRowsATile) {
+        set_error("K2b: the 128-rows-per-wave form takes A tiles of 512 rows");
+        return STORM_HIP_EINVAL;
+    }
+    if (int rc = ensure_strip_items(ctx, ranges, n_kslices2, shard_rank, shard_count, a_tile, rows128 ? (int)kStripRowsXcdGroup : 2))
         return rc;
     const uint32_t n_strip = ctx->n_strip_items;
-    const uint32_t waves = a_tile / (uint32_t)kStripBRows;   // 4, or 8 for the 512-row form (strip16_bits2_kernel)
+    const uint32_t waves = rows128 ? 4u : a_tile / (uint32_t)kStripBRows;   // 4, or 8 for the 512-row form (strip16_bits2_kernel)
     ctx->k2_operands_used = waves == 8u ? 6 : 5;
+    ctx->k2_strip_rows_used = rows128 ? 128 : 64;
     if (n_strip > 0) {
         ctx->pass_report[0] |= STORM_HIP_RAN_BIT_STRIPS;
-        ctx->pass_report[1] += ranges_word_pairs(ranges, (uint64_t)n_kslices2 * 4u, shard_count);  // a slice = 256 bit-MACs per pair = 4 words
+        ctx->pass_report[1] += ranges_word_pairs(ranges, (uint64_t)n_kslices2 * (rows128 ? 2u : 4u), shard_count);  // a slice = 256 bit-MACs per pair = 4 words (rows128: 128 = 2 words)
     }
     ctx->last_info[0] = n_strip;
     ctx->last_info[1] = ctx->k2_stages_per_item;
@@ -2602,13 +2643,19 @@ int launch_pairw_bits_ranges(storm_hip_ctx_t* ctx, const uint8_t* X, uint64_t pi
     const uint32_t fold_slots = n_strip <= 4096u ? 256u : (uint32_t)kSlots;
     const bool fold_wanted = ctx->k2_fold_inline > 0 || (ctx->k2_fold_inline < 0 && n_strip <= 4096u);
     const uint64_t arrivals_per_slot = (uint64_t)n_strip * (uint64_t)waves / (uint64_t)fold_slots + 1u;
-    const uint64_t wave_sum_max = 64ull * (4096ull * 64ull + 256ull) * 256ull;   // (runs are capped at 4096 stages)
+    // (rows128: 128 rows x (run x 64 + 512) rows x 128 bits)
+    const uint64_t wave_sum_max = rows128 ? 128ull * (4096ull * 64ull + 512ull) * 128ull
+                                          : 64ull * (4096ull * 64ull + 256ull) * 256ull;   // (runs are capped at 4096 stages)
     // (slots_hold_sums: another kernel of this pass — the list-probe kernel — has added sums of unknown size: fold launch)
     const bool fold_inline = fold_wanted && !slots_hold_sums && n_strip > 0 && arrivals_per_slot < 65535u &&
                              arrivals_per_slot * wave_sum_max < (1ull << 48);
     if (n_strip > 0) {
         kernel_time_mark(ctx);
-        if (waves == 8u)
+        if (rows128)
+            hipLaunchKernelGGL(strip16_rows_kernel, dim3(n_strip), dim3(256), (size_t)ctx->k2_lds_pad,
+                               ctx->stream, X, pitch, ctx->d_strip_items.d, ctx->d_slots,
+                               fold_inline ? reinterpret_cast<unsigned long long*>(d_total) : nullptr, fold_slots);
+        else if (waves == 8u)
             hipLaunchKernelGGL(strip16_bits2_kernel, dim3(n_strip), dim3(512), (size_t)ctx->k2_lds_pad,
                                ctx->stream, X, pitch, ctx->d_strip_items.d, ctx->d_slots,
                                fold_inline ? reinterpret_cast<unsigned long long*>(d_total) : nullptr, fold_slots);
@@ -2620,6 +2667,23 @@ int launch_pairw_bits_ranges(storm_hip_ctx_t* ctx, const uint8_t* X, uint64_t pi
         STORM_HIP_TRY(hipGetLastError());
     }
     return fold_inline ? STORM_HIP_OK : launch_fold_slots(ctx, d_total);
+}
+
+// K2b's A rows per wave (option k2_strip_rows): 128 = strip16_rows_kernel, wherever the zero rows of the allocation reach the
+// next multiple of 512 (its A tile; option 6's rule) — otherwise, and for 64, strip16_bits_kernel. 0 = by measurement
+// (profiles/k2b_rows128_ab.txt: kernel time by HIP events, the forms alternating in one process, two rounds; 256-row form
+// -> 128 rows per wave): 10000 x 65536 0.755 -> 0.721 ms, 10000 x 524288 6.11 -> 5.64, 8192 x 65536 0.512 -> 0.488,
+// 4096 x 65536 0.1422 -> 0.1331, 2048 x 65536 0.0450 -> 0.0442 — ahead by 1.5 .. 7.7 %, everywhere more than three times the
+// 256-row form's own spread between the rounds (0.1 .. 0.4 %). The rule takes the new form inside what was measured: one
+// device's whole pass, from 2048 rows of 65536 bits up. Smaller matrices (the diagonal phase is 8 of an item's stages, not
+// 4, and at 2048 rows the margin is down to 1.5 %), narrower rows (fewer than 512 slices for 8 XCDs in groups of 8) and the
+// shards of a multi-GPU pass were not measured and keep the 256-row form.
+static bool strip_rows128_by_rule(const storm_hip_matrix_s* m, uint32_t shard_count) {
+    return shard_count == 1 && m->n_rows >= 2048 && m->n_words >= 1024;
+}
+static bool strip_rows128(const storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint32_t shard_count) {
+    if (ctx->k2_strip_rows == 64 || ctx->k2_strip_operands == 6 || (m->n_rows + kStripRowsATile - 1) / kStripRowsATile * kStripRowsATile > m->n_rows_pad) return false;
+    return ctx->k2_strip_rows == 128 || strip_rows128_by_rule(m, shard_count);
 }
 
 // The default pass: strips on bit operands over the matrix itself (no shadow, nothing to expand).
@@ -2644,9 +2708,12 @@ static int launch_pairw_bits(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, 
 #endif
     ctx->n_items = 0;  // the strip items carry the diagonal tiles themselves
     ctx->items_key = std::monostate{};
+    if (operands == 5 && strip_rows128(ctx, m, shard_count))
+        return launch_pairw_bits_ranges(ctx, reinterpret_cast<const uint8_t*>(m->d), pitch, ranges, strip_rows_kslices(m->n_words),
+                                        shard_rank, shard_count, d_total, false, kStripRowsATile, true);
     if (operands == 5 || operands == 6)
         return launch_pairw_bits_ranges(ctx, reinterpret_cast<const uint8_t*>(m->d), pitch, ranges, n_kslices * 2u,
-                                        shard_rank, shard_count, d_total, false, operands == 6 ? 512u : (uint32_t)kStripATile);
+                                        shard_rank, shard_count, d_total, false, operands == 6 ? 512u : (uint32_t)kStripATile, false);
     if (int rc = ensure_strip_items(ctx, ranges, n_kslices, shard_rank, shard_count, (uint32_t)kStripATile))
         return rc;
 #ifndef STORM_HIP_PROBES
@@ -2724,6 +2791,7 @@ static int pairw_bits_upload_queue(storm_hip_ctx_t* ctx, storm_hip_matrix_s* m, 
     ctx->pass_report[0] |= STORM_HIP_RAN_BIT_STRIPS;
     ctx->pass_report[1] += ranges_word_pairs({{0, m->n_rows}}, (uint64_t)n_kslices2 * 4u, 1);
     ctx->k2_operands_used = 5;
+    ctx->k2_strip_rows_used = 64;
     uint64_t n_total = 0;
     for (uint64_t p = 0; p < n_panels; ++p) {
         const uint64_t t0 = first_tile[p], t1 = first_tile[p + 1];

@@ -1339,7 +1339,7 @@ extern "C" int storm_hip_strip_plan3(uint64_t n_rows, uint32_t n_words, uint32_t
                                      int tail_slices, int lpt_rounds, uint32_t n_cus, uint32_t* out,
                                      uint64_t capacity_items, uint64_t* n_items, int* run_chosen) {
     using namespace storm;
-    if (!n_items || shard_count == 0 || shard_rank >= shard_count || n_words == 0 || (form != 0 && form != 1) ||
+    if (!n_items || shard_count == 0 || shard_rank >= shard_count || n_words == 0 || form < 0 || form > 2 ||
         max_run < 0 || max_run > 4096 || tail_run < 1 || tail_run > 4096 || tail_slices < 0 || tail_slices > 255 ||
         lpt_rounds < 0 || lpt_rounds > 63 || n_cus == 0) {
         set_error("strip_plan: bad arguments");
@@ -1347,8 +1347,9 @@ extern "C" int storm_hip_strip_plan3(uint64_t n_rows, uint32_t n_words, uint32_t
     }
     try {
         // slices that hold data: form 0 (FP4 shadow, launch_pairw_mfma_ranges): 256 consecutive bits each;
-        // form 1 (K2b, launch_pairw_bits_ranges): slice ks = class pair ks & 1 of the 512-bit chunk ks / 2
-        const uint32_t n_kslices = form == 0 ? (n_words + 3u) / 4u : 2u * ((n_words + 7u) / 8u);
+        // form 1 (K2b, launch_pairw_bits_ranges): slice ks = class pair ks & 1 of the 512-bit chunk ks / 2;
+        // form 2 (K2b with 128 A rows per wave, strip16_rows_kernel): 128 consecutive bits each, A tiles of 512 rows
+        const uint32_t n_kslices = form == 0 ? (n_words + 3u) / 4u : form == 1 ? 2u * ((n_words + 7u) / 8u) : strip_rows_kslices(n_words);
         std::vector<RowRange> ranges;
         if (n_rows > 1) ranges.push_back({0, n_rows});
         std::vector<StripItem> items;
@@ -1360,10 +1361,10 @@ extern "C" int storm_hip_strip_plan3(uint64_t n_rows, uint32_t n_words, uint32_t
         o.lpt_rounds = lpt_rounds;
         o.shard_pairs = pair_space != 0;
         o.n_cus = (int)n_cus;
-        o.xcd_group = form == 0 ? 1 : 2;
+        o.xcd_group = form == 0 ? 1 : form == 1 ? 2 : (int)kStripRowsXcdGroup;
         // exactly what ensure_strip_items launches for these options (one function plans both)
-        plan_strips(strip_request(o, ranges, n_kslices, shard_rank, shard_count, (uint32_t)kStripATile), ranges, items, qb, qc,
-                    run_chosen);
+        plan_strips(strip_request(o, ranges, n_kslices, shard_rank, shard_count, form == 2 ? kStripRowsATile : (uint32_t)kStripATile),
+                    ranges, items, qb, qc, run_chosen);
         *n_items = items.size();
         if (out)
             for (uint64_t i = 0; i < std::min<uint64_t>(capacity_items, items.size()); ++i) {

@@ -46,6 +46,11 @@ constexpr int kStripRowBytes = 128;                      // 256 bits of k as nib
 constexpr int kStripBRows = 64;                          // B rows per stage
 constexpr int kStripWaves = 4;                           // waves per workgroup = A tile / 64 rows
 constexpr int kStripATile = 64 * kStripWaves;            // A rows per workgroup (256; 8 waves / 512 rows measured slower)
+// the third strip form (strip16_rows_kernel: 128 A rows per wave): A tiles of 512 rows, k-slices of 16 bytes = 2 words of every
+// row; the 8 slices of a 128-byte line stay on one XCD
+constexpr uint32_t kStripRowsATile = 512;
+constexpr uint32_t kStripRowsXcdGroup = 8;
+inline uint32_t strip_rows_kslices(uint32_t n_words) { return (n_words + 1u) / 2u; }
 
 struct StripItem {
     uint32_t a_row0;  // first row of the A tile (kStripATile rows, multiple of 64)

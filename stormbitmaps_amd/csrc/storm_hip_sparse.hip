@@ -1610,6 +1610,7 @@ int storm_hip_pairw_sparse_begin(storm_hip_ctx_t* ctx, const storm_hip_sparse_t*
             ctx->last_info[0] = 0;
             ctx->last_info[3] = s->n_probe_cols_launch;
             ctx->k2_operands_used = 5;
+            ctx->k2_strip_rows_used = 64;
             return STORM_HIP_OK;
         }
     }

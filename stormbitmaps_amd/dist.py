@@ -57,7 +57,9 @@ def strip_plan(n_rows: int, n_words: int, rank: int, world: int, form: int = 1, 
                return_run: bool = False):
     """The work items rank `rank` of `world` multiplies, as an [n, 5] uint32 array of {a_row0, diag, j0, j1, ks}
     (see storm_hip_strip_plan3 in include/storm_hip.h). form 1 = the default path (K2b: slice ks = class pair
-    ks & 1 of the 512-bit chunk ks / 2), form 0 = the FP4-shadow strips (slice ks = 256 consecutive bits);
+    ks & 1 of the 512-bit chunk ks / 2), form 0 = the FP4-shadow strips (slice ks = 256 consecutive bits),
+    form 2 = K2b with 128 A rows per wave (option k2_strip_rows = 128: slice ks = 128 consecutive bits, A tiles of
+    512 rows = 8 own blocks where forms 0 and 1 have 256 = 4);
     pair_space 1 = every slice cut along the pair space (option k2_shard_pairs). The keyword options are the
     context options of the same names (defaults = a fresh context on a 256-CU device): the list returned is the
     list such a context launches — one function derives the shaping for both. max_run 0 = automatic, the same
@@ -83,10 +85,12 @@ def strip_plan(n_rows: int, n_words: int, rank: int, world: int, form: int = 1, 
 def slice_columns(mat, ks: int, form: int = 1):
     """The bits of k-slice `ks` of a bit matrix [rows, words] as a matrix of the same row count (what an item of
     strip_plan(form) multiplies): form 0 = words [4 ks, 4 ks + 4); form 1 = the words [8 c, 8 c + 8) of chunk
-    c = ks // 2 masked to the class pair ks & 1 (bits b with (b % 4) // 2 == ks & 1)."""
+    c = ks // 2 masked to the class pair ks & 1 (bits b with (b % 4) // 2 == ks & 1); form 2 = words [2 ks, 2 ks + 2)."""
     import numpy as np
     if form == 0:
         return np.ascontiguousarray(mat[:, 4 * ks:4 * ks + 4])
+    if form == 2:
+        return np.ascontiguousarray(mat[:, 2 * ks:2 * ks + 2])
     c = ks // 2
     mask = np.uint64(0xCCCCCCCCCCCCCCCC if ks & 1 else 0x3333333333333333)
     return np.ascontiguousarray(mat[:, 8 * c:8 * c + 8] & mask)

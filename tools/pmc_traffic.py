@@ -5,7 +5,9 @@ profiles/pmc_hbm_bytes_per_launch.json (read by bench.py for roofline.traffic).
 FETCH_SIZE / WRITE_SIZE are in KiB (MI355X_MICROARCH.md, HBM section). On gfx950 FETCH_SIZE
 reports half of the bytes of a 16 B/lane stream; every load of these kernels is one, so fetch is
 doubled. The correction is checked on expand_fp4_kernel, which reads the bit matrix exactly once
-and writes the 4x larger FP4 shadow exactly once."""
+and writes the 4x larger FP4 shadow exactly once. strip16_rows_kernel's stream is 4 B/lane: for it the
+factor is inferred, not calibrated — its raw figure lies below the size of the matrix, which a launch must read
+at least once (LAB_NOTES.md has the numbers)."""
 import collections
 import csv
 import json
@@ -41,7 +43,10 @@ def main():
     doc["_about"] = ("HBM-side bytes per launch from rocprofv3 PMC (FETCH_SIZE, WRITE_SIZE; separate "
                      "passes; tools/profile_default.sh + tools/pmc_traffic.py), headline shape. FETCH_SIZE "
                      "is KiB and on gfx950 reports half of a 16 B/lane stream: doubled here, checked on "
-                     "expand_fp4_kernel (reads the bit matrix once, writes the 4x FP4 shadow once).")
+                     "expand_fp4_kernel (reads the bit matrix once, writes the 4x FP4 shadow once). For "
+                     "strip16_rows_kernel, whose stream is 4 B/lane, the same factor is INFERRED, not calibrated: "
+                     "its raw figure is below the size of the matrix, which every launch must read at least once "
+                     "(LAB_NOTES.md).")
     entry = {"source_hash": kernel_source_hash(),  # bench.py ignores traffic measured on other sources
              "dominant_kernel": dominant,
              "hbm_bytes_per_launch": sum(kernels[dominant].values()),

@@ -50,6 +50,7 @@ def main():
                 "k2_ring_sync": int(rng.choice([0, 0, 1])),
                 "k2_matrix_parts": int(rng.choice([0, 0, 1])),
                 "k2_strip_operands": int(rng.choice([0, 0, 5, 4, 1 if probes else 2, 2, 6, 6])),
+                "k2_strip_rows": int(rng.choice([0, 0, 64, 128, 128])),
                 "k2_matrix_pad": int(rng.choice([2, 2, 1, 0, 3])),
                 "k2_fold_inline": int(rng.choice([-1, -1, 0, 1])),
                 "k2_stream_groups_per_cu": int(rng.choice([0, 0, 1, 2, 3, 7])),
@@ -200,7 +201,7 @@ def main():
                 s.free()
         finally:
             for k, v in {"variant": -1, "k2_max_run": 0, "k2_tail_slices": 3, "k2_tail_run": 32,
-                         "k2_persistent": 0, "k2_pitch_pad": -1, "k2_matrix_pad": -1, "k2_shape": 16, "k2_tile_shape": 0, "k2_part_slots": 0, "k2_part_min_chunks": 8, "k2_part_narrow": 1, "k2_wave_below": 400, "probe_bundle": -1, "k2_ring_sync": 0, "k2_matrix_parts": 0, "k2_fold_inline": -1, "k2_strip_operands": 0,
+                         "k2_persistent": 0, "k2_pitch_pad": -1, "k2_matrix_pad": -1, "k2_shape": 16, "k2_tile_shape": 0, "k2_part_slots": 0, "k2_part_min_chunks": 8, "k2_part_narrow": 1, "k2_wave_below": 400, "probe_bundle": -1, "k2_ring_sync": 0, "k2_matrix_parts": 0, "k2_fold_inline": -1, "k2_strip_operands": 0, "k2_strip_rows": 0,
                          "k2_stream_groups_per_cu": 0, "k2_stream_min_piece": 6, "k2_stream_min_run": 2,
                          "k2_stream_w3_1": 120, "k2_stream_w3_2": 60, "k2_shadow_budget_mb": 98304, "sparse_probe": -1}.items():
                 ctx.set_option(k, v)
