@@ -383,8 +383,7 @@ int STORM_square_topk_device(STORM_t* a, STORM_t* b, int score, uint64_t n_bits,
  * the LD asked of them: PLINK's --r / --r2, the (squared) Pearson correlation of two dosage vectors. A row is n_samples
  * values in 0 .. 3, packed 2 bits each: sample s in bits 2 (s % 32) and 2 (s % 32) + 1 of 64-bit word s / 32, as an
  * unsigned integer; ceil(n_samples / 32) words per row, tail bits zero. 3 is an ordinary value (the arithmetic is linear
- * up to 3). MISSING GENOTYPES ARE OUT OF SCOPE: there is no missing code and no pairwise-complete statistic; impute or
- * drop such samples first. On the device one FP4 multiply does the work (the E2M1 codes 0 .. 3 are 0, 0.5, 1, 1.5: linear
+ * up to 3) in every call but the three "missing genotypes" calls below, which read it as STORM_DOSAGE_MISSING. On the device one FP4 multiply does the work (the E2M1 codes 0 .. 3 are 0, 0.5, 1, 1.5: linear
  * in the value), so a sample pair costs what a bit pair costs the other containers; every result is exact.
  *   STORM_dosage_new(n_samples)        1 <= n_samples <= 2^24, else NULL
  *   STORM_dosage_add(h, values, n)     one row, one byte per sample; n must be n_samples and every value <= 3
@@ -417,6 +416,33 @@ int STORM_dosage_pairw_dot(STORM_dosage_t* h, uint32_t* out, uint64_t out_rows, 
 int STORM_dosage_pairw_dot_device(STORM_dosage_t* h, uint32_t* d_out, uint64_t out_rows, uint64_t out_ld);
 int STORM_dosage_pairw_corr(STORM_dosage_t* h, int measure, float* out, uint64_t out_rows, uint64_t out_ld);
 int STORM_dosage_pairw_corr_device(STORM_dosage_t* h, int measure, float* d_out, uint64_t out_rows, uint64_t out_ld);
+
+/* The rectangle of two dosage containers, and rows with MISSING genotypes (PLINK's .bed spends one of its four codes on
+ * them): pairwise-complete statistics, over the samples that BOTH rows of a pair have.
+ *   STORM_dosage_square_dot            out[i * out_ld + j] = sum_s a_i[s] b_j[s] for EVERY row i of a and j of b (uint32,
+ *                                      exact; 3 is an ordinary value); out_rows >= a's rows, out_ld >= b's rows; both
+ *                                      containers must hold the same number of samples (-3 otherwise); an empty one: 0,
+ *                                      nothing written
+ * In the calls below, and only there, the value 3 (STORM_DOSAGE_MISSING) means "no call for this sample":
+ *   STORM_dosage_row_missing           missing[i] = the samples of row i that are missing
+ *   STORM_dosage_pairw_nobs            out[i * out_ld + j] = N(i, j), the samples both rows have, for i < j < n (uint32)
+ *   STORM_dosage_pairw_corr_complete   with g = the value (0 where missing) and m = 1 where present: P = sum g_i g_j,
+ *                                      Sx = sum g_i m_j, Sy = sum m_i g_j, Qx = sum g_i^2 m_j, Qy = sum m_i g_j^2;
+ *                                      num = N P - Sx Sy, dx = N Qx - Sx^2, dy = N Qy - Sy^2 exactly in 64-bit integers;
+ *                                      STORM_DOSAGE_R2: num^2 / (dx dy), STORM_DOSAGE_R: num / sqrt(dx dy), in double, rounded
+ *                                      once to float; NaN (0x7FC00000) exactly when dx or dy is 0: no or one shared sample,
+ *                                      or a row constant on the shared samples. On rows without a 3: the same bits as
+ *                                      STORM_dosage_pairw_corr. Device scratch: about 3 n^2 uint32 and three copies of the
+ *                                      rows, kept by the device context
+ * Output conventions, argument checks and return codes as STORM_dosage_pairw_dot / STORM_dosage_pairw_corr above. */
+#define STORM_DOSAGE_MISSING 3
+int STORM_dosage_square_dot(STORM_dosage_t* a, STORM_dosage_t* b, uint32_t* out, uint64_t out_rows, uint64_t out_ld);
+int STORM_dosage_square_dot_device(STORM_dosage_t* a, STORM_dosage_t* b, uint32_t* d_out, uint64_t out_rows, uint64_t out_ld);
+int STORM_dosage_row_missing(STORM_dosage_t* h, uint32_t* missing);
+int STORM_dosage_pairw_nobs(STORM_dosage_t* h, uint32_t* out, uint64_t out_rows, uint64_t out_ld);
+int STORM_dosage_pairw_nobs_device(STORM_dosage_t* h, uint32_t* d_out, uint64_t out_rows, uint64_t out_ld);
+int STORM_dosage_pairw_corr_complete(STORM_dosage_t* h, int measure, float* out, uint64_t out_rows, uint64_t out_ld);
+int STORM_dosage_pairw_corr_complete_device(STORM_dosage_t* h, int measure, float* d_out, uint64_t out_rows, uint64_t out_ld);
 
 /* ------------------------------------------------------------- extensions (not in ref) ---
  * Device selection for the entry points above. By default device 0 computes everything.

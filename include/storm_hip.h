@@ -300,7 +300,8 @@ int storm_hip_cross_dense_topk(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a
  * Unphased genotype data holds a dosage of 0, 1 or 2 per sample, and the LD asked of it is the (squared) Pearson
  * correlation of two dosage vectors. Here a "dosage matrix" is an ordinary storm_hip_matrix_t whose rows hold VALUES
  * 0 .. 3 in 2 bits each: value s of a row in bits 2 (s % 32) and 2 (s % 32) + 1 of word s / 32 (ceil(n_samples / 32)
- * words per row, tail bits zero, at most 2^24 samples). 3 is an ordinary value; missing genotypes are out of scope.
+ * words per row, tail bits zero, at most 2^24 samples). 3 is an ordinary value in the calls of this block; the block below
+ * reads it as "missing".
  * With P = sum v_i v_j, s = sum v, q = sum v^2 and S = n_samples:
  *   num = S P - s_i s_j and d = S q - s^2 exactly in 64-bit integers, then in double, rounded once to float,
  *   STORM_HIP_DOSAGE_R2   num^2 / (d_i d_j)          STORM_HIP_DOSAGE_R   num / sqrt(d_i d_j)
@@ -324,6 +325,41 @@ int storm_hip_pairw_dosage_corr_device(storm_hip_ctx_t* ctx, const storm_hip_mat
                                        float* d_out, uint64_t ld);
 int storm_hip_pairw_dosage_corr(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_samples,
                                 float* h_out, uint64_t ld);
+
+/* ---- the rectangle of two dosage matrices; rows with missing genotypes: pairwise-complete r / r^2 ----------------
+ * _square_dosage_matrix[_device]: out[i * ld + j] = sum_s a_i[s] b_j[s] for EVERY row i of A and j of B (uint32, exact;
+ *   3 is an ordinary value), ld >= b's rows. K2h in its dosage form over the rectangle's 128 x 128 tiles. Both matrices
+ *   must have the same words per row (a mismatch: STORM_HIP_EINVAL). An empty matrix: STORM_HIP_OK, nothing written.
+ *   _device: complete on return, nothing outside the n_a x n_b window is written.
+ * In the three calls below — and only there — code 3 of a value means MISSING. With g = the value (0 where missing) and
+ * m = 1 where a sample s < n_samples is present, per pair (i, j):
+ *   N = sum m_i m_j, P = sum g_i g_j, Sx = sum g_i m_j, Sy = sum m_i g_j, Qx = sum g_i^2 m_j, Qy = sum m_i g_j^2,
+ *   num = N P - Sx Sy, dx = N Qx - Sx^2, dy = N Qy - Sy^2 exactly in 64-bit integers, then in double, rounded once to float:
+ *   STORM_HIP_DOSAGE_R2 num^2 / (dx dy), STORM_HIP_DOSAGE_R num / sqrt(dx dy): PLINK's r over the samples BOTH rows have.
+ *   NaN (0x7FC00000) exactly when dx or dy is 0: N = 0, N = 1, or a row constant on the shared samples. On rows without a 3
+ *   the floats are bit-identical to _pairw_dosage_corr's.
+ * _dosage_row_missing: h_missing[i] = the samples of row i that are missing (host pointer, n_rows entries).
+ * _pairw_dosage_nobs[_device]: out[i * ld + j] = N(i, j) for i < j (uint32).
+ * _pairw_dosage_corr_complete[_device]: the rows are split on the device into three matrices of 2-bit rows (G: 3 -> 0;
+ *   H: 1 where the value is 2, so that g^2 = g + 2 h; M: 1 where present), K2h multiplies the triangles of G and of M and
+ *   the rectangle [G ; H] x M (3 n^2 row-pair products), and dosage_complete_finish_kernel finishes in place. Device
+ *   scratch held by the context: about 3 n^2 uint32 of sums and three copies of the rows; an allocation that fails returns
+ *   STORM_HIP_ENOMEM with the reason.
+ * Output conventions, n_samples and refusals as _pairw_dosage_corr[_device]: entries i >= j stay as they were (_device) or
+ * are 0 / +0.0f (host forms); fewer than two rows: STORM_HIP_OK, nothing written (host forms of one row: its single 0). */
+int storm_hip_square_dosage_matrix_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b,
+                                          uint32_t* d_out, uint64_t ld);
+int storm_hip_square_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b,
+                                   uint32_t* h_out, uint64_t ld);
+int storm_hip_dosage_row_missing(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint32_t* h_missing);
+int storm_hip_pairw_dosage_nobs_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint32_t* d_out,
+                                       uint64_t ld);
+int storm_hip_pairw_dosage_nobs(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint32_t* h_out,
+                                uint64_t ld);
+int storm_hip_pairw_dosage_corr_complete_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure,
+                                                uint64_t n_samples, float* d_out, uint64_t ld);
+int storm_hip_pairw_dosage_corr_complete(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_samples,
+                                         float* h_out, uint64_t ld);
 
 /* sum_c C(n_c,2) on the device — verification identity only, never the product
  * path: used by tests at sizes where a CPU pairwise oracle is infeasible */
@@ -467,6 +503,12 @@ int storm_hip_matrix_plan(uint64_t n_rows_a, uint64_t n_rows_b, uint32_t n_words
 int storm_hip_dosage_plan(uint64_t n_rows_a, uint64_t n_rows_b, uint32_t n_words, uint64_t band_row0, uint64_t band_rows,
                           uint32_t n_cus, int slots_per_cu, int min_chunks, int diag_cost_pct, uint32_t* out,
                           uint64_t capacity_items, uint64_t* n_items);
+
+/* The same for the dosage form's rectangle (storm_hip_square_dosage_matrix_device): every 128 x 128 tile of
+ * n_rows_a x n_rows_b, I over A's tiles and J counting on behind A's rows padded to 256 (storm_hip_matrix_plan's
+ * rectangle), under the same two limits. Host only; `out` may be NULL to query the count. */
+int storm_hip_dosage_square_plan(uint64_t n_rows_a, uint64_t n_rows_b, uint32_t n_words, uint32_t n_cus, int slots_per_cu,
+                                 int min_chunks, int diag_cost_pct, uint32_t* out, uint64_t capacity_items, uint64_t* n_items);
 
 /* The K2h list of the lag layout (storm_hip_pairw_lag_matrix_device): the same records for the triangle's tiles (I, J) that
  * hold a pair with j - i <= L = min(max_lag, n_rows - 1), I <= J <= (128 I + 127 + L) / 128; band_rows == 0: all rows.

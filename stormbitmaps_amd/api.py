@@ -235,8 +235,8 @@ def _device_window(device, n: int):
 
 class StormDosage:
     """STORM_dosage_t (storm.h, extension): rows of n_samples 2-bit dosages (0 / 1 / 2 copies of an allele per sample; 3 is an
-    ordinary value), their per-pair dot products and genotype correlations (PLINK --r / --r2) on the device. Missing
-    genotypes are out of scope."""
+    ordinary value), their per-pair dot products and genotype correlations (PLINK --r / --r2) on the device. In
+    row_missing, pairw_nobs and pairw_corr_complete — and only there — the value 3 means "missing"."""
 
     def __init__(self, n_samples: int):
         self._lib = _lib.load()
@@ -307,6 +307,64 @@ class StormDosage:
         self._check("STORM_dosage_pairw_corr",
                     int(self._lib.STORM_dosage_pairw_corr(self._h, DOSAGE_MEASURES[measure],
                                                           _ptr(out) if out.size else _ptr(np.zeros(1, np.float32)), n, n)))
+        return out
+
+    def square_dot(self, other: "StormDosage", device=None):
+        """STORM_dosage_square_dot: [n_rows, other.n_rows] uint32, entry (i, j) = sum_s v_i[s] w_j[s] for every row of this
+        container against every row of `other` (the same number of samples; 3 is an ordinary value).
+        device=: a 2-D torch tensor of 32-bit entries in device memory that receives the rectangle instead
+        (STORM_dosage_square_dot_device); returns None then."""
+        na, nb = self.n_rows, other.n_rows
+        if device is not None:
+            if device.dim() != 2 or device.element_size() != 4 or device.stride(1) != 1 or not device.is_cuda:
+                raise ValueError("device=: a 2-D tensor of 32-bit entries in device memory with contiguous rows")
+            if device.shape[0] < na or device.shape[1] < nb:
+                raise ValueError(f"device=: a tensor of {tuple(device.shape)} cannot hold {na} x {nb} entries")
+            self._check("STORM_dosage_square_dot_device",
+                        int(self._lib.STORM_dosage_square_dot_device(self._h, other._h, C.c_void_p(device.data_ptr()),
+                                                                     int(device.shape[0]), int(device.stride(0)))))
+            return None
+        out = np.zeros((na, nb), dtype=np.uint32)
+        self._check("STORM_dosage_square_dot",
+                    int(self._lib.STORM_dosage_square_dot(self._h, other._h, _ptr(out) if out.size else _ptr(np.zeros(1, np.uint32)),
+                                                          na, nb)))
+        return out
+
+    def row_missing(self):
+        """STORM_dosage_row_missing: the samples of every row that are missing (value 3), [n_rows] uint32, counted on the
+        device."""
+        n = self.n_rows
+        miss = np.zeros(max(n, 1), dtype=np.uint32)
+        self._check("STORM_dosage_row_missing", int(self._lib.STORM_dosage_row_missing(self._h, _ptr(miss))))
+        return miss[:n]
+
+    def pairw_nobs(self, device=None):
+        """STORM_dosage_pairw_nobs: [n_rows, n_rows] uint32, entry (i, j), i < j = the samples neither row is missing
+        (value 3) at; 0 for i >= j. device=: as pairw_dot (STORM_dosage_pairw_nobs_device)."""
+        n = self.n_rows
+        if device is not None:
+            ptr, rows, ld = _device_window(device, n)
+            self._check("STORM_dosage_pairw_nobs_device", int(self._lib.STORM_dosage_pairw_nobs_device(self._h, ptr, rows, ld)))
+            return None
+        out = np.zeros((n, n), dtype=np.uint32)
+        self._check("STORM_dosage_pairw_nobs",
+                    int(self._lib.STORM_dosage_pairw_nobs(self._h, _ptr(out) if out.size else _ptr(np.zeros(1, np.uint32)), n, n)))
+        return out
+
+    def pairw_corr_complete(self, measure: str = "r2", device=None):
+        """STORM_dosage_pairw_corr_complete: pairw_corr over the samples BOTH rows of a pair have (value 3 = missing): [n_rows,
+        n_rows] float32; NaN where the pair shares fewer than two samples or a row is constant on the shared ones; 0 for
+        i >= j. Rows without a 3 give pairw_corr's bits. device=: as pairw_dot (STORM_dosage_pairw_corr_complete_device)."""
+        n = self.n_rows
+        if device is not None:
+            ptr, rows, ld = _device_window(device, n)
+            self._check("STORM_dosage_pairw_corr_complete_device",
+                        int(self._lib.STORM_dosage_pairw_corr_complete_device(self._h, DOSAGE_MEASURES[measure], ptr, rows, ld)))
+            return None
+        out = np.zeros((n, n), dtype=np.float32)
+        self._check("STORM_dosage_pairw_corr_complete",
+                    int(self._lib.STORM_dosage_pairw_corr_complete(self._h, DOSAGE_MEASURES[measure],
+                                                                   _ptr(out) if out.size else _ptr(np.zeros(1, np.float32)), n, n)))
         return out
 
     def free(self) -> None:

@@ -3,7 +3,8 @@
  *
  * The host keeps the packed rows; they go up into an ordinary storm_hip_matrix_t on the first compute call after a change
  * (whole, from the row the device copy ends at: rows never change once added). On storm_host.c's locked paths without
- * adding to them, like storm_lag.c and storm_topk.c: one device slot and one process. No CPU fallback. */
+ * adding to them, like storm_lag.c and storm_topk.c: one device slot and one process. No CPU fallback. The rectangle of
+ * two containers and the calls that read 3 as "missing" are storm_dosage_complete.c's. */
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -12,20 +13,9 @@
 #include "storm.h"
 #include "storm_hip.h"
 #include "storm_host_internal.h"
+#include "storm_dosage_internal.h"
 
 #define DOSAGE_MAX_SAMPLES (1ull << 24)
-
-struct STORM_dosage_s {
-    uint64_t n_samples;
-    uint32_t n_words;    /* ceil(n_samples / 32) */
-    uint64_t n_rows, m_rows;
-    uint64_t* rows;      /* n_rows x n_words, packed */
-    /* the device copy: rows [0, synced) of `m` on device slot `slot`, made under view generation `generation` */
-    storm_hip_matrix_t* m;
-    int slot;
-    uint32_t generation;
-    uint64_t synced;
-};
 
 STORM_dosage_t* STORM_dosage_new(uint64_t n_samples) {
     if (n_samples == 0 || n_samples > DOSAGE_MAX_SAMPLES) return NULL;
@@ -137,7 +127,7 @@ int STORM_dosage_add_packed(STORM_dosage_t* h, const uint64_t* words, uint64_t n
 }
 
 /* the device copy brought up to date on the calling thread's slot (the caller holds the lock): NULL with the reason reported */
-static storm_hip_matrix_t* dosage_mirror(STORM_dosage_t* h, storm_hip_ctx_t** ctx_out) {
+storm_hip_matrix_t* storm_dosage_mirror(STORM_dosage_t* h, storm_hip_ctx_t** ctx_out) {
     const uint32_t generation = storm_host_view_generation();
     if (h->m && (h->generation != generation || h->slot != storm_host_slot() || h->synced > h->n_rows)) dosage_drop_device(h);
     storm_hip_ctx_t* ctx = storm_host_ctx();
@@ -173,7 +163,7 @@ int STORM_dosage_row_sums(STORM_dosage_t* h, uint32_t* sum, uint32_t* sum_sq) {
     int rc = storm_host_one_slot_or_refuse("STORM_dosage_row_sums");
     if (!rc && h->n_rows != 0) {
         storm_hip_ctx_t* ctx = NULL;
-        const storm_hip_matrix_t* m = dosage_mirror(h, &ctx);
+        const storm_hip_matrix_t* m = storm_dosage_mirror(h, &ctx);
         if (!m) rc = -3;
         else if (storm_hip_dosage_row_sums(ctx, m, sum, sum_sq) != STORM_HIP_OK) {
             storm_host_device_error("storm_hip_dosage_row_sums");
@@ -200,7 +190,7 @@ static int dosage_pairw(STORM_dosage_t* h, int measure, void* out, uint64_t out_
     }
     if (!rc && n >= 2) {
         storm_hip_ctx_t* ctx = NULL;
-        const storm_hip_matrix_t* m = dosage_mirror(h, &ctx);
+        const storm_hip_matrix_t* m = storm_dosage_mirror(h, &ctx);
         if (!m) rc = -3;
         else {
             int hrc;

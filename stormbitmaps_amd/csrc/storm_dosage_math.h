@@ -1,6 +1,8 @@
-// storm_dosage_math.h — the arithmetic of one entry of dosage_finish_kernel (storm_hip_dosage.hip): the Pearson
-// correlation of two rows of 2-bit values (genotype dosages), in a header of its own so that a host compiler can build
-// the very same lines: tests/test_dosage_math.py checks them against exactly rounded rationals without a device.
+// storm_dosage_math.h — the arithmetic of one entry of dosage_finish_kernel and dosage_complete_finish_kernel
+// (storm_hip_dosage.hip): the Pearson correlation of two rows of 2-bit values (genotype dosages), over all samples or
+// over the samples both rows have, and the word logic of dosage_split_missing_kernel — in a header of its own so that a
+// host compiler can build the very same lines: tests/test_dosage_math.py and tests/test_dosage_complete_math.py check
+// them against exactly rounded rationals and a per-sample loop without a device.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -28,6 +30,56 @@ STORM_DOSAGE_FN uint32_t dosage_corr_bits(uint32_t P, uint32_t s_i, uint32_t q_i
     const uint64_t d_i = S * q_i - (uint64_t)s_i * s_i, d_j = S * q_j - (uint64_t)s_j * s_j;
     if (d_i == 0 || d_j == 0) return kDosageNaN;
     const uint64_t x = S * P, y = (uint64_t)s_i * s_j;
+    const bool negative = x < y;
+    const double num = (double)(negative ? y - x : x - y);
+    const double den = (double)d_i * (double)d_j;
+    double v;
+    if (measure == 0 /* STORM_HIP_DOSAGE_R2 */) {
+        v = (num * num) / den;
+    } else {
+        v = num / sqrt(den);
+        if (negative) v = -v;
+    }
+    const float f = (float)v;
+    uint32_t bits;
+    memcpy(&bits, &f, sizeof(bits));
+    return bits;
+}
+
+// ---- rows with missing genotypes (code 3 = missing): pairwise-complete statistics ----
+constexpr uint64_t kDosageLowBits = 0x5555555555555555ull;   // the low bit of each of a word's 32 values
+
+// The low bits of the values of word `word` of a row that are samples: all 32 below the last word, the first
+// n_samples % 32 (0: all) in the last one, none in the pad words behind it.
+STORM_DOSAGE_FN uint64_t dosage_valid_mask(uint64_t word, uint32_t n_words, uint64_t n_samples) {
+    if (word + 1u < n_words) return kDosageLowBits;
+    if (word >= n_words) return 0ull;
+    const uint32_t tail = (uint32_t)(n_samples % 32u);
+    return tail ? kDosageLowBits & ((1ull << (2u * tail)) - 1ull) : kDosageLowBits;
+}
+
+// One word of a row split into three words of 2-bit values: g = the value with 3 -> 0, h = 1 where the value is 2
+// (so that g^2 = g + 2 h), m = 1 where a sample is present (`valid`: dosage_valid_mask of the word).
+STORM_DOSAGE_FN void dosage_split_word(uint64_t w, uint64_t valid, uint64_t* g, uint64_t* h, uint64_t* m) {
+    const uint64_t lo = w & kDosageLowBits, hi = (w >> 1) & kDosageLowBits;
+    const uint64_t both = lo & hi;
+    *g = w & ~(3ull * both);
+    *h = hi & ~lo;
+    *m = ~both & kDosageLowBits & valid;
+}
+
+// One entry over the samples BOTH rows have: N = their number, P = sum g_i g_j, sx = sum g_i m_j, sy = sum m_i g_j,
+// qx = sum g_i^2 m_j, qy = sum m_i g_j^2 (g: the value, 0 where missing; m: 1 where present; values 0 .. 2, at most 2^24
+// samples: every term below 2^51).
+//   num = N P - sx sy, dx = N qx - sx^2, dy = N qy - sy^2 exactly in 64-bit integers (dx, dy >= 0 by Cauchy-Schwarz over
+//   the shared samples), then dosage_corr_bits' scheme line for line: on rows without a missing sample (N = S,
+//   sx = s_i, ...) the result is the same bits. NaN when dx or dy is 0: no or one shared sample, or a row that is
+//   constant on the shared samples.
+STORM_DOSAGE_FN uint32_t dosage_corr_complete_bits(uint32_t P, uint32_t N, uint32_t sx, uint32_t sy, uint32_t qx, uint32_t qy,
+                                                   int measure) {
+    const uint64_t d_i = (uint64_t)N * qx - (uint64_t)sx * sx, d_j = (uint64_t)N * qy - (uint64_t)sy * sy;
+    if (d_i == 0 || d_j == 0) return kDosageNaN;
+    const uint64_t x = (uint64_t)N * P, y = (uint64_t)sx * sy;
     const bool negative = x < y;
     const double num = (double)(negative ? y - x : x - y);
     const double den = (double)d_i * (double)d_j;

@@ -3,7 +3,12 @@
 // pairs come from K2h in its dosage form (tile128_kernel<false, 2>, storm_hip_mfma.hip: launch_pairw_dosage_matrix); this
 // file holds the two small kernels around it — the rows' sums and sums of squares, and the in-place uint32 -> float pass
 // that turns a dot product into PLINK's --r / --r2, the (squared) Pearson correlation of two dosage vectors — and the
-// C-ABI of the form. Plain vector code; the formula is storm_dosage_math.h. Missing genotypes are out of scope.
+// C-ABI of the form. Plain vector code; the formulas are storm_dosage_math.h.
+// Missing genotypes (the *_complete, *_nobs and *_row_missing calls only: code 3 = missing there, an ordinary value in
+// every other call): dosage_split_missing_kernel splits the rows into three matrices of 2-bit rows — G (3 -> 0), H (1 where
+// the value is 2) and M (1 where present) — K2h multiplies the triangles of G and of M and the rectangle [G ; H] x M, and
+// dosage_complete_finish_kernel turns the five sums of a pair into r / r^2 over the samples both rows have (DESIGN.md §4,
+// "K2h, dosage form with missing genotypes").
 #include "storm_hip_internal.h"
 #include "storm_dosage_math.h"
 
@@ -98,6 +103,80 @@ __global__ __launch_bounds__(256) void dosage_finish_kernel(uint32_t* __restrict
     }
 }
 
+// ---- rows with missing genotypes ----
+// One word per thread: word w of row `row` of X into the same word of G, H and M (rows of `stride_words` words each,
+// rows_pad rows: the rows behind n_rows and the words behind n_words — the pad up to the stride and the 512-bit chunk — come
+// out zero in all three, and so do M's tail samples of the last word).
+__global__ __launch_bounds__(256) void dosage_split_missing_kernel(const uint64_t* __restrict__ X, uint64_t stride_words,
+                                                                   uint64_t n_rows, uint64_t rows_pad, uint32_t n_words,
+                                                                   uint64_t n_samples, uint64_t* __restrict__ G,
+                                                                   uint64_t* __restrict__ H, uint64_t* __restrict__ M) {
+    const uint64_t w = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const uint64_t row = blockIdx.y;
+    if (w >= stride_words || row >= rows_pad) return;
+    const bool data = row < n_rows && w < n_words;
+    const uint64_t x = data ? X[row * stride_words + w] : 0ull;
+    uint64_t g, h, m;
+    dosage_split_word(x, data ? dosage_valid_mask(w, n_words, n_samples) : 0ull, &g, &h, &m);
+    const uint64_t at = row * stride_words + w;
+    G[at] = g;
+    H[at] = h;
+    M[at] = m;
+}
+
+// One wave per row: the samples of a row that are missing (code 3 below n_samples). Four rows per workgroup.
+__global__ __launch_bounds__(kThreads) void dosage_row_missing_kernel(const uint64_t* __restrict__ X, uint64_t stride_words,
+                                                                      uint64_t n_rows, uint32_t n_words, uint64_t n_samples,
+                                                                      uint32_t* __restrict__ missing) {
+    const uint64_t row = (uint64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    if (row >= n_rows) return;
+    const uint64_t* const x = X + row * stride_words;
+    uint32_t present = 0;
+    for (uint32_t w = lane; w < n_words; w += kLanes) {
+        uint64_t g, h, m;
+        dosage_split_word(x[w], dosage_valid_mask(w, n_words, n_samples), &g, &h, &m);
+        present += (uint32_t)__popcll(m);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) present += __shfl_down(present, off, kLanes);
+    if (lane == 0) missing[row] = (uint32_t)n_samples - present;
+}
+
+constexpr int kDosCompleteTile = 64;   // a workgroup finishes 64 x 64 entries: wave w rows w, w + 4, ..., lane = column
+
+// The finishing pass of the pairwise-complete correlation over the upper triangle of an n x n matrix of dot products P, in
+// place (uint32 -> float). Entry (i, j) needs N(i, j) (`nobs`), sx = GM(i, j), qx = sx + 2 HM(i, j) and — from the
+// TRANSPOSED position — sy = GM(j, i), qy = sy + 2 HM(j, i) (`gm`, `hm`: n x n each, pitch lds, like nobs). The block
+// GM / HM [col0 .. + 63][row0 .. + 63] is read by rows (one 256-byte run per wave instruction) into the LDS at a pitch
+// of 65 words and read back down its columns without a bank conflict. Grid (column tiles, row tiles); a tile wholly at or
+// below the diagonal exits at once; entries i >= j, the pitch columns and rows beyond n are neither read nor written.
+__global__ __launch_bounds__(256) void dosage_complete_finish_kernel(uint32_t* __restrict__ io, uint64_t ld, uint64_t n,
+                                                                     const uint32_t* __restrict__ nobs,
+                                                                     const uint32_t* __restrict__ gm,
+                                                                     const uint32_t* __restrict__ hm, uint64_t lds, int measure) {
+    const uint64_t row0 = (uint64_t)blockIdx.y * kDosCompleteTile, col0 = (uint64_t)blockIdx.x * kDosCompleteTile;
+    if (col0 + kDosCompleteTile <= row0 + 1) return;   // the tile's last column is not beyond its first row
+    __shared__ uint32_t t_gm[kDosCompleteTile][kDosCompleteTile + 1], t_hm[kDosCompleteTile][kDosCompleteTile + 1];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    for (uint32_t r = wave; r < kDosCompleteTile; r += 4) {   // row col0 + r of GM / HM, its columns row0 .. row0 + 63
+        const bool in = col0 + r < n && row0 + lane < n;
+        const uint64_t at = (col0 + r) * lds + row0 + lane;
+        t_gm[r][lane] = in ? gm[at] : 0u;
+        t_hm[r][lane] = in ? hm[at] : 0u;
+    }
+    __syncthreads();
+    const uint64_t j = col0 + lane;
+    for (uint32_t a = wave; a < kDosCompleteTile; a += 4) {
+        const uint64_t i = row0 + a;
+        if (i >= n || j >= n || j <= i) continue;
+        const uint64_t at = i * lds + j;
+        const uint32_t sx = gm[at], sy = t_gm[lane][a];
+        const uint32_t qx = sx + 2u * hm[at], qy = sy + 2u * t_hm[lane][a];
+        io[i * ld + j] = dosage_corr_complete_bits(io[i * ld + j], nobs[at], sx, sy, qx, qy, measure);
+    }
+}
+
 // the rows' sums into the context's row-count scratch: sum at [0, n), sum of squares at [n, 2 n); queued
 static int dosage_sums_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m) {
     const uint64_t n = m->n_rows;
@@ -127,6 +206,82 @@ static int dosage_corr_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m,
     return STORM_HIP_OK;
 }
 
+// The split operands of a matrix with missing genotypes, in ctx->d_dosage_rows: G, H and M as matrices of rows128 =
+// n_rows up to the next multiple of 128 rows each (zero rows behind n_rows), G and H adjacent so that [G ; H] is one matrix
+// of rows128 + n_rows rows. Queued.
+struct DosageSplit {
+    storm_hip_matrix_s g, m, gh;   // views into the scratch (never destroyed)
+    uint64_t rows128;
+};
+static int dosage_split_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* x, uint64_t n_samples, DosageSplit* out) {
+    const uint64_t n = x->n_rows, rows128 = (n + kThTile - 1) / kThTile * kThTile, stride = x->stride_words;
+    const uint64_t words = rows128 * stride;
+    if (rows128 > 65535u) {
+        set_error("dosage rows with missing genotypes: %llu rows exceed the split's launch grid", (unsigned long long)n);
+        return STORM_HIP_EINVAL;
+    }
+    if (int rc = ctx->d_dosage_rows.ensure(3 * words * sizeof(uint64_t), "dosage rows with missing genotypes: the split operands G, H, M"))
+        return rc;
+    uint64_t* const G = ctx->d_dosage_rows.d;
+    hipLaunchKernelGGL(dosage_split_missing_kernel, dim3((uint32_t)((stride + 255u) / 256u), (uint32_t)rows128), dim3(256), 0,
+                       ctx->stream, x->d, stride, n, rows128, x->n_words, n_samples, G, G + words, G + 2 * words);
+    STORM_HIP_TRY(hipGetLastError());
+    auto view = [&](uint64_t* d, uint64_t rows, uint64_t rows_pad) {
+        storm_hip_matrix_s v;
+        v.d = d;
+        v.n_rows = rows;
+        v.n_rows_pad = rows_pad;
+        v.n_words = x->n_words;
+        v.stride_words = stride;
+        return v;
+    };
+    out->rows128 = rows128;
+    out->g = view(G, n, rows128);
+    out->gh = view(G, rows128 + n, 2 * rows128);
+    out->m = view(G + 2 * words, n, rows128);
+    return STORM_HIP_OK;
+}
+
+// N(i, j) for i < j at d_out (pitch ld): the split, then the triangle of M. Queued.
+static int dosage_nobs_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint64_t n_samples, uint32_t* d_out, uint64_t ld) {
+    DosageSplit sp;
+    if (int rc = dosage_split_queued(ctx, m, n_samples, &sp)) return rc;
+    return launch_pairw_dosage_matrix(ctx, &sp.m, d_out, ld, false);
+}
+
+// The pairwise-complete correlation at d_io (pitch ld): the split; P = the triangle of G straight into d_io; N = the
+// triangle of M and [G ; H] x M (rows [0, n): G M^T, rows [rows128, rows128 + n): H M^T) into ctx->d_dosage_sums — 3 n^2
+// row-pair products on the matrix cores; then the finish in place. Scratch: about 3 n^2 uint32 of sums (n + rows128 + n rows
+// of n up to the next multiple of 4 columns) and 3 rows128 rows of operands. All queued.
+static int dosage_corr_complete_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int measure, uint64_t n_samples,
+                                       uint32_t* d_io, uint64_t ld) {
+    const uint64_t n = m->n_rows;
+    DosageSplit sp;
+    if (int rc = dosage_split_queued(ctx, m, n_samples, &sp)) return rc;
+    const uint64_t lds = (n + 3u) / 4u * 4u;
+    if (int rc = ctx->d_dosage_sums.ensure((2 * n + sp.rows128) * lds * sizeof(uint32_t),
+                                           "pairw_dosage_corr_complete: the sums N, G M^T and H M^T"))
+        return rc;
+    uint32_t* const d_nobs = ctx->d_dosage_sums.d;
+    uint32_t* const d_gm = d_nobs + n * lds;
+    uint32_t* const d_hm = d_gm + sp.rows128 * lds;
+    // (the two triangles are planned alike: the second one launches from the first one's list)
+    if (int rc = launch_pairw_dosage_matrix(ctx, &sp.g, d_io, ld, false)) return rc;
+    if (int rc = launch_pairw_dosage_matrix(ctx, &sp.m, d_nobs, lds, false)) return rc;
+    if (int rc = launch_square_dosage_matrix(ctx, &sp.gh, &sp.m, d_gm, lds, false)) return rc;
+    const uint64_t tiles = (n + kDosCompleteTile - 1) / kDosCompleteTile;
+    if (tiles > 65535u) {
+        set_error("pairw_dosage_corr_complete: %llu rows exceed the finishing pass's launch grid", (unsigned long long)n);
+        return STORM_HIP_EINVAL;
+    }
+    hipLaunchKernelGGL(dosage_complete_finish_kernel, dim3((uint32_t)tiles, (uint32_t)tiles), dim3(256), 0, ctx->stream, d_io, ld, n,
+                       d_nobs, d_gm, d_hm, lds, measure);
+    STORM_HIP_TRY(hipGetLastError());
+    ctx->pass_report[0] = STORM_HIP_RAN_TILES_OUT | STORM_HIP_RAN_SIMILARITY;
+    ctx->pass_report[1] = 3 * n * n * m->n_words;
+    return STORM_HIP_OK;
+}
+
 // what every dosage call refuses alike
 static int check_dosage(const char* who, const storm_hip_matrix_s* m, const void* out, uint64_t ld) {
     if (!m || !out) {
@@ -143,14 +298,38 @@ static int check_dosage(const char* who, const storm_hip_matrix_s* m, const void
     }
     return STORM_HIP_OK;
 }
+static int check_samples(const char* who, const storm_hip_matrix_s* m, uint64_t n_samples) {
+    if (n_samples == 0 || (n_samples + 31u) / 32u != m->n_words) {
+        set_error("%s: %llu samples do not fill rows of %u words (32 values per word)", who, (unsigned long long)n_samples,
+                  m->n_words);
+        return STORM_HIP_EINVAL;
+    }
+    return STORM_HIP_OK;
+}
 static int check_corr(const char* who, const storm_hip_matrix_s* m, int measure, uint64_t n_samples) {
     if (measure != STORM_HIP_DOSAGE_R2 && measure != STORM_HIP_DOSAGE_R) {
         set_error("%s: unknown measure %d (0 r^2, 1 r)", who, measure);
         return STORM_HIP_EINVAL;
     }
-    if (n_samples == 0 || (n_samples + 31u) / 32u != m->n_words) {
-        set_error("%s: %llu samples do not fill rows of %u words (32 values per word)", who, (unsigned long long)n_samples,
-                  m->n_words);
+    return check_samples(who, m, n_samples);
+}
+// the rectangle of two dosage matrices: rows of the same width
+static int check_square(const char* who, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, const void* out, uint64_t ld) {
+    if (!a || !b || !out) {
+        set_error("%s: NULL argument", who);
+        return STORM_HIP_EINVAL;
+    }
+    if (a->n_words != b->n_words || a->stride_words != b->stride_words) {
+        set_error("%s: rows of %u and of %u words (both matrices must hold the same number of samples)", who, a->n_words,
+                  b->n_words);
+        return STORM_HIP_EINVAL;
+    }
+    if (ld < b->n_rows) {
+        set_error("%s: leading dimension %llu < B's rows %llu", who, (unsigned long long)ld, (unsigned long long)b->n_rows);
+        return STORM_HIP_EINVAL;
+    }
+    if ((uint64_t)a->n_words * 32u > kDosageMaxSamples) {
+        set_error("%s: rows of %u words hold more than 2^24 values", who, a->n_words);
         return STORM_HIP_EINVAL;
     }
     return STORM_HIP_OK;
@@ -240,6 +419,121 @@ int storm_hip_pairw_dosage_corr(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* 
         STORM_HIP_TRY(hipMemsetAsync(ctx->d_band, 0, need, ctx->stream));   // (entries i >= j: +0.0f is the same zero bits)
         if (n >= 2)
             if (int rc = dosage_corr_queued(ctx, m, measure, n_samples, ctx->d_band, n)) return rc;
+        STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(float), ctx->d_band, n * sizeof(uint32_t), n * sizeof(uint32_t), n,
+                                       hipMemcpyDeviceToHost, ctx->stream));
+        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return STORM_HIP_OK;
+    });
+}
+
+int storm_hip_square_dosage_matrix_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b,
+                                          uint32_t* d_out, uint64_t ld) {
+    return guarded("storm_hip_square_dosage_matrix_device", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        if (int rc = check_square("square_dosage_matrix", a, b, d_out, ld)) return rc;
+        if (a->n_rows == 0 || b->n_rows == 0) return STORM_HIP_OK;
+        STORM_HIP_TRY(hipSetDevice(ctx->device));
+        return launch_square_dosage_matrix(ctx, a, b, d_out, ld, true);
+    });
+}
+
+int storm_hip_square_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b, uint32_t* h_out,
+                                   uint64_t ld) {
+    return guarded("storm_hip_square_dosage_matrix", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        if (int rc = check_square("square_dosage_matrix", a, b, h_out, ld)) return rc;
+        const uint64_t na = a->n_rows, nb = b->n_rows;
+        if (na == 0 || nb == 0) return STORM_HIP_OK;
+        STORM_HIP_TRY(hipSetDevice(ctx->device));
+        if (int rc = ctx->d_band.ensure((size_t)na * nb * sizeof(uint32_t), "square_dosage_matrix: the output")) return rc;
+        if (int rc = launch_square_dosage_matrix(ctx, a, b, ctx->d_band, nb, false)) return rc;
+        STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(uint32_t), ctx->d_band, nb * sizeof(uint32_t), nb * sizeof(uint32_t), na,
+                                       hipMemcpyDeviceToHost, ctx->stream));
+        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return STORM_HIP_OK;
+    });
+}
+
+int storm_hip_dosage_row_missing(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint32_t* h_missing) {
+    return guarded("storm_hip_dosage_row_missing", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        if (int rc = check_dosage("dosage_row_missing", m, h_missing, m ? m->n_rows : 0)) return rc;
+        if (int rc = check_samples("dosage_row_missing", m, n_samples)) return rc;
+        const uint64_t n = m->n_rows;
+        if (n == 0) return STORM_HIP_OK;
+        STORM_HIP_TRY(hipSetDevice(ctx->device));
+        if (int rc = ctx->d_counts.ensure(n * sizeof(uint32_t), "dosage_row_missing: the row scratch")) return rc;
+        hipLaunchKernelGGL(dosage_row_missing_kernel, dim3((uint32_t)((n + kWaves - 1) / kWaves)), dim3(kThreads), 0, ctx->stream, m->d,
+                           m->stride_words, n, m->n_words, n_samples, ctx->d_counts.d);
+        STORM_HIP_TRY(hipGetLastError());
+        STORM_HIP_TRY(hipMemcpyAsync(h_missing, ctx->d_counts.d, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return STORM_HIP_OK;
+    });
+}
+
+int storm_hip_pairw_dosage_nobs_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint32_t* d_out,
+                                       uint64_t ld) {
+    return guarded("storm_hip_pairw_dosage_nobs_device", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        if (int rc = check_dosage("pairw_dosage_nobs", m, d_out, ld)) return rc;
+        if (int rc = check_samples("pairw_dosage_nobs", m, n_samples)) return rc;
+        if (m->n_rows < 2) return STORM_HIP_OK;
+        STORM_HIP_TRY(hipSetDevice(ctx->device));
+        if (int rc = dosage_nobs_queued(ctx, m, n_samples, d_out, ld)) return rc;
+        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return STORM_HIP_OK;
+    });
+}
+
+int storm_hip_pairw_dosage_nobs(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint32_t* h_out, uint64_t ld) {
+    return guarded("storm_hip_pairw_dosage_nobs", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        if (int rc = check_dosage("pairw_dosage_nobs", m, h_out, ld)) return rc;
+        if (int rc = check_samples("pairw_dosage_nobs", m, n_samples)) return rc;
+        const uint64_t n = m->n_rows;
+        if (n == 0) return STORM_HIP_OK;
+        STORM_HIP_TRY(hipSetDevice(ctx->device));
+        const size_t need = (size_t)n * n * sizeof(uint32_t);
+        if (int rc = ctx->d_band.ensure(need, "pairw_dosage_nobs: the output")) return rc;
+        STORM_HIP_TRY(hipMemsetAsync(ctx->d_band, 0, need, ctx->stream));   // (entries i >= j)
+        if (n >= 2)
+            if (int rc = dosage_nobs_queued(ctx, m, n_samples, ctx->d_band, n)) return rc;
+        STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(uint32_t), ctx->d_band, n * sizeof(uint32_t), n * sizeof(uint32_t), n,
+                                       hipMemcpyDeviceToHost, ctx->stream));
+        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return STORM_HIP_OK;
+    });
+}
+
+int storm_hip_pairw_dosage_corr_complete_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_samples,
+                                                float* d_out, uint64_t ld) {
+    return guarded("storm_hip_pairw_dosage_corr_complete_device", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        if (int rc = check_dosage("pairw_dosage_corr_complete", m, d_out, ld)) return rc;
+        if (int rc = check_corr("pairw_dosage_corr_complete", m, measure, n_samples)) return rc;
+        if (m->n_rows < 2) return STORM_HIP_OK;
+        STORM_HIP_TRY(hipSetDevice(ctx->device));
+        if (int rc = dosage_corr_complete_queued(ctx, m, measure, n_samples, reinterpret_cast<uint32_t*>(d_out), ld)) return rc;
+        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return STORM_HIP_OK;
+    });
+}
+
+int storm_hip_pairw_dosage_corr_complete(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_samples,
+                                         float* h_out, uint64_t ld) {
+    return guarded("storm_hip_pairw_dosage_corr_complete", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        if (int rc = check_dosage("pairw_dosage_corr_complete", m, h_out, ld)) return rc;
+        if (int rc = check_corr("pairw_dosage_corr_complete", m, measure, n_samples)) return rc;
+        const uint64_t n = m->n_rows;
+        if (n == 0) return STORM_HIP_OK;
+        STORM_HIP_TRY(hipSetDevice(ctx->device));
+        const size_t need = (size_t)n * n * sizeof(uint32_t);
+        if (int rc = ctx->d_band.ensure(need, "pairw_dosage_corr_complete: the output")) return rc;
+        STORM_HIP_TRY(hipMemsetAsync(ctx->d_band, 0, need, ctx->stream));   // (entries i >= j: +0.0f is the same zero bits)
+        if (n >= 2)
+            if (int rc = dosage_corr_complete_queued(ctx, m, measure, n_samples, ctx->d_band, n)) return rc;
         STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(float), ctx->d_band, n * sizeof(uint32_t), n * sizeof(uint32_t), n,
                                        hipMemcpyDeviceToHost, ctx->stream));
         STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));

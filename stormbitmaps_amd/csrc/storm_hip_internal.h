@@ -222,6 +222,8 @@ struct storm_hip_ctx_s {
     std::vector<hipEvent_t> kernel_events;  // begin/end alternating
     size_t kernel_events_used = 0;
     storm::DevBuf<uint32_t> d_band;     // device staging of the host-output matrix calls (band x n_rows uint32)
+    storm::DevBuf<uint64_t> d_dosage_rows;   // dosage rows with missing genotypes: the split operands G, H, M (storm_hip_dosage.hip)
+    storm::DevBuf<uint32_t> d_dosage_sums;   // ... and the products G M^T, H M^T and N of storm_hip_pairw_dosage_corr_complete
     storm::DevBuf<void> d_positions;    // staging of storm_hip_matrix_set_rows_from_positions: offsets, then positions
     storm::DevBuf<uint32_t> d_counts;   // row-count scratch of the matrix-output paths
     storm::DevBuf<unsigned long long> d_trace;  // k2_ring = 18: per-item schedule trace of the strip kernel
@@ -280,6 +282,9 @@ int launch_pairw_lag_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, i
                             uint64_t band_rows, uint32_t* d_out, uint64_t ld, bool sync);
 // the dot products of rows of 2-bit values, upper triangle (K2h in its dosage form; storm_hip_dosage.hip finishes them)
 int launch_pairw_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint32_t* d_out, uint64_t ld, bool sync);
+// the rectangle of two such matrices: every row of A against every row of B (K2h in its dosage form, rectangle)
+int launch_square_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, uint32_t* d_out,
+                                uint64_t ld, bool sync);
 int launch_square_mfma(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
                        const storm_hip_matrix_s* b, uint64_t* d_total);
 int launch_square_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,

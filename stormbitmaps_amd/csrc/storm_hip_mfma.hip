@@ -1650,6 +1650,8 @@ void release_mfma_state(storm_hip_ctx_t* ctx) {
     ctx->d_trace.release();
     ctx->d_counts.release();
     ctx->d_band.release();
+    ctx->d_dosage_rows.release();
+    ctx->d_dosage_sums.release();
     ctx->d_parts.release();
     ctx->d_tickets.release();
     ctx->d_bitsegs.release();
@@ -2164,8 +2166,8 @@ static bool choose_tile128(const storm_hip_ctx_t* ctx, uint64_t tiles256, uint64
 // Plans the K2h list (plan_tile128, storm_hip_plan.cpp; cached by its request while the same call repeats), uploads it
 // and launches tile128_kernel. lag != 0 (triangle only): the lag form — the tiles within `lag` rows of the diagonal, written
 // in the lag layout (j_base and j_count must be 0: the kernel takes the lag where the rectangle's column count travels).
-// value_bits = 2 (triangle, no lag, no row counts): the rows hold 2-bit values and the kernel writes their dot products
-// (tile128_kernel<false, 2>); the list is planned with a chunk's weight of 9 x 256.
+// value_bits = 2 (triangle or rectangle, no lag, no row counts): the rows hold 2-bit values and the kernel writes their dot
+// products (tile128_kernel<false, 2>); the list is planned with a chunk's weight of 9 x 256.
 static int run_tile128(storm_hip_ctx_t* ctx, uint32_t ia0, uint32_t ia1, uint32_t jb0, uint32_t jb1, bool triangle,
                        uint32_t total_stages, const TileOperands& ops, uint32_t* d_out, uint64_t ld, uint32_t n_rows,
                        const uint32_t* d_counts, uint32_t and_weight, uint32_t j_base, uint32_t j_count, uint32_t i_lo,
@@ -2211,8 +2213,8 @@ static int run_tile128(storm_hip_ctx_t* ctx, uint32_t ia0, uint32_t ia1, uint32_
                            n_cols, ctx->d_parts, ctx->d_tickets);
     else if (ctx->n_part_items && value_bits == 2u)
         hipLaunchKernelGGL((tile128_kernel<false, 2>), dim3(ctx->n_part_items), dim3(kThThreads), 0, ctx->stream, ops,
-                           static_cast<const PartItem*>(ctx->d_items.d), d_out, ld, n_rows, nullptr, 1u, 0u, 0u, i_lo, n_cols,
-                           ctx->d_parts, ctx->d_tickets);
+                           static_cast<const PartItem*>(ctx->d_items.d), d_out, ld, n_rows, nullptr, 1u, j_base, j_count, i_lo,
+                           n_cols, ctx->d_parts, ctx->d_tickets);
     else if (ctx->n_part_items)
         hipLaunchKernelGGL(tile128_kernel<false>, dim3(ctx->n_part_items), dim3(kThThreads), 0, ctx->stream, ops,
                            static_cast<const PartItem*>(ctx->d_items.d), d_out, ld, n_rows, d_counts, and_weight, j_base,
@@ -2416,6 +2418,42 @@ int launch_pairw_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m
                                (m->n_words + 7u) / 8u * 4u, ops, d_out, ld, (uint32_t)n, nullptr, 1u, 0u, 0u, 0u, (uint32_t)n, sync,
                                0u, 2u);
     if (rc == STORM_HIP_EHIP) set_error("pairw_dosage_matrix: HIP failure");
+    return rc;
+}
+
+// The rectangle of two matrices of rows of 2-bit values (storm_hip_square_dosage_matrix_device): out[i * ld + j] =
+// sum_s a_i[s] b_j[s] for every row i of A and j of B (device pointer, uint32, ld >= b->n_rows; equal n_words and strides).
+// launch_square_matrix's K2h branch in the dosage form: B's virtual rows count on behind A's rows padded to 256.
+int launch_square_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, uint32_t* d_out,
+                                uint64_t ld, bool sync) {
+    if (a->n_rows == 0 || b->n_rows == 0) return STORM_HIP_OK;
+    if (a->stride_words != b->stride_words || a->n_words != b->n_words) {
+        set_error("square_dosage_matrix: rows of %u and %u words", a->n_words, b->n_words);
+        return STORM_HIP_EINVAL;
+    }
+    const uint64_t pitch = a->stride_words * 8;
+    if (pitch * 128u >= (1ull << 32)) {
+        set_error("square_dosage_matrix: rows of %llu operand bytes exceed the tile kernel's 32-bit DMA offsets",
+                  (unsigned long long)pitch);
+        return STORM_HIP_EINVAL;
+    }
+    const uint64_t rows_a = (a->n_rows + kTile - 1) / kTile * kTile;
+    if ((rows_a + b->n_rows + kThTile - 1) / kThTile > 65535u) {
+        set_error("square_dosage_matrix: too many row blocks");
+        return STORM_HIP_EINVAL;
+    }
+    ctx->k2_tile_shape_eff = 7;
+    ctx->pass_report[0] = STORM_HIP_RAN_TILES_OUT;
+    ctx->pass_report[1] = a->n_rows * b->n_rows * a->n_words;
+    ctx->pass_report[2] = ctx->pass_report[3] = 0;
+    const TileOperands ops = {reinterpret_cast<const uint8_t*>(a->d), reinterpret_cast<const uint8_t*>(b->d), pitch,
+                              (uint32_t)rows_a, (uint32_t)std::min<uint64_t>(a->n_rows_pad, rows_a),
+                              (uint32_t)std::min<uint64_t>(b->n_rows_pad, (b->n_rows + kThTile - 1) / kThTile * kThTile)};
+    const int rc = run_tile128(ctx, 0u, (uint32_t)((a->n_rows + kThTile - 1) / kThTile), (uint32_t)(rows_a / kThTile),
+                               (uint32_t)((rows_a + b->n_rows + kThTile - 1) / kThTile), false, (a->n_words + 7u) / 8u * 4u, ops,
+                               d_out, ld, (uint32_t)a->n_rows, nullptr, 1u, (uint32_t)rows_a, (uint32_t)b->n_rows, 0u, 0u, sync,
+                               0u, 2u);
+    if (rc == STORM_HIP_EHIP) set_error("square_dosage_matrix: HIP failure");
     return rc;
 }
 

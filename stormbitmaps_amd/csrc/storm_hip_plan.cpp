@@ -1285,7 +1285,8 @@ extern "C" int storm_hip_matrix_plan(uint64_t n_rows_a, uint64_t n_rows_b, uint3
 }
 
 // The K2h list of the dosage form (launch_pairw_dosage_matrix): the triangle of one matrix of rows of 2-bit values, planned
-// with a chunk's weight of 9 x 256. Arguments and records as storm_hip_matrix_plan; the rectangle has no dosage form.
+// with a chunk's weight of 9 x 256. Arguments and records as storm_hip_matrix_plan; the rectangle's list is
+// storm_hip_dosage_square_plan's.
 extern "C" int storm_hip_dosage_plan(uint64_t n_rows_a, uint64_t n_rows_b, uint32_t n_words, uint64_t band_row0,
                                      uint64_t band_rows, uint32_t n_cus, int slots_per_cu, int min_chunks, int diag_cost_pct,
                                      uint32_t* out, uint64_t capacity_items, uint64_t* n_items) {
@@ -1305,6 +1306,31 @@ extern "C" int storm_hip_dosage_plan(uint64_t n_rows_a, uint64_t n_rows_b, uint3
         return export_part_items("dosage_plan", plan, out, capacity_items, n_items);
     } catch (const std::exception& e) {
         set_error("dosage_plan: %s", e.what());
+        return STORM_HIP_ENOMEM;
+    }
+}
+
+// The K2h list of the dosage form's rectangle (launch_square_dosage_matrix): every 128 x 128 tile of n_rows_a x n_rows_b,
+// B's tiles counting on behind A's rows padded to 256 as in storm_hip_matrix_plan's rectangle; a chunk weighs 9 x 256.
+extern "C" int storm_hip_dosage_square_plan(uint64_t n_rows_a, uint64_t n_rows_b, uint32_t n_words, uint32_t n_cus,
+                                            int slots_per_cu, int min_chunks, int diag_cost_pct, uint32_t* out,
+                                            uint64_t capacity_items, uint64_t* n_items) {
+    using namespace storm;
+    const uint64_t rows_a = (n_rows_a + kTile - 1) / kTile * kTile;
+    if (!n_items || n_rows_a == 0 || n_rows_b == 0 || n_words == 0 || n_cus == 0 || slots_per_cu < 0 || slots_per_cu > 2 ||
+        min_chunks < 1 || diag_cost_pct < 10 || diag_cost_pct > 100 || n_rows_a > (1ull << 32) || n_rows_b > (1ull << 32) ||
+        (rows_a + n_rows_b + kThTile - 1) / kThTile > 65535u) {
+        set_error("dosage_square_plan: bad arguments");
+        return STORM_HIP_EINVAL;
+    }
+    try {
+        Tile128Plan plan;
+        plan_tile128({0u, (uint32_t)((n_rows_a + kThTile - 1) / kThTile), (uint32_t)(rows_a / kThTile),
+                      (uint32_t)((rows_a + n_rows_b + kThTile - 1) / kThTile), 0u, (n_words + 7u) / 8u * 4u, n_cus, slots_per_cu,
+                      min_chunks, diag_cost_pct, 1u, 0u, kThWeightDosage}, &plan);
+        return export_part_items("dosage_square_plan", plan, out, capacity_items, n_items);
+    } catch (const std::exception& e) {
+        set_error("dosage_square_plan: %s", e.what());
         return STORM_HIP_ENOMEM;
     }
 }

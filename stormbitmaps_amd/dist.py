@@ -155,6 +155,27 @@ def dosage_plan(n_rows: int, n_words: int, n_cus: int = 256, slots_per_cu: int =
     return out
 
 
+def dosage_square_plan(n_rows_a: int, n_rows_b: int, n_words: int, n_cus: int = 256, slots_per_cu: int = 0, min_chunks: int = 8,
+                       diag_cost_pct: int = 80):
+    """The items K2h launches in its dosage form for the rectangle of n_rows_a x n_rows_b rows of n_words words of 2-bit
+    values, as matrix_plan's records (storm_hip_dosage_square_plan in include/storm_hip.h: J counts on behind A's rows
+    padded to 256). Host-only."""
+    import ctypes as C
+
+    import numpy as np
+
+    from . import _lib
+    lib = _lib.load()
+    n = C.c_uint64(0)
+    args = (n_rows_a, n_rows_b, n_words, n_cus, slots_per_cu, min_chunks, diag_cost_pct)
+    _lib.check(lib.storm_hip_dosage_square_plan(*args, None, 0, C.byref(n)), "storm_hip_dosage_square_plan")
+    out = np.zeros((int(n.value), 8), dtype=np.uint32)
+    if n.value:
+        _lib.check(lib.storm_hip_dosage_square_plan(*args, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)),
+                   "storm_hip_dosage_square_plan")
+    return out
+
+
 def lag_plan(n_rows: int, n_words: int, max_lag: int, band_row0: int = 0, band_rows: int = 0, n_cus: int = 256,
              slots_per_cu: int = 0, min_chunks: int = 8, diag_cost_pct: int = 80):
     """The items of the lag layout's launch (the pairs within max_lag rows of each other; storm_hip_lag_plan in
