@@ -711,6 +711,10 @@ int storm_hip_stage_create(storm_hip_ctx_t* ctx, storm_hip_stage_t** out) {
         }
         *out = nullptr;
         STORM_HIP_TRY(hipSetDevice(ctx->device));
+        // What earlier stages left behind (storm_hip_stage_destroy puts its frees off) goes now, while a container is being
+        // filled and no all-pairs call is running: a caller that only ever asks for matrices never reaches the arena build,
+        // and its freed containers' rings and chunks used to pile up until the context went away.
+        drain_deferred(ctx, false);
         std::unique_ptr<storm_hip_stage_t> st(new storm_hip_stage_t());
         const size_t ring_bytes = 2 * storm_hip_stage_s::kBufBlocks * storm_hip_stage_s::kBlockBytes;
         if (hipHostMalloc(reinterpret_cast<void**>(&st->h_ring), ring_bytes + 2 * storm_hip_stage_s::kListBuf,
@@ -1296,6 +1300,9 @@ int storm_hip_matrix_create_from_blocks_wide(storm_hip_ctx_t* ctx, uint64_t n_ro
         storm_hip_matrix_t* m = nullptr;
         if (int rc = storm_hip_matrix_create(ctx, n_rows, std::max(max_id + 1u, min_blocks) * kBlockWords, &m)) return rc;
         m->sparse_origin = true;   // (the output kernel is chosen by this: storm_hip_internal.h, k2_tile_shape)
+        // (as build_arena: whatever an EARLIER container's stage or build left behind — this container's own stage is alive
+        // and not on the list; without this a handle that is invalidated or staged with streaming off never drains)
+        drain_deferred(ctx, false);
         struct MatrixDeleter {
             storm_hip_ctx_t* ctx;
             void operator()(storm_hip_matrix_t* x) const { storm_hip_matrix_destroy(ctx, x); }
