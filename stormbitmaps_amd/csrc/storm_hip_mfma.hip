@@ -90,6 +90,8 @@ typedef float v16f __attribute__((ext_vector_type(16)));
 using gptr_t = const __attribute__((address_space(1))) void*;
 using lptr_t = __attribute__((address_space(3))) void*;
 
+#include "tile_window.inc"   // TileOperands, OutWindow
+
 // 8 bits -> 8 nibbles holding `nib` (0b0010 = 1.0 in E2M1; other codes only for the power probe)
 __device__ __forceinline__ uint32_t spread8_fp4(uint32_t b, uint32_t nib = 2u) {
     uint32_t x = (b | (b << 12)) & 0x000F000Fu;
@@ -198,17 +200,10 @@ __device__ __forceinline__ void stage_tile(uint8_t* lds_tile, const uint8_t* __r
 template <uint32_t probe, bool kWrite = false>
 __global__ __launch_bounds__(kMfmaThreads, 2) void pairw_fp4_kernel(
     const uint8_t* __restrict__ X4, uint64_t row_bytes, const MfmaItem* __restrict__ items,
-    unsigned long long* __restrict__ slots, uint32_t* __restrict__ out = nullptr, uint64_t ld = 0,
-    uint32_t n_rows = 0, const uint32_t* __restrict__ row_counts = nullptr, uint32_t and_weight = 0,
-    uint32_t j_base = 0, uint32_t j_count = 0, uint32_t split_from = 0xffffffffu,
-    uint32_t i_lo = 0, uint32_t n_cols = 0) {
-    // rows i_lo <= i < n_rows are written, at output row i - i_lo (a band of the matrix); in
-    // triangle mode the columns run to n_cols (the matrix's row count)
+    unsigned long long* __restrict__ slots, OutWindow window = OutWindow{}, uint32_t split_from = 0xffffffffu) {
+    // kWrite: the counts go to the window (triangle, or the rectangle A x B of a shadow holding [A ; B]).
     // Items from index split_from on cover only a part of k of their tile (several per tile, to
-    // fill the last round of workgroups): they ADD into `out`, which zero_tiles_kernel cleared.
-    // kWrite window: rows i < n_rows of the shadow against shadow rows j_base + [0, j_count);
-    // j_count == 0 selects the triangle of one matrix (i < j < n_rows), otherwise the rectangle
-    // A x B of a shadow holding [A ; B] (B from shadow row j_base), written at column j - j_base.
+    // fill the last round of workgroups): they ADD into the window, which zero_tiles_kernel cleared.
     __shared__ __attribute__((aligned(1024))) uint8_t lds[kRing][2][kTileStageBytes];  // [stage][A|B]
 
     const uint32_t tid = threadIdx.x;
@@ -310,28 +305,27 @@ __global__ __launch_bounds__(kMfmaThreads, 2) void pairw_fp4_kernel(
     // ---- epilogue ----
     // C/D map of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
     if constexpr (kWrite) {
+        const OutWindow w = window.loaded();
 #pragma unroll
         for (int m = 0; m < 4; ++m)
 #pragma unroll
             for (int n = 0; n < 2; ++n) {
                 const uint32_t j = b_row0 + wn * 64u + n * 32u + (lane & 31u);
-                const bool rect = j_count != 0;
-                const bool j_ok = rect ? (j >= j_base && j - j_base < j_count) : j < n_cols;
                 // union / symmetric difference: n_i + n_j - and_weight * |i & j|
                 // (row_counts is indexed by shadow row)
-                const uint32_t nj = (row_counts && j_ok) ? row_counts[j] : 0u;
+                const bool j_ok = w.wants_col(j);
+                const uint32_t nj = w.nj(j);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const uint32_t i = a_row0 + wm * 128u + m * 32u + (r & 3) + 8 * (r >> 2) +
                                        4 * (lane >> 5);
-                    if (j_ok && i >= i_lo && i < n_rows && (rect || i < j)) {
+                    if (j_ok && w.writes_row(i, j)) {
                         const uint32_t c = (uint32_t)acc[m][n][r];
-                        uint32_t* dst = &out[(uint64_t)(i - i_lo) * ld + (j - j_base)];
+                        uint32_t* dst = w.at(i, j);
                         if (item_idx < split_from) {
-                            *dst = row_counts ? row_counts[i] + nj - and_weight * c : c;
+                            *dst = w.value(c, i, nj);
                         } else {  // partial over k: the n_i + n_j term once, mod 2^32 throughout
-                            const uint32_t once = (row_counts && it.stage0 == 0) ? row_counts[i] + nj : 0u;
-                            atomicAdd(dst, row_counts ? once - and_weight * c : c);
+                            atomicAdd(dst, w.part_value(c, i, nj, it.stage0 == 0));
                         }
                     }
                 }
@@ -848,14 +842,6 @@ __device__ __forceinline__ int tb_scale() {  // E8M0 block scale undoing v_c on 
     return C == 0 ? 128 : C == 1 ? 127 : 126;
 }
 
-struct TileOperands {       // where the virtual rows of the item table live
-    const uint8_t* xa;      // virtual rows [0, split): matrix A (or the only matrix)
-    const uint8_t* xb;      // virtual rows [split, ..): matrix B
-    uint64_t pitch;         // bytes per row of both
-    uint32_t split;         // first virtual row of matrix B (0xffffffff: none)
-    uint32_t rows_a, rows_b;  // allocated rows behind xa / xb (reads beyond return zero)
-};
-
 // Epilogue of the bit-operand kernels for a tile that lies wholly inside the output (no diagonal,
 // no edge, no k-parts, 16-byte aligned rows): the accumulators hold 16 ROWS of one column per
 // lane, so storing them directly costs one 4-byte store per element, two 128-byte runs per
@@ -930,10 +916,9 @@ __device__ __forceinline__ void tb_fetch(v4i& dst, uint32_t addr) {
 }
 
 __global__ __launch_bounds__(kMfmaThreads, 2) void tilebits8_kernel(
-    TileOperands ops, const MfmaItem* __restrict__ items, uint32_t* __restrict__ out, uint64_t ld,
-    uint32_t n_rows, const uint32_t* __restrict__ row_counts, uint32_t and_weight, uint32_t j_base,
-    uint32_t j_count, uint32_t split_from, uint32_t i_lo, uint32_t n_cols, uint32_t* __restrict__ parts) {
+    TileOperands ops, const MfmaItem* __restrict__ items, OutWindow window, uint32_t split_from, uint32_t* __restrict__ parts) {
     __shared__ __attribute__((aligned(1024))) uint8_t lds[kTbRing][kTbStageBytes];
+    const OutWindow w = window.loaded();
 
     STORM_CLOCK_BEGIN();
     const uint32_t tid = threadIdx.x;
@@ -947,26 +932,17 @@ __global__ __launch_bounds__(kMfmaThreads, 2) void tilebits8_kernel(
     const uint32_t S = it.n_stages / 4u;
     const uint32_t kbyte0 = it.stage0 * 16u;
     const uint32_t pitch = (uint32_t)ops.pitch;
-    const bool rect = j_count != 0;
 
-    auto window = [&](uint32_t v0, const uint8_t*& base, uint32_t& bytes) {
-        const bool second = v0 >= ops.split;
-        const uint32_t r0 = second ? v0 - ops.split : v0;
-        const uint32_t have = second ? ops.rows_b : ops.rows_a;
-        const uint32_t rows = have > r0 ? min(have - r0, (uint32_t)kTile) : 0u;
-        base = (second ? ops.xb : ops.xa) + (uint64_t)r0 * ops.pitch;
-        bytes = rows * pitch;
-    };
     const uint8_t *a_base, *b_base;
     uint32_t a_bytes, b_bytes;
-    window(a_row0, a_base, a_bytes);
-    window(b_row0, b_base, b_bytes);
+    ops.tile_rows(a_row0, (uint32_t)kTile, a_base, a_bytes);
+    ops.tile_rows(b_row0, (uint32_t)kTile, b_base, b_bytes);
 
     // blocks of B this wave multiplies: [n_lo, n_hi)
-    const uint32_t col_limit = rect ? j_base + j_count : n_cols;
+    const uint32_t col_limit = w.col_end();
     const uint32_t vc = col_limit > b_row0 ? min(col_limit - b_row0, (uint32_t)kTile) : 0u;
     const uint32_t n_hi = vc > 32u * wb ? min((vc - 32u * wb + 63u) / 64u, 4u) : 0u;
-    const uint32_t n_lo = (!rect && a_row0 == b_row0) ? min(wa, n_hi) : 0u;
+    const uint32_t n_lo = (!w.rect() && a_row0 == b_row0) ? min(wa, n_hi) : 0u;
     const uint32_t nb = n_hi - n_lo;
 
     const uint32_t voff0 = (wave * 16u + (lane >> 2)) * pitch + (((lane & 3u) ^ ((lane >> 4) & 3u)) * 16u);
@@ -998,10 +974,8 @@ __global__ __launch_bounds__(kMfmaThreads, 2) void tilebits8_kernel(
     // (profiles/r05_k_matrix_sizes.jsonl): the atomics are 10 of this kernel's 51 us at 1024 rows, not the 36 a count of
     // L2 atomic operations suggested, and the second kernel costs more than that.
     uint32_t* part_tile = (item_idx >= split_from && parts) ? parts + (uint64_t)(item_idx - split_from) * (kTile * kTile) : nullptr;
-    const bool full_tile = a_row0 >= i_lo && a_row0 + kTile <= n_rows &&
-        (rect ? (b_row0 >= j_base && b_row0 - j_base + kTile <= j_count) : (b_row0 + kTile <= n_cols && a_row0 != b_row0));
-    const bool interior = full_tile && (part_tile ? true : (item_idx < split_from && (ld & 3u) == 0 && ((uintptr_t)out & 15u) == 0));
-
+    const bool full_tile = w.covers(a_row0, (uint32_t)kTile, b_row0, (uint32_t)kTile);
+    const bool interior = full_tile && (part_tile ? true : (item_idx < split_from && (w.ld & 3u) == 0 && ((uintptr_t)w.out & 15u) == 0));
 
     auto run = [&](auto nbc) __attribute__((always_inline)) {
         constexpr int NB = decltype(nbc)::value;
@@ -1096,10 +1070,9 @@ __global__ __launch_bounds__(kMfmaThreads, 2) void tilebits8_kernel(
                 uint32_t* w32 = reinterpret_cast<uint32_t*>(mine);
                 const uint4* r128 = reinterpret_cast<const uint4*>(mine);
                 const uint32_t i0 = a_row0 + wa * 64u, j0 = b_row0 + 32u * wb;
-                const uint32_t* rcs = part_tile ? nullptr : row_counts;   // (a part holds raw AND counts)
-                const uint64_t ldx = part_tile ? (uint64_t)kTile : ld;
-                uint32_t* out_tile = part_tile ? &part_tile[(i0 - a_row0) * (uint32_t)kTile + (j0 - b_row0)]
-                                               : &out[(uint64_t)(i0 - i_lo) * ld + (j0 - j_base)];
+                const OutWindow::counts_ptr_t rcs = part_tile ? nullptr : w.counts();   // (a part holds raw AND counts)
+                const uint64_t ldx = part_tile ? (uint64_t)kTile : w.ld;
+                uint32_t* out_tile = part_tile ? &part_tile[(i0 - a_row0) * (uint32_t)kTile + (j0 - b_row0)] : w.at(i0, j0);
                 uint32_t nj[4] = {0u, 0u, 0u, 0u};
                 if (rcs) {
 #pragma unroll
@@ -1114,7 +1087,7 @@ __global__ __launch_bounds__(kMfmaThreads, 2) void tilebits8_kernel(
 #pragma unroll
                         for (int n = 0; n < 4; ++n) {
                             const uint32_t c = (uint32_t)acc[m][n][r];
-                            w32[il * 128u + (uint32_t)n * 32u + (lane & 31u)] = rcs ? ni + nj[n] - and_weight * c : c;
+                            w32[il * 128u + (uint32_t)n * 32u + (lane & 31u)] = rcs ? ni + nj[n] - w.and_weight * c : c;
                         }
                     }
                     // lane piece p = lane & 31: columns 4 p .. 4 p + 3 of the wave's 128 = block p / 8
@@ -1133,24 +1106,23 @@ __global__ __launch_bounds__(kMfmaThreads, 2) void tilebits8_kernel(
 #pragma unroll
         for (int n = 0; n < NB; ++n) {
             const uint32_t j = b_row0 + 64u * (n_lo + (uint32_t)n) + 32u * wb + (lane & 31u);
-            const bool j_ok = rect ? (j >= j_base && j - j_base < j_count) : j < n_cols;
-            const uint32_t nj = (row_counts && j_ok) ? row_counts[j] : 0u;
+            const bool j_ok = w.wants_col(j);
+            const uint32_t nj = w.nj(j);
 #pragma unroll
             for (int m = 0; m < 2; ++m)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const uint32_t i = a_row0 + wa * 64u + (uint32_t)m * 32u + (uint32_t)((r & 3) + 8 * (r >> 2)) +
                                        4u * (lane >> 5);
-                    if (j_ok && i >= i_lo && i < n_rows && (rect || i < j)) {
+                    if (j_ok && w.writes_row(i, j)) {
                         const uint32_t c = (uint32_t)acc[m][n][r];
-                        uint32_t* dst = &out[(uint64_t)(i - i_lo) * ld + (j - j_base)];
+                        uint32_t* dst = w.at(i, j);
                         if (item_idx < split_from) {
-                            *dst = row_counts ? row_counts[i] + nj - and_weight * c : c;
+                            *dst = w.value(c, i, nj);
                         } else if (part_tile) {
                             part_tile[(i - a_row0) * (uint32_t)kTile + (j - b_row0)] = c;
                         } else {
-                            const uint32_t once = (row_counts && it.stage0 == 0) ? row_counts[i] + nj : 0u;
-                            atomicAdd(dst, row_counts ? once - and_weight * c : c);
+                            atomicAdd(dst, w.part_value(c, i, nj, it.stage0 == 0));
                         }
                     }
                 }
@@ -1995,21 +1967,16 @@ static int ensure_counts_scratch(storm_hip_ctx_t* ctx, size_t n, uint32_t** out)
 // Clears the output window of the tiles whose k range is split over several items (same write
 // predicate as pairw_fp4_kernel<., true>). Grid (cut tile, band of 16 rows), thread = column. (Until round 5 the grid ran over
 // the PARTS and all but the first part of a tile returned at once: 2560 workgroups for 10 windows at 1024 rows, 8 us.)
-__global__ __launch_bounds__(256) void zero_tiles_kernel(const MfmaItem* __restrict__ items,
-                                                         uint32_t first,
-                                                         uint32_t* __restrict__ out, uint64_t ld,
-                                                         uint32_t n_rows, uint32_t j_base,
-                                                         uint32_t j_count, uint32_t i_lo,
-                                                         uint32_t n_cols) {
+__global__ __launch_bounds__(256) void zero_tiles_kernel(const MfmaItem* __restrict__ items, uint32_t first, OutWindow window) {
+    const OutWindow w = window.loaded();
     const MfmaItem it = items[first + blockIdx.x];   // `first`: where the records of the cut tiles begin (behind all items)
     const uint32_t j = (uint32_t)it.J * kTile + threadIdx.x;
-    const bool rect = j_count != 0;
-    if (!(rect ? (j >= j_base && j - j_base < j_count) : j < n_cols)) return;
+    if (!w.wants_col(j)) return;
     // blockIdx.y: band of 16 rows (one workgroup per tile took 16 us for the 92 windows of the
     // headline call: a serial walk down 256 rows)
     for (uint32_t r = blockIdx.y * 16u; r < blockIdx.y * 16u + 16u; ++r) {
         const uint32_t i = (uint32_t)it.I * kTile + r;
-        if (i >= i_lo && i < n_rows && (rect || i < j)) out[(uint64_t)(i - i_lo) * ld + (j - j_base)] = 0;
+        if (w.writes_row(i, j)) *w.at(i, j) = 0;
     }
 }
 
@@ -2018,24 +1985,21 @@ __global__ __launch_bounds__(256) void zero_tiles_kernel(const MfmaItem* __restr
 // band of kReduceBand rows), thread = column; the tile's first part does the work, its parts follow it in the item list.
 constexpr uint32_t kReduceBand = 2;   // rows per workgroup of reduce_parts_kernel
 __global__ __launch_bounds__(256) void reduce_parts_kernel(const MfmaItem* __restrict__ items, uint32_t first, uint32_t n_items,
-                                                           const uint32_t* __restrict__ parts, uint32_t* __restrict__ out,
-                                                           uint64_t ld, uint32_t n_rows,
-                                                           const uint32_t* __restrict__ row_counts, uint32_t and_weight,
-                                                           uint32_t j_base, uint32_t j_count, uint32_t i_lo, uint32_t n_cols) {
+                                                           const uint32_t* __restrict__ parts, OutWindow window) {
+    const OutWindow w = window.loaded();
     const uint32_t k = first + blockIdx.x;
     const MfmaItem it = items[k];
     if (it.stage0 != 0) return;
     uint32_t n_parts = 1;
     while (k + n_parts < n_items && items[k + n_parts].stage0 != 0) ++n_parts;   // (a tile's parts: stage0 ascending from 0)
     const uint32_t j = (uint32_t)it.J * kTile + threadIdx.x;
-    const bool rect = j_count != 0;
-    if (!(rect ? (j >= j_base && j - j_base < j_count) : j < n_cols)) return;
-    const uint32_t nj = row_counts ? row_counts[j] : 0u;
+    if (!w.wants_col(j)) return;
+    const uint32_t nj = w.nj(j);
     const uint32_t* src = parts + (uint64_t)blockIdx.x * (kTile * kTile) + threadIdx.x;
     // blockIdx.y: band of kReduceBand rows; the parts' loads of a row are independent: eight in flight
     for (uint32_t r = blockIdx.y * kReduceBand; r < blockIdx.y * kReduceBand + kReduceBand; ++r) {
         const uint32_t i = (uint32_t)it.I * kTile + r;
-        if (i >= i_lo && i < n_rows && (rect || i < j)) {
+        if (w.writes_row(i, j)) {
             uint32_t c = 0;
             const uint32_t* row = src + r * (uint32_t)kTile;
             uint32_t p = 0;
@@ -2047,7 +2011,7 @@ __global__ __launch_bounds__(256) void reduce_parts_kernel(const MfmaItem* __res
                 for (uint32_t q = 0; q < 8u; ++q) c += v[q];
             }
             for (; p < n_parts; ++p) c += row[(uint64_t)p * (kTile * kTile)];
-            out[(uint64_t)(i - i_lo) * ld + (j - j_base)] = row_counts ? row_counts[i] + nj - and_weight * c : c;
+            *w.at(i, j) = w.value(c, i, nj);
         }
     }
 }
@@ -2080,16 +2044,14 @@ static int ensure_matrix_tiles(storm_hip_ctx_t* ctx, MatrixTilesRequest&& rq, Ma
     return STORM_HIP_OK;
 }
 
-// Runs the tile kernel in write mode over the planned items (shadow already expanded). The kernel
-// holds one workgroup per CU, so n tiles take ceil(n / CUs) rounds and a nearly empty last round
-// costs a whole one (820 tiles on 256 CUs at the headline shape: 3.2 -> 4). The tiles of the last
-// round are therefore cut along k into as many parts as fill the CUs; the parts add into a
-// cleared window.
-static int run_matrix_tiles(storm_hip_ctx_t* ctx, const MatrixPlan& plan, uint64_t pitch,
-                            uint32_t* d_out, uint64_t ld, uint32_t n_rows, const uint32_t* d_counts,
-                            uint32_t and_weight, uint32_t j_base, uint32_t j_count, uint32_t i_lo = 0,
-                            uint32_t n_cols = 0, bool sync = true, const TileOperands* bits = nullptr) {
-    if (n_cols == 0) n_cols = n_rows;
+// Runs the 256 x 256 tile kernel that k2_tile_shape_eff names over the planned items, into the window w. `bits` (the
+// default): the operands are the matrix rows themselves; otherwise (the FP4 forms) ops is the shadow, as one matrix, that
+// the caller has just expanded in the tile layout. The kernel holds one workgroup per CU, so n tiles take ceil(n / CUs)
+// rounds and a nearly empty last round costs a whole one (820 tiles on 256 CUs at the headline shape: 3.2 -> 4). The
+// tiles of the last round are therefore cut along k into as many parts as fill the CUs; the parts add into a cleared
+// window (or, option k2_matrix_parts, write windows of their own that reduce_parts_kernel adds up).
+static int run_matrix_tiles(storm_hip_ctx_t* ctx, const MatrixPlan& plan, const TileOperands& ops, bool bits, const OutWindow& w,
+                            bool sync) {
     if (!bits) memset(ctx->x4_key, 0, sizeof(ctx->x4_key));  // callers rebuilt the shadow in the tile layout
     const MfmaItem* d_items = static_cast<const MfmaItem*>(ctx->d_items.d);
     // [r5] option k2_matrix_parts: the k-parts of the tile kernels that ship write their own windows and a second kernel
@@ -2104,8 +2066,7 @@ static int run_matrix_tiles(storm_hip_ctx_t* ctx, const MatrixPlan& plan, uint64
             d_parts = ctx->d_parts;   // (no memory for the windows: the atomics still work)
     }
     if (n_split && !d_parts)
-        hipLaunchKernelGGL(zero_tiles_kernel, dim3(plan.n_cut, kTile / 16), dim3(256), 0,
-                           ctx->stream, d_items, plan.n_items, d_out, ld, n_rows, j_base, j_count, i_lo, n_cols);
+        hipLaunchKernelGGL(zero_tiles_kernel, dim3(plan.n_cut, kTile / 16), dim3(256), 0, ctx->stream, d_items, plan.n_items, w);
     if (bits && ctx->k2_tile_shape_eff == 3 && timing_env()) {
         int nb = -1;
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, tile16_bits_kernel, kTiThreads, kTiLdsBytes);
@@ -2113,45 +2074,71 @@ static int run_matrix_tiles(storm_hip_ctx_t* ctx, const MatrixPlan& plan, uint64
     }
     if (bits && ctx->k2_tile_shape_eff == 3)
         hipLaunchKernelGGL(tile16_bits_kernel, dim3((plan.n_items + 7u) / 8u * 16u), dim3(kTiThreads), kTiLdsBytes, ctx->stream,
-                           *bits, d_items, plan.n_items, d_out, ld, n_rows, d_counts, and_weight, j_base, j_count,
-                           plan.n_full, i_lo, n_cols);
+                           ops, d_items, plan.n_items, w, plan.n_full);
     else if (bits && ctx->k2_tile_shape_eff == 4)
         hipLaunchKernelGGL(tile32_bits_kernel, dim3((plan.n_items + 7u) / 8u * 16u), dim3(kTiThreads), kTiLdsBytes, ctx->stream,
-                           *bits, d_items, plan.n_items, d_out, ld, n_rows, d_counts, and_weight, j_base, j_count,
-                           plan.n_full, i_lo, n_cols);
+                           ops, d_items, plan.n_items, w, plan.n_full);
     else if (bits && ctx->k2_tile_shape_eff == 5 && ctx->k2_ring_sync == 0)
-        hipLaunchKernelGGL(tilering_kernel<false>, dim3(plan.n_items), dim3(kTrThreads), 0, ctx->stream,
-                           *bits, d_items, d_out, ld, n_rows, d_counts, and_weight, j_base, j_count,
-                           plan.n_full, i_lo, n_cols, d_parts);
+        hipLaunchKernelGGL(tilering_kernel<false>, dim3(plan.n_items), dim3(kTrThreads), 0, ctx->stream, ops, d_items, w,
+                           plan.n_full, d_parts);
     else if (bits && ctx->k2_tile_shape_eff == 5)
-        hipLaunchKernelGGL(tilering_kernel<true>, dim3(plan.n_items), dim3(kTrThreads), 0, ctx->stream,
-                           *bits, d_items, d_out, ld, n_rows, d_counts, and_weight, j_base, j_count,
-                           plan.n_full, i_lo, n_cols, d_parts);
+        hipLaunchKernelGGL(tilering_kernel<true>, dim3(plan.n_items), dim3(kTrThreads), 0, ctx->stream, ops, d_items, w,
+                           plan.n_full, d_parts);
     else if (bits && ctx->k2_tile_shape_eff == 2)
-        hipLaunchKernelGGL(tilebits8_kernel, dim3(plan.n_items), dim3(kMfmaThreads), 0, ctx->stream,
-                           *bits, d_items, d_out, ld, n_rows, d_counts, and_weight, j_base, j_count,
-                           plan.n_full, i_lo, n_cols, d_parts);
+        hipLaunchKernelGGL(tilebits8_kernel, dim3(plan.n_items), dim3(kMfmaThreads), 0, ctx->stream, ops, d_items, w,
+                           plan.n_full, d_parts);
 #ifdef STORM_HIP_PROBES
     else if (bits)
-        hipLaunchKernelGGL(tilebits_kernel, dim3(plan.n_items), dim3(kTbThreads), 0, ctx->stream,
-                           *bits, d_items, d_out, ld, n_rows, d_counts, and_weight, j_base, j_count,
-                           plan.n_full, i_lo, n_cols);
+        hipLaunchKernelGGL(tilebits_kernel, dim3(plan.n_items), dim3(kTbThreads), 0, ctx->stream, ops, d_items, w, plan.n_full);
     else if (ctx->k2_tile_shape_eff == 16)
-        hipLaunchKernelGGL(tile16_fp4_kernel, dim3(plan.n_items), dim3(kMfmaThreads), 0, ctx->stream,
-                           ctx->d_x4, pitch, d_items, d_out, ld, n_rows, d_counts, and_weight, j_base,
-                           j_count, plan.n_full, i_lo, n_cols);
+        hipLaunchKernelGGL(tile16_fp4_kernel, dim3(plan.n_items), dim3(kMfmaThreads), 0, ctx->stream, ops.xa, ops.pitch, d_items,
+                           w, plan.n_full);
 #endif
     else
-        hipLaunchKernelGGL((pairw_fp4_kernel<0, true>), dim3(plan.n_items), dim3(kMfmaThreads), 0,
-                           ctx->stream, ctx->d_x4, pitch, d_items, ctx->d_slots, d_out, ld, n_rows,
-                           d_counts, and_weight, j_base, j_count,
-                           plan.n_full, i_lo, n_cols);
+        hipLaunchKernelGGL((pairw_fp4_kernel<0, true>), dim3(plan.n_items), dim3(kMfmaThreads), 0, ctx->stream, ops.xa, ops.pitch,
+                           d_items, ctx->d_slots, w, plan.n_full);
     if (d_parts)
         hipLaunchKernelGGL(reduce_parts_kernel, dim3(n_split, kTile / kReduceBand), dim3(256), 0, ctx->stream, d_items, plan.n_full,
-                           plan.n_items, d_parts, d_out, ld, n_rows, d_counts, and_weight, j_base, j_count, i_lo, n_cols);
+                           plan.n_items, d_parts, w);
     if (hipGetLastError() != hipSuccess) return STORM_HIP_EHIP;
     if (sync && wait_stream(ctx) != hipSuccess) return STORM_HIP_EHIP;
     return STORM_HIP_OK;
+}
+
+// ---- what the materialised-output entry points share ----
+// The limits of the tile kernels, under the entry point's name: 32-bit DMA offsets within a tile of `tile_rows` rows, and
+// 16-bit row-block numbers in the item records. pitch_first: which of the two a call that exceeds both reports (each entry
+// point keeps the order it had).
+static int check_tile_limits(const char* entry, uint64_t pitch, uint64_t tile_rows, uint64_t row_blocks, bool pitch_first) {
+    const bool blocks_bad = row_blocks > 65535u;
+    const bool pitch_bad = pitch * tile_rows >= (1ull << 32);  // FP4 shadow: rows of 2^25 bits; bit operands: 2^27
+    if (pitch_bad && (pitch_first || !blocks_bad))
+        set_error("%s: rows of %llu operand bytes exceed the tile kernel's 32-bit DMA offsets", entry, (unsigned long long)pitch);
+    else if (blocks_bad)
+        set_error("%s: too many row blocks", entry);
+    return pitch_bad || blocks_bad ? STORM_HIP_EINVAL : STORM_HIP_OK;
+}
+
+// (a report of its own: the per-pair output is no all-pairs pass)
+static void report_tiles_out(storm_hip_ctx_t* ctx, uint64_t word_pairs) {
+    ctx->pass_report[0] = STORM_HIP_RAN_TILES_OUT;
+    ctx->pass_report[1] = word_pairs;
+    ctx->pass_report[2] = ctx->pass_report[3] = 0;
+}
+
+// The per-row counts the OR / XOR epilogues need, per virtual row: a's rows and, with b, b's from virtual row rows_a on
+// (n virtual rows in all). AND: none, *d_counts = null.
+static int op_row_counts(storm_hip_ctx_t* ctx, int op, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, uint64_t rows_a,
+                         uint64_t n, uint32_t** d_counts) {
+    *d_counts = nullptr;
+    if (op == STORM_HIP_OP_AND) return STORM_HIP_OK;
+    int rc = ensure_counts_scratch(ctx, n, d_counts);
+    if (rc == STORM_HIP_OK) rc = launch_row_counts(ctx, a, *d_counts);
+    if (rc == STORM_HIP_OK && b) rc = launch_row_counts(ctx, b, *d_counts + rows_a);
+    return rc;
+}
+static int op_row_counts(storm_hip_ctx_t* ctx, int op, const storm_hip_matrix_s* m, uint32_t** d_counts) {
+    return op_row_counts(ctx, op, m, nullptr, 0, m->n_rows, d_counts);
 }
 
 // ---- K2h (tile128_kernel): 128 x 128 tiles for matrices of few 256 x 256 tiles, k-parts whose sums meet inside the launch ----
@@ -2163,20 +2150,17 @@ static bool choose_tile128(const storm_hip_ctx_t* ctx, uint64_t tiles256, uint64
     return ctx->k2_tile_shape == 0 && tiles256 < (uint64_t)ctx->k2_wave_below;
 }
 
-// Plans the K2h list (plan_tile128, storm_hip_plan.cpp; cached by its request while the same call repeats), uploads it
-// and launches tile128_kernel. lag != 0 (triangle only): the lag form — the tiles within `lag` rows of the diagonal, written
-// in the lag layout (j_base and j_count must be 0: the kernel takes the lag where the rectangle's column count travels).
-// value_bits = 2 (triangle or rectangle, no lag, no row counts): the rows hold 2-bit values and the kernel writes their dot
-// products (tile128_kernel<false, 2>); the list is planned with a chunk's weight of 9 x 256.
-static int run_tile128(storm_hip_ctx_t* ctx, uint32_t ia0, uint32_t ia1, uint32_t jb0, uint32_t jb1, bool triangle,
-                       uint32_t total_stages, const TileOperands& ops, uint32_t* d_out, uint64_t ld, uint32_t n_rows,
-                       const uint32_t* d_counts, uint32_t and_weight, uint32_t j_base, uint32_t j_count, uint32_t i_lo,
-                       uint32_t n_cols, bool sync, uint32_t lag = 0u, uint32_t value_bits = 1u) {
-    if (ia1 > 65535u || jb1 > 65535u) {
-        set_error("pairw_matrix: too many row blocks");
-        return STORM_HIP_EINVAL;
-    }
-    const Tile128Request rq = {ia0, ia1, jb0, jb1, triangle ? 1u : 0u, total_stages, (uint32_t)std::max(1, ctx->n_cus),
+// Plans the K2h list of the 128 x 128 tiles that hold a pair of the window (plan_tile128, storm_hip_plan.cpp; cached by its
+// request while the same call repeats), uploads it and launches tile128_kernel in the window's form over total_stages
+// 128-bit stages of k. value_bits = 2 (triangle or rectangle, no row counts): the rows hold 2-bit values and the kernel
+// writes their dot products (tile128_kernel<false, 2>); the list is planned with a chunk's weight of 9 x 256.
+static int run_tile128(storm_hip_ctx_t* ctx, uint32_t total_stages, const TileOperands& ops, const OutWindow& w, bool sync,
+                       uint32_t value_bits) {
+    const uint32_t lag = w.form == OutForm::Lag ? w.lag : 0u;
+    const uint32_t ia0 = w.i_lo / kThTile, ia1 = (w.n_rows + kThTile - 1) / kThTile;
+    const uint32_t jb0 = w.j_base / kThTile, jb1 = (w.col_end() + kThTile - 1) / kThTile;
+    if (int rc = check_tile_limits("pairw_matrix", 0, kThTile, std::max(ia1, jb1), false)) return rc;
+    const Tile128Request rq = {ia0, ia1, jb0, jb1, w.rect() ? 0u : 1u, total_stages, (uint32_t)std::max(1, ctx->n_cus),
                                ctx->k2_part_slots, ctx->k2_part_min_chunks, ctx->k2_part_cost_diag,
                                ctx->k2_part_narrow != 0 ? 1u : 0u, lag, value_bits == 2u ? kThWeightDosage : kThWeightBits};
     const Tile128Request* have = std::get_if<Tile128Request>(&ctx->items_key);
@@ -2207,18 +2191,16 @@ static int run_tile128(storm_hip_ctx_t* ctx, uint32_t ia0, uint32_t ia1, uint32_
         STORM_HIP_TRY(hipMemsetAsync(ctx->d_tickets, 0, ctx->d_tickets.capacity, ctx->stream));
         ctx->tickets_dirty = false;
     }
-    if (ctx->n_part_items && lag)
-        hipLaunchKernelGGL(tile128_kernel<true>, dim3(ctx->n_part_items), dim3(kThThreads), 0, ctx->stream, ops,
-                           static_cast<const PartItem*>(ctx->d_items.d), d_out, ld, n_rows, d_counts, and_weight, 0u, lag, i_lo,
-                           n_cols, ctx->d_parts, ctx->d_tickets);
+    const PartItem* d_items = static_cast<const PartItem*>(ctx->d_items.d);
+    if (ctx->n_part_items && w.form == OutForm::Lag)
+        hipLaunchKernelGGL(tile128_kernel<true>, dim3(ctx->n_part_items), dim3(kThThreads), 0, ctx->stream, ops, d_items, w,
+                           ctx->d_parts, ctx->d_tickets);
     else if (ctx->n_part_items && value_bits == 2u)
-        hipLaunchKernelGGL((tile128_kernel<false, 2>), dim3(ctx->n_part_items), dim3(kThThreads), 0, ctx->stream, ops,
-                           static_cast<const PartItem*>(ctx->d_items.d), d_out, ld, n_rows, nullptr, 1u, j_base, j_count, i_lo,
-                           n_cols, ctx->d_parts, ctx->d_tickets);
+        hipLaunchKernelGGL((tile128_kernel<false, 2>), dim3(ctx->n_part_items), dim3(kThThreads), 0, ctx->stream, ops, d_items, w,
+                           ctx->d_parts, ctx->d_tickets);
     else if (ctx->n_part_items)
-        hipLaunchKernelGGL(tile128_kernel<false>, dim3(ctx->n_part_items), dim3(kThThreads), 0, ctx->stream, ops,
-                           static_cast<const PartItem*>(ctx->d_items.d), d_out, ld, n_rows, d_counts, and_weight, j_base,
-                           j_count, i_lo, n_cols, ctx->d_parts, ctx->d_tickets);
+        hipLaunchKernelGGL(tile128_kernel<false>, dim3(ctx->n_part_items), dim3(kThThreads), 0, ctx->stream, ops, d_items, w,
+                           ctx->d_parts, ctx->d_tickets);
     if (hipGetLastError() != hipSuccess) {
         ctx->tickets_dirty = true;
         return STORM_HIP_EHIP;
@@ -2239,9 +2221,7 @@ int launch_pairw_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int o
     const uint64_t band_end = std::min<uint64_t>(m->n_rows, band_row0 + band_rows);
     if (band_row0 >= band_end) return STORM_HIP_OK;
     ctx->k2_tile_shape_eff = (ctx->k2_tile_shape && ctx->k2_tile_shape != 6) ? ctx->k2_tile_shape : (m->sparse_origin ? 2 : 5);   // (6 = K2w, chosen below; not eligible: as 0)
-    ctx->pass_report[0] = STORM_HIP_RAN_TILES_OUT;   // (a report of its own: the per-pair output is no all-pairs pass)
-    ctx->pass_report[1] = m->n_rows * (m->n_rows - (m->n_rows != 0)) / 2 * m->n_words;
-    ctx->pass_report[2] = ctx->pass_report[3] = 0;
+    report_tiles_out(ctx, m->n_rows * (m->n_rows - (m->n_rows != 0)) / 2 * m->n_words);
     if (m->n_rows < 2) return STORM_HIP_OK;
     const uint64_t n_rows4 = (m->n_rows + kStripATile - 1) / kStripATile * kStripATile;
     const uint64_t row_bytes = m->stride_words * 32;
@@ -2249,15 +2229,7 @@ int launch_pairw_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int o
     const bool bits = ctx->k2_tile_shape_eff <= 5;
     const uint64_t pitch = bits ? m->stride_words * 8 : shadow_pitch(ctx, row_bytes);
     const size_t x4_bytes = bits ? 0 : (size_t)n_rows4 * pitch;
-    if (n_rows4 / kTile >= 65535) {
-        set_error("pairw_matrix: too many row blocks");
-        return STORM_HIP_EINVAL;
-    }
-    if (pitch * (uint64_t)kTile >= (1ull << 32)) {  // FP4 shadow: rows of 2^25 bits; bit operands: 2^27
-        set_error("pairw_matrix: rows of %llu operand bytes exceed the tile kernel's 32-bit DMA offsets",
-                  (unsigned long long)pitch);
-        return STORM_HIP_EINVAL;
-    }
+    if (int rc = check_tile_limits("pairw_matrix", pitch, kTile, n_rows4 / kTile + 1, false)) return rc;
     if (int rc = ensure_shadow(ctx, x4_bytes, "pairw_matrix: the FP4 shadow")) return rc;
     // stages of 128 bits; the bit kernels walk whole 512-bit chunks that hold DATA (the pitch's pad chunks — 8 of 136 at
     // the headline shape since round 4's pitch pad — are never multiplied)
@@ -2265,80 +2237,60 @@ int launch_pairw_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int o
     const uint32_t nT = (uint32_t)((m->n_rows + kTile - 1) / kTile);
     // [r6] few tiles: 128 x 128 tiles, cut along k where they are too few, the parts' sums meeting inside the launch
     // (tile128_kernel) instead of k-parts of 256 x 256 tiles that clear and atomically add into the output
-    {
-        const uint64_t band_tiles = (uint64_t)((band_end + kTile - 1) / kTile - band_row0 / kTile);
-        const uint64_t tiles256 = band_tiles * nT - (band_row0 / kTile) * band_tiles - band_tiles * (band_tiles - 1) / 2;
-        if (choose_tile128(ctx, tiles256, pitch, bits)) {
-            ctx->k2_tile_shape_eff = 6;
-            uint32_t* d_counts = nullptr;
-            int rc = STORM_HIP_OK;
-            if (op != STORM_HIP_OP_AND) {
-                rc = ensure_counts_scratch(ctx, m->n_rows, &d_counts);
-                if (rc == STORM_HIP_OK) rc = launch_row_counts(ctx, m, d_counts);
-            }
-            if (rc == STORM_HIP_OK) {
-                const TileOperands ops = {reinterpret_cast<const uint8_t*>(m->d), nullptr, pitch, 0xffffffffu,
-                                          (uint32_t)std::min<uint64_t>(m->n_rows_pad, 0xffffffffu), 0u};
-                rc = run_tile128(ctx, (uint32_t)(band_row0 / kThTile), (uint32_t)((band_end + kThTile - 1) / kThTile), 0u,
-                                 (uint32_t)((m->n_rows + kThTile - 1) / kThTile), true, total_stages, ops, d_out, ld,
-                                 (uint32_t)band_end, d_counts, op == STORM_HIP_OP_XOR ? 2u : 1u, 0u, 0u,
-                                 (uint32_t)band_row0, (uint32_t)m->n_rows, sync);
-            }
-            if (rc == STORM_HIP_EHIP) set_error("pairw_matrix: HIP failure");
-            return rc;
-        }
-    }
-    // off-diagonal tiles first; the diagonal ones (half of their window is written) go last,
-    // where run_matrix_tiles may cut them along k
-    MatrixTilesRequest rq;
-    rq.total_stages = total_stages;
-    std::vector<std::pair<uint16_t, uint16_t>>& tiles = rq.tiles;
-    const uint32_t t_lo = (uint32_t)(band_row0 / kTile), t_hi = (uint32_t)((band_end + kTile - 1) / kTile);
-    // ... and last of all the tiles of a ragged last row block (few valid columns): with
-    // tilebits8_kernel both kinds are short items, and the k-split of the last round then works on
-    // the shortest ones
-    const bool ragged = m->n_rows % kTile != 0 && m->n_rows % kTile <= 192 && nT > 1;
-    const uint32_t nT_full = ragged ? nT - 1 : nT;
-    xcd_grouped_tiles(t_lo, std::min(t_hi, nT_full), 0, nT_full, true, tiles);
-    for (uint32_t i = t_lo; i < std::min(t_hi, nT_full); ++i) tiles.emplace_back((uint16_t)i, (uint16_t)i);
-    if (ragged)
-        for (uint32_t i = t_lo; i < t_hi; ++i) tiles.emplace_back((uint16_t)i, (uint16_t)(nT - 1));
-    uint32_t* d_counts = nullptr;
+    const uint64_t band_tiles = (uint64_t)((band_end + kTile - 1) / kTile - band_row0 / kTile);
+    const uint64_t tiles256 = band_tiles * nT - (band_row0 / kTile) * band_tiles - band_tiles * (band_tiles - 1) / 2;
+    const bool k2h = choose_tile128(ctx, tiles256, pitch, bits);
+    int rc = STORM_HIP_OK;
     MatrixPlan plan;
-    // what a tile costs next to a full one under tilebits8_kernel: a diagonal tile multiplies 5 of its
-    // 8 block pairs per SIMD; a ragged one ceil(columns / 64) of 4 blocks per wave, but not below the
-    // inflation work of its A operands (measured: 0.3)
-    std::vector<float>& cost = rq.cost;
-    if (ctx->k2_tile_shape_eff >= 2 && ctx->k2_tile_shape_eff <= 5) {
-        // (tilering_kernel: a diagonal tile keeps its busiest SIMD at 12 of 16 block rows; a ragged column multiplies one
-        //  block column in two of the eight waves but stores all of its images: options k2_ring_cost_*)
-        const bool ring = ctx->k2_tile_shape_eff == 5;
-        const float ragged_cost = ring ? std::max(ctx->k2_ring_cost_ragged / 100.0f, m->n_rows % kTile > 16 ? 1.0f : 0.0f)
-                                       : std::max(ctx->k2_tile_cost_ragged / 100.0f, (float)((m->n_rows % kTile + 63) / 64) / 4.0f);
-        for (const auto& t : tiles) {
-            float c = t.first == t.second ? (ring ? ctx->k2_ring_cost_diag : ctx->k2_tile_cost_diag) / 100.0f : 1.0f;
-            if (ragged && t.second == nT - 1) c *= ragged_cost;
-            cost.push_back(c);
+    if (k2h) {
+        ctx->k2_tile_shape_eff = 6;
+    } else {
+        // off-diagonal tiles first; the diagonal ones (half of their window is written) go last,
+        // where run_matrix_tiles may cut them along k
+        MatrixTilesRequest rq;
+        rq.total_stages = total_stages;
+        std::vector<std::pair<uint16_t, uint16_t>>& tiles = rq.tiles;
+        const uint32_t t_lo = (uint32_t)(band_row0 / kTile), t_hi = (uint32_t)((band_end + kTile - 1) / kTile);
+        // ... and last of all the tiles of a ragged last row block (few valid columns): with
+        // tilebits8_kernel both kinds are short items, and the k-split of the last round then works on
+        // the shortest ones
+        const bool ragged = m->n_rows % kTile != 0 && m->n_rows % kTile <= 192 && nT > 1;
+        const uint32_t nT_full = ragged ? nT - 1 : nT;
+        xcd_grouped_tiles(t_lo, std::min(t_hi, nT_full), 0, nT_full, true, tiles);
+        for (uint32_t i = t_lo; i < std::min(t_hi, nT_full); ++i) tiles.emplace_back((uint16_t)i, (uint16_t)i);
+        if (ragged)
+            for (uint32_t i = t_lo; i < t_hi; ++i) tiles.emplace_back((uint16_t)i, (uint16_t)(nT - 1));
+        // what a tile costs next to a full one under tilebits8_kernel: a diagonal tile multiplies 5 of its
+        // 8 block pairs per SIMD; a ragged one ceil(columns / 64) of 4 blocks per wave, but not below the
+        // inflation work of its A operands (measured: 0.3)
+        std::vector<float>& cost = rq.cost;
+        if (ctx->k2_tile_shape_eff >= 2 && ctx->k2_tile_shape_eff <= 5) {
+            // (tilering_kernel: a diagonal tile keeps its busiest SIMD at 12 of 16 block rows; a ragged column multiplies one
+            //  block column in two of the eight waves but stores all of its images: options k2_ring_cost_*)
+            const bool ring = ctx->k2_tile_shape_eff == 5;
+            const float ragged_cost = ring ? std::max(ctx->k2_ring_cost_ragged / 100.0f, m->n_rows % kTile > 16 ? 1.0f : 0.0f)
+                                           : std::max(ctx->k2_tile_cost_ragged / 100.0f, (float)((m->n_rows % kTile + 63) / 64) / 4.0f);
+            for (const auto& t : tiles) {
+                float c = t.first == t.second ? (ring ? ctx->k2_ring_cost_diag : ctx->k2_tile_cost_diag) / 100.0f : 1.0f;
+                if (ragged && t.second == nT - 1) c *= ragged_cost;
+                cost.push_back(c);
+            }
         }
+        rc = ensure_matrix_tiles(ctx, std::move(rq), &plan);
     }
-    int rc = ensure_matrix_tiles(ctx, std::move(rq), &plan);
-    if (rc == STORM_HIP_OK && op != STORM_HIP_OP_AND) {
-        rc = ensure_counts_scratch(ctx, m->n_rows, &d_counts);
-        if (rc == STORM_HIP_OK) rc = launch_row_counts(ctx, m, d_counts);
-    }
+    uint32_t* d_counts = nullptr;
+    if (rc == STORM_HIP_OK) rc = op_row_counts(ctx, op, m, &d_counts);
     if (rc == STORM_HIP_OK) {
-        const TileOperands ops = {reinterpret_cast<const uint8_t*>(m->d), nullptr, pitch, 0xffffffffu,
-                                  (uint32_t)std::min<uint64_t>(m->n_rows_pad, 0xffffffffu), 0u};
+        // rows [band_row0, band_end) are written; the columns run over the whole matrix
+        const OutWindow w = triangle_window(d_out, ld, band_row0, band_end, m->n_rows, d_counts, op);
         if (!bits) {
             const dim3 grid = expand_grid(n_rows4, m->stride_words);
             hipLaunchKernelGGL(expand_fp4_kernel, grid, dim3(256), 0, ctx->stream, m->d,
                                m->stride_words, std::min<uint64_t>(m->n_rows_pad, n_rows4), n_rows4,
                                reinterpret_cast<uint4*>(ctx->d_x4.d), kExpandAll, 2u, pitch / 16);
         }
-        // rows [band_row0, band_end) are written; the columns run over the whole matrix
-        rc = run_matrix_tiles(ctx, plan, pitch, d_out, ld, (uint32_t)band_end, d_counts,
-                              op == STORM_HIP_OP_XOR ? 2u : 1u, 0u, 0u, (uint32_t)band_row0,
-                              (uint32_t)m->n_rows, sync, bits ? &ops : nullptr);
+        const TileOperands ops = bits ? operands_of(m->d, pitch, m->n_rows_pad) : operands_of(ctx->d_x4.d, pitch, n_rows4);
+        rc = k2h ? run_tile128(ctx, total_stages, ops, w, sync, 1u) : run_matrix_tiles(ctx, plan, ops, bits, w, sync);
     }
     if (rc == STORM_HIP_EHIP) set_error("pairw_matrix: HIP failure");
     return rc;
@@ -2355,15 +2307,7 @@ int launch_pairw_lag_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, i
     if (n < 2 || band_row0 >= band_end || max_lag == 0) return STORM_HIP_OK;
     const uint64_t L = std::min<uint64_t>(max_lag, n - 1);
     const uint64_t pitch = m->stride_words * 8;
-    if (pitch * 128u >= (1ull << 32)) {
-        set_error("pairw_lag_matrix: rows of %llu operand bytes exceed the tile kernel's 32-bit DMA offsets",
-                  (unsigned long long)pitch);
-        return STORM_HIP_EINVAL;
-    }
-    if ((n + kThTile - 1) / kThTile > 65535u) {
-        set_error("pairw_lag_matrix: too many row blocks");
-        return STORM_HIP_EINVAL;
-    }
+    if (int rc = check_tile_limits("pairw_lag_matrix", pitch, kThTile, (n + kThTile - 1) / kThTile, true)) return rc;
     // pairs (i, j) of the band within the lag: row i has min(L, n - 1 - i) of them
     auto pairs_below = [&](uint64_t r) {   // ... of the rows [0, r)
         const uint64_t full = std::min(r, n - L);            // rows with all L partners
@@ -2371,23 +2315,12 @@ int launch_pairw_lag_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, i
         return full * L + rest * L - rest * (rest + 1) / 2;
     };
     ctx->k2_tile_shape_eff = 6;
-    ctx->pass_report[0] = STORM_HIP_RAN_TILES_OUT;
-    ctx->pass_report[1] = (pairs_below(band_end) - pairs_below(band_row0)) * m->n_words;
-    ctx->pass_report[2] = ctx->pass_report[3] = 0;
+    report_tiles_out(ctx, (pairs_below(band_end) - pairs_below(band_row0)) * m->n_words);
     uint32_t* d_counts = nullptr;
-    int rc = STORM_HIP_OK;
-    if (op != STORM_HIP_OP_AND) {
-        rc = ensure_counts_scratch(ctx, n, &d_counts);
-        if (rc == STORM_HIP_OK) rc = launch_row_counts(ctx, m, d_counts);
-    }
-    if (rc == STORM_HIP_OK) {
-        const TileOperands ops = {reinterpret_cast<const uint8_t*>(m->d), nullptr, pitch, 0xffffffffu,
-                                  (uint32_t)std::min<uint64_t>(m->n_rows_pad, 0xffffffffu), 0u};
-        rc = run_tile128(ctx, (uint32_t)(band_row0 / kThTile), (uint32_t)((band_end + kThTile - 1) / kThTile), 0u,
-                         (uint32_t)((n + kThTile - 1) / kThTile), true, (m->n_words + 7u) / 8u * 4u, ops, d_out, ld,
-                         (uint32_t)band_end, d_counts, op == STORM_HIP_OP_XOR ? 2u : 1u, 0u, 0u, (uint32_t)band_row0, (uint32_t)n,
-                         sync, (uint32_t)L);
-    }
+    int rc = op_row_counts(ctx, op, m, &d_counts);
+    if (rc == STORM_HIP_OK)
+        rc = run_tile128(ctx, (m->n_words + 7u) / 8u * 4u, operands_of(m->d, pitch, m->n_rows_pad),
+                         lag_window(d_out, ld, band_row0, band_end, n, L, d_counts, op), sync, 1u);
     if (rc == STORM_HIP_EHIP) set_error("pairw_lag_matrix: HIP failure");
     return rc;
 }
@@ -2399,24 +2332,11 @@ int launch_pairw_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m
     const uint64_t n = m->n_rows;
     if (n < 2) return STORM_HIP_OK;
     const uint64_t pitch = m->stride_words * 8;
-    if (pitch * 128u >= (1ull << 32)) {
-        set_error("pairw_dosage_matrix: rows of %llu operand bytes exceed the tile kernel's 32-bit DMA offsets",
-                  (unsigned long long)pitch);
-        return STORM_HIP_EINVAL;
-    }
-    if ((n + kThTile - 1) / kThTile > 65535u) {
-        set_error("pairw_dosage_matrix: too many row blocks");
-        return STORM_HIP_EINVAL;
-    }
+    if (int rc = check_tile_limits("pairw_dosage_matrix", pitch, kThTile, (n + kThTile - 1) / kThTile, true)) return rc;
     ctx->k2_tile_shape_eff = 7;   // (option k2_tile_shape_used: 6 = K2h on bits, 7 = K2h on 2-bit values)
-    ctx->pass_report[0] = STORM_HIP_RAN_TILES_OUT;
-    ctx->pass_report[1] = n * (n - 1) / 2 * m->n_words;
-    ctx->pass_report[2] = ctx->pass_report[3] = 0;
-    const TileOperands ops = {reinterpret_cast<const uint8_t*>(m->d), nullptr, pitch, 0xffffffffu,
-                              (uint32_t)std::min<uint64_t>(m->n_rows_pad, 0xffffffffu), 0u};
-    const int rc = run_tile128(ctx, 0u, (uint32_t)((n + kThTile - 1) / kThTile), 0u, (uint32_t)((n + kThTile - 1) / kThTile), true,
-                               (m->n_words + 7u) / 8u * 4u, ops, d_out, ld, (uint32_t)n, nullptr, 1u, 0u, 0u, 0u, (uint32_t)n, sync,
-                               0u, 2u);
+    report_tiles_out(ctx, n * (n - 1) / 2 * m->n_words);
+    const int rc = run_tile128(ctx, (m->n_words + 7u) / 8u * 4u, operands_of(m->d, pitch, m->n_rows_pad),
+                               triangle_window(d_out, ld, 0, n, n, nullptr, STORM_HIP_OP_AND), sync, 2u);
     if (rc == STORM_HIP_EHIP) set_error("pairw_dosage_matrix: HIP failure");
     return rc;
 }
@@ -2432,33 +2352,20 @@ int launch_square_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* 
         return STORM_HIP_EINVAL;
     }
     const uint64_t pitch = a->stride_words * 8;
-    if (pitch * 128u >= (1ull << 32)) {
-        set_error("square_dosage_matrix: rows of %llu operand bytes exceed the tile kernel's 32-bit DMA offsets",
-                  (unsigned long long)pitch);
-        return STORM_HIP_EINVAL;
-    }
     const uint64_t rows_a = (a->n_rows + kTile - 1) / kTile * kTile;
-    if ((rows_a + b->n_rows + kThTile - 1) / kThTile > 65535u) {
-        set_error("square_dosage_matrix: too many row blocks");
-        return STORM_HIP_EINVAL;
-    }
+    if (int rc = check_tile_limits("square_dosage_matrix", pitch, kThTile, (rows_a + b->n_rows + kThTile - 1) / kThTile, true)) return rc;
     ctx->k2_tile_shape_eff = 7;
-    ctx->pass_report[0] = STORM_HIP_RAN_TILES_OUT;
-    ctx->pass_report[1] = a->n_rows * b->n_rows * a->n_words;
-    ctx->pass_report[2] = ctx->pass_report[3] = 0;
-    const TileOperands ops = {reinterpret_cast<const uint8_t*>(a->d), reinterpret_cast<const uint8_t*>(b->d), pitch,
-                              (uint32_t)rows_a, (uint32_t)std::min<uint64_t>(a->n_rows_pad, rows_a),
-                              (uint32_t)std::min<uint64_t>(b->n_rows_pad, (b->n_rows + kThTile - 1) / kThTile * kThTile)};
-    const int rc = run_tile128(ctx, 0u, (uint32_t)((a->n_rows + kThTile - 1) / kThTile), (uint32_t)(rows_a / kThTile),
-                               (uint32_t)((rows_a + b->n_rows + kThTile - 1) / kThTile), false, (a->n_words + 7u) / 8u * 4u, ops,
-                               d_out, ld, (uint32_t)a->n_rows, nullptr, 1u, (uint32_t)rows_a, (uint32_t)b->n_rows, 0u, 0u, sync,
-                               0u, 2u);
+    report_tiles_out(ctx, a->n_rows * b->n_rows * a->n_words);
+    const TileOperands ops = operands_of(a->d, b->d, pitch, rows_a, std::min<uint64_t>(a->n_rows_pad, rows_a),
+                                         std::min<uint64_t>(b->n_rows_pad, (b->n_rows + kThTile - 1) / kThTile * kThTile));
+    const int rc = run_tile128(ctx, (a->n_words + 7u) / 8u * 4u, ops,
+                               rectangle_window(d_out, ld, a->n_rows, rows_a, b->n_rows, nullptr, STORM_HIP_OP_AND), sync, 2u);
     if (rc == STORM_HIP_EHIP) set_error("square_dosage_matrix: HIP failure");
     return rc;
 }
 
 // Materialised rectangle: out[i * ld + j] = popcount(a_i OP b_j) for every row i of A and j of B
-// (device pointer, uint32, ld >= b->n_rows): the tile kernel over a shadow holding [A ; B].
+// (device pointer, uint32, ld >= b->n_rows): the tile kernel over the virtual rows [A ; B] (FP4 forms: a shadow holding them).
 int launch_square_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
                          const storm_hip_matrix_s* b, int op, uint32_t* d_out, uint64_t ld, bool sync) {
     if (a->n_rows == 0 || b->n_rows == 0) return STORM_HIP_OK;
@@ -2469,57 +2376,27 @@ int launch_square_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
     const uint64_t pitch = bits ? stride_words * 8 : shadow_pitch(ctx, row_bytes);
     const uint64_t rows_a = (a->n_rows + kTile - 1) / kTile * kTile;
     const uint64_t rows_b = (b->n_rows + kTile - 1) / kTile * kTile;
-    if ((rows_a + rows_b) / kTile >= 65535) {
-        set_error("square_matrix: too many row blocks");
-        return STORM_HIP_EINVAL;
-    }
-    if (pitch * (uint64_t)kTile >= (1ull << 32)) {
-        set_error("square_matrix: rows of %llu operand bytes exceed the tile kernel's 32-bit DMA offsets",
-                  (unsigned long long)pitch);
-        return STORM_HIP_EINVAL;
-    }
+    if (int rc = check_tile_limits("square_matrix", pitch, kTile, (rows_a + rows_b) / kTile + 1, false)) return rc;
     const size_t x4_bytes = bits ? 0 : (size_t)(rows_a + rows_b) * pitch;
     if (int rc = ensure_shadow(ctx, x4_bytes, "square_matrix: the FP4 shadow")) return rc;
     // (bit kernels: whole 512-bit chunks that hold DATA; the pitch's pad chunks are never multiplied)
     const uint32_t total_stages = bits ? (std::max(a->n_words, b->n_words) + 7u) / 8u * 4u : (uint32_t)(row_bytes / kStageBytes);
     const uint32_t ta = (uint32_t)(rows_a / kTile), tb = (uint32_t)(rows_b / kTile);
-    if (choose_tile128(ctx, (uint64_t)ta * tb, pitch, bits)) {   // [r6] few tiles: tile128_kernel
-        ctx->k2_tile_shape_eff = 6;
-        uint32_t* d_counts = nullptr;
-        int rc = STORM_HIP_OK;
-        if (op != STORM_HIP_OP_AND) {
-            rc = ensure_counts_scratch(ctx, rows_a + rows_b, &d_counts);
-            if (rc == STORM_HIP_OK) rc = launch_row_counts(ctx, a, d_counts);
-            if (rc == STORM_HIP_OK) rc = launch_row_counts(ctx, b, d_counts + rows_a);
-        }
-        if (rc == STORM_HIP_OK) {
-            const TileOperands ops = {reinterpret_cast<const uint8_t*>(a->d), reinterpret_cast<const uint8_t*>(b->d), pitch,
-                                      (uint32_t)rows_a, (uint32_t)std::min<uint64_t>(a->n_rows_pad, rows_a),
-                                      (uint32_t)std::min<uint64_t>(b->n_rows_pad, rows_b)};
-            rc = run_tile128(ctx, 0u, (uint32_t)((a->n_rows + kThTile - 1) / kThTile), (uint32_t)(rows_a / kThTile),
-                             (uint32_t)((rows_a + b->n_rows + kThTile - 1) / kThTile), false, total_stages, ops, d_out, ld,
-                             (uint32_t)a->n_rows, d_counts, op == STORM_HIP_OP_XOR ? 2u : 1u, (uint32_t)rows_a,
-                             (uint32_t)b->n_rows, 0u, 0u, sync);
-        }
-        if (rc == STORM_HIP_EHIP) set_error("square_matrix: HIP failure");
-        return rc;
-    }
-    MatrixTilesRequest rq;
-    rq.total_stages = total_stages;
-    xcd_grouped_tiles(0, ta, ta, ta + tb, false, rq.tiles);
-    uint32_t* d_counts = nullptr;  // per shadow row
+    const bool k2h = choose_tile128(ctx, (uint64_t)ta * tb, pitch, bits);   // [r6] few tiles: tile128_kernel
+    int rc = STORM_HIP_OK;
     MatrixPlan plan;
-    int rc = ensure_matrix_tiles(ctx, std::move(rq), &plan);
-    if (rc == STORM_HIP_OK && op != STORM_HIP_OP_AND) {
-        rc = ensure_counts_scratch(ctx, rows_a + rows_b, &d_counts);
-        if (rc == STORM_HIP_OK) rc = launch_row_counts(ctx, a, d_counts);
-        if (rc == STORM_HIP_OK) rc = launch_row_counts(ctx, b, d_counts + rows_a);
+    if (k2h) {
+        ctx->k2_tile_shape_eff = 6;
+    } else {
+        MatrixTilesRequest rq;
+        rq.total_stages = total_stages;
+        xcd_grouped_tiles(0, ta, ta, ta + tb, false, rq.tiles);
+        rc = ensure_matrix_tiles(ctx, std::move(rq), &plan);
     }
+    uint32_t* d_counts = nullptr;  // per virtual row
+    if (rc == STORM_HIP_OK) rc = op_row_counts(ctx, op, a, b, rows_a, rows_a + rows_b, &d_counts);
     if (rc == STORM_HIP_OK) {
-        const TileOperands ops = {reinterpret_cast<const uint8_t*>(a->d),
-                                  reinterpret_cast<const uint8_t*>(b->d), pitch, (uint32_t)rows_a,
-                                  (uint32_t)std::min<uint64_t>(a->n_rows_pad, rows_a),
-                                  (uint32_t)std::min<uint64_t>(b->n_rows_pad, rows_b)};
+        const OutWindow w = rectangle_window(d_out, ld, a->n_rows, rows_a, b->n_rows, d_counts, op);
         for (int side = 0; side < 2 && !bits; ++side) {
             const storm_hip_matrix_s* m = side ? b : a;
             const uint64_t rows_dst = side ? rows_b : rows_a;
@@ -2529,9 +2406,10 @@ int launch_square_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
                                reinterpret_cast<uint4*>(ctx->d_x4.d + (side ? rows_a * pitch : 0)),
                                kExpandAll, 2u, pitch / 16);
         }
-        rc = run_matrix_tiles(ctx, plan, pitch, d_out, ld, (uint32_t)a->n_rows, d_counts,
-                              op == STORM_HIP_OP_XOR ? 2u : 1u, (uint32_t)rows_a, (uint32_t)b->n_rows,
-                              0u, 0u, sync, bits ? &ops : nullptr);
+        const TileOperands ops = bits ? operands_of(a->d, b->d, pitch, rows_a, std::min<uint64_t>(a->n_rows_pad, rows_a),
+                                                    std::min<uint64_t>(b->n_rows_pad, rows_b))
+                                      : operands_of(ctx->d_x4.d, pitch, rows_a + rows_b);
+        rc = k2h ? run_tile128(ctx, total_stages, ops, w, sync, 1u) : run_matrix_tiles(ctx, plan, ops, bits, w, sync);
     }
     if (rc == STORM_HIP_EHIP) set_error("square_matrix: HIP failure");
     return rc;

@@ -32,8 +32,8 @@
 // reference (README.md:165-167: per-pair counts for LD); the loop it stands for is storm.c:1199-1238 with the leaf's
 // result kept per pair.
 //
-// Lag form (kLag, DESIGN.md §4 "lag layout"): the triangle's pairs with j - i <= L only (L travels in `j_count`, which the
-// triangle never uses), written as out[(i - i_lo) * ld + (j - i - 1)]: an n x L matrix instead of n x n. The host lists only
+// Lag form (kLag, DESIGN.md §4 "lag layout"; the window's form is OutForm::Lag): the triangle's pairs with j - i <= L =
+// w.lag only, written as out[(i - i_lo) * ld + (j - i - 1)]: an n x L matrix instead of n x n. The host lists only
 // the tiles that hold such a pair; a wave whose 64 x 64 block holds none takes the "nothing to multiply" dispatch, and the
 // epilogue is the per-element one (a row's columns shift by one word per row: no 16-byte row runs to store).
 constexpr int kThThreads = 256;
@@ -58,9 +58,8 @@ __device__ __forceinline__ v4i th_inflate2(v4i w) {
 
 template <bool kLag, int kBits = 1>
 __global__ __launch_bounds__(kThThreads, 2) void tile128_kernel(
-    TileOperands ops, const PartItem* __restrict__ items, uint32_t* __restrict__ out, uint64_t ld,
-    uint32_t n_rows, const uint32_t* __restrict__ row_counts, uint32_t and_weight, uint32_t j_base,
-    uint32_t j_count, uint32_t i_lo, uint32_t n_cols, uint32_t* __restrict__ parts, uint32_t* __restrict__ tickets) {
+    TileOperands ops, const PartItem* __restrict__ items, OutWindow window, uint32_t* __restrict__ parts, uint32_t* __restrict__ tickets) {
+    const OutWindow w = window.loaded();
     __shared__ __attribute__((aligned(1024))) uint8_t lds[kThRing * kThSlotBytes];
     __shared__ uint32_t ticket_seen;
     static_assert(kBits == 1 || (kBits == 2 && !kLag), "bits, or 2-bit values in the triangle form");
@@ -76,20 +75,11 @@ __global__ __launch_bounds__(kThThreads, 2) void tile128_kernel(
     const uint32_t nC = it.n_stages / 4u;                      // chunks of 64 B (512 bits of k)
     const uint32_t kbyte0 = it.stage0 * 16u;
     const uint32_t pitch = (uint32_t)ops.pitch;
-    const bool rect = !kLag && j_count != 0;
 
-    auto window = [&](uint32_t v0, const uint8_t*& base, uint32_t& bytes) {
-        const bool second = v0 >= ops.split;
-        const uint32_t r0 = second ? v0 - ops.split : v0;
-        const uint32_t have = second ? ops.rows_b : ops.rows_a;
-        const uint32_t rows = have > r0 ? min(have - r0, kThTile) : 0u;
-        base = (second ? ops.xb : ops.xa) + (uint64_t)r0 * ops.pitch;
-        bytes = rows * pitch;
-    };
     const uint8_t *a_base, *b_base;
     uint32_t a_bytes, b_bytes;
-    window(a_row0, a_base, a_bytes);
-    window(b_row0, b_base, b_bytes);
+    ops.tile_rows(a_row0, kThTile, a_base, a_bytes);
+    ops.tile_rows(b_row0, kThTile, b_base, b_bytes);
 
     // DMA: piece g of an operand = rows 16 g .. 16 g + 15; wave w moves pieces w and w + 4 of A and of B. Lane l: row l / 4
     // of the piece, quarter (l % 4) ^ swizzle of that row ((row / 4) % 4 = (l / 16) % 4 whatever the piece).
@@ -119,9 +109,9 @@ __global__ __launch_bounds__(kThThreads, 2) void tile128_kernel(
     const uint32_t fb0 = lds_base + kThTile * 64u + (64u * wb + frow) * 64u + fq * 16u, fb1 = fb0 ^ 32u;
 
     // block offset of the wave's B rows from its A rows: block (m, n) holds a pair i < j iff n + d >= m
-    int32_t d = rect ? 64 : (int32_t)((b_row0 + 64u * wb) / 32u) - (int32_t)((a_row0 + 64u * wa) / 32u);
+    int32_t d = w.rect() ? 64 : (int32_t)((b_row0 + 64u * wb) / 32u) - (int32_t)((a_row0 + 64u * wa) / 32u);
     if constexpr (kLag)   // the block's nearest pair (i0 + 63, j0) is already beyond the lag: every part of the tile agrees
-        if (b_row0 + 64u * wb > a_row0 + 64u * wa + 63u + j_count) d = -1;
+        if (b_row0 + 64u * wb > a_row0 + 64u * wa + 63u + w.lag) d = -1;
 
     auto run = [&](auto dc) __attribute__((always_inline)) {
         constexpr int D = decltype(dc)::value;          // 64: every block; 0: the block below the diagonal drops out; -1: nothing
@@ -345,13 +335,12 @@ __global__ __launch_bounds__(kThThreads, 2) void tile128_kernel(
             // column per lane, so storing them directly is one 4-byte store per element with a 64-bit address and a predicate
             // each (5 us of a 29 us item at 1024 rows). 32 rows at a time go through 8.5 KiB of the idle ring (row pitch 68
             // words: conflict-free 4-byte stores) and leave as 16 bytes per lane, four 256-byte runs per instruction.
-            const bool inside = i0 >= i_lo && i0 + 64u <= n_rows &&
-                                (rect ? (j0 >= j_base && j0 - j_base + 64u <= j_count) : (j0 + 64u <= n_cols && i0 + 64u <= j0)) &&
-                                (ld & 3u) == 0 && ((uintptr_t)out & 15u) == 0 && (j_base & 3u) == 0;
             if constexpr (D > 0 && !kLag) {
-                if (inside) {
+                if (w.covers(i0, 64u, j0, 64u) && (w.ld & 3u) == 0 && ((uintptr_t)w.out & 15u) == 0 && (w.j_base & 3u) == 0) {
                     uint32_t* w32 = reinterpret_cast<uint32_t*>(lds + wave * (32u * 68u * 4u));
-                    uint32_t* out_tile = &out[(uint64_t)(i0 - i_lo) * ld + (j0 - j_base)];
+                    uint32_t* out_tile = w.at(i0, j0);
+                    const OutWindow::counts_ptr_t row_counts = w.counts();
+                    const uint64_t ld = w.ld;
                     uint32_t nj[2] = {0u, 0u};
                     if (row_counts) {
                         nj[0] = row_counts[j0 + col];
@@ -366,7 +355,7 @@ __global__ __launch_bounds__(kThThreads, 2) void tile128_kernel(
 #pragma unroll
                             for (int n = 0; n < 2; ++n)
                                 w32[il * 68u + 32u * (uint32_t)n + col] =
-                                    row_counts ? ni + nj[n] - and_weight * cnt[m][n][r] : cnt[m][n][r];
+                                    row_counts ? ni + nj[n] - w.and_weight * cnt[m][n][r] : cnt[m][n][r];
                         }
 #pragma unroll
                         for (int q = 0; q < 8; ++q) {
@@ -381,22 +370,16 @@ __global__ __launch_bounds__(kThThreads, 2) void tile128_kernel(
 #pragma unroll
             for (int n = 0; n < 2; ++n) {
                 const uint32_t jj = j0 + 32u * (uint32_t)n + col;
-                const bool j_ok = rect ? (jj >= j_base && jj - j_base < j_count) : jj < n_cols;   // (lag form: rect is false)
-                const uint32_t nj = (row_counts && j_ok) ? row_counts[jj] : 0u;
+                const bool j_ok = w.wants_col(jj);
+                const uint32_t nj = w.nj(jj);
 #pragma unroll
                 for (int m = 0; m < 2; ++m) {
                     if (!needed(m, n)) continue;
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const uint32_t ii = i0 + 32u * (uint32_t)m + (uint32_t)((r & 3) + 8 * (r >> 2)) + 4u * (lane >> 5);
-                        if constexpr (kLag) {
-                            // (a register's 32 lanes of one half-wave: one row, 32 consecutive columns = one 128-byte run)
-                            if (j_ok && ii >= i_lo && ii < n_rows && ii < jj && jj - ii <= j_count)
-                                out[(uint64_t)(ii - i_lo) * ld + (jj - ii - 1u)] =
-                                    row_counts ? row_counts[ii] + nj - and_weight * cnt[m][n][r] : cnt[m][n][r];
-                        } else if (j_ok && ii >= i_lo && ii < n_rows && (rect || ii < jj))
-                            out[(uint64_t)(ii - i_lo) * ld + (jj - j_base)] =
-                                row_counts ? row_counts[ii] + nj - and_weight * cnt[m][n][r] : cnt[m][n][r];
+                        // (lag form: a register's 32 lanes of one half-wave are one row, 32 consecutive columns = one 128-byte run)
+                        if (j_ok && w.writes_row<kLag>(ii, jj)) *w.at<kLag>(ii, jj) = w.value(cnt[m][n][r], ii, nj);
                     }
                 }
             }

@@ -2,9 +2,8 @@
 // (STORM_TI_SHAPE 16 -> tile16_bits_kernel on v_mfma_f32_16x16x128_f8f6f4, 32 -> tile32_bits_kernel on
 // v_mfma_f32_32x32x64_f8f6f4 — the unscaled forms: the operand codes are reciprocal per class, ti_infl1 / ti_inflb; STORM_TI_NAME = the kernel's name). Design notes: storm_hip_mfma.hip, "K2tb".
 __global__ __launch_bounds__(kTiThreads, 2) void STORM_TI_NAME(
-    TileOperands ops, const MfmaItem* __restrict__ items, uint32_t n_items, uint32_t* __restrict__ out, uint64_t ld,
-    uint32_t n_rows, const uint32_t* __restrict__ row_counts, uint32_t and_weight, uint32_t j_base,
-    uint32_t j_count, uint32_t split_from, uint32_t i_lo, uint32_t n_cols) {
+    TileOperands ops, const MfmaItem* __restrict__ items, uint32_t n_items, OutWindow window, uint32_t split_from) {
+    const OutWindow w = window.loaded();
     extern __shared__ __attribute__((aligned(1024))) uint8_t ti_lds[];
 
     // blocks 16 g .. 16 g + 7 are the first halves of items 8 g .. 8 g + 7, the next eight their second halves:
@@ -20,22 +19,13 @@ __global__ __launch_bounds__(kTiThreads, 2) void STORM_TI_NAME(
     const uint32_t C = it.n_stages / 4u;          // chunks of 64 B
     const uint32_t kbyte0 = it.stage0 * 16u;
     const uint32_t pitch = (uint32_t)ops.pitch;
-    const bool rect = j_count != 0;
-    const uint32_t col_limit = rect ? j_base + j_count : n_cols;
+    const uint32_t col_limit = w.col_end();
     if (b_row0 >= col_limit) return;   // the whole half lies beyond the output (ragged last tile column)
 
-    auto window = [&](uint32_t v0, uint32_t want, const uint8_t*& base, uint32_t& bytes) {
-        const bool second = v0 >= ops.split;
-        const uint32_t r0 = second ? v0 - ops.split : v0;
-        const uint32_t have = second ? ops.rows_b : ops.rows_a;
-        const uint32_t rows = have > r0 ? min(have - r0, want) : 0u;
-        base = (second ? ops.xb : ops.xa) + (uint64_t)r0 * ops.pitch;
-        bytes = rows * pitch;
-    };
     const uint8_t *a_base, *b_base;
     uint32_t a_bytes, b_bytes;
-    window(a_row0, (uint32_t)kTile, a_base, a_bytes);
-    window(b_row0, 128u, b_base, b_bytes);
+    ops.tile_rows(a_row0, (uint32_t)kTile, a_base, a_bytes);
+    ops.tile_rows(b_row0, 128u, b_base, b_bytes);
 
     const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)&ti_lds[0];
     // B pieces of this wave: pieces 2 w and 2 w + 1 of the half's 8 (16 rows x 64 B each); lanes 4 g .. 4 g + 3 hold
@@ -101,9 +91,8 @@ __global__ __launch_bounds__(kTiThreads, 2) void STORM_TI_NAME(
     };
 
     const bool interior =
-        item_idx < split_from && a_row0 >= i_lo && a_row0 + kTile <= n_rows &&
-        (rect ? (b_row0 >= j_base && b_row0 - j_base + 128u <= j_count) : (b_row0 + 128u <= n_cols && a_row0 != (uint32_t)it.J * kTile)) &&
-        (ld & 3u) == 0 && ((uintptr_t)out & 15u) == 0 && ((j_base & 3u) == 0);
+        item_idx < split_from && w.covers(a_row0, (uint32_t)kTile, b_row0, 128u) &&
+        (w.ld & 3u) == 0 && ((uintptr_t)w.out & 15u) == 0 && ((w.j_base & 3u) == 0);
     (void)interior;
     auto run = [&](auto nlo_c, auto nhi_c) __attribute__((always_inline)) {
     // this wave multiplies the 32-row B blocks [NLO, NHI) of its half only (diagonal tiles: the blocks wholly below
@@ -244,20 +233,17 @@ __global__ __launch_bounds__(kTiThreads, 2) void STORM_TI_NAME(
 #pragma unroll
     for (int n = 2 * NLO; n < 2 * NHI; ++n) {
         const uint32_t j = b_row0 + 16u * (uint32_t)n + (lane & 15u);
-        const bool j_ok = rect ? (j >= j_base && j - j_base < j_count) : j < n_cols;
-        const uint32_t nj = (row_counts && j_ok) ? row_counts[j] : 0u;
+        const bool j_ok = w.wants_col(j);
+        const uint32_t nj = w.nj(j);
 #pragma unroll
         for (int m = 0; m < 4; ++m)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const uint32_t i = a_row0 + wave * 64u + 16u * (uint32_t)m + 4u * (lane >> 4) + (uint32_t)r;
-                if (j_ok && i >= i_lo && i < n_rows && (rect || i < j)) {
-                    const uint32_t cnt = (uint32_t)acc[m][n][r];
-                    uint32_t* dst = &out[(uint64_t)(i - i_lo) * ld + (j - j_base)];
-                    const uint32_t ni = row_counts ? row_counts[i] : 0u;
-                    const uint32_t val = row_counts ? ((whole || it.stage0 == 0) ? ni + nj : 0u) - and_weight * cnt : cnt;
-                    if (whole) *dst = val;
-                    else atomicAdd(dst, val);
+                if (j_ok && w.writes_row(i, j)) {
+                    const uint32_t val = w.part_value((uint32_t)acc[m][n][r], i, nj, whole || it.stage0 == 0);
+                    if (whole) *w.at(i, j) = val;
+                    else atomicAdd(w.at(i, j), val);
                 }
             }
     }
@@ -271,7 +257,7 @@ __global__ __launch_bounds__(kTiThreads, 2) void STORM_TI_NAME(
             for (int n = 0; n < 4; ++n)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) sum_ += acc[m][n][r];
-        if (sum_ == -1.0f) out[0] = 1u;
+        if (sum_ == -1.0f) w.out[0] = 1u;
         return;
     }
 #endif
@@ -287,7 +273,9 @@ __global__ __launch_bounds__(kTiThreads, 2) void STORM_TI_NAME(
             uint32_t* w32 = reinterpret_cast<uint32_t*>(ti_lds + wave * 16384u);
             const uint4* r128 = reinterpret_cast<const uint4*>(ti_lds + wave * 16384u);
             const uint32_t i0 = a_row0 + wave * 64u;
-            uint32_t* out_tile = &out[(uint64_t)(i0 - i_lo) * ld + (b_row0 - j_base)];
+            uint32_t* out_tile = w.at(i0, b_row0);
+            const OutWindow::counts_ptr_t row_counts = w.counts();
+            const uint64_t ld = w.ld;
             uint32_t njv[4] = {0u, 0u, 0u, 0u};
             if (row_counts) {
 #pragma unroll
@@ -302,7 +290,7 @@ __global__ __launch_bounds__(kTiThreads, 2) void STORM_TI_NAME(
 #pragma unroll
                     for (int n = 0; n < 4; ++n) {
                         const uint32_t cnt = (uint32_t)acc[m][n][r];
-                        w32[il * 128u + (uint32_t)n * 32u + (lane & 31u)] = row_counts ? ni + njv[n] - and_weight * cnt : cnt;
+                        w32[il * 128u + (uint32_t)n * 32u + (lane & 31u)] = row_counts ? ni + njv[n] - w.and_weight * cnt : cnt;
                     }
                 }
 #pragma unroll
@@ -318,20 +306,17 @@ __global__ __launch_bounds__(kTiThreads, 2) void STORM_TI_NAME(
 #pragma unroll
     for (int n = NLO; n < NHI; ++n) {
         const uint32_t j = b_row0 + 32u * (uint32_t)n + (lane & 31u);
-        const bool j_ok = rect ? (j >= j_base && j - j_base < j_count) : j < n_cols;
-        const uint32_t nj = (row_counts && j_ok) ? row_counts[j] : 0u;
+        const bool j_ok = w.wants_col(j);
+        const uint32_t nj = w.nj(j);
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const uint32_t i = a_row0 + wave * 64u + 32u * (uint32_t)m + (uint32_t)((r & 3) + 8 * (r >> 2)) + 4u * (lane >> 5);
-                if (j_ok && i >= i_lo && i < n_rows && (rect || i < j)) {
-                    const uint32_t cnt = (uint32_t)acc[m][n][r];
-                    uint32_t* dst = &out[(uint64_t)(i - i_lo) * ld + (j - j_base)];
-                    const uint32_t ni = row_counts ? row_counts[i] : 0u;
-                    const uint32_t val = row_counts ? ((whole || it.stage0 == 0) ? ni + nj : 0u) - and_weight * cnt : cnt;
-                    if (whole) *dst = val;
-                    else atomicAdd(dst, val);
+                if (j_ok && w.writes_row(i, j)) {
+                    const uint32_t val = w.part_value((uint32_t)acc[m][n][r], i, nj, whole || it.stage0 == 0);
+                    if (whole) *w.at(i, j) = val;
+                    else atomicAdd(w.at(i, j), val);
                 }
             }
     }
@@ -340,7 +325,7 @@ __global__ __launch_bounds__(kTiThreads, 2) void STORM_TI_NAME(
 
     // blocks of 32 B rows this wave needs: [n_lo, n_hi) (any superset is correct: the epilogue masks)
     const uint32_t n_hi = min(4u, (col_limit - b_row0 + 31u) / 32u);
-    const uint32_t below = (!rect && a_row0 == (uint32_t)it.J * kTile && wave * 64u > 128u * half) ? (wave * 64u - 128u * half) / 32u : 0u;
+    const uint32_t below = (!w.rect() && a_row0 == (uint32_t)it.J * kTile && wave * 64u > 128u * half) ? (wave * 64u - 128u * half) / 32u : 0u;
     const uint32_t n_lo = min(below, 4u);
     using std::integral_constant;
     if (n_lo >= n_hi) run(integral_constant<int, 4>{}, integral_constant<int, 4>{});

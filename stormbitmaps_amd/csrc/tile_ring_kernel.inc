@@ -127,9 +127,7 @@ struct tr_waits {
 //               wave spins only when it is more than half a stage ahead of the slowest; waves may drift a stage apart.
 template <bool kFlags>
 __global__ __launch_bounds__(kTrThreads, 2) void tilering_kernel(
-    TileOperands ops, const MfmaItem* __restrict__ items, uint32_t* __restrict__ out, uint64_t ld,
-    uint32_t n_rows, const uint32_t* __restrict__ row_counts, uint32_t and_weight, uint32_t j_base,
-    uint32_t j_count, uint32_t split_from, uint32_t i_lo, uint32_t n_cols, uint32_t* __restrict__ parts) {
+    TileOperands ops, const MfmaItem* __restrict__ items, OutWindow window, uint32_t split_from, uint32_t* __restrict__ parts) {
     __shared__ __attribute__((aligned(1024))) uint8_t lds[kTrLdsBytes + 64u];   // + the four arrival counters
     STORM_CLOCK_BEGIN();
 
@@ -145,28 +143,19 @@ __global__ __launch_bounds__(kTrThreads, 2) void tilering_kernel(
     const uint32_t S = it.n_stages / 4u;          // chunks of 64 B (512 bits of k)
     const uint32_t kbyte0 = it.stage0 * 16u;
     const uint32_t pitch = (uint32_t)ops.pitch;
-    const bool rect = j_count != 0;
 
-    auto window = [&](uint32_t v0, const uint8_t*& base, uint32_t& bytes) {
-        const bool second = v0 >= ops.split;
-        const uint32_t r0 = second ? v0 - ops.split : v0;
-        const uint32_t have = second ? ops.rows_b : ops.rows_a;
-        const uint32_t rows = have > r0 ? min(have - r0, (uint32_t)kTile) : 0u;
-        base = (second ? ops.xb : ops.xa) + (uint64_t)r0 * ops.pitch;
-        bytes = rows * pitch;
-    };
     const uint8_t *a_base, *b_base;
     uint32_t a_bytes, b_bytes;
-    window(a_row0, a_base, a_bytes);
-    window(b_row0, b_base, b_bytes);
+    ops.tile_rows(a_row0, (uint32_t)kTile, a_base, a_bytes);
+    ops.tile_rows(b_row0, (uint32_t)kTile, b_base, b_bytes);
 
     // blocks this wave multiplies: rows [0, mh) x columns [0, nh) of its 8 x 4
-    const uint32_t col_limit = rect ? j_base + j_count : n_cols;
+    const uint32_t col_limit = window.col_end();
     const uint32_t vc = col_limit > b_row0 ? min(col_limit - b_row0, (uint32_t)kTile) : 0u;
-    const uint32_t va = n_rows > a_row0 ? min(n_rows - a_row0, (uint32_t)kTile) : 0u;
+    const uint32_t va = window.n_rows > a_row0 ? min(window.n_rows - a_row0, (uint32_t)kTile) : 0u;
     const uint32_t nh = vc > 64u * wb ? min((vc - 64u * wb + 15u) / 16u, 4u) : 0u;
     uint32_t mh = va > 128u * wa ? min((va - 128u * wa + 15u) / 16u, 8u) : 0u;
-    const bool diag = !rect && a_row0 == b_row0;
+    const bool diag = !window.rect() && a_row0 == b_row0;
     if (diag) {   // rows at or beyond the wave's last column meet no column behind them
         const uint32_t jmax = 64u * wb + 16u * nh;
         mh = jmax > 128u * wa ? min(mh, (jmax - 128u * wa + 15u) / 16u) : 0u;
@@ -204,10 +193,9 @@ __global__ __launch_bounds__(kTrThreads, 2) void tilering_kernel(
     // [r5] a k-part writes its counts into its own 256 x 256 window of `parts` (plain stores; reduce_parts_kernel adds a tile's
     // windows up): see tilebits8_kernel. parts == nullptr: the parts add into the cleared output with atomics.
     uint32_t* part_tile = (item_idx >= split_from && parts) ? parts + (uint64_t)(item_idx - split_from) * (kTile * kTile) : nullptr;
-    const bool full_tile = a_row0 >= i_lo && a_row0 + kTile <= n_rows &&
-        (rect ? (b_row0 >= j_base && b_row0 - j_base + kTile <= j_count) : (b_row0 + kTile <= n_cols && a_row0 != b_row0));
+    const bool full_tile = window.covers(a_row0, (uint32_t)kTile, b_row0, (uint32_t)kTile);
     const bool interior = full_tile && (part_tile ? true
-                                                  : (item_idx < split_from && (ld & 3u) == 0 && ((uintptr_t)out & 15u) == 0 && (j_base & 3u) == 0));
+                                                  : (item_idx < split_from && (window.ld & 3u) == 0 && ((uintptr_t)window.out & 15u) == 0 && (window.j_base & 3u) == 0));
 
     auto run = [&](auto mhc, auto nhc, auto latec) __attribute__((always_inline)) {
         constexpr int MH = decltype(mhc)::value, NH = decltype(nhc)::value;   // MH = 0: nothing to multiply
@@ -427,6 +415,9 @@ __global__ __launch_bounds__(kTrThreads, 2) void tilering_kernel(
         if constexpr (MH == 0) return;
 
         // ---- epilogue. C/D map of a 16 x 16 block: col = lane & 15, row = 4 (lane >> 4) + reg.
+        // (the window's fields are read here, behind the k-loop, and once: the kernel holds 256 VGPRs, and SGPRs kept live across
+        //  the loop end up in spilled lanes; read where the members use them they would be fetched again behind every branch)
+        const OutWindow w = window.loaded();
         const uint32_t le = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
         const uint32_t i0 = a_row0 + wa * 128u, j0 = b_row0 + wb * 64u;
         if constexpr (MH == 8 && NH == 4) {
@@ -436,10 +427,9 @@ __global__ __launch_bounds__(kTrThreads, 2) void tilering_kernel(
                 // and stores 16 bytes per lane: four 256-byte runs per instruction.
                 __builtin_amdgcn_s_barrier();   // every wave has left the ring
                 uint32_t* w32 = reinterpret_cast<uint32_t*>(&lds[0] + wave * 16384u);
-                const uint32_t* rcs = part_tile ? nullptr : row_counts;   // (a part holds raw AND counts)
-                const uint64_t ldx = part_tile ? (uint64_t)kTile : ld;
-                uint32_t* out_tile = part_tile ? &part_tile[(i0 - a_row0) * (uint32_t)kTile + (j0 - b_row0)]
-                                               : &out[(uint64_t)(i0 - i_lo) * ld + (j0 - j_base)];
+                const OutWindow::counts_ptr_t rcs = part_tile ? nullptr : w.counts();   // (a part holds raw AND counts)
+                const uint64_t ldx = part_tile ? (uint64_t)kTile : w.ld;
+                uint32_t* out_tile = part_tile ? &part_tile[(i0 - a_row0) * (uint32_t)kTile + (j0 - b_row0)] : w.at(i0, j0);
                 uint32_t nj[4] = {0u, 0u, 0u, 0u};
                 if (rcs) {
 #pragma unroll
@@ -456,7 +446,7 @@ __global__ __launch_bounds__(kTrThreads, 2) void tilering_kernel(
 #pragma unroll
                             for (int n = 0; n < 4; ++n) {
                                 const uint32_t c = (uint32_t)acc[2 * mp + mm][n][r];
-                                w32[il * 68u + (uint32_t)n * 16u + (le & 15u)] = rcs ? ni + nj[n] - and_weight * c : c;
+                                w32[il * 68u + (uint32_t)n * 16u + (le & 15u)] = rcs ? ni + nj[n] - w.and_weight * c : c;
                             }
                         }
 #pragma unroll
@@ -472,23 +462,22 @@ __global__ __launch_bounds__(kTrThreads, 2) void tilering_kernel(
 #pragma unroll
         for (int n = 0; n < NH; ++n) {
             const uint32_t j = j0 + (uint32_t)n * 16u + (le & 15u);
-            const bool j_ok = rect ? (j >= j_base && j - j_base < j_count) : j < n_cols;
-            const uint32_t njv = (row_counts && j_ok) ? row_counts[j] : 0u;
+            const bool j_ok = w.wants_col(j);
+            const uint32_t njv = w.nj(j);
 #pragma unroll
             for (int m = 0; m < MH; ++m)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const uint32_t i = i0 + (uint32_t)m * 16u + 4u * (le >> 4) + (uint32_t)r;
-                    if (j_ok && i >= i_lo && i < n_rows && (rect || i < j)) {
+                    if (j_ok && w.writes_row(i, j)) {
                         const uint32_t c = (uint32_t)acc[m][n][r];
-                        uint32_t* dst = &out[(uint64_t)(i - i_lo) * ld + (j - j_base)];
+                        uint32_t* dst = w.at(i, j);
                         if (item_idx < split_from) {
-                            *dst = row_counts ? row_counts[i] + njv - and_weight * c : c;
+                            *dst = w.value(c, i, njv);
                         } else if (part_tile) {
                             part_tile[(i - a_row0) * (uint32_t)kTile + (j - b_row0)] = c;
                         } else {
-                            const uint32_t once = (row_counts && it.stage0 == 0) ? row_counts[i] + njv : 0u;
-                            atomicAdd(dst, row_counts ? once - and_weight * c : c);
+                            atomicAdd(dst, w.part_value(c, i, njv, it.stage0 == 0));
                         }
                     }
                 }

@@ -621,23 +621,42 @@ def _run_into(torch, fn, rows, ld, offset_words, want_of):
         raise AssertionError((_first_diffs(body, g), "words touched outside the buffer:", outside[:4].tolist()))
 
 
-@pytest.mark.parametrize("tile_shape", (5, 6, 2))
-def test_device_outputs_touch_only_what_the_header_says(ctx, tile_shape):
+# (k2_tile_shape, further options, the whole loop or the reduced one). Every kernel that writes a caller's window stands here:
+# 5 tilering_kernel<false> (and <true> under k2_ring_sync), 6 tile128_kernel, 2 tilebits8_kernel, 3 / 4 tile16_bits_kernel /
+# tile32_bits_kernel, 32 expand_fp4_kernel + pairw_fp4_kernel<0, true>. The rows are 20 stages of 128 bits, so the tiles are
+# cut along k only under k2_matrix_min_part = 4 (default 32): then the parts add into the window zero_tiles_kernel cleared
+# or, with k2_matrix_parts = 1, write windows of their own that reduce_parts_kernel adds up.
+_PLACEMENT_CASES = [
+    pytest.param(5, {}, True, id="5"), pytest.param(6, {}, True, id="6"), pytest.param(2, {}, True, id="2"),
+    pytest.param(3, {}, False, id="3"), pytest.param(4, {}, False, id="4"), pytest.param(32, {}, False, id="32"),
+    pytest.param(5, {"k2_ring_sync": 1}, False, id="5-ring_sync"),
+    pytest.param(2, {"k2_matrix_parts": 1, "k2_matrix_min_part": 4}, False, id="2-matrix_parts"),
+    pytest.param(5, {"k2_matrix_parts": 1, "k2_matrix_min_part": 4}, False, id="5-matrix_parts"),
+    pytest.param(5, {"k2_matrix_min_part": 4}, False, id="5-cleared_window"),
+]
+
+
+@pytest.mark.parametrize("tile_shape,options,whole", _PLACEMENT_CASES)
+def test_device_outputs_touch_only_what_the_header_says(ctx, tile_shape, options, whole):
     """storm_hip_pairw_matrix_device, _band_device and storm_hip_square_matrix_device write out[i * ld + j] for i < j (every
     i, j of a rectangle) and leave everything else untouched: entries on and below the diagonal, the columns from n_rows (B's
     rows) up to ld. Outputs pre-filled with a sentinel, ld = 0, 1, 3 (mod 4), a 16-byte aligned address and one 4 bytes
     further (tile128_kernel's 16-byte row stores have a scalar fall-back selected by exactly these), bands from row 0, 1,
     63, 64, 127, 129, a band of 0 rows, a band that ends at the last row, rectangles whose B has 1, 63, 257 rows. Staircase
-    rows: a misplaced row or column shows as a wrong VALUE, not only as a touched sentinel."""
+    rows: a misplaced row or column shows as a wrong VALUE, not only as a touched sentinel. The cases beyond the three default
+    forms run the reduced loop: both ops, ld = 0 and 3 (mod 4), both addresses, the first three bands, the rectangles of 200
+    rows against 63 and 257."""
     import torch
+    if tile_shape not in shipped(ctx, "k2_tile_shape", (tile_shape,)):
+        pytest.skip("this build of the library does not carry the form")
     M, N, pre, suf = _placement_inputs()
     mat = de.staircase(M, pre, suf)
     n_i, _, cnt = de.staircase_counts(M, pre, suf)
     m = ctx.matrix_from_host(mat)
-    _set(ctx, k2_tile_shape=tile_shape)
+    _set(ctx, k2_tile_shape=tile_shape, **options)
     for op in ("and", "xor"):
         full = de.op_counts(n_i, n_i, cnt, op)
-        for ld in (N, N + 1, N + 3, N + 8):
+        for ld in ((N, N + 1, N + 3, N + 8) if whole else (N, N + 3)):
             for offset in (0, 1):
                 what = (tile_shape, op, ld, offset)
 
@@ -649,19 +668,19 @@ def test_device_outputs_touch_only_what_the_header_says(ctx, tile_shape):
                     _run_into(torch, lambda p: m.pairw_matrix_device(p, ld, op), N, ld, offset, triangle)
                     assert ctx.get_option("k2_tile_shape_used") == tile_shape
                     bands = [(0, 100), (1, 64), (63, 66), (64, 64), (127, 130), (129, 40), (50, 0), (N - 37, 37), (0, N)]
-                    for row0, rows in (bands if (op, offset) != ("xor", 1) else bands[:3]):
+                    for row0, rows in (bands if whole and (op, offset) != ("xor", 1) else bands[:3]):
                         what = (tile_shape, op, ld, offset, "band", row0, rows)
                         _run_into(torch, lambda p: m.pairw_matrix_band_device(p, ld, row0, rows, op), max(rows, 1), ld, offset,
                                   lambda body: triangle(body, row0, rows))
                 except AssertionError as e:
                     raise AssertionError((what,) + e.args) from None
-    for nb in (1, 63, 257):
+    for nb in ((1, 63, 257) if whole else (63, 257)):
         b = ctx.matrix_from_host(mat[N - nb:])
-        for na in (1, 200):
+        for na in ((1, 200) if whole else (200,)):
             a = ctx.matrix_from_host(mat[:na])
             for op in ("and", "or"):
                 full = de.op_counts(n_i[:na], n_i[N - nb:], cnt[:na, N - nb:], op)
-                for ld in (nb, nb + 1, nb + 3, (nb + 3) // 4 * 4 + 4):
+                for ld in ((nb, nb + 1, nb + 3, (nb + 3) // 4 * 4 + 4) if whole else (nb, nb + 3)):
                     for offset in (0, 1):
                         def rectangle(body):
                             body[:, :nb] = full

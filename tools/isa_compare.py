@@ -2,16 +2,19 @@
 """Are two builds' device code the same, kernel by kernel?
 
     hipcc <the Makefile's HIPFLAGS> [-DSTORM_HIP_PROBES] --cuda-device-only -S -c X.hip -o DIR/X.s   (for both trees)
-    tools/isa_compare.py BEFORE_DIR AFTER_DIR [more pairs ...]
+    tools/isa_compare.py [--by-name] BEFORE_DIR AFTER_DIR [more pairs ...]
 
 For every .s file of BEFORE_DIR: the set of kernel names, and per kernel its instruction text with the .amdhsa_kernel
 descriptor that follows it, and its metadata entry (.vgpr_count, .sgpr_count, .group_segment_fixed_size, ...), compared by kernel name so
 that the order of definitions does not matter (function-local label numbers are dropped with it). Lines that name files
 (.file, .ident, paths) are dropped. Prints one line per file and every difference; exit status 1 if there is one.
+--by-name: kernels are paired by their demangled name up to the parameter list (c++filt), for a change of signatures; the
+mangled name reads as that name in both texts.
 """
 import difflib
 import os
 import re
+import subprocess
 import sys
 
 LOCAL_LABEL = re.compile(r"\.L(BB|func_end|func_begin|tmp|JTI)\d+(_\d+)?")
@@ -58,15 +61,35 @@ def kernels_of(path):
     return found
 
 
+def by_name(found):
+    """The same kernels under 'ns::kernel<args>': the demangled name without 'void ' and the parameter list."""
+    out = {}
+    names = list(found)
+    dems = subprocess.run(["c++filt"] + names, capture_output=True, text=True, check=True).stdout.split("\n") if names else []
+    for name, dem in zip(names, dems):
+        k = found[name]
+        dem = dem[5:] if dem.startswith("void ") else dem
+        depth, base = 0, dem
+        for i, ch in enumerate(dem):
+            depth += (ch == "<") - (ch == ">")
+            if ch == "(" and depth == 0:
+                base = dem[:i]
+                break
+        out[base] = {part: [ln.replace(name, base) for ln in lines] for part, lines in k.items()}
+    return out
+
+
 def _file_entry(found, entry):
     name = next(ln.split(":", 1)[1].strip() for ln in entry if ln.strip().lstrip("- ").startswith(".name:"))
     found[name]["metadata"] = clean(entry)
 
 
-def compare(before_dir, after_dir):
+def compare(before_dir, after_dir, pair_by_name=False):
     differ = False
     for fn in sorted(f for f in os.listdir(before_dir) if f.endswith(".s")):
         a, b = kernels_of(os.path.join(before_dir, fn)), kernels_of(os.path.join(after_dir, fn))
+        if pair_by_name:
+            a, b = by_name(a), by_name(b)
         report = []
         if set(a) != set(b):
             report.append(f"  kernel names differ: only before {sorted(set(a) - set(b))}, only after {sorted(set(b) - set(a))}")
@@ -85,9 +108,10 @@ def compare(before_dir, after_dir):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) < 3 or len(sys.argv) % 2 == 0:
+    args = [x for x in sys.argv[1:] if x != "--by-name"]
+    if len(args) < 2 or len(args) % 2:
         sys.exit(__doc__)
     bad = False
-    for k in range(1, len(sys.argv), 2):
-        bad = compare(sys.argv[k], sys.argv[k + 1]) or bad
+    for k in range(0, len(args), 2):
+        bad = compare(args[k], args[k + 1], pair_by_name="--by-name" in sys.argv) or bad
     sys.exit(1 if bad else 0)

@@ -5,9 +5,8 @@
 
 __global__ __launch_bounds__(kMfmaThreads, 2) void tile16_fp4_kernel(
     const uint8_t* __restrict__ X4, uint64_t row_bytes, const MfmaItem* __restrict__ items,
-    uint32_t* __restrict__ out, uint64_t ld, uint32_t n_rows, const uint32_t* __restrict__ row_counts,
-    uint32_t and_weight, uint32_t j_base, uint32_t j_count, uint32_t split_from, uint32_t i_lo,
-    uint32_t n_cols) {
+    OutWindow window, uint32_t split_from) {
+    const OutWindow w = window.loaded();
     __shared__ __attribute__((aligned(1024))) uint8_t lds[kT16Ring][kT16StageBytes];
 
     const uint32_t tid = threadIdx.x;
@@ -171,25 +170,23 @@ __global__ __launch_bounds__(kMfmaThreads, 2) void tile16_fp4_kernel(
 #undef STORM_T16_FETCH
 
     // ---- epilogue: C/D map of the 16x16 form: col = lane & 15, row = 4 * (lane >> 4) + reg
-    const bool rect = j_count != 0;
 #pragma unroll
     for (int n = 0; n < 16; ++n) {
         const uint32_t j = b_row0 + (uint32_t)n * 16u + (lane & 15u);
-        const bool j_ok = rect ? (j >= j_base && j - j_base < j_count) : j < n_cols;
-        const uint32_t nj = (row_counts && j_ok) ? row_counts[j] : 0u;
+        const bool j_ok = w.wants_col(j);
+        const uint32_t nj = w.nj(j);
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const uint32_t i = a_row0 + wave * 32u + (uint32_t)m * 16u + 4u * (lane >> 4) + (uint32_t)r;
-                if (j_ok && i >= i_lo && i < n_rows && (rect || i < j)) {
+                if (j_ok && w.writes_row(i, j)) {
                     const uint32_t c = (uint32_t)acc[m][n][r];
-                    uint32_t* dst = &out[(uint64_t)(i - i_lo) * ld + (j - j_base)];
+                    uint32_t* dst = w.at(i, j);
                     if (item_idx < split_from) {
-                        *dst = row_counts ? row_counts[i] + nj - and_weight * c : c;
+                        *dst = w.value(c, i, nj);
                     } else {  // partial over k: the n_i + n_j term once, mod 2^32 throughout
-                        const uint32_t once = (row_counts && it.stage0 == 0) ? row_counts[i] + nj : 0u;
-                        atomicAdd(dst, row_counts ? once - and_weight * c : c);
+                        atomicAdd(dst, w.part_value(c, i, nj, it.stage0 == 0));
                     }
                 }
             }

@@ -4,9 +4,8 @@
 // stand; it is not part of the shipped library.
 
 __global__ __launch_bounds__(kTbThreads, 1) void tilebits_kernel(
-    TileOperands ops, const MfmaItem* __restrict__ items, uint32_t* __restrict__ out, uint64_t ld,
-    uint32_t n_rows, const uint32_t* __restrict__ row_counts, uint32_t and_weight, uint32_t j_base,
-    uint32_t j_count, uint32_t split_from, uint32_t i_lo, uint32_t n_cols) {
+    TileOperands ops, const MfmaItem* __restrict__ items, OutWindow window, uint32_t split_from) {
+    const OutWindow w = window.loaded();
     __shared__ __attribute__((aligned(1024))) uint8_t lds[kTbRing][kTbStageBytes];
 
     const uint32_t tid = threadIdx.x;
@@ -21,18 +20,10 @@ __global__ __launch_bounds__(kTbThreads, 1) void tilebits_kernel(
     const uint32_t pitch = (uint32_t)ops.pitch;
 
     // operand windows: base of the tile's first row and the bytes of it that exist
-    auto window = [&](uint32_t v0, const uint8_t*& base, uint32_t& bytes) {
-        const bool second = v0 >= ops.split;
-        const uint32_t r0 = second ? v0 - ops.split : v0;
-        const uint32_t have = second ? ops.rows_b : ops.rows_a;
-        const uint32_t rows = have > r0 ? min(have - r0, (uint32_t)kTile) : 0u;
-        base = (second ? ops.xb : ops.xa) + (uint64_t)r0 * ops.pitch;
-        bytes = rows * pitch;
-    };
     const uint8_t *a_base, *b_base;
     uint32_t a_bytes, b_bytes;
-    window(a_row0, a_base, a_bytes);
-    window(b_row0, b_base, b_bytes);
+    ops.tile_rows(a_row0, (uint32_t)kTile, a_base, a_bytes);
+    ops.tile_rows(b_row0, (uint32_t)kTile, b_base, b_bytes);
 
     // DMA: an image is 16 wave-instructions of 1 KiB (16 rows each). Piece p of a stage (one per class
     // phase): instruction w + 4 (p % 4) of the A image (p < 4) or of the B image. Lane L fills row
@@ -389,40 +380,34 @@ __global__ __launch_bounds__(kTbThreads, 1) void tilebits_kernel(
 #undef STORM_TB_FETCH
 
     // ---- epilogue: C/D map of the 32x32 form: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-    const bool rect = j_count != 0;
     {
-        const uint32_t col0 = b_row0 - j_base;  // rect: j_base <= b_row0 is implied by the range test
-        const bool interior =
-            item_idx < split_from && a_row0 >= i_lo && a_row0 + kTile <= n_rows &&
-            (rect ? (b_row0 >= j_base && col0 + kTile <= j_count) : (b_row0 + kTile <= n_cols && a_row0 != b_row0)) &&
-            (ld & 3u) == 0 && ((uintptr_t)out & 15u) == 0;
+        const bool interior = item_idx < split_from && w.covers(a_row0, (uint32_t)kTile, b_row0, (uint32_t)kTile) &&
+                              (w.ld & 3u) == 0 && ((uintptr_t)w.out & 15u) == 0;
         if (interior) {
             __builtin_amdgcn_s_barrier();  // every wave has left the ring
-            tb_store_interior<4>(acc, &lds[0][0] + wave * 16384u,
-                                 &out[(uint64_t)(a_row0 + wa * 128u - i_lo) * ld + col0 + wb * 128u], ld, lane,
-                                 row_counts, a_row0 + wa * 128u, b_row0 + wb * 128u, and_weight);
+            tb_store_interior<4>(acc, &lds[0][0] + wave * 16384u, w.at(a_row0 + wa * 128u, b_row0 + wb * 128u), w.ld, lane,
+                                 w.row_counts, a_row0 + wa * 128u, b_row0 + wb * 128u, w.and_weight);
             return;
         }
     }
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
         const uint32_t j = b_row0 + wb * 128u + (uint32_t)n * 32u + (lane & 31u);
-        const bool j_ok = rect ? (j >= j_base && j - j_base < j_count) : j < n_cols;
-        const uint32_t nj = (row_counts && j_ok) ? row_counts[j] : 0u;
+        const bool j_ok = w.wants_col(j);
+        const uint32_t nj = w.nj(j);
 #pragma unroll
         for (int m = 0; m < 4; ++m)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const uint32_t i = a_row0 + wa * 128u + (uint32_t)m * 32u + (uint32_t)((r & 3) + 8 * (r >> 2)) +
                                    4u * (lane >> 5);
-                if (j_ok && i >= i_lo && i < n_rows && (rect || i < j)) {
+                if (j_ok && w.writes_row(i, j)) {
                     const uint32_t c = (uint32_t)acc[m][n][r];
-                    uint32_t* dst = &out[(uint64_t)(i - i_lo) * ld + (j - j_base)];
+                    uint32_t* dst = w.at(i, j);
                     if (item_idx < split_from) {
-                        *dst = row_counts ? row_counts[i] + nj - and_weight * c : c;
+                        *dst = w.value(c, i, nj);
                     } else {  // partial over k: the n_i + n_j term once, mod 2^32 throughout
-                        const uint32_t once = (row_counts && it.stage0 == 0) ? row_counts[i] + nj : 0u;
-                        atomicAdd(dst, row_counts ? once - and_weight * c : c);
+                        atomicAdd(dst, w.part_value(c, i, nj, it.stage0 == 0));
                     }
                 }
             }
