@@ -50,7 +50,31 @@ int storm_hip_device_arch(int device, char* buf, size_t buflen);
 /* PCI address of `device` ("0000:75:00.0") into buf: which physical GPU a rank drives */
 int storm_hip_device_pci_bus_id(int device, char* buf, size_t buflen);
 
-/* ---- context: device, stream, reusable workspace ---- */
+/* ---- context: device, stream, reusable workspace ----
+ * The stream contract (tests/test_gpu_streams.py):
+ *   - Everything a context enqueues — kernels, zero fills, copies, the zeroing of its own workspace at creation — goes on its
+ *     stream (`stream` of storm_hip_ctx_create, later storm_hip_ctx_set_stream's; NULL = the default stream). The one
+ *     internal second stream (the panel copies of storm_hip_pairw_dense_upload) is ordered against it by events, both ways.
+ *   - A call documented "synchronous" or "complete on return" has waited for the context's stream: its outputs, in host or
+ *     in device memory, may be read by the host and by work on ANY other stream as soon as it returns.
+ *   - The asynchronous calls only enqueue; a consumer enqueued on the same stream afterwards needs no host wait. They are:
+ *       storm_hip_matrix_create (its zero fill), storm_hip_matrix_clear, storm_hip_matrix_fill_synthetic,
+ *       storm_hip_matrix_import, storm_hip_matrix_resize when it shrinks (a growing resize waits),
+ *       every `_launch` (storm_hip_pairw_dense_launch), every `_begin` (storm_hip_pairw_dense_begin, _pairw_sparse_begin,
+ *       _pairw_matrix_band_begin), and the primitives that say so (storm_hip_similarity_finish_device, _finish_lag_device,
+ *       storm_hip_topk_rows_device).
+ *     A `_begin` is finished by its `_end` on the same context, whatever stream the context has by then.
+ *   - storm_hip_ctx_set_stream: work enqueued through the context after the call is ordered after ALL work enqueued through it
+ *     before the call (an event recorded on the stream that is left, which the new stream waits for; if no event can be made
+ *     the call waits for the old stream). The context's workspace (partial-sum slots, result word, mailbox, cached work lists)
+ *     is therefore never used by two passes at once, and matrices, sparse arenas, row lists and stages made under the context
+ *     stay usable. The call itself does not wait; a stream equal to the current one is a no-op. The old stream must still
+ *     exist when the call is made.
+ *   - The caller orders its OWN producers and consumers against the context's stream: a tensor handed to
+ *     storm_hip_matrix_import or read from storm_hip_matrix_device_ptr, the word a `_launch` writes, must be produced / consumed
+ *     on that stream or behind an event of the caller's.
+ *   - One context is driven by one host thread at a time; two contexts on one device are independent (each has its own
+ *     workspace) and may be interleaved call by call from one thread. */
 int storm_hip_ctx_create(int device, void* stream, storm_hip_ctx_t** out);
 int storm_hip_ctx_set_stream(storm_hip_ctx_t* ctx, void* stream);
 int storm_hip_ctx_synchronize(storm_hip_ctx_t* ctx);

@@ -552,8 +552,10 @@ int storm_hip_ctx_create(int device, void* stream, storm_hip_ctx_t** out) {
         storm_hip_ctx_destroy(ctx);
         return STORM_HIP_ENOMEM;
     }
-    if (hipMemset(ctx->d_slots, 0, (kSlots + kSlotsExtra) * sizeof(uint64_t)) != hipSuccess ||
-        hipMemset(ctx->d_scalar, 0, 64) != hipSuccess) {
+    // (on the context's stream: a caller's non-blocking stream is not ordered against the NULL stream, and with
+    //  STORM_HIP_NO_WARM nothing below waits before the first pass adds into the slots)
+    if (hipMemsetAsync(ctx->d_slots, 0, (kSlots + kSlotsExtra) * sizeof(uint64_t), ctx->stream) != hipSuccess ||
+        hipMemsetAsync(ctx->d_scalar, 0, 64, ctx->stream) != hipSuccess) {
         set_error("workspace memset failed");
         storm_hip_ctx_destroy(ctx);
         return STORM_HIP_EHIP;
@@ -590,7 +592,21 @@ int storm_hip_ctx_create(int device, void* stream, storm_hip_ctx_t** out) {
 
 int storm_hip_ctx_set_stream(storm_hip_ctx_t* ctx, void* stream) {
     if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-    ctx->stream = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t next = reinterpret_cast<hipStream_t>(stream);
+    if (next == ctx->stream) return STORM_HIP_OK;
+    STORM_HIP_TRY(hipSetDevice(ctx->device));
+    // What the context enqueues from now on comes after everything it has enqueued so far: the zero fills of create / clear /
+    // fill_synthetic / resize, passes that still use the slots, the result word and the cached work lists, a _begin whose
+    // _end waits for the new stream. One event on the stream that is left; without one, the host waits for that stream.
+    bool ordered = false;
+    if (ctx->switch_ev || hipEventCreateWithFlags(&ctx->switch_ev, hipEventDisableTiming) == hipSuccess)
+        ordered = hipEventRecord(ctx->switch_ev, ctx->stream) == hipSuccess &&
+                  hipStreamWaitEvent(next, ctx->switch_ev, 0) == hipSuccess;
+    if (!ordered) {
+        (void)hipGetLastError();
+        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    ctx->stream = next;
     return STORM_HIP_OK;
 }
 
@@ -625,6 +641,7 @@ void storm_hip_ctx_destroy(storm_hip_ctx_t* ctx) {
     if (ctx->h_stage_ring) (void)hipHostFree(ctx->h_stage_ring);
     for (hipEvent_t e : ctx->stage_ev)
         if (e) (void)hipEventDestroy(e);
+    if (ctx->switch_ev) (void)hipEventDestroy(ctx->switch_ev);
     ctx->d_segs.release();
     release_mfma_state(ctx);
     for (hipEvent_t ev : ctx->kernel_events) (void)hipEventDestroy(ev);

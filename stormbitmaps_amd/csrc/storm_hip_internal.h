@@ -114,6 +114,7 @@ int launch_pairw_segments(storm_hip_ctx_t* ctx, const uint64_t* X, uint64_t stri
 struct storm_hip_ctx_s {
     int device = 0;
     hipStream_t stream = nullptr;
+    hipEvent_t switch_ev = nullptr;          // storm_hip_ctx_set_stream: recorded on the stream that is left, waited for by the next one
     int n_cus = 0;
     // workspace
     unsigned long long* d_slots = nullptr;   // kSlots partial sums
