@@ -444,6 +444,34 @@ int STORM_dosage_pairw_nobs_device(STORM_dosage_t* h, uint32_t* d_out, uint64_t 
 int STORM_dosage_pairw_corr_complete(STORM_dosage_t* h, int measure, float* out, uint64_t out_rows, uint64_t out_ld);
 int STORM_dosage_pairw_corr_complete_device(STORM_dosage_t* h, int measure, float* d_out, uint64_t out_rows, uint64_t out_ld);
 
+/* The four pairwise calls of the dosage container for the pairs within max_lag rows of each other only — PLINK's --r / --r2
+ * as it is run on genotype files: within a window (--ld-window), never all-vs-all. The layout is STORM_pairw_lag_matrix's:
+ * with n the rows held and L = min(max_lag, n - 1), `out` holds out_rows x out_ld entries (out_rows >= n, out_ld >= L) and
+ * the pair (i, j), 1 <= j - i <= L, lies at out[i * out_ld + (j - i - 1)]. Memory and work are O(n L): only the tiles within
+ * L rows of the diagonal are multiplied, and no buffer of any of the calls grows with n^2.
+ *   STORM_dosage_pairw_lag_dot             P(i, j) (uint32, exact; 3 is an ordinary value)
+ *   STORM_dosage_pairw_lag_corr            STORM_dosage_pairw_corr's float at the pair: the same bits
+ *   STORM_dosage_pairw_lag_nobs            N(i, j), 3 = STORM_DOSAGE_MISSING
+ *   STORM_dosage_pairw_lag_corr_complete   STORM_dosage_pairw_corr_complete's float at the pair: the same bits (and, on rows
+ *                                          without a 3, STORM_dosage_pairw_lag_corr's). Device scratch: 3 n x (3 L + 2)
+ *                                          uint32 and three copies of the rows, kept by the device context
+ * Host forms write columns [0, L) of every row (0 / +0.0f where i + 1 + d >= n); _device forms (`d_out` in device memory)
+ * leave everything outside the layout untouched. One device slot and one process.
+ * Returns 0; -1 NULL handle, -2 NULL out, -4 out_rows < n or out_ld < L (nothing is written), -3 device failure, an unknown
+ * measure or max_lag 0 (STORM_hip_error says which), -5 several device slots in view. Fewer than two rows: 0, nothing
+ * written. */
+int STORM_dosage_pairw_lag_dot(STORM_dosage_t* h, uint64_t max_lag, uint32_t* out, uint64_t out_rows, uint64_t out_ld);
+int STORM_dosage_pairw_lag_dot_device(STORM_dosage_t* h, uint64_t max_lag, uint32_t* d_out, uint64_t out_rows, uint64_t out_ld);
+int STORM_dosage_pairw_lag_corr(STORM_dosage_t* h, int measure, uint64_t max_lag, float* out, uint64_t out_rows, uint64_t out_ld);
+int STORM_dosage_pairw_lag_corr_device(STORM_dosage_t* h, int measure, uint64_t max_lag, float* d_out, uint64_t out_rows,
+                                       uint64_t out_ld);
+int STORM_dosage_pairw_lag_nobs(STORM_dosage_t* h, uint64_t max_lag, uint32_t* out, uint64_t out_rows, uint64_t out_ld);
+int STORM_dosage_pairw_lag_nobs_device(STORM_dosage_t* h, uint64_t max_lag, uint32_t* d_out, uint64_t out_rows, uint64_t out_ld);
+int STORM_dosage_pairw_lag_corr_complete(STORM_dosage_t* h, int measure, uint64_t max_lag, float* out, uint64_t out_rows,
+                                         uint64_t out_ld);
+int STORM_dosage_pairw_lag_corr_complete_device(STORM_dosage_t* h, int measure, uint64_t max_lag, float* d_out, uint64_t out_rows,
+                                                uint64_t out_ld);
+
 /* ------------------------------------------------------------- extensions (not in ref) ---
  * Device selection for the entry points above. By default device 0 computes everything.
  * STORM_hip_set_devices(n, ids): the pair space is sharded over the listed GPUs of this node

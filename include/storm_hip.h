@@ -385,6 +385,53 @@ int storm_hip_pairw_dosage_corr_complete_device(storm_hip_ctx_t* ctx, const stor
 int storm_hip_pairw_dosage_corr_complete(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_samples,
                                          float* h_out, uint64_t ld);
 
+/* ---- dosage matrices in the lag layout: PLINK --r / --r2 within a window (--ld-window) ---------------------------
+ * The calls of the two blocks above for the pairs within max_lag rows of each other, in the lag layout of
+ * storm_hip_pairw_lag_matrix_device: with L = min(max_lag, n_rows - 1), entry out[i * ld + (j - i - 1)] is the pair
+ * (i, j), 1 <= j - i <= L, ld >= L: n x L entries, and memory and work are O(n L). Always K2h in its lag and dosage form
+ * (tile128_kernel<true, 2>); read-only option "k2_tile_shape_used" reads 7.
+ * _lag_dosage_matrix_device: P(i, j) = sum v_i v_j (uint32, exact; 3 is an ordinary value) into DEVICE memory; the row band
+ *   [row0, row0 + n_band_rows) (n_band_rows = ~0: all rows from row0) is written from output row 0. Complete on return.
+ *   The lower-right corner (i + 1 + d >= n_rows) and the pitch columns [L, ld) stay untouched.
+ * _lag_dosage_matrix: all rows into HOST memory: columns [0, L) of every row are written, 0 in the corner; columns [L, ld)
+ *   stay untouched.
+ * _dosage_finish_lag_device: the in-place uint32 -> float pass alone over a matrix of dot products in the lag layout
+ *   (dosage_finish_lag_kernel): entry (i - row0, d) from d_sum / d_sum_sq (n_rows entries each, device) of rows i and
+ *   i + 1 + d. Asynchronous on the context's stream; alone the last-pass report is STORM_HIP_RAN_SIMILARITY.
+ * _lag_dosage_corr[_device]: the dot products, the rows' sums, then that pass. Bit-identical to the same pairs of
+ *   storm_hip_pairw_dosage_corr. Host form: +0.0f in the corner.
+ * _lag_dosage_nobs[_device], _lag_dosage_corr_complete[_device]: code 3 means MISSING, as in the block above. The rows are
+ *   split on the device into ONE matrix of 3 n rows (row 3 i: G_i, 3 i + 1: H_i, 3 i + 2: M_i); _nobs is the lag form on
+ *   its M rows; _corr_complete is one launch of K2h over all 3 n rows at lag 3 L + 2 — which holds every product of G, H
+ *   and M of two rows within L of each other — into a scratch matrix of 3 n x (3 L + 2) uint32 and
+ *   dosage_complete_finish_lag_kernel from there into the caller's matrix. Device scratch held by the context: that
+ *   matrix and three copies of the rows, nothing that grows with n^2; an allocation that fails returns STORM_HIP_ENOMEM
+ *   with the buffer named. Bit-identical to the same pairs of storm_hip_pairw_dosage_corr_complete; on rows without a 3,
+ *   to _lag_dosage_corr's.
+ * STORM_HIP_EINVAL: NULL argument, unknown measure, max_lag 0, ld < L, a band outside the rows, n_samples that does not match
+ * the row width, rows of more than 2^24 values, rows beyond K2h's reach (for the two calls on missing genotypes: 3 n rows).
+ * Fewer than two rows or an empty band: STORM_HIP_OK, nothing written. Last-pass report: STORM_HIP_RAN_TILES_OUT
+ * (| STORM_HIP_RAN_SIMILARITY), [1] = the pairs within the lag x n_words (_corr_complete: of the 3 n rows within 3 L + 2). */
+int storm_hip_pairw_lag_dosage_matrix_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t max_lag, uint64_t row0,
+                                             uint64_t n_band_rows, uint32_t* d_out, uint64_t ld);
+int storm_hip_pairw_lag_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t max_lag, uint32_t* h_out,
+                                      uint64_t ld);
+int storm_hip_dosage_finish_lag_device(storm_hip_ctx_t* ctx, void* d_io, uint64_t ld, uint64_t n_rows, uint64_t row0,
+                                       uint64_t n_band_rows, uint64_t max_lag, const uint32_t* d_sum, const uint32_t* d_sum_sq,
+                                       int measure, uint64_t n_samples);
+int storm_hip_pairw_lag_dosage_corr_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_samples,
+                                           uint64_t max_lag, float* d_out, uint64_t ld);
+int storm_hip_pairw_lag_dosage_corr(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_samples,
+                                    uint64_t max_lag, float* h_out, uint64_t ld);
+int storm_hip_pairw_lag_dosage_nobs_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples,
+                                           uint64_t max_lag, uint32_t* d_out, uint64_t ld);
+int storm_hip_pairw_lag_dosage_nobs(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint64_t max_lag,
+                                    uint32_t* h_out, uint64_t ld);
+int storm_hip_pairw_lag_dosage_corr_complete_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure,
+                                                    uint64_t n_samples, uint64_t max_lag, float* d_out, uint64_t ld);
+int storm_hip_pairw_lag_dosage_corr_complete(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_samples,
+                                             uint64_t max_lag, float* h_out, uint64_t ld);
+
 /* sum_c C(n_c,2) on the device — verification identity only, never the product
  * path: used by tests at sizes where a CPU pairwise oracle is infeasible */
 int storm_hip_column_identity(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m,
@@ -540,6 +587,13 @@ int storm_hip_dosage_square_plan(uint64_t n_rows_a, uint64_t n_rows_b, uint32_t 
 int storm_hip_lag_plan(uint64_t n_rows, uint32_t n_words, uint64_t max_lag, uint64_t band_row0, uint64_t band_rows,
                        uint32_t n_cus, int slots_per_cu, int min_chunks, int diag_cost_pct, uint32_t* out,
                        uint64_t capacity_items, uint64_t* n_items);
+
+/* The K2h list of the dosage form in the lag layout (storm_hip_pairw_lag_dosage_matrix_device): storm_hip_lag_plan's tiles
+ * for a matrix of n_words words of 2-bit values, under storm_hip_dosage_plan's two limits (7281 chunks per item, narrow
+ * windows up to 28 chunks per part). Host only; `out` may be NULL. */
+int storm_hip_lag_dosage_plan(uint64_t n_rows, uint32_t n_words, uint64_t max_lag, uint64_t band_row0, uint64_t band_rows,
+                              uint32_t n_cus, int slots_per_cu, int min_chunks, int diag_cost_pct, uint32_t* out,
+                              uint64_t capacity_items, uint64_t* n_items);
 
 /* The same for the one-launch stage stream on bit operands (K2q, the default for matrices of up to 8192
  * rows on one device): the segments shard `shard_rank` of `shard_count` walks on a device of

@@ -367,6 +367,39 @@ class StormDosage:
                                                                    _ptr(out) if out.size else _ptr(np.zeros(1, np.float32)), n, n)))
         return out
 
+    # ---- the pairs within max_lag rows of each other: pair (i, j) at [i, j - i - 1] of an [n_rows, L] matrix ----
+    def _pairw_lag(self, name: str, dtype, max_lag: int, device, *args):
+        n, w = self.n_rows, min(max_lag, max(self.n_rows - 1, 0))
+        if device is not None:
+            if device.dim() != 2 or device.element_size() != 4 or device.stride(1) != 1 or not device.is_cuda:
+                raise ValueError("device=: a 2-D tensor of 32-bit entries in device memory with contiguous rows")
+            self._check(name + "_device", int(getattr(self._lib, name + "_device")(self._h, *args, max_lag, C.c_void_p(device.data_ptr()),
+                                                                                   int(device.shape[0]), int(device.stride(0)))))
+            return None
+        out = np.zeros((n, w), dtype=dtype)
+        self._check(name, int(getattr(self._lib, name)(self._h, *args, max_lag, _ptr(out) if out.size else _ptr(np.zeros(1, dtype)),
+                                                       n, w)))
+        return out
+
+    def pairw_lag_dot(self, max_lag: int, device=None):
+        """STORM_dosage_pairw_lag_dot: [n_rows, L] uint32, L = min(max_lag, n_rows - 1): entry (i, d) = the dot product of rows i
+        and i + 1 + d, 0 where i + 1 + d >= n_rows. device=: a 2-D torch tensor of 32-bit entries in device memory (at least
+        n_rows x L) that receives the layout instead (everything outside it stays as it was); returns None then."""
+        return self._pairw_lag("STORM_dosage_pairw_lag_dot", np.uint32, max_lag, device)
+
+    def pairw_lag_corr(self, max_lag: int, measure: str = "r2", device=None):
+        """STORM_dosage_pairw_lag_corr: [n_rows, L] float32, pairw_corr's value (the same bits) of rows i and i + 1 + d."""
+        return self._pairw_lag("STORM_dosage_pairw_lag_corr", np.float32, max_lag, device, DOSAGE_MEASURES[measure])
+
+    def pairw_lag_nobs(self, max_lag: int, device=None):
+        """STORM_dosage_pairw_lag_nobs: [n_rows, L] uint32, the samples neither of rows i and i + 1 + d is missing (3) at."""
+        return self._pairw_lag("STORM_dosage_pairw_lag_nobs", np.uint32, max_lag, device)
+
+    def pairw_lag_corr_complete(self, max_lag: int, measure: str = "r2", device=None):
+        """STORM_dosage_pairw_lag_corr_complete: [n_rows, L] float32, pairw_corr_complete's value (the same bits) of rows i and
+        i + 1 + d (value 3 = missing); memory and work are O(n_rows x L)."""
+        return self._pairw_lag("STORM_dosage_pairw_lag_corr_complete", np.float32, max_lag, device, DOSAGE_MEASURES[measure])
+
     def free(self) -> None:
         if self._h:
             self._lib.STORM_dosage_free(self._h)
@@ -826,6 +859,64 @@ class HipMatrix:
                                                                (1 << 64) - 1 if n_band_rows is None else n_band_rows, max_lag,
                                                                C.c_void_p(d_counts), MEASURES[measure], n_bits),
               "storm_hip_similarity_finish_lag_device")
+
+    # ---- a matrix whose rows hold 2-bit dosages (32 values per word), in the lag layout (storm_hip.h) ----
+    def _lag_dosage_host(self, name: str, dtype, max_lag: int, *args) -> np.ndarray:
+        w = self._lag_width(max_lag)
+        out = np.zeros((self.n_rows, w), dtype=dtype)
+        check(getattr(self._lib, name)(self.ctx._h, self._h, *args, max_lag, _ptr(out) if out.size else _ptr(np.zeros(1, dtype)), w),
+              name)
+        return out
+
+    def pairw_lag_dosage_matrix(self, max_lag: int) -> np.ndarray:
+        """[n_rows, L] uint32: entry (i, d) = sum_s v_i[s] v_{i+1+d}[s] of the rows' 2-bit values, 0 in the corner."""
+        return self._lag_dosage_host("storm_hip_pairw_lag_dosage_matrix", np.uint32, max_lag)
+
+    def pairw_lag_dosage_matrix_device(self, d_out: int, ld: int, max_lag: int, row0: int = 0,
+                                       n_band_rows: Optional[int] = None) -> None:
+        """Same, rows [row0, row0 + n_band_rows) (None: all) into a device buffer (n_band_rows x ld uint32); synchronous."""
+        check(self._lib.storm_hip_pairw_lag_dosage_matrix_device(self.ctx._h, self._h, max_lag, row0,
+                                                                 (1 << 64) - 1 if n_band_rows is None else n_band_rows,
+                                                                 C.c_void_p(d_out), ld),
+              "storm_hip_pairw_lag_dosage_matrix_device")
+
+    def pairw_lag_dosage_corr(self, max_lag: int, n_samples: int, measure: str = "r2") -> np.ndarray:
+        """[n_rows, L] float32: the genotype correlation ("r") of rows i and i + 1 + d or its square ("r2"), +0.0 in the corner."""
+        return self._lag_dosage_host("storm_hip_pairw_lag_dosage_corr", np.float32, max_lag, DOSAGE_MEASURES[measure], n_samples)
+
+    def pairw_lag_dosage_corr_device(self, d_out: int, ld: int, max_lag: int, n_samples: int, measure: str = "r2") -> None:
+        """Same, into a device buffer (n_rows x ld float32); complete on return."""
+        check(self._lib.storm_hip_pairw_lag_dosage_corr_device(self.ctx._h, self._h, DOSAGE_MEASURES[measure], n_samples, max_lag,
+                                                               C.c_void_p(d_out), ld),
+              "storm_hip_pairw_lag_dosage_corr_device")
+
+    def dosage_finish_lag_device(self, d_io: int, ld: int, max_lag: int, d_sum: int, d_sum_sq: int, n_samples: int,
+                                 measure: str = "r2", row0: int = 0, n_band_rows: Optional[int] = None) -> None:
+        """The finish pass alone over a matrix of dot products in the lag layout at d_io (d_sum, d_sum_sq: n_rows uint32 each
+        on the device); asynchronous on the context's stream."""
+        check(self._lib.storm_hip_dosage_finish_lag_device(self.ctx._h, C.c_void_p(d_io), ld, self.n_rows, row0,
+                                                           (1 << 64) - 1 if n_band_rows is None else n_band_rows, max_lag,
+                                                           C.c_void_p(d_sum), C.c_void_p(d_sum_sq), DOSAGE_MEASURES[measure],
+                                                           n_samples),
+              "storm_hip_dosage_finish_lag_device")
+
+    def pairw_lag_dosage_nobs(self, max_lag: int, n_samples: int) -> np.ndarray:
+        """[n_rows, L] uint32: the samples neither of rows i and i + 1 + d is missing (value 3) at, 0 in the corner."""
+        return self._lag_dosage_host("storm_hip_pairw_lag_dosage_nobs", np.uint32, max_lag, n_samples)
+
+    def pairw_lag_dosage_nobs_device(self, d_out: int, ld: int, max_lag: int, n_samples: int) -> None:
+        check(self._lib.storm_hip_pairw_lag_dosage_nobs_device(self.ctx._h, self._h, n_samples, max_lag, C.c_void_p(d_out), ld),
+              "storm_hip_pairw_lag_dosage_nobs_device")
+
+    def pairw_lag_dosage_corr_complete(self, max_lag: int, n_samples: int, measure: str = "r2") -> np.ndarray:
+        """[n_rows, L] float32: pairw_lag_dosage_corr over the samples both rows have (value 3 = missing)."""
+        return self._lag_dosage_host("storm_hip_pairw_lag_dosage_corr_complete", np.float32, max_lag, DOSAGE_MEASURES[measure],
+                                     n_samples)
+
+    def pairw_lag_dosage_corr_complete_device(self, d_out: int, ld: int, max_lag: int, n_samples: int, measure: str = "r2") -> None:
+        check(self._lib.storm_hip_pairw_lag_dosage_corr_complete_device(self.ctx._h, self._h, DOSAGE_MEASURES[measure], n_samples,
+                                                                        max_lag, C.c_void_p(d_out), ld),
+              "storm_hip_pairw_lag_dosage_corr_complete_device")
 
     def pairw_topk(self, k: int, score: str = "jaccard", n_bits: int = 1, panel_rows: int = 0):
         """(idx [n_rows, k] uint32, val [n_rows, k] float32, or uint32 for score "count"): for each row its k best other rows,

@@ -68,6 +68,20 @@ STORM_DOSAGE_FN void dosage_split_word(uint64_t w, uint64_t valid, uint64_t* g, 
     *m = ~both & kDosageLowBits & valid;
 }
 
+// Word w of row r of the INTERLEAVED split of a matrix X (n_rows rows of stride_words words, n_words of them data): row
+// 3 i is G_i, row 3 i + 1 is H_i, row 3 i + 2 is M_i — one matrix of 3 n_rows rows whose lag layout at lag 3 L + 2 holds
+// every product of G, H, M of two rows within L of each other (dosage_split_interleaved_kernel). Rows behind 3 n_rows
+// and the words behind n_words are zero.
+STORM_DOSAGE_FN uint64_t dosage_interleaved_word(const uint64_t* X, uint64_t stride_words, uint64_t n_rows, uint32_t n_words,
+                                                 uint64_t n_samples, uint64_t r, uint64_t w) {
+    const uint64_t row = r / 3u;
+    if (row >= n_rows || w >= n_words) return 0ull;
+    uint64_t g, h, m;
+    dosage_split_word(X[row * stride_words + w], dosage_valid_mask(w, n_words, n_samples), &g, &h, &m);
+    const uint32_t which = (uint32_t)(r % 3u);
+    return which == 0u ? g : which == 1u ? h : m;
+}
+
 // One entry over the samples BOTH rows have: N = their number, P = sum g_i g_j, sx = sum g_i m_j, sy = sum m_i g_j,
 // qx = sum g_i^2 m_j, qy = sum m_i g_j^2 (g: the value, 0 where missing; m: 1 where present; values 0 .. 2, at most 2^24
 // samples: every term below 2^51).
@@ -94,6 +108,20 @@ STORM_DOSAGE_FN uint32_t dosage_corr_complete_bits(uint32_t P, uint32_t N, uint3
     uint32_t bits;
     memcpy(&bits, &f, sizeof(bits));
     return bits;
+}
+
+// Where the six sums of the pair (i, i + 1 + d) lie in the lag layout (lag 3 L + 2) of the interleaved split, and what
+// entry (i, d) of the caller's matrix is made of (g_row, h_row, m_row: rows 3 i, 3 i + 1, 3 i + 2 of that layout):
+//   row 3 i     : P = G_i G_j at 3 d + 2, Sx = G_i M_j at 3 d + 4
+//   row 3 i + 1 : H_i M_j at 3 d + 3                      (Qx = Sx + 2 H_i M_j)
+//   row 3 i + 2 : Sy = M_i G_j at 3 d, M_i H_j at 3 d + 1 (Qy = Sy + 2 M_i H_j), N = M_i M_j at 3 d + 2
+// (rows 3 i + a and 3 j + b are 3 (d + 1) + b - a apart: column 3 d + 2 + b - a, at most 3 L + 1.)
+STORM_DOSAGE_FN uint32_t dosage_interleaved_entry_bits(const uint32_t* g_row, const uint32_t* h_row, const uint32_t* m_row,
+                                                       uint32_t d, int measure) {
+    const uint32_t c = 3u * d;
+    const uint32_t sx = g_row[c + 4u], sy = m_row[c];
+    return dosage_corr_complete_bits(g_row[c + 2u], m_row[c + 2u], sx, sy, sx + 2u * h_row[c + 3u], sy + 2u * m_row[c + 1u],
+                                     measure);
 }
 
 }  // namespace storm

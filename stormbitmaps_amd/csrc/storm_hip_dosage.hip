@@ -9,6 +9,11 @@
 // the value is 2) and M (1 where present) — K2h multiplies the triangles of G and of M and the rectangle [G ; H] x M, and
 // dosage_complete_finish_kernel turns the five sums of a pair into r / r^2 over the samples both rows have (DESIGN.md §4,
 // "K2h, dosage form with missing genotypes").
+// The lag layout (the *_lag_dosage_* calls: the pairs within max_lag rows of each other, an n x L matrix): K2h in its lag and
+// dosage form (tile128_kernel<true, 2>: launch_pairw_lag_dosage_matrix), dosage_finish_lag_kernel over it, and for missing
+// genotypes dosage_split_interleaved_kernel — G, H and M as ONE matrix of 3 n rows — one launch at lag 3 L + 2 into a scratch
+// matrix of 3 n x (3 L + 2) words and dosage_complete_finish_lag_kernel from there into the caller's matrix: O(n L)
+// throughout ("K2h, dosage form in the lag layout").
 #include "storm_hip_internal.h"
 #include "storm_dosage_math.h"
 
@@ -177,6 +182,121 @@ __global__ __launch_bounds__(256) void dosage_complete_finish_kernel(uint32_t* _
     }
 }
 
+// ---- the lag layout ("K2h, dosage form in the lag layout") ----
+// dosage_finish_kernel over the LAG layout (similarity_finish_lag_kernel's shape): entry (r, d) of the band is the pair
+// (i, i + 1 + d), i = row0 + r, so a tile of kDosTileRows x kDosTileCols entries reads s and q of its 64 rows and of the
+// 64 + 256 rows i0 + 1 + col0 .. behind them: both staged once per workgroup. Only entries with d < lag and
+// i + 1 + d < n_rows are touched (the lower-right corner and the pitch columns are neither read nor written); a lane's 4
+// entries are one 128-bit access where all 4 are converted and `vec`, else entry by entry.
+__global__ __launch_bounds__(256) void dosage_finish_lag_kernel(uint32_t* __restrict__ io, uint64_t ld, uint64_t n_rows, uint64_t row0,
+                                                                uint64_t band_end, uint64_t lag, const uint32_t* __restrict__ sum,
+                                                                const uint32_t* __restrict__ sum_sq, int measure,
+                                                                uint64_t n_samples, int vec) {
+    const uint64_t i0 = row0 + (uint64_t)blockIdx.y * kDosTileRows, col0 = (uint64_t)blockIdx.x * kDosTileCols;
+    if (i0 + 1 + col0 >= n_rows) return;   // the tile's first pair is already in the corner
+    __shared__ uint32_t s_sum[kDosTileRows], s_sq[kDosTileRows];
+    __shared__ uint32_t c_sum[kDosTileRows + kDosTileCols], c_sq[kDosTileRows + kDosTileCols];
+    if (threadIdx.x < kDosTileRows) {
+        const bool in = i0 + threadIdx.x < band_end;
+        s_sum[threadIdx.x] = in ? sum[i0 + threadIdx.x] : 0u;
+        s_sq[threadIdx.x] = in ? sum_sq[i0 + threadIdx.x] : 0u;
+    }
+    for (uint32_t k = threadIdx.x; k < kDosTileRows + kDosTileCols; k += 256u) {
+        const bool in = i0 + 1 + col0 + k < n_rows;
+        c_sum[k] = in ? sum[i0 + 1 + col0 + k] : 0u;
+        c_sq[k] = in ? sum_sq[i0 + 1 + col0 + k] : 0u;
+    }
+    __syncthreads();
+    const uint32_t lane4 = (threadIdx.x & 63u) * 4u;
+    const uint64_t c0 = col0 + lane4;
+    const uint32_t wave = threadIdx.x >> 6;
+    for (uint32_t r = wave; r < kDosTileRows; r += 4 * kDosUnroll) {
+        uint4 v[kDosUnroll];
+        bool whole[kDosUnroll];
+#pragma unroll
+        for (int u = 0; u < kDosUnroll; ++u) {   // the loads of kDosUnroll rows leave before the first divide
+            const uint64_t i = i0 + r + 4u * u;
+            whole[u] = vec && i < band_end && c0 + 4 <= lag && i + 1 + c0 + 3 < n_rows;
+            if (whole[u]) v[u] = *reinterpret_cast<const uint4*>(io + (i - row0) * ld + c0);
+        }
+#pragma unroll
+        for (int u = 0; u < kDosUnroll; ++u) {
+            const uint32_t rr = r + 4u * u;
+            const uint64_t i = i0 + rr;
+            if (i >= band_end) continue;
+            const uint32_t as = s_sum[rr], aq = s_sq[rr];
+            const uint32_t* const bs = &c_sum[rr + lane4];   // entry d = c0 + k: row i + 1 + c0 + k
+            const uint32_t* const bq = &c_sq[rr + lane4];
+            uint32_t* const p = io + (i - row0) * ld + c0;
+            if (whole[u]) {
+                uint4 w;
+                w.x = dosage_corr_bits(v[u].x, as, aq, bs[0], bq[0], measure, n_samples);
+                w.y = dosage_corr_bits(v[u].y, as, aq, bs[1], bq[1], measure, n_samples);
+                w.z = dosage_corr_bits(v[u].z, as, aq, bs[2], bq[2], measure, n_samples);
+                w.w = dosage_corr_bits(v[u].w, as, aq, bs[3], bq[3], measure, n_samples);
+                *reinterpret_cast<uint4*>(p) = w;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (c0 + k < lag && i + 1 + c0 + k < n_rows) p[k] = dosage_corr_bits(p[k], as, aq, bs[k], bq[k], measure, n_samples);
+            }
+        }
+    }
+}
+
+// One word per thread of the INTERLEAVED split of X (dosage_interleaved_word: row 3 i = G_i, 3 i + 1 = H_i, 3 i + 2 = M_i):
+// rows_out rows of stride_words words, zero behind row 3 n_rows and behind word n_words. Grid (rows, word tiles).
+__global__ __launch_bounds__(256) void dosage_split_interleaved_kernel(const uint64_t* __restrict__ X, uint64_t stride_words,
+                                                                       uint64_t n_rows, uint64_t rows_out, uint32_t n_words,
+                                                                       uint64_t n_samples, uint64_t* __restrict__ T) {
+    const uint64_t w = (uint64_t)blockIdx.y * 256u + threadIdx.x;
+    const uint64_t r = blockIdx.x;
+    if (w >= stride_words || r >= rows_out) return;
+    T[r * stride_words + w] = dosage_interleaved_word(X, stride_words, n_rows, n_words, n_samples, r, w);
+}
+
+constexpr uint32_t kDosLagTile = 64;                     // a workgroup finishes 64 rows x 64 lags ...
+constexpr uint32_t kDosLagPass = 8;                      // ... 8 rows at a time: wave w rows w and w + 4 of a pass
+constexpr uint32_t kDosLagRun = 3u * kDosLagTile + 2u;   // the columns of a scratch row that 64 lags read
+constexpr uint32_t kDosLagPitch = kDosLagRun + 2u;
+
+// The finishing pass of the pairwise-complete correlation in the lag layout. `sums` is the lag layout (lag 3 lag + 2, pitch
+// lds) of the dot products of the interleaved split (3 n rows): the six sums of entry (i, d) sit in its rows 3 i, 3 i + 1 and
+// 3 i + 2 at columns 3 d .. 3 d + 4 (dosage_interleaved_entry_bits). A wave reads the run [3 col0, 3 col0 + 194) of each of
+// the three rows of a row i — consecutive lanes, consecutive words — into the LDS, and lane l takes its six words from
+// there at a stride of 3 words (no bank conflict). Writes out[i * ld + d] for d < lag, i + 1 + d < n, nothing else; reads
+// nothing of `sums` beyond column lds of a row (what lies in its own corner is read into the LDS and never used).
+__global__ __launch_bounds__(256) void dosage_complete_finish_lag_kernel(const uint32_t* __restrict__ sums, uint64_t lds,
+                                                                         uint32_t* __restrict__ out, uint64_t ld, uint64_t n,
+                                                                         uint64_t lag, int measure) {
+    const uint64_t i0 = (uint64_t)blockIdx.y * kDosLagTile, col0 = (uint64_t)blockIdx.x * kDosLagTile;
+    if (i0 + 1 + col0 >= n) return;   // the tile's first pair is already in the corner
+    __shared__ uint32_t t[kDosLagPass][3][kDosLagPitch];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint64_t d = col0 + lane;
+    for (uint32_t pass = 0; pass < kDosLagTile / kDosLagPass; ++pass) {
+#pragma unroll
+        for (uint32_t h = 0; h < 2; ++h) {
+            const uint32_t k = wave + 4u * h;
+            const uint64_t i = i0 + pass * kDosLagPass + k;
+#pragma unroll
+            for (uint32_t a = 0; a < 3; ++a) {
+                const uint32_t* const row = sums + (3u * i + a) * lds + 3u * col0;
+                for (uint32_t c = lane; c < kDosLagRun; c += 64u) t[k][a][c] = (i < n && 3u * col0 + c < lds) ? row[c] : 0u;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t h = 0; h < 2; ++h) {
+            const uint32_t k = wave + 4u * h;
+            const uint64_t i = i0 + pass * kDosLagPass + k;
+            if (i < n && d < lag && i + 1 + d < n)
+                out[i * ld + d] = dosage_interleaved_entry_bits(t[k][0], t[k][1], t[k][2], lane, measure);
+        }
+        __syncthreads();
+    }
+}
+
 // the rows' sums into the context's row-count scratch: sum at [0, n), sum of squares at [n, 2 n); queued
 static int dosage_sums_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m) {
     const uint64_t n = m->n_rows;
@@ -332,6 +452,158 @@ static int check_square(const char* who, const storm_hip_matrix_s* a, const stor
         set_error("%s: rows of %u words hold more than 2^24 values", who, a->n_words);
         return STORM_HIP_EINVAL;
     }
+    return STORM_HIP_OK;
+}
+
+// ---- the lag layout ----
+// what the lag calls of the dosage form refuse alike (check_lag of storm_hip_similarity.hip and check_dosage); *lag = L
+static int check_lag_dosage(const char* who, const storm_hip_matrix_s* m, const void* out, uint64_t max_lag, uint64_t ld,
+                            uint64_t* lag) {
+    if (!m || !out || max_lag == 0) {
+        set_error("%s: NULL argument or max_lag 0", who);
+        return STORM_HIP_EINVAL;
+    }
+    *lag = m->n_rows ? std::min(max_lag, m->n_rows - 1) : 0;
+    if (ld < *lag) {
+        set_error("%s: leading dimension %llu < min(max_lag, rows - 1) = %llu", who, (unsigned long long)ld, (unsigned long long)*lag);
+        return STORM_HIP_EINVAL;
+    }
+    if ((uint64_t)m->n_words * 32u > kDosageMaxSamples) {
+        set_error("%s: rows of %u words hold more than 2^24 values", who, m->n_words);
+        return STORM_HIP_EINVAL;
+    }
+    return STORM_HIP_OK;
+}
+
+// dosage_finish_lag_kernel over a matrix of dot products in the lag layout, asynchronous (the checks of
+// storm_hip_dosage_finish_lag_device)
+static int launch_dosage_finish_lag(storm_hip_ctx_t* ctx, void* d_io, uint64_t ld, uint64_t n_rows, uint64_t row0,
+                                    uint64_t n_band_rows, uint64_t max_lag, const uint32_t* d_sum, const uint32_t* d_sum_sq,
+                                    int measure, uint64_t n_samples) {
+    if (!d_io || !d_sum || !d_sum_sq) {
+        set_error("dosage_finish_lag: NULL argument");
+        return STORM_HIP_EINVAL;
+    }
+    if (measure != STORM_HIP_DOSAGE_R2 && measure != STORM_HIP_DOSAGE_R) {
+        set_error("dosage_finish_lag: unknown measure %d (0 r^2, 1 r)", measure);
+        return STORM_HIP_EINVAL;
+    }
+    if (n_samples == 0 || n_samples > kDosageMaxSamples) {
+        set_error("dosage_finish_lag: n_samples %llu is not in [1, 2^24]", (unsigned long long)n_samples);
+        return STORM_HIP_EINVAL;
+    }
+    if (n_band_rows == ~0ull && row0 <= n_rows) n_band_rows = n_rows - row0;
+    const uint64_t lag = n_rows ? std::min(max_lag, n_rows - 1) : 0;
+    if (max_lag == 0 || row0 > n_rows || n_band_rows > n_rows - row0 || ld < lag) {
+        set_error("dosage_finish_lag: max_lag 0, a band outside the rows, or leading dimension < min(max_lag, rows - 1)");
+        return STORM_HIP_EINVAL;
+    }
+    if (n_rows < 2 || n_band_rows == 0) return STORM_HIP_OK;
+    const uint64_t tiles_x = (lag + kDosTileCols - 1) / kDosTileCols, tiles_y = (n_band_rows + kDosTileRows - 1) / kDosTileRows;
+    if (tiles_y > 65535u || tiles_x > 0x7fffffffu) {
+        set_error("dosage_finish_lag: %llu x %llu entries exceed the launch grid", (unsigned long long)n_band_rows,
+                  (unsigned long long)lag);
+        return STORM_HIP_EINVAL;
+    }
+    STORM_HIP_TRY(hipSetDevice(ctx->device));
+    const int vec = reinterpret_cast<uintptr_t>(d_io) % 16 == 0 && ld % 4 == 0;
+    hipLaunchKernelGGL(dosage_finish_lag_kernel, dim3((uint32_t)tiles_x, (uint32_t)tiles_y), dim3(256), 0, ctx->stream,
+                       static_cast<uint32_t*>(d_io), ld, n_rows, row0, row0 + n_band_rows, lag, d_sum, d_sum_sq, measure, n_samples,
+                       vec);
+    STORM_HIP_TRY(hipGetLastError());
+    ctx->pass_report[0] |= STORM_HIP_RAN_SIMILARITY;
+    return STORM_HIP_OK;
+}
+
+// dot products in the lag layout at d_io (pitch ld), the rows' sums, then the finish: all queued
+static int lag_dosage_corr_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int measure, uint64_t n_samples,
+                                  uint64_t max_lag, uint32_t* d_io, uint64_t ld) {
+    const uint64_t n = m->n_rows;
+    if (int rc = launch_pairw_lag_dosage_matrix(ctx, m, max_lag, 0, n, d_io, ld, false)) return rc;
+    if (int rc = dosage_sums_queued(ctx, m)) return rc;
+    return launch_dosage_finish_lag(ctx, d_io, ld, n, 0, n, max_lag, ctx->d_counts.d, ctx->d_counts.d + n, measure, n_samples);
+}
+
+// The interleaved split of a matrix with missing genotypes, in ctx->d_dosage_rows: one matrix of 3 n rows (G_i, H_i, M_i at
+// rows 3 i, 3 i + 1, 3 i + 2) of the source's stride, zero rows up to the next multiple of 128 (and two more: M's view
+// below ends a row pitch behind its last row). `m`: the M rows alone, a view of every third row. Queued.
+struct DosageInterleaved {
+    storm_hip_matrix_s all, m;   // views into the scratch (never destroyed)
+};
+static int dosage_interleave_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* x, uint64_t n_samples, DosageInterleaved* out) {
+    const uint64_t n = x->n_rows, stride = x->stride_words;
+    const uint64_t rows128 = (3 * n + kThTile - 1) / kThTile * kThTile, rows_out = rows128 + 2;
+    if (rows_out > 0x7fffffffu) {
+        set_error("dosage rows with missing genotypes: %llu rows exceed the split's launch grid", (unsigned long long)n);
+        return STORM_HIP_EINVAL;
+    }
+    if (int rc = ctx->d_dosage_rows.ensure(rows_out * stride * sizeof(uint64_t),
+                                           "dosage rows with missing genotypes: the interleaved operand G, H, M"))
+        return rc;
+    uint64_t* const T = ctx->d_dosage_rows.d;
+    hipLaunchKernelGGL(dosage_split_interleaved_kernel, dim3((uint32_t)rows_out, (uint32_t)((stride + 255u) / 256u)), dim3(256), 0,
+                       ctx->stream, x->d, stride, n, rows_out, x->n_words, n_samples, T);
+    STORM_HIP_TRY(hipGetLastError());
+    auto view = [&](uint64_t* d, uint64_t rows, uint64_t rows_pad, uint64_t stride_words) {
+        storm_hip_matrix_s v;
+        v.d = d;
+        v.n_rows = rows;
+        v.n_rows_pad = rows_pad;
+        v.n_words = x->n_words;
+        v.stride_words = stride_words;
+        return v;
+    };
+    out->all = view(T, 3 * n, rows128, stride);
+    out->m = view(T + 2 * stride, n, n, 3 * stride);
+    return STORM_HIP_OK;
+}
+
+// N(i, i + 1 + d) in the lag layout at d_out (pitch ld): the split, then the lag form on the M rows. Queued.
+static int lag_dosage_nobs_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint64_t n_samples, uint64_t max_lag,
+                                  uint32_t* d_out, uint64_t ld) {
+    DosageInterleaved sp;
+    if (int rc = dosage_interleave_queued(ctx, m, n_samples, &sp)) return rc;
+    return launch_pairw_lag_dosage_matrix(ctx, &sp.m, max_lag, 0, m->n_rows, d_out, ld, false);
+}
+
+// The pairwise-complete correlation in the lag layout at d_out (pitch ld): the interleaved split; ONE launch of K2h in its
+// lag and dosage form over its 3 n rows at lag 3 L + 2 into ctx->d_dosage_sums — every product of G, H, M of two rows within
+// L of each other: 9 per row pair where the finish reads 6 — then the finish into d_out. Scratch: 3 n x (3 L + 2 up to the
+// next multiple of 4) uint32 of sums and 3 n rows of operands: O(n L), nothing of n^2. All queued.
+static int lag_dosage_corr_complete_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int measure, uint64_t n_samples,
+                                           uint64_t max_lag, uint32_t* d_out, uint64_t ld) {
+    const uint64_t n = m->n_rows, L = std::min<uint64_t>(max_lag, n - 1);
+    const uint64_t lag3 = 3 * L + 2, lds = (lag3 + 3u) / 4u * 4u;
+    const uint64_t tiles_x = (L + kDosLagTile - 1) / kDosLagTile, tiles_y = (n + kDosLagTile - 1) / kDosLagTile;
+    if (tiles_y > 65535u || tiles_x > 0x7fffffffu) {
+        set_error("pairw_lag_dosage_corr_complete: %llu rows exceed the finishing pass's launch grid", (unsigned long long)n);
+        return STORM_HIP_EINVAL;
+    }
+    DosageInterleaved sp;
+    if (int rc = dosage_interleave_queued(ctx, m, n_samples, &sp)) return rc;
+    if (int rc = ctx->d_dosage_sums.ensure(3 * n * lds * sizeof(uint32_t),
+                                           "pairw_lag_dosage_corr_complete: the sums of the interleaved rows within the lag"))
+        return rc;
+    if (int rc = launch_pairw_lag_dosage_matrix(ctx, &sp.all, lag3, 0, 3 * n, ctx->d_dosage_sums.d, lds, false)) return rc;
+    hipLaunchKernelGGL(dosage_complete_finish_lag_kernel, dim3((uint32_t)tiles_x, (uint32_t)tiles_y), dim3(256), 0, ctx->stream,
+                       ctx->d_dosage_sums.d, lds, d_out, ld, n, L, measure);
+    STORM_HIP_TRY(hipGetLastError());
+    ctx->pass_report[0] |= STORM_HIP_RAN_SIMILARITY;   // ([1]: the interleaved rows' pairs within 3 L + 2 x n_words)
+    return STORM_HIP_OK;
+}
+
+// the host forms: `queued` writes the n x L matrix into the band buffer (0 in the corner), which then goes to h_out
+template <typename Queued>
+static int lag_dosage_to_host(storm_hip_ctx_t* ctx, const char* what, uint64_t n, uint64_t lag, void* h_out, uint64_t ld,
+                              Queued queued) {
+    STORM_HIP_TRY(hipSetDevice(ctx->device));
+    const size_t need = (size_t)n * lag * sizeof(uint32_t);
+    if (int rc = ctx->d_band.ensure(need, what)) return rc;
+    STORM_HIP_TRY(hipMemsetAsync(ctx->d_band, 0, need, ctx->stream));   // (the lower-right corner: +0.0f is the same zero bits)
+    if (int rc = queued(ctx->d_band.d, lag)) return rc;
+    STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(uint32_t), ctx->d_band, lag * sizeof(uint32_t), lag * sizeof(uint32_t), n,
+                                   hipMemcpyDeviceToHost, ctx->stream));
+    STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
     return STORM_HIP_OK;
 }
 
@@ -538,6 +810,146 @@ int storm_hip_pairw_dosage_corr_complete(storm_hip_ctx_t* ctx, const storm_hip_m
                                        hipMemcpyDeviceToHost, ctx->stream));
         STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
         return STORM_HIP_OK;
+    });
+}
+
+// ---- the lag layout ----
+int storm_hip_pairw_lag_dosage_matrix_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t max_lag, uint64_t row0,
+                                             uint64_t n_band_rows, uint32_t* d_out, uint64_t ld) {
+    return guarded("storm_hip_pairw_lag_dosage_matrix_device", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        uint64_t lag = 0;
+        if (int rc = check_lag_dosage("pairw_lag_dosage_matrix", m, d_out, max_lag, ld, &lag)) return rc;
+        if (n_band_rows == ~0ull && row0 <= m->n_rows) n_band_rows = m->n_rows - row0;
+        if (row0 > m->n_rows || n_band_rows > m->n_rows - row0) {
+            set_error("pairw_lag_dosage_matrix: a band outside the rows");
+            return STORM_HIP_EINVAL;
+        }
+        if (m->n_rows < 2 || n_band_rows == 0) return STORM_HIP_OK;
+        STORM_HIP_TRY(hipSetDevice(ctx->device));
+        return launch_pairw_lag_dosage_matrix(ctx, m, max_lag, row0, n_band_rows, d_out, ld, true);
+    });
+}
+
+int storm_hip_pairw_lag_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t max_lag, uint32_t* h_out,
+                                      uint64_t ld) {
+    return guarded("storm_hip_pairw_lag_dosage_matrix", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        uint64_t lag = 0;
+        if (int rc = check_lag_dosage("pairw_lag_dosage_matrix", m, h_out, max_lag, ld, &lag)) return rc;
+        const uint64_t n = m->n_rows;
+        if (n < 2) return STORM_HIP_OK;
+        return lag_dosage_to_host(ctx, "pairw_lag_dosage_matrix: the output", n, lag, h_out, ld, [&](uint32_t* d, uint64_t d_ld) {
+            return launch_pairw_lag_dosage_matrix(ctx, m, max_lag, 0, n, d, d_ld, false);
+        });
+    });
+}
+
+int storm_hip_dosage_finish_lag_device(storm_hip_ctx_t* ctx, void* d_io, uint64_t ld, uint64_t n_rows, uint64_t row0,
+                                       uint64_t n_band_rows, uint64_t max_lag, const uint32_t* d_sum, const uint32_t* d_sum_sq,
+                                       int measure, uint64_t n_samples) {
+    return guarded("storm_hip_dosage_finish_lag_device", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        if (int rc = launch_dosage_finish_lag(ctx, d_io, ld, n_rows, row0, n_band_rows, max_lag, d_sum, d_sum_sq, measure, n_samples))
+            return rc;
+        // (alone on a caller's matrix: a report of its own, as storm_hip_similarity_finish_lag_device; nothing launched: as it was)
+        if (n_rows >= 2 && n_band_rows != 0 && row0 < n_rows) {
+            memset(ctx->pass_report, 0, sizeof(ctx->pass_report));
+            ctx->pass_report[0] = STORM_HIP_RAN_SIMILARITY;
+        }
+        return STORM_HIP_OK;
+    });
+}
+
+int storm_hip_pairw_lag_dosage_corr_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_samples,
+                                           uint64_t max_lag, float* d_out, uint64_t ld) {
+    return guarded("storm_hip_pairw_lag_dosage_corr_device", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        uint64_t lag = 0;
+        if (int rc = check_lag_dosage("pairw_lag_dosage_corr", m, d_out, max_lag, ld, &lag)) return rc;
+        if (int rc = check_corr("pairw_lag_dosage_corr", m, measure, n_samples)) return rc;
+        if (m->n_rows < 2) return STORM_HIP_OK;
+        STORM_HIP_TRY(hipSetDevice(ctx->device));
+        if (int rc = lag_dosage_corr_queued(ctx, m, measure, n_samples, max_lag, reinterpret_cast<uint32_t*>(d_out), ld)) return rc;
+        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return STORM_HIP_OK;
+    });
+}
+
+int storm_hip_pairw_lag_dosage_corr(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_samples,
+                                    uint64_t max_lag, float* h_out, uint64_t ld) {
+    return guarded("storm_hip_pairw_lag_dosage_corr", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        uint64_t lag = 0;
+        if (int rc = check_lag_dosage("pairw_lag_dosage_corr", m, h_out, max_lag, ld, &lag)) return rc;
+        if (int rc = check_corr("pairw_lag_dosage_corr", m, measure, n_samples)) return rc;
+        const uint64_t n = m->n_rows;
+        if (n < 2) return STORM_HIP_OK;
+        return lag_dosage_to_host(ctx, "pairw_lag_dosage_corr: the output", n, lag, h_out, ld, [&](uint32_t* d, uint64_t d_ld) {
+            return lag_dosage_corr_queued(ctx, m, measure, n_samples, max_lag, d, d_ld);
+        });
+    });
+}
+
+int storm_hip_pairw_lag_dosage_nobs_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint64_t max_lag,
+                                           uint32_t* d_out, uint64_t ld) {
+    return guarded("storm_hip_pairw_lag_dosage_nobs_device", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        uint64_t lag = 0;
+        if (int rc = check_lag_dosage("pairw_lag_dosage_nobs", m, d_out, max_lag, ld, &lag)) return rc;
+        if (int rc = check_samples("pairw_lag_dosage_nobs", m, n_samples)) return rc;
+        if (m->n_rows < 2) return STORM_HIP_OK;
+        STORM_HIP_TRY(hipSetDevice(ctx->device));
+        if (int rc = lag_dosage_nobs_queued(ctx, m, n_samples, max_lag, d_out, ld)) return rc;
+        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return STORM_HIP_OK;
+    });
+}
+
+int storm_hip_pairw_lag_dosage_nobs(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint64_t max_lag,
+                                    uint32_t* h_out, uint64_t ld) {
+    return guarded("storm_hip_pairw_lag_dosage_nobs", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        uint64_t lag = 0;
+        if (int rc = check_lag_dosage("pairw_lag_dosage_nobs", m, h_out, max_lag, ld, &lag)) return rc;
+        if (int rc = check_samples("pairw_lag_dosage_nobs", m, n_samples)) return rc;
+        const uint64_t n = m->n_rows;
+        if (n < 2) return STORM_HIP_OK;
+        return lag_dosage_to_host(ctx, "pairw_lag_dosage_nobs: the output", n, lag, h_out, ld, [&](uint32_t* d, uint64_t d_ld) {
+            return lag_dosage_nobs_queued(ctx, m, n_samples, max_lag, d, d_ld);
+        });
+    });
+}
+
+int storm_hip_pairw_lag_dosage_corr_complete_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure,
+                                                    uint64_t n_samples, uint64_t max_lag, float* d_out, uint64_t ld) {
+    return guarded("storm_hip_pairw_lag_dosage_corr_complete_device", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        uint64_t lag = 0;
+        if (int rc = check_lag_dosage("pairw_lag_dosage_corr_complete", m, d_out, max_lag, ld, &lag)) return rc;
+        if (int rc = check_corr("pairw_lag_dosage_corr_complete", m, measure, n_samples)) return rc;
+        if (m->n_rows < 2) return STORM_HIP_OK;
+        STORM_HIP_TRY(hipSetDevice(ctx->device));
+        if (int rc = lag_dosage_corr_complete_queued(ctx, m, measure, n_samples, max_lag, reinterpret_cast<uint32_t*>(d_out), ld))
+            return rc;
+        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return STORM_HIP_OK;
+    });
+}
+
+int storm_hip_pairw_lag_dosage_corr_complete(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_samples,
+                                             uint64_t max_lag, float* h_out, uint64_t ld) {
+    return guarded("storm_hip_pairw_lag_dosage_corr_complete", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        uint64_t lag = 0;
+        if (int rc = check_lag_dosage("pairw_lag_dosage_corr_complete", m, h_out, max_lag, ld, &lag)) return rc;
+        if (int rc = check_corr("pairw_lag_dosage_corr_complete", m, measure, n_samples)) return rc;
+        const uint64_t n = m->n_rows;
+        if (n < 2) return STORM_HIP_OK;
+        return lag_dosage_to_host(ctx, "pairw_lag_dosage_corr_complete: the output", n, lag, h_out, ld,
+                                  [&](uint32_t* d, uint64_t d_ld) {
+                                      return lag_dosage_corr_complete_queued(ctx, m, measure, n_samples, max_lag, d, d_ld);
+                                  });
     });
 }
 

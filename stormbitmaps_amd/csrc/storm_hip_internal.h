@@ -283,6 +283,9 @@ int launch_pairw_lag_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, i
                             uint64_t band_rows, uint32_t* d_out, uint64_t ld, bool sync);
 // the dot products of rows of 2-bit values, upper triangle (K2h in its dosage form; storm_hip_dosage.hip finishes them)
 int launch_pairw_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint32_t* d_out, uint64_t ld, bool sync);
+// ... for the pairs within max_lag rows of each other, in the lag layout (K2h in its lag and dosage form)
+int launch_pairw_lag_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint64_t max_lag, uint64_t band_row0,
+                                   uint64_t band_rows, uint32_t* d_out, uint64_t ld, bool sync);
 // the rectangle of two such matrices: every row of A against every row of B (K2h in its dosage form, rectangle)
 int launch_square_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, uint32_t* d_out,
                                 uint64_t ld, bool sync);

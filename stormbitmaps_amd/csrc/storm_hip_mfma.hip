@@ -2152,8 +2152,8 @@ static bool choose_tile128(const storm_hip_ctx_t* ctx, uint64_t tiles256, uint64
 
 // Plans the K2h list of the 128 x 128 tiles that hold a pair of the window (plan_tile128, storm_hip_plan.cpp; cached by its
 // request while the same call repeats), uploads it and launches tile128_kernel in the window's form over total_stages
-// 128-bit stages of k. value_bits = 2 (triangle or rectangle, no row counts): the rows hold 2-bit values and the kernel
-// writes their dot products (tile128_kernel<false, 2>); the list is planned with a chunk's weight of 9 x 256.
+// 128-bit stages of k. value_bits = 2 (any form, no row counts): the rows hold 2-bit values and the kernel writes their
+// dot products (tile128_kernel<false, 2>, or <true, 2> in the lag form); the list is planned with a chunk's weight of 9 x 256.
 static int run_tile128(storm_hip_ctx_t* ctx, uint32_t total_stages, const TileOperands& ops, const OutWindow& w, bool sync,
                        uint32_t value_bits) {
     const uint32_t lag = w.form == OutForm::Lag ? w.lag : 0u;
@@ -2192,7 +2192,10 @@ static int run_tile128(storm_hip_ctx_t* ctx, uint32_t total_stages, const TileOp
         ctx->tickets_dirty = false;
     }
     const PartItem* d_items = static_cast<const PartItem*>(ctx->d_items.d);
-    if (ctx->n_part_items && w.form == OutForm::Lag)
+    if (ctx->n_part_items && w.form == OutForm::Lag && value_bits == 2u)
+        hipLaunchKernelGGL((tile128_kernel<true, 2>), dim3(ctx->n_part_items), dim3(kThThreads), 0, ctx->stream, ops, d_items, w,
+                           ctx->d_parts, ctx->d_tickets);
+    else if (ctx->n_part_items && w.form == OutForm::Lag)
         hipLaunchKernelGGL(tile128_kernel<true>, dim3(ctx->n_part_items), dim3(kThThreads), 0, ctx->stream, ops, d_items, w,
                            ctx->d_parts, ctx->d_tickets);
     else if (ctx->n_part_items && value_bits == 2u)
@@ -2338,6 +2341,30 @@ int launch_pairw_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m
     const int rc = run_tile128(ctx, (m->n_words + 7u) / 8u * 4u, operands_of(m->d, pitch, m->n_rows_pad),
                                triangle_window(d_out, ld, 0, n, n, nullptr, STORM_HIP_OP_AND), sync, 2u);
     if (rc == STORM_HIP_EHIP) set_error("pairw_dosage_matrix: HIP failure");
+    return rc;
+}
+
+// The dot products of rows of 2-bit values for the pairs within max_lag rows of each other, in the lag layout
+// (storm_hip_pairw_lag_dosage_matrix_device): out[(i - band_row0) * ld + (j - i - 1)] = sum_s v_i[s] v_j[s] for the band's
+// rows i, i < j < n_rows, j - i <= L = min(max_lag, n_rows - 1). launch_pairw_lag_matrix on 2-bit values: K2h in its lag
+// and dosage form (tile128_kernel<true, 2>), no row counts.
+int launch_pairw_lag_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint64_t max_lag, uint64_t band_row0,
+                                   uint64_t band_rows, uint32_t* d_out, uint64_t ld, bool sync) {
+    const uint64_t n = m->n_rows;
+    const uint64_t band_end = std::min<uint64_t>(n, band_row0 + std::min<uint64_t>(band_rows, n));
+    if (n < 2 || band_row0 >= band_end || max_lag == 0) return STORM_HIP_OK;
+    const uint64_t L = std::min<uint64_t>(max_lag, n - 1);
+    const uint64_t pitch = m->stride_words * 8;
+    if (int rc = check_tile_limits("pairw_lag_dosage_matrix", pitch, kThTile, (n + kThTile - 1) / kThTile, true)) return rc;
+    auto pairs_below = [&](uint64_t r) {   // the pairs within the lag of the rows [0, r): launch_pairw_lag_matrix's count
+        const uint64_t full = std::min(r, n - L), rest = r - full;
+        return full * L + rest * L - rest * (rest + 1) / 2;
+    };
+    ctx->k2_tile_shape_eff = 7;
+    report_tiles_out(ctx, (pairs_below(band_end) - pairs_below(band_row0)) * m->n_words);
+    const int rc = run_tile128(ctx, (m->n_words + 7u) / 8u * 4u, operands_of(m->d, pitch, m->n_rows_pad),
+                               lag_window(d_out, ld, band_row0, band_end, n, L, nullptr, STORM_HIP_OP_AND), sync, 2u);
+    if (rc == STORM_HIP_EHIP) set_error("pairw_lag_dosage_matrix: HIP failure");
     return rc;
 }
 

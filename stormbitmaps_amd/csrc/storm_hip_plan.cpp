@@ -1360,6 +1360,32 @@ extern "C" int storm_hip_lag_plan(uint64_t n_rows, uint32_t n_words, uint64_t ma
     }
 }
 
+// The K2h list of the dosage form in the lag layout (launch_pairw_lag_dosage_matrix): storm_hip_lag_plan's tiles, planned
+// with a chunk's weight of 9 x 256 like storm_hip_dosage_plan's.
+extern "C" int storm_hip_lag_dosage_plan(uint64_t n_rows, uint32_t n_words, uint64_t max_lag, uint64_t band_row0,
+                                         uint64_t band_rows, uint32_t n_cus, int slots_per_cu, int min_chunks, int diag_cost_pct,
+                                         uint32_t* out, uint64_t capacity_items, uint64_t* n_items) {
+    using namespace storm;
+    if (!n_items || n_rows == 0 || n_words == 0 || max_lag == 0 || n_cus == 0 || slots_per_cu < 0 || slots_per_cu > 2 ||
+        min_chunks < 1 || diag_cost_pct < 10 || diag_cost_pct > 100 || (n_rows + kThTile - 1) / kThTile > 65535u) {
+        set_error("lag_dosage_plan: bad arguments");
+        return STORM_HIP_EINVAL;
+    }
+    try {
+        Tile128Plan plan;
+        const uint64_t end = std::min(n_rows, band_row0 + std::min(band_rows ? band_rows : n_rows, n_rows));
+        const uint32_t lag = (uint32_t)std::min<uint64_t>(max_lag, n_rows - 1);
+        if (band_row0 < end && lag)
+            plan_tile128({(uint32_t)(band_row0 / kThTile), (uint32_t)((end + kThTile - 1) / kThTile), 0u,
+                          (uint32_t)((n_rows + kThTile - 1) / kThTile), 1u, (n_words + 7u) / 8u * 4u, n_cus, slots_per_cu,
+                          min_chunks, diag_cost_pct, 1u, lag, kThWeightDosage}, &plan);
+        return export_part_items("lag_dosage_plan", plan, out, capacity_items, n_items);
+    } catch (const std::exception& e) {
+        set_error("lag_dosage_plan: %s", e.what());
+        return STORM_HIP_ENOMEM;
+    }
+}
+
 extern "C" int storm_hip_strip_plan3(uint64_t n_rows, uint32_t n_words, uint32_t shard_rank,
                                      uint32_t shard_count, int form, int pair_space, int max_run, int tail_run,
                                      int tail_slices, int lpt_rounds, uint32_t n_cus, uint32_t* out,

@@ -47,8 +47,8 @@ constexpr uint32_t kThWindowWords = kThTile * kThTile;   // a part's window: 64 
 // read as E2M1 are 0, 0.5, 1.0, 1.5: linear in the value. So there are two classes per piece instead of four — class 0:
 // w & 0x33333333, class 1: (w >> 2) & 0x33333333 — and block scale 128 (x 2) on both operands of both makes the operand
 // the value itself; 16 multiply steps per trip instead of 32. A chunk (256 values) adds up to 9 x 256 = 2304 to an
-// accumulator: the host plans the k-parts and the narrow windows by that weight (plan_tile128, chunk_weight). Triangle
-// only, row_counts null.
+// accumulator: the host plans the k-parts and the narrow windows by that weight (plan_tile128, chunk_weight). Every output
+// form (kLag too: the lag dispatch and the per-element epilogue do not ask what a word holds), row_counts null.
 template <int C>
 __device__ __forceinline__ v4i th_inflate2(v4i w) {
     typedef unsigned v4u __attribute__((ext_vector_type(4)));
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(kThThreads, 2) void tile128_kernel(
     const OutWindow w = window.loaded();
     __shared__ __attribute__((aligned(1024))) uint8_t lds[kThRing * kThSlotBytes];
     __shared__ uint32_t ticket_seen;
-    static_assert(kBits == 1 || (kBits == 2 && !kLag), "bits, or 2-bit values in the triangle form");
+    static_assert(kBits == 1 || kBits == 2, "bits, or 2-bit values");
     constexpr int kClasses = kBits == 1 ? 4 : 2;   // multiply steps per piece
     STORM_CLOCK_BEGIN();
 

@@ -195,6 +195,26 @@ def lag_plan(n_rows: int, n_words: int, max_lag: int, band_row0: int = 0, band_r
     return out
 
 
+def lag_dosage_plan(n_rows: int, n_words: int, max_lag: int, band_row0: int = 0, band_rows: int = 0, n_cus: int = 256,
+                    slots_per_cu: int = 0, min_chunks: int = 8, diag_cost_pct: int = 80):
+    """The items of the lag layout's launch in the dosage form (rows of n_words words of 2-bit values: lag_plan's tiles under
+    dosage_plan's weight of 9 x 256 a chunk; storm_hip_lag_dosage_plan in include/storm_hip.h). Host-only."""
+    import ctypes as C
+
+    import numpy as np
+
+    from . import _lib
+    lib = _lib.load()
+    n = C.c_uint64(0)
+    args = (n_rows, n_words, max_lag, band_row0, band_rows, n_cus, slots_per_cu, min_chunks, diag_cost_pct)
+    _lib.check(lib.storm_hip_lag_dosage_plan(*args, None, 0, C.byref(n)), "storm_hip_lag_dosage_plan")
+    out = np.zeros((int(n.value), 8), dtype=np.uint32)
+    if n.value:
+        _lib.check(lib.storm_hip_lag_dosage_plan(*args, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)),
+                   "storm_hip_lag_dosage_plan")
+    return out
+
+
 def allreduce_total(partial: int, device=None) -> int:
     """Sum the per-rank partial totals. Totals are < 2^63 for every supported shape
     (N^2/2 * M < 2^63), so the int64 transport is exact."""
