@@ -472,6 +472,37 @@ int STORM_dosage_pairw_lag_corr_complete(STORM_dosage_t* h, int measure, uint64_
 int STORM_dosage_pairw_lag_corr_complete_device(STORM_dosage_t* h, int measure, uint64_t max_lag, float* d_out, uint64_t out_rows,
                                                 uint64_t out_ld);
 
+/* Per-variant LD scores — the input of LD-score regression — from the rows within max_lag on BOTH sides of every row, reduced
+ * on the device: n floats leave it instead of the n x L matrix of STORM_dosage_pairw_lag_corr. With n the rows held and
+ * L = min(max_lag, n - 1), row i's neighbours are the rows j with 1 <= |i - j| <= L. For a pair (i, j) let rho be the FLOAT
+ * that STORM_dosage_pairw_lag_corr writes for it under STORM_DOSAGE_R2 (the _complete calls: the float of
+ * STORM_dosage_pairw_lag_corr_complete, 3 = STORM_DOSAGE_MISSING), widened to double. The pair's term t is
+ *   STORM_LDSCORE_R2      t = rho
+ *   STORM_LDSCORE_R2_ADJ  t = rho - (1 - rho) / (N - 2) in double, the small-sample correction of LDSC; N is the container's
+ *                         n_samples, and in the _complete calls N(i, j), the samples both rows have (what
+ *                         STORM_dosage_pairw_lag_nobs returns)
+ * and a pair is NOT summed when rho is NaN (a constant row; _complete: no variance on the shared samples) or when stat is
+ * _ADJ and N < 3. Then
+ *   score[i]   = the sum of the terms of row i's summed pairs, accumulated in double, rounded once to float; +0.0f when no
+ *                pair is summed. The variant itself is not included: LDSC's l_i is 1 + score[i].
+ *   n_pairs[i] = the number of pairs summed (n_pairs may be NULL).
+ * Exactly elements [0, n) of either output are written (out_len >= n is the length of both), in host memory or, for the
+ * _device forms, in device memory (complete on return); nothing behind n is touched. Two calls on unchanged rows return identical bits: the
+ * additions have one fixed order, no floating-point atomics. Device scratch: the n x L floats of r^2 and the scratch of
+ * the corr call beneath. No CPU fallback. One device slot and one process.
+ * Returns 0; -1 NULL handle, -2 NULL score, -3 max_lag 0 (said before the size check, even on an empty container), -4
+ * out_len < n (nothing is written), -3 an unknown stat (before any device is asked for), _ADJ with n_samples < 3, or a
+ * device failure (STORM_hip_error says which), -5 several device slots in view. Fewer than two rows: 0, nothing written. */
+#define STORM_LDSCORE_R2 0
+#define STORM_LDSCORE_R2_ADJ 1
+int STORM_dosage_lag_ldscore(STORM_dosage_t* h, int stat, uint64_t max_lag, float* score, uint32_t* n_pairs, uint64_t out_len);
+int STORM_dosage_lag_ldscore_device(STORM_dosage_t* h, int stat, uint64_t max_lag, float* d_score, uint32_t* d_n_pairs,
+                                    uint64_t out_len);
+int STORM_dosage_lag_ldscore_complete(STORM_dosage_t* h, int stat, uint64_t max_lag, float* score, uint32_t* n_pairs,
+                                      uint64_t out_len);
+int STORM_dosage_lag_ldscore_complete_device(STORM_dosage_t* h, int stat, uint64_t max_lag, float* d_score, uint32_t* d_n_pairs,
+                                             uint64_t out_len);
+
 /* ------------------------------------------------------------- extensions (not in ref) ---
  * Device selection for the entry points above. By default device 0 computes everything.
  * STORM_hip_set_devices(n, ids): the pair space is sharded over the listed GPUs of this node

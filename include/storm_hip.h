@@ -432,6 +432,45 @@ int storm_hip_pairw_lag_dosage_corr_complete_device(storm_hip_ctx_t* ctx, const 
 int storm_hip_pairw_lag_dosage_corr_complete(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_samples,
                                              uint64_t max_lag, float* h_out, uint64_t ld);
 
+/* ---- LD scores: per-row sums over both sides of a band in the lag layout, reduced on the device --------------------
+ * storm_hip_lag_band_sums_device: d_vals is any float matrix in the lag layout in DEVICE memory (n_rows rows of pitch ld,
+ *   the pair (i, i + 1 + d) at d_vals[i * ld + d], L = min(max_lag, n_rows - 1), ld >= L). For every row i,
+ *     d_score[i]   = the sum of the terms of the pairs (i, j), 1 <= |i - j| <= L, accumulated in double, rounded once to
+ *                    float (+0.0f when no pair is summed),
+ *     d_n_pairs[i] = how many pairs were summed (may be NULL),
+ *   where a pair's term is its float widened to double (stat STORM_HIP_LDSCORE_R2) or rho - (1 - rho) / (N - 2) in double
+ *   (STORM_HIP_LDSCORE_R2_ADJ), and a pair is NOT summed when its float is NaN or, under _ADJ, N < 3. N is n_const, or,
+ *   with d_nobs not NULL, the uint32 at d_nobs[i * nobs_row_pitch + d * nobs_col_stride] of the pair's entry (i, d).
+ *   Exactly elements [0, n_rows) of the outputs are written. The lower-right corner (i + 1 + d >= n_rows) and the pitch
+ *   columns [L, ld) of d_vals — and the same places of d_nobs — are never read. lag_band_sums_kernel: one workgroup per
+ *   64 rows, every entry read twice (once for either row of its pair), no atomics and no clearing launch: the order of the
+ *   additions is fixed, two calls on the same band return the same bits. Queued on the context's stream; no host wait.
+ *   The LD r^2 of storm_hip_pairw_lag_similarity_device goes through the same call with n_const = n_bits.
+ * storm_hip_lag_dosage_ldscore[_device]: rows of 2-bit dosages: storm_hip_pairw_lag_dosage_corr's r^2 into the context's
+ *   band buffer (n x L floats of device scratch, beside that call's own), then the reduction with n_const = n_samples.
+ * storm_hip_lag_dosage_ldscore_complete[_device]: the same over storm_hip_pairw_lag_dosage_corr_complete's r^2 (value 3 =
+ *   missing); under _ADJ N(i, j) is read from that call's scratch matrix of sums, where it already lies: the nobs form is
+ *   not launched again.
+ *   The _device forms write d_score / d_n_pairs in DEVICE memory and return with everything queued on the context's
+ *   stream; the host forms copy 2 n words back and wait.
+ *   NOTE: unlike storm_hip_pairw_lag_dosage_*_device above, which are complete on return, these _device forms (and
+ *   storm_hip_lag_band_sums_device) do NOT wait: order later work on the context's stream, or call storm_hip_ctx_synchronize. Sums are over the neighbours only: LDSC's l_i is 1 + score[i].
+ * STORM_HIP_EINVAL: NULL context, matrix, band or score, unknown stat, max_lag 0, ld < L, n_samples that does not match the
+ * row width, rows of more than 2^24 values. Fewer than two rows: STORM_HIP_OK, nothing written. */
+#define STORM_HIP_LDSCORE_R2 0
+#define STORM_HIP_LDSCORE_R2_ADJ 1
+int storm_hip_lag_band_sums_device(storm_hip_ctx_t* ctx, const float* d_vals, uint64_t ld, uint64_t n_rows, uint64_t max_lag,
+                                   int stat, uint64_t n_const, const uint32_t* d_nobs, uint64_t nobs_row_pitch,
+                                   uint64_t nobs_col_stride, float* d_score, uint32_t* d_n_pairs);
+int storm_hip_lag_dosage_ldscore_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int stat, uint64_t n_samples,
+                                        uint64_t max_lag, float* d_score, uint32_t* d_n_pairs);
+int storm_hip_lag_dosage_ldscore(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int stat, uint64_t n_samples, uint64_t max_lag,
+                                 float* h_score, uint32_t* h_n_pairs);
+int storm_hip_lag_dosage_ldscore_complete_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int stat, uint64_t n_samples,
+                                                 uint64_t max_lag, float* d_score, uint32_t* d_n_pairs);
+int storm_hip_lag_dosage_ldscore_complete(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int stat, uint64_t n_samples,
+                                          uint64_t max_lag, float* h_score, uint32_t* h_n_pairs);
+
 /* sum_c C(n_c,2) on the device — verification identity only, never the product
  * path: used by tests at sizes where a CPU pairwise oracle is infeasible */
 int storm_hip_column_identity(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m,

@@ -153,6 +153,11 @@ SIGNATURES = {
     "storm_hip_pairw_lag_dosage_nobs": (C.c_int, [vp, vp, u64, u64, vp, u64]),
     "storm_hip_pairw_lag_dosage_corr_complete_device": (C.c_int, [vp, vp, C.c_int, u64, u64, vp, u64]),
     "storm_hip_pairw_lag_dosage_corr_complete": (C.c_int, [vp, vp, C.c_int, u64, u64, vp, u64]),
+    "storm_hip_lag_band_sums_device": (C.c_int, [vp, vp, u64, u64, u64, C.c_int, u64, vp, u64, u64, vp, vp]),
+    "storm_hip_lag_dosage_ldscore_device": (C.c_int, [vp, vp, C.c_int, u64, u64, vp, vp]),
+    "storm_hip_lag_dosage_ldscore": (C.c_int, [vp, vp, C.c_int, u64, u64, vp, vp]),
+    "storm_hip_lag_dosage_ldscore_complete_device": (C.c_int, [vp, vp, C.c_int, u64, u64, vp, vp]),
+    "storm_hip_lag_dosage_ldscore_complete": (C.c_int, [vp, vp, C.c_int, u64, u64, vp, vp]),
     "storm_hip_matrix_create_from_blocks_wide": (C.c_int, [vp, u64, u64, vp, vp, vp, vp, vp, u32, P(vp)]),
     "storm_hip_pairw_sparse_begin": (C.c_int, [vp, vp, u32, u32]),
     "storm_hip_pairw_sparse_end": (C.c_int, [vp, P(u64)]),
@@ -245,6 +250,10 @@ SIGNATURES = {
     "STORM_dosage_pairw_lag_nobs_device": (C.c_int, [vp, u64, vp, u64, u64]),
     "STORM_dosage_pairw_lag_corr_complete": (C.c_int, [vp, C.c_int, u64, vp, u64, u64]),
     "STORM_dosage_pairw_lag_corr_complete_device": (C.c_int, [vp, C.c_int, u64, vp, u64, u64]),
+    "STORM_dosage_lag_ldscore": (C.c_int, [vp, C.c_int, u64, vp, vp, u64]),
+    "STORM_dosage_lag_ldscore_device": (C.c_int, [vp, C.c_int, u64, vp, vp, u64]),
+    "STORM_dosage_lag_ldscore_complete": (C.c_int, [vp, C.c_int, u64, vp, vp, u64]),
+    "STORM_dosage_lag_ldscore_complete_device": (C.c_int, [vp, C.c_int, u64, vp, vp, u64]),
     "STORM_hip_set_option": (C.c_int, [C.c_char_p, C.c_int64]),
     "STORM_contig_pairw_matrix_device": (C.c_int, [vp, C.c_int, vp, u64, u64]),
     "STORM_serialize": (u64, [vp, vp, u64]),

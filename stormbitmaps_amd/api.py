@@ -221,6 +221,7 @@ class StormContig(_LagForms, _TopkForms):
 
 
 DOSAGE_MEASURES = {"r2": 0, "r": 1}  # STORM_DOSAGE_* (storm.h)
+LDSCORE_STATS = {"r2": 0, "r2_adj": 1}  # STORM_LDSCORE_* (storm.h)
 
 
 def _device_window(device, n: int):
@@ -399,6 +400,31 @@ class StormDosage:
         """STORM_dosage_pairw_lag_corr_complete: [n_rows, L] float32, pairw_corr_complete's value (the same bits) of rows i and
         i + 1 + d (value 3 = missing); memory and work are O(n_rows x L)."""
         return self._pairw_lag("STORM_dosage_pairw_lag_corr_complete", np.float32, max_lag, device, DOSAGE_MEASURES[measure])
+
+    def lag_ldscore(self, max_lag: int, stat: str = "r2", complete: bool = False, device=None):
+        """STORM_dosage_lag_ldscore[_complete]: (score [n_rows] float32, n_pairs [n_rows] uint32): for every row the sum, reduced
+        on the device, of r2 ("r2") or of r2 - (1 - r2) / (N - 2) ("r2_adj") over the rows within max_lag on both sides of it,
+        and the number of pairs summed (a NaN pair is not; under "r2_adj" neither is one with N < 3). complete=True: r2 over the
+        samples both rows have (value 3 = missing), N = their number. The row itself is not included: LDSC's l is 1 + score.
+        device=: (score, n_pairs) — two 1-D torch tensors of 32-bit entries in device memory, at least n_rows long (n_pairs
+        may be None) — receive elements [0, n_rows) instead (complete on return); returns None then."""
+        n = self.n_rows
+        name = "STORM_dosage_lag_ldscore_complete" if complete else "STORM_dosage_lag_ldscore"
+        code = LDSCORE_STATS[stat]
+        if device is not None:
+            d_score, d_pairs = device
+            for t in (d_score, d_pairs):
+                if t is not None and (t.dim() != 1 or t.element_size() != 4 or t.stride(0) != 1 or not t.is_cuda):
+                    raise ValueError("device=: 1-D contiguous tensors of 32-bit entries in device memory")
+            length = int(d_score.shape[0]) if d_pairs is None else min(int(d_score.shape[0]), int(d_pairs.shape[0]))
+            self._check(name + "_device",
+                        int(getattr(self._lib, name + "_device")(self._h, code, max_lag, C.c_void_p(d_score.data_ptr()),
+                                                                 None if d_pairs is None else C.c_void_p(d_pairs.data_ptr()),
+                                                                 length)))
+            return None
+        score, pairs = np.zeros(max(n, 1), dtype=np.float32), np.zeros(max(n, 1), dtype=np.uint32)
+        self._check(name, int(getattr(self._lib, name)(self._h, code, max_lag, _ptr(score), _ptr(pairs), n)))
+        return score[:n], pairs[:n]
 
     def free(self) -> None:
         if self._h:
@@ -669,6 +695,18 @@ class HipContext:
         return {"kernels": [n for b, n in names.items() if out[0] & b], "dense_word_pairs": int(out[1]),
                 "probe_lookups": int(out[2]), "rows_per_lookup": int(out[3])}
 
+    def lag_band_sums_device(self, d_vals: int, ld: int, n_rows: int, max_lag: int, d_score: int, d_n_pairs: Optional[int] = None,
+                             stat: str = "r2", n_const: int = 0, d_nobs: Optional[int] = None, nobs_row_pitch: int = 0,
+                             nobs_col_stride: int = 1) -> None:
+        """storm_hip_lag_band_sums_device: per-row sums over both sides of a float band in the lag layout at d_vals (n_rows rows
+        of pitch ld, device memory) into d_score / d_n_pairs (n_rows entries each, device memory); N of "r2_adj" is n_const
+        or the uint32 at d_nobs[i * nobs_row_pitch + d * nobs_col_stride]. Queued on the context's stream."""
+        check(self._lib.storm_hip_lag_band_sums_device(self._h, C.c_void_p(d_vals), ld, n_rows, max_lag, LDSCORE_STATS[stat], n_const,
+                                                       None if d_nobs is None else C.c_void_p(d_nobs), nobs_row_pitch,
+                                                       nobs_col_stride, C.c_void_p(d_score),
+                                                       None if d_n_pairs is None else C.c_void_p(d_n_pairs)),
+              "storm_hip_lag_band_sums_device")
+
     def matrix(self, n_rows: int, n_words: int) -> "HipMatrix":
         return HipMatrix(self, n_rows, n_words)
 
@@ -917,6 +955,23 @@ class HipMatrix:
         check(self._lib.storm_hip_pairw_lag_dosage_corr_complete_device(self.ctx._h, self._h, DOSAGE_MEASURES[measure], n_samples,
                                                                         max_lag, C.c_void_p(d_out), ld),
               "storm_hip_pairw_lag_dosage_corr_complete_device")
+
+    # ---- LD scores: per-row sums over both sides of a band in the lag layout (storm_hip.h) ----
+    def lag_dosage_ldscore(self, max_lag: int, n_samples: int, stat: str = "r2", complete: bool = False):
+        """(score [n_rows] float32, n_pairs [n_rows] uint32): the sums of r2 ("r2") or its small-sample correction ("r2_adj")
+        over the rows within max_lag on both sides of every row; complete=True: over the samples both rows have."""
+        name = "storm_hip_lag_dosage_ldscore_complete" if complete else "storm_hip_lag_dosage_ldscore"
+        n = self.n_rows
+        score, pairs = np.zeros(max(n, 1), dtype=np.float32), np.zeros(max(n, 1), dtype=np.uint32)
+        check(getattr(self._lib, name)(self.ctx._h, self._h, LDSCORE_STATS[stat], n_samples, max_lag, _ptr(score), _ptr(pairs)), name)
+        return score[:n], pairs[:n]
+
+    def lag_dosage_ldscore_device(self, d_score: int, d_n_pairs: Optional[int], max_lag: int, n_samples: int, stat: str = "r2",
+                                  complete: bool = False) -> None:
+        """Same, into device buffers of n_rows entries each (d_n_pairs may be None); queued on the context's stream."""
+        name = "storm_hip_lag_dosage_ldscore_complete_device" if complete else "storm_hip_lag_dosage_ldscore_device"
+        check(getattr(self._lib, name)(self.ctx._h, self._h, LDSCORE_STATS[stat], n_samples, max_lag, C.c_void_p(d_score),
+                                       None if d_n_pairs is None else C.c_void_p(d_n_pairs)), name)
 
     def pairw_topk(self, k: int, score: str = "jaccard", n_bits: int = 1, panel_rows: int = 0):
         """(idx [n_rows, k] uint32, val [n_rows, k] float32, or uint32 for score "count"): for each row its k best other rows,

@@ -566,6 +566,10 @@ static int lag_dosage_nobs_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s
     return launch_pairw_lag_dosage_matrix(ctx, &sp.m, max_lag, 0, m->n_rows, d_out, ld, false);
 }
 
+// The pitch of the scratch matrix of sums below (the LD-score call reads N out of it): 3 L + 2 columns up to the next
+// multiple of 4.
+static inline uint64_t lag_complete_pitch(uint64_t L) { return (3 * L + 2 + 3u) / 4u * 4u; }
+
 // The pairwise-complete correlation in the lag layout at d_out (pitch ld): the interleaved split; ONE launch of K2h in its
 // lag and dosage form over its 3 n rows at lag 3 L + 2 into ctx->d_dosage_sums — every product of G, H, M of two rows within
 // L of each other: 9 per row pair where the finish reads 6 — then the finish into d_out. Scratch: 3 n x (3 L + 2 up to the
@@ -573,7 +577,7 @@ static int lag_dosage_nobs_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s
 static int lag_dosage_corr_complete_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int measure, uint64_t n_samples,
                                            uint64_t max_lag, uint32_t* d_out, uint64_t ld) {
     const uint64_t n = m->n_rows, L = std::min<uint64_t>(max_lag, n - 1);
-    const uint64_t lag3 = 3 * L + 2, lds = (lag3 + 3u) / 4u * 4u;
+    const uint64_t lag3 = 3 * L + 2, lds = lag_complete_pitch(L);
     const uint64_t tiles_x = (L + kDosLagTile - 1) / kDosLagTile, tiles_y = (n + kDosLagTile - 1) / kDosLagTile;
     if (tiles_y > 65535u || tiles_x > 0x7fffffffu) {
         set_error("pairw_lag_dosage_corr_complete: %llu rows exceed the finishing pass's launch grid", (unsigned long long)n);
@@ -603,6 +607,43 @@ static int lag_dosage_to_host(storm_hip_ctx_t* ctx, const char* what, uint64_t n
     if (int rc = queued(ctx->d_band.d, lag)) return rc;
     STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(uint32_t), ctx->d_band, lag * sizeof(uint32_t), lag * sizeof(uint32_t), n,
                                    hipMemcpyDeviceToHost, ctx->stream));
+    STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return STORM_HIP_OK;
+}
+
+// ---- LD scores: the band of r^2 into ctx->d_band, then lag_band_sums_kernel (storm_hip_ldscore.hip) over it ----
+// Both composed calls: r^2 (complete-case or pairwise-complete) of the pairs within the lag into the first n x L floats of
+// the band buffer, the reduction over them, and for a host form 2 n words behind the band on their way back. All queued
+// on ctx->stream; the host form alone waits. For the pairwise-complete adjusted statistic N(i, d) is read where the corr
+// call left it: row 3 i + 2, column 3 d + 2 of ctx->d_dosage_sums (dosage_interleaved_entry_bits).
+static int lag_dosage_ldscore(storm_hip_ctx_t* ctx, const char* who, const storm_hip_matrix_s* m, int stat, uint64_t n_samples,
+                              uint64_t max_lag, bool complete, float* score, uint32_t* n_pairs, bool host) {
+    uint64_t lag = 0;
+    if (int rc = check_lag_dosage(who, m, score, max_lag, ~0ull, &lag)) return rc;
+    if (stat != STORM_HIP_LDSCORE_R2 && stat != STORM_HIP_LDSCORE_R2_ADJ) {
+        set_error("%s: unknown stat %d (0 r^2, 1 r^2 adjusted)", who, stat);
+        return STORM_HIP_EINVAL;
+    }
+    if (int rc = check_samples(who, m, n_samples)) return rc;
+    const uint64_t n = m->n_rows;
+    if (n < 2) return STORM_HIP_OK;
+    STORM_HIP_TRY(hipSetDevice(ctx->device));
+    const size_t band = (size_t)n * lag;
+    if (int rc = ctx->d_band.ensure((band + (host ? 2 * n : 0)) * sizeof(uint32_t), "lag_dosage_ldscore: the band of r^2")) return rc;
+    uint32_t* const d_band = ctx->d_band.d;
+    if (int rc = complete ? lag_dosage_corr_complete_queued(ctx, m, STORM_HIP_DOSAGE_R2, n_samples, max_lag, d_band, lag)
+                          : lag_dosage_corr_queued(ctx, m, STORM_HIP_DOSAGE_R2, n_samples, max_lag, d_band, lag))
+        return rc;
+    const bool view = complete && stat == STORM_HIP_LDSCORE_R2_ADJ;
+    const uint64_t lds = lag_complete_pitch(lag);
+    float* const d_score = host ? reinterpret_cast<float*>(d_band + band) : score;
+    uint32_t* const d_pairs = host ? d_band + band + n : n_pairs;
+    if (int rc = launch_lag_band_sums(ctx, reinterpret_cast<const float*>(d_band), lag, n, max_lag, stat, n_samples,
+                                      view ? ctx->d_dosage_sums.d + 2 * lds + 2 : nullptr, 3 * lds, 3, d_score, d_pairs))
+        return rc;
+    if (!host) return STORM_HIP_OK;
+    STORM_HIP_TRY(hipMemcpyAsync(score, d_score, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (n_pairs) STORM_HIP_TRY(hipMemcpyAsync(n_pairs, d_pairs, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
     return STORM_HIP_OK;
 }
@@ -950,6 +991,38 @@ int storm_hip_pairw_lag_dosage_corr_complete(storm_hip_ctx_t* ctx, const storm_h
                                   [&](uint32_t* d, uint64_t d_ld) {
                                       return lag_dosage_corr_complete_queued(ctx, m, measure, n_samples, max_lag, d, d_ld);
                                   });
+    });
+}
+
+int storm_hip_lag_dosage_ldscore_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int stat, uint64_t n_samples,
+                                        uint64_t max_lag, float* d_score, uint32_t* d_n_pairs) {
+    return guarded("storm_hip_lag_dosage_ldscore_device", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        return lag_dosage_ldscore(ctx, "lag_dosage_ldscore", m, stat, n_samples, max_lag, false, d_score, d_n_pairs, false);
+    });
+}
+
+int storm_hip_lag_dosage_ldscore(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int stat, uint64_t n_samples, uint64_t max_lag,
+                                 float* h_score, uint32_t* h_n_pairs) {
+    return guarded("storm_hip_lag_dosage_ldscore", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        return lag_dosage_ldscore(ctx, "lag_dosage_ldscore", m, stat, n_samples, max_lag, false, h_score, h_n_pairs, true);
+    });
+}
+
+int storm_hip_lag_dosage_ldscore_complete_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int stat, uint64_t n_samples,
+                                                 uint64_t max_lag, float* d_score, uint32_t* d_n_pairs) {
+    return guarded("storm_hip_lag_dosage_ldscore_complete_device", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        return lag_dosage_ldscore(ctx, "lag_dosage_ldscore_complete", m, stat, n_samples, max_lag, true, d_score, d_n_pairs, false);
+    });
+}
+
+int storm_hip_lag_dosage_ldscore_complete(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int stat, uint64_t n_samples,
+                                          uint64_t max_lag, float* h_score, uint32_t* h_n_pairs) {
+    return guarded("storm_hip_lag_dosage_ldscore_complete", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        return lag_dosage_ldscore(ctx, "lag_dosage_ldscore_complete", m, stat, n_samples, max_lag, true, h_score, h_n_pairs, true);
     });
 }
 

@@ -303,6 +303,11 @@ int launch_similarity_finish(storm_hip_ctx_t* ctx, void* d_io, uint64_t ld, uint
 // similarity_finish_lag_kernel: the same pass over the lag layout (rows [row0, row0 + n_band_rows) from output row 0)
 int launch_similarity_finish_lag(storm_hip_ctx_t* ctx, void* d_io, uint64_t ld, uint64_t n_rows, uint64_t row0,
                                  uint64_t n_band_rows, uint64_t max_lag, const uint32_t* d_counts, int measure, uint64_t n_bits);
+// lag_band_sums_kernel over a float matrix in the lag layout: per-row sums over both sides of the band, queued
+// (storm_hip_ldscore.hip; the checks of storm_hip_lag_band_sums_device)
+int launch_lag_band_sums(storm_hip_ctx_t* ctx, const float* d_vals, uint64_t ld, uint64_t n_rows, uint64_t max_lag, int stat,
+                         uint64_t n_const, const uint32_t* d_nobs, uint64_t nobs_row_pitch, uint64_t nobs_col_stride,
+                         float* d_score, uint32_t* d_n_pairs);
 void release_mfma_state(storm_hip_ctx_t* ctx);
 // releases what was put off (storm_hip_ctx_s::deferred_free); `aged`: only what an earlier call left behind
 void drain_deferred(storm_hip_ctx_t* ctx, bool aged);
