@@ -503,6 +503,53 @@ int STORM_dosage_lag_ldscore_complete(STORM_dosage_t* h, int stat, uint64_t max_
 int STORM_dosage_lag_ldscore_complete_device(STORM_dosage_t* h, int stat, uint64_t max_lag, float* d_score, uint32_t* d_n_pairs,
                                              uint64_t out_len);
 
+/* Stratified LD scores in a distance window — what `ldsc --l2 --ld-wind-cm / --ld-wind-kb --annot` computes — reduced on the
+ * device: n x n_annot floats leave it instead of the n x L matrix. With the terms t(i, j), the rule which pairs are summed
+ * and the statistics of STORM_dosage_lag_ldscore above,
+ *   score[i * score_ld + c] = the sum over row i's window W(i) of t(i, j) * annot[j * annot_ld + c], accumulated in double
+ *                             (the products are not rounded on their own), rounded once to float; +0.0f when no pair of the
+ *                             window is summed.
+ *   n_pairs[i]              = the number of pairs summed for row i (one number per row; n_pairs may be NULL).
+ * The variant itself is not summed (its r^2 is 1): LDSC's l(i, c) is annot[i][c] + score[i][c].
+ * The window W(i):
+ *   pos == NULL               the rows j with 1 <= |i - j| <= min(max_lag, n - 1); max_dist is ignored.
+ *   pos given (n doubles, HOST memory in every form, not decreasing; equal positions are allowed)
+ *                             the rows j != i with |pos[j] - pos[i]| <= max_dist (max_dist >= 0; +inf: every row). The band
+ *                             is computed at the lag the windows need, max_i max(i - lo[i], hi[i] - i)
+ *                             (STORM_ldscore_window_lag), when max_lag is 0; with max_lag > 0 the call REFUSES when the
+ *                             windows need more than max_lag rows — it never clips a window silently — and otherwise
+ *                             computes the band at max_lag.
+ *   Positions are per chromosome: make one call per chromosome, or offset the chromosomes by more than max_dist.
+ * annot: n rows of n_annot floats (1 .. STORM_LDSCORE_MAX_ANNOT), pitch annot_ld >= n_annot; score: out_rows >= n rows of
+ * pitch score_ld >= n_annot; columns [n_annot, score_ld) are not touched, columns [n_annot, annot_ld) not read. The host
+ * forms refuse an annotation that is not finite, naming the first (row, column); in the _device forms annot, score and
+ * n_pairs are DEVICE memory (complete on return) and finite annotations are the caller's obligation (a NaN or an infinity
+ * spreads over its column's window). A column has the same bits whatever other columns are passed with it, and two calls on
+ * unchanged rows return identical bits. Device work and scratch are O(n L (1 + n_annot / 64)) and O(n (L + n_annot)). No
+ * CPU fallback. One device slot and one process.
+ * Returns 0; -1 NULL handle, -2 NULL score or annot, -3 max_lag 0 without positions (said before the size check), -4
+ * out_rows < n (nothing is written), -3 an unknown stat, _ADJ with n_samples < 3, n_annot outside its range, -4 annot_ld or
+ * score_ld < n_annot, -3 a negative or NaN max_dist, a position that is not finite or decreases, windows that need more
+ * than max_lag (the message names both numbers), an annotation that is not finite (host forms), or a device failure
+ * (STORM_hip_error says which), -5 several device slots in view. Nothing is written on a refusal. Fewer than two rows: 0,
+ * nothing written.
+ * STORM_ldscore_window_lag: the lag the windows of `pos` (n doubles) need under max_dist, for sizing buffers before the
+ * call; host only. 0; -2 NULL argument; -3 the refusals of the positions and max_dist above. */
+#define STORM_LDSCORE_MAX_ANNOT 1024
+int STORM_ldscore_window_lag(const double* pos, uint64_t n, double max_dist, uint64_t* lag);
+int STORM_dosage_lag_ldscore_annot(STORM_dosage_t* h, int stat, uint64_t max_lag, const double* pos, double max_dist,
+                                   const float* annot, uint64_t n_annot, uint64_t annot_ld, float* score, uint64_t score_ld,
+                                   uint32_t* n_pairs, uint64_t out_rows);
+int STORM_dosage_lag_ldscore_annot_device(STORM_dosage_t* h, int stat, uint64_t max_lag, const double* pos, double max_dist,
+                                          const float* d_annot, uint64_t n_annot, uint64_t annot_ld, float* d_score,
+                                          uint64_t score_ld, uint32_t* d_n_pairs, uint64_t out_rows);
+int STORM_dosage_lag_ldscore_annot_complete(STORM_dosage_t* h, int stat, uint64_t max_lag, const double* pos, double max_dist,
+                                            const float* annot, uint64_t n_annot, uint64_t annot_ld, float* score, uint64_t score_ld,
+                                            uint32_t* n_pairs, uint64_t out_rows);
+int STORM_dosage_lag_ldscore_annot_complete_device(STORM_dosage_t* h, int stat, uint64_t max_lag, const double* pos, double max_dist,
+                                                   const float* d_annot, uint64_t n_annot, uint64_t annot_ld, float* d_score,
+                                                   uint64_t score_ld, uint32_t* d_n_pairs, uint64_t out_rows);
+
 /* ------------------------------------------------------------- extensions (not in ref) ---
  * Device selection for the entry points above. By default device 0 computes everything.
  * STORM_hip_set_devices(n, ids): the pair space is sharded over the listed GPUs of this node

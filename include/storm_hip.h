@@ -471,6 +471,56 @@ int storm_hip_lag_dosage_ldscore_complete_device(storm_hip_ctx_t* ctx, const sto
 int storm_hip_lag_dosage_ldscore_complete(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int stat, uint64_t n_samples,
                                           uint64_t max_lag, float* h_score, uint32_t* h_n_pairs);
 
+/* ---- stratified LD scores: the band times an annotation matrix, with a window per row ------------------------------
+ * storm_hip_lag_band_annot_sums_device: d_vals, ld, n_rows, max_lag, stat, n_const and the d_nobs view as in
+ *   storm_hip_lag_band_sums_device. d_annot: n_rows x n_annot floats of pitch annot_ld, d_score: n_rows x n_annot floats
+ *   of pitch score_ld, d_lo / d_hi: n_rows uint32 each or both NULL, all in DEVICE memory. For every row i and column c,
+ *     d_score[i * score_ld + c] = the sum over the summed pairs (i, j), j != i, |i - j| <= L, d_lo[i] <= j <= d_hi[i], of
+ *                                 term(i, j) * (double)d_annot[j * annot_ld + c], accumulated in double (the
+ *                                 products are not rounded on their own), rounded once to float (+0.0f when no pair is
+ *                                 summed),
+ *     d_n_pairs[i]              = how many pairs were summed (one number per row; may be NULL).
+ *   d_lo / d_hi NULL: the whole lag. The bounds must be symmetric — j within [d_lo[i], d_hi[i]] exactly when i is within
+ *   [d_lo[j], d_hi[j]] — as storm.h's planner makes them: the kernel tests d_lo[i] behind row i and d_hi[i] ahead of it.
+ *   Whatever they hold, nothing outside the band is read. The annotations must be finite (a NaN or an infinity spreads
+ *   over its column's window). Columns [n_annot, annot_ld) of d_annot are never read and columns [n_annot, score_ld) of
+ *   d_score never written; the corner and the pitch columns of d_vals and d_nobs are never read.
+ *   lag_band_annot_sums_kernel: one workgroup per 64 rows x 64 columns, tiles of 64 source rows through the LDS, double
+ *   accumulators of v_mfma_f64_16x16x4_f64 in registers (STORM_HIP_LDSCORE_ANNOT_INNER=fma in the environment runs the
+ *   v_fma_f64 form instead, for comparison; read at every launch); no atomics and no clearing launch. The order of the additions of (i, c) depends on i and
+ *   L alone: a column has the same bits whatever other columns are passed with it, and two calls return the same bits.
+ *   Queued on the context's stream; no host wait.
+ * storm_hip_lag_dosage_ldscore_annot[_complete][_device]: rows of 2-bit dosages: the band of r^2 as in
+ *   storm_hip_lag_dosage_ldscore[_complete] (L = min(max_lag, n - 1)), then the kernel above. h_lo / h_hi are HOST arrays
+ *   of n entries in every form (both or NULL); the windows must need no more than max_lag rows (storm.h checks). The host
+ *   forms upload the annotations, download n x n_annot scores and the counts, and wait; the _device forms take d_annot,
+ *   d_score and d_n_pairs in device memory and return with everything queued: h_lo / h_hi must stay unchanged until that
+ *   work is complete (storm_hip_ctx_synchronize). Device scratch: n x L floats, 2 n words, and for the host forms
+ *   2 n x n_annot + n words, in the context's band buffer.
+ * STORM_HIP_EINVAL: what storm_hip_lag_band_sums_device / storm_hip_lag_dosage_ldscore refuse, in their order, then NULL
+ * annotations, n_annot outside [1, 1024], annot_ld or score_ld < n_annot, one of lo / hi without the other. Fewer than two
+ * rows: STORM_HIP_OK, nothing written. */
+int storm_hip_lag_band_annot_sums_device(storm_hip_ctx_t* ctx, const float* d_vals, uint64_t ld, uint64_t n_rows, uint64_t max_lag,
+                                         int stat, uint64_t n_const, const uint32_t* d_nobs, uint64_t nobs_row_pitch,
+                                         uint64_t nobs_col_stride, const uint32_t* d_lo, const uint32_t* d_hi,
+                                         const float* d_annot, uint64_t annot_ld, uint64_t n_annot, float* d_score,
+                                         uint64_t score_ld, uint32_t* d_n_pairs);
+int storm_hip_lag_dosage_ldscore_annot_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int stat, uint64_t n_samples,
+                                              uint64_t max_lag, const uint32_t* h_lo, const uint32_t* h_hi, const float* d_annot,
+                                              uint64_t annot_ld, uint64_t n_annot, float* d_score, uint64_t score_ld,
+                                              uint32_t* d_n_pairs);
+int storm_hip_lag_dosage_ldscore_annot(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int stat, uint64_t n_samples,
+                                       uint64_t max_lag, const uint32_t* h_lo, const uint32_t* h_hi, const float* h_annot,
+                                       uint64_t annot_ld, uint64_t n_annot, float* h_score, uint64_t score_ld, uint32_t* h_n_pairs);
+int storm_hip_lag_dosage_ldscore_annot_complete_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int stat,
+                                                       uint64_t n_samples, uint64_t max_lag, const uint32_t* h_lo,
+                                                       const uint32_t* h_hi, const float* d_annot, uint64_t annot_ld,
+                                                       uint64_t n_annot, float* d_score, uint64_t score_ld, uint32_t* d_n_pairs);
+int storm_hip_lag_dosage_ldscore_annot_complete(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int stat, uint64_t n_samples,
+                                                uint64_t max_lag, const uint32_t* h_lo, const uint32_t* h_hi, const float* h_annot,
+                                                uint64_t annot_ld, uint64_t n_annot, float* h_score, uint64_t score_ld,
+                                                uint32_t* h_n_pairs);
+
 /* sum_c C(n_c,2) on the device — verification identity only, never the product
  * path: used by tests at sizes where a CPU pairwise oracle is infeasible */
 int storm_hip_column_identity(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m,

@@ -426,6 +426,64 @@ class StormDosage:
         self._check(name, int(getattr(self._lib, name)(self._h, code, max_lag, _ptr(score), _ptr(pairs), n)))
         return score[:n], pairs[:n]
 
+    def lag_ldscore_annot(self, annot, max_lag: Optional[int] = None, stat: str = "r2", complete: bool = False, pos=None,
+                          max_dist: Optional[float] = None, device=None):
+        """STORM_dosage_lag_ldscore_annot[_complete]: (score [n_rows, C] float32, n_pairs [n_rows] uint32): stratified LD scores,
+        score[i, c] = the sum over row i's window of annot[j, c] times lag_ldscore's term of the pair (i, j), reduced on the
+        device. annot: [n_rows, C] float32, finite. The window: pos=None — the max_lag rows on each side; pos (n_rows
+        non-decreasing coordinates) and max_dist — the rows within that distance, computed at the lag the windows need
+        (max_lag=None) or refused when they need more than max_lag. The row itself is not included: LDSC's l is annot + score.
+        device=: (score, n_pairs) — a 2-D torch float32 tensor of at least n_rows rows and C columns with unit column stride
+        and a 1-D tensor of 32-bit entries (or None), in device memory, and annot a torch tensor there too — receive the
+        results instead (complete on return); returns None then."""
+        n = self.n_rows
+        name = "STORM_dosage_lag_ldscore_annot_complete" if complete else "STORM_dosage_lag_ldscore_annot"
+        code = LDSCORE_STATS[stat]
+        lag = 0 if max_lag is None else int(max_lag)
+        p = None
+        if pos is not None:
+            p = np.ascontiguousarray(pos, dtype=np.float64)
+            if p.shape != (n,):
+                raise ValueError("pos: one coordinate per row")
+            if max_dist is None:
+                raise ValueError("pos needs max_dist")
+        dist = 0.0 if max_dist is None else float(max_dist)
+        p_ptr = None if p is None else _ptr(p if p.size else np.zeros(1))   # (no rows: still "positions given")
+        if device is not None:
+            d_score, d_pairs = device
+            for t in (annot, d_score):
+                if t.dim() != 2 or t.element_size() != 4 or not t.is_floating_point() or t.stride(1) != 1 or not t.is_cuda:
+                    raise ValueError("device=: annot and score are 2-D float32 tensors with unit column stride in device memory")
+            if d_pairs is not None and (d_pairs.dim() != 1 or d_pairs.element_size() != 4 or d_pairs.stride(0) != 1 or not d_pairs.is_cuda):
+                raise ValueError("device=: n_pairs is a 1-D contiguous tensor of 32-bit entries in device memory")
+            if int(annot.shape[0]) < n or int(d_score.shape[1]) < int(annot.shape[1]):
+                raise ValueError("device=: annot has a row per row of the container, score a column per column of annot")
+            rows = int(d_score.shape[0]) if d_pairs is None else min(int(d_score.shape[0]), int(d_pairs.shape[0]))
+            self._check(name + "_device",
+                        int(getattr(self._lib, name + "_device")(self._h, code, lag, p_ptr, dist, C.c_void_p(annot.data_ptr()),
+                                                                 int(annot.shape[1]), int(annot.stride(0)),
+                                                                 C.c_void_p(d_score.data_ptr()), int(d_score.stride(0)),
+                                                                 None if d_pairs is None else C.c_void_p(d_pairs.data_ptr()), rows)))
+            return None
+        a = np.ascontiguousarray(annot, dtype=np.float32)
+        if a.ndim != 2 or a.shape[0] != n:
+            raise ValueError("annot: [n_rows, C]")
+        c = int(a.shape[1])
+        score, pairs = np.zeros((max(n, 1), max(c, 1)), dtype=np.float32), np.zeros(max(n, 1), dtype=np.uint32)
+        spare = np.zeros(1, dtype=np.float32)
+        self._check(name, int(getattr(self._lib, name)(self._h, code, lag, p_ptr, dist, _ptr(a) if a.size else _ptr(spare), c, max(c, 1),
+                                                       _ptr(score), max(c, 1), _ptr(pairs), n)))
+        return score[:n, :c], pairs[:n]
+
+    def ldscore_window_lag(self, pos, max_dist: float) -> int:
+        """STORM_ldscore_window_lag: the lag the windows of these coordinates need under max_dist (host only)."""
+        p = np.ascontiguousarray(pos, dtype=np.float64)
+        out = C.c_uint64(0)
+        self._check("STORM_ldscore_window_lag",
+                    int(self._lib.STORM_ldscore_window_lag(C.c_void_p(p.ctypes.data if p.size else 0), int(p.size), float(max_dist),
+                                                           C.byref(out))))
+        return int(out.value)
+
     def free(self) -> None:
         if self._h:
             self._lib.STORM_dosage_free(self._h)
@@ -707,6 +765,20 @@ class HipContext:
                                                        None if d_n_pairs is None else C.c_void_p(d_n_pairs)),
               "storm_hip_lag_band_sums_device")
 
+    def lag_band_annot_sums_device(self, d_vals: int, ld: int, n_rows: int, max_lag: int, d_annot: int, annot_ld: int, n_annot: int,
+                                   d_score: int, score_ld: int, d_n_pairs: Optional[int] = None, stat: str = "r2", n_const: int = 0,
+                                   d_nobs: Optional[int] = None, nobs_row_pitch: int = 0, nobs_col_stride: int = 1,
+                                   d_lo: Optional[int] = None, d_hi: Optional[int] = None) -> None:
+        """storm_hip_lag_band_annot_sums_device: the band at d_vals times the n_rows x n_annot annotations at d_annot, within
+        the windows [d_lo[i], d_hi[i]] (uint32, both or neither: the whole lag), into d_score (pitch score_ld) and d_n_pairs;
+        everything in device memory. Queued on the context's stream."""
+        opt = lambda p: None if p is None else C.c_void_p(p)
+        check(self._lib.storm_hip_lag_band_annot_sums_device(self._h, C.c_void_p(d_vals), ld, n_rows, max_lag, LDSCORE_STATS[stat],
+                                                             n_const, opt(d_nobs), nobs_row_pitch, nobs_col_stride, opt(d_lo),
+                                                             opt(d_hi), C.c_void_p(d_annot), annot_ld, n_annot, C.c_void_p(d_score),
+                                                             score_ld, opt(d_n_pairs)),
+              "storm_hip_lag_band_annot_sums_device")
+
     def matrix(self, n_rows: int, n_words: int) -> "HipMatrix":
         return HipMatrix(self, n_rows, n_words)
 
@@ -972,6 +1044,36 @@ class HipMatrix:
         name = "storm_hip_lag_dosage_ldscore_complete_device" if complete else "storm_hip_lag_dosage_ldscore_device"
         check(getattr(self._lib, name)(self.ctx._h, self._h, LDSCORE_STATS[stat], n_samples, max_lag, C.c_void_p(d_score),
                                        None if d_n_pairs is None else C.c_void_p(d_n_pairs)), name)
+
+    def lag_dosage_ldscore_annot(self, annot: np.ndarray, max_lag: int, n_samples: int, stat: str = "r2", complete: bool = False,
+                                 lo: Optional[np.ndarray] = None, hi: Optional[np.ndarray] = None):
+        """(score [n_rows, C] float32, n_pairs [n_rows] uint32): the stratified sums — annot[j, c] times the pair's term over
+        the rows j within max_lag of every row and inside its window [lo[i], hi[i]] (uint32 arrays, both or neither)."""
+        name = "storm_hip_lag_dosage_ldscore_annot_complete" if complete else "storm_hip_lag_dosage_ldscore_annot"
+        n = self.n_rows
+        a = np.ascontiguousarray(annot, dtype=np.float32)
+        c = int(a.shape[1])
+        lo = None if lo is None else np.ascontiguousarray(lo, dtype=np.uint32)
+        hi = None if hi is None else np.ascontiguousarray(hi, dtype=np.uint32)
+        score, pairs = np.zeros((max(n, 1), max(c, 1)), dtype=np.float32), np.zeros(max(n, 1), dtype=np.uint32)
+        check(getattr(self._lib, name)(self.ctx._h, self._h, LDSCORE_STATS[stat], n_samples, max_lag,
+                                       None if lo is None else _ptr(lo), None if hi is None else _ptr(hi), _ptr(a), max(c, 1), c,
+                                       _ptr(score), max(c, 1), _ptr(pairs)), name)
+        return score[:n, :c], pairs[:n]
+
+    def lag_dosage_ldscore_annot_device(self, d_annot: int, annot_ld: int, n_annot: int, d_score: int, score_ld: int,
+                                        d_n_pairs: Optional[int], max_lag: int, n_samples: int, stat: str = "r2",
+                                        complete: bool = False, lo: Optional[np.ndarray] = None, hi: Optional[np.ndarray] = None) -> None:
+        """Same, from annotations and into buffers in device memory (d_n_pairs may be None); lo / hi stay host arrays. The C
+        call returns with its work queued and lo / hi still to be read; this wrapper owns their copies and waits."""
+        name = "storm_hip_lag_dosage_ldscore_annot_complete_device" if complete else "storm_hip_lag_dosage_ldscore_annot_device"
+        lo = None if lo is None else np.ascontiguousarray(lo, dtype=np.uint32)
+        hi = None if hi is None else np.ascontiguousarray(hi, dtype=np.uint32)
+        check(getattr(self._lib, name)(self.ctx._h, self._h, LDSCORE_STATS[stat], n_samples, max_lag,
+                                       None if lo is None else _ptr(lo), None if hi is None else _ptr(hi), C.c_void_p(d_annot),
+                                       annot_ld, n_annot, C.c_void_p(d_score), score_ld,
+                                       None if d_n_pairs is None else C.c_void_p(d_n_pairs)), name)
+        self.ctx.synchronize()   # (lo / hi are this call's own copies: they must outlive the upload)
 
     def pairw_topk(self, k: int, score: str = "jaccard", n_bits: int = 1, panel_rows: int = 0):
         """(idx [n_rows, k] uint32, val [n_rows, k] float32, or uint32 for score "count"): for each row its k best other rows,

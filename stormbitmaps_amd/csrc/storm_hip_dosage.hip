@@ -648,6 +648,76 @@ static int lag_dosage_ldscore(storm_hip_ctx_t* ctx, const char* who, const storm
     return STORM_HIP_OK;
 }
 
+// ---- stratified LD scores: the same band, then lag_band_annot_sums_kernel (storm_hip_ldscore_annot.hip) over it ----
+// The band of r^2 into the first n x L floats of the band buffer exactly as above; behind it the window bounds (h_lo / h_hi
+// are HOST arrays of n entries in every form, both or neither: the planner runs on the host) and, for a host form, the n x C
+// annotations on their way in and the n x C scores and n counts on their way back, all dense. All queued on ctx->stream;
+// the host form alone waits.
+static int lag_dosage_ldscore_annot(storm_hip_ctx_t* ctx, const char* who, const storm_hip_matrix_s* m, int stat, uint64_t n_samples,
+                                    uint64_t max_lag, bool complete, const uint32_t* h_lo, const uint32_t* h_hi, const float* annot,
+                                    uint64_t annot_ld, uint64_t n_annot, float* score, uint64_t score_ld, uint32_t* n_pairs,
+                                    bool host) {
+    uint64_t lag = 0;
+    if (int rc = check_lag_dosage(who, m, score, max_lag, ~0ull, &lag)) return rc;
+    if (stat != STORM_HIP_LDSCORE_R2 && stat != STORM_HIP_LDSCORE_R2_ADJ) {
+        set_error("%s: unknown stat %d (0 r^2, 1 r^2 adjusted)", who, stat);
+        return STORM_HIP_EINVAL;
+    }
+    if (int rc = check_samples(who, m, n_samples)) return rc;
+    if (!annot) {
+        set_error("%s: NULL annotations", who);
+        return STORM_HIP_EINVAL;
+    }
+    if (n_annot < 1 || n_annot > kLdscoreMaxAnnot) {
+        set_error("%s: %llu annotation columns (1 .. %u)", who, (unsigned long long)n_annot, kLdscoreMaxAnnot);
+        return STORM_HIP_EINVAL;
+    }
+    if (annot_ld < n_annot || score_ld < n_annot) {
+        set_error("%s: annot_ld %llu or score_ld %llu < %llu annotation columns", who, (unsigned long long)annot_ld,
+                  (unsigned long long)score_ld, (unsigned long long)n_annot);
+        return STORM_HIP_EINVAL;
+    }
+    if (!h_lo != !h_hi) {
+        set_error("%s: the window bounds lo and hi come together or not at all", who);
+        return STORM_HIP_EINVAL;
+    }
+    const uint64_t n = m->n_rows;
+    if (n < 2) return STORM_HIP_OK;
+    STORM_HIP_TRY(hipSetDevice(ctx->device));
+    const size_t band = (size_t)n * lag, cells = (size_t)n * n_annot;
+    const size_t words = band + (h_lo ? 2 * n : 0) + (host ? 2 * cells + n : 0);
+    if (int rc = ctx->d_band.ensure(words * sizeof(uint32_t), "lag_dosage_ldscore_annot: the band of r^2")) return rc;
+    uint32_t* const d_band = ctx->d_band.d;
+    uint32_t* const d_lo = h_lo ? d_band + band : nullptr;
+    uint32_t* const d_hi = h_lo ? d_lo + n : nullptr;
+    uint32_t* const d_io = d_band + band + (h_lo ? 2 * n : 0);
+    if (h_lo) {
+        STORM_HIP_TRY(hipMemcpyAsync(d_lo, h_lo, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        STORM_HIP_TRY(hipMemcpyAsync(d_hi, h_hi, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (host)
+        STORM_HIP_TRY(hipMemcpy2DAsync(d_io, n_annot * sizeof(float), annot, annot_ld * sizeof(float), n_annot * sizeof(float), n,
+                                       hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = complete ? lag_dosage_corr_complete_queued(ctx, m, STORM_HIP_DOSAGE_R2, n_samples, max_lag, d_band, lag)
+                          : lag_dosage_corr_queued(ctx, m, STORM_HIP_DOSAGE_R2, n_samples, max_lag, d_band, lag))
+        return rc;
+    const bool view = complete && stat == STORM_HIP_LDSCORE_R2_ADJ;
+    const uint64_t lds = lag_complete_pitch(lag);
+    const float* const d_annot = host ? reinterpret_cast<const float*>(d_io) : annot;
+    float* const d_score = host ? reinterpret_cast<float*>(d_io + cells) : score;
+    uint32_t* const d_pairs = host ? d_io + 2 * cells : n_pairs;
+    if (int rc = launch_lag_band_annot_sums(ctx, reinterpret_cast<const float*>(d_band), lag, n, max_lag, stat, n_samples,
+                                            view ? ctx->d_dosage_sums.d + 2 * lds + 2 : nullptr, 3 * lds, 3, d_lo, d_hi, d_annot,
+                                            host ? n_annot : annot_ld, n_annot, d_score, host ? n_annot : score_ld, d_pairs))
+        return rc;
+    if (!host) return STORM_HIP_OK;
+    STORM_HIP_TRY(hipMemcpy2DAsync(score, score_ld * sizeof(float), d_score, n_annot * sizeof(float), n_annot * sizeof(float), n,
+                                   hipMemcpyDeviceToHost, ctx->stream));
+    if (n_pairs) STORM_HIP_TRY(hipMemcpyAsync(n_pairs, d_pairs, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return STORM_HIP_OK;
+}
+
 }  // namespace storm
 
 using namespace storm;
@@ -1023,6 +1093,49 @@ int storm_hip_lag_dosage_ldscore_complete(storm_hip_ctx_t* ctx, const storm_hip_
     return guarded("storm_hip_lag_dosage_ldscore_complete", [&]() -> int {
         if (check_ctx(ctx)) return STORM_HIP_EINVAL;
         return lag_dosage_ldscore(ctx, "lag_dosage_ldscore_complete", m, stat, n_samples, max_lag, true, h_score, h_n_pairs, true);
+    });
+}
+
+int storm_hip_lag_dosage_ldscore_annot_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int stat, uint64_t n_samples,
+                                              uint64_t max_lag, const uint32_t* h_lo, const uint32_t* h_hi, const float* d_annot,
+                                              uint64_t annot_ld, uint64_t n_annot, float* d_score, uint64_t score_ld,
+                                              uint32_t* d_n_pairs) {
+    return guarded("storm_hip_lag_dosage_ldscore_annot_device", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        return lag_dosage_ldscore_annot(ctx, "lag_dosage_ldscore_annot", m, stat, n_samples, max_lag, false, h_lo, h_hi, d_annot,
+                                        annot_ld, n_annot, d_score, score_ld, d_n_pairs, false);
+    });
+}
+
+int storm_hip_lag_dosage_ldscore_annot(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int stat, uint64_t n_samples,
+                                       uint64_t max_lag, const uint32_t* h_lo, const uint32_t* h_hi, const float* h_annot,
+                                       uint64_t annot_ld, uint64_t n_annot, float* h_score, uint64_t score_ld, uint32_t* h_n_pairs) {
+    return guarded("storm_hip_lag_dosage_ldscore_annot", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        return lag_dosage_ldscore_annot(ctx, "lag_dosage_ldscore_annot", m, stat, n_samples, max_lag, false, h_lo, h_hi, h_annot,
+                                        annot_ld, n_annot, h_score, score_ld, h_n_pairs, true);
+    });
+}
+
+int storm_hip_lag_dosage_ldscore_annot_complete_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int stat,
+                                                       uint64_t n_samples, uint64_t max_lag, const uint32_t* h_lo,
+                                                       const uint32_t* h_hi, const float* d_annot, uint64_t annot_ld,
+                                                       uint64_t n_annot, float* d_score, uint64_t score_ld, uint32_t* d_n_pairs) {
+    return guarded("storm_hip_lag_dosage_ldscore_annot_complete_device", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        return lag_dosage_ldscore_annot(ctx, "lag_dosage_ldscore_annot_complete", m, stat, n_samples, max_lag, true, h_lo, h_hi,
+                                        d_annot, annot_ld, n_annot, d_score, score_ld, d_n_pairs, false);
+    });
+}
+
+int storm_hip_lag_dosage_ldscore_annot_complete(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int stat, uint64_t n_samples,
+                                                uint64_t max_lag, const uint32_t* h_lo, const uint32_t* h_hi, const float* h_annot,
+                                                uint64_t annot_ld, uint64_t n_annot, float* h_score, uint64_t score_ld,
+                                                uint32_t* h_n_pairs) {
+    return guarded("storm_hip_lag_dosage_ldscore_annot_complete", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        return lag_dosage_ldscore_annot(ctx, "lag_dosage_ldscore_annot_complete", m, stat, n_samples, max_lag, true, h_lo, h_hi,
+                                        h_annot, annot_ld, n_annot, h_score, score_ld, h_n_pairs, true);
     });
 }
 

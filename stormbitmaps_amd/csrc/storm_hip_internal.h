@@ -308,6 +308,13 @@ int launch_similarity_finish_lag(storm_hip_ctx_t* ctx, void* d_io, uint64_t ld, 
 int launch_lag_band_sums(storm_hip_ctx_t* ctx, const float* d_vals, uint64_t ld, uint64_t n_rows, uint64_t max_lag, int stat,
                          uint64_t n_const, const uint32_t* d_nobs, uint64_t nobs_row_pitch, uint64_t nobs_col_stride,
                          float* d_score, uint32_t* d_n_pairs);
+// lag_band_annot_sums_kernel: the band times an annotation matrix with a window per row (d_lo / d_hi: both or neither), queued
+// (storm_hip_ldscore_annot.hip; the checks of storm_hip_lag_band_annot_sums_device)
+constexpr uint32_t kLdscoreMaxAnnot = 1024;   // annotation columns of one call (the launch grid's y: 16 chunks of 64)
+int launch_lag_band_annot_sums(storm_hip_ctx_t* ctx, const float* d_vals, uint64_t ld, uint64_t n_rows, uint64_t max_lag, int stat,
+                               uint64_t n_const, const uint32_t* d_nobs, uint64_t nobs_row_pitch, uint64_t nobs_col_stride,
+                               const uint32_t* d_lo, const uint32_t* d_hi, const float* d_annot, uint64_t annot_ld,
+                               uint64_t n_annot, float* d_score, uint64_t score_ld, uint32_t* d_n_pairs);
 void release_mfma_state(storm_hip_ctx_t* ctx);
 // releases what was put off (storm_hip_ctx_s::deferred_free); `aged`: only what an earlier call left behind
 void drain_deferred(storm_hip_ctx_t* ctx, bool aged);

@@ -38,4 +38,10 @@ STORM_LDSCORE_FN uint64_t ldscore_nobs_at(const uint32_t* nobs, uint64_t row_pit
     return (uint64_t)nobs[i * row_pitch + d * col_stride];
 }
 
+// One pair in one column of the stratified scores (lag_band_annot_sums_kernel, storm_hip_ldscore_annot.hip): the pair's
+// term times the annotation of the OTHER row, added to the column's sum by one explicit fused multiply-add — one rounding,
+// whatever -ffp-contract says, on the device and in the host restatement of tests/test_ldscore_annot_math.py alike. A pair
+// that is not summed enters as term +0.0 and leaves the sum's bits as they are for every finite a.
+STORM_LDSCORE_FN double ldscore_annot_add(double sum, double term, float a) { return __builtin_fma(term, (double)a, sum); }
+
 }  // namespace storm
