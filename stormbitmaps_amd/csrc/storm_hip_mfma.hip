@@ -717,25 +717,33 @@ __device__ __forceinline__ v4i sb16_inflate(v4i w, uint32_t rot) {
 // K2b with 128 A rows per wave (strip16_rows_kernel, option k2_strip_rows = 128): the same 96 registers spent the other way
 // round. strip16_bits_kernel keeps 64 A rows x 256 bit-MACs per wave (a[2][4]) and accumulates 64 x 64: a B fragment meets
 // the 4 A fragments of its k-step. Here a wave keeps 128 A rows x 128 bit-MACs — 8 A fragments of ONE k-step, blocks w and
-// w + 4 of a 512-row A tile — and accumulates 128 x 32 (acc[8][2]): every B fragment feeds 8 MFMAs.
+// 7 - w of a 512-row A tile — and accumulates 128 x 32 (acc[8][2]): every B fragment feeds 8 MFMAs.
 //   * k-slice `ks` = the 16 bytes [16 ks, 16 ks + 16) of every row, all four bit classes of its four dwords; element order
 //     inside the k-step = (dword, class, nibble) on both sides (sr16_inflate builds both).
 //   * B stage = 64 rows x 16 B = 1 KiB of bits: wave w DMAs its 16 rows as 4 bytes per lane (256 B per wave and slot, ring
 //     of 3, own vmcnt), reads its dword back (ds_read_b32), inflates the four classes (7 VALU) and writes ONE ds_write_b128
 //     into the image: 64 rows x 64 B = 4 KiB, ring of 3.
-//   per 64 B rows and wave    strip16_bits_kernel    strip16_rows_kernel
-//   MFMAs                     32                     32
-//   fragment ds_read_b128     8                      4
-//   image ds_write_b128       2                      1
-//   inflation VALU            16                     7
-//   piece read-back           ds_read_b128           ds_read_b32
-//   LDS per workgroup         36 KiB                 15 KiB
-// Ring protocol, barrier per stage, diagonal phase outside the pipelined loop, epilogue and fold: strip16_bits_kernel's.
-// The A tile has 8 own blocks, so an item with a diagonal spends 8 non-pipelined stages where the 256-row form spends 4.
+//   * diagonal phase (items with `diag`): the 8 B blocks are the A tile's own rows, which the waves hold inflated. Every wave
+//     stores its 8 A fragments as the images of its two blocks (8 ds_write_b128 at the fragment-read address), ONE barrier
+//     publishes the 8 resident images, and every wave walks the blocks d = w .. 7 without a barrier, a DMA or an inflation:
+//     block w's triangle, whole products up to block 7 - w, that block's triangle beside them, both halves whole behind it
+//     (strip_rows_role, storm_hip_plan.h) — 7 whole products and 2 triangles = 132 MFMAs for every wave. Four fragments of
+//     a block are asked for at once and multiplied behind lgkmcnt(3 .. 0). The pieces of the first three pipelined stages
+//     are in flight meanwhile; one more barrier, and the pipelined ring of 3 images is overlaid on resident images 0 .. 2.
+//   per 64 B rows and wave    strip16_bits_kernel    strip16_rows_kernel    its diagonal phase (per block step)
+//   MFMAs                     32                     32                     10 / 16 / 26 / 32
+//   fragment ds_read_b128     8                      4                      4
+//   image ds_write_b128       2                      1                      0 (8 per item)
+//   inflation VALU            16                     7                      0
+//   piece read-back           ds_read_b128           ds_read_b32            none
+//   barriers                  1                      1                      0 (2 per item)
+//   LDS per workgroup         36 KiB                 35 KiB: 8 images of 4 KiB (the ring of 3 overlaid) + 3 KiB of bits
+// 35 KiB x 4 workgroups = 140 of a CU's 160 KiB: the registers (<= 128) already cap a CU at 4 workgroups.
+// Ring protocol, barrier per stage, epilogue and fold: strip16_bits_kernel's.
 constexpr uint32_t kSr16SliceBytes = 16;                          // a k-slice of a row: 128 bits
 constexpr uint32_t kSr16PerTile = kStripRowsATile / kStripBRows;  // 8 own blocks
 constexpr uint32_t kSr16StageBytes = kStripBRows * 64;            // an FP4 image: 64 rows x 64 B
-constexpr uint32_t kSr16ImgBytes = 3 * kSr16StageBytes;
+constexpr uint32_t kSr16ImgBytes = kSr16PerTile * kSr16StageBytes;   // the diagonal phase's 8 resident images; the ring of 3 is images 0 .. 2
 constexpr uint32_t kSr16BitRing = 3;
 constexpr uint32_t kSr16BitStage = 4 * 256;                       // 1 KiB of bits per B stage, 256 B per wave
 

@@ -51,6 +51,31 @@ constexpr int kStripATile = 64 * kStripWaves;            // A rows per workgroup
 constexpr uint32_t kStripRowsATile = 512;
 constexpr uint32_t kStripRowsXcdGroup = 8;
 inline uint32_t strip_rows_kslices(uint32_t n_words) { return (n_words + 1u) / 2u; }
+// ... and the schedule of its diagonal phase (the A tile's 8 blocks of 64 rows among themselves: block b against every
+// block d > b whole, against itself as the strict upper triangle). Wave w of the 4 keeps two blocks, its HALVES: the low
+// half is block w, the high half block 7 - w, so that every wave owes 7 whole block products and 2 triangles. The wave
+// walks the blocks d upwards from its first one; at block d a half skips (d in front of its block), multiplies its own
+// triangle (d is its block) or multiplies whole. The kernel takes its loop bounds from these functions and
+// tests/strip_rows_diag/driver.cpp checks them on the host.
+constexpr uint32_t kStripRowsBlocks = kStripRowsATile / (uint32_t)kStripBRows;   // 8
+constexpr uint32_t kStripRowsWaves = 4;
+enum StripRowsRole : uint32_t { kStripRowsSkip = 0, kStripRowsOwn = 1, kStripRowsWhole = 2 };
+constexpr uint32_t strip_rows_block(uint32_t wave, uint32_t half) { return half ? kStripRowsBlocks - 1u - wave : wave; }
+constexpr StripRowsRole strip_rows_role(uint32_t wave, uint32_t half, uint32_t d) {
+    return d < strip_rows_block(wave, half) ? kStripRowsSkip : d == strip_rows_block(wave, half) ? kStripRowsOwn : kStripRowsWhole;
+}
+// the first block at which the wave has anything to multiply, and one past the last
+constexpr uint32_t strip_rows_diag_begin(uint32_t wave) {
+    return strip_rows_block(wave, 0) < strip_rows_block(wave, 1) ? strip_rows_block(wave, 0) : strip_rows_block(wave, 1);
+}
+constexpr uint32_t strip_rows_diag_end(uint32_t) { return kStripRowsBlocks; }
+// MFMAs of a half at block d: a whole product is 4 x 4 sub-blocks of 16 x 16, an own block the 10 with i <= j
+constexpr uint32_t strip_rows_role_mfmas(StripRowsRole r) { return r == kStripRowsWhole ? 16u : r == kStripRowsOwn ? 10u : 0u; }
+// (the kernel's five runs — low own | low whole | low whole + high own | both whole, nothing skipped in between — need the
+//  low half's block in front of the high half's for every wave)
+static_assert(strip_rows_block(0, 0) < strip_rows_block(0, 1) && strip_rows_block(1, 0) < strip_rows_block(1, 1) &&
+              strip_rows_block(2, 0) < strip_rows_block(2, 1) && strip_rows_block(3, 0) < strip_rows_block(3, 1),
+              "strip16_rows_kernel walks the low half's own block first");
 
 struct StripItem {
     uint32_t a_row0;  // first row of the A tile (kStripATile rows, multiple of 64)

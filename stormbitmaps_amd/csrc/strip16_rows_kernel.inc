@@ -5,18 +5,22 @@ __global__ __launch_bounds__(256, 4) void strip16_rows_kernel(
     unsigned long long* __restrict__ slots, unsigned long long* __restrict__ out, uint32_t fold_slots) {
     __shared__ __attribute__((aligned(1024))) uint8_t lds_raw[kSr16ImgBytes + kSr16BitRing * kSr16BitStage];
 
-    constexpr uint32_t kW = 4u;                     // waves per workgroup; wave w keeps blocks w and w + 4 of the A tile
+    constexpr uint32_t kW = kStripRowsWaves;        // waves per workgroup; wave w keeps blocks w and 7 - w of the A tile
+    static_assert(kSr16PerTile == kStripRowsBlocks && kSr16ImgBytes >= kStripRowsBlocks * kSr16StageBytes, "eight resident images");
     STORM_CLOCK_BEGIN();
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const StripItem it = items[blockIdx.x];
     const uint64_t kbyte = (uint64_t)it.ks * (uint64_t)kSr16SliceBytes;
-    const uint32_t D = it.diag ? kSr16PerTile : 0u;
-    const uint32_t T = D + (it.j1 - it.j0);
-    // Stage s lives in ring slot (s + cslot) % 3 of both rings, the first pipelined stage (s = D) in slot 0: the three
-    // instances of the loop body address their images and pieces with immediate offsets (as strip16_bits_kernel)
-    const uint32_t cslot = (3u - D % 3u) % 3u;
+    // Pipelined stage s (B block j1 - 1 - s) lives in ring slot s % 3 of both rings: the three instances of the loop body
+    // address their images and pieces with immediate offsets (as strip16_bits_kernel). The diagonal phase in front of it
+    // is no stage of the rings. An item that has only its diagonal (T == 0) still issues its three pieces — of the tile's
+    // own first block, a valid address — and drains them at the end.
+    const uint32_t T = it.j1 - it.j0;
+    const uint32_t s_last = T ? T - 1u : 0u;
+    const uint32_t blk_top = T ? it.j1 - 1u : it.a_row0 / (uint32_t)kStripBRows;
+    const uint32_t blk_lo = strip_rows_block(wave, 0u), blk_hi = strip_rows_block(wave, 1u);
 
     const uint32_t lds_base =
         (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)&lds_raw[0];
@@ -33,8 +37,7 @@ __global__ __launch_bounds__(256, 4) void strip16_rows_kernel(
     // LDS-DMA of the wave's piece of stage s into bit slot `slot`. Stages beyond the last one re-read the
     // last block (never consumed): every iteration issues exactly one piece, so every wait is vmcnt(2).
     auto issue = [&](uint32_t s, uint32_t slot) {
-        const uint32_t sc = min(s, T - 1u);
-        const uint32_t blk = sc < D ? it.a_row0 / (uint32_t)kStripBRows + sc : it.j1 - 1u - (sc - D);
+        const uint32_t blk = blk_top - min(s, s_last);
         const uint8_t* base = X + (uint64_t)(blk * (uint32_t)kStripBRows) * row_bytes + kbyte;
         const __amdgpu_buffer_rsrc_t rsrc =
             __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(base), 0, -1, 0x00020000);
@@ -44,21 +47,21 @@ __global__ __launch_bounds__(256, 4) void strip16_rows_kernel(
     };
 
     // A fragments: a[m] = the four classes of dword lane >> 4 of the slice of row
-    //   m < 4 : a_row0 + 64 wave + 16 m + (lane & 15)               (block wave of the tile)
-    //   m >= 4: a_row0 + 256 + 64 wave + 16 (m - 4) + (lane & 15)   (block wave + 4)
+    //   m < 4 : a_row0 + 64 wave + 16 m + (lane & 15)               (block wave of the tile: the low half)
+    //   m >= 4: a_row0 + 64 (7 - wave) + 16 (m - 4) + (lane & 15)   (block 7 - wave: the high half)
     // Element order inside the k-step: (dword, class, nibble), the image's order.
     // (loaded in front of the DMA pieces, so that the wait for them leaves the pieces in flight)
     v4i a[8];
     {
-        const uint8_t* ap = X + (uint64_t)(it.a_row0 + wave * 64u + (lane & 15u)) * row_bytes + kbyte +
-                            (lane >> 4) * 4u;
+        const uint8_t* ap = X + (uint64_t)(it.a_row0 + (lane & 15u)) * row_bytes + kbyte + (lane >> 4) * 4u;
         uint32_t aw[8];
 #pragma unroll
         for (int m = 0; m < 8; ++m)
-            aw[m] = *reinterpret_cast<const uint32_t*>(ap + (uint64_t)((m & 3) * 16 + (m >> 2) * 256) * row_bytes);
-        issue(0u, cslot);
-        issue(1u, (cslot + 1u) % 3u);
-        issue(2u, (cslot + 2u) % 3u);
+            aw[m] = *reinterpret_cast<const uint32_t*>(
+                ap + (uint64_t)((m < 4 ? blk_lo : blk_hi) * (uint32_t)kStripBRows + (uint32_t)(m & 3) * 16u) * row_bytes);
+        issue(0u, 0u);
+        issue(1u, 1u);
+        issue(2u, 2u);
 #pragma unroll
         for (int m = 0; m < 8; ++m) a[m] = sr16_inflate(aw[m]);
     }
@@ -99,9 +102,9 @@ __global__ __launch_bounds__(256, 4) void strip16_rows_kernel(
     __builtin_amdgcn_sched_barrier(0)
 
     uint32_t wb = 0;
-    // the wave's quarter of the image of stage s, start to finish (prologue and diagonal phase)
+    // the wave's quarter of the image of stage s, start to finish (prologue)
     auto build_image = [&](uint32_t s) {
-        uint32_t slot = (s + cslot) % 3u;
+        uint32_t slot = s % 3u;
         asm volatile("" : "+s"(slot));   // (opaque: the two addresses below are one addition each, not induction variables)
         asm volatile("ds_read_b32 %0, %1" : "=&v"(wb) : "v"(bits_rd + slot * kSr16BitStage));
         STORM_LGKM(0);
@@ -111,114 +114,102 @@ __global__ __launch_bounds__(256, 4) void strip16_rows_kernel(
     };
 
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // scalar loads of the item record
-    // Invariant at the top of iteration t, in front of its issue: the pieces of stages <= t + 3 have been
-    // issued, those of stages <= t + 1 have landed and been turned into images.
-    STORM_VM2();        // stage 0 (1 and 2 in flight)
-    build_image(0u);
-    STORM_LGKM(0);      // the piece has been read: its slot takes stage 3
-    issue(3u, cslot);
-    STORM_VM2();        // stage 1
-    build_image(1u);
 
-    v4i b0 = {}, b1 = {}, b2 = {};
+    v4i b0 = {}, b1 = {}, b2 = {}, b3 = {};
     uint32_t t = 0;
-    // ---- the A tile's own 8 blocks. At stage d the low half of wave w (block w, m < 4) skips d < w, keeps the strict upper
-    //      triangle of its own 64 x 64 block at d == w and takes d > w whole; the high half (block w + 4, m >= 4) does the same
-    //      around d == w + 4. Own block, A sub-block i = m & 3 against B sub-block j: only i <= j is multiplied, and the
-    //      accumulator of (j, j) is masked IN PLACE (row < col of the C/D map) right behind fragment j. That is exact:
-    //      acc[base + i][n] takes the fragments j = n and j = n + 2 with i <= j, so when (j, j) is masked acc[base + j][j & 1]
-    //      holds nothing else — no earlier stage reached this half (all were skipped), and of this stage (j, j - 2) was skipped
-    //      and (j, j + 2) is still to come: acc[.][0] of i = 0 and acc[.][1] of i = 1 are masked before fragments 2 and 3 add
-    //      to them, acc[i = 2][0] and acc[i = 3][1] are empty until (2, 2) and (3, 3) because (2, 0) and (3, 1) were skipped.
-    //      The phase is five runs of stages, each with ONE dataflow (a loop that branched per stage made the register
-    //      allocator shuffle the 64 accumulators between the paths and spill): both halves skip | low own | low whole |
-    //      low whole + high own | both whole. Fragments 0 and 1 of a stage, then 2 and 3 in the same two registers.
-    if (D != 0u) {
+    // ---- the A tile's own 8 blocks, from RESIDENT images: the 8 B blocks of this phase are the tile's own 512 rows, which
+    //      the four waves already hold inflated — a[m] has the bytes and the lane layout a fragment read returns (row
+    //      16 j + (lane & 15), the four classes of dword lane >> 4). Every wave stores its 8 fragments at the address a
+    //      fragment read uses, image blk = its block, fragment j = m & 3; one barrier publishes the tile, and behind it the
+    //      phase has no DMA, no read-back, no inflation and no barrier. (A store is served in groups of 8 lanes on banks
+    //      (a / 4) mod 32, a period of 128 bytes: lanes 8 g .. 8 g + 7 are rows 8 (g & 1) .. + 7 of the fragment at dword
+    //      g >> 1, and rows r and r + 2 of a run of 4 share a slot, so every one of these stores is a 2-way conflict — 8
+    //      LDS cycles each, 64 per wave and item, measured. The layout is the one the fragment reads need.)
+    //      At block d the low half of wave w (block w, m < 4) keeps the strict upper triangle of its own 64 x 64 block at
+    //      d == w and takes d > w whole; the high half (block 7 - w, m >= 4) does the same around d == 7 - w
+    //      (strip_rows_role, storm_hip_plan.h): 7 whole products and 2 triangles for every wave, so the waves start at
+    //      block w and finish together. Own block, A sub-block i = m & 3 against B sub-block j: only i <= j is multiplied,
+    //      and the accumulator of (j, j) is masked IN PLACE (row < col of the C/D map) right behind fragment j. That is
+    //      exact: acc[base + i][n] takes the fragments j = n and j = n + 2 with i <= j, so when (j, j) is masked
+    //      acc[base + j][j & 1] holds nothing else — a half's own block is the first thing its accumulators see, and of
+    //      that block (j, j - 2) was skipped and (j, j + 2) is still to come: acc[.][0] of i = 0 and acc[.][1] of i = 1 are
+    //      masked before fragments 2 and 3 add to them, acc[i = 2][0] and acc[i = 3][1] are empty until (2, 2) and (3, 3)
+    //      because (2, 0) and (3, 1) were skipped.
+    //      The phase is four runs of blocks, each with ONE dataflow (a loop that branched per block made the register
+    //      allocator shuffle the 64 accumulators between the paths and spill): low own | low whole | low whole + high own |
+    //      both whole. A block step asks for its four fragments up front and multiplies behind counted waits (the four
+    //      registers as a rotation across the steps, every wait lgkmcnt(3), measured the same: LAB_NOTES).
+    if (it.diag) {
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            uint32_t ib = (m < 4 ? blk_lo : blk_hi) * kSr16StageBytes;
+            asm volatile("" : "+s"(ib));
+            asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(boff + ib), "v"(a[m]), "n"((m & 3) * 16 * 64) : "memory");
+        }
+        STORM_LGKM(0);
+        __builtin_amdgcn_s_barrier();    // the eight images are complete
         // C/D map: col = lane & 15 (B row), row = 4 * (lane >> 4) + reg (A row): reg r survives where r < tri
 #define STORM_SR16_MASK(m, n)                                                             \
     _Pragma("unroll") for (int r = 0; r < 4; ++r) acc[m][n][r] = r < tri ? acc[m][n][r] : 0.0f;
-#define STORM_SR16_WHOLE(base, j)                                                         \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                       \
-        STORM_MUL1((base) + i, j, b0);                                                    \
-        STORM_MUL1((base) + i, (j) + 1, b1);                                              \
-    }
-#define STORM_SR16_OWN01(base)                                                            \
-    STORM_MUL1((base) + 0, 0, b0);                                                        \
-    STORM_SR16_MASK((base) + 0, 0)                                                        \
-    STORM_MUL1((base) + 0, 1, b1);                                                        \
-    STORM_MUL1((base) + 1, 1, b1);                                                        \
-    STORM_SR16_MASK((base) + 1, 1)
-#define STORM_SR16_OWN23(base)                                                            \
-    STORM_MUL1((base) + 0, 2, b0);                                                        \
-    STORM_MUL1((base) + 1, 2, b0);                                                        \
-    STORM_MUL1((base) + 2, 2, b0);                                                        \
-    STORM_SR16_MASK((base) + 2, 0)                                                        \
-    STORM_MUL1((base) + 0, 3, b1);                                                        \
-    STORM_MUL1((base) + 1, 3, b1);                                                        \
-    STORM_MUL1((base) + 2, 3, b1);                                                        \
-    STORM_MUL1((base) + 3, 3, b1);                                                        \
-    STORM_SR16_MASK((base) + 3, 1)
+        // fragment j of block d against the half's four A sub-blocks
+#define STORM_SR16_WHOLE(base, j, frag)                                                   \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i) STORM_MUL1((base) + i, j, frag);
+        // fragment j of the half's own block: sub-blocks i <= j, (j, j) masked
+#define STORM_SR16_OWN01(base, j, frag)                                                   \
+    _Pragma("unroll") for (int i = 0; i <= (j); ++i) STORM_MUL1((base) + i, j, frag);     \
+    STORM_SR16_MASK((base) + (j), j)
+#define STORM_SR16_OWN23(base, j, frag)                                                   \
+    _Pragma("unroll") for (int i = 0; i <= (j); ++i) STORM_MUL1((base) + i, j, frag);     \
+    STORM_SR16_MASK((base) + (j), (j) - 2)
         // (sb: the image's offset as an opaque scalar, added to the fragment address at every use — as an induction
         //  variable in a vector register it costs what the loops do not have)
 #define STORM_SR16_HEAD()                                                                 \
-    STORM_LGKM(0);                   /* own image writes */                               \
-    __builtin_amdgcn_s_barrier();    /* images t and t + 1 complete, the slot of image t - 1 free */ \
-    issue(t + 4u, (t + 1u + cslot) % 3u);                                                 \
-    STORM_VM2();                     /* stage t + 2 */                                    \
-    build_image(t + 2u);                                                                  \
-    uint32_t sb = ((t + cslot) % 3u) * kSr16StageBytes;                                   \
-    asm volatile("" : "+s"(sb))
-#define STORM_SR16_PAIR(j)                                                                \
+    uint32_t sb = d * kSr16StageBytes;                                                    \
+    asm volatile("" : "+s"(sb));                                                          \
     __builtin_amdgcn_sched_barrier(0);                                                    \
-    STORM_FETCH16V(b0, sb, j);                                                            \
-    STORM_FETCH16V(b1, sb, (j) + 1);                                                      \
-    STORM_LGKM(0)
-#pragma unroll 1
-        for (; t < wave; ++t) {          // both halves skip
-            STORM_SR16_HEAD();
-        }
-        {                                // t == wave: low own
+    STORM_FETCH16V(b0, sb, 0);                                                            \
+    STORM_FETCH16V(b1, sb, 1);                                                            \
+    STORM_FETCH16V(b2, sb, 2);                                                            \
+    STORM_FETCH16V(b3, sb, 3)
+        uint32_t d = strip_rows_diag_begin(wave);
+        {                                // d == blk_lo: low own
             STORM_SR16_HEAD();
             const uint32_t lane_d = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
             const int tri = (int)(lane_d & 15u) - (int)(4u * (lane_d >> 4));
-            STORM_SR16_PAIR(0);
-            STORM_SR16_OWN01(0)
-            STORM_SR16_PAIR(2);
-            STORM_SR16_OWN23(0)
-            ++t;
+            STORM_LGKM(3); STORM_SR16_OWN01(0, 0, b0) __builtin_amdgcn_sched_barrier(0);
+            STORM_LGKM(2); STORM_SR16_OWN01(0, 1, b1) __builtin_amdgcn_sched_barrier(0);
+            STORM_LGKM(1); STORM_SR16_OWN23(0, 2, b2) __builtin_amdgcn_sched_barrier(0);
+            STORM_LGKM(0); STORM_SR16_OWN23(0, 3, b3) __builtin_amdgcn_sched_barrier(0);
+            ++d;
         }
 #pragma unroll 1
-        for (; t < wave + 4u; ++t) {     // low whole
+        for (; d < blk_hi; ++d) {        // low whole
             STORM_SR16_HEAD();
-            STORM_SR16_PAIR(0);
-            STORM_SR16_WHOLE(0, 0)
-            STORM_SR16_PAIR(2);
-            STORM_SR16_WHOLE(0, 2)
+            STORM_LGKM(3); STORM_SR16_WHOLE(0, 0, b0) __builtin_amdgcn_sched_barrier(0);
+            STORM_LGKM(2); STORM_SR16_WHOLE(0, 1, b1) __builtin_amdgcn_sched_barrier(0);
+            STORM_LGKM(1); STORM_SR16_WHOLE(0, 2, b2) __builtin_amdgcn_sched_barrier(0);
+            STORM_LGKM(0); STORM_SR16_WHOLE(0, 3, b3) __builtin_amdgcn_sched_barrier(0);
         }
-        {                                // t == wave + 4: low whole, high own
+        {                                // d == blk_hi: low whole, high own
             STORM_SR16_HEAD();
             const uint32_t lane_d = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
             const int tri = (int)(lane_d & 15u) - (int)(4u * (lane_d >> 4));
-            STORM_SR16_PAIR(0);
-            STORM_SR16_WHOLE(0, 0)
-            STORM_SR16_OWN01(4)
-            STORM_SR16_PAIR(2);
-            STORM_SR16_WHOLE(0, 2)
-            STORM_SR16_OWN23(4)
-            ++t;
+            STORM_LGKM(3); STORM_SR16_WHOLE(0, 0, b0) STORM_SR16_OWN01(4, 0, b0) __builtin_amdgcn_sched_barrier(0);
+            STORM_LGKM(2); STORM_SR16_WHOLE(0, 1, b1) STORM_SR16_OWN01(4, 1, b1) __builtin_amdgcn_sched_barrier(0);
+            STORM_LGKM(1); STORM_SR16_WHOLE(0, 2, b2) STORM_SR16_OWN23(4, 2, b2) __builtin_amdgcn_sched_barrier(0);
+            STORM_LGKM(0); STORM_SR16_WHOLE(0, 3, b3) STORM_SR16_OWN23(4, 3, b3) __builtin_amdgcn_sched_barrier(0);
+            ++d;
         }
 #pragma unroll 1
-        for (; t < kSr16PerTile; ++t) {  // both whole
+        for (; d < strip_rows_diag_end(wave); ++d) {   // both whole
             STORM_SR16_HEAD();
-            STORM_SR16_PAIR(0);
-            STORM_SR16_WHOLE(0, 0)
-            STORM_SR16_WHOLE(4, 0)
-            STORM_SR16_PAIR(2);
-            STORM_SR16_WHOLE(0, 2)
-            STORM_SR16_WHOLE(4, 2)
+            STORM_LGKM(3); STORM_MUL16(0, b0); __builtin_amdgcn_sched_barrier(0);
+            STORM_LGKM(2); STORM_MUL16(1, b1); __builtin_amdgcn_sched_barrier(0);
+            STORM_LGKM(1); STORM_MUL16(2, b2); __builtin_amdgcn_sched_barrier(0);
+            STORM_LGKM(0); STORM_MUL16(3, b3); __builtin_amdgcn_sched_barrier(0);
         }
         __builtin_amdgcn_sched_barrier(0);
-#undef STORM_SR16_PAIR
+        __builtin_amdgcn_s_barrier();    // every wave has read images 0 and 1: the pipelined ring is overlaid on images 0 .. 2
 #undef STORM_SR16_HEAD
 #undef STORM_SR16_OWN23
 #undef STORM_SR16_OWN01
@@ -242,8 +233,8 @@ __global__ __launch_bounds__(256, 4) void strip16_rows_kernel(
     //      — strip16_bits_kernel's convention, with 4 MFMAs in front of the reload there.
     //      Beyond the last stage the next image, the piece and the image written are stale and never consumed: the body is
     //      branch-free.
-    //      Exactness: an accumulator gains at most 2 x 128 = 256 per stage and runs are capped at 4096 stages (+ 8 of the
-    //      diagonal phase): below 2^24.
+    //      Exactness: an accumulator gains at most 2 x 128 = 256 per stage and runs are capped at 4096 stages (+ 8 blocks of
+    //      the diagonal phase): below 2^24.
 #define STORM_SR16_BODY(I, fa, fb, fc)                                                                      \
     {                                                                                                       \
         issue(t + 4u, ((I) + 1) % 3);   /* into the slot of stage t + 1, read an iteration ago */           \
@@ -260,10 +251,18 @@ __global__ __launch_bounds__(256, 4) void strip16_rows_kernel(
         if (t >= T) break;                                                                                  \
         __builtin_amdgcn_s_barrier();                                                                       \
     }
-    if (t < T) {
+    if (T != 0u) {
+        // Invariant at the top of iteration t, in front of its issue: the pieces of stages <= t + 3 have been
+        // issued, those of stages <= t + 1 have landed and been turned into images.
+        STORM_VM2();        // stage 0 (1 and 2 in flight)
+        build_image(0u);
+        STORM_LGKM(0);      // the piece has been read: its slot takes stage 3
+        issue(3u, 0u);
+        STORM_VM2();        // stage 1
+        build_image(1u);
         STORM_LGKM(0);
         __builtin_amdgcn_s_barrier();
-        STORM_FETCH16(b0, 0, 0);   // stage D sits in slot 0
+        STORM_FETCH16(b0, 0, 0);   // stage 0 sits in slot 0
         STORM_FETCH16(b1, 0, 1);
         for (;;) {
             STORM_SR16_BODY(0, b0, b1, b2)   // leaves fragments 0, 1 of the next image in b1, b2
@@ -273,7 +272,7 @@ __global__ __launch_bounds__(256, 4) void strip16_rows_kernel(
         STORM_LGKM(0);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the pieces issued beyond the last stage: none may land in a successor's LDS
-    asm volatile("" ::"v"(b0), "v"(b1), "v"(b2), "v"(wb));   // (every asm load's output lives up to its wait)
+    asm volatile("" ::"v"(b0), "v"(b1), "v"(b2), "v"(b3), "v"(wb));   // (every asm load's output lives up to its wait)
 #undef STORM_SR16_BODY
 #undef STORM_VM2
 #undef STORM_FETCH16V
