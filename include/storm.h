@@ -550,6 +550,48 @@ int STORM_dosage_lag_ldscore_annot_complete_device(STORM_dosage_t* h, int stat, 
                                                    const float* d_annot, uint64_t n_annot, uint64_t annot_ld, float* d_score,
                                                    uint64_t score_ld, uint32_t* d_n_pairs, uint64_t out_rows);
 
+/* Greedy LD pruning and clumping, resolved on the device: n bytes leave it instead of the n x L matrix of
+ * STORM_dosage_pairw_lag_corr. Both are ONE definition — the lexicographically first maximal independent set of a graph:
+ *   vertices  the n rows held.
+ *   edges     rows i < j are adjacent when j - i <= L = min(max_lag, n - 1), j lies in i's window — pos == NULL: the lag
+ *             alone; pos given (n doubles, HOST memory in every form): |pos[j] - pos[i]| <= max_dist, with max_lag 0 taking
+ *             the lag the windows need and a max_lag the windows exceed REFUSED, never clipped: the rule and the planner of
+ *             STORM_dosage_lag_ldscore_annot above — and rho > min_r2, where rho is the FLOAT that
+ *             STORM_dosage_pairw_lag_corr writes for the pair under STORM_DOSAGE_R2 (the _complete calls: the float of
+ *             STORM_dosage_pairw_lag_corr_complete, 3 = STORM_DOSAGE_MISSING). The comparison is between floats and
+ *             strict: a pair exactly at the threshold is not an edge, and a NaN rho is never an edge.
+ *   order     priority: n floats in HOST memory in every form, or NULL. Higher priority comes first, ties go to the lower
+ *             row index; NULL means row order. +-inf is allowed, a NaN priority is refused (the message names the first
+ *             such row). Clumping: priority = -log10(p) or -p. Pruning: NULL, or the minor allele frequency.
+ *   result    walk the rows in that order; a row is KEPT exactly when no already-kept row is adjacent to it.
+ *               keep[i]  = 1 or 0.
+ *               owner[i] = i for a kept row; for a removed row the kept row adjacent to it that comes first in the order —
+ *                          the clump the row belongs to. owner may be NULL; keep is the same bytes either way.
+ * A row without any edge is always kept — also a CONSTANT row, whose pairs are all NaN (_complete: a row with fewer than
+ * two calls, or constant on them): drop monomorphic rows with STORM_dosage_row_sums before or after. With exactly one row,
+ * keep[0] = 1 and owner[0] = 0; with none, nothing is written.
+ * This is the greedy of clumping tools and of priority pruning. It is NOT PLINK's --indep-pairwise, which slides a window
+ * by a step and removes by MAF inside it, and the r^2 here is this library's float: no bit-equality with any outside tool
+ * is claimed. The answer is unique: two calls on unchanged rows return identical bytes.
+ * Exactly elements [0, n) of keep and owner are written (out_len >= n is the length of both), in host memory or, for the
+ * _device forms, in DEVICE memory (complete on return; pos and priority stay host memory). Nothing is written on a
+ * refusal. At most STORM_PRUNE_MAX_ROWS rows: the device resolves the order in one workgroup with a bit per row in its
+ * local memory; more are refused, never truncated. Device scratch: the n x L floats of r^2, n x (2 ceil(L / 32) + 2) words
+ * of adjacency masks and the scratch of the corr call beneath. No CPU fallback. One device slot and one process.
+ * Returns 0; -1 NULL handle, -2 NULL keep, -3 max_lag 0 without positions (said before the size check), -4 out_len < n
+ * (nothing is written), -3 a NaN min_r2, more than STORM_PRUNE_MAX_ROWS rows, a negative or NaN max_dist, a position that
+ * is not finite or decreases, windows that need more than max_lag (the message names both numbers), a NaN priority, or a
+ * device failure (STORM_hip_error says which), -5 several device slots in view. */
+#define STORM_PRUNE_MAX_ROWS 1048576
+int STORM_dosage_lag_prune(STORM_dosage_t* h, float min_r2, uint64_t max_lag, const double* pos, double max_dist,
+                           const float* priority, uint8_t* keep, uint32_t* owner, uint64_t out_len);
+int STORM_dosage_lag_prune_device(STORM_dosage_t* h, float min_r2, uint64_t max_lag, const double* pos, double max_dist,
+                                  const float* priority, uint8_t* d_keep, uint32_t* d_owner, uint64_t out_len);
+int STORM_dosage_lag_prune_complete(STORM_dosage_t* h, float min_r2, uint64_t max_lag, const double* pos, double max_dist,
+                                    const float* priority, uint8_t* keep, uint32_t* owner, uint64_t out_len);
+int STORM_dosage_lag_prune_complete_device(STORM_dosage_t* h, float min_r2, uint64_t max_lag, const double* pos, double max_dist,
+                                           const float* priority, uint8_t* d_keep, uint32_t* d_owner, uint64_t out_len);
+
 /* ------------------------------------------------------------- extensions (not in ref) ---
  * Device selection for the entry points above. By default device 0 computes everything.
  * STORM_hip_set_devices(n, ids): the pair space is sharded over the listed GPUs of this node

@@ -521,6 +521,51 @@ int storm_hip_lag_dosage_ldscore_annot_complete(storm_hip_ctx_t* ctx, const stor
                                                 uint64_t annot_ld, uint64_t n_annot, float* h_score, uint64_t score_ld,
                                                 uint32_t* h_n_pairs);
 
+/* ---- greedy LD pruning and clumping from a band in the lag layout, resolved on the device ---------------------------
+ * storm_hip_lag_band_prune_device: d_vals is any float matrix in the lag layout in DEVICE memory (as in
+ *   storm_hip_lag_band_sums_device: the pair (i, i + 1 + d) at d_vals[i * ld + d], L = min(max_lag, n_rows - 1), ld >= L).
+ *   Rows i < j are ADJACENT when j - i <= L, j <= h_hi[i] and i >= h_lo[j] (both NULL: the lag alone; storm.h's planner
+ *   makes bounds for which the two tests agree), and d_vals' float of the pair > min_r2, compared as floats, strictly (a NaN
+ *   float is never an edge). The rows are walked in the order h_order[0], h_order[1], .. (a permutation of the rows; NULL:
+ *   row order) and a row is KEPT exactly when no row kept before it is adjacent to it — the lexicographically first
+ *   maximal independent set:
+ *     d_keep[i]  = 1 or 0 (uint8_t),
+ *     d_owner[i] = i for a kept row, else the kept row adjacent to it that comes first in the order (may be NULL; d_keep is
+ *                  the same bytes either way).
+ *   Exactly elements [0, n_rows) of the outputs, in DEVICE memory, are written. h_lo, h_hi, h_order are HOST arrays of
+ *   n_rows uint32 in every form; the corner and the pitch columns of d_vals are never read. Three kernels
+ *   (lag_band_threshold_kernel: one adjacency bit mask per row, the band read once; band_mis_resolve_kernel: ONE workgroup,
+ *   the removed bits of all rows in 128 KiB of LDS, hence n_rows <= 2^20; band_mis_owner_kernel: only with d_owner), no
+ *   atomics on floats and nothing that waits for another workgroup: two calls return the same bytes. Device scratch in the
+ *   context's band buffer: n x (2 ceil(L / 32) + 2) words of masks, 2 n words of bounds, 2 n words of order and rank.
+ *   Queued on the context's stream; no host wait: h_lo / h_hi / h_order must stay unchanged until that work is complete
+ *   (storm_hip_ctx_synchronize). The LD r^2 of storm_hip_pairw_lag_similarity_device goes through the same call.
+ * storm_hip_lag_dosage_prune[_complete][_device]: rows of 2-bit dosages: the band of r^2 as in
+ *   storm_hip_lag_dosage_ldscore[_complete] into the context's band buffer, then the kernels above. The host forms copy n
+ *   bytes (and n words when h_owner is given) back and wait; the _device forms take d_keep / d_owner in device memory and
+ *   return with everything queued: h_lo / h_hi / h_order must stay unchanged until that work is complete
+ *   (storm_hip_ctx_synchronize).
+ * STORM_HIP_EINVAL: NULL context, band / matrix or keep, max_lag 0, ld < L, (dosage forms: rows of more than 2^24 values,
+ * n_samples that does not match the row width,) one of lo / hi without the other, more than 2^20 rows (never truncated), a
+ * NaN min_r2, an order that is not a permutation. STORM_HIP_ENOMEM names the buffer. Fewer than two rows: STORM_HIP_OK,
+ * nothing written — except that the dosage forms answer a matrix of exactly ONE row: keep[0] = 1, owner[0] = 0 (a row
+ * without any edge is kept and owns itself), so that storm.h's _device forms have someone to write it. */
+int storm_hip_lag_band_prune_device(storm_hip_ctx_t* ctx, const float* d_vals, uint64_t ld, uint64_t n_rows, uint64_t max_lag,
+                                    float min_r2, const uint32_t* h_lo, const uint32_t* h_hi, const uint32_t* h_order,
+                                    uint8_t* d_keep, uint32_t* d_owner);
+int storm_hip_lag_dosage_prune_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint64_t max_lag,
+                                      float min_r2, const uint32_t* h_lo, const uint32_t* h_hi, const uint32_t* h_order,
+                                      uint8_t* d_keep, uint32_t* d_owner);
+int storm_hip_lag_dosage_prune(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint64_t max_lag, float min_r2,
+                               const uint32_t* h_lo, const uint32_t* h_hi, const uint32_t* h_order, uint8_t* h_keep,
+                               uint32_t* h_owner);
+int storm_hip_lag_dosage_prune_complete_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples,
+                                               uint64_t max_lag, float min_r2, const uint32_t* h_lo, const uint32_t* h_hi,
+                                               const uint32_t* h_order, uint8_t* d_keep, uint32_t* d_owner);
+int storm_hip_lag_dosage_prune_complete(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint64_t max_lag,
+                                        float min_r2, const uint32_t* h_lo, const uint32_t* h_hi, const uint32_t* h_order,
+                                        uint8_t* h_keep, uint32_t* h_owner);
+
 /* sum_c C(n_c,2) on the device — verification identity only, never the product
  * path: used by tests at sizes where a CPU pairwise oracle is infeasible */
 int storm_hip_column_identity(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m,

@@ -475,6 +475,52 @@ class StormDosage:
                                                        _ptr(score), max(c, 1), _ptr(pairs), n)))
         return score[:n, :c], pairs[:n]
 
+    def lag_prune(self, min_r2: float, max_lag: Optional[int] = None, pos=None, max_dist: Optional[float] = None, priority=None,
+                  complete: bool = False, owner: bool = False, device=None):
+        """STORM_dosage_lag_prune[_complete]: keep [n_rows] uint8, or (keep, owner [n_rows] uint32) with owner=True: greedy LD
+        pruning / clumping resolved on the device. Rows i < j are adjacent when they lie within max_lag rows (and, with pos and
+        max_dist, within that distance: computed at the lag the windows need when max_lag is None, refused when they need
+        more than max_lag) and their r2 — pairw_lag_corr's float, complete=True: pairw_lag_corr_complete's — is > min_r2. The
+        rows are walked by priority ([n_rows] floats, higher first, ties to the lower row; None: row order; NaN refused) and
+        a row is kept exactly when no kept row is adjacent to it; owner[i] is i for a kept row, else the kept neighbour that
+        came first. A row without an edge — a constant row too — is kept. Not PLINK's --indep-pairwise.
+        device=: (keep, owner) — 1-D contiguous torch tensors in device memory, uint8 and 32-bit entries (owner may be
+        None), at least n_rows long — receive elements [0, n_rows) instead (complete on return); returns None then."""
+        n = self.n_rows
+        name = "STORM_dosage_lag_prune_complete" if complete else "STORM_dosage_lag_prune"
+        lag = 0 if max_lag is None else int(max_lag)
+        p = None
+        if pos is not None:
+            p = np.ascontiguousarray(pos, dtype=np.float64)
+            if p.shape != (n,):
+                raise ValueError("pos: one coordinate per row")
+            if max_dist is None:
+                raise ValueError("pos needs max_dist")
+        dist = 0.0 if max_dist is None else float(max_dist)
+        p_ptr = None if p is None else _ptr(p if p.size else np.zeros(1))   # (no rows: still "positions given")
+        pr = None
+        if priority is not None:
+            pr = np.ascontiguousarray(priority, dtype=np.float32)
+            if pr.shape != (n,):
+                raise ValueError("priority: one number per row")
+        pr_ptr = None if pr is None else _ptr(pr if pr.size else np.zeros(1, np.float32))
+        if device is not None:
+            d_keep, d_owner = device
+            if d_keep.dim() != 1 or d_keep.element_size() != 1 or d_keep.stride(0) != 1 or not d_keep.is_cuda:
+                raise ValueError("device=: keep is a 1-D contiguous tensor of 8-bit entries in device memory")
+            if d_owner is not None and (d_owner.dim() != 1 or d_owner.element_size() != 4 or d_owner.stride(0) != 1 or not d_owner.is_cuda):
+                raise ValueError("device=: owner is a 1-D contiguous tensor of 32-bit entries in device memory")
+            length = int(d_keep.shape[0]) if d_owner is None else min(int(d_keep.shape[0]), int(d_owner.shape[0]))
+            self._check(name + "_device",
+                        int(getattr(self._lib, name + "_device")(self._h, float(min_r2), lag, p_ptr, dist, pr_ptr,
+                                                                 C.c_void_p(d_keep.data_ptr()),
+                                                                 None if d_owner is None else C.c_void_p(d_owner.data_ptr()), length)))
+            return None
+        keep, own = np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.uint32)
+        self._check(name, int(getattr(self._lib, name)(self._h, float(min_r2), lag, p_ptr, dist, pr_ptr, _ptr(keep),
+                                                       _ptr(own) if owner else None, n)))
+        return (keep[:n], own[:n]) if owner else keep[:n]
+
     def ldscore_window_lag(self, pos, max_dist: float) -> int:
         """STORM_ldscore_window_lag: the lag the windows of these coordinates need under max_dist (host only)."""
         p = np.ascontiguousarray(pos, dtype=np.float64)
@@ -779,6 +825,24 @@ class HipContext:
                                                              score_ld, opt(d_n_pairs)),
               "storm_hip_lag_band_annot_sums_device")
 
+    def lag_band_prune_device(self, d_vals: int, ld: int, n_rows: int, max_lag: int, min_r2: float, d_keep: int,
+                              d_owner: Optional[int] = None, lo: Optional[np.ndarray] = None, hi: Optional[np.ndarray] = None,
+                              order: Optional[np.ndarray] = None) -> None:
+        """storm_hip_lag_band_prune_device: greedy pruning / clumping over a float band in the lag layout at d_vals (n_rows rows
+        of pitch ld, device memory): rows i < j within max_lag, with j <= hi[i] and i >= lo[j] (host uint32 arrays, both or
+        neither) and an entry > min_r2 are adjacent; walked in `order` (a host permutation; None: row order), a row is kept
+        when no kept row is adjacent to it. d_keep (n_rows uint8) and d_owner (n_rows uint32, may be None) are device memory.
+        The C call returns with its work queued and the host arrays still to be read; this wrapper owns their copies and
+        waits."""
+        u32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.uint32)
+        lo, hi, order = u32(lo), u32(hi), u32(order)
+        opt = lambda a: None if a is None else _ptr(a if a.size else np.zeros(1, np.uint32))
+        check(self._lib.storm_hip_lag_band_prune_device(self._h, C.c_void_p(d_vals), ld, n_rows, max_lag, float(min_r2), opt(lo),
+                                                        opt(hi), opt(order), C.c_void_p(d_keep),
+                                                        None if d_owner is None else C.c_void_p(d_owner)),
+              "storm_hip_lag_band_prune_device")
+        self.synchronize()   # (lo / hi / order are this call's own copies: they must outlive the upload)
+
     def matrix(self, n_rows: int, n_words: int) -> "HipMatrix":
         return HipMatrix(self, n_rows, n_words)
 
@@ -1074,6 +1138,32 @@ class HipMatrix:
                                        annot_ld, n_annot, C.c_void_p(d_score), score_ld,
                                        None if d_n_pairs is None else C.c_void_p(d_n_pairs)), name)
         self.ctx.synchronize()   # (lo / hi are this call's own copies: they must outlive the upload)
+
+    def lag_dosage_prune(self, min_r2: float, max_lag: int, n_samples: int, complete: bool = False, owner: bool = False,
+                         lo: Optional[np.ndarray] = None, hi: Optional[np.ndarray] = None, order: Optional[np.ndarray] = None):
+        """storm_hip_lag_dosage_prune[_complete]: keep [n_rows] uint8, or (keep, owner [n_rows] uint32): greedy pruning /
+        clumping over the rows' r2 within max_lag (and within [lo, hi], host uint32 arrays, both or neither), walked in
+        `order` (a host permutation; None: row order)."""
+        name = "storm_hip_lag_dosage_prune_complete" if complete else "storm_hip_lag_dosage_prune"
+        n = self.n_rows
+        u32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.uint32)
+        lo, hi, order = u32(lo), u32(hi), u32(order)
+        keep, own = np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.uint32)
+        check(getattr(self._lib, name)(self.ctx._h, self._h, n_samples, max_lag, float(min_r2), _ptr(lo), _ptr(hi), _ptr(order),
+                                       _ptr(keep), _ptr(own) if owner else None), name)
+        return (keep[:n], own[:n]) if owner else keep[:n]
+
+    def lag_dosage_prune_device(self, d_keep: int, d_owner: Optional[int], min_r2: float, max_lag: int, n_samples: int,
+                                complete: bool = False, lo: Optional[np.ndarray] = None, hi: Optional[np.ndarray] = None,
+                                order: Optional[np.ndarray] = None) -> None:
+        """Same, into buffers in device memory (d_owner may be None); lo / hi / order stay host arrays. The C call returns with
+        its work queued and the host arrays still to be read; this wrapper owns their copies and waits."""
+        name = "storm_hip_lag_dosage_prune_complete_device" if complete else "storm_hip_lag_dosage_prune_device"
+        u32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.uint32)
+        lo, hi, order = u32(lo), u32(hi), u32(order)
+        check(getattr(self._lib, name)(self.ctx._h, self._h, n_samples, max_lag, float(min_r2), _ptr(lo), _ptr(hi), _ptr(order),
+                                       C.c_void_p(d_keep), None if d_owner is None else C.c_void_p(d_owner)), name)
+        self.ctx.synchronize()   # (lo / hi / order are this call's own copies: they must outlive the upload)
 
     def pairw_topk(self, k: int, score: str = "jaccard", n_bits: int = 1, panel_rows: int = 0):
         """(idx [n_rows, k] uint32, val [n_rows, k] float32, or uint32 for score "count"): for each row its k best other rows,

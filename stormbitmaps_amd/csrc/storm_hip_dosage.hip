@@ -718,6 +718,49 @@ static int lag_dosage_ldscore_annot(storm_hip_ctx_t* ctx, const char* who, const
     return STORM_HIP_OK;
 }
 
+// ---- greedy pruning / clumping: the same band, then the kernels of storm_hip_prune.hip over it ----
+// The band of r^2 into the first n x L floats of the band buffer exactly as above; behind it the adjacency masks, the
+// window bounds and the order (h_lo / h_hi / h_order are HOST arrays of n entries in every form, or NULL) and, for a host
+// form, the n owners and the n keep bytes on their way back. All queued on ctx->stream; the host form alone waits.
+static int lag_dosage_prune(storm_hip_ctx_t* ctx, const char* who, const storm_hip_matrix_s* m, uint64_t n_samples, uint64_t max_lag,
+                            float min_r2, bool complete, const uint32_t* h_lo, const uint32_t* h_hi, const uint32_t* h_order,
+                            uint8_t* keep, uint32_t* owner, bool host) {
+    uint64_t lag = 0;
+    if (int rc = check_lag_dosage(who, m, keep, max_lag, ~0ull, &lag)) return rc;
+    if (int rc = check_samples(who, m, n_samples)) return rc;
+    const uint64_t n = m->n_rows;
+    if (int rc = check_lag_band_prune(who, n, h_lo, h_hi, min_r2)) return rc;
+    if (n == 0) return STORM_HIP_OK;
+    STORM_HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 1) {   // a row without any edge is kept and owns itself: no band, no kernel
+        if (host) {
+            keep[0] = 1;
+            if (owner) owner[0] = 0;
+            return STORM_HIP_OK;
+        }
+        STORM_HIP_TRY(hipMemsetAsync(keep, 1, 1, ctx->stream));
+        if (owner) STORM_HIP_TRY(hipMemsetAsync(owner, 0, sizeof(uint32_t), ctx->stream));
+        return STORM_HIP_OK;
+    }
+    const size_t band = (size_t)n * lag, scratch = lag_band_prune_scratch_words(n, lag, h_lo != nullptr, h_order != nullptr);
+    const size_t words = band + scratch + (host ? n + (n + 3) / 4 : 0);
+    if (int rc = ctx->d_band.ensure(words * sizeof(uint32_t), "lag_dosage_prune: the band of r^2 and the adjacency masks")) return rc;
+    uint32_t* const d_band = ctx->d_band.d;
+    if (int rc = complete ? lag_dosage_corr_complete_queued(ctx, m, STORM_HIP_DOSAGE_R2, n_samples, max_lag, d_band, lag)
+                          : lag_dosage_corr_queued(ctx, m, STORM_HIP_DOSAGE_R2, n_samples, max_lag, d_band, lag))
+        return rc;
+    uint32_t* const d_owner = host ? (owner ? d_band + band + scratch : nullptr) : owner;
+    uint8_t* const d_keep = host ? reinterpret_cast<uint8_t*>(d_band + band + scratch + n) : keep;
+    if (int rc = launch_lag_band_prune(ctx, who, reinterpret_cast<const float*>(d_band), lag, n, lag, min_r2, h_lo, h_hi, h_order,
+                                       d_keep, d_owner, d_band + band))
+        return rc;
+    if (!host) return STORM_HIP_OK;
+    STORM_HIP_TRY(hipMemcpyAsync(keep, d_keep, n, hipMemcpyDeviceToHost, ctx->stream));
+    if (owner) STORM_HIP_TRY(hipMemcpyAsync(owner, d_owner, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return STORM_HIP_OK;
+}
+
 }  // namespace storm
 
 using namespace storm;
@@ -1136,6 +1179,46 @@ int storm_hip_lag_dosage_ldscore_annot_complete(storm_hip_ctx_t* ctx, const stor
         if (check_ctx(ctx)) return STORM_HIP_EINVAL;
         return lag_dosage_ldscore_annot(ctx, "lag_dosage_ldscore_annot_complete", m, stat, n_samples, max_lag, true, h_lo, h_hi,
                                         h_annot, annot_ld, n_annot, h_score, score_ld, h_n_pairs, true);
+    });
+}
+
+int storm_hip_lag_dosage_prune_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint64_t max_lag,
+                                      float min_r2, const uint32_t* h_lo, const uint32_t* h_hi, const uint32_t* h_order,
+                                      uint8_t* d_keep, uint32_t* d_owner) {
+    return guarded("storm_hip_lag_dosage_prune_device", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        return lag_dosage_prune(ctx, "lag_dosage_prune", m, n_samples, max_lag, min_r2, false, h_lo, h_hi, h_order, d_keep, d_owner,
+                                false);
+    });
+}
+
+int storm_hip_lag_dosage_prune(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint64_t max_lag, float min_r2,
+                               const uint32_t* h_lo, const uint32_t* h_hi, const uint32_t* h_order, uint8_t* h_keep,
+                               uint32_t* h_owner) {
+    return guarded("storm_hip_lag_dosage_prune", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        return lag_dosage_prune(ctx, "lag_dosage_prune", m, n_samples, max_lag, min_r2, false, h_lo, h_hi, h_order, h_keep, h_owner,
+                                true);
+    });
+}
+
+int storm_hip_lag_dosage_prune_complete_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples,
+                                               uint64_t max_lag, float min_r2, const uint32_t* h_lo, const uint32_t* h_hi,
+                                               const uint32_t* h_order, uint8_t* d_keep, uint32_t* d_owner) {
+    return guarded("storm_hip_lag_dosage_prune_complete_device", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        return lag_dosage_prune(ctx, "lag_dosage_prune_complete", m, n_samples, max_lag, min_r2, true, h_lo, h_hi, h_order, d_keep,
+                                d_owner, false);
+    });
+}
+
+int storm_hip_lag_dosage_prune_complete(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint64_t max_lag,
+                                        float min_r2, const uint32_t* h_lo, const uint32_t* h_hi, const uint32_t* h_order,
+                                        uint8_t* h_keep, uint32_t* h_owner) {
+    return guarded("storm_hip_lag_dosage_prune_complete", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        return lag_dosage_prune(ctx, "lag_dosage_prune_complete", m, n_samples, max_lag, min_r2, true, h_lo, h_hi, h_order, h_keep,
+                                h_owner, true);
     });
 }
 

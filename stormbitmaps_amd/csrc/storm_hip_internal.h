@@ -315,6 +315,14 @@ int launch_lag_band_annot_sums(storm_hip_ctx_t* ctx, const float* d_vals, uint64
                                uint64_t n_const, const uint32_t* d_nobs, uint64_t nobs_row_pitch, uint64_t nobs_col_stride,
                                const uint32_t* d_lo, const uint32_t* d_hi, const float* d_annot, uint64_t annot_ld,
                                uint64_t n_annot, float* d_score, uint64_t score_ld, uint32_t* d_n_pairs);
+// greedy pruning / clumping from a band in the lag layout (storm_hip_prune.hip): the checks the prune calls share behind
+// their own NULL / max_lag / ld checks; the words of scratch the kernels need; the kernels themselves with that scratch at
+// d_scratch, queued (n_rows >= 2, lag = min(max_lag, n_rows - 1); h_lo / h_hi / h_order are HOST arrays or NULL)
+int check_lag_band_prune(const char* who, uint64_t n_rows, const uint32_t* h_lo, const uint32_t* h_hi, float min_r2);
+size_t lag_band_prune_scratch_words(uint64_t n_rows, uint64_t lag, bool windows, bool order);
+int launch_lag_band_prune(storm_hip_ctx_t* ctx, const char* who, const float* d_vals, uint64_t ld, uint64_t n_rows, uint64_t lag,
+                          float min_r2, const uint32_t* h_lo, const uint32_t* h_hi, const uint32_t* h_order, uint8_t* d_keep,
+                          uint32_t* d_owner, uint32_t* d_scratch);
 void release_mfma_state(storm_hip_ctx_t* ctx);
 // releases what was put off (storm_hip_ctx_s::deferred_free); `aged`: only what an earlier call left behind
 void drain_deferred(storm_hip_ctx_t* ctx, bool aged);
