@@ -51,7 +51,7 @@ int storm_hip_device_arch(int device, char* buf, size_t buflen);
 int storm_hip_device_pci_bus_id(int device, char* buf, size_t buflen);
 
 /* ---- context: device, stream, reusable workspace ----
- * The stream contract (tests/test_gpu_streams.py):
+ * The stream contract (tests/test_gpu_streams.py; for the lag-dosage, LD-score and pruning calls tests/test_gpu_streams_ld.py):
  *   - Everything a context enqueues — kernels, zero fills, copies, the zeroing of its own workspace at creation — goes on its
  *     stream (`stream` of storm_hip_ctx_create, later storm_hip_ctx_set_stream's; NULL = the default stream). The one
  *     internal second stream (the panel copies of storm_hip_pairw_dense_upload) is ordered against it by events, both ways.
@@ -61,9 +61,17 @@ int storm_hip_device_pci_bus_id(int device, char* buf, size_t buflen);
  *       storm_hip_matrix_create (its zero fill), storm_hip_matrix_clear, storm_hip_matrix_fill_synthetic,
  *       storm_hip_matrix_import, storm_hip_matrix_resize when it shrinks (a growing resize waits),
  *       every `_launch` (storm_hip_pairw_dense_launch), every `_begin` (storm_hip_pairw_dense_begin, _pairw_sparse_begin,
- *       _pairw_matrix_band_begin), and the primitives that say so (storm_hip_similarity_finish_device, _finish_lag_device,
- *       storm_hip_topk_rows_device).
+ *       _pairw_matrix_band_begin), the primitives that say so (storm_hip_similarity_finish_device, _finish_lag_device,
+ *       storm_hip_topk_rows_device, storm_hip_dosage_finish_lag_device, storm_hip_lag_band_sums_device,
+ *       storm_hip_lag_band_annot_sums_device, storm_hip_lag_band_prune_device), and the `_device` forms of the calls composed of
+ *       them: storm_hip_lag_dosage_ldscore[_complete]_device, storm_hip_lag_dosage_ldscore_annot[_complete]_device and
+ *       storm_hip_lag_dosage_prune[_complete]_device — unlike storm_hip_pairw_lag_dosage_*_device, whose band they reduce and
+ *       which are complete on return.
  *     A `_begin` is finished by its `_end` on the same context, whatever stream the context has by then.
+ *   - HOST arrays handed to an asynchronous call (h_lo, h_hi, h_order of the LD-score and pruning calls, in every form) are
+ *     read by copies queued on the context's stream: they must stay allocated and unchanged until that work is complete
+ *     (storm_hip_ctx_synchronize, or a wait of the caller's for the stream); the outputs are final then, whatever happens to
+ *     the arrays afterwards. The host forms of these calls wait themselves.
  *   - storm_hip_ctx_set_stream: work enqueued through the context after the call is ordered after ALL work enqueued through it
  *     before the call (an event recorded on the stream that is left, which the new stream waits for; if no event can be made
  *     the call waits for the old stream). The context's workspace (partial-sum slots, result word, mailbox, cached work lists)

@@ -804,7 +804,8 @@ class HipContext:
                              nobs_col_stride: int = 1) -> None:
         """storm_hip_lag_band_sums_device: per-row sums over both sides of a float band in the lag layout at d_vals (n_rows rows
         of pitch ld, device memory) into d_score / d_n_pairs (n_rows entries each, device memory); N of "r2_adj" is n_const
-        or the uint32 at d_nobs[i * nobs_row_pitch + d * nobs_col_stride]. Queued on the context's stream."""
+        or the uint32 at d_nobs[i * nobs_row_pitch + d * nobs_col_stride]. The C call returns with its work
+        queued: order later work on the context's stream or call `synchronize()`."""
         check(self._lib.storm_hip_lag_band_sums_device(self._h, C.c_void_p(d_vals), ld, n_rows, max_lag, LDSCORE_STATS[stat], n_const,
                                                        None if d_nobs is None else C.c_void_p(d_nobs), nobs_row_pitch,
                                                        nobs_col_stride, C.c_void_p(d_score),
@@ -817,7 +818,8 @@ class HipContext:
                                    d_lo: Optional[int] = None, d_hi: Optional[int] = None) -> None:
         """storm_hip_lag_band_annot_sums_device: the band at d_vals times the n_rows x n_annot annotations at d_annot, within
         the windows [d_lo[i], d_hi[i]] (uint32, both or neither: the whole lag), into d_score (pitch score_ld) and d_n_pairs;
-        everything in device memory. Queued on the context's stream."""
+        everything in device memory. The C call returns with its work
+        queued: order later work on the context's stream or call `synchronize()`."""
         opt = lambda p: None if p is None else C.c_void_p(p)
         check(self._lib.storm_hip_lag_band_annot_sums_device(self._h, C.c_void_p(d_vals), ld, n_rows, max_lag, LDSCORE_STATS[stat],
                                                              n_const, opt(d_nobs), nobs_row_pitch, nobs_col_stride, opt(d_lo),
@@ -1104,7 +1106,8 @@ class HipMatrix:
 
     def lag_dosage_ldscore_device(self, d_score: int, d_n_pairs: Optional[int], max_lag: int, n_samples: int, stat: str = "r2",
                                   complete: bool = False) -> None:
-        """Same, into device buffers of n_rows entries each (d_n_pairs may be None); queued on the context's stream."""
+        """Same, into device buffers of n_rows entries each (d_n_pairs may be None). The C call returns with its work
+        queued: order later work on the context's stream or call `synchronize()`."""
         name = "storm_hip_lag_dosage_ldscore_complete_device" if complete else "storm_hip_lag_dosage_ldscore_device"
         check(getattr(self._lib, name)(self.ctx._h, self._h, LDSCORE_STATS[stat], n_samples, max_lag, C.c_void_p(d_score),
                                        None if d_n_pairs is None else C.c_void_p(d_n_pairs)), name)
