@@ -234,6 +234,26 @@ def _device_window(device, n: int):
     return C.c_void_p(device.data_ptr()), int(device.shape[0]), int(device.stride(0))
 
 
+def _device_vector(t, message: str, entry_bytes: int = 4) -> None:
+    """ValueError(message) unless t is None or a 1-D contiguous torch tensor of entry_bytes-byte entries in device memory"""
+    if t is not None and (t.dim() != 1 or t.element_size() != entry_bytes or t.stride(0) != 1 or not t.is_cuda):
+        raise ValueError(message)
+
+
+def _window_args(n: int, max_lag: Optional[int], pos, max_dist: Optional[float]):
+    """(max_lag, pos, max_dist) of a windowed band call as the C call takes them: max_lag None is 0 ("what the windows
+    need"), pos is n float64 coordinates or NULL, and comes with max_dist"""
+    p = None
+    if pos is not None:
+        p = np.ascontiguousarray(pos, dtype=np.float64)
+        if p.shape != (n,):
+            raise ValueError("pos: one coordinate per row")
+        if max_dist is None:
+            raise ValueError("pos needs max_dist")
+    p_ptr = None if p is None else _ptr(p if p.size else np.zeros(1))   # (no rows: still "positions given")
+    return 0 if max_lag is None else int(max_lag), p_ptr, 0.0 if max_dist is None else float(max_dist)
+
+
 class StormDosage:
     """STORM_dosage_t (storm.h, extension): rows of n_samples 2-bit dosages (0 / 1 / 2 copies of an allele per sample; 3 is an
     ordinary value), their per-pair dot products and genotype correlations (PLINK --r / --r2) on the device. In
@@ -414,8 +434,7 @@ class StormDosage:
         if device is not None:
             d_score, d_pairs = device
             for t in (d_score, d_pairs):
-                if t is not None and (t.dim() != 1 or t.element_size() != 4 or t.stride(0) != 1 or not t.is_cuda):
-                    raise ValueError("device=: 1-D contiguous tensors of 32-bit entries in device memory")
+                _device_vector(t, "device=: 1-D contiguous tensors of 32-bit entries in device memory")
             length = int(d_score.shape[0]) if d_pairs is None else min(int(d_score.shape[0]), int(d_pairs.shape[0]))
             self._check(name + "_device",
                         int(getattr(self._lib, name + "_device")(self._h, code, max_lag, C.c_void_p(d_score.data_ptr()),
@@ -439,23 +458,13 @@ class StormDosage:
         n = self.n_rows
         name = "STORM_dosage_lag_ldscore_annot_complete" if complete else "STORM_dosage_lag_ldscore_annot"
         code = LDSCORE_STATS[stat]
-        lag = 0 if max_lag is None else int(max_lag)
-        p = None
-        if pos is not None:
-            p = np.ascontiguousarray(pos, dtype=np.float64)
-            if p.shape != (n,):
-                raise ValueError("pos: one coordinate per row")
-            if max_dist is None:
-                raise ValueError("pos needs max_dist")
-        dist = 0.0 if max_dist is None else float(max_dist)
-        p_ptr = None if p is None else _ptr(p if p.size else np.zeros(1))   # (no rows: still "positions given")
+        lag, p_ptr, dist = _window_args(n, max_lag, pos, max_dist)
         if device is not None:
             d_score, d_pairs = device
             for t in (annot, d_score):
                 if t.dim() != 2 or t.element_size() != 4 or not t.is_floating_point() or t.stride(1) != 1 or not t.is_cuda:
                     raise ValueError("device=: annot and score are 2-D float32 tensors with unit column stride in device memory")
-            if d_pairs is not None and (d_pairs.dim() != 1 or d_pairs.element_size() != 4 or d_pairs.stride(0) != 1 or not d_pairs.is_cuda):
-                raise ValueError("device=: n_pairs is a 1-D contiguous tensor of 32-bit entries in device memory")
+            _device_vector(d_pairs, "device=: n_pairs is a 1-D contiguous tensor of 32-bit entries in device memory")
             if int(annot.shape[0]) < n or int(d_score.shape[1]) < int(annot.shape[1]):
                 raise ValueError("device=: annot has a row per row of the container, score a column per column of annot")
             rows = int(d_score.shape[0]) if d_pairs is None else min(int(d_score.shape[0]), int(d_pairs.shape[0]))
@@ -488,16 +497,7 @@ class StormDosage:
         None), at least n_rows long — receive elements [0, n_rows) instead (complete on return); returns None then."""
         n = self.n_rows
         name = "STORM_dosage_lag_prune_complete" if complete else "STORM_dosage_lag_prune"
-        lag = 0 if max_lag is None else int(max_lag)
-        p = None
-        if pos is not None:
-            p = np.ascontiguousarray(pos, dtype=np.float64)
-            if p.shape != (n,):
-                raise ValueError("pos: one coordinate per row")
-            if max_dist is None:
-                raise ValueError("pos needs max_dist")
-        dist = 0.0 if max_dist is None else float(max_dist)
-        p_ptr = None if p is None else _ptr(p if p.size else np.zeros(1))   # (no rows: still "positions given")
+        lag, p_ptr, dist = _window_args(n, max_lag, pos, max_dist)
         pr = None
         if priority is not None:
             pr = np.ascontiguousarray(priority, dtype=np.float32)
@@ -506,10 +506,8 @@ class StormDosage:
         pr_ptr = None if pr is None else _ptr(pr if pr.size else np.zeros(1, np.float32))
         if device is not None:
             d_keep, d_owner = device
-            if d_keep.dim() != 1 or d_keep.element_size() != 1 or d_keep.stride(0) != 1 or not d_keep.is_cuda:
-                raise ValueError("device=: keep is a 1-D contiguous tensor of 8-bit entries in device memory")
-            if d_owner is not None and (d_owner.dim() != 1 or d_owner.element_size() != 4 or d_owner.stride(0) != 1 or not d_owner.is_cuda):
-                raise ValueError("device=: owner is a 1-D contiguous tensor of 32-bit entries in device memory")
+            _device_vector(d_keep, "device=: keep is a 1-D contiguous tensor of 8-bit entries in device memory", 1)
+            _device_vector(d_owner, "device=: owner is a 1-D contiguous tensor of 32-bit entries in device memory")
             length = int(d_keep.shape[0]) if d_owner is None else min(int(d_keep.shape[0]), int(d_owner.shape[0]))
             self._check(name + "_device",
                         int(getattr(self._lib, name + "_device")(self._h, float(min_r2), lag, p_ptr, dist, pr_ptr,

@@ -19,3 +19,20 @@ struct STORM_dosage_s {
 
 /* the device copy brought up to date on the calling thread's slot (the caller holds the lock): NULL with the reason reported */
 storm_hip_matrix_t* storm_dosage_mirror(STORM_dosage_t* h, storm_hip_ctx_t** ctx_out);
+
+/* ---- storm_dosage_band.c: shared by the calls on the band of r^2. Each returns 0, or -3 with the reason reported; the
+ * caller holds the lock. ---- */
+
+/* a shim call's return code `rc` as storm.h's: a _device form (`device`) returns with its work queued, and a caller of
+ * storm.h has no handle on that stream, so it is waited for here; a failure is reported under the shim call's `name` */
+int storm_dosage_shim_result(storm_hip_ctx_t* ctx, int rc, int device, const char* name);
+
+/* stat is neither STORM_LDSCORE_R2 nor _R2_ADJ, or the complete-case adjusted statistic has fewer than 3 samples */
+int storm_dosage_ldscore_stat_refusal(const char* who, int stat, int complete, uint64_t n_samples);
+
+/* (max_lag, pos, max_dist) into the lag to ask the device for and the rows' windows. *plan: NULL, or malloc'd n x (2 +
+ * extra_words_per_row) words for the caller to free in every case: lo, then hi (filled where pos is given), then the
+ * caller's own. It is allocated where there are rows and positions or extra words. *lag: max_lag, or with max_lag 0 what
+ * the windows need. Refused: no memory, positions or max_dist the planner refuses, windows wider than a max_lag > 0. */
+int storm_dosage_band_windows(const char* who, uint64_t n, uint64_t max_lag, const double* pos, double max_dist,
+                              unsigned extra_words_per_row, uint32_t** plan, uint64_t* lag);

@@ -35,11 +35,8 @@ static int lag_run(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int what, 
             rc = device ? storm_hip_pairw_lag_dosage_corr_complete_device(ctx, m, measure, n_samples, max_lag, (float*)out, out_ld)
                         : storm_hip_pairw_lag_dosage_corr_complete(ctx, m, measure, n_samples, max_lag, (float*)out, out_ld);
     }
-    if (rc != STORM_HIP_OK) {
-        storm_host_device_error(names[what]);
-        return -3;
-    }
-    return 0;
+    /* (device 0 in every form: these calls read no host array after they return, so a _device form is not waited for) */
+    return storm_dosage_shim_result(ctx, rc, 0, names[what]);
 }
 
 static int dosage_lag(STORM_dosage_t* h, int what, int measure, uint64_t max_lag, void* out, uint64_t out_rows, uint64_t out_ld,

@@ -22,13 +22,7 @@ static int ldscore_run(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int st
     else
         rc = device ? storm_hip_lag_dosage_ldscore_device(ctx, m, stat, n_samples, max_lag, score, n_pairs)
                     : storm_hip_lag_dosage_ldscore(ctx, m, stat, n_samples, max_lag, score, n_pairs);
-    /* the shim's _device forms return with their work queued; a caller of storm.h has no handle on that stream: wait here */
-    if (rc == STORM_HIP_OK && device) rc = storm_hip_ctx_synchronize(ctx);
-    if (rc != STORM_HIP_OK) {
-        storm_host_device_error(names[complete]);
-        return -3;
-    }
-    return 0;
+    return storm_dosage_shim_result(ctx, rc, device, names[complete]);
 }
 
 static int dosage_ldscore(STORM_dosage_t* h, int stat, uint64_t max_lag, float* score, uint32_t* n_pairs, uint64_t out_len,
@@ -45,18 +39,7 @@ static int dosage_ldscore(STORM_dosage_t* h, int stat, uint64_t max_lag, float* 
         storm_host_error(msg);
         rc = -3;
     }
-    if (!rc && stat != STORM_LDSCORE_R2 && stat != STORM_LDSCORE_R2_ADJ) {
-        char msg[160];
-        snprintf(msg, sizeof(msg), "%s: stat must be 0 (STORM_LDSCORE_R2) or 1 (STORM_LDSCORE_R2_ADJ)", who);
-        storm_host_error(msg);
-        rc = -3;
-    }
-    if (!rc && !complete && stat == STORM_LDSCORE_R2_ADJ && h->n_samples < 3) {
-        char msg[200];
-        snprintf(msg, sizeof(msg), "%s: STORM_LDSCORE_R2_ADJ divides by n_samples - 2: at least 3 samples", who);
-        storm_host_error(msg);
-        rc = -3;
-    }
+    if (!rc) rc = storm_dosage_ldscore_stat_refusal(who, stat, complete, h->n_samples);
     if (!rc && n >= 2) {
         storm_hip_ctx_t* ctx = NULL;
         const storm_hip_matrix_t* m = storm_dosage_mirror(h, &ctx);

@@ -1,9 +1,9 @@
 /* storm_dosage_ldscore_annot.c — the dosage container's stratified LD scores in a distance window (storm.h:
- * STORM_dosage_lag_ldscore_annot, _annot_complete, their _device forms and STORM_ldscore_window_lag): for every row and
- * every annotation column the sum of a[j][c] r^2(i, j) over the rows j of row i's window, reduced on the device from the band
- * storm_dosage_lag.c's corr calls write (storm_hip.h: storm_hip_lag_dosage_ldscore_annot). The windows come from the
- * host-only planner (storm_ldscore_window.h); the container, its device copy and the locked paths are storm_dosage.c's; the
- * order of the checks is storm_dosage_ldscore.c's, then the new ones. No CPU fallback. */
+ * STORM_dosage_lag_ldscore_annot, _annot_complete and their _device forms): for every row and every annotation column the sum
+ * of a[j][c] r^2(i, j) over the rows j of row i's window, reduced on the device from the band storm_dosage_lag.c's corr
+ * calls write (storm_hip.h: storm_hip_lag_dosage_ldscore_annot). The windows are resolved in storm_dosage_band.c; the
+ * container, its device copy and the locked paths are storm_dosage.c's; the order of the checks is storm_dosage_ldscore.c's,
+ * then the new ones. No CPU fallback. */
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -13,40 +13,6 @@
 #include "storm_hip.h"
 #include "storm_host_internal.h"
 #include "storm_dosage_internal.h"
-#include "storm_ldscore_window.h"
-
-/* the planner's refusal in words: -3, or 0 */
-static int window_refusal(const char* who, int code, const double* pos, uint64_t bad) {
-    char msg[240];
-    switch (code) {
-        case STORM_LDSCORE_WINDOW_OK: return 0;
-        case STORM_LDSCORE_WINDOW_BAD_DIST: snprintf(msg, sizeof(msg), "%s: max_dist must be a number >= 0 (+inf: every row)", who); break;
-        case STORM_LDSCORE_WINDOW_NOT_FINITE:
-            snprintf(msg, sizeof(msg), "%s: pos[%llu] is not finite", who, (unsigned long long)bad);
-            break;
-        case STORM_LDSCORE_WINDOW_DECREASING:
-            snprintf(msg, sizeof(msg), "%s: pos[%llu] = %.17g is less than pos[%llu] = %.17g: positions must not decrease", who,
-                     (unsigned long long)bad, pos[bad], (unsigned long long)(bad - 1), pos[bad - 1]);
-            break;
-        default: snprintf(msg, sizeof(msg), "%s: more than 2^32 - 1 rows", who); break;
-    }
-    storm_host_error(msg);
-    return -3;
-}
-
-int STORM_ldscore_window_lag(const double* pos, uint64_t n, double max_dist, uint64_t* lag) {
-    if (!lag || (!pos && n)) return -2;
-    uint64_t need = 0, bad = 0;
-    const int code = storm_ldscore_window_plan(pos, n, max_dist, NULL, NULL, &need, &bad);
-    if (code) {
-        storm_host_lock();
-        const int rc = window_refusal("STORM_ldscore_window_lag", code, pos, bad);
-        storm_host_unlock();
-        return rc;
-    }
-    *lag = need;
-    return 0;
-}
 
 /* the shim call on the container's device copy: 0 or -3 */
 static int annot_run(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int stat, uint64_t n_samples, uint64_t lag,
@@ -64,14 +30,8 @@ static int annot_run(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int stat
                                                                 score_ld, n_pairs)
                     : storm_hip_lag_dosage_ldscore_annot(ctx, m, stat, n_samples, lag, lo, hi, annot, annot_ld, n_annot, score,
                                                          score_ld, n_pairs);
-    /* the shim's _device forms return with their work queued, lo / hi still being read; a caller of storm.h has no handle on
-     * that stream: wait here */
-    if (rc == STORM_HIP_OK && device) rc = storm_hip_ctx_synchronize(ctx);
-    if (rc != STORM_HIP_OK) {
-        storm_host_device_error(names[complete]);
-        return -3;
-    }
-    return 0;
+    /* (a _device form is waited for: it returns with lo / hi still being read) */
+    return storm_dosage_shim_result(ctx, rc, device, names[complete]);
 }
 
 static int dosage_ldscore_annot(STORM_dosage_t* h, int stat, uint64_t max_lag, const double* pos, double max_dist, const float* annot,
@@ -90,16 +50,7 @@ static int dosage_ldscore_annot(STORM_dosage_t* h, int stat, uint64_t max_lag, c
         storm_host_error(msg);
         rc = -3;
     }
-    if (!rc && stat != STORM_LDSCORE_R2 && stat != STORM_LDSCORE_R2_ADJ) {
-        snprintf(msg, sizeof(msg), "%s: stat must be 0 (STORM_LDSCORE_R2) or 1 (STORM_LDSCORE_R2_ADJ)", who);
-        storm_host_error(msg);
-        rc = -3;
-    }
-    if (!rc && !complete && stat == STORM_LDSCORE_R2_ADJ && h->n_samples < 3) {
-        snprintf(msg, sizeof(msg), "%s: STORM_LDSCORE_R2_ADJ divides by n_samples - 2: at least 3 samples", who);
-        storm_host_error(msg);
-        rc = -3;
-    }
+    if (!rc) rc = storm_dosage_ldscore_stat_refusal(who, stat, complete, h->n_samples);
     /* ---- the new checks */
     if (!rc && (n_annot < 1 || n_annot > STORM_LDSCORE_MAX_ANNOT)) {
         snprintf(msg, sizeof(msg), "%s: n_annot = %llu: 1 .. %d annotation columns", who, (unsigned long long)n_annot,
@@ -108,30 +59,9 @@ static int dosage_ldscore_annot(STORM_dosage_t* h, int stat, uint64_t max_lag, c
         rc = -3;
     }
     if (!rc && (annot_ld < n_annot || score_ld < n_annot)) rc = -4;
-    uint32_t* bounds = NULL;   /* lo, then hi */
+    uint32_t* bounds = NULL;   /* lo, then hi: where positions are given */
     uint64_t lag = max_lag;
-    if (!rc && pos) {
-        uint64_t need = 0, bad = 0;
-        if (n) {
-            bounds = (uint32_t*)malloc((size_t)n * 2u * sizeof(uint32_t));
-            if (!bounds) {
-                snprintf(msg, sizeof(msg), "%s: out of host memory for the windows of %llu rows", who, (unsigned long long)n);
-                storm_host_error(msg);
-                rc = -3;
-            }
-        }
-        if (!rc) {
-            const int code = storm_ldscore_window_plan(pos, n, max_dist, bounds, bounds ? bounds + n : NULL, &need, &bad);
-            rc = window_refusal(who, code, pos, bad);
-        }
-        if (!rc && max_lag != 0 && need > max_lag) {
-            snprintf(msg, sizeof(msg), "%s: the windows need a lag of %llu rows, max_lag is %llu (0 takes what the windows need)", who,
-                     (unsigned long long)need, (unsigned long long)max_lag);
-            storm_host_error(msg);
-            rc = -3;
-        }
-        if (!rc && max_lag == 0) lag = need ? need : 1u;   /* (no row has a neighbour: the windows still say so) */
-    }
+    if (!rc) rc = storm_dosage_band_windows(who, n, max_lag, pos, max_dist, 0, &bounds, &lag);
     if (!rc && !device) {
         for (uint64_t i = 0; i < n && !rc; ++i)
             for (uint64_t c = 0; c < n_annot; ++c)

@@ -1,8 +1,8 @@
 /* storm_dosage_prune.c — greedy LD pruning and clumping on the dosage container (storm.h: STORM_dosage_lag_prune, _complete
  * and their _device forms): the rows kept when the rows are walked in order of priority and a row is dropped as soon as a
  * kept row within its window exceeds min_r2 with it, resolved on the device from the band storm_dosage_lag.c's corr calls
- * write (storm_hip.h: storm_hip_lag_dosage_prune). The windows come from the host-only planner storm_ldscore_window.h, the
- * order from storm_prune_order.h; the container, its device copy and the locked paths are storm_dosage.c's; the order of the
+ * write (storm_hip.h: storm_hip_lag_dosage_prune). The windows are resolved in storm_dosage_band.c, the order comes from the
+ * host-only planner storm_prune_order.h; the container, its device copy and the locked paths are storm_dosage.c's; the order of the
  * checks is storm_dosage_ldscore_annot.c's. No CPU fallback. */
 #include <math.h>
 #include <stdint.h>
@@ -13,27 +13,7 @@
 #include "storm_hip.h"
 #include "storm_host_internal.h"
 #include "storm_dosage_internal.h"
-#include "storm_ldscore_window.h"
 #include "storm_prune_order.h"
-
-/* the window planner's refusal in words: -3, or 0 */
-static int window_refusal(const char* who, int code, const double* pos, uint64_t bad) {
-    char msg[240];
-    switch (code) {
-        case STORM_LDSCORE_WINDOW_OK: return 0;
-        case STORM_LDSCORE_WINDOW_BAD_DIST: snprintf(msg, sizeof(msg), "%s: max_dist must be a number >= 0 (+inf: every row)", who); break;
-        case STORM_LDSCORE_WINDOW_NOT_FINITE:
-            snprintf(msg, sizeof(msg), "%s: pos[%llu] is not finite", who, (unsigned long long)bad);
-            break;
-        case STORM_LDSCORE_WINDOW_DECREASING:
-            snprintf(msg, sizeof(msg), "%s: pos[%llu] = %.17g is less than pos[%llu] = %.17g: positions must not decrease", who,
-                     (unsigned long long)bad, pos[bad], (unsigned long long)(bad - 1), pos[bad - 1]);
-            break;
-        default: snprintf(msg, sizeof(msg), "%s: more than 2^32 - 1 rows", who); break;
-    }
-    storm_host_error(msg);
-    return -3;
-}
 
 /* the shim call on the container's device copy: 0 or -3 */
 static int prune_run(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint64_t lag, float min_r2,
@@ -47,14 +27,8 @@ static int prune_run(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t
     else
         rc = device ? storm_hip_lag_dosage_prune_device(ctx, m, n_samples, lag, min_r2, lo, hi, order, keep, owner)
                     : storm_hip_lag_dosage_prune(ctx, m, n_samples, lag, min_r2, lo, hi, order, keep, owner);
-    /* the shim's _device forms return with their work queued, lo / hi / order still being read; a caller of storm.h has no
-     * handle on that stream: wait here */
-    if (rc == STORM_HIP_OK && device) rc = storm_hip_ctx_synchronize(ctx);
-    if (rc != STORM_HIP_OK) {
-        storm_host_device_error(names[complete]);
-        return -3;
-    }
-    return 0;
+    /* (a _device form is waited for: it returns with lo / hi / order still being read) */
+    return storm_dosage_shim_result(ctx, rc, device, names[complete]);
 }
 
 static int dosage_prune(STORM_dosage_t* h, float min_r2, uint64_t max_lag, const double* pos, double max_dist, const float* priority,
@@ -85,26 +59,8 @@ static int dosage_prune(STORM_dosage_t* h, float min_r2, uint64_t max_lag, const
     }
     uint32_t* plan = NULL;   /* lo, then hi, then the order */
     uint64_t lag = max_lag;
-    if (!rc && n && (pos || priority)) {
-        plan = (uint32_t*)malloc((size_t)n * 3u * sizeof(uint32_t));
-        if (!plan) {
-            snprintf(msg, sizeof(msg), "%s: out of host memory for the windows and the order of %llu rows", who, (unsigned long long)n);
-            storm_host_error(msg);
-            rc = -3;
-        }
-    }
-    if (!rc && pos) {
-        uint64_t need = 0, bad = 0;
-        const int code = storm_ldscore_window_plan(pos, n, max_dist, plan, plan ? plan + n : NULL, &need, &bad);
-        rc = window_refusal(who, code, pos, bad);
-        if (!rc && max_lag != 0 && need > max_lag) {
-            snprintf(msg, sizeof(msg), "%s: the windows need a lag of %llu rows, max_lag is %llu (0 takes what the windows need)", who,
-                     (unsigned long long)need, (unsigned long long)max_lag);
-            storm_host_error(msg);
-            rc = -3;
-        }
-        if (!rc && max_lag == 0) lag = need ? need : 1u;   /* (no row has a neighbour: the windows still say so) */
-    }
+    /* (one buffer of three words per row as soon as either the windows or the order want one) */
+    if (!rc) rc = storm_dosage_band_windows(who, n, max_lag, pos, max_dist, pos || priority, &plan, &lag);
     if (!rc && priority && n) {
         uint64_t bad = 0;
         const int code = storm_prune_order_plan(priority, n, plan + 2 * n, NULL, &bad);

@@ -566,7 +566,7 @@ static int lag_dosage_nobs_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s
     return launch_pairw_lag_dosage_matrix(ctx, &sp.m, max_lag, 0, m->n_rows, d_out, ld, false);
 }
 
-// The pitch of the scratch matrix of sums below (the LD-score call reads N out of it): 3 L + 2 columns up to the next
+// The pitch of the scratch matrix of sums below (lag_dosage_r2_band_queued hands N out of it to the LD-score calls): 3 L + 2 columns up to the next
 // multiple of 4.
 static inline uint64_t lag_complete_pitch(uint64_t L) { return (3 * L + 2 + 3u) / 4u * 4u; }
 
@@ -611,35 +611,68 @@ static int lag_dosage_to_host(storm_hip_ctx_t* ctx, const char* what, uint64_t n
     return STORM_HIP_OK;
 }
 
-// ---- LD scores: the band of r^2 into ctx->d_band, then lag_band_sums_kernel (storm_hip_ldscore.hip) over it ----
-// Both composed calls: r^2 (complete-case or pairwise-complete) of the pairs within the lag into the first n x L floats of
-// the band buffer, the reduction over them, and for a host form 2 n words behind the band on their way back. All queued
-// on ctx->stream; the host form alone waits. For the pairwise-complete adjusted statistic N(i, d) is read where the corr
-// call left it: row 3 i + 2, column 3 d + 2 of ctx->d_dosage_sums (dosage_interleaved_entry_bits).
+// ---- the band of r^2 in ctx->d_band, as every composed call below starts ----
+// r^2 (complete-case or pairwise-complete) of the pairs within the lag in the first n x L floats of the band buffer, and
+// `tail_words` words behind them that are the caller's to lay out. `n`: where the pairwise-complete call left N(i, d), row
+// 3 i + 2, column 3 d + 2 of ctx->d_dosage_sums (dosage_interleaved_entry_bits): N(i, d) = n[i * n_ld + d * n_step]. NULL
+// in the complete-case form, which has no such matrix.
+struct LagR2Band {
+    uint32_t *band, *tail;
+    const uint32_t* n;
+    uint64_t n_ld, n_step;
+};
+// the buffer alone: a caller with arrays to send ahead of the band's kernels queues them between this and the next
+static int lag_dosage_r2_band_ensure(storm_hip_ctx_t* ctx, uint64_t n, uint64_t lag, size_t tail_words, const char* what,
+                                     LagR2Band* out) {
+    const size_t band = (size_t)n * lag;
+    if (int rc = ctx->d_band.ensure((band + tail_words) * sizeof(uint32_t), what)) return rc;
+    *out = LagR2Band{ctx->d_band.d, ctx->d_band.d + band, nullptr, 0, 0};
+    return STORM_HIP_OK;
+}
+// the band's kernels, queued
+static int lag_dosage_r2_band_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint64_t n_samples, uint64_t max_lag,
+                                     uint64_t lag, bool complete, LagR2Band* b) {
+    if (int rc = complete ? lag_dosage_corr_complete_queued(ctx, m, STORM_HIP_DOSAGE_R2, n_samples, max_lag, b->band, lag)
+                          : lag_dosage_corr_queued(ctx, m, STORM_HIP_DOSAGE_R2, n_samples, max_lag, b->band, lag))
+        return rc;
+    const uint64_t lds = lag_complete_pitch(lag);
+    b->n = complete ? ctx->d_dosage_sums.d + 2 * lds + 2 : nullptr;
+    b->n_ld = 3 * lds;
+    b->n_step = 3;
+    return STORM_HIP_OK;
+}
+static int lag_dosage_r2_band(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint64_t n_samples, uint64_t max_lag, uint64_t lag,
+                              bool complete, size_t tail_words, const char* what, LagR2Band* out) {
+    if (int rc = lag_dosage_r2_band_ensure(ctx, m->n_rows, lag, tail_words, what, out)) return rc;
+    return lag_dosage_r2_band_queued(ctx, m, n_samples, max_lag, lag, complete, out);
+}
+
+static int check_ldscore_stat(const char* who, int stat) {
+    if (stat == STORM_HIP_LDSCORE_R2 || stat == STORM_HIP_LDSCORE_R2_ADJ) return STORM_HIP_OK;
+    set_error("%s: unknown stat %d (0 r^2, 1 r^2 adjusted)", who, stat);
+    return STORM_HIP_EINVAL;
+}
+
+// ---- LD scores: the band, then lag_band_sums_kernel (storm_hip_ldscore.hip) over it ----
+// Tail, for a host form: the n scores and the n counts on their way back. All queued on ctx->stream; the host form alone
+// waits. The adjusted pairwise-complete statistic alone reads N.
 static int lag_dosage_ldscore(storm_hip_ctx_t* ctx, const char* who, const storm_hip_matrix_s* m, int stat, uint64_t n_samples,
                               uint64_t max_lag, bool complete, float* score, uint32_t* n_pairs, bool host) {
     uint64_t lag = 0;
     if (int rc = check_lag_dosage(who, m, score, max_lag, ~0ull, &lag)) return rc;
-    if (stat != STORM_HIP_LDSCORE_R2 && stat != STORM_HIP_LDSCORE_R2_ADJ) {
-        set_error("%s: unknown stat %d (0 r^2, 1 r^2 adjusted)", who, stat);
-        return STORM_HIP_EINVAL;
-    }
+    if (int rc = check_ldscore_stat(who, stat)) return rc;
     if (int rc = check_samples(who, m, n_samples)) return rc;
     const uint64_t n = m->n_rows;
     if (n < 2) return STORM_HIP_OK;
     STORM_HIP_TRY(hipSetDevice(ctx->device));
-    const size_t band = (size_t)n * lag;
-    if (int rc = ctx->d_band.ensure((band + (host ? 2 * n : 0)) * sizeof(uint32_t), "lag_dosage_ldscore: the band of r^2")) return rc;
-    uint32_t* const d_band = ctx->d_band.d;
-    if (int rc = complete ? lag_dosage_corr_complete_queued(ctx, m, STORM_HIP_DOSAGE_R2, n_samples, max_lag, d_band, lag)
-                          : lag_dosage_corr_queued(ctx, m, STORM_HIP_DOSAGE_R2, n_samples, max_lag, d_band, lag))
+    LagR2Band b;
+    if (int rc = lag_dosage_r2_band(ctx, m, n_samples, max_lag, lag, complete, host ? 2 * n : 0,
+                                    "lag_dosage_ldscore: the band of r^2", &b))
         return rc;
-    const bool view = complete && stat == STORM_HIP_LDSCORE_R2_ADJ;
-    const uint64_t lds = lag_complete_pitch(lag);
-    float* const d_score = host ? reinterpret_cast<float*>(d_band + band) : score;
-    uint32_t* const d_pairs = host ? d_band + band + n : n_pairs;
-    if (int rc = launch_lag_band_sums(ctx, reinterpret_cast<const float*>(d_band), lag, n, max_lag, stat, n_samples,
-                                      view ? ctx->d_dosage_sums.d + 2 * lds + 2 : nullptr, 3 * lds, 3, d_score, d_pairs))
+    float* const d_score = host ? reinterpret_cast<float*>(b.tail) : score;
+    uint32_t* const d_pairs = host ? b.tail + n : n_pairs;
+    if (int rc = launch_lag_band_sums(ctx, reinterpret_cast<const float*>(b.band), lag, n, max_lag, stat, n_samples,
+                                      stat == STORM_HIP_LDSCORE_R2_ADJ ? b.n : nullptr, b.n_ld, b.n_step, d_score, d_pairs))
         return rc;
     if (!host) return STORM_HIP_OK;
     STORM_HIP_TRY(hipMemcpyAsync(score, d_score, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
@@ -648,21 +681,17 @@ static int lag_dosage_ldscore(storm_hip_ctx_t* ctx, const char* who, const storm
     return STORM_HIP_OK;
 }
 
-// ---- stratified LD scores: the same band, then lag_band_annot_sums_kernel (storm_hip_ldscore_annot.hip) over it ----
-// The band of r^2 into the first n x L floats of the band buffer exactly as above; behind it the window bounds (h_lo / h_hi
-// are HOST arrays of n entries in every form, both or neither: the planner runs on the host) and, for a host form, the n x C
-// annotations on their way in and the n x C scores and n counts on their way back, all dense. All queued on ctx->stream;
-// the host form alone waits.
+// ---- stratified LD scores: the band, then lag_band_annot_sums_kernel (storm_hip_ldscore_annot.hip) over it ----
+// Tail: the window bounds (h_lo / h_hi are HOST arrays of n entries in every form, both or neither: the planner runs on the
+// host) and, for a host form, the n x C annotations on their way in and the n x C scores and n counts on their way back, all
+// dense. The bounds and the annotations are queued ahead of the band's kernels. The host form alone waits.
 static int lag_dosage_ldscore_annot(storm_hip_ctx_t* ctx, const char* who, const storm_hip_matrix_s* m, int stat, uint64_t n_samples,
                                     uint64_t max_lag, bool complete, const uint32_t* h_lo, const uint32_t* h_hi, const float* annot,
                                     uint64_t annot_ld, uint64_t n_annot, float* score, uint64_t score_ld, uint32_t* n_pairs,
                                     bool host) {
     uint64_t lag = 0;
     if (int rc = check_lag_dosage(who, m, score, max_lag, ~0ull, &lag)) return rc;
-    if (stat != STORM_HIP_LDSCORE_R2 && stat != STORM_HIP_LDSCORE_R2_ADJ) {
-        set_error("%s: unknown stat %d (0 r^2, 1 r^2 adjusted)", who, stat);
-        return STORM_HIP_EINVAL;
-    }
+    if (int rc = check_ldscore_stat(who, stat)) return rc;
     if (int rc = check_samples(who, m, n_samples)) return rc;
     if (!annot) {
         set_error("%s: NULL annotations", who);
@@ -684,13 +713,14 @@ static int lag_dosage_ldscore_annot(storm_hip_ctx_t* ctx, const char* who, const
     const uint64_t n = m->n_rows;
     if (n < 2) return STORM_HIP_OK;
     STORM_HIP_TRY(hipSetDevice(ctx->device));
-    const size_t band = (size_t)n * lag, cells = (size_t)n * n_annot;
-    const size_t words = band + (h_lo ? 2 * n : 0) + (host ? 2 * cells + n : 0);
-    if (int rc = ctx->d_band.ensure(words * sizeof(uint32_t), "lag_dosage_ldscore_annot: the band of r^2")) return rc;
-    uint32_t* const d_band = ctx->d_band.d;
-    uint32_t* const d_lo = h_lo ? d_band + band : nullptr;
+    const size_t cells = (size_t)n * n_annot;
+    LagR2Band b;
+    if (int rc = lag_dosage_r2_band_ensure(ctx, n, lag, (h_lo ? 2 * n : 0) + (host ? 2 * cells + n : 0),
+                                           "lag_dosage_ldscore_annot: the band of r^2", &b))
+        return rc;
+    uint32_t* const d_lo = h_lo ? b.tail : nullptr;
     uint32_t* const d_hi = h_lo ? d_lo + n : nullptr;
-    uint32_t* const d_io = d_band + band + (h_lo ? 2 * n : 0);
+    uint32_t* const d_io = b.tail + (h_lo ? 2 * n : 0);
     if (h_lo) {
         STORM_HIP_TRY(hipMemcpyAsync(d_lo, h_lo, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
         STORM_HIP_TRY(hipMemcpyAsync(d_hi, h_hi, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
@@ -698,16 +728,12 @@ static int lag_dosage_ldscore_annot(storm_hip_ctx_t* ctx, const char* who, const
     if (host)
         STORM_HIP_TRY(hipMemcpy2DAsync(d_io, n_annot * sizeof(float), annot, annot_ld * sizeof(float), n_annot * sizeof(float), n,
                                        hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = complete ? lag_dosage_corr_complete_queued(ctx, m, STORM_HIP_DOSAGE_R2, n_samples, max_lag, d_band, lag)
-                          : lag_dosage_corr_queued(ctx, m, STORM_HIP_DOSAGE_R2, n_samples, max_lag, d_band, lag))
-        return rc;
-    const bool view = complete && stat == STORM_HIP_LDSCORE_R2_ADJ;
-    const uint64_t lds = lag_complete_pitch(lag);
+    if (int rc = lag_dosage_r2_band_queued(ctx, m, n_samples, max_lag, lag, complete, &b)) return rc;
     const float* const d_annot = host ? reinterpret_cast<const float*>(d_io) : annot;
     float* const d_score = host ? reinterpret_cast<float*>(d_io + cells) : score;
     uint32_t* const d_pairs = host ? d_io + 2 * cells : n_pairs;
-    if (int rc = launch_lag_band_annot_sums(ctx, reinterpret_cast<const float*>(d_band), lag, n, max_lag, stat, n_samples,
-                                            view ? ctx->d_dosage_sums.d + 2 * lds + 2 : nullptr, 3 * lds, 3, d_lo, d_hi, d_annot,
+    if (int rc = launch_lag_band_annot_sums(ctx, reinterpret_cast<const float*>(b.band), lag, n, max_lag, stat, n_samples,
+                                            stat == STORM_HIP_LDSCORE_R2_ADJ ? b.n : nullptr, b.n_ld, b.n_step, d_lo, d_hi, d_annot,
                                             host ? n_annot : annot_ld, n_annot, d_score, host ? n_annot : score_ld, d_pairs))
         return rc;
     if (!host) return STORM_HIP_OK;
@@ -718,10 +744,10 @@ static int lag_dosage_ldscore_annot(storm_hip_ctx_t* ctx, const char* who, const
     return STORM_HIP_OK;
 }
 
-// ---- greedy pruning / clumping: the same band, then the kernels of storm_hip_prune.hip over it ----
-// The band of r^2 into the first n x L floats of the band buffer exactly as above; behind it the adjacency masks, the
-// window bounds and the order (h_lo / h_hi / h_order are HOST arrays of n entries in every form, or NULL) and, for a host
-// form, the n owners and the n keep bytes on their way back. All queued on ctx->stream; the host form alone waits.
+// ---- greedy pruning / clumping: the band, then the kernels of storm_hip_prune.hip over it ----
+// Tail: the adjacency masks, the window bounds and the order (h_lo / h_hi / h_order are HOST arrays of n entries in every
+// form, or NULL; the launcher lays them out and sends them) and, for a host form, the n owners and the n keep bytes on their
+// way back. All queued on ctx->stream; the host form alone waits.
 static int lag_dosage_prune(storm_hip_ctx_t* ctx, const char* who, const storm_hip_matrix_s* m, uint64_t n_samples, uint64_t max_lag,
                             float min_r2, bool complete, const uint32_t* h_lo, const uint32_t* h_hi, const uint32_t* h_order,
                             uint8_t* keep, uint32_t* owner, bool host) {
@@ -742,17 +768,15 @@ static int lag_dosage_prune(storm_hip_ctx_t* ctx, const char* who, const storm_h
         if (owner) STORM_HIP_TRY(hipMemsetAsync(owner, 0, sizeof(uint32_t), ctx->stream));
         return STORM_HIP_OK;
     }
-    const size_t band = (size_t)n * lag, scratch = lag_band_prune_scratch_words(n, lag, h_lo != nullptr, h_order != nullptr);
-    const size_t words = band + scratch + (host ? n + (n + 3) / 4 : 0);
-    if (int rc = ctx->d_band.ensure(words * sizeof(uint32_t), "lag_dosage_prune: the band of r^2 and the adjacency masks")) return rc;
-    uint32_t* const d_band = ctx->d_band.d;
-    if (int rc = complete ? lag_dosage_corr_complete_queued(ctx, m, STORM_HIP_DOSAGE_R2, n_samples, max_lag, d_band, lag)
-                          : lag_dosage_corr_queued(ctx, m, STORM_HIP_DOSAGE_R2, n_samples, max_lag, d_band, lag))
+    const size_t scratch = lag_band_prune_scratch_words(n, lag, h_lo != nullptr, h_order != nullptr);
+    LagR2Band b;
+    if (int rc = lag_dosage_r2_band(ctx, m, n_samples, max_lag, lag, complete, scratch + (host ? n + (n + 3) / 4 : 0),
+                                    "lag_dosage_prune: the band of r^2 and the adjacency masks", &b))
         return rc;
-    uint32_t* const d_owner = host ? (owner ? d_band + band + scratch : nullptr) : owner;
-    uint8_t* const d_keep = host ? reinterpret_cast<uint8_t*>(d_band + band + scratch + n) : keep;
-    if (int rc = launch_lag_band_prune(ctx, who, reinterpret_cast<const float*>(d_band), lag, n, lag, min_r2, h_lo, h_hi, h_order,
-                                       d_keep, d_owner, d_band + band))
+    uint32_t* const d_owner = host ? (owner ? b.tail + scratch : nullptr) : owner;
+    uint8_t* const d_keep = host ? reinterpret_cast<uint8_t*>(b.tail + scratch + n) : keep;
+    if (int rc = launch_lag_band_prune(ctx, who, reinterpret_cast<const float*>(b.band), lag, n, lag, min_r2, h_lo, h_hi, h_order,
+                                       d_keep, d_owner, b.tail))
         return rc;
     if (!host) return STORM_HIP_OK;
     STORM_HIP_TRY(hipMemcpyAsync(keep, d_keep, n, hipMemcpyDeviceToHost, ctx->stream));

@@ -7,10 +7,9 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "storm_hip.h"
+#include "stub_dosage.h"   /* struct storm_hip_matrix_s: host memory */
 
 struct storm_hip_ctx_s { int device; uint64_t pending; };
-struct storm_hip_matrix_s { uint64_t n_rows; uint32_t n_words; uint64_t* rows; };
 struct storm_hip_sparse_s { uint64_t set_bits; };
 
 static const char* g_err = "";

@@ -1,17 +1,10 @@
 /* dosage_complete_stub.c — TEST ONLY. The dosage entry points of the device library for dosage_complete_driver.c, beside
  * device_stub.c (whose matrix is host memory): every call computes its result from the words that reached it, sample by
  * sample on the CPU, and writes exactly the window the real call writes. Never linked into the product. */
-#include <math.h>
-#include <stdint.h>
 #include <string.h>
 
-#include "storm_hip.h"
+#include "stub_dosage.h"
 
-struct storm_hip_matrix_s { uint64_t n_rows; uint32_t n_words; uint64_t* rows; }; /* device_stub.c's */
-
-static unsigned value_at(const storm_hip_matrix_t* m, uint64_t row, uint64_t s) {
-    return (unsigned)(m->rows[row * m->n_words + s / 32] >> (2 * (s % 32))) & 3u;
-}
 static uint32_t dot(const storm_hip_matrix_t* a, uint64_t i, const storm_hip_matrix_t* b, uint64_t j) {
     uint32_t p = 0;
     for (uint64_t s = 0; s < (uint64_t)a->n_words * 32; ++s) p += value_at(a, i, s) * value_at(b, j, s);

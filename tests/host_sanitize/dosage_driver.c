@@ -10,9 +10,7 @@
 #include <string.h>
 
 #include "storm.h"
-#include "storm_hip.h"
-
-struct storm_hip_matrix_s { uint64_t n_rows; uint32_t n_words; uint64_t* rows; }; /* device_stub.c's */
+#include "stub_dosage.h"
 
 #define CHECK(cond)                                                         \
     do {                                                                    \
@@ -24,9 +22,6 @@ struct storm_hip_matrix_s { uint64_t n_rows; uint32_t n_words; uint64_t* rows; }
 
 static const storm_hip_matrix_t* g_seen; /* the matrix of the last dosage call */
 
-static unsigned value_at(const storm_hip_matrix_t* m, uint64_t row, uint64_t s) {
-    return (unsigned)(m->rows[row * m->n_words + s / 32] >> (2 * (s % 32))) & 3u;
-}
 int storm_hip_dosage_row_sums(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint32_t* h_sum, uint32_t* h_sum_sq) {
     (void)ctx;
     g_seen = m;

@@ -2,17 +2,9 @@
  * device_stub.c (whose matrix is host memory) and dosage_complete_stub.c: every call computes its result from the words that
  * reached it, sample by sample on the CPU, and writes exactly what the real call writes — the pairs (i, i + 1 + d), d < L,
  * i + 1 + d < n, and in the host forms 0 in the corner. Never linked into the product. */
-#include <math.h>
-#include <stdint.h>
 #include <string.h>
 
-#include "storm_hip.h"
-
-struct storm_hip_matrix_s { uint64_t n_rows; uint32_t n_words; uint64_t* rows; }; /* device_stub.c's */
-
-static unsigned value_at(const storm_hip_matrix_t* m, uint64_t row, uint64_t s) {
-    return (unsigned)(m->rows[row * m->n_words + s / 32] >> (2 * (s % 32))) & 3u;
-}
+#include "stub_dosage.h"
 
 enum { DOT, CORR, NOBS, COMPLETE };
 

@@ -1,7 +1,7 @@
 /* dosage_ldscore_annot_driver.c — TEST ONLY. The host entry points of the dosage container's stratified LD scores
  * (stormbitmaps_amd/csrc/storm_dosage_ldscore_annot.c and the planner storm_ldscore_window.c, on storm_dosage.c and
  * storm_host.c's locked paths) as a stand-alone program for AddressSanitizer / UBSan, on device_stub.c,
- * dosage_complete_stub.c, dosage_ldscore_stub.c and dosage_ldscore_annot_stub.c: outputs of exactly n x C elements (a write
+ * dosage_complete_stub.c and dosage_band_stub.c: outputs of exactly n x C elements (a write
  * behind them is a heap overflow), score_ld > C with the pitch elements untouched, windows that need exactly max_lag rows
  * and one row more than max_lag, every refusal with nothing written. Never linked into the product. */
 #include <math.h>

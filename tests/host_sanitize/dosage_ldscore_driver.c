@@ -1,6 +1,6 @@
 /* dosage_ldscore_driver.c — TEST ONLY. The host entry points of the dosage container's LD scores
  * (stormbitmaps_amd/csrc/storm_dosage_ldscore.c on storm_dosage.c and storm_host.c's locked paths) as a stand-alone program
- * for AddressSanitizer / UBSan, on device_stub.c, dosage_complete_stub.c and dosage_ldscore_stub.c: outputs of exactly n
+ * for AddressSanitizer / UBSan, on device_stub.c, dosage_complete_stub.c and dosage_band_stub.c: outputs of exactly n
  * elements (a write behind n is a heap overflow), lags below, at and beyond n - 1, every refusal (several device slots in
  * view among them), rows added between calls. Never linked into the product. */
 #include <math.h>

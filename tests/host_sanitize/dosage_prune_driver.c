@@ -1,7 +1,7 @@
 /* dosage_prune_driver.c — TEST ONLY. The host entry points of the dosage container's prune / clump calls
  * (stormbitmaps_amd/csrc/storm_dosage_prune.c with the planners storm_ldscore_window.c and storm_prune_order.c, on
  * storm_dosage.c and storm_host.c's locked paths) as a stand-alone program for AddressSanitizer / UBSan, on device_stub.c,
- * dosage_complete_stub.c, dosage_ldscore_stub.c and dosage_prune_stub.c: outputs of exactly n elements (a write behind them
+ * dosage_complete_stub.c and dosage_band_stub.c: outputs of exactly n elements (a write behind them
  * is a heap overflow), owner NULL and given, priorities NULL, random, tied and infinite, windows that need exactly max_lag
  * rows and one row more than max_lag, every refusal with nothing written. Never linked into the product. */
 #include <math.h>

@@ -8,17 +8,13 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests._host_sanitize import ROOT, dosage_sources
 
 
 @pytest.mark.skipif(shutil.which("gcc") is None, reason="needs gcc")
 def test_rectangle_and_missing_genotype_calls_under_asan_ubsan(tmp_path):
     exe = tmp_path / "dosage_complete_sanitize"
-    csrc = os.path.join(ROOT, "stormbitmaps_amd", "csrc")
-    srcs = [os.path.join(csrc, f) for f in ("storm_host.c", "storm_dosage.c", "storm_dosage_complete.c", "storm_synth.c",
-                                            "storm_leaves.c")] + \
-           [os.path.join(ROOT, "tests", "host_sanitize", f) for f in ("device_stub.c", "dosage_complete_stub.c",
-                                                                      "dosage_complete_driver.c")]
+    srcs = dosage_sources(("storm_dosage_complete.c",), ("dosage_complete_driver.c",))
     build = subprocess.run(["gcc", "-std=gnu11", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                             "-fno-omit-frame-pointer", "-Wall", "-pthread", "-I" + os.path.join(ROOT, "include"), *srcs,
                             "-o", str(exe), "-lm"], capture_output=True, text=True)

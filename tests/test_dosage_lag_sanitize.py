@@ -1,6 +1,6 @@
 """The host entry points of the dosage container's lag calls (stormbitmaps_amd/csrc/storm_dosage_lag.c) as a stand-alone
-program under AddressSanitizer, UBSan and LeakSanitizer: tests/host_sanitize/dosage_lag_driver.c on device_stub.c,
-dosage_complete_stub.c and dosage_lag_stub.c (the "device" is host memory and computes sample by sample). Outputs of exactly
+program under AddressSanitizer, UBSan and LeakSanitizer: tests/host_sanitize/dosage_lag_driver.c on the common sources of
+tests/_host_sanitize.py and dosage_lag_stub.c (the "device" is host memory and computes sample by sample). Outputs of exactly
 n x L entries — a write outside the layout is a heap overflow there — and with a pitch, lags below, at and beyond n - 1,
 every refusal, rows added between calls."""
 import os
@@ -9,17 +9,13 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests._host_sanitize import ROOT, dosage_sources
 
 
 @pytest.mark.skipif(shutil.which("gcc") is None, reason="needs gcc")
 def test_lag_calls_under_asan_ubsan(tmp_path):
     exe = tmp_path / "dosage_lag_sanitize"
-    csrc = os.path.join(ROOT, "stormbitmaps_amd", "csrc")
-    srcs = [os.path.join(csrc, f) for f in ("storm_host.c", "storm_dosage.c", "storm_dosage_lag.c", "storm_synth.c",
-                                            "storm_leaves.c")] + \
-           [os.path.join(ROOT, "tests", "host_sanitize", f) for f in ("device_stub.c", "dosage_complete_stub.c",
-                                                                      "dosage_lag_stub.c", "dosage_lag_driver.c")]
+    srcs = dosage_sources(("storm_dosage_lag.c",), ("dosage_lag_stub.c", "dosage_lag_driver.c"))
     build = subprocess.run(["gcc", "-std=gnu11", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                             "-fno-omit-frame-pointer", "-Wall", "-pthread", "-I" + os.path.join(ROOT, "include"), *srcs,
                             "-o", str(exe), "-lm"], capture_output=True, text=True)

@@ -1,8 +1,8 @@
 """The host entry points of the dosage container's prune / clump calls (stormbitmaps_amd/csrc/storm_dosage_prune.c and the
 planners storm_ldscore_window.c and storm_prune_order.c) as a stand-alone program under AddressSanitizer, UBSan and
-LeakSanitizer: tests/host_sanitize/dosage_prune_driver.c on device_stub.c, dosage_complete_stub.c, dosage_ldscore_stub.c and
-dosage_prune_stub.c (the "device" is host memory running the plain greedy, sample by sample); the driver sizes its windows
-with STORM_ldscore_window_lag, so storm_dosage_ldscore_annot.c and its stub are linked too. Outputs of exactly n elements —
+LeakSanitizer: tests/host_sanitize/dosage_prune_driver.c on the common sources of tests/_host_sanitize.py (the "device" is
+host memory running the plain greedy, sample by sample); the driver sizes its windows with STORM_ldscore_window_lag, which
+storm_dosage_band.c among them has. Outputs of exactly n elements —
 a write behind them is a heap overflow there — owner NULL and given, windows that need exactly max_lag rows and one row
 more, every refusal. Nothing is loaded into Python under a sanitizer: the program is its own executable."""
 import os
@@ -11,20 +11,15 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests._host_sanitize import CSRC, ROOT, dosage_sources
 
 
 @pytest.mark.skipif(shutil.which("gcc") is None, reason="needs gcc")
 def test_prune_calls_under_asan_ubsan(tmp_path):
     exe = tmp_path / "dosage_prune_sanitize"
-    csrc = os.path.join(ROOT, "stormbitmaps_amd", "csrc")
-    srcs = [os.path.join(csrc, f) for f in ("storm_host.c", "storm_dosage.c", "storm_dosage_prune.c", "storm_ldscore_window.c",
-                                            "storm_prune_order.c", "storm_dosage_ldscore_annot.c", "storm_synth.c", "storm_leaves.c")] + \
-           [os.path.join(ROOT, "tests", "host_sanitize", f) for f in ("device_stub.c", "dosage_complete_stub.c", "dosage_ldscore_stub.c",
-                                                                      "dosage_ldscore_annot_stub.c", "dosage_prune_stub.c",
-                                                                      "dosage_prune_driver.c")]
+    srcs = dosage_sources(("storm_dosage_prune.c", "storm_prune_order.c"), ("dosage_prune_driver.c",))
     build = subprocess.run(["gcc", "-std=gnu11", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                            "-fno-omit-frame-pointer", "-Wall", "-pthread", "-I" + os.path.join(ROOT, "include"), "-I" + csrc, *srcs,
+                            "-fno-omit-frame-pointer", "-Wall", "-pthread", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, *srcs,
                             "-o", str(exe), "-lm"], capture_output=True, text=True)
     if build.returncode != 0 and "asan" in build.stderr.lower() and "cannot find" in build.stderr.lower():
         pytest.skip("libasan not installed")

@@ -1,7 +1,7 @@
 """The host entry points of the dosage container's stratified LD scores (stormbitmaps_amd/csrc/storm_dosage_ldscore_annot.c
 and the planner storm_ldscore_window.c) as a stand-alone program under AddressSanitizer, UBSan and LeakSanitizer:
-tests/host_sanitize/dosage_ldscore_annot_driver.c on device_stub.c, dosage_complete_stub.c, dosage_ldscore_stub.c and
-dosage_ldscore_annot_stub.c (the "device" is host memory and computes sample by sample). Outputs of exactly n x C elements —
+tests/host_sanitize/dosage_ldscore_annot_driver.c on the common sources of tests/_host_sanitize.py, dosage_band_stub.c among
+them (the "device" is host memory and computes sample by sample). Outputs of exactly n x C elements —
 a write behind them is a heap overflow there — score_ld > C, windows that need exactly max_lag rows and one row more, every
 refusal. Nothing is loaded into Python under a sanitizer: the program is its own executable."""
 import os
@@ -10,19 +10,15 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests._host_sanitize import CSRC, ROOT, dosage_sources
 
 
 @pytest.mark.skipif(shutil.which("gcc") is None, reason="needs gcc")
 def test_ldscore_annot_calls_under_asan_ubsan(tmp_path):
     exe = tmp_path / "dosage_ldscore_annot_sanitize"
-    csrc = os.path.join(ROOT, "stormbitmaps_amd", "csrc")
-    srcs = [os.path.join(csrc, f) for f in ("storm_host.c", "storm_dosage.c", "storm_dosage_ldscore_annot.c", "storm_ldscore_window.c",
-                                            "storm_synth.c", "storm_leaves.c")] + \
-           [os.path.join(ROOT, "tests", "host_sanitize", f) for f in ("device_stub.c", "dosage_complete_stub.c", "dosage_ldscore_stub.c",
-                                                                      "dosage_ldscore_annot_stub.c", "dosage_ldscore_annot_driver.c")]
+    srcs = dosage_sources(("storm_dosage_ldscore_annot.c",), ("dosage_ldscore_annot_driver.c",))
     build = subprocess.run(["gcc", "-std=gnu11", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                            "-fno-omit-frame-pointer", "-Wall", "-pthread", "-I" + os.path.join(ROOT, "include"), "-I" + csrc, *srcs,
+                            "-fno-omit-frame-pointer", "-Wall", "-pthread", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, *srcs,
                             "-o", str(exe), "-lm"], capture_output=True, text=True)
     if build.returncode != 0 and "asan" in build.stderr.lower() and "cannot find" in build.stderr.lower():
         pytest.skip("libasan not installed")

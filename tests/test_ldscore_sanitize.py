@@ -1,6 +1,6 @@
 """The host entry points of the dosage container's LD scores (stormbitmaps_amd/csrc/storm_dosage_ldscore.c) as a stand-alone
-program under AddressSanitizer, UBSan and LeakSanitizer: tests/host_sanitize/dosage_ldscore_driver.c on device_stub.c,
-dosage_complete_stub.c and dosage_ldscore_stub.c (the "device" is host memory and computes sample by sample). Outputs of
+program under AddressSanitizer, UBSan and LeakSanitizer: tests/host_sanitize/dosage_ldscore_driver.c on the common sources of
+tests/_host_sanitize.py, dosage_band_stub.c among them (the "device" is host memory and computes sample by sample). Outputs of
 exactly n elements — a write behind n is a heap overflow there — lags below, at and beyond n - 1, every refusal, rows added
 between calls."""
 import os
@@ -9,17 +9,13 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests._host_sanitize import ROOT, dosage_sources
 
 
 @pytest.mark.skipif(shutil.which("gcc") is None, reason="needs gcc")
 def test_ldscore_calls_under_asan_ubsan(tmp_path):
     exe = tmp_path / "dosage_ldscore_sanitize"
-    csrc = os.path.join(ROOT, "stormbitmaps_amd", "csrc")
-    srcs = [os.path.join(csrc, f) for f in ("storm_host.c", "storm_dosage.c", "storm_dosage_ldscore.c", "storm_synth.c",
-                                            "storm_leaves.c")] + \
-           [os.path.join(ROOT, "tests", "host_sanitize", f) for f in ("device_stub.c", "dosage_complete_stub.c",
-                                                                      "dosage_ldscore_stub.c", "dosage_ldscore_driver.c")]
+    srcs = dosage_sources(("storm_dosage_ldscore.c",), ("dosage_ldscore_driver.c",))
     build = subprocess.run(["gcc", "-std=gnu11", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                             "-fno-omit-frame-pointer", "-Wall", "-pthread", "-I" + os.path.join(ROOT, "include"), *srcs,
                             "-o", str(exe), "-lm"], capture_output=True, text=True)
