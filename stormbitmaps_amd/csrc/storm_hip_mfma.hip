@@ -730,7 +730,10 @@ __device__ __forceinline__ v4i sb16_inflate(v4i w, uint32_t rot) {
 //     (strip_rows_role, storm_hip_plan.h) — 7 whole products and 2 triangles = 132 MFMAs for every wave. Four fragments of
 //     a block are asked for at once and multiplied behind lgkmcnt(3 .. 0). The pieces of the first three pipelined stages
 //     are in flight meanwhile; one more barrier, and the pipelined ring of 3 images is overlaid on resident images 0 .. 2.
-//   per 64 B rows and wave    strip16_bits_kernel    strip16_rows_kernel    its diagonal phase (per block step)
+//   * zero rows past the matrix's end (argument n_rows, storm_hip_plan.h): a run's top block with rows in 1 or 2 of its 4
+//     fragments is the run's last stage and multiplies those alone (8 or 16 MFMAs per wave behind the loop, where a stage
+//     has 32); the diagonal phase walks only the tile's blocks that hold a row. 10000 rows: 1.08 % fewer MFMAs per launch.
+//   per 64 B rows and wave   strip16_bits_kernel    strip16_rows_kernel    its diagonal phase (per block step)
 //   MFMAs                     32                     32                     10 / 16 / 26 / 32
 //   fragment ds_read_b128     8                      4                      4
 //   image ds_write_b128       2                      1                      0 (8 per item)
@@ -2602,11 +2605,16 @@ int launch_pairw_bits_ranges(storm_hip_ctx_t* ctx, const uint8_t* X, uint64_t pi
                              arrivals_per_slot * wave_sum_max < (1ull << 48);
     if (n_strip > 0) {
         kernel_time_mark(ctx);
-        if (rows128)
+        if (rows128) {
+            // where the rows end, for a pass that is one plain range from row 0 (the dense matrix, whole or sharded): the
+            // kernel issues no MFMA for the zero rows behind r1 in whole fragments and blocks (storm_hip_plan.h)
+            const bool plain = ranges.size() == 1 && ranges[0].r0 == 0 && ranges[0].a_end == 0 && ranges[0].back_from == ~0ull &&
+                               ranges[0].r1 < (uint64_t)kStripRowsNoTrim;
             hipLaunchKernelGGL(strip16_rows_kernel, dim3(n_strip), dim3(256), (size_t)ctx->k2_lds_pad,
                                ctx->stream, X, pitch, ctx->d_strip_items.d, ctx->d_slots,
-                               fold_inline ? reinterpret_cast<unsigned long long*>(d_total) : nullptr, fold_slots);
-        else if (waves == 8u)
+                               fold_inline ? reinterpret_cast<unsigned long long*>(d_total) : nullptr, fold_slots,
+                               plain ? (uint32_t)ranges[0].r1 : kStripRowsNoTrim);
+        } else if (waves == 8u)
             hipLaunchKernelGGL(strip16_bits2_kernel, dim3(n_strip), dim3(512), (size_t)ctx->k2_lds_pad,
                                ctx->stream, X, pitch, ctx->d_strip_items.d, ctx->d_slots,
                                fold_inline ? reinterpret_cast<unsigned long long*>(d_total) : nullptr, fold_slots);

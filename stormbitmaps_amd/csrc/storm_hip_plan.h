@@ -77,6 +77,45 @@ static_assert(strip_rows_block(0, 0) < strip_rows_block(0, 1) && strip_rows_bloc
               strip_rows_block(2, 0) < strip_rows_block(2, 1) && strip_rows_block(3, 0) < strip_rows_block(3, 1),
               "strip16_rows_kernel walks the low half's own block first");
 
+// ... and where the rows end (strip16_rows_kernel's argument n_rows: the r1 of a pass that is one plain range from row 0,
+// kStripRowsNoTrim otherwise). The rows from n_rows up to the next multiple of 512 are zero, and the kernel issues no MFMA
+// for what is zero in whole units — a 16-row fragment of an item's top B block, a 64-row block of the A tile's own eight:
+//   * the top B block j1 - 1 of a run, when only 1 or 2 of its 4 fragments hold a row, becomes the run's LAST stage and
+//     multiplies those fragments alone; with 3 or 4 the run is walked as without the argument;
+//   * the diagonal phase stops at the tile's last block that holds a row, for both halves of every wave.
+// Inside a fragment or a block nothing is trimmed. tests/strip_rows_trim/driver.cpp checks these functions on the host.
+constexpr uint32_t kStripRowsNoTrim = 0xFFFFFFFFu;
+// fragments of 16 rows of B block `blk` that hold a row below n_rows: 0 .. 4
+constexpr uint32_t strip_rows_real_frags(uint32_t blk, uint32_t n_rows) {
+    const uint32_t row0 = blk * (uint32_t)kStripBRows;   // (row indices are 32-bit: blk < 2^26)
+    return n_rows <= row0 ? 0u : n_rows - row0 >= (uint32_t)kStripBRows ? 4u : (n_rows - row0 + 15u) / 16u;
+}
+// blocks of 64 rows of the A tile at a_row0 that hold a row below n_rows: 0 .. 8
+constexpr uint32_t strip_rows_real_blocks(uint32_t a_row0, uint32_t n_rows) {
+    return n_rows <= a_row0 ? 0u : n_rows - a_row0 >= kStripRowsATile ? kStripRowsBlocks
+                                                                     : (n_rows - a_row0 + (uint32_t)kStripBRows - 1u) / (uint32_t)kStripBRows;
+}
+// does the run [j0, j1) end in a block that is multiplied last and in part? (its fragments: strip_rows_real_frags(j1 - 1))
+constexpr bool strip_rows_top_trimmed(uint32_t j0, uint32_t j1, uint32_t n_rows) {
+    return j1 > j0 && strip_rows_real_frags(j1 - 1u, n_rows) - 1u < 2u;
+}
+// MFMAs the four waves of an item issue: a stage is 4 fragments x 8 A fragments per wave, the diagonal phase the roles
+// above at the blocks d < nb of the halves whose own block lies below nb
+constexpr uint32_t strip_rows_item_mfmas(uint32_t a_row0, uint32_t diag, uint32_t j0, uint32_t j1, uint32_t n_rows) {
+    const uint32_t T = j1 - j0;
+    uint32_t n = strip_rows_top_trimmed(j0, j1, n_rows)
+                     ? kStripRowsWaves * 8u * (4u * (T - 1u) + strip_rows_real_frags(j1 - 1u, n_rows))
+                     : kStripRowsWaves * 8u * 4u * T;
+    if (diag) {
+        const uint32_t nb = strip_rows_real_blocks(a_row0, n_rows);
+        for (uint32_t w = 0; w < kStripRowsWaves; ++w)
+            for (uint32_t half = 0; half < 2u; ++half)
+                for (uint32_t d = 0; d < nb; ++d)
+                    if (strip_rows_block(w, half) < nb) n += strip_rows_role_mfmas(strip_rows_role(w, half, d));
+    }
+    return n;
+}
+
 struct StripItem {
     uint32_t a_row0;  // first row of the A tile (kStripATile rows, multiple of 64)
     uint32_t diag;    // 1: the item starts with the stages of its own tile (strict upper part)

@@ -2,7 +2,7 @@
 // storm_hip_mfma.hip; the comment block in front of the include has the dataflow and the counts per stage.
 __global__ __launch_bounds__(256, 4) void strip16_rows_kernel(
     const uint8_t* __restrict__ X, uint64_t row_bytes, const StripItem* __restrict__ items,
-    unsigned long long* __restrict__ slots, unsigned long long* __restrict__ out, uint32_t fold_slots) {
+    unsigned long long* __restrict__ slots, unsigned long long* __restrict__ out, uint32_t fold_slots, uint32_t n_rows) {
     __shared__ __attribute__((aligned(1024))) uint8_t lds_raw[kSr16ImgBytes + kSr16BitRing * kSr16BitStage];
 
     constexpr uint32_t kW = kStripRowsWaves;        // waves per workgroup; wave w keeps blocks w and 7 - w of the A tile
@@ -17,9 +17,16 @@ __global__ __launch_bounds__(256, 4) void strip16_rows_kernel(
     // address their images and pieces with immediate offsets (as strip16_bits_kernel). The diagonal phase in front of it
     // is no stage of the rings. An item that has only its diagonal (T == 0) still issues its three pieces — of the tile's
     // own first block, a valid address — and drains them at the end.
+    // Rows from n_rows on are zero (storm_hip_plan.h: kStripRowsNoTrim switches this off). A run whose top block j1 - 1 has
+    // rows in only 1 or 2 of its fragments is walked from j1 - 2 down, Tl = T - 1 whole stages, and the top block is stage
+    // T - 1: its image is complete when the loop ends, and those fragments alone are multiplied behind the loop — no barrier,
+    // no ring upkeep. Stage s is block blk_first - s for s < s_turn and blk_rest from there on (the stale pieces too).
     const uint32_t T = it.j1 - it.j0;
-    const uint32_t s_last = T ? T - 1u : 0u;
-    const uint32_t blk_top = T ? it.j1 - 1u : it.a_row0 / (uint32_t)kStripBRows;
+    const uint32_t top_frags = strip_rows_top_trimmed(it.j0, it.j1, n_rows) ? strip_rows_real_frags(it.j1 - 1u, n_rows) : 0u;   // 0: nothing trimmed
+    const uint32_t Tl = top_frags ? T - 1u : T;
+    const uint32_t s_turn = top_frags ? Tl : T ? T - 1u : 0u;
+    const uint32_t blk_first = T ? it.j1 - (top_frags ? 2u : 1u) : it.a_row0 / (uint32_t)kStripBRows;
+    const uint32_t blk_rest = top_frags ? it.j1 - 1u : blk_first - s_turn;
     const uint32_t blk_lo = strip_rows_block(wave, 0u), blk_hi = strip_rows_block(wave, 1u);
 
     const uint32_t lds_base =
@@ -37,7 +44,7 @@ __global__ __launch_bounds__(256, 4) void strip16_rows_kernel(
     // LDS-DMA of the wave's piece of stage s into bit slot `slot`. Stages beyond the last one re-read the
     // last block (never consumed): every iteration issues exactly one piece, so every wait is vmcnt(2).
     auto issue = [&](uint32_t s, uint32_t slot) {
-        const uint32_t blk = blk_top - min(s, s_last);
+        const uint32_t blk = s < s_turn ? blk_first - s : blk_rest;
         const uint8_t* base = X + (uint64_t)(blk * (uint32_t)kStripBRows) * row_bytes + kbyte;
         const __amdgpu_buffer_rsrc_t rsrc =
             __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(base), 0, -1, 0x00020000);
@@ -171,7 +178,11 @@ __global__ __launch_bounds__(256, 4) void strip16_rows_kernel(
     STORM_FETCH16V(b1, sb, 1);                                                            \
     STORM_FETCH16V(b2, sb, 2);                                                            \
     STORM_FETCH16V(b3, sb, 3)
+        // Blocks from nb on hold no row below n_rows: nothing is multiplied against them, and a half whose own block is one of
+        // them multiplies nothing. The four runs keep their dataflow and are bounded by uniform conditions alone.
+        const uint32_t nb = strip_rows_real_blocks(it.a_row0, n_rows);
         uint32_t d = strip_rows_diag_begin(wave);
+        if (blk_lo < nb) {
         {                                // d == blk_lo: low own
             STORM_SR16_HEAD();
             const uint32_t lane_d = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
@@ -183,13 +194,14 @@ __global__ __launch_bounds__(256, 4) void strip16_rows_kernel(
             ++d;
         }
 #pragma unroll 1
-        for (; d < blk_hi; ++d) {        // low whole
+        for (; d < min(blk_hi, nb); ++d) {   // low whole
             STORM_SR16_HEAD();
             STORM_LGKM(3); STORM_SR16_WHOLE(0, 0, b0) __builtin_amdgcn_sched_barrier(0);
             STORM_LGKM(2); STORM_SR16_WHOLE(0, 1, b1) __builtin_amdgcn_sched_barrier(0);
             STORM_LGKM(1); STORM_SR16_WHOLE(0, 2, b2) __builtin_amdgcn_sched_barrier(0);
             STORM_LGKM(0); STORM_SR16_WHOLE(0, 3, b3) __builtin_amdgcn_sched_barrier(0);
         }
+        if (blk_hi < nb) {
         {                                // d == blk_hi: low whole, high own
             STORM_SR16_HEAD();
             const uint32_t lane_d = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
@@ -201,13 +213,15 @@ __global__ __launch_bounds__(256, 4) void strip16_rows_kernel(
             ++d;
         }
 #pragma unroll 1
-        for (; d < strip_rows_diag_end(wave); ++d) {   // both whole
+        for (; d < min(strip_rows_diag_end(wave), nb); ++d) {   // both whole
             STORM_SR16_HEAD();
             STORM_LGKM(3); STORM_MUL16(0, b0); __builtin_amdgcn_sched_barrier(0);
             STORM_LGKM(2); STORM_MUL16(1, b1); __builtin_amdgcn_sched_barrier(0);
             STORM_LGKM(1); STORM_MUL16(2, b2); __builtin_amdgcn_sched_barrier(0);
             STORM_LGKM(0); STORM_MUL16(3, b3); __builtin_amdgcn_sched_barrier(0);
         }
+        }   // blk_hi < nb
+        }   // blk_lo < nb
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();    // every wave has read images 0 and 1: the pipelined ring is overlaid on images 0 .. 2
 #undef STORM_SR16_HEAD
@@ -248,7 +262,7 @@ __global__ __launch_bounds__(256, 4) void strip16_rows_kernel(
         STORM_FETCH16(fb, (((I) + 1) % 3) * kSr16StageBytes, 0); STORM_LGKM(3); STORM_MUL16(2, fc); __builtin_amdgcn_sched_barrier(0); \
         STORM_FETCH16(fc, (((I) + 1) % 3) * kSr16StageBytes, 1); STORM_LGKM(2); STORM_MUL16(3, fa); __builtin_amdgcn_sched_barrier(0); \
         ++t;                                                                                                \
-        if (t >= T) break;                                                                                  \
+        if (t >= Tl) break;                                                                                 \
         __builtin_amdgcn_s_barrier();                                                                       \
     }
     if (T != 0u) {
@@ -264,12 +278,27 @@ __global__ __launch_bounds__(256, 4) void strip16_rows_kernel(
         __builtin_amdgcn_s_barrier();
         STORM_FETCH16(b0, 0, 0);   // stage 0 sits in slot 0
         STORM_FETCH16(b1, 0, 1);
-        for (;;) {
-            STORM_SR16_BODY(0, b0, b1, b2)   // leaves fragments 0, 1 of the next image in b1, b2
-            STORM_SR16_BODY(1, b1, b2, b0)   // ... in b2, b0
-            STORM_SR16_BODY(2, b2, b0, b1)   // ... in b0, b1
-        }
+        if (Tl != 0u)
+            for (;;) {
+                STORM_SR16_BODY(0, b0, b1, b2)   // leaves fragments 0, 1 of the next image in b1, b2
+                STORM_SR16_BODY(1, b1, b2, b0)   // ... in b2, b0
+                STORM_SR16_BODY(2, b2, b0, b1)   // ... in b0, b1
+            }
         STORM_LGKM(0);
+        // The trimmed top block: image Tl in slot Tl % 3, published by the barrier in front of body Tl - 1 (or the prologue's);
+        // body Tl - 1 of any wave still writes slot (Tl + 1) % 3 only. Its fragments 0 and 1 are in flight in the registers of
+        // the exit site — b0, b1 | b1, b2 | b2, b0 — but MFMAs on three paths, or one path behind selects, made the register
+        // allocator move the accumulators and spill: the two fragments are read AGAIN, at a scalar offset, into b0 and b1.
+        // One dataflow, two ds_read_b128 and one LDS round trip per trimmed item; no barrier, no ring upkeep.
+        if (top_frags) {
+            uint32_t sb = (Tl % 3u) * kSr16StageBytes;
+            asm volatile("" : "+s"(sb));
+            STORM_FETCH16V(b0, sb, 0);
+            STORM_FETCH16V(b1, sb, 1);
+            STORM_LGKM(1); STORM_MUL16(0, b0); __builtin_amdgcn_sched_barrier(0);
+            STORM_LGKM(0);
+            if (top_frags == 2u) { STORM_MUL16(1, b1); __builtin_amdgcn_sched_barrier(0); }
+        }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the pieces issued beyond the last stage: none may land in a successor's LDS
     asm volatile("" ::"v"(b0), "v"(b1), "v"(b2), "v"(b3), "v"(wb));   // (every asm load's output lives up to its wait)
