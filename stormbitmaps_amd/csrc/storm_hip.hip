@@ -1534,8 +1534,9 @@ int storm_hip_square_matrix_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_
         set_error("square_matrix: NULL argument, unknown op, row widths differ or ld < rows of B");
         return STORM_HIP_EINVAL;
     }
-    STORM_HIP_TRY(hipSetDevice(ctx->device));
-    return launch_square_matrix(ctx, a, b, op, d_out, ld);
+    // (an empty side: nothing is queued and nothing waited for)
+    return pair_matrix_out(ctx, "square_matrix: the output", a->n_rows, b->n_rows, d_out, ld, false, false, a->n_rows && b->n_rows,
+                           [&](uint32_t* d, uint64_t d_ld) { return launch_square_matrix(ctx, a, b, op, d, d_ld); });
     });
 }
 
@@ -1578,40 +1579,46 @@ int storm_hip_cross_dense_total(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* 
     return STORM_HIP_OK;
 }
 
-int storm_hip_cross_dense_matrix_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b,
-                                        int op, uint32_t* d_out, uint64_t ld) {
-    int rc = storm_hip_square_matrix_device(ctx, a, b, op, d_out, ld);
-    if (rc == STORM_HIP_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) {
-        set_error("cross_dense_matrix: HIP failure");
-        rc = STORM_HIP_EHIP;
+// ... the per-pair counts: storm_hip_square_matrix_device's checks and kernels under its own name, into a caller's device
+// matrix or, with a row pitch, into HOST memory: h_out[i * ld + j], i < a rows, j < b rows (pair_matrix_out). The host form
+// checks its own arguments first and returns at an empty side; the device form writes the report then too.
+static int cross_dense_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b, int op, uint32_t* out,
+                              uint64_t ld, bool host) {
+    if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+    uint64_t rows = 0, cols = 0;   // what the host form's buffer holds
+    if (host) {
+        if (!a || !b || !out || ld < b->n_rows) {
+            set_error("cross_dense_matrix: NULL argument or ld < rows of B");
+            return STORM_HIP_EINVAL;
+        }
+        rows = a->n_rows, cols = b->n_rows;
+        if (rows == 0 || cols == 0) return STORM_HIP_OK;
     }
-    if (rc != STORM_HIP_OK) return rc;
+    // (storm_hip_square_matrix_device's checks come with the kernels: the host form meets them behind its buffer)
+    if (int rc = pair_matrix_out(ctx, "cross_dense_matrix: the output", rows, cols, out, ld, host, false, true,
+                                 [&](uint32_t* d, uint64_t d_ld) {
+                                     if (!a || !b || !d || d_ld < b->n_rows || op < STORM_HIP_OP_AND || op > STORM_HIP_OP_XOR ||
+                                         a->n_words != b->n_words) {
+                                         set_error("square_matrix: NULL argument, unknown op, row widths differ or ld < rows of B");
+                                         return STORM_HIP_EINVAL;
+                                     }
+                                     return launch_square_matrix(ctx, a, b, op, d, d_ld);
+                                 }))
+        return rc;
     ctx->pass_report[0] = STORM_HIP_RAN_TILES_OUT;
     ctx->pass_report[1] = a->n_rows * b->n_rows * a->n_words;
     ctx->pass_report[2] = ctx->pass_report[3] = 0;
     return STORM_HIP_OK;
 }
 
-// ... into HOST memory with a row pitch: h_out[i * ld + j], i < a rows, j < b rows (the context's band buffer in between)
+int storm_hip_cross_dense_matrix_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b,
+                                        int op, uint32_t* d_out, uint64_t ld) {
+    return guarded("storm_hip_cross_dense_matrix_device", [&] { return cross_dense_matrix(ctx, a, b, op, d_out, ld, false); });
+}
+
 int storm_hip_cross_dense_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b, int op,
                                  uint32_t* h_out, uint64_t ld) {
-    return guarded("storm_hip_cross_dense_matrix", [&]() -> int {
-    if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-    if (!a || !b || !h_out || ld < b->n_rows) {
-        set_error("cross_dense_matrix: NULL argument or ld < rows of B");
-        return STORM_HIP_EINVAL;
-    }
-    const uint64_t na = a->n_rows, nb = b->n_rows;
-    if (na == 0 || nb == 0) return STORM_HIP_OK;
-    STORM_HIP_TRY(hipSetDevice(ctx->device));
-    const size_t need = (size_t)na * nb * sizeof(uint32_t);
-    if (int rc = ctx->d_band.ensure(need, "cross_dense_matrix: the output")) return rc;
-    if (int rc = storm_hip_cross_dense_matrix_device(ctx, a, b, op, ctx->d_band, nb)) return rc;
-    STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(uint32_t), ctx->d_band, nb * sizeof(uint32_t), nb * sizeof(uint32_t), na,
-                                   hipMemcpyDeviceToHost, ctx->stream));
-    STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return STORM_HIP_OK;
-    });
+    return guarded("storm_hip_cross_dense_matrix", [&] { return cross_dense_matrix(ctx, a, b, op, h_out, ld, true); });
 }
 
 int storm_hip_pairw_matrix_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int op,
@@ -1622,51 +1629,41 @@ int storm_hip_pairw_matrix_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t
         set_error("pairw_matrix: NULL argument, unknown op or leading dimension < rows");
         return STORM_HIP_EINVAL;
     }
-    STORM_HIP_TRY(hipSetDevice(ctx->device));
-    return launch_pairw_matrix(ctx, m, op, d_out, ld);
+    // (below two rows the launcher queues nothing — a single row: the report of no pairs — and nothing is waited for)
+    return pair_matrix_out(ctx, "pairw_matrix: the output", m->n_rows, m->n_rows, d_out, ld, false, false, m->n_rows >= 2,
+                           [&](uint32_t* d, uint64_t d_ld) { return launch_pairw_matrix(ctx, m, op, d, d_ld); });
     });
 }
 
-int storm_hip_pairw_matrix_band_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int op,
-                                       uint64_t row0, uint64_t n_band_rows, uint32_t* d_out,
-                                       uint64_t ld) {
-    return guarded("storm_hip_pairw_matrix_band_device", [&]() -> int {
+// Rows [row0, row0 + n_band_rows) of the triangle from output row 0, into a caller's device matrix (complete on return) or
+// into HOST memory: the band is computed into the context's band buffer (kept between calls), cleared first, and copied out
+// row by row (ld may exceed n_rows). The host form only enqueues, so that one host thread can keep one band per GPU in
+// flight; storm_hip_pairw_matrix_band_end waits.
+static int pairw_matrix_band(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int op, uint64_t row0, uint64_t n_band_rows,
+                             uint32_t* out, uint64_t ld, bool host) {
     if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-    if (!m || !d_out || ld < m->n_rows || op < STORM_HIP_OP_AND || op > STORM_HIP_OP_XOR ||
-        row0 > m->n_rows || n_band_rows > m->n_rows - row0) {
-        set_error("pairw_matrix_band: NULL argument, unknown op, band outside the matrix or ld < rows");
-        return STORM_HIP_EINVAL;
-    }
-    STORM_HIP_TRY(hipSetDevice(ctx->device));
-    return launch_pairw_matrix(ctx, m, op, d_out, ld, row0, n_band_rows);
-    });
-}
-
-// Host-output band: the band is computed into a staging buffer of the context (kept between
-// calls) and copied out row by row (ld may exceed n_rows). _begin only enqueues, so that one host
-// thread can keep one band per GPU in flight; _end waits.
-int storm_hip_pairw_matrix_band_begin(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int op,
-                                      uint64_t row0, uint64_t n_band_rows, uint32_t* h_out,
-                                      uint64_t ld) {
-    return guarded("storm_hip_pairw_matrix_band_begin", [&]() -> int {
-    if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-    if (!m || !h_out || op < STORM_HIP_OP_AND || op > STORM_HIP_OP_XOR || ld < m->n_rows ||
+    if (!m || !out || op < STORM_HIP_OP_AND || op > STORM_HIP_OP_XOR || ld < m->n_rows ||
         row0 > m->n_rows || n_band_rows > m->n_rows - row0) {
         set_error("pairw_matrix_band: NULL argument, unknown op, band outside the matrix or ld < rows");
         return STORM_HIP_EINVAL;
     }
     const uint64_t n = m->n_rows;
     if (n == 0 || n_band_rows == 0) return STORM_HIP_OK;
-    STORM_HIP_TRY(hipSetDevice(ctx->device));
-    const size_t need = (size_t)n_band_rows * n * sizeof(uint32_t);
-    if (int rc = ctx->d_band.ensure(need, "pairw_matrix_band: the output band")) return rc;
-    STORM_HIP_TRY(hipMemsetAsync(ctx->d_band, 0, need, ctx->stream));
-    if (int rc = launch_pairw_matrix(ctx, m, op, ctx->d_band, n, row0, n_band_rows, false)) return rc;
-    STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(uint32_t), ctx->d_band, n * sizeof(uint32_t),
-                                   n * sizeof(uint32_t), n_band_rows, hipMemcpyDeviceToHost,
-                                   ctx->stream));
-    return STORM_HIP_OK;
-    });
+    // (device form, a single row: the launcher writes the report of no pairs and queues nothing to wait for)
+    return pair_matrix_out(ctx, "pairw_matrix_band: the output band", n_band_rows, n, out, ld, host, true, !host && n >= 2,
+                           [&](uint32_t* d, uint64_t d_ld) { return launch_pairw_matrix(ctx, m, op, d, d_ld, row0, n_band_rows); });
+}
+
+int storm_hip_pairw_matrix_band_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int op,
+                                       uint64_t row0, uint64_t n_band_rows, uint32_t* d_out,
+                                       uint64_t ld) {
+    return guarded("storm_hip_pairw_matrix_band_device", [&] { return pairw_matrix_band(ctx, m, op, row0, n_band_rows, d_out, ld, false); });
+}
+
+int storm_hip_pairw_matrix_band_begin(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int op,
+                                      uint64_t row0, uint64_t n_band_rows, uint32_t* h_out,
+                                      uint64_t ld) {
+    return guarded("storm_hip_pairw_matrix_band_begin", [&] { return pairw_matrix_band(ctx, m, op, row0, n_band_rows, h_out, ld, true); });
 }
 
 int storm_hip_pairw_matrix_band_end(storm_hip_ctx_t* ctx) {

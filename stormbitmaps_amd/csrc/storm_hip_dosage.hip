@@ -311,7 +311,7 @@ static int dosage_sums_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m)
 static int dosage_corr_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int measure, uint64_t n_samples, uint32_t* d_io,
                               uint64_t ld) {
     const uint64_t n = m->n_rows;
-    if (int rc = launch_pairw_dosage_matrix(ctx, m, d_io, ld, false)) return rc;
+    if (int rc = launch_pairw_dosage_matrix(ctx, m, d_io, ld)) return rc;
     if (int rc = dosage_sums_queued(ctx, m)) return rc;
     const uint64_t tiles_x = (n + kDosTileCols - 1) / kDosTileCols, tiles_y = (n + kDosTileRows - 1) / kDosTileRows;
     if (tiles_y > 65535u) {
@@ -366,7 +366,7 @@ static int dosage_split_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* x
 static int dosage_nobs_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint64_t n_samples, uint32_t* d_out, uint64_t ld) {
     DosageSplit sp;
     if (int rc = dosage_split_queued(ctx, m, n_samples, &sp)) return rc;
-    return launch_pairw_dosage_matrix(ctx, &sp.m, d_out, ld, false);
+    return launch_pairw_dosage_matrix(ctx, &sp.m, d_out, ld);
 }
 
 // The pairwise-complete correlation at d_io (pitch ld): the split; P = the triangle of G straight into d_io; N = the
@@ -386,9 +386,9 @@ static int dosage_corr_complete_queued(storm_hip_ctx_t* ctx, const storm_hip_mat
     uint32_t* const d_gm = d_nobs + n * lds;
     uint32_t* const d_hm = d_gm + sp.rows128 * lds;
     // (the two triangles are planned alike: the second one launches from the first one's list)
-    if (int rc = launch_pairw_dosage_matrix(ctx, &sp.g, d_io, ld, false)) return rc;
-    if (int rc = launch_pairw_dosage_matrix(ctx, &sp.m, d_nobs, lds, false)) return rc;
-    if (int rc = launch_square_dosage_matrix(ctx, &sp.gh, &sp.m, d_gm, lds, false)) return rc;
+    if (int rc = launch_pairw_dosage_matrix(ctx, &sp.g, d_io, ld)) return rc;
+    if (int rc = launch_pairw_dosage_matrix(ctx, &sp.m, d_nobs, lds)) return rc;
+    if (int rc = launch_square_dosage_matrix(ctx, &sp.gh, &sp.m, d_gm, lds)) return rc;
     const uint64_t tiles = (n + kDosCompleteTile - 1) / kDosCompleteTile;
     if (tiles > 65535u) {
         set_error("pairw_dosage_corr_complete: %llu rows exceed the finishing pass's launch grid", (unsigned long long)n);
@@ -519,7 +519,7 @@ static int launch_dosage_finish_lag(storm_hip_ctx_t* ctx, void* d_io, uint64_t l
 static int lag_dosage_corr_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int measure, uint64_t n_samples,
                                   uint64_t max_lag, uint32_t* d_io, uint64_t ld) {
     const uint64_t n = m->n_rows;
-    if (int rc = launch_pairw_lag_dosage_matrix(ctx, m, max_lag, 0, n, d_io, ld, false)) return rc;
+    if (int rc = launch_pairw_lag_dosage_matrix(ctx, m, max_lag, 0, n, d_io, ld)) return rc;
     if (int rc = dosage_sums_queued(ctx, m)) return rc;
     return launch_dosage_finish_lag(ctx, d_io, ld, n, 0, n, max_lag, ctx->d_counts.d, ctx->d_counts.d + n, measure, n_samples);
 }
@@ -563,7 +563,7 @@ static int lag_dosage_nobs_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s
                                   uint32_t* d_out, uint64_t ld) {
     DosageInterleaved sp;
     if (int rc = dosage_interleave_queued(ctx, m, n_samples, &sp)) return rc;
-    return launch_pairw_lag_dosage_matrix(ctx, &sp.m, max_lag, 0, m->n_rows, d_out, ld, false);
+    return launch_pairw_lag_dosage_matrix(ctx, &sp.m, max_lag, 0, m->n_rows, d_out, ld);
 }
 
 // The pitch of the scratch matrix of sums below (lag_dosage_r2_band_queued hands N out of it to the LD-score calls): 3 L + 2 columns up to the next
@@ -588,26 +588,11 @@ static int lag_dosage_corr_complete_queued(storm_hip_ctx_t* ctx, const storm_hip
     if (int rc = ctx->d_dosage_sums.ensure(3 * n * lds * sizeof(uint32_t),
                                            "pairw_lag_dosage_corr_complete: the sums of the interleaved rows within the lag"))
         return rc;
-    if (int rc = launch_pairw_lag_dosage_matrix(ctx, &sp.all, lag3, 0, 3 * n, ctx->d_dosage_sums.d, lds, false)) return rc;
+    if (int rc = launch_pairw_lag_dosage_matrix(ctx, &sp.all, lag3, 0, 3 * n, ctx->d_dosage_sums.d, lds)) return rc;
     hipLaunchKernelGGL(dosage_complete_finish_lag_kernel, dim3((uint32_t)tiles_x, (uint32_t)tiles_y), dim3(256), 0, ctx->stream,
                        ctx->d_dosage_sums.d, lds, d_out, ld, n, L, measure);
     STORM_HIP_TRY(hipGetLastError());
     ctx->pass_report[0] |= STORM_HIP_RAN_SIMILARITY;   // ([1]: the interleaved rows' pairs within 3 L + 2 x n_words)
-    return STORM_HIP_OK;
-}
-
-// the host forms: `queued` writes the n x L matrix into the band buffer (0 in the corner), which then goes to h_out
-template <typename Queued>
-static int lag_dosage_to_host(storm_hip_ctx_t* ctx, const char* what, uint64_t n, uint64_t lag, void* h_out, uint64_t ld,
-                              Queued queued) {
-    STORM_HIP_TRY(hipSetDevice(ctx->device));
-    const size_t need = (size_t)n * lag * sizeof(uint32_t);
-    if (int rc = ctx->d_band.ensure(need, what)) return rc;
-    STORM_HIP_TRY(hipMemsetAsync(ctx->d_band, 0, need, ctx->stream));   // (the lower-right corner: +0.0f is the same zero bits)
-    if (int rc = queued(ctx->d_band.d, lag)) return rc;
-    STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(uint32_t), ctx->d_band, lag * sizeof(uint32_t), lag * sizeof(uint32_t), n,
-                                   hipMemcpyDeviceToHost, ctx->stream));
-    STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
     return STORM_HIP_OK;
 }
 
@@ -785,6 +770,100 @@ static int lag_dosage_prune(storm_hip_ctx_t* ctx, const char* who, const storm_h
     return STORM_HIP_OK;
 }
 
+// ---- the per-pair matrix calls: one body for the device form and the host form of each (pair_matrix_out, storm_hip_internal.h) ----
+// A triangle of n x n entries, cleared in the band buffer (entries i >= j): `queued` where there is a pair. The device form
+// returns below two rows without touching its matrix; the host form returns without rows and writes the one zero of a single row.
+template <typename Queued>
+static int dosage_triangle_out(storm_hip_ctx_t* ctx, const char* what, uint64_t n, void* out, uint64_t ld, bool host, Queued queued) {
+    if (host ? n == 0 : n < 2) return STORM_HIP_OK;
+    return pair_matrix_out(ctx, what, n, n, out, ld, host, true, true,
+                           [&](uint32_t* d, uint64_t d_ld) { return n >= 2 ? queued(d, d_ld) : STORM_HIP_OK; });
+}
+
+static int pairw_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint32_t* out, uint64_t ld, bool host) {
+    if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+    if (int rc = check_dosage("pairw_dosage_matrix", m, out, ld)) return rc;
+    return dosage_triangle_out(ctx, "pairw_dosage_matrix: the output", m->n_rows, out, ld, host,
+                               [&](uint32_t* d, uint64_t d_ld) { return launch_pairw_dosage_matrix(ctx, m, d, d_ld); });
+}
+
+static int pairw_dosage_corr(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int measure, uint64_t n_samples, bool complete,
+                             float* out, uint64_t ld, bool host) {
+    if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+    const char* const who = complete ? "pairw_dosage_corr_complete" : "pairw_dosage_corr";
+    if (int rc = check_dosage(who, m, out, ld)) return rc;
+    if (int rc = check_corr(who, m, measure, n_samples)) return rc;
+    return dosage_triangle_out(ctx, complete ? "pairw_dosage_corr_complete: the output" : "pairw_dosage_corr: the output", m->n_rows,
+                               out, ld, host, [&](uint32_t* d, uint64_t d_ld) {
+                                   return complete ? dosage_corr_complete_queued(ctx, m, measure, n_samples, d, d_ld)
+                                                   : dosage_corr_queued(ctx, m, measure, n_samples, d, d_ld);
+                               });
+}
+
+static int pairw_dosage_nobs(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint64_t n_samples, uint32_t* out, uint64_t ld,
+                             bool host) {
+    if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+    if (int rc = check_dosage("pairw_dosage_nobs", m, out, ld)) return rc;
+    if (int rc = check_samples("pairw_dosage_nobs", m, n_samples)) return rc;
+    return dosage_triangle_out(ctx, "pairw_dosage_nobs: the output", m->n_rows, out, ld, host,
+                               [&](uint32_t* d, uint64_t d_ld) { return dosage_nobs_queued(ctx, m, n_samples, d, d_ld); });
+}
+
+// (a rectangle: every entry is written, nothing to clear)
+static int square_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, uint32_t* out,
+                                uint64_t ld, bool host) {
+    if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+    if (int rc = check_square("square_dosage_matrix", a, b, out, ld)) return rc;
+    if (a->n_rows == 0 || b->n_rows == 0) return STORM_HIP_OK;
+    return pair_matrix_out(ctx, "square_dosage_matrix: the output", a->n_rows, b->n_rows, out, ld, host, false, true,
+                           [&](uint32_t* d, uint64_t d_ld) { return launch_square_dosage_matrix(ctx, a, b, d, d_ld); });
+}
+
+// The lag layout, n x L, cleared in the band buffer (the lower-right corner): both forms return below two rows. The dot
+// products alone take a band of rows in their device form (the host form: every row).
+static int pairw_lag_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint64_t max_lag, uint64_t row0,
+                                   uint64_t n_band_rows, uint32_t* out, uint64_t ld, bool host) {
+    if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+    uint64_t lag = 0;
+    if (int rc = check_lag_dosage("pairw_lag_dosage_matrix", m, out, max_lag, ld, &lag)) return rc;
+    if (n_band_rows == ~0ull && row0 <= m->n_rows) n_band_rows = m->n_rows - row0;
+    if (row0 > m->n_rows || n_band_rows > m->n_rows - row0) {
+        set_error("pairw_lag_dosage_matrix: a band outside the rows");
+        return STORM_HIP_EINVAL;
+    }
+    if (m->n_rows < 2 || n_band_rows == 0) return STORM_HIP_OK;
+    return pair_matrix_out(ctx, "pairw_lag_dosage_matrix: the output", n_band_rows, lag, out, ld, host, true, true,
+                           [&](uint32_t* d, uint64_t d_ld) {
+                               return launch_pairw_lag_dosage_matrix(ctx, m, max_lag, row0, n_band_rows, d, d_ld);
+                           });
+}
+
+static int pairw_lag_dosage_corr(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int measure, uint64_t n_samples, uint64_t max_lag,
+                                 bool complete, float* out, uint64_t ld, bool host) {
+    if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+    const char* const who = complete ? "pairw_lag_dosage_corr_complete" : "pairw_lag_dosage_corr";
+    uint64_t lag = 0;
+    if (int rc = check_lag_dosage(who, m, out, max_lag, ld, &lag)) return rc;
+    if (int rc = check_corr(who, m, measure, n_samples)) return rc;
+    if (m->n_rows < 2) return STORM_HIP_OK;
+    return pair_matrix_out(ctx, complete ? "pairw_lag_dosage_corr_complete: the output" : "pairw_lag_dosage_corr: the output",
+                           m->n_rows, lag, out, ld, host, true, true, [&](uint32_t* d, uint64_t d_ld) {
+                               return complete ? lag_dosage_corr_complete_queued(ctx, m, measure, n_samples, max_lag, d, d_ld)
+                                               : lag_dosage_corr_queued(ctx, m, measure, n_samples, max_lag, d, d_ld);
+                           });
+}
+
+static int pairw_lag_dosage_nobs(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint64_t n_samples, uint64_t max_lag,
+                                 uint32_t* out, uint64_t ld, bool host) {
+    if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+    uint64_t lag = 0;
+    if (int rc = check_lag_dosage("pairw_lag_dosage_nobs", m, out, max_lag, ld, &lag)) return rc;
+    if (int rc = check_samples("pairw_lag_dosage_nobs", m, n_samples)) return rc;
+    if (m->n_rows < 2) return STORM_HIP_OK;
+    return pair_matrix_out(ctx, "pairw_lag_dosage_nobs: the output", m->n_rows, lag, out, ld, host, true, true,
+                           [&](uint32_t* d, uint64_t d_ld) { return lag_dosage_nobs_queued(ctx, m, n_samples, max_lag, d, d_ld); });
+}
+
 }  // namespace storm
 
 using namespace storm;
@@ -814,94 +893,33 @@ int storm_hip_dosage_row_sums(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m,
 }
 
 int storm_hip_pairw_dosage_matrix_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint32_t* d_out, uint64_t ld) {
-    return guarded("storm_hip_pairw_dosage_matrix_device", [&]() -> int {
-        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-        if (int rc = check_dosage("pairw_dosage_matrix", m, d_out, ld)) return rc;
-        if (m->n_rows < 2) return STORM_HIP_OK;
-        STORM_HIP_TRY(hipSetDevice(ctx->device));
-        return launch_pairw_dosage_matrix(ctx, m, d_out, ld, true);
-    });
+    return guarded("storm_hip_pairw_dosage_matrix_device", [&] { return pairw_dosage_matrix(ctx, m, d_out, ld, false); });
 }
 
 int storm_hip_pairw_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint32_t* h_out, uint64_t ld) {
-    return guarded("storm_hip_pairw_dosage_matrix", [&]() -> int {
-        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-        if (int rc = check_dosage("pairw_dosage_matrix", m, h_out, ld)) return rc;
-        const uint64_t n = m->n_rows;
-        if (n == 0) return STORM_HIP_OK;
-        STORM_HIP_TRY(hipSetDevice(ctx->device));
-        const size_t need = (size_t)n * n * sizeof(uint32_t);
-        if (int rc = ctx->d_band.ensure(need, "pairw_dosage_matrix: the output")) return rc;
-        STORM_HIP_TRY(hipMemsetAsync(ctx->d_band, 0, need, ctx->stream));   // (entries i >= j)
-        if (int rc = launch_pairw_dosage_matrix(ctx, m, ctx->d_band, n, false)) return rc;
-        STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(uint32_t), ctx->d_band, n * sizeof(uint32_t), n * sizeof(uint32_t), n,
-                                       hipMemcpyDeviceToHost, ctx->stream));
-        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return STORM_HIP_OK;
-    });
+    return guarded("storm_hip_pairw_dosage_matrix", [&] { return pairw_dosage_matrix(ctx, m, h_out, ld, true); });
 }
 
 int storm_hip_pairw_dosage_corr_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_samples,
                                        float* d_out, uint64_t ld) {
-    return guarded("storm_hip_pairw_dosage_corr_device", [&]() -> int {
-        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-        if (int rc = check_dosage("pairw_dosage_corr", m, d_out, ld)) return rc;
-        if (int rc = check_corr("pairw_dosage_corr", m, measure, n_samples)) return rc;
-        if (m->n_rows < 2) return STORM_HIP_OK;
-        STORM_HIP_TRY(hipSetDevice(ctx->device));
-        if (int rc = dosage_corr_queued(ctx, m, measure, n_samples, reinterpret_cast<uint32_t*>(d_out), ld)) return rc;
-        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return STORM_HIP_OK;
-    });
+    return guarded("storm_hip_pairw_dosage_corr_device",
+                   [&] { return pairw_dosage_corr(ctx, m, measure, n_samples, false, d_out, ld, false); });
 }
 
 int storm_hip_pairw_dosage_corr(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_samples, float* h_out,
                                 uint64_t ld) {
-    return guarded("storm_hip_pairw_dosage_corr", [&]() -> int {
-        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-        if (int rc = check_dosage("pairw_dosage_corr", m, h_out, ld)) return rc;
-        if (int rc = check_corr("pairw_dosage_corr", m, measure, n_samples)) return rc;
-        const uint64_t n = m->n_rows;
-        if (n == 0) return STORM_HIP_OK;
-        STORM_HIP_TRY(hipSetDevice(ctx->device));
-        const size_t need = (size_t)n * n * sizeof(uint32_t);
-        if (int rc = ctx->d_band.ensure(need, "pairw_dosage_corr: the output")) return rc;
-        STORM_HIP_TRY(hipMemsetAsync(ctx->d_band, 0, need, ctx->stream));   // (entries i >= j: +0.0f is the same zero bits)
-        if (n >= 2)
-            if (int rc = dosage_corr_queued(ctx, m, measure, n_samples, ctx->d_band, n)) return rc;
-        STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(float), ctx->d_band, n * sizeof(uint32_t), n * sizeof(uint32_t), n,
-                                       hipMemcpyDeviceToHost, ctx->stream));
-        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return STORM_HIP_OK;
-    });
+    return guarded("storm_hip_pairw_dosage_corr",
+                   [&] { return pairw_dosage_corr(ctx, m, measure, n_samples, false, h_out, ld, true); });
 }
 
 int storm_hip_square_dosage_matrix_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b,
                                           uint32_t* d_out, uint64_t ld) {
-    return guarded("storm_hip_square_dosage_matrix_device", [&]() -> int {
-        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-        if (int rc = check_square("square_dosage_matrix", a, b, d_out, ld)) return rc;
-        if (a->n_rows == 0 || b->n_rows == 0) return STORM_HIP_OK;
-        STORM_HIP_TRY(hipSetDevice(ctx->device));
-        return launch_square_dosage_matrix(ctx, a, b, d_out, ld, true);
-    });
+    return guarded("storm_hip_square_dosage_matrix_device", [&] { return square_dosage_matrix(ctx, a, b, d_out, ld, false); });
 }
 
 int storm_hip_square_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b, uint32_t* h_out,
                                    uint64_t ld) {
-    return guarded("storm_hip_square_dosage_matrix", [&]() -> int {
-        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-        if (int rc = check_square("square_dosage_matrix", a, b, h_out, ld)) return rc;
-        const uint64_t na = a->n_rows, nb = b->n_rows;
-        if (na == 0 || nb == 0) return STORM_HIP_OK;
-        STORM_HIP_TRY(hipSetDevice(ctx->device));
-        if (int rc = ctx->d_band.ensure((size_t)na * nb * sizeof(uint32_t), "square_dosage_matrix: the output")) return rc;
-        if (int rc = launch_square_dosage_matrix(ctx, a, b, ctx->d_band, nb, false)) return rc;
-        STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(uint32_t), ctx->d_band, nb * sizeof(uint32_t), nb * sizeof(uint32_t), na,
-                                       hipMemcpyDeviceToHost, ctx->stream));
-        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return STORM_HIP_OK;
-    });
+    return guarded("storm_hip_square_dosage_matrix", [&] { return square_dosage_matrix(ctx, a, b, h_out, ld, true); });
 }
 
 int storm_hip_dosage_row_missing(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint32_t* h_missing) {
@@ -924,103 +942,36 @@ int storm_hip_dosage_row_missing(storm_hip_ctx_t* ctx, const storm_hip_matrix_t*
 
 int storm_hip_pairw_dosage_nobs_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint32_t* d_out,
                                        uint64_t ld) {
-    return guarded("storm_hip_pairw_dosage_nobs_device", [&]() -> int {
-        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-        if (int rc = check_dosage("pairw_dosage_nobs", m, d_out, ld)) return rc;
-        if (int rc = check_samples("pairw_dosage_nobs", m, n_samples)) return rc;
-        if (m->n_rows < 2) return STORM_HIP_OK;
-        STORM_HIP_TRY(hipSetDevice(ctx->device));
-        if (int rc = dosage_nobs_queued(ctx, m, n_samples, d_out, ld)) return rc;
-        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return STORM_HIP_OK;
-    });
+    return guarded("storm_hip_pairw_dosage_nobs_device", [&] { return pairw_dosage_nobs(ctx, m, n_samples, d_out, ld, false); });
 }
 
 int storm_hip_pairw_dosage_nobs(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint32_t* h_out, uint64_t ld) {
-    return guarded("storm_hip_pairw_dosage_nobs", [&]() -> int {
-        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-        if (int rc = check_dosage("pairw_dosage_nobs", m, h_out, ld)) return rc;
-        if (int rc = check_samples("pairw_dosage_nobs", m, n_samples)) return rc;
-        const uint64_t n = m->n_rows;
-        if (n == 0) return STORM_HIP_OK;
-        STORM_HIP_TRY(hipSetDevice(ctx->device));
-        const size_t need = (size_t)n * n * sizeof(uint32_t);
-        if (int rc = ctx->d_band.ensure(need, "pairw_dosage_nobs: the output")) return rc;
-        STORM_HIP_TRY(hipMemsetAsync(ctx->d_band, 0, need, ctx->stream));   // (entries i >= j)
-        if (n >= 2)
-            if (int rc = dosage_nobs_queued(ctx, m, n_samples, ctx->d_band, n)) return rc;
-        STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(uint32_t), ctx->d_band, n * sizeof(uint32_t), n * sizeof(uint32_t), n,
-                                       hipMemcpyDeviceToHost, ctx->stream));
-        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return STORM_HIP_OK;
-    });
+    return guarded("storm_hip_pairw_dosage_nobs", [&] { return pairw_dosage_nobs(ctx, m, n_samples, h_out, ld, true); });
 }
 
 int storm_hip_pairw_dosage_corr_complete_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_samples,
                                                 float* d_out, uint64_t ld) {
-    return guarded("storm_hip_pairw_dosage_corr_complete_device", [&]() -> int {
-        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-        if (int rc = check_dosage("pairw_dosage_corr_complete", m, d_out, ld)) return rc;
-        if (int rc = check_corr("pairw_dosage_corr_complete", m, measure, n_samples)) return rc;
-        if (m->n_rows < 2) return STORM_HIP_OK;
-        STORM_HIP_TRY(hipSetDevice(ctx->device));
-        if (int rc = dosage_corr_complete_queued(ctx, m, measure, n_samples, reinterpret_cast<uint32_t*>(d_out), ld)) return rc;
-        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return STORM_HIP_OK;
-    });
+    return guarded("storm_hip_pairw_dosage_corr_complete_device",
+                   [&] { return pairw_dosage_corr(ctx, m, measure, n_samples, true, d_out, ld, false); });
 }
 
 int storm_hip_pairw_dosage_corr_complete(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_samples,
                                          float* h_out, uint64_t ld) {
-    return guarded("storm_hip_pairw_dosage_corr_complete", [&]() -> int {
-        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-        if (int rc = check_dosage("pairw_dosage_corr_complete", m, h_out, ld)) return rc;
-        if (int rc = check_corr("pairw_dosage_corr_complete", m, measure, n_samples)) return rc;
-        const uint64_t n = m->n_rows;
-        if (n == 0) return STORM_HIP_OK;
-        STORM_HIP_TRY(hipSetDevice(ctx->device));
-        const size_t need = (size_t)n * n * sizeof(uint32_t);
-        if (int rc = ctx->d_band.ensure(need, "pairw_dosage_corr_complete: the output")) return rc;
-        STORM_HIP_TRY(hipMemsetAsync(ctx->d_band, 0, need, ctx->stream));   // (entries i >= j: +0.0f is the same zero bits)
-        if (n >= 2)
-            if (int rc = dosage_corr_complete_queued(ctx, m, measure, n_samples, ctx->d_band, n)) return rc;
-        STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(float), ctx->d_band, n * sizeof(uint32_t), n * sizeof(uint32_t), n,
-                                       hipMemcpyDeviceToHost, ctx->stream));
-        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return STORM_HIP_OK;
-    });
+    return guarded("storm_hip_pairw_dosage_corr_complete",
+                   [&] { return pairw_dosage_corr(ctx, m, measure, n_samples, true, h_out, ld, true); });
 }
 
 // ---- the lag layout ----
 int storm_hip_pairw_lag_dosage_matrix_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t max_lag, uint64_t row0,
                                              uint64_t n_band_rows, uint32_t* d_out, uint64_t ld) {
-    return guarded("storm_hip_pairw_lag_dosage_matrix_device", [&]() -> int {
-        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-        uint64_t lag = 0;
-        if (int rc = check_lag_dosage("pairw_lag_dosage_matrix", m, d_out, max_lag, ld, &lag)) return rc;
-        if (n_band_rows == ~0ull && row0 <= m->n_rows) n_band_rows = m->n_rows - row0;
-        if (row0 > m->n_rows || n_band_rows > m->n_rows - row0) {
-            set_error("pairw_lag_dosage_matrix: a band outside the rows");
-            return STORM_HIP_EINVAL;
-        }
-        if (m->n_rows < 2 || n_band_rows == 0) return STORM_HIP_OK;
-        STORM_HIP_TRY(hipSetDevice(ctx->device));
-        return launch_pairw_lag_dosage_matrix(ctx, m, max_lag, row0, n_band_rows, d_out, ld, true);
-    });
+    return guarded("storm_hip_pairw_lag_dosage_matrix_device",
+                   [&] { return pairw_lag_dosage_matrix(ctx, m, max_lag, row0, n_band_rows, d_out, ld, false); });
 }
 
 int storm_hip_pairw_lag_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t max_lag, uint32_t* h_out,
                                       uint64_t ld) {
-    return guarded("storm_hip_pairw_lag_dosage_matrix", [&]() -> int {
-        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-        uint64_t lag = 0;
-        if (int rc = check_lag_dosage("pairw_lag_dosage_matrix", m, h_out, max_lag, ld, &lag)) return rc;
-        const uint64_t n = m->n_rows;
-        if (n < 2) return STORM_HIP_OK;
-        return lag_dosage_to_host(ctx, "pairw_lag_dosage_matrix: the output", n, lag, h_out, ld, [&](uint32_t* d, uint64_t d_ld) {
-            return launch_pairw_lag_dosage_matrix(ctx, m, max_lag, 0, n, d, d_ld, false);
-        });
-    });
+    return guarded("storm_hip_pairw_lag_dosage_matrix",
+                   [&] { return pairw_lag_dosage_matrix(ctx, m, max_lag, 0, ~0ull, h_out, ld, true); });
 }
 
 int storm_hip_dosage_finish_lag_device(storm_hip_ctx_t* ctx, void* d_io, uint64_t ld, uint64_t n_rows, uint64_t row0,
@@ -1041,94 +992,38 @@ int storm_hip_dosage_finish_lag_device(storm_hip_ctx_t* ctx, void* d_io, uint64_
 
 int storm_hip_pairw_lag_dosage_corr_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_samples,
                                            uint64_t max_lag, float* d_out, uint64_t ld) {
-    return guarded("storm_hip_pairw_lag_dosage_corr_device", [&]() -> int {
-        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-        uint64_t lag = 0;
-        if (int rc = check_lag_dosage("pairw_lag_dosage_corr", m, d_out, max_lag, ld, &lag)) return rc;
-        if (int rc = check_corr("pairw_lag_dosage_corr", m, measure, n_samples)) return rc;
-        if (m->n_rows < 2) return STORM_HIP_OK;
-        STORM_HIP_TRY(hipSetDevice(ctx->device));
-        if (int rc = lag_dosage_corr_queued(ctx, m, measure, n_samples, max_lag, reinterpret_cast<uint32_t*>(d_out), ld)) return rc;
-        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return STORM_HIP_OK;
-    });
+    return guarded("storm_hip_pairw_lag_dosage_corr_device",
+                   [&] { return pairw_lag_dosage_corr(ctx, m, measure, n_samples, max_lag, false, d_out, ld, false); });
 }
 
 int storm_hip_pairw_lag_dosage_corr(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_samples,
                                     uint64_t max_lag, float* h_out, uint64_t ld) {
-    return guarded("storm_hip_pairw_lag_dosage_corr", [&]() -> int {
-        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-        uint64_t lag = 0;
-        if (int rc = check_lag_dosage("pairw_lag_dosage_corr", m, h_out, max_lag, ld, &lag)) return rc;
-        if (int rc = check_corr("pairw_lag_dosage_corr", m, measure, n_samples)) return rc;
-        const uint64_t n = m->n_rows;
-        if (n < 2) return STORM_HIP_OK;
-        return lag_dosage_to_host(ctx, "pairw_lag_dosage_corr: the output", n, lag, h_out, ld, [&](uint32_t* d, uint64_t d_ld) {
-            return lag_dosage_corr_queued(ctx, m, measure, n_samples, max_lag, d, d_ld);
-        });
-    });
+    return guarded("storm_hip_pairw_lag_dosage_corr",
+                   [&] { return pairw_lag_dosage_corr(ctx, m, measure, n_samples, max_lag, false, h_out, ld, true); });
 }
 
 int storm_hip_pairw_lag_dosage_nobs_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint64_t max_lag,
                                            uint32_t* d_out, uint64_t ld) {
-    return guarded("storm_hip_pairw_lag_dosage_nobs_device", [&]() -> int {
-        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-        uint64_t lag = 0;
-        if (int rc = check_lag_dosage("pairw_lag_dosage_nobs", m, d_out, max_lag, ld, &lag)) return rc;
-        if (int rc = check_samples("pairw_lag_dosage_nobs", m, n_samples)) return rc;
-        if (m->n_rows < 2) return STORM_HIP_OK;
-        STORM_HIP_TRY(hipSetDevice(ctx->device));
-        if (int rc = lag_dosage_nobs_queued(ctx, m, n_samples, max_lag, d_out, ld)) return rc;
-        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return STORM_HIP_OK;
-    });
+    return guarded("storm_hip_pairw_lag_dosage_nobs_device",
+                   [&] { return pairw_lag_dosage_nobs(ctx, m, n_samples, max_lag, d_out, ld, false); });
 }
 
 int storm_hip_pairw_lag_dosage_nobs(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint64_t max_lag,
                                     uint32_t* h_out, uint64_t ld) {
-    return guarded("storm_hip_pairw_lag_dosage_nobs", [&]() -> int {
-        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-        uint64_t lag = 0;
-        if (int rc = check_lag_dosage("pairw_lag_dosage_nobs", m, h_out, max_lag, ld, &lag)) return rc;
-        if (int rc = check_samples("pairw_lag_dosage_nobs", m, n_samples)) return rc;
-        const uint64_t n = m->n_rows;
-        if (n < 2) return STORM_HIP_OK;
-        return lag_dosage_to_host(ctx, "pairw_lag_dosage_nobs: the output", n, lag, h_out, ld, [&](uint32_t* d, uint64_t d_ld) {
-            return lag_dosage_nobs_queued(ctx, m, n_samples, max_lag, d, d_ld);
-        });
-    });
+    return guarded("storm_hip_pairw_lag_dosage_nobs",
+                   [&] { return pairw_lag_dosage_nobs(ctx, m, n_samples, max_lag, h_out, ld, true); });
 }
 
 int storm_hip_pairw_lag_dosage_corr_complete_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure,
                                                     uint64_t n_samples, uint64_t max_lag, float* d_out, uint64_t ld) {
-    return guarded("storm_hip_pairw_lag_dosage_corr_complete_device", [&]() -> int {
-        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-        uint64_t lag = 0;
-        if (int rc = check_lag_dosage("pairw_lag_dosage_corr_complete", m, d_out, max_lag, ld, &lag)) return rc;
-        if (int rc = check_corr("pairw_lag_dosage_corr_complete", m, measure, n_samples)) return rc;
-        if (m->n_rows < 2) return STORM_HIP_OK;
-        STORM_HIP_TRY(hipSetDevice(ctx->device));
-        if (int rc = lag_dosage_corr_complete_queued(ctx, m, measure, n_samples, max_lag, reinterpret_cast<uint32_t*>(d_out), ld))
-            return rc;
-        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return STORM_HIP_OK;
-    });
+    return guarded("storm_hip_pairw_lag_dosage_corr_complete_device",
+                   [&] { return pairw_lag_dosage_corr(ctx, m, measure, n_samples, max_lag, true, d_out, ld, false); });
 }
 
 int storm_hip_pairw_lag_dosage_corr_complete(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_samples,
                                              uint64_t max_lag, float* h_out, uint64_t ld) {
-    return guarded("storm_hip_pairw_lag_dosage_corr_complete", [&]() -> int {
-        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-        uint64_t lag = 0;
-        if (int rc = check_lag_dosage("pairw_lag_dosage_corr_complete", m, h_out, max_lag, ld, &lag)) return rc;
-        if (int rc = check_corr("pairw_lag_dosage_corr_complete", m, measure, n_samples)) return rc;
-        const uint64_t n = m->n_rows;
-        if (n < 2) return STORM_HIP_OK;
-        return lag_dosage_to_host(ctx, "pairw_lag_dosage_corr_complete: the output", n, lag, h_out, ld,
-                                  [&](uint32_t* d, uint64_t d_ld) {
-                                      return lag_dosage_corr_complete_queued(ctx, m, measure, n_samples, max_lag, d, d_ld);
-                                  });
-    });
+    return guarded("storm_hip_pairw_lag_dosage_corr_complete",
+                   [&] { return pairw_lag_dosage_corr(ctx, m, measure, n_samples, max_lag, true, h_out, ld, true); });
 }
 
 int storm_hip_lag_dosage_ldscore_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int stat, uint64_t n_samples,

@@ -275,25 +275,24 @@ static inline uint64_t ranges_word_pairs(const std::vector<RowRange>& ranges, ui
     }
     return pairs * words / (shard_count ? shard_count : 1);
 }
+// The per-pair launchers below only queue; pair_matrix_out (further down) is where a synchronous call waits.
 int launch_pairw_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int op, uint32_t* d_out,
-                        uint64_t ld, uint64_t band_row0 = 0, uint64_t band_rows = ~0ull,
-                        bool sync = true);
+                        uint64_t ld, uint64_t band_row0 = 0, uint64_t band_rows = ~0ull);
 // the same for the pairs within max_lag rows of each other, in the lag layout (n x L instead of n x n): always K2h
 int launch_pairw_lag_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int op, uint64_t max_lag, uint64_t band_row0,
-                            uint64_t band_rows, uint32_t* d_out, uint64_t ld, bool sync);
+                            uint64_t band_rows, uint32_t* d_out, uint64_t ld);
 // the dot products of rows of 2-bit values, upper triangle (K2h in its dosage form; storm_hip_dosage.hip finishes them)
-int launch_pairw_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint32_t* d_out, uint64_t ld, bool sync);
+int launch_pairw_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint32_t* d_out, uint64_t ld);
 // ... for the pairs within max_lag rows of each other, in the lag layout (K2h in its lag and dosage form)
 int launch_pairw_lag_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint64_t max_lag, uint64_t band_row0,
-                                   uint64_t band_rows, uint32_t* d_out, uint64_t ld, bool sync);
+                                   uint64_t band_rows, uint32_t* d_out, uint64_t ld);
 // the rectangle of two such matrices: every row of A against every row of B (K2h in its dosage form, rectangle)
 int launch_square_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, uint32_t* d_out,
-                                uint64_t ld, bool sync);
+                                uint64_t ld);
 int launch_square_mfma(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
                        const storm_hip_matrix_s* b, uint64_t* d_total);
 int launch_square_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
-                         const storm_hip_matrix_s* b, int op, uint32_t* d_out, uint64_t ld,
-                         bool sync = true);   // false: queued only, the caller waits for the stream
+                         const storm_hip_matrix_s* b, int op, uint32_t* d_out, uint64_t ld);
 int launch_row_counts(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint32_t* d_counts);
 // similarity_finish_kernel over a count matrix in device memory, asynchronous (storm_hip_similarity.hip; the checks of
 // storm_hip_similarity_finish_device)
@@ -445,6 +444,40 @@ inline int upload_bytes(storm_hip_ctx_t* ctx, void* d_dst, const void* h_src, si
     Stager stager(ctx);
     if (int rc = stager.init()) return rc;
     return stager.send_run(static_cast<uint8_t*>(d_dst), {{h_src, bytes}});
+}
+
+// the end of a synchronous call: polls for sync_poll_us, then parks in hipStreamSynchronize (storm_hip_mfma.hip)
+hipError_t wait_stream(storm_hip_ctx_t* ctx);
+
+// The one output path of the per-pair matrix calls, whose two forms are one body each: `queued(d, d_ld)` queues the call's
+// kernels for a rows x cols matrix of 32-bit entries at d, pitch d_ld. The device form hands it the caller's matrix; the
+// host form the context's band buffer at pitch cols (cleared first where the kernels leave entries alone: a triangle's
+// i >= j, the lag layout's corner; +0.0f is the same zero bits), which then goes to `out` at pitch ld in one 2-D copy:
+// entries [cols, ld) of the caller's rows are never touched. `what` = "<who>: <the buffer>" names the allocation; a wait
+// that fails reports "<who>: HIP failure" and has the next K2h launch clear its tickets (a launch that died may have left
+// some behind). wait = false: queued only (storm_hip_pairw_matrix_band_begin).
+template <typename Queued>
+static inline int pair_matrix_out(storm_hip_ctx_t* ctx, const char* what, uint64_t rows, uint64_t cols, void* out, uint64_t ld,
+                                  bool host, bool clear, bool wait, Queued&& queued) {
+    STORM_HIP_TRY(hipSetDevice(ctx->device));
+    uint32_t* d = static_cast<uint32_t*>(out);
+    uint32_t* const h_out = host ? d : nullptr;
+    if (h_out) {
+        const size_t need = (size_t)rows * cols * sizeof(uint32_t);
+        if (int rc = ctx->d_band.ensure(need, what)) return rc;
+        if (clear) STORM_HIP_TRY(hipMemsetAsync(ctx->d_band, 0, need, ctx->stream));
+        d = ctx->d_band;
+    }
+    if (int rc = queued(d, h_out ? cols : ld)) return rc;
+    if (h_out)
+        STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(uint32_t), d, cols * sizeof(uint32_t), cols * sizeof(uint32_t), rows,
+                                       hipMemcpyDeviceToHost, ctx->stream));
+    if (wait && wait_stream(ctx) != hipSuccess) {
+        ctx->tickets_dirty = true;
+        set_error("%.*s: HIP failure", (int)strcspn(what, ":"), what);
+        return STORM_HIP_EHIP;
+    }
+    return STORM_HIP_OK;
 }
 
 

@@ -915,9 +915,27 @@ static int launch_lists(storm_hip_ctx_t* ctx, const storm_hip_rowlists_t* l, int
     return STORM_HIP_OK;
 }
 
+// The per-pair matrix of the lists into a caller's device matrix or into HOST memory, whole rows (zeros at i >= j, as
+// storm_hip_pairw_matrix writes them): one body (pair_matrix_out). The host form checks its pitch ahead of its buffer.
+static int rowlists_pairw_matrix(storm_hip_ctx_t* ctx, const storm_hip_rowlists_t* l, int op, uint32_t* out, uint64_t ld, bool host) {
+    if (!ctx || !l || !out) {
+        set_error("rowlists_pairw_matrix: NULL argument");
+        return STORM_HIP_EINVAL;
+    }
+    const uint64_t n = l->n_rows;
+    if (host && ld < n) {
+        set_error("rowlists_pairw_matrix: ld %llu < %llu rows", (unsigned long long)ld, (unsigned long long)n);
+        return STORM_HIP_EINVAL;
+    }
+    return pair_matrix_out(ctx, "rowlists_pairw_matrix: the output", n, n, out, ld, host, true, true,
+                           [&](uint32_t* d, uint64_t d_ld) { return launch_lists(ctx, l, op, d, d_ld); });
+}
+
 int storm_hip_rowlists_pairw_matrix_device(storm_hip_ctx_t* ctx, const storm_hip_rowlists_t* l, int op,
                                            uint32_t* d_out, uint64_t ld) {
-    if (getenv("STORM_HIP_TIMING") != nullptr) {   // the kernel alone by the card's clock beside the host's view of launch + wait
+    return guarded("storm_hip_rowlists_pairw_matrix_device", [&]() -> int {
+        if (getenv("STORM_HIP_TIMING") == nullptr) return rowlists_pairw_matrix(ctx, l, op, d_out, ld, false);
+        // the kernel alone by the card's clock beside the host's view of launch + wait
         hipEvent_t e0 = nullptr, e1 = nullptr;
         STORM_HIP_TRY(hipSetDevice(ctx->device));
         STORM_HIP_TRY(hipEventCreate(&e0));
@@ -934,34 +952,12 @@ int storm_hip_rowlists_pairw_matrix_device(storm_hip_ctx_t* ctx, const storm_hip
         (void)hipEventDestroy(e0);
         (void)hipEventDestroy(e1);
         return STORM_HIP_OK;
-    }
-    if (int rc = launch_lists(ctx, l, op, d_out, ld)) return rc;
-    STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return STORM_HIP_OK;
+    });
 }
 
-// The same into HOST memory, whole rows (zeros at i >= j, as storm_hip_pairw_matrix writes them): the matrix is built in
-// the context's band buffer and copied out.
 int storm_hip_rowlists_pairw_matrix(storm_hip_ctx_t* ctx, const storm_hip_rowlists_t* l, int op, uint32_t* h_out,
                                     uint64_t ld) {
-    if (!ctx || !l || !h_out) {
-        set_error("rowlists_pairw_matrix: NULL argument");
-        return STORM_HIP_EINVAL;
-    }
-    const uint64_t n = l->n_rows;
-    if (ld < n) {
-        set_error("rowlists_pairw_matrix: ld %llu < %llu rows", (unsigned long long)ld, (unsigned long long)n);
-        return STORM_HIP_EINVAL;
-    }
-    STORM_HIP_TRY(hipSetDevice(ctx->device));
-    const size_t need = (size_t)n * n * sizeof(uint32_t);
-    if (int rc = ctx->d_band.ensure(need, "rowlists_pairw_matrix: the output")) return rc;
-    STORM_HIP_TRY(hipMemsetAsync(ctx->d_band, 0, need, ctx->stream));
-    if (int rc = launch_lists(ctx, l, op, ctx->d_band, n)) return rc;
-    STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(uint32_t), ctx->d_band, n * sizeof(uint32_t), n * sizeof(uint32_t), n,
-                                   hipMemcpyDeviceToHost, ctx->stream));
-    STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return STORM_HIP_OK;
+    return guarded("storm_hip_rowlists_pairw_matrix", [&] { return rowlists_pairw_matrix(ctx, l, op, h_out, ld, true); });
 }
 
 uint64_t storm_hip_rowlists_n_elems(const storm_hip_rowlists_t* l) { return l ? l->n_elems : 0; }
@@ -1037,49 +1033,43 @@ int storm_hip_rowlists_square_total(storm_hip_ctx_t* ctx, storm_hip_rowlists_t* 
     });
 }
 
-int storm_hip_rowlists_square_matrix_device(storm_hip_ctx_t* ctx, storm_hip_rowlists_t* la, const storm_hip_rowlists_t* lb,
-                                            int op, uint32_t* d_out, uint64_t ld) {
-    return guarded("storm_hip_rowlists_square_matrix_device", [&]() -> int {
-        if (!d_out) {
-            set_error("rowlists_square_matrix: NULL output");
-            return STORM_HIP_EINVAL;
-        }
-        if (int rc = launch_lists_square(ctx, la, lb, op, d_out, ld)) return rc;
-        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return STORM_HIP_OK;
-    });
+// The rectangle's entries into a caller's device matrix or into HOST memory (pair_matrix_out: the n_A x n_B window is built in
+// the context's band buffer and copied out row by row). Each form refuses in its own words.
+static int rowlists_square_matrix(storm_hip_ctx_t* ctx, storm_hip_rowlists_t* la, const storm_hip_rowlists_t* lb, int op, uint32_t* out,
+                                  uint64_t ld, bool host) {
+    if (host ? (!ctx || !la || !lb || !out) : !out) {
+        set_error(host ? "rowlists_square_matrix: NULL argument" : "rowlists_square_matrix: NULL output");
+        return STORM_HIP_EINVAL;
+    }
+    if (!ctx || !la || !lb) {
+        set_error("rowlists_square: NULL argument");
+        return STORM_HIP_EINVAL;
+    }
+    if (host && ld < lb->n_rows) {
+        set_error("rowlists_square_matrix: ld %llu < %llu rows of B", (unsigned long long)ld, (unsigned long long)lb->n_rows);
+        return STORM_HIP_EINVAL;
+    }
+    return pair_matrix_out(ctx, "rowlists_square_matrix: the output", la->n_rows, lb->n_rows, out, ld, host, false, true,
+                           [&](uint32_t* d, uint64_t d_ld) { return launch_lists_square(ctx, la, lb, op, d, d_ld); });
 }
 
-// ... into HOST memory: the n_A x n_B window is built in the context's band buffer and copied out row by row
+int storm_hip_rowlists_square_matrix_device(storm_hip_ctx_t* ctx, storm_hip_rowlists_t* la, const storm_hip_rowlists_t* lb,
+                                            int op, uint32_t* d_out, uint64_t ld) {
+    return guarded("storm_hip_rowlists_square_matrix_device", [&] { return rowlists_square_matrix(ctx, la, lb, op, d_out, ld, false); });
+}
+
 int storm_hip_rowlists_square_matrix(storm_hip_ctx_t* ctx, storm_hip_rowlists_t* la, const storm_hip_rowlists_t* lb, int op,
                                      uint32_t* h_out, uint64_t ld) {
-    return guarded("storm_hip_rowlists_square_matrix", [&]() -> int {
-        if (!ctx || !la || !lb || !h_out) {
-            set_error("rowlists_square_matrix: NULL argument");
-            return STORM_HIP_EINVAL;
-        }
-        const uint64_t na = la->n_rows, nb = lb->n_rows;
-        if (ld < nb) {
-            set_error("rowlists_square_matrix: ld %llu < %llu rows of B", (unsigned long long)ld, (unsigned long long)nb);
-            return STORM_HIP_EINVAL;
-        }
-        STORM_HIP_TRY(hipSetDevice(ctx->device));
-        const size_t need = (size_t)na * nb * sizeof(uint32_t);
-        if (int rc = ctx->d_band.ensure(need, "rowlists_square_matrix: the output")) return rc;
-        if (int rc = launch_lists_square(ctx, la, lb, op, ctx->d_band, nb)) return rc;
-        STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(uint32_t), ctx->d_band, nb * sizeof(uint32_t), nb * sizeof(uint32_t), na,
-                                       hipMemcpyDeviceToHost, ctx->stream));
-        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return STORM_HIP_OK;
-    });
+    return guarded("storm_hip_rowlists_square_matrix", [&] { return rowlists_square_matrix(ctx, la, lb, op, h_out, ld, true); });
 }
 
 // ---- the similarity forms (storm_hip.h: storm_hip_similarity_finish_device): K5 / K5x with op AND, then
 // similarity_finish_kernel on the same stream with the lists' own row lengths as the rows' counts. lb == nullptr: the
-// triangle of la. h_out: through the context's band buffer (cleared for a triangle: +0.0f at i >= j), one 2-D copy out.
+// triangle of la. host: through the context's band buffer (cleared for a triangle: +0.0f at i >= j), one 2-D copy out
+// (pair_matrix_out).
 static int lists_similarity(storm_hip_ctx_t* ctx, storm_hip_rowlists_t* la, const storm_hip_rowlists_t* lb, int measure,
-                            uint64_t n_bits, float* d_out, float* h_out, uint64_t ld) {
-    if (!ctx || !la || !(d_out || h_out)) {
+                            uint64_t n_bits, float* out, uint64_t ld, bool host) {
+    if (!ctx || !la || !out) {
         set_error("rowlists_similarity: NULL argument");
         return STORM_HIP_EINVAL;
     }
@@ -1094,40 +1084,26 @@ static int lists_similarity(storm_hip_ctx_t* ctx, storm_hip_rowlists_t* la, cons
         return STORM_HIP_EINVAL;
     }
     if (na == 0 || nb == 0) return STORM_HIP_OK;
-    STORM_HIP_TRY(hipSetDevice(ctx->device));
-    uint32_t* d_io = reinterpret_cast<uint32_t*>(d_out);
-    uint64_t d_ld = ld;
-    if (h_out) {
-        const size_t need = (size_t)na * nb * sizeof(uint32_t);
-        if (int rc = ctx->d_band.ensure(need, "rowlists_similarity: the output")) return rc;
-        if (triangle) STORM_HIP_TRY(hipMemsetAsync(ctx->d_band, 0, need, ctx->stream));
-        d_io = ctx->d_band;
-        d_ld = nb;
-    }
-    if (int rc = triangle ? launch_lists(ctx, la, STORM_HIP_OP_AND, d_io, d_ld)
-                          : launch_lists_square(ctx, la, lb, STORM_HIP_OP_AND, d_io, d_ld))
-        return rc;
-    if (int rc = launch_similarity_finish(ctx, d_io, d_ld, na, nb, la->d_rowlen, triangle ? la->d_rowlen : lb->d_rowlen,
-                                          triangle ? 1 : 0, measure, n_bits))
-        return rc;
-    if (h_out)
-        STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(float), d_io, nb * sizeof(uint32_t), nb * sizeof(uint32_t), na,
-                                       hipMemcpyDeviceToHost, ctx->stream));
-    STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return STORM_HIP_OK;
+    return pair_matrix_out(ctx, "rowlists_similarity: the output", na, nb, out, ld, host, triangle, true, [&](uint32_t* d_io, uint64_t d_ld) {
+        if (int rc = triangle ? launch_lists(ctx, la, STORM_HIP_OP_AND, d_io, d_ld)
+                              : launch_lists_square(ctx, la, lb, STORM_HIP_OP_AND, d_io, d_ld))
+            return rc;
+        return launch_similarity_finish(ctx, d_io, d_ld, na, nb, la->d_rowlen, triangle ? la->d_rowlen : lb->d_rowlen, triangle ? 1 : 0,
+                                        measure, n_bits);
+    });
 }
 
 int storm_hip_rowlists_pairw_similarity_device(storm_hip_ctx_t* ctx, const storm_hip_rowlists_t* l, int measure,
                                                uint64_t n_bits, float* d_out, uint64_t ld) {
     return guarded("storm_hip_rowlists_pairw_similarity_device", [&]() -> int {
-        return lists_similarity(ctx, const_cast<storm_hip_rowlists_t*>(l), nullptr, measure, n_bits, d_out, nullptr, ld);
+        return lists_similarity(ctx, const_cast<storm_hip_rowlists_t*>(l), nullptr, measure, n_bits, d_out, ld, false);
     });
 }
 
 int storm_hip_rowlists_pairw_similarity(storm_hip_ctx_t* ctx, const storm_hip_rowlists_t* l, int measure, uint64_t n_bits,
                                         float* h_out, uint64_t ld) {
     return guarded("storm_hip_rowlists_pairw_similarity", [&]() -> int {
-        return lists_similarity(ctx, const_cast<storm_hip_rowlists_t*>(l), nullptr, measure, n_bits, nullptr, h_out, ld);
+        return lists_similarity(ctx, const_cast<storm_hip_rowlists_t*>(l), nullptr, measure, n_bits, h_out, ld, true);
     });
 }
 
@@ -1138,7 +1114,7 @@ int storm_hip_rowlists_square_similarity_device(storm_hip_ctx_t* ctx, storm_hip_
             set_error("rowlists_similarity: NULL argument");
             return STORM_HIP_EINVAL;
         }
-        return lists_similarity(ctx, la, lb, measure, n_bits, d_out, nullptr, ld);
+        return lists_similarity(ctx, la, lb, measure, n_bits, d_out, ld, false);
     });
 }
 
@@ -1149,7 +1125,7 @@ int storm_hip_rowlists_square_similarity(storm_hip_ctx_t* ctx, storm_hip_rowlist
             set_error("rowlists_similarity: NULL argument");
             return STORM_HIP_EINVAL;
         }
-        return lists_similarity(ctx, la, lb, measure, n_bits, nullptr, h_out, ld);
+        return lists_similarity(ctx, la, lb, measure, n_bits, h_out, ld, true);
     });
 }
 

@@ -64,7 +64,7 @@ __device__ unsigned long long g_clock_probe[4];
 // The end of a synchronous call whose kernels have just been queued: hipStreamSynchronize parks the thread and is woken
 // by an interrupt (5 - 8 us of a call that runs 20 - 40); a few hundred hipStreamQuery polls see the end of a short
 // launch sooner. Option sync_poll_us: how long to poll before parking (0: park at once).
-static hipError_t wait_stream(storm_hip_ctx_t* ctx) {
+hipError_t wait_stream(storm_hip_ctx_t* ctx) {
     if (ctx->sync_poll_us > 0) {
         const auto t0 = std::chrono::steady_clock::now();
         for (uint32_t spin = 0;; ++spin) {
@@ -2061,8 +2061,7 @@ static int ensure_matrix_tiles(storm_hip_ctx_t* ctx, MatrixTilesRequest&& rq, Ma
 // rounds and a nearly empty last round costs a whole one (820 tiles on 256 CUs at the headline shape: 3.2 -> 4). The
 // tiles of the last round are therefore cut along k into as many parts as fill the CUs; the parts add into a cleared
 // window (or, option k2_matrix_parts, write windows of their own that reduce_parts_kernel adds up).
-static int run_matrix_tiles(storm_hip_ctx_t* ctx, const MatrixPlan& plan, const TileOperands& ops, bool bits, const OutWindow& w,
-                            bool sync) {
+static int run_matrix_tiles(storm_hip_ctx_t* ctx, const MatrixPlan& plan, const TileOperands& ops, bool bits, const OutWindow& w) {
     if (!bits) memset(ctx->x4_key, 0, sizeof(ctx->x4_key));  // callers rebuilt the shadow in the tile layout
     const MfmaItem* d_items = static_cast<const MfmaItem*>(ctx->d_items.d);
     // [r5] option k2_matrix_parts: the k-parts of the tile kernels that ship write their own windows and a second kernel
@@ -2111,9 +2110,7 @@ static int run_matrix_tiles(storm_hip_ctx_t* ctx, const MatrixPlan& plan, const 
     if (d_parts)
         hipLaunchKernelGGL(reduce_parts_kernel, dim3(n_split, kTile / kReduceBand), dim3(256), 0, ctx->stream, d_items, plan.n_full,
                            plan.n_items, d_parts, w);
-    if (hipGetLastError() != hipSuccess) return STORM_HIP_EHIP;
-    if (sync && wait_stream(ctx) != hipSuccess) return STORM_HIP_EHIP;
-    return STORM_HIP_OK;
+    return hipGetLastError() == hipSuccess ? STORM_HIP_OK : STORM_HIP_EHIP;
 }
 
 // ---- what the materialised-output entry points share ----
@@ -2165,8 +2162,7 @@ static bool choose_tile128(const storm_hip_ctx_t* ctx, uint64_t tiles256, uint64
 // request while the same call repeats), uploads it and launches tile128_kernel in the window's form over total_stages
 // 128-bit stages of k. value_bits = 2 (any form, no row counts): the rows hold 2-bit values and the kernel writes their
 // dot products (tile128_kernel<false, 2>, or <true, 2> in the lag form); the list is planned with a chunk's weight of 9 x 256.
-static int run_tile128(storm_hip_ctx_t* ctx, uint32_t total_stages, const TileOperands& ops, const OutWindow& w, bool sync,
-                       uint32_t value_bits) {
+static int run_tile128(storm_hip_ctx_t* ctx, uint32_t total_stages, const TileOperands& ops, const OutWindow& w, uint32_t value_bits) {
     const uint32_t lag = w.form == OutForm::Lag ? w.lag : 0u;
     const uint32_t ia0 = w.i_lo / kThTile, ia1 = (w.n_rows + kThTile - 1) / kThTile;
     const uint32_t jb0 = w.j_base / kThTile, jb1 = (w.col_end() + kThTile - 1) / kThTile;
@@ -2219,18 +2215,14 @@ static int run_tile128(storm_hip_ctx_t* ctx, uint32_t total_stages, const TileOp
         ctx->tickets_dirty = true;
         return STORM_HIP_EHIP;
     }
-    if (sync && wait_stream(ctx) != hipSuccess) {
-        ctx->tickets_dirty = true;   // (a launch that died may have left tickets behind)
-        return STORM_HIP_EHIP;
-    }
-    return STORM_HIP_OK;
+    return STORM_HIP_OK;   // (a failed wait marks the tickets as well: pair_matrix_out, storm_hip_internal.h)
 }
 
 // Materialised upper triangle: out[i * ld + j] = popcount(row_i & row_j) for i < j < n_rows
 // (device pointer, uint32). One tile item per (I <= J) spanning all of k; f32 accumulation is
 // exact for rows of fewer than 2^24 bits.
 int launch_pairw_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int op, uint32_t* d_out,
-                        uint64_t ld, uint64_t band_row0, uint64_t band_rows, bool sync) {
+                        uint64_t ld, uint64_t band_row0, uint64_t band_rows) {
     // band: only rows [band_row0, band_row0 + band_rows) of the triangle, written from output row 0
     const uint64_t band_end = std::min<uint64_t>(m->n_rows, band_row0 + band_rows);
     if (band_row0 >= band_end) return STORM_HIP_OK;
@@ -2304,108 +2296,91 @@ int launch_pairw_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int o
                                reinterpret_cast<uint4*>(ctx->d_x4.d), kExpandAll, 2u, pitch / 16);
         }
         const TileOperands ops = bits ? operands_of(m->d, pitch, m->n_rows_pad) : operands_of(ctx->d_x4.d, pitch, n_rows4);
-        rc = k2h ? run_tile128(ctx, total_stages, ops, w, sync, 1u) : run_matrix_tiles(ctx, plan, ops, bits, w, sync);
+        rc = k2h ? run_tile128(ctx, total_stages, ops, w, 1u) : run_matrix_tiles(ctx, plan, ops, bits, w);
     }
     if (rc == STORM_HIP_EHIP) set_error("pairw_matrix: HIP failure");
     return rc;
 }
 
+// ---- the calls that have K2h alone: the lag layout and the rows of 2-bit values (the other output kernels know neither) ----
+// the pairs within L rows of each other among the rows [0, r) of n: row i has min(L, n - 1 - i) of them (L = n - 1: all pairs)
+static uint64_t pairs_below(uint64_t r, uint64_t n, uint64_t L) {
+    const uint64_t full = std::min(r, n - L);            // rows with all L partners
+    const uint64_t rest = r - full;                      // rows n - L + t, t < rest: L - t partners
+    return full * L + rest * L - rest * (rest + 1) / 2;
+}
+
+// tile128_kernel over one matrix (b null) or over [A ; B] (B's virtual rows count on from w.j_base: A's rows padded to 256;
+// equal n_words and strides) into the finished window w, under the entry point's name: the limits, what the call ran
+// (k2_tile_shape_used: 6 = K2h on bits, 7 = on 2-bit values, value_bits 2), the report of the window's pairs, the rows'
+// counts for `op` (one matrix; the dot products are AND: none), the launch. Queued.
+static int launch_tile128(storm_hip_ctx_t* ctx, const char* entry, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, OutWindow w,
+                          uint32_t value_bits, int op) {
+    const uint64_t pitch = a->stride_words * 8, rows_a = b ? w.j_base : 0;
+    if (int rc = check_tile_limits(entry, pitch, kThTile, (rows_a + (b ? b : a)->n_rows + kThTile - 1) / kThTile, true)) return rc;
+    const uint64_t L = w.form == OutForm::Lag ? w.lag : w.n_cols - 1;   // (a triangle: every pair)
+    const uint64_t pairs = w.rect() ? (uint64_t)w.n_rows * w.j_count : pairs_below(w.n_rows, w.n_cols, L) - pairs_below(w.i_lo, w.n_cols, L);
+    ctx->k2_tile_shape_eff = value_bits == 2u ? 7 : 6;
+    report_tiles_out(ctx, pairs * a->n_words);
+    uint32_t* d_counts = nullptr;
+    int rc = op_row_counts(ctx, op, a, &d_counts);
+    w.row_counts = d_counts;
+    const TileOperands ops = b ? operands_of(a->d, b->d, pitch, rows_a, std::min<uint64_t>(a->n_rows_pad, rows_a),
+                                             std::min<uint64_t>(b->n_rows_pad, (b->n_rows + kThTile - 1) / kThTile * kThTile))
+                               : operands_of(a->d, pitch, a->n_rows_pad);
+    if (rc == STORM_HIP_OK) rc = run_tile128(ctx, (a->n_words + 7u) / 8u * 4u, ops, w, value_bits);
+    if (rc == STORM_HIP_EHIP) set_error("%s: HIP failure", entry);
+    return rc;
+}
+
 // The triangle's pairs within max_lag rows of each other, in the lag layout: out[(i - band_row0) * ld + (j - i - 1)] =
 // popcount(row_i OP row_j) for band_row0 <= i < band_row0 + band_rows, i < j < n_rows, j - i <= L = min(max_lag, n_rows - 1)
-// (device pointer, uint32, ld >= L). Always K2h (tile128_kernel<true>): the tile list follows the diagonal, whatever
-// k2_tile_shape says; nothing outside the layout is written.
-int launch_pairw_lag_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int op, uint64_t max_lag, uint64_t band_row0,
-                            uint64_t band_rows, uint32_t* d_out, uint64_t ld, bool sync) {
+// (device pointer, uint32, ld >= L); value_bits 2: sum_s v_i[s] v_j[s] of rows of 2-bit values instead. The tile list follows
+// the diagonal; nothing outside the layout is written.
+static int launch_lag(storm_hip_ctx_t* ctx, const char* entry, const storm_hip_matrix_s* m, int op, uint64_t max_lag, uint64_t band_row0,
+                      uint64_t band_rows, uint32_t* d_out, uint64_t ld, uint32_t value_bits) {
     const uint64_t n = m->n_rows;
     const uint64_t band_end = std::min<uint64_t>(n, band_row0 + std::min<uint64_t>(band_rows, n));
     if (n < 2 || band_row0 >= band_end || max_lag == 0) return STORM_HIP_OK;
-    const uint64_t L = std::min<uint64_t>(max_lag, n - 1);
-    const uint64_t pitch = m->stride_words * 8;
-    if (int rc = check_tile_limits("pairw_lag_matrix", pitch, kThTile, (n + kThTile - 1) / kThTile, true)) return rc;
-    // pairs (i, j) of the band within the lag: row i has min(L, n - 1 - i) of them
-    auto pairs_below = [&](uint64_t r) {   // ... of the rows [0, r)
-        const uint64_t full = std::min(r, n - L);            // rows with all L partners
-        const uint64_t rest = r - full;                      // rows n - L + t, t < rest: L - t partners
-        return full * L + rest * L - rest * (rest + 1) / 2;
-    };
-    ctx->k2_tile_shape_eff = 6;
-    report_tiles_out(ctx, (pairs_below(band_end) - pairs_below(band_row0)) * m->n_words);
-    uint32_t* d_counts = nullptr;
-    int rc = op_row_counts(ctx, op, m, &d_counts);
-    if (rc == STORM_HIP_OK)
-        rc = run_tile128(ctx, (m->n_words + 7u) / 8u * 4u, operands_of(m->d, pitch, m->n_rows_pad),
-                         lag_window(d_out, ld, band_row0, band_end, n, L, d_counts, op), sync, 1u);
-    if (rc == STORM_HIP_EHIP) set_error("pairw_lag_matrix: HIP failure");
-    return rc;
+    return launch_tile128(ctx, entry, m, nullptr, lag_window(d_out, ld, band_row0, band_end, n, std::min<uint64_t>(max_lag, n - 1), nullptr, op),
+                          value_bits, op);
+}
+int launch_pairw_lag_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int op, uint64_t max_lag, uint64_t band_row0,
+                            uint64_t band_rows, uint32_t* d_out, uint64_t ld) {
+    return launch_lag(ctx, "pairw_lag_matrix", m, op, max_lag, band_row0, band_rows, d_out, ld, 1u);
+}
+int launch_pairw_lag_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint64_t max_lag, uint64_t band_row0,
+                                   uint64_t band_rows, uint32_t* d_out, uint64_t ld) {
+    return launch_lag(ctx, "pairw_lag_dosage_matrix", m, STORM_HIP_OP_AND, max_lag, band_row0, band_rows, d_out, ld, 2u);
 }
 
 // The dot products of rows of 2-bit values (storm_hip_pairw_dosage_matrix_device): out[i * ld + j] = sum_s v_i[s] v_j[s] for
-// i < j < n_rows, value s of a row in bits 2 (s % 32), 2 (s % 32) + 1 of word s / 32 (device pointer, uint32). Always K2h in
-// its dosage form (tile128_kernel<false, 2>), whatever k2_tile_shape says: the other output kernels know bits only.
-int launch_pairw_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint32_t* d_out, uint64_t ld, bool sync) {
+// i < j < n_rows, value s of a row in bits 2 (s % 32), 2 (s % 32) + 1 of word s / 32 (device pointer, uint32).
+int launch_pairw_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint32_t* d_out, uint64_t ld) {
     const uint64_t n = m->n_rows;
     if (n < 2) return STORM_HIP_OK;
-    const uint64_t pitch = m->stride_words * 8;
-    if (int rc = check_tile_limits("pairw_dosage_matrix", pitch, kThTile, (n + kThTile - 1) / kThTile, true)) return rc;
-    ctx->k2_tile_shape_eff = 7;   // (option k2_tile_shape_used: 6 = K2h on bits, 7 = K2h on 2-bit values)
-    report_tiles_out(ctx, n * (n - 1) / 2 * m->n_words);
-    const int rc = run_tile128(ctx, (m->n_words + 7u) / 8u * 4u, operands_of(m->d, pitch, m->n_rows_pad),
-                               triangle_window(d_out, ld, 0, n, n, nullptr, STORM_HIP_OP_AND), sync, 2u);
-    if (rc == STORM_HIP_EHIP) set_error("pairw_dosage_matrix: HIP failure");
-    return rc;
-}
-
-// The dot products of rows of 2-bit values for the pairs within max_lag rows of each other, in the lag layout
-// (storm_hip_pairw_lag_dosage_matrix_device): out[(i - band_row0) * ld + (j - i - 1)] = sum_s v_i[s] v_j[s] for the band's
-// rows i, i < j < n_rows, j - i <= L = min(max_lag, n_rows - 1). launch_pairw_lag_matrix on 2-bit values: K2h in its lag
-// and dosage form (tile128_kernel<true, 2>), no row counts.
-int launch_pairw_lag_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint64_t max_lag, uint64_t band_row0,
-                                   uint64_t band_rows, uint32_t* d_out, uint64_t ld, bool sync) {
-    const uint64_t n = m->n_rows;
-    const uint64_t band_end = std::min<uint64_t>(n, band_row0 + std::min<uint64_t>(band_rows, n));
-    if (n < 2 || band_row0 >= band_end || max_lag == 0) return STORM_HIP_OK;
-    const uint64_t L = std::min<uint64_t>(max_lag, n - 1);
-    const uint64_t pitch = m->stride_words * 8;
-    if (int rc = check_tile_limits("pairw_lag_dosage_matrix", pitch, kThTile, (n + kThTile - 1) / kThTile, true)) return rc;
-    auto pairs_below = [&](uint64_t r) {   // the pairs within the lag of the rows [0, r): launch_pairw_lag_matrix's count
-        const uint64_t full = std::min(r, n - L), rest = r - full;
-        return full * L + rest * L - rest * (rest + 1) / 2;
-    };
-    ctx->k2_tile_shape_eff = 7;
-    report_tiles_out(ctx, (pairs_below(band_end) - pairs_below(band_row0)) * m->n_words);
-    const int rc = run_tile128(ctx, (m->n_words + 7u) / 8u * 4u, operands_of(m->d, pitch, m->n_rows_pad),
-                               lag_window(d_out, ld, band_row0, band_end, n, L, nullptr, STORM_HIP_OP_AND), sync, 2u);
-    if (rc == STORM_HIP_EHIP) set_error("pairw_lag_dosage_matrix: HIP failure");
-    return rc;
+    return launch_tile128(ctx, "pairw_dosage_matrix", m, nullptr, triangle_window(d_out, ld, 0, n, n, nullptr, STORM_HIP_OP_AND), 2u,
+                          STORM_HIP_OP_AND);
 }
 
 // The rectangle of two matrices of rows of 2-bit values (storm_hip_square_dosage_matrix_device): out[i * ld + j] =
 // sum_s a_i[s] b_j[s] for every row i of A and j of B (device pointer, uint32, ld >= b->n_rows; equal n_words and strides).
-// launch_square_matrix's K2h branch in the dosage form: B's virtual rows count on behind A's rows padded to 256.
 int launch_square_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, uint32_t* d_out,
-                                uint64_t ld, bool sync) {
+                                uint64_t ld) {
     if (a->n_rows == 0 || b->n_rows == 0) return STORM_HIP_OK;
     if (a->stride_words != b->stride_words || a->n_words != b->n_words) {
         set_error("square_dosage_matrix: rows of %u and %u words", a->n_words, b->n_words);
         return STORM_HIP_EINVAL;
     }
-    const uint64_t pitch = a->stride_words * 8;
     const uint64_t rows_a = (a->n_rows + kTile - 1) / kTile * kTile;
-    if (int rc = check_tile_limits("square_dosage_matrix", pitch, kThTile, (rows_a + b->n_rows + kThTile - 1) / kThTile, true)) return rc;
-    ctx->k2_tile_shape_eff = 7;
-    report_tiles_out(ctx, a->n_rows * b->n_rows * a->n_words);
-    const TileOperands ops = operands_of(a->d, b->d, pitch, rows_a, std::min<uint64_t>(a->n_rows_pad, rows_a),
-                                         std::min<uint64_t>(b->n_rows_pad, (b->n_rows + kThTile - 1) / kThTile * kThTile));
-    const int rc = run_tile128(ctx, (a->n_words + 7u) / 8u * 4u, ops,
-                               rectangle_window(d_out, ld, a->n_rows, rows_a, b->n_rows, nullptr, STORM_HIP_OP_AND), sync, 2u);
-    if (rc == STORM_HIP_EHIP) set_error("square_dosage_matrix: HIP failure");
-    return rc;
+    return launch_tile128(ctx, "square_dosage_matrix", a, b, rectangle_window(d_out, ld, a->n_rows, rows_a, b->n_rows, nullptr, STORM_HIP_OP_AND),
+                          2u, STORM_HIP_OP_AND);
 }
 
 // Materialised rectangle: out[i * ld + j] = popcount(a_i OP b_j) for every row i of A and j of B
 // (device pointer, uint32, ld >= b->n_rows): the tile kernel over the virtual rows [A ; B] (FP4 forms: a shadow holding them).
 int launch_square_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
-                         const storm_hip_matrix_s* b, int op, uint32_t* d_out, uint64_t ld, bool sync) {
+                         const storm_hip_matrix_s* b, int op, uint32_t* d_out, uint64_t ld) {
     if (a->n_rows == 0 || b->n_rows == 0) return STORM_HIP_OK;
     ctx->k2_tile_shape_eff = (ctx->k2_tile_shape && ctx->k2_tile_shape != 6) ? ctx->k2_tile_shape : ((a->sparse_origin && b->sparse_origin) ? 2 : 5);
     const uint64_t stride_words = a->stride_words;
@@ -2447,7 +2422,7 @@ int launch_square_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
         const TileOperands ops = bits ? operands_of(a->d, b->d, pitch, rows_a, std::min<uint64_t>(a->n_rows_pad, rows_a),
                                                     std::min<uint64_t>(b->n_rows_pad, rows_b))
                                       : operands_of(ctx->d_x4.d, pitch, rows_a + rows_b);
-        rc = k2h ? run_tile128(ctx, total_stages, ops, w, sync, 1u) : run_matrix_tiles(ctx, plan, ops, bits, w, sync);
+        rc = k2h ? run_tile128(ctx, total_stages, ops, w, 1u) : run_matrix_tiles(ctx, plan, ops, bits, w);
     }
     if (rc == STORM_HIP_EHIP) set_error("square_matrix: HIP failure");
     return rc;

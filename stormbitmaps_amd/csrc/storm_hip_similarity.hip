@@ -221,7 +221,7 @@ static int cross_counts(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a, const
         set_error("cross_dense_similarity: row widths differ");
         return STORM_HIP_EINVAL;
     }
-    if (int rc = launch_square_matrix(ctx, a, b, STORM_HIP_OP_AND, d_out, ld, false)) return rc;
+    if (int rc = launch_square_matrix(ctx, a, b, STORM_HIP_OP_AND, d_out, ld)) return rc;
     ctx->pass_report[0] = STORM_HIP_RAN_TILES_OUT;
     ctx->pass_report[1] = a->n_rows * b->n_rows * a->n_words;
     ctx->pass_report[2] = ctx->pass_report[3] = 0;
@@ -235,6 +235,98 @@ static int check_measure(int measure, uint64_t n_bits) {
         return STORM_HIP_EINVAL;
     }
     return STORM_HIP_OK;
+}
+
+// ---- the per-pair matrix calls: one body for the device form and the host form of each (pair_matrix_out, storm_hip_internal.h) ----
+// The triangle, cleared in the band buffer (entries i >= j). The device form returns below two rows without touching its
+// matrix; the host form returns without rows, and for a single row writes its one zero (and the report of no pairs).
+static int pairw_similarity(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int measure, uint64_t n_bits, float* out, uint64_t ld,
+                            bool host) {
+    if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+    if (!m || !out || ld < m->n_rows) {
+        set_error("pairw_similarity: NULL argument or leading dimension < rows");
+        return STORM_HIP_EINVAL;
+    }
+    if (int rc = check_measure(measure, n_bits)) return rc;
+    const uint64_t n = m->n_rows;
+    if (host ? n == 0 : n < 2) return STORM_HIP_OK;
+    return pair_matrix_out(ctx, "pairw_similarity: the output", n, n, out, ld, host, true, true, [&](uint32_t* d, uint64_t d_ld) {
+        if (int rc = launch_pairw_matrix(ctx, m, STORM_HIP_OP_AND, d, d_ld)) return rc;
+        return n >= 2 ? finish_dense(ctx, m, m, d, d_ld, 1, measure, n_bits) : STORM_HIP_OK;
+    });
+}
+
+// (a rectangle: every entry is written, nothing to clear)
+static int cross_dense_similarity(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, int measure,
+                                  uint64_t n_bits, float* out, uint64_t ld, bool host) {
+    if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+    if (!a || !b || !out || ld < b->n_rows) {
+        set_error("cross_dense_similarity: NULL argument or ld < rows of B");
+        return STORM_HIP_EINVAL;
+    }
+    if (int rc = check_measure(measure, n_bits)) return rc;
+    if (a->n_rows == 0 || b->n_rows == 0) return STORM_HIP_OK;
+    return pair_matrix_out(ctx, "cross_dense_similarity: the output", a->n_rows, b->n_rows, out, ld, host, false, true,
+                           [&](uint32_t* d, uint64_t d_ld) {
+                               if (int rc = cross_counts(ctx, a, b, d, d_ld)) return rc;
+                               return finish_dense(ctx, a, b, d, d_ld, 0, measure, n_bits);
+                           });
+}
+
+// ---- the lag layout (storm_hip.h): row i against the next L = min(max_lag, rows - 1) rows, an n x L matrix, cleared in the
+// band buffer (the lower-right corner); both forms return below two rows ----
+// what the lag calls refuse alike; *lag = L (0 for an empty matrix)
+static int check_lag(const char* who, const storm_hip_matrix_s* m, const void* out, uint64_t max_lag, uint64_t ld, uint64_t* lag) {
+    if (!m || !out || max_lag == 0) {
+        set_error("%s: NULL argument or max_lag 0", who);
+        return STORM_HIP_EINVAL;
+    }
+    *lag = m->n_rows ? std::min(max_lag, m->n_rows - 1) : 0;
+    if (ld < *lag) {
+        set_error("%s: leading dimension %llu < min(max_lag, rows - 1) = %llu", who, (unsigned long long)ld, (unsigned long long)*lag);
+        return STORM_HIP_EINVAL;
+    }
+    return STORM_HIP_OK;
+}
+
+// the counts alone: the device form takes a band of rows; the host form every row, and names the op it refuses
+static int pairw_lag_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int op, uint64_t max_lag, uint64_t row0,
+                            uint64_t n_band_rows, uint32_t* out, uint64_t ld, bool host) {
+    if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+    uint64_t lag = 0;
+    if (int rc = check_lag("pairw_lag_matrix", m, out, max_lag, ld, &lag)) return rc;
+    if (n_band_rows == ~0ull && row0 <= m->n_rows) n_band_rows = m->n_rows - row0;
+    if (op < STORM_HIP_OP_AND || op > STORM_HIP_OP_XOR || row0 > m->n_rows || n_band_rows > m->n_rows - row0) {
+        if (host) set_error("pairw_lag_matrix: unknown op %d", op);
+        else set_error("pairw_lag_matrix: unknown op or a band outside the rows");
+        return STORM_HIP_EINVAL;
+    }
+    if (m->n_rows < 2 || n_band_rows == 0) return STORM_HIP_OK;
+    return pair_matrix_out(ctx, "pairw_lag_matrix: the output", n_band_rows, lag, out, ld, host, true, true,
+                           [&](uint32_t* d, uint64_t d_ld) {
+                               return launch_pairw_lag_matrix(ctx, m, op, max_lag, row0, n_band_rows, d, d_ld);
+                           });
+}
+
+// counts in the lag layout at d_io (pitch ld), queued; then the rows' counts and the finish, queued too
+static int lag_similarity_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int measure, uint64_t n_bits, uint64_t max_lag,
+                                 uint32_t* d_io, uint64_t ld) {
+    const uint64_t n = m->n_rows;
+    if (int rc = launch_pairw_lag_matrix(ctx, m, STORM_HIP_OP_AND, max_lag, 0, n, d_io, ld)) return rc;
+    if (int rc = ctx->d_counts.ensure(n * sizeof(uint32_t), "similarity: the row-count scratch")) return rc;
+    if (int rc = counts_of(ctx, m, 0)) return rc;
+    return launch_similarity_finish_lag(ctx, d_io, ld, n, 0, n, max_lag, ctx->d_counts.d, measure, n_bits);
+}
+
+static int pairw_lag_similarity(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, int measure, uint64_t n_bits, uint64_t max_lag,
+                                float* out, uint64_t ld, bool host) {
+    if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+    uint64_t lag = 0;
+    if (int rc = check_lag("pairw_lag_similarity", m, out, max_lag, ld, &lag)) return rc;
+    if (int rc = check_measure(measure, n_bits)) return rc;
+    if (m->n_rows < 2) return STORM_HIP_OK;
+    return pair_matrix_out(ctx, "pairw_lag_similarity: the output", m->n_rows, lag, out, ld, host, true, true,
+                           [&](uint32_t* d, uint64_t d_ld) { return lag_similarity_queued(ctx, m, measure, n_bits, max_lag, d, d_ld); });
 }
 
 }  // namespace storm
@@ -263,101 +355,23 @@ int storm_hip_similarity_finish_device(storm_hip_ctx_t* ctx, void* d_io, uint64_
 
 int storm_hip_pairw_similarity_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_bits,
                                       float* d_out, uint64_t ld) {
-    return guarded("storm_hip_pairw_similarity_device", [&]() -> int {
-        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-        if (!m || !d_out || ld < m->n_rows) {
-            set_error("pairw_similarity: NULL argument or leading dimension < rows");
-            return STORM_HIP_EINVAL;
-        }
-        if (int rc = check_measure(measure, n_bits)) return rc;
-        if (m->n_rows < 2) return STORM_HIP_OK;
-        STORM_HIP_TRY(hipSetDevice(ctx->device));
-        if (int rc = launch_pairw_matrix(ctx, m, STORM_HIP_OP_AND, reinterpret_cast<uint32_t*>(d_out), ld, 0, ~0ull, false)) return rc;
-        if (int rc = finish_dense(ctx, m, m, d_out, ld, 1, measure, n_bits)) return rc;
-        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return STORM_HIP_OK;
-    });
+    return guarded("storm_hip_pairw_similarity_device", [&] { return pairw_similarity(ctx, m, measure, n_bits, d_out, ld, false); });
 }
 
 int storm_hip_pairw_similarity(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_bits, float* h_out,
                                uint64_t ld) {
-    return guarded("storm_hip_pairw_similarity", [&]() -> int {
-        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-        if (!m || !h_out || ld < m->n_rows) {
-            set_error("pairw_similarity: NULL argument or leading dimension < rows");
-            return STORM_HIP_EINVAL;
-        }
-        if (int rc = check_measure(measure, n_bits)) return rc;
-        const uint64_t n = m->n_rows;
-        if (n == 0) return STORM_HIP_OK;
-        STORM_HIP_TRY(hipSetDevice(ctx->device));
-        const size_t need = (size_t)n * n * sizeof(uint32_t);
-        if (int rc = ctx->d_band.ensure(need, "pairw_similarity: the output")) return rc;
-        STORM_HIP_TRY(hipMemsetAsync(ctx->d_band, 0, need, ctx->stream));   // (entries i >= j: +0.0f is the same zero bits)
-        if (int rc = launch_pairw_matrix(ctx, m, STORM_HIP_OP_AND, ctx->d_band, n, 0, ~0ull, false)) return rc;
-        if (n >= 2)
-            if (int rc = finish_dense(ctx, m, m, ctx->d_band, n, 1, measure, n_bits)) return rc;
-        STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(float), ctx->d_band, n * sizeof(uint32_t), n * sizeof(uint32_t), n,
-                                       hipMemcpyDeviceToHost, ctx->stream));
-        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return STORM_HIP_OK;
-    });
-}
-
-// ---- the lag layout (storm_hip.h): row i against the next L = min(max_lag, rows - 1) rows, an n x L matrix ----
-// what the lag calls refuse alike; *lag = L (0 for an empty matrix)
-static int check_lag(const char* who, const storm_hip_matrix_t* m, const void* out, uint64_t max_lag, uint64_t ld, uint64_t* lag) {
-    if (!m || !out || max_lag == 0) {
-        set_error("%s: NULL argument or max_lag 0", who);
-        return STORM_HIP_EINVAL;
-    }
-    *lag = m->n_rows ? std::min(max_lag, m->n_rows - 1) : 0;
-    if (ld < *lag) {
-        set_error("%s: leading dimension %llu < min(max_lag, rows - 1) = %llu", who, (unsigned long long)ld, (unsigned long long)*lag);
-        return STORM_HIP_EINVAL;
-    }
-    return STORM_HIP_OK;
+    return guarded("storm_hip_pairw_similarity", [&] { return pairw_similarity(ctx, m, measure, n_bits, h_out, ld, true); });
 }
 
 int storm_hip_pairw_lag_matrix_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int op, uint64_t max_lag, uint64_t row0,
                                       uint64_t n_band_rows, uint32_t* d_out, uint64_t ld) {
-    return guarded("storm_hip_pairw_lag_matrix_device", [&]() -> int {
-        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-        uint64_t lag = 0;
-        if (int rc = check_lag("pairw_lag_matrix", m, d_out, max_lag, ld, &lag)) return rc;
-        if (n_band_rows == ~0ull && row0 <= m->n_rows) n_band_rows = m->n_rows - row0;
-        if (op < STORM_HIP_OP_AND || op > STORM_HIP_OP_XOR || row0 > m->n_rows || n_band_rows > m->n_rows - row0) {
-            set_error("pairw_lag_matrix: unknown op or a band outside the rows");
-            return STORM_HIP_EINVAL;
-        }
-        if (m->n_rows < 2 || n_band_rows == 0) return STORM_HIP_OK;
-        STORM_HIP_TRY(hipSetDevice(ctx->device));
-        return launch_pairw_lag_matrix(ctx, m, op, max_lag, row0, n_band_rows, d_out, ld, true);
-    });
+    return guarded("storm_hip_pairw_lag_matrix_device",
+                   [&] { return pairw_lag_matrix(ctx, m, op, max_lag, row0, n_band_rows, d_out, ld, false); });
 }
 
 int storm_hip_pairw_lag_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int op, uint64_t max_lag, uint32_t* h_out,
                                uint64_t ld) {
-    return guarded("storm_hip_pairw_lag_matrix", [&]() -> int {
-        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-        uint64_t lag = 0;
-        if (int rc = check_lag("pairw_lag_matrix", m, h_out, max_lag, ld, &lag)) return rc;
-        if (op < STORM_HIP_OP_AND || op > STORM_HIP_OP_XOR) {
-            set_error("pairw_lag_matrix: unknown op %d", op);
-            return STORM_HIP_EINVAL;
-        }
-        const uint64_t n = m->n_rows;
-        if (n < 2) return STORM_HIP_OK;
-        STORM_HIP_TRY(hipSetDevice(ctx->device));
-        const size_t need = (size_t)n * lag * sizeof(uint32_t);
-        if (int rc = ctx->d_band.ensure(need, "pairw_lag_matrix: the output")) return rc;
-        STORM_HIP_TRY(hipMemsetAsync(ctx->d_band, 0, need, ctx->stream));   // (the lower-right corner)
-        if (int rc = launch_pairw_lag_matrix(ctx, m, op, max_lag, 0, n, ctx->d_band, lag, false)) return rc;
-        STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(uint32_t), ctx->d_band, lag * sizeof(uint32_t), lag * sizeof(uint32_t), n,
-                                       hipMemcpyDeviceToHost, ctx->stream));
-        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return STORM_HIP_OK;
-    });
+    return guarded("storm_hip_pairw_lag_matrix", [&] { return pairw_lag_matrix(ctx, m, op, max_lag, 0, ~0ull, h_out, ld, true); });
 }
 
 int storm_hip_similarity_finish_lag_device(storm_hip_ctx_t* ctx, void* d_io, uint64_t ld, uint64_t n_rows, uint64_t row0,
@@ -376,90 +390,28 @@ int storm_hip_similarity_finish_lag_device(storm_hip_ctx_t* ctx, void* d_io, uin
     });
 }
 
-// counts in the lag layout at d_io (pitch ld), queued; then the rows' counts and the finish, queued too
-static int lag_similarity_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_bits, uint64_t max_lag,
-                                 uint32_t* d_io, uint64_t ld) {
-    const uint64_t n = m->n_rows;
-    if (int rc = launch_pairw_lag_matrix(ctx, m, STORM_HIP_OP_AND, max_lag, 0, n, d_io, ld, false)) return rc;
-    if (int rc = ctx->d_counts.ensure(n * sizeof(uint32_t), "similarity: the row-count scratch")) return rc;
-    if (int rc = counts_of(ctx, m, 0)) return rc;
-    return launch_similarity_finish_lag(ctx, d_io, ld, n, 0, n, max_lag, ctx->d_counts.d, measure, n_bits);
-}
-
 int storm_hip_pairw_lag_similarity_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_bits,
                                           uint64_t max_lag, float* d_out, uint64_t ld) {
-    return guarded("storm_hip_pairw_lag_similarity_device", [&]() -> int {
-        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-        uint64_t lag = 0;
-        if (int rc = check_lag("pairw_lag_similarity", m, d_out, max_lag, ld, &lag)) return rc;
-        if (int rc = check_measure(measure, n_bits)) return rc;
-        if (m->n_rows < 2) return STORM_HIP_OK;
-        STORM_HIP_TRY(hipSetDevice(ctx->device));
-        if (int rc = lag_similarity_queued(ctx, m, measure, n_bits, max_lag, reinterpret_cast<uint32_t*>(d_out), ld)) return rc;
-        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return STORM_HIP_OK;
-    });
+    return guarded("storm_hip_pairw_lag_similarity_device",
+                   [&] { return pairw_lag_similarity(ctx, m, measure, n_bits, max_lag, d_out, ld, false); });
 }
 
 int storm_hip_pairw_lag_similarity(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_bits,
                                    uint64_t max_lag, float* h_out, uint64_t ld) {
-    return guarded("storm_hip_pairw_lag_similarity", [&]() -> int {
-        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-        uint64_t lag = 0;
-        if (int rc = check_lag("pairw_lag_similarity", m, h_out, max_lag, ld, &lag)) return rc;
-        if (int rc = check_measure(measure, n_bits)) return rc;
-        const uint64_t n = m->n_rows;
-        if (n < 2) return STORM_HIP_OK;
-        STORM_HIP_TRY(hipSetDevice(ctx->device));
-        const size_t need = (size_t)n * lag * sizeof(uint32_t);
-        if (int rc = ctx->d_band.ensure(need, "pairw_lag_similarity: the output")) return rc;
-        STORM_HIP_TRY(hipMemsetAsync(ctx->d_band, 0, need, ctx->stream));   // (the corner: +0.0f is the same zero bits)
-        if (int rc = lag_similarity_queued(ctx, m, measure, n_bits, max_lag, ctx->d_band, lag)) return rc;
-        STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(float), ctx->d_band, lag * sizeof(uint32_t), lag * sizeof(uint32_t), n,
-                                       hipMemcpyDeviceToHost, ctx->stream));
-        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return STORM_HIP_OK;
-    });
+    return guarded("storm_hip_pairw_lag_similarity",
+                   [&] { return pairw_lag_similarity(ctx, m, measure, n_bits, max_lag, h_out, ld, true); });
 }
 
 int storm_hip_cross_dense_similarity_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b,
                                             int measure, uint64_t n_bits, float* d_out, uint64_t ld) {
-    return guarded("storm_hip_cross_dense_similarity_device", [&]() -> int {
-        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-        if (!a || !b || !d_out || ld < b->n_rows) {
-            set_error("cross_dense_similarity: NULL argument or ld < rows of B");
-            return STORM_HIP_EINVAL;
-        }
-        if (int rc = check_measure(measure, n_bits)) return rc;
-        if (a->n_rows == 0 || b->n_rows == 0) return STORM_HIP_OK;
-        STORM_HIP_TRY(hipSetDevice(ctx->device));
-        if (int rc = cross_counts(ctx, a, b, reinterpret_cast<uint32_t*>(d_out), ld)) return rc;
-        if (int rc = finish_dense(ctx, a, b, d_out, ld, 0, measure, n_bits)) return rc;
-        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return STORM_HIP_OK;
-    });
+    return guarded("storm_hip_cross_dense_similarity_device",
+                   [&] { return cross_dense_similarity(ctx, a, b, measure, n_bits, d_out, ld, false); });
 }
 
 int storm_hip_cross_dense_similarity(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b, int measure,
                                      uint64_t n_bits, float* h_out, uint64_t ld) {
-    return guarded("storm_hip_cross_dense_similarity", [&]() -> int {
-        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-        if (!a || !b || !h_out || ld < b->n_rows) {
-            set_error("cross_dense_similarity: NULL argument or ld < rows of B");
-            return STORM_HIP_EINVAL;
-        }
-        if (int rc = check_measure(measure, n_bits)) return rc;
-        const uint64_t na = a->n_rows, nb = b->n_rows;
-        if (na == 0 || nb == 0) return STORM_HIP_OK;
-        STORM_HIP_TRY(hipSetDevice(ctx->device));
-        if (int rc = ctx->d_band.ensure((size_t)na * nb * sizeof(uint32_t), "cross_dense_similarity: the output")) return rc;
-        if (int rc = cross_counts(ctx, a, b, ctx->d_band, nb)) return rc;
-        if (int rc = finish_dense(ctx, a, b, ctx->d_band, nb, 0, measure, n_bits)) return rc;
-        STORM_HIP_TRY(hipMemcpy2DAsync(h_out, ld * sizeof(float), ctx->d_band, nb * sizeof(uint32_t), nb * sizeof(uint32_t), na,
-                                       hipMemcpyDeviceToHost, ctx->stream));
-        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return STORM_HIP_OK;
-    });
+    return guarded("storm_hip_cross_dense_similarity",
+                   [&] { return cross_dense_similarity(ctx, a, b, measure, n_bits, h_out, ld, true); });
 }
 
 }  // extern "C"

@@ -205,7 +205,7 @@ static int topk_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a, const 
         view.d = a->d + p0 * a->stride_words;
         view.n_rows = std::min(panel_rows, na - p0);
         view.n_rows_pad = a->n_rows_pad - p0;
-        if (int rc = launch_square_matrix(ctx, &view, b, STORM_HIP_OP_AND, ctx->d_band.d, ld, false)) return rc;
+        if (int rc = launch_square_matrix(ctx, &view, b, STORM_HIP_OP_AND, ctx->d_band.d, ld)) return rc;
         if (int rc = launch_topk_rows(ctx, ctx->d_band.d, ld, view.n_rows, nb, d_rows + p0, d_cols, self ? p0 : ~0ull, score, n_bits,
                                       k, d_idx + p0 * ld_k, d_val + p0 * ld_k, ld_k))
             return rc;
