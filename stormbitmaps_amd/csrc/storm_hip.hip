@@ -436,41 +436,12 @@ __global__ __launch_bounds__(kThreads) void synth_fill_kernel(uint64_t* __restri
 // ------------------------------------------------------------------------------------------
 static int ensure_segments(storm_hip_ctx_t* ctx, uint64_t n_rows, uint32_t shard_rank,
                            uint32_t shard_count) {
-    const uint32_t seg_len = (uint32_t)ctx->seg_rows;
-    if (ctx->d_segs && ctx->seg_rows_n == n_rows && ctx->seg_shard_rank == shard_rank &&
-        ctx->seg_shard_count == shard_count && ctx->seg_len == seg_len)
-        return STORM_HIP_OK;
-
-    // Full segments first (A-block major), the short diagonal segments last; the shard takes
-    // every shard_count-th entry of each list, so the shards partition the pair space.
-    std::vector<Seg> full, diag, mine;
-    for (uint64_t a0 = 0; a0 < n_rows; a0 += kABlockRows) {
-        const uint32_t a_end = (uint32_t)std::min<uint64_t>(a0 + kABlockRows, n_rows);
-        if (a_end - a0 > 1) diag.push_back({(uint32_t)a0, a_end, (uint32_t)a0, a_end});
-        for (uint64_t j = a0 + kABlockRows; j < n_rows; j += seg_len)
-            full.push_back({(uint32_t)a0, a_end, (uint32_t)j,
-                            (uint32_t)std::min<uint64_t>(j + seg_len, n_rows)});
-    }
-    for (size_t i = shard_rank; i < full.size(); i += shard_count) mine.push_back(full[i]);
-    // rotate the diagonal list so that rank r does not always start at the same A block
-    for (size_t i = shard_rank; i < diag.size(); i += shard_count) mine.push_back(diag[i]);
-
-    uint64_t row_sum = 0;
-    for (const Seg& s : mine) row_sum += s.j_hi - s.j_lo;
-    if (int rc = ctx->d_segs.ensure(mine.size() * sizeof(Seg), "pairw_dense: the segment table", 1024 * sizeof(Seg))) return rc;
-    if (!mine.empty()) {
-        // pageable host memory: the copy is complete (staged) when the call returns
-        STORM_HIP_TRY(hipMemcpyAsync(ctx->d_segs, mine.data(), mine.size() * sizeof(Seg),
-                                     hipMemcpyHostToDevice, ctx->stream));
-        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    }
-    ctx->n_segs = (uint32_t)mine.size();
-    ctx->seg_row_sum = row_sum;
-    ctx->seg_rows_n = n_rows;
-    ctx->seg_shard_rank = shard_rank;
-    ctx->seg_shard_count = shard_count;
-    ctx->seg_len = seg_len;
-    return STORM_HIP_OK;
+    const SegRequest rq = {n_rows, shard_rank, shard_count, (uint32_t)ctx->seg_rows};
+    if (ctx->segs.holds(rq)) return STORM_HIP_OK;
+    // the matrix is one block column from row 0 (plan_sparse_segments, storm_hip_plan.cpp)
+    std::vector<Seg> mine;
+    plan_sparse_segments({{0, n_rows}}, rq.seg_len, shard_rank, shard_count, &mine, &ctx->segs.row_sum);
+    return ctx->segs.put(ctx, rq, mine.data(), mine.size(), "pairw_dense: the segment table", 1024 * sizeof(Seg));
 }
 
 void drain_deferred(storm_hip_ctx_t* ctx, bool aged) {
@@ -642,7 +613,7 @@ void storm_hip_ctx_destroy(storm_hip_ctx_t* ctx) {
     for (hipEvent_t e : ctx->stage_ev)
         if (e) (void)hipEventDestroy(e);
     if (ctx->switch_ev) (void)hipEventDestroy(ctx->switch_ev);
-    ctx->d_segs.release();
+    ctx->segs.release();
     release_mfma_state(ctx);
     for (hipEvent_t ev : ctx->kernel_events) (void)hipEventDestroy(ev);
     delete ctx;
@@ -874,7 +845,7 @@ int storm_hip_debug_strip_trace(storm_hip_ctx_t* ctx, uint64_t* out, uint64_t ca
     std::vector<uint32_t> items(n * 5, 0);
     STORM_HIP_TRY(hipMemcpy(raw.data(), ctx->d_trace, n * 4 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     if (!ctx->trace_is_stream)  // (bitstream_kernel traces workgroups, which have no item record)
-        STORM_HIP_TRY(hipMemcpy(items.data(), ctx->d_strip_items, n * 5 * sizeof(uint32_t),
+        STORM_HIP_TRY(hipMemcpy(items.data(), ctx->strips.d, n * 5 * sizeof(uint32_t),
                                 hipMemcpyDeviceToHost));
     for (uint64_t i = 0; i < n; ++i) {
         for (int k = 0; k < 4; ++k) out[i * 8 + k] = raw[i * 4 + k];
@@ -1335,8 +1306,7 @@ int storm_hip_pairw_dense_launch(storm_hip_ctx_t* ctx, const storm_hip_matrix_t*
     if (int rc = ensure_segments(ctx, m->n_rows, shard_rank, shard_count)) return rc;
     ctx->pass_report[0] |= STORM_HIP_RAN_POPCOUNT;
     ctx->pass_report[1] += m->n_rows * (m->n_rows - (m->n_rows != 0)) / 2 * m->n_words / shard_count;
-    return launch_pairw_segments(ctx, m->d, m->stride_words, ctx->d_segs, ctx->n_segs,
-                                 ctx->seg_row_sum, d_total);
+    return launch_pairw_segments(ctx, m->d, m->stride_words, ctx->segs.d, ctx->segs.n, ctx->segs.row_sum, d_total);
     });
 }
 

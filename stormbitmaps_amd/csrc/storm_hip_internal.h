@@ -91,6 +91,69 @@ struct DevBuf {
     }
 };
 
+// A work list planned on the host and kept on the device with the request it was planned from (DESIGN.md "One cached work
+// list"): the record buffer, the key and the count. A launcher builds its request; a list that holds() it is launched as it
+// stands; otherwise the launcher plans, checks its limits and put()s the new list, the one place where a list goes up and
+// the host waits for it. forget() drops the key and the count and keeps the buffer; whoever overwrites a buffer that several
+// lists share forgets the list it held. Rec void: a buffer of one record type at a time (put takes the records' type).
+template <class Rec, class Key>
+struct WorkList {
+    DevBuf<Rec> d;
+    std::optional<Key> key;   // the request the list was planned from (none: no list)
+    uint32_t n = 0;           // records of that list
+    const Rec* recs() const { return d.d; }
+    bool holds(const Key& k) const { return d && key == k; }
+    void forget() {
+        key.reset();
+        n = 0;
+    }
+    // forgets; grows the buffer (to floor_bytes at least when it grows); copies the records up on the context's stream and
+    // waits for them (the host vector is pageable and leaves scope; nothing for an empty list); then count and key (none:
+    // a list nobody asks for again). Every early return leaves the list forgotten. `what` names the list in the messages.
+    template <class R>
+    int put(storm_hip_ctx_t* ctx, std::optional<Key>&& k, const R* recs, size_t count, const char* what, size_t floor_bytes = 0);
+    void release() {
+        d.release();
+        forget();
+    }
+};
+
+// K1's segment table, of the context (the dense matrix) or of a sparse container (its block columns)
+struct SegRequest {
+    uint64_t n_rows;   // the dense matrix's rows; a sparse container's columns are its own: 0
+    uint32_t shard_rank, shard_count, seg_len;
+    bool operator==(const SegRequest& o) const {
+        return n_rows == o.n_rows && shard_rank == o.shard_rank && shard_count == o.shard_count && seg_len == o.seg_len;
+    }
+};
+struct SegList : WorkList<Seg, SegRequest> {
+    uint64_t row_sum = 0;   // sum over segments of (j_hi - j_lo)
+};
+
+// The item buffer of the tile kernels: ONE list at a time, of MfmaItem records (sum mode, matrix output) or of PartItem
+// records (K2h). The key's alternative says which; `n` counts the list that is there, so a forgotten or another kind's list
+// is zero items to every reader that has just ensured its own.
+struct ItemList : WorkList<void, std::variant<TileSumRequest, MatrixTilesRequest, Tile128Request>> {
+    MatrixPlan matrix_plan;   // of the matrix-output list
+    template <class Rq>
+    bool holds(const Rq& rq) const {   // (no variant is built for the comparison: a MatrixTilesRequest owns vectors)
+        const Rq* have = key ? std::get_if<Rq>(&*key) : nullptr;
+        return d && have && *have == rq;
+    }
+};
+
+// The strip list of an all-pairs pass with the per-XCD queue bounds of its persistent form (plan_strips)
+struct StripList : WorkList<StripItem, StripRequest> {
+    uint32_t queue_base[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t queue_count[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+
+// The strip list of one row panel of launch_pairw_bits_upload, kept on the device between calls
+struct PanelList {
+    WorkList<StripItem, StripRequest> list;
+    hipEvent_t landed = nullptr;   // the panel's rows have arrived
+};
+
 // Geometry of the dense kernel (see DESIGN.md "K1").
 constexpr int kLanes = 64;                           // gfx950 wavefront
 constexpr int kWaves = 4;                            // waves per workgroup
@@ -137,12 +200,7 @@ struct storm_hip_ctx_s {
     bool stage_used[3] = {false, false, false};
     int stage_next = 0;
     void* h_stage_ring = nullptr;            // pinned staging ring of the sparse arena builder (storm_hip_sparse.hip: Stager), allocated on first use
-    storm::DevBuf<storm::Seg> d_segs;        // segment table of the last geometry
-    // cache key of d_segs
-    uint64_t seg_rows_n = 0;
-    uint32_t seg_shard_rank = 0, seg_shard_count = 0, seg_len = 0;
-    uint32_t n_segs = 0;
-    uint64_t seg_row_sum = 0;  // sum over segments of (j_hi - j_lo)
+    storm::SegList segs;                     // K1: segment table of the last geometry
     // options
     int variant = -1;       // -1 auto, 0/1/2 popcount kernel (B path), 3 MFMA tiles, 4 MFMA strips
     int variant_used = 2;   // what the last dense launch ran
@@ -165,16 +223,10 @@ struct storm_hip_ctx_s {
     uint64_t pass_report[4] = {0, 0, 0, 0};
     // K2 (MFMA FP4) state: nibble-expanded shadow of the matrix + item table
     storm::DevBuf<uint8_t> d_x4;
-    storm::DevBuf<void> d_items;     // one list at a time: MfmaItem records (sum mode, matrix output) or PartItem records (K2h)
-    // the request the list in d_items was planned from (monostate: none)
-    std::variant<std::monostate, storm::TileSumRequest, storm::MatrixTilesRequest, storm::Tile128Request> items_key;
-    uint32_t n_items = 0;            // items of the sum-mode list
-    storm::MatrixPlan matrix_plan;   // ... of the matrix-output list
-    void* panel_lists = nullptr;     // work lists of the row panels of storm_hip_pairw_dense_upload (std::vector<PanelList>*)
+    storm::ItemList items;           // the tile kernels' list: one at a time (sum mode, matrix output or K2h)
+    std::vector<storm::PanelList> panel_lists;   // work lists of the row panels of storm_hip_pairw_dense_upload
     hipStream_t copy_stream = nullptr;   // ... its copies travel here while ctx->stream multiplies the panel before
-    storm::DevBuf<storm::StripItem> d_strip_items;
-    std::optional<storm::StripRequest> strip_key;   // the request the all-pairs list in d_strip_items was planned from
-    uint32_t n_strip_items = 0;
+    storm::StripList strips;         // the strip list of the last all-pairs pass; the rectangle (launch_square_mfma) overwrites it without a key
     int k2_stages_per_item = 32;
     int k2_max_run = 0;     // strips: B stages per item at most; 0 = 64 / 96 / 128, whichever list schedules shortest (ensure_strip_items)
     int k2_ring = 4;        // K2s: LDS ring depth (3, 4 or 5)
@@ -193,7 +245,6 @@ struct storm_hip_ctx_s {
     int k2_part_min_chunks = 8;   // K2h: a k-part is at least this many 512-bit chunks
     int k2_part_narrow = 1;       // K2h: windows of 16-bit counts where every part of a tile covers fewer than 2^16 bits of k (half the bytes the part that ends the tile has to read)
     int k2_part_cost_diag = 80;   // K2h: what a chunk of a tile on the diagonal costs next to one of a full tile, percent
-    uint32_t n_part_items = 0;    // items of the K2h list cached in d_items (items_key)
     storm::DevBuf<uint32_t> d_tickets;   // K2h: one arrival counter per tile (zero between launches)
     bool tickets_dirty = false;   // a launch failed: clear the tickets before the next one
     int k2_tile_shape_eff = 2;  // what the call in flight runs (set by launch_pairw_matrix / launch_square_matrix)
@@ -202,8 +253,6 @@ struct storm_hip_ctx_s {
     int k2_tile_cost_diag = 63, k2_tile_cost_ragged = 30;  // percent of a full tile (tilebits8_kernel): what the planner assumes when it cuts the last round
     int k2_shape = 16;      // K2s: MFMA shape of the default strip kernel: 16 = 16x16x128 (default), 32 = 32x32x64
     int k2_persistent = 0;  // K2s: workgroups pull items from per-XCD queues (0: one item per workgroup)
-    uint32_t strip_queue_base[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint32_t strip_queue_count[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // "keep_shadow": reuse the FP4 shadow across all-pairs calls while (matrix, generation, shard,
     // layout) are unchanged. Only valid if the matrix is modified through the library alone.
     int keep_shadow = 0;
@@ -229,10 +278,10 @@ struct storm_hip_ctx_s {
     storm::DevBuf<uint32_t> d_counts;   // row-count scratch of the matrix-output paths
     storm::DevBuf<unsigned long long> d_trace;  // k2_ring = 18: per-item schedule trace of the strip kernel
     uint32_t trace_items = 0;
-    // K2q (bitstream_kernel): segment table + per-workgroup bounds of the last geometry
+    // K2q (bitstream_kernel): per-workgroup bounds + stage bases of the last geometry (never empty: it carries the key) and
+    // the segment table planned with them
+    storm::WorkList<uint32_t, storm::BitstreamRequest> bitfirst;
     storm::DevBuf<storm::BitSeg> d_bitsegs;
-    storm::DevBuf<uint32_t> d_bitfirst;
-    std::optional<storm::BitstreamRequest> bit_key;   // the request both were planned from
     uint32_t n_bit_groups = 0, n_bit_segs = 0, bit_max_stages = 0;
     uint64_t bit_stages = 0;
     int k2_stream_groups_per_cu = 0;  // K2q: workgroups per CU (0 = by the length of the stream: 1, 2 or 3)
@@ -444,6 +493,24 @@ inline int upload_bytes(storm_hip_ctx_t* ctx, void* d_dst, const void* h_src, si
     Stager stager(ctx);
     if (int rc = stager.init()) return rc;
     return stager.send_run(static_cast<uint8_t*>(d_dst), {{h_src, bytes}});
+}
+
+template <class Rec, class Key>
+template <class R>
+int WorkList<Rec, Key>::put(storm_hip_ctx_t* ctx, std::optional<Key>&& k, const R* recs, size_t count, const char* what,
+                            size_t floor_bytes) {
+    forget();
+    if (int rc = d.ensure(count * sizeof(R), what, floor_bytes)) return rc;
+    if (count) {
+        if (int rc = upload_bytes(ctx, d.d, recs, count * sizeof(R))) {
+            if (rc == STORM_HIP_EHIP) set_error("%s: the copy to the device failed", what);
+            return rc;
+        }
+        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    n = (uint32_t)count;
+    key = std::move(k);
+    return STORM_HIP_OK;
 }
 
 // the end of a synchronous call: polls for sync_poll_us, then parks in hipStreamSynchronize (storm_hip_mfma.hip)

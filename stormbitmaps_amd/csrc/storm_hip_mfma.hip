@@ -1599,22 +1599,12 @@ __global__ __launch_bounds__(kStripThreads, 3) void bitstream_kernel(
 #include "../../tools/probes/bitwave.hip"
 #endif  // STORM_HIP_PROBES
 
-struct PanelList {   // the work list of one row panel of launch_pairw_bits_upload, kept on the device between calls
-    std::optional<StripRequest> key;   // the request it was planned from
-    DevBuf<StripItem> d;
-    uint32_t n = 0;
-    hipEvent_t landed = nullptr;
-};
 static void release_panel_lists(storm_hip_ctx_t* ctx) {
-    auto* lists = static_cast<std::vector<PanelList>*>(ctx->panel_lists);
-    if (lists) {
-        for (PanelList& l : *lists) {
-            l.d.release();
-            if (l.landed) (void)hipEventDestroy(l.landed);
-        }
-        delete lists;
+    for (PanelList& l : ctx->panel_lists) {
+        l.list.release();
+        if (l.landed) (void)hipEventDestroy(l.landed);
     }
-    ctx->panel_lists = nullptr;
+    ctx->panel_lists.clear();
     if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
     ctx->copy_stream = nullptr;
 }
@@ -1628,8 +1618,8 @@ void warm_mfma_code(hipStream_t stream) { hipLaunchKernelGGL(warm_mfma_kernel, d
 void release_mfma_state(storm_hip_ctx_t* ctx) {
     release_panel_lists(ctx);
     ctx->d_x4.release();
-    ctx->d_items.release();
-    ctx->d_strip_items.release();
+    ctx->items.release();
+    ctx->strips.release();
     ctx->d_trace.release();
     ctx->d_counts.release();
     ctx->d_band.release();
@@ -1638,12 +1628,12 @@ void release_mfma_state(storm_hip_ctx_t* ctx) {
     ctx->d_parts.release();
     ctx->d_tickets.release();
     ctx->d_bitsegs.release();
-    ctx->d_bitfirst.release();
-    ctx->bit_key.reset();
+    ctx->bitfirst.release();
 }
 
 // The list buffers start at 4096 records: the lists of small matrices never reallocate them.
 constexpr size_t kItemsFloorBytes = 4096 * sizeof(MfmaItem);
+constexpr size_t kStripItemsFloorBytes = 4096 * sizeof(StripItem);
 
 // The summing tile kernel's list (plan_tile_sum, storm_hip_plan.cpp), cached by its request.
 static int ensure_items(storm_hip_ctx_t* ctx, const std::vector<RowRange>& ranges,
@@ -1652,20 +1642,10 @@ static int ensure_items(storm_hip_ctx_t* ctx, const std::vector<RowRange>& range
     const TileSumRequest rq = {ranges_hash(ranges), total_stages, shard_rank, shard_count,
                                (uint32_t)std::max(1, ctx->k2_stages_per_item), diag_only ? 1u : 0u,
                                (ctx->k2_debug & 3) == 1 ? 1u : 0u};
-    const TileSumRequest* have = std::get_if<TileSumRequest>(&ctx->items_key);
-    if (ctx->d_items && have && *have == rq) return STORM_HIP_OK;
+    if (ctx->items.holds(rq)) return STORM_HIP_OK;
     std::vector<MfmaItem> items;
     if (int rc = plan_tile_sum(rq, ranges, items)) return rc;
-    ctx->items_key = std::monostate{};
-    if (int rc = ctx->d_items.ensure(items.size() * sizeof(MfmaItem), "K2: the item table", kItemsFloorBytes)) return rc;
-    if (!items.empty()) {
-        STORM_HIP_TRY(hipMemcpyAsync(ctx->d_items, items.data(), items.size() * sizeof(MfmaItem),
-                                     hipMemcpyHostToDevice, ctx->stream));
-        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    }
-    ctx->n_items = (uint32_t)items.size();
-    ctx->items_key = rq;
-    return STORM_HIP_OK;
+    return ctx->items.put(ctx, rq, items.data(), items.size(), "K2: the item table", kItemsFloorBytes);
 }
 
 // The strip list of an all-pairs pass (plan_strips, storm_hip_plan.cpp), cached by its request: the context's shaping
@@ -1688,22 +1668,15 @@ static int ensure_strip_items(storm_hip_ctx_t* ctx, const std::vector<RowRange>&
                               uint32_t n_kslices, uint32_t shard_rank, uint32_t shard_count,
                               uint32_t a_tile, int xcd_group = 1) {
     const StripRequest rq = strip_request(strip_options_of(ctx, xcd_group), ranges, n_kslices, shard_rank, shard_count, a_tile);
-    if (ctx->d_strip_items && ctx->strip_key == rq) return STORM_HIP_OK;
-    ctx->strip_key.reset();
+    if (ctx->strips.holds(rq)) return STORM_HIP_OK;
+    ctx->strips.forget();   // (the queue bounds below are the new list's)
     std::vector<StripItem> items;
-    plan_strips(rq, ranges, items, ctx->strip_queue_base, ctx->strip_queue_count);
+    plan_strips(rq, ranges, items, ctx->strips.queue_base, ctx->strips.queue_count);
     if (items.size() >= (1ull << 31)) {
         set_error("K2s: %zu strip items exceed the grid limit", items.size());
         return STORM_HIP_EINVAL;
     }
-    if (int rc = ctx->d_strip_items.ensure(items.size() * sizeof(StripItem), "K2s: the strip items", 4096 * sizeof(StripItem))) return rc;
-    if (!items.empty()) {
-        if (int rc_up = upload_bytes(ctx, ctx->d_strip_items, items.data(), items.size() * sizeof(StripItem))) return rc_up;
-        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    }
-    ctx->n_strip_items = (uint32_t)items.size();
-    ctx->strip_key = rq;
-    return STORM_HIP_OK;
+    return ctx->strips.put(ctx, rq, items.data(), items.size(), "K2s: the strip items", kStripItemsFloorBytes);
 }
 
 // Row pitch of the FP4 shadow. Rows whose byte length is a multiple of a large power of two put
@@ -1780,8 +1753,7 @@ int launch_pairw_mfma_ranges(storm_hip_ctx_t* ctx, const uint64_t* X, uint64_t s
     if (int rc = ensure_shadow(ctx, x4_bytes, "K2: the FP4 shadow matrix")) return rc;
     const uint32_t total_stages = (uint32_t)(row_bytes / kStageBytes);
     if (strips) {
-        ctx->n_items = 0;  // the strip items carry the diagonal tiles themselves
-        ctx->items_key = std::monostate{};
+        ctx->items.forget();  // the strip items carry the diagonal tiles themselves: no sum-mode items
     } else if (int rc = ensure_items(ctx, ranges, total_stages, shard_rank, shard_count, false)) {
         return rc;
     }
@@ -1798,7 +1770,8 @@ int launch_pairw_mfma_ranges(storm_hip_ctx_t* ctx, const uint64_t* X, uint64_t s
         set_error("K2: k-slice too long for exact f32 accumulation");
         return STORM_HIP_EINVAL;
     }
-    const uint32_t n_strip = strips ? ctx->n_strip_items : 0;
+    const uint32_t n_strip = strips ? ctx->strips.n : 0;
+    const uint32_t n_tiles = ctx->items.n;   // the sum-mode list just ensured, or none
     const uint64_t key[4] = {(uint64_t)(uintptr_t)X, shadow_generation,
                              ((uint64_t)shard_rank << 32) | shard_count,
                              (pitch << 20) ^ (n_rows_dst << 2) ^ (uint64_t)strip_mode};
@@ -1814,7 +1787,7 @@ int launch_pairw_mfma_ranges(storm_hip_ctx_t* ctx, const uint64_t* X, uint64_t s
                                  : ExpandOwn{shard_rank, shard_count, 7u, 0xffffffffu};
     const uint32_t nib = (ctx->k2_debug >> 8) ? (uint32_t)(ctx->k2_debug >> 8) & 15u : 2u;
     const uint64_t n_src = std::min(n_rows_src, n_rows_dst);
-    for (uint32_t chunk = 0; chunk < n_chunks && (ctx->n_items > 0 || n_strip > 0); ++chunk) {
+    for (uint32_t chunk = 0; chunk < n_chunks && (n_tiles > 0 || n_strip > 0); ++chunk) {
         if (!shadow_valid) {
             if (n_chunks == 1) {
                 hipLaunchKernelGGL(expand_fp4_kernel,
@@ -1834,12 +1807,12 @@ int launch_pairw_mfma_ranges(storm_hip_ctx_t* ctx, const uint64_t* X, uint64_t s
         else memset(ctx->x4_key, 0, sizeof(ctx->x4_key));
         if (n_strip > 0) {
             kernel_time_mark(ctx);
-            const StripItem* sit = ctx->d_strip_items;
+            const StripItem* sit = ctx->strips.d;
             const dim3 sgrid(n_strip), sblock(kStripThreads);
 #ifdef STORM_HIP_PROBES   // the other forms of the strips (ring depths, 32x32x64, wide, persistent, timing probes, trace): tools build
             StripQueues queues;
-            memcpy(queues.base, ctx->strip_queue_base, sizeof(queues.base));
-            memcpy(queues.count, ctx->strip_queue_count, sizeof(queues.count));
+            memcpy(queues.base, ctx->strips.queue_base, sizeof(queues.base));
+            memcpy(queues.count, ctx->strips.queue_count, sizeof(queues.count));
             unsigned int* heads = reinterpret_cast<unsigned int*>(ctx->d_slots + kSlots);
             // persistent form: one workgroup per resident slot
             const dim3 pgrid(std::min<uint32_t>(n_strip, (uint32_t)ctx->n_cus * (strip_mode == 2 ? 2u : 4u)));
@@ -1872,10 +1845,10 @@ int launch_pairw_mfma_ranges(storm_hip_ctx_t* ctx, const uint64_t* X, uint64_t s
             kernel_time_mark(ctx);
             STORM_HIP_TRY(hipGetLastError());
         }
-        if (ctx->n_items > 0) {
+        if (n_tiles > 0) {
             kernel_time_mark(ctx);
-            const dim3 kgrid(ctx->n_items), block(kMfmaThreads);
-            const MfmaItem* items = static_cast<const MfmaItem*>(ctx->d_items.d);
+            const dim3 kgrid(n_tiles), block(kMfmaThreads);
+            const MfmaItem* items = static_cast<const MfmaItem*>(ctx->items.recs());
             switch (ctx->k2_debug & 12) {  // 4 / 8: timing probes without DMA / without MFMA
 #ifdef STORM_HIP_PROBES
                 case 4:
@@ -1896,11 +1869,11 @@ int launch_pairw_mfma_ranges(storm_hip_ctx_t* ctx, const uint64_t* X, uint64_t s
             STORM_HIP_TRY(hipGetLastError());
         }
     }
-    if (ctx->n_items + n_strip > 0) {
+    if (n_tiles + n_strip > 0) {
         ctx->pass_report[0] |= strips ? STORM_HIP_RAN_FP4_STRIPS : STORM_HIP_RAN_FP4_TILES;
         ctx->pass_report[1] += ranges_word_pairs(ranges, n_words_logical ? n_words_logical : stride_words, shard_count);
     }
-    ctx->last_info[0] = ctx->n_items + n_strip;
+    ctx->last_info[0] = n_tiles + n_strip;
     ctx->last_info[1] = ctx->k2_stages_per_item;
     ctx->last_info[2] = n_chunks;
     ctx->last_info[3] = 0;
@@ -1938,11 +1911,8 @@ int launch_square_mfma(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
         set_error("square: %zu strip items exceed the grid limit", items.size());
         return STORM_HIP_EINVAL;
     }
-    ctx->strip_key.reset();  // the cached all-pairs table is gone
-    ctx->n_strip_items = 0;
-    if (int rc = ctx->d_strip_items.ensure(items.size() * sizeof(StripItem), "square: the strip items", 4096 * sizeof(StripItem))) return rc;
-    if (int rc_up = upload_bytes(ctx, ctx->d_strip_items, items.data(), items.size() * sizeof(StripItem))) return rc_up;
-    STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));  // `items` leaves scope
+    // (no key: the cached all-pairs list is gone and nobody asks for this one again)
+    if (int rc = ctx->strips.put(ctx, std::nullopt, items.data(), items.size(), "square: the strip items", kStripItemsFloorBytes)) return rc;
     for (int side = 0; side < 2; ++side) {
         const storm_hip_matrix_s* m = side ? b : a;
         const uint64_t rows_dst = side ? rows_b : rows_a;
@@ -1957,12 +1927,12 @@ int launch_square_mfma(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
     if (ctx->k2_shape != 16)
         hipLaunchKernelGGL(strip_fp4_kernel<kStripRingDefault>, dim3((uint32_t)items.size()),
                            dim3(kStripThreads), 0, ctx->stream, ctx->d_x4, pitch,
-                           ctx->d_strip_items.d, ctx->d_slots);
+                           ctx->strips.recs(), ctx->d_slots);
     else
 #endif
         hipLaunchKernelGGL(strip16_fp4_kernel<kStripRingDefault>, dim3((uint32_t)items.size()),
                            dim3(kStripThreads), 0, ctx->stream, ctx->d_x4, pitch,
-                           ctx->d_strip_items.d, ctx->d_slots);
+                           ctx->strips.recs(), ctx->d_slots);
     STORM_HIP_TRY(hipGetLastError());
     ctx->last_info[0] = (uint32_t)items.size();
     return launch_fold_slots(ctx, d_total);
@@ -2035,24 +2005,16 @@ static int ensure_matrix_tiles(storm_hip_ctx_t* ctx, MatrixTilesRequest&& rq, Ma
     rq.n_cus = (uint32_t)std::max(1, ctx->n_cus);
     rq.split = ctx->k2_matrix_split;
     rq.min_part = ctx->k2_matrix_min_part;
-    const MatrixTilesRequest* have = std::get_if<MatrixTilesRequest>(&ctx->items_key);
-    if (ctx->d_items && have && *have == rq) {
-        *plan = ctx->matrix_plan;
+    if (ctx->items.holds(rq)) {
+        *plan = ctx->items.matrix_plan;
         return STORM_HIP_OK;
     }
     std::vector<MfmaItem> items;
     plan_matrix_tiles(rq, items, plan);
-    // the context's item buffer (shared with the tile kernel's sum mode, whose cached table is
-    // dropped here); hipMalloc / hipFree per call would cost more than the kernel's tail
-    ctx->items_key = std::monostate{};
-    ctx->n_items = 0;
-    if (int rc = ctx->d_items.ensure(items.size() * sizeof(MfmaItem), "matrix output: the item table", kItemsFloorBytes)) return rc;
-    STORM_HIP_TRY(hipMemcpyAsync(ctx->d_items, items.data(), items.size() * sizeof(MfmaItem),
-                                 hipMemcpyHostToDevice, ctx->stream));
-    STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));  // `items` is pageable and leaves scope
-    ctx->matrix_plan = *plan;
-    ctx->items_key = std::move(rq);
-    return STORM_HIP_OK;
+    // the context's item buffer (shared with the tile kernel's sum mode and K2h, whose cached list is dropped here);
+    // hipMalloc / hipFree per call would cost more than the kernel's tail
+    ctx->items.matrix_plan = *plan;
+    return ctx->items.put(ctx, std::move(rq), items.data(), items.size(), "matrix output: the item table", kItemsFloorBytes);
 }
 
 // Runs the 256 x 256 tile kernel that k2_tile_shape_eff names over the planned items, into the window w. `bits` (the
@@ -2063,7 +2025,7 @@ static int ensure_matrix_tiles(storm_hip_ctx_t* ctx, MatrixTilesRequest&& rq, Ma
 // window (or, option k2_matrix_parts, write windows of their own that reduce_parts_kernel adds up).
 static int run_matrix_tiles(storm_hip_ctx_t* ctx, const MatrixPlan& plan, const TileOperands& ops, bool bits, const OutWindow& w) {
     if (!bits) memset(ctx->x4_key, 0, sizeof(ctx->x4_key));  // callers rebuilt the shadow in the tile layout
-    const MfmaItem* d_items = static_cast<const MfmaItem*>(ctx->d_items.d);
+    const MfmaItem* d_items = static_cast<const MfmaItem*>(ctx->items.recs());
     // [r5] option k2_matrix_parts: the k-parts of the tile kernels that ship write their own windows and a second kernel
     // adds them up (no clearing, no atomics); otherwise — and for the other forms, and for part lists beyond 1 GiB of
     // windows — the parts add into the cleared output
@@ -2170,15 +2132,10 @@ static int run_tile128(storm_hip_ctx_t* ctx, uint32_t total_stages, const TileOp
     const Tile128Request rq = {ia0, ia1, jb0, jb1, w.rect() ? 0u : 1u, total_stages, (uint32_t)std::max(1, ctx->n_cus),
                                ctx->k2_part_slots, ctx->k2_part_min_chunks, ctx->k2_part_cost_diag,
                                ctx->k2_part_narrow != 0 ? 1u : 0u, lag, value_bits == 2u ? kThWeightDosage : kThWeightBits};
-    const Tile128Request* have = std::get_if<Tile128Request>(&ctx->items_key);
-    if (!(ctx->d_items && have && *have == rq)) {
+    if (!ctx->items.holds(rq)) {
         Tile128Plan plan;
         plan_tile128(rq, &plan);
-        const size_t bytes = plan.items.size() * sizeof(PartItem);
-        ctx->items_key = std::monostate{};
-        ctx->n_items = 0;
-        ctx->n_part_items = 0;
-        if (int rc = ctx->d_items.ensure(bytes, "pairw_matrix: the item table", kItemsFloorBytes)) return rc;
+        ctx->items.forget();
         // the parts' windows and the tiles' tickets (zero between launches: the part that ends a tile clears its ticket)
         if (int rc = ctx->d_parts.ensure((size_t)plan.n_windows * kThWindowWords * sizeof(uint32_t), "pairw_matrix: the k-parts' windows"))
             return rc;
@@ -2188,28 +2145,25 @@ static int run_tile128(storm_hip_ctx_t* ctx, uint32_t total_stages, const TileOp
             STORM_HIP_TRY(hipMemsetAsync(ctx->d_tickets, 0, ctx->d_tickets.capacity, ctx->stream));
             ctx->tickets_dirty = false;
         }
-        if (!plan.items.empty()) {
-            STORM_HIP_TRY(hipMemcpyAsync(ctx->d_items, plan.items.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-            STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));  // the list is pageable and leaves scope
-        }
-        ctx->items_key = rq;
-        ctx->n_part_items = (uint32_t)plan.items.size();
+        if (int rc = ctx->items.put(ctx, rq, plan.items.data(), plan.items.size(), "pairw_matrix: the item table", kItemsFloorBytes))
+            return rc;
     } else if (ctx->tickets_dirty) {
         STORM_HIP_TRY(hipMemsetAsync(ctx->d_tickets, 0, ctx->d_tickets.capacity, ctx->stream));
         ctx->tickets_dirty = false;
     }
-    const PartItem* d_items = static_cast<const PartItem*>(ctx->d_items.d);
-    if (ctx->n_part_items && w.form == OutForm::Lag && value_bits == 2u)
-        hipLaunchKernelGGL((tile128_kernel<true, 2>), dim3(ctx->n_part_items), dim3(kThThreads), 0, ctx->stream, ops, d_items, w,
+    const PartItem* d_items = static_cast<const PartItem*>(ctx->items.recs());
+    const uint32_t n_parts = ctx->items.n;
+    if (n_parts && w.form == OutForm::Lag && value_bits == 2u)
+        hipLaunchKernelGGL((tile128_kernel<true, 2>), dim3(n_parts), dim3(kThThreads), 0, ctx->stream, ops, d_items, w,
                            ctx->d_parts, ctx->d_tickets);
-    else if (ctx->n_part_items && w.form == OutForm::Lag)
-        hipLaunchKernelGGL(tile128_kernel<true>, dim3(ctx->n_part_items), dim3(kThThreads), 0, ctx->stream, ops, d_items, w,
+    else if (n_parts && w.form == OutForm::Lag)
+        hipLaunchKernelGGL(tile128_kernel<true>, dim3(n_parts), dim3(kThThreads), 0, ctx->stream, ops, d_items, w,
                            ctx->d_parts, ctx->d_tickets);
-    else if (ctx->n_part_items && value_bits == 2u)
-        hipLaunchKernelGGL((tile128_kernel<false, 2>), dim3(ctx->n_part_items), dim3(kThThreads), 0, ctx->stream, ops, d_items, w,
+    else if (n_parts && value_bits == 2u)
+        hipLaunchKernelGGL((tile128_kernel<false, 2>), dim3(n_parts), dim3(kThThreads), 0, ctx->stream, ops, d_items, w,
                            ctx->d_parts, ctx->d_tickets);
-    else if (ctx->n_part_items)
-        hipLaunchKernelGGL(tile128_kernel<false>, dim3(ctx->n_part_items), dim3(kThThreads), 0, ctx->stream, ops, d_items, w,
+    else if (n_parts)
+        hipLaunchKernelGGL(tile128_kernel<false>, dim3(n_parts), dim3(kThThreads), 0, ctx->stream, ops, d_items, w,
                            ctx->d_parts, ctx->d_tickets);
     if (hipGetLastError() != hipSuccess) {
         ctx->tickets_dirty = true;
@@ -2443,8 +2397,8 @@ static BitstreamRequest bitstream_request_of(const storm_hip_ctx_t* ctx, const s
 static int ensure_bitstream(storm_hip_ctx_t* ctx, const std::vector<RowRange>& ranges, uint32_t n_kslices,
                             uint32_t shard_rank, uint32_t shard_count, uint64_t pitch) {
     const BitstreamRequest rq = bitstream_request_of(ctx, ranges, n_kslices, shard_rank, shard_count, pitch);
-    if (ctx->d_bitsegs && ctx->bit_key == rq) return STORM_HIP_OK;
-    ctx->bit_key.reset();
+    if (ctx->bitfirst.holds(rq)) return STORM_HIP_OK;
+    ctx->bitfirst.forget();   // (the segment table and the counters below change in front of the put)
     BitstreamPlan plan;
     build_bitstream(rq, ranges, plan);
     if (plan.bases.size() >= (1ull << 32) ||
@@ -2462,21 +2416,17 @@ static int ensure_bitstream(storm_hip_ctx_t* ctx, const std::vector<RowRange>& r
     packed.insert(packed.end(), plan.first_stage.begin(), plan.first_stage.end());
     packed.insert(packed.end(), plan.bases.begin(), plan.bases.end());
     packed.push_back(0u);  // a trailing workgroup without stages reads bases[total stages] (bitstream_kernel: prep)
-    const size_t first_bytes = packed.size() * sizeof(uint32_t);
+    // the segments travel in front of the stage tables, whose put waits for both
     if (int rc = ctx->d_bitsegs.ensure(seg_bytes, "K2q: the segment table")) return rc;
-    if (int rc = ctx->d_bitfirst.ensure(first_bytes, "K2q: the workgroups' stage tables")) return rc;
-    if (!plan.segs.empty())
-        STORM_HIP_TRY(hipMemcpyAsync(ctx->d_bitsegs, plan.segs.data(), plan.segs.size() * sizeof(BitSeg),
-                                     hipMemcpyHostToDevice, ctx->stream));
-    STORM_HIP_TRY(hipMemcpyAsync(ctx->d_bitfirst, packed.data(), first_bytes, hipMemcpyHostToDevice,
-                                 ctx->stream));
-    STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (upload_bytes(ctx, ctx->d_bitsegs, plan.segs.data(), plan.segs.size() * sizeof(BitSeg))) {
+        set_error("K2q: the segment table: the copy to the device failed");
+        return STORM_HIP_EHIP;
+    }
     ctx->n_bit_groups = plan.groups;
     ctx->bit_stages = plan.stages;
     ctx->bit_max_stages = plan.max_stages;
     ctx->n_bit_segs = (uint32_t)plan.segs.size();
-    ctx->bit_key = rq;
-    return STORM_HIP_OK;
+    return ctx->bitfirst.put(ctx, rq, packed.data(), packed.size(), "K2q: the workgroups' stage tables");
 }
 
 // One launch: the all-pairs total of every row range of a bit matrix (pitch in bytes, rows up to the
@@ -2492,8 +2442,7 @@ int launch_pairw_bitstream(storm_hip_ctx_t* ctx, const uint64_t* X, uint64_t pit
     if (int rc = ensure_bitstream(ctx, ranges, n_kslices, shard_rank, shard_count, pitch)) return rc;
     ctx->pass_report[0] |= STORM_HIP_RAN_BITSTREAM;
     ctx->pass_report[1] += ranges_word_pairs(ranges, (uint64_t)n_kslices * 8u, shard_count);
-    ctx->n_items = 0;
-    ctx->items_key = std::monostate{};
+    ctx->items.forget();
     ctx->last_info[0] = ctx->n_bit_groups;
     ctx->last_info[1] = ctx->bit_max_stages;
     ctx->last_info[2] = 1;
@@ -2510,17 +2459,17 @@ int launch_pairw_bitstream(storm_hip_ctx_t* ctx, const uint64_t* X, uint64_t pit
         ctx->trace_is_stream = true;
         hipLaunchKernelGGL(bitstream_kernel<true>, grid, block, 0, ctx->stream,
                            reinterpret_cast<const uint8_t*>(X), pitch, ctx->d_bitsegs.d,
-                           ctx->d_bitfirst.d,
-                           ctx->d_bitfirst.d + 2 * ((size_t)ctx->n_bit_groups + 1),
-                           ctx->d_bitfirst.d + ((size_t)ctx->n_bit_groups + 1), ctx->d_slots,
+                           ctx->bitfirst.recs(),
+                           ctx->bitfirst.recs() + 2 * ((size_t)ctx->n_bit_groups + 1),
+                           ctx->bitfirst.recs() + ((size_t)ctx->n_bit_groups + 1), ctx->d_slots,
                            reinterpret_cast<unsigned long long*>(d_total), ctx->d_trace);
     } else
 #endif
         hipLaunchKernelGGL(bitstream_kernel<false>, grid, block, 0, ctx->stream,
                            reinterpret_cast<const uint8_t*>(X), pitch, ctx->d_bitsegs.d,
-                           ctx->d_bitfirst.d,
-                           ctx->d_bitfirst.d + 2 * ((size_t)ctx->n_bit_groups + 1),
-                           ctx->d_bitfirst.d + ((size_t)ctx->n_bit_groups + 1), ctx->d_slots,
+                           ctx->bitfirst.recs(),
+                           ctx->bitfirst.recs() + 2 * ((size_t)ctx->n_bit_groups + 1),
+                           ctx->bitfirst.recs() + ((size_t)ctx->n_bit_groups + 1), ctx->d_slots,
                            reinterpret_cast<unsigned long long*>(d_total), (unsigned long long*)nullptr);
     kernel_time_mark(ctx);
     STORM_HIP_TRY(hipGetLastError());
@@ -2542,8 +2491,7 @@ int launch_pairw_bits_ranges(storm_hip_ctx_t* ctx, const uint8_t* X, uint64_t pi
         set_error("K2b: rows of %llu bytes are beyond the strips' 32-bit DMA offsets", (unsigned long long)pitch);
         return STORM_HIP_EINVAL;
     }
-    ctx->n_items = 0;  // the strip items carry the diagonal tiles themselves
-    ctx->items_key = std::monostate{};
+    ctx->items.forget();  // the strip items carry the diagonal tiles themselves
     // (rows128 — strip16_rows_kernel: n_kslices2 counts slices of 16 bytes, a_tile is 512, the 8 slices of a 128-byte line share an XCD)
     if (rows128 && a_tile != kStripRowsATile) {
         set_error("K2b: the 128-rows-per-wave form takes A tiles of 512 rows");
@@ -2551,7 +2499,7 @@ int launch_pairw_bits_ranges(storm_hip_ctx_t* ctx, const uint8_t* X, uint64_t pi
     }
     if (int rc = ensure_strip_items(ctx, ranges, n_kslices2, shard_rank, shard_count, a_tile, rows128 ? (int)kStripRowsXcdGroup : 2))
         return rc;
-    const uint32_t n_strip = ctx->n_strip_items;
+    const uint32_t n_strip = ctx->strips.n;
     const uint32_t waves = rows128 ? 4u : a_tile / (uint32_t)kStripBRows;   // 4, or 8 for the 512-row form (strip16_bits2_kernel)
     ctx->k2_operands_used = waves == 8u ? 6 : 5;
     ctx->k2_strip_rows_used = rows128 ? 128 : 64;
@@ -2586,16 +2534,16 @@ int launch_pairw_bits_ranges(storm_hip_ctx_t* ctx, const uint8_t* X, uint64_t pi
             const bool plain = ranges.size() == 1 && ranges[0].r0 == 0 && ranges[0].a_end == 0 && ranges[0].back_from == ~0ull &&
                                ranges[0].r1 < (uint64_t)kStripRowsNoTrim;
             hipLaunchKernelGGL(strip16_rows_kernel, dim3(n_strip), dim3(256), (size_t)ctx->k2_lds_pad,
-                               ctx->stream, X, pitch, ctx->d_strip_items.d, ctx->d_slots,
+                               ctx->stream, X, pitch, ctx->strips.recs(), ctx->d_slots,
                                fold_inline ? reinterpret_cast<unsigned long long*>(d_total) : nullptr, fold_slots,
                                plain ? (uint32_t)ranges[0].r1 : kStripRowsNoTrim);
         } else if (waves == 8u)
             hipLaunchKernelGGL(strip16_bits2_kernel, dim3(n_strip), dim3(512), (size_t)ctx->k2_lds_pad,
-                               ctx->stream, X, pitch, ctx->d_strip_items.d, ctx->d_slots,
+                               ctx->stream, X, pitch, ctx->strips.recs(), ctx->d_slots,
                                fold_inline ? reinterpret_cast<unsigned long long*>(d_total) : nullptr, fold_slots);
         else
             hipLaunchKernelGGL(strip16_bits_kernel, dim3(n_strip), dim3(kStripThreads), (size_t)ctx->k2_lds_pad,
-                               ctx->stream, X, pitch, ctx->d_strip_items.d, ctx->d_slots,
+                               ctx->stream, X, pitch, ctx->strips.recs(), ctx->d_slots,
                                fold_inline ? reinterpret_cast<unsigned long long*>(d_total) : nullptr, fold_slots);
         kernel_time_mark(ctx);
         STORM_HIP_TRY(hipGetLastError());
@@ -2640,8 +2588,7 @@ static int launch_pairw_bits(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, 
     if (operands == 3)
         return launch_pairw_bitwave(ctx, m->d, pitch, ranges, n_kslices, shard_rank, shard_count, d_total);
 #endif
-    ctx->n_items = 0;  // the strip items carry the diagonal tiles themselves
-    ctx->items_key = std::monostate{};
+    ctx->items.forget();  // the strip items carry the diagonal tiles themselves
     if (operands == 5 && strip_rows128(ctx, m, shard_count))
         return launch_pairw_bits_ranges(ctx, reinterpret_cast<const uint8_t*>(m->d), pitch, ranges, strip_rows_kslices(m->n_words),
                                         shard_rank, shard_count, d_total, false, kStripRowsATile, true);
@@ -2654,12 +2601,12 @@ static int launch_pairw_bits(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, 
     set_error("k2_strip_operands = 1 (stripbits_kernel) is in the tools build only (`make probes`)");
     return STORM_HIP_EINVAL;
 #else
-    const uint32_t n_strip = ctx->n_strip_items;
+    const uint32_t n_strip = ctx->strips.n;
     if (n_strip > 0) {
         kernel_time_mark(ctx);
         hipLaunchKernelGGL(stripbits_kernel, dim3(n_strip), dim3(kStripThreads), 0, ctx->stream,
                            reinterpret_cast<const uint8_t*>(m->d), pitch,
-                           ctx->d_strip_items.d, ctx->d_slots);
+                           ctx->strips.recs(), ctx->d_slots);
         kernel_time_mark(ctx);
         STORM_HIP_TRY(hipGetLastError());
     }
@@ -2701,8 +2648,7 @@ static int pairw_bits_upload_queue(storm_hip_ctx_t* ctx, storm_hip_matrix_s* m, 
         return STORM_HIP_EINVAL;
     }
     if (!ctx->copy_stream) STORM_HIP_TRY(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    if (!ctx->panel_lists) ctx->panel_lists = new std::vector<PanelList>();
-    auto& lists = *static_cast<std::vector<PanelList>*>(ctx->panel_lists);
+    std::vector<PanelList>& lists = ctx->panel_lists;
     // The copies must not overtake what the context's stream still has to do to this matrix: storm_hip_matrix_create
     // zero-fills a fresh allocation ASYNCHRONOUSLY there, storm_hip_matrix_resize clears the rows a shrinking matrix gives
     // up (a first call on a new shape lost rows to that memset one time in six before this wait was here).
@@ -2745,8 +2691,7 @@ static int pairw_bits_upload_queue(storm_hip_ctx_t* ctx, storm_hip_matrix_s* m, 
         rg.back_from = row0;
         const std::vector<RowRange> panel = {rg};
         const StripRequest rq = strip_request(po, panel, n_kslices2, 0, 1, (uint32_t)kStripATile);
-        if (!l.d || !(l.key == rq)) {
-            l.key.reset();
+        if (!l.list.holds(rq)) {
             std::vector<StripItem> items;
             uint32_t qb[8], qc[8];
             plan_strips(rq, panel, items, qb, qc);
@@ -2754,23 +2699,17 @@ static int pairw_bits_upload_queue(storm_hip_ctx_t* ctx, storm_hip_matrix_s* m, 
                 set_error("pairw_dense_upload: %zu strip items exceed the grid limit", items.size());
                 return STORM_HIP_EINVAL;
             }
-            if (int rc = l.d.ensure(items.size() * sizeof(StripItem), "pairw_dense_upload: a panel's strip items", 1024 * sizeof(StripItem)))
+            if (int rc = l.list.put(ctx, rq, items.data(), items.size(), "pairw_dense_upload: a panel's strip items", 1024 * sizeof(StripItem)))
                 return rc;
-            l.n = (uint32_t)items.size();
-            if (l.n) {
-                if (int rc_up = upload_bytes(ctx, l.d, items.data(), items.size() * sizeof(StripItem))) return rc_up;
-                STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));   // `items` leaves scope
-            }
-            l.key = rq;
         }
         STORM_HIP_TRY(hipStreamWaitEvent(ctx->stream, l.landed, 0));
-        if (l.n) {
-            hipLaunchKernelGGL(strip16_bits_kernel, dim3(l.n), dim3(kStripThreads), (size_t)ctx->k2_lds_pad, ctx->stream,
-                               reinterpret_cast<const uint8_t*>(m->d), pitch, l.d.d, ctx->d_slots,
+        if (l.list.n) {
+            hipLaunchKernelGGL(strip16_bits_kernel, dim3(l.list.n), dim3(kStripThreads), (size_t)ctx->k2_lds_pad, ctx->stream,
+                               reinterpret_cast<const uint8_t*>(m->d), pitch, l.list.recs(), ctx->d_slots,
                                (unsigned long long*)nullptr, (uint32_t)kSlots);
             STORM_HIP_TRY(hipGetLastError());
         }
-        n_total += l.n;
+        n_total += l.list.n;
     }
     ctx->last_info[0] = n_total;
     ctx->last_info[1] = ctx->k2_stages_per_item;

@@ -49,11 +49,7 @@ struct storm_hip_sparse_s : storm::ArenaColumns, storm::ProbeWork {   // the col
     size_t probe_items_capacity = 0;
     uint32_t n_probe_launch = 0, n_probe_cols_launch = 0;
     uint64_t probe_lookups_launch = 0;  // positions the launched items stream + their own rows' elements (this shard)
-    // segment table cache (per shard)
-    Seg* d_segs = nullptr;
-    uint32_t n_segs = 0;
-    uint64_t seg_row_sum = 0;
-    uint32_t seg_rank = 0, seg_count = 0, seg_len = 0;
+    storm::SegList segs;   // K1's segment table of the columns (per shard and segment length)
 };
 
 namespace {
@@ -1435,7 +1431,7 @@ void storm_hip_sparse_destroy(storm_hip_ctx_t* ctx, storm_hip_sparse_t* s) {
         (void)hipStreamSynchronize(ctx->stream);
     }
     if (s->d_pool) (void)hipFree(s->d_pool);
-    if (s->d_segs) (void)hipFree(s->d_segs);
+    s->segs.release();
     if (s->d_probe_elems) (void)hipFree(s->d_probe_elems);
     if (s->d_probe_pos16) (void)hipFree(s->d_probe_pos16);
     if (s->d_probe_items) (void)hipFree(s->d_probe_items);
@@ -1528,21 +1524,11 @@ static int launch_probe(storm_hip_ctx_t* ctx, const storm_hip_sparse_t* s, uint3
 
 // K1's segment table of this shard on the device (cached per shard and segment length)
 static int ensure_segments(storm_hip_ctx_t* ctx, storm_hip_sparse_t* s, uint32_t seg_len, uint32_t shard_rank, uint32_t shard_count) {
-    if (s->d_segs && s->seg_rank == shard_rank && s->seg_count == shard_count && s->seg_len == seg_len) return STORM_HIP_OK;
+    const SegRequest rq = {0, shard_rank, shard_count, seg_len};
+    if (s->segs.holds(rq)) return STORM_HIP_OK;
     std::vector<Seg> mine;
-    if (s->d_segs) STORM_HIP_TRY(hipFree(s->d_segs));
-    s->d_segs = nullptr;
-    plan_sparse_segments(s->cols, seg_len, shard_rank, shard_count, &mine, &s->seg_row_sum);
-    if (!mine.empty()) {
-        STORM_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s->d_segs), mine.size() * sizeof(Seg)));
-        STORM_HIP_TRY(hipMemcpyAsync(s->d_segs, mine.data(), mine.size() * sizeof(Seg), hipMemcpyHostToDevice, ctx->stream));
-        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    }
-    s->n_segs = (uint32_t)mine.size();
-    s->seg_rank = shard_rank;
-    s->seg_count = shard_count;
-    s->seg_len = seg_len;
-    return STORM_HIP_OK;
+    plan_sparse_segments(s->cols, seg_len, shard_rank, shard_count, &mine, &s->segs.row_sum);
+    return s->segs.put(ctx, rq, mine.data(), mine.size(), "pairw_sparse: the segment table");
 }
 
 // Launches this shard's share into the context's result word; _end fetches it.
@@ -1573,7 +1559,7 @@ int storm_hip_pairw_sparse_begin(storm_hip_ctx_t* ctx, const storm_hip_sparse_t*
     if (variant < 3) {
         if (int rc = ensure_full_pool(ctx, s)) return rc;  // the popcount kernel walks every column's pool rows
         if (int rc = ensure_segments(ctx, s, (uint32_t)ctx->seg_rows, shard_rank, shard_count)) return rc;
-        return launch_pairw_segments(ctx, s->d_pool, s->pitch, s->d_segs, s->n_segs, s->seg_row_sum, d_result);
+        return launch_pairw_segments(ctx, s->d_pool, s->pitch, s->segs.d, s->segs.n, s->segs.row_sum, d_result);
     }
     // K4: columns of short lists go to the probe kernel ("sparse_probe": -1 = when the mean list
     // has at most 1000 positions — measured at c4 (profiles/r02_q_sparse_probe.jsonl): 47x faster

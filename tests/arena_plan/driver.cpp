@@ -8,6 +8,7 @@
 //     per block:  id kind n ptr  v[0 .. n)      kind 0 = list of n positions (the values follow), else no values;
 //                                                ptr 0 = the block has data, 1 = at an odd address, 2 = NULL
 //     n_overrides, then per override:  probe_block octant value     (replaces a computed run end)
+// With the argument --single-column instead of a case file: K1's segment tables of a dense matrix (one column from row 0).
 #include <cstdarg>
 #include <cstdio>
 #include <fstream>
@@ -63,8 +64,32 @@ static std::vector<std::vector<uint32_t>> with_col(const std::vector<Item>& item
     return rows;
 }
 
+// K1's segment table of a dense matrix: plan_sparse_segments over the single column from row 0 (storm_hip.hip: ensure_segments)
+static int single_column_segments() {
+    printf("{\n");
+    bool first_case = true;
+    for (uint64_t n : {1ull, 2ull, 128ull, 129ull, 600ull})
+        for (uint32_t seg_len : {256u, 100u})
+            for (uint32_t world : {1u, 3u})
+                for (uint32_t rank = 0; rank < world; ++rank) {
+                    std::vector<Seg> mine;
+                    uint64_t row_sum = 0;
+                    plan_sparse_segments({{0, n}}, seg_len, rank, world, &mine, &row_sum);
+                    std::vector<std::vector<uint32_t>> recs;
+                    for (const Seg& g : mine) recs.push_back({g.a_row0, g.a_end, g.j_lo, g.j_hi});
+                    printf("%s\"n%llu/len%u/w%u/r%u\": {\n", first_case ? "" : ",", (unsigned long long)n, seg_len, world, rank);
+                    first_case = false;
+                    put_rows("segs", recs);
+                    put("row_sum", std::vector<uint64_t>{row_sum}, "");
+                    printf("}\n");
+                }
+    printf("}\n");
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc != 2) return 2;
+    if (std::string(argv[1]) == "--single-column") return single_column_segments();
     std::ifstream f(argv[1]);
     uint64_t n_rows = 0, n_blocks = 0;
     if (!(f >> n_rows >> n_blocks)) return 2;

@@ -183,6 +183,38 @@ def test_the_segments_cover_every_row_pair_of_a_column_once(plans, name):
             assert pairs == want
 
 
+def _dense_segments(n_rows, seg_len, rank, world, block=128):
+    """The loop that stood in storm_hip.hip's ensure_segments (the dense matrix's own planner), transcribed: full segments
+    first (A-block major), the short diagonal segments last; a shard takes every world-th entry of each list."""
+    full, diag = [], []
+    for a0 in range(0, n_rows, block):
+        a_end = min(a0 + block, n_rows)
+        if a_end - a0 > 1:
+            diag.append([a0, a_end, a0, a_end])
+        for j in range(a0 + block, n_rows, seg_len):
+            full.append([a0, a_end, j, min(j + seg_len, n_rows)])
+    mine = full[rank::world] + diag[rank::world]
+    return mine, sum(j1 - j0 for _, _, j0, j1 in mine)
+
+
+def test_the_dense_matrix_is_the_single_column_from_row_0(tmp_path):
+    """plan_sparse_segments over the column {0, n} is what the dense container's own loop planned."""
+    import subprocess
+    exe = tmp_path / "arena_plan"
+    build = gen.build_driver(exe)
+    assert build.returncode == 0, build.stderr
+    run = subprocess.run([str(exe), "--single-column"], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0, run.stderr[-3000:]
+    doc = json.loads(run.stdout)
+    cases = [(n, seg_len, world, rank) for n in (1, 2, 128, 129, 600) for seg_len in (256, 100) for world in (1, 3)
+             for rank in range(world)]
+    assert len(doc) == len(cases)
+    for n, seg_len, world, rank in cases:
+        segs, row_sum = _dense_segments(n, seg_len, rank, world)
+        assert doc[f"n{n}/len{seg_len}/w{world}/r{rank}"] == {"segs": segs, "row_sum": [row_sum]}, (n, seg_len, world, rank)
+    assert doc["n1/len256/w1/r0"]["segs"] == [] and len(doc["n600/len100/w1/r0"]["segs"]) == 13 + 5
+
+
 def test_planners_under_asan_ubsan(tmp_path):
     exe = tmp_path / "arena_plan_sanitized"
     build = gen.build_driver(exe, sanitize=True)

@@ -9,8 +9,7 @@ static int ensure_bitwave(storm_hip_ctx_t* ctx, const std::vector<RowRange>& ran
     const BitstreamRequest rq = bitstream_request_of(ctx, ranges, n_kslices, shard_rank, shard_count, pitch);
     BitstreamRequest key = rq;
     key.ranges_hash ^= 0x77aa77aa77aa77aaull;   // (the same plan in another device layout than ensure_bitstream's)
-    if (ctx->d_bitfirst && ctx->bit_key == key) return STORM_HIP_OK;
-    ctx->bit_key.reset();
+    if (ctx->bitfirst.holds(key)) return STORM_HIP_OK;
     BitstreamPlan plan;
     build_bitstream(rq, ranges, plan);
     if (!ranges.empty() && ranges.back().r1 * pitch / 64 + n_kslices + 4 * pitch >= (1ull << 30)) {
@@ -44,17 +43,13 @@ static int ensure_bitwave(storm_hip_ctx_t* ctx, const std::vector<RowRange>& ran
         set_error("K2w: a wave of %u stages exceeds the exact range of its accumulators", longest);
         return STORM_HIP_EINVAL;
     }
-    std::vector<uint32_t> packed(first);
+    std::vector<uint32_t> packed(first);   // (never empty: first[4 G] is there)
     packed.insert(packed.end(), words.begin(), words.end());
-    const size_t bytes = std::max<size_t>(packed.size(), 1) * sizeof(uint32_t);
-    if (int rc = ctx->d_bitfirst.ensure(bytes, "K2w: the waves' stage words")) return rc;
-    STORM_HIP_TRY(hipMemcpyAsync(ctx->d_bitfirst, packed.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-    STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (int rc = ctx->bitfirst.put(ctx, key, packed.data(), packed.size(), "K2w: the waves' stage words")) return rc;
     ctx->n_bit_groups = plan.groups;
     ctx->bit_stages = words.size();
     ctx->bit_max_stages = longest;
     ctx->n_bit_segs = (uint32_t)plan.segs.size();
-    ctx->bit_key = key;
     return STORM_HIP_OK;
 }
 
@@ -67,8 +62,7 @@ int launch_pairw_bitwave(storm_hip_ctx_t* ctx, const uint64_t* X, uint64_t pitch
         return STORM_HIP_EINVAL;
     }
     if (int rc = ensure_bitwave(ctx, ranges, n_kslices, shard_rank, shard_count, pitch)) return rc;
-    ctx->n_items = 0;
-    ctx->items_key = std::monostate{};
+    ctx->items.forget();
     ctx->last_info[0] = ctx->n_bit_groups;
     ctx->last_info[1] = ctx->bit_max_stages;
     ctx->last_info[2] = 1;
@@ -80,7 +74,7 @@ int launch_pairw_bitwave(storm_hip_ctx_t* ctx, const uint64_t* X, uint64_t pitch
     const uint32_t G = ctx->n_bit_groups, cus = (uint32_t)std::max(1, ctx->n_cus);
     int ring = ctx->k2_wave_ring;
     if (ring == 0) ring = G <= cus ? 8 : G <= 2 * cus ? 4 : 3;
-    const uint32_t* first = ctx->d_bitfirst.d;
+    const uint32_t* first = ctx->bitfirst.recs();
     const uint32_t* words = first + 4 * (size_t)G + 1;
     kernel_time_mark(ctx);
 #define STORM_BW_LAUNCH(R)                                                                                      \
