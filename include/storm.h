@@ -444,6 +444,32 @@ int STORM_dosage_pairw_nobs_device(STORM_dosage_t* h, uint32_t* d_out, uint64_t 
 int STORM_dosage_pairw_corr_complete(STORM_dosage_t* h, int measure, float* out, uint64_t out_rows, uint64_t out_ld);
 int STORM_dosage_pairw_corr_complete_device(STORM_dosage_t* h, int measure, float* d_out, uint64_t out_rows, uint64_t out_ld);
 
+/* r / r^2 between TWO dosage containers: every row i of a against every row j of b at out[i * out_ld + j] — a list of index
+ * variants against a panel (PLINK's --r2 --ld-snp-list ... inter-chr), one chromosome against another, a new batch
+ * against what is loaded — for 6 n_a n_b row-pair products where the triangle of the stacked container costs 3 (n_a + n_b)^2.
+ *   STORM_dosage_square_corr            STORM_dosage_pairw_corr's formula with P = sum_s a_i[s] b_j[s] and s, q of each row
+ *                                       taken in its own container (S = n_samples; 3 is an ordinary value); NaN
+ *                                       (0x7FC00000) when either row is constant
+ *   STORM_dosage_square_nobs            N(i, j): the samples that neither a_i nor b_j has as 3 (STORM_DOSAGE_MISSING) (uint32)
+ *   STORM_dosage_square_corr_complete   STORM_dosage_pairw_corr_complete's formula over the samples both rows have; on rows
+ *                                       without a 3 the same bits as STORM_dosage_square_corr. Device scratch: about
+ *                                       5 n_a n_b uint32 and three copies of the rows of each container, kept by the
+ *                                       device context (nothing bounds it by panels of b: cut b into several containers)
+ * Each float is bit-identical to the pairw call's for the same two rows in one container. Output conventions, argument
+ * checks and return codes are STORM_dosage_square_dot's: every entry (i, j), i < a's rows, j < b's rows, is written by the
+ * host and the _device forms alike and nothing outside that window is touched; out_rows >= a's rows and out_ld >= b's rows
+ * (-4 otherwise, nothing written); unequal sample counts or an unknown measure: -3, STORM_hip_error says which; an empty
+ * container: 0, nothing written; a may be b; -1 NULL handle, -2 NULL out, -5 several device slots in view. */
+int STORM_dosage_square_corr(STORM_dosage_t* a, STORM_dosage_t* b, int measure, float* out, uint64_t out_rows, uint64_t out_ld);
+int STORM_dosage_square_corr_device(STORM_dosage_t* a, STORM_dosage_t* b, int measure, float* d_out, uint64_t out_rows,
+                                    uint64_t out_ld);
+int STORM_dosage_square_nobs(STORM_dosage_t* a, STORM_dosage_t* b, uint32_t* out, uint64_t out_rows, uint64_t out_ld);
+int STORM_dosage_square_nobs_device(STORM_dosage_t* a, STORM_dosage_t* b, uint32_t* d_out, uint64_t out_rows, uint64_t out_ld);
+int STORM_dosage_square_corr_complete(STORM_dosage_t* a, STORM_dosage_t* b, int measure, float* out, uint64_t out_rows,
+                                      uint64_t out_ld);
+int STORM_dosage_square_corr_complete_device(STORM_dosage_t* a, STORM_dosage_t* b, int measure, float* d_out, uint64_t out_rows,
+                                             uint64_t out_ld);
+
 /* The four pairwise calls of the dosage container for the pairs within max_lag rows of each other only — PLINK's --r / --r2
  * as it is run on genotype files: within a window (--ld-window), never all-vs-all. The layout is STORM_pairw_lag_matrix's:
  * with n the rows held and L = min(max_lag, n - 1), `out` holds out_rows x out_ld entries (out_rows >= n, out_ld >= L) and

@@ -393,6 +393,38 @@ int storm_hip_pairw_dosage_corr_complete_device(storm_hip_ctx_t* ctx, const stor
 int storm_hip_pairw_dosage_corr_complete(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_samples,
                                          float* h_out, uint64_t ld);
 
+/* ---- r / r^2 and N of the rectangle of two dosage matrices ---------------------------------------------------------
+ * The three correlation calls above for EVERY row i of A against every row j of B (a list of index variants against a
+ * panel: PLINK's --r2 --ld-snp-list ... inter-chr), entry out[i * ld + j], ld >= b's rows; each row's sums are taken in
+ * its own matrix. A may be B.
+ * _square_dosage_corr[_device]: 3 is an ordinary value. The dot products (storm_hip_square_dosage_matrix_device), both
+ *   matrices' row sums, then dosage_square_finish_kernel in place: _pairw_dosage_corr's formula and bits for the pair.
+ * _square_dosage_nobs[_device], _square_dosage_corr_complete[_device]: code 3 means MISSING, as in the block above. Both
+ *   matrices are split into G, H and M (once when A is B); _nobs is M_a x M_b; _corr_complete is six n_a x n_b products on
+ *   K2h in three launches — G_a x G_b into the output, [G_a ; H_a] x M_b and M_a x [G_b ; H_b ; M_b] into scratch — and
+ *   dosage_square_complete_finish_kernel in place: _pairw_dosage_corr_complete's formula and bits for the pair, and on rows
+ *   without a 3 _square_dosage_corr's. Device scratch held by the context: about 5 n_a n_b uint32 of sums and three copies
+ *   of the rows of each matrix (nothing bounds it by panels of B: the caller cuts B); an allocation that fails returns
+ *   STORM_HIP_ENOMEM with the buffer named.
+ * n_samples, the measures and the refusals as _square_dosage_matrix and _pairw_dosage_corr: STORM_HIP_EINVAL for a NULL
+ * argument, rows of different widths, ld < b's rows, an unknown measure, n_samples that does not match the row width,
+ * rows of more than 2^24 values, rows beyond the reach of K2h, of the split (65408 rows) or of the finishing pass's launch
+ * grid. An empty matrix: STORM_HIP_OK, nothing written. _device: complete on return, nothing outside the n_a x n_b window
+ * is written; host forms write the window alone. Last-pass report: STORM_HIP_RAN_TILES_OUT (| STORM_HIP_RAN_SIMILARITY for
+ * the correlations), [1] = n_a n_b n_words (_corr_complete: 6 times that). */
+int storm_hip_square_dosage_corr_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b, int measure,
+                                        uint64_t n_samples, float* d_out, uint64_t ld);
+int storm_hip_square_dosage_corr(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b, int measure,
+                                 uint64_t n_samples, float* h_out, uint64_t ld);
+int storm_hip_square_dosage_nobs_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b,
+                                        uint64_t n_samples, uint32_t* d_out, uint64_t ld);
+int storm_hip_square_dosage_nobs(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b, uint64_t n_samples,
+                                 uint32_t* h_out, uint64_t ld);
+int storm_hip_square_dosage_corr_complete_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b,
+                                                 int measure, uint64_t n_samples, float* d_out, uint64_t ld);
+int storm_hip_square_dosage_corr_complete(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b, int measure,
+                                          uint64_t n_samples, float* h_out, uint64_t ld);
+
 /* ---- dosage matrices in the lag layout: PLINK --r / --r2 within a window (--ld-window) ---------------------------
  * The calls of the two blocks above for the pairs within max_lag rows of each other, in the lag layout of
  * storm_hip_pairw_lag_matrix_device: with L = min(max_lag, n_rows - 1), entry out[i * ld + (j - i - 1)] is the pair

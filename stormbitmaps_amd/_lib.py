@@ -138,6 +138,12 @@ SIGNATURES = {
     "storm_hip_dosage_square_plan": (C.c_int, [u64, u64, u32, u32, C.c_int, C.c_int, C.c_int, vp, u64, vp]),
     "storm_hip_square_dosage_matrix_device": (C.c_int, [vp, vp, vp, vp, u64]),
     "storm_hip_square_dosage_matrix": (C.c_int, [vp, vp, vp, vp, u64]),
+    "storm_hip_square_dosage_corr_device": (C.c_int, [vp, vp, vp, C.c_int, u64, vp, u64]),
+    "storm_hip_square_dosage_corr": (C.c_int, [vp, vp, vp, C.c_int, u64, vp, u64]),
+    "storm_hip_square_dosage_nobs_device": (C.c_int, [vp, vp, vp, u64, vp, u64]),
+    "storm_hip_square_dosage_nobs": (C.c_int, [vp, vp, vp, u64, vp, u64]),
+    "storm_hip_square_dosage_corr_complete_device": (C.c_int, [vp, vp, vp, C.c_int, u64, vp, u64]),
+    "storm_hip_square_dosage_corr_complete": (C.c_int, [vp, vp, vp, C.c_int, u64, vp, u64]),
     "storm_hip_dosage_row_missing": (C.c_int, [vp, vp, u64, vp]),
     "storm_hip_pairw_dosage_nobs_device": (C.c_int, [vp, vp, u64, vp, u64]),
     "storm_hip_pairw_dosage_nobs": (C.c_int, [vp, vp, u64, vp, u64]),
@@ -248,6 +254,12 @@ SIGNATURES = {
     "STORM_dosage_pairw_corr_device": (C.c_int, [vp, C.c_int, vp, u64, u64]),
     "STORM_dosage_square_dot": (C.c_int, [vp, vp, vp, u64, u64]),
     "STORM_dosage_square_dot_device": (C.c_int, [vp, vp, vp, u64, u64]),
+    "STORM_dosage_square_corr": (C.c_int, [vp, vp, C.c_int, vp, u64, u64]),
+    "STORM_dosage_square_corr_device": (C.c_int, [vp, vp, C.c_int, vp, u64, u64]),
+    "STORM_dosage_square_nobs": (C.c_int, [vp, vp, vp, u64, u64]),
+    "STORM_dosage_square_nobs_device": (C.c_int, [vp, vp, vp, u64, u64]),
+    "STORM_dosage_square_corr_complete": (C.c_int, [vp, vp, C.c_int, vp, u64, u64]),
+    "STORM_dosage_square_corr_complete_device": (C.c_int, [vp, vp, C.c_int, vp, u64, u64]),
     "STORM_dosage_row_missing": (C.c_int, [vp, vp]),
     "STORM_dosage_pairw_nobs": (C.c_int, [vp, vp, u64, u64]),
     "STORM_dosage_pairw_nobs_device": (C.c_int, [vp, vp, u64, u64]),

@@ -257,7 +257,8 @@ def _window_args(n: int, max_lag: Optional[int], pos, max_dist: Optional[float])
 class StormDosage:
     """STORM_dosage_t (storm.h, extension): rows of n_samples 2-bit dosages (0 / 1 / 2 copies of an allele per sample; 3 is an
     ordinary value), their per-pair dot products and genotype correlations (PLINK --r / --r2) on the device. In
-    row_missing, pairw_nobs and pairw_corr_complete — and only there — the value 3 means "missing"."""
+    row_missing, pairw_nobs, pairw_corr_complete, their lag forms, square_nobs and square_corr(complete=True) — and only there —
+    the value 3 means "missing"."""
 
     def __init__(self, n_samples: int):
         self._lib = _lib.load()
@@ -335,21 +336,37 @@ class StormDosage:
         container against every row of `other` (the same number of samples; 3 is an ordinary value).
         device=: a 2-D torch tensor of 32-bit entries in device memory that receives the rectangle instead
         (STORM_dosage_square_dot_device); returns None then."""
+        return self._square("STORM_dosage_square_dot", np.uint32, other, device)
+
+    def _square(self, name: str, dtype, other: "StormDosage", device, *args):
+        """one statistic of the rectangle with `other` (args: what the C call takes between the handles and the output)"""
         na, nb = self.n_rows, other.n_rows
         if device is not None:
             if device.dim() != 2 or device.element_size() != 4 or device.stride(1) != 1 or not device.is_cuda:
                 raise ValueError("device=: a 2-D tensor of 32-bit entries in device memory with contiguous rows")
             if device.shape[0] < na or device.shape[1] < nb:
                 raise ValueError(f"device=: a tensor of {tuple(device.shape)} cannot hold {na} x {nb} entries")
-            self._check("STORM_dosage_square_dot_device",
-                        int(self._lib.STORM_dosage_square_dot_device(self._h, other._h, C.c_void_p(device.data_ptr()),
-                                                                     int(device.shape[0]), int(device.stride(0)))))
+            self._check(name + "_device", int(getattr(self._lib, name + "_device")(self._h, other._h, *args, C.c_void_p(device.data_ptr()),
+                                                                                   int(device.shape[0]), int(device.stride(0)))))
             return None
-        out = np.zeros((na, nb), dtype=np.uint32)
-        self._check("STORM_dosage_square_dot",
-                    int(self._lib.STORM_dosage_square_dot(self._h, other._h, _ptr(out) if out.size else _ptr(np.zeros(1, np.uint32)),
-                                                          na, nb)))
+        out = np.zeros((na, nb), dtype=dtype)
+        self._check(name, int(getattr(self._lib, name)(self._h, other._h, *args, _ptr(out) if out.size else _ptr(np.zeros(1, dtype)),
+                                                       na, nb)))
         return out
+
+    def square_corr(self, other: "StormDosage", measure: str = "r2", complete: bool = False, device=None):
+        """STORM_dosage_square_corr[_complete]: [n_rows, other.n_rows] float32, entry (i, j) = the Pearson correlation ("r") or
+        its square ("r2") of row i of this container and row j of `other` (the same number of samples) — a list of index
+        variants against a panel — with pairw_corr's bits for the two rows; NaN against a constant row. complete=True: over the
+        samples both rows have (value 3 = missing), pairw_corr_complete's bits. device=: as square_dot
+        (STORM_dosage_square_corr[_complete]_device); every entry of the rectangle is written in both forms."""
+        return self._square("STORM_dosage_square_corr_complete" if complete else "STORM_dosage_square_corr", np.float32, other, device,
+                            DOSAGE_MEASURES[measure])
+
+    def square_nobs(self, other: "StormDosage", device=None):
+        """STORM_dosage_square_nobs: [n_rows, other.n_rows] uint32, entry (i, j) = the samples that neither row i of this
+        container nor row j of `other` is missing (value 3) at. device=: as square_dot (STORM_dosage_square_nobs_device)."""
+        return self._square("STORM_dosage_square_nobs", np.uint32, other, device)
 
     def row_missing(self):
         """STORM_dosage_row_missing: the samples of every row that are missing (value 3), [n_rows] uint32, counted on the

@@ -1,4 +1,4 @@
-/* storm_dosage_internal.h — the dosage container as storm_dosage.c and storm_dosage_complete.c share it. */
+/* storm_dosage_internal.h — the dosage container as storm_dosage.c and the storm_dosage_*.c units beside it share it. */
 #pragma once
 #include <stdint.h>
 

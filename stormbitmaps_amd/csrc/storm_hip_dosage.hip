@@ -9,6 +9,9 @@
 // the value is 2) and M (1 where present) — K2h multiplies the triangles of G and of M and the rectangle [G ; H] x M, and
 // dosage_complete_finish_kernel turns the five sums of a pair into r / r^2 over the samples both rows have (DESIGN.md §4,
 // "K2h, dosage form with missing genotypes").
+// The rectangle of two matrices (the *_square_dosage_* calls): K2h over n_a x n_b; for r / r^2 both matrices' row sums and
+// dosage_square_finish_kernel, or both matrices' splits, six products in three launches and
+// dosage_square_complete_finish_kernel ("K2h, dosage form: the rectangle of two containers").
 // The lag layout (the *_lag_dosage_* calls: the pairs within max_lag rows of each other, an n x L matrix): K2h in its lag and
 // dosage form (tile128_kernel<true, 2>: launch_pairw_lag_dosage_matrix), dosage_finish_lag_kernel over it, and for missing
 // genotypes dosage_split_interleaved_kernel — G, H and M as ONE matrix of 3 n rows — one launch at lag 3 L + 2 into a scratch
@@ -330,19 +333,23 @@ static int dosage_corr_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m,
 // n_rows up to the next multiple of 128 rows each (zero rows behind n_rows), G and H adjacent so that [G ; H] is one matrix
 // of rows128 + n_rows rows. Queued.
 struct DosageSplit {
-    storm_hip_matrix_s g, m, gh;   // views into the scratch (never destroyed)
+    storm_hip_matrix_s g, m, gh, ghm;   // views into the scratch (never destroyed)
     uint64_t rows128;
 };
-static int dosage_split_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* x, uint64_t n_samples, DosageSplit* out) {
-    const uint64_t n = x->n_rows, rows128 = (n + kThTile - 1) / kThTile * kThTile, stride = x->stride_words;
-    const uint64_t words = rows128 * stride;
+// the words of one matrix of the split (rows128 rows of the source's stride); refuses what the split's launch grid cannot hold
+static int dosage_split_words(const storm_hip_matrix_s* x, uint64_t* words) {
+    const uint64_t rows128 = (x->n_rows + kThTile - 1) / kThTile * kThTile;
     if (rows128 > 65535u) {
-        set_error("dosage rows with missing genotypes: %llu rows exceed the split's launch grid", (unsigned long long)n);
+        set_error("dosage rows with missing genotypes: %llu rows exceed the split's launch grid", (unsigned long long)x->n_rows);
         return STORM_HIP_EINVAL;
     }
-    if (int rc = ctx->d_dosage_rows.ensure(3 * words * sizeof(uint64_t), "dosage rows with missing genotypes: the split operands G, H, M"))
-        return rc;
-    uint64_t* const G = ctx->d_dosage_rows.d;
+    *words = rows128 * x->stride_words;
+    return STORM_HIP_OK;
+}
+// the split of x at G (3 x dosage_split_words words of ctx->d_dosage_rows, already there), queued
+static int dosage_split_at(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* x, uint64_t n_samples, uint64_t* G, DosageSplit* out) {
+    const uint64_t n = x->n_rows, rows128 = (n + kThTile - 1) / kThTile * kThTile, stride = x->stride_words;
+    const uint64_t words = rows128 * stride;
     hipLaunchKernelGGL(dosage_split_missing_kernel, dim3((uint32_t)((stride + 255u) / 256u), (uint32_t)rows128), dim3(256), 0,
                        ctx->stream, x->d, stride, n, rows128, x->n_words, n_samples, G, G + words, G + 2 * words);
     STORM_HIP_TRY(hipGetLastError());
@@ -358,8 +365,16 @@ static int dosage_split_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* x
     out->rows128 = rows128;
     out->g = view(G, n, rows128);
     out->gh = view(G, rows128 + n, 2 * rows128);
+    out->ghm = view(G, 2 * rows128 + n, 3 * rows128);   // (the rectangle of two containers: [G ; H ; M] as ONE operand)
     out->m = view(G + 2 * words, n, rows128);
     return STORM_HIP_OK;
+}
+static int dosage_split_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* x, uint64_t n_samples, DosageSplit* out) {
+    uint64_t words = 0;
+    if (int rc = dosage_split_words(x, &words)) return rc;
+    if (int rc = ctx->d_dosage_rows.ensure(3 * words * sizeof(uint64_t), "dosage rows with missing genotypes: the split operands G, H, M"))
+        return rc;
+    return dosage_split_at(ctx, x, n_samples, ctx->d_dosage_rows.d, out);
 }
 
 // N(i, j) for i < j at d_out (pitch ld): the split, then the triangle of M. Queued.
@@ -452,6 +467,196 @@ static int check_square(const char* who, const storm_hip_matrix_s* a, const stor
         set_error("%s: rows of %u words hold more than 2^24 values", who, a->n_words);
         return STORM_HIP_EINVAL;
     }
+    return STORM_HIP_OK;
+}
+
+// ---- the rectangle of two matrices: r / r^2 and N of every row of A against every row of B ("K2h, dosage
+// form: the rectangle of two containers") ----
+// dosage_finish_kernel without the triangle test, over an n_a x n_b matrix of dot products in place: s and q of the tile's
+// rows of A through the LDS, those of a lane's 4 columns of B in registers. Entries outside the n_a x n_b window — the pitch
+// columns, rows beyond n_a — are neither read nor written; vec: 16-byte aligned base and ld a multiple of 4, and then a
+// lane whose 4 columns all exist takes them in one 128-bit access.
+__global__ __launch_bounds__(256) void dosage_square_finish_kernel(uint32_t* __restrict__ io, uint64_t ld, uint64_t n_a, uint64_t n_b,
+                                                                   const uint32_t* __restrict__ a_sum, const uint32_t* __restrict__ a_sq,
+                                                                   const uint32_t* __restrict__ b_sum, const uint32_t* __restrict__ b_sq,
+                                                                   int measure, uint64_t n_samples, int vec) {
+    const uint64_t row0 = (uint64_t)blockIdx.y * kDosTileRows, col0 = (uint64_t)blockIdx.x * kDosTileCols;
+    __shared__ uint32_t s_sum[kDosTileRows], s_sq[kDosTileRows];
+    if (threadIdx.x < kDosTileRows) {
+        const bool in = row0 + threadIdx.x < n_a;
+        s_sum[threadIdx.x] = in ? a_sum[row0 + threadIdx.x] : 0u;
+        s_sq[threadIdx.x] = in ? a_sq[row0 + threadIdx.x] : 0u;
+    }
+    const uint64_t c0 = col0 + (threadIdx.x & 63u) * 4u;
+    uint32_t bs[4], bq[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        bs[k] = c0 + k < n_b ? b_sum[c0 + k] : 0u;
+        bq[k] = c0 + k < n_b ? b_sq[c0 + k] : 0u;
+    }
+    __syncthreads();
+    const bool whole = vec && c0 + 4 <= n_b;
+    const uint32_t wave = threadIdx.x >> 6;
+    for (uint32_t r = wave; r < kDosTileRows; r += 4 * kDosUnroll) {
+        uint4 v[kDosUnroll];
+#pragma unroll
+        for (int u = 0; u < kDosUnroll; ++u) {   // the loads of kDosUnroll rows leave before the first divide
+            const uint64_t i = row0 + r + 4u * u;
+            if (whole && i < n_a) v[u] = *reinterpret_cast<const uint4*>(io + i * ld + c0);
+        }
+#pragma unroll
+        for (int u = 0; u < kDosUnroll; ++u) {
+            const uint64_t i = row0 + r + 4u * u;
+            if (i >= n_a) continue;
+            const uint32_t as = s_sum[r + 4u * u], aq = s_sq[r + 4u * u];
+            uint32_t* const p = io + i * ld + c0;
+            if (whole) {
+                uint4 w;
+                w.x = dosage_corr_bits(v[u].x, as, aq, bs[0], bq[0], measure, n_samples);
+                w.y = dosage_corr_bits(v[u].y, as, aq, bs[1], bq[1], measure, n_samples);
+                w.z = dosage_corr_bits(v[u].z, as, aq, bs[2], bq[2], measure, n_samples);
+                w.w = dosage_corr_bits(v[u].w, as, aq, bs[3], bq[3], measure, n_samples);
+                *reinterpret_cast<uint4*>(p) = w;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (c0 + k < n_b) p[k] = dosage_corr_bits(p[k], as, aq, bs[k], bq[k], measure, n_samples);
+            }
+        }
+    }
+}
+
+// The finishing pass of the pairwise-complete correlation over an n_a x n_b matrix of dot products P = G_a G_b^T, in place
+// (uint32 -> float). All six sums of entry (i, j) lie at (i, j) of their matrices — `ghm` = [G_a ; H_a] x M_b (pitch ld_ghm:
+// sx at row i, H_a M_b at row h_row0 + i) and `mghm` = M_a x [G_b ; H_b ; M_b] (pitch ld_mghm: sy at column j, M_a H_b at
+// h_col0 + j, N at m_col0 + j) — so there is no transposed tile and no LDS: wave w takes rows w, w + 4, ... of a 64 x 64
+// tile, lane = column, every read one run along j. Entries outside the n_a x n_b window are neither read nor written.
+__global__ __launch_bounds__(256) void dosage_square_complete_finish_kernel(uint32_t* __restrict__ io, uint64_t ld, uint64_t n_a,
+                                                                            uint64_t n_b, const uint32_t* __restrict__ ghm,
+                                                                            uint64_t ld_ghm, uint64_t h_row0,
+                                                                            const uint32_t* __restrict__ mghm, uint64_t ld_mghm,
+                                                                            uint64_t h_col0, uint64_t m_col0, int measure) {
+    const uint64_t row0 = (uint64_t)blockIdx.y * kDosCompleteTile, j = (uint64_t)blockIdx.x * kDosCompleteTile + (threadIdx.x & 63u);
+    if (j >= n_b) return;
+    for (uint32_t a = threadIdx.x >> 6; a < kDosCompleteTile; a += 4 * kDosUnroll) {
+        uint32_t P[kDosUnroll], N[kDosUnroll], sx[kDosUnroll], sy[kDosUnroll], hx[kDosUnroll], hy[kDosUnroll];
+#pragma unroll
+        for (int u = 0; u < kDosUnroll; ++u) {   // the loads of kDosUnroll rows leave before the first divide
+            const uint64_t i = row0 + a + 4u * u;
+            if (i >= n_a) continue;
+            const uint32_t* const mrow = mghm + i * ld_mghm;
+            P[u] = io[i * ld + j];
+            sx[u] = ghm[i * ld_ghm + j];
+            hx[u] = ghm[(h_row0 + i) * ld_ghm + j];
+            sy[u] = mrow[j];
+            hy[u] = mrow[h_col0 + j];
+            N[u] = mrow[m_col0 + j];
+        }
+#pragma unroll
+        for (int u = 0; u < kDosUnroll; ++u) {
+            const uint64_t i = row0 + a + 4u * u;
+            if (i < n_a) io[i * ld + j] = dosage_corr_complete_bits(P[u], N[u], sx[u], sy[u], sx[u] + 2u * hx[u], sy[u] + 2u * hy[u], measure);
+        }
+    }
+}
+
+// the sums of both matrices' rows into the context's row-count scratch, 2 (n_a + n_b) words: A's s and q, then B's; queued
+struct SquareSums {
+    const uint32_t *a_sum, *a_sq, *b_sum, *b_sq;
+};
+static int dosage_square_sums_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, SquareSums* out) {
+    const uint64_t na = a->n_rows, nb = b->n_rows;
+    if (int rc = ctx->d_counts.ensure(2 * (na + nb) * sizeof(uint32_t), "square_dosage_corr: the row-sum scratch")) return rc;
+    uint32_t* const d = ctx->d_counts.d;
+    hipLaunchKernelGGL(dosage_row_sums_kernel, dim3((uint32_t)((na + kWaves - 1) / kWaves)), dim3(kThreads), 0, ctx->stream, a->d,
+                       a->stride_words, na, a->n_words, d, d + na);
+    hipLaunchKernelGGL(dosage_row_sums_kernel, dim3((uint32_t)((nb + kWaves - 1) / kWaves)), dim3(kThreads), 0, ctx->stream, b->d,
+                       b->stride_words, nb, b->n_words, d + 2 * na, d + 2 * na + nb);
+    STORM_HIP_TRY(hipGetLastError());
+    *out = SquareSums{d, d + na, d + 2 * na, d + 2 * na + nb};
+    return STORM_HIP_OK;
+}
+
+// r / r^2 of every row of A against every row of B at d_io (pitch ld), 3 an ordinary value: the dot products, both
+// matrices' row sums, then the finish in place. All queued.
+static int square_dosage_corr_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, int measure,
+                                     uint64_t n_samples, uint32_t* d_io, uint64_t ld) {
+    const uint64_t na = a->n_rows, nb = b->n_rows;
+    const uint64_t tiles_x = (nb + kDosTileCols - 1) / kDosTileCols, tiles_y = (na + kDosTileRows - 1) / kDosTileRows;
+    if (tiles_y > 65535u || tiles_x > 0x7fffffffu) {
+        set_error("square_dosage_corr: %llu x %llu entries exceed the finishing pass's launch grid", (unsigned long long)na,
+                  (unsigned long long)nb);
+        return STORM_HIP_EINVAL;
+    }
+    if (int rc = launch_square_dosage_matrix(ctx, a, b, d_io, ld)) return rc;
+    SquareSums s;
+    if (int rc = dosage_square_sums_queued(ctx, a, b, &s)) return rc;
+    const int vec = reinterpret_cast<uintptr_t>(d_io) % 16 == 0 && ld % 4 == 0;
+    hipLaunchKernelGGL(dosage_square_finish_kernel, dim3((uint32_t)tiles_x, (uint32_t)tiles_y), dim3(256), 0, ctx->stream, d_io, ld, na,
+                       nb, s.a_sum, s.a_sq, s.b_sum, s.b_sq, measure, n_samples, vec);
+    STORM_HIP_TRY(hipGetLastError());
+    ctx->pass_report[0] |= STORM_HIP_RAN_SIMILARITY;   // ([1]: n_a n_b n_words, the launch's own)
+    return STORM_HIP_OK;
+}
+
+// The splits of both matrices side by side in ctx->d_dosage_rows (A's three matrices, then B's; one split when b is a),
+// queued. The buffer is sized for both before either kernel starts: growing it drops what it held.
+static int dosage_split_pair_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, uint64_t n_samples,
+                                    DosageSplit* sa, DosageSplit* sb) {
+    uint64_t words_a = 0, words_b = 0;
+    if (int rc = dosage_split_words(a, &words_a)) return rc;
+    if (b != a)
+        if (int rc = dosage_split_words(b, &words_b)) return rc;
+    if (int rc = ctx->d_dosage_rows.ensure(3 * (words_a + words_b) * sizeof(uint64_t),
+                                           "dosage rows with missing genotypes: the split operands G, H, M of two matrices"))
+        return rc;
+    if (int rc = dosage_split_at(ctx, a, n_samples, ctx->d_dosage_rows.d, sa)) return rc;
+    if (b == a) {
+        *sb = *sa;
+        return STORM_HIP_OK;
+    }
+    return dosage_split_at(ctx, b, n_samples, ctx->d_dosage_rows.d + 3 * words_a, sb);
+}
+
+// N(i, j) of every row of A against every row of B at d_out (pitch ld): the splits, then M_a x M_b. Queued.
+static int square_dosage_nobs_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, uint64_t n_samples,
+                                     uint32_t* d_out, uint64_t ld) {
+    DosageSplit sa, sb;
+    if (int rc = dosage_split_pair_queued(ctx, a, b, n_samples, &sa, &sb)) return rc;
+    return launch_square_dosage_matrix(ctx, &sa.m, &sb.m, d_out, ld);   // ([1]: n_a n_b n_words)
+}
+
+// The pairwise-complete correlation of every row of A against every row of B at d_io (pitch ld): the splits; six n_a x n_b
+// products on K2h in three launches — P = G_a x G_b straight into d_io, [G_a ; H_a] x M_b (rows [0, n_a): sx, rows
+// [rows128_a, rows128_a + n_a): H_a M_b) and M_a x [G_b ; H_b ; M_b] (columns [0, n_b): sy, from rows128_b: M_a H_b, from
+// 2 rows128_b: N; the operand's zero rows between the three cost up to 127 columns each) into ctx->d_dosage_sums — then the
+// finish in place. Scratch: about 5 n_a n_b uint32 of sums and both splits. All queued.
+static int square_dosage_corr_complete_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b,
+                                              int measure, uint64_t n_samples, uint32_t* d_io, uint64_t ld) {
+    const uint64_t na = a->n_rows, nb = b->n_rows;
+    const uint64_t tiles_x = (nb + kDosCompleteTile - 1) / kDosCompleteTile, tiles_y = (na + kDosCompleteTile - 1) / kDosCompleteTile;
+    if (tiles_y > 65535u || tiles_x > 0x7fffffffu) {
+        set_error("square_dosage_corr_complete: %llu x %llu entries exceed the finishing pass's launch grid", (unsigned long long)na,
+                  (unsigned long long)nb);
+        return STORM_HIP_EINVAL;
+    }
+    DosageSplit sa, sb;
+    if (int rc = dosage_split_pair_queued(ctx, a, b, n_samples, &sa, &sb)) return rc;
+    const uint64_t ld_ghm = (nb + 3u) / 4u * 4u, ld_mghm = 2 * sb.rows128 + ld_ghm;
+    const uint64_t ghm_words = (sa.rows128 + na) * ld_ghm;
+    if (int rc = ctx->d_dosage_sums.ensure((ghm_words + na * ld_mghm) * sizeof(uint32_t),
+                                           "square_dosage_corr_complete: the sums [G_a ; H_a] M_b^T and M_a [G_b ; H_b ; M_b]^T"))
+        return rc;
+    uint32_t* const d_ghm = ctx->d_dosage_sums.d;
+    uint32_t* const d_mghm = d_ghm + ghm_words;
+    if (int rc = launch_square_dosage_matrix(ctx, &sa.g, &sb.g, d_io, ld)) return rc;
+    if (int rc = launch_square_dosage_matrix(ctx, &sa.gh, &sb.m, d_ghm, ld_ghm)) return rc;
+    if (int rc = launch_square_dosage_matrix(ctx, &sa.m, &sb.ghm, d_mghm, ld_mghm)) return rc;
+    hipLaunchKernelGGL(dosage_square_complete_finish_kernel, dim3((uint32_t)tiles_x, (uint32_t)tiles_y), dim3(256), 0, ctx->stream, d_io,
+                       ld, na, nb, d_ghm, ld_ghm, sa.rows128, d_mghm, ld_mghm, sb.rows128, 2 * sb.rows128, measure);
+    STORM_HIP_TRY(hipGetLastError());
+    ctx->pass_report[0] = STORM_HIP_RAN_TILES_OUT | STORM_HIP_RAN_SIMILARITY;
+    ctx->pass_report[1] = 6 * na * nb * a->n_words;
     return STORM_HIP_OK;
 }
 
@@ -819,6 +1024,31 @@ static int square_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* 
                            [&](uint32_t* d, uint64_t d_ld) { return launch_square_dosage_matrix(ctx, a, b, d, d_ld); });
 }
 
+// r / r^2 (complete: over the samples both rows have) and N of the rectangle: every entry is written in both forms
+static int square_dosage_corr(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, int measure,
+                              uint64_t n_samples, bool complete, float* out, uint64_t ld, bool host) {
+    if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+    const char* const who = complete ? "square_dosage_corr_complete" : "square_dosage_corr";
+    if (int rc = check_square(who, a, b, out, ld)) return rc;
+    if (int rc = check_corr(who, a, measure, n_samples)) return rc;
+    if (a->n_rows == 0 || b->n_rows == 0) return STORM_HIP_OK;
+    return pair_matrix_out(ctx, complete ? "square_dosage_corr_complete: the output" : "square_dosage_corr: the output", a->n_rows,
+                           b->n_rows, out, ld, host, false, true, [&](uint32_t* d, uint64_t d_ld) {
+                               return complete ? square_dosage_corr_complete_queued(ctx, a, b, measure, n_samples, d, d_ld)
+                                               : square_dosage_corr_queued(ctx, a, b, measure, n_samples, d, d_ld);
+                           });
+}
+
+static int square_dosage_nobs(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, uint64_t n_samples,
+                              uint32_t* out, uint64_t ld, bool host) {
+    if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+    if (int rc = check_square("square_dosage_nobs", a, b, out, ld)) return rc;
+    if (int rc = check_samples("square_dosage_nobs", a, n_samples)) return rc;
+    if (a->n_rows == 0 || b->n_rows == 0) return STORM_HIP_OK;
+    return pair_matrix_out(ctx, "square_dosage_nobs: the output", a->n_rows, b->n_rows, out, ld, host, false, true,
+                           [&](uint32_t* d, uint64_t d_ld) { return square_dosage_nobs_queued(ctx, a, b, n_samples, d, d_ld); });
+}
+
 // The lag layout, n x L, cleared in the band buffer (the lower-right corner): both forms return below two rows. The dot
 // products alone take a band of rows in their device form (the host form: every row).
 static int pairw_lag_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint64_t max_lag, uint64_t row0,
@@ -920,6 +1150,40 @@ int storm_hip_square_dosage_matrix_device(storm_hip_ctx_t* ctx, const storm_hip_
 int storm_hip_square_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b, uint32_t* h_out,
                                    uint64_t ld) {
     return guarded("storm_hip_square_dosage_matrix", [&] { return square_dosage_matrix(ctx, a, b, h_out, ld, true); });
+}
+
+int storm_hip_square_dosage_corr_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b, int measure,
+                                        uint64_t n_samples, float* d_out, uint64_t ld) {
+    return guarded("storm_hip_square_dosage_corr_device",
+                   [&] { return square_dosage_corr(ctx, a, b, measure, n_samples, false, d_out, ld, false); });
+}
+
+int storm_hip_square_dosage_corr(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b, int measure,
+                                 uint64_t n_samples, float* h_out, uint64_t ld) {
+    return guarded("storm_hip_square_dosage_corr",
+                   [&] { return square_dosage_corr(ctx, a, b, measure, n_samples, false, h_out, ld, true); });
+}
+
+int storm_hip_square_dosage_nobs_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b,
+                                        uint64_t n_samples, uint32_t* d_out, uint64_t ld) {
+    return guarded("storm_hip_square_dosage_nobs_device", [&] { return square_dosage_nobs(ctx, a, b, n_samples, d_out, ld, false); });
+}
+
+int storm_hip_square_dosage_nobs(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b, uint64_t n_samples,
+                                 uint32_t* h_out, uint64_t ld) {
+    return guarded("storm_hip_square_dosage_nobs", [&] { return square_dosage_nobs(ctx, a, b, n_samples, h_out, ld, true); });
+}
+
+int storm_hip_square_dosage_corr_complete_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b,
+                                                 int measure, uint64_t n_samples, float* d_out, uint64_t ld) {
+    return guarded("storm_hip_square_dosage_corr_complete_device",
+                   [&] { return square_dosage_corr(ctx, a, b, measure, n_samples, true, d_out, ld, false); });
+}
+
+int storm_hip_square_dosage_corr_complete(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b, int measure,
+                                          uint64_t n_samples, float* h_out, uint64_t ld) {
+    return guarded("storm_hip_square_dosage_corr_complete",
+                   [&] { return square_dosage_corr(ctx, a, b, measure, n_samples, true, h_out, ld, true); });
 }
 
 int storm_hip_dosage_row_missing(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint32_t* h_missing) {
