@@ -912,6 +912,8 @@ class HipMatrix:
         return out
 
     def set_rows_from_positions(self, rows: Sequence[Iterable[int]], row0: int = 0) -> None:
+        """storm_hip_matrix_set_rows_from_positions: SETS the listed bits of rows [row0, row0 + len(rows)) (the bit-setting loop
+        of STORM_contig_add on the device); bits a row already has stay set — clear or upload first to replace a row."""
         arrs = [_u32(r) for r in rows]
         offs = np.zeros(len(arrs) + 1, dtype=np.uint64)
         offs[1:] = np.cumsum([a.size for a in arrs], dtype=np.uint64)

@@ -462,3 +462,305 @@ def test_the_float_rule_and_the_equality_report_catch_what_they_should():
     assert stats.worst_ratio == 0.25
     with pytest.raises(AssertionError):
         _sweep.within_bound(stats, np.float32([1.0, 2.0]), np.array([1.0 + 2.0 ** -20, 2.0]), np.array([0.0, 1.0]), "b")
+
+
+# ------------------------------------------------------------------------------------------ the session family
+from tests import test_gpu_sweep_sessions as _sessions  # noqa: E402
+
+NXN = ("pairw_matrix", "pairw_similarity", "pairw_dot", "pairw_corr", "pairw_nobs", "pairw_corr_complete")
+
+
+def session_records(seed=None):
+    return [rec for s in (_sessions.SEEDS if seed is None else (seed,)) for rec in _sweep.cases(_sweep.SESSION, s, _sessions.COUNT)]
+
+
+def trace(rec):
+    """per step: the step, the rows of every container before and behind it, the options in force, the model behind it"""
+    model, opts, out = _sweep.SessionModel(rec), dict(_sweep.SESSION_DEFAULTS), []
+    for i, st in enumerate(rec["steps"]):
+        before = {cid: m.shape[0] for cid, m in model.m.items()}
+        if st["op"] == "set_option":
+            opts[st["key"]] = st["value"]
+        model.apply(i)
+        out.append({"i": i, "st": st, "before": before, "after": {cid: m.shape[0] for cid, m in model.m.items()}, "opts": dict(opts),
+                    "model": model.snapshot()})
+    return out
+
+
+def is_query(t, cid=None, kinds=None):
+    st = t["st"]
+    return st["op"] == "query" and (cid is None or cid in (st["on"], st.get("other"))) and (kinds is None or st["kind"] in kinds)
+
+
+def test_sessions_are_deterministic():
+    a, b = session_records(), session_records()
+    assert a == b and len(a) == 3 * _sessions.COUNT and _sessions.SEEDS == (1, 2, 3)
+    assert [r["kind"] for r in a[:4]] == ["storm", "hip", "storm", "hip"]
+    assert list(_sweep.cases(_sweep.SESSION, 1, 3)) == a[:3]                       # a prefix does not depend on the count
+    assert a[0]["steps"] != a[_sessions.COUNT]["steps"]                            # ... and the seed matters
+    for rec in a[:4]:                                                              # the same model states, step by step
+        for ta, tb in zip(trace(rec), trace(rec)):
+            assert all(np.array_equal(ta["model"].m[cid], tb["model"].m[cid]) for cid in rec["containers"])
+    for rec in a:
+        assert all(tuple(o) in _sweep.SESSION_OPTIONS[rec["kind"]] for o in rec["options"])
+        assert all((st["key"], st["value"]) in _sweep.SESSION_OPTIONS[rec["kind"]] for st in rec["steps"] if st["op"] == "set_option")
+
+
+def test_session_shapes_stay_small_and_reach_the_edges():
+    recs = session_records()
+    rows = [n for rec in recs for t in trace(rec) if is_query(t) for n in [t["after"][t["st"]["on"]]]]
+    assert max(rows) <= 1100 and sum(n < 300 for n in rows) > 0.9 * len(rows)
+    assert 0 in rows and 1 in rows                                                 # a query of an empty and of a one-row container
+    for edge in (64, 128, 256, 512, 1024):
+        assert any(edge // 2 < n <= edge for n in rows) and any(edge < n <= 2 * edge for n in rows), edge
+    storm = [rec for rec in recs if rec["kind"] == "storm"]
+    assert {len([c for c in rec["containers"].values() if c["type"] == "storm"]) for rec in storm} == {1, 2}
+    assert all(c["width"] <= 4096 and c["width"] in _sweep.M_SET for rec in storm for c in rec["containers"].values() if c["type"] == "contig")
+    assert all(c["S"] in _sweep.S_SET for rec in storm for c in rec["containers"].values() if c["type"] == "dosage")
+    kinds = {st.get("row_kind") for rec in storm for st in rec["steps"] if st["op"] == "add"}
+    assert {"short", "bitmap", "far"} <= kinds
+    ops = {st["op"] for rec in recs for st in rec["steps"]}
+    assert set(_sweep.MUTATIONS) | {"set_option", "query", "hip_invalidate"} == ops
+    for kind in _sweep.SESSION_KINDS:
+        asked = {st["kind"] for rec in recs if rec["kind"] == kind for st in rec["steps"] if st["op"] == "query"}
+        assert asked == set(_sweep.session_queries(kind)), (kind, set(_sweep.session_queries(kind)) - asked)
+    margins = [float(_sweep.session_answer(t["model"], t["i"])["margin"]) for rec in storm for t in trace(rec) if is_query(t, kinds=("lag_prune",))]
+    assert margins and min(margins) >= _sweep.PRUNE_MARGIN                          # min_r2 stands clear of every in-window r^2
+
+
+def test_no_mutation_of_a_session_is_invisible():
+    for rec in session_records():
+        assert _sweep.invisible_mutations(rec) == [], (rec["seed"], rec["index"])
+
+
+def test_an_invisible_mutation_is_rejected():
+    """hand-made: an upload that no query of its matrix follows before the next upload, and a resize to the same row count"""
+    q = {"op": "query", "kind": "pairw_matrix", "pad": 1, "off": 0, "max_lag": 3, "bit_op": "and", "measure": "jaccard", "k": 2,
+         "score": "count", "world": 1, "row0": 0}
+    rec = {"kind": "hip", "input_seed": 5, "options": [], "containers": {c: {"type": "hip", "words": 1, "n": 8} for c in ("h0", "h1")},
+           "steps": [{"op": "upload", "on": "h0", "row0": 0, "rows": 8}, dict(q, on="h0"),
+                     {"op": "upload", "on": "h1", "row0": 0, "rows": 8}, dict(q, on="h1"),
+                     {"op": "upload", "on": "h0", "row0": 2, "rows": 3}, dict(q, on="h1"),     # step 4: only h1 is asked
+                     {"op": "upload", "on": "h0", "row0": 4, "rows": 2}, dict(q, on="h0"),
+                     {"op": "resize", "on": "h1", "n": 8}, dict(q, on="h1"),                   # step 8: nothing changes
+                     {"op": "resize", "on": "h1", "n": 5}, dict(q, on="h1", kind="total"), dict(q, on="h1")]}
+    assert _sweep.invisible_mutations(rec) == [4, 8]
+    rec["steps"][5]["on"] = "h0"
+    assert _sweep.invisible_mutations(rec) == [8]
+
+
+def off_lists(t):
+    """the query of this step runs on the dense paths QUERY_KINDS is about: not a Storm's total (its arena), not a Storm whose
+    matrix comes from its lists — matrix_lists 1 or -1 on a container that test_gpu_storm_edges.py's rule calls K5-eligible;
+    two Storms (K5x): only matrix_lists 0 counts"""
+    from tests.test_gpu_storm_edges import _k5_eligible
+    st, model = t["st"], t["model"]
+    if model.type(st["on"]) != "storm":
+        return True
+    if st["kind"] == "total":
+        return False
+    if t["opts"]["matrix_lists"] == 0:
+        return True
+    return "other" not in st and not _k5_eligible([_sweep.storm_positions(row) for row in model.m[st["on"]]])
+
+
+@pytest.mark.parametrize("kind", _sweep.SESSION_KINDS)
+def test_every_hand_over_of_a_shared_buffer_occurs(kind):
+    """consecutive queries (mutations and option steps may stand between them), both on the dense paths"""
+    seen, per_seed = set(), {}
+    for rec in session_records():
+        if rec["kind"] == kind:
+            asked = [(t["st"]["kind"], off_lists(t)) for t in trace(rec) if is_query(t)]
+            pairs = {(a[0], b[0]) for a, b in zip(asked, asked[1:]) if a[1] and b[1]}
+            seen |= pairs
+            per_seed.setdefault(rec["seed"], set()).update(pairs)
+    table = _sweep.session_handovers(kind)
+    assert set(table) == set(_sweep.SESSION_BUFFERS)
+    for buf, pairs in table.items():
+        assert len(pairs) >= 2, buf
+        missing = [p for p in pairs if p not in seen]
+        assert not missing, (buf, len(missing), missing[:8])
+    for seed, pairs in per_seed.items():                                           # the strip list's hand-over in every seed
+        assert {("total", "square_total"), ("square_total", "total")} <= pairs, seed
+
+
+@pytest.mark.parametrize("seed", _sessions.SEEDS)
+def test_every_option_of_the_table_is_set(seed):
+    for kind in _sweep.SESSION_KINDS:
+        done = {(st["key"], st["value"]) for rec in session_records(seed) if rec["kind"] == kind for st in rec["steps"]
+                if st["op"] == "set_option"}
+        assert done == set(_sweep.SESSION_OPTIONS[kind]), (kind, set(_sweep.SESSION_OPTIONS[kind]) - done)
+
+
+def _around(tr, i, cid):
+    """a query of `cid` right before and right behind step i"""
+    return i > 0 and i + 1 < len(tr) and is_query(tr[i - 1], cid) and is_query(tr[i + 1], cid)
+
+
+@pytest.mark.parametrize("seed", _sessions.SEEDS)
+def test_growth_across_the_pads_and_the_first_reallocation(seed):
+    crossed, realloc = set(), False
+    for rec in session_records(seed):
+        tr = trace(rec)
+        alloc, grown = {}, set()      # the mirror's allocated rows (storm_hip_matrix_create / _resize), made by the first query
+        for t in tr:
+            st, cid = t["st"], t["st"].get("on")
+            ctype = rec["containers"][cid]["type"] if cid else None
+            if st["op"] in ("clear", "free_new") and ctype != "hip":
+                alloc.pop(cid, None)
+                grown.discard(cid)
+            if ctype == "hip" and (st["op"] == "free_new" or t["i"] == 0 or cid not in alloc):
+                alloc[cid] = max(256, -(-t["after" if st["op"] == "free_new" else "before"][cid] // 256) * 256)
+                grown.discard(cid) if st["op"] == "free_new" else None
+            if st["op"] == "query" and ctype == "dosage" and cid not in alloc and t["after"][cid] >= 2:
+                alloc[cid] = max(256, -(-t["after"][cid] // 256) * 256)
+            if st["op"] in ("add", "resize") and _around(tr, t["i"], cid):
+                for edge in (256, 512, 1024):
+                    if t["before"][cid] <= edge < t["after"][cid]:
+                        crossed.add(edge)
+                if cid in alloc and t["after"][cid] > alloc[cid]:
+                    realloc = realloc or cid not in grown
+            if st["op"] in ("add", "resize") and cid in alloc and t["after"][cid] > alloc[cid]:
+                grown.add(cid)
+                alloc[cid] = max(-(-t["after"][cid] // 256) * 256, 2 * alloc[cid])
+    assert crossed == {256, 512, 1024} and realloc
+
+
+@pytest.mark.parametrize("seed", _sessions.SEEDS)
+def test_a_storm_loses_k5_eligibility_and_regains_it_behind_clear(seed):
+    from tests.test_gpu_storm_edges import _k5_eligible
+    done = False
+    for rec in session_records(seed):
+        for cid in (c for c, v in rec["containers"].items() if v["type"] == "storm"):
+            phase, lists, cleared = 0, set(), False                                # phases: eligible, not, eligible behind a clear
+            for t in trace(rec):
+                st = t["st"]
+                if st.get("on") == cid and st["op"] == "clear":
+                    cleared = phase == 2
+                if phase == 3 or not is_query(t, kinds=("pairw_matrix",)) or st["on"] != cid:
+                    continue
+                eligible = _k5_eligible([_sweep.storm_positions(row) for row in t["model"].m[cid]])
+                if eligible != (phase != 1) or (phase == 2 and not cleared):
+                    lists = set()
+                    continue
+                lists.add(t["opts"]["matrix_lists"])                               # a query in the phase under matrix_lists 1 and -1
+                if {1, -1} <= lists:
+                    phase, lists = phase + 1, set()
+            done = done or phase == 3
+    assert done
+
+
+def _steps_between(tr, i, k, cid, ops=_sweep.MUTATIONS):
+    return [t for t in tr[i + 1:k] if t["st"]["op"] in ops and t["st"].get("on") == cid]
+
+
+def _same_answer(tr, i, k):
+    a, b = tr[i]["st"], tr[k]["st"]
+    return a["kind"] == b["kind"] and a["on"] == b["on"] and a.get("other") == b.get("other") and \
+        not _sweep.answers_differ(_sweep.session_answer(tr[i]["model"], i), _sweep.session_answer(tr[k]["model"], k))
+
+
+@pytest.mark.parametrize("seed", _sessions.SEEDS)
+def test_the_named_transitions_of_a_storm_session(seed):
+    found = set()
+    for rec in session_records(seed):
+        if rec["kind"] != "storm":
+            continue
+        tr = trace(rec)
+        blocks = lambda t, cid: int(np.flatnonzero(t["model"].m[cid].any(axis=0)).max(initial=-1)) // _sweep.STORM_SPAN + 1
+        for i, t in enumerate(tr):
+            st = t["st"]
+            if st["op"] in _sweep.MUTATIONS and 0 < i and i + 3 < len(tr) and is_query(tr[i - 1]) and tr[i - 1]["st"]["on"] != st["on"]:
+                for k in (i + 1, i + 2, i + 3):            # a mutation of B between two equal queries of an unchanged A
+                    if is_query(tr[k]) and _same_answer(tr, i - 1, k) and not _steps_between(tr, i - 1, k, tr[k]["st"]["on"]):
+                        found.add("free between" if st["op"] == "free_new" else "B between")
+            if st["op"] == "add" and rec["containers"][st["on"]]["type"] == "dosage" and t["before"][st["on"]] >= 2:
+                asked = [u for u in tr[:i] if is_query(u, st["on"]) or u["st"]["op"] in ("clear", "free_new") and u["st"]["on"] == st["on"]]
+                if asked and asked[-1]["st"]["op"] == "query" and i + 1 < len(tr) and is_query(tr[i + 1], st["on"]):
+                    found.add("incremental upload")        # rows [synced, n_rows) go up behind a query
+            if st["op"] == "clear":
+                later = [u for u in tr[i + 1:] if is_query(u, st["on"]) and u["after"][st["on"]] > 0]
+                if later and later[0]["after"][st["on"]] < t["before"][st["on"]] and not _steps_between(tr, i, later[0]["i"], st["on"], ("clear", "free_new")):
+                    found.add("clear, fewer rows")
+            if i + 1 < len(tr) and is_query(t) and is_query(tr[i + 1]) and st["on"] == tr[i + 1]["st"]["on"]:
+                a, b = st["kind"], tr[i + 1]["st"]["kind"]
+                if a in NXN and b.startswith("lag_"):
+                    found.add("lag behind n x n")
+                if b in NXN and a.startswith("lag_"):
+                    found.add("n x n behind lag")
+            # the dense replica: A alone, A x a wider B, A alone, A grown, A x B again — under matrix_lists 0, A never cleared
+            if is_query(t, kinds=("square_matrix",)) and t["opts"]["matrix_lists"] == 0 and blocks(t, st["other"]) > blocks(t, st["on"]):
+                a = st["on"]
+                rest = tr[i + 1:]
+                alone = [u for u in rest if is_query(u, a, ("pairw_matrix",)) and u["st"]["on"] == a]
+                grown = [u for u in rest if alone and u["i"] > alone[0]["i"] and u["st"]["op"] == "add" and u["st"]["on"] == a]
+                again = [u for u in rest if grown and u["i"] > grown[0]["i"] and is_query(u, kinds=("square_matrix",)) and u["st"]["on"] == a
+                         and u["st"]["other"] == st["other"] and u["opts"]["matrix_lists"] == 0]
+                first = [u for u in tr[:i] if is_query(u, a, ("pairw_matrix",)) and u["opts"]["matrix_lists"] == 0]
+                if first and again and not _steps_between(tr, first[-1]["i"], again[0]["i"], a, ("clear", "free_new")):
+                    found.add("replica widened")
+    assert found == {"B between", "free between", "incremental upload", "clear, fewer rows", "lag behind n x n", "n x n behind lag",
+                     "replica widened"}
+
+
+@pytest.mark.parametrize("seed", _sessions.SEEDS)
+def test_the_named_transitions_of_a_hip_session(seed):
+    found = set()
+    for rec in session_records(seed):
+        if rec["kind"] != "hip":
+            continue
+        tr = trace(rec)
+        assert all(c["n"] <= 256 for c in rec["containers"].values())               # (the allocation a resize stays inside or leaves)
+        for i, t in enumerate(tr):
+            st = t["st"]
+            if st["op"] == "upload" and 0 < st["row0"] and st["row0"] + st["rows"] < t["before"][st["on"]] and _around(tr, i, st["on"]):
+                if all(u["opts"]["keep_shadow"] == 1 and u["st"].get("kind", "total") == "total" for u in tr[i - 1:i + 2]):
+                    found.add("keep_shadow across an upload")
+            if st["op"] == "resize":
+                found.add("resize down" if t["after"][st["on"]] < t["before"][st["on"]] else
+                          "resize up inside" if t["after"][st["on"]] <= 256 else "resize past the allocation")
+            if st["op"] in _sweep.MUTATIONS and 0 < i and i + 2 < len(tr) and is_query(tr[i - 1]) and tr[i - 1]["st"]["on"] != st["on"]:
+                if is_query(tr[i + 2]) and _same_answer(tr, i - 1, i + 2):
+                    found.add("B between")
+            if i + 1 < len(tr) and is_query(t) and is_query(tr[i + 1]) and st["on"] == tr[i + 1]["st"]["on"]:
+                found |= {"lag behind n x n"} if st["kind"] in NXN and tr[i + 1]["st"]["kind"].startswith("lag_") else set()
+                found |= {"n x n behind lag"} if tr[i + 1]["st"]["kind"] in NXN and st["kind"].startswith("lag_") else set()
+    assert found == {"keep_shadow across an upload", "resize down", "resize up inside", "resize past the allocation", "B between",
+                     "lag behind n x n", "n x n behind lag"}
+
+
+def test_the_model_against_rows_kept_in_plain_lists():
+    """the model's mutation functions, step by step, against Python lists written one row (one bit) at a time"""
+    recs = session_records(1)
+    for rec in (recs[4], recs[1], recs[3]):                                        # storm (the small theme), hip, hip with growth
+        state = {cid: [[0] * (64 * c["words"]) for _ in range(c["n"])] if c["type"] == "hip" else [] for cid, c in rec["containers"].items()}
+        for t in trace(rec):
+            st = t["st"]
+            if st["op"] not in _sweep.MUTATIONS:
+                continue
+            cid, rows = st["on"], state[st["on"]]
+            hip = rec["containers"][cid]["type"] == "hip"
+            width = t["model"].m[cid].shape[1]
+            new = _sweep.session_rows(rec, t["i"]).tolist() if "rows" in st else []
+            if st["op"] == "add":
+                for row in new:
+                    rows.append(row)
+            elif st["op"] == "clear":
+                state[cid] = [[0] * width for _ in rows] if hip else []
+            elif st["op"] == "free_new":
+                state[cid] = [[0] * width for _ in range(st.get("n", 0))]
+            elif st["op"] == "resize":
+                while len(rows) > st["n"]:
+                    rows.pop()
+                while len(rows) < st["n"]:
+                    rows.append([0] * width)
+            else:
+                for r, row in enumerate(new):
+                    if st["op"] == "set_rows_from_positions":                      # sets bits, clears none
+                        for col, bit in enumerate(row):
+                            if bit:
+                                rows[st["row0"] + r][col] = 1
+                    else:
+                        rows[st["row0"] + r] = row
+            want = np.array(state[cid], dtype=np.uint8).reshape(len(state[cid]), width)
+            assert np.array_equal(t["model"].m[cid], want), (rec["index"], t["i"], st["op"])

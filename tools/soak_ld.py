@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Randomised parity soak of the lag, dosage, LD and top-k calls on the GPU: the families of tests/_sweep.py — bit
-containers, top-k, dosage n x n and rectangle, dosage in the lag layout, LD scores, pruning — drawn from seeds the suite
-does not use, each case compared with plain numpy on the unpacked rows, for a bounded time. For whoever changes these
+containers, top-k, dosage n x n and rectangle, dosage in the lag layout, LD scores, pruning, and the sessions of interleaved
+calls and mutations on live containers — drawn from seeds the suite does not use, each case compared with plain numpy on the unpacked rows, for a bounded time. For whoever changes these
 kernels; the suite does not run it. Prints one JSON line; exit code 1 on the first mismatch (the line names the case and
 its replay command).   soak_ld.py [--seconds 240] [--seed 1] [--family F]"""
 import argparse
@@ -22,10 +22,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=240.0)
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--family", choices=_sweep.FAMILIES, default=None)
+    ap.add_argument("--family", choices=_sweep.FAMILIES + (_sweep.SESSION,), default=None)
     args = ap.parse_args()
     import stormbitmaps_amd as sb
-    families = _sweep.FAMILIES if args.family is None else (args.family,)
+    families = _sweep.FAMILIES + (_sweep.SESSION,) if args.family is None else (args.family,)
     ctx = sb.HipContext(0)
     t0 = time.time()
     totals = {f: _sweep.Stats() for f in families}
