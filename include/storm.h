@@ -470,6 +470,46 @@ int STORM_dosage_square_corr_complete(STORM_dosage_t* a, STORM_dosage_t* b, int 
 int STORM_dosage_square_corr_complete_device(STORM_dosage_t* a, STORM_dosage_t* b, int measure, float* d_out, uint64_t out_rows,
                                              uint64_t out_ld);
 
+/* The best LD tags of a variant for UNPHASED genotypes: for each row of a dosage container its k best rows, selected on the
+ * device — n x k indices and values leave it instead of the n x n float matrix of STORM_dosage_pairw_corr /
+ * _square_corr[_complete] (4 GiB at 32768 variants), and the device scratch is one row panel of integer sums: O(panel_rows x
+ * n_b) words, about 6 times that in the _complete forms, never O(n_a x n_b).
+ *   STORM_dosage_pairw_topk[_complete]    row i of h against every OTHER row of h (a row never lists itself)
+ *   STORM_dosage_square_topk[_complete]   row i of a against every row of b (the same number of samples; a may be b, and a
+ *                                         row lists itself then)
+ * `score`: STORM_DOSAGE_R2, STORM_DOSAGE_R — ranked by the SIGNED value; ranking by |r| is what STORM_DOSAGE_R2 gives — or
+ * STORM_DOSAGE_TOPK_DOT, the dot product P itself (val is uint32 then; valid in these calls only and in the plain forms only:
+ * the _complete forms refuse it with -3). The value bits are exactly what STORM_dosage_square_corr writes for the two rows
+ * (bit-identical to STORM_dosage_pairw_corr; 3 is an ordinary value), in the _complete forms exactly what
+ * STORM_dosage_square_corr_complete writes (3 = STORM_DOSAGE_MISSING).
+ * Order, padding and limits are STORM_pairw_topk's: idx[i * out_ld + t] is the row that ranks t-th for row i, val[i * out_ld
+ * + t] its value; value descending, then row index ascending; a NaN entry (0x7FC00000: a constant row, no shared samples)
+ * is never a candidate; a row with fewer than k candidates is padded with idx 0xFFFFFFFF and val NaN (val 0 under
+ * STORM_DOSAGE_TOPK_DOT); columns [k, out_ld) and everything outside the n_a x k window are not touched. 1 <= k <=
+ * STORM_TOPK_MAX; out_rows >= a's rows and out_ld >= k. panel_rows: rows of a whose sums are on the device at a time, 0
+ * (chosen by the library: at most 256 MiB of them, at least 256 rows) or a multiple of 256. The _device forms take idx /
+ * val in DEVICE memory and are complete on return. The _complete forms hold at most 65408 rows per container.
+ * Returns 0; -1 NULL handle; -2 NULL idx or val; -4 out_rows or out_ld too small (nothing written); -3 a bad score, k or
+ * panel_rows, unequal sample counts, or a device failure (STORM_hip_error says which); -5 several device slots in view. An
+ * empty a: 0, nothing written. An empty b, or pairw on one row: every row is k paddings. */
+#define STORM_DOSAGE_TOPK_DOT 2
+int STORM_dosage_pairw_topk(STORM_dosage_t* h, int score, uint64_t k, uint64_t panel_rows, uint32_t* idx, void* val,
+                            uint64_t out_rows, uint64_t out_ld);
+int STORM_dosage_pairw_topk_device(STORM_dosage_t* h, int score, uint64_t k, uint64_t panel_rows, uint32_t* d_idx, void* d_val,
+                                   uint64_t out_rows, uint64_t out_ld);
+int STORM_dosage_pairw_topk_complete(STORM_dosage_t* h, int score, uint64_t k, uint64_t panel_rows, uint32_t* idx, void* val,
+                                     uint64_t out_rows, uint64_t out_ld);
+int STORM_dosage_pairw_topk_complete_device(STORM_dosage_t* h, int score, uint64_t k, uint64_t panel_rows, uint32_t* d_idx,
+                                            void* d_val, uint64_t out_rows, uint64_t out_ld);
+int STORM_dosage_square_topk(STORM_dosage_t* a, STORM_dosage_t* b, int score, uint64_t k, uint64_t panel_rows, uint32_t* idx,
+                             void* val, uint64_t out_rows, uint64_t out_ld);
+int STORM_dosage_square_topk_device(STORM_dosage_t* a, STORM_dosage_t* b, int score, uint64_t k, uint64_t panel_rows,
+                                    uint32_t* d_idx, void* d_val, uint64_t out_rows, uint64_t out_ld);
+int STORM_dosage_square_topk_complete(STORM_dosage_t* a, STORM_dosage_t* b, int score, uint64_t k, uint64_t panel_rows,
+                                      uint32_t* idx, void* val, uint64_t out_rows, uint64_t out_ld);
+int STORM_dosage_square_topk_complete_device(STORM_dosage_t* a, STORM_dosage_t* b, int score, uint64_t k, uint64_t panel_rows,
+                                             uint32_t* d_idx, void* d_val, uint64_t out_rows, uint64_t out_ld);
+
 /* The four pairwise calls of the dosage container for the pairs within max_lag rows of each other only — PLINK's --r / --r2
  * as it is run on genotype files: within a window (--ld-window), never all-vs-all. The layout is STORM_pairw_lag_matrix's:
  * with n the rows held and L = min(max_lag, n - 1), `out` holds out_rows x out_ld entries (out_rows >= n, out_ld >= L) and

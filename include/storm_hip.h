@@ -425,6 +425,56 @@ int storm_hip_square_dosage_corr_complete_device(storm_hip_ctx_t* ctx, const sto
 int storm_hip_square_dosage_corr_complete(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b, int measure,
                                           uint64_t n_samples, float* h_out, uint64_t ld);
 
+/* ---- per-row top-k neighbours of dosage rows: the best r^2 / r tags of a variant, selected on the device -----------
+ * The top-k calls above for dosage matrices: for each row its k best rows by STORM_HIP_DOSAGE_R2, STORM_HIP_DOSAGE_R (the
+ * SIGNED value: ranking by |r| is what STORM_HIP_DOSAGE_R2 gives) or STORM_HIP_DOSAGE_TOPK_DOT, the dot product itself
+ * (val is uint32 then and a padding entry has val 0; valid in the top-k calls only, and not in the _complete forms).
+ * Order, NaN entries, padding, k and the outputs idx / val (pitch ld_k) exactly as in the top-k block above. The value bits
+ * are what _square_dosage_corr writes for the two rows (3 an ordinary value), in the _complete forms what
+ * _square_dosage_corr_complete writes (3 = MISSING). No float matrix is formed: the selection kernel (topk_rows_kernel over
+ * a dosage scorer) reads the panel of integer sums once and forms each entry's value itself.
+ * _dosage_topk_rows_device, the primitive: `d_dots` is a COMPLETE panel of dot products in DEVICE memory, n_rows x ld uint32
+ *   (read, never written; the pitch columns [n_cols, ld) are not read), d_sum_rows / d_sq_rows [n_rows] and d_sum_cols /
+ *   d_sq_cols [n_cols] the sums s and q of the rows' and of the columns' side, n_samples in [1, 2^24]; skip0 as in
+ *   _topk_rows_device. Asynchronous on the context's stream; alone the last-pass report is STORM_HIP_RAN_TOPK.
+ * _pairw_dosage_topk[_complete]: row i of `m` against every other row, on both sides of the diagonal (twice the work of
+ *   the triangle: DESIGN.md §8, open). _square_dosage_topk[_complete]: every row of `a` against every row of `b` (a may be
+ *   b: a row lists itself then). Row panels: each matrix's row sums (plain) or split into G, H, M (complete: at most 65408
+ *   rows per matrix) once per call, then per panel of panel_rows rows of `a` the sums' rectangles against all of `b` — one
+ *   K2h launch, or G_p x G_b, G_p x M_b, H_p x M_b and M_p x [G_b ; H_b ; M_b] — into the context's scratch and the
+ *   selection over them. panel_rows = 0: the largest multiple of 256 whose planes (1 word per entry, complete: about 6)
+ *   hold at most 256 MiB, at least 256; else a multiple of 256. The scratch is O(panel_rows x n_b), not O(n_a x n_b).
+ *   _device: idx / val in DEVICE memory, complete on return; the others copy n x k of each back.
+ * STORM_HIP_EINVAL: NULL argument, rows of different widths, unknown score (or the dot product in a _complete form),
+ *   n_samples that does not match the row width, rows of more than 2^24 values, k of 0 or above STORM_HIP_TOPK_MAX,
+ *   ld_k < k, ld < n_cols, panel_rows not a multiple of 256. No rows: STORM_HIP_OK, nothing written; pairw on one row, or an
+ *   empty `b`: every row is k paddings. Last-pass report: STORM_HIP_RAN_TILES_OUT | STORM_HIP_RAN_TOPK, [1] = n_a n_b
+ *   n_words (_complete: 6 times that). */
+#define STORM_HIP_DOSAGE_TOPK_DOT 2
+int storm_hip_dosage_topk_rows_device(storm_hip_ctx_t* ctx, const uint32_t* d_dots, uint64_t ld, uint64_t n_rows, uint64_t n_cols,
+                                      const uint32_t* d_sum_rows, const uint32_t* d_sq_rows, const uint32_t* d_sum_cols,
+                                      const uint32_t* d_sq_cols, uint64_t n_samples, uint64_t skip0, int score, uint64_t k,
+                                      uint32_t* d_idx, void* d_val, uint64_t ld_k);
+int storm_hip_pairw_dosage_topk_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int score, uint64_t n_samples, uint64_t k,
+                                       uint64_t panel_rows, uint32_t* d_idx, void* d_val, uint64_t ld_k);
+int storm_hip_pairw_dosage_topk(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int score, uint64_t n_samples, uint64_t k,
+                                uint64_t panel_rows, uint32_t* h_idx, void* h_val, uint64_t ld_k);
+int storm_hip_pairw_dosage_topk_complete_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int score, uint64_t n_samples,
+                                                uint64_t k, uint64_t panel_rows, uint32_t* d_idx, void* d_val, uint64_t ld_k);
+int storm_hip_pairw_dosage_topk_complete(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int score, uint64_t n_samples, uint64_t k,
+                                         uint64_t panel_rows, uint32_t* h_idx, void* h_val, uint64_t ld_k);
+int storm_hip_square_dosage_topk_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b, int score,
+                                        uint64_t n_samples, uint64_t k, uint64_t panel_rows, uint32_t* d_idx, void* d_val,
+                                        uint64_t ld_k);
+int storm_hip_square_dosage_topk(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b, int score,
+                                 uint64_t n_samples, uint64_t k, uint64_t panel_rows, uint32_t* h_idx, void* h_val, uint64_t ld_k);
+int storm_hip_square_dosage_topk_complete_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b,
+                                                 int score, uint64_t n_samples, uint64_t k, uint64_t panel_rows, uint32_t* d_idx,
+                                                 void* d_val, uint64_t ld_k);
+int storm_hip_square_dosage_topk_complete(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b, int score,
+                                          uint64_t n_samples, uint64_t k, uint64_t panel_rows, uint32_t* h_idx, void* h_val,
+                                          uint64_t ld_k);
+
 /* ---- dosage matrices in the lag layout: PLINK --r / --r2 within a window (--ld-window) ---------------------------
  * The calls of the two blocks above for the pairs within max_lag rows of each other, in the lag layout of
  * storm_hip_pairw_lag_matrix_device: with L = min(max_lag, n_rows - 1), entry out[i * ld + (j - i - 1)] is the pair

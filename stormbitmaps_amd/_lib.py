@@ -144,6 +144,15 @@ SIGNATURES = {
     "storm_hip_square_dosage_nobs": (C.c_int, [vp, vp, vp, u64, vp, u64]),
     "storm_hip_square_dosage_corr_complete_device": (C.c_int, [vp, vp, vp, C.c_int, u64, vp, u64]),
     "storm_hip_square_dosage_corr_complete": (C.c_int, [vp, vp, vp, C.c_int, u64, vp, u64]),
+    "storm_hip_dosage_topk_rows_device": (C.c_int, [vp, vp, u64, u64, u64, vp, vp, vp, vp, u64, u64, C.c_int, u64, vp, vp, u64]),
+    "storm_hip_pairw_dosage_topk_device": (C.c_int, [vp, vp, C.c_int, u64, u64, u64, vp, vp, u64]),
+    "storm_hip_square_dosage_topk_device": (C.c_int, [vp, vp, vp, C.c_int, u64, u64, u64, vp, vp, u64]),
+    "storm_hip_pairw_dosage_topk": (C.c_int, [vp, vp, C.c_int, u64, u64, u64, vp, vp, u64]),
+    "storm_hip_square_dosage_topk": (C.c_int, [vp, vp, vp, C.c_int, u64, u64, u64, vp, vp, u64]),
+    "storm_hip_pairw_dosage_topk_complete_device": (C.c_int, [vp, vp, C.c_int, u64, u64, u64, vp, vp, u64]),
+    "storm_hip_square_dosage_topk_complete_device": (C.c_int, [vp, vp, vp, C.c_int, u64, u64, u64, vp, vp, u64]),
+    "storm_hip_pairw_dosage_topk_complete": (C.c_int, [vp, vp, C.c_int, u64, u64, u64, vp, vp, u64]),
+    "storm_hip_square_dosage_topk_complete": (C.c_int, [vp, vp, vp, C.c_int, u64, u64, u64, vp, vp, u64]),
     "storm_hip_dosage_row_missing": (C.c_int, [vp, vp, u64, vp]),
     "storm_hip_pairw_dosage_nobs_device": (C.c_int, [vp, vp, u64, vp, u64]),
     "storm_hip_pairw_dosage_nobs": (C.c_int, [vp, vp, u64, vp, u64]),
@@ -260,6 +269,14 @@ SIGNATURES = {
     "STORM_dosage_square_nobs_device": (C.c_int, [vp, vp, vp, u64, u64]),
     "STORM_dosage_square_corr_complete": (C.c_int, [vp, vp, C.c_int, vp, u64, u64]),
     "STORM_dosage_square_corr_complete_device": (C.c_int, [vp, vp, C.c_int, vp, u64, u64]),
+    "STORM_dosage_pairw_topk": (C.c_int, [vp, C.c_int, u64, u64, vp, vp, u64, u64]),
+    "STORM_dosage_square_topk": (C.c_int, [vp, vp, C.c_int, u64, u64, vp, vp, u64, u64]),
+    "STORM_dosage_pairw_topk_device": (C.c_int, [vp, C.c_int, u64, u64, vp, vp, u64, u64]),
+    "STORM_dosage_square_topk_device": (C.c_int, [vp, vp, C.c_int, u64, u64, vp, vp, u64, u64]),
+    "STORM_dosage_pairw_topk_complete": (C.c_int, [vp, C.c_int, u64, u64, vp, vp, u64, u64]),
+    "STORM_dosage_square_topk_complete": (C.c_int, [vp, vp, C.c_int, u64, u64, vp, vp, u64, u64]),
+    "STORM_dosage_pairw_topk_complete_device": (C.c_int, [vp, C.c_int, u64, u64, vp, vp, u64, u64]),
+    "STORM_dosage_square_topk_complete_device": (C.c_int, [vp, vp, C.c_int, u64, u64, vp, vp, u64, u64]),
     "STORM_dosage_row_missing": (C.c_int, [vp, vp]),
     "STORM_dosage_pairw_nobs": (C.c_int, [vp, vp, u64, u64]),
     "STORM_dosage_pairw_nobs_device": (C.c_int, [vp, vp, u64, u64]),

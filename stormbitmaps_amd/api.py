@@ -221,6 +221,7 @@ class StormContig(_LagForms, _TopkForms):
 
 
 DOSAGE_MEASURES = {"r2": 0, "r": 1}  # STORM_DOSAGE_* (storm.h)
+DOSAGE_SCORES = dict(DOSAGE_MEASURES, dot=2)  # what the dosage top-k calls rank by: a measure, or STORM_DOSAGE_TOPK_DOT
 LDSCORE_STATS = {"r2": 0, "r2_adj": 1}  # STORM_LDSCORE_* (storm.h)
 
 
@@ -367,6 +368,44 @@ class StormDosage:
         """STORM_dosage_square_nobs: [n_rows, other.n_rows] uint32, entry (i, j) = the samples that neither row i of this
         container nor row j of `other` is missing (value 3) at. device=: as square_dot (STORM_dosage_square_nobs_device)."""
         return self._square("STORM_dosage_square_nobs", np.uint32, other, device)
+
+    def _topk(self, name: str, handles, n: int, k: int, score: str, complete: bool, panel_rows: int, device):
+        """one of the STORM_dosage_*_topk calls: (idx, val) of [n, k] as numpy arrays, or with device= (a torch device) as
+        torch tensors there — idx int32 (the padding 0xFFFFFFFF reads -1), val float32, or int32 for score "dot" """
+        name += "_complete" if complete else ""
+        if device is not None:
+            import torch
+            idx = torch.empty((max(n, 1), k), dtype=torch.int32, device=device)
+            val = torch.empty((max(n, 1), k), dtype=torch.int32 if score == "dot" else torch.float32, device=device)
+            if not idx.is_cuda:
+                raise ValueError("device=: a torch device with device memory")
+            torch.cuda.synchronize(idx.device)   # (the allocator's stream is not the library's)
+            self._check(name + "_device", int(getattr(self._lib, name + "_device")(
+                *handles, DOSAGE_SCORES[score], k, panel_rows, C.c_void_p(idx.data_ptr()), C.c_void_p(val.data_ptr()), n, k)))
+            return idx[:n], val[:n]
+        idx = np.zeros((n, k), dtype=np.uint32)
+        val = np.zeros((n, k), dtype=np.uint32 if score == "dot" else np.float32)
+        spare = np.zeros(1, np.uint32)
+        self._check(name, int(getattr(self._lib, name)(*handles, DOSAGE_SCORES[score], k, panel_rows,
+                                                       _ptr(idx) if idx.size else _ptr(spare),
+                                                       _ptr(val) if val.size else _ptr(spare), n, k)))
+        return idx, val
+
+    def pairw_topk(self, k: int, score: str = "r2", complete: bool = False, panel_rows: int = 0, device=None):
+        """STORM_dosage_pairw_topk[_complete]: (idx [n_rows, k] uint32, val [n_rows, k] float32, or uint32 for score "dot"):
+        for each row its k best OTHER rows by "r2", "r" (the signed value; rank by |r| with "r2") or "dot" (the dot product;
+        not with complete=True), selected on the device: value descending, then row index ascending, pairw_corr's bits;
+        fewer than k candidates (NaN entries are none): idx 0xFFFFFFFF with val NaN (0 for "dot"). complete=True: over the
+        samples both rows have (value 3 = missing), pairw_corr_complete's bits. panel_rows: rows whose sums are on the
+        device at a time (0: chosen by the library; else a multiple of 256). device=: a torch device; both results stay
+        there as torch tensors (idx int32: the padding reads -1; val float32, or int32 for "dot")."""
+        return self._topk("STORM_dosage_pairw_topk", (self._h,), self.n_rows, k, score, complete, panel_rows, device)
+
+    def square_topk(self, other: "StormDosage", k: int, score: str = "r2", complete: bool = False, panel_rows: int = 0, device=None):
+        """STORM_dosage_square_topk[_complete]: (idx, val) of [n_rows, k]: for each row of this container its k best rows of
+        `other` (the same number of samples; other may be self, and a row lists itself then), square_corr's bits. Everything
+        else as pairw_topk."""
+        return self._topk("STORM_dosage_square_topk", (self._h, other._h), self.n_rows, k, score, complete, panel_rows, device)
 
     def row_missing(self):
         """STORM_dosage_row_missing: the samples of every row that are missing (value 3), [n_rows] uint32, counted on the
@@ -1222,6 +1261,37 @@ class HipMatrix:
                                                    (1 << 64) - 1 if skip0 is None else skip0, SCORES[score], n_bits, k,
                                                    C.c_void_p(d_idx), C.c_void_p(d_val), ld_k),
               "storm_hip_topk_rows_device")
+
+    def pairw_dosage_topk(self, n_samples: int, k: int, score: str = "r2", complete: bool = False, panel_rows: int = 0):
+        """storm_hip_pairw_dosage_topk[_complete] on a dosage matrix: (idx [n_rows, k] uint32, val [n_rows, k] float32, or
+        uint32 for score "dot"): for each row its k best other rows by r^2, r or the dot product."""
+        name = "storm_hip_pairw_dosage_topk" + ("_complete" if complete else "")
+        idx, val = _topk_out(self.n_rows, k, "count" if score == "dot" else score)
+        spare = np.zeros(1, np.uint32)
+        check(getattr(self._lib, name)(self.ctx._h, self._h, DOSAGE_SCORES[score], n_samples, k, panel_rows,
+                                       _ptr(idx) if idx.size else _ptr(spare), _ptr(val) if val.size else _ptr(spare), k), name)
+        return idx, val
+
+    def cross_dosage_topk(self, other: "HipMatrix", n_samples: int, k: int, score: str = "r2", complete: bool = False,
+                          panel_rows: int = 0):
+        """storm_hip_square_dosage_topk[_complete]: (idx, val) of [n_rows, k]: for each row of self its k best rows of other."""
+        name = "storm_hip_square_dosage_topk" + ("_complete" if complete else "")
+        idx, val = _topk_out(self.n_rows, k, "count" if score == "dot" else score)
+        spare = np.zeros(1, np.uint32)
+        check(getattr(self._lib, name)(self.ctx._h, self._h, other._h, DOSAGE_SCORES[score], n_samples, k, panel_rows,
+                                       _ptr(idx) if idx.size else _ptr(spare), _ptr(val) if val.size else _ptr(spare), k), name)
+        return idx, val
+
+    def dosage_topk_rows_device(self, d_dots: int, ld: int, n_rows: int, n_cols: int, d_sum_rows: int, d_sq_rows: int,
+                                d_sum_cols: int, d_sq_cols: int, n_samples: int, d_idx: int, d_val: int, ld_k: int, k: int,
+                                score: str = "r2", skip0: Optional[int] = None) -> None:
+        """The selection alone over a complete panel of dot products of the caller's in device memory
+        (storm_hip_dosage_topk_rows_device; the matrix only lends its context); asynchronous on the context's stream."""
+        check(self._lib.storm_hip_dosage_topk_rows_device(self.ctx._h, C.c_void_p(d_dots), ld, n_rows, n_cols, C.c_void_p(d_sum_rows),
+                                                          C.c_void_p(d_sq_rows), C.c_void_p(d_sum_cols), C.c_void_p(d_sq_cols),
+                                                          n_samples, (1 << 64) - 1 if skip0 is None else skip0,
+                                                          DOSAGE_SCORES[score], k, C.c_void_p(d_idx), C.c_void_p(d_val), ld_k),
+              "storm_hip_dosage_topk_rows_device")
 
     def row_counts(self) -> np.ndarray:
         out = np.zeros(self.n_rows, dtype=np.uint32)

@@ -332,10 +332,7 @@ static int dosage_corr_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m,
 // The split operands of a matrix with missing genotypes, in ctx->d_dosage_rows: G, H and M as matrices of rows128 =
 // n_rows up to the next multiple of 128 rows each (zero rows behind n_rows), G and H adjacent so that [G ; H] is one matrix
 // of rows128 + n_rows rows. Queued.
-struct DosageSplit {
-    storm_hip_matrix_s g, m, gh, ghm;   // views into the scratch (never destroyed)
-    uint64_t rows128;
-};
+// (struct DosageSplit: storm_hip_internal.h — the top-k calls take panels of its matrices)
 // the words of one matrix of the split (rows128 rows of the source's stride); refuses what the split's launch grid cannot hold
 static int dosage_split_words(const storm_hip_matrix_s* x, uint64_t* words) {
     const uint64_t rows128 = (x->n_rows + kThTile - 1) / kThTile * kThTile;
@@ -433,7 +430,7 @@ static int check_dosage(const char* who, const storm_hip_matrix_s* m, const void
     }
     return STORM_HIP_OK;
 }
-static int check_samples(const char* who, const storm_hip_matrix_s* m, uint64_t n_samples) {
+int check_samples(const char* who, const storm_hip_matrix_s* m, uint64_t n_samples) {
     if (n_samples == 0 || (n_samples + 31u) / 32u != m->n_words) {
         set_error("%s: %llu samples do not fill rows of %u words (32 values per word)", who, (unsigned long long)n_samples,
                   m->n_words);
@@ -449,7 +446,7 @@ static int check_corr(const char* who, const storm_hip_matrix_s* m, int measure,
     return check_samples(who, m, n_samples);
 }
 // the rectangle of two dosage matrices: rows of the same width
-static int check_square(const char* who, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, const void* out, uint64_t ld) {
+int check_square(const char* who, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, const void* out, uint64_t ld) {
     if (!a || !b || !out) {
         set_error("%s: NULL argument", who);
         return STORM_HIP_EINVAL;
@@ -561,10 +558,8 @@ __global__ __launch_bounds__(256) void dosage_square_complete_finish_kernel(uint
 }
 
 // the sums of both matrices' rows into the context's row-count scratch, 2 (n_a + n_b) words: A's s and q, then B's; queued
-struct SquareSums {
-    const uint32_t *a_sum, *a_sq, *b_sum, *b_sq;
-};
-static int dosage_square_sums_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, SquareSums* out) {
+// (struct SquareSums: storm_hip_internal.h)
+int dosage_square_sums_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, SquareSums* out) {
     const uint64_t na = a->n_rows, nb = b->n_rows;
     if (int rc = ctx->d_counts.ensure(2 * (na + nb) * sizeof(uint32_t), "square_dosage_corr: the row-sum scratch")) return rc;
     uint32_t* const d = ctx->d_counts.d;
@@ -601,8 +596,8 @@ static int square_dosage_corr_queued(storm_hip_ctx_t* ctx, const storm_hip_matri
 
 // The splits of both matrices side by side in ctx->d_dosage_rows (A's three matrices, then B's; one split when b is a),
 // queued. The buffer is sized for both before either kernel starts: growing it drops what it held.
-static int dosage_split_pair_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, uint64_t n_samples,
-                                    DosageSplit* sa, DosageSplit* sb) {
+int dosage_split_pair_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, uint64_t n_samples,
+                             DosageSplit* sa, DosageSplit* sb) {
     uint64_t words_a = 0, words_b = 0;
     if (int rc = dosage_split_words(a, &words_a)) return rc;
     if (b != a)

@@ -571,3 +571,27 @@ struct storm_hip_matrix_s {
     uint64_t generation = 0;    // changes with every mutation through the library (see "keep_shadow")
     bool sparse_origin = false; // the dense replica of a sparse container (storm_hip_matrix_create_from_blocks): mostly zeros
 };
+
+namespace storm {
+
+// ---- what the dosage top-k calls (storm_hip_topk.hip) take from storm_hip_dosage.hip ----
+// the refusals the dosage calls share: n_samples that does not fill the rows; the rectangle's NULL arguments, widths that
+// differ, ld < b's rows, rows of more than 2^24 values
+int check_samples(const char* who, const storm_hip_matrix_s* m, uint64_t n_samples);
+int check_square(const char* who, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, const void* out, uint64_t ld);
+// the sums of both matrices' rows in the context's row-count scratch, 2 (n_a + n_b) words: A's s and q, then B's; queued
+struct SquareSums {
+    const uint32_t *a_sum, *a_sq, *b_sum, *b_sq;
+};
+int dosage_square_sums_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, SquareSums* out);
+// The split operands of a matrix with missing genotypes: G, H and M as matrices of rows128 = n_rows up to the next multiple
+// of 128 rows each (zero rows behind n_rows), adjacent in that order, so that [G ; H] and [G ; H ; M] are one matrix each.
+struct DosageSplit {
+    storm_hip_matrix_s g, m, gh, ghm;   // views into the scratch (never destroyed)
+    uint64_t rows128;
+};
+// the splits of both matrices side by side in ctx->d_dosage_rows (one split when b is a: *sb = *sa), queued
+int dosage_split_pair_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, uint64_t n_samples,
+                             DosageSplit* sa, DosageSplit* sb);
+
+}  // namespace storm

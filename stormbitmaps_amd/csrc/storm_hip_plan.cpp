@@ -1228,6 +1228,21 @@ bool stage_list_readable(const std::vector<uint64_t>& written, uint64_t token, u
     return off + n * 2u <= written[chunk];                      // not in the gap, not across the chunk's end
 }
 
+uint64_t dosage_topk_plane_words(uint64_t n_b, bool complete) {
+    const uint64_t ld = (n_b + 3u) / 4u * 4u;
+    if (!complete) return ld;
+    const uint64_t rows128 = (n_b + kThTile - 1) / kThTile * kThTile;
+    return ld + 2 * ld + (2 * rows128 + ld);   // P, G_p M_b and H_p M_b, M_p x [G_b ; H_b ; M_b]
+}
+
+uint64_t dosage_topk_panel_rows(uint64_t panel_rows, uint64_t n_rows, uint64_t plane_words_per_row) {
+    if (panel_rows == 0) {
+        const uint64_t row_bytes = std::max<uint64_t>(plane_words_per_row, 1u) * sizeof(uint32_t);
+        panel_rows = std::max<uint64_t>(256u, kTopkPanelBytes / row_bytes / 256u * 256u);
+    }
+    return std::min<uint64_t>(panel_rows, (n_rows + 255u) / 256u * 256u);
+}
+
 }  // namespace storm
 
 // a K2h list as the 8-word records of storm_hip_matrix_plan / storm_hip_lag_plan (out == NULL: the count alone)

@@ -439,4 +439,14 @@ void stage_note_list(std::vector<uint64_t>* written, uint64_t token, uint32_t n)
 // points into the middle of a staged list is in bounds: yes.)
 bool stage_list_readable(const std::vector<uint64_t>& written, uint64_t token, uint64_t n);
 
+// ---- the row panels of the dosage top-k calls (storm_hip_topk.hip: dosage_topk_queued) ----
+// A panel's planes hold `plane_words_per_row` uint32 per panel row: dosage_topk_plane_words — the plain form's one plane of
+// ld = n_b up to the next multiple of 4 words; the complete form's P, the two planes G_p M_b and H_p M_b of the same pitch
+// and M_p x [G_b ; H_b ; M_b] of 2 rows128_b + ld words (rows128_b: n_b up to the next multiple of 128), about 6 n_b.
+constexpr uint64_t kTopkPanelBytes = 256ull << 20;
+uint64_t dosage_topk_plane_words(uint64_t n_b, bool complete);
+// Rows per panel: `panel_rows` as given (a multiple of 256: the caller has checked), or for 0 the largest multiple of 256
+// whose planes hold at most kTopkPanelBytes, at least 256; never more than n_rows rounded up to 256.
+uint64_t dosage_topk_panel_rows(uint64_t panel_rows, uint64_t n_rows, uint64_t plane_words_per_row);
+
 }  // namespace storm
