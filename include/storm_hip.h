@@ -678,7 +678,10 @@ int storm_hip_column_identity(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m,
  *   key "seg_rows": K1 B rows per work item (default 256)
  *   key "chunks_per_item": K1 k-chunks (64 words each) per work item, 0 = auto
  *   key "k2_stages_per_item": K2 tile kernel k-slice length in 128-bit stages (default 32)
- *   keys "k2_max_run" (128), "k2_tail_slices" (3), "k2_tail_run" (32): strip work-list shaping;
+ *   keys "k2_max_run" (128), "k2_tail_slices" (3), "k2_tail_run" (32): strip work-list shaping; once either tail key
+ *        is set on a context both hold as they stand, until then the 128-rows-per-wave strips choose them for one
+ *        device's whole pass; read-only "k2_max_run_used", "k2_tail_run_used", "k2_tail_slices_used": the shaping of
+ *        the strip list planned last (0 before the first);
  *        "k2_persistent" (0): per-XCD work queues; "k2_ring" (4): LDS ring depth 3..5;
  *        "k2_pitch_pad" (-1 = auto): extra bytes per shadow row; "k2_lds_pad": cap workgroups per CU;
  *        "k2_matrix_split" (1): cut the last round of matrix-output tiles along k;
@@ -768,8 +771,13 @@ int storm_hip_strip_plan2(uint64_t n_rows, uint32_t n_words, uint32_t shard_rank
  * launches for this shard: one function derives the shaping for the device path and for this planner. max_run = 0
  * selects the run length automatically (64 / 96 / 128, whichever schedules the SLOWEST of the shard_count ranks
  * shortest: the choice never depends on shard_rank, so that all ranks cut the slices they deal among themselves at
- * the same length); *run_chosen (may be NULL) receives the run length used. storm_hip_strip_plan2 = the defaults
- * (max_run 0, tail_run 32, tail_slices 3, lpt_rounds 6, 256 compute units). */
+ * the same length); *run_chosen (may be NULL) receives the run length used.
+ * tail_run = 0 stands for a context on which neither k2_tail_run nor k2_tail_slices was set (tail_slices is then not
+ * read): form 2 with shard_count 1 chooses run length and tail together, from a fixed set of candidates by a model of
+ * what an XCD makes of its list, and orders its items by what they cost in that model; every other list
+ * takes tail_run 32 and tail_slices 3. *run_chosen then receives max_run | tail_run << 16 | tail_slices << 24 as used.
+ * tail_run >= 1 gives the list of a context with both options set to these values.
+ * storm_hip_strip_plan2 = the defaults (max_run 0, no tail set, lpt_rounds 6, 256 compute units). */
 int storm_hip_strip_plan3(uint64_t n_rows, uint32_t n_words, uint32_t shard_rank, uint32_t shard_count,
                           int form, int pair_space, int max_run, int tail_run, int tail_slices, int lpt_rounds,
                           uint32_t n_cus, uint32_t* out, uint64_t capacity_items, uint64_t* n_items,

@@ -643,6 +643,8 @@ struct OptionRow {
     void (*after)(storm_hip_ctx_t* ctx, int64_t value);   // runs behind the store (the value as it was given)
 };
 
+// k2_tail_slices / k2_tail_run: once either is set, the planner of the 128-rows-per-wave form chooses neither
+static void tail_is_set(storm_hip_ctx_t* ctx, int64_t) { ctx->k2_tail_set = 1; }
 static void drop_shadow(storm_hip_ctx_t* ctx, int64_t) { memset(ctx->x4_key, 0, sizeof(ctx->x4_key)); }
 // time_kernels 1: start a new series of bracketed launches; 0: pause (the series is kept for storm_hip_kernel_time);
 // 2: resume it (bench.py brackets every 4th step at N > 1)
@@ -747,8 +749,8 @@ static const std::vector<OptionRow>& option_table() {
         {"k2_persistent", &C::k2_persistent, BOOL, 0, 0, 0, {}, nullptr, {1},
          "k2_persistent (strip_fp4_kernel with work queues) is a form of the tools build (`make probes`), not of the shipped library"},
         {"k2_lpt_rounds", &C::k2_lpt_rounds, RANGE, 0, 63, 0, {}, "k2_lpt_rounds must be 0..63"},
-        {"k2_tail_slices", &C::k2_tail_slices, RANGE, 0, 255, 0, {}, "k2_tail_slices must be 0..255"},
-        {"k2_tail_run", &C::k2_tail_run, RANGE, 1, 4096, 0, {}, "k2_tail_run must be 1..4096"},
+        {"k2_tail_slices", &C::k2_tail_slices, RANGE, 0, 255, 0, {}, "k2_tail_slices must be 0..255", {}, nullptr, nullptr, tail_is_set},
+        {"k2_tail_run", &C::k2_tail_run, RANGE, 1, 4096, 0, {}, "k2_tail_run must be 1..4096", {}, nullptr, nullptr, tail_is_set},
         {"k2_debug", &C::k2_debug, HOOK, 0, 0, 0, {}, nullptr, {}, nullptr, set_debug},
         {"time_kernels", &C::time_kernels, BOOL, 0, 0, 0, {}, nullptr, {}, nullptr, nullptr, restart_series},
         {"chunks_per_item", &C::chunks_per_item, RANGE, 0, 4096, 0, {}, "chunks_per_item out of range"},
@@ -801,6 +803,9 @@ int64_t storm_hip_ctx_get_option(storm_hip_ctx_t* ctx, const char* key) {
     if (!strcmp(key, "k2_operands_used")) return ctx->k2_operands_used;
     if (!strcmp(key, "k2_strip_rows_used")) return ctx->k2_strip_rows_used;
     if (!strcmp(key, "k2_tile_shape_used")) return ctx->k2_tile_shape_eff;
+    if (!strcmp(key, "k2_max_run_used")) return ctx->k2_max_run_used;
+    if (!strcmp(key, "k2_tail_run_used")) return ctx->k2_tail_run_used;
+    if (!strcmp(key, "k2_tail_slices_used")) return ctx->k2_tail_slices_used;
     if (!strcmp(key, "n_cus")) return ctx->n_cus;
     if (!strcmp(key, "probes_build") || !strcmp(key, "probes_built")) return kToolsBuild;
     return -1;

@@ -266,6 +266,8 @@ struct storm_hip_ctx_s {
     int k2_lpt_rounds = 6;  // K2s: XCD lists of at most this many rounds of 128 items are sorted longest-first
     int k2_tail_slices = 3; // K2s: last slices of every XCD's list are cut into short runs ...
     int k2_tail_run = 32;   //      ... of at most this many stages, merged longest-first
+    int k2_tail_set = 0;    // the caller has set k2_tail_slices or k2_tail_run: the 128-rows-per-wave form's planner then takes both as they are (otherwise it chooses them with the run length: choose_strip_shaping)
+    int k2_max_run_used = 0, k2_tail_run_used = 0, k2_tail_slices_used = 0;   // the shaping of the strip list planned last (0: none yet)
     // "time_kernels" option: HIP event pairs around the dominant kernel of every pairwise launch
     // (the popcount kernel, the tile kernel or the strip kernel), read by storm_hip_kernel_time
     int time_kernels = 0;

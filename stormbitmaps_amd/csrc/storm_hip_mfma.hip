@@ -1650,11 +1650,13 @@ static int ensure_items(storm_hip_ctx_t* ctx, const std::vector<RowRange>& range
 
 // The strip list of an all-pairs pass (plan_strips, storm_hip_plan.cpp), cached by its request: the context's shaping
 // options, the shape and the shard.
-static StripOptions strip_options_of(const storm_hip_ctx_t* ctx, int xcd_group) {
+static StripOptions strip_options_of(const storm_hip_ctx_t* ctx, int xcd_group, bool rows_form) {
     StripOptions o;
     o.max_run = ctx->k2_max_run;
     o.tail_run = ctx->k2_tail_run;
     o.tail_slices = ctx->k2_tail_slices;
+    o.rows_form = rows_form;
+    o.tail_auto = rows_form && !ctx->k2_tail_set;   // (the planner chooses the tail for one device's whole pass only)
     o.lpt_rounds = ctx->k2_lpt_rounds;
     o.shard_pairs = ctx->k2_shard_pairs != 0;
     o.n_cus = ctx->n_cus;
@@ -1666,12 +1668,16 @@ static StripOptions strip_options_of(const storm_hip_ctx_t* ctx, int xcd_group) 
 
 static int ensure_strip_items(storm_hip_ctx_t* ctx, const std::vector<RowRange>& ranges,
                               uint32_t n_kslices, uint32_t shard_rank, uint32_t shard_count,
-                              uint32_t a_tile, int xcd_group = 1) {
-    const StripRequest rq = strip_request(strip_options_of(ctx, xcd_group), ranges, n_kslices, shard_rank, shard_count, a_tile);
-    if (ctx->strips.holds(rq)) return STORM_HIP_OK;
+                              uint32_t a_tile, int xcd_group = 1, bool rows_form = false) {
+    const StripRequest rq = strip_request(strip_options_of(ctx, xcd_group, rows_form), ranges, n_kslices, shard_rank, shard_count, a_tile);
+    if (ctx->strips.holds(rq)) return STORM_HIP_OK;   // (k2_*_used are still this list's: nothing else writes them)
     ctx->strips.forget();   // (the queue bounds below are the new list's)
     std::vector<StripItem> items;
-    plan_strips(rq, ranges, items, ctx->strips.queue_base, ctx->strips.queue_count);
+    StripChoice used;
+    plan_strips(rq, ranges, items, ctx->strips.queue_base, ctx->strips.queue_count, &used);
+    ctx->k2_max_run_used = used.max_run;
+    ctx->k2_tail_run_used = used.tail_run;
+    ctx->k2_tail_slices_used = used.tail_slices;
     if (items.size() >= (1ull << 31)) {
         set_error("K2s: %zu strip items exceed the grid limit", items.size());
         return STORM_HIP_EINVAL;
@@ -2497,7 +2503,7 @@ int launch_pairw_bits_ranges(storm_hip_ctx_t* ctx, const uint8_t* X, uint64_t pi
         set_error("K2b: the 128-rows-per-wave form takes A tiles of 512 rows");
         return STORM_HIP_EINVAL;
     }
-    if (int rc = ensure_strip_items(ctx, ranges, n_kslices2, shard_rank, shard_count, a_tile, rows128 ? (int)kStripRowsXcdGroup : 2))
+    if (int rc = ensure_strip_items(ctx, ranges, n_kslices2, shard_rank, shard_count, a_tile, rows128 ? (int)kStripRowsXcdGroup : 2, rows128))
         return rc;
     const uint32_t n_strip = ctx->strips.n;
     const uint32_t waves = rows128 ? 4u : a_tile / (uint32_t)kStripBRows;   // 4, or 8 for the 512-row form (strip16_bits2_kernel)
@@ -2684,7 +2690,7 @@ static int pairw_bits_upload_queue(storm_hip_ctx_t* ctx, storm_hip_matrix_s* m, 
                                        ctx->copy_stream));
         STORM_HIP_TRY(hipEventRecord(l.landed, ctx->copy_stream));
         // (a fixed run length: a panel's list is short and all tail)
-        StripOptions po = strip_options_of(ctx, 2);
+        StripOptions po = strip_options_of(ctx, 2, false);
         po.max_run = 128;
         po.shard_pairs = po.persistent = po.one_slice_probe = 0;
         RowRange rg{0, row1};

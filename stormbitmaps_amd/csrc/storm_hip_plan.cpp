@@ -105,7 +105,47 @@ struct StripShaping {  // work-list shaping knobs: StripOptions with the run len
     // its share of the tile pairs over all of k). Option k2_shard_pairs; rehearsed side by side in
     // tools/bench_shards.py.
     bool pair_space = false;
+    // The rows form with its tail chosen (choose_strip_shaping): longest first means by what the kernel issues for an item
+    // below n_rows (strip_rows_item_mfmas: a resident diagonal is 4 1/8 stages, not 8), and the estimate is strip_rows_makespan.
+    bool rows_cost = false;
+    uint32_t n_rows = kStripRowsNoTrim;
 };
+// One slice = every A tile against the B blocks behind it; `max_run` caps the stages per item.
+static void emit_strip_slice(const std::vector<RowRange>& ranges, uint32_t a_tile, uint32_t ks_data, uint32_t max_run,
+                             std::vector<StripItem>& dst) {
+    const uint32_t kPerTile = a_tile / kStripBRows;
+    for (const RowRange& rg : ranges) {
+        if (rg.back_from != ~0ull) {   // a row panel that has just arrived: its tiles against everything in front of them
+            const uint32_t blk0 = (uint32_t)(rg.r0 / kStripBRows);
+            for (uint64_t a0 = rg.back_from; a0 < rg.r1; a0 += a_tile) {
+                const uint32_t a_row0 = (uint32_t)a0, end = (uint32_t)(a0 / kStripBRows);
+                if (end <= blk0) {
+                    dst.push_back({a_row0, 1, end, end, ks_data});
+                    continue;
+                }
+                for (uint32_t j0 = blk0; j0 < end; j0 += max_run)
+                    dst.push_back({a_row0, (uint32_t)(j0 == blk0), j0, std::min(end, j0 + max_run), ks_data});
+            }
+            continue;
+        }
+        // A tiles of a_tile rows from the start of the range (the rows between r1 and
+        // the end of its last A tile are zero: the caller pads ranges accordingly)
+        const uint64_t a_rows = (rg.a_end ? std::min(rg.a_end, rg.r1) : rg.r1) - rg.r0;  // A tiles only below a_end
+        const uint32_t nA = (uint32_t)((a_rows + a_tile - 1) / a_tile);
+        const uint32_t jend = (uint32_t)((rg.r1 + kStripBRows - 1) / kStripBRows);  // absolute
+        for (uint32_t i = 0; i < nA; ++i) {
+            const uint32_t a_row0 = (uint32_t)rg.r0 + i * a_tile;
+            const uint32_t first = a_row0 / (uint32_t)kStripBRows + kPerTile;
+            if (first >= jend) {  // last tile of the range: only its own triangle
+                dst.push_back({a_row0, 1, first, first, ks_data});
+                continue;
+            }
+            for (uint32_t j0 = first; j0 < jend; j0 += max_run)
+                dst.push_back({a_row0, (uint32_t)(j0 == first), j0,
+                               std::min(jend, j0 + max_run), ks_data});
+        }
+    }
+}
 // Pure host computation (no device): the list, in launch order, and for the persistent form the
 // per-XCD queue bounds.
 static void build_strip_items(const StripShaping& sh, const std::vector<RowRange>& ranges,
@@ -126,43 +166,11 @@ static void build_strip_items(const StripShaping& sh, const std::vector<RowRange
     const uint32_t xg = (uint32_t)std::max(1, sh.xcd_group);
     for (uint32_t ks = 0; ks < modulo_slices; ++ks)
         if (pair_mode || strip_owns_slice(ks, shard_rank, shard_count)) slices_of[(local++ / xg) % 8].push_back(ks);
-    // One slice = every A tile against the B blocks behind it; `max_run` caps the stages per item.
     std::vector<uint64_t> pair_load(shard_count, 0);  // pair mode: stages dealt to every shard so far
     auto emit_slice_all = [&](uint32_t ks, uint32_t max_run, std::vector<StripItem>& dst) {
         // k2_debug & 16 (timing probe, wrong results): every XCD re-reads one k-slice, i.e. the
         // launch as it would run if nothing ever missed in L2
-        const uint32_t ks_data = sh.one_slice_probe ? ks % 8u : ks;
-        for (const RowRange& rg : ranges) {
-            if (rg.back_from != ~0ull) {   // a row panel that has just arrived: its tiles against everything in front of them
-                const uint32_t blk0 = (uint32_t)(rg.r0 / kStripBRows);
-                for (uint64_t a0 = rg.back_from; a0 < rg.r1; a0 += a_tile) {
-                    const uint32_t a_row0 = (uint32_t)a0, end = (uint32_t)(a0 / kStripBRows);
-                    if (end <= blk0) {
-                        dst.push_back({a_row0, 1, end, end, ks_data});
-                        continue;
-                    }
-                    for (uint32_t j0 = blk0; j0 < end; j0 += max_run)
-                        dst.push_back({a_row0, (uint32_t)(j0 == blk0), j0, std::min(end, j0 + max_run), ks_data});
-                }
-                continue;
-            }
-            // A tiles of a_tile rows from the start of the range (the rows between r1 and
-            // the end of its last A tile are zero: the caller pads ranges accordingly)
-            const uint64_t a_rows = (rg.a_end ? std::min(rg.a_end, rg.r1) : rg.r1) - rg.r0;  // A tiles only below a_end
-            const uint32_t nA = (uint32_t)((a_rows + a_tile - 1) / a_tile);
-            const uint32_t jend = (uint32_t)((rg.r1 + kStripBRows - 1) / kStripBRows);  // absolute
-            for (uint32_t i = 0; i < nA; ++i) {
-                const uint32_t a_row0 = (uint32_t)rg.r0 + i * a_tile;
-                const uint32_t first = a_row0 / (uint32_t)kStripBRows + kPerTile;
-                if (first >= jend) {  // last tile of the range: only its own triangle
-                    dst.push_back({a_row0, 1, first, first, ks_data});
-                    continue;
-                }
-                for (uint32_t j0 = first; j0 < jend; j0 += max_run)
-                    dst.push_back({a_row0, (uint32_t)(j0 == first), j0,
-                                   std::min(jend, j0 + max_run), ks_data});
-            }
-        }
+        emit_strip_slice(ranges, a_tile, sh.one_slice_probe ? ks % 8u : ks, max_run, dst);
     };
     // Every slice holds the same items but for its slice number: the list of one slice is built (and, for the long runs,
     // sorted longest first) ONCE per run length and copied with the number filled in — built and sorted slice by slice,
@@ -171,15 +179,31 @@ static void build_strip_items(const StripShaping& sh, const std::vector<RowRange
     const uint32_t kTailLen = std::min(kMaxRun, kTailRun);
     std::vector<StripItem> proto_main, proto_tail;
     bool have_main = false, have_tail = false;
-    auto by_length = [&](const StripItem& p, const StripItem& q) {
-        return (p.j1 - p.j0) + p.diag * kPerTile > (q.j1 - q.j0) + q.diag * kPerTile;
+    // (rows_cost: MFMAs; a diagonal's by the tile's blocks that hold a row, counted once per block count)
+    uint32_t diag_mfmas[kStripRowsBlocks + 1] = {};
+    if (sh.rows_cost)
+        for (uint32_t nb = 0; nb <= kStripRowsBlocks; ++nb) diag_mfmas[nb] = strip_rows_item_mfmas(0, 1, 0, 0, nb * (uint32_t)kStripBRows);
+    auto length_of = [&](const StripItem& p) -> uint32_t {
+        if (!sh.rows_cost) return (p.j1 - p.j0) + p.diag * kPerTile;
+        return strip_rows_item_mfmas(p.a_row0, 0, p.j0, p.j1, sh.n_rows) + (p.diag ? diag_mfmas[strip_rows_real_blocks(p.a_row0, sh.n_rows)] : 0u);
+    };
+    auto by_length = [&](const StripItem& p, const StripItem& q) { return length_of(p) > length_of(q); };
+    auto longest_first = [&](std::vector<StripItem>& v) {
+        if (!sh.rows_cost) return std::stable_sort(v.begin(), v.end(), by_length);
+        // (what an item costs in the model is worked out once per item, not once per comparison)
+        std::vector<std::pair<uint32_t, uint32_t>> order(v.size());
+        for (size_t k = 0; k < v.size(); ++k) order[k] = {length_of(v[k]), (uint32_t)k};
+        std::stable_sort(order.begin(), order.end(), [](const auto& p, const auto& q) { return p.first > q.first; });
+        std::vector<StripItem> sorted(v.size());
+        for (size_t k = 0; k < v.size(); ++k) sorted[k] = v[order[k].second];
+        v.swap(sorted);
     };
     auto emit_copy = [&](uint32_t ks, uint32_t max_run, std::vector<StripItem>& dst) {
         std::vector<StripItem>& proto = max_run == kMaxRun ? proto_main : proto_tail;
         bool& have = max_run == kMaxRun ? have_main : have_tail;
         if (!have) {
             emit_slice_all(0u, max_run, proto);
-            if (max_run == kMaxRun) std::stable_sort(proto.begin(), proto.end(), by_length);
+            if (max_run == kMaxRun) longest_first(proto);
             have = true;
         }
         const uint32_t ks_data = sh.one_slice_probe ? ks % 8u : ks;
@@ -251,19 +275,14 @@ static void build_strip_items(const StripShaping& sh, const std::vector<RowRange
         std::vector<StripItem> tail;
         for (size_t k = n_main; k < sl.size(); ++k) emit_slice(sl[k], std::min(kMaxRun, kTailRun), tail);
         tail.insert(tail.end(), leftover_of[x].begin(), leftover_of[x].end());
-        std::stable_sort(tail.begin(), tail.end(), [&](const StripItem& p, const StripItem& q) {
-            return (p.j1 - p.j0) + p.diag * kPerTile > (q.j1 - q.j0) + q.diag * kPerTile;
-        });
+        longest_first(tail);
         per_xcd[x].insert(per_xcd[x].end(), tail.begin(), tail.end());
         // A short list (a few rounds of the XCD's ~128 slots: small N, or a 1/8 shard) is all
         // tail: order the whole of it longest-first. The L2 locality that slice-major order buys
         // is worth 1-2 %, the tail of a 2-round launch a third of its time (N = 2048: the
         // schedule trace showed the launch draining for 24 of its 66 us).
         if (per_xcd[x].size() <= (size_t)128 * (size_t)std::max(0, sh.lpt_rounds))
-            std::stable_sort(per_xcd[x].begin(), per_xcd[x].end(),
-                             [&](const StripItem& p, const StripItem& q) {
-                                 return (p.j1 - p.j0) + p.diag * kPerTile > (q.j1 - q.j0) + q.diag * kPerTile;
-                             });
+            longest_first(per_xcd[x]);
     }
     if (makespan) {
         // List-scheduling estimate of the launch, in stage times: an XCD hands its list, in order, to its workgroup
@@ -306,6 +325,131 @@ static void build_strip_items(const StripShaping& sh, const std::vector<RowRange
     }
 }
 
+// The rows form's tail, chosen with the run length: one device's whole pass, neither k2_tail_run nor k2_tail_slices set.
+// `now` is the shaping such a pass always had — the run length above (or the caller's), the last 3 slices in runs of 32 —
+// and stays unless one of kStripRowsShapings models at least 0.5 % shorter than the choice so far (the near-tie rule of
+// the run length). Where it stays the list is the one the pass always had, byte for byte; a list of another shaping is
+// ordered by what its items cost in the model (rows_cost).
+// The model (strip_rows_makespan, storm_hip_plan.h) walks the list of the XCD that gets the most slices, a compute unit
+// holding 4 workgroups of the kernel. No list is built for it: a slice's items cut at the main and at the tail length,
+// each sorted as the list will have them, give every position of the XCD's list — the main slices one behind another, then
+// every item of the tail's sorted slice once per tail slice. Of a long list only the last kStripRowsWalkRounds rounds are
+// walked, from the middle of a launch: everything in front of them is taken to have kept every pipe busy, and at the start
+// of the walk every slot holds a workgroup whose work left is spread evenly up to an item of the walk's first round — on a
+// compute unit whose four workgroups share the pipe, items of one length end a quarter of their time apart, and the compute
+// units a fraction of that apart. (All slots free at once would walk the rounds in step, which no launch does behind its
+// first.) A list whose front holds less than twice that work is walked whole, from an empty XCD.
+constexpr size_t kStripRowsWalkRounds = 4;
+static StripShaping choose_rows_tail(const StripShaping& now, const std::vector<RowRange>& ranges, uint32_t n_kslices, uint32_t a_tile,
+                                     uint32_t slots_per_xcd, bool run_is_set) {
+    const bool timing = timing_env();
+    uint32_t n_rows = kStripRowsNoTrim;   // (where the launcher tells the kernel that the rows end)
+    if (ranges.size() == 1 && ranges[0].r0 == 0 && ranges[0].a_end == 0 && ranges[0].back_from == ~0ull && ranges[0].r1 < (uint64_t)kStripRowsNoTrim)
+        n_rows = (uint32_t)ranges[0].r1;
+    // the slices of the XCD that gets the most: whole units in turn, the leftover ones (cut like the tail) behind them
+    uint32_t whole[8] = {}, left_over[8] = {}, local = 0;
+    const uint32_t modulo_slices = strip_modulo_slices(n_kslices, 1), xg = (uint32_t)std::max(1, now.xcd_group);
+    for (uint32_t ks = 0; ks < n_kslices; ++ks) ++(ks < modulo_slices ? whole : left_over)[(local++ / xg) % 8];
+    uint32_t x = 0;
+    for (uint32_t i = 1; i < 8; ++i)
+        if (whole[i] + left_over[i] > whole[x] + left_over[x]) x = i;
+    // a slice cut at `run`, in the order of the list: what each item costs (stages), longest first by the list's key
+    struct SliceCosts {
+        uint32_t run;
+        bool rows_cost;
+        std::vector<double> cost;
+        double sum;
+    };
+    std::vector<SliceCosts> slices;
+    slices.reserve(16);
+    auto slice_costs = [&](uint32_t run, bool rows_cost) -> const SliceCosts& {
+        for (const SliceCosts& sc : slices)
+            if (sc.run == run && sc.rows_cost == rows_cost) return sc;
+        std::vector<StripItem> items;
+        emit_strip_slice(ranges, a_tile, 0u, run, items);
+        std::vector<std::pair<uint32_t, uint32_t>> keyed(items.size());   // (the list's key, MFMAs)
+        for (size_t k = 0; k < items.size(); ++k) {
+            const StripItem& it = items[k];
+            const uint32_t mfmas = strip_rows_item_mfmas(it.a_row0, it.diag, it.j0, it.j1, n_rows);
+            keyed[k] = {rows_cost ? mfmas : (it.j1 - it.j0) + it.diag * (a_tile / (uint32_t)kStripBRows), mfmas};
+        }
+        std::stable_sort(keyed.begin(), keyed.end(), [](const auto& p, const auto& q) { return p.first > q.first; });
+        slices.push_back({run, rows_cost, {}, 0.0});
+        SliceCosts& sc = slices.back();
+        sc.cost.resize(keyed.size());
+        for (size_t k = 0; k < keyed.size(); ++k) sc.sum += sc.cost[k] = (double)keyed[k].second / kStripRowsStageMfmas;
+        return sc;
+    };
+    struct Walk {
+        std::vector<double> cost, resident;
+        double t0 = 0, makespan = 0;
+    };
+    std::vector<Walk> walks;   // (candidates whose lists end alike — a long tail behind any run length — are walked once)
+    walks.reserve(8);
+    const uint32_t n_cus = std::max<uint32_t>(1, slots_per_xcd / 4u), n_slots = n_cus * 4u;
+    auto model = [&](const StripShaping& sh) {
+        const uint32_t run = (uint32_t)std::min(4096, std::max(1, sh.max_run));
+        const SliceCosts& main = slice_costs(run, sh.rows_cost);
+        const SliceCosts& tail = slice_costs(std::min(run, (uint32_t)std::min(4096, std::max(1, sh.tail_run))), sh.rows_cost);
+        const size_t n_main = whole[x] > (uint32_t)std::max(0, sh.tail_slices) ? whole[x] - (uint32_t)sh.tail_slices : 0;
+        const size_t n_tail = whole[x] - n_main + left_over[x];
+        const size_t in_main = n_main * main.cost.size(), n_list = in_main + n_tail * tail.cost.size();
+        walks.emplace_back();
+        Walk& w = walks.back();
+        if (n_list == 0) return 0.0;
+        auto at = [&](size_t k) { return k < in_main ? main.cost[k % main.cost.size()] : tail.cost[(k - in_main) / n_tail]; };
+        size_t start = n_list > kStripRowsWalkRounds * (size_t)n_slots ? n_list - kStripRowsWalkRounds * (size_t)n_slots : 0;
+        if (n_list <= (size_t)128 * (size_t)std::max(0, sh.lpt_rounds)) start = 0;   // (a short list: all of it longest first)
+        for (int pass = 0; pass < 2; ++pass) {
+            w.cost.resize(n_list - start);
+            double walked = 0;
+            for (size_t k = start; k < n_list; ++k) walked += w.cost[k - start] = at(k);
+            if (start == 0) break;
+            const double before = main.sum * (double)(n_main + n_tail) - walked;   // (a slice holds the same work however it is cut)
+            double round = 0, held = 0;
+            for (uint32_t k = 0; k < n_slots; ++k) round += w.cost[k];
+            round /= (double)n_slots;
+            w.resident.resize(n_slots);
+            for (uint32_t c = 0; c < n_cus; ++c)
+                for (uint32_t s = 0; s < 4u; ++s) held += w.resident[c * 4u + s] = round * ((double)s + (double)(c + 1u) / (double)n_cus) / 4.0;
+            if (before >= 2.0 * held) {
+                w.t0 = (before - held) / (double)n_cus;
+                break;
+            }
+            w.resident.clear();
+            start = 0;
+        }
+        if (n_list <= (size_t)128 * (size_t)std::max(0, sh.lpt_rounds)) std::sort(w.cost.begin(), w.cost.end(), std::greater<double>());
+        for (size_t seen = 0; seen + 1 < walks.size(); ++seen)
+            if (walks[seen].t0 == w.t0 && walks[seen].cost == w.cost && walks[seen].resident == w.resident) return w.makespan = walks[seen].makespan;
+        return w.makespan = strip_rows_makespan(w.cost.data(), w.cost.size(), n_cus, 4u, kStripRowsStartStages, w.t0,
+                                                w.resident.empty() ? nullptr : w.resident.data());
+    };
+    StripShaping best = now;
+    double best_ms = model(now);
+    if (timing)
+        fprintf(stderr, "[strip plan] rows form, max_run %3d tail_run %2d tail_slices %2d (as it was): modelled makespan %.1f stages\n",
+                now.max_run, now.tail_run, now.tail_slices, best_ms);
+    for (const StripChoice& cand : kStripRowsShapings) {
+        if (run_is_set && cand.max_run != kStripRowsShapings[0].max_run) continue;   // a set run length: the tails alone, once each
+        StripShaping trial = now;
+        trial.rows_cost = true;
+        trial.n_rows = n_rows;
+        if (!run_is_set) trial.max_run = cand.max_run;
+        trial.tail_run = cand.tail_run;
+        trial.tail_slices = cand.tail_slices;
+        const double ms = model(trial);
+        if (timing)
+            fprintf(stderr, "[strip plan] rows form, max_run %3d tail_run %2d tail_slices %2d: modelled makespan %.1f stages\n",
+                    trial.max_run, trial.tail_run, trial.tail_slices, ms);
+        if (ms < best_ms * 0.995) {   // (ties and near-ties go to the earlier candidate)
+            best = trial;
+            best_ms = ms;
+        }
+    }
+    return best;
+}
+
 // The shaping a pass runs with, from the options alone — NEVER from the calling rank. Where ownership is dealt along
 // the pair space (k2_shard_pairs, and the leftover slices of the default mode) every rank replays the same deal of
 // the same items, so every rank must cut the slices at the same run length: a choice made from one rank's own list
@@ -324,11 +468,13 @@ static StripShaping choose_strip_shaping(const StripOptions& o, const std::vecto
     sh.one_slice_probe = o.one_slice_probe != 0;
     sh.pair_space = o.shard_pairs != 0;
     sh.max_run = o.max_run;
-    if (o.max_run != 0) return sh;
-    // auto: the run length whose list schedules shortest (the tail of the launch decides between them: N = 6144 is
-    // 6 % faster with 64, N = 7168 / 8192 with 96, N = 3072 with 128; tools/archive/sweep_maxrun.py)
     const uint32_t slots = (uint32_t)std::max(1, o.n_cus / 8 * 4);
     const bool timing = timing_env();
+    // (the rows form, one device's whole pass, no tail set: the tail is chosen too, behind the run length)
+    const bool rows_tail = o.rows_form && o.tail_auto && shard_count == 1;
+    if (o.max_run != 0) return rows_tail ? choose_rows_tail(sh, ranges, n_kslices, a_tile, slots, true) : sh;
+    // auto: the run length whose list schedules shortest (the tail of the launch decides between them: N = 6144 is
+    // 6 % faster with 64, N = 7168 / 8192 with 96, N = 3072 with 128; tools/archive/sweep_maxrun.py)
     double best = 0;
     for (int cand : {96, 64, 128}) {
         StripShaping trial = sh;
@@ -351,7 +497,7 @@ static StripShaping choose_strip_shaping(const StripOptions& o, const std::vecto
             best = worst;
         }
     }
-    return sh;
+    return rows_tail ? choose_rows_tail(sh, ranges, n_kslices, a_tile, slots, false) : sh;
 }
 
 StripRequest strip_request(const StripOptions& opt, const std::vector<RowRange>& ranges, uint32_t n_kslices,
@@ -367,9 +513,9 @@ StripRequest strip_request(const StripOptions& opt, const std::vector<RowRange>&
 }
 
 void plan_strips(const StripRequest& rq, const std::vector<RowRange>& ranges, std::vector<StripItem>& items,
-                 uint32_t queue_base[8], uint32_t queue_count[8], int* run_chosen) {
+                 uint32_t queue_base[8], uint32_t queue_count[8], StripChoice* chosen) {
     const StripShaping sh = choose_strip_shaping(rq.opt, ranges, rq.n_kslices, rq.shard_count, rq.a_tile);
-    if (run_chosen) *run_chosen = sh.max_run;
+    if (chosen) *chosen = {sh.max_run, sh.tail_run, sh.tail_slices};
     build_strip_items(sh, ranges, rq.n_kslices, rq.shard_rank, rq.shard_count, rq.a_tile, items, queue_base, queue_count);
 }
 
@@ -1407,7 +1553,7 @@ extern "C" int storm_hip_strip_plan3(uint64_t n_rows, uint32_t n_words, uint32_t
                                      uint64_t capacity_items, uint64_t* n_items, int* run_chosen) {
     using namespace storm;
     if (!n_items || shard_count == 0 || shard_rank >= shard_count || n_words == 0 || form < 0 || form > 2 ||
-        max_run < 0 || max_run > 4096 || tail_run < 1 || tail_run > 4096 || tail_slices < 0 || tail_slices > 255 ||
+        max_run < 0 || max_run > 4096 || tail_run < 0 || tail_run > 4096 || tail_slices < 0 || tail_slices > 255 ||
         lpt_rounds < 0 || lpt_rounds > 63 || n_cus == 0) {
         set_error("strip_plan: bad arguments");
         return STORM_HIP_EINVAL;
@@ -1423,15 +1569,21 @@ extern "C" int storm_hip_strip_plan3(uint64_t n_rows, uint32_t n_words, uint32_t
         uint32_t qb[8], qc[8];
         StripOptions o;
         o.max_run = max_run;
-        o.tail_run = tail_run;
-        o.tail_slices = tail_slices;
+        // tail_run 0: neither tail option is set (a fresh context) — form 2 chooses both for a whole pass, elsewhere the defaults
+        o.tail_auto = tail_run == 0;
+        o.rows_form = form == 2;
+        o.tail_run = tail_run == 0 ? StripOptions().tail_run : tail_run;
+        o.tail_slices = tail_run == 0 ? StripOptions().tail_slices : tail_slices;
         o.lpt_rounds = lpt_rounds;
         o.shard_pairs = pair_space != 0;
         o.n_cus = (int)n_cus;
         o.xcd_group = form == 0 ? 1 : form == 1 ? 2 : (int)kStripRowsXcdGroup;
         // exactly what ensure_strip_items launches for these options (one function plans both)
+        StripChoice used;
         plan_strips(strip_request(o, ranges, n_kslices, shard_rank, shard_count, form == 2 ? kStripRowsATile : (uint32_t)kStripATile),
-                    ranges, items, qb, qc, run_chosen);
+                    ranges, items, qb, qc, &used);
+        // (tail_run 0: the tail in use rides above the run length, which is at most 4096)
+        if (run_chosen) *run_chosen = tail_run == 0 ? used.max_run | used.tail_run << 16 | used.tail_slices << 24 : used.max_run;
         *n_items = items.size();
         if (out)
             for (uint64_t i = 0; i < std::min<uint64_t>(capacity_items, items.size()); ++i) {
@@ -1453,7 +1605,7 @@ extern "C" int storm_hip_strip_plan2(uint64_t n_rows, uint32_t n_words, uint32_t
                                      uint32_t shard_count, int form, int pair_space, uint32_t* out,
                                      uint64_t capacity_items, uint64_t* n_items) {
     const storm::StripOptions d;
-    return storm_hip_strip_plan3(n_rows, n_words, shard_rank, shard_count, form, pair_space, d.max_run, d.tail_run,
+    return storm_hip_strip_plan3(n_rows, n_words, shard_rank, shard_count, form, pair_space, d.max_run, 0 /* not set */,
                                  d.tail_slices, d.lpt_rounds, (uint32_t)d.n_cus, out, capacity_items, n_items, nullptr);
 }
 

@@ -8,6 +8,7 @@
 // and compare requests for equality, so an option the planner reads cannot be missing from the key.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <type_traits>
@@ -124,6 +125,148 @@ struct StripItem {
 };
 static_assert(sizeof(StripItem) == 20, "read by device code");
 
+// ---- the scheduling model of the 128-rows-per-wave form ----
+// What one XCD makes of its list, in STAGE units (the time a compute unit's matrix pipe takes for one stage of one
+// workgroup: 128 MFMAs). The XCD has n_cus compute units of slots_per_cu workgroup slots. It hands its list out in order:
+// an item goes to a free slot as soon as there is one, on the compute unit that holds the fewest workgroups (the lowest
+// index among equals). A workgroup first waits start_latency without using the pipe (its launch, the A rows, the first
+// images), then has work; a compute unit's pipe does one stage per unit of time, shared equally among its workgroups that
+// have work. The answer is the time at which the last item ends, counted from `t0`, the time at which every slot is free.
+// tests/strip_rows_tail/driver.cpp checks it against schedules worked out by hand.
+constexpr double kStripRowsStageMfmas = 128.0;   // 4 waves x 4 fragments x 8 A fragments
+inline double strip_rows_item_cost(const StripItem& it, uint32_t n_rows) {   // trims and the resident diagonal included
+    return (double)strip_rows_item_mfmas(it.a_row0, it.diag, it.j0, it.j1, n_rows) / kStripRowsStageMfmas;
+}
+inline double strip_rows_makespan(const double* cost, size_t n_items, uint32_t n_cus, uint32_t slots_per_cu, double start_latency,
+                                  double t0 = 0.0, const double* resident = nullptr) {
+    // resident (may be NULL; n_cus x slots_per_cu, a compute unit's slots together): work that the slots still hold at t0
+    // from what ran before the list (0: the slot is free) — the middle of a launch instead of its start
+    if (n_cus == 0 || slots_per_cu == 0 || (n_items == 0 && !resident)) return t0;
+    constexpr double kNever = 1e300, kDone = 1e-9;
+    const size_t n_slots = (size_t)n_cus * slots_per_cu;
+    // per slot: the work left (< 0: free) and the time from which the workgroup works; per compute unit: the time up to
+    // which `left` is accounted, the time at which its next workgroup ends, the groups it holds
+    std::vector<double> left(n_slots, -1.0), ready(n_slots, t0), last(n_cus, t0), next(n_cus, kNever), tmp(slots_per_cu);
+    std::vector<uint32_t> held(n_cus, 0u);
+    // One step of a compute unit's own time line from `cur`, over the work `l`: up to `until`, or to the next start of a
+    // waiting group if that comes first; the pipe's work in between comes off the working groups in equal shares. Returns
+    // the time reached and says through `end` when the first working group would end if nothing started before.
+    auto step = [&](const double* r, double* l, double cur, double until, double* end) {
+        uint32_t working = 0;
+        double wake = kNever, least = kNever;
+        for (uint32_t s = 0; s < slots_per_cu; ++s) {
+            if (l[s] < 0.0) continue;
+            if (r[s] <= cur) {
+                ++working;
+                if (l[s] < least) least = l[s];
+            } else if (r[s] < wake)
+                wake = r[s];
+        }
+        *end = working ? cur + least * (double)working : kNever;
+        const double to = wake < until ? wake : until;
+        if (working && to > cur && to < kNever) {
+            const double each = (to - cur) / (double)working;
+            for (uint32_t s = 0; s < slots_per_cu; ++s)
+                if (l[s] >= 0.0 && r[s] <= cur) l[s] = l[s] > each ? l[s] - each : 0.0;   // (never below 0: that marks a free slot)
+        }
+        return to;
+    };
+    // bring compute unit c to time t (no later than its next end)
+    auto advance = [&](uint32_t c, double t) {
+        double end;
+        for (double cur = last[c]; cur < t;) cur = step(&ready[(size_t)c * slots_per_cu], &left[(size_t)c * slots_per_cu], cur, t, &end);
+        last[c] = t;
+    };
+    // when its next workgroup ends: its time line walked ahead on a copy, through the starts of its waiting groups
+    auto next_end = [&](uint32_t c) {
+        const double* r = &ready[(size_t)c * slots_per_cu];
+        for (uint32_t s = 0; s < slots_per_cu; ++s) tmp[s] = left[(size_t)c * slots_per_cu + s];
+        for (double cur = last[c];;) {
+            double end;
+            const double to = step(r, tmp.data(), cur, kNever, &end);
+            if (end <= to) return end;   // (also: nothing held, both never)
+            cur = to;
+        }
+    };
+    uint32_t free_slots = (uint32_t)n_slots;
+    if (resident)
+        for (uint32_t c = 0; c < n_cus; ++c) {
+            for (uint32_t s = 0; s < slots_per_cu; ++s)
+                if (resident[(size_t)c * slots_per_cu + s] > kDone) {
+                    left[(size_t)c * slots_per_cu + s] = resident[(size_t)c * slots_per_cu + s];
+                    ++held[c];
+                    --free_slots;
+                }
+            next[c] = next_end(c);
+        }
+    size_t k = 0;
+    double now = t0;
+    constexpr uint32_t kNone = ~0u;
+    uint32_t only = kNone;   // the one compute unit that has free slots, where that is known
+    // the groups of compute unit c that end at `now` leave
+    auto let_go = [&](uint32_t c) {
+        advance(c, now);
+        double* l = &left[(size_t)c * slots_per_cu];
+        uint32_t gone = 0;
+        for (uint32_t s = 0; s < slots_per_cu; ++s)
+            if (l[s] >= 0.0 && l[s] <= kDone && ready[(size_t)c * slots_per_cu + s] <= now) {
+                l[s] = -1.0;
+                ++gone;
+            }
+        held[c] -= gone;
+        free_slots += gone;
+        return gone;
+    };
+    for (;;) {
+        while (k < n_items && free_slots) {   // hand out: the emptiest compute unit first
+            uint32_t c = only != kNone ? only : 0u;
+            if (only == kNone)
+                for (uint32_t i = 1; i < n_cus; ++i)
+                    if (held[i] < held[c]) c = i;
+            advance(c, now);
+            double* l = &left[(size_t)c * slots_per_cu];
+            uint32_t s = 0;
+            while (l[s] >= 0.0) ++s;
+            l[s] = cost[k] > kDone ? cost[k] : 2.0 * kDone;   // (an item of no work still takes its start)
+            ++k;
+            ready[(size_t)c * slots_per_cu + s] = now + start_latency;
+            ++held[c];
+            --free_slots;
+            next[c] = next_end(c);
+        }
+        only = kNone;
+        uint32_t first = 0, ties = 1;
+        for (uint32_t i = 1; i < n_cus; ++i)
+            if (next[i] < next[first]) {
+                first = i;
+                ties = 1;
+            } else
+                ties += next[i] == next[first];
+        if (next[first] >= kNever) return now;   // nothing is held and nothing is left
+        now = next[first];
+        // every group that ends at this time leaves before the next item is handed out
+        if (ties == 1) {
+            // (items left: every slot was taken, the free ones are all here, and this unit's next end is found when it has them)
+            if (let_go(first) && k < n_items)
+                only = first;
+            else
+                next[first] = next_end(first);
+            continue;
+        }
+        for (uint32_t c = first; c < n_cus; ++c)
+            if (next[c] <= now) {
+                let_go(c);
+                next[c] = next_end(c);
+            }
+    }
+}
+inline double strip_rows_makespan(const StripItem* list, size_t n_items, uint32_t n_rows, uint32_t n_cus, uint32_t slots_per_cu,
+                                  double start_latency) {
+    std::vector<double> cost(n_items);
+    for (size_t k = 0; k < n_items; ++k) cost[k] = strip_rows_item_cost(list[k], n_rows);
+    return strip_rows_makespan(cost.data(), n_items, n_cus, slots_per_cu, start_latency);
+}
+
 // ---- K2q (bitstream_kernel) ----
 struct BitSeg {
     uint32_t a_blk;     // first 64-row block of the A tile (4 blocks; absolute block index)
@@ -209,7 +352,22 @@ struct StripOptions {
     int32_t xcd_group = 1;         // consecutive slices that share an XCD (2 for the bit-operand strips: slices 2j, 2j + 1 read the same bits)
     int32_t persistent = 0;        // k2_persistent: one contiguous queue per XCD
     int32_t one_slice_probe = 0;   // k2_debug & 16 (timing probe, wrong results): every XCD re-reads one k-slice
+    int32_t rows_form = 0;         // the list is strip16_rows_kernel's (128 A rows per wave): its items cost what strip_rows_item_mfmas counts
+    int32_t tail_auto = 0;         // the caller has set neither tail_run nor tail_slices: for one device's whole pass of the rows form
+                                   // they are chosen with the run length (kStripRowsShapings), otherwise they hold as they stand
 };
+// The shaping a list was cut with: what the automatic choices came to, the caller's values where there was no choice.
+struct StripChoice {
+    int max_run = 0, tail_run = 0, tail_slices = 0;
+};
+// The candidates of the rows form's automatic choice next to the shaping the pass always had (the run length chosen as
+// for every form, the last 3 slices in runs of 32): the three run lengths with a long tail of the same runs and with a
+// tail of shorter runs. One is taken only where the model (strip_rows_makespan) has it at least 0.5 % shorter than the
+// choice so far. With a run length the caller has set, the two tails are tried on that run length.
+constexpr StripChoice kStripRowsShapings[6] = {{96, 32, 12}, {96, 24, 8}, {64, 32, 12}, {64, 24, 8}, {128, 32, 12}, {128, 24, 8}};
+// A workgroup's start in stage units (strip_rows_makespan's start_latency): about 1.8 us at the 0.23 us a stage takes when
+// a compute unit's pipe is busy — the launch of a workgroup, its A rows and the first two images. Not fitted to a device.
+constexpr double kStripRowsStartStages = 8.0;
 struct StripRequest {
     StripOptions opt;
     uint32_t n_kslices, shard_rank, shard_count, a_tile;
@@ -219,9 +377,9 @@ struct StripRequest {
 };
 StripRequest strip_request(const StripOptions& opt, const std::vector<RowRange>& ranges, uint32_t n_kslices,
                            uint32_t shard_rank, uint32_t shard_count, uint32_t a_tile);
-// The list in launch order and, for the persistent form, the per-XCD queue bounds; run_chosen: the run length in use.
+// The list in launch order and, for the persistent form, the per-XCD queue bounds; chosen: the shaping in use.
 void plan_strips(const StripRequest& rq, const std::vector<RowRange>& ranges, std::vector<StripItem>& items,
-                 uint32_t queue_base[8], uint32_t queue_count[8], int* run_chosen = nullptr);
+                 uint32_t queue_base[8], uint32_t queue_count[8], StripChoice* chosen = nullptr);
 
 // ---- write-mode tiles of 256 x 256 ----
 // Launch order of the tiles [i0, i1) x [j0, j1) (upper triangle only when `triangle`) for L2 reuse: appended to `out`.

@@ -64,6 +64,9 @@ def strip_plan(n_rows: int, n_words: int, rank: int, world: int, form: int = 1, 
     context options of the same names (defaults = a fresh context on a 256-CU device): the list returned is the
     list such a context launches — one function derives the shaping for both. max_run 0 = automatic, the same
     for every rank of a world; return_run=True also returns the run length chosen.
+    tail_run 0 = neither tail option was set on the context, which is what a context that was given no options launches:
+    form 2 in a world of 1 then chooses the run length and the tail together (tail_slices is not read), every other list
+    takes 32 and 3; return_run=True then returns the triple (max_run, tail_run, tail_slices) in use.
     Host-only: computed by libstorm_hip.so without touching a device."""
     import ctypes as C
 
@@ -79,6 +82,8 @@ def strip_plan(n_rows: int, n_words: int, rank: int, world: int, form: int = 1, 
     if n.value:
         _lib.check(lib.storm_hip_strip_plan3(*args, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n), C.byref(run)),
                    "storm_hip_strip_plan3")
+    if return_run and tail_run == 0:
+        return out, (run.value & 0xFFFF, run.value >> 16 & 0xFF, run.value >> 24 & 0xFF)
     return (out, int(run.value)) if return_run else out
 
 
