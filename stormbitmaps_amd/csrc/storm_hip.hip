@@ -1293,21 +1293,10 @@ int storm_hip_pairw_dense_launch(storm_hip_ctx_t* ctx, const storm_hip_matrix_t*
         return STORM_HIP_EINVAL;
     }
     STORM_HIP_TRY(hipSetDevice(ctx->device));
-    // variant -1 = auto: the matrix-core strips at every size (rows beyond their 32-bit DMA offsets
-    // are multiplied k-chunk by k-chunk over a compact shadow). Measured (tools/archive/bench_crossover.py):
-    // they beat the popcount kernel from N = 64 up (10-37 us vs its 42-84 us latency floor at
-    // N <= 256).
-    int variant = ctx->variant;
-    if (variant < 0) variant = 4;
-    ctx->variant_used = variant;
+    const PassChoice pass = choose_pass(PassCaller::Dense, pass_options_of(ctx), pass_shape_of(m, shard_count));
+    ctx->variant_used = pass.variant_used;
     memset(ctx->pass_report, 0, sizeof(ctx->pass_report));
-    if (variant >= 3) {
-        const int saved = ctx->variant;
-        ctx->variant = variant;
-        const int rc = launch_pairw_mfma(ctx, m, shard_rank, shard_count, d_total);
-        ctx->variant = saved;
-        return rc;
-    }
+    if (pass.kernel != PassKernel::Popcount) return launch_pairw_mfma(ctx, m, shard_rank, shard_count, pass, d_total);
     if (int rc = ensure_segments(ctx, m->n_rows, shard_rank, shard_count)) return rc;
     ctx->pass_report[0] |= STORM_HIP_RAN_POPCOUNT;
     ctx->pass_report[1] += m->n_rows * (m->n_rows - (m->n_rows != 0)) / 2 * m->n_words / shard_count;
@@ -1347,16 +1336,14 @@ int storm_hip_pairw_dense_upload(storm_hip_ctx_t* ctx, storm_hip_matrix_t* m, co
     }
     STORM_HIP_TRY(hipSetDevice(ctx->device));
     m->generation = next_matrix_generation();
-    const bool strips = (ctx->variant < 0 || ctx->variant == 4) && strip_operands_of(ctx) == 5 && !ctx->k2_persistent &&
-                        ctx->k2_debug == 0 && m->n_rows >= 2048 &&
-                        (m->n_rows + 255) / 256 * 256 <= m->n_rows_pad && m->stride_words * 8 * 64ull < (1ull << 32);
-    if (!strips) {   // small matrices, forced kernel forms: the copy, then the pass
+    const PassChoice pass = choose_pass(PassCaller::DenseUpload, pass_options_of(ctx), pass_shape_of(m, 1));
+    if (!pass.in_panels) {   // small matrices, forced kernel forms: the copy, then the pass
         if (int rc = storm_hip_matrix_upload(ctx, m, 0, m->n_rows, host_rows, src_stride_words)) return rc;
         return storm_hip_pairw_dense(ctx, m, 0, 1, h_total);
     }
     memset(ctx->pass_report, 0, sizeof(ctx->pass_report));
-    ctx->variant_used = 4;
-    if (int rc = launch_pairw_bits_upload(ctx, m, host_rows, src_stride_words, result_target(ctx)))
+    ctx->variant_used = pass.variant_used;
+    if (int rc = launch_pairw_bits_upload(ctx, m, host_rows, src_stride_words, *pass.form, result_target(ctx)))
         return rc;
     return fetch_result_word(ctx, h_total);
     });

@@ -236,8 +236,8 @@ struct storm_hip_ctx_s {
     int k2_shard_pairs = 0;         // ownership among shards: 0 = whole k-slices first (leftover slices along the pair space), 1 = every slice along the pair space
     int k2_matrix_pad = -1;         // matrices created from now on: rows that are a multiple of 1 KiB get this many 512-byte chunks more of pitch (0: dense pitch; -1: by the pitch, pitch_pad_chunks)
     int k2_fold_inline = -1;        // K2b: the workgroup dispatched last folds the partial sums inside the launch: -1 = for short launches (<= 4096 workgroups, where the fold launch and its gaps are a fifth of a pass), 1 = always (level at N = 10000), 0 = never (a fold launch behind the strips); profiles/r05_c_fold_ab.jsonl
-    int k2_operands_used = 4;       // what the last strip launch ran (1, 2 or 4)
-    int k2_strip_rows = 0;          // K2b: A rows per wave: 64 = strip16_bits_kernel (256-row A tiles, slices of a class pair of 512 bits), 128 = strip16_rows_kernel (512-row A tiles, slices of 128 bits) where the matrix's zero rows reach the next multiple of 512 (otherwise 64), 0 = by the rule (strip_rows128_by_rule, storm_hip_mfma.hip)
+    int k2_operands_used = 4;       // what the last strip launch ran: 4 = FP4, 5 = K2b (64 or 128 A rows per wave: k2_strip_rows_used), 6 = K2b on 512-row A tiles, 2 = K2q; tools build: 1, 3 (choose_pass, storm_hip_plan.h)
+    int k2_strip_rows = 0;          // K2b: A rows per wave: 64 = strip16_bits_kernel (256-row A tiles, slices of a class pair of 512 bits), 128 = strip16_rows_kernel (512-row A tiles, slices of 128 bits) where the matrix's zero rows reach the next multiple of 512 (otherwise 64), 0 = by the rule (choose_pass, storm_hip_plan.cpp)
     int k2_strip_rows_used = 64;    // what the last K2b launch ran: 64 or 128
     int k2_tile_shape = 0;  // write-mode tile kernel: 0 = by the matrix (5 for a dense matrix, 2 for the dense replica of a sparse container: sparse operands let tilebits8_kernel, which sits at the socket's power cap, clock higher; crossover near 20 % density, profiles/r05_g_*); 5 = tilering_kernel (both operands as FP4 images in the LDS, 16x16x128); 2 = tilebits8_kernel (bit operands inflated in registers, 32x32x64); 3 / 4 = K2tb; 1 / 16 / 32: tools build
     int k2_wave_below = 400;      // [r6] k2_tile_shape 0: matrices (bands, rectangles) of fewer 256 x 256 tiles than this take tile128_kernel (K2h: 128 x 128 tiles, cut along k where they are too few, the parts' sums meeting inside the launch; no window clearing, no atomics into the output)
@@ -300,23 +300,29 @@ struct storm_hip_ctx_s {
 namespace storm {
 // K2: all-pairs total of a dense matrix through v_mfma_f32_32x32x64_f8f6f4 (storm_hip_mfma.hip)
 int launch_pairw_mfma(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint32_t shard_rank,
-                      uint32_t shard_count, uint64_t* d_total);
+                      uint32_t shard_count, const PassChoice& pass, uint64_t* d_total);
 int launch_pairw_mfma_ranges(storm_hip_ctx_t* ctx, const uint64_t* X, uint64_t stride_words,
                              uint64_t n_rows_src, uint64_t n_rows_dst,
                              const std::vector<RowRange>& ranges, uint32_t shard_rank,
                              uint32_t shard_count, int strip_mode, uint64_t* d_total,
                              uint64_t shadow_generation = 0, uint32_t n_words_logical = 0);
 int launch_pairw_bits_upload(storm_hip_ctx_t* ctx, storm_hip_matrix_s* m, const uint64_t* host_rows,
-                             uint64_t src_stride_words, uint64_t* d_total);   // storm_hip_mfma.hip
+                             uint64_t src_stride_words, const StripForm& form, uint64_t* d_total);   // storm_hip_mfma.hip
 int stage_check_lists(const storm_hip_stage_s* stage, const std::vector<uint64_t>& ltable);   // storm_hip_sparse.hip: EINVAL for a token the stage cannot answer
 int stage_gather_lists(storm_hip_ctx_t* ctx, storm_hip_stage_s* stage, const std::vector<uint64_t>& ltable, uint16_t* d_lists,
                        uint64_t** d_table);   // storm_hip_sparse.hip: staged list blocks -> a block-ordered list buffer
-int strip_operands_of(const storm_hip_ctx_t* ctx);   // 5 = K2b, 4 = FP4 strips, ... (storm_hip_mfma.hip)
 int launch_pairw_bits_ranges(storm_hip_ctx_t* ctx, const uint8_t* X, uint64_t pitch_bytes,
-                             const std::vector<RowRange>& ranges, uint32_t n_kslices2, uint32_t shard_rank,
-                             uint32_t shard_count, uint64_t* d_total, bool slots_hold_sums = false,
-                             uint32_t a_tile = 256u,    // a_tile 512: strip16_bits2_kernel (the last tile's rows up to the multiple of 512 must exist and be zero)
-                             bool rows128 = false);     // strip16_rows_kernel: a_tile 512, n_kslices2 = its slices of 16 bytes (strip_rows_kslices)
+                             const std::vector<RowRange>& ranges, const StripForm& form, uint32_t n_words, uint32_t shard_rank,
+                             uint32_t shard_count, uint64_t* d_total, bool slots_hold_sums = false);
+// what choose_pass (storm_hip_plan.h) reads of the context
+static inline PassOptions pass_options_of(const storm_hip_ctx_t* ctx) {
+#ifdef STORM_HIP_PROBES
+    constexpr bool tools = true;
+#else
+    constexpr bool tools = false;
+#endif
+    return {ctx->variant, ctx->k2_strip_operands, ctx->k2_strip_rows, ctx->k2_ring, ctx->k2_shape, ctx->k2_persistent, ctx->k2_debug, tools};
+}
 // pairs x words of a set of row ranges, divided among shard_count shards (the report's algorithmic word pairs)
 static inline uint64_t ranges_word_pairs(const std::vector<RowRange>& ranges, uint64_t words, uint32_t shard_count) {
     uint64_t pairs = 0;
@@ -575,6 +581,17 @@ struct storm_hip_matrix_s {
 };
 
 namespace storm {
+
+// what choose_pass reads of a dense matrix
+static inline PassShape pass_shape_of(const storm_hip_matrix_s* m, uint32_t shard_count) {
+    PassShape s;
+    s.n_rows = m->n_rows;
+    s.n_rows_pad = m->n_rows_pad;
+    s.stride_words = m->stride_words;
+    s.n_words = m->n_words;
+    s.shard_count = shard_count;
+    return s;
+}
 
 // ---- what the dosage top-k calls (storm_hip_topk.hip) take from storm_hip_dosage.hip ----
 // the refusals the dosage calls share: n_samples that does not fill the rows; the rectangle's NULL arguments, widths that

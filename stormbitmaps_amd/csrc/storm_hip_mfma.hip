@@ -406,12 +406,11 @@ __global__ __launch_bounds__(kMfmaThreads, 2) void pairw_fp4_kernel(
 // (N x 128 B = 1.3 MB at N = 10000); the shadow's row pitch is padded off powers of two, so the
 // strips miss L2 for only ~2.6x the shadow's size per launch.
 // ------------------------------------------------------------------------------------------
-// (kStripRowBytes = 128, kStripBRows = 64, kStripWaves = 4, kStripATile = 256: storm_hip_plan.h)
+// (kStripRowBytes = 128, kStripBRows = 64, kStripWaves = 4, kStripATile = 256, kStripRingDefault = 4: storm_hip_plan.h)
 constexpr int kStripStageBytes = kStripBRows * kStripRowBytes;  // 8 KiB
 constexpr int kStripThreads = 64 * kStripWaves;
 [[maybe_unused]] constexpr int kStripPieces = 8 / kStripWaves;            // LDS-DMA instructions per wave and stage
 static_assert(kStripWaves == 4 || kStripWaves == 8, "a B stage is 8 DMA pieces");
-constexpr int kStripRingDefault = 4;
 
 // (the item record StripItem: storm_hip_plan.h)
 
@@ -1721,7 +1720,7 @@ int launch_pairw_mfma_ranges(storm_hip_ctx_t* ctx, const uint64_t* X, uint64_t s
     // k-slices that hold data: the zero padding of the rows up to 64 words is never multiplied
     // (a 256-bit matrix is one slice, not sixteen)
     const uint32_t n_kslices = n_words_logical
-                                   ? (n_words_logical + 3u) / 4u
+                                   ? kStripFp4.kslices(n_words_logical)
                                    : (uint32_t)(row_bytes / kStripRowBytes);
     // HBM tiling along k: the FP4 shadow is 4 x the bits. When the whole of it would exceed the
     // context's budget ("k2_shadow_budget_mb") the strips run k-chunk by k-chunk over a compact
@@ -2486,133 +2485,78 @@ int launch_pairw_bitstream(storm_hip_ctx_t* ctx, const uint64_t* X, uint64_t pit
 #include "../../tools/probes/bitwave_launch.hip"
 #endif  // STORM_HIP_PROBES
 
-// K2b over arbitrary row ranges of a bit matrix X (pitch bytes per row): the FP4 strips' items over slices of
-// 256 bit-MACs = one class pair of a 512-bit chunk (n_kslices2 = 2 x the chunks that hold data). The rows of
-// every range's last A tile beyond its r1 must be readable and zero in X. Dense container: the matrix;
-// sparse container: the pool rows of its block columns.
+// K2b over arbitrary row ranges of a bit matrix X (pitch bytes per row, n_words of them hold data), in one of the K2b
+// forms of the table (storm_hip_plan.h: kStripBits, kStripBitsWide, kStripRows). The rows of every range's last A tile
+// beyond its r1 must be readable and zero in X. Dense container: the matrix; sparse container: the pool rows of its
+// block columns.
 int launch_pairw_bits_ranges(storm_hip_ctx_t* ctx, const uint8_t* X, uint64_t pitch,
-                             const std::vector<RowRange>& ranges, uint32_t n_kslices2, uint32_t shard_rank,
-                             uint32_t shard_count, uint64_t* d_total, bool slots_hold_sums, uint32_t a_tile, bool rows128) {
+                             const std::vector<RowRange>& ranges, const StripForm& form, uint32_t n_words, uint32_t shard_rank,
+                             uint32_t shard_count, uint64_t* d_total, bool slots_hold_sums) {
     if (pitch * (uint64_t)kStripBRows >= (1ull << 32)) {
         set_error("K2b: rows of %llu bytes are beyond the strips' 32-bit DMA offsets", (unsigned long long)pitch);
         return STORM_HIP_EINVAL;
     }
     ctx->items.forget();  // the strip items carry the diagonal tiles themselves
-    // (rows128 — strip16_rows_kernel: n_kslices2 counts slices of 16 bytes, a_tile is 512, the 8 slices of a 128-byte line share an XCD)
-    if (rows128 && a_tile != kStripRowsATile) {
-        set_error("K2b: the 128-rows-per-wave form takes A tiles of 512 rows");
-        return STORM_HIP_EINVAL;
-    }
-    if (int rc = ensure_strip_items(ctx, ranges, n_kslices2, shard_rank, shard_count, a_tile, rows128 ? (int)kStripRowsXcdGroup : 2, rows128))
+    const uint32_t n_kslices = form.kslices(n_words);
+    if (int rc = ensure_strip_items(ctx, ranges, n_kslices, shard_rank, shard_count, form.a_tile, form.xcd_group, form.rows_form()))
         return rc;
     const uint32_t n_strip = ctx->strips.n;
-    const uint32_t waves = rows128 ? 4u : a_tile / (uint32_t)kStripBRows;   // 4, or 8 for the 512-row form (strip16_bits2_kernel)
-    ctx->k2_operands_used = waves == 8u ? 6 : 5;
-    ctx->k2_strip_rows_used = rows128 ? 128 : 64;
+    ctx->k2_operands_used = form.operands_report;
+    ctx->k2_strip_rows_used = form.rows_report;
     if (n_strip > 0) {
         ctx->pass_report[0] |= STORM_HIP_RAN_BIT_STRIPS;
-        ctx->pass_report[1] += ranges_word_pairs(ranges, (uint64_t)n_kslices2 * (rows128 ? 2u : 4u), shard_count);  // a slice = 256 bit-MACs per pair = 4 words (rows128: 128 = 2 words)
+        ctx->pass_report[1] += ranges_word_pairs(ranges, (uint64_t)n_kslices * form.slice_words(), shard_count);
     }
     ctx->last_info[0] = n_strip;
     ctx->last_info[1] = ctx->k2_stages_per_item;
     ctx->last_info[2] = 1;
     ctx->last_info[3] = 0;
     // the fold inside the launch (option k2_fold_inline: -1 = whenever the packed slot words cannot overflow, 0 = never:
-    // a fold launch follows): arrivals per slot below 2^16, a slot's sum below 2^48 — a wave adds at most 64 rows x
-    // (run x 64 + 256) rows x 256 bits
+    // a fold launch follows): arrivals per slot below 2^16, a slot's sum below 2^48 (StripForm::wave_sum_max)
     // ... and what it is worth depends on the launch: a short one (up to 4096 workgroups: N <= ~2000 at M = 65536) spends a
     // fifth of a pass in the fold launch and its gaps and uses 256 slots, one per polling thread (-1 = on for those); a long
     // one gains nothing (profiles/r05_c_fold_ab.jsonl) and keeps the fold launch unless the option is 1
     const uint32_t fold_slots = n_strip <= 4096u ? 256u : (uint32_t)kSlots;
     const bool fold_wanted = ctx->k2_fold_inline > 0 || (ctx->k2_fold_inline < 0 && n_strip <= 4096u);
-    const uint64_t arrivals_per_slot = (uint64_t)n_strip * (uint64_t)waves / (uint64_t)fold_slots + 1u;
-    // (rows128: 128 rows x (run x 64 + 512) rows x 128 bits)
-    const uint64_t wave_sum_max = rows128 ? 128ull * (4096ull * 64ull + 512ull) * 128ull
-                                          : 64ull * (4096ull * 64ull + 256ull) * 256ull;   // (runs are capped at 4096 stages)
+    const uint64_t arrivals_per_slot = (uint64_t)n_strip * (uint64_t)form.waves / (uint64_t)fold_slots + 1u;
     // (slots_hold_sums: another kernel of this pass — the list-probe kernel — has added sums of unknown size: fold launch)
     const bool fold_inline = fold_wanted && !slots_hold_sums && n_strip > 0 && arrivals_per_slot < 65535u &&
-                             arrivals_per_slot * wave_sum_max < (1ull << 48);
+                             arrivals_per_slot * form.wave_sum_max < (1ull << 48);   // (runs are capped at 4096 stages)
     if (n_strip > 0) {
         kernel_time_mark(ctx);
-        if (rows128) {
+        const dim3 grid(n_strip), block(form.threads());
+        unsigned long long* const fold_to = fold_inline ? reinterpret_cast<unsigned long long*>(d_total) : nullptr;
+        if (form.kernel == StripKernel::Rows) {
             // where the rows end, for a pass that is one plain range from row 0 (the dense matrix, whole or sharded): the
             // kernel issues no MFMA for the zero rows behind r1 in whole fragments and blocks (storm_hip_plan.h)
             const bool plain = ranges.size() == 1 && ranges[0].r0 == 0 && ranges[0].a_end == 0 && ranges[0].back_from == ~0ull &&
                                ranges[0].r1 < (uint64_t)kStripRowsNoTrim;
-            hipLaunchKernelGGL(strip16_rows_kernel, dim3(n_strip), dim3(256), (size_t)ctx->k2_lds_pad,
-                               ctx->stream, X, pitch, ctx->strips.recs(), ctx->d_slots,
-                               fold_inline ? reinterpret_cast<unsigned long long*>(d_total) : nullptr, fold_slots,
-                               plain ? (uint32_t)ranges[0].r1 : kStripRowsNoTrim);
-        } else if (waves == 8u)
-            hipLaunchKernelGGL(strip16_bits2_kernel, dim3(n_strip), dim3(512), (size_t)ctx->k2_lds_pad,
-                               ctx->stream, X, pitch, ctx->strips.recs(), ctx->d_slots,
-                               fold_inline ? reinterpret_cast<unsigned long long*>(d_total) : nullptr, fold_slots);
+            hipLaunchKernelGGL(strip16_rows_kernel, grid, block, (size_t)ctx->k2_lds_pad, ctx->stream, X, pitch, ctx->strips.recs(),
+                               ctx->d_slots, fold_to, fold_slots, plain ? (uint32_t)ranges[0].r1 : kStripRowsNoTrim);
+        } else if (form.kernel == StripKernel::BitsWide)
+            hipLaunchKernelGGL(strip16_bits2_kernel, grid, block, (size_t)ctx->k2_lds_pad, ctx->stream, X, pitch, ctx->strips.recs(),
+                               ctx->d_slots, fold_to, fold_slots);
         else
-            hipLaunchKernelGGL(strip16_bits_kernel, dim3(n_strip), dim3(kStripThreads), (size_t)ctx->k2_lds_pad,
-                               ctx->stream, X, pitch, ctx->strips.recs(), ctx->d_slots,
-                               fold_inline ? reinterpret_cast<unsigned long long*>(d_total) : nullptr, fold_slots);
+            hipLaunchKernelGGL(strip16_bits_kernel, grid, block, (size_t)ctx->k2_lds_pad, ctx->stream, X, pitch, ctx->strips.recs(),
+                               ctx->d_slots, fold_to, fold_slots);
         kernel_time_mark(ctx);
         STORM_HIP_TRY(hipGetLastError());
     }
     return fold_inline ? STORM_HIP_OK : launch_fold_slots(ctx, d_total);
 }
 
-// K2b's A rows per wave (option k2_strip_rows): 128 = strip16_rows_kernel, wherever the zero rows of the allocation reach the
-// next multiple of 512 (its A tile; option 6's rule) — otherwise, and for 64, strip16_bits_kernel. 0 = by measurement
-// (profiles/k2b_rows128_ab.txt: kernel time by HIP events, the forms alternating in one process, two rounds; 256-row form
-// -> 128 rows per wave): 10000 x 65536 0.755 -> 0.721 ms, 10000 x 524288 6.11 -> 5.64, 8192 x 65536 0.512 -> 0.488,
-// 4096 x 65536 0.1422 -> 0.1331, 2048 x 65536 0.0450 -> 0.0442 — ahead by 1.5 .. 7.7 %, everywhere more than three times the
-// 256-row form's own spread between the rounds (0.1 .. 0.4 %). The rule takes the new form inside what was measured: one
-// device's whole pass, from 2048 rows of 65536 bits up. Smaller matrices (the diagonal phase is 8 of an item's stages, not
-// 4, and at 2048 rows the margin is down to 1.5 %), narrower rows (fewer than 512 slices for 8 XCDs in groups of 8) and the
-// shards of a multi-GPU pass were not measured and keep the 256-row form.
-static bool strip_rows128_by_rule(const storm_hip_matrix_s* m, uint32_t shard_count) {
-    return shard_count == 1 && m->n_rows >= 2048 && m->n_words >= 1024;
-}
-static bool strip_rows128(const storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint32_t shard_count) {
-    if (ctx->k2_strip_rows == 64 || ctx->k2_strip_operands == 6 || (m->n_rows + kStripRowsATile - 1) / kStripRowsATile * kStripRowsATile > m->n_rows_pad) return false;
-    return ctx->k2_strip_rows == 128 || strip_rows128_by_rule(m, shard_count);
-}
-
-// The default pass: strips on bit operands over the matrix itself (no shadow, nothing to expand).
-static int launch_pairw_bits(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint32_t shard_rank,
-                             uint32_t shard_count, int operands, uint64_t* d_total) {
-    const uint64_t pitch = m->stride_words * 8;
-    const uint64_t n_rows4 = (m->n_rows + kStripATile - 1) / kStripATile * kStripATile;
-    if (n_rows4 > m->n_rows_pad || pitch * (uint64_t)kStripBRows >= (1ull << 32)) {
-        set_error("K2sb: matrix of %llu rows (%llu allocated) x %llu bytes per row is outside the bit-operand strips' reach",
-                  (unsigned long long)m->n_rows, (unsigned long long)m->n_rows_pad, (unsigned long long)pitch);
-        return STORM_HIP_EINVAL;
-    }
-    std::vector<RowRange> ranges;
-    if (m->n_rows > 1) ranges.push_back({0, m->n_rows});
-    // k-slices of 512 bits that hold data (the zero padding of the rows is never multiplied)
-    const uint32_t n_kslices = (m->n_words + 7u) / 8u;
-    if (operands == 2)
-        return launch_pairw_bitstream(ctx, m->d, pitch, ranges, n_kslices, shard_rank, shard_count, d_total);
 #ifdef STORM_HIP_PROBES
-    if (operands == 3)
-        return launch_pairw_bitwave(ctx, m->d, pitch, ranges, n_kslices, shard_rank, shard_count, d_total);
-#endif
+// k2_strip_operands = 1 (tools build): the strips on bit operands, one item per workgroup (stripbits_kernel)
+static int launch_pairw_stripbits(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, const std::vector<RowRange>& ranges,
+                                  uint32_t shard_rank, uint32_t shard_count, uint64_t* d_total) {
     ctx->items.forget();  // the strip items carry the diagonal tiles themselves
-    if (operands == 5 && strip_rows128(ctx, m, shard_count))
-        return launch_pairw_bits_ranges(ctx, reinterpret_cast<const uint8_t*>(m->d), pitch, ranges, strip_rows_kslices(m->n_words),
-                                        shard_rank, shard_count, d_total, false, kStripRowsATile, true);
-    if (operands == 5 || operands == 6)
-        return launch_pairw_bits_ranges(ctx, reinterpret_cast<const uint8_t*>(m->d), pitch, ranges, n_kslices * 2u,
-                                        shard_rank, shard_count, d_total, false, operands == 6 ? 512u : (uint32_t)kStripATile, false);
-    if (int rc = ensure_strip_items(ctx, ranges, n_kslices, shard_rank, shard_count, (uint32_t)kStripATile))
+    if (int rc = ensure_strip_items(ctx, ranges, kStripBits.chunks(m->n_words), shard_rank, shard_count, kStripBits.a_tile))
         return rc;
-#ifndef STORM_HIP_PROBES
-    set_error("k2_strip_operands = 1 (stripbits_kernel) is in the tools build only (`make probes`)");
-    return STORM_HIP_EINVAL;
-#else
     const uint32_t n_strip = ctx->strips.n;
     if (n_strip > 0) {
         kernel_time_mark(ctx);
         hipLaunchKernelGGL(stripbits_kernel, dim3(n_strip), dim3(kStripThreads), 0, ctx->stream,
-                           reinterpret_cast<const uint8_t*>(m->d), pitch,
-                           ctx->strips.recs(), ctx->d_slots);
+                           reinterpret_cast<const uint8_t*>(m->d), m->stride_words * 8, ctx->strips.recs(), ctx->d_slots);
         kernel_time_mark(ctx);
         STORM_HIP_TRY(hipGetLastError());
     }
@@ -2621,8 +2565,8 @@ static int launch_pairw_bits(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, 
     ctx->last_info[2] = 1;
     ctx->last_info[3] = 0;
     return launch_fold_slots(ctx, d_total);
-#endif
 }
+#endif
 
 // The all-pairs total of a matrix that is still in the CALLER's memory (STORM_wrapper_diag[_blocked], storm.c:132-150,
 // :222-279: the raw-buffer entry points pay the transfer on every call — 82 MB at the headline shape, 1.5 ms in front of
@@ -2631,10 +2575,10 @@ static int launch_pairw_bits(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, 
 // of them streaming past) while the next panel is on the bus. What stays exposed is the first panel's copy and the last
 // panel's pairs. One fold at the end; the work lists of the panels stay on the device between calls.
 static int pairw_bits_upload_queue(storm_hip_ctx_t* ctx, storm_hip_matrix_s* m, const uint64_t* host_rows,
-                                   uint64_t src_stride_words, uint64_t* d_total);
+                                   uint64_t src_stride_words, const StripForm& form, uint64_t* d_total);
 int launch_pairw_bits_upload(storm_hip_ctx_t* ctx, storm_hip_matrix_s* m, const uint64_t* host_rows,
-                             uint64_t src_stride_words, uint64_t* d_total) {
-    const int rc = pairw_bits_upload_queue(ctx, m, host_rows, src_stride_words, d_total);
+                             uint64_t src_stride_words, const StripForm& form, uint64_t* d_total) {
+    const int rc = pairw_bits_upload_queue(ctx, m, host_rows, src_stride_words, form, d_total);
     if (rc != STORM_HIP_OK) {
         // a failure behind the first panel copy: the copies may still be reading the caller's rows (which the caller is about
         // to get back, and may free) and writing the matrix (which the caller of this function releases): drain both streams,
@@ -2645,14 +2589,11 @@ int launch_pairw_bits_upload(storm_hip_ctx_t* ctx, storm_hip_matrix_s* m, const 
     }
     return rc;
 }
+// (choose_pass has said "in panels" on `form`: the matrix's zero rows reach the form's A tile and its pitch the DMA offsets)
 static int pairw_bits_upload_queue(storm_hip_ctx_t* ctx, storm_hip_matrix_s* m, const uint64_t* host_rows,
-                                   uint64_t src_stride_words, uint64_t* d_total) {
+                                   uint64_t src_stride_words, const StripForm& form, uint64_t* d_total) {
     const uint64_t pitch = m->stride_words * 8;
-    const uint64_t tiles = (m->n_rows + kStripATile - 1) / kStripATile;
-    if (tiles * kStripATile > m->n_rows_pad || pitch * (uint64_t)kStripBRows >= (1ull << 32) || m->n_rows < 2) {
-        set_error("pairw_dense_upload: matrix outside the bit-operand strips' reach");
-        return STORM_HIP_EINVAL;
-    }
+    const uint64_t tiles = (m->n_rows + form.a_tile - 1) / form.a_tile;
     if (!ctx->copy_stream) STORM_HIP_TRY(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
     std::vector<PanelList>& lists = ctx->panel_lists;
     // The copies must not overtake what the context's stream still has to do to this matrix: storm_hip_matrix_create
@@ -2672,17 +2613,17 @@ static int pairw_bits_upload_queue(storm_hip_ctx_t* ctx, storm_hip_matrix_s* m, 
         for (uint64_t p = 0; p <= n; ++p) first_tile.push_back(tiles * p / n);
     }
     const uint64_t n_panels = first_tile.size() - 1;
-    const uint32_t n_kslices2 = 2u * ((m->n_words + 7u) / 8u);
+    const uint32_t n_kslices = form.kslices(m->n_words);
     if (lists.size() < n_panels) lists.resize(n_panels);
     ctx->pass_report[0] |= STORM_HIP_RAN_BIT_STRIPS;
-    ctx->pass_report[1] += ranges_word_pairs({{0, m->n_rows}}, (uint64_t)n_kslices2 * 4u, 1);
-    ctx->k2_operands_used = 5;
-    ctx->k2_strip_rows_used = 64;
+    ctx->pass_report[1] += ranges_word_pairs({{0, m->n_rows}}, (uint64_t)n_kslices * form.slice_words(), 1);
+    ctx->k2_operands_used = form.operands_report;
+    ctx->k2_strip_rows_used = form.rows_report;
     uint64_t n_total = 0;
     for (uint64_t p = 0; p < n_panels; ++p) {
         const uint64_t t0 = first_tile[p], t1 = first_tile[p + 1];
         if (t0 >= t1) continue;
-        const uint64_t row0 = t0 * kStripATile, row1 = std::min<uint64_t>(m->n_rows, t1 * kStripATile);
+        const uint64_t row0 = t0 * form.a_tile, row1 = std::min<uint64_t>(m->n_rows, t1 * form.a_tile);
         PanelList& l = lists[p];
         if (!l.landed) STORM_HIP_TRY(hipEventCreateWithFlags(&l.landed, hipEventDisableTiming));
         STORM_HIP_TRY(hipMemcpy2DAsync(m->d + row0 * m->stride_words, pitch, host_rows + row0 * src_stride_words,
@@ -2690,13 +2631,13 @@ static int pairw_bits_upload_queue(storm_hip_ctx_t* ctx, storm_hip_matrix_s* m, 
                                        ctx->copy_stream));
         STORM_HIP_TRY(hipEventRecord(l.landed, ctx->copy_stream));
         // (a fixed run length: a panel's list is short and all tail)
-        StripOptions po = strip_options_of(ctx, 2, false);
+        StripOptions po = strip_options_of(ctx, form.xcd_group, form.rows_form());
         po.max_run = 128;
         po.shard_pairs = po.persistent = po.one_slice_probe = 0;
         RowRange rg{0, row1};
         rg.back_from = row0;
         const std::vector<RowRange> panel = {rg};
-        const StripRequest rq = strip_request(po, panel, n_kslices2, 0, 1, (uint32_t)kStripATile);
+        const StripRequest rq = strip_request(po, panel, n_kslices, 0, 1, form.a_tile);
         if (!l.list.holds(rq)) {
             std::vector<StripItem> items;
             uint32_t qb[8], qc[8];
@@ -2710,7 +2651,7 @@ static int pairw_bits_upload_queue(storm_hip_ctx_t* ctx, storm_hip_matrix_s* m, 
         }
         STORM_HIP_TRY(hipStreamWaitEvent(ctx->stream, l.landed, 0));
         if (l.list.n) {
-            hipLaunchKernelGGL(strip16_bits_kernel, dim3(l.list.n), dim3(kStripThreads), (size_t)ctx->k2_lds_pad, ctx->stream,
+            hipLaunchKernelGGL(strip16_bits_kernel, dim3(l.list.n), dim3(form.threads()), (size_t)ctx->k2_lds_pad, ctx->stream,
                                reinterpret_cast<const uint8_t*>(m->d), pitch, l.list.recs(), ctx->d_slots,
                                (unsigned long long*)nullptr, (uint32_t)kSlots);
             STORM_HIP_TRY(hipGetLastError());
@@ -2724,41 +2665,36 @@ static int pairw_bits_upload_queue(storm_hip_ctx_t* ctx, storm_hip_matrix_s* m, 
     return launch_fold_slots(ctx, d_total);
 }
 
-// Which strips an all-pairs pass runs (option k2_strip_operands; 0 = the default: K2b unless a non-default ring or MFMA
-// shape asks for the FP4 strips): ONE rule for the dense matrix and for the pool rows of a sparse container.
-int strip_operands_of(const storm_hip_ctx_t* ctx) {
-    if (ctx->k2_strip_operands == 6) return 5;   // (K2b with 512-row A tiles: a form of K2b; launch_pairw_mfma takes it where the matrix allows)
-    if (ctx->k2_strip_operands != 0) return ctx->k2_strip_operands;
-    return (ctx->k2_ring == kStripRingDefault && ctx->k2_shape == 16) ? 5 : 4;
-}
+// The dense container's pass on the matrix cores, in the form choose_pass has named (storm_hip_plan.cpp).
 int launch_pairw_mfma(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint32_t shard_rank,
-                      uint32_t shard_count, uint64_t* d_total) {
-    const int strip_mode = ctx->variant == 5 ? 2 : ctx->variant == 4 ? 1 : 0;
-    // (a matrix created before the option was set may lack the zero rows up to a multiple of 256)
-    // Which strips (option k2_strip_operands; 0 = by measurement, same box, M = 65536, tools/archive/sweep_k2b.py,
-    // profiles/r04_a_sweep_k2b.jsonl): the strips on bit operands with the FP4 image built in the LDS (K2b,
-    // strip16_bits_kernel) are ahead of the one-launch stream (K2q) and of the FP4 strips at every size —
-    // 8.2 / 9.5 / 14.9 us at N = 256, 17.1 / 20.2 / 31.8 at 1024, 41.9 / 43.4 / 60.4 at 2048, 142 / 143 / 169 at
-    // 4096, 537 / 539 / 591 at 8192, 752 / 809 / 817 at 10000 (K2q is ahead around N = 6144 only: 311 against
-    // 325) — and for the shards of a multi-GPU pass (an eighth of the headline matrix: 103 against 119 us).
-    const int operands = strip_operands_of(ctx);
-    if (strip_mode == 1 && (operands == 1 || operands == 2 || operands == 3 || operands == 5) && !ctx->k2_persistent && ctx->k2_debug == 0 &&
-        (m->n_rows + kStripATile - 1) / kStripATile * kStripATile <= m->n_rows_pad &&
-        m->stride_words * 8 * (uint64_t)kStripBRows < (1ull << 32))
-    {
-        // (6: 512-row A tiles want the zero rows up to a multiple of 512)
-        const bool wide = operands == 5 && ctx->k2_strip_operands == 6 && (m->n_rows + 511u) / 512u * 512u <= m->n_rows_pad;
-        ctx->k2_operands_used = wide ? 6 : operands;
-        return launch_pairw_bits(ctx, m, shard_rank, shard_count, wide ? 6 : operands, d_total);
-    }
-    ctx->k2_operands_used = 4;
-    const uint64_t tile = strip_mode == 2 ? 512 : kStripATile;
-    const uint64_t n_rows4 = (m->n_rows + tile - 1) / tile * tile;
+                      uint32_t shard_count, const PassChoice& pass, uint64_t* d_total) {
+    ctx->k2_operands_used = pass.operands_used;
+    const uint64_t pitch = m->stride_words * 8;
     std::vector<RowRange> ranges;
     if (m->n_rows > 1) ranges.push_back({0, m->n_rows});
-    return launch_pairw_mfma_ranges(ctx, m->d, m->stride_words, m->n_rows_pad, n_rows4, ranges,
-                                    shard_rank, shard_count, strip_mode, d_total, m->generation,
-                                    m->n_words);
+    switch (pass.kernel) {
+    case PassKernel::Strips:   // the default: strips on bit operands over the matrix itself (no shadow, nothing to expand)
+        return launch_pairw_bits_ranges(ctx, reinterpret_cast<const uint8_t*>(m->d), pitch, ranges, *pass.form, m->n_words,
+                                        shard_rank, shard_count, d_total);
+    case PassKernel::Bitstream:   // (k-slices of 512 bits that hold data: the zero padding of the rows is never multiplied)
+        return launch_pairw_bitstream(ctx, m->d, pitch, ranges, kStripBits.chunks(m->n_words), shard_rank, shard_count, d_total);
+#ifdef STORM_HIP_PROBES
+    case PassKernel::ToolsBitwave:
+        return launch_pairw_bitwave(ctx, m->d, pitch, ranges, kStripBits.chunks(m->n_words), shard_rank, shard_count, d_total);
+    case PassKernel::ToolsStripBits:
+        return launch_pairw_stripbits(ctx, m, ranges, shard_rank, shard_count, d_total);
+#else
+    case PassKernel::ToolsBitwave:
+    case PassKernel::ToolsStripBits:
+        set_error("k2_strip_operands = 1 (stripbits_kernel) is in the tools build only (`make probes`)");
+        return STORM_HIP_EINVAL;
+#endif
+    default: {   // the FP4 kernels over the shadow
+        const uint64_t tile = pass.strip_mode == 2 ? 512 : kStripATile;
+        return launch_pairw_mfma_ranges(ctx, m->d, m->stride_words, m->n_rows_pad, (m->n_rows + tile - 1) / tile * tile, ranges,
+                                        shard_rank, shard_count, pass.strip_mode, d_total, m->generation, m->n_words);
+    }
+    }
 }
 
 }  // namespace storm

@@ -519,6 +519,90 @@ void plan_strips(const StripRequest& rq, const std::vector<RowRange>& ranges, st
     build_strip_items(sh, ranges, rq.n_kslices, rq.shard_rank, rq.shard_count, rq.a_tile, items, queue_base, queue_count);
 }
 
+// ---- how an all-pairs pass chooses its form ----
+// Which strips (option k2_strip_operands; 0 = the default: K2b unless a non-default ring or MFMA shape asks for the FP4
+// strips; 6 = K2b with 512-row A tiles, a form of K2b taken where the matrix allows): ONE rule for the dense matrix, the
+// panels of an upload and the pool rows of a sparse container. The default is by measurement (same box, M = 65536,
+// tools/archive/sweep_k2b.py, profiles/r04_a_sweep_k2b.jsonl): the strips on bit operands with the FP4 image built in the
+// LDS (K2b, strip16_bits_kernel) are ahead of the one-launch stream (K2q) and of the FP4 strips at every size —
+// 8.2 / 9.5 / 14.9 us at N = 256, 17.1 / 20.2 / 31.8 at 1024, 41.9 / 43.4 / 60.4 at 2048, 142 / 143 / 169 at
+// 4096, 537 / 539 / 591 at 8192, 752 / 809 / 817 at 10000 (K2q is ahead around N = 6144 only: 311 against
+// 325) — and for the shards of a multi-GPU pass (an eighth of the headline matrix: 103 against 119 us).
+static int strip_operands_of(const PassOptions& o) {
+    if (o.k2_strip_operands == 6) return 5;
+    if (o.k2_strip_operands != 0) return o.k2_strip_operands;
+    return (o.k2_ring == kStripRingDefault && o.k2_shape == 16) ? 5 : 4;
+}
+// The bit operands are read where they lie: the zero rows of the allocation must reach the next multiple of the form's A
+// tile (a matrix created before an option was set may lack them) and a B stage of 64 rows is addressed with 32-bit DMA
+// offsets. The timing probes and the work queues exist for the FP4 strips only.
+static bool rows_padded_to(const PassShape& s, uint64_t a_tile) { return (s.n_rows + a_tile - 1) / a_tile * a_tile <= s.n_rows_pad; }
+static bool bit_operands_reach(const PassOptions& o, const PassShape& s) {
+    return !o.k2_persistent && o.k2_debug == 0 && rows_padded_to(s, kStripBits.a_tile) &&
+           s.stride_words * 8 * (uint64_t)kStripBRows < (1ull << 32);
+}
+// K2b's A rows per wave (option k2_strip_rows): 128 = strip16_rows_kernel, wherever the zero rows of the allocation reach the
+// next multiple of 512 (its A tile; option 6's rule) — otherwise, and for 64, strip16_bits_kernel. 0 = by measurement
+// (profiles/k2b_rows128_ab.txt: kernel time by HIP events, the forms alternating in one process, two rounds; 256-row form
+// -> 128 rows per wave): 10000 x 65536 0.755 -> 0.721 ms, 10000 x 524288 6.11 -> 5.64, 8192 x 65536 0.512 -> 0.488,
+// 4096 x 65536 0.1422 -> 0.1331, 2048 x 65536 0.0450 -> 0.0442 — ahead by 1.5 .. 7.7 %, everywhere more than three times the
+// 256-row form's own spread between the rounds (0.1 .. 0.4 %). The rule takes the new form inside what was measured: one
+// device's whole pass, from 2048 rows of 65536 bits up. Smaller matrices (the diagonal phase is 8 of an item's stages, not
+// 4, and at 2048 rows the margin is down to 1.5 %), narrower rows (fewer than 512 slices for 8 XCDs in groups of 8) and the
+// shards of a multi-GPU pass were not measured and keep the 256-row form. Where the 512-row tiles were asked for (6) the
+// option is not read.
+static const StripForm* dense_strip_form(const PassOptions& o, const PassShape& s) {
+    const bool pad512 = rows_padded_to(s, kStripRows.a_tile);
+    if (o.k2_strip_operands == 6) return pad512 ? &kStripBitsWide : &kStripBits;
+    const bool by_rule = s.shard_count == 1 && s.n_rows >= 2048 && s.n_words >= 1024;
+    return o.k2_strip_rows != 64 && pad512 && (o.k2_strip_rows == 128 || by_rule) ? &kStripRows : &kStripBits;
+}
+static PassChoice fp4_pass(int variant, int operands_used) {
+    return {variant == 5 ? PassKernel::Fp4StripsWide : variant == 4 ? PassKernel::Fp4Strips : PassKernel::Fp4Tiles, nullptr, variant,
+            operands_used, variant == 5 ? 2 : variant == 4 ? 1 : 0, false};
+}
+static PassChoice choose_dense_pass(const PassOptions& o, const PassShape& s) {
+    // variant -1 = auto: the matrix-core strips at every size (rows beyond their 32-bit DMA offsets are multiplied k-chunk by
+    // k-chunk over a compact shadow). Measured (tools/archive/bench_crossover.py): they beat the popcount kernel from N = 64
+    // up (10-37 us vs its 42-84 us latency floor at N <= 256).
+    const int variant = o.variant < 0 ? 4 : o.variant;
+    if (variant < 3) return {PassKernel::Popcount, nullptr, variant, 0, 0, false};
+    const int ops = strip_operands_of(o);
+    if (variant != 4 || !(ops == 1 || ops == 2 || ops == 3 || ops == 5) || !bit_operands_reach(o, s)) return fp4_pass(variant, 4);
+    if (ops == 5) {
+        const StripForm* form = dense_strip_form(o, s);
+        return {PassKernel::Strips, form, variant, form->operands_report, 0, false};
+    }
+    const PassKernel kernel = ops == 2 ? PassKernel::Bitstream : ops == 3 && o.tools_build ? PassKernel::ToolsBitwave : PassKernel::ToolsStripBits;
+    return {kernel, nullptr, variant, ops, 0, false};
+}
+PassChoice choose_pass(PassCaller caller, const PassOptions& o, const PassShape& s) {
+    switch (caller) {
+    case PassCaller::Dense:
+        return choose_dense_pass(o, s);
+    case PassCaller::DenseUpload: {
+        // the rows travel in panels behind which K2b multiplies (launch_pairw_bits_upload) from 2048 rows on; small matrices
+        // and forced kernel forms: the copy, then the pass
+        if ((o.variant < 0 || o.variant == 4) && strip_operands_of(o) == 5 && s.n_rows >= 2048 && bit_operands_reach(o, s))
+            return {PassKernel::Strips, &kStripBits, 4, kStripBits.operands_report, 0, true};
+        return choose_dense_pass(o, s);
+    }
+    case PassCaller::SparsePool: {
+        // Matrix-core path when the columns are big enough to fill the chip (same rule as the dense container): every column
+        // is an independent all-pairs problem over its pool rows.
+        const int variant = o.variant < 0 ? (s.widest >= 64 ? 4 : 2) : o.variant;
+        if (variant < 3) return {PassKernel::Popcount, nullptr, variant, 0, 0, false};
+        // K2b multiplies the pool rows as they are: no FP4 shadow of the pool (2.6 GB at c4), no expansion pass. The rows
+        // behind a column's last one up to the next multiple of 512 are zero in the pool (columns start on multiples of 512
+        // and nothing writes between them). Always the 256-row form.
+        if (variant == 4 && strip_operands_of(o) == 5 && o.k2_debug == 0 && !o.k2_persistent && s.rows_dst <= s.pool_rows_ready + 512)
+            return {PassKernel::Strips, &kStripBits, variant, kStripBits.operands_report, 0, false};
+        return fp4_pass(variant, 0);
+    }
+    }
+    return {PassKernel::Popcount, nullptr, 2, 0, 0, false};   // (not reached)
+}
+
 // ---- write-mode tiles of 256 x 256 ----
 // Launch order of write-mode tiles for L2 reuse. A tile item streams 8 MiB per operand at the
 // headline shape (256 rows x all of k), twice an XCD's L2: in row-major order the 32 tiles an
@@ -1562,7 +1646,7 @@ extern "C" int storm_hip_strip_plan3(uint64_t n_rows, uint32_t n_words, uint32_t
         // slices that hold data: form 0 (FP4 shadow, launch_pairw_mfma_ranges): 256 consecutive bits each;
         // form 1 (K2b, launch_pairw_bits_ranges): slice ks = class pair ks & 1 of the 512-bit chunk ks / 2;
         // form 2 (K2b with 128 A rows per wave, strip16_rows_kernel): 128 consecutive bits each, A tiles of 512 rows
-        const uint32_t n_kslices = form == 0 ? (n_words + 3u) / 4u : form == 1 ? 2u * ((n_words + 7u) / 8u) : strip_rows_kslices(n_words);
+        const StripForm& f = *strip_form_of_plan(form);
         std::vector<RowRange> ranges;
         if (n_rows > 1) ranges.push_back({0, n_rows});
         std::vector<StripItem> items;
@@ -1571,17 +1655,16 @@ extern "C" int storm_hip_strip_plan3(uint64_t n_rows, uint32_t n_words, uint32_t
         o.max_run = max_run;
         // tail_run 0: neither tail option is set (a fresh context) — form 2 chooses both for a whole pass, elsewhere the defaults
         o.tail_auto = tail_run == 0;
-        o.rows_form = form == 2;
+        o.rows_form = f.rows_form();
         o.tail_run = tail_run == 0 ? StripOptions().tail_run : tail_run;
         o.tail_slices = tail_run == 0 ? StripOptions().tail_slices : tail_slices;
         o.lpt_rounds = lpt_rounds;
         o.shard_pairs = pair_space != 0;
         o.n_cus = (int)n_cus;
-        o.xcd_group = form == 0 ? 1 : form == 1 ? 2 : (int)kStripRowsXcdGroup;
+        o.xcd_group = f.xcd_group;
         // exactly what ensure_strip_items launches for these options (one function plans both)
         StripChoice used;
-        plan_strips(strip_request(o, ranges, n_kslices, shard_rank, shard_count, form == 2 ? kStripRowsATile : (uint32_t)kStripATile),
-                    ranges, items, qb, qc, &used);
+        plan_strips(strip_request(o, ranges, f.kslices(n_words), shard_rank, shard_count, f.a_tile), ranges, items, qb, qc, &used);
         // (tail_run 0: the tail in use rides above the run length, which is at most 4096)
         if (run_chosen) *run_chosen = tail_run == 0 ? used.max_run | used.tail_run << 16 | used.tail_slices << 24 : used.max_run;
         *n_items = items.size();

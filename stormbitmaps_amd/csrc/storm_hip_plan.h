@@ -48,10 +48,9 @@ constexpr int kStripBRows = 64;                          // B rows per stage
 constexpr int kStripWaves = 4;                           // waves per workgroup = A tile / 64 rows
 constexpr int kStripATile = 64 * kStripWaves;            // A rows per workgroup (256; 8 waves / 512 rows measured slower)
 // the third strip form (strip16_rows_kernel: 128 A rows per wave): A tiles of 512 rows, k-slices of 16 bytes = 2 words of every
-// row; the 8 slices of a 128-byte line stay on one XCD
+// row; the 8 slices of a 128-byte line stay on one XCD (kStripRows below holds the form's other numbers)
 constexpr uint32_t kStripRowsATile = 512;
 constexpr uint32_t kStripRowsXcdGroup = 8;
-inline uint32_t strip_rows_kslices(uint32_t n_words) { return (n_words + 1u) / 2u; }
 // ... and the schedule of its diagonal phase (the A tile's 8 blocks of 64 rows among themselves: block b against every
 // block d > b whole, against itself as the strict upper triangle). Wave w of the 4 keeps two blocks, its HALVES: the low
 // half is block w, the high half block 7 - w, so that every wave owes 7 whole block products and 2 triangles. The wave
@@ -380,6 +379,77 @@ StripRequest strip_request(const StripOptions& opt, const std::vector<RowRange>&
 // The list in launch order and, for the persistent form, the per-XCD queue bounds; chosen: the shaping in use.
 void plan_strips(const StripRequest& rq, const std::vector<RowRange>& ranges, std::vector<StripItem>& items,
                  uint32_t queue_base[8], uint32_t queue_count[8], StripChoice* chosen = nullptr);
+
+// ---- how an all-pairs pass chooses its form ----
+// One record per strip form: the ONLY place where a form's numbers are written down. The launchers, the panels of
+// storm_hip_pairw_dense_upload, the sparse pass and storm_hip_strip_plan3 read them from here.
+enum class StripKernel : uint32_t { Fp4, Bits, BitsWide, Rows };
+struct StripForm {
+    StripKernel kernel;          // strip16_fp4_kernel | strip16_bits_kernel | strip16_bits2_kernel | strip16_rows_kernel
+    uint32_t a_tile;             // A rows per workgroup: the rows up to the next multiple of it must exist and be zero
+    uint32_t waves;              // a workgroup is 64 x waves threads
+    uint32_t chunk_words;        // a row's words are taken in chunks of this many ...
+    uint32_t slices_per_chunk;   // ... of this many k-slices each (bits: the two class pairs of a 512-bit chunk)
+    int32_t xcd_group;           // consecutive slices that share an XCD
+    uint64_t wave_sum_max;       // the most a wave adds to a slot (the fold inside the launch): A rows per wave x
+                                 // (4096 stages x 64 + the tile's own) rows x bits per slice; 0: the form never folds inline
+    int32_t operands_report;     // k2_operands_used
+    int32_t rows_report;         // k2_strip_rows_used; 0: not a K2b form
+    int32_t plan_form;           // storm_hip_strip_plan3's `form`; -1: none
+    constexpr uint32_t threads() const { return 64u * waves; }
+    constexpr uint32_t chunks(uint32_t n_words) const { return (n_words + chunk_words - 1u) / chunk_words; }
+    constexpr uint32_t kslices(uint32_t n_words) const { return slices_per_chunk * chunks(n_words); }   // slices that hold data
+    constexpr uint32_t slice_words() const { return chunk_words / slices_per_chunk; }                   // the pass report's unit
+    constexpr bool rows_form() const { return kernel == StripKernel::Rows; }
+};
+constexpr StripForm kStripFp4 = {StripKernel::Fp4, (uint32_t)kStripATile, (uint32_t)kStripWaves, 4u, 1u, 1, 0ull, 4, 0, 0};
+constexpr StripForm kStripBits = {StripKernel::Bits, (uint32_t)kStripATile, (uint32_t)kStripWaves, 8u, 2u, 2,
+                                  64ull * (4096ull * 64ull + 256ull) * 256ull, 5, 64, 1};
+constexpr StripForm kStripBitsWide = {StripKernel::BitsWide, 512u, 8u, 8u, 2u, 2, kStripBits.wave_sum_max, 6, 64, -1};
+constexpr StripForm kStripRows = {StripKernel::Rows, kStripRowsATile, kStripRowsWaves, 2u, 1u, (int32_t)kStripRowsXcdGroup,
+                                  128ull * (4096ull * 64ull + 512ull) * 128ull, 5, 128, 2};
+static_assert(kStripRows.kslices(1023) == 512u && kStripBits.kslices(1024) == 256u && kStripFp4.kslices(5) == 2u, "slices that hold data");
+static_assert(kStripBits.slice_words() == 4u && kStripRows.slice_words() == 2u, "a slice is 256 bit-MACs per pair, the rows form's 128");
+constexpr const StripForm* strip_form_of_plan(int form) {   // storm_hip_strip_plan3's forms 0 / 1 / 2
+    return form == kStripFp4.plan_form ? &kStripFp4 : form == kStripBits.plan_form ? &kStripBits
+         : form == kStripRows.plan_form ? &kStripRows : nullptr;
+}
+
+// Which kernel an all-pairs pass runs, on which form: ONE pure function of the selecting options, the shape and the
+// caller (storm_hip_plan.cpp, with the measurements behind its rules). Every pass asks it once and switches on the answer.
+constexpr int kStripRingDefault = 4;
+enum class PassCaller : uint32_t { Dense, DenseUpload, SparsePool };
+enum class PassKernel : uint32_t {
+    Popcount,        // K1
+    Fp4Tiles,        // pairw_fp4_kernel over the FP4 shadow (variant 3)
+    Fp4Strips,       // the FP4 strips, 256-row A tiles (also where the bit operands cannot run: the chunked shadow path)
+    Fp4StripsWide,   // ... 512-row A tiles (variant 5)
+    Bitstream,       // K2q
+    Strips,          // K2b: `form` says which
+    ToolsStripBits,  // k2_strip_operands 1 (stripbits_kernel): tools build; the shipped library refuses at the launch
+    ToolsBitwave,    // k2_strip_operands 3 (K2w): tools build
+};
+struct PassOptions {   // context options of the same names
+    int32_t variant, k2_strip_operands, k2_strip_rows, k2_ring, k2_shape, k2_persistent, k2_debug;
+    bool tools_build;
+};
+struct PassShape {
+    uint64_t n_rows = 0, n_rows_pad = 0, stride_words = 0;   // dense and dense-upload: the matrix
+    uint32_t n_words = 0, shard_count = 1;
+    // sparse pool: the pool rows the matrix cores multiply up to the next multiple of 512, the rows the pool holds, and
+    // the widest block column (variant -1 decides by it)
+    uint64_t rows_dst = 0, pool_rows_ready = 0, widest = 0;
+};
+struct PassChoice {
+    PassKernel kernel;
+    const StripForm* form;   // Strips: the form; NULL otherwise
+    int32_t variant_used;
+    int32_t operands_used;   // k2_operands_used; 0: the pass does not write it (popcount, the pool's FP4 paths)
+    int32_t strip_mode;      // launch_pairw_mfma_ranges' (the FP4 kernels): 0 tiles, 1 strips, 2 wide strips
+    bool in_panels;          // dense-upload: the pass runs panel by panel behind the copies (always kStripBits, runs of
+                             // 128); false: the copy, then the dense pass, which the other members describe
+};
+PassChoice choose_pass(PassCaller caller, const PassOptions& o, const PassShape& s);
 
 // ---- write-mode tiles of 256 x 256 ----
 // Launch order of the tiles [i0, i1) x [j0, j1) (upper triangle only when `triangle`) for L2 reuse: appended to `out`.

@@ -1549,12 +1549,10 @@ int storm_hip_pairw_sparse_begin(storm_hip_ctx_t* ctx, const storm_hip_sparse_t*
     uint64_t* const d_result = result_target(ctx);   // the mailbox, or ctx->d_scalar
     memcpy(ctx->sparse_census, s->census, sizeof(s->census));
     memset(ctx->pass_report, 0, sizeof(ctx->pass_report));
-    // Matrix-core path when the columns are big enough to fill the chip (same rule as the dense
-    // container): every column is an independent all-pairs problem over its pool rows.
-    uint64_t widest = 0;
-    for (const RowRange& c : s->cols) widest = std::max(widest, c.r1 - c.r0);
-    int variant = ctx->variant;
-    if (variant < 0) variant = widest >= 64 ? 4 : 2;
+    // (choose_pass is asked twice: the variant needs the widest column only, the strips' form what the pool holds by then)
+    PassShape shape;
+    for (const RowRange& c : s->cols) shape.widest = std::max(shape.widest, c.r1 - c.r0);
+    const int variant = choose_pass(PassCaller::SparsePool, pass_options_of(ctx), shape).variant_used;
     ctx->variant_used = variant;
     if (variant < 3) {
         if (int rc = ensure_full_pool(ctx, s)) return rc;  // the popcount kernel walks every column's pool rows
@@ -1602,28 +1600,25 @@ int storm_hip_pairw_sparse_begin(storm_hip_ctx_t* ctx, const storm_hip_sparse_t*
         if (probe_folds) {   // the total is in d_scalar already: nothing to multiply, nothing to fold
             ctx->last_info[0] = 0;
             ctx->last_info[3] = s->n_probe_cols_launch;
-            ctx->k2_operands_used = 5;
-            ctx->k2_strip_rows_used = 64;
+            ctx->k2_operands_used = kStripBits.operands_report;
+            ctx->k2_strip_rows_used = kStripBits.rows_report;
             return STORM_HIP_OK;
         }
     }
     if (rows_needed > s->pool_rows_ready)
         if (int rc = ensure_full_pool(ctx, s)) return rc;
     // (only the rows the dense pass multiplies are expanded: the probe columns lie behind them)
-    const uint64_t rows_dst = (rows_needed + 511) / 512 * 512;
-    // The strips on bit operands (K2b) multiply the pool rows as they are: no FP4 shadow of the pool (2.6 GB
-    // at c4), no expansion pass. The rows behind a column's last one up to the next multiple of 512 are zero
-    // in the pool (columns start on multiples of 512 and nothing writes between them).
-    if (variant == 4 && strip_operands_of(ctx) == 5 && ctx->k2_debug == 0 && !ctx->k2_persistent &&
-        rows_dst <= s->pool_rows_ready + 512) {
+    shape.rows_dst = (rows_needed + 511) / 512 * 512;
+    shape.pool_rows_ready = s->pool_rows_ready;
+    const PassChoice pass = choose_pass(PassCaller::SparsePool, pass_options_of(ctx), shape);
+    if (pass.kernel == PassKernel::Strips) {   // K2b on the pool rows as they are (a block is kBlockWords wide)
         if (int rc = launch_pairw_bits_ranges(ctx, reinterpret_cast<const uint8_t*>(s->d_pool), s->pitch * 8ull,
-                                              ranges, kBlockWords / 4u, shard_rank, shard_count,
+                                              ranges, *pass.form, kBlockWords, shard_rank, shard_count,
                                               d_result, s->n_probe_launch > 0))
             return rc;
     } else if (int rc = launch_pairw_mfma_ranges(ctx, s->d_pool, s->pitch, s->pool_rows_ready + 512,
-                                                 std::max<uint64_t>(rows_dst, 512), ranges,
-                                                 shard_rank, shard_count, variant == 5 ? 2 : variant == 4 ? 1 : 0,
-                                                 d_result))
+                                                 std::max<uint64_t>(shape.rows_dst, 512), ranges,
+                                                 shard_rank, shard_count, pass.strip_mode, d_result))
         return rc;
     ctx->last_info[3] = s->n_probe_cols_launch;  // block columns counted by the list-probe kernel
     return STORM_HIP_OK;
