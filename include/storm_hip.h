@@ -229,7 +229,7 @@ int storm_hip_cross_dense_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_t*
  *   every converted entry is overwritten in place with its float. d_counts_rows[n_rows] / d_counts_cols[n_cols] (device)
  *   are the set-bit counts of the rows' and the columns' side. triangle != 0: only entries i < j (n_rows == n_cols);
  *   entries i >= j and the pitch columns [n_cols, ld) are neither read nor written. Asynchronous on the context's
- *   stream (similarity_finish_kernel). STORM_HIP_EINVAL: NULL argument, unknown measure, n_bits 0 or above 2^32,
+ *   stream (finish_tiles_kernel<SimilarityStat>). STORM_HIP_EINVAL: NULL argument, unknown measure, n_bits 0 or above 2^32,
  *   ld < n_cols, a triangle that is not square. Empty shapes: STORM_HIP_OK, nothing touched. A caller with a count
  *   matrix of its own needs nothing else; the last-pass report is then STORM_HIP_RAN_SIMILARITY alone.
  * The other forms are the AND-count path of the operand kind (storm_hip_pairw_matrix_device, _cross_dense_matrix_device,
@@ -268,7 +268,7 @@ int storm_hip_cross_dense_similarity(storm_hip_ctx_t* ctx, const storm_hip_matri
  *   columns [L, ld) stay untouched (the n x L device matrix in between is the context's band buffer).
  * _similarity_finish_lag_device: the in-place uint32 -> float pass (see storm_hip_similarity_finish_device) over a count
  *   matrix in the lag layout: entry (i - row0, d) from d_counts[i] and d_counts[i + 1 + d] (d_counts: n_rows set-bit counts,
- *   device). Asynchronous on the context's stream (similarity_finish_lag_kernel); alone the last-pass report is
+ *   device). Asynchronous on the context's stream (finish_lag_tiles_kernel<SimilarityStat>); alone the last-pass report is
  *   STORM_HIP_RAN_SIMILARITY.
  * _lag_similarity_device / _lag_similarity: the AND counts, the rows' counts, then that pass; complete on return; host form:
  *   +0.0f in the corner. Bit-identical to the same pairs of storm_hip_pairw_similarity.
@@ -343,7 +343,7 @@ int storm_hip_cross_dense_topk(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a
  *   dosage form (tile128_kernel on two classes per nibble at block scale 128: the FP4 codes 0 .. 3 are linear in the
  *   value), whatever k2_tile_shape says; read-only option "k2_tile_shape_used" then reads 7 (6: K2h on
  *   bits). _device: entries i >= j stay as they were, complete on return. Host form: whole rows, 0 at i >= j.
- * _pairw_dosage_corr[_device]: the dot products, the rows' sums, then dosage_finish_kernel in place; n_samples must be
+ * _pairw_dosage_corr[_device]: the dot products, the rows' sums, then finish_tiles_kernel<DosageStat, true> in place; n_samples must be
  *   the S the rows were packed with (ceil(S / 32) == the matrix's words). Host form: +0.0f at i >= j.
  * STORM_HIP_EINVAL: NULL argument, ld < rows, unknown measure, n_samples that does not match the row width, rows of more
  * than 2^24 values, rows beyond K2h's reach. Fewer than two rows: STORM_HIP_OK, nothing written (host forms of one row:
@@ -398,7 +398,7 @@ int storm_hip_pairw_dosage_corr_complete(storm_hip_ctx_t* ctx, const storm_hip_m
  * panel: PLINK's --r2 --ld-snp-list ... inter-chr), entry out[i * ld + j], ld >= b's rows; each row's sums are taken in
  * its own matrix. A may be B.
  * _square_dosage_corr[_device]: 3 is an ordinary value. The dot products (storm_hip_square_dosage_matrix_device), both
- *   matrices' row sums, then dosage_square_finish_kernel in place: _pairw_dosage_corr's formula and bits for the pair.
+ *   matrices' row sums, then finish_tiles_kernel<DosageStat, false> in place: _pairw_dosage_corr's formula and bits for the pair.
  * _square_dosage_nobs[_device], _square_dosage_corr_complete[_device]: code 3 means MISSING, as in the block above. Both
  *   matrices are split into G, H and M (once when A is B); _nobs is M_a x M_b; _corr_complete is six n_a x n_b products on
  *   K2h in three launches — G_a x G_b into the output, [G_a ; H_a] x M_b and M_a x [G_b ; H_b ; M_b] into scratch — and
@@ -486,7 +486,7 @@ int storm_hip_square_dosage_topk_complete(storm_hip_ctx_t* ctx, const storm_hip_
  * _lag_dosage_matrix: all rows into HOST memory: columns [0, L) of every row are written, 0 in the corner; columns [L, ld)
  *   stay untouched.
  * _dosage_finish_lag_device: the in-place uint32 -> float pass alone over a matrix of dot products in the lag layout
- *   (dosage_finish_lag_kernel): entry (i - row0, d) from d_sum / d_sum_sq (n_rows entries each, device) of rows i and
+ *   (finish_lag_tiles_kernel<DosageStat>): entry (i - row0, d) from d_sum / d_sum_sq (n_rows entries each, device) of rows i and
  *   i + 1 + d. Asynchronous on the context's stream; alone the last-pass report is STORM_HIP_RAN_SIMILARITY.
  * _lag_dosage_corr[_device]: the dot products, the rows' sums, then that pass. Bit-identical to the same pairs of
  *   storm_hip_pairw_dosage_corr. Host form: +0.0f in the corner.
@@ -870,7 +870,7 @@ typedef struct storm_hip_comm_s storm_hip_comm_t;
 #define STORM_HIP_RAN_TILES_OUT 128u  /* tilering_kernel / tilebits8_kernel: per-pair output of a dense matrix (or replica) roof: FP4 matrix cores */
 #define STORM_HIP_RAN_LISTS_MATRIX 64u /* lists_matrix_kernel (K5), per-pair output from the lists: out[2] = its table lookups, out[3] = 64 */
 #define STORM_HIP_RAN_LISTS_SQUARE 256u /* lists_square_kernel (K5x), the rectangle of two list-only containers: out[2] = its table lookups, out[3] = 64 */
-#define STORM_HIP_RAN_SIMILARITY 512u /* similarity_finish_kernel behind one of the per-pair kernels above (its flag stays set), or alone (storm_hip_similarity_finish_device)  roof: HBM bandwidth */
+#define STORM_HIP_RAN_SIMILARITY 512u /* the finishing pass (finish_tiles_kernel, finish_lag_tiles_kernel) behind one of the per-pair kernels above (its flag stays set), or alone (storm_hip_similarity_finish_device)  roof: HBM bandwidth */
 #define STORM_HIP_RAN_TOPK 1024u /* topk_rows_kernel behind the panels' count kernel (its flag stays set), or alone (storm_hip_topk_rows_device)  roof: HBM bandwidth */
 int storm_hip_last_pass_report(storm_hip_ctx_t* ctx, uint64_t out[4]);
 

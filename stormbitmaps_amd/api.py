@@ -849,7 +849,7 @@ class HipContext:
         out = (C.c_uint64 * 4)()
         check(self._lib.storm_hip_last_pass_report(self._h, out), "storm_hip_last_pass_report")
         names = {1: "pairw_dense_kernel", 2: "pairw_fp4_kernel", 4: "strip16_fp4_kernel", 8: "bitstream_kernel",
-                 16: "strip16_bits_kernel", 32: "probe_lists_kernel", 512: "similarity_finish_kernel"}
+                 16: "strip16_bits_kernel", 32: "probe_lists_kernel", 512: "finish_tiles_kernel"}
         return {"kernels": [n for b, n in names.items() if out[0] & b], "dense_word_pairs": int(out[1]),
                 "probe_lookups": int(out[2]), "rows_per_lookup": int(out[3])}
 

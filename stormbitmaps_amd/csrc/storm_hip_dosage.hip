@@ -1,19 +1,19 @@
 // storm_hip_dosage.hip — rows of 2-bit VALUES (genotype dosages 0 / 1 / 2; 3 is an ordinary value) instead of bits: value s
 // of a row in bits 2 (s % 32), 2 (s % 32) + 1 of word s / 32 of an ordinary storm_hip_matrix_t. The dot products of all row
 // pairs come from K2h in its dosage form (tile128_kernel<false, 2>, storm_hip_mfma.hip: launch_pairw_dosage_matrix); this
-// file holds the two small kernels around it — the rows' sums and sums of squares, and the in-place uint32 -> float pass
-// that turns a dot product into PLINK's --r / --r2, the (squared) Pearson correlation of two dosage vectors — and the
-// C-ABI of the form. Plain vector code; the formulas are storm_dosage_math.h.
+// file holds what stands around it — the rows' sums and sums of squares, and DosageStat, the policy under which the shared
+// in-place uint32 -> float pass (finish_tiles_kernel.inc; the triangle: finish_tiles_kernel<DosageStat, true>) turns a dot
+// product into PLINK's --r / --r2, the (squared) Pearson correlation of two dosage vectors — and the C-ABI of the form. Plain vector code; the formulas are storm_dosage_math.h.
 // Missing genotypes (the *_complete, *_nobs and *_row_missing calls only: code 3 = missing there, an ordinary value in
 // every other call): dosage_split_missing_kernel splits the rows into three matrices of 2-bit rows — G (3 -> 0), H (1 where
 // the value is 2) and M (1 where present) — K2h multiplies the triangles of G and of M and the rectangle [G ; H] x M, and
 // dosage_complete_finish_kernel turns the five sums of a pair into r / r^2 over the samples both rows have (DESIGN.md §4,
 // "K2h, dosage form with missing genotypes").
 // The rectangle of two matrices (the *_square_dosage_* calls): K2h over n_a x n_b; for r / r^2 both matrices' row sums and
-// dosage_square_finish_kernel, or both matrices' splits, six products in three launches and
+// finish_tiles_kernel<DosageStat, false>, or both matrices' splits, six products in three launches and
 // dosage_square_complete_finish_kernel ("K2h, dosage form: the rectangle of two containers").
 // The lag layout (the *_lag_dosage_* calls: the pairs within max_lag rows of each other, an n x L matrix): K2h in its lag and
-// dosage form (tile128_kernel<true, 2>: launch_pairw_lag_dosage_matrix), dosage_finish_lag_kernel over it, and for missing
+// dosage form (tile128_kernel<true, 2>: launch_pairw_lag_dosage_matrix), finish_lag_tiles_kernel<DosageStat> over it, and for missing
 // genotypes dosage_split_interleaved_kernel — G, H and M as ONE matrix of 3 n rows — one launch at lag 3 L + 2 into a scratch
 // matrix of 3 n x (3 L + 2) words and dosage_complete_finish_lag_kernel from there into the caller's matrix: O(n L)
 // throughout ("K2h, dosage form in the lag layout").
@@ -53,63 +53,28 @@ __global__ __launch_bounds__(kThreads) void dosage_row_sums_kernel(const uint64_
     }
 }
 
-constexpr int kDosTileRows = 64;    // a wave walks every 4th row of the tile ...
-constexpr int kDosTileCols = 256;   // ... one 128-bit vector (4 entries) per lane
-constexpr int kDosUnroll = 4;       // rows a wave has in flight
+// r / r^2 as finish_tiles_kernel.inc takes them — the finishing pass over a matrix of dot products in place, shared with the
+// bit statistics (storm_hip_similarity.hip) — two words per row: its sum and its sum of squares
+struct DosageStat {
+    static constexpr int W = 2;
+    static __device__ __forceinline__ uint32_t bits(uint32_t P, const uint32_t (&a)[2], const uint32_t (&b)[2], int measure,
+                                                    uint64_t n_samples) {
+        return dosage_corr_bits(P, a[0], a[1], b[0], b[1], measure, n_samples);
+    }
+    static int check(const char* who, int measure, uint64_t n_samples) {
+        if (measure != STORM_HIP_DOSAGE_R2 && measure != STORM_HIP_DOSAGE_R) {
+            set_error("%s: unknown measure %d (0 r^2, 1 r)", who, measure);
+            return STORM_HIP_EINVAL;
+        }
+        if (n_samples == 0 || n_samples > kDosageMaxSamples) {
+            set_error("%s: n_samples %llu is not in [1, 2^24]", who, (unsigned long long)n_samples);
+            return STORM_HIP_EINVAL;
+        }
+        return STORM_HIP_OK;
+    }
+};
 
-// The finishing pass over the upper triangle of an n x n matrix of dot products, in place (similarity_finish_kernel's
-// shape: grid (column tiles, row tiles), a tile at or below the diagonal exits at once; entries i >= j and the pitch columns
-// [n, ld) are neither read nor written; vec: 16-byte aligned base and ld a multiple of 4).
-__global__ __launch_bounds__(256) void dosage_finish_kernel(uint32_t* __restrict__ io, uint64_t ld, uint64_t n,
-                                                            const uint32_t* __restrict__ sum, const uint32_t* __restrict__ sum_sq,
-                                                            int measure, uint64_t n_samples, int vec) {
-    const uint64_t row0 = (uint64_t)blockIdx.y * kDosTileRows, col0 = (uint64_t)blockIdx.x * kDosTileCols;
-    if (col0 + kDosTileCols <= row0 + 1) return;   // the tile's last column is not beyond its first row
-    __shared__ uint32_t s_sum[kDosTileRows], s_sq[kDosTileRows];
-    if (threadIdx.x < kDosTileRows) {
-        const bool in = row0 + threadIdx.x < n;
-        s_sum[threadIdx.x] = in ? sum[row0 + threadIdx.x] : 0u;
-        s_sq[threadIdx.x] = in ? sum_sq[row0 + threadIdx.x] : 0u;
-    }
-    const uint64_t c0 = col0 + (threadIdx.x & 63u) * 4u;
-    uint32_t bs[4], bq[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        bs[k] = c0 + k < n ? sum[c0 + k] : 0u;
-        bq[k] = c0 + k < n ? sum_sq[c0 + k] : 0u;
-    }
-    __syncthreads();
-    const uint32_t wave = threadIdx.x >> 6;
-    for (uint32_t r = wave; r < kDosTileRows; r += 4 * kDosUnroll) {
-        uint4 v[kDosUnroll];
-        bool whole[kDosUnroll];
-#pragma unroll
-        for (int u = 0; u < kDosUnroll; ++u) {   // the loads of kDosUnroll rows leave before the first divide
-            const uint64_t i = row0 + r + 4u * u;
-            whole[u] = vec && i < n && c0 + 4 <= n && c0 > i;
-            if (whole[u]) v[u] = *reinterpret_cast<const uint4*>(io + i * ld + c0);
-        }
-#pragma unroll
-        for (int u = 0; u < kDosUnroll; ++u) {
-            const uint64_t i = row0 + r + 4u * u;
-            if (i >= n) continue;
-            const uint32_t as = s_sum[r + 4u * u], aq = s_sq[r + 4u * u];
-            uint32_t* const p = io + i * ld + c0;
-            if (whole[u]) {
-                uint4 w;
-                w.x = dosage_corr_bits(v[u].x, as, aq, bs[0], bq[0], measure, n_samples);
-                w.y = dosage_corr_bits(v[u].y, as, aq, bs[1], bq[1], measure, n_samples);
-                w.z = dosage_corr_bits(v[u].z, as, aq, bs[2], bq[2], measure, n_samples);
-                w.w = dosage_corr_bits(v[u].w, as, aq, bs[3], bq[3], measure, n_samples);
-                *reinterpret_cast<uint4*>(p) = w;
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (c0 + k < n && c0 + k > i) p[k] = dosage_corr_bits(p[k], as, aq, bs[k], bq[k], measure, n_samples);
-            }
-        }
-    }
-}
+#include "finish_tiles_kernel.inc"
 
 // ---- rows with missing genotypes ----
 // One word per thread: word w of row `row` of X into the same word of G, H and M (rows of `stride_words` words each,
@@ -186,67 +151,6 @@ __global__ __launch_bounds__(256) void dosage_complete_finish_kernel(uint32_t* _
 }
 
 // ---- the lag layout ("K2h, dosage form in the lag layout") ----
-// dosage_finish_kernel over the LAG layout (similarity_finish_lag_kernel's shape): entry (r, d) of the band is the pair
-// (i, i + 1 + d), i = row0 + r, so a tile of kDosTileRows x kDosTileCols entries reads s and q of its 64 rows and of the
-// 64 + 256 rows i0 + 1 + col0 .. behind them: both staged once per workgroup. Only entries with d < lag and
-// i + 1 + d < n_rows are touched (the lower-right corner and the pitch columns are neither read nor written); a lane's 4
-// entries are one 128-bit access where all 4 are converted and `vec`, else entry by entry.
-__global__ __launch_bounds__(256) void dosage_finish_lag_kernel(uint32_t* __restrict__ io, uint64_t ld, uint64_t n_rows, uint64_t row0,
-                                                                uint64_t band_end, uint64_t lag, const uint32_t* __restrict__ sum,
-                                                                const uint32_t* __restrict__ sum_sq, int measure,
-                                                                uint64_t n_samples, int vec) {
-    const uint64_t i0 = row0 + (uint64_t)blockIdx.y * kDosTileRows, col0 = (uint64_t)blockIdx.x * kDosTileCols;
-    if (i0 + 1 + col0 >= n_rows) return;   // the tile's first pair is already in the corner
-    __shared__ uint32_t s_sum[kDosTileRows], s_sq[kDosTileRows];
-    __shared__ uint32_t c_sum[kDosTileRows + kDosTileCols], c_sq[kDosTileRows + kDosTileCols];
-    if (threadIdx.x < kDosTileRows) {
-        const bool in = i0 + threadIdx.x < band_end;
-        s_sum[threadIdx.x] = in ? sum[i0 + threadIdx.x] : 0u;
-        s_sq[threadIdx.x] = in ? sum_sq[i0 + threadIdx.x] : 0u;
-    }
-    for (uint32_t k = threadIdx.x; k < kDosTileRows + kDosTileCols; k += 256u) {
-        const bool in = i0 + 1 + col0 + k < n_rows;
-        c_sum[k] = in ? sum[i0 + 1 + col0 + k] : 0u;
-        c_sq[k] = in ? sum_sq[i0 + 1 + col0 + k] : 0u;
-    }
-    __syncthreads();
-    const uint32_t lane4 = (threadIdx.x & 63u) * 4u;
-    const uint64_t c0 = col0 + lane4;
-    const uint32_t wave = threadIdx.x >> 6;
-    for (uint32_t r = wave; r < kDosTileRows; r += 4 * kDosUnroll) {
-        uint4 v[kDosUnroll];
-        bool whole[kDosUnroll];
-#pragma unroll
-        for (int u = 0; u < kDosUnroll; ++u) {   // the loads of kDosUnroll rows leave before the first divide
-            const uint64_t i = i0 + r + 4u * u;
-            whole[u] = vec && i < band_end && c0 + 4 <= lag && i + 1 + c0 + 3 < n_rows;
-            if (whole[u]) v[u] = *reinterpret_cast<const uint4*>(io + (i - row0) * ld + c0);
-        }
-#pragma unroll
-        for (int u = 0; u < kDosUnroll; ++u) {
-            const uint32_t rr = r + 4u * u;
-            const uint64_t i = i0 + rr;
-            if (i >= band_end) continue;
-            const uint32_t as = s_sum[rr], aq = s_sq[rr];
-            const uint32_t* const bs = &c_sum[rr + lane4];   // entry d = c0 + k: row i + 1 + c0 + k
-            const uint32_t* const bq = &c_sq[rr + lane4];
-            uint32_t* const p = io + (i - row0) * ld + c0;
-            if (whole[u]) {
-                uint4 w;
-                w.x = dosage_corr_bits(v[u].x, as, aq, bs[0], bq[0], measure, n_samples);
-                w.y = dosage_corr_bits(v[u].y, as, aq, bs[1], bq[1], measure, n_samples);
-                w.z = dosage_corr_bits(v[u].z, as, aq, bs[2], bq[2], measure, n_samples);
-                w.w = dosage_corr_bits(v[u].w, as, aq, bs[3], bq[3], measure, n_samples);
-                *reinterpret_cast<uint4*>(p) = w;
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (c0 + k < lag && i + 1 + c0 + k < n_rows) p[k] = dosage_corr_bits(p[k], as, aq, bs[k], bq[k], measure, n_samples);
-            }
-        }
-    }
-}
-
 // One word per thread of the INTERLEAVED split of X (dosage_interleaved_word: row 3 i = G_i, 3 i + 1 = H_i, 3 i + 2 = M_i):
 // rows_out rows of stride_words words, zero behind row 3 n_rows and behind word n_words. Grid (rows, word tiles).
 __global__ __launch_bounds__(256) void dosage_split_interleaved_kernel(const uint64_t* __restrict__ X, uint64_t stride_words,
@@ -316,17 +220,12 @@ static int dosage_corr_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m,
     const uint64_t n = m->n_rows;
     if (int rc = launch_pairw_dosage_matrix(ctx, m, d_io, ld)) return rc;
     if (int rc = dosage_sums_queued(ctx, m)) return rc;
-    const uint64_t tiles_x = (n + kDosTileCols - 1) / kDosTileCols, tiles_y = (n + kDosTileRows - 1) / kDosTileRows;
-    if (tiles_y > 65535u) {
+    if (!finish_tiles_fit(n, n)) {
         set_error("pairw_dosage_corr: %llu rows exceed the finishing pass's launch grid", (unsigned long long)n);
         return STORM_HIP_EINVAL;
     }
-    const int vec = reinterpret_cast<uintptr_t>(d_io) % 16 == 0 && ld % 4 == 0;
-    hipLaunchKernelGGL(dosage_finish_kernel, dim3((uint32_t)tiles_x, (uint32_t)tiles_y), dim3(256), 0, ctx->stream, d_io, ld, n,
-                       ctx->d_counts.d, ctx->d_counts.d + n, measure, n_samples, vec);
-    STORM_HIP_TRY(hipGetLastError());
-    ctx->pass_report[0] |= STORM_HIP_RAN_SIMILARITY;
-    return STORM_HIP_OK;
+    const StatWords<2> sums{{ctx->d_counts.d, ctx->d_counts.d + n}};
+    return launch_finish_tiles<DosageStat>(ctx, "pairw_dosage_corr", d_io, ld, n, n, sums, sums, true, measure, n_samples);
 }
 
 // The split operands of a matrix with missing genotypes, in ctx->d_dosage_rows: G, H and M as matrices of rows128 =
@@ -469,60 +368,6 @@ int check_square(const char* who, const storm_hip_matrix_s* a, const storm_hip_m
 
 // ---- the rectangle of two matrices: r / r^2 and N of every row of A against every row of B ("K2h, dosage
 // form: the rectangle of two containers") ----
-// dosage_finish_kernel without the triangle test, over an n_a x n_b matrix of dot products in place: s and q of the tile's
-// rows of A through the LDS, those of a lane's 4 columns of B in registers. Entries outside the n_a x n_b window — the pitch
-// columns, rows beyond n_a — are neither read nor written; vec: 16-byte aligned base and ld a multiple of 4, and then a
-// lane whose 4 columns all exist takes them in one 128-bit access.
-__global__ __launch_bounds__(256) void dosage_square_finish_kernel(uint32_t* __restrict__ io, uint64_t ld, uint64_t n_a, uint64_t n_b,
-                                                                   const uint32_t* __restrict__ a_sum, const uint32_t* __restrict__ a_sq,
-                                                                   const uint32_t* __restrict__ b_sum, const uint32_t* __restrict__ b_sq,
-                                                                   int measure, uint64_t n_samples, int vec) {
-    const uint64_t row0 = (uint64_t)blockIdx.y * kDosTileRows, col0 = (uint64_t)blockIdx.x * kDosTileCols;
-    __shared__ uint32_t s_sum[kDosTileRows], s_sq[kDosTileRows];
-    if (threadIdx.x < kDosTileRows) {
-        const bool in = row0 + threadIdx.x < n_a;
-        s_sum[threadIdx.x] = in ? a_sum[row0 + threadIdx.x] : 0u;
-        s_sq[threadIdx.x] = in ? a_sq[row0 + threadIdx.x] : 0u;
-    }
-    const uint64_t c0 = col0 + (threadIdx.x & 63u) * 4u;
-    uint32_t bs[4], bq[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        bs[k] = c0 + k < n_b ? b_sum[c0 + k] : 0u;
-        bq[k] = c0 + k < n_b ? b_sq[c0 + k] : 0u;
-    }
-    __syncthreads();
-    const bool whole = vec && c0 + 4 <= n_b;
-    const uint32_t wave = threadIdx.x >> 6;
-    for (uint32_t r = wave; r < kDosTileRows; r += 4 * kDosUnroll) {
-        uint4 v[kDosUnroll];
-#pragma unroll
-        for (int u = 0; u < kDosUnroll; ++u) {   // the loads of kDosUnroll rows leave before the first divide
-            const uint64_t i = row0 + r + 4u * u;
-            if (whole && i < n_a) v[u] = *reinterpret_cast<const uint4*>(io + i * ld + c0);
-        }
-#pragma unroll
-        for (int u = 0; u < kDosUnroll; ++u) {
-            const uint64_t i = row0 + r + 4u * u;
-            if (i >= n_a) continue;
-            const uint32_t as = s_sum[r + 4u * u], aq = s_sq[r + 4u * u];
-            uint32_t* const p = io + i * ld + c0;
-            if (whole) {
-                uint4 w;
-                w.x = dosage_corr_bits(v[u].x, as, aq, bs[0], bq[0], measure, n_samples);
-                w.y = dosage_corr_bits(v[u].y, as, aq, bs[1], bq[1], measure, n_samples);
-                w.z = dosage_corr_bits(v[u].z, as, aq, bs[2], bq[2], measure, n_samples);
-                w.w = dosage_corr_bits(v[u].w, as, aq, bs[3], bq[3], measure, n_samples);
-                *reinterpret_cast<uint4*>(p) = w;
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (c0 + k < n_b) p[k] = dosage_corr_bits(p[k], as, aq, bs[k], bq[k], measure, n_samples);
-            }
-        }
-    }
-}
-
 // The finishing pass of the pairwise-complete correlation over an n_a x n_b matrix of dot products P = G_a G_b^T, in place
 // (uint32 -> float). All six sums of entry (i, j) lie at (i, j) of their matrices — `ghm` = [G_a ; H_a] x M_b (pitch ld_ghm:
 // sx at row i, H_a M_b at row h_row0 + i) and `mghm` = M_a x [G_b ; H_b ; M_b] (pitch ld_mghm: sy at column j, M_a H_b at
@@ -535,10 +380,10 @@ __global__ __launch_bounds__(256) void dosage_square_complete_finish_kernel(uint
                                                                             uint64_t h_col0, uint64_t m_col0, int measure) {
     const uint64_t row0 = (uint64_t)blockIdx.y * kDosCompleteTile, j = (uint64_t)blockIdx.x * kDosCompleteTile + (threadIdx.x & 63u);
     if (j >= n_b) return;
-    for (uint32_t a = threadIdx.x >> 6; a < kDosCompleteTile; a += 4 * kDosUnroll) {
-        uint32_t P[kDosUnroll], N[kDosUnroll], sx[kDosUnroll], sy[kDosUnroll], hx[kDosUnroll], hy[kDosUnroll];
+    for (uint32_t a = threadIdx.x >> 6; a < kDosCompleteTile; a += 4 * kFinishUnroll) {
+        uint32_t P[kFinishUnroll], N[kFinishUnroll], sx[kFinishUnroll], sy[kFinishUnroll], hx[kFinishUnroll], hy[kFinishUnroll];
 #pragma unroll
-        for (int u = 0; u < kDosUnroll; ++u) {   // the loads of kDosUnroll rows leave before the first divide
+        for (int u = 0; u < kFinishUnroll; ++u) {   // the loads of kFinishUnroll rows leave before the first divide
             const uint64_t i = row0 + a + 4u * u;
             if (i >= n_a) continue;
             const uint32_t* const mrow = mghm + i * ld_mghm;
@@ -550,7 +395,7 @@ __global__ __launch_bounds__(256) void dosage_square_complete_finish_kernel(uint
             N[u] = mrow[m_col0 + j];
         }
 #pragma unroll
-        for (int u = 0; u < kDosUnroll; ++u) {
+        for (int u = 0; u < kFinishUnroll; ++u) {
             const uint64_t i = row0 + a + 4u * u;
             if (i < n_a) io[i * ld + j] = dosage_corr_complete_bits(P[u], N[u], sx[u], sy[u], sx[u] + 2u * hx[u], sy[u] + 2u * hy[u], measure);
         }
@@ -577,8 +422,7 @@ int dosage_square_sums_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
 static int square_dosage_corr_queued(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a, const storm_hip_matrix_s* b, int measure,
                                      uint64_t n_samples, uint32_t* d_io, uint64_t ld) {
     const uint64_t na = a->n_rows, nb = b->n_rows;
-    const uint64_t tiles_x = (nb + kDosTileCols - 1) / kDosTileCols, tiles_y = (na + kDosTileRows - 1) / kDosTileRows;
-    if (tiles_y > 65535u || tiles_x > 0x7fffffffu) {
+    if (!finish_tiles_fit(na, nb)) {   // (before anything is queued)
         set_error("square_dosage_corr: %llu x %llu entries exceed the finishing pass's launch grid", (unsigned long long)na,
                   (unsigned long long)nb);
         return STORM_HIP_EINVAL;
@@ -586,12 +430,9 @@ static int square_dosage_corr_queued(storm_hip_ctx_t* ctx, const storm_hip_matri
     if (int rc = launch_square_dosage_matrix(ctx, a, b, d_io, ld)) return rc;
     SquareSums s;
     if (int rc = dosage_square_sums_queued(ctx, a, b, &s)) return rc;
-    const int vec = reinterpret_cast<uintptr_t>(d_io) % 16 == 0 && ld % 4 == 0;
-    hipLaunchKernelGGL(dosage_square_finish_kernel, dim3((uint32_t)tiles_x, (uint32_t)tiles_y), dim3(256), 0, ctx->stream, d_io, ld, na,
-                       nb, s.a_sum, s.a_sq, s.b_sum, s.b_sq, measure, n_samples, vec);
-    STORM_HIP_TRY(hipGetLastError());
-    ctx->pass_report[0] |= STORM_HIP_RAN_SIMILARITY;   // ([1]: n_a n_b n_words, the launch's own)
-    return STORM_HIP_OK;
+    // (the report's [1]: n_a n_b n_words, the launch's own)
+    return launch_finish_tiles<DosageStat>(ctx, "square_dosage_corr", d_io, ld, na, nb, {{s.a_sum, s.a_sq}}, {{s.b_sum, s.b_sq}}, false,
+                                           measure, n_samples);
 }
 
 // The splits of both matrices side by side in ctx->d_dosage_rows (A's three matrices, then B's; one split when b is a),
@@ -656,18 +497,10 @@ static int square_dosage_corr_complete_queued(storm_hip_ctx_t* ctx, const storm_
 }
 
 // ---- the lag layout ----
-// what the lag calls of the dosage form refuse alike (check_lag of storm_hip_similarity.hip and check_dosage); *lag = L
+// what the lag calls of the dosage form refuse alike (check_lag, and check_dosage's width test); *lag = L
 static int check_lag_dosage(const char* who, const storm_hip_matrix_s* m, const void* out, uint64_t max_lag, uint64_t ld,
                             uint64_t* lag) {
-    if (!m || !out || max_lag == 0) {
-        set_error("%s: NULL argument or max_lag 0", who);
-        return STORM_HIP_EINVAL;
-    }
-    *lag = m->n_rows ? std::min(max_lag, m->n_rows - 1) : 0;
-    if (ld < *lag) {
-        set_error("%s: leading dimension %llu < min(max_lag, rows - 1) = %llu", who, (unsigned long long)ld, (unsigned long long)*lag);
-        return STORM_HIP_EINVAL;
-    }
+    if (int rc = check_lag(who, m, out, max_lag, ld, lag)) return rc;
     if ((uint64_t)m->n_words * 32u > kDosageMaxSamples) {
         set_error("%s: rows of %u words hold more than 2^24 values", who, m->n_words);
         return STORM_HIP_EINVAL;
@@ -675,44 +508,12 @@ static int check_lag_dosage(const char* who, const storm_hip_matrix_s* m, const 
     return STORM_HIP_OK;
 }
 
-// dosage_finish_lag_kernel over a matrix of dot products in the lag layout, asynchronous (the checks of
-// storm_hip_dosage_finish_lag_device)
+// r / r^2 over a matrix of dot products in the lag layout, asynchronous (the checks of storm_hip_dosage_finish_lag_device)
 static int launch_dosage_finish_lag(storm_hip_ctx_t* ctx, void* d_io, uint64_t ld, uint64_t n_rows, uint64_t row0,
                                     uint64_t n_band_rows, uint64_t max_lag, const uint32_t* d_sum, const uint32_t* d_sum_sq,
                                     int measure, uint64_t n_samples) {
-    if (!d_io || !d_sum || !d_sum_sq) {
-        set_error("dosage_finish_lag: NULL argument");
-        return STORM_HIP_EINVAL;
-    }
-    if (measure != STORM_HIP_DOSAGE_R2 && measure != STORM_HIP_DOSAGE_R) {
-        set_error("dosage_finish_lag: unknown measure %d (0 r^2, 1 r)", measure);
-        return STORM_HIP_EINVAL;
-    }
-    if (n_samples == 0 || n_samples > kDosageMaxSamples) {
-        set_error("dosage_finish_lag: n_samples %llu is not in [1, 2^24]", (unsigned long long)n_samples);
-        return STORM_HIP_EINVAL;
-    }
-    if (n_band_rows == ~0ull && row0 <= n_rows) n_band_rows = n_rows - row0;
-    const uint64_t lag = n_rows ? std::min(max_lag, n_rows - 1) : 0;
-    if (max_lag == 0 || row0 > n_rows || n_band_rows > n_rows - row0 || ld < lag) {
-        set_error("dosage_finish_lag: max_lag 0, a band outside the rows, or leading dimension < min(max_lag, rows - 1)");
-        return STORM_HIP_EINVAL;
-    }
-    if (n_rows < 2 || n_band_rows == 0) return STORM_HIP_OK;
-    const uint64_t tiles_x = (lag + kDosTileCols - 1) / kDosTileCols, tiles_y = (n_band_rows + kDosTileRows - 1) / kDosTileRows;
-    if (tiles_y > 65535u || tiles_x > 0x7fffffffu) {
-        set_error("dosage_finish_lag: %llu x %llu entries exceed the launch grid", (unsigned long long)n_band_rows,
-                  (unsigned long long)lag);
-        return STORM_HIP_EINVAL;
-    }
-    STORM_HIP_TRY(hipSetDevice(ctx->device));
-    const int vec = reinterpret_cast<uintptr_t>(d_io) % 16 == 0 && ld % 4 == 0;
-    hipLaunchKernelGGL(dosage_finish_lag_kernel, dim3((uint32_t)tiles_x, (uint32_t)tiles_y), dim3(256), 0, ctx->stream,
-                       static_cast<uint32_t*>(d_io), ld, n_rows, row0, row0 + n_band_rows, lag, d_sum, d_sum_sq, measure, n_samples,
-                       vec);
-    STORM_HIP_TRY(hipGetLastError());
-    ctx->pass_report[0] |= STORM_HIP_RAN_SIMILARITY;
-    return STORM_HIP_OK;
+    return launch_finish_lag_tiles<DosageStat>(ctx, "dosage_finish_lag", d_io, ld, n_rows, row0, n_band_rows, max_lag,
+                                               {{d_sum, d_sum_sq}}, measure, n_samples);
 }
 
 // dot products in the lag layout at d_io (pitch ld), the rows' sums, then the finish: all queued

@@ -351,12 +351,36 @@ int launch_square_mfma(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
 int launch_square_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* a,
                          const storm_hip_matrix_s* b, int op, uint32_t* d_out, uint64_t ld);
 int launch_row_counts(storm_hip_ctx_t* ctx, const storm_hip_matrix_s* m, uint32_t* d_counts);
-// similarity_finish_kernel over a count matrix in device memory, asynchronous (storm_hip_similarity.hip; the checks of
+// ---- the finishing pass (finish_tiles_kernel.inc; Stat: the statistic, brought by the file that includes it) ----
+// a statistic's words per row, planar: one device array per word
+template <int W>
+struct StatWords {
+    const uint32_t* w[W];
+    bool all() const {   // none is NULL
+        for (const uint32_t* p : w)
+            if (!p) return false;
+        return true;
+    }
+};
+// can one launch hold the tiles of rows x cols entries? (64 x 256 entries a tile; grid (column tiles, row tiles))
+static inline bool finish_tiles_fit(uint64_t rows, uint64_t cols) { return (rows + 63) / 64 <= 65535u && (cols + 255) / 256 <= 0x7fffffffu; }
+// finish_tiles_kernel<Stat, triangle> over n_rows x n_cols entries at d_io, finish_lag_tiles_kernel<Stat> over the rows
+// [row0, row0 + n_band_rows) of the lag layout (from output row 0; ~0: to the last row): the checks of the *_finish_device
+// calls under the name `who`, then queued on the context's stream
+template <typename Stat>
+int launch_finish_tiles(storm_hip_ctx_t* ctx, const char* who, void* d_io, uint64_t ld, uint64_t n_rows, uint64_t n_cols,
+                        StatWords<Stat::W> rows, StatWords<Stat::W> cols, bool triangle, int measure, uint64_t scale);
+template <typename Stat>
+int launch_finish_lag_tiles(storm_hip_ctx_t* ctx, const char* who, void* d_io, uint64_t ld, uint64_t n_rows, uint64_t row0,
+                            uint64_t n_band_rows, uint64_t max_lag, StatWords<Stat::W> stats, int measure, uint64_t scale);
+// what the lag calls refuse alike; *lag = L = min(max_lag, rows - 1) (0 for an empty matrix) (storm_hip_similarity.hip)
+int check_lag(const char* who, const storm_hip_matrix_s* m, const void* out, uint64_t max_lag, uint64_t ld, uint64_t* lag);
+// the bit statistics over a count matrix in device memory, asynchronous (storm_hip_similarity.hip; the checks of
 // storm_hip_similarity_finish_device)
 int launch_similarity_finish(storm_hip_ctx_t* ctx, void* d_io, uint64_t ld, uint64_t n_rows, uint64_t n_cols,
                              const uint32_t* d_counts_rows, const uint32_t* d_counts_cols, int triangle, int measure,
                              uint64_t n_bits);
-// similarity_finish_lag_kernel: the same pass over the lag layout (rows [row0, row0 + n_band_rows) from output row 0)
+// the same pass over the lag layout (rows [row0, row0 + n_band_rows) from output row 0)
 int launch_similarity_finish_lag(storm_hip_ctx_t* ctx, void* d_io, uint64_t ld, uint64_t n_rows, uint64_t row0,
                                  uint64_t n_band_rows, uint64_t max_lag, const uint32_t* d_counts, int measure, uint64_t n_bits);
 // lag_band_sums_kernel over a float matrix in the lag layout: per-row sums over both sides of the band, queued

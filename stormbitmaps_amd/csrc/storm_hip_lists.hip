@@ -1064,7 +1064,7 @@ int storm_hip_rowlists_square_matrix(storm_hip_ctx_t* ctx, storm_hip_rowlists_t*
 }
 
 // ---- the similarity forms (storm_hip.h: storm_hip_similarity_finish_device): K5 / K5x with op AND, then
-// similarity_finish_kernel on the same stream with the lists' own row lengths as the rows' counts. lb == nullptr: the
+// finish_tiles_kernel<SimilarityStat> on the same stream with the lists' own row lengths as the rows' counts. lb == nullptr: the
 // triangle of la. host: through the context's band buffer (cleared for a triangle: +0.0f at i >= j), one 2-D copy out
 // (pair_matrix_out).
 static int lists_similarity(storm_hip_ctx_t* ctx, storm_hip_rowlists_t* la, const storm_hip_rowlists_t* lb, int measure,

@@ -6,194 +6,49 @@
 // A separate launch on the context's stream, not an epilogue of the count kernels: those finish an entry in different
 // places (k-parts that add into a cleared window, counts that are complete only at the end of a launch), and a
 // non-linear formula is right only on complete counts. 4 bytes read and 4 written per converted entry: the pass is
-// bound by HBM bandwidth.
+// bound by HBM bandwidth. The kernels and their launchers are finish_tiles_kernel.inc, shared with the dosage
+// statistics (storm_hip_dosage.hip): finish_tiles_kernel<SimilarityStat, triangle> over a rectangle or an upper triangle,
+// finish_lag_tiles_kernel<SimilarityStat> over the lag layout.
 #include "storm_hip_internal.h"
 #include "storm_similarity_math.h"
 
 namespace storm {
 
-constexpr int kSimThreads = 256;    // 4 waves
-constexpr int kSimTileRows = 64;    // a wave walks every 4th row of the tile ...
-constexpr int kSimTileCols = 256;   // ... one 128-bit vector (4 entries) per lane
-constexpr int kSimUnroll = 4;       // rows a wave has in flight
-
-// Grid (column tiles, row tiles) of kSimTileRows x kSimTileCols entries. triangle: only entries i < j are touched — a
-// tile at or below the diagonal exits at once; entries i >= j and the pitch columns [n_cols, ld) are neither read nor
-// written. vec: the base is 16-byte aligned and ld a multiple of 4, so a lane's 4 entries are one 128-bit access
-// wherever all 4 are converted; the diagonal's vector, the last columns and everything of a misaligned matrix go entry
-// by entry.
-__global__ __launch_bounds__(kSimThreads) void similarity_finish_kernel(uint32_t* __restrict__ io, uint64_t ld, uint64_t n_rows,
-                                                                        uint64_t n_cols,
-                                                                        const uint32_t* __restrict__ counts_rows,
-                                                                        const uint32_t* __restrict__ counts_cols, int triangle,
-                                                                        int measure, uint64_t n_bits, int vec) {
-    const uint64_t row0 = (uint64_t)blockIdx.y * kSimTileRows, col0 = (uint64_t)blockIdx.x * kSimTileCols;
-    if (triangle && col0 + kSimTileCols <= row0 + 1) return;   // the tile's last column is not beyond its first row
-    // the tile's counts, once per workgroup: the rows' through the LDS, a lane's 4 columns in registers
-    __shared__ uint32_t s_rows[kSimTileRows];
-    if (threadIdx.x < kSimTileRows) s_rows[threadIdx.x] = row0 + threadIdx.x < n_rows ? counts_rows[row0 + threadIdx.x] : 0u;
-    const uint64_t c0 = col0 + (threadIdx.x & 63u) * 4u;
-    uint32_t b[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) b[k] = c0 + k < n_cols ? counts_cols[c0 + k] : 0u;
-    __syncthreads();
-    const uint32_t wave = threadIdx.x >> 6;
-    for (uint32_t r = wave; r < kSimTileRows; r += 4 * kSimUnroll) {
-        uint4 v[kSimUnroll];
-        bool whole[kSimUnroll];
-#pragma unroll
-        for (int u = 0; u < kSimUnroll; ++u) {   // the loads of kSimUnroll rows leave before the first divide
-            const uint64_t i = row0 + r + 4u * u;
-            whole[u] = vec && i < n_rows && c0 + 4 <= n_cols && (!triangle || c0 > i);
-            if (whole[u]) v[u] = *reinterpret_cast<const uint4*>(io + i * ld + c0);
-        }
-#pragma unroll
-        for (int u = 0; u < kSimUnroll; ++u) {
-            const uint64_t i = row0 + r + 4u * u;
-            if (i >= n_rows) continue;
-            const uint32_t a = s_rows[r + 4u * u];
-            uint32_t* const p = io + i * ld + c0;
-            if (whole[u]) {
-                uint4 w;
-                w.x = similarity_bits(v[u].x, a, b[0], measure, n_bits);
-                w.y = similarity_bits(v[u].y, a, b[1], measure, n_bits);
-                w.z = similarity_bits(v[u].z, a, b[2], measure, n_bits);
-                w.w = similarity_bits(v[u].w, a, b[3], measure, n_bits);
-                *reinterpret_cast<uint4*>(p) = w;
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (c0 + k < n_cols && (!triangle || c0 + k > i)) p[k] = similarity_bits(p[k], a, b[k], measure, n_bits);
-            }
-        }
+// the bit statistics as finish_tiles_kernel.inc takes them: one word per row, its count
+struct SimilarityStat {
+    static constexpr int W = 1;
+    static __device__ __forceinline__ uint32_t bits(uint32_t c, const uint32_t (&a)[1], const uint32_t (&b)[1], int measure,
+                                                    uint64_t n_bits) {
+        return similarity_bits(c, a[0], b[0], measure, n_bits);
     }
-}
+    static int check(const char* who, int measure, uint64_t n_bits) {
+        if (measure < STORM_HIP_SIM_JACCARD || measure > STORM_HIP_SIM_LD_R2) {
+            set_error("%s: unknown measure %d (0 Jaccard, 1 cosine, 2 LD D, 3 LD r^2)", who, measure);
+            return STORM_HIP_EINVAL;
+        }
+        if (n_bits == 0 || n_bits > (1ull << 32)) {
+            set_error("%s: n_bits %llu is not in [1, 2^32]", who, (unsigned long long)n_bits);
+            return STORM_HIP_EINVAL;
+        }
+        return STORM_HIP_OK;
+    }
+};
+
+#include "finish_tiles_kernel.inc"
 
 int launch_similarity_finish(storm_hip_ctx_t* ctx, void* d_io, uint64_t ld, uint64_t n_rows, uint64_t n_cols,
                              const uint32_t* d_counts_rows, const uint32_t* d_counts_cols, int triangle, int measure,
                              uint64_t n_bits) {
     if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-    if (!d_io || !d_counts_rows || !d_counts_cols) {
-        set_error("similarity_finish: NULL argument");
-        return STORM_HIP_EINVAL;
-    }
-    if (measure < STORM_HIP_SIM_JACCARD || measure > STORM_HIP_SIM_LD_R2) {
-        set_error("similarity_finish: unknown measure %d (0 Jaccard, 1 cosine, 2 LD D, 3 LD r^2)", measure);
-        return STORM_HIP_EINVAL;
-    }
-    if (n_bits == 0 || n_bits > (1ull << 32)) {
-        set_error("similarity_finish: n_bits %llu is not in [1, 2^32]", (unsigned long long)n_bits);
-        return STORM_HIP_EINVAL;
-    }
-    if (ld < n_cols || (triangle && n_rows != n_cols)) {
-        set_error("similarity_finish: leading dimension < columns, or a triangle that is not square");
-        return STORM_HIP_EINVAL;
-    }
-    if (n_rows == 0 || n_cols == 0) return STORM_HIP_OK;
-    const uint64_t tiles_x = (n_cols + kSimTileCols - 1) / kSimTileCols, tiles_y = (n_rows + kSimTileRows - 1) / kSimTileRows;
-    if (tiles_y > 65535u || tiles_x > 0x7fffffffu) {
-        set_error("similarity_finish: %llu x %llu entries exceed the launch grid", (unsigned long long)n_rows,
-                  (unsigned long long)n_cols);
-        return STORM_HIP_EINVAL;
-    }
-    STORM_HIP_TRY(hipSetDevice(ctx->device));
-    const int vec = reinterpret_cast<uintptr_t>(d_io) % 16 == 0 && ld % 4 == 0;
-    hipLaunchKernelGGL(similarity_finish_kernel, dim3((uint32_t)tiles_x, (uint32_t)tiles_y), dim3(kSimThreads), 0, ctx->stream,
-                       static_cast<uint32_t*>(d_io), ld, n_rows, n_cols, d_counts_rows, d_counts_cols, triangle ? 1 : 0, measure,
-                       n_bits, vec);
-    STORM_HIP_TRY(hipGetLastError());
-    ctx->pass_report[0] |= STORM_HIP_RAN_SIMILARITY;
-    return STORM_HIP_OK;
-}
-
-// The same pass over the LAG layout (storm_hip_pairw_lag_matrix_device): entry (r, d) of the band is the pair (i, i + 1 + d),
-// i = row0 + r, so a tile of kSimTileRows x kSimTileCols entries reads the counts of its 64 rows and of the 64 + 256 - 1 rows
-// i0 + 1 + col0 .. behind them: both staged once per workgroup. Only entries with d < lag and i + 1 + d < n_rows are
-// touched (the lower-right corner and the pitch columns are neither read nor written); a lane's 4 entries are one
-// 128-bit access where all 4 are converted and `vec` (base 16-byte aligned, ld a multiple of 4), else entry by entry.
-__global__ __launch_bounds__(kSimThreads) void similarity_finish_lag_kernel(uint32_t* __restrict__ io, uint64_t ld, uint64_t n_rows,
-                                                                            uint64_t row0, uint64_t band_end, uint64_t lag,
-                                                                            const uint32_t* __restrict__ counts, int measure,
-                                                                            uint64_t n_bits, int vec) {
-    const uint64_t i0 = row0 + (uint64_t)blockIdx.y * kSimTileRows, col0 = (uint64_t)blockIdx.x * kSimTileCols;
-    if (i0 + 1 + col0 >= n_rows) return;   // the tile's first pair is already in the corner
-    __shared__ uint32_t s_rows[kSimTileRows];
-    __shared__ uint32_t s_cols[kSimTileRows + kSimTileCols];
-    if (threadIdx.x < kSimTileRows) s_rows[threadIdx.x] = i0 + threadIdx.x < band_end ? counts[i0 + threadIdx.x] : 0u;
-    for (uint32_t k = threadIdx.x; k < kSimTileRows + kSimTileCols; k += kSimThreads)
-        s_cols[k] = i0 + 1 + col0 + k < n_rows ? counts[i0 + 1 + col0 + k] : 0u;
-    __syncthreads();
-    const uint32_t lane4 = (threadIdx.x & 63u) * 4u;
-    const uint64_t c0 = col0 + lane4;
-    const uint32_t wave = threadIdx.x >> 6;
-    for (uint32_t r = wave; r < kSimTileRows; r += 4 * kSimUnroll) {
-        uint4 v[kSimUnroll];
-        bool whole[kSimUnroll];
-#pragma unroll
-        for (int u = 0; u < kSimUnroll; ++u) {   // the loads of kSimUnroll rows leave before the first divide
-            const uint64_t i = i0 + r + 4u * u;
-            whole[u] = vec && i < band_end && c0 + 4 <= lag && i + 1 + c0 + 3 < n_rows;
-            if (whole[u]) v[u] = *reinterpret_cast<const uint4*>(io + (i - row0) * ld + c0);
-        }
-#pragma unroll
-        for (int u = 0; u < kSimUnroll; ++u) {
-            const uint32_t rr = r + 4u * u;
-            const uint64_t i = i0 + rr;
-            if (i >= band_end) continue;
-            const uint32_t a = s_rows[rr];
-            const uint32_t* const b = &s_cols[rr + lane4];   // entry d = c0 + k: row i + 1 + c0 + k
-            uint32_t* const p = io + (i - row0) * ld + c0;
-            if (whole[u]) {
-                uint4 w;
-                w.x = similarity_bits(v[u].x, a, b[0], measure, n_bits);
-                w.y = similarity_bits(v[u].y, a, b[1], measure, n_bits);
-                w.z = similarity_bits(v[u].z, a, b[2], measure, n_bits);
-                w.w = similarity_bits(v[u].w, a, b[3], measure, n_bits);
-                *reinterpret_cast<uint4*>(p) = w;
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (c0 + k < lag && i + 1 + c0 + k < n_rows) p[k] = similarity_bits(p[k], a, b[k], measure, n_bits);
-            }
-        }
-    }
+    return launch_finish_tiles<SimilarityStat>(ctx, "similarity_finish", d_io, ld, n_rows, n_cols, {{d_counts_rows}}, {{d_counts_cols}},
+                                               triangle != 0, measure, n_bits);
 }
 
 int launch_similarity_finish_lag(storm_hip_ctx_t* ctx, void* d_io, uint64_t ld, uint64_t n_rows, uint64_t row0,
                                  uint64_t n_band_rows, uint64_t max_lag, const uint32_t* d_counts, int measure, uint64_t n_bits) {
     if (check_ctx(ctx)) return STORM_HIP_EINVAL;
-    if (!d_io || !d_counts) {
-        set_error("similarity_finish_lag: NULL argument");
-        return STORM_HIP_EINVAL;
-    }
-    if (measure < STORM_HIP_SIM_JACCARD || measure > STORM_HIP_SIM_LD_R2) {
-        set_error("similarity_finish_lag: unknown measure %d (0 Jaccard, 1 cosine, 2 LD D, 3 LD r^2)", measure);
-        return STORM_HIP_EINVAL;
-    }
-    if (n_bits == 0 || n_bits > (1ull << 32)) {
-        set_error("similarity_finish_lag: n_bits %llu is not in [1, 2^32]", (unsigned long long)n_bits);
-        return STORM_HIP_EINVAL;
-    }
-    if (n_band_rows == ~0ull && row0 <= n_rows) n_band_rows = n_rows - row0;
-    const uint64_t lag = n_rows ? std::min(max_lag, n_rows - 1) : 0;
-    if (max_lag == 0 || row0 > n_rows || n_band_rows > n_rows - row0 || ld < lag) {
-        set_error("similarity_finish_lag: max_lag 0, a band outside the rows, or leading dimension < min(max_lag, rows - 1)");
-        return STORM_HIP_EINVAL;
-    }
-    if (n_rows < 2 || n_band_rows == 0) return STORM_HIP_OK;
-    const uint64_t tiles_x = (lag + kSimTileCols - 1) / kSimTileCols, tiles_y = (n_band_rows + kSimTileRows - 1) / kSimTileRows;
-    if (tiles_y > 65535u || tiles_x > 0x7fffffffu) {
-        set_error("similarity_finish_lag: %llu x %llu entries exceed the launch grid", (unsigned long long)n_band_rows,
-                  (unsigned long long)lag);
-        return STORM_HIP_EINVAL;
-    }
-    STORM_HIP_TRY(hipSetDevice(ctx->device));
-    const int vec = reinterpret_cast<uintptr_t>(d_io) % 16 == 0 && ld % 4 == 0;
-    hipLaunchKernelGGL(similarity_finish_lag_kernel, dim3((uint32_t)tiles_x, (uint32_t)tiles_y), dim3(kSimThreads), 0, ctx->stream,
-                       static_cast<uint32_t*>(d_io), ld, n_rows, row0, row0 + n_band_rows, lag, d_counts, measure, n_bits, vec);
-    STORM_HIP_TRY(hipGetLastError());
-    ctx->pass_report[0] |= STORM_HIP_RAN_SIMILARITY;
-    return STORM_HIP_OK;
+    return launch_finish_lag_tiles<SimilarityStat>(ctx, "similarity_finish_lag", d_io, ld, n_rows, row0, n_band_rows, max_lag,
+                                                   {{d_counts}}, measure, n_bits);
 }
 
 // the row counts of `m` into the context's scratch at word `at` (ensured by the caller)
@@ -275,8 +130,8 @@ static int cross_dense_similarity(storm_hip_ctx_t* ctx, const storm_hip_matrix_s
 
 // ---- the lag layout (storm_hip.h): row i against the next L = min(max_lag, rows - 1) rows, an n x L matrix, cleared in the
 // band buffer (the lower-right corner); both forms return below two rows ----
-// what the lag calls refuse alike; *lag = L (0 for an empty matrix)
-static int check_lag(const char* who, const storm_hip_matrix_s* m, const void* out, uint64_t max_lag, uint64_t ld, uint64_t* lag) {
+// what the lag calls refuse alike; *lag = L (0 for an empty matrix) (shared: storm_hip_internal.h)
+int check_lag(const char* who, const storm_hip_matrix_s* m, const void* out, uint64_t max_lag, uint64_t ld, uint64_t* lag) {
     if (!m || !out || max_lag == 0) {
         set_error("%s: NULL argument or max_lag 0", who);
         return STORM_HIP_EINVAL;

@@ -163,7 +163,7 @@ int STORM_square_matrix_device(STORM_t* a, STORM_t* b, int op, uint32_t* d_out, 
 
 
 /* ---- Extension (storm.h): the per-pair matrices finished into a similarity statistic on the device — the AND-count path of
- * the matrix calls as it is (same kernels, same choice), the rows' counts, then similarity_finish_kernel
+ * the matrix calls as it is (same kernels, same choice), the rows' counts, then finish_tiles_kernel<SimilarityStat>
  * (storm_hip_similarity.hip) behind the count kernel. One device slot and one process, host forms too. */
 /* The measure and the universe size as the shim takes them: 0, or -3 with the reason. Jaccard and cosine do not read n_bits;
  * the LD measures take `n_bits_default` (a STORM_contiguous_t's vector_length; 0 for a STORM_t, which declares none) for 0. */

@@ -1,4 +1,4 @@
-"""The arithmetic of dosage_finish_kernel without a device: storm_dosage_math.h holds the lines the kernel runs per entry
+"""The arithmetic of finish_tiles_kernel<DosageStat, true> without a device: storm_dosage_math.h holds the lines the kernel runs per entry
 (the Pearson correlation r and r^2 of two rows of 2-bit dosages from their dot product, sums and sums of squares), and a
 host compiler builds the same lines here (IEEE double division and square root on both sides, no fast-math, no
 contraction). Every value is compared with the exactly rounded rational (Python integers, fractions.Fraction, the

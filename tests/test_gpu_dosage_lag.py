@@ -1,6 +1,6 @@
 """The dosage container's pairwise calls in the lag layout on the device (storm.h: STORM_dosage_pairw_lag_dot, _lag_corr,
 _lag_nobs, _lag_corr_complete; storm_hip.h: storm_hip_pairw_lag_dosage_*): K2h in its lag and dosage form
-(tile128_kernel<true, 2>), dosage_finish_lag_kernel, and for rows with missing genotypes the interleaved split (G, H, M as
+(tile128_kernel<true, 2>), finish_lag_tiles_kernel<DosageStat>, and for rows with missing genotypes the interleaved split (G, H, M as
 one matrix of 3 n rows), one launch at lag 3 L + 2 and dosage_complete_finish_lag_kernel. Everything goes through the
 C-ABI, in the host and the _device forms.
 

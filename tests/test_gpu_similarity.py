@@ -1,4 +1,4 @@
-"""Per-pair similarity matrices on the device: similarity_finish_kernel alone on count matrices of the test's own, and
+"""Per-pair similarity matrices on the device: finish_tiles_kernel<SimilarityStat> alone on count matrices of the test's own, and
 behind every matrix-output path (STORM_contig_pairw_similarity, STORM_pairw_similarity, STORM_square_similarity and their
 _device forms).
 

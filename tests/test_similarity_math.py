@@ -1,4 +1,4 @@
-"""The arithmetic of similarity_finish_kernel without a device: storm_similarity_math.h holds the lines the kernel runs
+"""The arithmetic of finish_tiles_kernel<SimilarityStat> without a device: storm_similarity_math.h holds the lines the kernel runs
 per entry, and a host compiler builds the same lines here (IEEE double division and square root on both sides, no
 fast-math, no contraction). Every value is compared with the exactly rounded rational of tests/test_gpu_similarity.py's
 generator (`_exact`: Python integers and fractions.Fraction): the one NaN pattern exactly where a measure is undefined,

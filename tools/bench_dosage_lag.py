@@ -3,7 +3,7 @@
 completion included), S = 65536 samples of random codes 0 .. 3 (a quarter of them 3: missing, for the calls that read it
 so), per row count and max_lag:
   lag_dot_us        storm_hip_pairw_lag_dosage_matrix_device (tile128_kernel<true, 2>)
-  lag_corr_us       storm_hip_pairw_lag_dosage_corr_device: dot products + row sums + dosage_finish_lag_kernel
+  lag_corr_us       storm_hip_pairw_lag_dosage_corr_device: dot products + row sums + finish_lag_tiles_kernel<DosageStat>
   lag_complete_us   storm_hip_pairw_lag_dosage_corr_complete_device: interleaved split, ONE launch over 3 n rows at lag
                     3 L + 2, dosage_complete_finish_lag_kernel
   complete_over_corr  lag_complete_us / lag_corr_us: the cost of the interleaved layout (the MFMA count predicts about 9)

@@ -2,7 +2,7 @@
 """The lag layout against the full triangle: us per synchronous call into device memory (launch + completion included),
 M = 65536 dense, per row count and max_lag:
   lag_us        storm_hip_pairw_lag_matrix_device, op AND (tile128_kernel, lag form)
-  lag_sim_us    storm_hip_pairw_lag_similarity_device (LD r^2): counts + row counts + similarity_finish_lag_kernel
+  lag_sim_us    storm_hip_pairw_lag_similarity_device (LD r^2): counts + row counts + finish_lag_tiles_kernel<SimilarityStat>
   finish_us     lag_sim_us - lag_us: the finish pass (and the row counts) alone
   triangle_us   storm_hip_pairw_matrix_device for the whole triangle of the same matrix, same process, alternating with the
                 lag calls (the automatic kernel choice; `triangle_kernel` says which ran)

@@ -1,4 +1,4 @@
-"""What finishing the per-pair matrix on the device costs (similarity_finish_kernel behind the count kernels). Per
+"""What finishing the per-pair matrix on the device costs (finish_tiles_kernel<SimilarityStat> behind the count kernels). Per
 shape, alternating in one process after a warm-up, every call synchronous (the wait is inside the timed window):
   (a) the existing *_pairw_matrix_device with op AND (the counts alone);
   (b) *_pairw_similarity_device for each measure (counts + row counts + finish);

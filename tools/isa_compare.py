@@ -18,6 +18,7 @@ import subprocess
 import sys
 
 LOCAL_LABEL = re.compile(r"\.L(BB|func_end|func_begin|tmp|JTI)\d+(_\d+)?")
+LOOP_HEADER = re.compile(r"(Header=|Loop )BB\d+_")   # (a loop comment names a label with the function's number in the file)
 
 
 def clean(lines):
@@ -26,7 +27,8 @@ def clean(lines):
         s = ln.strip()
         if s.startswith((".file", ".ident", "; %bb.")) or "/" in s and (".hip" in s or ".inc" in s or ".h" in s):
             continue
-        out.append(LOCAL_LABEL.sub(lambda m: ".L" + m.group(1) + (m.group(2) and "_" + m.group(2).split("_")[1] or ""), ln.rstrip()))
+        ln = LOOP_HEADER.sub(lambda m: m.group(1) + "BB_", ln.rstrip())
+        out.append(LOCAL_LABEL.sub(lambda m: ".L" + m.group(1) + (m.group(2) and "_" + m.group(2).split("_")[1] or ""), ln))
     return out
 
 
