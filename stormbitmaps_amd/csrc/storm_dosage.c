@@ -3,10 +3,10 @@
  *
  * The host keeps the packed rows; they go up into an ordinary storm_hip_matrix_t on the first compute call after a change
  * (whole, from the row the device copy ends at: rows never change once added). On storm_host.c's locked paths without
- * adding to them, like storm_lag.c and storm_topk.c: one device slot and one process. No CPU fallback. The rectangle of
- * two containers and the calls that read 3 as "missing" are storm_dosage_complete.c's. */
+ * adding to them, like storm_lag.c and storm_topk.c: one device slot and one process. No CPU fallback. Here too: what the
+ * storm_dosage_*.c units beside it resolve and check alike (storm_dosage_internal.h). The per-pair matrices of one or two
+ * containers are storm_dosage_pairs.c's. */
 #include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -58,15 +58,10 @@ static int dosage_reserve(STORM_dosage_t* h, uint64_t more) {
     if (h->n_rows + more <= h->m_rows) return 0;
     uint64_t want = h->m_rows ? h->m_rows : 64;
     while (want < h->n_rows + more) want *= 2;
-    if (want > SIZE_MAX / sizeof(uint64_t) / h->n_words) {
-        storm_host_error("STORM_dosage_add: the container would exceed the address space");
-        return -3;
-    }
+    if (want > SIZE_MAX / sizeof(uint64_t) / h->n_words)
+        return storm_host_refuse("STORM_dosage_add", "the container would exceed the address space");
     uint64_t* p = (uint64_t*)realloc(h->rows, (size_t)want * h->n_words * sizeof(uint64_t));
-    if (!p) {
-        storm_host_error("STORM_dosage_add: out of host memory");
-        return -3;
-    }
+    if (!p) return storm_host_refuse("STORM_dosage_add", "out of host memory");
     h->rows = p;
     h->m_rows = want;
     return 0;
@@ -75,21 +70,13 @@ static int dosage_reserve(STORM_dosage_t* h, uint64_t more) {
 int STORM_dosage_add(STORM_dosage_t* h, const uint8_t* values, uint64_t n_values) {
     if (!h) return -1;
     if (!values) return -2;
-    if (n_values != h->n_samples) {
-        char msg[160];
-        snprintf(msg, sizeof(msg), "STORM_dosage_add: %llu values for rows of %llu samples", (unsigned long long)n_values,
-                 (unsigned long long)h->n_samples);
-        storm_host_error(msg);
-        return -3;
-    }
+    if (n_values != h->n_samples)
+        return storm_host_refuse("STORM_dosage_add", "%llu values for rows of %llu samples", (unsigned long long)n_values,
+                                 (unsigned long long)h->n_samples);
     for (uint64_t s = 0; s < n_values; ++s)
-        if (values[s] > 3) {
-            char msg[160];
-            snprintf(msg, sizeof(msg), "STORM_dosage_add: value %u at sample %llu (a dosage is 0 .. 3)", (unsigned)values[s],
-                     (unsigned long long)s);
-            storm_host_error(msg);
-            return -3;
-        }
+        if (values[s] > 3)
+            return storm_host_refuse("STORM_dosage_add", "value %u at sample %llu (a dosage is 0 .. 3)", (unsigned)values[s],
+                                     (unsigned long long)s);
     if (dosage_reserve(h, 1)) return -3;
     uint64_t* row = h->rows + h->n_rows * h->n_words;
     for (uint32_t w = 0; w < h->n_words; ++w) {
@@ -109,17 +96,10 @@ int STORM_dosage_add_packed(STORM_dosage_t* h, const uint64_t* words, uint64_t n
     const uint32_t tail = (uint32_t)(h->n_samples % 32u); /* values in the last word (0: all 32) */
     if (tail)
         for (uint64_t r = 0; r < n_rows; ++r)
-            if (words[r * h->n_words + h->n_words - 1u] >> (2u * tail)) {
-                char msg[160];
-                snprintf(msg, sizeof(msg), "STORM_dosage_add_packed: row %llu has bits beyond sample %llu", (unsigned long long)r,
-                         (unsigned long long)h->n_samples);
-                storm_host_error(msg);
-                return -3;
-            }
-    if (n_rows > UINT64_MAX - h->n_rows) {
-        storm_host_error("STORM_dosage_add_packed: too many rows");
-        return -3;
-    }
+            if (words[r * h->n_words + h->n_words - 1u] >> (2u * tail))
+                return storm_host_refuse("STORM_dosage_add_packed", "row %llu has bits beyond sample %llu", (unsigned long long)r,
+                                         (unsigned long long)h->n_samples);
+    if (n_rows > UINT64_MAX - h->n_rows) return storm_host_refuse("STORM_dosage_add_packed", "too many rows");
     if (dosage_reserve(h, n_rows)) return -3;
     memcpy(h->rows + h->n_rows * h->n_words, words, (size_t)n_rows * h->n_words * sizeof(uint64_t));
     h->n_rows += n_rows;
@@ -127,7 +107,7 @@ int STORM_dosage_add_packed(STORM_dosage_t* h, const uint64_t* words, uint64_t n
 }
 
 /* the device copy brought up to date on the calling thread's slot (the caller holds the lock): NULL with the reason reported */
-storm_hip_matrix_t* storm_dosage_mirror(STORM_dosage_t* h, storm_hip_ctx_t** ctx_out) {
+static storm_hip_matrix_t* storm_dosage_mirror(STORM_dosage_t* h, storm_hip_ctx_t** ctx_out) {
     const uint32_t generation = storm_host_view_generation();
     if (h->m && (h->generation != generation || h->slot != storm_host_slot() || h->synced > h->n_rows)) dosage_drop_device(h);
     storm_hip_ctx_t* ctx = storm_host_ctx();
@@ -156,69 +136,49 @@ storm_hip_matrix_t* storm_dosage_mirror(STORM_dosage_t* h, storm_hip_ctx_t** ctx
     return h->m;
 }
 
+int storm_dosage_operands(STORM_dosage_t* a, STORM_dosage_t* b, storm_hip_ctx_t** ctx, const storm_hip_matrix_t** ma,
+                          const storm_hip_matrix_t** mb) {
+    storm_hip_ctx_t* ctx_b = NULL;
+    if (!(*ma = storm_dosage_mirror(a, ctx))) return -3;
+    if (mb && !(*mb = b && b != a ? storm_dosage_mirror(b, &ctx_b) : *ma)) return -3;
+    return 0;
+}
+
+int storm_dosage_measure_refusal(const char* who, int measure) {
+    if (measure == STORM_DOSAGE_R2 || measure == STORM_DOSAGE_R) return 0;
+    return storm_host_refuse(who, "measure must be 0 (STORM_DOSAGE_R2) or 1 (STORM_DOSAGE_R)");
+}
+
+int storm_dosage_samples_refusal(const char* who, const STORM_dosage_t* a, const STORM_dosage_t* b) {
+    if (a->n_samples == b->n_samples) return 0;
+    return storm_host_refuse(who, "containers of %llu and of %llu samples", (unsigned long long)a->n_samples,
+                             (unsigned long long)b->n_samples);
+}
+
+/* a count per row: the sums and sums of squares, or (`missing`: into `sum`) the numbers of 3s */
+static int dosage_rows(STORM_dosage_t* h, uint32_t* sum, uint32_t* sum_sq, int missing, const char* who) {
+    int rc = storm_host_begin(who);
+    if (!rc && h->n_rows != 0) {
+        storm_hip_ctx_t* ctx = NULL;
+        const storm_hip_matrix_t* m = NULL;
+        rc = storm_dosage_operands(h, NULL, &ctx, &m, NULL);
+        if (!rc)
+            rc = storm_host_shim_result(ctx, missing ? storm_hip_dosage_row_missing(ctx, m, h->n_samples, sum)
+                                                     : storm_hip_dosage_row_sums(ctx, m, sum, sum_sq),
+                                        0, missing ? "storm_hip_dosage_row_missing" : "storm_hip_dosage_row_sums");
+    }
+    return storm_host_end(rc);
+}
+
 int STORM_dosage_row_sums(STORM_dosage_t* h, uint32_t* sum, uint32_t* sum_sq) {
     if (!h) return -1;
     if (!sum || !sum_sq) return -2;
-    storm_host_lock();
-    int rc = storm_host_one_slot_or_refuse("STORM_dosage_row_sums");
-    if (!rc && h->n_rows != 0) {
-        storm_hip_ctx_t* ctx = NULL;
-        const storm_hip_matrix_t* m = storm_dosage_mirror(h, &ctx);
-        if (!m) rc = -3;
-        else if (storm_hip_dosage_row_sums(ctx, m, sum, sum_sq) != STORM_HIP_OK) {
-            storm_host_device_error("storm_hip_dosage_row_sums");
-            rc = -3;
-        }
-    }
-    storm_host_unlock();
-    return rc;
+    return dosage_rows(h, sum, sum_sq, 0, "STORM_dosage_row_sums");
 }
 
-/* measure < 0: the dot products */
-static int dosage_pairw(STORM_dosage_t* h, int measure, void* out, uint64_t out_rows, uint64_t out_ld, int device, const char* who) {
+/* (the value 3 means "missing" there and only there, as in the _nobs and _complete calls) */
+int STORM_dosage_row_missing(STORM_dosage_t* h, uint32_t* missing) {
     if (!h) return -1;
-    if (!out) return -2;
-    storm_host_lock();
-    int rc = storm_host_one_slot_or_refuse(who);
-    const uint64_t n = h->n_rows;
-    if (!rc && (out_rows < n || out_ld < n)) rc = -4;
-    if (!rc && measure >= 0 && measure != STORM_DOSAGE_R2 && measure != STORM_DOSAGE_R) {
-        char msg[160];
-        snprintf(msg, sizeof(msg), "%s: measure must be 0 (STORM_DOSAGE_R2) or 1 (STORM_DOSAGE_R)", who);
-        storm_host_error(msg);
-        rc = -3;
-    }
-    if (!rc && n >= 2) {
-        storm_hip_ctx_t* ctx = NULL;
-        const storm_hip_matrix_t* m = storm_dosage_mirror(h, &ctx);
-        if (!m) rc = -3;
-        else {
-            int hrc;
-            if (measure < 0)
-                hrc = device ? storm_hip_pairw_dosage_matrix_device(ctx, m, (uint32_t*)out, out_ld)
-                             : storm_hip_pairw_dosage_matrix(ctx, m, (uint32_t*)out, out_ld);
-            else
-                hrc = device ? storm_hip_pairw_dosage_corr_device(ctx, m, measure, h->n_samples, (float*)out, out_ld)
-                             : storm_hip_pairw_dosage_corr(ctx, m, measure, h->n_samples, (float*)out, out_ld);
-            if (hrc != STORM_HIP_OK) {
-                storm_host_device_error(measure < 0 ? "storm_hip_pairw_dosage_matrix" : "storm_hip_pairw_dosage_corr");
-                rc = -3;
-            }
-        }
-    }
-    storm_host_unlock();
-    return rc;
-}
-
-int STORM_dosage_pairw_dot(STORM_dosage_t* h, uint32_t* out, uint64_t out_rows, uint64_t out_ld) {
-    return dosage_pairw(h, -1, out, out_rows, out_ld, 0, "STORM_dosage_pairw_dot");
-}
-int STORM_dosage_pairw_dot_device(STORM_dosage_t* h, uint32_t* d_out, uint64_t out_rows, uint64_t out_ld) {
-    return dosage_pairw(h, -1, d_out, out_rows, out_ld, 1, "STORM_dosage_pairw_dot_device");
-}
-int STORM_dosage_pairw_corr(STORM_dosage_t* h, int measure, float* out, uint64_t out_rows, uint64_t out_ld) {
-    return dosage_pairw(h, measure < 0 ? STORM_DOSAGE_R + 1 : measure, out, out_rows, out_ld, 0, "STORM_dosage_pairw_corr");
-}
-int STORM_dosage_pairw_corr_device(STORM_dosage_t* h, int measure, float* d_out, uint64_t out_rows, uint64_t out_ld) {
-    return dosage_pairw(h, measure < 0 ? STORM_DOSAGE_R + 1 : measure, d_out, out_rows, out_ld, 1, "STORM_dosage_pairw_corr_device");
+    if (!missing) return -2;
+    return dosage_rows(h, missing, NULL, 1, "STORM_dosage_row_missing");
 }

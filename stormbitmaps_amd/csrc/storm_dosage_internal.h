@@ -17,15 +17,23 @@ struct STORM_dosage_s {
     uint64_t synced;
 };
 
-/* the device copy brought up to date on the calling thread's slot (the caller holds the lock): NULL with the reason reported */
-storm_hip_matrix_t* storm_dosage_mirror(STORM_dosage_t* h, storm_hip_ctx_t** ctx_out);
+/* ---- storm_dosage.c: what the storm_dosage_*.c units resolve and check alike. Each returns 0, or -3 with the reason
+ * reported; the caller holds the lock. ---- */
+
+/* the device copies of one container or two brought up to date on the calling thread's slot: *ctx, *ma and, where mb is
+ * given, *mb (b NULL or the same container as a: *mb = *ma) */
+int storm_dosage_operands(STORM_dosage_t* a, STORM_dosage_t* b, storm_hip_ctx_t** ctx, const storm_hip_matrix_t** ma,
+                          const storm_hip_matrix_t** mb);
+/* measure is neither STORM_DOSAGE_R2 nor STORM_DOSAGE_R */
+int storm_dosage_measure_refusal(const char* who, int measure);
+/* two containers whose rows have different numbers of samples */
+int storm_dosage_samples_refusal(const char* who, const STORM_dosage_t* a, const STORM_dosage_t* b);
 
 /* ---- storm_dosage_band.c: shared by the calls on the band of r^2. Each returns 0, or -3 with the reason reported; the
  * caller holds the lock. ---- */
 
-/* a shim call's return code `rc` as storm.h's: a _device form (`device`) returns with its work queued, and a caller of
- * storm.h has no handle on that stream, so it is waited for here; a failure is reported under the shim call's `name` */
-int storm_dosage_shim_result(storm_hip_ctx_t* ctx, int rc, int device, const char* name);
+/* a band call's return code `rc` as storm.h's (storm_host_shim_result), a _device form waited for */
+int storm_dosage_band_result(storm_hip_ctx_t* ctx, int rc, int device, const char* name);
 
 /* stat is neither STORM_LDSCORE_R2 nor _R2_ADJ, or the complete-case adjusted statistic has fewer than 3 samples */
 int storm_dosage_ldscore_stat_refusal(const char* who, int stat, int complete, uint64_t n_samples);

@@ -3,7 +3,6 @@
  * rows, an n x L matrix in the lag layout (storm_hip.h: storm_hip_pairw_lag_dosage_matrix_device). The container, its
  * device copy and the locked paths are storm_dosage.c's; the order of the checks is storm_lag.c's. No CPU fallback. */
 #include <stdint.h>
-#include <stdio.h>
 
 #include "storm.h"
 #include "storm_hip.h"
@@ -35,38 +34,27 @@ static int lag_run(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int what, 
             rc = device ? storm_hip_pairw_lag_dosage_corr_complete_device(ctx, m, measure, n_samples, max_lag, (float*)out, out_ld)
                         : storm_hip_pairw_lag_dosage_corr_complete(ctx, m, measure, n_samples, max_lag, (float*)out, out_ld);
     }
-    /* (device 0 in every form: these calls read no host array after they return, so a _device form is not waited for) */
-    return storm_dosage_shim_result(ctx, rc, 0, names[what]);
+    /* (these calls read no host array after they return, so a _device form is not waited for) */
+    return storm_host_shim_result(ctx, rc, 0, names[what]);
 }
 
 static int dosage_lag(STORM_dosage_t* h, int what, int measure, uint64_t max_lag, void* out, uint64_t out_rows, uint64_t out_ld,
                       int device, const char* who) {
     if (!h) return -1;
     if (!out) return -2;
-    storm_host_lock();
-    int rc = storm_host_one_slot_or_refuse(who);
+    int rc = storm_host_begin(who);
     const uint64_t n = h->n_rows;
     const uint64_t lag = n ? (max_lag < n - 1 ? max_lag : n - 1) : 0;
     if (!rc && max_lag != 0 && (out_rows < n || out_ld < lag)) rc = -4;
-    if (!rc && max_lag == 0) {
-        char msg[160];
-        snprintf(msg, sizeof(msg), "%s: max_lag must be at least 1", who);
-        storm_host_error(msg);
-        rc = -3;
-    }
-    if (!rc && (what == LAG_CORR || what == LAG_CORR_COMPLETE) && measure != STORM_DOSAGE_R2 && measure != STORM_DOSAGE_R) {
-        char msg[160];
-        snprintf(msg, sizeof(msg), "%s: measure must be 0 (STORM_DOSAGE_R2) or 1 (STORM_DOSAGE_R)", who);
-        storm_host_error(msg);
-        rc = -3;
-    }
+    if (!rc && max_lag == 0) rc = storm_host_refuse(who, "max_lag must be at least 1");
+    if (!rc && (what == LAG_CORR || what == LAG_CORR_COMPLETE)) rc = storm_dosage_measure_refusal(who, measure);
     if (!rc && n >= 2) {
         storm_hip_ctx_t* ctx = NULL;
-        const storm_hip_matrix_t* m = storm_dosage_mirror(h, &ctx);
-        rc = m ? lag_run(ctx, m, what, measure, h->n_samples, max_lag, out, out_ld, device) : -3;
+        const storm_hip_matrix_t* m = NULL;
+        rc = storm_dosage_operands(h, NULL, &ctx, &m, NULL);
+        if (!rc) rc = lag_run(ctx, m, what, measure, h->n_samples, max_lag, out, out_ld, device);
     }
-    storm_host_unlock();
-    return rc;
+    return storm_host_end(rc);
 }
 
 int STORM_dosage_pairw_lag_dot(STORM_dosage_t* h, uint64_t max_lag, uint32_t* out, uint64_t out_rows, uint64_t out_ld) {

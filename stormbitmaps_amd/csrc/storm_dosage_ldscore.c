@@ -4,7 +4,6 @@
  * its device copy and the locked paths are storm_dosage.c's; the order of the checks is storm_dosage_lag.c's. No CPU
  * fallback. */
 #include <stdint.h>
-#include <stdio.h>
 
 #include "storm.h"
 #include "storm_hip.h"
@@ -22,31 +21,25 @@ static int ldscore_run(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int st
     else
         rc = device ? storm_hip_lag_dosage_ldscore_device(ctx, m, stat, n_samples, max_lag, score, n_pairs)
                     : storm_hip_lag_dosage_ldscore(ctx, m, stat, n_samples, max_lag, score, n_pairs);
-    return storm_dosage_shim_result(ctx, rc, device, names[complete]);
+    return storm_dosage_band_result(ctx, rc, device, names[complete]);
 }
 
 static int dosage_ldscore(STORM_dosage_t* h, int stat, uint64_t max_lag, float* score, uint32_t* n_pairs, uint64_t out_len,
                           int complete, int device, const char* who) {
     if (!h) return -1;
     if (!score) return -2;
-    storm_host_lock();
-    int rc = storm_host_one_slot_or_refuse(who);
+    int rc = storm_host_begin(who);
     const uint64_t n = h->n_rows;
     if (!rc && max_lag != 0 && out_len < n) rc = -4;
-    if (!rc && max_lag == 0) {
-        char msg[160];
-        snprintf(msg, sizeof(msg), "%s: max_lag must be at least 1", who);
-        storm_host_error(msg);
-        rc = -3;
-    }
+    if (!rc && max_lag == 0) rc = storm_host_refuse(who, "max_lag must be at least 1");
     if (!rc) rc = storm_dosage_ldscore_stat_refusal(who, stat, complete, h->n_samples);
     if (!rc && n >= 2) {
         storm_hip_ctx_t* ctx = NULL;
-        const storm_hip_matrix_t* m = storm_dosage_mirror(h, &ctx);
-        rc = m ? ldscore_run(ctx, m, stat, h->n_samples, max_lag, score, n_pairs, complete, device) : -3;
+        const storm_hip_matrix_t* m = NULL;
+        rc = storm_dosage_operands(h, NULL, &ctx, &m, NULL);
+        if (!rc) rc = ldscore_run(ctx, m, stat, h->n_samples, max_lag, score, n_pairs, complete, device);
     }
-    storm_host_unlock();
-    return rc;
+    return storm_host_end(rc);
 }
 
 int STORM_dosage_lag_ldscore(STORM_dosage_t* h, int stat, uint64_t max_lag, float* score, uint32_t* n_pairs, uint64_t out_len) {

@@ -6,7 +6,6 @@
  * then the new ones. No CPU fallback. */
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 
 #include "storm.h"
@@ -30,8 +29,7 @@ static int annot_run(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int stat
                                                                 score_ld, n_pairs)
                     : storm_hip_lag_dosage_ldscore_annot(ctx, m, stat, n_samples, lag, lo, hi, annot, annot_ld, n_annot, score,
                                                          score_ld, n_pairs);
-    /* (a _device form is waited for: it returns with lo / hi still being read) */
-    return storm_dosage_shim_result(ctx, rc, device, names[complete]);
+    return storm_dosage_band_result(ctx, rc, device, names[complete]);
 }
 
 static int dosage_ldscore_annot(STORM_dosage_t* h, int stat, uint64_t max_lag, const double* pos, double max_dist, const float* annot,
@@ -39,25 +37,15 @@ static int dosage_ldscore_annot(STORM_dosage_t* h, int stat, uint64_t max_lag, c
                                 uint64_t out_rows, int complete, int device, const char* who) {
     if (!h) return -1;
     if (!score || !annot) return -2;
-    storm_host_lock();
-    int rc = storm_host_one_slot_or_refuse(who);
+    int rc = storm_host_begin(who);
     const uint64_t n = h->n_rows;
     const int no_lag = max_lag == 0 && !pos;   /* (with positions, max_lag 0 asks for the lag the windows need) */
-    char msg[320];
     if (!rc && !no_lag && out_rows < n) rc = -4;
-    if (!rc && no_lag) {
-        snprintf(msg, sizeof(msg), "%s: max_lag must be at least 1 where no positions are given", who);
-        storm_host_error(msg);
-        rc = -3;
-    }
+    if (!rc && no_lag) rc = storm_host_refuse(who, "max_lag must be at least 1 where no positions are given");
     if (!rc) rc = storm_dosage_ldscore_stat_refusal(who, stat, complete, h->n_samples);
     /* ---- the new checks */
-    if (!rc && (n_annot < 1 || n_annot > STORM_LDSCORE_MAX_ANNOT)) {
-        snprintf(msg, sizeof(msg), "%s: n_annot = %llu: 1 .. %d annotation columns", who, (unsigned long long)n_annot,
-                 STORM_LDSCORE_MAX_ANNOT);
-        storm_host_error(msg);
-        rc = -3;
-    }
+    if (!rc && (n_annot < 1 || n_annot > STORM_LDSCORE_MAX_ANNOT))
+        rc = storm_host_refuse(who, "n_annot = %llu: 1 .. %d annotation columns", (unsigned long long)n_annot, STORM_LDSCORE_MAX_ANNOT);
     if (!rc && (annot_ld < n_annot || score_ld < n_annot)) rc = -4;
     uint32_t* bounds = NULL;   /* lo, then hi: where positions are given */
     uint64_t lag = max_lag;
@@ -66,22 +54,20 @@ static int dosage_ldscore_annot(STORM_dosage_t* h, int stat, uint64_t max_lag, c
         for (uint64_t i = 0; i < n && !rc; ++i)
             for (uint64_t c = 0; c < n_annot; ++c)
                 if (!isfinite(annot[i * annot_ld + c])) {
-                    snprintf(msg, sizeof(msg), "%s: annot[%llu][%llu] is not finite", who, (unsigned long long)i, (unsigned long long)c);
-                    storm_host_error(msg);
-                    rc = -3;
+                    rc = storm_host_refuse(who, "annot[%llu][%llu] is not finite", (unsigned long long)i, (unsigned long long)c);
                     break;
                 }
     }
     if (!rc && n >= 2) {
         storm_hip_ctx_t* ctx = NULL;
-        const storm_hip_matrix_t* m = storm_dosage_mirror(h, &ctx);
-        rc = m ? annot_run(ctx, m, stat, h->n_samples, lag, bounds, bounds ? bounds + n : NULL, annot, annot_ld, n_annot, score,
-                           score_ld, n_pairs, complete, device)
-               : -3;
+        const storm_hip_matrix_t* m = NULL;
+        rc = storm_dosage_operands(h, NULL, &ctx, &m, NULL);
+        if (!rc)
+            rc = annot_run(ctx, m, stat, h->n_samples, lag, bounds, bounds ? bounds + n : NULL, annot, annot_ld, n_annot, score,
+                           score_ld, n_pairs, complete, device);
     }
     free(bounds);
-    storm_host_unlock();
-    return rc;
+    return storm_host_end(rc);
 }
 
 int STORM_dosage_lag_ldscore_annot(STORM_dosage_t* h, int stat, uint64_t max_lag, const double* pos, double max_dist,

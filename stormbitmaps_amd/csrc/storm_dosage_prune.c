@@ -6,7 +6,6 @@
  * checks is storm_dosage_ldscore_annot.c's. No CPU fallback. */
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 
 #include "storm.h"
@@ -27,36 +26,22 @@ static int prune_run(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t
     else
         rc = device ? storm_hip_lag_dosage_prune_device(ctx, m, n_samples, lag, min_r2, lo, hi, order, keep, owner)
                     : storm_hip_lag_dosage_prune(ctx, m, n_samples, lag, min_r2, lo, hi, order, keep, owner);
-    /* (a _device form is waited for: it returns with lo / hi / order still being read) */
-    return storm_dosage_shim_result(ctx, rc, device, names[complete]);
+    return storm_dosage_band_result(ctx, rc, device, names[complete]);
 }
 
 static int dosage_prune(STORM_dosage_t* h, float min_r2, uint64_t max_lag, const double* pos, double max_dist, const float* priority,
                         uint8_t* keep, uint32_t* owner, uint64_t out_len, int complete, int device, const char* who) {
     if (!h) return -1;
     if (!keep) return -2;
-    storm_host_lock();
-    int rc = storm_host_one_slot_or_refuse(who);
+    int rc = storm_host_begin(who);
     const uint64_t n = h->n_rows;
     const int no_lag = max_lag == 0 && !pos;   /* (with positions, max_lag 0 asks for the lag the windows need) */
-    char msg[320];
     if (!rc && !no_lag && out_len < n) rc = -4;
-    if (!rc && no_lag) {
-        snprintf(msg, sizeof(msg), "%s: max_lag must be at least 1 where no positions are given", who);
-        storm_host_error(msg);
-        rc = -3;
-    }
-    if (!rc && isnan(min_r2)) {
-        snprintf(msg, sizeof(msg), "%s: min_r2 is NaN", who);
-        storm_host_error(msg);
-        rc = -3;
-    }
-    if (!rc && n > STORM_PRUNE_MAX_ROWS) {
-        snprintf(msg, sizeof(msg), "%s: %llu rows: at most %d (the device keeps a bit per row in one workgroup's memory)", who,
-                 (unsigned long long)n, STORM_PRUNE_MAX_ROWS);
-        storm_host_error(msg);
-        rc = -3;
-    }
+    if (!rc && no_lag) rc = storm_host_refuse(who, "max_lag must be at least 1 where no positions are given");
+    if (!rc && isnan(min_r2)) rc = storm_host_refuse(who, "min_r2 is NaN");
+    if (!rc && n > STORM_PRUNE_MAX_ROWS)
+        rc = storm_host_refuse(who, "%llu rows: at most %d (the device keeps a bit per row in one workgroup's memory)",
+                               (unsigned long long)n, STORM_PRUNE_MAX_ROWS);
     uint32_t* plan = NULL;   /* lo, then hi, then the order */
     uint64_t lag = max_lag;
     /* (one buffer of three words per row as soon as either the windows or the order want one) */
@@ -64,28 +49,22 @@ static int dosage_prune(STORM_dosage_t* h, float min_r2, uint64_t max_lag, const
     if (!rc && priority && n) {
         uint64_t bad = 0;
         const int code = storm_prune_order_plan(priority, n, plan + 2 * n, NULL, &bad);
-        if (code == STORM_PRUNE_ORDER_NAN)
-            snprintf(msg, sizeof(msg), "%s: priority[%llu] is NaN", who, (unsigned long long)bad);
-        else if (code)
-            snprintf(msg, sizeof(msg), "%s: out of host memory for the order of %llu rows", who, (unsigned long long)n);
-        if (code) {
-            storm_host_error(msg);
-            rc = -3;
-        }
+        if (code == STORM_PRUNE_ORDER_NAN) rc = storm_host_refuse(who, "priority[%llu] is NaN", (unsigned long long)bad);
+        else if (code) rc = storm_host_refuse(who, "out of host memory for the order of %llu rows", (unsigned long long)n);
     }
     if (!rc && n == 1 && !device) {   /* a row without any edge is kept and owns itself: no device is asked */
         keep[0] = 1;
         if (owner) owner[0] = 0;
     } else if (!rc && n >= 1) {
         storm_hip_ctx_t* ctx = NULL;
-        const storm_hip_matrix_t* m = storm_dosage_mirror(h, &ctx);
-        rc = m ? prune_run(ctx, m, h->n_samples, lag, min_r2, pos ? plan : NULL, pos ? plan + n : NULL, priority ? plan + 2 * n : NULL,
-                           keep, owner, complete, device)
-               : -3;
+        const storm_hip_matrix_t* m = NULL;
+        rc = storm_dosage_operands(h, NULL, &ctx, &m, NULL);
+        if (!rc)
+            rc = prune_run(ctx, m, h->n_samples, lag, min_r2, pos ? plan : NULL, pos ? plan + n : NULL, priority ? plan + 2 * n : NULL,
+                           keep, owner, complete, device);
     }
     free(plan);
-    storm_host_unlock();
-    return rc;
+    return storm_host_end(rc);
 }
 
 int STORM_dosage_lag_prune(STORM_dosage_t* h, float min_r2, uint64_t max_lag, const double* pos, double max_dist,

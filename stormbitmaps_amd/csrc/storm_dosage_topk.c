@@ -1,10 +1,9 @@
 /* storm_dosage_topk.c — for each row of a dosage container its k best rows by r^2, r or the dot product, selected on the
  * device (storm.h: STORM_dosage_pairw_topk, STORM_dosage_square_topk, their _complete and _device forms; storm_hip.h:
  * storm_hip_pairw_dosage_topk, storm_hip_square_dosage_topk). The container, its device copy and the locked paths are
- * storm_dosage.c's, as in storm_dosage_square.c; arguments and return codes are those of STORM_dosage_square_corr and
+ * storm_dosage.c's, as in storm_dosage_pairs.c; arguments and return codes are those of STORM_dosage_square_corr and
  * STORM_square_topk. Every refusal comes before the device is touched. No CPU fallback. */
 #include <stdint.h>
-#include <stdio.h>
 
 #include "storm.h"
 #include "storm_hip.h"
@@ -13,24 +12,13 @@
 
 /* the arguments as the shim takes them: 0, or -3 with the reason */
 static int topk_args(const char* who, int score, int complete, uint64_t k, uint64_t panel_rows) {
-    char msg[220];
-    if (score != STORM_DOSAGE_R2 && score != STORM_DOSAGE_R && (complete || score != STORM_DOSAGE_TOPK_DOT)) {
-        snprintf(msg, sizeof(msg), "%s: score must be 0 (STORM_DOSAGE_R2)%s", who,
-                 complete ? " or 1 (STORM_DOSAGE_R): the dot product has no pairwise-complete form"
-                          : ", 1 (STORM_DOSAGE_R) or 2 (STORM_DOSAGE_TOPK_DOT)");
-        storm_host_error(msg);
-        return -3;
-    }
-    if (k == 0 || k > STORM_TOPK_MAX) {
-        snprintf(msg, sizeof(msg), "%s: k must be in [1, %d]", who, STORM_TOPK_MAX);
-        storm_host_error(msg);
-        return -3;
-    }
-    if (panel_rows % 256u != 0) {
-        snprintf(msg, sizeof(msg), "%s: panel_rows must be 0 (chosen by the library) or a multiple of 256", who);
-        storm_host_error(msg);
-        return -3;
-    }
+    if (score != STORM_DOSAGE_R2 && score != STORM_DOSAGE_R && (complete || score != STORM_DOSAGE_TOPK_DOT))
+        return storm_host_refuse(who, "score must be 0 (STORM_DOSAGE_R2)%s",
+                                 complete ? " or 1 (STORM_DOSAGE_R): the dot product has no pairwise-complete form"
+                                          : ", 1 (STORM_DOSAGE_R) or 2 (STORM_DOSAGE_TOPK_DOT)");
+    if (k == 0 || k > STORM_TOPK_MAX) return storm_host_refuse(who, "k must be in [1, %d]", STORM_TOPK_MAX);
+    if (panel_rows % 256u != 0)
+        return storm_host_refuse(who, "panel_rows must be 0 (chosen by the library) or a multiple of 256");
     return 0;
 }
 
@@ -39,24 +27,16 @@ static int dosage_topk(STORM_dosage_t* a, STORM_dosage_t* b, int have_b, int com
                        uint32_t* idx, void* val, uint64_t out_rows, uint64_t out_ld, int device, const char* who) {
     if (!a || (have_b && !b)) return -1;
     if (!idx || !val) return -2;
-    storm_host_lock();
-    int rc = storm_host_one_slot_or_refuse(who);
+    int rc = storm_host_begin(who);
     if (!rc && (out_rows < a->n_rows || out_ld < k)) rc = -4;
     if (!rc) rc = topk_args(who, score, complete, k, panel_rows);
-    if (!rc && have_b && a->n_samples != b->n_samples) {
-        char msg[200];
-        snprintf(msg, sizeof(msg), "%s: containers of %llu and of %llu samples", who, (unsigned long long)a->n_samples,
-                 (unsigned long long)b->n_samples);
-        storm_host_error(msg);
-        rc = -3;
-    }
+    if (!rc && have_b) rc = storm_dosage_samples_refusal(who, a, b);
     if (!rc && a->n_rows != 0) {
-        storm_hip_ctx_t *ctx = NULL, *ctx_b = NULL;
-        const storm_hip_matrix_t* ma = storm_dosage_mirror(a, &ctx);
-        const storm_hip_matrix_t* mb = !ma ? NULL : !have_b || a == b ? ma : storm_dosage_mirror(b, &ctx_b);
+        storm_hip_ctx_t* ctx = NULL;
+        const storm_hip_matrix_t *ma = NULL, *mb = NULL;
         const uint64_t S = a->n_samples;
-        if (!ma || !mb) rc = -3;
-        else {
+        rc = storm_dosage_operands(a, b, &ctx, &ma, &mb);
+        if (!rc) {
             int hrc;
             const char* name;
             if (!have_b) {
@@ -76,14 +56,10 @@ static int dosage_topk(STORM_dosage_t* a, STORM_dosage_t* b, int have_b, int com
                     hrc = device ? storm_hip_square_dosage_topk_device(ctx, ma, mb, score, S, k, panel_rows, idx, val, out_ld)
                                  : storm_hip_square_dosage_topk(ctx, ma, mb, score, S, k, panel_rows, idx, val, out_ld);
             }
-            if (hrc != STORM_HIP_OK) {
-                storm_host_device_error(name);
-                rc = -3;
-            }
+            rc = storm_host_shim_result(ctx, hrc, 0, name);
         }
     }
-    storm_host_unlock();
-    return rc;
+    return storm_host_end(rc);
 }
 
 int STORM_dosage_pairw_topk(STORM_dosage_t* h, int score, uint64_t k, uint64_t panel_rows, uint32_t* idx, void* val,

@@ -11,7 +11,6 @@
  * Also here, because they too sit on storm_host.c's locked paths without adding to them: the similarity forms of all three
  * per-pair matrices (storm.h: STORM_contig_pairw_similarity, STORM_pairw_similarity, STORM_square_similarity and _device). */
 #include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 
 #include "storm.h"
@@ -97,11 +96,7 @@ static int square_locked(STORM_t* a, STORM_t* b, int what, int op, uint32_t* out
                                                        : storm_hip_rowlists_square_similarity_device(ctx, la, lb, measure, n_bits, (float*)out, out_ld))
                            : what == 1  ? storm_hip_rowlists_square_matrix(ctx, la, lb, op, out, out_ld)
                                         : storm_hip_rowlists_square_matrix_device(ctx, la, lb, op, out, out_ld);
-            if (rc != STORM_HIP_OK) {
-                storm_host_device_error("storm_hip_rowlists_square");
-                return -3;
-            }
-            return 0;
+            return storm_host_shim_result(ctx, rc, 0, "storm_hip_rowlists_square");
         }
     }
     if (storm_host_common_dense(a, sa, b, sb, slot)) return -3;
@@ -110,11 +105,7 @@ static int square_locked(STORM_t* a, STORM_t* b, int what, int op, uint32_t* out
                                                : storm_hip_cross_dense_similarity_device(ctx, sa->m[slot], sb->m[slot], measure, n_bits, (float*)out, out_ld))
                    : what == 1  ? storm_hip_cross_dense_matrix(ctx, sa->m[slot], sb->m[slot], op, out, out_ld)
                                 : storm_hip_cross_dense_matrix_device(ctx, sa->m[slot], sb->m[slot], op, out, out_ld);
-    if (rc != STORM_HIP_OK) {
-        storm_host_device_error("storm_hip_cross_dense");
-        return -3;
-    }
-    return 0;
+    return storm_host_shim_result(ctx, rc, 0, "storm_hip_cross_dense");
 }
 
 uint64_t STORM_intersect_cardinality_square(const STORM_t* STORM_RESTRICT bitmap1, const STORM_t* STORM_RESTRICT bitmap2) {
@@ -124,10 +115,9 @@ uint64_t STORM_intersect_cardinality_square(const STORM_t* STORM_RESTRICT bitmap
     }
     if (bitmap1->n_conts == 0 || bitmap2->n_conts == 0) return 0;
     uint64_t total = 0;
-    storm_host_lock();
+    storm_host_begin(NULL);   /* (no one-slot check of the frame's: square_locked refuses several slots or shards in its own words) */
     /* (the containers are const; the device copies behind them are built and kept as for every other call) */
-    const int rc = square_locked((STORM_t*)bitmap1, (STORM_t*)bitmap2, 0, 0, NULL, 0, &total, -1, 0);
-    storm_host_unlock();
+    const int rc = storm_host_end(square_locked((STORM_t*)bitmap1, (STORM_t*)bitmap2, 0, 0, NULL, 0, &total, -1, 0));
     return rc ? (uint64_t)-1 : total;
 }
 
@@ -135,30 +125,20 @@ int STORM_square_matrix(STORM_t* a, STORM_t* b, int op, uint32_t* out, uint64_t 
     if (!a || !b) return -1;
     if (!out) return -2;
     if (out_rows < a->n_conts || out_ld < b->n_conts) return -4;
-    if (op < 0 || op > 2) {
-        storm_host_error("STORM_square_matrix: op must be 0 (and), 1 (or) or 2 (xor)");
-        return -3;
-    }
+    if (op < 0 || op > 2) return storm_host_refuse("STORM_square_matrix", "op must be 0 (and), 1 (or) or 2 (xor)");
     if (a->n_conts == 0 || b->n_conts == 0) return 0;
-    storm_host_lock();
-    const int rc = square_locked(a, b, 1, op, out, out_ld, NULL, -1, 0);
-    storm_host_unlock();
-    return rc;
+    storm_host_begin(NULL);   /* (as above) */
+    return storm_host_end(square_locked(a, b, 1, op, out, out_ld, NULL, -1, 0));
 }
 
 int STORM_square_matrix_device(STORM_t* a, STORM_t* b, int op, uint32_t* d_out, uint64_t out_rows, uint64_t out_ld) {
     if (!a || !b) return -1;
     if (!d_out) return -2;
-    storm_host_lock();
-    int rc = storm_host_one_slot_or_refuse("STORM_square_matrix_device");
+    int rc = storm_host_begin("STORM_square_matrix_device");
     if (!rc && (out_rows < a->n_conts || out_ld < b->n_conts)) rc = -4;
-    if (!rc && (op < 0 || op > 2)) {
-        storm_host_error("STORM_square_matrix_device: op must be 0 (and), 1 (or) or 2 (xor)");
-        rc = -3;
-    }
+    if (!rc && (op < 0 || op > 2)) rc = storm_host_refuse("STORM_square_matrix_device", "op must be 0 (and), 1 (or) or 2 (xor)");
     if (!rc && a->n_conts != 0 && b->n_conts != 0) rc = square_locked(a, b, 2, op, d_out, out_ld, NULL, -1, 0);
-    storm_host_unlock();
-    return rc;
+    return storm_host_end(rc);
 }
 
 
@@ -168,47 +148,33 @@ int STORM_square_matrix_device(STORM_t* a, STORM_t* b, int op, uint32_t* d_out, 
 /* The measure and the universe size as the shim takes them: 0, or -3 with the reason. Jaccard and cosine do not read n_bits;
  * the LD measures take `n_bits_default` (a STORM_contiguous_t's vector_length; 0 for a STORM_t, which declares none) for 0. */
 static int similarity_args(const char* who, int measure, uint64_t* n_bits, uint64_t n_bits_default) {
-    char msg[200];
-    if (measure < STORM_SIM_JACCARD || measure > STORM_SIM_LD_R2) {
-        snprintf(msg, sizeof(msg), "%s: measure must be 0 (Jaccard), 1 (cosine), 2 (LD D) or 3 (LD r^2)", who);
-        storm_host_error(msg);
-        return -3;
-    }
+    if (measure < STORM_SIM_JACCARD || measure > STORM_SIM_LD_R2)
+        return storm_host_refuse(who, "measure must be 0 (Jaccard), 1 (cosine), 2 (LD D) or 3 (LD r^2)");
     if (measure < STORM_SIM_LD_D) {
         *n_bits = 1;
         return 0;
     }
-    if (*n_bits == 0) *n_bits = n_bits_default;
-    if (*n_bits == 0 || *n_bits > (1ull << 32)) {
-        snprintf(msg, sizeof(msg), "%s: the LD measures need n_bits, the size of the universe, in [1, 2^32]%s", who,
-                 n_bits_default ? "" : " (a STORM_t declares none: 0 is refused)");
-        storm_host_error(msg);
-        return -3;
-    }
-    return 0;
+    return storm_host_ld_n_bits(who, n_bits, n_bits_default);
 }
 
 static int contig_pairw_similarity(STORM_contiguous_t* h, int measure, uint64_t n_bits, float* out, uint64_t out_rows,
                                    uint64_t out_ld, int device, const char* who) {
     if (!h) return -1;
     if (!out) return -2;
-    storm_host_lock();
-    int rc = storm_host_one_slot_or_refuse(who);
+    int rc = storm_host_begin(who);
     const uint64_t n = h->n_data;
     if (!rc && (out_rows < n || out_ld < n)) rc = -4;
     if (!rc) rc = similarity_args(who, measure, &n_bits, h->vector_length);
     if (!rc && n != 0) {
-        const storm_hip_matrix_t* m = storm_host_contig_matrix(h);
-        storm_hip_ctx_t* ctx = m ? storm_host_ctx() : NULL;
-        if (!ctx) rc = -3;
-        else if ((device ? storm_hip_pairw_similarity_device(ctx, m, measure, n_bits, out, out_ld)
-                         : storm_hip_pairw_similarity(ctx, m, measure, n_bits, out, out_ld)) != STORM_HIP_OK) {
-            storm_host_device_error("storm_hip_pairw_similarity");
-            rc = -3;
-        }
+        storm_hip_ctx_t* ctx = NULL;
+        const storm_hip_matrix_t* m = NULL;
+        rc = storm_host_contig_operand(h, &ctx, &m);
+        if (!rc)
+            rc = storm_host_shim_result(ctx, device ? storm_hip_pairw_similarity_device(ctx, m, measure, n_bits, out, out_ld)
+                                                    : storm_hip_pairw_similarity(ctx, m, measure, n_bits, out, out_ld),
+                                        0, "storm_hip_pairw_similarity");
     }
-    storm_host_unlock();
-    return rc;
+    return storm_host_end(rc);
 }
 
 int STORM_contig_pairw_similarity(STORM_contiguous_t* h, int measure, uint64_t n_bits, float* out, uint64_t out_rows,
@@ -221,12 +187,12 @@ int STORM_contig_pairw_similarity_device(STORM_contiguous_t* h, int measure, uin
     return contig_pairw_similarity(h, measure, n_bits, d_out, out_rows, out_ld, 1, "STORM_contig_pairw_similarity_device");
 }
 
+/* (the operand by the path choice of STORM_pairw_matrix_device: the row lists or the dense replica) */
 static int storm_pairw_similarity(STORM_t* h, int measure, uint64_t n_bits, float* out, uint64_t out_rows, uint64_t out_ld,
                                   int device, const char* who) {
     if (!h) return -1;
     if (!out) return -2;
-    storm_host_lock();
-    int rc = storm_host_one_slot_or_refuse(who);
+    int rc = storm_host_begin(who);
     const uint64_t n = h->n_conts;
     if (!rc && (out_rows < n || out_ld < n)) rc = -4;
     if (!rc) rc = similarity_args(who, measure, &n_bits, 0);
@@ -237,20 +203,17 @@ static int storm_pairw_similarity(STORM_t* h, int measure, uint64_t n_bits, floa
         storm_hip_ctx_t* ctx = rc ? NULL : storm_host_ctx();
         const int slot = storm_host_slot();
         if (!rc && !ctx) rc = -3;
-        if (!rc && from_lists) {
-            if ((device ? storm_hip_rowlists_pairw_similarity_device(ctx, st->l[slot], measure, n_bits, out, out_ld)
-                        : storm_hip_rowlists_pairw_similarity(ctx, st->l[slot], measure, n_bits, out, out_ld)) != STORM_HIP_OK) {
-                storm_host_device_error("storm_hip_rowlists_pairw_similarity");
-                rc = -3;
-            }
-        } else if (!rc && (device ? storm_hip_pairw_similarity_device(ctx, st->m[slot], measure, n_bits, out, out_ld)
-                                  : storm_hip_pairw_similarity(ctx, st->m[slot], measure, n_bits, out, out_ld)) != STORM_HIP_OK) {
-            storm_host_device_error("storm_hip_pairw_similarity");
-            rc = -3;
-        }
+        if (!rc && from_lists)
+            rc = storm_host_shim_result(
+                ctx, device ? storm_hip_rowlists_pairw_similarity_device(ctx, st->l[slot], measure, n_bits, out, out_ld)
+                            : storm_hip_rowlists_pairw_similarity(ctx, st->l[slot], measure, n_bits, out, out_ld),
+                0, "storm_hip_rowlists_pairw_similarity");
+        else if (!rc)
+            rc = storm_host_shim_result(ctx, device ? storm_hip_pairw_similarity_device(ctx, st->m[slot], measure, n_bits, out, out_ld)
+                                                    : storm_hip_pairw_similarity(ctx, st->m[slot], measure, n_bits, out, out_ld),
+                                        0, "storm_hip_pairw_similarity");
     }
-    storm_host_unlock();
-    return rc;
+    return storm_host_end(rc);
 }
 
 int STORM_pairw_similarity(STORM_t* h, int measure, uint64_t n_bits, float* out, uint64_t out_rows, uint64_t out_ld) {
@@ -266,13 +229,11 @@ static int square_similarity(STORM_t* a, STORM_t* b, int measure, uint64_t n_bit
                              int what, const char* who) {
     if (!a || !b) return -1;
     if (!out) return -2;
-    storm_host_lock();
-    int rc = storm_host_one_slot_or_refuse(who);
+    int rc = storm_host_begin(who);
     if (!rc && (out_rows < a->n_conts || out_ld < b->n_conts)) rc = -4;
     if (!rc) rc = similarity_args(who, measure, &n_bits, 0);
     if (!rc && a->n_conts != 0 && b->n_conts != 0) rc = square_locked(a, b, what, 0, (uint32_t*)out, out_ld, NULL, measure, n_bits);
-    storm_host_unlock();
-    return rc;
+    return storm_host_end(rc);
 }
 
 int STORM_square_similarity(STORM_t* a, STORM_t* b, int measure, uint64_t n_bits, float* out, uint64_t out_rows,

@@ -1,6 +1,6 @@
 /* dosage_complete_driver.c — TEST ONLY. The host entry points of the dosage container's rectangle and of its calls for rows
- * with missing genotypes (stormbitmaps_amd/csrc/storm_dosage_complete.c on storm_dosage.c and storm_host.c's locked paths)
- * as a stand-alone program for AddressSanitizer / UBSan, on device_stub.c and dosage_complete_stub.c: what reaches the
+ * with missing genotypes (stormbitmaps_amd/csrc/storm_dosage_pairs.c on storm_dosage.c and storm_host.c's locked paths) as
+ * a stand-alone program for AddressSanitizer / UBSan, on device_stub.c, dosage_complete_stub.c and dosage_pairs_stub.c: what reaches the
  * "device" from two containers, outputs with a pitch, every refusal, growth between calls. Never linked into the product. */
 #include <math.h>
 #include <stdint.h>
@@ -62,7 +62,32 @@ static void one_shape(uint64_t S, uint64_t na, uint64_t nb) {
     }
     if (na) CHECK(STORM_dosage_square_dot(a, b, out, na - 1, ld) == -4);
     if (nb) CHECK(STORM_dosage_square_dot(a, b, out, na, nb - 1) == -4);
-    free(out);
+
+    /* the rectangle's statistics go through the same body: the shared samples, r with row 0 (all missing) sharing nothing */
+    float* fout = (float*)malloc((size_t)(na + 1) * ld * sizeof(float));
+    CHECK(fout);
+    for (int device = 0; device < 2; ++device) {
+        for (uint64_t k = 0; k < (na + 1) * ld; ++k) out[k] = 0xDEADBEEFu, fout[k] = -7.5f;
+        CHECK((device ? STORM_dosage_square_nobs_device(a, b, out, na + 1, ld) : STORM_dosage_square_nobs(a, b, out, na + 1, ld)) == 0);
+        CHECK((device ? STORM_dosage_square_corr_complete_device(a, b, STORM_DOSAGE_R, fout, na + 1, ld)
+                      : STORM_dosage_square_corr_complete(a, b, STORM_DOSAGE_R, fout, na + 1, ld)) == 0);
+        for (uint64_t i = 0; i <= na; ++i)
+            for (uint64_t j = 0; j < ld; ++j) {
+                if (i >= na || j >= nb || na == 0 || nb == 0) {
+                    CHECK(out[i * ld + j] == 0xDEADBEEFu && fout[i * ld + j] == -7.5f);
+                    continue;
+                }
+                uint32_t c = 0;
+                for (uint64_t s = 0; s < S; ++s) c += va[i * S + s] != 3 && vb[j * S + s] != 3;
+                CHECK(out[i * ld + j] == c);
+                CHECK((i != 0 && j != 0) || (c == 0 && isnan(fout[i * ld + j])));
+            }
+        CHECK((device ? STORM_dosage_square_corr_device(a, b, STORM_DOSAGE_R2, fout, na + 1, ld)
+                      : STORM_dosage_square_corr(a, b, STORM_DOSAGE_R2, fout, na + 1, ld)) == 0);
+    }
+    CHECK(STORM_dosage_square_corr(a, b, 2, fout, na + 1, ld) == -3 && STORM_dosage_square_corr_complete_device(a, b, -1, fout, na + 1, ld) == -3);
+    if (na) CHECK(STORM_dosage_square_nobs(a, b, out, na - 1, ld) == -4 && STORM_dosage_square_corr(a, b, 0, fout, na - 1, ld) == -4);
+    free(out), free(fout);
 
     /* missing genotypes on `a`: the triangle with a pitch, host zeros at i >= j, nothing outside the n x n window */
     const uint64_t n = na, ldn = n + 3;

@@ -1,7 +1,8 @@
 /* dosage_complete_stub.c — TEST ONLY. The dosage entry points of the device library for dosage_complete_driver.c, beside
  * device_stub.c (whose matrix is host memory): every call computes its result from the words that reached it, sample by
- * sample on the CPU, and writes exactly the window the real call writes. Never linked into the product. */
-#include <string.h>
+ * sample on the CPU, and writes exactly the window the real call writes. Here the row sums and the triangle's dot products
+ * and correlations (the five calls dosage_driver.c answers itself); the rectangle and the calls that read 3 as "missing"
+ * are dosage_pairs_stub.c's. Never linked into the product. */
 
 #include "stub_dosage.h"
 
@@ -47,69 +48,4 @@ int storm_hip_pairw_dosage_corr(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* 
     for (uint64_t i = 0; i < m->n_rows; ++i)
         for (uint64_t j = 0; j < m->n_rows; ++j) h_out[i * ld + j] = 0.0f;
     return storm_hip_pairw_dosage_corr_device(ctx, m, measure, n_samples, h_out, ld);
-}
-
-/* ---- the rectangle, and the calls that read 3 as "missing" ---- */
-int storm_hip_square_dosage_matrix_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b,
-                                          uint32_t* d_out, uint64_t ld) {
-    (void)ctx;
-    if (a->n_words != b->n_words || ld < b->n_rows) return STORM_HIP_EINVAL;
-    for (uint64_t i = 0; i < a->n_rows; ++i)
-        for (uint64_t j = 0; j < b->n_rows; ++j) d_out[i * ld + j] = dot(a, i, b, j);
-    return STORM_HIP_OK;
-}
-int storm_hip_square_dosage_matrix(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a, const storm_hip_matrix_t* b, uint32_t* h_out,
-                                   uint64_t ld) {
-    return storm_hip_square_dosage_matrix_device(ctx, a, b, h_out, ld);
-}
-int storm_hip_dosage_row_missing(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint32_t* h_missing) {
-    (void)ctx;
-    if ((n_samples + 31) / 32 != m->n_words) return STORM_HIP_EINVAL;
-    for (uint64_t i = 0; i < m->n_rows; ++i) {
-        h_missing[i] = 0;
-        for (uint64_t s = 0; s < n_samples; ++s) h_missing[i] += value_at(m, i, s) == 3u;
-    }
-    return STORM_HIP_OK;
-}
-int storm_hip_pairw_dosage_nobs_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint32_t* d_out,
-                                       uint64_t ld) {
-    (void)ctx;
-    if (ld < m->n_rows || (n_samples + 31) / 32 != m->n_words) return STORM_HIP_EINVAL;
-    for (uint64_t i = 0; i < m->n_rows; ++i)
-        for (uint64_t j = i + 1; j < m->n_rows; ++j) {
-            uint32_t n = 0;
-            for (uint64_t s = 0; s < n_samples; ++s) n += value_at(m, i, s) != 3u && value_at(m, j, s) != 3u;
-            d_out[i * ld + j] = n;
-        }
-    return STORM_HIP_OK;
-}
-int storm_hip_pairw_dosage_nobs(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint32_t* h_out, uint64_t ld) {
-    if (ld < m->n_rows) return STORM_HIP_EINVAL;
-    for (uint64_t i = 0; i < m->n_rows; ++i)
-        for (uint64_t j = 0; j < m->n_rows; ++j) h_out[i * ld + j] = 0;
-    return storm_hip_pairw_dosage_nobs_device(ctx, m, n_samples, h_out, ld);
-}
-int storm_hip_pairw_dosage_corr_complete_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_samples,
-                                                float* d_out, uint64_t ld) {
-    (void)ctx;
-    if (ld < m->n_rows || (n_samples + 31) / 32 != m->n_words || measure < 0 || measure > 1) return STORM_HIP_EINVAL;
-    for (uint64_t i = 0; i < m->n_rows; ++i)
-        for (uint64_t j = i + 1; j < m->n_rows; ++j) {
-            double N = 0, P = 0, sx = 0, sy = 0, qx = 0, qy = 0;
-            for (uint64_t s = 0; s < n_samples; ++s) {
-                const unsigned x = value_at(m, i, s), y = value_at(m, j, s);
-                if (x == 3u || y == 3u) continue;
-                N += 1, P += x * y, sx += x, sy += y, qx += x * x, qy += y * y;
-            }
-            const double num = N * P - sx * sy, dx = N * qx - sx * sx, dy = N * qy - sy * sy;
-            d_out[i * ld + j] = dx == 0 || dy == 0 ? NAN : (float)(measure == 0 ? num * num / (dx * dy) : num / sqrt(dx * dy));
-        }
-    return STORM_HIP_OK;
-}
-int storm_hip_pairw_dosage_corr_complete(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int measure, uint64_t n_samples,
-                                         float* h_out, uint64_t ld) {
-    if (ld < m->n_rows) return STORM_HIP_EINVAL;
-    for (uint64_t i = 0; i < m->n_rows; ++i)
-        for (uint64_t j = 0; j < m->n_rows; ++j) h_out[i * ld + j] = 0.0f;
-    return storm_hip_pairw_dosage_corr_complete_device(ctx, m, measure, n_samples, h_out, ld);
 }

@@ -64,11 +64,14 @@ def test_add_against_add_packed_word_for_word_under_asan_ubsan(tmp_path):
     """The words STORM_dosage_add packs against the words STORM_dosage_add_packed is given, as they reach the device
     (tests/host_sanitize/dosage_driver.c on the device stub: the upload's destination is host memory there), word for word
     and against the layout; growth, refusals, clear and free along the way. A stand-alone program under AddressSanitizer,
-    UBSan and LeakSanitizer: the host side of the container (storm_dosage.c on storm_host.c's locked paths)."""
+    UBSan and LeakSanitizer: the host side of the container (storm_dosage.c and storm_dosage_pairs.c on storm_host.c's locked
+    paths; the calls the driver does not answer itself are dosage_pairs_stub.c's and dosage_band_stub.c's)."""
     exe = tmp_path / "dosage_sanitize"
     csrc = os.path.join(ROOT, "stormbitmaps_amd", "csrc")
-    srcs = [os.path.join(csrc, f) for f in ("storm_host.c", "storm_dosage.c", "storm_synth.c", "storm_leaves.c")] + \
-           [os.path.join(ROOT, "tests", "host_sanitize", f) for f in ("device_stub.c", "dosage_driver.c")]
+    srcs = [os.path.join(csrc, f) for f in ("storm_host.c", "storm_host_call.c", "storm_dosage.c", "storm_dosage_pairs.c",
+                                            "storm_synth.c", "storm_leaves.c")] + \
+           [os.path.join(ROOT, "tests", "host_sanitize", f) for f in ("device_stub.c", "dosage_pairs_stub.c", "dosage_band_stub.c",
+                                                                      "dosage_driver.c")]
     build = subprocess.run(["gcc", "-std=gnu11", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                             "-fno-omit-frame-pointer", "-Wall", "-pthread", "-I" + os.path.join(ROOT, "include"), *srcs,
                             "-o", str(exe), "-lm"], capture_output=True, text=True)

@@ -1,7 +1,7 @@
 """The host entry points of the dosage container's rectangle and of its calls for rows with missing genotypes
-(stormbitmaps_amd/csrc/storm_dosage_complete.c) as a stand-alone program under AddressSanitizer, UBSan and LeakSanitizer:
-tests/host_sanitize/dosage_complete_driver.c on device_stub.c and dosage_complete_stub.c (the "device" is host memory and
-computes sample by sample). Two containers, outputs with a pitch, every refusal, rows added between calls."""
+(stormbitmaps_amd/csrc/storm_dosage_pairs.c, and STORM_dosage_row_missing in storm_dosage.c) as a stand-alone program under
+AddressSanitizer, UBSan and LeakSanitizer: tests/host_sanitize/dosage_complete_driver.c on device_stub.c, dosage_complete_stub.c
+and dosage_pairs_stub.c (the "device" is host memory and computes sample by sample). Two containers, outputs with a pitch, every refusal, rows added between calls."""
 import os
 import shutil
 import subprocess
@@ -14,7 +14,7 @@ from tests._host_sanitize import ROOT, dosage_sources
 @pytest.mark.skipif(shutil.which("gcc") is None, reason="needs gcc")
 def test_rectangle_and_missing_genotype_calls_under_asan_ubsan(tmp_path):
     exe = tmp_path / "dosage_complete_sanitize"
-    srcs = dosage_sources(("storm_dosage_complete.c",), ("dosage_complete_driver.c",))
+    srcs = dosage_sources(("storm_dosage_pairs.c",), ("dosage_complete_driver.c",))
     build = subprocess.run(["gcc", "-std=gnu11", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                             "-fno-omit-frame-pointer", "-Wall", "-pthread", "-I" + os.path.join(ROOT, "include"), *srcs,
                             "-o", str(exe), "-lm"], capture_output=True, text=True)
