@@ -26,6 +26,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cerrno>
 #include <cstdarg>
 #include <cstdlib>
 #include <cstring>
@@ -486,6 +487,22 @@ int storm_hip_device_pci_bus_id(int device, char* buf, size_t buflen) {
 
 namespace storm {
 __global__ void warm_core_kernel() {}
+
+// STORM_HIP_VARIANT / _SEG_ROWS / _CHUNKS_PER_ITEM are the options "variant" / "seg_rows" / "chunks_per_item" of a new
+// context and take what storm_hip_ctx_set_option takes. (They went through atoi unchecked: STORM_HIP_SEG_ROWS=0, or a word,
+// divided by zero in the first popcount pass, and STORM_HIP_VARIANT=5 chose a form this build does not carry.) A value the
+// option refuses is reported and ignored.
+static void option_from_env(storm_hip_ctx_t* ctx, const char* name, const char* key) {
+    const char* v = getenv(name);
+    if (!v) return;
+    char* end = nullptr;
+    errno = 0;
+    const long long value = strtoll(v, &end, 10);
+    if (end == v || *end != '\0' || errno != 0)
+        fprintf(stderr, "libstorm_hip: %s: \"%s\" ignored (a decimal number expected)\n", name, v);
+    else if (storm_hip_ctx_set_option(ctx, key, value) != STORM_HIP_OK)
+        fprintf(stderr, "libstorm_hip: %s: \"%s\" ignored: %s\n", name, v, g_error);
+}
 }
 
 int storm_hip_ctx_create(int device, void* stream, storm_hip_ctx_t** out) {
@@ -554,9 +571,9 @@ int storm_hip_ctx_create(int device, void* stream, storm_hip_ctx_t** out) {
             return STORM_HIP_EHIP;
         }
     }
-    if (const char* v = getenv("STORM_HIP_VARIANT")) ctx->variant = atoi(v);
-    if (const char* v = getenv("STORM_HIP_SEG_ROWS")) ctx->seg_rows = atoi(v);
-    if (const char* v = getenv("STORM_HIP_CHUNKS_PER_ITEM")) ctx->chunks_per_item = atoi(v);
+    option_from_env(ctx, "STORM_HIP_VARIANT", "variant");
+    option_from_env(ctx, "STORM_HIP_SEG_ROWS", "seg_rows");
+    option_from_env(ctx, "STORM_HIP_CHUNKS_PER_ITEM", "chunks_per_item");
     *out = ctx;
     return STORM_HIP_OK;
 }

@@ -156,22 +156,50 @@ static void configure_from_env_locked(void) {
         for (int d = 0; d < n; ++d) g_device_ids[d] = d;
         n_devices = n > 0 ? n : 1;
     } else if (devs && devs[0]) {
-        int n = 0;
+        /* decimal ordinals separated by single commas, at most MAX_DEVICES of them; anything else is reported and the
+         * process runs on device 0 alone (strtol used to stand still on garbage: all 16 slots became device 0, silently).
+         * An ordinal that names no device is not judged here: creating its context fails, and says so. */
+        int n = 0, bad = 0;
         const char* p = devs;
-        while (*p && n < MAX_DEVICES) {
-            g_device_ids[n++] = (int)strtol(p, (char**)&p, 10);
-            if (*p == ',') ++p;
+        for (;;) {
+            char* end = NULL;
+            const char* digits = *p == '-' ? p + 1 : p; /* (a negative ordinal is a number: it fails at context creation) */
+            const long v = *digits >= '0' && *digits <= '9' ? strtol(p, &end, 10) : 0;
+            if (!end || v < INT32_MIN || v > INT32_MAX || n == MAX_DEVICES) bad = 1;
+            if (bad) break;
+            g_device_ids[n++] = (int)v;
+            if (*end == '\0') break;
+            if (*end != ',') bad = 1;
+            p = end + 1;
         }
-        n_devices = n > 0 ? n : 1;
+        if (bad) {
+            fprintf(stderr, "libstorm_hip: STORM_HIP_DEVICES: \"%s\" ignored (\"all\" or up to %d decimal ordinals separated by commas expected): device 0 alone\n",
+                    devs, MAX_DEVICES);
+            g_device_ids[0] = 0;
+            n = 1;
+        }
+        n_devices = n;
     } else {
         g_device_ids[0] = 0;
         n_devices = 1;
     }
     const char* shard = getenv("STORM_HIP_SHARD");
-    unsigned r = 0, c = 1;
-    if (shard && sscanf(shard, "%u/%u", &r, &c) == 2 && c > 0 && r < c) {
-        g_shard_rank = r;
-        g_shard_count = c;
+    if (shard && shard[0]) {
+        /* "rank/world", both decimal, rank < world; anything else is reported and the process stays unsharded (it used
+         * to be dropped silently: every rank of a job then returned the whole total) */
+        unsigned long long r = 0, c = 0;
+        char *e1 = NULL, *e2 = NULL;
+        int ok = shard[0] >= '0' && shard[0] <= '9';
+        if (ok) r = strtoull(shard, &e1, 10);
+        ok = ok && *e1 == '/' && e1[1] >= '0' && e1[1] <= '9';
+        if (ok) c = strtoull(e1 + 1, &e2, 10);
+        ok = ok && *e2 == '\0' && c > 0 && c <= UINT32_MAX && r < c;
+        if (ok) {
+            g_shard_rank = (uint32_t)r;
+            g_shard_count = (uint32_t)c;
+        } else {
+            fprintf(stderr, "libstorm_hip: STORM_HIP_SHARD: \"%s\" ignored (rank/world expected, rank < world)\n", shard);
+        }
     }
     __atomic_store_n(&g_n_devices, n_devices, __ATOMIC_RELEASE); /* last: readers take the fast path from here on */
 }
@@ -208,19 +236,28 @@ static int remember_host_option(const char* key, int64_t value) {
 static void read_env_options_once(void) {
     const char* e = getenv("STORM_HIP_OPTIONS");
     if (!e) return;
-    char buf[512];
-    snprintf(buf, sizeof(buf), "%s", e);
+    /* the copy is as long as the string (a fixed 512-byte buffer used to cut a longer one mid-entry, and the cut entry,
+     * "k2_max_run=40" of "=4096", passed the check and was applied) */
+    char* buf = strdup(e);
+    if (!buf) {
+        fprintf(stderr, "libstorm_hip: STORM_HIP_OPTIONS: ignored (out of memory)\n");
+        return;
+    }
     char* save = NULL;
     for (char* tok = strtok_r(buf, ",", &save); tok; tok = strtok_r(NULL, ",", &save)) {
         char* eq = strchr(tok, '=');
         if (eq) *eq = '\0';
         char* end = NULL;
         const long long v = eq ? strtoll(eq + 1, &end, 10) : 0;
-        if (!eq || end == eq + 1 || *end != '\0' || storm_hip_option_check(tok, v) != STORM_HIP_OK ||
-            remember_host_option(tok, v) != 0)
-            fprintf(stderr, "libstorm_hip: STORM_HIP_OPTIONS: entry \"%s%s%s\" ignored%s%s\n", tok, eq ? "=" : "", eq ? eq + 1 : "",
-                    eq ? ": " : " (key=value expected)", eq ? storm_hip_last_error() : "");
+        const char* why = NULL;
+        if (!eq) why = "key=value expected";
+        else if (end == eq + 1 || *end != '\0') why = "the value is not a decimal number";
+        else if (storm_hip_option_check(tok, v) != STORM_HIP_OK) why = storm_hip_last_error();
+        else if (remember_host_option(tok, v) != 0) why = "more options than the library remembers";
+        if (why)
+            fprintf(stderr, "libstorm_hip: STORM_HIP_OPTIONS: entry \"%s%s%s\" ignored: %s\n", tok, eq ? "=" : "", eq ? eq + 1 : "", why);
     }
+    free(buf);
 }
 static void read_env_options(void) { pthread_once(&g_env_opts_once, read_env_options_once); }
 
@@ -342,9 +379,13 @@ static int run_on_devices(slot_fn fn, void* arg, const char* what) {
     pthread_mutex_unlock(&g_pool.mu);
     for (int d = 1; d < n; ++d)
         if (g_pool.rc[d]) {
-            g_host_error[0] = '\0';
             fprintf(stderr, "[storm_hip] %s (device slot %d): %s\n", what, d, g_pool.err[d]);
-            if (!rc0) rc0 = g_pool.rc[d];
+            /* the device library's last error is per thread: the worker's text is not what storm_hip_last_error() gives the
+             * caller, so STORM_hip_error() gets it from here (the first failure's; slot 0's own is already the caller's) */
+            if (!rc0) {
+                snprintf(g_host_error, sizeof(g_host_error), "%s (device slot %d): %s", what, d, g_pool.err[d]);
+                rc0 = g_pool.rc[d];
+            }
         }
     return rc0;
 }

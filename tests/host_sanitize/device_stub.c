@@ -3,17 +3,63 @@
  * marshalling towards the device) can run under AddressSanitizer / UBSan on a machine without a
  * GPU. It computes no pair counts: the "totals" it returns are the number of set bits that
  * reached it, which the driver compares with what it fed in. Never linked into the product. */
+#include <pthread.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include "stub_dosage.h"   /* struct storm_hip_matrix_s: host memory */
+#include "stub_hooks.h"
 
 struct storm_hip_ctx_s { int device; uint64_t pending; };
 struct storm_hip_sparse_s { uint64_t set_bits; };
 
-static const char* g_err = "";
+static __thread const char* g_err = "";   /* per calling thread, like the library's */
 const char* storm_hip_last_error(void) { return g_err; }
+
+/* stub_hooks.h: which thread launched each shard of the passes since stub_hook_caller(), and one launch made to fail */
+static pthread_mutex_t g_hook_mu = PTHREAD_MUTEX_INITIALIZER;
+static pthread_t g_hook_caller;
+static int g_hook_on = 0, g_hook_driver[64], g_hook_square_foreign = 0, g_hook_fail_rank = -1;
+void stub_hook_caller(void) {
+    pthread_mutex_lock(&g_hook_mu);
+    g_hook_caller = pthread_self();
+    g_hook_on = 1;
+    memset(g_hook_driver, 0, sizeof(g_hook_driver));
+    g_hook_square_foreign = 0;
+    pthread_mutex_unlock(&g_hook_mu);
+}
+int stub_hook_driver(uint32_t shard_rank) {
+    pthread_mutex_lock(&g_hook_mu);
+    const int v = shard_rank < 64 ? g_hook_driver[shard_rank] : 0;
+    pthread_mutex_unlock(&g_hook_mu);
+    return v;
+}
+int stub_hook_square_foreign(void) {
+    pthread_mutex_lock(&g_hook_mu);
+    const int v = g_hook_square_foreign;
+    pthread_mutex_unlock(&g_hook_mu);
+    return v;
+}
+void stub_hook_fail_launch(int shard_rank) {
+    pthread_mutex_lock(&g_hook_mu);
+    g_hook_fail_rank = shard_rank;
+    pthread_mutex_unlock(&g_hook_mu);
+}
+/* a launch of shard `shard_rank` on the calling thread: noted; STORM_HIP_EINVAL if it is the one to fail (once) */
+static int hook_launch(uint32_t shard_rank) {
+    int rc = STORM_HIP_OK;
+    pthread_mutex_lock(&g_hook_mu);
+    if (g_hook_on && shard_rank < 64)
+        g_hook_driver[shard_rank] |= pthread_equal(pthread_self(), g_hook_caller) ? STUB_DRIVER_CALLER : STUB_DRIVER_OTHER;
+    if (g_hook_fail_rank >= 0 && (uint32_t)g_hook_fail_rank == shard_rank) {
+        g_hook_fail_rank = -1;
+        g_err = "stub: injected launch failure";
+        rc = STORM_HIP_EINVAL;
+    }
+    pthread_mutex_unlock(&g_hook_mu);
+    return rc;
+}
 int storm_hip_device_count(void) { return 1; }
 
 int storm_hip_ctx_create(int device, void* stream, storm_hip_ctx_t** out) {
@@ -93,7 +139,7 @@ int storm_hip_pairw_dense_begin(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* 
                                 uint32_t shard_rank, uint32_t shard_count) {
     if (shard_rank >= shard_count) return STORM_HIP_EINVAL;
     ctx->pending = shard_rank == 0 ? set_bits_of(m) : 0;
-    return STORM_HIP_OK;
+    return hook_launch(shard_rank);
 }
 int storm_hip_pairw_dense_end(storm_hip_ctx_t* ctx, uint64_t* h_total) {
     *h_total = ctx->pending;
@@ -108,7 +154,18 @@ int storm_hip_pairw_dense_upload(storm_hip_ctx_t* ctx, storm_hip_matrix_t* m, co
 int storm_hip_square_dense(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* a,
                            const storm_hip_matrix_t* b, uint64_t* h_total) {
     (void)ctx;
-    *h_total = set_bits_of(a) + set_bits_of(b);
+    /* (the product itself, small as the drivers' shapes are: the host splits A's rows over the device slots, and only a
+     * value that adds up over those slices is the same for every number of slots) */
+    if (a->n_words != b->n_words) return STORM_HIP_EINVAL;
+    uint64_t t = 0;
+    for (uint64_t i = 0; i < a->n_rows; ++i)
+        for (uint64_t j = 0; j < b->n_rows; ++j)
+            for (uint32_t k = 0; k < a->n_words; ++k)
+                t += (uint64_t)__builtin_popcountll(a->rows[i * a->n_words + k] & b->rows[j * b->n_words + k]);
+    *h_total = t;
+    pthread_mutex_lock(&g_hook_mu);
+    if (g_hook_on && !pthread_equal(pthread_self(), g_hook_caller)) ++g_hook_square_foreign;
+    pthread_mutex_unlock(&g_hook_mu);
     return STORM_HIP_OK;
 }
 int storm_hip_pairw_matrix_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, int op, uint32_t* d_out,
@@ -268,7 +325,7 @@ int storm_hip_pairw_sparse_begin(storm_hip_ctx_t* ctx, const storm_hip_sparse_t*
                                  uint32_t shard_count) {
     if (shard_rank >= shard_count) return STORM_HIP_EINVAL;
     ctx->pending = shard_rank == 0 ? s->set_bits : 0;
-    return STORM_HIP_OK;
+    return hook_launch(shard_rank);
 }
 int storm_hip_pairw_sparse_end(storm_hip_ctx_t* ctx, uint64_t* h_total) {
     *h_total = ctx->pending;
