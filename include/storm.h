@@ -658,6 +658,47 @@ int STORM_dosage_lag_prune_complete(STORM_dosage_t* h, float min_r2, uint64_t ma
 int STORM_dosage_lag_prune_complete_device(STORM_dosage_t* h, float min_r2, uint64_t max_lag, const double* pos, double max_dist,
                                            const float* priority, uint8_t* d_keep, uint32_t* d_owner, uint64_t out_len);
 
+/* The sparse LD report, compacted on the device: the pairs of STORM_dosage_pairw_lag_corr's n x L matrix whose r^2 passes a
+ * threshold (PLINK's --r2 --ld-window N --ld-window-kb K --ld-window-r2 T), instead of the matrix. The list is exactly the
+ * edge set STORM_dosage_lag_prune above walks, forward pairs only (i < j):
+ *   listed    i < j with j - i <= L = min(max_lag, n - 1), j in i's window — pos == NULL: the lag alone; pos given (n doubles,
+ *             HOST memory in every form): the windows, max_lag 0 and the refusal of a max_lag the windows exceed as in
+ *             STORM_dosage_lag_prune — and rho > min_r2, where rho is the FLOAT STORM_dosage_pairw_lag_corr[_complete] writes
+ *             for the pair under STORM_DOSAGE_R2. The comparison is between floats and STRICT: a pair exactly at the
+ *             threshold is NOT listed (PLINK's filter is >=: pass the next float below T for that), and a NaN rho is never
+ *             listed. A negative min_r2 lists every pair of the window whose rho is a number.
+ *   layout    CSR: row i's pairs are col[row_start[i] .. row_start[i + 1]), col holds j ascending within a row, val the
+ *             pair's rho — the same 32 bits as out[i * ld + (j - i - 1)] of the corr call. row_start has n + 1 entries of 64
+ *             bits (out_rows >= n + 1 is its length), row_start[n] is the total; col is 32 bits.
+ *   capacity  the length of col and val. col == NULL && val == NULL with capacity 0 is the count-only call: row_start and
+ *             *n_pairs alone. Host forms: a total above capacity returns -4 with row_start and *n_pairs valid, col / val
+ *             unspecified, and the message naming both numbers. _device forms (d_row_start, d_col, d_val in DEVICE memory;
+ *             no n_pairs): they return with their work queued and cannot know the total — d_row_start always holds the true
+ *             offsets, only the first `capacity` pairs in (i, j) order are written, nothing is ever written at or beyond
+ *             index capacity, and the caller compares d_row_start[n] with capacity. A _device form given pos waits before it
+ *             returns (its windows are freed on return); without pos its outputs are final once the work queued on the
+ *             container's stream is.
+ * With no row, row_start[0] = 0 is written where out_rows >= 1; with one row, row_start[0] = row_start[1] = 0; the host
+ * forms ask no device for either. There is no limit of STORM_PRUNE_MAX_ROWS rows here. Two calls on unchanged rows return
+ * identical bytes. Device scratch: the n x L floats of r^2, n x ceil(L / 64) 64-bit mask words, and for a host form the staged
+ * list; no CPU fallback. One device slot and one process.
+ * Returns 0; -1 NULL handle, -2 NULL row_start (host forms: or NULL n_pairs), exactly one of col / val NULL, or a capacity
+ * without them, -3 max_lag 0 without positions (said before the size check), -4 out_rows < n + 1 (nothing is written), -3 a
+ * NaN min_r2, a negative or NaN max_dist, a position that is not finite or decreases, windows that need more than max_lag
+ * (the message names both numbers), or a device failure (STORM_hip_error says which), -4 a capacity below the total (host
+ * forms), -5 several device slots in view. */
+int STORM_dosage_lag_corr_sparse(STORM_dosage_t* h, float min_r2, uint64_t max_lag, const double* pos, double max_dist,
+                                 uint64_t* row_start, uint64_t out_rows, uint32_t* col, float* val, uint64_t capacity,
+                                 uint64_t* n_pairs);
+int STORM_dosage_lag_corr_sparse_device(STORM_dosage_t* h, float min_r2, uint64_t max_lag, const double* pos, double max_dist,
+                                        uint64_t* d_row_start, uint64_t out_rows, uint32_t* d_col, float* d_val, uint64_t capacity);
+int STORM_dosage_lag_corr_sparse_complete(STORM_dosage_t* h, float min_r2, uint64_t max_lag, const double* pos, double max_dist,
+                                          uint64_t* row_start, uint64_t out_rows, uint32_t* col, float* val, uint64_t capacity,
+                                          uint64_t* n_pairs);
+int STORM_dosage_lag_corr_sparse_complete_device(STORM_dosage_t* h, float min_r2, uint64_t max_lag, const double* pos,
+                                                 double max_dist, uint64_t* d_row_start, uint64_t out_rows, uint32_t* d_col,
+                                                 float* d_val, uint64_t capacity);
+
 /* ------------------------------------------------------------- extensions (not in ref) ---
  * Device selection for the entry points above. By default device 0 computes everything.
  * STORM_hip_set_devices(n, ids): the pair space is sharded over the listed GPUs of this node

@@ -63,10 +63,11 @@ int storm_hip_device_pci_bus_id(int device, char* buf, size_t buflen);
  *       every `_launch` (storm_hip_pairw_dense_launch), every `_begin` (storm_hip_pairw_dense_begin, _pairw_sparse_begin,
  *       _pairw_matrix_band_begin), the primitives that say so (storm_hip_similarity_finish_device, _finish_lag_device,
  *       storm_hip_topk_rows_device, storm_hip_dosage_finish_lag_device, storm_hip_lag_band_sums_device,
- *       storm_hip_lag_band_annot_sums_device, storm_hip_lag_band_prune_device), and the `_device` forms of the calls composed of
- *       them: storm_hip_lag_dosage_ldscore[_complete]_device, storm_hip_lag_dosage_ldscore_annot[_complete]_device and
- *       storm_hip_lag_dosage_prune[_complete]_device — unlike storm_hip_pairw_lag_dosage_*_device, whose band they reduce and
- *       which are complete on return.
+ *       storm_hip_lag_band_annot_sums_device, storm_hip_lag_band_prune_device, storm_hip_lag_band_sparse_device), and the
+ *       `_device` forms of the calls composed of them: storm_hip_lag_dosage_ldscore[_complete]_device,
+ *       storm_hip_lag_dosage_ldscore_annot[_complete]_device, storm_hip_lag_dosage_prune[_complete]_device and
+ *       storm_hip_lag_dosage_corr_sparse[_complete]_device — unlike storm_hip_pairw_lag_dosage_*_device, whose band they
+ *       reduce and which are complete on return.
  *     A `_begin` is finished by its `_end` on the same context, whatever stream the context has by then.
  *   - HOST arrays handed to an asynchronous call (h_lo, h_hi, h_order of the LD-score and pruning calls, in every form) are
  *     read by copies queued on the context's stream: they must stay allocated and unchanged until that work is complete
@@ -655,6 +656,51 @@ int storm_hip_lag_dosage_prune_complete_device(storm_hip_ctx_t* ctx, const storm
 int storm_hip_lag_dosage_prune_complete(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint64_t max_lag,
                                         float min_r2, const uint32_t* h_lo, const uint32_t* h_hi, const uint32_t* h_order,
                                         uint8_t* h_keep, uint32_t* h_owner);
+
+/* ---- the sparse pair list of a band in the lag layout, compacted on the device ------------------------------------------
+ * storm_hip_lag_band_sparse_device: d_vals is any float matrix in the lag layout in DEVICE memory, as in
+ *   storm_hip_lag_band_prune_device, and a pair i < j is LISTED exactly when it is adjacent there: j - i <= L =
+ *   min(max_lag, n_rows - 1), j <= h_hi[i] and i >= h_lo[j] (both NULL: the lag alone), and d_vals' float of the pair >
+ *   min_r2, compared as floats, strictly (a NaN float is never listed; a negative min_r2 lists every pair that is a number).
+ *   The output is CSR over the forward pairs, in DEVICE memory:
+ *     d_row_start[0 .. n_rows]  uint64: row i's pairs are the slots [d_row_start[i], d_row_start[i + 1]); [n_rows] the total,
+ *     d_col[s]                  uint32: j, ascending within a row,
+ *     d_val[s]                  the very float of d_vals (the same 32 bits).
+ *   d_row_start always holds the true offsets. Only the slots below `capacity` are written — the first `capacity` pairs in
+ *   (i, j) order — and nothing is written at or behind d_col[capacity] / d_val[capacity]: the caller compares
+ *   d_row_start[n_rows] with capacity. d_col and d_val NULL with capacity 0 is the count-only call. h_lo / h_hi are HOST
+ *   arrays of n_rows uint32; the corner and the pitch columns of d_vals are never read. Five plain launches
+ *   (lag_band_sparse_count_kernel: one 64-bit forward mask word per 64 lags and one count per row, the band read once;
+ *   three launches of a reduce-then-scan over the counts; lag_band_sparse_fill_kernel: reads the masks and, of the band, the
+ *   listed entries only), no atomics and nothing that waits for another workgroup: two calls return the same bytes. Device
+ *   scratch in the context's band buffer: n x ceil(L / 64) 64-bit words of masks, a 64-bit sum per 1024 rows, n words of
+ *   counts, 2 n words of bounds. Queued on the context's stream; no host wait: h_lo / h_hi must stay unchanged until that
+ *   work is complete (storm_hip_ctx_synchronize). Fewer than two rows: d_row_start[0 .. n_rows] = 0. The LD r^2 of
+ *   storm_hip_pairw_lag_similarity_device goes through the same call.
+ * storm_hip_lag_dosage_corr_sparse[_complete][_device]: rows of 2-bit dosages: the band of r^2 as in
+ *   storm_hip_lag_dosage_ldscore[_complete] into the context's band buffer, then the kernels above. The _device forms take
+ *   d_row_start / d_col / d_val in device memory and return with everything queued. The host forms stage the list behind the
+ *   band (min(capacity, n L) entries), copy the offsets back, wait, write the total to *h_n_pairs (may be NULL) and copy
+ *   exactly that many entries of col and val; a total above capacity is STORM_HIP_EINVAL with h_row_start and *h_n_pairs
+ *   valid and the message naming both numbers.
+ * STORM_HIP_EINVAL: NULL context, band / matrix or row_start, max_lag 0, ld < L, (dosage forms: rows of more than 2^24 values,
+ * n_samples that does not match the row width,) one of lo / hi without the other, one of col / val without the other or a
+ * capacity without them, 2^32 rows or more, a NaN min_r2. STORM_HIP_ENOMEM names the buffer. */
+int storm_hip_lag_band_sparse_device(storm_hip_ctx_t* ctx, const float* d_vals, uint64_t ld, uint64_t n_rows, uint64_t max_lag,
+                                     float min_r2, const uint32_t* h_lo, const uint32_t* h_hi, uint64_t* d_row_start,
+                                     uint32_t* d_col, float* d_val, uint64_t capacity);
+int storm_hip_lag_dosage_corr_sparse_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint64_t max_lag,
+                                            float min_r2, const uint32_t* h_lo, const uint32_t* h_hi, uint64_t* d_row_start,
+                                            uint32_t* d_col, float* d_val, uint64_t capacity);
+int storm_hip_lag_dosage_corr_sparse(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint64_t max_lag,
+                                     float min_r2, const uint32_t* h_lo, const uint32_t* h_hi, uint64_t* h_row_start, uint32_t* h_col,
+                                     float* h_val, uint64_t capacity, uint64_t* h_n_pairs);
+int storm_hip_lag_dosage_corr_sparse_complete_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples,
+                                                     uint64_t max_lag, float min_r2, const uint32_t* h_lo, const uint32_t* h_hi,
+                                                     uint64_t* d_row_start, uint32_t* d_col, float* d_val, uint64_t capacity);
+int storm_hip_lag_dosage_corr_sparse_complete(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint64_t max_lag,
+                                              float min_r2, const uint32_t* h_lo, const uint32_t* h_hi, uint64_t* h_row_start,
+                                              uint32_t* h_col, float* h_val, uint64_t capacity, uint64_t* h_n_pairs);
 
 /* sum_c C(n_c,2) on the device — verification identity only, never the product
  * path: used by tests at sizes where a CPU pairwise oracle is infeasible */

@@ -184,7 +184,12 @@ SIGNATURES = {
     "storm_hip_lag_dosage_prune": (C.c_int, [vp, vp, u64, u64, C.c_float, vp, vp, vp, vp, vp]),
     "storm_hip_lag_dosage_prune_complete_device": (C.c_int, [vp, vp, u64, u64, C.c_float, vp, vp, vp, vp, vp]),
     "storm_hip_lag_dosage_prune_complete": (C.c_int, [vp, vp, u64, u64, C.c_float, vp, vp, vp, vp, vp]),
-    "storm_hip_matrix_create_from_blocks_wide": (C.c_int, [vp, u64, u64, vp, vp, vp, vp, vp, u32, P(vp)]),
+    "storm_hip_lag_band_sparse_device": (C.c_int, [vp, vp, u64, u64, u64, C.c_float, vp, vp, vp, vp, vp, u64]),
+    "storm_hip_lag_dosage_corr_sparse_device": (C.c_int, [vp, vp, u64, u64, C.c_float, vp, vp, vp, vp, vp, u64]),
+    "storm_hip_lag_dosage_corr_sparse": (C.c_int, [vp, vp, u64, u64, C.c_float, vp, vp, vp, vp, vp, u64, vp]),
+    "storm_hip_lag_dosage_corr_sparse_complete_device": (C.c_int, [vp, vp, u64, u64, C.c_float, vp, vp, vp, vp, vp, u64]),
+    "storm_hip_lag_dosage_corr_sparse_complete": (C.c_int, [vp, vp, u64, u64, C.c_float, vp, vp, vp, vp, vp, u64, vp]),
+    "storm_hip_matrix_create_from_blocks_wide":(C.c_int, [vp, u64, u64, vp, vp, vp, vp, vp, u32, P(vp)]),
     "storm_hip_pairw_sparse_begin": (C.c_int, [vp, vp, u32, u32]),
     "storm_hip_pairw_sparse_end": (C.c_int, [vp, P(u64)]),
     "storm_hip_sparse_last_census": (C.c_int, [vp, P(u64 * 4)]),
@@ -303,6 +308,10 @@ SIGNATURES = {
     "STORM_dosage_lag_prune_device": (C.c_int, [vp, C.c_float, u64, vp, C.c_double, vp, vp, vp, u64]),
     "STORM_dosage_lag_prune_complete": (C.c_int, [vp, C.c_float, u64, vp, C.c_double, vp, vp, vp, u64]),
     "STORM_dosage_lag_prune_complete_device": (C.c_int, [vp, C.c_float, u64, vp, C.c_double, vp, vp, vp, u64]),
+    "STORM_dosage_lag_corr_sparse": (C.c_int, [vp, C.c_float, u64, vp, C.c_double, vp, u64, vp, vp, u64, vp]),
+    "STORM_dosage_lag_corr_sparse_device": (C.c_int, [vp, C.c_float, u64, vp, C.c_double, vp, u64, vp, vp, u64]),
+    "STORM_dosage_lag_corr_sparse_complete": (C.c_int, [vp, C.c_float, u64, vp, C.c_double, vp, u64, vp, vp, u64, vp]),
+    "STORM_dosage_lag_corr_sparse_complete_device": (C.c_int, [vp, C.c_float, u64, vp, C.c_double, vp, u64, vp, vp, u64]),
     "STORM_hip_set_option": (C.c_int, [C.c_char_p, C.c_int64]),
     "STORM_contig_pairw_matrix_device": (C.c_int, [vp, C.c_int, vp, u64, u64]),
     "STORM_serialize": (u64, [vp, vp, u64]),

@@ -575,6 +575,52 @@ class StormDosage:
                                                        _ptr(own) if owner else None, n)))
         return (keep[:n], own[:n]) if owner else keep[:n]
 
+    def lag_corr_sparse(self, min_r2: float, max_lag: Optional[int] = None, pos=None, max_dist: Optional[float] = None,
+                        complete: bool = False, capacity: Optional[int] = None, device=None):
+        """STORM_dosage_lag_corr_sparse[_complete]: (row_start [n_rows + 1] uint64, col uint32, val float32): the pairs i < j
+        within max_lag rows (and, with pos and max_dist, within that distance, as lag_prune) whose r2 — pairw_lag_corr's
+        float, complete=True: pairw_lag_corr_complete's — is > min_r2, compacted on the device: row i's pairs are
+        col[row_start[i]:row_start[i + 1]], ascending, val their r2 (the same bits), row_start[-1] the total. Strict: a pair
+        exactly at min_r2 is not listed (PLINK's filter is >=), a NaN never; a negative min_r2 lists every pair that is a number.
+        capacity=None makes the count-only call and then the exact fill, which COSTS THE BAND TWICE; given a capacity, one
+        call is made and a RuntimeError names the total when the capacity is too small.
+        device=: (row_start, col, val) — 1-D contiguous torch tensors in device memory of 64-bit, 32-bit and float32 entries,
+        row_start at least n_rows + 1 long, col and val of one length, the capacity (both None: the offsets alone) — receive
+        the list instead: only the first len(col) pairs are written, row_start always holds the true offsets, and the caller
+        compares row_start[n_rows] with len(col). Complete on return with pos, queued on the container's stream without;
+        returns None."""
+        n = self.n_rows
+        name = "STORM_dosage_lag_corr_sparse_complete" if complete else "STORM_dosage_lag_corr_sparse"
+        lag, p_ptr, dist = _window_args(n, max_lag, pos, max_dist)
+        if device is not None:
+            d_rows, d_col, d_val = device
+            _device_vector(d_rows, "device=: row_start is a 1-D contiguous tensor of 64-bit entries in device memory", 8)
+            for t in (d_col, d_val):
+                _device_vector(t, "device=: col and val are 1-D contiguous tensors of 32-bit entries in device memory")
+            if d_rows is None or (d_col is None) != (d_val is None) or (d_col is not None and d_col.shape[0] != d_val.shape[0]):
+                raise ValueError("device=: row_start, and col and val of one length or both None")
+            self._check(name + "_device",
+                        int(getattr(self._lib, name + "_device")(self._h, float(min_r2), lag, p_ptr, dist, C.c_void_p(d_rows.data_ptr()),
+                                                                 int(d_rows.shape[0]),
+                                                                 None if d_col is None else C.c_void_p(d_col.data_ptr()),
+                                                                 None if d_val is None else C.c_void_p(d_val.data_ptr()),
+                                                                 0 if d_col is None else int(d_col.shape[0]))))
+            return None
+        rows = np.zeros(n + 1, dtype=np.uint64)
+        total = C.c_uint64(0)
+        if capacity is None:
+            self._check(name, int(getattr(self._lib, name)(self._h, float(min_r2), lag, p_ptr, dist, _ptr(rows), n + 1, None, None, 0,
+                                                           C.byref(total))))
+            capacity = int(total.value)
+        capacity = int(capacity)
+        col, val = np.zeros(max(capacity, 1), dtype=np.uint32), np.zeros(max(capacity, 1), dtype=np.float32)
+        rc = int(getattr(self._lib, name)(self._h, float(min_r2), lag, p_ptr, dist, _ptr(rows), n + 1, _ptr(col), _ptr(val), capacity,
+                                          C.byref(total)))
+        if rc == -4 and int(total.value) > capacity:
+            raise RuntimeError(f"{name}: {int(total.value)} pairs are listed, capacity is {capacity}")
+        self._check(name, rc)
+        return rows, col[:int(total.value)], val[:int(total.value)]
+
     def ldscore_window_lag(self, pos, max_dist: float) -> int:
         """STORM_ldscore_window_lag: the lag the windows of these coordinates need under max_dist (host only)."""
         p = np.ascontiguousarray(pos, dtype=np.float64)
@@ -898,6 +944,25 @@ class HipContext:
                                                         None if d_owner is None else C.c_void_p(d_owner)),
               "storm_hip_lag_band_prune_device")
         self.synchronize()   # (lo / hi / order are this call's own copies: they must outlive the upload)
+
+    def lag_band_sparse_device(self, d_vals: int, ld: int, n_rows: int, max_lag: int, min_r2: float, d_row_start: int,
+                               d_col: Optional[int] = None, d_val: Optional[int] = None, capacity: int = 0,
+                               lo: Optional[np.ndarray] = None, hi: Optional[np.ndarray] = None, wait: bool = True) -> None:
+        """storm_hip_lag_band_sparse_device: the pairs of a float band in the lag layout at d_vals (n_rows rows of pitch ld,
+        device memory) that lag_band_prune_device calls adjacent, as a CSR list in device memory: d_row_start (n_rows + 1
+        uint64: the true offsets, the total last), d_col / d_val (uint32 j ascending / the band's float; both None with
+        capacity 0: the offsets alone). Only the first `capacity` pairs are written. lo / hi: host uint32 arrays, both or
+        neither. The C call returns with its work queued and the host arrays still to be read; this wrapper owns their copies
+        and waits (wait=False, without lo / hi only: queued on the context's stream)."""
+        u32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.uint32)
+        lo, hi = u32(lo), u32(hi)
+        opt = lambda a: None if a is None else _ptr(a if a.size else np.zeros(1, np.uint32))
+        dev = lambda p: None if p is None else C.c_void_p(p)
+        check(self._lib.storm_hip_lag_band_sparse_device(self._h, dev(d_vals), ld, n_rows, max_lag, float(min_r2), opt(lo), opt(hi),
+                                                         dev(d_row_start), dev(d_col), dev(d_val), capacity),
+              "storm_hip_lag_band_sparse_device")
+        if wait or lo is not None or hi is not None:
+            self.synchronize()   # (lo / hi are this call's own copies: they must outlive the upload)
 
     def matrix(self, n_rows: int, n_words: int) -> "HipMatrix":
         return HipMatrix(self, n_rows, n_words)
@@ -1223,6 +1288,42 @@ class HipMatrix:
         check(getattr(self._lib, name)(self.ctx._h, self._h, n_samples, max_lag, float(min_r2), _ptr(lo), _ptr(hi), _ptr(order),
                                        C.c_void_p(d_keep), None if d_owner is None else C.c_void_p(d_owner)), name)
         self.ctx.synchronize()   # (lo / hi / order are this call's own copies: they must outlive the upload)
+
+    def lag_dosage_corr_sparse(self, min_r2: float, max_lag: int, n_samples: int, complete: bool = False,
+                               capacity: Optional[int] = None, lo: Optional[np.ndarray] = None, hi: Optional[np.ndarray] = None):
+        """storm_hip_lag_dosage_corr_sparse[_complete]: (row_start [n_rows + 1] uint64, col uint32, val float32): the pairs
+        within max_lag (and within [lo, hi], host uint32 arrays, both or neither) whose r2 is > min_r2, CSR over the forward
+        pairs. capacity=None: the count-only call, then the exact fill (the band twice); else one call, and a RuntimeError
+        naming the total where the capacity is too small."""
+        name = "storm_hip_lag_dosage_corr_sparse_complete" if complete else "storm_hip_lag_dosage_corr_sparse"
+        n = self.n_rows
+        u32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.uint32)
+        lo, hi = u32(lo), u32(hi)
+        rows, total = np.zeros(n + 1, dtype=np.uint64), C.c_uint64(0)
+        call = lambda c, v, cap: getattr(self._lib, name)(self.ctx._h, self._h, n_samples, max_lag, float(min_r2), _ptr(lo), _ptr(hi),
+                                                          _ptr(rows), c, v, cap, C.byref(total))
+        if capacity is None:
+            check(call(None, None, 0), name)
+            capacity = int(total.value)
+        col, val = np.zeros(max(capacity, 1), dtype=np.uint32), np.zeros(max(capacity, 1), dtype=np.float32)
+        check(call(_ptr(col), _ptr(val), int(capacity)), name)
+        return rows, col[:int(total.value)], val[:int(total.value)]
+
+    def lag_dosage_corr_sparse_device(self, d_row_start: int, d_col: Optional[int], d_val: Optional[int], capacity: int, min_r2: float,
+                                      max_lag: int, n_samples: int, complete: bool = False, lo: Optional[np.ndarray] = None,
+                                      hi: Optional[np.ndarray] = None, wait: bool = True) -> None:
+        """Same, into buffers in device memory (d_col / d_val None with capacity 0: the offsets alone); only the first
+        `capacity` pairs are written. lo / hi stay host arrays. The C call returns with its work queued and the host arrays
+        still to be read; this wrapper owns their copies and waits (wait=False, without lo / hi only: queued on the
+        context's stream)."""
+        name = "storm_hip_lag_dosage_corr_sparse_complete_device" if complete else "storm_hip_lag_dosage_corr_sparse_device"
+        u32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.uint32)
+        lo, hi = u32(lo), u32(hi)
+        dev = lambda p: None if p is None else C.c_void_p(p)
+        check(getattr(self._lib, name)(self.ctx._h, self._h, n_samples, max_lag, float(min_r2), _ptr(lo), _ptr(hi), dev(d_row_start),
+                                       dev(d_col), dev(d_val), capacity), name)
+        if wait or lo is not None or hi is not None:
+            self.ctx.synchronize()   # (lo / hi are this call's own copies: they must outlive the upload)
 
     def pairw_topk(self, k: int, score: str = "jaccard", n_bits: int = 1, panel_rows: int = 0):
         """(idx [n_rows, k] uint32, val [n_rows, k] float32, or uint32 for score "count"): for each row its k best other rows,

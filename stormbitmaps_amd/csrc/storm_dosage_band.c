@@ -71,6 +71,7 @@ int storm_dosage_band_result(storm_hip_ctx_t* ctx, int rc, int device, const cha
     /* The one place that asks for the wait. A _device form of the LD scores, the stratified scores and pruning returns with
      * its work queued while lo / hi / order, host arrays its caller here frees on return, are still being read, and a caller
      * of storm.h has no handle on that stream: it is waited for. Every other _device form leaves no host array of the
-     * library's behind it, passes wait 0 and returns with its work queued. */
+     * library's behind it, passes wait 0 and returns with its work queued — as does the sparse list's _device form where it
+     * was given no positions (storm_dosage_lag_sparse.c passes `device` only with windows). */
     return storm_host_shim_result(ctx, rc, device, name);
 }

@@ -771,6 +771,63 @@ static int lag_dosage_prune(storm_hip_ctx_t* ctx, const char* who, const storm_h
     return STORM_HIP_OK;
 }
 
+// ---- the sparse pair list: the band, then the kernels of storm_hip_lag_sparse.hip over it ----
+// Tail, from the next 8-byte boundary (n x lag words can be odd): the forward masks, the blocks' sums, the rows' counts and the
+// window bounds (h_lo / h_hi are HOST arrays of n entries in every form, or NULL; the launcher lays them out and sends them)
+// and, for a host form, again from an 8-byte boundary, the n + 1 offsets and min(capacity, n x lag) staged (col, val) entries
+// on their way back. All queued on ctx->stream; the host form alone waits: it reads the total, refuses a capacity below it
+// (row_start and *n_pairs are valid then) and otherwise copies exactly `total` entries of col and val.
+static int lag_dosage_corr_sparse(storm_hip_ctx_t* ctx, const char* who, const storm_hip_matrix_s* m, uint64_t n_samples,
+                                  uint64_t max_lag, float min_r2, bool complete, const uint32_t* h_lo, const uint32_t* h_hi,
+                                  uint64_t* row_start, uint32_t* col, float* val, uint64_t capacity, uint64_t* h_n_pairs, bool host) {
+    uint64_t lag = 0;
+    if (int rc = check_lag_dosage(who, m, row_start, max_lag, ~0ull, &lag)) return rc;
+    if (int rc = check_samples(who, m, n_samples)) return rc;
+    const uint64_t n = m->n_rows;
+    if (int rc = check_lag_band_sparse(who, n, h_lo, h_hi, min_r2, col, val, capacity)) return rc;
+    STORM_HIP_TRY(hipSetDevice(ctx->device));
+    if (n < 2) {   // no pair: the offsets alone, n + 1 zeros; no band, no kernel
+        if (host) {
+            for (uint64_t i = 0; i <= n; ++i) row_start[i] = 0;
+            if (h_n_pairs) *h_n_pairs = 0;
+            return STORM_HIP_OK;
+        }
+        STORM_HIP_TRY(hipMemsetAsync(row_start, 0, (n + 1) * sizeof(uint64_t), ctx->stream));
+        return STORM_HIP_OK;
+    }
+    const size_t pad = ((size_t)n * lag) & 1u;
+    const size_t scratch = (lag_band_sparse_scratch_words(n, lag, h_lo != nullptr) + 1u) & ~(size_t)1u;
+    const uint64_t staged = col ? std::min<uint64_t>(capacity, n * lag) : 0;
+    LagR2Band b;
+    if (int rc = lag_dosage_r2_band(ctx, m, n_samples, max_lag, lag, complete,
+                                    pad + scratch + (host ? 2 * (size_t)(n + 1) + 2 * (size_t)staged : 0),
+                                    "lag_dosage_corr_sparse: the band of r^2, the forward masks and the list", &b))
+        return rc;
+    uint32_t* const d_scratch = b.tail + pad;
+    uint64_t* const d_row_start = host ? reinterpret_cast<uint64_t*>(d_scratch + scratch) : row_start;
+    uint32_t* const d_col = host ? (col ? d_scratch + scratch + 2 * (size_t)(n + 1) : nullptr) : col;
+    float* const d_val = host ? (col ? reinterpret_cast<float*>(d_col + staged) : nullptr) : val;
+    if (int rc = launch_lag_band_sparse(ctx, reinterpret_cast<const float*>(b.band), lag, n, lag, min_r2, h_lo, h_hi, d_row_start,
+                                        d_col, d_val, host ? staged : capacity, d_scratch))
+        return rc;
+    if (!host) return STORM_HIP_OK;
+    STORM_HIP_TRY(hipMemcpyAsync(row_start, d_row_start, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const uint64_t total = row_start[n];
+    if (h_n_pairs) *h_n_pairs = total;
+    if (!col) return STORM_HIP_OK;
+    if (total > capacity) {
+        set_error("%s: %llu pairs are listed, capacity is %llu", who, (unsigned long long)total, (unsigned long long)capacity);
+        return STORM_HIP_EINVAL;
+    }
+    if (total) {
+        STORM_HIP_TRY(hipMemcpyAsync(col, d_col, total * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        STORM_HIP_TRY(hipMemcpyAsync(val, d_val, total * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        STORM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    return STORM_HIP_OK;
+}
+
 // ---- the per-pair matrix calls: one body for the device form and the host form of each (pair_matrix_out, storm_hip_internal.h) ----
 // A triangle of n x n entries, cleared in the band buffer (entries i >= j): `queued` where there is a pair. The device form
 // returns below two rows without touching its matrix; the host form returns without rows and writes the one zero of a single row.
@@ -1198,6 +1255,46 @@ int storm_hip_lag_dosage_prune_complete(storm_hip_ctx_t* ctx, const storm_hip_ma
         if (check_ctx(ctx)) return STORM_HIP_EINVAL;
         return lag_dosage_prune(ctx, "lag_dosage_prune_complete", m, n_samples, max_lag, min_r2, true, h_lo, h_hi, h_order, h_keep,
                                 h_owner, true);
+    });
+}
+
+int storm_hip_lag_dosage_corr_sparse_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint64_t max_lag,
+                                            float min_r2, const uint32_t* h_lo, const uint32_t* h_hi, uint64_t* d_row_start,
+                                            uint32_t* d_col, float* d_val, uint64_t capacity) {
+    return guarded("storm_hip_lag_dosage_corr_sparse_device", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        return lag_dosage_corr_sparse(ctx, "lag_dosage_corr_sparse", m, n_samples, max_lag, min_r2, false, h_lo, h_hi, d_row_start,
+                                      d_col, d_val, capacity, nullptr, false);
+    });
+}
+
+int storm_hip_lag_dosage_corr_sparse(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint64_t max_lag,
+                                     float min_r2, const uint32_t* h_lo, const uint32_t* h_hi, uint64_t* h_row_start, uint32_t* h_col,
+                                     float* h_val, uint64_t capacity, uint64_t* h_n_pairs) {
+    return guarded("storm_hip_lag_dosage_corr_sparse", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        return lag_dosage_corr_sparse(ctx, "lag_dosage_corr_sparse", m, n_samples, max_lag, min_r2, false, h_lo, h_hi, h_row_start,
+                                      h_col, h_val, capacity, h_n_pairs, true);
+    });
+}
+
+int storm_hip_lag_dosage_corr_sparse_complete_device(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples,
+                                                     uint64_t max_lag, float min_r2, const uint32_t* h_lo, const uint32_t* h_hi,
+                                                     uint64_t* d_row_start, uint32_t* d_col, float* d_val, uint64_t capacity) {
+    return guarded("storm_hip_lag_dosage_corr_sparse_complete_device", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        return lag_dosage_corr_sparse(ctx, "lag_dosage_corr_sparse_complete", m, n_samples, max_lag, min_r2, true, h_lo, h_hi,
+                                      d_row_start, d_col, d_val, capacity, nullptr, false);
+    });
+}
+
+int storm_hip_lag_dosage_corr_sparse_complete(storm_hip_ctx_t* ctx, const storm_hip_matrix_t* m, uint64_t n_samples, uint64_t max_lag,
+                                              float min_r2, const uint32_t* h_lo, const uint32_t* h_hi, uint64_t* h_row_start,
+                                              uint32_t* h_col, float* h_val, uint64_t capacity, uint64_t* h_n_pairs) {
+    return guarded("storm_hip_lag_dosage_corr_sparse_complete", [&]() -> int {
+        if (check_ctx(ctx)) return STORM_HIP_EINVAL;
+        return lag_dosage_corr_sparse(ctx, "lag_dosage_corr_sparse_complete", m, n_samples, max_lag, min_r2, true, h_lo, h_hi,
+                                      h_row_start, h_col, h_val, capacity, h_n_pairs, true);
     });
 }
 

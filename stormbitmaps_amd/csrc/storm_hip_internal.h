@@ -403,6 +403,16 @@ size_t lag_band_prune_scratch_words(uint64_t n_rows, uint64_t lag, bool windows,
 int launch_lag_band_prune(storm_hip_ctx_t* ctx, const char* who, const float* d_vals, uint64_t ld, uint64_t n_rows, uint64_t lag,
                           float min_r2, const uint32_t* h_lo, const uint32_t* h_hi, const uint32_t* h_order, uint8_t* d_keep,
                           uint32_t* d_owner, uint32_t* d_scratch);
+// the sparse pair list of a band in the lag layout (storm_hip_lag_sparse.hip): the checks the sparse calls share behind their
+// own NULL / max_lag / ld checks; the 32-bit words of scratch the kernels need; the kernels themselves with that scratch at
+// d_scratch (8-byte aligned), queued (n_rows >= 2, lag = min(max_lag, n_rows - 1); h_lo / h_hi are HOST arrays or NULL;
+// d_col / d_val NULL: the offsets alone)
+int check_lag_band_sparse(const char* who, uint64_t n_rows, const uint32_t* h_lo, const uint32_t* h_hi, float min_r2,
+                          const void* col, const void* val, uint64_t capacity);
+size_t lag_band_sparse_scratch_words(uint64_t n_rows, uint64_t lag, bool windows);
+int launch_lag_band_sparse(storm_hip_ctx_t* ctx, const float* d_vals, uint64_t ld, uint64_t n_rows, uint64_t lag, float min_r2,
+                           const uint32_t* h_lo, const uint32_t* h_hi, uint64_t* d_row_start, uint32_t* d_col, float* d_val,
+                           uint64_t capacity, uint32_t* d_scratch);
 void release_mfma_state(storm_hip_ctx_t* ctx);
 // releases what was put off (storm_hip_ctx_s::deferred_free); `aged`: only what an earlier call left behind
 void drain_deferred(storm_hip_ctx_t* ctx, bool aged);
